@@ -14,10 +14,10 @@ step's proposals uploaded under it.  `--mode stream` (round 4) runs the K timed 
 (psoap_stream_*: include/psoap_gp.h), the ensemble as two half-ensembles in flight -- a half is fetched and its successor
 submitted while the other half keeps the device busy (the back-to-back iterations of psoap/sample_parallel.py:434-438); the
 timed region then starts with nothing in flight and no launch resident and ends when the last result is back and the
-launch has left.  Whichever mode is `value`, the other is measured beside it in the same run (`stream_beside` /
+launch has left.  Whichever mode is `value`, a --full run measures the other beside it (`stream_beside` /
 `launch_per_step`): since round 5 the two tie (N = 6000: 0.99-1.005 x), so the simple one is the default.
 Chunks are independent, so per-GPU work is fixed as N grows ("weak"); at 8 GPUs a step is exactly
-the 32-walker x 8-chunk ensemble of configs[3].  The same run also times configs[3] AS NAMED -- the fixed
+the 32-walker x 8-chunk ensemble of configs[3].  A --full run also times configs[3] AS NAMED -- the fixed
 8-chunk x 32-walker ensemble, chunk k on rank k mod G, 256 evaluations per step at every G -- and reports
 it as `cfg4_strong` (strong scaling; never `value`).
 
@@ -25,9 +25,15 @@ it as `cfg4_strong` (strong scaling; never `value`).
     python bench.py --gpus 8             # spawns 8 ranks itself (torch.distributed.run, RCCL)
     python -m torch.distributed.run --nproc-per-node 8 ... bench.py --gpus 8     # or under a launcher
     python bench.py --gpus 2 --backend gloo    # dry run of the N>1 path on a 1-GPU box
+    python bench.py --full               # + every side measurement and check (below)
+    python bench.py --dump-outputs bench_outputs   # + the last timed step's lnprobs as bench_outputs/*.npy
 
-Rank 0 prints ONE JSON line.  Every reported lnprob is checked against the committed golden values
-of the reference (tests/golden/*.npz) and, at N = 1, against the CPU baseline timed beside it.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the steps and prints the headline
+(`value`, `ms_per_step`); the inputs are seeded, so two builds given the same arguments can be compared
+through --dump-outputs.  With --full the line also carries the other execution mode beside the headline,
+the proposals-resident rate, the per-kernel roofline, the side legs (run_extras), the configs[3] strong leg
+and the CPU baselines, and every reported lnprob is checked against the committed golden values of the
+reference (tests/golden/*.npz) and, at N = 1, against the CPU baseline timed beside it.
 """
 import argparse
 import glob
@@ -197,6 +203,48 @@ def cpu_baseline(chunk, sweep=(8, 16, 32, 64, 128), n_sweep: int = 3, n_best: in
             "lnprob": float(val), "fill_ms": 1e3 * float(np.median(tf))}
 
 
+def dump_outputs(out_dir: str, arrays: dict):
+    """--dump-outputs: every array as out_dir/<name>.npy in float64"""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float64))
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps (>= 1)")
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--walkers", type=int, default=N_WALKERS)
+    ap.add_argument("--groups", type=int, default=2, help="concurrent stream groups per batch (staged mode)")
+    ap.add_argument("--mode", default=None, choices=["stream", "dag", "staged"],
+                    help="stream: the timed steps through ONE resident launch (two half-ensembles in flight); dag / staged: "
+                         "one launch (three per panel) per step.  Default: dag on any number of GPUs -- on several, the RCCL "
+                         "gather of a step then runs between two launches (beside a resident launch a device collective "
+                         "waits for the launch to leave: profiles/r5_gather_beside_stream.txt; --mode stream on several "
+                         "ranks gathers every half-ensemble through the gloo side group on the host instead)")
+    ap.add_argument("--stream-groups", type=int, default=2, help="sub-ensembles in flight in --mode stream")
+    ap.add_argument("--allow-fallback", action="store_true",
+                    help="print `value` even if the library was built from the fallback flag rung (psoap_amd/build.py)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also every side measurement and check: the reference goldens, the other "
+                         "execution mode beside the headline, the proposals-resident rate, the per-kernel roofline, the side "
+                         "legs, the configs[3] strong leg and the CPU baselines (off: the headline alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned -- the summed lnprob of every walker "
+                         "(lnprob.npy) and the (chunk, walker) table (chunk_lnprob.npy) -- as float64 .npy files in DIR")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baselines")
+    ap.add_argument("--no-strong", action="store_true", help="(--full) skip the configs[3] strong-scaling leg (cfg4_strong)")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="(--full) only the timed loop + roofline (profiling runs: keeps every k_chol_dag dispatch alike)")
+    ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
+                    help="process-group backend (nccl = RCCL; gloo only for single-GPU dry runs of the N>1 path)")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
 def launch_ranks(args) -> int:
     """`python bench.py --gpus N` outside a launcher: start the N ranks as children (one process per
     GPU under torch.distributed.run) BEFORE this process touches the GPU, relay rank 0's JSON line."""
@@ -219,28 +267,7 @@ def launch_ranks(args) -> int:
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--walkers", type=int, default=N_WALKERS)
-    ap.add_argument("--groups", type=int, default=2, help="concurrent stream groups per batch (staged mode)")
-    ap.add_argument("--mode", default=None, choices=["stream", "dag", "staged"],
-                    help="stream: the timed steps through ONE resident launch (two half-ensembles in flight); dag / staged: "
-                         "one launch (three per panel) per step.  Default: stream on one GPU; dag on several -- the RCCL "
-                         "gather of a step then runs between two launches (beside a resident launch a device collective "
-                         "waits for the launch to leave: profiles/r5_gather_beside_stream.txt; --mode stream on several "
-                         "ranks gathers every half-ensemble through the gloo side group on the host instead)")
-    ap.add_argument("--stream-groups", type=int, default=2, help="sub-ensembles in flight in --mode stream")
-    ap.add_argument("--allow-fallback", action="store_true",
-                    help="print `value` even if the library was built from the fallback flag rung (psoap_amd/build.py)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-strong", action="store_true", help="skip the configs[3] strong-scaling leg (cfg4_strong)")
-    ap.add_argument("--no-extras", action="store_true",
-                    help="only the timed loop + roofline (profiling runs: keeps every k_chol_dag dispatch alike)")
-    ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
-                    help="process-group backend (nccl = RCCL; gloo only for single-GPU dry runs of the N>1 path)")
-    args = ap.parse_args()
+    args = parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(launch_ranks(args))
@@ -257,7 +284,7 @@ def main():
         # Round 6: one launch per step IS the headline path on every number of GPUs.  The resident launch (round 4) ties
         # with it since the batch kernels' round-5 gains (N = 6000: 0.99-1.005 x, N = 8192: 1.002 x, below N = 5000 slower:
         # profiles/r5_stream_table.jsonl, r6_stream_table.jsonl), needs ~1,500 lines of protocol, and cannot run beside a
-        # device collective; it stays an opt-in (--mode stream) and is measured BESIDE the headline in every default run
+        # device collective; it stays an opt-in (--mode stream) and is measured BESIDE the headline in every --full run
         # (`stream_beside`), so that the choice is re-made from data each round.
         args.mode = "dag"
     if not torch.cuda.is_available():
@@ -425,8 +452,53 @@ def main():
         dt = float(tmax.item())
     evals = world * B * args.steps
     value = evals / dt
+    if args.dump_outputs and rank == 0:      # as the last timed step returned them (its proposal set's walker order)
+        dump_outputs(args.dump_outputs, {"lnprob": total, "chunk_lnprob": table})
     if last_set == 1:                        # back to walker order
         table, total = np.roll(table, -1, axis=1), np.roll(total, -1)
+
+    def headline():
+        """the fields of the line that describe the timed steps (every run)"""
+        return {
+            "metric": "GP lnprob evals/sec (SB2, N=6000)",
+            "value": value, "unit": "evals/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": "f64", "data": "synthetic", "full": args.full,
+            # ranks of the RCCL communicator the gathers of this run actually went through (0: none ran -- one GPU, or gloo)
+            "rccl_ranks": dist.get_world_size() if (world > 1 and args.backend == "nccl" and collectives["n"] > 0) else 0,
+            "collectives_completed": collectives["n"],
+            "host_gathers_completed": collectives.get("host", 0),
+            "backend": args.backend if world > 1 else None,
+            "config": {"workload": f"SB2 chunk 20 epochs x 300 px (N={N}), {B} walkers per step per GPU, "
+                                   f"one chunk per GPU (BASELINE.json configs[2]; configs[3] at 8 GPUs); " +
+                                   (f"the {args.steps} timed steps through ONE resident launch, {args.stream_groups} sub-ensembles "
+                                    f"of {B // args.stream_groups} walkers in flight (proposals pulled from pinned host memory, "
+                                    f"{B} lnprobs per step written to it), every sub-ensemble gathered over the ranks before its successor is submitted"
+                                    if args.mode == "stream" else
+                                    f"timed step = H2D of next proposals || eval, D2H of {B} lnprobs, gather"),
+                       "N": N, "components": c, "walkers": B, "chunks_per_gpu": 1, "mode": args.mode,
+                       "stream_groups": args.stream_groups if args.mode == "stream" else args.groups,
+                       "parallelism": f"chunk-sharded x{world}, RCCL all_gather of walker lnprobs"},
+            "timing_boundary": ("pcie_inclusive (every proposal is pulled from pinned host memory by the resident launch, "
+                                "every result written to it; the timed region starts and ends with nothing in flight and "
+                                "no launch resident)" if args.mode == "stream" else
+                                "pcie_inclusive (per-step H2D of B*c*N doubles double-buffered under the previous eval)"),
+            "library": library,
+            "stream": stream_info,
+            "lnprob_walker0": float(total[0]),
+            "parity_checked": False,
+        }
+
+    if not args.full:
+        # a plain run: the headline alone (the side measurements and checks below: --full)
+        with gpu:
+            h.close()
+        if rank == 0:
+            print(json.dumps(headline()), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # ---- parity gate on what the timed loop produced (reference goldens, no tolerance games)
     parity = {}
@@ -562,33 +634,9 @@ def main():
                     traffic = tj["hbm_bytes_per_launch"]
                 traffic_src = os.path.relpath(path, ROOT)
                 break
-        out = {
-            "metric": "GP lnprob evals/sec (SB2, N=6000)",
-            "value": value, "unit": "evals/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            # ranks of the RCCL communicator the gathers of this run actually went through (0: none ran -- one GPU, or gloo)
-            "rccl_ranks": dist.get_world_size() if (world > 1 and args.backend == "nccl" and collectives["n"] > 0) else 0,
-            "collectives_completed": collectives["n"],
-            "host_gathers_completed": collectives.get("host", 0),
-            "backend": args.backend if world > 1 else None,
-            "config": {"workload": f"SB2 chunk 20 epochs x 300 px (N={N}), {B} walkers per step per GPU, "
-                                   f"one chunk per GPU (BASELINE.json configs[2]; configs[3] at 8 GPUs); " +
-                                   (f"the {args.steps} timed steps through ONE resident launch, {args.stream_groups} sub-ensembles "
-                                    f"of {B // args.stream_groups} walkers in flight (proposals pulled from pinned host memory, "
-                                    f"{B} lnprobs per step written to it), every sub-ensemble gathered over the ranks before its successor is submitted"
-                                    if args.mode == "stream" else
-                                    f"timed step = H2D of next proposals || eval, D2H of {B} lnprobs, gather"),
-                       "N": N, "components": c, "walkers": B, "chunks_per_gpu": 1, "mode": args.mode,
-                       "stream_groups": args.stream_groups if args.mode == "stream" else args.groups,
-                       "parallelism": f"chunk-sharded x{world}, RCCL all_gather of walker lnprobs"},
-            "timing_boundary": ("pcie_inclusive (every proposal is pulled from pinned host memory by the resident launch, "
-                                "every result written to it; the timed region starts and ends with nothing in flight and "
-                                "no launch resident)" if args.mode == "stream" else
-                                "pcie_inclusive (per-step H2D of B*c*N doubles double-buffered under the previous eval)"),
-            "library": library,
+        out = headline()
+        out.update({
             "launch_per_step": per_step,
-            "stream": stream_info,
             "stream_beside": stream_beside,
             "resident_evals_per_s": resident_value,
             "inclusive_over_resident": value / resident_value,
@@ -611,9 +659,8 @@ def main():
             "kernel_ms_profiled_step": {k: round(tm[k]["ms"], 3) for k in
                                         ("fill", "panel_update", "potrf", "trsm", "misc", "dag")},
             "profiled_step_total_ms": tm["total_ms"],
-            "lnprob_walker0": float(total[0]),
             "parity_checked": True, "parity": parity,
-        }
+        })
         out.update(extras)
         if strong is not None:
             out["cfg4_strong"] = strong

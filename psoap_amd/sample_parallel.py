@@ -185,7 +185,7 @@ class Posterior:
 # Round 6: the automatic rule never streams.  The resident launch ties with one launch per step since the batch kernels'
 # round-5 gains (N = 6000: 0.99-1.005 x, N = 8192: 1.002 x, 1-7 % slower below N = 5000: profiles/r5_stream_table.jsonl,
 # r6_*), cannot run beside a device collective, and holds the device while it has results outstanding: it has to be asked
-# for (`--stream on`, `run(stream=True)`).  bench.py measures it beside the headline in every default run (`stream_beside`).
+# for (`--stream on`, `run(stream=True)`).  `bench.py --full` measures it beside the headline (`stream_beside`).
 STREAM_MIN_N = 5000            # (where a forced stream is at least level: below, the launch-per-step path is 1-7 % ahead)
 STREAM_MIN_CHAINS = 16
 

@@ -97,6 +97,22 @@ def test_bench_flop_formulas():
     assert 0.93 < share < 1.0
 
 
+def test_bench_options_and_output_dump(tmp_path):
+    """A plain bench.py run is the headline alone (--full adds the side legs); --steps sets the timed steps; --dump-outputs
+    writes float64 .npy files."""
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 3, False, None)
+    a = bench.parse_args(["--full", "--dump-outputs", str(tmp_path / "out")])
+    assert a.full and a.dump_outputs == str(tmp_path / "out")
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+    bench.dump_outputs(str(tmp_path / "out"), {"lnprob": np.arange(4, dtype=np.float32), "chunk_lnprob": np.ones((1, 4))})
+    got = np.load(tmp_path / "out" / "lnprob.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, np.arange(4))
+    assert np.load(tmp_path / "out" / "chunk_lnprob.npy").shape == (1, 4)
+
+
 def test_synthetic_generator_is_deterministic():
     from psoap_amd import synthetic as syn
     a = syn.make_config_chunk(3, chunk_index=2)

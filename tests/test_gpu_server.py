@@ -39,14 +39,14 @@ def _direct_values(k, n_iter):
         return [h.lnlike(ch.lwls, np.asarray(syn.GP_BASE[2]) * (1.0 + 0.01 * (it % 3))) for it in range(min(n_iter, 3))]
 
 
-def test_workers_through_an_auto_started_server(tmp_path):
+def test_workers_through_an_auto_started_server(sock_dir):
     """PSOAP_GPU_SERVER=auto: the first of 6 forked-style workers starts the server, all six evaluate through it -- group
     launches of up to 6 chunks of different sizes -- without ever loading the HIP runtime themselves; the values are the
     in-process path's to the parity contract; the server leaves once it has had no client for its idle time."""
-    prog = tmp_path / "worker.py"
+    prog = sock_dir / "worker.py"
     prog.write_text(_WORKER % {"root": ROOT})
-    sock = str(tmp_path / "locks" / "gpu_server_0.sock")
-    env = dict(os.environ, PSOAP_GPU_SERVER="auto", PSOAP_LOCK_DIR=str(tmp_path / "locks"), PSOAP_GPU_SERVER_IDLE_S="3")
+    sock = str(sock_dir / "locks" / "gpu_server_0.sock")
+    env = dict(os.environ, PSOAP_GPU_SERVER="auto", PSOAP_LOCK_DIR=str(sock_dir / "locks"), PSOAP_GPU_SERVER_IDLE_S="3")
     K, n_iter = 6, 30
     ps = [subprocess.Popen([sys.executable, str(prog), str(k), str(n_iter)], stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                            text=True, env=env) for k in range(K)]
@@ -72,13 +72,13 @@ def test_workers_through_an_auto_started_server(tmp_path):
     assert "psoap GPU server" in open(sock + ".log").read()
 
 
-def test_reference_goldens_through_the_server(tmp_path):
+def test_reference_goldens_through_the_server(sock_dir):
     """The drop-in functions against the reference's goldens (all five BASELINE shapes) and its recorded behaviour on degenerate
     input, with the evaluation in the server's process."""
-    env = dict(os.environ, PSOAP_GPU_SERVER="auto", PSOAP_LOCK_DIR=str(tmp_path / "locks"), PSOAP_GPU_SERVER_IDLE_S="3")
+    env = dict(os.environ, PSOAP_GPU_SERVER="auto", PSOAP_LOCK_DIR=str(sock_dir / "locks"), PSOAP_GPU_SERVER_IDLE_S="3")
     res = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_gpu_parity.py"), "-q", "-m", "gpu", "-x",
                           "-k", "lnlike_golden or conventions", "-p", "no:cacheprovider"],
                          env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-2000:]
     assert " passed" in res.stdout
-    assert "psoap GPU server" in open(str(tmp_path / "locks" / "gpu_server_0.sock.log")).read()
+    assert "psoap GPU server" in open(str(sock_dir / "locks" / "gpu_server_0.sock.log")).read()

@@ -169,14 +169,14 @@ def test_two_ranks_one_gpu_gloo_same_sums_as_single_process(tmp_path, n_chunks):
 
 
 def test_bench_launches_its_own_ranks_gloo_dry_run():
-    """`python bench.py --gpus 2 --backend gloo` (no launcher, one GPU): the parent spawns both ranks before
+    """`python bench.py --gpus 2 --backend gloo --full` (no launcher, one GPU): the parent spawns both ranks before
     touching the device and relays ONE JSON line; the gathered table is checked against the reference goldens
     inside bench.py (parity_checked)."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     for key in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(key, None)
     res, first = _run_retry_rendezvous_only([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo",
-                                       "--steps", "2", "--warmup", "1", "--walkers", "8"],
+                                       "--full", "--steps", "2", "--warmup", "1", "--walkers", "8"],
                                       capture_output=True, text=True, timeout=1500, env=env)
     assert res.returncode == 0, (first, res.stdout[-1500:], res.stderr[-3000:])
     lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
@@ -264,14 +264,14 @@ def test_gather_beside_the_resident_launch_and_between_launches():
 
 
 def test_bench_eight_ranks_gloo_dry_run():
-    """The 8-rank layout of BASELINE configs[3] as a dry run on ONE GPU: `python bench.py --gpus 8 --backend gloo` -- one
+    """The 8-rank layout of BASELINE configs[3] as a dry run on ONE GPU: `python bench.py --gpus 8 --backend gloo --full` -- one
     chunk per rank, the gathered (chunk, walker) table against the reference goldens, the strong leg with one chunk per
     rank.  (The ranks share the device: their resident launches take turns, so this says nothing about speed.)"""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", PSOAP_STREAM_IDLE_MS="2")
     for key in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(key, None)
     res, first = _run_retry_rendezvous_only([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--backend", "gloo",
-                                             "--steps", "2", "--warmup", "1", "--walkers", "8"],
+                                             "--full", "--steps", "2", "--warmup", "1", "--walkers", "8"],
                                             capture_output=True, text=True, timeout=1500, env=env)
     noise = ("[Gloo]", "amdgpu.ids", "hostname of the client socket")
     err = "\n".join(ln for ln in res.stderr.splitlines() if not any(x in ln for x in noise))

@@ -67,8 +67,8 @@ class _Backend:
         return _Group(handles, self.log)
 
 
-def _start(tmp_path, **kw):
-    path = str(tmp_path / "srv.sock")
+def _start(sock_dir, **kw):
+    path = str(sock_dir / "srv.sock")
     be = _Backend()
     srv = server.GpuServer(path, be, idle_exit_s=0, **kw)
     th = threading.Thread(target=srv.serve, daemon=True)
@@ -76,9 +76,9 @@ def _start(tmp_path, **kw):
     return path, be, srv, th
 
 
-def test_round_trips_errors_and_bookkeeping(tmp_path):
+def test_round_trips_errors_and_bookkeeping(sock_dir):
     import oracle
-    path, be, srv, th = _start(tmp_path)
+    path, be, srv, th = _start(sock_dir)
     ch = syn.make_chunk(2, 3, 40, seed=31)
     gp = syn.GP_BASE[2]
     rc = server.RemoteChunk(ch.fl, ch.sigma, path)
@@ -129,13 +129,13 @@ def _worker(k, path, n_iter, barrier, q):
     q.put((k, vals, st))
 
 
-def test_requests_of_one_iteration_share_a_launch(tmp_path, monkeypatch):
+def test_requests_of_one_iteration_share_a_launch(sock_dir, monkeypatch):
     """K worker processes, each with its own chunk, ask at the same time (the reference's master sends a proposal to all its
     workers, sample_parallel.py:378-381): from the second iteration on the server evaluates them as ONE group launch."""
     import oracle
     # (a generous window and memory: what is tested is the grouping rule, not this machine's scheduling of six processes)
     monkeypatch.setattr(server, "RECENT_S", 30.0)
-    path, be, srv, th = _start(tmp_path, window_s=5.0)
+    path, be, srv, th = _start(sock_dir, window_s=5.0)
     K, n_iter = 5, 4
     ctx = mp.get_context("fork")
     barrier, q = ctx.Barrier(K), ctx.Queue()
@@ -155,13 +155,13 @@ def test_requests_of_one_iteration_share_a_launch(tmp_path, monkeypatch):
     assert st["launches"] < K * n_iter
 
 
-def test_drop_in_call_goes_through_the_server(tmp_path, monkeypatch):
+def test_drop_in_call_goes_through_the_server(sock_dir, monkeypatch):
     """PSOAP_GPU_SERVER=on: covariance.lnlike_f_g in a worker is a round trip to the process that owns the GPU -- the worker
     loads no HIP library (this test has none to load); the shim's conventions (negative hyper-parameter, l == 0, NaN) stay
     on the worker's side."""
     import oracle
     from psoap_amd import covariance
-    path, be, srv, th = _start(tmp_path)
+    path, be, srv, th = _start(sock_dir)
     monkeypatch.setenv("PSOAP_GPU_SERVER", "on")
     monkeypatch.setenv("PSOAP_GPU_SERVER_SOCKET", path)
     ch = syn.make_chunk(2, 3, 40, seed=51)
@@ -179,19 +179,19 @@ def test_drop_in_call_goes_through_the_server(tmp_path, monkeypatch):
         for h in list(covariance._handles.values()):
             h.close()
         covariance._handles.clear()
-    monkeypatch.setenv("PSOAP_GPU_SERVER_SOCKET", str(tmp_path / "nobody.sock"))
+    monkeypatch.setenv("PSOAP_GPU_SERVER_SOCKET", str(sock_dir / "nobody.sock"))
     from psoap_amd._lib import PsoapError
     with pytest.raises(PsoapError, match="no server answers"):
         server.connect_chunk(ch.fl, ch.sigma, device=0)
 
 
-def test_a_worker_that_dies_with_a_request_pending_fails_nobody_else(tmp_path):
+def test_a_worker_that_dies_with_a_request_pending_fails_nobody_else(sock_dir):
     """Three workers are expected (a long window); one sends its request and dies before the launch: its request is
     dropped with it, the other two get their values (round 5's review: the dead worker's entry stayed in `pending` and the
     launch then failed for everybody with the same component count).  A second server on a live socket is refused."""
     import struct
     import oracle
-    path, be, srv, th = _start(tmp_path, window_s=0.5)
+    path, be, srv, th = _start(sock_dir, window_s=0.5)
     chs = [syn.make_chunk(2, 3, 30 + 4 * k, seed=70 + k) for k in range(3)]
     gp = syn.GP_BASE[2]
     rcs = [server.RemoteChunk(c.fl, c.sigma, path) for c in chs]

@@ -93,7 +93,7 @@ tpath = os.path.join(dst, f"{tag}_traffic.json")
 old = json.load(open(tpath)) if os.path.exists(tpath) and json.load(open(tpath)).get("workload", {}).get("mode") == MODE else {
     "round": int(tag[1:]) if tag[1:].isdigit() else tag,
     "source": f"profiles/{tag}_summary.md (rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE, separate passes, "
-              "bench.py --steps 5 --warmup 5 --no-cpu-baseline --no-extras --no-strong)",
+              "bench.py --full --steps 5 --warmup 5 --no-cpu-baseline --no-extras --no-strong)",
     "kernel": ("k_chol_dag<2, false, false, true, 2> (the resident launch of bench.py --mode stream)" if MODE == "stream" else
                "k_chol_dag<2, false, false, false, 2> (one launch per step: bench.py's default --mode dag)"),
     "workload": {"N": 6000, "components": 2, "walkers": 32, "mode": MODE, "evaluations_per_launch": EVALS_PER_DISPATCH},

@@ -11,6 +11,7 @@ set -u -o pipefail
 TAG=${1:-r4}; MINPEAK=${2:-0}
 mkdir -p gpurun_out
 STATUS=gpurun_out/evidence_status_$TAG.txt
+OUT=$(dirname "$STATUS")          # where the outputs go
 : > $STATUS
 FAILED=0
 step() {   # step NAME command...: run, record the exit code
@@ -29,7 +30,7 @@ if python -c "import sys; sys.exit(0 if float('$PEAK') < float('$MINPEAK') else 
 sha256sum psoap_amd/csrc/libpsoap_gp.so > gpurun_out/lib_sha256_$TAG.txt
 step gputests bash -c "python -m pytest tests -m gpu -q > gpurun_out/gputests_$TAG.txt 2>&1"; grep -v amdgpu.ids gpurun_out/gputests_$TAG.txt | tail -1
 step soak bash -c "timeout 500 python tools/soak.py 200 > gpurun_out/soak_$TAG.txt 2>&1"; tail -1 gpurun_out/soak_$TAG.txt
-step bench bash -c "python bench.py --steps 20 --warmup 5 > gpurun_out/bench_$TAG.json 2> gpurun_out/bench_$TAG.err"; cut -c1-160 gpurun_out/bench_$TAG.json
+step bench bash -c "python bench.py --full --steps 20 --warmup 5 > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err"; cut -c1-160 $OUT/bench_$TAG.json
 step profile bash -c "tools/profile_round.sh $TAG > gpurun_out/profile_round_$TAG.log 2>&1"
 step latency bash -c "timeout 900 python tools/latency_quick.py 1,2,3,5 1,2,4,8,16,32 > gpurun_out/latency_$TAG.jsonl 2>/dev/null"
 step stream_table bash -c "timeout 900 python tools/stream_table.py > gpurun_out/stream_table_$TAG.jsonl 2>/dev/null"

@@ -10,8 +10,8 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 # (round 4: --warmup 5 -- the resident launch of the warm-up and that of the timed region then complete 160 matrices each,
 # so the dispatches of k_chol_dag<2, false, false, stream> in one run are alike)
-BENCH="python3 $ROOT/bench.py --steps 5 --warmup 5 --no-cpu-baseline --no-extras --no-strong"
-FULL="python3 $ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline"
+BENCH="python3 $ROOT/bench.py --full --steps 5 --warmup 5 --no-cpu-baseline --no-extras --no-strong"
+FULL="python3 $ROOT/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- $BENCH > $OUT/trace.log 2>&1
 # (round 5) the DRIVER's exact command under the kernel trace: its timed region is ONE dispatch of the resident kernel that
 # completes 20 x 32 = 640 evaluations -- roofline.frac of the bench line can be recomputed from this trace alone

@@ -7,13 +7,13 @@ def one(pattern):
     return max(g, key=os.path.getmtime) if g else None      # (the newest: a directory may hold the files of an earlier call)
 
 print(f"# rocprofv3 summary {tag}\n")
-print("Command profiled: `python3 bench.py --steps 5 --warmup 5 --no-cpu-baseline --no-extras --no-strong` on one MI355X (ROCm 7.2): 32 walkers x SB2")
+print("Command profiled: `python3 bench.py --full --steps 5 --warmup 5 --no-cpu-baseline --no-extras --no-strong` on one MI355X (ROCm 7.2): 32 walkers x SB2")
 print("N=6000 per step.  From round 6 on the headline is again ONE launch of `k_chol_dag<2, false, false, false, 2>` per step (the")
 print("template arguments: C, AUG, LAT, STREAM, WPE): every dispatch of that kernel in this run evaluates 32 matrices -- 5 warm-up +")
 print("5 timed + 1 + 5 proposals-resident + 1 event-profiled.  (Rounds 4-5: `--mode stream`, one resident dispatch of")
-print("`k_chol_dag<2, false, false, true, 2>` per region; still measured beside the headline by the default `bench.py` --")
+print("`k_chol_dag<2, false, false, true, 2>` per region; still measured beside the headline by `bench.py --full` --")
 print("`stream_beside`.)  The k_stream_* / k_mfma_f64_peak / k_tile_engine_bench kernels are the micro-benchmarks behind")
-print("`measured_peak` (libpsoap_bench.so).  The second trace (`trace_full`) is the default `bench.py` with its side legs: the staged")
+print("`measured_peak` (libpsoap_bench.so).  The second trace (`trace_full`) is `bench.py --full` with its side legs: the staged")
 print("step that times k_fill_sym, predict at the retrieve shape (k_chol_dag<3, true, true, false>), the configs[3] strong leg (8")
 print("chunks x 32 walkers in one launch: the one long dispatch of the headline kernel), the lnprob(p) and sampler legs.\n")
 f = one("trace/**/*kernel_stats.csv")
@@ -27,7 +27,7 @@ if f:
     print()
 f = one("trace_full/**/*kernel_stats.csv")
 if f:
-    print("## --kernel-trace --stats, default bench.py with the side legs\n")
+    print("## --kernel-trace --stats, bench.py --full with the side legs\n")
     print("| kernel | calls | total ms | avg us | % |")
     print("|---|---|---|---|---|")
     for r in csv.DictReader(open(f)):
