@@ -89,4 +89,34 @@ __device__ inline void decode_upper(int t, int P, int& ti, int& tj)
     tj = r + (t - (r * P - r * (r - 1) / 2));
 }
 
+// ---- host ----------------------------------------------------------------------------------
+// Owning, grow-only device (or pinned host) buffer: need() allocates only when a call outgrows it (a workspace reused call
+// after call allocates nothing), and the destructor frees it on every return path.
+template <class T, bool HOST = false>
+struct Grow {
+    T* p = nullptr;
+    size_t cap = 0;
+    Grow() = default;
+    Grow(const Grow&) = delete;
+    Grow& operator=(const Grow&) = delete;
+    ~Grow() { release(); }
+    void release()
+    {
+        if (p) (void)(HOST ? hipHostFree(p) : hipFree(p));
+        p = nullptr;
+        cap = 0;
+    }
+    hipError_t need(size_t count)
+    {
+        if (count <= cap && p) return hipSuccess;
+        release();
+        const hipError_t e = HOST ? hipHostMalloc(reinterpret_cast<void**>(&p), sizeof(T) * count)
+                                  : hipMalloc(reinterpret_cast<void**>(&p), sizeof(T) * count);
+        if (e == hipSuccess) cap = count;
+        else p = nullptr;
+        return e;
+    }
+    operator T*() const { return p; }
+};
+
 }  // namespace psoap

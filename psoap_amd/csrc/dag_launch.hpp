@@ -1,0 +1,180 @@
+// dag_launch.hpp -- host side of the persistent kernel's launches (k_chol_dag, dag_kernel.hpp): the plan rule, the device
+// copy of a task list with its control region (DagWorkspace), the launch shape, and the one list of built instantiations
+// that the launcher dispatches over and the LDS-attribute pass walks.
+#pragma once
+#include <stdlib.h>
+#include <string.h>
+#include <vector>
+
+#include "dag_kernel.hpp"
+
+namespace psoap {
+
+// ---- the plan rule ---------------------------------------------------------------------------------
+// PSOAP_DAG_SCHEME=0|1|2 pins the split scheme (experiments); -1: automatic.  Read when a plan is built.
+inline int dag_env_scheme()
+{
+    const char* e = getenv("PSOAP_DAG_SCHEME");
+    return e ? atoi(e) : -1;
+}
+
+// workgroups of a batch (Ps[b] block rows each, Mt appended column tiles) on a device with `compute_units` CUs that admits
+// `max_workers` of them
+inline int dag_batch_workers(const std::vector<int>& Ps, int Mt, int compute_units, int max_workers)
+{
+    int Pmax = 0;
+    for (int P : Ps) Pmax = P > Pmax ? P : Pmax;
+    return dag_pick_workers(dag_batch_flops(Ps, Mt), Pmax, compute_units, max_workers, (int)Ps.size());
+}
+
+// The task list of a likelihood launch (a chunk's batch, a group's): the batch's workers (*workers), the scheme
+// PSOAP_DAG_SCHEME pins, and under PSOAP_FIXED_PLAN=1 the task structure of a stream lane for every matrix, whatever the
+// batch (dag_fixed_plan).  Predict builds its plan from the same pieces with its Mt / Ms (predict_run).
+inline DagPlan dag_lnlike_plan(const std::vector<int>& Ps, int n_cus, int dag_grid, int* workers)
+{
+    *workers = dag_batch_workers(Ps, 0, n_cus, dag_grid);
+    return dag_build_tasks(Ps, *workers, dag_env_scheme(), 0, 0, dag_fixed_plan() ? dag_nominal_share(dag_grid - 1) : 0);
+}
+
+// the LAT kernels (and predict's, the stream's): at most two workgroups per compute unit
+inline int dag_two_per_cu(int workers, int n_cus) { return workers > 2 * n_cus ? 2 * n_cus : workers; }
+
+// ---- one task list on the device ------------------------------------------------------------------
+// The plan's tasks (and, for the ready-only hand-out, order[] and dep[]), the split-K partial tiles, and the control region:
+// DagCtl, MatFlags[n_mats], the arrival counters, and behind them the `taken` bitmap (one bit per task) -- all of it zeroed
+// by one memset of ctl_bytes before every launch.  Grow-only; load() only while no launch reads it.
+struct DagWorkspace {
+    Grow<DagTask> tasks;
+    Grow<unsigned int> order, dep;
+    Grow<double> ws;
+    Grow<unsigned char> ctl;
+    size_t arrive_off = 0, taken_off = 0, ctl_bytes = 0;
+    DagQueues queues{};
+    unsigned int n_main[DAG_QUEUES] = {};
+    bool pool = false;
+    int scheme = 0;
+    unsigned int n_tasks = 0, n_slots = 0;
+
+    hipError_t load(const DagPlan& plan, size_t n_mats)
+    {
+        const size_t nt = plan.tasks.size();
+        arrive_off = sizeof(DagCtl) + sizeof(MatFlags) * n_mats;
+        taken_off = arrive_off + sizeof(int) * ((size_t)plan.n_ctrs + 4);
+        ctl_bytes = taken_off + sizeof(unsigned int) * ((nt + 31) / 32 + 1);
+        pool = !plan.order.empty();
+        hipError_t e = ctl.need(ctl_bytes);
+        if (e == hipSuccess) e = tasks.need(nt);
+        if (e == hipSuccess) e = ws.need((size_t)NB * NB * ((size_t)plan.n_slots + 1));
+        if (e == hipSuccess) e = hipMemcpy(tasks, plan.tasks.data(), sizeof(DagTask) * nt, hipMemcpyHostToDevice);
+        if (pool) {
+            if (e == hipSuccess) e = order.need(plan.order.size());
+            if (e == hipSuccess) e = dep.need(plan.dep.size());
+            if (e == hipSuccess)
+                e = hipMemcpy(order, plan.order.data(), sizeof(unsigned int) * plan.order.size(), hipMemcpyHostToDevice);
+            if (e == hipSuccess)
+                e = hipMemcpy(dep, plan.dep.data(), sizeof(unsigned int) * plan.dep.size(), hipMemcpyHostToDevice);
+            memcpy(n_main, plan.n_main, sizeof n_main);
+        }
+        queues = plan.queues;
+        scheme = plan.scheme;
+        n_tasks = (unsigned int)nt;
+        n_slots = plan.n_slots;
+        return e;
+    }
+    DagCtl* dag_ctl() const { return reinterpret_cast<DagCtl*>(ctl.p); }
+    MatFlags* flags() const { return reinterpret_cast<MatFlags*>(ctl.p + sizeof(DagCtl)); }
+    int* arrive() const { return reinterpret_cast<int*>(ctl.p + arrive_off); }
+    DagPool dag_pool() const
+    {
+        DagPool p{};
+        if (pool) {
+            p.order = order;
+            p.dep = dep;
+            p.taken = reinterpret_cast<unsigned int*>(ctl.p + taken_off);
+            memcpy(p.n_main, n_main, sizeof p.n_main);
+        }
+        return p;
+    }
+};
+
+// Grid and form of a launch of a task list: at most one workgroup per task, `workers` of them, the LAT kernels at most two
+// per compute unit.  Where that leaves at most one workgroup per compute unit (single evaluations, predict:
+// dag_pick_workers) the LAT kernels compiled for one wave per SIMD -- 512 registers per lane, nothing of the chain phases in
+// scratch memory; PSOAP_DAG_WIDE=0 forbids them (read at every launch).
+struct DagShape {
+    int grid;
+    bool lat, wide;
+};
+inline DagShape dag_shape(const DagWorkspace& w, int workers, int n_cus)
+{
+    DagShape s;
+    s.lat = w.scheme >= 1;
+    s.grid = (long long)w.n_tasks < workers ? (int)w.n_tasks : workers;
+    if (s.lat && n_cus > 0) s.grid = dag_two_per_cu(s.grid, n_cus);
+    s.wide = s.lat && n_cus > 0 && s.grid <= n_cus && !(getenv("PSOAP_DAG_WIDE") && getenv("PSOAP_DAG_WIDE")[0] == '0');
+    return s;
+}
+
+// ---- the built instantiations -----------------------------------------------------------------------
+// Every k_chol_dag the library launches comes from this list: dag_launch dispatches over it and dag_set_lds gives each
+// member its LDS attribute, so no form is launched without one.  C in 1..3 x {throughput, LAT, LAT wide}, for the
+// likelihood (AUG = false) and predict (AUG = true); the stream (STREAM = true) has no wide form.
+// Waves per SIMD, the one rule: wide 1; LAT 2; throughput DAG_WPE_TP for the likelihood, 2 for predict and the stream (the
+// stream kernels are compiled for two workgroups per compute unit also in a -DPSOAP_WPE3 build: with three, hipcc's code
+// for them shows the exec-restore defect of psoap_amd/asmcheck.py and the build refuses it).
+enum DagForm { DAG_TP, DAG_LAT, DAG_WIDE };
+
+template <int C_, bool AUG, bool STREAM, int FORM>
+struct DagKernel {
+    static constexpr int C = C_;
+    static constexpr bool LAT = FORM != DAG_TP;
+    static constexpr int WPE = FORM == DAG_WIDE ? 1 : (LAT || AUG || STREAM) ? 2 : DAG_WPE_TP;
+    static const void* fn() { return reinterpret_cast<const void*>(k_chol_dag<C, AUG, LAT, STREAM, WPE>); }
+};
+
+template <int C, bool AUG, bool STREAM, class F>
+inline void dag_visit_form(DagForm form, F& f)
+{
+    if constexpr (!STREAM) {
+        if (form == DAG_WIDE) return f(DagKernel<C, AUG, STREAM, DAG_WIDE>{});
+    }
+    if (form != DAG_TP) f(DagKernel<C, AUG, STREAM, DAG_LAT>{});
+    else f(DagKernel<C, AUG, STREAM, DAG_TP>{});
+}
+// f(DagKernel<C, AUG, STREAM, form>{}) -- the list's member for the runtime choice (C, form)
+template <bool AUG, bool STREAM, class F>
+inline void dag_visit(int C, DagForm form, F&& f)
+{
+    if (C == 1) dag_visit_form<1, AUG, STREAM>(form, f);
+    else if (C == 2) dag_visit_form<2, AUG, STREAM>(form, f);
+    else dag_visit_form<3, AUG, STREAM>(form, f);
+}
+
+// the LDS attribute of every member (per device: hipFuncSetAttribute applies to the current one)
+template <bool AUG, bool STREAM>
+inline hipError_t dag_set_lds()
+{
+    hipError_t e = hipSuccess;
+    for (int C = 1; C <= 3; ++C)
+        for (int form = DAG_TP; form <= (STREAM ? DAG_LAT : DAG_WIDE); ++form)
+            dag_visit<AUG, STREAM>(C, (DagForm)form, [&](auto k) {
+                if (e == hipSuccess)
+                    e = hipFuncSetAttribute(k.fn(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)GEMM_LDS_BYTES);
+            });
+    return e;
+}
+
+// One launch of the persistent kernel: the member for (C, lat, wide) on `grid` workgroups
+template <bool AUG, bool STREAM>
+inline void dag_launch(int C, bool lat, bool wide, int grid, hipStream_t s, const DagMat* mats, const DagTask* tasks,
+                       DagQueues queues, MatFlags* flags, int* arrive, double* wspace, DagCtl* ctl,
+                       unsigned long long* tlog, DagAug aug, StreamArgs st, DagPool pool)
+{
+    dag_visit<AUG, STREAM>(C, wide ? DAG_WIDE : lat ? DAG_LAT : DAG_TP, [&](auto k) {
+        using K = decltype(k);
+        hipLaunchKernelGGL((k_chol_dag<K::C, AUG, K::LAT, STREAM, K::WPE>), dim3(grid), dim3(GEMM_THREADS), GEMM_LDS_BYTES,
+                           s, mats, tasks, queues, flags, arrive, wspace, ctl, tlog, aug, st, pool);
+    });
+}
+
+}  // namespace psoap

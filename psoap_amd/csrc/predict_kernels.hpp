@@ -21,6 +21,7 @@
 
 #include "chol_kernels.hpp"
 #include "dag_kernel.hpp"
+#include "dag_launch.hpp"
 #include "fill_kernels.hpp"
 
 namespace psoap {
@@ -205,51 +206,9 @@ inline hipError_t predict_configure_kernels()
     if (e == hipSuccess)
         e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_syrk_sub_sym),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)GEMM_LDS_BYTES);
-#define PSOAP_SET_LDS(...)                                                                            \
-    if (e == hipSuccess)                                                                              \
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(__VA_ARGS__), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                (int)GEMM_LDS_BYTES)
-    PSOAP_SET_LDS(k_chol_dag<1, true, false>);
-    PSOAP_SET_LDS(k_chol_dag<2, true, false>);
-    PSOAP_SET_LDS(k_chol_dag<3, true, false>);
-    PSOAP_SET_LDS(k_chol_dag<1, true, true>);
-    PSOAP_SET_LDS(k_chol_dag<2, true, true>);
-    PSOAP_SET_LDS(k_chol_dag<3, true, true>);
-    PSOAP_SET_LDS(k_chol_dag<1, true, true, false, 1>);
-    PSOAP_SET_LDS(k_chol_dag<2, true, true, false, 1>);
-    PSOAP_SET_LDS(k_chol_dag<3, true, true, false, 1>);
-#undef PSOAP_SET_LDS
+    if (e == hipSuccess) e = dag_set_lds<true, false>();
     return e;
 }
-
-// Grow-only device (or pinned host) buffer of a predict workspace: repeated calls on one chunk handle
-// allocate nothing (the retrieve loop calls predict once per chunk, psoap_retrieve_ST3.py:148).
-template <class T, bool HOST = false>
-struct Grow {
-    T* p = nullptr;
-    size_t cap = 0;
-    Grow() = default;
-    Grow(const Grow&) = delete;
-    Grow& operator=(const Grow&) = delete;
-    ~Grow() { release(); }
-    void release()
-    {
-        if (p) (void)(HOST ? hipHostFree(p) : hipFree(p));
-        p = nullptr;
-        cap = 0;
-    }
-    hipError_t need(size_t count)
-    {
-        if (count <= cap && p) return hipSuccess;
-        release();
-        const hipError_t e = HOST ? hipHostMalloc(reinterpret_cast<void**>(&p), sizeof(T) * count)
-                                  : hipMalloc(reinterpret_cast<void**>(&p), sizeof(T) * count);
-        if (e == hipSuccess) cap = count;
-        else p = nullptr;
-        return e;
-    }
-    operator T*() const { return p; }
-};
 
 // timings of the last predict call (ms): everything on the device up to mu / Sigma complete, the Sigma
 // download, and the whole call (host wall clock)
@@ -259,17 +218,14 @@ struct PredictTimes {
 };
 
 struct PredictWs {
-    Grow<double> K, W, R, Lwl, Pred, Fl, Sig, Gp, S, Mu, M0, Part, Colx, Ws;
+    Grow<double> K, W, R, Lwl, Pred, Fl, Sig, Gp, S, Mu, M0, Part, Colx;
     Grow<MatAcc> Acc;
-    Grow<unsigned char> Dag;
-    Grow<DagTask> Tasks;
-    Grow<unsigned int> Order, Dep;   // ready-only hand-out (DagPool)
+    DagWorkspace dag;
     Grow<unsigned long long> Tlog;   // per-task stamps of the launch (PSOAP_PREDICT_TLOG=<file>: tools/predict_timeline.py)
     Grow<DagMat> Mat;
     Grow<double, true> hSmall;   // pinned: colx / m0 staging, mu
-    // task list cache
+    // what the task list in `dag` was built for
     int plan_P = -1, plan_Mt = -1, plan_workers = -1, plan_scheme = -2, plan_Ms = -1;
-    DagPlan plan;
     int workers = 0, n_cus = 0;   // persistent workgroups the device admits; compute units
     hipStream_t stream = nullptr;
     hipEvent_t ev[5] = {};
@@ -498,42 +454,27 @@ inline int predict_run(PredictWs& ws, int mode, int c, int N, int M, const doubl
             }
             for (int q = Rq; q < Rq_pad; ++q) row[q] = 0.0;
         }
-        const char* env_scheme = getenv("PSOAP_DAG_SCHEME");
-        const int scheme = env_scheme ? atoi(env_scheme) : -1;
-        const int workers = dag_pick_workers(dag_batch_flops(std::vector<int>(1, P), Mt), P, ws.n_cus > 0 ? ws.n_cus : ws.workers,
-                                             ws.workers);
+        const int scheme = dag_env_scheme();
+        const int workers = dag_batch_workers(std::vector<int>(1, P), Mt, ws.n_cus > 0 ? ws.n_cus : ws.workers, ws.workers);
         if (ws.plan_P != P || ws.plan_Mt != Mt || ws.plan_workers != workers || ws.plan_scheme != scheme || ws.plan_Ms != Ms) {
-            ws.plan = dag_build_tasks(1, P, workers, scheme, Mt, Ms);
+            const DagPlan plan = dag_build_tasks(1, P, workers, scheme, Mt, Ms);
             PR_TRY(hipStreamSynchronize(st));
-            PR_TRY(ws.Tasks.need(ws.plan.tasks.size()));
-            PR_TRY(hipMemcpy(ws.Tasks, ws.plan.tasks.data(), sizeof(DagTask) * ws.plan.tasks.size(),
-                             hipMemcpyHostToDevice));
-            PR_TRY(ws.Ws.need((size_t)NB * NB * ((size_t)ws.plan.n_slots + 1)));
-            if (!ws.plan.order.empty()) {
-                PR_TRY(ws.Order.need(ws.plan.order.size()));
-                PR_TRY(ws.Dep.need(ws.plan.dep.size()));
-                PR_TRY(hipMemcpy(ws.Order, ws.plan.order.data(), sizeof(unsigned int) * ws.plan.order.size(), hipMemcpyHostToDevice));
-                PR_TRY(hipMemcpy(ws.Dep, ws.plan.dep.data(), sizeof(unsigned int) * ws.plan.dep.size(), hipMemcpyHostToDevice));
-            }
+            ws.plan_P = -1;      // (until the workspace holds the new list)
+            PR_TRY(ws.dag.load(plan, 1));
             ws.plan_P = P;
             ws.plan_Mt = Mt;
             ws.plan_workers = workers;
             ws.plan_scheme = scheme;
             ws.plan_Ms = Ms;
         }
-        const DagPlan& plan = ws.plan;
-        const size_t arrive_off = sizeof(DagCtl) + sizeof(MatFlags);
-        const size_t taken_off = arrive_off + sizeof(int) * ((size_t)plan.n_ctrs + 4);      // the ready-only hand-out's bitmap
-        const size_t dag_bytes = taken_off + sizeof(unsigned int) * ((plan.tasks.size() + 31) / 32 + 1);
+        const DagWorkspace& dag = ws.dag;
         PR_TRY(ws.Colx.need((size_t)c * Rq_pad));
-        PR_TRY(ws.Dag.need(dag_bytes));
         PR_TRY(ws.Mat.need(1));
         PR_TRY(hipMemcpyAsync(ws.Colx, h_colx, sizeof(double) * (size_t)c * Rq_pad, hipMemcpyHostToDevice, st));
-        PR_TRY(hipMemsetAsync(ws.Dag, 0, dag_bytes, st));
+        PR_TRY(hipMemsetAsync(dag.ctl, 0, dag.ctl_bytes, st));
         PR_TRY(hipMemsetAsync(dW, 0, sizeof(double) * 2 * NB * NB, st));  // the strictly upper part of W stays zero
         PR_TRY(hipMemsetAsync(dW + WT_THIRD, 0, sizeof(double) * NB * NB, st));   // (scheme 0's third tile)
         hipLaunchKernelGGL(k_init_rhs, dim3((Npad + 255) / 256, 1), dim3(256), 0, st, dR, Npad, N, dFl, offset, dAcc);
-        const int grid = (int)(plan.tasks.size() < (size_t)workers ? plan.tasks.size() : (size_t)workers);
         DagAug aug{P + Mt, Rq, Rq_pad, ws.Colx, nullptr, nullptr, nullptr, 0};
         if (fused_sigma) {
             // row abscissae of the Sigma tiles: the column ones with the opposite sentinel; prior variances for the diagonal
@@ -553,8 +494,6 @@ inline int predict_run(PredictWs& ws, int mode, int c, int N, int M, const doubl
             aug.S = ws.S;
             aug.lds = (size_t)Rq_pad;
         }
-        MatFlags* fl_ = reinterpret_cast<MatFlags*>(ws.Dag.p + sizeof(DagCtl));
-        DagCtl* ctl_ = reinterpret_cast<DagCtl*>(ws.Dag.p);
         DagMat hm{};
         hm.K = dK; hm.R = dR; hm.Wt = dW; hm.lw = dLwl; hm.gp = dGp; hm.sigma = dSig; hm.acc = dAcc;
         hm.N = N; hm.Npad = Npad; hm.P = P; hm.ld = (int)ld;
@@ -562,31 +501,17 @@ inline int predict_run(PredictWs& ws, int mode, int c, int N, int M, const doubl
         PR_TRY(hipMemcpyAsync(ws.Mat, &hm, sizeof(DagMat), hipMemcpyHostToDevice, st));
         PR_TRY(hipStreamSynchronize(st));   // hm is a stack object; the staging copies are tiny
         PR_TRY(hipEventRecord(ws.ev[1], st));
-#define PSOAP_LAUNCH_AUG(CC, LAT, WPE)                                                                            \
-    hipLaunchKernelGGL((k_chol_dag<CC, true, LAT, false, WPE>), dim3(grid), dim3(GEMM_THREADS), GEMM_LDS_BYTES, st,  \
-                       ws.Mat.p, ws.Tasks.p, plan.queues, fl_, reinterpret_cast<int*>(ws.Dag.p + arrive_off),        \
-                       ws.Ws.p, ctl_, tlog_, aug, StreamArgs{}, pool_)
         // debug: per-task stamps of this launch, written with the task list to the file PSOAP_PREDICT_TLOG names
         unsigned long long* tlog_ = nullptr;
         if (getenv("PSOAP_PREDICT_TLOG")) {
-            PR_TRY(ws.Tlog.need(plan.tasks.size() * 8));
-            PR_TRY(hipMemsetAsync(ws.Tlog, 0, sizeof(unsigned long long) * plan.tasks.size() * 8, st));
+            PR_TRY(ws.Tlog.need((size_t)dag.n_tasks * 8));
+            PR_TRY(hipMemsetAsync(ws.Tlog, 0, sizeof(unsigned long long) * dag.n_tasks * 8, st));
             tlog_ = ws.Tlog.p;
         }
-        DagPool pool_{};
-        if (!plan.order.empty()) {
-            pool_.order = ws.Order.p;
-            pool_.dep = ws.Dep.p;
-            pool_.taken = reinterpret_cast<unsigned int*>(ws.Dag.p + taken_off);
-            memcpy(pool_.n_main, plan.n_main, sizeof pool_.n_main);
-        }
-        const bool lat = plan.scheme >= 1;
-        // (at most one workgroup per compute unit: the kernels compiled for one wave per SIMD, as in psoap_gp.hip: eval_dag)
-        const bool wide = lat && ws.n_cus > 0 && grid <= ws.n_cus && !(getenv("PSOAP_DAG_WIDE") && getenv("PSOAP_DAG_WIDE")[0] == '0');
-        if (c == 1) { if (wide) PSOAP_LAUNCH_AUG(1, true, 1); else if (lat) PSOAP_LAUNCH_AUG(1, true, 2); else PSOAP_LAUNCH_AUG(1, false, 2); }
-        else if (c == 2) { if (wide) PSOAP_LAUNCH_AUG(2, true, 1); else if (lat) PSOAP_LAUNCH_AUG(2, true, 2); else PSOAP_LAUNCH_AUG(2, false, 2); }
-        else { if (wide) PSOAP_LAUNCH_AUG(3, true, 1); else if (lat) PSOAP_LAUNCH_AUG(3, true, 2); else PSOAP_LAUNCH_AUG(3, false, 2); }
-#undef PSOAP_LAUNCH_AUG
+        // (the workers are clamped to two per compute unit already: predict_ws_init)
+        const DagShape sh = dag_shape(dag, workers, ws.n_cus);
+        dag_launch<true, false>(c, sh.lat, sh.wide, sh.grid, st, ws.Mat, dag.tasks, dag.queues, dag.flags(), dag.arrive(),
+                                dag.ws, dag.dag_ctl(), tlog_, aug, StreamArgs{}, dag.dag_pool());
         PR_TRY(hipGetLastError());
     } else {
         PR_TRY(hipEventRecord(ws.ev[1], st));
@@ -692,19 +617,22 @@ inline int predict_run(PredictWs& ws, int mode, int c, int N, int M, const doubl
     PR_TRY(hipStreamSynchronize(st));
     if (use_dag) {
         unsigned int dag_err[6] = {0, 0, 0, 0, 0, 0};      // DagCtl::error, pad[0..4]
-        PR_TRY(hipMemcpy(dag_err, ws.Dag.p + offsetof(DagCtl, error), sizeof(dag_err), hipMemcpyDeviceToHost));
+        PR_TRY(hipMemcpy(dag_err, ws.dag.ctl.p + offsetof(DagCtl, error), sizeof(dag_err), hipMemcpyDeviceToHost));
         if (dag_err[0] != 0) {
             err = "predict: dependency wait timed out inside the persistent kernel";
             return 1;
         }
         if (const char* tpath = getenv("PSOAP_PREDICT_TLOG")) {
-            std::vector<unsigned long long> hl(ws.plan.tasks.size() * 8);
+            const size_t nt = ws.dag.n_tasks;
+            std::vector<unsigned long long> hl(nt * 8);
+            std::vector<DagTask> tasks(nt);
             PR_TRY(hipMemcpy(hl.data(), ws.Tlog.p, sizeof(unsigned long long) * hl.size(), hipMemcpyDeviceToHost));
+            PR_TRY(hipMemcpy(tasks.data(), ws.dag.tasks.p, sizeof(DagTask) * nt, hipMemcpyDeviceToHost));
             if (FILE* fh = fopen(tpath, "wb")) {
-                const unsigned long long hdr[4] = {(unsigned long long)ws.plan.tasks.size(), (unsigned long long)P,
-                                                   (unsigned long long)Mt, (unsigned long long)ws.plan.scheme};
+                const unsigned long long hdr[4] = {(unsigned long long)nt, (unsigned long long)P, (unsigned long long)Mt,
+                                                   (unsigned long long)ws.dag.scheme};
                 fwrite(hdr, sizeof hdr, 1, fh);
-                fwrite(ws.plan.tasks.data(), sizeof(DagTask), ws.plan.tasks.size(), fh);
+                fwrite(tasks.data(), sizeof(DagTask), nt, fh);
                 fwrite(hl.data(), sizeof(unsigned long long), hl.size(), fh);
                 fclose(fh);
             }

@@ -28,6 +28,7 @@
 #include "chol_kernels.hpp"
 #include "dag_kernel.hpp"
 #include "solo_kernel.hpp"
+#include "dag_launch.hpp"
 #include "fill_kernels.hpp"
 #include "orbit_kernels.hpp"
 #include "predict_kernels.hpp"
@@ -507,18 +508,6 @@ struct DeviceScope {
 // memory, nor make the caller's close() raise: hipDeviceSynchronize + hipFree disturb nobody's persistent launch)
 #define DEVICE_SCOPE_DESTROY(d) DeviceScope scope_(d)
 
-// Owning device / pinned-host pointer: early returns free whatever was allocated so far.
-template <class T>
-struct DevBuf {
-    T* p = nullptr;
-    DevBuf() = default;
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t count) { return hipMalloc(reinterpret_cast<void**>(&p), sizeof(T) * (count ? count : 1)); }
-    operator T*() const { return p; }
-};
-
 // One uploaded batch of proposals.  A handle keeps two, so the proposals of step k+1 travel over
 // PCIe (copy stream) while the persistent kernel still factors step k: psoap_batch_upload fills the slot
 // that is not being evaluated, psoap_batch_eval promotes the pending slot.
@@ -602,25 +591,12 @@ struct psoap_chunk {
     double* dDates = nullptr;  // n_epochs observation dates (orbit proposals)
     double* dPorb = nullptr;   // max_batch x 13 orbital parameters
     double* hPorb = nullptr;
-    char* dDag = nullptr;    // DagCtl followed by max_batch MatFlags (zeroed before every DAG launch)
     unsigned int* hDagErr = nullptr;
     int mode = 1;            // 1 = persistent DAG kernel, 0 = staged panels
     int dag_grid = 0, n_cus = 0;   // persistent workgroups the device admits; compute units
-    int plan_workers = 0;          // workgroups of the current task list (dag_pick_workers)
-    // task list of the persistent kernel for the current batch size (dag_build_tasks)
-    int plan_B = 0, plan_scheme = 0;
-    unsigned int plan_tasks = 0, plan_ctrs = 0, plan_slots = 0;
-    DagQueues plan_queues{};
-    DagTask* dTasks = nullptr;
-    unsigned int* dOrder = nullptr;   // ready-only hand-out (DagPool): order[] and dep[], tasks_cap entries each
-    unsigned int* dDep = nullptr;
-    unsigned int plan_n_main[DAG_QUEUES] = {};
-    bool plan_pool = false;
-    size_t tasks_cap = 0;
-    double* dWs = nullptr;   // split-K partial tiles, plan_slots x 128 x 128
-    size_t ws_cap = 0;
-    size_t arrive_off = 0;   // byte offset of the arrival counters inside dDag
-    size_t arrive_cap = 0;   // ints
+    // task list of the persistent kernel for the current batch size (dag_lnlike_plan), and its workgroups
+    DagWorkspace dag;
+    int plan_B = 0, plan_workers = 0;
     unsigned long long* dTlog = nullptr;  // optional per-task timestamps (debug)
     long long tlog_tasks = 0;
     // pinned host staging (one set: reused once the previous upload's copies have completed)
@@ -717,27 +693,11 @@ static int configure_kernels(int device)
                                 hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_trsm_strip),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-#define PSOAP_SET_LDS(...) \
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(__VA_ARGS__), hipFuncAttributeMaxDynamicSharedMemorySize, lds))
-    PSOAP_SET_LDS(k_chol_dag<1, false, false, false, DAG_WPE_TP>);
-    PSOAP_SET_LDS(k_chol_dag<2, false, false, false, DAG_WPE_TP>);
-    PSOAP_SET_LDS(k_chol_dag<3, false, false, false, DAG_WPE_TP>);
-    PSOAP_SET_LDS(k_chol_dag<1, false, true>);
-    PSOAP_SET_LDS(k_chol_dag<2, false, true>);
-    PSOAP_SET_LDS(k_chol_dag<3, false, true>);
-    PSOAP_SET_LDS(k_chol_dag<1, false, true, false, 1>);
-    PSOAP_SET_LDS(k_chol_dag<2, false, true, false, 1>);
-    PSOAP_SET_LDS(k_chol_dag<3, false, true, false, 1>);
-    PSOAP_SET_LDS(k_chol_solo<1>);
-    PSOAP_SET_LDS(k_chol_solo<2>);
-    PSOAP_SET_LDS(k_chol_solo<3>);
-    PSOAP_SET_LDS(k_chol_dag<1, false, false, true>);
-    PSOAP_SET_LDS(k_chol_dag<2, false, false, true>);
-    PSOAP_SET_LDS(k_chol_dag<3, false, false, true>);
-    PSOAP_SET_LDS(k_chol_dag<1, false, true, true>);
-    PSOAP_SET_LDS(k_chol_dag<2, false, true, true>);
-    PSOAP_SET_LDS(k_chol_dag<3, false, true, true>);
-#undef PSOAP_SET_LDS
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_chol_solo<1>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_chol_solo<2>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_chol_solo<3>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    HIP_TRY((dag_set_lds<false, false>()));     // the likelihood's k_chol_dag forms
+    HIP_TRY((dag_set_lds<false, true>()));      // the stream's
     HIP_TRY(predict_configure_kernels());
     if (done.size() <= (size_t)device) done.resize((size_t)device + 1, 0);
     done[device] = 1;
@@ -793,11 +753,11 @@ static int chunk_alloc(psoap_chunk* h, const double* fl, const double* sigma)
         HIP_TRY(hipEventCreateWithFlags(&sl.evUpload, hipEventDisableTiming));
         HIP_TRY(hipEventCreateWithFlags(&sl.evEval, hipEventDisableTiming));
     }
-    h->arrive_off = sizeof(DagCtl) + sizeof(MatFlags) * nb;
-    // (arrival counters, and behind them the `taken` bitmap of the ready-only hand-out: one bit per task, at most 9 parts
-    // per tile + the early diagonal parts)
-    h->arrive_cap = nb * (size_t)h->P * (h->P + 1) / 2 + 16 + (9 * nb * (size_t)h->P * (h->P + 1) / 2 + 1024) / 32 + 8;
-    HIP_TRY(hipMalloc(&h->dDag, h->arrive_off + sizeof(int) * h->arrive_cap));
+    // the control region of the persistent kernel, sized for max_batch here (out of memory surfaces at create, not in the
+    // first evaluation): DagCtl, the matrices' flags, the arrival counters, and behind them the `taken` bitmap of the
+    // ready-only hand-out -- one bit per task, at most 9 parts per tile + the early diagonal parts
+    const size_t tiles = nb * (size_t)h->P * (h->P + 1) / 2;
+    HIP_TRY(h->dag.ctl.need(sizeof(DagCtl) + sizeof(MatFlags) * nb + sizeof(int) * (tiles + 16 + (9 * tiles + 1024) / 32 + 8)));
     HIP_TRY(hipHostMalloc(&h->hDagErr, 64));
     h->hDagErr[0] = 0;
     if (int rc = dag_workers(h->device, &h->dag_grid, &h->n_cus)) return rc;
@@ -867,8 +827,7 @@ extern "C" int psoap_chunk_destroy(psoap_chunk* h)
     (void)hipFree(h->dFl); (void)hipFree(h->dSigma); (void)hipFree(h->dGrid); (void)hipFree(h->dEpoch);
     (void)hipFree(h->dK); (void)hipFree(h->dWt); (void)hipFree(h->dR); (void)hipFree(h->dAcc);
     (void)hipFree(h->dVel); (void)hipFree(h->dOut);
-    (void)hipFree(h->dDag); (void)hipHostFree(h->hDagErr); (void)hipFree(h->dTlog);
-    (void)hipFree(h->dTasks); (void)hipFree(h->dWs); (void)hipFree(h->dOrder); (void)hipFree(h->dDep);
+    (void)hipHostFree(h->hDagErr); (void)hipFree(h->dTlog);
     (void)hipFree(h->dDates); (void)hipFree(h->dPorb); (void)hipHostFree(h->hPorb);
     (void)hipHostFree(h->hLwl); (void)hipHostFree(h->hGp); (void)hipHostFree(h->hVel); (void)hipHostFree(h->hOut);
     for (BatchSlot& sl : h->slot) {
@@ -1060,10 +1019,7 @@ extern "C" int psoap_dag_plan_pool(int B, const int* Ps, int workers, int Mt, in
 extern "C" int psoap_dag_pick_workers(int B, const int* Ps, int Mt, int compute_units, int max_workers, int* workers)
 {
     if (B < 1 || !Ps || Mt < 0 || compute_units < 1 || max_workers < 1 || !workers) FAIL("psoap_dag_pick_workers: bad arguments");
-    const std::vector<int> v(Ps, Ps + B);
-    int Pmax = 0;
-    for (int P : v) Pmax = P > Pmax ? P : Pmax;
-    *workers = dag_pick_workers(dag_batch_flops(v, Mt), Pmax, compute_units, max_workers, B);
+    *workers = dag_batch_workers(std::vector<int>(Ps, Ps + B), Mt, compute_units, max_workers);
     return 0;
 }
 
@@ -1073,10 +1029,10 @@ extern "C" int psoap_chunk_dag_tasks(psoap_chunk* h, void* out, long long max_ta
     if (!h || !n_tasks) FAIL("bad arguments");
     DEVICE_SCOPE(h->device);
     if (set_dev(h)) return 1;
-    *n_tasks = h->plan_tasks;
-    if (out && h->dTasks) {
-        const long long n = max_tasks < (long long)h->plan_tasks ? max_tasks : (long long)h->plan_tasks;
-        HIP_TRY(hipMemcpy(out, h->dTasks, sizeof(DagTask) * n, hipMemcpyDeviceToHost));
+    *n_tasks = h->dag.n_tasks;
+    if (out && h->dag.tasks) {
+        const long long n = max_tasks < (long long)h->dag.n_tasks ? max_tasks : (long long)h->dag.n_tasks;
+        HIP_TRY(hipMemcpy(out, h->dag.tasks, sizeof(DagTask) * n, hipMemcpyDeviceToHost));
     }
     return 0;
 }
@@ -1259,10 +1215,10 @@ extern "C" int psoap_orbit_velocities(int device, int model, int B, const double
     DEVICE_SCOPE(device);
     HIP_TRY(hipSetDevice(device));
     const int c = orbit_n_components(model), np = orbit_n_params(model);
-    DevBuf<double> dP, dD, dV;
-    HIP_TRY(dP.alloc((size_t)B * np));
-    HIP_TRY(dD.alloc(n_dates));
-    HIP_TRY(dV.alloc((size_t)B * c * n_dates));
+    Grow<double> dP, dD, dV;
+    HIP_TRY(dP.need((size_t)B * np));
+    HIP_TRY(dD.need(n_dates));
+    HIP_TRY(dV.need((size_t)B * c * n_dates));
     HIP_TRY(hipMemcpy(dP, p_orb, sizeof(double) * (size_t)B * np, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(dD, dates, sizeof(double) * n_dates, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_orbit_velocities, dim3((n_dates + 63) / 64, B), dim3(64), 0, 0, model, B, n_dates, dP.p, dD.p,
@@ -1363,54 +1319,16 @@ static int dag_prepare(psoap_chunk* h)
     if (h->plan_B == sl.B) return 0;
     if (h->P > 255) FAIL("N too large for the persistent kernel's 8-bit block-row indices (N <= 32640)");
     HIP_TRY(hipStreamSynchronize(h->streams[0]));
-    // PSOAP_DAG_SCHEME=0|1 pins the split scheme (experiments); default: automatic
-    const char* env_scheme = getenv("PSOAP_DAG_SCHEME");
-    const std::vector<int> Ps((size_t)sl.B, h->P);
-    const int workers = dag_pick_workers(dag_batch_flops(Ps), h->P, h->n_cus, h->dag_grid, (int)Ps.size());
-    // (PSOAP_FIXED_PLAN=1: the task structure of a stream lane for every matrix, whatever the batch -- dag_fixed_plan)
-    DagPlan plan = dag_build_tasks(Ps, workers, env_scheme ? atoi(env_scheme) : -1, 0, 0,
-                                   dag_fixed_plan() ? dag_nominal_share(h->dag_grid - 1) : 0);
-    if ((size_t)plan.n_ctrs + 4 + (plan.tasks.size() + 31) / 32 + 1 > h->arrive_cap)
-        FAIL("internal: arrival counter capacity exceeded");
-    if (plan.tasks.size() > h->tasks_cap) {
-        if (h->dTasks) HIP_TRY(hipFree(h->dTasks));
-        if (h->dOrder) HIP_TRY(hipFree(h->dOrder));
-        if (h->dDep) HIP_TRY(hipFree(h->dDep));
-        h->dTasks = nullptr;
-        h->dOrder = h->dDep = nullptr;
-        h->tasks_cap = 0;
-        HIP_TRY(hipMalloc(&h->dTasks, sizeof(DagTask) * plan.tasks.size()));
-        HIP_TRY(hipMalloc(&h->dOrder, sizeof(unsigned int) * plan.tasks.size()));
-        HIP_TRY(hipMalloc(&h->dDep, sizeof(unsigned int) * plan.tasks.size()));
-        h->tasks_cap = plan.tasks.size();
-    }
-    h->plan_pool = !plan.order.empty();
-    if (h->plan_pool) {
-        HIP_TRY(hipMemcpy(h->dOrder, plan.order.data(), sizeof(unsigned int) * plan.order.size(), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(h->dDep, plan.dep.data(), sizeof(unsigned int) * plan.dep.size(), hipMemcpyHostToDevice));
-        memcpy(h->plan_n_main, plan.n_main, sizeof h->plan_n_main);
-    }
-    if (plan.n_slots > h->ws_cap) {
-        if (h->dWs) HIP_TRY(hipFree(h->dWs));
-        h->dWs = nullptr;
-        h->ws_cap = 0;
-        HIP_TRY(hipMalloc(&h->dWs, sizeof(double) * NB * NB * (size_t)plan.n_slots));
-        h->ws_cap = plan.n_slots;
-    }
-    HIP_TRY(hipMemcpy(h->dTasks, plan.tasks.data(), sizeof(DagTask) * plan.tasks.size(), hipMemcpyHostToDevice));
+    const DagPlan plan = dag_lnlike_plan(std::vector<int>((size_t)sl.B, h->P), h->n_cus, h->dag_grid, &h->plan_workers);
+    h->plan_B = 0;      // (until the workspace holds the new list)
+    HIP_TRY(h->dag.load(plan, (size_t)h->max_batch));
     h->plan_B = sl.B;
-    h->plan_workers = workers;
-    h->plan_scheme = plan.scheme;
-    h->plan_tasks = (unsigned int)plan.tasks.size();
-    h->plan_ctrs = plan.n_ctrs;
-    h->plan_slots = plan.n_slots;
-    h->plan_queues = plan.queues;
     return 0;
 }
 
 // Many small matrices: one workgroup per matrix (solo_kernel.hpp) instead of the dependency graph.  PSOAP_SOLO=1 / 0 forces /
-// forbids it; otherwise from PSOAP_SOLO_MIN matrices on (default: solo_min_default, from the measured table of round 6)
-// while the largest matrix has at most PSOAP_SOLO_MAX_P block rows.
+// forbids it; otherwise it runs from PSOAP_SOLO_MIN matrices on (unset: never) while the largest matrix has at most
+// PSOAP_SOLO_MAX_P block rows (default 24).
 static bool solo_wanted(int n_mats, int Pmax)
 {
     // (read at every launch: the tests and tools switch it inside one process)
@@ -1421,12 +1339,26 @@ static bool solo_wanted(int n_mats, int Pmax)
     const int max_p = getenv("PSOAP_SOLO_MAX_P") ? atoi(getenv("PSOAP_SOLO_MAX_P")) : 24;
     return n_mats >= min_mats && Pmax <= max_p;
 }
-template <class... Args>
-static void launch_solo(int C, int grid, hipStream_t s, Args... args)
+
+// The factorisation of a likelihood batch (a chunk's, a group's) whose task list is in `w`: the solo kernel where
+// solo_wanted says so, otherwise the persistent kernel in the shape dag_shape picks.  h: the device's workgroup and
+// compute-unit counts.
+static void launch_lnlike(const psoap_chunk* h, const DagWorkspace& w, int workers, int C, const DagMat* mats, int n_mats,
+                          int Pmax, hipStream_t s, unsigned long long* tlog)
 {
-    if (C == 1) hipLaunchKernelGGL(k_chol_solo<1>, dim3(grid), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, args...);
-    else if (C == 2) hipLaunchKernelGGL(k_chol_solo<2>, dim3(grid), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, args...);
-    else hipLaunchKernelGGL(k_chol_solo<3>, dim3(grid), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, args...);
+    if (solo_wanted(n_mats, Pmax)) {
+        const int grid = n_mats < h->dag_grid ? n_mats : h->dag_grid;
+        SoloCtl* ctl = reinterpret_cast<SoloCtl*>(w.ctl.p);
+        const unsigned int* order = nullptr;
+        if (C == 1) hipLaunchKernelGGL(k_chol_solo<1>, dim3(grid), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, mats, order, n_mats, ctl);
+        else if (C == 2) hipLaunchKernelGGL(k_chol_solo<2>, dim3(grid), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, mats, order, n_mats, ctl);
+        else hipLaunchKernelGGL(k_chol_solo<3>, dim3(grid), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, mats, order, n_mats, ctl);
+        return;
+    }
+    const DagShape sh = dag_shape(w, workers, h->n_cus);
+    // (DagAug: read by the AUG kernels only)
+    dag_launch<false, false>(C, sh.lat, sh.wide, sh.grid, s, mats, w.tasks, w.queues, w.flags(), w.arrive(), w.ws, w.dag_ctl(),
+                             tlog, DagAug{}, StreamArgs{}, w.dag_pool());
 }
 
 // One persistent launch for the whole batched factorisation (dag_kernel.hpp).
@@ -1444,8 +1376,7 @@ static int eval_dag(psoap_chunk* h)
                        sl.mu, h->dAcc);
     HIP_TRY(hipGetLastError());
     // (flags, arrival counters and -- behind them -- the taken bitmap of the ready-only hand-out: one memset)
-    const size_t taken_off = h->arrive_off + sizeof(int) * ((size_t)h->plan_ctrs + 4);
-    HIP_TRY(hipMemsetAsync(h->dDag, 0, taken_off + sizeof(unsigned int) * (((size_t)h->plan_tasks + 31) / 32 + 1), s));
+    HIP_TRY(hipMemsetAsync(h->dag.ctl, 0, h->dag.ctl_bytes, s));
     // PSOAP_DEBUG_POISON (tools/soak_batch_perm.py; bit 0: the matrices, bit 1: the mailboxes, bit 2: the partial-tile
     // workspace, bit 3: the block records of the accumulators): NaN patterns in whatever the launch must write before it
     // reads -- a task that reads ahead of its producer then returns NaN instead of the previous launch's (possibly
@@ -1456,42 +1387,14 @@ static int eval_dag(psoap_chunk* h)
     if (poison & 2)
         for (int b = 0; b < B; ++b)
             HIP_TRY(hipMemsetAsync(h->dWt + (size_t)b * WT_STRIDE + (size_t)2 * NB * NB, 0xFF, sizeof(double) * MB_DOUBLES, s));
-    if ((poison & 4) && h->dWs && h->plan_slots) HIP_TRY(hipMemsetAsync(h->dWs, 0xFF, sizeof(double) * NB * NB * (size_t)h->plan_slots, s));
+    if ((poison & 4) && h->dag.n_slots) HIP_TRY(hipMemsetAsync(h->dag.ws, 0xFF, sizeof(double) * NB * NB * (size_t)h->dag.n_slots, s));
     if (poison & 8) HIP_TRY(hipMemsetAsync(h->dAcc, 0xFF, sizeof(MatAcc) * ACC_ROWS * (size_t)B, s));
     if (prof_end(h, s)) return 1;
-    const long long tasks = h->plan_tasks;
-    const int grid_all = (int)(tasks < h->plan_workers ? tasks : h->plan_workers);
     // executed MFMA flops: left-looking updates + strip solves, full 128^3 tiles
     double fl = 0.0;
     for (int q = 0; q < P; ++q) fl += 2.0 * NB * NB * ((double)q * NB * (P - q) + (double)NB * (P - q - 1));
     if (prof_begin(h, s, PSOAP_K_DAG, fl * B, 0.0)) return 1;
-    if (solo_wanted(B, P)) {
-        const int grid = B < h->dag_grid ? B : h->dag_grid;
-        launch_solo(C, grid, s, (const DagMat*)sl.dMats, (const unsigned int*)nullptr, B, reinterpret_cast<SoloCtl*>(h->dDag));
-    } else {
-        MatFlags* fl_ = reinterpret_cast<MatFlags*>(h->dDag + sizeof(DagCtl));
-        DagCtl* ctl_ = reinterpret_cast<DagCtl*>(h->dDag);
-#define PSOAP_LAUNCH_DAG(CC, LAT, WPE)                                                                           \
-    hipLaunchKernelGGL((k_chol_dag<CC, false, LAT, false, WPE>), dim3(grid), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, \
-                       sl.dMats, h->dTasks, h->plan_queues, fl_, reinterpret_cast<int*>(h->dDag + h->arrive_off),   \
-                       h->dWs, ctl_, h->dTlog, DagAug{P, 0, 0, nullptr}, StreamArgs{}, pool_)
-        DagPool pool_{};
-        if (h->plan_pool) {
-            pool_.order = h->dOrder;
-            pool_.dep = h->dDep;
-            pool_.taken = reinterpret_cast<unsigned int*>(h->dDag + taken_off);
-            memcpy(pool_.n_main, h->plan_n_main, sizeof pool_.n_main);
-        }
-        const bool lat = h->plan_scheme >= 1;
-        const int grid = (lat && grid_all > 2 * h->n_cus) ? 2 * h->n_cus : grid_all;     // (the LAT kernels: two per compute unit)
-        // at most one workgroup per compute unit (single evaluations: dag_pick_workers): the kernels compiled for one wave
-        // per SIMD -- 512 registers per lane, nothing of the chain phases in scratch memory
-        const bool wide = lat && grid <= h->n_cus && !(getenv("PSOAP_DAG_WIDE") && getenv("PSOAP_DAG_WIDE")[0] == '0');
-        if (C == 1) { if (wide) PSOAP_LAUNCH_DAG(1, true, 1); else if (lat) PSOAP_LAUNCH_DAG(1, true, 2); else PSOAP_LAUNCH_DAG(1, false, DAG_WPE_TP); }
-        else if (C == 2) { if (wide) PSOAP_LAUNCH_DAG(2, true, 1); else if (lat) PSOAP_LAUNCH_DAG(2, true, 2); else PSOAP_LAUNCH_DAG(2, false, DAG_WPE_TP); }
-        else { if (wide) PSOAP_LAUNCH_DAG(3, true, 1); else if (lat) PSOAP_LAUNCH_DAG(3, true, 2); else PSOAP_LAUNCH_DAG(3, false, DAG_WPE_TP); }
-#undef PSOAP_LAUNCH_DAG
-    }
+    launch_lnlike(h, h->dag, h->plan_workers, C, sl.dMats, B, P, s, h->dTlog);
     HIP_TRY(hipGetLastError());
     if (prof_end(h, s)) return 1;
     if (prof_begin(h, s, PSOAP_K_MISC, 0.0, 0.0)) return 1;
@@ -1502,7 +1405,7 @@ static int eval_dag(psoap_chunk* h)
     HIP_TRY(hipEventRecord(h->evLast, s));
     h->last_recorded = true;
     HIP_TRY(hipMemcpyAsync(h->hOut, h->dOut, sizeof(double) * B, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(h->hDagErr, h->dDag + offsetof(DagCtl, error), 6 * sizeof(unsigned int),
+    HIP_TRY(hipMemcpyAsync(h->hDagErr, h->dag.ctl.p + offsetof(DagCtl, error), 6 * sizeof(unsigned int),
                            hipMemcpyDeviceToHost, s));
     h->last_path = 1;
     g_share.dag_launches += 1;
@@ -1649,26 +1552,11 @@ struct psoap_group {
     std::vector<psoap_chunk*> hs;
     hipStream_t stream = nullptr;
     hipEvent_t evDone = nullptr;
-    unsigned char* dDag = nullptr;
-    size_t dag_cap = 0, dag_bytes = 0, arrive_off = 0;
-    DagMat* dMats = nullptr;
-    size_t mats_cap = 0;
-    DagTask* dTasks = nullptr;
-    unsigned int* dOrder = nullptr;   // DagPool: order[], dep[] (tasks_cap entries each)
-    unsigned int* dDep = nullptr;
-    unsigned int n_main[DAG_QUEUES] = {};
-    bool pool = false;
-    size_t taken_off = 0;
-    size_t tasks_cap = 0;
-    double* dWs = nullptr;
-    size_t ws_cap = 0;
+    DagWorkspace dag;
+    Grow<DagMat> dMats;
     std::vector<int> key;      // B of every handle, then C: the plan is rebuilt when it changes
     std::vector<int> acts;     // proposal slot of every handle the records in dMats point into
     long long plan_builds = 0, record_refreshes = 0;   // psoap_group_stats
-    DagQueues queues{};
-    long long n_tasks = 0;
-    int total_B = 0;
-    int scheme = 0;
     int workers = 0;
 };
 
@@ -1715,8 +1603,6 @@ extern "C" int psoap_group_destroy(psoap_group* g)
         std::lock_guard<std::mutex> lk(g_groups_mu);
         g_live_groups.erase(g);
     }
-    (void)hipFree(g->dDag); (void)hipFree(g->dMats); (void)hipFree(g->dTasks); (void)hipFree(g->dWs);
-    (void)hipFree(g->dOrder); (void)hipFree(g->dDep);
     if (g->stream) (void)hipStreamDestroy(g->stream);
     if (g->evDone) (void)hipEventDestroy(g->evDone);
     delete g;
@@ -1780,56 +1666,10 @@ static int group_eval_locked(psoap_group* g, bool promote)
         std::vector<int> Ps;
         for (psoap_chunk* h : g->hs)
             for (int b = 0; b < h->slot[h->act].B; ++b) Ps.push_back(h->P);
-        const char* env_scheme = getenv("PSOAP_DAG_SCHEME");
-        int Pmax = 0;
-        for (int P : Ps) Pmax = P > Pmax ? P : Pmax;
-        g->workers = dag_pick_workers(dag_batch_flops(Ps), Pmax, g->hs[0]->n_cus, g->hs[0]->dag_grid, (int)Ps.size());
-        DagPlan plan = dag_build_tasks(Ps, g->workers, env_scheme ? atoi(env_scheme) : -1, 0, 0,
-                                       dag_fixed_plan() ? dag_nominal_share(g->hs[0]->dag_grid - 1) : 0);
-        if ((size_t)total > g->mats_cap) {
-            if (g->dMats) HIP_TRY(hipFree(g->dMats));
-            g->dMats = nullptr;
-            HIP_TRY(hipMalloc(&g->dMats, sizeof(DagMat) * (size_t)total));
-            g->mats_cap = (size_t)total;
-        }
-        if (plan.tasks.size() > g->tasks_cap) {
-            if (g->dTasks) HIP_TRY(hipFree(g->dTasks));
-            if (g->dOrder) HIP_TRY(hipFree(g->dOrder));
-            if (g->dDep) HIP_TRY(hipFree(g->dDep));
-            g->dTasks = nullptr;
-            g->dOrder = g->dDep = nullptr;
-            g->tasks_cap = 0;
-            HIP_TRY(hipMalloc(&g->dTasks, sizeof(DagTask) * plan.tasks.size()));
-            HIP_TRY(hipMalloc(&g->dOrder, sizeof(unsigned int) * plan.tasks.size()));
-            HIP_TRY(hipMalloc(&g->dDep, sizeof(unsigned int) * plan.tasks.size()));
-            g->tasks_cap = plan.tasks.size();
-        }
-        g->pool = !plan.order.empty();
-        if (g->pool) {
-            HIP_TRY(hipMemcpy(g->dOrder, plan.order.data(), sizeof(unsigned int) * plan.order.size(), hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(g->dDep, plan.dep.data(), sizeof(unsigned int) * plan.dep.size(), hipMemcpyHostToDevice));
-            memcpy(g->n_main, plan.n_main, sizeof g->n_main);
-        }
-        if ((size_t)plan.n_slots + 1 > g->ws_cap) {
-            if (g->dWs) HIP_TRY(hipFree(g->dWs));
-            g->dWs = nullptr;
-            HIP_TRY(hipMalloc(&g->dWs, sizeof(double) * NB * NB * ((size_t)plan.n_slots + 1)));
-            g->ws_cap = (size_t)plan.n_slots + 1;
-        }
-        g->arrive_off = sizeof(DagCtl) + sizeof(MatFlags) * (size_t)total;
-        g->taken_off = g->arrive_off + sizeof(int) * ((size_t)plan.n_ctrs + 4);
-        g->dag_bytes = g->taken_off + sizeof(unsigned int) * ((plan.tasks.size() + 31) / 32 + 1);
-        if (g->dag_bytes > g->dag_cap) {
-            if (g->dDag) HIP_TRY(hipFree(g->dDag));
-            g->dDag = nullptr;
-            HIP_TRY(hipMalloc(&g->dDag, g->dag_bytes));
-            g->dag_cap = g->dag_bytes;
-        }
-        HIP_TRY(hipMemcpy(g->dTasks, plan.tasks.data(), sizeof(DagTask) * plan.tasks.size(), hipMemcpyHostToDevice));
-        g->queues = plan.queues;
-        g->scheme = plan.scheme;
-        g->n_tasks = (long long)plan.tasks.size();
-        g->total_B = total;
+        const DagPlan plan = dag_lnlike_plan(Ps, g->hs[0]->n_cus, g->hs[0]->dag_grid, &g->workers);
+        g->key.clear();      // (until the workspace holds the new list)
+        HIP_TRY(g->dMats.need((size_t)total));
+        HIP_TRY(g->dag.load(plan, (size_t)total));
         g->key = key;
         g->acts.clear();
         ++g->plan_builds;
@@ -1857,35 +1697,10 @@ static int group_eval_locked(psoap_group* g, bool promote)
         h->recs.clear();
     }
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemsetAsync(g->dDag, 0, g->dag_bytes, s));
+    HIP_TRY(hipMemsetAsync(g->dag.ctl, 0, g->dag.ctl_bytes, s));
     int Pmax_g = 0;
     for (psoap_chunk* h : g->hs) Pmax_g = h->P > Pmax_g ? h->P : Pmax_g;
-    if (solo_wanted(total, Pmax_g)) {
-        const int grid = total < g->hs[0]->dag_grid ? total : g->hs[0]->dag_grid;
-        launch_solo(C, grid, s, (const DagMat*)g->dMats, (const unsigned int*)nullptr, total, reinterpret_cast<SoloCtl*>(g->dDag));
-    } else {
-        const int workers = (g->scheme >= 1 && g->workers > 2 * g->hs[0]->n_cus) ? 2 * g->hs[0]->n_cus : g->workers;
-        const int grid = (int)(g->n_tasks < workers ? g->n_tasks : workers);
-        MatFlags* fl_ = reinterpret_cast<MatFlags*>(g->dDag + sizeof(DagCtl));
-        DagCtl* ctl_ = reinterpret_cast<DagCtl*>(g->dDag);
-#define PSOAP_LAUNCH_GROUP(CC, LAT, WPE)                                                                        \
-    hipLaunchKernelGGL((k_chol_dag<CC, false, LAT, false, WPE>), dim3(grid), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, \
-                       g->dMats, g->dTasks, g->queues, fl_, reinterpret_cast<int*>(g->dDag + g->arrive_off),        \
-                       g->dWs, ctl_, (unsigned long long*)nullptr, DagAug{0, 0, 0, nullptr}, StreamArgs{}, pool_)
-        DagPool pool_{};
-        if (g->pool) {
-            pool_.order = g->dOrder;
-            pool_.dep = g->dDep;
-            pool_.taken = reinterpret_cast<unsigned int*>(g->dDag + g->taken_off);
-            memcpy(pool_.n_main, g->n_main, sizeof pool_.n_main);
-        }
-        const bool lat = g->scheme >= 1;
-        const bool wide = lat && grid <= g->hs[0]->n_cus && !(getenv("PSOAP_DAG_WIDE") && getenv("PSOAP_DAG_WIDE")[0] == '0');
-        if (C == 1) { if (wide) PSOAP_LAUNCH_GROUP(1, true, 1); else if (lat) PSOAP_LAUNCH_GROUP(1, true, 2); else PSOAP_LAUNCH_GROUP(1, false, DAG_WPE_TP); }
-        else if (C == 2) { if (wide) PSOAP_LAUNCH_GROUP(2, true, 1); else if (lat) PSOAP_LAUNCH_GROUP(2, true, 2); else PSOAP_LAUNCH_GROUP(2, false, DAG_WPE_TP); }
-        else { if (wide) PSOAP_LAUNCH_GROUP(3, true, 1); else if (lat) PSOAP_LAUNCH_GROUP(3, true, 2); else PSOAP_LAUNCH_GROUP(3, false, DAG_WPE_TP); }
-#undef PSOAP_LAUNCH_GROUP
-    }
+    launch_lnlike(g->hs[0], g->dag, g->workers, C, g->dMats, total, Pmax_g, s, nullptr);
     HIP_TRY(hipGetLastError());
     for (psoap_chunk* h : g->hs) {
         const BatchSlot& sl = h->slot[h->act];
@@ -1894,7 +1709,7 @@ static int group_eval_locked(psoap_group* g, bool promote)
         HIP_TRY(hipEventRecord(h->evLast, s));
         h->last_recorded = true;
         HIP_TRY(hipMemcpyAsync(h->hOut, h->dOut, sizeof(double) * sl.B, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(h->hDagErr, g->dDag + offsetof(DagCtl, error), 6 * sizeof(unsigned int),
+        HIP_TRY(hipMemcpyAsync(h->hDagErr, g->dag.ctl.p + offsetof(DagCtl, error), 6 * sizeof(unsigned int),
                                hipMemcpyDeviceToHost, s));
         h->last_path = 1;
         h->last_group = g;
@@ -1953,20 +1768,11 @@ static int stream_launch(psoap_chunk* h)
         a.gate = (st.scheme == 0 && DAG_TILE_DEPS && us > 0.0) ? (unsigned int)(us * 100.0) : 0u;
     }
     a.tlog_cap = st.tlog_cap;
-    MatFlags* fl_ = reinterpret_cast<MatFlags*>(st.dDag + sizeof(DagCtl));
-    DagCtl* ctl_ = reinterpret_cast<DagCtl*>(st.dDag);
-    // (the stream kernels are compiled for two workgroups per compute unit, also in a -DPSOAP_WPE3 build: with three, hipcc's
-    // code for them shows the exec-restore defect of psoap_amd/asmcheck.py and the build refuses it)
-    const int grid = h->dag_grid > 2 * h->n_cus ? 2 * h->n_cus : h->dag_grid;
-#define PSOAP_LAUNCH_STREAM(CC, LAT, WPE)                                                                         \
-    hipLaunchKernelGGL((k_chol_dag<CC, false, LAT, true, WPE>), dim3(grid), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, \
-                       st.dMats, st.dTasks, st.queues, fl_, reinterpret_cast<int*>(st.dDag + st.arrive_off), st.dWs, \
-                       ctl_, st.dTlog, DagAug{h->P, 0, 0, nullptr}, a, DagPool{})
-    const bool lat = st.scheme >= 1;
-    if (st.C == 1) { if (lat) PSOAP_LAUNCH_STREAM(1, true, 2); else PSOAP_LAUNCH_STREAM(1, false, 2); }
-    else if (st.C == 2) { if (lat) PSOAP_LAUNCH_STREAM(2, true, 2); else PSOAP_LAUNCH_STREAM(2, false, 2); }
-    else { if (lat) PSOAP_LAUNCH_STREAM(3, true, 2); else PSOAP_LAUNCH_STREAM(3, false, 2); }
-#undef PSOAP_LAUNCH_STREAM
+    // (every workgroup the device admits, at most two per compute unit: no task bound, never wide)
+    dag_launch<false, true>(st.C, st.scheme >= 1, false, dag_two_per_cu(h->dag_grid, h->n_cus), s, st.dMats, st.dTasks,
+                            st.queues, reinterpret_cast<MatFlags*>(st.dDag + sizeof(DagCtl)),
+                            reinterpret_cast<int*>(st.dDag + st.arrive_off), st.dWs, reinterpret_cast<DagCtl*>(st.dDag),
+                            st.dTlog, DagAug{h->P, 0, 0, nullptr}, a, DagPool{});
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(st.evExit, s));
     st.launched = true;
@@ -2558,8 +2364,8 @@ extern "C" int psoap_batch_fetch(psoap_chunk* h, double* out)
     if (h->last_path == 1 && h->hDagErr[0] != 0) {
         char buf[512];
         int dbg[32] = {0};
-        (void)hipMemcpy(dbg, h->dDag, 16 * sizeof(int), hipMemcpyDeviceToHost);
-        (void)hipMemcpy(dbg + 16, h->dDag + sizeof(DagCtl), 16 * sizeof(int), hipMemcpyDeviceToHost);
+        (void)hipMemcpy(dbg, h->dag.ctl, 16 * sizeof(int), hipMemcpyDeviceToHost);
+        (void)hipMemcpy(dbg + 16, h->dag.ctl.p + sizeof(DagCtl), 16 * sizeof(int), hipMemcpyDeviceToHost);
         snprintf(buf, sizeof buf,
                  "psoap_batch_fetch: a dependency wait in the DAG kernel timed out (results invalid); "
                  "first failing wait: code=%u target=%u seen=%u; err=%d; matrix0 rows_done=%d "
@@ -2622,14 +2428,14 @@ extern "C" int psoap_fill_sym(int device, int c, int N, const double* lwl, const
     DEVICE_SCOPE(device);
     HIP_TRY(hipSetDevice(device));
     const int Npad = round_up(N, NB), P = Npad / NB;
-    DevBuf<double> dK, dLwl, dGp, dSig;
-    HIP_TRY(dK.alloc((size_t)Npad * Npad));
-    HIP_TRY(dLwl.alloc((size_t)c * N));
-    HIP_TRY(dGp.alloc(6));
+    Grow<double> dK, dLwl, dGp, dSig;
+    HIP_TRY(dK.need((size_t)Npad * Npad));
+    HIP_TRY(dLwl.need((size_t)c * N));
+    HIP_TRY(dGp.need(6));
     HIP_TRY(hipMemcpy(dLwl, lwl, sizeof(double) * (size_t)c * N, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(dGp, gp, sizeof(double) * 2 * c, hipMemcpyHostToDevice));
     if (sigma) {
-        HIP_TRY(dSig.alloc(N));
+        HIP_TRY(dSig.need(N));
         HIP_TRY(hipMemcpy(dSig, sigma, sizeof(double) * N, hipMemcpyHostToDevice));
     }
     dim3 grid(P * P, 1);
@@ -2652,10 +2458,10 @@ extern "C" int psoap_fill_cross(int device, int M, int N, const double* lwl_row,
     DEVICE_SCOPE(device);
     HIP_TRY(hipSetDevice(device));
     const int ld = round_up(N, 2);
-    DevBuf<double> dO, dRow, dCol;
-    HIP_TRY(dO.alloc((size_t)M * ld));
-    HIP_TRY(dRow.alloc(M));
-    HIP_TRY(dCol.alloc(N));
+    Grow<double> dO, dRow, dCol;
+    HIP_TRY(dO.need((size_t)M * ld));
+    HIP_TRY(dRow.need(M));
+    HIP_TRY(dCol.need(N));
     HIP_TRY(hipMemcpy(dRow, lwl_row, sizeof(double) * M, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(dCol, lwl_col, sizeof(double) * N, hipMemcpyHostToDevice));
     dim3 grid((N + NB - 1) / NB, (M + NB - 1) / NB);
@@ -2701,6 +2507,14 @@ static int predict_settled(PredictWs& ws, int device, int mode, int c, int N, in
     }
 }
 
+// the workgroups of a predict workspace: what the device admits, at most two per compute unit (the AUG kernels)
+static int predict_ws_init(PredictWs& ws, int device)
+{
+    if (int rc = dag_workers(device, &ws.workers, &ws.n_cus)) return rc;
+    ws.workers = dag_two_per_cu(ws.workers, ws.n_cus);
+    return 0;
+}
+
 // handle-less form: a workspace for this one call (freed on every path by its destructor)
 extern "C" int psoap_predict(int device, int mode, int c, int N, int M, const double* lwl, const double* fl,
                              const double* sigma, const double* lwl_pred, const double* mu_c, const double* gp,
@@ -2711,8 +2525,7 @@ extern "C" int psoap_predict(int device, int mode, int c, int N, int M, const do
     DEVICE_SCOPE(device);
     if (int rc = enter_device(device)) return rc;
     PredictWs ws;
-    if (int rc = dag_workers(device, &ws.workers, &ws.n_cus)) return rc;
-    if (ws.workers > 2 * ws.n_cus) ws.workers = 2 * ws.n_cus;
+    if (int rc = predict_ws_init(ws, device)) return rc;
     int status = 0;
     const int rc = predict_settled(ws, device, mode, c, N, M, lwl, fl, sigma, nullptr, nullptr, lwl_pred, mu_c, gp, mu_out,
                                    Sigma_out, &status, nullptr);
@@ -2746,11 +2559,10 @@ extern "C" int psoap_predictor_create(psoap_predictor** out, int device)
     if (int rc = enter_device(device)) return rc;
     psoap_predictor* p = new psoap_predictor();
     p->device = device;
-    if (int rc = dag_workers(device, &p->ws.workers, &p->ws.n_cus)) {
+    if (int rc = predict_ws_init(p->ws, device)) {
         delete p;
         return rc;
     }
-    if (p->ws.workers > 2 * p->ws.n_cus) p->ws.workers = 2 * p->ws.n_cus;
     *out = p;
     return 0;
 }
@@ -2835,7 +2647,7 @@ static int chunk_predict(psoap_chunk* h, int mode, int c, int M, const double* l
     if (int rc = enter_device(h->device)) return rc;
     if (!h->pws) {
         h->pws = new PredictWs();
-        h->pws->workers = h->dag_grid < 2 * h->n_cus ? h->dag_grid : 2 * h->n_cus;       // (the AUG kernels: two per compute unit)
+        h->pws->workers = dag_two_per_cu(h->dag_grid, h->n_cus);       // (as predict_ws_init)
         h->pws->n_cus = h->n_cus;
     }
     int status = 0;
