@@ -82,6 +82,14 @@ enum {
 };
 int psoap_share_stats(int device, long long *out, int n);
 
+/* Launches of the persistent kernel per built form so far (process-wide, all
+ * devices): out[k], k < min(n, forms); returns the number of forms (24).
+ *   likelihood and predict: k = 9*AUG + 3*(C-1) + {0 throughput, 1 LAT, 2 LAT wide}
+ *                           (AUG: 0 likelihood, 1 predict)
+ *   resident stream:        k = 18 + 2*(C-1) + {0 throughput, 1 LAT}
+ * out may be NULL. */
+int psoap_dag_form_launches(long long *out, int n);
+
 /* ---- per-chunk handle ---------------------------------------------------------
  * Replaces the per-chunk state of Worker.initialize (psoap/sample_parallel.py:
  * 126-166): fl, sigma and the N x N scratch matrix V11 (:163) live on the device

@@ -254,3 +254,128 @@ def calibration_blocks(lwls_cal, sigma_cal, lwls_fixed, sigma_fixed, gp):
     A[np.diag_indices_from(A)] += np.asarray(sigma_cal) ** 2
     B[np.diag_indices_from(B)] += np.asarray(sigma_fixed) ** 2
     return A, B, C
+
+
+def predict_f(lwl_known, fl_known, sigma_known, lwl_predict, amp_f, l_f, mu_GP=1.0):
+    """Single-component conditional, psoap/covariance.py:25-54 with ``N = len(lwl_predict)``: mean offset
+    ``fl - mu_GP`` and prior mean ``mu_GP`` (:52), no nugget on the prior ``V22`` (:45)."""
+    lwl_known, lwl_predict = _vec(lwl_known), _vec(lwl_predict)
+    N, M = lwl_known.shape[0], lwl_predict.shape[0]
+    V11 = np.empty((N, N))
+    fill_V11_f(V11, lwl_known, amp_f, l_f)
+    V11 = V11 + _vec(sigma_known) ** 2 * np.eye(N)
+    V12 = np.empty((N, M))
+    fill_V12_f(V12, lwl_known, lwl_predict, amp_f, l_f)
+    V22 = np.empty((M, M))
+    fill_V11_f(V22, lwl_predict, amp_f, l_f)
+    factor = cho_factor(V11)
+    mu = mu_GP + np.dot(V12.T, cho_solve(factor, _vec(fl_known) - mu_GP))
+    Sigma = V22 - np.dot(V12.T, cho_solve(factor, V12))
+    return mu, Sigma
+
+
+# --------------------------------------------------------------------------- extended precision
+# The same operations in np.longdouble (x87 80-bit on x86-64: 64-bit significand), written from the math -- fills,
+# a blocked Cholesky, the solves and the log-determinant -- as the yardstick the LAPACK oracle itself is measured
+# against.  O(N^3) in numpy's generic long-double loops: a few seconds at N ~ 1300, meant for N <= ~1300.
+_LD = np.longdouble
+_C_KMS = _LD("2.99792458e5")
+_EXT_NB = 128
+
+
+def _fill_ext(x_row, x_col, amp, l):
+    """amp^2 exp(-0.5 c^2 (x_col[j] - x_row[i])^2 / l^2) in long double, (len(x_row), len(x_col))."""
+    r = np.asarray(x_col, dtype=_LD)[None, :] - np.asarray(x_row, dtype=_LD)[:, None]
+    return _LD(amp) ** 2 * np.exp(_LD(-0.5) * _C_KMS * _C_KMS / (_LD(l) * _LD(l)) * r * r)
+
+
+def _sym_ext(lwls, gp):
+    """sum over the components of the symmetric fill; the diagonal is sum amp^2 (the reference's diagonal rule)."""
+    c = lwls.shape[0]
+    K = sum(_fill_ext(lwls[k], lwls[k], gp[2 * k], gp[2 * k + 1]) for k in range(c))
+    K[np.diag_indices_from(K)] = sum(_LD(gp[2 * k]) ** 2 for k in range(c))
+    return K
+
+
+def _chol_ext(K):
+    """Lower Cholesky factor of K (long double), right-looking in 128-wide column blocks."""
+    A = np.array(K, dtype=_LD)
+    n = A.shape[0]
+    for k0 in range(0, n, _EXT_NB):
+        k1 = min(k0 + _EXT_NB, n)
+        for j in range(k0, k1):             # the diagonal block and the panel below it, column by column
+            if j > k0:
+                A[j:, j] -= A[j:, k0:j] @ A[j, k0:j]
+            d = A[j, j]
+            if not d > 0:
+                raise np.linalg.LinAlgError("not positive definite")
+            A[j, j] = np.sqrt(d)
+            A[j + 1:, j] /= A[j, j]
+        if k1 < n:                          # the trailing update
+            P = A[k1:, k0:k1]
+            A[k1:, k1:] -= P @ P.T
+    return np.tril(A)
+
+
+def _fsolve_ext(L, B):
+    """L^-1 B by forward substitution (long double); B (n,) or (n, r)."""
+    X = np.array(B, dtype=_LD)
+    for j in range(L.shape[0]):
+        if j:
+            X[j] -= L[j, :j] @ X[:j]
+        X[j] /= L[j, j]
+    return X
+
+
+def lnlike_ext(lwls, fl, sigma, gp, mu_GP=1.0, terms=False):
+    """lnlike (psoap/covariance.py:299-376) with every step in long double; -> np.longdouble, or with ``terms`` the
+    tuple (lnp, r^T K^-1 r, log det K) -- lnp is -1/2 of their sum, and can be far smaller than either."""
+    lwls = np.atleast_2d(np.asarray(lwls, dtype=np.float64))
+    K = _sym_ext(lwls, gp)
+    K[np.diag_indices_from(K)] += np.asarray(sigma, dtype=_LD) ** 2
+    L = _chol_ext(K)
+    z = _fsolve_ext(L, np.asarray(fl, dtype=_LD) - _LD(mu_GP))
+    quad, logdet = z @ z, _LD(2) * np.sum(np.log(np.diag(L)))
+    lnp = _LD(-0.5) * (quad + logdet)
+    return (lnp, quad, logdet) if terms else lnp
+
+
+def predict_ext(mode, lwls, fl, sigma, lwls_predict, mu_c, gp, want_sigma=True):
+    """The conditional of psoap_amd.covariance._predict's ``mode`` in long double; -> (mu, Sigma) as np.longdouble.
+
+    mode 0: the c components jointly (predict_components: block-diagonal prior, stacked cross fills, ``fl - 1.0``);
+    mode 1: their sum (predict_sum: c = 2 with the 1e-8 nugget and ``fl - 1.0``; c = 3 with ``fl - mu`` and ``V12.T``
+    in the mean, M == N); mode 2: predict_f (c = 1, ``fl - mu_GP``)."""
+    lwls = np.atleast_2d(np.asarray(lwls, dtype=np.float64))
+    pred = np.atleast_2d(np.asarray(lwls_predict, dtype=np.float64))
+    c, N = lwls.shape
+    M = pred.shape[1]
+    mu_c = [float(m) for m in np.atleast_1d(mu_c)]
+    K = _sym_ext(lwls, gp)
+    K[np.diag_indices_from(K)] += np.asarray(sigma, dtype=_LD) ** 2
+    L = _chol_ext(K)
+    if mode == 0:
+        Ct = np.concatenate([_fill_ext(lwls[k], pred[k], gp[2 * k], gp[2 * k + 1]) for k in range(c)], axis=1)
+        A = np.zeros((c * M, c * M), dtype=_LD)
+        for k in range(c):
+            A[k * M:(k + 1) * M, k * M:(k + 1) * M] = _sym_ext(pred[k:k + 1], gp[2 * k:2 * k + 2])
+        m0 = np.concatenate([np.full(M, m, dtype=_LD) for m in mu_c])
+        offset = _LD(1.0)
+    else:
+        Ct = sum(_fill_ext(lwls[k], pred[k], gp[2 * k], gp[2 * k + 1]) for k in range(c))     # V12.T: (N, M)
+        A = sum(_sym_ext(pred[k:k + 1], gp[2 * k:2 * k + 2]) for k in range(c))
+        if mode == 1 and c == 2:
+            A[np.diag_indices_from(A)] += _LD(1e-8)
+        m0 = np.full(M, mu_c[0], dtype=_LD)
+        offset = _LD(1.0) if (mode == 1 and c == 2) else _LD(mu_c[0])
+    W = _fsolve_ext(L, Ct)
+    z = _fsolve_ext(L, np.asarray(fl, dtype=_LD) - offset)
+    if mode == 1 and c == 3:
+        assert M == N, "predict_f_g_h_sum is only defined for M == N in the reference"
+        alpha = _fsolve_ext(L.T[::-1, ::-1], z[::-1])[::-1]        # K^-1 r: L^T alpha = z, reversed into a lower solve
+        mu = m0 + Ct @ alpha                                      # V12.T K^-1 r (covariance.py:294)
+    else:
+        mu = m0 + W.T @ z
+    if not want_sigma:
+        return mu
+    return mu, A - W.T @ W

@@ -43,6 +43,7 @@ SIGNATURES = {
     "psoap_last_error": (ctypes.c_char_p, []),
     "psoap_device_count": (ctypes.c_int, [_ip]),
     "psoap_share_stats": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_longlong), ctypes.c_int]),
+    "psoap_dag_form_launches": (ctypes.c_int, [ctypes.POINTER(ctypes.c_longlong), ctypes.c_int]),
     "psoap_chunk_create": (ctypes.c_int, [ctypes.POINTER(_vp), ctypes.c_int, ctypes.c_int, _dp, _dp, ctypes.c_int]),
     "psoap_chunk_destroy": (ctypes.c_int, [_vp]),
     "psoap_chunk_set_data": (ctypes.c_int, [_vp, _dp, _dp]),
@@ -215,6 +216,23 @@ def share_stats(device: int | None = None) -> dict:
     check(load().psoap_share_stats(default_device() if device is None else int(device), out, len(SHARE_NAMES)),
           "psoap_share_stats")
     return dict(zip(SHARE_NAMES, (int(v) for v in out)))
+
+
+DAG_FORM_NAMES = tuple([f"{kind}/C{c}/{form}" for kind in ("lnlike", "predict") for c in (1, 2, 3)
+                        for form in ("TP", "LAT", "wide")] +
+                       [f"stream/C{c}/{form}" for c in (1, 2, 3) for form in ("TP", "LAT")])
+
+
+def dag_form_launches() -> dict:
+    """Persistent launches per built form of k_chol_dag so far in this process (include/psoap_gp.h:
+    psoap_dag_form_launches), keyed ``"<lnlike|predict|stream>/C<c>/<TP|LAT|wide>"``."""
+    L = load()
+    n = L.psoap_dag_form_launches(None, 0)
+    if n != len(DAG_FORM_NAMES):
+        raise PsoapError(f"the library has {n} persistent-kernel forms, psoap_amd._lib names {len(DAG_FORM_NAMES)}")
+    out = (ctypes.c_longlong * n)()
+    L.psoap_dag_form_launches(out, n)
+    return dict(zip(DAG_FORM_NAMES, (int(v) for v in out)))
 
 
 def default_device() -> int:

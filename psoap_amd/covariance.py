@@ -195,9 +195,10 @@ def predict_components_var(lwls, fl, sigma, lwls_predict, mus, gp):
 
 
 def predict_f(lwl_known, fl_known, sigma_known, lwl_predict, amp_f, l_f, mu_GP=1.0):
-    """Single-component conditional.  The reference body is unrunnable
-    (NameError ``wl_predict``, covariance.py:38); this implements the evidently
-    intended ``N = len(lwl_predict)``."""
+    """Single-component conditional (covariance.py:25-54): mean ``mu_GP + V12^T V11^-1 (fl - mu_GP)``.  The reference
+    body reads ``len(wl_predict)`` (:38), a name it does not define; with ``covariance.wl_predict = lwl_predict`` set as
+    a module global it runs unmodified, and its values at several ``mu_GP`` are pinned
+    (tests/golden/golden_predict_f_v1.npz).  This implements that ``N = len(lwl_predict)``."""
     return _predict(2, [lwl_known], fl_known, sigma_known, [lwl_predict], [mu_GP], [amp_f, l_f])
 
 

@@ -4,6 +4,7 @@
 #pragma once
 #include <stdlib.h>
 #include <string.h>
+#include <atomic>
 #include <vector>
 
 #include "dag_kernel.hpp"
@@ -129,6 +130,8 @@ struct DagKernel {
     static constexpr int C = C_;
     static constexpr bool LAT = FORM != DAG_TP;
     static constexpr int WPE = FORM == DAG_WIDE ? 1 : (LAT || AUG || STREAM) ? 2 : DAG_WPE_TP;
+    // the member's place in the list (include/psoap_gp.h: psoap_dag_form_launches)
+    static constexpr int INDEX = STREAM ? 18 + 2 * (C - 1) + (LAT ? 1 : 0) : 9 * (AUG ? 1 : 0) + 3 * (C - 1) + FORM;
     static const void* fn() { return reinterpret_cast<const void*>(k_chol_dag<C, AUG, LAT, STREAM, WPE>); }
 };
 
@@ -164,6 +167,15 @@ inline hipError_t dag_set_lds()
     return e;
 }
 
+// launches of every member so far, process-wide, by DagKernel::INDEX (psoap_dag_form_launches: the tests read which form ran)
+constexpr int DAG_N_FORMS = 24;
+static_assert(DAG_N_FORMS == 2 * 3 * (DAG_WIDE + 1) + 3 * (DAG_LAT + 1), "a form was added to the list: give it an index");
+inline std::atomic<long long>* dag_form_launches()
+{
+    static std::atomic<long long> n[DAG_N_FORMS];
+    return n;
+}
+
 // One launch of the persistent kernel: the member for (C, lat, wide) on `grid` workgroups
 template <bool AUG, bool STREAM>
 inline void dag_launch(int C, bool lat, bool wide, int grid, hipStream_t s, const DagMat* mats, const DagTask* tasks,
@@ -174,6 +186,7 @@ inline void dag_launch(int C, bool lat, bool wide, int grid, hipStream_t s, cons
         using K = decltype(k);
         hipLaunchKernelGGL((k_chol_dag<K::C, AUG, K::LAT, STREAM, K::WPE>), dim3(grid), dim3(GEMM_THREADS), GEMM_LDS_BYTES,
                            s, mats, tasks, queues, flags, arrive, wspace, ctl, tlog, aug, st, pool);
+        dag_form_launches()[K::INDEX] += 1;
     });
 }
 

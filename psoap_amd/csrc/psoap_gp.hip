@@ -679,6 +679,13 @@ extern "C" int psoap_share_stats(int device, long long* out, int n)
     return 0;
 }
 
+// Persistent launches per built form so far, process-wide (include/psoap_gp.h); -> the number of forms
+extern "C" int psoap_dag_form_launches(long long* out, int n)
+{
+    for (int k = 0; out && k < n && k < DAG_N_FORMS; ++k) out[k] = dag_form_launches()[k].load();
+    return DAG_N_FORMS;
+}
+
 // hipFuncSetAttribute applies to the CURRENT device's function object: one pass per device, under a lock
 // (a process may open handles on several GPUs, from several host threads).
 static int configure_kernels(int device)

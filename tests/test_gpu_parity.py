@@ -210,7 +210,7 @@ def test_batches_that_are_not_a_multiple_of_eight(oracle, nw):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("c,ne,npx,nw", [(1, 8, 250, 1), (2, 10, 300, 1), (3, 4, 128, 1), (1, 4, 128, 4), (2, 6, 100, 8)])
-def test_single_evaluation_kernels_give_the_same_bits_in_512_and_in_256_registers(c, ne, npx, nw):
+def test_single_evaluation_kernels_give_the_same_bits_in_512_and_in_256_registers(oracle, c, ne, npx, nw):
     """Launches with at most one workgroup per compute unit run the LAT kernels compiled for one wave per SIMD
     (k_chol_dag<.., WPE = 1>); PSOAP_DAG_WIDE=0 keeps them on the 256-register forms: the same source, the same arithmetic,
     bit-identical results."""
@@ -228,6 +228,9 @@ def test_single_evaluation_kernels_give_the_same_bits_in_512_and_in_256_register
     finally:
         os.environ.pop("PSOAP_DAG_WIDE", None)
     assert np.all(np.isfinite(got["1"])) and np.array_equal(got["1"], got["0"])
+    for w in range(nw):
+        want = oracle.lnlike(lw[w], ch.fl, ch.sigma, gps[w])
+        assert lnp_close(got["1"][w], want), (w, got["1"][w], want)
 
 
 @pytest.mark.parametrize("mode", ["dag", "staged"])
@@ -347,6 +350,27 @@ def test_predict_sum_transposed_mean_and_predict_f(oracle, cov):
     np.testing.assert_allclose(Sig, Sig_o, rtol=0, atol=1e-9)
     with pytest.raises(AssertionError, match="Input wavelengths must be the same length."):
         cov.predict_f_g(ch.lwls[0], ch.lwls[1][:-1], ch.fl, ch.sigma, pg, pg, 0.0, 0.2, 5.0, 0.0, 0.1, 7.0)
+    # away from mu = 1 the two offsets differ (predict_kernels.hpp: 1.0 for the joint conditional and the sum of two, the
+    # prior mean for predict_f and the sum of three): predict_f against oracle.predict_f, and both against the values the
+    # reference itself returned (golden_predict_f_v1.npz)
+    for mu_gp in (0.9, 1.15):
+        mu, Sig = cov.predict_f(ch.lwls[0], ch.fl, ch.sigma, pg, 0.2, 5.0, mu_GP=mu_gp)
+        mu_o, Sig_o = oracle.predict_f(ch.lwls[0], ch.fl, ch.sigma, pg, 0.2, 5.0, mu_gp)
+        np.testing.assert_allclose(mu, mu_o, rtol=0, atol=1e-10)
+        np.testing.assert_allclose(Sig, Sig_o, rtol=0, atol=1e-9)
+    gold = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "golden_predict_f_v1.npz"))
+    for i, (ne, npx, seed, M, mu_gp, amp, l) in enumerate(gold["pf_meta"]):
+        chf = syn.make_chunk(1, int(ne), int(npx), seed=int(seed))
+        pgf = np.linspace(chf.lwls[0].min(), chf.lwls[0].max(), int(M))
+        mu, Sig = cov.predict_f(chf.lwls[0], chf.fl, chf.sigma, pgf, amp, l, mu_GP=mu_gp)
+        np.testing.assert_allclose(mu, gold[f"pf{i}_mu"], rtol=0, atol=1e-10)
+        np.testing.assert_allclose(Sig, gold[f"pf{i}_Sigma"], rtol=0, atol=1e-9)
+    for i, (ne, npx, seed, mu_fgh) in enumerate(gold["ps_meta"]):
+        chs = syn.make_chunk(3, int(ne), int(npx), seed=int(seed))
+        preds = [np.linspace(w.min(), w.max(), chs.N) for w in chs.lwls]
+        mu, Sig = cov.predict_f_g_h_sum(*chs.lwls, chs.fl, chs.sigma, *preds, mu_fgh, *syn.GP_BASE[3])
+        np.testing.assert_allclose(mu, gold[f"ps{i}_mu"], rtol=0, atol=1e-10)
+        np.testing.assert_allclose(Sig, gold[f"ps{i}_Sigma"], rtol=0, atol=1e-9)
 
 
 def test_batched_exp_is_bit_identical_to_library_exp():
@@ -387,6 +411,10 @@ def test_predict_edge_shapes_vs_oracle(oracle, cov, c, ne, npx, M, seed):
     if c == 1:
         mu, Sig = cov.predict_f(ch.lwls[0], ch.fl, ch.sigma, pred[0], *gp, mu_GP=1.0)
         mu_o, Sig_o = oracle.predict_components(ch.lwls, ch.fl, ch.sigma, pred, [1.0], gp)
+        mu_f, Sig_f = cov.predict_f(ch.lwls[0], ch.fl, ch.sigma, pred[0], *gp, mu_GP=0.93)     # offset = prior mean
+        mu_fo, Sig_fo = oracle.predict_f(ch.lwls[0], ch.fl, ch.sigma, pred[0], *gp, 0.93)
+        np.testing.assert_allclose(mu_f, mu_fo, rtol=0, atol=1e-10)
+        np.testing.assert_allclose(Sig_f, Sig_fo, rtol=0, atol=1e-9)
     elif c == 2:
         mu, Sig = cov.predict_f_g(ch.lwls[0], ch.lwls[1], ch.fl, ch.sigma, pred[0], pred[1], mus[0], gp[0], gp[1],
                                   mus[1], gp[2], gp[3])
@@ -398,6 +426,12 @@ def test_predict_edge_shapes_vs_oracle(oracle, cov, c, ne, npx, M, seed):
     else:
         mu, Sig = cov.predict_f_g_h(*ch.lwls, ch.fl, ch.sigma, *pred, *mus, *gp)
         mu_o, Sig_o = oracle.predict_components(ch.lwls, ch.fl, ch.sigma, pred, mus, gp)
+        # the sum of three at mu != 1 (offset = prior mean, V12.T in the mean: M == N on a grid of its own)
+        sp = [np.linspace(w.min(), w.max(), ch.N) for w in ch.lwls]
+        mu_s, Sig_s = cov.predict_f_g_h_sum(*ch.lwls, ch.fl, ch.sigma, *sp, 1.07, *gp)
+        mu_so, Sig_so = oracle.predict_sum(ch.lwls, ch.fl, ch.sigma, sp, 1.07, gp)
+        np.testing.assert_allclose(mu_s, mu_so, rtol=0, atol=1e-10)
+        np.testing.assert_allclose(Sig_s, Sig_so, rtol=0, atol=1e-9)
     assert mu.shape == (c * M,) and Sig.shape == (c * M, c * M)
     np.testing.assert_allclose(mu, mu_o, rtol=0, atol=1e-10)
     np.testing.assert_allclose(Sig, Sig_o, rtol=0, atol=1e-9)

@@ -90,8 +90,9 @@ def test_both_split_schemes_agree_with_oracle(oracle, monkeypatch):
                 assert np.array_equal(h.lnlike_batch(lw, gps), got[scheme])
         for w in range(B):
             assert close(got["0"][w], got["1"][w]), (ch.N, w)
-        want = oracle.lnlike(lw[B - 1], ch.fl, ch.sigma, gps[B - 1])
-        assert close(got["0"][B - 1], want) and close(got["1"][B - 1], want), (ch.N, got, want)
+        for w in range(B):
+            want = oracle.lnlike(lw[w], ch.fl, ch.sigma, gps[w])
+            assert close(got["0"][w], want) and close(got["1"][w], want), (ch.N, w, got, want)
 
 
 def test_large_matrix_against_oracle(oracle):
@@ -127,4 +128,4 @@ def test_smallest_matrices_one_to_four_block_rows(oracle):
                 assert np.array_equal(h.lnlike_batch(lw, gps), got)
             for w in range(B):
                 assert close(got[w], staged[w]), (ch.N, B, w)
-            assert close(got[0], oracle.lnlike(lw[0], ch.fl, ch.sigma, gps[0])), (ch.N, B)
+                assert close(got[w], oracle.lnlike(lw[w], ch.fl, ch.sigma, gps[w])), (ch.N, B, w)
