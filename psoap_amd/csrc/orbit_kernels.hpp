@@ -6,8 +6,15 @@
 //                 f = th (E < pi) or th + 2 pi;
 //   velocities    :74-93 (SB1), :135-170 (SB2), :256-320 (ST1), :349-417 (ST2), :443-487 (ST3).
 // The reference solves Kepler's equation with scipy.optimize.fsolve from E0 = M (xtol 1.5e-8); here
-// Newton's method runs to machine precision.  Measured difference to the reference: <= 1.4e-10 km/s
-// over 200 random SB2 orbits with e up to 0.9 (tests pin 1e-8 km/s).
+// Newton's method runs to machine precision.  Two things are pinned ("orbit tolerance"):
+//   * against the reference's own output (fsolve, xtol 1.5e-8): 1e-8 km/s (golden_orbit_v1.npz; measured <= 1.4e-10
+//     over 200 random SB2 orbits with e up to 0.9);
+//   * against an independent long-double value (oracle/orbit_ext.py: bisection, atan2): a fixed multiple of
+//     u = eps (sum over the velocity terms of K_eff (1 + sqrt(1+e) / (1-e)^1.5) + |gamma|), the condition of the map
+//     at periastron -- the multiple is 4x what the double-precision CPU oracle needs over the case table of
+//     tests/orbit_cases.py (GPU_BOUND_UNITS there), for e from 0 to 0.999, every phase edge and all five models.
+// orbit_velocities_at is evaluated by two kernels (k_orbit_velocities here, the resident stream's dispatcher in
+// dag_kernel.hpp); tests/test_gpu_orbit_front.py holds them to the same bits.
 // One thread per (proposal, epoch); output layout (B, c, n_epochs) as k_doppler_shift expects.
 #pragma once
 #include "common.hpp"

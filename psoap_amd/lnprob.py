@@ -13,7 +13,7 @@ import numpy as np
 from . import _lib
 from ._lib import as_f64, check, dptr
 from .chunk import ChunkHandle
-from .utils import MODEL_ID, N_COMPONENTS, convert_vectors
+from .utils import MODEL_ID, N_COMPONENTS, convert_vectors, n_params_orb
 
 
 class ChunkWorker:
@@ -36,7 +36,17 @@ class ChunkWorker:
         """Ship fitted parameter vectors (B, n_fit); the orbit solve and the Doppler shift are queued on the
         chunk's stream.  Follow with ``handle.eval()`` (or a ``ChunkGroup.eval()``) and ``handle.fetch()``."""
         p_orb, p_gp = convert_vectors(np.atleast_2d(ps), self.model, self.fix_params, **self.defaults)
+        self.upload_orbits(p_orb, p_gp, mu_GP)
+
+    def upload_orbits(self, p_orb, p_gp, mu_GP: float = 1.0) -> None:
+        """The same with the vectors already split: orbital parameters (B, n_orb) and GP parameters (B, 2c).  The library
+        reads exactly 2c GP parameters per proposal, so a narrower array is refused here.  (ST2 registers two GP
+        parameters, utils.py:7, for a likelihood of two components, covariance.py:379: its fitted vectors stop at
+        ``upload_proposals`` as they stop with a TypeError in ``Worker.lnprob``; this entry takes all four.)"""
+        p_orb = as_f64(np.atleast_2d(p_orb))
         B = p_orb.shape[0]
+        p_orb = as_f64(p_orb, (B, n_params_orb[self.model]))
+        p_gp = as_f64(np.atleast_2d(p_gp), (B, 2 * N_COMPONENTS[self.model]))
         h = self.handle
         check(h._L.psoap_batch_upload_orbits(h._h, B, MODEL_ID[self.model], dptr(p_orb), dptr(p_gp), float(mu_GP)),
               "psoap_batch_upload_orbits")
