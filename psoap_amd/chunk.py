@@ -266,6 +266,16 @@ class ChunkHandle:
             out[name] = {"ms": t.ms[k], "launches": int(t.launches[k]), "flops": t.flops[k], "bytes": t.bytes[k]}
         return out
 
+    def sky_stats(self) -> dict:
+        """The skyline of the last evaluation (include/psoap_gp.h: psoap_chunk_sky_stats): tiles and tile-GEMM units of the
+        list that ran against the dense ones, plan builds and plan-cache hits so far, whether the slot's skyline was read."""
+        names = ("tiles_planned", "tiles_dense", "units_planned", "units_dense", "plan_builds", "cache_hits", "skyline_on")
+        out = (ctypes.c_longlong * len(names))()
+        n = self._L.psoap_chunk_sky_stats(self._h, out, len(names))
+        if n != len(names):
+            raise _lib.PsoapError(f"psoap_chunk_sky_stats reports {n} fields, psoap_amd.chunk names {len(names)}")
+        return dict(zip(names, (int(v) for v in out)))
+
 
 class StreamPipeline:
     """``groups`` sub-ensembles of one walker ensemble in flight through a stream (``ChunkHandle.stream_open``): step k of

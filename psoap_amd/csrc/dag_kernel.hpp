@@ -177,6 +177,7 @@ struct DagTask {
     unsigned int ctr;
 };
 static_assert(sizeof(DagTask) == 16, "DagTask is 16 bytes");
+constexpr unsigned int DAG_CTR_MASK = 0x00ffffffu;   // DagTask::ctr of a final: bits 24.. belong to the skyline (dag_build_tasks)
 
 constexpr long long DAG_MAX_SPINS = 2000000;  // x (s_sleep + atomic round trip) ~ seconds
 
@@ -2041,7 +2042,11 @@ __global__ __launch_bounds__(GEMM_THREADS, WPE) void k_chol_dag(const DagMat* __
         const int ld = mat.ld, N = mat.N, Npad = mat.Npad;
         MatFlags* f = flags + b;
         const int k0 = q * NB, j0 = j * NB;
-        const int ntasks_row = (AUG ? aug.Pt : mat.P) - q;
+        // (the likelihood's throughput form: a block row inside a skyline is short of the dense P - q by what its finals'
+        // records say -- dag_build_tasks; zero in a dense list)
+        constexpr bool SKY = !LAT && !AUG && !STREAM;
+        const unsigned int tctr = SKY ? (task.ctr & DAG_CTR_MASK) : task.ctr;
+        const int ntasks_row = (AUG ? aug.Pt : mat.P) - q - (SKY ? (int)(task.ctr >> 24) : 0);
 
         if (tlog_l && threadIdx.x == 0) {
             tlog_l[ticket * 8 + 0] = __builtin_amdgcn_s_memrealtime();
@@ -2117,7 +2122,7 @@ __global__ __launch_bounds__(GEMM_THREADS, WPE) void k_chol_dag(const DagMat* __
         t.zero();
         if (preload) {
             // the chain ran ahead (its PARTs need older block rows): normally no wait at all
-            dag_wait_ge(&arrive_l[task.ctr], n_wait, ctl, 4u);
+            dag_wait_ge(&arrive_l[tctr], n_wait, ctl, 4u);
             dag_sub_partials<false, true>(t, prev, 1);
             n_prev = 0;
         }
@@ -2128,7 +2133,7 @@ __global__ __launch_bounds__(GEMM_THREADS, WPE) void k_chol_dag(const DagMat* __
             t, Km, ld, k0, j0, task.pa, task.pb, f, ctl, ttype == DAG_DIAG && (task.type & DAG_WAITNEXT) != 0,
             tlog_l ? tlog_l + ticket * 8 : nullptr, wave_s, SmemKernel(), &f->rvrow[q], &f->rvrow[j]);
         if (tlog_l && threadIdx.x == 0) tlog_l[ticket * 8 + 5] = __builtin_amdgcn_s_memrealtime();
-        if (!preload && n_wait > 0) dag_wait_ge(&arrive_l[task.ctr], n_wait, ctl, 4u);
+        if (!preload && n_wait > 0) dag_wait_ge(&arrive_l[tctr], n_wait, ctl, 4u);
         if (tlog_l && threadIdx.x == 0) tlog_l[ticket * 8 + 6] = __builtin_amdgcn_s_memrealtime();
         dag_sub_partials<false, true>(t, prev, n_prev);
         {
@@ -2164,7 +2169,7 @@ __global__ __launch_bounds__(GEMM_THREADS, WPE) void k_chol_dag(const DagMat* __
             if (tlog_l && threadIdx.x == 0) tlog_l[ticket * 8 + 4] = __builtin_amdgcn_s_memrealtime();              // drained
             if (threadIdx.x == 0) {
                 dag_release_fence();
-                __hip_atomic_fetch_add(&arrive_l[task.ctr], 1, PSOAP_RLX_AGENT);
+                __hip_atomic_fetch_add(&arrive_l[tctr], 1, PSOAP_RLX_AGENT);
             }
             if (tlog_l && threadIdx.x == 0) tlog_l[ticket * 8 + 3] = __builtin_amdgcn_s_memrealtime();
             dag_task_end<STREAM>(st, b, mat.acc, mat.P, where0, ctl, wave_s);
@@ -2428,8 +2433,18 @@ inline bool dag_fixed_plan()
 constexpr int STREAM_NOMINAL_LANES = 32;
 inline int dag_nominal_share(int workers_total) { const int s = workers_total / STREAM_NOMINAL_LANES / 2; return s > 0 ? s : 1; }
 
+// tiles of block row q inside the skyline `first` of a matrix of P block rows (the diagonal tile included)
+inline int dag_sky_row_tiles(const int* first, int P, int q)
+{
+    int n = 0;
+    for (int j = q; j < P && first[j] <= q; ++j) ++n;
+    return n;
+}
+// `first` (scheme 0, uniform batches without appended columns; nullptr: dense): the skyline -- tile (q, j) exists iff
+// q >= first[j], first non-decreasing with first[j] <= max(j - 1, 0); the update of an existing tile runs over the block rows
+// [first[j], q) and is cut into equal ranges of that.  All zero: the dense list, byte for byte.
 inline void dag_build_queue(DagPlan& plan, const std::vector<int>& mats, const std::vector<int>& Ps, int workers,
-                            int Bq_nominal, int scheme, int Mt = 0, int Ms = 0, int fixed_share = 0)
+                            int Bq_nominal, int scheme, int Mt = 0, int Ms = 0, int fixed_share = 0, const int* first = nullptr)
 {
     // Ps[b]: block rows of matrix b.  A heterogeneous batch (matrices of several chunks) walks the block
     // rows of all its matrices together; a matrix simply drops out once its rows are used up.
@@ -2447,6 +2462,7 @@ inline void dag_build_queue(DagPlan& plan, const std::vector<int>& mats, const s
     const bool cont0 = (scheme == 0) && DAG_TILE_DEPS;
     std::vector<DagTask> owned_final(Ps.size());          // per matrix: the DIAG(q+1) final to emit behind tile (q, q+1)
     std::vector<char> has_owned(Ps.size(), 0);
+    auto fj = [first](int j) { return first ? first[j] : 0; };
     for (int q = 0; q < P; ++q) {
         // tiles of this block row in the queue; uniform batches use the nominal matrix count so that the
         // split factors do not depend on the slot a matrix sits in
@@ -2461,11 +2477,13 @@ inline void dag_build_queue(DagPlan& plan, const std::vector<int>& mats, const s
             row_tiles = (long long)Bq_nominal * (P + Mt - q);
             live = Bq_nominal;
         }
+        if (first) row_tiles = (long long)Bq_nominal * dag_sky_row_tiles(first, P, q);
         const int Bq = live;
         // (fixed_share > 0: per matrix, from its own size only)
-        auto s_off = [&](int b) {
+        // (span: the block rows the tile's update runs over -- q, or q - first[j] inside a skyline)
+        auto s_off = [&](int b, int span) {
             return fixed_share > 0 ? dag_split_factor(Ps[b] + Mt - q, q, fixed_share, scheme, 1)
-                                   : dag_split_factor((int)row_tiles, q, workers, scheme, (int)Ps.size(), Mt > 0);
+                                   : dag_split_factor((int)row_tiles, span, workers, scheme, (int)Ps.size(), Mt > 0);
         };
         // latency scheme: DIAG(q) also solves the tile right of the diagonal (DAG_FUSED) whenever a next
         // diagonal tile exists, and DIAG(q >= 1) waits only for that tile of the row above (DAG_WAITNEXT)
@@ -2530,9 +2548,10 @@ inline void dag_build_queue(DagPlan& plan, const std::vector<int>& mats, const s
         // Latency scheme: the PART that needs the block row just above (panel q-1, available only when ALL
         // of row q-1 is finished) is one panel long; the long ones cover [0, q-1) and run a row earlier.
         if (q + 1 < P && q >= 1) {
+            const int f_pre = fj(q + 1), span_pre = q - f_pre;      // (skyline: the diagonal tile's history starts at first[q+1])
             const int S_pre = fixed_share > 0
                                   ? dag_split_factor(1, q, fixed_share / 4 > 0 ? fixed_share / 4 : 1, scheme, 1)
-                                  : dag_split_factor(Bq, q, workers / 4 > 0 ? workers / 4 : 1, scheme, (int)Ps.size());
+                                  : dag_split_factor(Bq, span_pre, workers / 4 > 0 ? workers / 4 : 1, scheme, (int)Ps.size());
             for (int b : mats) {
                 if (q + 1 >= Ps[b]) continue;
                 const unsigned int ctr = plan.n_ctrs++;
@@ -2552,9 +2571,10 @@ inline void dag_build_queue(DagPlan& plan, const std::vector<int>& mats, const s
                         ranges.emplace_back((int)((long long)(q - 1) * sidx / S_long),
                                             (int)((long long)(q - 1) * (sidx + 1) / S_long));
                     if (!two) ranges.emplace_back(q - 1, q);
-                } else {
+                } else if (span_pre > 0) {      // (nothing to pre-accumulate when the history starts at row q: the final alone)
                     for (int sidx = 0; sidx < S_pre; ++sidx)
-                        ranges.emplace_back((int)((long long)q * sidx / S_pre), (int)((long long)q * (sidx + 1) / S_pre));
+                        ranges.emplace_back(f_pre + (int)((long long)span_pre * sidx / S_pre),
+                                            f_pre + (int)((long long)span_pre * (sidx + 1) / S_pre));
                 }
                 const int n_parts = (int)ranges.size();
                 for (int sidx = 0; sidx < n_parts; ++sidx) {
@@ -2583,7 +2603,7 @@ inline void dag_build_queue(DagPlan& plan, const std::vector<int>& mats, const s
                 fin.S = (unsigned char)(n_parts + 1);
                 fin.pa = (unsigned char)(two && chain && q >= 2 ? q - 1 : q);
                 fin.pb = (unsigned char)(q + 1);
-                fin.slot = chain ? slot0 + (unsigned int)((n_parts - 1) & 1) : slot0;
+                fin.slot = n_parts == 0 ? 0u : chain ? slot0 + (unsigned int)((n_parts - 1) & 1) : slot0;
                 fin.ctr = ctr;
                 if (cont0) {
                     fin.type |= DAG_NOSOLVE;          // owned by the strip solve of tile (q, q+1): step 3
@@ -2597,8 +2617,9 @@ inline void dag_build_queue(DagPlan& plan, const std::vector<int>& mats, const s
         // 3. off-diagonal tiles of this row
         for (int b : mats)
             for (int j = q + 1; j < Ps[b] + Mt && q < Ps[b]; ++j) {
+                if (fj(j) > q) break;      // outside the skyline (first is non-decreasing: so is the rest of the row)
                 const bool owner = cont0 && j == q + 1 && q + 1 < Ps[b];     // its workgroup goes on with DIAG(q+1)
-                dag_emit(plan, DAG_OFF, b, q, j, 0, q, s_off(b), scheme,
+                dag_emit(plan, DAG_OFF, b, q, j, fj(j), q, s_off(b, q - fj(j)), scheme,
                          following ? (unsigned char)(DAG_WAITNEXT | (xlink(q) ? DAG_FUSED : 0) |
                                                      ((j == q + 1 && q + 1 < Ps[b]) ? DAG_NOSOLVE : 0))
                                    : (unsigned char)(((j == q + 1 && fused(b)) ? DAG_NOSOLVE : 0) | (owner ? DAG_FUSED : 0)),
@@ -2715,12 +2736,15 @@ inline int dag_auto_scheme(const std::vector<int>& Ps)
     return latency;
 }
 // fixed_share > 0: the fixed plan (dag_fixed_plan) -- scheme 0, every matrix cut as ONE matrix on `fixed_share` workgroups
+// first: the skyline of a uniform likelihood batch (dag_build_queue) -- scheme 0 then, whatever `scheme` says.  A final's
+// DagTask::ctr carries in bits 24.. how many tiles its block row is SHORT of the dense P - q (the kernel counts a row's
+// finished tasks against it); zero everywhere in a dense list.
 inline DagPlan dag_build_tasks(const std::vector<int>& Ps, int workers, int scheme = -1, int Mt = 0, int Ms = 0,
-                               int fixed_share = 0)
+                               int fixed_share = 0, const int* first = nullptr)
 {
     DagPlan plan;
     const int B = (int)Ps.size();
-    if (fixed_share > 0) scheme = 0;
+    if (fixed_share > 0 || first) scheme = 0;
     if (scheme < 0) scheme = dag_auto_scheme(Ps);
 #ifndef PSOAP_FOLLOW
     if (scheme == 2) scheme = 1;       // the following scheme needs the kernels built with -DPSOAP_FOLLOW
@@ -2735,7 +2759,7 @@ inline DagPlan dag_build_tasks(const std::vector<int>& Ps, int workers, int sche
         std::vector<int> mats;
         if (g < nq)
             for (int b = g; b < B; b += nq) mats.push_back(b);
-        dag_build_queue(plan, mats, Ps, per_queue, (B + nq - 1) / nq, scheme, Mt, Ms, fixed_share);
+        dag_build_queue(plan, mats, Ps, per_queue, (B + nq - 1) / nq, scheme, Mt, Ms, fixed_share, first);
         if (scheme >= 1) {
             // Latency scheme: hand the tasks out in order of READINESS instead of block row by block row.
             // A task over panels [pa, pb) can run once block row pb-1 is finished ("stage" pb); within a
@@ -2807,6 +2831,10 @@ inline DagPlan dag_build_tasks(const std::vector<int>& Ps, int workers, int sche
         }
     }
     plan.queues.first[DAG_QUEUES] = (unsigned int)plan.tasks.size();
+    if (first)
+        for (DagTask& t : plan.tasks)
+            if ((t.type & DAG_TYPE_MASK) != DAG_PART)
+                t.ctr |= (unsigned int)(Ps[t.b] - t.q - dag_sky_row_tiles(first, Ps[t.b], t.q)) << 24;
     plan.queues.follow_first = (unsigned int)dag_follow_first_row();
 #ifdef PSOAP_POOL
     if (scheme >= 1) dag_build_pool(plan);

@@ -37,6 +37,45 @@ inline DagPlan dag_lnlike_plan(const std::vector<int>& Ps, int n_cus, int dag_gr
     return dag_build_tasks(Ps, *workers, dag_env_scheme(), 0, 0, dag_fixed_plan() ? dag_nominal_share(dag_grid - 1) : 0);
 }
 
+// the scheme dag_lnlike_plan's list is built for (psoap_batch_eval asks before it builds: only scheme 0 reads a skyline)
+inline int dag_lnlike_scheme(const std::vector<int>& Ps)
+{
+    if (dag_fixed_plan()) return 0;
+    const int e = dag_env_scheme();
+    int scheme = e >= 0 ? e : dag_auto_scheme(Ps);
+#ifndef PSOAP_FOLLOW
+    if (scheme == 2) scheme = 1;
+#endif
+    return scheme;
+}
+
+// The throughput list of a uniform batch inside the skyline first[0 .. P) (sky_kernels.hpp; dag_build_queue)
+inline DagPlan dag_lnlike_plan_sky(int B, int P, const int* first, int n_cus, int dag_grid, int* workers)
+{
+    const std::vector<int> Ps((size_t)B, P);
+    *workers = dag_batch_workers(Ps, 0, n_cus, dag_grid);
+    return dag_build_tasks(Ps, *workers, 0, 0, 0, 0, first);
+}
+
+// what a list executes: tiles (finals), tile-GEMM units (128-row panels of the updates), MFMA flops (updates + strip solves)
+struct DagPlanWork {
+    long long tiles = 0, units = 0;
+    double flops = 0.0;
+};
+inline DagPlanWork dag_plan_work(const DagPlan& plan)
+{
+    DagPlanWork w;
+    long long solves = 0;
+    for (const DagTask& t : plan.tasks) {
+        const int ty = t.type & DAG_TYPE_MASK;
+        w.units += (int)t.pb - (int)t.pa;
+        if (ty != DAG_PART) ++w.tiles;
+        if (ty == DAG_OFF) ++solves;
+    }
+    w.flops = 2.0 * NB * NB * NB * (double)(w.units + solves);
+    return w;
+}
+
 // the LAT kernels (and predict's, the stream's): at most two workgroups per compute unit
 inline int dag_two_per_cu(int workers, int n_cus) { return workers > 2 * n_cus ? 2 * n_cus : workers; }
 
@@ -56,17 +95,27 @@ struct DagWorkspace {
     int scheme = 0;
     unsigned int n_tasks = 0, n_slots = 0;
 
-    hipError_t load(const DagPlan& plan, size_t n_mats)
+    // (resident: the same list in device memory already -- a cached one; it is copied on `s`, behind the launches queued
+    // there, and the host waits for them only where a buffer has to grow)
+    hipError_t load(const DagPlan& plan, size_t n_mats, const DagTask* resident = nullptr, hipStream_t s = nullptr)
     {
         const size_t nt = plan.tasks.size();
+        // (the throughput kernels read bits 24.. of a final's ctr as its block row's shortfall: dag_build_tasks)
+        if (plan.n_ctrs > DAG_CTR_MASK) return hipErrorInvalidValue;
         arrive_off = sizeof(DagCtl) + sizeof(MatFlags) * n_mats;
         taken_off = arrive_off + sizeof(int) * ((size_t)plan.n_ctrs + 4);
         ctl_bytes = taken_off + sizeof(unsigned int) * ((nt + 31) / 32 + 1);
         pool = !plan.order.empty();
-        hipError_t e = ctl.need(ctl_bytes);
+        hipError_t e = hipSuccess;
+        const size_t ws_count = (size_t)NB * NB * ((size_t)plan.n_slots + 1);
+        if (resident && (ctl_bytes > ctl.cap || nt > tasks.cap || ws_count > ws.cap || !ctl.p || !tasks.p || !ws.p))
+            e = hipStreamSynchronize(s);
+        if (e == hipSuccess) e = ctl.need(ctl_bytes);
         if (e == hipSuccess) e = tasks.need(nt);
         if (e == hipSuccess) e = ws.need((size_t)NB * NB * ((size_t)plan.n_slots + 1));
-        if (e == hipSuccess) e = hipMemcpy(tasks, plan.tasks.data(), sizeof(DagTask) * nt, hipMemcpyHostToDevice);
+        if (e == hipSuccess)
+            e = resident ? hipMemcpyAsync(tasks, resident, sizeof(DagTask) * nt, hipMemcpyDeviceToDevice, s)
+                         : hipMemcpy(tasks, plan.tasks.data(), sizeof(DagTask) * nt, hipMemcpyHostToDevice);
         if (pool) {
             if (e == hipSuccess) e = order.need(plan.order.size());
             if (e == hipSuccess) e = dep.need(plan.dep.size());

@@ -16,10 +16,12 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <set>
 #include <string>
@@ -30,6 +32,7 @@
 #include "solo_kernel.hpp"
 #include "dag_launch.hpp"
 #include "fill_kernels.hpp"
+#include "sky_kernels.hpp"
 #include "orbit_kernels.hpp"
 #include "predict_kernels.hpp"
 #include "calibrate_kernels.hpp"
@@ -514,10 +517,20 @@ struct DeviceScope {
 struct BatchSlot {
     double* dLwl = nullptr;    // max_batch x 3 x N
     double* dGp = nullptr;     // max_batch x 6
+    // sorted layout (sky_kernels.hpp; a handle with the skyline on): the slot's rows in ascending ln-wavelength of its first
+    // walker's first component -- what the evaluations read; dLwl keeps the upload's order
+    double* dLwlS = nullptr;   // max_batch x 3 x N
+    double* dFlS = nullptr;    // N: the handle's fl and sigma through the same permutation
+    double* dSigmaS = nullptr;
+    int* dPerm = nullptr;      // N
+    int* dFirstB = nullptr;    // max_batch x P: first_b per matrix
+    int* hFirst = nullptr;     // P, pinned: the union over the batch
     int* dTooFast = nullptr;   // max_batch: |v| >= c flags (orbit proposals)
     bool toofast_dirty = false;  // an orbit upload may have raised flags: clear before the slot is reused
     DagMat* dMats = nullptr;   // per-matrix records of this slot (max_batch entries)
     int mats_B = 0, mats_C = 0;
+    bool mats_sorted = false;  // the records point at the sorted copies
+    bool sky_valid = false;    // the last upload computed the sorted copies and the skyline (upload_end)
     int B = 0, C = 0;
     double mu = 1.0;
     std::vector<char> neg;     // per-proposal: a hyper-parameter was negative -> -inf
@@ -597,6 +610,20 @@ struct psoap_chunk {
     // task list of the persistent kernel for the current batch size (dag_lnlike_plan), and its workgroups
     DagWorkspace dag;
     int plan_B = 0, plan_workers = 0;
+    // skyline (PSOAP_SKYLINE=0, read at create, or N > SKY_MAX_N: off -- identity order, dense plan)
+    bool sky = false;
+    std::vector<int> plan_first;      // the skyline of the list in `dag` (empty: dense)
+    DagPlanWork plan_work;            // what that list executes (a skyline list only)
+    struct SkyPlan {
+        int B;
+        std::vector<int> first;
+        DagPlan plan;
+        int workers;
+        DagPlanWork work;
+        std::unique_ptr<Grow<DagTask>> dTasks;      // the list on the device
+    };
+    std::vector<SkyPlan> sky_cache;   // the last few skyline lists, newest first
+    long long sky_stats[7] = {};      // psoap_chunk_sky_stats
     unsigned long long* dTlog = nullptr;  // optional per-task timestamps (debug)
     long long tlog_tasks = 0;
     // pinned host staging (one set: reused once the previous upload's copies have completed)
@@ -751,7 +778,20 @@ static int chunk_alloc(psoap_chunk* h, const double* fl, const double* sigma)
     HIP_TRY(hipHostMalloc(&h->hLwl, sizeof(double) * nb * 3 * N));
     HIP_TRY(hipHostMalloc(&h->hGp, sizeof(double) * nb * 6));
     HIP_TRY(hipHostMalloc(&h->hOut, sizeof(double) * nb));
+    {
+        const char* e = getenv("PSOAP_SKYLINE");
+        h->sky = N <= SKY_MAX_N && !(e && e[0] == '0');
+    }
     for (BatchSlot& sl : h->slot) {
+        if (h->sky) {
+            HIP_TRY(hipMalloc(&sl.dLwlS, sizeof(double) * nb * 3 * N));
+            HIP_TRY(hipMalloc(&sl.dFlS, sizeof(double) * N));
+            HIP_TRY(hipMalloc(&sl.dSigmaS, sizeof(double) * N));
+            HIP_TRY(hipMalloc(&sl.dPerm, sizeof(int) * N));
+            HIP_TRY(hipMalloc(&sl.dFirstB, sizeof(int) * nb * h->P));
+            HIP_TRY(hipHostMalloc(&sl.hFirst, sizeof(int) * h->P));
+            memset(sl.hFirst, 0, sizeof(int) * h->P);
+        }
         HIP_TRY(hipMalloc(&sl.dLwl, sizeof(double) * nb * 3 * N));
         HIP_TRY(hipMalloc(&sl.dGp, sizeof(double) * nb * 6));
         HIP_TRY(hipMalloc(&sl.dTooFast, sizeof(int) * nb));
@@ -839,6 +879,8 @@ extern "C" int psoap_chunk_destroy(psoap_chunk* h)
     (void)hipHostFree(h->hLwl); (void)hipHostFree(h->hGp); (void)hipHostFree(h->hVel); (void)hipHostFree(h->hOut);
     for (BatchSlot& sl : h->slot) {
         (void)hipFree(sl.dLwl); (void)hipFree(sl.dGp); (void)hipFree(sl.dTooFast); (void)hipFree(sl.dMats);
+        (void)hipFree(sl.dLwlS); (void)hipFree(sl.dFlS); (void)hipFree(sl.dSigmaS); (void)hipFree(sl.dPerm);
+        (void)hipFree(sl.dFirstB); (void)hipHostFree(sl.hFirst);
         if (sl.evUpload) (void)hipEventDestroy(sl.evUpload);
         if (sl.evEval) (void)hipEventDestroy(sl.evEval);
     }
@@ -864,6 +906,14 @@ extern "C" int psoap_chunk_set_data(psoap_chunk* h, const double* fl, const doub
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(h->dFl, fl, sizeof(double) * h->N, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(h->dSigma, sigma, sizeof(double) * h->N, hipMemcpyHostToDevice));
+    // the sorted copies of the slots that hold a batch
+    for (BatchSlot& sl : h->slot)
+        if (h->sky && sl.B > 0 && sl.sky_valid) {
+            hipLaunchKernelGGL(k_sky_gather, dim3((h->N + 255) / 256, 2), dim3(256), 0, h->streams[0], sl.dPerm, h->N, 0,
+                               (const double*)nullptr, (double*)nullptr, h->dFl, sl.dFlS, h->dSigma, sl.dSigmaS);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipStreamSynchronize(h->streams[0]));
+        }
     return 0;
 }
 
@@ -932,6 +982,70 @@ extern "C" int psoap_dag_plan(int B, int P, int workers, void* out, long long ma
         memcpy(out, plan.tasks.data(), sizeof(DagTask) * n);
     }
     return 0;
+}
+
+// Pure host function: the throughput list of the same batch inside the skyline first[0 .. P) (tile (q, j) exists iff
+// q >= first[j]; non-decreasing, first[j] <= max(j - 1, 0)).  All zero: psoap_dag_plan's list, byte for byte.
+extern "C" int psoap_dag_plan_sky(int B, int P, const int* first, int workers, void* out, long long max_tasks,
+                                  long long* n_tasks, long long* n_slots, long long* n_ctrs, unsigned int* queue_first)
+{
+    if (B < 1 || P < 1 || P > 255 || workers < 1 || !n_tasks || !first) FAIL("psoap_dag_plan_sky: bad arguments");
+    bool any = false;
+    for (int j = 0; j < P; ++j) {
+        if (first[j] < 0 || first[j] > (j > 0 ? j - 1 : 0) || (j > 0 && first[j] < first[j - 1]))
+            FAIL("psoap_dag_plan_sky: first must be non-decreasing with 0 <= first[j] <= max(j - 1, 0)");
+        any = any || first[j] > 0;
+    }
+    DagPlan plan = any ? dag_build_tasks(std::vector<int>((size_t)B, P), workers, 0, 0, 0, 0, first) : dag_build_tasks(B, P, workers);
+    *n_tasks = (long long)plan.tasks.size();
+    if (n_slots) *n_slots = plan.n_slots;
+    if (n_ctrs) *n_ctrs = plan.n_ctrs;
+    if (queue_first) memcpy(queue_first, plan.queues.first, sizeof plan.queues.first);
+    if (out) {
+        const long long n = max_tasks < *n_tasks ? max_tasks : *n_tasks;
+        memcpy(out, plan.tasks.data(), sizeof(DagTask) * n);
+    }
+    return 0;
+}
+
+// Pure host function, the twin of the upload-side kernels (sky_kernels.hpp, same routines): the permutation and the
+// union skyline of a batch lwl (B, c, N), gp (B, 2c).  perm_out (N), first_out (ceil(N / 128)); either may be null.
+extern "C" int psoap_sky_first(int c, int N, int B, const double* lwl, const double* gp, int* first_out, int* perm_out)
+{
+    if (c < 1 || c > 3 || N < 1 || B < 1 || !lwl || !gp) FAIL("psoap_sky_first: bad arguments");
+    const int P = round_up(N, NB) / NB;
+    std::vector<int> perm((size_t)N), first((size_t)P, 0);
+    for (int i = 0; i < N; ++i) perm[i] = i;
+    if (N <= SKY_MAX_N) {
+        std::stable_sort(perm.begin(), perm.end(), [lwl](int a, int b) { return sky_key(lwl[a]) < sky_key(lwl[b]); });
+        std::vector<double> x((size_t)c * N), lo((size_t)c * P), hi((size_t)c * P);
+        std::vector<int> fb((size_t)P);
+        for (int b = 0; b < B; ++b) {
+            for (int k = 0; k < c; ++k)
+                for (int r = 0; r < N; ++r) x[(size_t)k * N + r] = lwl[((size_t)b * c + k) * N + perm[r]];
+            for (int k = 0; k < c; ++k)
+                for (int t = 0; t < P; ++t)
+                    sky_interval(x.data() + (size_t)k * N, t * NB, (t + 1) * NB < N ? (t + 1) * NB : N, &lo[(size_t)k * P + t],
+                                 &hi[(size_t)k * P + t]);
+            double p2[3] = {0.0, 0.0, 0.0};
+            const bool ok = sky_gp(gp + (size_t)b * 2 * c, c, p2);
+            for (int j = 0; j < P; ++j) fb[j] = sky_first_raw(j, P, c, lo.data(), hi.data(), p2, ok);
+            sky_first_finish(fb.data(), P);
+            for (int j = 0; j < P; ++j) first[j] = (b == 0 || fb[j] < first[j]) ? fb[j] : first[j];
+        }
+    }
+    if (perm_out) memcpy(perm_out, perm.data(), sizeof(int) * (size_t)N);
+    if (first_out) memcpy(first_out, first.data(), sizeof(int) * (size_t)P);
+    return 0;
+}
+
+// The skyline of the handle's last evaluation: out[0 .. n) of { tiles planned, tiles dense, tile-GEMM units planned, units
+// dense, plan builds so far, plan-cache hits so far, 1 if the evaluation read the slot's skyline }.
+extern "C" int psoap_chunk_sky_stats(psoap_chunk* h, long long* out, int n)
+{
+    if (!h || !out || n < 0) FAIL("psoap_chunk_sky_stats: bad arguments");
+    for (int i = 0; i < n && i < 7; ++i) out[i] = h->sky_stats[i];
+    return 7;
 }
 
 // Pure host function: the task list every lane of a stream of `lanes` lanes runs for matrices of P block rows
@@ -1110,9 +1224,29 @@ static int clear_too_fast(psoap_chunk* h, BatchSlot& sl)
     return 0;
 }
 
+// a batch of B matrices of this handle would read a skyline: the persistent kernel's throughput scheme, not the fixed plan
+static bool sky_batch(const psoap_chunk* h, int B)
+{
+    return h->mode == 1 && h->P <= 255 && !dag_fixed_plan() && dag_lnlike_scheme(std::vector<int>((size_t)B, h->P)) == 0;
+}
+
 static int upload_end(psoap_chunk* h, BatchSlot& sl)
 {
     HIP_TRY(hipMemcpyAsync(sl.dGp, h->hGp, sizeof(double) * (size_t)sl.B * 2 * sl.C, hipMemcpyHostToDevice, h->copy));
+    // the slot's sorted layout and its skyline (sky_kernels.hpp): functions of the slot's contents alone -- for a batch that
+    // can take the throughput scheme of the persistent kernel; no other evaluation reads them, and a kernel on this stream
+    // waits for a running persistent launch to leave
+    sl.sky_valid = h->sky && sky_batch(h, sl.B);
+    if (sl.sky_valid) {
+        const int N = h->N, rows = sl.B * sl.C;
+        hipStream_t s = h->copy;
+        hipLaunchKernelGGL(k_sky_perm, dim3((N + 255) / 256), dim3(256), 0, s, sl.dLwl, N, sl.dPerm);
+        hipLaunchKernelGGL(k_sky_gather, dim3((N + 255) / 256, rows + 2), dim3(256), 0, s, sl.dPerm, N, rows, sl.dLwl, sl.dLwlS,
+                           h->dFl, sl.dFlS, h->dSigma, sl.dSigmaS);
+        hipLaunchKernelGGL(k_sky_first, dim3(sl.B), dim3(256), 0, s, sl.dLwlS, sl.dGp, sl.C, N, h->P, sl.dFirstB);
+        hipLaunchKernelGGL(k_sky_union, dim3(1), dim3(64), 0, s, sl.dFirstB, sl.B, h->P, sl.hFirst);
+        HIP_TRY(hipGetLastError());
+    }
     HIP_TRY(hipEventRecord(h->evStaging, h->copy));
     HIP_TRY(hipEventRecord(sl.evUpload, h->copy));
     return 0;
@@ -1272,16 +1406,17 @@ static void launch_fill(psoap_chunk* h, const BatchSlot& sl, hipStream_t s, int 
 }
 
 // per-matrix records of a slot's batch (uniform: every matrix shares N, fl, sigma)
-static void fill_mats(const psoap_chunk* h, const BatchSlot& sl, DagMat* out)
+// (sorted: for an evaluation inside the slot's skyline, the sorted copies; everything else reads the upload's order)
+static void fill_mats(const psoap_chunk* h, const BatchSlot& sl, DagMat* out, bool sorted)
 {
     for (int b = 0; b < sl.B; ++b) {
         DagMat m{};
         m.K = h->dK + (size_t)b * h->mat_stride;
         m.R = h->dR + (size_t)b * h->Npad;
         m.Wt = h->dWt + (size_t)b * WT_STRIDE;
-        m.lw = sl.dLwl + (size_t)b * sl.C * h->N;
+        m.lw = (sorted ? sl.dLwlS : sl.dLwl) + (size_t)b * sl.C * h->N;
         m.gp = sl.dGp + (size_t)b * 2 * sl.C;
-        m.sigma = h->dSigma;
+        m.sigma = sorted ? sl.dSigmaS : h->dSigma;
         m.acc = h->dAcc + (size_t)b * ACC_ROWS;
         m.N = h->N;
         m.Npad = h->Npad;
@@ -1306,11 +1441,12 @@ static int promote_slot(psoap_chunk* h, const char* who)
 }
 
 // the slot's per-matrix records on the device: written once per (slot, B, C)
-static int ensure_slot_mats(psoap_chunk* h, BatchSlot& sl)
+static int ensure_slot_mats(psoap_chunk* h, BatchSlot& sl, bool sorted = false)
 {
-    if (sl.mats_B == sl.B && sl.mats_C == sl.C) return 0;
+    if (sl.mats_B == sl.B && sl.mats_C == sl.C && sl.mats_sorted == sorted) return 0;
     std::vector<DagMat> mats(sl.B);
-    fill_mats(h, sl, mats.data());
+    fill_mats(h, sl, mats.data(), sorted);
+    sl.mats_sorted = sorted;
     HIP_TRY(hipStreamSynchronize(h->streams[0]));   // an earlier launch may still read the records
     HIP_TRY(hipMemcpy(sl.dMats, mats.data(), sizeof(DagMat) * sl.B, hipMemcpyHostToDevice));
     sl.mats_B = sl.B;
@@ -1322,14 +1458,77 @@ static int ensure_slot_mats(psoap_chunk* h, BatchSlot& sl)
 static int dag_prepare(psoap_chunk* h)
 {
     BatchSlot& sl = h->slot[h->act];
-    if (int rc = ensure_slot_mats(h, sl)) return rc;
-    if (h->plan_B == sl.B) return 0;
     if (h->P > 255) FAIL("N too large for the persistent kernel's 8-bit block-row indices (N <= 32640)");
-    HIP_TRY(hipStreamSynchronize(h->streams[0]));
-    const DagPlan plan = dag_lnlike_plan(std::vector<int>((size_t)sl.B, h->P), h->n_cus, h->dag_grid, &h->plan_workers);
+    const int B = sl.B, P = h->P;
+    const std::vector<int> Ps((size_t)B, P);
+    // The skyline of the slot (throughput scheme only): the upload that computed it was queued an evaluation ago.
+    std::vector<int> first;      // empty: dense
+    const bool sky_on = h->sky && sl.sky_valid && sky_batch(h, B);
+    if (sky_on) {
+        HIP_TRY(hipEventSynchronize(sl.evUpload));
+        bool any = false;
+        for (int j = 0; j < P; ++j) {
+            const int f = sl.hFirst[j];
+            // (what the planner relies on, checked: a list built from anything else could name a tile nobody writes)
+            if (f < 0 || f > (j > 0 ? j - 1 : 0) || (j > 0 && f < sl.hFirst[j - 1])) FAIL("psoap_batch_eval: the slot's skyline is not a monotone envelope");
+            any = any || f > 0;
+        }
+        if (any) first.assign(sl.hFirst, sl.hFirst + P);
+    }
+    // (a proper skyline: the evaluation reads the slot's sorted copies; a dense one the upload's order, as ever)
+    if (int rc = ensure_slot_mats(h, sl, !first.empty())) return rc;
+    long long units_dense = 0;
+    for (int q = 0; q < P; ++q) units_dense += (long long)q * (P - q);
+    h->sky_stats[1] = (long long)B * P * (P + 1) / 2;
+    h->sky_stats[3] = (long long)B * units_dense;
+    h->sky_stats[6] = sky_on ? 1 : 0;
+    auto report = [h] {
+        const bool dense = h->plan_first.empty();
+        h->sky_stats[0] = dense ? h->sky_stats[1] : h->plan_work.tiles;
+        h->sky_stats[2] = dense ? h->sky_stats[3] : h->plan_work.units;
+    };
+    if (h->plan_B == B && h->plan_first == first) {
+        if (!first.empty()) h->sky_stats[5] += 1;      // (a skyline list, still loaded)
+        report();
+        return 0;
+    }
     h->plan_B = 0;      // (until the workspace holds the new list)
-    HIP_TRY(h->dag.load(plan, (size_t)h->max_batch));
-    h->plan_B = sl.B;
+    if (first.empty()) {
+        HIP_TRY(hipStreamSynchronize(h->streams[0]));
+        const DagPlan plan = dag_lnlike_plan(Ps, h->n_cus, h->dag_grid, &h->plan_workers);
+        h->sky_stats[4] += 1;
+        HIP_TRY(h->dag.load(plan, (size_t)h->max_batch));
+    } else {
+        size_t at = 0;
+        while (at < h->sky_cache.size() && !(h->sky_cache[at].B == B && h->sky_cache[at].first == first)) ++at;
+        if (at == h->sky_cache.size()) {
+            psoap_chunk::SkyPlan e;
+            e.B = B;
+            e.first = first;
+            e.plan = dag_lnlike_plan_sky(B, P, first.data(), h->n_cus, h->dag_grid, &e.workers);
+            e.work = dag_plan_work(e.plan);
+            e.dTasks.reset(new Grow<DagTask>());
+            HIP_TRY(e.dTasks->need(e.plan.tasks.size()));
+            HIP_TRY(hipMemcpy(e.dTasks->p, e.plan.tasks.data(), sizeof(DagTask) * e.plan.tasks.size(), hipMemcpyHostToDevice));
+            h->sky_stats[4] += 1;
+            if (h->sky_cache.size() >= 4) {
+                HIP_TRY(hipStreamSynchronize(h->streams[0]));      // (a copy out of the evicted list may still be queued)
+                h->sky_cache.pop_back();
+            }
+            h->sky_cache.insert(h->sky_cache.begin(), std::move(e));
+            at = 0;
+        } else {
+            h->sky_stats[5] += 1;
+        }
+        const psoap_chunk::SkyPlan& e = h->sky_cache[at];
+        h->plan_workers = e.workers;
+        h->plan_work = e.work;
+        // (the list is resident: a device-to-device copy behind the previous launch, no wait on the host)
+        HIP_TRY(h->dag.load(e.plan, (size_t)h->max_batch, e.dTasks->p, h->streams[0]));
+    }
+    h->plan_first = first;
+    h->plan_B = B;
+    report();
     return 0;
 }
 
@@ -1379,8 +1578,8 @@ static int eval_dag(psoap_chunk* h)
     HIP_TRY(hipStreamWaitEvent(s, sl.evUpload, 0));
     // no fill kernel: the DAG kernel evaluates the covariance tiles on the fly (dag_store_updated)
     if (prof_begin(h, s, PSOAP_K_MISC, 0.0, 0.0)) return 1;
-    hipLaunchKernelGGL(k_init_rhs, dim3((h->Npad + 255) / 256, B), dim3(256), 0, s, h->dR, h->Npad, N, h->dFl,
-                       sl.mu, h->dAcc);
+    hipLaunchKernelGGL(k_init_rhs, dim3((h->Npad + 255) / 256, B), dim3(256), 0, s, h->dR, h->Npad, N,
+                       h->plan_first.empty() ? h->dFl : sl.dFlS, sl.mu, h->dAcc);
     HIP_TRY(hipGetLastError());
     // (flags, arrival counters and -- behind them -- the taken bitmap of the ready-only hand-out: one memset)
     HIP_TRY(hipMemsetAsync(h->dag.ctl, 0, h->dag.ctl_bytes, s));
@@ -1400,7 +1599,8 @@ static int eval_dag(psoap_chunk* h)
     // executed MFMA flops: left-looking updates + strip solves, full 128^3 tiles
     double fl = 0.0;
     for (int q = 0; q < P; ++q) fl += 2.0 * NB * NB * ((double)q * NB * (P - q) + (double)NB * (P - q - 1));
-    if (prof_begin(h, s, PSOAP_K_DAG, fl * B, 0.0)) return 1;
+    // (inside a skyline: the flops of the list that runs)
+    if (prof_begin(h, s, PSOAP_K_DAG, h->plan_first.empty() ? fl * B : h->plan_work.flops, 0.0)) return 1;
     launch_lnlike(h, h->dag, h->plan_workers, C, sl.dMats, B, P, s, h->dTlog);
     HIP_TRY(hipGetLastError());
     if (prof_end(h, s)) return 1;
