@@ -115,6 +115,34 @@ int psoap_lnlike(psoap_chunk *h, int c, const double *lwl, const double *gp,
 int psoap_lnlike_batch(psoap_chunk *h, int B, int c, const double *lwl,
                        const double *gp, double mu_GP, double *out);
 
+/* ---- gradient of lnlike -------------------------------------------------------
+ * Value and analytic gradient for B proposals: lwl (B, c, N), gp (B, 2c) as for
+ * psoap_lnlike_batch; B is NOT bound by max_batch.
+ *   lnp      (B)       the value, summed in the order of the staged path (a few ulp
+ *                      from psoap_lnlike, which may run another scheme);
+ *   grad_gp  (B, 2c)   d lnp / d (amp_0, l_0, amp_1, l_1, ...);
+ *   grad_lwl (B, c, N) d lnp / d lwl[c][i]; may be NULL;
+ *   grad_mu  (B)       d lnp / d mu_GP; may be NULL.
+ * With alpha = K^-1 r and Q = alpha alpha^T - K^-1 the gradient is 1/2 sum_ij Q_ij
+ * dK_ij; the staged factorisation runs on [K | I], which leaves W = U^-T beside the
+ * factor (K^-1 = W^T W), and one fused kernel contracts the tiles of Q with the
+ * covariance derivatives without ever storing K^-1 (csrc/grad_kernels.hpp; N^3
+ * flops in all).  No atomics: the same arguments give the same bits, alone or in
+ * any batch.
+ * Conventions: a negative hyper-parameter or a matrix that is not positive
+ * definite gives lnp = -inf and NaN in every gradient entry of that proposal; the
+ * status is non-zero for runtime errors only.
+ * Workspace: 16 Npad^2 bytes per matrix (Npad = N rounded up to 128), allocated by
+ * the first call, kept with the handle and freed by psoap_chunk_grad_release or
+ * psoap_chunk_destroy.  The proposals are walked in groups of at most 8 matrices
+ * and at most 1 GiB of that storage (never less than one matrix), so the
+ * workspace does not grow with B.  The handle's uploaded batches, their results
+ * and the likelihood workspaces are left as they are. */
+int psoap_chunk_lnlike_grad(psoap_chunk *h, int B, int c, const double *lwl,
+                            const double *gp, double mu_GP, double *lnp,
+                            double *grad_gp, double *grad_lwl, double *grad_mu);
+int psoap_chunk_grad_release(psoap_chunk *h);
+
 /* Split-phase form of psoap_lnlike_batch: upload (H2D, async, on a copy stream of
  * its own), eval (kernels only, async), fetch (sync + D2H of B doubles).
  * A handle holds TWO proposal batches: an upload always goes to the one that is
@@ -272,7 +300,8 @@ enum {
     PSOAP_K_TRSM = 3,
     PSOAP_K_MISC = 4,
     PSOAP_K_DAG = 5,          /* the persistent dependency-graph kernel (whole factorisation) */
-    PSOAP_K_CLASSES = 6
+    PSOAP_K_GRAD = 6,         /* the fused contraction of psoap_chunk_lnlike_grad */
+    PSOAP_K_CLASSES = 7
 };
 typedef struct {
     double ms[PSOAP_K_CLASSES];      /* summed device time per class */

@@ -14,8 +14,8 @@ _ip = ctypes.POINTER(ctypes.c_int)
 _i32p = ctypes.POINTER(ctypes.c_int32)
 _vp = ctypes.c_void_p
 
-K_CLASSES = 6
-K_NAMES = ("fill", "panel_update", "potrf", "trsm", "misc", "dag")
+K_CLASSES = 7
+K_NAMES = ("fill", "panel_update", "potrf", "trsm", "misc", "dag", "grad_contract")
 
 
 class Timings(ctypes.Structure):
@@ -50,6 +50,8 @@ SIGNATURES = {
     "psoap_chunk_set_grid": (ctypes.c_int, [_vp, _dp, _i32p, ctypes.c_int]),
     "psoap_lnlike": (ctypes.c_int, [_vp, ctypes.c_int, _dp, _dp, ctypes.c_double, _dp]),
     "psoap_lnlike_batch": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _dp, _dp, ctypes.c_double, _dp]),
+    "psoap_chunk_lnlike_grad": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _dp, _dp, ctypes.c_double, _dp, _dp, _dp, _dp]),
+    "psoap_chunk_grad_release": (ctypes.c_int, [_vp]),
     "psoap_batch_upload": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _dp, _dp, ctypes.c_double]),
     "psoap_batch_upload_velocities": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _dp, _dp, ctypes.c_double]),
     "psoap_chunk_set_dates": (ctypes.c_int, [_vp, _dp, ctypes.c_int]),

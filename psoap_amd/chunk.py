@@ -97,6 +97,32 @@ class ChunkHandle:
               "psoap_lnlike_batch")
         return out
 
+    def lnlike_grad(self, lwls, gp, mu_GP: float = 1.0):
+        """Value and analytic gradient of the likelihood (include/psoap_gp.h: psoap_chunk_lnlike_grad).
+
+        ``lwls`` (c, N) with ``gp`` (2c,) -> ``(lnp, grad_gp (2c,), grad_lwl (c, N), grad_mu)``; ``lwls`` (B, c, N) with
+        ``gp`` (B, 2c) -> the same with a leading axis of B (any B: the proposals are walked in groups through a bounded
+        workspace).  A negative hyper-parameter or a matrix that is not positive definite gives ``-inf`` and NaN gradients."""
+        lwls = as_f64(lwls)
+        single = lwls.ndim <= 2
+        if single:
+            lwls = np.atleast_2d(lwls)[None]
+        if lwls.ndim != 3 or lwls.shape[2] != self.N:
+            raise ValueError("lwls must have shape (c, N) or (B, c, N)")
+        B, c, _ = lwls.shape
+        lwls = as_f64(lwls, (B, c, self.N))
+        gps = as_f64(np.atleast_2d(as_f64(gp)), (B, 2 * c))
+        lnp, g_gp, g_lwl, g_mu = np.empty(B), np.empty((B, 2 * c)), np.empty((B, c, self.N)), np.empty(B)
+        check(self._L.psoap_chunk_lnlike_grad(self._h, B, c, dptr(lwls), dptr(gps), float(mu_GP), dptr(lnp), dptr(g_gp),
+                                              dptr(g_lwl), dptr(g_mu)), "psoap_chunk_lnlike_grad")
+        if single:
+            return float(lnp[0]), g_gp[0], g_lwl[0], float(g_mu[0])
+        return lnp, g_gp, g_lwl, g_mu
+
+    def grad_release(self):
+        """Free the gradient workspace (16 Npad^2 bytes per matrix of a group); the next ``lnlike_grad`` allocates it again."""
+        check(self._L.psoap_chunk_grad_release(self._h), "psoap_chunk_grad_release")
+
     def upload(self, lwls, gps, mu_GP: float = 1.0):
         lwls = as_f64(lwls)
         B, c, _ = lwls.shape

@@ -250,6 +250,75 @@ def optimize_GP_f(wl_known, fl_known, sigma_known, amp_f, l_f, mu_GP=1.0):
     return minimize(func, np.array([amp_f, l_f]), method="Nelder-Mead")["x"]
 
 
+# ---- gradient of the likelihood (not in the reference) ----------------------------------------------
+def lnlike_grad(lwls, fl, sigma, gp, mu_GP=1.0):
+    """``(lnp, grad_gp (2c,), grad_lwl (c, N), grad_mu)``: the value of ``lnlike_f`` / ``lnlike_f_g`` / ``lnlike_f_g_h`` (by the
+    number of rows of ``lwls``) and its analytic derivatives with respect to ``gp = (amp_0, l_0, ...)``, every rest-frame
+    ln-wavelength and ``mu_GP``, evaluated on the device (``ChunkHandle.lnlike_grad``).
+
+    Degenerate input follows ``_lnlike``: a negative hyper-parameter gives ``-inf`` with NaN gradients before any work,
+    ``l == 0`` raises ``ZeroDivisionError``, a non-finite matrix raises ``ValueError``; a matrix that is not positive definite
+    gives ``-inf`` with NaN gradients."""
+    gp = [float(g) for g in gp]
+    lw = np.stack([as_f64(w) for w in np.atleast_2d(lwls)])
+    if len(gp) != 2 * lw.shape[0]:
+        raise ValueError(f"gp must hold {2 * lw.shape[0]} values for {lw.shape[0]} component(s)")
+    if any(g < 0.0 for g in gp):
+        return -np.inf, np.full(len(gp), np.nan), np.full(lw.shape, np.nan), np.nan
+    if any(l == 0.0 for l in gp[1::2]):
+        raise ZeroDivisionError("float division")
+    if not _matrix_is_finite(lw, sigma, gp):
+        raise ValueError(_NONFINITE)
+    h = _chunk_for(fl, sigma)
+    if not hasattr(h, "lnlike_grad"):
+        raise _lib.PsoapError("lnlike_grad needs the device in this process (PSOAP_GPU_SERVER serves values only)")
+    lnp, g_gp, g_lwl, g_mu = h.lnlike_grad(lw, gp, mu_GP)
+    if not np.isneginf(lnp) and not (np.all(np.isfinite(np.asarray(fl, dtype=np.float64))) and np.isfinite(mu_GP)):
+        raise ValueError(_NONFINITE)
+    return np.float64(lnp), g_gp, g_lwl, np.float64(g_mu)
+
+
+def velocity_gradient(grad_lwl, epoch_index, n_epochs):
+    """``dlnL/dv[c, e]`` from ``dlnL/dlwl[c, i]``: the rest-frame grids are ``lwl - v[c, epoch]/c_kms``
+    (``data.replicate_wls``), so ``dlnL/dv[c, e] = -(1/c_kms) sum_{i in epoch e} dlnL/dlwl[c, i]``.
+    ``grad_lwl`` (c, N) or (B, c, N); ``epoch_index`` (N,) as from ``data.epoch_index_of``; -> (c, n_epochs) or (B, c, n_epochs)."""
+    from .data import c_kms
+    g = np.asarray(grad_lwl, dtype=np.float64)
+    ep = np.asarray(epoch_index)
+    if ep.shape != g.shape[-1:]:
+        raise ValueError("epoch_index must have one entry per pixel")
+    if ep.size and (ep.min() < 0 or ep.max() >= n_epochs):
+        raise ValueError("epoch index out of range")
+    flat = g.reshape(-1, g.shape[-1])
+    out = np.zeros((flat.shape[0], int(n_epochs)))
+    for k, row in enumerate(flat):
+        out[k] = np.bincount(ep, weights=row, minlength=int(n_epochs))
+    return (-out / c_kms).reshape(g.shape[:-1] + (int(n_epochs),))
+
+
+GP_LOWER_BOUND = 1e-6       # optimize_GP keeps every amplitude and length scale at or above this
+
+
+def optimize_GP(lwls, fl, sigma, gp0, mu_GP=1.0, ftol=1e-10, full_output=False):
+    """L-BFGS-B fit of the ``2c`` hyper-parameters ``(amp_0, l_0, ...)`` to one chunk from ``gp0``, with the analytic
+    gradient (``lnlike_grad``, ``jac=True``) and every parameter bounded below at ``GP_LOWER_BOUND``.  Returns the fitted
+    vector, or SciPy's whole result with ``full_output`` (``-result.fun`` is the likelihood reached, ``result.jac`` the
+    gradient of ``-lnL`` there).  ``optimize_GP_f`` is the reference's derivative-free fit."""
+    from scipy.optimize import minimize
+    lw = np.stack([as_f64(w) for w in np.atleast_2d(lwls)])
+    x0 = np.maximum(as_f64(gp0, (2 * lw.shape[0],)), GP_LOWER_BOUND)
+
+    def func(x):
+        lnp, g_gp, _g_lwl, _g_mu = lnlike_grad(lw, fl, sigma, x, mu_GP)
+        if not np.isfinite(lnp):
+            return np.inf, np.zeros_like(x)
+        return -lnp, -g_gp
+
+    res = minimize(func, x0, jac=True, method="L-BFGS-B", bounds=[(GP_LOWER_BOUND, None)] * x0.size,
+                   options={"ftol": ftol})
+    return res if full_output else res["x"]
+
+
 # ---- calibration (SURVEY.md 8(f) f-4) ---------------------------------------------------------------
 _CAL_FAIL = {1: "reference-epoch covariance B", 2: "conditional covariance C'", 3: "Chebyshev normal equations"}
 

@@ -36,6 +36,7 @@
 #include "orbit_kernels.hpp"
 #include "predict_kernels.hpp"
 #include "calibrate_kernels.hpp"
+#include "grad_kernels.hpp"
 
 using namespace psoap;
 
@@ -538,7 +539,7 @@ struct BatchSlot {
     hipEvent_t evEval = nullptr;     // compute stream: last evaluation that read this slot complete
 };
 
-namespace psoap { struct PredictWs; }
+namespace psoap { struct PredictWs; struct GradWs; }
 
 // Streamed evaluation (dag_kernel.hpp, "Streamed evaluation"): one resident launch of the persistent kernel, matrices
 // come and go through `lanes` workspaces of the handle.  Host side: lane allocation, the submission ring in pinned
@@ -655,6 +656,8 @@ struct psoap_chunk {
     psoap_timings last = {};
     // predict workspace (grow-only; psoap_chunk_predict)
     psoap::PredictWs* pws = nullptr;
+    // gradient workspace (allocated by the first psoap_chunk_lnlike_grad; psoap_chunk_grad_release)
+    psoap::GradWs* gws = nullptr;
     // streamed evaluation (psoap_stream_*)
     StreamState stream;
     bool dev_locked = false;     // this handle holds a reference on the device's inter-process lock (device_lock_acquire)
@@ -733,6 +736,7 @@ static int configure_kernels(int device)
     HIP_TRY((dag_set_lds<false, false>()));     // the likelihood's k_chol_dag forms
     HIP_TRY((dag_set_lds<false, true>()));      // the stream's
     HIP_TRY(predict_configure_kernels());
+    HIP_TRY(grad_configure_kernels());
     if (done.size() <= (size_t)device) done.resize((size_t)device + 1, 0);
     done[device] = 1;
     return 0;
@@ -893,6 +897,7 @@ extern "C" int psoap_chunk_destroy(psoap_chunk* h)
     if (h->evLast) (void)hipEventDestroy(h->evLast);
     for (auto e : h->evPool) (void)hipEventDestroy(e);
     delete h->pws;
+    delete h->gws;
     delete h;
     return 0;
 }
@@ -2625,6 +2630,145 @@ extern "C" int psoap_lnlike_batch(psoap_chunk* h, int B, int c, const double* lw
 extern "C" int psoap_lnlike(psoap_chunk* h, int c, const double* lwl, const double* gp, double mu_GP, double* out)
 {
     return psoap_lnlike_batch(h, 1, c, lwl, gp, mu_GP, out);
+}
+
+// ---- gradient of the likelihood (grad_kernels.hpp) ------------------------------------------------
+// The staged factorisation of [K | I] per group of matrices, alpha = W^T z, the fused contraction, the finishing sums.
+// Everything lives in the handle's gradient workspace and runs on the handle's first stream behind whatever the handle
+// has in flight: neither the proposal slots nor the workspaces of the likelihood paths are touched.
+template <int C>
+static void launch_grad_fill_contract(bool contract, hipStream_t s, int nb, int ntiles, double* A, size_t mstride, int ld, int N,
+                                      int Npad, int P, const double* dLwl, const double* dGp, const double* dSigma,
+                                      const double* dAlpha, double* dPart)
+{
+    if (!contract)
+        hipLaunchKernelGGL(k_fill_sym<C>, dim3(ntiles, nb), dim3(256), 0, s, A, mstride, ld, N, P, dLwl, dGp, dSigma, 1);
+    else
+        hipLaunchKernelGGL(k_grad_contract<C>, dim3(ntiles, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)A, mstride,
+                           ld, N, Npad, P, dLwl, dGp, dAlpha, dPart);
+}
+
+extern "C" int psoap_chunk_lnlike_grad(psoap_chunk* h, int B, int c, const double* lwl, const double* gp, double mu_GP,
+                                       double* lnp, double* grad_gp, double* grad_lwl, double* grad_mu)
+{
+    if (!h || !lwl || !gp || !lnp || !grad_gp) FAIL("psoap_chunk_lnlike_grad: bad arguments");
+    if (B < 1) FAIL("psoap_chunk_lnlike_grad: B must be at least 1");
+    if (c < 1 || c > 3) FAIL("number of components must be 1, 2 or 3");
+    if (h->stream.open) FAIL("psoap_chunk_lnlike_grad: the handle has an open stream (psoap_stream_close first)");
+    DEVICE_SCOPE(h->device);
+    if (int rc = enter_device(h->device)) return rc;
+    const int N = h->N, Npad = h->Npad, P = h->P, ld = 2 * h->Npad;
+    const size_t mstride = (size_t)Npad * ld;
+    const int G = grad_group_size(B, Npad);
+    const int ntiles = P * (P + 1) / 2, nslab = (Npad + 255) / 256;
+    if (!h->gws) h->gws = new GradWs();
+    GradWs& w = *h->gws;
+    HIP_TRY(w.A.need((size_t)G * mstride));
+    HIP_TRY(w.Wt.need((size_t)G * NB * NB));
+    HIP_TRY(w.R.need((size_t)G * Npad));
+    HIP_TRY(w.Acc.need((size_t)G * ACC_ROWS));
+    HIP_TRY(w.Lwl.need((size_t)G * 3 * N));
+    HIP_TRY(w.Gp.need((size_t)G * 6));
+    HIP_TRY(w.Alpha.need((size_t)G * Npad));
+    HIP_TRY(w.APart.need((size_t)G * nslab * Npad));
+    HIP_TRY(w.Part.need((size_t)G * ntiles * GRAD_TILE_DOUBLES));
+    HIP_TRY(w.Out.need(G));
+    HIP_TRY(w.GradGp.need((size_t)G * 6));
+    HIP_TRY(w.GradX.need((size_t)G * 3 * N));
+    HIP_TRY(w.GradMu.need(G));
+    hipStream_t s = h->streams[0];
+    h->recs.clear();
+    const double tile_flops = 2.0 * NB * NB * (double)NB;
+    for (int b0 = 0; b0 < B; b0 += G) {
+        const int nb = (B - b0 < G) ? B - b0 : G;
+        HIP_TRY(hipMemcpyAsync(w.Lwl, lwl + (size_t)b0 * c * N, sizeof(double) * (size_t)nb * c * N, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(w.Gp, gp + (size_t)b0 * 2 * c, sizeof(double) * (size_t)nb * 2 * c, hipMemcpyHostToDevice, s));
+        if (prof_begin(h, s, PSOAP_K_FILL, 0.0, (double)nb * 12.0 * N * (N + 1.0))) return 1;
+        if (c == 1) launch_grad_fill_contract<1>(false, s, nb, ntiles, w.A, mstride, ld, N, Npad, P, w.Lwl, w.Gp, h->dSigma, nullptr, nullptr);
+        else if (c == 2) launch_grad_fill_contract<2>(false, s, nb, ntiles, w.A, mstride, ld, N, Npad, P, w.Lwl, w.Gp, h->dSigma, nullptr, nullptr);
+        else launch_grad_fill_contract<3>(false, s, nb, ntiles, w.A, mstride, ld, N, Npad, P, w.Lwl, w.Gp, h->dSigma, nullptr, nullptr);
+        hipLaunchKernelGGL(k_grad_init, dim3(ntiles, nb), dim3(256), 0, s, w.A.p, mstride, ld, Npad, P);
+        HIP_TRY(hipGetLastError());
+        if (prof_end(h, s)) return 1;
+        if (prof_begin(h, s, PSOAP_K_MISC, 0.0, 0.0)) return 1;
+        hipLaunchKernelGGL(k_init_rhs, dim3((Npad + 255) / 256, nb), dim3(256), 0, s, w.R.p, Npad, N, h->dFl, mu_GP, w.Acc.p);
+        HIP_TRY(hipGetLastError());
+        if (prof_end(h, s)) return 1;
+        // block row p: tile columns p .. P + p -- the rest of K's row and the appended tiles j <= p
+        for (int p = 0; p < P; ++p) {
+            const int k0 = p * NB;
+            if (p > 0) {
+                const double units = (double)p * (P - p) + 0.5 * p * (p + 1.0);
+                if (prof_begin(h, s, PSOAP_K_PANEL_UPDATE, tile_flops * units * nb, 0.0)) return 1;
+                hipLaunchKernelGGL(k_grad_panel_update, dim3(P + 1, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, w.A.p, mstride, ld, k0, P);
+                HIP_TRY(hipGetLastError());
+                if (prof_end(h, s)) return 1;
+            }
+            if (prof_begin(h, s, PSOAP_K_POTRF, 0.0, 0.0)) return 1;
+            hipLaunchKernelGGL(k_potrf_diag, dim3(nb), dim3(512), 0, s, w.A.p, mstride, ld, k0, w.Wt.p, w.R.p, Npad, w.Acc.p,
+                               (size_t)NB * NB);
+            HIP_TRY(hipGetLastError());
+            if (prof_end(h, s)) return 1;
+            if (prof_begin(h, s, PSOAP_K_TRSM, tile_flops * P * nb, 0.0)) return 1;
+            hipLaunchKernelGGL(k_trsm_strip, dim3(P, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, w.A.p, mstride, ld, k0,
+                               (const double*)w.Wt.p, w.R.p, Npad, (size_t)NB * NB);
+            HIP_TRY(hipGetLastError());
+            if (prof_end(h, s)) return 1;
+        }
+        if (prof_begin(h, s, PSOAP_K_MISC, 0.0, 0.0)) return 1;
+        hipLaunchKernelGGL(k_finalize, dim3((nb + 63) / 64), dim3(64), 0, s, (const MatAcc*)w.Acc.p, w.Out.p, nb, (const int*)nullptr, P);
+        hipLaunchKernelGGL(k_grad_alpha_partial, dim3(P, nslab, nb), dim3(256), 0, s, (const double*)w.A.p, mstride, ld, Npad,
+                           (const double*)w.R.p, w.APart.p, nslab);
+        hipLaunchKernelGGL(k_grad_alpha_finish, dim3((Npad + 255) / 256, nb), dim3(256), 0, s, (const double*)w.APart.p, nslab, Npad,
+                           w.Alpha.p);
+        HIP_TRY(hipGetLastError());
+        if (prof_end(h, s)) return 1;
+        double cunits = 0.0;
+        for (int tj = 0; tj < P; ++tj) cunits += (double)(tj + 1) * (P - tj);
+        if (prof_begin(h, s, PSOAP_K_GRAD, tile_flops * cunits * nb, 0.0)) return 1;
+        if (c == 1) launch_grad_fill_contract<1>(true, s, nb, ntiles, w.A, mstride, ld, N, Npad, P, w.Lwl, w.Gp, nullptr, w.Alpha, w.Part);
+        else if (c == 2) launch_grad_fill_contract<2>(true, s, nb, ntiles, w.A, mstride, ld, N, Npad, P, w.Lwl, w.Gp, nullptr, w.Alpha, w.Part);
+        else launch_grad_fill_contract<3>(true, s, nb, ntiles, w.A, mstride, ld, N, Npad, P, w.Lwl, w.Gp, nullptr, w.Alpha, w.Part);
+        HIP_TRY(hipGetLastError());
+        if (prof_end(h, s)) return 1;
+        if (prof_begin(h, s, PSOAP_K_MISC, 0.0, 0.0)) return 1;
+        hipLaunchKernelGGL(k_grad_finish, dim3(P + 1, nb), dim3(128), 0, s, (const double*)w.Part.p, (const double*)w.Alpha.p,
+                           (const double*)w.Gp.p, c, N, Npad, P, w.GradGp.p, w.GradX.p, w.GradMu.p);
+        HIP_TRY(hipGetLastError());
+        if (prof_end(h, s)) return 1;
+        HIP_TRY(hipMemcpyAsync(lnp + b0, w.Out, sizeof(double) * nb, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(grad_gp + (size_t)b0 * 2 * c, w.GradGp, sizeof(double) * (size_t)nb * 2 * c, hipMemcpyDeviceToHost, s));
+        if (grad_lwl)
+            HIP_TRY(hipMemcpyAsync(grad_lwl + (size_t)b0 * c * N, w.GradX, sizeof(double) * (size_t)nb * c * N, hipMemcpyDeviceToHost, s));
+        if (grad_mu) HIP_TRY(hipMemcpyAsync(grad_mu + b0, w.GradMu, sizeof(double) * nb, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));       // the next group reuses the workspace and the caller's arrays are pageable
+    }
+    if (collect_timings(h)) return 1;
+    // the conventions of the likelihood: a negative hyper-parameter or a matrix that is not positive definite -> -inf,
+    // and no gradient there
+    for (int b = 0; b < B; ++b) {
+        bool neg = false;
+        for (int k = 0; k < 2 * c; ++k) neg = neg || gp[(size_t)b * 2 * c + k] < 0.0;
+        if (neg) lnp[b] = -INFINITY;
+        if (lnp[b] == -INFINITY) {
+            for (int k = 0; k < 2 * c; ++k) grad_gp[(size_t)b * 2 * c + k] = NAN;
+            if (grad_lwl)
+                for (size_t k = 0; k < (size_t)c * N; ++k) grad_lwl[(size_t)b * c * N + k] = NAN;
+            if (grad_mu) grad_mu[b] = NAN;
+        }
+    }
+    return 0;
+}
+
+extern "C" int psoap_chunk_grad_release(psoap_chunk* h)
+{
+    if (!h) FAIL("null handle");
+    DEVICE_SCOPE(h->device);
+    if (set_dev(h)) return 1;
+    HIP_TRY(hipStreamSynchronize(h->streams[0]));
+    delete h->gws;
+    h->gws = nullptr;
+    return 0;
 }
 
 // ---- fills (matrix_functions drop-ins) ------------------------------------------------------
