@@ -143,6 +143,44 @@ int psoap_chunk_lnlike_grad(psoap_chunk *h, int B, int c, const double *lwl,
                             double *grad_gp, double *grad_lwl, double *grad_mu);
 int psoap_chunk_grad_release(psoap_chunk *h);
 
+/* ---- gradient of lnprob(p): through the Kepler solve and the Doppler shift ----------
+ * B proposals as for psoap_batch_upload_orbits (needs set_grid + set_dates); B is NOT
+ * bound by max_batch.
+ *   lnp      (B)               the value psoap_chunk_lnlike_grad gives on the grids
+ *                              that psoap_orbit_velocities and the Doppler shift make;
+ *   grad_orb (B, n_orb)        d lnp / d p_orb, registered order up to gamma;
+ *   grad_gp  (B, 2c)           as for psoap_chunk_lnlike_grad;
+ *   grad_vel (B, c, n_epochs)  d lnp / d v[c][epoch]; may be NULL;
+ *   grad_mu  (B)               may be NULL.
+ * Per group of matrices one kernel evaluates the velocities (the arithmetic and the
+ * bits of psoap_orbit_velocities) and their Jacobian at the same converged E, by
+ * implicit differentiation of Kepler's equation (csrc/orbit_grad_kernels.hpp); the
+ * grids are shifted on the device, the gradient above runs untouched, and two small
+ * kernels fold d lnp / d lwl over the pixels of every epoch
+ * (grad_vel = -1/c_kms * the sum over the epoch's pixels; 0.0 for an epoch with no
+ * pixel) and contract it with the Jacobian.  The (B, c, N) wavelength gradient never
+ * leaves the device: the host ships n_orb + 2c doubles per proposal and receives
+ * 1 + n_orb + 2c + 1.  No atomics in any sum: the order is fixed by the chunk alone.
+ * Conventions: a proposal with some |v| >= c_kms, a negative hyper-parameter or a
+ * matrix that is not positive definite gives lnp = -inf and NaN in every gradient
+ * entry of that proposal; the other proposals of the batch keep the bits they have
+ * alone; the status is non-zero for runtime errors only (an eccentricity outside
+ * [0, 1) is one, as for psoap_batch_upload_orbits).  An open stream on the handle is
+ * refused.  The workspace is that of psoap_chunk_lnlike_grad plus a few KB per
+ * matrix (psoap_chunk_grad_release frees both), walked in the same groups.  The
+ * handle's uploaded batches, their results and the likelihood workspaces are left
+ * as they are. */
+int psoap_chunk_lnprob_grad(psoap_chunk *h, int B, int model, const double *p_orb,
+                            const double *gp, double mu_GP, double *lnp,
+                            double *grad_orb, double *grad_gp, double *grad_vel,
+                            double *grad_mu);
+/* stand-alone, beside psoap_orbit_velocities: vel_out (B, c, n_dates) with the bits of
+ * psoap_orbit_velocities, jac_out (B, c, n_dates, n_orb) = d v / d p_orb; entries of
+ * parameters a component does not depend on are exact zeros. */
+int psoap_orbit_velocity_jacobian(int device, int model, int B, const double *p_orb,
+                                  int n_dates, const double *dates, double *vel_out,
+                                  double *jac_out);
+
 /* Split-phase form of psoap_lnlike_batch: upload (H2D, async, on a copy stream of
  * its own), eval (kernels only, async), fetch (sync + D2H of B doubles).
  * A handle holds TWO proposal batches: an upload always goes to the one that is

@@ -119,6 +119,28 @@ class ChunkHandle:
             return float(lnp[0]), g_gp[0], g_lwl[0], float(g_mu[0])
         return lnp, g_gp, g_lwl, g_mu
 
+    def lnprob_grad(self, model_id: int, p_orb, gps, mu_GP: float = 1.0, want_vel: bool = False):
+        """Value and gradient of ``lnprob`` through the Kepler solve and the Doppler shift (include/psoap_gp.h:
+        psoap_chunk_lnprob_grad; needs ``set_grid`` and the dates).
+
+        ``p_orb`` (B, n_orb), ``gps`` (B, 2c) -> ``(lnp (B,), grad_orb (B, n_orb), grad_gp (B, 2c), grad_mu (B,))``, with
+        ``grad_vel (B, c, n_epochs)`` appended when ``want_vel``.  A faster-than-light proposal, a negative hyper-parameter
+        or a matrix that is not positive definite gives ``-inf`` and NaN gradients for that proposal."""
+        from .utils import MODEL_ID, N_COMPONENTS, n_params_orb
+        name = {v: k for k, v in MODEL_ID.items()}.get(int(model_id))
+        if name is None:
+            raise ValueError(f"unknown orbit model {model_id}")
+        p_orb = as_f64(np.atleast_2d(p_orb))
+        B, c, n_orb = p_orb.shape[0], N_COMPONENTS[name], n_params_orb[name]
+        p_orb = as_f64(p_orb, (B, n_orb))      # (the library reads exactly that many doubles per proposal)
+        gps = as_f64(np.atleast_2d(as_f64(gps)), (B, 2 * c))
+        lnp, g_orb, g_gp, g_mu = np.empty(B), np.empty((B, n_orb)), np.empty((B, 2 * c)), np.empty(B)
+        g_vel = np.empty((B, c, self.n_epochs)) if want_vel else None
+        check(self._L.psoap_chunk_lnprob_grad(self._h, B, int(model_id), dptr(p_orb), dptr(gps), float(mu_GP), dptr(lnp),
+                                              dptr(g_orb), dptr(g_gp), dptr(g_vel) if want_vel else None, dptr(g_mu)),
+              "psoap_chunk_lnprob_grad")
+        return (lnp, g_orb, g_gp, g_mu, g_vel) if want_vel else (lnp, g_orb, g_gp, g_mu)
+
     def grad_release(self):
         """Free the gradient workspace (16 Npad^2 bytes per matrix of a group); the next ``lnlike_grad`` allocates it again."""
         check(self._L.psoap_chunk_grad_release(self._h), "psoap_chunk_grad_release")

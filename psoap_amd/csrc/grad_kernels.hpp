@@ -322,6 +322,11 @@ inline int grad_group_size(int B, int Npad)
 struct GradWs {
     Grow<double> A, Wt, R, Lwl, Gp, Alpha, APart, Part, Out, GradGp, GradX, GradMu;
     Grow<MatAcc> Acc;
+    // psoap_chunk_lnprob_grad (orbit_grad_kernels.hpp): the group's orbital parameters, velocities, Jacobian, dlnL/dv and
+    // dlnL/dp_orb, its |v| >= c flags, and the pixels of every epoch (valid until the next psoap_chunk_set_grid)
+    Grow<double> Porb, Vel, Jac, Gv, GradOrb;
+    Grow<int> TooFast, EpStart, EpPix;
+    bool epochs_valid = false;
 };
 
 }  // namespace psoap

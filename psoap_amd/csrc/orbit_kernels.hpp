@@ -32,7 +32,8 @@ __host__ __device__ inline int orbit_n_components(int model)
     return (model == ORB_SB1 || model == ORB_ST1) ? 1 : (model == ORB_ST3 ? 3 : 2);
 }
 
-__device__ inline double true_anomaly(double t, double T0, double P, double e)
+// E_out (optional): the converged eccentric anomaly, for the Jacobian of orbit_grad_kernels.hpp
+__device__ inline double true_anomaly(double t, double T0, double P, double e, double* E_out = nullptr)
 {
     const double two_pi = 6.283185307179586476925286766559;
     double tt = fmod(t - T0, P);               // Python's % : result takes the sign of P (> 0 here)
@@ -44,6 +45,7 @@ __device__ inline double true_anomaly(double t, double T0, double P, double e)
         E -= dE;
         if (fabs(dE) <= 1e-16 * fmax(1.0, fabs(E))) break;
     }
+    if (E_out) *E_out = E;
     const double th = 2.0 * atan(sqrt((1.0 + e) / (1.0 - e)) * tan(0.5 * E));
     return (E < 3.14159265358979323846) ? th : th + two_pi;
 }
@@ -56,15 +58,19 @@ __device__ inline double rv_term(double K, double e, double omega_deg, double f)
 }
 
 // velocities of the c components of one proposal at one date (p: its orbit_n_params(model) parameters)
-__device__ inline void orbit_velocities_at(int model, const double* __restrict__ p, double t, double (&v)[3])
+// fE (optional): true and eccentric anomaly of the orbit (SB) or of the inner and the outer orbit: f_in, E_in, f_out, E_out
+__device__ inline void orbit_velocities_at(int model, const double* __restrict__ p, double t, double (&v)[3],
+                                           double* fE = nullptr)
 {
     const int c = orbit_n_components(model);
     v[0] = v[1] = v[2] = 0.0;
     if (model == ORB_SB1) {                       // K, e, omega, P, T0, gamma
-        const double f = true_anomaly(t, p[4], p[3], p[1]);
+        const double f = true_anomaly(t, p[4], p[3], p[1], fE ? fE + 1 : nullptr);
+        if (fE) fE[0] = f;
         v[0] = rv_term(p[0], p[1], p[2], f) + p[5];
     } else if (model == ORB_SB2) {                // q, K, e, omega, P, T0, gamma
-        const double f = true_anomaly(t, p[5], p[4], p[2]);
+        const double f = true_anomaly(t, p[5], p[4], p[2], fE ? fE + 1 : nullptr);
+        if (fE) fE[0] = f;
         v[0] = rv_term(p[1], p[2], p[3], f) + p[6];
         v[1] = rv_term(p[1] / p[0], p[2], p[3] + 180.0, f) + p[6];
     } else {
@@ -77,8 +83,9 @@ __device__ inline void orbit_velocities_at(int model, const double* __restrict__
         const double q_out = (model == ORB_ST3) ? p[o + 5] : 1.0;
         const double K_out = p[oo], e_out = p[oo + 1], w_out = p[oo + 2], P_out = p[oo + 3], T0_out = p[oo + 4];
         const double gamma = p[oo + 5];
-        const double f_in = true_anomaly(t, T0_in, P_in, e_in);
-        const double f_out = true_anomaly(t, T0_out, P_out, e_out);
+        const double f_in = true_anomaly(t, T0_in, P_in, e_in, fE ? fE + 1 : nullptr);
+        const double f_out = true_anomaly(t, T0_out, P_out, e_out, fE ? fE + 3 : nullptr);
+        if (fE) { fE[0] = f_in; fE[2] = f_out; }
         const double v3 = rv_term(K_out, e_out, w_out, f_out);
         v[0] = rv_term(K_in, e_in, w_in, f_in) + v3 + gamma;                                   // orbit.py:274
         if (c >= 2) v[1] = rv_term(K_in / q_in, e_in, w_in + 180.0, f_in) + v3 + gamma;         // :364

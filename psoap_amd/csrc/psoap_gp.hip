@@ -37,6 +37,7 @@
 #include "predict_kernels.hpp"
 #include "calibrate_kernels.hpp"
 #include "grad_kernels.hpp"
+#include "orbit_grad_kernels.hpp"
 
 using namespace psoap;
 
@@ -938,6 +939,7 @@ extern "C" int psoap_chunk_set_grid(psoap_chunk* h, const double* lwl, const int
     HIP_TRY(hipMalloc(&h->dVel, sizeof(double) * (size_t)h->max_batch * 3 * n_epochs));
     HIP_TRY(hipHostMalloc(&h->hVel, sizeof(double) * (size_t)h->max_batch * 3 * n_epochs));
     h->n_epochs = n_epochs;
+    if (h->gws) h->gws->epochs_valid = false;
     HIP_TRY(hipMemcpy(h->dGrid, lwl, sizeof(double) * h->N, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(h->dEpoch, epoch, sizeof(int32_t) * h->N, hipMemcpyHostToDevice));
     return 0;
@@ -2648,13 +2650,37 @@ static void launch_grad_fill_contract(bool contract, hipStream_t s, int nb, int 
                            ld, N, Npad, P, dLwl, dGp, dAlpha, dPart);
 }
 
-extern "C" int psoap_chunk_lnlike_grad(psoap_chunk* h, int B, int c, const double* lwl, const double* gp, double mu_GP,
-                                       double* lnp, double* grad_gp, double* grad_lwl, double* grad_mu)
+// The pixels of every epoch for k_epoch_fold: a counting sort of the handle's epoch index (stable: ascending pixels within an
+// epoch), made once per psoap_chunk_set_grid.
+static int grad_epoch_lists(psoap_chunk* h, GradWs& w, hipStream_t s)
 {
-    if (!h || !lwl || !gp || !lnp || !grad_gp) FAIL("psoap_chunk_lnlike_grad: bad arguments");
-    if (B < 1) FAIL("psoap_chunk_lnlike_grad: B must be at least 1");
-    if (c < 1 || c > 3) FAIL("number of components must be 1, 2 or 3");
-    if (h->stream.open) FAIL("psoap_chunk_lnlike_grad: the handle has an open stream (psoap_stream_close first)");
+    if (w.epochs_valid) return 0;
+    const int N = h->N, ne = h->n_epochs;
+    std::vector<int32_t> ep((size_t)N);
+    HIP_TRY(hipMemcpyAsync(ep.data(), h->dEpoch, sizeof(int32_t) * (size_t)N, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    std::vector<int> start((size_t)ne + 1, 0), pix((size_t)N);
+    for (int i = 0; i < N; ++i) start[(size_t)ep[i] + 1]++;
+    for (int e = 0; e < ne; ++e) start[(size_t)e + 1] += start[e];
+    std::vector<int> at(start.begin(), start.end() - 1);
+    for (int i = 0; i < N; ++i) pix[(size_t)at[ep[i]]++] = i;
+    HIP_TRY(w.EpStart.need((size_t)ne + 1));
+    HIP_TRY(w.EpPix.need((size_t)N));
+    HIP_TRY(hipMemcpyAsync(w.EpStart, start.data(), sizeof(int) * ((size_t)ne + 1), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(w.EpPix, pix.data(), sizeof(int) * (size_t)N, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));       // (the vectors leave scope)
+    w.epochs_valid = true;
+    return 0;
+}
+
+// The ln-wavelengths of a gradient call come from the host (lwl: psoap_chunk_lnlike_grad) or, with lwl == nullptr, from
+// the orbits p_orb of `model`: per group k_orbit_jacobian and k_doppler_shift make them from the handle's grid and dates, and
+// after k_grad_finish the fold and the chain (orbit_grad_kernels.hpp) turn GradX into grad_vel and grad_orb on the device.
+static int grad_run(psoap_chunk* h, int B, int c, const double* lwl, int model, const double* p_orb,
+                    const double* gp, double mu_GP, double* lnp, double* grad_gp, double* grad_lwl, double* grad_mu,
+                    double* grad_orb, double* grad_vel)
+{
+    const bool orbits = lwl == nullptr;
     DEVICE_SCOPE(h->device);
     if (int rc = enter_device(h->device)) return rc;
     const int N = h->N, Npad = h->Npad, P = h->P, ld = 2 * h->Npad;
@@ -2677,11 +2703,32 @@ extern "C" int psoap_chunk_lnlike_grad(psoap_chunk* h, int B, int c, const doubl
     HIP_TRY(w.GradX.need((size_t)G * 3 * N));
     HIP_TRY(w.GradMu.need(G));
     hipStream_t s = h->streams[0];
+    const int ne = h->n_epochs, np = orbits ? orbit_n_params(model) : 0;
+    std::vector<int> fast(orbits ? (size_t)B : 0, 0);
+    if (orbits) {
+        HIP_TRY(w.Porb.need((size_t)G * np));
+        HIP_TRY(w.Vel.need((size_t)G * c * ne));
+        HIP_TRY(w.Jac.need((size_t)G * c * ne * np));
+        HIP_TRY(w.Gv.need((size_t)G * c * ne));
+        HIP_TRY(w.GradOrb.need((size_t)G * np));
+        HIP_TRY(w.TooFast.need(G));
+        if (int rc = grad_epoch_lists(h, w, s)) return rc;
+    }
     h->recs.clear();
     const double tile_flops = 2.0 * NB * NB * (double)NB;
     for (int b0 = 0; b0 < B; b0 += G) {
         const int nb = (B - b0 < G) ? B - b0 : G;
-        HIP_TRY(hipMemcpyAsync(w.Lwl, lwl + (size_t)b0 * c * N, sizeof(double) * (size_t)nb * c * N, hipMemcpyHostToDevice, s));
+        if (!orbits) {
+            HIP_TRY(hipMemcpyAsync(w.Lwl, lwl + (size_t)b0 * c * N, sizeof(double) * (size_t)nb * c * N, hipMemcpyHostToDevice, s));
+        } else {
+            HIP_TRY(hipMemcpyAsync(w.Porb, p_orb + (size_t)b0 * np, sizeof(double) * (size_t)nb * np, hipMemcpyHostToDevice, s));
+            HIP_TRY(hipMemsetAsync(w.TooFast, 0, sizeof(int) * (size_t)nb, s));
+            hipLaunchKernelGGL(k_orbit_jacobian, dim3((ne + 63) / 64, nb), dim3(64), 0, s, model, nb, ne, (const double*)w.Porb.p,
+                               (const double*)h->dDates, w.Vel.p, w.Jac.p, w.TooFast.p);
+            hipLaunchKernelGGL(k_doppler_shift, dim3((N + 255) / 256, nb * c), dim3(256), 0, s, w.Lwl.p, h->dGrid, h->dEpoch,
+                               (const double*)w.Vel.p, N, ne, nb * c);
+            HIP_TRY(hipGetLastError());
+        }
         HIP_TRY(hipMemcpyAsync(w.Gp, gp + (size_t)b0 * 2 * c, sizeof(double) * (size_t)nb * 2 * c, hipMemcpyHostToDevice, s));
         if (prof_begin(h, s, PSOAP_K_FILL, 0.0, (double)nb * 12.0 * N * (N + 1.0))) return 1;
         if (c == 1) launch_grad_fill_contract<1>(false, s, nb, ntiles, w.A, mstride, ld, N, Npad, P, w.Lwl, w.Gp, h->dSigma, nullptr, nullptr);
@@ -2741,6 +2788,18 @@ extern "C" int psoap_chunk_lnlike_grad(psoap_chunk* h, int B, int c, const doubl
         if (grad_lwl)
             HIP_TRY(hipMemcpyAsync(grad_lwl + (size_t)b0 * c * N, w.GradX, sizeof(double) * (size_t)nb * c * N, hipMemcpyDeviceToHost, s));
         if (grad_mu) HIP_TRY(hipMemcpyAsync(grad_mu + b0, w.GradMu, sizeof(double) * nb, hipMemcpyDeviceToHost, s));
+        if (orbits) {
+            const int CE = c * ne;
+            hipLaunchKernelGGL(k_epoch_fold, dim3((CE + 3) / 4, nb), dim3(256), 0, s, (const double*)w.GradX.p, (const int*)w.EpStart.p,
+                               (const int*)w.EpPix.p, c, N, ne, w.Gv.p);
+            hipLaunchKernelGGL(k_orbit_chain, dim3(nb), dim3(256), 0, s, (const double*)w.Gv.p, (const double*)w.Jac.p, CE, np,
+                               w.GradOrb.p);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(grad_orb + (size_t)b0 * np, w.GradOrb, sizeof(double) * (size_t)nb * np, hipMemcpyDeviceToHost, s));
+            if (grad_vel)
+                HIP_TRY(hipMemcpyAsync(grad_vel + (size_t)b0 * CE, w.Gv, sizeof(double) * (size_t)nb * CE, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemcpyAsync(fast.data() + b0, w.TooFast, sizeof(int) * (size_t)nb, hipMemcpyDeviceToHost, s));
+        }
         HIP_TRY(hipStreamSynchronize(s));       // the next group reuses the workspace and the caller's arrays are pageable
     }
     if (collect_timings(h)) return 1;
@@ -2749,14 +2808,67 @@ extern "C" int psoap_chunk_lnlike_grad(psoap_chunk* h, int B, int c, const doubl
     for (int b = 0; b < B; ++b) {
         bool neg = false;
         for (int k = 0; k < 2 * c; ++k) neg = neg || gp[(size_t)b * 2 * c + k] < 0.0;
+        if (orbits && fast[b]) neg = true;          // sample_parallel.py:186-187: |v| >= c  ->  -inf
         if (neg) lnp[b] = -INFINITY;
         if (lnp[b] == -INFINITY) {
             for (int k = 0; k < 2 * c; ++k) grad_gp[(size_t)b * 2 * c + k] = NAN;
             if (grad_lwl)
                 for (size_t k = 0; k < (size_t)c * N; ++k) grad_lwl[(size_t)b * c * N + k] = NAN;
             if (grad_mu) grad_mu[b] = NAN;
+            if (orbits) {
+                for (int k = 0; k < np; ++k) grad_orb[(size_t)b * np + k] = NAN;
+                if (grad_vel)
+                    for (size_t k = 0; k < (size_t)c * ne; ++k) grad_vel[(size_t)b * c * ne + k] = NAN;
+            }
         }
     }
+    return 0;
+}
+
+extern "C" int psoap_chunk_lnlike_grad(psoap_chunk* h, int B, int c, const double* lwl, const double* gp, double mu_GP,
+                                       double* lnp, double* grad_gp, double* grad_lwl, double* grad_mu)
+{
+    if (!h || !lwl || !gp || !lnp || !grad_gp) FAIL("psoap_chunk_lnlike_grad: bad arguments");
+    if (B < 1) FAIL("psoap_chunk_lnlike_grad: B must be at least 1");
+    if (c < 1 || c > 3) FAIL("number of components must be 1, 2 or 3");
+    if (h->stream.open) FAIL("psoap_chunk_lnlike_grad: the handle has an open stream (psoap_stream_close first)");
+    return grad_run(h, B, c, lwl, -1, nullptr, gp, mu_GP, lnp, grad_gp, grad_lwl, grad_mu, nullptr,
+                    nullptr);
+}
+
+extern "C" int psoap_chunk_lnprob_grad(psoap_chunk* h, int B, int model, const double* p_orb, const double* gp, double mu_GP,
+                                       double* lnp, double* grad_orb, double* grad_gp, double* grad_vel, double* grad_mu)
+{
+    if (!h || !p_orb || !gp || !lnp || !grad_orb || !grad_gp) FAIL("psoap_chunk_lnprob_grad: bad arguments");
+    if (B < 1) FAIL("psoap_chunk_lnprob_grad: B must be at least 1");
+    if (!h->dGrid || !h->dDates) FAIL("psoap_chunk_lnprob_grad: call psoap_chunk_set_grid and psoap_chunk_set_dates first");
+    if (h->stream.open) FAIL("psoap_chunk_lnprob_grad: the handle has an open stream (psoap_stream_close first)");
+    if (int rc = check_orbits(model, B, p_orb)) return rc;
+    return grad_run(h, B, orbit_n_components(model), nullptr, model, p_orb, gp, mu_GP, lnp, grad_gp,
+                    nullptr, grad_mu, grad_orb, grad_vel);
+}
+
+// stand-alone, beside psoap_orbit_velocities: vel_out (B, c, n_dates), jac_out (B, c, n_dates, n_orb)
+extern "C" int psoap_orbit_velocity_jacobian(int device, int model, int B, const double* p_orb, int n_dates,
+                                             const double* dates, double* vel_out, double* jac_out)
+{
+    if (B < 1 || n_dates < 1 || !p_orb || !dates || !vel_out || !jac_out) FAIL("psoap_orbit_velocity_jacobian: bad arguments");
+    if (int rc = check_orbits(model, B, p_orb)) return rc;
+    DEVICE_SCOPE(device);
+    HIP_TRY(hipSetDevice(device));
+    const int c = orbit_n_components(model), np = orbit_n_params(model);
+    Grow<double> dP, dD, dV, dJ;
+    HIP_TRY(dP.need((size_t)B * np));
+    HIP_TRY(dD.need(n_dates));
+    HIP_TRY(dV.need((size_t)B * c * n_dates));
+    HIP_TRY(dJ.need((size_t)B * c * n_dates * np));
+    HIP_TRY(hipMemcpy(dP, p_orb, sizeof(double) * (size_t)B * np, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dD, dates, sizeof(double) * n_dates, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_orbit_jacobian, dim3((n_dates + 63) / 64, B), dim3(64), 0, 0, model, B, n_dates, (const double*)dP.p,
+                       (const double*)dD.p, dV.p, dJ.p, (int*)nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(vel_out, dV, sizeof(double) * (size_t)B * c * n_dates, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(jac_out, dJ, sizeof(double) * (size_t)B * c * n_dates * np, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -8,12 +8,14 @@ the host ships ``n_orb + 2c`` doubles and receives one.  ``lnprob_batch`` evalua
 """
 from __future__ import annotations
 
+import os
+
 import numpy as np
 
 from . import _lib
 from ._lib import as_f64, check, dptr
 from .chunk import ChunkHandle
-from .utils import MODEL_ID, N_COMPONENTS, convert_vectors, n_params_orb
+from .utils import MODEL_ID, N_COMPONENTS, convert_vectors, n_params_orb, registered_params
 
 
 class ChunkWorker:
@@ -75,3 +77,55 @@ class ChunkWorker:
 
     def lnprob(self, p, mu_GP: float = 1.0) -> float:
         return float(self.lnprob_batch(np.atleast_2d(p), mu_GP)[0])
+
+    # -- gradient of lnprob(p) (include/psoap_gp.h: psoap_chunk_lnprob_grad) ----------------------------------------
+    def lnprob_grad_orbits(self, p_orb, p_gp, mu_GP: float = 1.0, want_vel: bool = False):
+        """The gradient with the vectors already split, as ``upload_orbits`` takes them: orbital parameters (B, n_orb) and
+        GP parameters (B, 2c) -> ``(lnp (B,), grad_orb (B, n_orb), grad_gp (B, 2c), grad_mu (B,))`` (and ``grad_vel
+        (B, c, n_epochs)`` with ``want_vel``).  Kepler solve, orbit Jacobian, Doppler shift, likelihood gradient and the
+        chain rule run on the device.  The only way in for ST2, for the reason ``upload_orbits`` documents."""
+        if os.environ.get("PSOAP_GPU_SERVER", "").strip().lower() not in ("", "0"):
+            raise _lib.PsoapError("lnprob_grad needs the device in this process (PSOAP_GPU_SERVER serves values only)")
+        p_orb = as_f64(np.atleast_2d(p_orb))
+        B = p_orb.shape[0]
+        p_orb = as_f64(p_orb, (B, n_params_orb[self.model]))
+        p_gp = as_f64(np.atleast_2d(p_gp), (B, 2 * N_COMPONENTS[self.model]))
+        return self.handle.lnprob_grad(MODEL_ID[self.model], p_orb, p_gp, mu_GP, want_vel=want_vel)
+
+    def lnprob_grad_batch(self, ps, mu_GP: float = 1.0):
+        """Fitted parameter vectors (B, n_fit) -> ``(lnp (B,), grad (B, n_fit))``: the derivative with respect to every
+        non-fixed parameter, in registered order; fixed parameters drop out.  A proposal whose ``lnp`` is ``-inf`` has a
+        NaN gradient."""
+        p_orb, p_gp = convert_vectors(np.atleast_2d(ps), self.model, self.fix_params, **self.defaults)
+        lnp, g_orb, g_gp, _g_mu = self.lnprob_grad_orbits(p_orb, p_gp, mu_GP)
+        full = np.concatenate([g_orb, g_gp], axis=1)
+        fit_ind = [i for i, name in enumerate(registered_params[self.model]) if name not in self.fix_params]
+        return lnp, np.ascontiguousarray(full[:, fit_ind])
+
+    def lnprob_grad(self, p, mu_GP: float = 1.0):
+        lnp, grad = self.lnprob_grad_batch(np.atleast_2d(p), mu_GP)
+        return float(lnp[0]), grad[0]
+
+
+def optimize_orbit(workers, p0, bounds=None, mu_GP=1.0, ftol=1e-10, full_output=False):
+    """L-BFGS-B fit of one fitted parameter vector to several chunks from ``p0``, with the analytic gradient
+    (``ChunkWorker.lnprob_grad``, ``jac=True``): the objective is minus the SUM of the workers' ``lnprob``, the sum
+    ``sample_parallel`` takes over its chunks.  No priors: the caller passes ``bounds`` (SciPy's form, one pair per fitted
+    parameter).  Returns the fitted vector, or SciPy's whole result with ``full_output`` (``-result.fun`` is the summed
+    ``lnprob`` reached, ``result.jac`` the gradient of minus that sum there).  Modelled on ``covariance.optimize_GP``."""
+    from scipy.optimize import minimize
+    workers = list(workers) if isinstance(workers, (list, tuple)) else [workers]
+    x0 = as_f64(np.atleast_1d(p0))
+
+    def func(x):
+        total, grad = 0.0, np.zeros_like(x)
+        for w in workers:
+            lnp, g = w.lnprob_grad(x, mu_GP)
+            if not np.isfinite(lnp):
+                return np.inf, np.zeros_like(x)
+            total += lnp
+            grad += g
+        return -total, -grad
+
+    res = minimize(func, x0, jac=True, method="L-BFGS-B", bounds=bounds, options={"ftol": ftol})
+    return res if full_output else res["x"]

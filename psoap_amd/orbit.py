@@ -29,6 +29,24 @@ def velocities(model: str, p_orb, dates, device=None) -> np.ndarray:
     return out
 
 
+def velocity_jacobian(model: str, p_orb, dates, device=None):
+    """Batched: p_orb (B, n_orb) -> ``(vel (B, c, n_dates), jac (B, c, n_dates, n_orb))``: the velocities of ``velocities``
+    (the same bits) and ``d vel / d p_orb`` in registered order up to ``gamma``, taken at the same converged eccentric
+    anomaly by implicit differentiation of Kepler's equation (psoap_orbit_velocity_jacobian).  Entries of parameters a
+    component does not depend on are exact zeros."""
+    p_orb = as_f64(np.atleast_2d(p_orb))
+    dates = as_f64(np.atleast_1d(dates))
+    B, n_orb = p_orb.shape
+    if n_orb != n_params_orb[model]:
+        raise ValueError(f"model {model} takes {n_params_orb[model]} orbital parameters, got {n_orb}")
+    vel = np.empty((B, N_COMPONENTS[model], dates.shape[0]))
+    jac = np.empty((B, N_COMPONENTS[model], dates.shape[0], n_orb))
+    dev = _lib.default_device() if device is None else device
+    check(_lib.load().psoap_orbit_velocity_jacobian(dev, MODEL_ID[model], B, dptr(p_orb), dates.shape[0], dptr(dates),
+                                                    dptr(vel), dptr(jac)), "psoap_orbit_velocity_jacobian")
+    return vel, jac
+
+
 class _Orbit:
     model = ""
 
