@@ -433,13 +433,19 @@ int psoap_dag_plan(int B, int P, int workers, void *out, long long max_tasks, lo
  * psoap_dag_plan_sky: the throughput list inside the skyline first[0 .. P) (tile (q, j) exists iff q >= first[j]; first
  *   non-decreasing, first[j] <= max(j - 1, 0)); the ctr field of a final carries in bits 24.. how many tiles its block row
  *   is short of P - q.  first all zero: the list of psoap_dag_plan, byte for byte.
- * psoap_sky_first: host twin of the upload-side kernels -- the permutation perm_out (N) and the union skyline first_out
- *   (ceil(N / 128)) of a batch lwl (B, c, N), gp (B, 2c); either output may be NULL.
+ * The row order is chosen behind every upload from the slot's contents: among convex blends of the first walker's component
+ * grids (1, 9, 15 candidates for 1, 2, 3 components; candidate 0 is the first component alone) the one whose union skyline
+ * costs the fewest tile-GEMM units, ties to the lowest candidate.  PSOAP_SKY_ORDER=0 at handle creation: always candidate 0.
+ * psoap_sky_first: host twin of the upload-side kernels pinned to candidate 0 -- the permutation perm_out (N) and the union
+ *   skyline first_out (ceil(N / 128)) of a batch lwl (B, c, N), gp (B, 2c); either output may be NULL.
+ * psoap_sky_order: host twin of the upload-side kernels with the choice -- the same outputs for the winning candidate, and
+ *   its index in *cand_out; any output may be NULL.
  * psoap_chunk_sky_stats: out[0 .. n) of { tiles planned, tiles dense, tile-GEMM units planned, units dense, plan builds,
  *   plan-cache hits, skyline read (0 / 1) } for the handle's last evaluation; returns the number of fields (7). */
 int psoap_dag_plan_sky(int B, int P, const int *first, int workers, void *out, long long max_tasks, long long *n_tasks,
                        long long *n_slots, long long *n_ctrs, unsigned int *queue_first /* 9 entries or NULL */);
 int psoap_sky_first(int c, int N, int B, const double *lwl, const double *gp, int *first_out, int *perm_out);
+int psoap_sky_order(int c, int N, int B, const double *lwl, const double *gp, int *first_out, int *perm_out, int *cand_out);
 int psoap_chunk_sky_stats(psoap_chunk *h, long long *out, int n);
 /* The same for a heterogeneous batch (matrices of several chunks in one launch): matrix b has Ps[b]
  * block rows. */

@@ -519,14 +519,15 @@ struct DeviceScope {
 struct BatchSlot {
     double* dLwl = nullptr;    // max_batch x 3 x N
     double* dGp = nullptr;     // max_batch x 6
-    // sorted layout (sky_kernels.hpp; a handle with the skyline on): the slot's rows in ascending ln-wavelength of its first
-    // walker's first component -- what the evaluations read; dLwl keeps the upload's order
+    // sorted layout (sky_kernels.hpp; a handle with the skyline on): the slot's rows in the order chosen for its contents
+    // (ascending in a blend of its first walker's component grids) -- what the evaluations read; dLwl keeps the upload's order
     double* dLwlS = nullptr;   // max_batch x 3 x N
     double* dFlS = nullptr;    // N: the handle's fl and sigma through the same permutation
     double* dSigmaS = nullptr;
-    int* dPerm = nullptr;      // N
-    int* dFirstB = nullptr;    // max_batch x P: first_b per matrix
-    int* hFirst = nullptr;     // P, pinned: the union over the batch
+    int* dPerm = nullptr;      // candidates x N
+    int* dCand = nullptr;      // the candidate the last upload chose: its permutation is the one of the sorted copies
+    int* dFirstB = nullptr;    // candidates x max_batch x P: first_b per candidate and matrix
+    int* hFirst = nullptr;     // P, pinned: the chosen candidate's union over the batch
     int* dTooFast = nullptr;   // max_batch: |v| >= c flags (orbit proposals)
     bool toofast_dirty = false;  // an orbit upload may have raised flags: clear before the slot is reused
     DagMat* dMats = nullptr;   // per-matrix records of this slot (max_batch entries)
@@ -614,6 +615,7 @@ struct psoap_chunk {
     int plan_B = 0, plan_workers = 0;
     // skyline (PSOAP_SKYLINE=0, read at create, or N > SKY_MAX_N: off -- identity order, dense plan)
     bool sky = false;
+    bool sky_order = true;            // PSOAP_SKY_ORDER=0, read at create: always candidate 0, the first component's order
     std::vector<int> plan_first;      // the skyline of the list in `dag` (empty: dense)
     DagPlanWork plan_work;            // what that list executes (a skyline list only)
     struct SkyPlan {
@@ -786,14 +788,19 @@ static int chunk_alloc(psoap_chunk* h, const double* fl, const double* sigma)
     {
         const char* e = getenv("PSOAP_SKYLINE");
         h->sky = N <= SKY_MAX_N && !(e && e[0] == '0');
+        e = getenv("PSOAP_SKY_ORDER");
+        h->sky_order = !(e && e[0] == '0');
     }
+    const size_t n_cand = h->sky_order ? SKY_MAX_CAND : 1;
     for (BatchSlot& sl : h->slot) {
         if (h->sky) {
             HIP_TRY(hipMalloc(&sl.dLwlS, sizeof(double) * nb * 3 * N));
             HIP_TRY(hipMalloc(&sl.dFlS, sizeof(double) * N));
             HIP_TRY(hipMalloc(&sl.dSigmaS, sizeof(double) * N));
-            HIP_TRY(hipMalloc(&sl.dPerm, sizeof(int) * N));
-            HIP_TRY(hipMalloc(&sl.dFirstB, sizeof(int) * nb * h->P));
+            HIP_TRY(hipMalloc(&sl.dPerm, sizeof(int) * n_cand * N));
+            HIP_TRY(hipMalloc(&sl.dCand, sizeof(int)));
+            HIP_TRY(hipMemset(sl.dCand, 0, sizeof(int)));
+            HIP_TRY(hipMalloc(&sl.dFirstB, sizeof(int) * n_cand * nb * h->P));
             HIP_TRY(hipHostMalloc(&sl.hFirst, sizeof(int) * h->P));
             memset(sl.hFirst, 0, sizeof(int) * h->P);
         }
@@ -884,7 +891,7 @@ extern "C" int psoap_chunk_destroy(psoap_chunk* h)
     (void)hipHostFree(h->hLwl); (void)hipHostFree(h->hGp); (void)hipHostFree(h->hVel); (void)hipHostFree(h->hOut);
     for (BatchSlot& sl : h->slot) {
         (void)hipFree(sl.dLwl); (void)hipFree(sl.dGp); (void)hipFree(sl.dTooFast); (void)hipFree(sl.dMats);
-        (void)hipFree(sl.dLwlS); (void)hipFree(sl.dFlS); (void)hipFree(sl.dSigmaS); (void)hipFree(sl.dPerm);
+        (void)hipFree(sl.dLwlS); (void)hipFree(sl.dFlS); (void)hipFree(sl.dSigmaS); (void)hipFree(sl.dPerm); (void)hipFree(sl.dCand);
         (void)hipFree(sl.dFirstB); (void)hipHostFree(sl.hFirst);
         if (sl.evUpload) (void)hipEventDestroy(sl.evUpload);
         if (sl.evEval) (void)hipEventDestroy(sl.evEval);
@@ -915,7 +922,7 @@ extern "C" int psoap_chunk_set_data(psoap_chunk* h, const double* fl, const doub
     // the sorted copies of the slots that hold a batch
     for (BatchSlot& sl : h->slot)
         if (h->sky && sl.B > 0 && sl.sky_valid) {
-            hipLaunchKernelGGL(k_sky_gather, dim3((h->N + 255) / 256, 2), dim3(256), 0, h->streams[0], sl.dPerm, h->N, 0,
+            hipLaunchKernelGGL(k_sky_gather, dim3((h->N + 255) / 256, 2), dim3(256), 0, h->streams[0], sl.dPerm, sl.dCand, h->N, 0,
                                (const double*)nullptr, (double*)nullptr, h->dFl, sl.dFlS, h->dSigma, sl.dSigmaS);
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipStreamSynchronize(h->streams[0]));
@@ -1015,34 +1022,84 @@ extern "C" int psoap_dag_plan_sky(int B, int P, const int* first, int workers, v
     return 0;
 }
 
-// Pure host function, the twin of the upload-side kernels (sky_kernels.hpp, same routines): the permutation and the
-// union skyline of a batch lwl (B, c, N), gp (B, 2c).  perm_out (N), first_out (ceil(N / 128)); either may be null.
+// One candidate order on the host, by the routines the upload-side kernels run (sky_kernels.hpp): its permutation and its
+// union skyline over the batch lwl (B, c, N), gp (B, 2c); returns the envelope's cost (sky_cost)
+static long long sky_host_candidate(int c, int N, int B, const double* lwl, const double* gp, int cand, std::vector<int>& perm,
+                                    std::vector<int>& first)
+{
+    const int P = round_up(N, NB) / NB;
+    double w[3];
+    sky_cand_weights(c, cand, w);
+    std::vector<unsigned long long> key((size_t)N);
+    for (int i = 0; i < N; ++i) {
+        double v[3] = {0.0, 0.0, 0.0};
+        for (int k = 0; k < c; ++k) v[k] = lwl[(size_t)k * N + i];
+        key[i] = sky_key(sky_cand_key(c, w, v));
+    }
+    perm.resize((size_t)N);
+    first.assign((size_t)P, 0);
+    for (int i = 0; i < N; ++i) perm[i] = i;
+    std::stable_sort(perm.begin(), perm.end(), [&key](int a, int b) { return key[a] < key[b]; });
+    std::vector<double> x((size_t)c * N), lo((size_t)c * P), hi((size_t)c * P);
+    std::vector<int> fb((size_t)P);
+    for (int b = 0; b < B; ++b) {
+        for (int k = 0; k < c; ++k)
+            for (int r = 0; r < N; ++r) x[(size_t)k * N + r] = lwl[((size_t)b * c + k) * N + perm[r]];
+        for (int k = 0; k < c; ++k)
+            for (int t = 0; t < P; ++t)
+                sky_interval(x.data() + (size_t)k * N, t * NB, (t + 1) * NB < N ? (t + 1) * NB : N, &lo[(size_t)k * P + t],
+                             &hi[(size_t)k * P + t]);
+        double p2[3] = {0.0, 0.0, 0.0};
+        const bool ok = sky_gp(gp + (size_t)b * 2 * c, c, p2);
+        for (int j = 0; j < P; ++j) fb[j] = sky_first_raw(j, P, c, lo.data(), hi.data(), p2, ok);
+        sky_first_finish(fb.data(), P);
+        for (int j = 0; j < P; ++j) first[j] = (b == 0 || fb[j] < first[j]) ? fb[j] : first[j];
+    }
+    return sky_cost(first.data(), P);
+}
+
+// Pure host function, the twin of the upload-side kernels pinned to candidate 0 (the order by the first walker's first
+// component; what a handle created under PSOAP_SKY_ORDER=0 computes): the permutation and the union skyline of a batch
+// lwl (B, c, N), gp (B, 2c).  perm_out (N), first_out (ceil(N / 128)); either may be null.
 extern "C" int psoap_sky_first(int c, int N, int B, const double* lwl, const double* gp, int* first_out, int* perm_out)
 {
     if (c < 1 || c > 3 || N < 1 || B < 1 || !lwl || !gp) FAIL("psoap_sky_first: bad arguments");
     const int P = round_up(N, NB) / NB;
     std::vector<int> perm((size_t)N), first((size_t)P, 0);
     for (int i = 0; i < N; ++i) perm[i] = i;
+    if (N <= SKY_MAX_N) sky_host_candidate(c, N, B, lwl, gp, 0, perm, first);
+    if (perm_out) memcpy(perm_out, perm.data(), sizeof(int) * (size_t)N);
+    if (first_out) memcpy(first_out, first.data(), sizeof(int) * (size_t)P);
+    return 0;
+}
+
+// Pure host function, the twin of the upload-side kernels as a handle runs them: every candidate order of the batch
+// (sky_n_cand(c) of them), the cheapest envelope wins, ties to the lowest candidate.  cand_out: the winner; perm_out (N)
+// and first_out (ceil(N / 128)): its permutation and union skyline; any output may be null.
+extern "C" int psoap_sky_order(int c, int N, int B, const double* lwl, const double* gp, int* first_out, int* perm_out,
+                               int* cand_out)
+{
+    if (c < 1 || c > 3 || N < 1 || B < 1 || !lwl || !gp) FAIL("psoap_sky_order: bad arguments");
+    const int P = round_up(N, NB) / NB;
+    std::vector<int> perm((size_t)N), first((size_t)P, 0);
+    for (int i = 0; i < N; ++i) perm[i] = i;
+    int best = 0;
     if (N <= SKY_MAX_N) {
-        std::stable_sort(perm.begin(), perm.end(), [lwl](int a, int b) { return sky_key(lwl[a]) < sky_key(lwl[b]); });
-        std::vector<double> x((size_t)c * N), lo((size_t)c * P), hi((size_t)c * P);
-        std::vector<int> fb((size_t)P);
-        for (int b = 0; b < B; ++b) {
-            for (int k = 0; k < c; ++k)
-                for (int r = 0; r < N; ++r) x[(size_t)k * N + r] = lwl[((size_t)b * c + k) * N + perm[r]];
-            for (int k = 0; k < c; ++k)
-                for (int t = 0; t < P; ++t)
-                    sky_interval(x.data() + (size_t)k * N, t * NB, (t + 1) * NB < N ? (t + 1) * NB : N, &lo[(size_t)k * P + t],
-                                 &hi[(size_t)k * P + t]);
-            double p2[3] = {0.0, 0.0, 0.0};
-            const bool ok = sky_gp(gp + (size_t)b * 2 * c, c, p2);
-            for (int j = 0; j < P; ++j) fb[j] = sky_first_raw(j, P, c, lo.data(), hi.data(), p2, ok);
-            sky_first_finish(fb.data(), P);
-            for (int j = 0; j < P; ++j) first[j] = (b == 0 || fb[j] < first[j]) ? fb[j] : first[j];
+        long long best_cost = sky_host_candidate(c, N, B, lwl, gp, 0, perm, first);
+        std::vector<int> pk, fk;
+        for (int k = 1; k < sky_n_cand(c); ++k) {
+            const long long cost = sky_host_candidate(c, N, B, lwl, gp, k, pk, fk);
+            if (cost < best_cost) {
+                best_cost = cost;
+                best = k;
+                perm.swap(pk);
+                first.swap(fk);
+            }
         }
     }
     if (perm_out) memcpy(perm_out, perm.data(), sizeof(int) * (size_t)N);
     if (first_out) memcpy(first_out, first.data(), sizeof(int) * (size_t)P);
+    if (cand_out) *cand_out = best;
     return 0;
 }
 
@@ -1247,11 +1304,14 @@ static int upload_end(psoap_chunk* h, BatchSlot& sl)
     if (sl.sky_valid) {
         const int N = h->N, rows = sl.B * sl.C;
         hipStream_t s = h->copy;
-        hipLaunchKernelGGL(k_sky_perm, dim3((N + 255) / 256), dim3(256), 0, s, sl.dLwl, N, sl.dPerm);
-        hipLaunchKernelGGL(k_sky_gather, dim3((N + 255) / 256, rows + 2), dim3(256), 0, s, sl.dPerm, N, rows, sl.dLwl, sl.dLwlS,
-                           h->dFl, sl.dFlS, h->dSigma, sl.dSigmaS);
-        hipLaunchKernelGGL(k_sky_first, dim3(sl.B), dim3(256), 0, s, sl.dLwlS, sl.dGp, sl.C, N, h->P, sl.dFirstB);
-        hipLaunchKernelGGL(k_sky_union, dim3(1), dim3(64), 0, s, sl.dFirstB, sl.B, h->P, sl.hFirst);
+        // (the candidates ride in the grids: four launches whatever their number; the order is chosen from this upload's
+        // contents, never carried over from an earlier one)
+        const int K = h->sky_order ? sky_n_cand(sl.C) : 1;
+        hipLaunchKernelGGL(k_sky_perm, dim3((N + 255) / 256, K), dim3(256), 0, s, sl.dLwl, sl.C, N, sl.dPerm);
+        hipLaunchKernelGGL(k_sky_first, dim3(sl.B, K), dim3(256), 0, s, sl.dLwl, sl.dPerm, sl.dGp, sl.C, N, h->P, sl.dFirstB);
+        hipLaunchKernelGGL(k_sky_choose, dim3(1), dim3(256), 0, s, sl.dFirstB, sl.B, h->P, K, sl.hFirst, sl.dCand);
+        hipLaunchKernelGGL(k_sky_gather, dim3((N + 255) / 256, rows + 2), dim3(256), 0, s, sl.dPerm, sl.dCand, N, rows, sl.dLwl,
+                           sl.dLwlS, h->dFl, sl.dFlS, h->dSigma, sl.dSigmaS);
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipEventRecord(h->evStaging, h->copy));

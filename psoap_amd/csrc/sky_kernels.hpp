@@ -2,17 +2,25 @@
 //
 // The covariance is a sum of squared exponentials that underflow to exactly +0 once p2 d^2 <= -746 (kern_elem4_skip,
 // fill_kernels.hpp).  With the rows ordered by ln-wavelength the matrix is a band, and a Cholesky factor stays inside the
-// skyline of its matrix: tile (q, j) of the factor is zero whenever tiles (0 .. q, j) of the matrix are.  Behind every
-// upload into a batch slot these kernels
-//   1. rank the first walker's first component (a total order on the BITS of the keys, ties by index: a pure function of
-//      the slot's contents) and gather lwl, fl and sigma through that permutation;
-//   2. compute, per matrix, component and 128-row tile, the interval of the sorted ln-wavelengths, and from the intervals
-//      first_b[j] -- the first block row q whose tile (q, j) is not PROVABLY zero: the gap g between the two intervals is
-//      a lower bound of every |d| in the tile, rounding is monotone, so p2 g g <= -746 in the kernel's own arithmetic
-//      implies the same for every element;
-//   3. clamp first_b[j] <= j - 1 (the hand-over of the diagonal chain), make it non-decreasing, and write the union over
-//      the batch, first[j] = min_b first_b[j], to pinned host memory for the planner (dag_build_tasks).
-// The routines marked __host__ __device__ are shared with the host twin psoap_sky_first (psoap_gp.hip).
+// skyline of its matrix: tile (q, j) of the factor is zero whenever tiles (0 .. q, j) of the matrix are.  Any symmetric
+// permutation is valid, and with several components no single order makes every component a band: the order by one
+// component's grid spreads the others by the epochs' velocity differences.  So the order is CHOSEN per upload among a few
+// candidates, convex blends of the first walker's component grids (sky_cand_weights: 1, 9 or 15 of them for 1, 2 or 3
+// components; candidate 0 is the first component alone).  Behind every upload into a batch slot these kernels
+//   1. per candidate, rank the blended key (a total order on the BITS of the keys, ties by index: a pure function of the
+//      slot's contents);
+//   2. per candidate, matrix, component and 128-row tile, compute the interval of the ln-wavelengths read through the
+//      candidate's permutation, and from the intervals first_b[j] -- the first block row q whose tile (q, j) is not
+//      PROVABLY zero: the gap g between the two intervals is a lower bound of every |d| in the tile, rounding is monotone,
+//      so p2 g g <= -746 in the kernel's own arithmetic implies the same for every element; first_b[j] is clamped to
+//      j - 1 (the hand-over of the diagonal chain) and made non-decreasing;
+//   3. per candidate, form the union over the batch, first[j] = min_b first_b[j], and its cost in tile-GEMM units
+//      (sky_cost: what the planner's list executes per matrix); the smallest cost wins, ties to the lowest candidate, so
+//      the plan is never larger than candidate 0's; the winner's first[] goes to pinned host memory for the planner
+//      (dag_build_tasks);
+//   4. gather lwl, fl and sigma through the winner's permutation -- nothing is gathered for a candidate that loses.
+// The routines marked __host__ __device__ are shared with the host twins psoap_sky_first (candidate 0) and psoap_sky_order
+// (psoap_gp.hip): the envelope is integer work on comparisons both sides make alike, the keys are the same arithmetic.
 #pragma once
 #include "common.hpp"
 
@@ -20,12 +28,64 @@ namespace psoap {
 
 constexpr int SKY_MAX_N = 8192;              // beyond: identity permutation, dense plan
 constexpr int SKY_MAX_P = SKY_MAX_N / NB;
+constexpr int SKY_MAX_CAND = 15;             // candidate orders of a slot (three components)
 
 // a double as an unsigned key whose order is the order of the finite values and total on all bit patterns
 __host__ __device__ inline unsigned long long sky_key(double x)
 {
     const unsigned long long u = __builtin_bit_cast(unsigned long long, x);
     return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+
+// candidate orders of a slot with C components
+__host__ __device__ inline int sky_n_cand(int C) { return C == 2 ? 9 : C == 3 ? 15 : 1; }
+
+// the blend of candidate k: eighths between two components; quarters over three, for a in 0..4: for b in 0..4-a the
+// weights ((4-a-b)/4, a/4, b/4) -- all exact; candidate 0 is (1, 0, 0)
+__host__ __device__ inline void sky_cand_weights(int C, int k, double* w)
+{
+    w[0] = 1.0;
+    w[1] = w[2] = 0.0;
+    if (C == 2) {
+        w[0] = 1.0 - k / 8.0;
+        w[1] = k / 8.0;
+    } else if (C == 3) {
+        int at = 0;
+        for (int a = 0; a <= 4; ++a)
+            for (int b = 0; b <= 4 - a; ++b, ++at)
+                if (at == k) {
+                    w[0] = (4 - a - b) / 4.0;
+                    w[1] = a / 4.0;
+                    w[2] = b / 4.0;
+                }
+    }
+}
+
+// the key of one row: sum of w[c] x[c] left to right, no contraction; a term of weight exactly 0 is skipped and a lone
+// weight of 1 hands the component's bits through (an infinity or NaN elsewhere never reaches candidate 0's key)
+__host__ __device__ inline double sky_cand_key(int C, const double* w, const double* x)
+{
+#pragma clang fp contract(off)
+    double acc = 0.0;
+    bool any = false;
+    for (int c = 0; c < C; ++c) {
+        if (w[c] == 0.0) continue;
+        const double t = w[c] == 1.0 ? x[c] : w[c] * x[c];
+        acc = any ? acc + t : t;
+        any = true;
+    }
+    return acc;
+}
+
+// tile-GEMM units per matrix of the list inside first[0 .. P): tile (q, j) runs q - first[j] of them
+__host__ __device__ inline long long sky_cost(const int* first, int P)
+{
+    long long u = 0;
+    for (int j = 0; j < P; ++j) {
+        const long long d = j - first[j];
+        u += d * (d + 1) / 2;
+    }
+    return u;
 }
 
 // p2[c] as load_gp computes it; false: a hyper-parameter is negative, zero, NaN or infinite, or amp^2 is not finite (an
@@ -93,53 +153,84 @@ __host__ __device__ inline void sky_first_finish(int* first, int P)
 }
 
 // ---- device ----------------------------------------------------------------------------------------
-// perm[rank(i)] = i, rank by (sky_key, index); x: the N keys
-__global__ __launch_bounds__(256) void k_sky_perm(const double* __restrict__ x, int N, int* __restrict__ perm)
+// candidate blockIdx.y: perm[cand][rank(i)] = i, rank by (sky_key of the blended key, index); x: the first walker's C grids
+__global__ __launch_bounds__(256) void k_sky_perm(const double* __restrict__ x, int C, int N, int* __restrict__ perm)
 {
     __shared__ unsigned long long keys[1024];
+    const int cand = blockIdx.y;
+    double w[3];
+    sky_cand_weights(C, cand, w);
+    auto key = [&](int i) {
+        double v[3] = {0.0, 0.0, 0.0};
+        for (int c = 0; c < C; ++c) v[c] = x[(size_t)c * N + i];
+        return sky_key(sky_cand_key(C, w, v));
+    };
     const int i = blockIdx.x * 256 + threadIdx.x;
-    const unsigned long long mine = i < N ? sky_key(x[i]) : 0ull;
+    const unsigned long long mine = i < N ? key(i) : 0ull;
     int rank = 0;
     for (int k0 = 0; k0 < N; k0 += 1024) {
         __syncthreads();
-        for (int k = threadIdx.x; k < 1024; k += 256) keys[k] = k0 + k < N ? sky_key(x[k0 + k]) : 0ull;
+        // (past N: the largest key under an index no row has -- it counts for nobody, and the loop below has a fixed length:
+        // unrolled, its LDS reads overlap; one block per compute unit has no other wavefront to hide their latency)
+        for (int k = threadIdx.x; k < 1024; k += 256) keys[k] = k0 + k < N ? key(k0 + k) : ~0ull;
         __syncthreads();
-        const int n = N - k0 < 1024 ? N - k0 : 1024;
-        for (int k = 0; k < n; ++k) {
+#pragma unroll 16
+        for (int k = 0; k < 1024; ++k) {
             const unsigned long long o = keys[k];
             rank += (o < mine || (o == mine && k0 + k < i)) ? 1 : 0;
         }
     }
-    if (i < N) perm[rank] = i;
+    if (i < N) perm[(size_t)cand * N + rank] = i;
 }
 
-// out[row][r] = in[row][perm[r]]: blockIdx.y < rows the slot's ln-wavelengths, then the handle's fl and sigma
-__global__ __launch_bounds__(256) void k_sky_gather(const int* __restrict__ perm, int N, int rows,
+// out[row][r] = in[row][perm[*cand][r]]: blockIdx.y < rows the slot's ln-wavelengths, then the handle's fl and sigma
+__global__ __launch_bounds__(256) void k_sky_gather(const int* __restrict__ perm, const int* __restrict__ cand, int N, int rows,
                                                     const double* __restrict__ lwl, double* __restrict__ lwl_s,
                                                     const double* __restrict__ fl, double* __restrict__ fl_s,
                                                     const double* __restrict__ sigma, double* __restrict__ sigma_s)
 {
     const int r = blockIdx.x * 256 + threadIdx.x;
     if (r >= N) return;
-    const int src = perm[r];
+    const int src = perm[(size_t)cand[0] * N + r];
     const int row = blockIdx.y;
     if (row < rows) lwl_s[(size_t)row * N + r] = lwl[(size_t)row * N + src];
     else if (row == rows) fl_s[r] = fl[src];
     else sigma_s[r] = sigma[src];
 }
 
-// first_b of matrix blockIdx.x (P <= SKY_MAX_P)
-__global__ __launch_bounds__(256) void k_sky_first(const double* __restrict__ lwl_s, const double* __restrict__ gp, int C, int N,
-                                                   int P, int* __restrict__ first_b)
+// first_b of matrix blockIdx.x under candidate blockIdx.y (P <= SKY_MAX_P): lwl in the upload's order, read through the
+// candidate's permutation.  One wavefront per (component, tile) interval; minimum, maximum and the NaN flag do not depend
+// on the order of the reduction, so the intervals are sky_interval's.
+__global__ __launch_bounds__(256) void k_sky_first(const double* __restrict__ lwl, const int* __restrict__ perm,
+                                                   const double* __restrict__ gp, int C, int N, int P, int* __restrict__ first_b)
 {
     __shared__ double lo[3 * SKY_MAX_P], hi[3 * SKY_MAX_P];
     __shared__ int fb[SKY_MAX_P];
-    const int b = blockIdx.x;
-    const double* x = lwl_s + (size_t)b * C * N;
-    for (int idx = threadIdx.x; idx < C * P; idx += 256) {
+    const int b = blockIdx.x, cand = blockIdx.y, B = gridDim.x;
+    const double* x = lwl + (size_t)b * C * N;
+    const int* pm = perm + (size_t)cand * N;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int idx = wave; idx < C * P; idx += 4) {
         const int c = idx / P, t = idx % P;
         const int i1 = (t + 1) * NB < N ? (t + 1) * NB : N;
-        sky_interval(x + (size_t)c * N, t * NB, i1, &lo[idx], &hi[idx]);
+        double a = __builtin_inf(), z = -__builtin_inf();
+        int nan = 0;
+        for (int i = t * NB + lane; i < i1; i += 64) {
+            const double v = x[(size_t)c * N + pm[i]];
+            nan |= !(v == v) ? 1 : 0;
+            a = v < a ? v : a;
+            z = v > z ? v : z;
+        }
+        for (int off = 32; off > 0; off >>= 1) {
+            const double a2 = __shfl_xor(a, off), z2 = __shfl_xor(z, off);
+            nan |= __shfl_xor(nan, off);
+            a = a2 < a ? a2 : a;
+            z = z2 > z ? z2 : z;
+        }
+        if (lane == 0) {
+            lo[idx] = nan ? -__builtin_inf() : a;
+            hi[idx] = nan ? __builtin_inf() : z;
+        }
     }
     __syncthreads();
     double p2[3] = {0.0, 0.0, 0.0};
@@ -148,17 +239,35 @@ __global__ __launch_bounds__(256) void k_sky_first(const double* __restrict__ lw
     __syncthreads();
     if (threadIdx.x == 0) sky_first_finish(fb, P);
     __syncthreads();
-    if ((int)threadIdx.x < P) first_b[(size_t)b * P + threadIdx.x] = fb[threadIdx.x];
+    if ((int)threadIdx.x < P) first_b[((size_t)cand * B + b) * P + threadIdx.x] = fb[threadIdx.x];
 }
 
-// the union over the batch, to pinned host memory
-__global__ void k_sky_union(const int* __restrict__ first_b, int B, int P, int* __restrict__ first_host)
+// per candidate the union over the batch and its cost; the cheapest candidate (ties: the lowest) to *cand_out, its union to
+// pinned host memory.  One block; first_b (K, B, P), K <= SKY_MAX_CAND, P <= SKY_MAX_P.
+__global__ __launch_bounds__(256) void k_sky_choose(const int* __restrict__ first_b, int B, int P, int K,
+                                                    int* __restrict__ first_host, int* __restrict__ cand_out)
 {
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= P) return;
-    int m = first_b[j];
-    for (int b = 1; b < B; ++b) m = first_b[(size_t)b * P + j] < m ? first_b[(size_t)b * P + j] : m;
-    first_host[j] = m;
+    __shared__ int fu[SKY_MAX_CAND * SKY_MAX_P];
+    __shared__ long long cost[SKY_MAX_CAND];
+    __shared__ int win;
+    for (int idx = threadIdx.x; idx < K * P; idx += 256) {
+        const int k = idx / P, j = idx % P;
+        const int* f = first_b + (size_t)k * B * P + j;
+        int m = f[0];
+        for (int b = 1; b < B; ++b) m = f[(size_t)b * P] < m ? f[(size_t)b * P] : m;
+        fu[idx] = m;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < K) cost[threadIdx.x] = sky_cost(fu + threadIdx.x * P, P);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int best = 0;
+        for (int k = 1; k < K; ++k) best = cost[k] < cost[best] ? k : best;
+        win = best;
+        cand_out[0] = best;
+    }
+    __syncthreads();
+    for (int j = threadIdx.x; j < P; j += 256) first_host[j] = fu[win * P + j];
 }
 
 }  // namespace psoap
