@@ -2,17 +2,13 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "tile_consts.hpp"
 
 namespace psoap {
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 typedef double d2 __attribute__((ext_vector_type(2)));
 
-// psoap/matrix_functions.pyx:16-17 (reference tree): c_kms and c_kms**2
-constexpr double C_KMS = 2.99792458e5;
-
-constexpr int NB = 128;       // panel width == tile edge of every blocked kernel
-constexpr int KB = 16;        // k-rows staged per LDS buffer in the MFMA tile loop
 constexpr int LDS_LD = 144;   // LDS row stride (doubles): 128 + 16 keeps ds_read_b64 fragment
                               // reads of two consecutive k-rows on disjoint bank halves
 constexpr int GEMM_THREADS = 256;
@@ -72,8 +68,6 @@ __device__ __forceinline__ T poll_word(T* p)
     return __hip_atomic_fetch_add(p, (T)0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #endif
 }
-
-__host__ __device__ inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
 // row-major upper-triangle tile index t in [0, P(P+1)/2)  ->  (ti, tj), tj >= ti
 __device__ inline void decode_upper(int t, int P, int& ti, int& tj)

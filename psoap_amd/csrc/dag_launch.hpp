@@ -1,6 +1,6 @@
-// dag_launch.hpp -- host side of the persistent kernel's launches (k_chol_dag, dag_kernel.hpp): the plan rule, the device
-// copy of a task list with its control region (DagWorkspace), the launch shape, and the one list of built instantiations
-// that the launcher dispatches over and the LDS-attribute pass walks.
+// dag_launch.hpp -- host side of the persistent kernel's launches (k_chol_dag, dag_kernel.hpp): the device copy of a task
+// list (dag_plan.hpp builds it) with its control region (DagWorkspace), the launch shape, and the one list of built
+// instantiations that the launcher dispatches over and the LDS-attribute pass walks.
 #pragma once
 #include <stdlib.h>
 #include <string.h>
@@ -8,76 +8,9 @@
 #include <vector>
 
 #include "dag_kernel.hpp"
+#include "dag_plan.hpp"
 
 namespace psoap {
-
-// ---- the plan rule ---------------------------------------------------------------------------------
-// PSOAP_DAG_SCHEME=0|1|2 pins the split scheme (experiments); -1: automatic.  Read when a plan is built.
-inline int dag_env_scheme()
-{
-    const char* e = getenv("PSOAP_DAG_SCHEME");
-    return e ? atoi(e) : -1;
-}
-
-// workgroups of a batch (Ps[b] block rows each, Mt appended column tiles) on a device with `compute_units` CUs that admits
-// `max_workers` of them
-inline int dag_batch_workers(const std::vector<int>& Ps, int Mt, int compute_units, int max_workers)
-{
-    int Pmax = 0;
-    for (int P : Ps) Pmax = P > Pmax ? P : Pmax;
-    return dag_pick_workers(dag_batch_flops(Ps, Mt), Pmax, compute_units, max_workers, (int)Ps.size());
-}
-
-// The task list of a likelihood launch (a chunk's batch, a group's): the batch's workers (*workers), the scheme
-// PSOAP_DAG_SCHEME pins, and under PSOAP_FIXED_PLAN=1 the task structure of a stream lane for every matrix, whatever the
-// batch (dag_fixed_plan).  Predict builds its plan from the same pieces with its Mt / Ms (predict_run).
-inline DagPlan dag_lnlike_plan(const std::vector<int>& Ps, int n_cus, int dag_grid, int* workers)
-{
-    *workers = dag_batch_workers(Ps, 0, n_cus, dag_grid);
-    return dag_build_tasks(Ps, *workers, dag_env_scheme(), 0, 0, dag_fixed_plan() ? dag_nominal_share(dag_grid - 1) : 0);
-}
-
-// the scheme dag_lnlike_plan's list is built for (psoap_batch_eval asks before it builds: only scheme 0 reads a skyline)
-inline int dag_lnlike_scheme(const std::vector<int>& Ps)
-{
-    if (dag_fixed_plan()) return 0;
-    const int e = dag_env_scheme();
-    int scheme = e >= 0 ? e : dag_auto_scheme(Ps);
-#ifndef PSOAP_FOLLOW
-    if (scheme == 2) scheme = 1;
-#endif
-    return scheme;
-}
-
-// The throughput list of a uniform batch inside the skyline first[0 .. P) (sky_kernels.hpp; dag_build_queue)
-inline DagPlan dag_lnlike_plan_sky(int B, int P, const int* first, int n_cus, int dag_grid, int* workers)
-{
-    const std::vector<int> Ps((size_t)B, P);
-    *workers = dag_batch_workers(Ps, 0, n_cus, dag_grid);
-    return dag_build_tasks(Ps, *workers, 0, 0, 0, 0, first);
-}
-
-// what a list executes: tiles (finals), tile-GEMM units (128-row panels of the updates), MFMA flops (updates + strip solves)
-struct DagPlanWork {
-    long long tiles = 0, units = 0;
-    double flops = 0.0;
-};
-inline DagPlanWork dag_plan_work(const DagPlan& plan)
-{
-    DagPlanWork w;
-    long long solves = 0;
-    for (const DagTask& t : plan.tasks) {
-        const int ty = t.type & DAG_TYPE_MASK;
-        w.units += (int)t.pb - (int)t.pa;
-        if (ty != DAG_PART) ++w.tiles;
-        if (ty == DAG_OFF) ++solves;
-    }
-    w.flops = 2.0 * NB * NB * NB * (double)(w.units + solves);
-    return w;
-}
-
-// the LAT kernels (and predict's, the stream's): at most two workgroups per compute unit
-inline int dag_two_per_cu(int workers, int n_cus) { return workers > 2 * n_cus ? 2 * n_cus : workers; }
 
 // ---- one task list on the device ------------------------------------------------------------------
 // The plan's tasks (and, for the ready-only hand-out, order[] and dep[]), the split-K partial tiles, and the control region:

@@ -1,0 +1,211 @@
+// plan_abi.hpp -- the pure-host entry points of the C ABI (include/psoap_gp.h): the planner's task lists and the host
+// twins of the skyline kernels.  No HIP call and no HIP header: psoap_gp.hip includes it into the library, and a host
+// compiler builds the same text into a stand-alone, sanitized program (tests/host/plan_host_check.cpp).
+#pragma once
+#include <string.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "abi_error.hpp"
+#include "dag_plan.hpp"
+#include "sky_rules.hpp"
+
+using namespace psoap;
+
+// what every plan entry point hands back: the counts, the queues' first tickets, and min(max_tasks, n_tasks) task records
+static void plan_export(const DagPlan& plan, void* out, long long max_tasks, long long* n_tasks, long long* n_slots,
+                        long long* n_ctrs, unsigned int* queue_first)
+{
+    *n_tasks = (long long)plan.tasks.size();
+    if (n_slots) *n_slots = plan.n_slots;
+    if (n_ctrs) *n_ctrs = plan.n_ctrs;
+    if (queue_first) memcpy(queue_first, plan.queues.first, sizeof plan.queues.first);
+    if (out) {
+        const long long n = max_tasks < *n_tasks ? max_tasks : *n_tasks;
+        memcpy(out, plan.tasks.data(), sizeof(DagTask) * n);
+    }
+}
+
+// Pure host function (no HIP call): the task list the persistent kernel would run for a batch of
+// B matrices with P block rows on `workers` workgroups.  Lets the scheduler be validated on a CPU.
+extern "C" int psoap_dag_plan(int B, int P, int workers, void* out, long long max_tasks, long long* n_tasks,
+                              long long* n_slots, long long* n_ctrs, unsigned int* queue_first)
+{
+    if (B < 1 || P < 1 || P > 255 || workers < 1 || !n_tasks) FAIL("psoap_dag_plan: bad arguments");
+    plan_export(dag_build_tasks(B, P, workers), out, max_tasks, n_tasks, n_slots, n_ctrs, queue_first);
+    return 0;
+}
+
+// Pure host function: the throughput list of the same batch inside the skyline first[0 .. P) (tile (q, j) exists iff
+// q >= first[j]; non-decreasing, first[j] <= max(j - 1, 0)).  All zero: psoap_dag_plan's list, byte for byte.
+extern "C" int psoap_dag_plan_sky(int B, int P, const int* first, int workers, void* out, long long max_tasks,
+                                  long long* n_tasks, long long* n_slots, long long* n_ctrs, unsigned int* queue_first)
+{
+    if (B < 1 || P < 1 || P > 255 || workers < 1 || !n_tasks || !first) FAIL("psoap_dag_plan_sky: bad arguments");
+    bool any = false;
+    for (int j = 0; j < P; ++j) {
+        if (first[j] < 0 || first[j] > (j > 0 ? j - 1 : 0) || (j > 0 && first[j] < first[j - 1]))
+            FAIL("psoap_dag_plan_sky: first must be non-decreasing with 0 <= first[j] <= max(j - 1, 0)");
+        any = any || first[j] > 0;
+    }
+    DagPlan plan = any ? dag_build_tasks(std::vector<int>((size_t)B, P), workers, 0, 0, 0, 0, first) : dag_build_tasks(B, P, workers);
+    plan_export(plan, out, max_tasks, n_tasks, n_slots, n_ctrs, queue_first);
+    return 0;
+}
+
+// One candidate order on the host, by the routines the upload-side kernels run (sky_rules.hpp): its permutation and its
+// union skyline over the batch lwl (B, c, N), gp (B, 2c); returns the envelope's cost (sky_cost)
+static long long sky_host_candidate(int c, int N, int B, const double* lwl, const double* gp, int cand, std::vector<int>& perm,
+                                    std::vector<int>& first)
+{
+    const int P = round_up(N, NB) / NB;
+    double w[3];
+    sky_cand_weights(c, cand, w);
+    std::vector<unsigned long long> key((size_t)N);
+    for (int i = 0; i < N; ++i) {
+        double v[3] = {0.0, 0.0, 0.0};
+        for (int k = 0; k < c; ++k) v[k] = lwl[(size_t)k * N + i];
+        key[i] = sky_key(sky_cand_key(c, w, v));
+    }
+    perm.resize((size_t)N);
+    first.assign((size_t)P, 0);
+    for (int i = 0; i < N; ++i) perm[i] = i;
+    std::stable_sort(perm.begin(), perm.end(), [&key](int a, int b) { return key[a] < key[b]; });
+    std::vector<double> x((size_t)c * N), lo((size_t)c * P), hi((size_t)c * P);
+    std::vector<int> fb((size_t)P);
+    for (int b = 0; b < B; ++b) {
+        for (int k = 0; k < c; ++k)
+            for (int r = 0; r < N; ++r) x[(size_t)k * N + r] = lwl[((size_t)b * c + k) * N + perm[r]];
+        for (int k = 0; k < c; ++k)
+            for (int t = 0; t < P; ++t)
+                sky_interval(x.data() + (size_t)k * N, t * NB, (t + 1) * NB < N ? (t + 1) * NB : N, &lo[(size_t)k * P + t],
+                             &hi[(size_t)k * P + t]);
+        double p2[3] = {0.0, 0.0, 0.0};
+        const bool ok = sky_gp(gp + (size_t)b * 2 * c, c, p2);
+        for (int j = 0; j < P; ++j) fb[j] = sky_first_raw(j, P, c, lo.data(), hi.data(), p2, ok);
+        sky_first_finish(fb.data(), P);
+        for (int j = 0; j < P; ++j) first[j] = (b == 0 || fb[j] < first[j]) ? fb[j] : first[j];
+    }
+    return sky_cost(first.data(), P);
+}
+
+// The first n_cand candidate orders of the batch lwl (B, c, N), gp (B, 2c): the cheapest envelope wins, ties to the lowest
+// candidate.  cand_out: the winner; perm_out (N) and first_out (ceil(N / 128)): its permutation and union skyline; any
+// output may be null.  Beyond SKY_MAX_N: the identity permutation and the dense skyline.
+static void sky_host_order(int c, int N, int B, const double* lwl, const double* gp, int n_cand, int* first_out, int* perm_out,
+                           int* cand_out)
+{
+    const int P = round_up(N, NB) / NB;
+    std::vector<int> perm((size_t)N), first((size_t)P, 0);
+    for (int i = 0; i < N; ++i) perm[i] = i;
+    int best = 0;
+    if (N <= SKY_MAX_N) {
+        long long best_cost = sky_host_candidate(c, N, B, lwl, gp, 0, perm, first);
+        std::vector<int> pk, fk;
+        for (int k = 1; k < n_cand; ++k) {
+            const long long cost = sky_host_candidate(c, N, B, lwl, gp, k, pk, fk);
+            if (cost < best_cost) {
+                best_cost = cost;
+                best = k;
+                perm.swap(pk);
+                first.swap(fk);
+            }
+        }
+    }
+    if (perm_out) memcpy(perm_out, perm.data(), sizeof(int) * (size_t)N);
+    if (first_out) memcpy(first_out, first.data(), sizeof(int) * (size_t)P);
+    if (cand_out) *cand_out = best;
+}
+
+// Pure host function, the twin of the upload-side kernels pinned to candidate 0 (the order by the first walker's first
+// component; what a handle created under PSOAP_SKY_ORDER=0 computes): the permutation and the union skyline of a batch
+// lwl (B, c, N), gp (B, 2c).  perm_out (N), first_out (ceil(N / 128)); either may be null.
+extern "C" int psoap_sky_first(int c, int N, int B, const double* lwl, const double* gp, int* first_out, int* perm_out)
+{
+    if (c < 1 || c > 3 || N < 1 || B < 1 || !lwl || !gp) FAIL("psoap_sky_first: bad arguments");
+    sky_host_order(c, N, B, lwl, gp, 1, first_out, perm_out, nullptr);
+    return 0;
+}
+
+// Pure host function, the twin of the upload-side kernels as a handle runs them: every candidate order of the batch
+// (sky_n_cand(c) of them), the cheapest envelope wins, ties to the lowest candidate.  cand_out: the winner; perm_out (N)
+// and first_out (ceil(N / 128)): its permutation and union skyline; any output may be null.
+extern "C" int psoap_sky_order(int c, int N, int B, const double* lwl, const double* gp, int* first_out, int* perm_out,
+                               int* cand_out)
+{
+    if (c < 1 || c > 3 || N < 1 || B < 1 || !lwl || !gp) FAIL("psoap_sky_order: bad arguments");
+    sky_host_order(c, N, B, lwl, gp, sky_n_cand(c), first_out, perm_out, cand_out);
+    return 0;
+}
+
+// Pure host function: the task list every lane of a stream of `lanes` lanes runs for matrices of P block rows
+// (dag_build_lane_plan); DagTask::b carries the burst marks (0x8000: the last ticket of a burst).
+extern "C" int psoap_stream_plan(int P, int lanes, int workers, int scheme, void* out, long long max_tasks,
+                                 long long* n_tasks, long long* n_slots, long long* n_ctrs, int* scheme_out)
+{
+    if (P < 1 || P > 255 || lanes < 1 || lanes > STREAM_MAX_LANES || workers < 1 || scheme < -1 || scheme > 2 || !n_tasks)
+        FAIL("psoap_stream_plan: bad arguments");
+    if (scheme < 0) scheme = dag_auto_scheme(std::vector<int>((size_t)lanes, P));
+    DagPlan plan = dag_build_lane_plan(P, lanes, workers, scheme);
+    plan_export(plan, out, max_tasks, n_tasks, n_slots, n_ctrs, nullptr);
+    if (scheme_out) *scheme_out = plan.scheme;
+    return 0;
+}
+
+// One matrix with Mt appended column tiles (predict) and, when Ms > 0, the Ms x Ms tiles of their Schur complement as
+// tasks of the same launch (DAG_SCHUR).  scheme: -1 automatic, 0 throughput, 1 latency.
+extern "C" int psoap_dag_plan_aug(int P, int Mt, int Ms, int workers, int scheme, void* out, long long max_tasks,
+                                  long long* n_tasks, long long* n_slots, long long* n_ctrs, unsigned int* queue_first)
+{
+    if (P < 1 || Mt < 0 || Ms < 0 || Ms > Mt || P + Mt > 255 || workers < 1 || !n_tasks)
+        FAIL("psoap_dag_plan_aug: bad arguments");
+    plan_export(dag_build_tasks(1, P, workers, scheme, Mt, Ms), out, max_tasks, n_tasks, n_slots, n_ctrs, queue_first);
+    return 0;
+}
+
+// The same for a heterogeneous batch: matrix b has Ps[b] block rows.
+extern "C" int psoap_dag_plan_multi(int B, const int* Ps, int workers, void* out, long long max_tasks,
+                                    long long* n_tasks, long long* n_slots, long long* n_ctrs,
+                                    unsigned int* queue_first)
+{
+    if (B < 1 || !Ps || workers < 1 || !n_tasks) FAIL("psoap_dag_plan_multi: bad arguments");
+    for (int b = 0; b < B; ++b)
+        if (Ps[b] < 1 || Ps[b] > 255) FAIL("psoap_dag_plan_multi: 1 <= P <= 255");
+    plan_export(dag_build_tasks(std::vector<int>(Ps, Ps + B), workers), out, max_tasks, n_tasks, n_slots, n_ctrs, queue_first);
+    return 0;
+}
+
+// Pure host function: the task list of a batch (Ps[b] block rows each; Mt appended column tiles and an Ms x Ms Schur block
+// for a single matrix: predict) together with the two hand-out orders of the ready-only scheme (DagPool, dag_task.hpp):
+// order[] (per queue the finals' task indices, then the parts'), dep[] (per final: the position in order[] of the last
+// part of its chain, 0xffffffff without one), n_main[8].  Empty orders (*has_pool = 0) for the throughput scheme.
+extern "C" int psoap_dag_plan_pool(int B, const int* Ps, int workers, int Mt, int Ms, int scheme, void* tasks_out,
+                                   long long max_tasks, long long* n_tasks, unsigned int* order_out, unsigned int* dep_out,
+                                   unsigned int* n_main_out, unsigned int* queue_first, int* has_pool, long long* n_ctrs)
+{
+    if (B < 1 || !Ps || workers < 1 || !n_tasks || Mt < 0 || Ms < 0 || Ms > Mt || (Mt > 0 && B != 1))
+        FAIL("psoap_dag_plan_pool: bad arguments");
+    for (int b = 0; b < B; ++b)
+        if (Ps[b] < 1 || Ps[b] + Mt > 255) FAIL("psoap_dag_plan_pool: 1 <= P (+ Mt) <= 255");
+    DagPlan plan = dag_build_tasks(std::vector<int>(Ps, Ps + B), workers, scheme, Mt, Ms);
+    if (plan.scheme >= 1 && plan.order.empty()) dag_build_pool(plan);      // (the shipped build does not use the orders)
+    plan_export(plan, tasks_out, max_tasks, n_tasks, nullptr, n_ctrs, queue_first);
+    if (has_pool) *has_pool = plan.order.empty() ? 0 : 1;
+    if (n_main_out) memcpy(n_main_out, plan.n_main, sizeof plan.n_main);
+    if (!plan.order.empty()) {      // (each by its own size -- today both equal the task count)
+        const long long n_order = (long long)plan.order.size(), n_dep = (long long)plan.dep.size();
+        if (order_out) memcpy(order_out, plan.order.data(), sizeof(unsigned int) * (max_tasks < n_order ? max_tasks : n_order));
+        if (dep_out) memcpy(dep_out, plan.dep.data(), sizeof(unsigned int) * (max_tasks < n_dep ? max_tasks : n_dep));
+    }
+    return 0;
+}
+
+// Pure host function: how many persistent workgroups a batch of B matrices (Ps[b] block rows each, Mt appended
+// column tiles) gets on a device with `compute_units` CUs that admits `max_workers` of them (dag_pick_workers).
+extern "C" int psoap_dag_pick_workers(int B, const int* Ps, int Mt, int compute_units, int max_workers, int* workers)
+{
+    if (B < 1 || !Ps || Mt < 0 || compute_units < 1 || max_workers < 1 || !workers) FAIL("psoap_dag_pick_workers: bad arguments");
+    *workers = dag_batch_workers(std::vector<int>(Ps, Ps + B), Mt, compute_units, max_workers);
+    return 0;
+}

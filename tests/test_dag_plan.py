@@ -575,7 +575,7 @@ def _simulate_pool(tasks, order, dep, n_main, first, Ps, Pt, workers, rng, windo
                                                      ([16, 13, 11, 16, 20, 7], 512, 0, 0, -1), ([47], 1, 0, 0, -1), ([20], 3, 0, 0, 1),
                                                      ([64], 512, 24, 24, -1), ([9], 256, 4, 4, 1), ([16], 8, 6, 3, 2)])
 def test_ready_only_hand_out_is_complete_and_cannot_deadlock(Ps, workers, Mt, Ms, scheme):
-    """DagPool (dag_kernel.hpp): finals in list order -- a final with a chain only once the chain's last part is taken --
+    """DagPool (dag_task.hpp): finals in list order -- a final with a chain only once the chain's last part is taken --
     and parts taken only when ready.  The orders cover every task once, a final's `dep` is its chain's last part, a chain's
     parts appear in chain order, and the hand-out played through with many, few and ONE workgroup (random queue order)
     always completes."""

@@ -1,4 +1,4 @@
-"""Ticket queues in use (PSOAP_DAG_QUEUES=8 | 4 | 2 | 1 against the automatic rule, dag_kernel.hpp: dag_queue_count) over batch
+"""Ticket queues in use (PSOAP_DAG_QUEUES=8 | 4 | 2 | 1 against the automatic rule, dag_plan.hpp: dag_queue_count) over batch
 sizes that are not multiples of 8."""
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
