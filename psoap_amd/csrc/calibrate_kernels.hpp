@@ -101,21 +101,18 @@ struct CalibInputs {
     const double* C;  // (M, N)
 };
 
-// every failure leaves through the one cleanup block at `done`
 #define CAL_TRY(expr)                                                \
     do {                                                             \
         hipError_t _e = (expr);                                      \
         if (_e != hipSuccess) {                                      \
             err = std::string(#expr) + ": " + hipGetErrorString(_e); \
-            rc = 1;                                                  \
-            goto done;                                               \
+            return 1;                                                \
         }                                                            \
     } while (0)
 
 // status: 0 ok, 1 B not positive definite, 2 C' not positive definite, 3 normal equations not positive definite
 inline int calibrate_run(const CalibInputs& in, double* fl_cor, double* X, int* status, std::string& err)
 {
-    int rc = 0;
     const int M = in.M, N = in.N, order = in.order, c = in.c;
     const int Npad = round_up(N, NB), P1 = Npad / NB;
     const int Mpad = round_up(M, NB), P2 = Mpad / NB;
@@ -126,25 +123,25 @@ inline int calibrate_run(const CalibInputs& in, double* fl_cor, double* X, int* 
     const double off = (in.lwl1 * -1.0 - in.lwl0 * 1.0) / (in.lwl1 - in.lwl0);   // numpy polyutils.mapparms
     *status = 0;
 
-    double *dK1 = nullptr, *dK2 = nullptr, *dW = nullptr, *dR = nullptr, *dTmp = nullptr, *dCal = nullptr,
-           *dFix = nullptr, *dVec = nullptr, *dGp = nullptr, *dMu = nullptr, *dM0 = nullptr, *dPart = nullptr,
-           *dG = nullptr;
-    MatAcc* dAcc = nullptr;
+    Grow<double> dK1, dK2, dW, dR, dTmp, dCal, dFix, dVec, dGp, dMu, dM0, dPart, dG;
+    Grow<MatAcc> dAcc;
+    // (declared behind the buffers, so it runs ahead of them: every return waits for the device before they go)
+    struct Drain { ~Drain() { (void)hipDeviceSynchronize(); } } drain;
     MatAcc hacc;
     std::vector<double> G((size_t)NB * NB), m0(M, in.mu), L((size_t)(order + 1) * (order + 1)), rhs(order + 1);
     GpHost gall;
     for (int k = 0; k < 6; ++k) gall.v[k] = (k < 2 * c) ? in.gp[k] : 0.0;
 
-    CAL_TRY(hipMalloc(&dK1, sizeof(double) * (size_t)Npad * ld1));
-    CAL_TRY(hipMalloc(&dK2, sizeof(double) * (size_t)Mpad * ld2));
-    CAL_TRY(hipMalloc(&dW, sizeof(double) * NB * NB));
-    CAL_TRY(hipMalloc(&dR, sizeof(double) * (size_t)std::max(Npad, Mpad)));
-    CAL_TRY(hipMalloc(&dAcc, sizeof(MatAcc) * (ACC_ROWS + 1)));      // block-row records + their total
-    CAL_TRY(hipMalloc(&dVec, sizeof(double) * (size_t)(3 * M + 2 * N)));    // lwl_cal, fl_cal, sigma_cal, fl_fixed, sigma_fixed
-    CAL_TRY(hipMalloc(&dMu, sizeof(double) * Mpad));
-    CAL_TRY(hipMalloc(&dM0, sizeof(double) * Mpad));
-    CAL_TRY(hipMalloc(&dPart, sizeof(double) * (size_t)nslab * Mpad));
-    CAL_TRY(hipMalloc(&dG, sizeof(double) * NB * NB));
+    CAL_TRY(dK1.need((size_t)Npad * ld1));
+    CAL_TRY(dK2.need((size_t)Mpad * ld2));
+    CAL_TRY(dW.need(NB * NB));
+    CAL_TRY(dR.need((size_t)std::max(Npad, Mpad)));
+    CAL_TRY(dAcc.need(ACC_ROWS + 1));      // block-row records + their total
+    CAL_TRY(dVec.need((size_t)(3 * M + 2 * N)));    // lwl_cal, fl_cal, sigma_cal, fl_fixed, sigma_fixed
+    CAL_TRY(dMu.need(Mpad));
+    CAL_TRY(dM0.need(Mpad));
+    CAL_TRY(dPart.need((size_t)nslab * Mpad));
+    CAL_TRY(dG.need(NB * NB));
     {
         double* dLwlCal = dVec;
         double* dFlCal = dVec + M;
@@ -158,9 +155,9 @@ inline int calibrate_run(const CalibInputs& in, double* fl_cor, double* X, int* 
         hipLaunchKernelGGL(k_zero, dim3(1024), dim3(256), 0, 0, dK2, (size_t)Mpad * ld2);
         hipLaunchKernelGGL(k_zero, dim3(64), dim3(256), 0, 0, dG, (size_t)NB * NB);
         if (c > 0) {
-            CAL_TRY(hipMalloc(&dCal, sizeof(double) * (size_t)c * M));
-            CAL_TRY(hipMalloc(&dFix, sizeof(double) * (size_t)c * N));
-            CAL_TRY(hipMalloc(&dGp, sizeof(double) * 6));
+            CAL_TRY(dCal.need((size_t)c * M));
+            CAL_TRY(dFix.need((size_t)c * N));
+            CAL_TRY(dGp.need(6));
             CAL_TRY(hipMemcpy(dCal, in.lwls_cal, sizeof(double) * (size_t)c * M, hipMemcpyHostToDevice));
             CAL_TRY(hipMemcpy(dFix, in.lwls_fixed, sizeof(double) * (size_t)c * N, hipMemcpyHostToDevice));
             CAL_TRY(hipMemcpy(dSigCal, in.sigma_cal, sizeof(double) * M, hipMemcpyHostToDevice));
@@ -168,9 +165,9 @@ inline int calibrate_run(const CalibInputs& in, double* fl_cor, double* X, int* 
             CAL_TRY(hipMemcpy(dGp, in.gp, sizeof(double) * 2 * c, hipMemcpyHostToDevice));
             // B = sum_k K_k(fixed) + sigma_fixed^2 (script :170-176), upper tiles, identity padding
             dim3 grid(P1 * (P1 + 1) / 2, 1);
-            if (c == 1) hipLaunchKernelGGL(k_fill_sym<1>, grid, dim3(256), 0, 0, dK1, (size_t)0, (int)ld1, N, P1, dFix, dGp, dSigFix, 1);
-            else if (c == 2) hipLaunchKernelGGL(k_fill_sym<2>, grid, dim3(256), 0, 0, dK1, (size_t)0, (int)ld1, N, P1, dFix, dGp, dSigFix, 1);
-            else hipLaunchKernelGGL(k_fill_sym<3>, grid, dim3(256), 0, 0, dK1, (size_t)0, (int)ld1, N, P1, dFix, dGp, dSigFix, 1);
+            with_components(c, [&](auto nc) {
+                hipLaunchKernelGGL(k_fill_sym<nc()>, grid, dim3(256), 0, 0, dK1, (size_t)0, (int)ld1, N, P1, dFix, dGp, dSigFix, 1);
+            });
             // C^T[j][i] = sum_k K_k(cal_i, fixed_j) (script :160-166): rows = fixed grid, columns = epoch grid
             launch_region_c((hipStream_t)0, c, dK1, ld1, Npad, N, M, dFix, (size_t)N, dCal, (size_t)M, gall, 0, 0.0);
             // A = sum_k K_k(cal) + sigma_cal^2 (script :150-158), written into pass 2's buffer
@@ -179,7 +176,7 @@ inline int calibrate_run(const CalibInputs& in, double* fl_cor, double* X, int* 
         } else {
             CAL_TRY(hipMemcpy2D(dK1, sizeof(double) * ld1, in.B, sizeof(double) * N, sizeof(double) * N, N, hipMemcpyHostToDevice));
             hipLaunchKernelGGL(k_pad_identity, dim3((Npad - N + 255) / 256 + 1), dim3(256), 0, 0, dK1, ld1, N, Npad);
-            CAL_TRY(hipMalloc(&dTmp, sizeof(double) * (size_t)M * N));
+            CAL_TRY(dTmp.need((size_t)M * N));
             CAL_TRY(hipMemcpy(dTmp, in.C, sizeof(double) * (size_t)M * N, hipMemcpyHostToDevice));
             hipLaunchKernelGGL(k_transpose_in, dim3((N + 31) / 32, (M + 31) / 32), dim3(256), 0, 0, dK1, ld1, Npad, dTmp,
                                (size_t)N, M, N);
@@ -193,7 +190,7 @@ inline int calibrate_run(const CalibInputs& in, double* fl_cor, double* X, int* 
         hipLaunchKernelGGL(k_acc_total, dim3(1), dim3(1), 0, 0, dAcc, P1, dAcc + ACC_ROWS);
         CAL_TRY(hipGetLastError());
         CAL_TRY(hipMemcpy(&hacc, dAcc + ACC_ROWS, sizeof(MatAcc), hipMemcpyDeviceToHost));
-        if (hacc.info != 0.0) { *status = 1; goto done; }
+        if (hacc.info != 0.0) { *status = 1; return 0; }
         CAL_TRY(hipMemcpy(dM0, m0.data(), sizeof(double) * M, hipMemcpyHostToDevice));
         hipLaunchKernelGGL(k_gemv_t_partial, dim3((M + 127) / 128, nslab), dim3(256), 0, 0, dK1 + Npad, ld1, Npad, M, dR, dPart);
         hipLaunchKernelGGL(k_gemv_finish, dim3((M + 255) / 256), dim3(256), 0, 0, dPart, nslab, M, dM0, dMu);     // fl'
@@ -209,7 +206,7 @@ inline int calibrate_run(const CalibInputs& in, double* fl_cor, double* X, int* 
         hipLaunchKernelGGL(k_acc_total, dim3(1), dim3(1), 0, 0, dAcc, P2, dAcc + ACC_ROWS);
         CAL_TRY(hipGetLastError());
         CAL_TRY(hipMemcpy(&hacc, dAcc + ACC_ROWS, sizeof(MatAcc), hipMemcpyDeviceToHost));
-        if (hacc.info != 0.0) { *status = 2; goto done; }
+        if (hacc.info != 0.0) { *status = 2; return 0; }
         hipLaunchKernelGGL(k_syrk_sub, dim3(1, 1), dim3(GEMM_THREADS), GEMM_LDS_BYTES, 0, dK2 + Mpad, ld2, Mpad, dG, (size_t)NB);
         CAL_TRY(hipGetLastError());
         CAL_TRY(hipMemcpy(G.data(), dG, sizeof(double) * NB * NB, hipMemcpyDeviceToHost));
@@ -224,7 +221,7 @@ inline int calibrate_run(const CalibInputs& in, double* fl_cor, double* X, int* 
         for (int j = 0; j < n; ++j) {              // in-place lower Cholesky
             double d = L[(size_t)j * n + j];
             for (int k = 0; k < j; ++k) d -= L[(size_t)j * n + k] * L[(size_t)j * n + k];
-            if (!(d > 0.0)) { *status = 3; goto done; }
+            if (!(d > 0.0)) { *status = 3; return 0; }
             d = std::sqrt(d);
             L[(size_t)j * n + j] = d;
             for (int i = j + 1; i < n; ++i) {
@@ -251,12 +248,7 @@ inline int calibrate_run(const CalibInputs& in, double* fl_cor, double* X, int* 
             fl_cor[i] = s;
         }
     }
-done:
-    (void)hipDeviceSynchronize();
-    (void)hipFree(dK1); (void)hipFree(dK2); (void)hipFree(dW); (void)hipFree(dR); (void)hipFree(dAcc); (void)hipFree(dTmp);
-    (void)hipFree(dCal); (void)hipFree(dFix); (void)hipFree(dVec); (void)hipFree(dGp); (void)hipFree(dMu); (void)hipFree(dM0);
-    (void)hipFree(dPart); (void)hipFree(dG);
-    return rc;
+    return 0;
 }
 
 }  // namespace psoap

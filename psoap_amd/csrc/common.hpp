@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
+#include <utility>
 #include "tile_consts.hpp"
 
 namespace psoap {
@@ -84,15 +86,25 @@ __device__ inline void decode_upper(int t, int P, int& ti, int& tj)
 }
 
 // ---- host ----------------------------------------------------------------------------------
-// Owning, grow-only device (or pinned host) buffer: need() allocates only when a call outgrows it (a workspace reused call
-// after call allocates nothing), and the destructor frees it on every return path.
+// The owners.  A field that holds a device resource is one of these: it is released where the field goes out of scope, on
+// every return path, and no destroy function names it.  All are move-only and convert to the raw handle.
+//
+// Grow: a grow-only device (or pinned host) buffer.  need() allocates only when a call outgrows it (a workspace reused call
+// after call allocates nothing).  `flags`: hipHostMalloc's, for the pinned form.
 template <class T, bool HOST = false>
 struct Grow {
+    static constexpr bool pinned = HOST;
     T* p = nullptr;
     size_t cap = 0;
+    unsigned int flags = hipHostMallocDefault;
     Grow() = default;
-    Grow(const Grow&) = delete;
-    Grow& operator=(const Grow&) = delete;
+    explicit Grow(unsigned int host_flags) : flags(host_flags) {}
+    Grow(Grow&& o) noexcept : p(o.p), cap(o.cap), flags(o.flags) { o.p = nullptr, o.cap = 0; }
+    Grow& operator=(Grow&& o) noexcept      // (a swap: what this one held goes with `o`)
+    {
+        std::swap(p, o.p), std::swap(cap, o.cap), std::swap(flags, o.flags);
+        return *this;
+    }
     ~Grow() { release(); }
     void release()
     {
@@ -104,13 +116,48 @@ struct Grow {
     {
         if (count <= cap && p) return hipSuccess;
         release();
-        const hipError_t e = HOST ? hipHostMalloc(reinterpret_cast<void**>(&p), sizeof(T) * count)
+        const hipError_t e = HOST ? hipHostMalloc(reinterpret_cast<void**>(&p), sizeof(T) * count, flags)
                                   : hipMalloc(reinterpret_cast<void**>(&p), sizeof(T) * count);
         if (e == hipSuccess) cap = count;
         else p = nullptr;
         return e;
     }
     operator T*() const { return p; }
+    T* operator->() const { return p; }
 };
+
+// a stream of its own (hipStreamNonBlocking)
+struct Stream {
+    hipStream_t s = nullptr;
+    Stream() = default;
+    Stream(Stream&& o) noexcept : s(o.s) { o.s = nullptr; }
+    Stream& operator=(Stream&& o) noexcept { return std::swap(s, o.s), *this; }
+    ~Stream() { release(); }
+    void release() { if (s) (void)hipStreamDestroy(s); s = nullptr; }
+    hipError_t create() { release(); return hipStreamCreateWithFlags(&s, hipStreamNonBlocking); }
+    operator hipStream_t() const { return s; }
+};
+
+// an event: an ordering mark (hipEventDisableTiming) unless it is created to be timed (hipEventDefault)
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(Event&& o) noexcept : e(o.e) { o.e = nullptr; }
+    Event& operator=(Event&& o) noexcept { return std::swap(e, o.e), *this; }
+    ~Event() { release(); }
+    void release() { if (e) (void)hipEventDestroy(e); e = nullptr; }
+    hipError_t create(unsigned int flags = hipEventDisableTiming) { release(); return hipEventCreateWithFlags(&e, flags); }
+    operator hipEvent_t() const { return e; }
+};
+
+// A runtime component count (1 .. 3) as a compile-time one: f(std::integral_constant<int, C>()), for the kernels that are
+// templates over it.
+template <class F>
+inline void with_components(int c, F&& f)
+{
+    if (c == 1) f(std::integral_constant<int, 1>());
+    else if (c == 2) f(std::integral_constant<int, 2>());
+    else f(std::integral_constant<int, 3>());
+}
 
 }  // namespace psoap

@@ -227,16 +227,10 @@ struct PredictWs {
     // what the task list in `dag` was built for
     int plan_P = -1, plan_Mt = -1, plan_workers = -1, plan_scheme = -2, plan_Ms = -1;
     int workers = 0, n_cus = 0;   // persistent workgroups the device admits; compute units
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[5] = {};
+    Stream stream;
+    Event ev[5];                  // (timed)
     Grow<double> Var, Prior, Rowx, Diag;
     PredictTimes times;
-    ~PredictWs()
-    {
-        if (stream) (void)hipStreamDestroy(stream);
-        for (auto e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
 };
 
 #define PR_TRY(expr)                                                 \
@@ -261,9 +255,7 @@ static void launch_region_c(hipStream_t st, int C, double* out, size_t ld, int c
                             const double* xrow, size_t xrs, const double* xcol, size_t xcs, const GpHost& g, int sym,
                             double nug)
 {
-    if (C == 1) launch_region<1>(st, out, ld, col0, nrows, ncols, xrow, xrs, xcol, xcs, g, sym, nug);
-    else if (C == 2) launch_region<2>(st, out, ld, col0, nrows, ncols, xrow, xrs, xcol, xcs, g, sym, nug);
-    else launch_region<3>(st, out, ld, col0, nrows, ncols, xrow, xrs, xcol, xcs, g, sym, nug);
+    with_components(C, [&](auto nc) { launch_region<nc()>(st, out, ld, col0, nrows, ncols, xrow, xrs, xcol, xcs, g, sym, nug); });
 }
 
 // The left-looking factorisation of an Npad x (Npad + Mt*128) augmented matrix [B | extra columns]:
@@ -393,8 +385,8 @@ inline int predict_run(PredictWs& ws, int mode, int c, int N, int M, const doubl
     for (int k = 0; k < 6; ++k) gall.v[k] = (k < 2 * c) ? gp[k] : 0.0;
 
     if (!ws.stream) {
-        PR_TRY(hipStreamCreateWithFlags(&ws.stream, hipStreamNonBlocking));
-        for (auto& e : ws.ev) PR_TRY(hipEventCreate(&e));
+        PR_TRY(ws.stream.create());
+        for (Event& e : ws.ev) PR_TRY(e.create(hipEventDefault));
     }
     if (Sigma_out) {
         int dev_now = 0;
@@ -519,9 +511,9 @@ inline int predict_run(PredictWs& ws, int mode, int c, int N, int M, const doubl
         hipLaunchKernelGGL(k_zero, dim3(2048), dim3(256), 0, st, dK, (size_t)Npad * ld);
         {
             dim3 grid(P * (P + 1) / 2, 1);
-            if (c == 1) hipLaunchKernelGGL(k_fill_sym<1>, grid, dim3(256), 0, st, dK, (size_t)0, (int)ld, N, P, dLwl, dGp, dSig, 1);
-            else if (c == 2) hipLaunchKernelGGL(k_fill_sym<2>, grid, dim3(256), 0, st, dK, (size_t)0, (int)ld, N, P, dLwl, dGp, dSig, 1);
-            else hipLaunchKernelGGL(k_fill_sym<3>, grid, dim3(256), 0, st, dK, (size_t)0, (int)ld, N, P, dLwl, dGp, dSig, 1);
+            with_components(c, [&](auto nc) {
+                hipLaunchKernelGGL(k_fill_sym<nc()>, grid, dim3(256), 0, st, dK, (size_t)0, (int)ld, N, P, dLwl, dGp, dSig, 1);
+            });
         }
         PR_TRY(hipGetLastError());
         if (mode == 0) {
@@ -530,7 +522,7 @@ inline int predict_run(PredictWs& ws, int mode, int c, int N, int M, const doubl
                 GpHost g1;
                 g1.v[0] = gp[2 * k];
                 g1.v[1] = gp[2 * k + 1];
-                launch_region<1>(st, dK, ld, Npad + k * M, N, M, dLwl + (size_t)k * N, 0, dPred + (size_t)k * M, 0, g1, 0, 0.0);
+                launch_region_c(st, 1, dK, ld, Npad + k * M, N, M, dLwl + (size_t)k * N, 0, dPred + (size_t)k * M, 0, g1, 0, 0.0);
             }
         } else {
             // V12 = V12_f + V12_g (+ V12_h) (:171,:279); predict_f's single V12 (:39-40) is the C = 1 case
@@ -573,7 +565,7 @@ inline int predict_run(PredictWs& ws, int mode, int c, int N, int M, const doubl
                     GpHost g1;
                     g1.v[0] = gp[2 * k];
                     g1.v[1] = gp[2 * k + 1];
-                    launch_region<1>(st, dS + (size_t)k * M * Rq_pad, (size_t)Rq_pad, k * M, M, M, dPred + (size_t)k * M, 0,
+                    launch_region_c(st, 1, dS + (size_t)k * M * Rq_pad, (size_t)Rq_pad, k * M, M, M, dPred + (size_t)k * M, 0,
                                      dPred + (size_t)k * M, 0, g1, 1, 0.0);
                 }
             } else {

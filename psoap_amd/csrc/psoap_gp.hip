@@ -43,17 +43,20 @@
 
 using namespace psoap;
 
-#define HIP_TRY(expr)                                                                              \
+#define HIP_TRY_AS(what, expr)                                                                     \
     do {                                                                                           \
         hipError_t _e = (expr);                                                                    \
         if (_e != hipSuccess) {                                                                    \
             char _buf[512];                                                                        \
-            snprintf(_buf, sizeof _buf, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, \
+            snprintf(_buf, sizeof _buf, "%s failed: %s (%s:%d)", what, hipGetErrorString(_e), __FILE__, \
                      __LINE__);                                                                    \
             g_err = _buf;                                                                          \
             return 1;                                                                              \
         }                                                                                          \
     } while (0)
+#define HIP_TRY(expr) HIP_TRY_AS(#expr, expr)
+// a handle's buffer of `count` elements: Grow::need, reported under the runtime call that refused
+#define NEED(buf, count) HIP_TRY_AS((buf).pinned ? "hipHostMalloc(" #buf ")" : "hipMalloc(" #buf ")", (buf).need(count))
 
 static const int MAX_GROUPS = 8;
 
@@ -504,35 +507,35 @@ struct DeviceScope {
     DeviceScope scope_(d);   \
     if (!scope_.ok) return 2
 // the destroy entry points: the resources go whether or not the lock could be had (a time-out there must not leak device
-// memory, nor make the caller's close() raise: hipDeviceSynchronize + hipFree disturb nobody's persistent launch)
+// memory, nor make the caller's close() raise: a device-wide synchronise and freeing memory disturb nobody's persistent launch)
 #define DEVICE_SCOPE_DESTROY(d) DeviceScope scope_(d)
 
 // One uploaded batch of proposals.  A handle keeps two, so the proposals of step k+1 travel over
 // PCIe (copy stream) while the persistent kernel still factors step k: psoap_batch_upload fills the slot
 // that is not being evaluated, psoap_batch_eval promotes the pending slot.
 struct BatchSlot {
-    double* dLwl = nullptr;    // max_batch x 3 x N
-    double* dGp = nullptr;     // max_batch x 6
+    Grow<double> dLwl;         // max_batch x 3 x N
+    Grow<double> dGp;          // max_batch x 6
     // sorted layout (sky_kernels.hpp; a handle with the skyline on): the slot's rows in the order chosen for its contents
     // (ascending in a blend of its first walker's component grids) -- what the evaluations read; dLwl keeps the upload's order
-    double* dLwlS = nullptr;   // max_batch x 3 x N
-    double* dFlS = nullptr;    // N: the handle's fl and sigma through the same permutation
-    double* dSigmaS = nullptr;
-    int* dPerm = nullptr;      // candidates x N
-    int* dCand = nullptr;      // the candidate the last upload chose: its permutation is the one of the sorted copies
-    int* dFirstB = nullptr;    // candidates x max_batch x P: first_b per candidate and matrix
-    int* hFirst = nullptr;     // P, pinned: the chosen candidate's union over the batch
-    int* dTooFast = nullptr;   // max_batch: |v| >= c flags (orbit proposals)
+    Grow<double> dLwlS;        // max_batch x 3 x N
+    Grow<double> dFlS;         // N: the handle's fl and sigma through the same permutation
+    Grow<double> dSigmaS;
+    Grow<int> dPerm;           // candidates x N
+    Grow<int> dCand;           // the candidate the last upload chose: its permutation is the one of the sorted copies
+    Grow<int> dFirstB;         // candidates x max_batch x P: first_b per candidate and matrix
+    Grow<int, true> hFirst;    // P, pinned: the chosen candidate's union over the batch
+    Grow<int> dTooFast;        // max_batch: |v| >= c flags (orbit proposals)
     bool toofast_dirty = false;  // an orbit upload may have raised flags: clear before the slot is reused
-    DagMat* dMats = nullptr;   // per-matrix records of this slot (max_batch entries)
+    Grow<DagMat> dMats;        // per-matrix records of this slot (max_batch entries)
     int mats_B = 0, mats_C = 0;
     bool mats_sorted = false;  // the records point at the sorted copies
     bool sky_valid = false;    // the last upload computed the sorted copies and the skyline (upload_end)
     int B = 0, C = 0;
     double mu = 1.0;
     std::vector<char> neg;     // per-proposal: a hyper-parameter was negative -> -inf
-    hipEvent_t evUpload = nullptr;   // copy stream: H2D (+ Doppler shift) of this slot complete
-    hipEvent_t evEval = nullptr;     // compute stream: last evaluation that read this slot complete
+    Event evUpload;            // copy stream: H2D (+ Doppler shift) of this slot complete
+    Event evEval;              // compute stream: last evaluation that read this slot complete
 };
 
 namespace psoap { struct PredictWs; struct GradWs; }
@@ -546,19 +549,19 @@ struct StreamState {
     size_t h_stride = 0;               // doubles per lane in hLw
     unsigned int n_tasks = 0, ctrs_per_lane = 0, slots_per_lane = 0;
     DagQueues queues{};
-    DagTask* dTasks = nullptr;
-    StreamLane* dLanes = nullptr;
-    StreamDev* dDev = nullptr;
-    StreamHost* hHost = nullptr;       // pinned, host-coherent
-    double* hLw = nullptr;             // pinned proposals, lane-major
-    double* hGp = nullptr;
-    double* dWs = nullptr;             // lanes x slots_per_lane partial tiles
-    char* dDag = nullptr;              // DagCtl, MatFlags[lanes], arrival counters[lanes x ctrs_per_lane]
+    Grow<DagTask> dTasks;
+    Grow<StreamLane> dLanes;
+    Grow<StreamDev> dDev;
+    Grow<StreamHost, true> hHost{hipHostMallocCoherent};       // pinned, host-coherent (as are hLw and hGp)
+    Grow<double, true> hLw{hipHostMallocCoherent};             // pinned proposals, lane-major
+    Grow<double, true> hGp{hipHostMallocCoherent};
+    Grow<double> dWs;                  // lanes x slots_per_lane partial tiles
+    Grow<char> dDag;                   // DagCtl, MatFlags[lanes], arrival counters[lanes x ctrs_per_lane]
     size_t arrive_off = 0;
-    DagMat* dMats = nullptr;
-    unsigned long long* dTlog = nullptr;
+    Grow<DagMat> dMats;
+    Grow<unsigned long long> dTlog;
     unsigned int tlog_cap = 0;
-    hipEvent_t evStart = nullptr, evExit = nullptr;   // around the resident launch (timed: the roofline of bench.py)
+    Event evStart, evExit;             // around the resident launch (timed: the roofline of bench.py)
     bool launched = false;
     unsigned long long completed_before = 0;     // StreamDev::completed when the current launch started
     double last_launch_ms = 0.0;                 // the launch that ended last (psoap_stream_pause / close measure it)
@@ -586,22 +589,20 @@ struct psoap_chunk {
     int max_batch = 0;
     size_t mat_stride = 0;
     // resident data
-    double* dFl = nullptr;
-    double* dSigma = nullptr;
-    double* dGrid = nullptr;
-    int32_t* dEpoch = nullptr;
+    Grow<double> dFl, dSigma, dGrid;
+    Grow<int32_t> dEpoch;
     int n_epochs = 0;
     // workspaces
-    double* dK = nullptr;    // max_batch x Npad x ld
-    double* dWt = nullptr;   // max_batch x 2 x 128 x 128 (the persistent kernel alternates two per matrix)
-    double* dR = nullptr;    // max_batch x Npad
-    MatAcc* dAcc = nullptr;  // max_batch
-    double* dVel = nullptr;  // max_batch x 3 x n_epochs
-    double* dOut = nullptr;  // max_batch
-    double* dDates = nullptr;  // n_epochs observation dates (orbit proposals)
-    double* dPorb = nullptr;   // max_batch x 13 orbital parameters
-    double* hPorb = nullptr;
-    unsigned int* hDagErr = nullptr;
+    Grow<double> dK;         // max_batch x Npad x ld
+    Grow<double> dWt;        // max_batch x 2 x 128 x 128 (the persistent kernel alternates two per matrix)
+    Grow<double> dR;         // max_batch x Npad
+    Grow<MatAcc> dAcc;       // max_batch
+    Grow<double> dVel;       // max_batch x 3 x n_epochs
+    Grow<double> dOut;       // max_batch
+    Grow<double> dDates;     // n_epochs observation dates (orbit proposals)
+    Grow<double> dPorb;      // max_batch x 13 orbital parameters
+    Grow<double, true> hPorb;
+    Grow<unsigned int, true> hDagErr;
     int mode = 1;            // 1 = persistent DAG kernel, 0 = staged panels
     int dag_grid = 0, n_cus = 0;   // persistent workgroups the device admits; compute units
     // task list of the persistent kernel for the current batch size (dag_lnlike_plan), and its workgroups
@@ -618,32 +619,30 @@ struct psoap_chunk {
         DagPlan plan;
         int workers;
         DagPlanWork work;
-        std::unique_ptr<Grow<DagTask>> dTasks;      // the list on the device
+        Grow<DagTask> dTasks;                       // the list on the device
     };
     std::vector<SkyPlan> sky_cache;   // the last few skyline lists, newest first
     long long sky_stats[7] = {};      // psoap_chunk_sky_stats
-    unsigned long long* dTlog = nullptr;  // optional per-task timestamps (debug)
+    Grow<unsigned long long> dTlog;       // optional per-task timestamps (debug)
     long long tlog_tasks = 0;
     // pinned host staging (one set: reused once the previous upload's copies have completed)
-    double* hLwl = nullptr;
-    double* hGp = nullptr;
-    double* hVel = nullptr;
-    double* hOut = nullptr;
+    Grow<double, true> hLwl, hGp, hVel, hOut;
     // proposal batches
     BatchSlot slot[2];
     int act = -1;            // slot of the last / running evaluation
     int pend = -1;           // uploaded, not yet evaluated
-    hipStream_t copy = nullptr;
-    hipEvent_t evStaging = nullptr;   // copy stream: the pinned staging buffers have been consumed
-    hipEvent_t evLast = nullptr;      // the most recent evaluation of this handle, whichever slot and stream it used:
+    Stream own_copy;                  // the uploads' own stream, where they have one (chunk_alloc, upload_begin) ...
+    hipStream_t copy() const { return own_copy.s ? own_copy.s : streams[0].s; }      // ... else they share the evaluation's
+    Event evStaging;                  // copy stream: the pinned staging buffers have been consumed
+    Event evLast;                     // the most recent evaluation of this handle, whichever slot and stream it used:
     bool last_recorded = false;       // the shared workspaces (K, r, Wt, acc, out) are free once it has completed
     // execution
     int groups = 2;
-    hipStream_t streams[MAX_GROUPS] = {};
-    hipEvent_t evDone[MAX_GROUPS] = {};
+    Stream streams[MAX_GROUPS];
+    Event evDone[MAX_GROUPS];
     // profiling
     bool profiling = false;
-    std::vector<hipEvent_t> evPool;
+    std::vector<Event> evPool;
     struct Rec {
         int cls;
         int e0, e1;
@@ -652,9 +651,9 @@ struct psoap_chunk {
     std::vector<Rec> recs;
     psoap_timings last = {};
     // predict workspace (grow-only; psoap_chunk_predict)
-    psoap::PredictWs* pws = nullptr;
+    std::unique_ptr<psoap::PredictWs> pws;
     // gradient workspace (allocated by the first psoap_chunk_lnlike_grad; psoap_chunk_grad_release)
-    psoap::GradWs* gws = nullptr;
+    std::unique_ptr<psoap::GradWs> gws;
     // streamed evaluation (psoap_stream_*)
     StreamState stream;
     bool dev_locked = false;     // this handle holds a reference on the device's inter-process lock (device_lock_acquire)
@@ -765,19 +764,20 @@ static int chunk_alloc(psoap_chunk* h, const double* fl, const double* sigma)
 {
     const int N = h->N;
     const size_t nb = (size_t)h->max_batch;
-    HIP_TRY(hipMalloc(&h->dFl, sizeof(double) * N));
-    HIP_TRY(hipMalloc(&h->dSigma, sizeof(double) * N));
-    HIP_TRY(hipMalloc(&h->dK, sizeof(double) * nb * h->mat_stride));
-    HIP_TRY(hipMalloc(&h->dWt, sizeof(double) * nb * WT_STRIDE));       // two Wt tiles + the mailbox per matrix
+    // (dK, the large one, ahead of every pinned buffer: a handle too large for the device has pinned nothing when it is refused)
+    NEED(h->dFl, N);
+    NEED(h->dSigma, N);
+    NEED(h->dK, nb * h->mat_stride);
+    NEED(h->dWt, nb * WT_STRIDE);                                      // two Wt tiles + the mailbox per matrix
     HIP_TRY(hipMemset(h->dWt, 0, sizeof(double) * nb * WT_STRIDE));   // the strictly upper part of every W stays zero
-    HIP_TRY(hipMalloc(&h->dR, sizeof(double) * nb * h->Npad));
-    HIP_TRY(hipMalloc(&h->dAcc, sizeof(MatAcc) * ACC_ROWS * nb));      // per matrix: one record per block row (common.hpp)
-    HIP_TRY(hipMalloc(&h->dOut, sizeof(double) * nb));
-    HIP_TRY(hipMalloc(&h->dPorb, sizeof(double) * nb * 13));
-    HIP_TRY(hipHostMalloc(&h->hPorb, sizeof(double) * nb * 13));
-    HIP_TRY(hipHostMalloc(&h->hLwl, sizeof(double) * nb * 3 * N));
-    HIP_TRY(hipHostMalloc(&h->hGp, sizeof(double) * nb * 6));
-    HIP_TRY(hipHostMalloc(&h->hOut, sizeof(double) * nb));
+    NEED(h->dR, nb * h->Npad);
+    NEED(h->dAcc, ACC_ROWS * nb);                                      // per matrix: one record per block row (common.hpp)
+    NEED(h->dOut, nb);
+    NEED(h->dPorb, nb * 13);
+    NEED(h->hPorb, nb * 13);
+    NEED(h->hLwl, nb * 3 * N);
+    NEED(h->hGp, nb * 6);
+    NEED(h->hOut, nb);
     {
         const char* e = getenv("PSOAP_SKYLINE");
         h->sky = N <= SKY_MAX_N && !(e && e[0] == '0');
@@ -787,36 +787,36 @@ static int chunk_alloc(psoap_chunk* h, const double* fl, const double* sigma)
     const size_t n_cand = h->sky_order ? SKY_MAX_CAND : 1;
     for (BatchSlot& sl : h->slot) {
         if (h->sky) {
-            HIP_TRY(hipMalloc(&sl.dLwlS, sizeof(double) * nb * 3 * N));
-            HIP_TRY(hipMalloc(&sl.dFlS, sizeof(double) * N));
-            HIP_TRY(hipMalloc(&sl.dSigmaS, sizeof(double) * N));
-            HIP_TRY(hipMalloc(&sl.dPerm, sizeof(int) * n_cand * N));
-            HIP_TRY(hipMalloc(&sl.dCand, sizeof(int)));
+            NEED(sl.dLwlS, nb * 3 * N);
+            NEED(sl.dFlS, N);
+            NEED(sl.dSigmaS, N);
+            NEED(sl.dPerm, n_cand * N);
+            NEED(sl.dCand, 1);
             HIP_TRY(hipMemset(sl.dCand, 0, sizeof(int)));
-            HIP_TRY(hipMalloc(&sl.dFirstB, sizeof(int) * n_cand * nb * h->P));
-            HIP_TRY(hipHostMalloc(&sl.hFirst, sizeof(int) * h->P));
+            NEED(sl.dFirstB, n_cand * nb * h->P);
+            NEED(sl.hFirst, h->P);
             memset(sl.hFirst, 0, sizeof(int) * h->P);
         }
-        HIP_TRY(hipMalloc(&sl.dLwl, sizeof(double) * nb * 3 * N));
-        HIP_TRY(hipMalloc(&sl.dGp, sizeof(double) * nb * 6));
-        HIP_TRY(hipMalloc(&sl.dTooFast, sizeof(int) * nb));
+        NEED(sl.dLwl, nb * 3 * N);
+        NEED(sl.dGp, nb * 6);
+        NEED(sl.dTooFast, nb);
         HIP_TRY(hipMemset(sl.dTooFast, 0, sizeof(int) * nb));
-        HIP_TRY(hipMalloc(&sl.dMats, sizeof(DagMat) * nb));
-        HIP_TRY(hipEventCreateWithFlags(&sl.evUpload, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&sl.evEval, hipEventDisableTiming));
+        NEED(sl.dMats, nb);
+        HIP_TRY(sl.evUpload.create());
+        HIP_TRY(sl.evEval.create());
     }
     // the control region of the persistent kernel, sized for max_batch here (out of memory surfaces at create, not in the
     // first evaluation): DagCtl, the matrices' flags, the arrival counters, and behind them the `taken` bitmap of the
     // ready-only hand-out -- one bit per task, at most 9 parts per tile + the early diagonal parts
     const size_t tiles = nb * (size_t)h->P * (h->P + 1) / 2;
     HIP_TRY(h->dag.ctl.need(sizeof(DagCtl) + sizeof(MatFlags) * nb + sizeof(int) * (tiles + 16 + (9 * tiles + 1024) / 32 + 8)));
-    HIP_TRY(hipHostMalloc(&h->hDagErr, 64));
+    NEED(h->hDagErr, 16);
     h->hDagErr[0] = 0;
     if (int rc = dag_workers(h->device, &h->dag_grid, &h->n_cus)) return rc;
     // one compute stream per handle; the extra streams of the staged mode's groups are created on first
     // use, so that the streams of several handles spread over the runtime's hardware queues (handles that
     // evaluate concurrently must not share one).  Uploads run on a stream of their own.
-    HIP_TRY(hipStreamCreateWithFlags(&h->streams[0], hipStreamNonBlocking));
+    HIP_TRY(h->streams[0].create());
     // The uploads share the evaluation's stream.  (Rounds 1-3 gave them a stream of their own; the copies of the next
     // proposals are blit kernels that get compute units only when the persistent launch leaves, so nothing overlapped
     // anyway -- and every stream is a hardware queue: with three per process, eight worker processes on one GPU
@@ -825,13 +825,10 @@ static int chunk_alloc(psoap_chunk* h, const double* fl, const double* sigma)
     // per process: 2.64 ms, none in 36,000.  A handle that uploads WHILE it evaluates -- the pipelined loops of bench.py and
     // EnsembleEvaluator, one process per GPU -- gets its copy stream then (upload_begin: 0.6 % on a 32-walker step);
     // PSOAP_COPY_STREAM=1 creates it here, =0 never.)
-    if (getenv("PSOAP_COPY_STREAM") && getenv("PSOAP_COPY_STREAM")[0] == '1')
-        HIP_TRY(hipStreamCreateWithFlags(&h->copy, hipStreamNonBlocking));
-    else
-        h->copy = h->streams[0];
-    for (int g = 0; g < MAX_GROUPS; ++g) HIP_TRY(hipEventCreateWithFlags(&h->evDone[g], hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&h->evStaging, hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&h->evLast, hipEventDisableTiming));
+    if (getenv("PSOAP_COPY_STREAM") && getenv("PSOAP_COPY_STREAM")[0] == '1') HIP_TRY(h->own_copy.create());
+    for (Event& e : h->evDone) HIP_TRY(e.create());
+    HIP_TRY(h->evStaging.create());
+    HIP_TRY(h->evLast.create());
     HIP_TRY(hipMemcpy(h->dFl, fl, sizeof(double) * N, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(h->dSigma, sigma, sizeof(double) * N, hipMemcpyHostToDevice));
     return 0;
@@ -857,6 +854,7 @@ extern "C" int psoap_chunk_create(psoap_chunk** out, int device, int N, const do
         // e.g. out of memory half way: give everything back (the message of the failing call is kept)
         const std::string keep = g_err;
         (void)psoap_chunk_destroy(h);
+        (void)hipGetLastError();      // (the refusal is reported here: the next launch's check must not find it again)
         g_err = keep;
         return rc;
     }
@@ -876,30 +874,7 @@ extern "C" int psoap_chunk_destroy(psoap_chunk* h)
     if (h->stream.open) (void)psoap_stream_close(h);
     (void)hipDeviceSynchronize();
     handle_unlock(h, true);
-    (void)hipFree(h->dFl); (void)hipFree(h->dSigma); (void)hipFree(h->dGrid); (void)hipFree(h->dEpoch);
-    (void)hipFree(h->dK); (void)hipFree(h->dWt); (void)hipFree(h->dR); (void)hipFree(h->dAcc);
-    (void)hipFree(h->dVel); (void)hipFree(h->dOut);
-    (void)hipHostFree(h->hDagErr); (void)hipFree(h->dTlog);
-    (void)hipFree(h->dDates); (void)hipFree(h->dPorb); (void)hipHostFree(h->hPorb);
-    (void)hipHostFree(h->hLwl); (void)hipHostFree(h->hGp); (void)hipHostFree(h->hVel); (void)hipHostFree(h->hOut);
-    for (BatchSlot& sl : h->slot) {
-        (void)hipFree(sl.dLwl); (void)hipFree(sl.dGp); (void)hipFree(sl.dTooFast); (void)hipFree(sl.dMats);
-        (void)hipFree(sl.dLwlS); (void)hipFree(sl.dFlS); (void)hipFree(sl.dSigmaS); (void)hipFree(sl.dPerm); (void)hipFree(sl.dCand);
-        (void)hipFree(sl.dFirstB); (void)hipHostFree(sl.hFirst);
-        if (sl.evUpload) (void)hipEventDestroy(sl.evUpload);
-        if (sl.evEval) (void)hipEventDestroy(sl.evEval);
-    }
-    for (int g = 0; g < MAX_GROUPS; ++g) {
-        if (h->streams[g]) (void)hipStreamDestroy(h->streams[g]);
-        if (h->evDone[g]) (void)hipEventDestroy(h->evDone[g]);
-    }
-    if (h->copy && h->copy != h->streams[0]) (void)hipStreamDestroy(h->copy);
-    if (h->evStaging) (void)hipEventDestroy(h->evStaging);
-    if (h->evLast) (void)hipEventDestroy(h->evLast);
-    for (auto e : h->evPool) (void)hipEventDestroy(e);
-    delete h->pws;
-    delete h->gws;
-    delete h;
+    delete h;        // (every buffer, stream and event is a field that owns it: common.hpp)
     return 0;
 }
 
@@ -932,12 +907,10 @@ extern "C" int psoap_chunk_set_grid(psoap_chunk* h, const double* lwl, const int
     DEVICE_SCOPE(h->device);
     if (set_dev(h)) return 1;
     HIP_TRY(hipDeviceSynchronize());
-    if (!h->dGrid) HIP_TRY(hipMalloc(&h->dGrid, sizeof(double) * h->N));
-    if (!h->dEpoch) HIP_TRY(hipMalloc(&h->dEpoch, sizeof(int32_t) * h->N));
-    if (h->dVel) { HIP_TRY(hipFree(h->dVel)); h->dVel = nullptr; }
-    if (h->hVel) { HIP_TRY(hipHostFree(h->hVel)); h->hVel = nullptr; }
-    HIP_TRY(hipMalloc(&h->dVel, sizeof(double) * (size_t)h->max_batch * 3 * n_epochs));
-    HIP_TRY(hipHostMalloc(&h->hVel, sizeof(double) * (size_t)h->max_batch * 3 * n_epochs));
+    NEED(h->dGrid, h->N);
+    NEED(h->dEpoch, h->N);
+    NEED(h->dVel, (size_t)h->max_batch * 3 * n_epochs);      // (grow-only: at least what this grid needs)
+    NEED(h->hVel, (size_t)h->max_batch * 3 * n_epochs);
     h->n_epochs = n_epochs;
     if (h->gws) h->gws->epochs_valid = false;
     HIP_TRY(hipMemcpy(h->dGrid, lwl, sizeof(double) * h->N, hipMemcpyHostToDevice));
@@ -961,7 +934,7 @@ extern "C" int psoap_chunk_dag_tasklog(psoap_chunk* h, unsigned long long* out, 
     if (set_dev(h)) return 1;
     const long long tasks = 9ll * h->max_batch * h->P * (h->P + 1) / 2 + 1024;   // <= 8 parts per tile + early DIAG parts
     if (!h->dTlog) {
-        HIP_TRY(hipMalloc(&h->dTlog, sizeof(unsigned long long) * 8 * tasks));
+        NEED(h->dTlog, (size_t)(8 * tasks));
         HIP_TRY(hipMemset(h->dTlog, 0, sizeof(unsigned long long) * 8 * tasks));
         h->tlog_tasks = tasks;
         return 0;
@@ -1025,19 +998,17 @@ static int upload_begin(psoap_chunk* h, int B, int c, const double* gp, double m
     // evaluation ago: normally long finished)
     HIP_TRY(hipEventSynchronize(h->evStaging));
     // an upload under a running evaluation: from now on the copies have a stream of their own (see psoap_chunk_create)
-    if (h->copy == h->streams[0] && h->last_recorded && !(getenv("PSOAP_COPY_STREAM") && getenv("PSOAP_COPY_STREAM")[0] == '0')) {
+    if (!h->own_copy && h->last_recorded && !(getenv("PSOAP_COPY_STREAM") && getenv("PSOAP_COPY_STREAM")[0] == '0')) {
         const hipError_t q = hipEventQuery(h->evLast);
         if (q == hipErrorNotReady) {
             (void)hipGetLastError();
-            hipStream_t cs = nullptr;
-            HIP_TRY(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
-            h->copy = cs;
+            HIP_TRY(h->own_copy.create());
         } else if (q != hipSuccess) {
             HIP_TRY(q);
         }
     }
     // the slot's device arrays: the evaluation that last read them must be over before they are rewritten
-    HIP_TRY(hipStreamWaitEvent(h->copy, sl.evEval, 0));
+    HIP_TRY(hipStreamWaitEvent(h->copy(), sl.evEval, 0));
     sl.B = B;
     sl.C = c;
     sl.mu = mu_GP;
@@ -1059,7 +1030,7 @@ static int upload_begin(psoap_chunk* h, int B, int c, const double* gp, double m
 static int clear_too_fast(psoap_chunk* h, BatchSlot& sl)
 {
     if (!sl.toofast_dirty) return 0;
-    HIP_TRY(hipMemsetAsync(sl.dTooFast, 0, sizeof(int) * (size_t)h->max_batch, h->copy));
+    HIP_TRY(hipMemsetAsync(sl.dTooFast, 0, sizeof(int) * (size_t)h->max_batch, h->copy()));
     sl.toofast_dirty = false;
     return 0;
 }
@@ -1072,14 +1043,14 @@ static bool sky_batch(const psoap_chunk* h, int B)
 
 static int upload_end(psoap_chunk* h, BatchSlot& sl)
 {
-    HIP_TRY(hipMemcpyAsync(sl.dGp, h->hGp, sizeof(double) * (size_t)sl.B * 2 * sl.C, hipMemcpyHostToDevice, h->copy));
+    HIP_TRY(hipMemcpyAsync(sl.dGp, h->hGp, sizeof(double) * (size_t)sl.B * 2 * sl.C, hipMemcpyHostToDevice, h->copy()));
     // the slot's sorted layout and its skyline (sky_kernels.hpp): functions of the slot's contents alone -- for a batch that
     // can take the throughput scheme of the persistent kernel; no other evaluation reads them, and a kernel on this stream
     // waits for a running persistent launch to leave
     sl.sky_valid = h->sky && sky_batch(h, sl.B);
     if (sl.sky_valid) {
         const int N = h->N, rows = sl.B * sl.C;
-        hipStream_t s = h->copy;
+        hipStream_t s = h->copy();
         // (the candidates ride in the grids: four launches whatever their number; the order is chosen from this upload's
         // contents, never carried over from an earlier one)
         const int K = h->sky_order ? sky_n_cand(sl.C) : 1;
@@ -1090,8 +1061,8 @@ static int upload_end(psoap_chunk* h, BatchSlot& sl)
                            sl.dLwlS, h->dFl, sl.dFlS, h->dSigma, sl.dSigmaS);
         HIP_TRY(hipGetLastError());
     }
-    HIP_TRY(hipEventRecord(h->evStaging, h->copy));
-    HIP_TRY(hipEventRecord(sl.evUpload, h->copy));
+    HIP_TRY(hipEventRecord(h->evStaging, h->copy()));
+    HIP_TRY(hipEventRecord(sl.evUpload, h->copy()));
     return 0;
 }
 
@@ -1105,7 +1076,7 @@ extern "C" int psoap_batch_upload(psoap_chunk* h, int B, int c, const double* lw
     const size_t nl = (size_t)B * c * h->N;
     memcpy(h->hLwl, lwl, sizeof(double) * nl);
     if (int rc = clear_too_fast(h, *sl)) return rc;
-    HIP_TRY(hipMemcpyAsync(sl->dLwl, h->hLwl, sizeof(double) * nl, hipMemcpyHostToDevice, h->copy));
+    HIP_TRY(hipMemcpyAsync(sl->dLwl, h->hLwl, sizeof(double) * nl, hipMemcpyHostToDevice, h->copy()));
     return upload_end(h, *sl);
 }
 
@@ -1120,7 +1091,7 @@ extern "C" int psoap_batch_upload_velocities(psoap_chunk* h, int B, int c, const
     if (int rc = upload_begin(h, B, c, gp, mu_GP, &sl)) return rc;
     const size_t nv = (size_t)B * c * h->n_epochs;
     memcpy(h->hVel, vel, sizeof(double) * nv);
-    hipStream_t s = h->copy;
+    hipStream_t s = h->copy();
     if (int rc = clear_too_fast(h, *sl)) return rc;
     HIP_TRY(hipMemcpyAsync(h->dVel, h->hVel, sizeof(double) * nv, hipMemcpyHostToDevice, s));
     dim3 grid((h->N + 255) / 256, B * c);
@@ -1138,9 +1109,7 @@ extern "C" int psoap_chunk_set_dates(psoap_chunk* h, const double* dates, int n_
     DEVICE_SCOPE(h->device);
     if (set_dev(h)) return 1;
     HIP_TRY(hipDeviceSynchronize());
-    if (h->dDates) HIP_TRY(hipFree(h->dDates));
-    h->dDates = nullptr;
-    HIP_TRY(hipMalloc(&h->dDates, sizeof(double) * n_epochs));
+    NEED(h->dDates, n_epochs);
     HIP_TRY(hipMemcpy(h->dDates, dates, sizeof(double) * n_epochs, hipMemcpyHostToDevice));
     return 0;
 }
@@ -1176,7 +1145,7 @@ extern "C" int psoap_batch_upload_orbits(psoap_chunk* h, int B, int model, const
     BatchSlot* sl = nullptr;
     if (int rc = upload_begin(h, B, c, gp, mu_GP, &sl)) return rc;
     memcpy(h->hPorb, p_orb, sizeof(double) * (size_t)B * np);
-    hipStream_t s = h->copy;
+    hipStream_t s = h->copy();
     HIP_TRY(hipMemcpyAsync(h->dPorb, h->hPorb, sizeof(double) * (size_t)B * np, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemsetAsync(sl->dTooFast, 0, sizeof(int) * (size_t)h->max_batch, s));
     sl->toofast_dirty = true;
@@ -1218,9 +1187,9 @@ static int prof_begin(psoap_chunk* h, hipStream_t s, int cls, double flops, doub
     if (!h->profiling) return 0;
     size_t need = h->recs.size() * 2 + 2;
     while (h->evPool.size() < need) {
-        hipEvent_t e;
-        HIP_TRY(hipEventCreate(&e));
-        h->evPool.push_back(e);
+        Event e;
+        HIP_TRY(e.create(hipEventDefault));      // (timed)
+        h->evPool.push_back(std::move(e));
     }
     psoap_chunk::Rec r;
     r.cls = cls;
@@ -1239,6 +1208,21 @@ static int prof_end(psoap_chunk* h, hipStream_t s)
     return 0;
 }
 
+// One bracketed step: what `launch` queues on s, booked under class cls.  A launch that returns nothing queues kernels
+// only and the launch error is asked for here; one that makes runtime calls of its own returns its status.
+template <class L>
+static int prof_launch(psoap_chunk* h, hipStream_t s, int cls, double flops, double bytes, L&& launch)
+{
+    if (prof_begin(h, s, cls, flops, bytes)) return 1;
+    if constexpr (std::is_void<decltype(launch())>::value) {
+        launch();
+        HIP_TRY(hipGetLastError());
+    } else if (int rc = launch()) {
+        return rc;
+    }
+    return prof_end(h, s);
+}
+
 template <int C>
 static void launch_fill(psoap_chunk* h, const BatchSlot& sl, hipStream_t s, int b0, int nb, int upper_only)
 {
@@ -1248,25 +1232,31 @@ static void launch_fill(psoap_chunk* h, const BatchSlot& sl, hipStream_t s, int 
                        sl.dGp + (size_t)b0 * 2 * C, h->dSigma, upper_only);
 }
 
+// The record of the handle's matrix b: its share of the workspaces, and what it reads -- proposal b of the arrays lw and gp
+// (C components each) and the noise sigma.
+static DagMat chunk_mat(const psoap_chunk* h, int b, int C, const double* lw, const double* gp, const double* sigma)
+{
+    DagMat m{};
+    m.K = h->dK + (size_t)b * h->mat_stride;
+    m.R = h->dR + (size_t)b * h->Npad;
+    m.Wt = h->dWt + (size_t)b * WT_STRIDE;
+    m.lw = lw + (size_t)b * C * h->N;
+    m.gp = gp + (size_t)b * 2 * C;
+    m.sigma = sigma;
+    m.acc = h->dAcc + (size_t)b * ACC_ROWS;
+    m.N = h->N;
+    m.Npad = h->Npad;
+    m.P = h->P;
+    m.ld = h->ld;
+    return m;
+}
+
 // per-matrix records of a slot's batch (uniform: every matrix shares N, fl, sigma)
 // (sorted: for an evaluation inside the slot's skyline, the sorted copies; everything else reads the upload's order)
 static void fill_mats(const psoap_chunk* h, const BatchSlot& sl, DagMat* out, bool sorted)
 {
-    for (int b = 0; b < sl.B; ++b) {
-        DagMat m{};
-        m.K = h->dK + (size_t)b * h->mat_stride;
-        m.R = h->dR + (size_t)b * h->Npad;
-        m.Wt = h->dWt + (size_t)b * WT_STRIDE;
-        m.lw = (sorted ? sl.dLwlS : sl.dLwl) + (size_t)b * sl.C * h->N;
-        m.gp = sl.dGp + (size_t)b * 2 * sl.C;
-        m.sigma = sorted ? sl.dSigmaS : h->dSigma;
-        m.acc = h->dAcc + (size_t)b * ACC_ROWS;
-        m.N = h->N;
-        m.Npad = h->Npad;
-        m.P = h->P;
-        m.ld = h->ld;
-        out[b] = m;
-    }
+    for (int b = 0; b < sl.B; ++b)
+        out[b] = chunk_mat(h, b, sl.C, sorted ? sl.dLwlS : sl.dLwl, sl.dGp, sorted ? sl.dSigmaS : h->dSigma);
 }
 
 // An evaluation consumes the pending upload, if there is one; otherwise it re-evaluates the active slot.
@@ -1316,7 +1306,7 @@ static int dag_prepare(psoap_chunk* h)
             if (f < 0 || f > (j > 0 ? j - 1 : 0) || (j > 0 && f < sl.hFirst[j - 1])) FAIL("psoap_batch_eval: the slot's skyline is not a monotone envelope");
             any = any || f > 0;
         }
-        if (any) first.assign(sl.hFirst, sl.hFirst + P);
+        if (any) first.assign(sl.hFirst.p, sl.hFirst.p + P);
     }
     // (a proper skyline: the evaluation reads the slot's sorted copies; a dense one the upload's order, as ever)
     if (int rc = ensure_slot_mats(h, sl, !first.empty())) return rc;
@@ -1350,9 +1340,8 @@ static int dag_prepare(psoap_chunk* h)
             e.first = first;
             e.plan = dag_lnlike_plan_sky(B, P, first.data(), h->n_cus, h->dag_grid, &e.workers);
             e.work = dag_plan_work(e.plan);
-            e.dTasks.reset(new Grow<DagTask>());
-            HIP_TRY(e.dTasks->need(e.plan.tasks.size()));
-            HIP_TRY(hipMemcpy(e.dTasks->p, e.plan.tasks.data(), sizeof(DagTask) * e.plan.tasks.size(), hipMemcpyHostToDevice));
+            HIP_TRY(e.dTasks.need(e.plan.tasks.size()));
+            HIP_TRY(hipMemcpy(e.dTasks, e.plan.tasks.data(), sizeof(DagTask) * e.plan.tasks.size(), hipMemcpyHostToDevice));
             h->sky_stats[4] += 1;
             if (h->sky_cache.size() >= 4) {
                 HIP_TRY(hipStreamSynchronize(h->streams[0]));      // (a copy out of the evicted list may still be queued)
@@ -1367,7 +1356,7 @@ static int dag_prepare(psoap_chunk* h)
         h->plan_workers = e.workers;
         h->plan_work = e.work;
         // (the list is resident: a device-to-device copy behind the previous launch, no wait on the host)
-        HIP_TRY(h->dag.load(e.plan, (size_t)h->max_batch, e.dTasks->p, h->streams[0]));
+        HIP_TRY(h->dag.load(e.plan, (size_t)h->max_batch, e.dTasks, h->streams[0]));
     }
     h->plan_first = first;
     h->plan_B = B;
@@ -1399,15 +1388,34 @@ static void launch_lnlike(const psoap_chunk* h, const DagWorkspace& w, int worke
         const int grid = n_mats < h->dag_grid ? n_mats : h->dag_grid;
         SoloCtl* ctl = reinterpret_cast<SoloCtl*>(w.ctl.p);
         const unsigned int* order = nullptr;
-        if (C == 1) hipLaunchKernelGGL(k_chol_solo<1>, dim3(grid), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, mats, order, n_mats, ctl);
-        else if (C == 2) hipLaunchKernelGGL(k_chol_solo<2>, dim3(grid), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, mats, order, n_mats, ctl);
-        else hipLaunchKernelGGL(k_chol_solo<3>, dim3(grid), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, mats, order, n_mats, ctl);
+        with_components(C, [&](auto nc) {
+            hipLaunchKernelGGL(k_chol_solo<nc()>, dim3(grid), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, mats, order, n_mats, ctl);
+        });
         return;
     }
     const DagShape sh = dag_shape(w, workers, h->n_cus);
     // (DagAug: read by the AUG kernels only)
     dag_launch<false, false>(C, sh.lat, sh.wide, sh.grid, s, mats, w.tasks, w.queues, w.flags(), w.arrive(), w.ws, w.dag_ctl(),
                              tlog, DagAug{}, StreamArgs{}, w.dag_pool());
+}
+
+// The tail of a persistent launch for one handle, queued on s (the handle's stream, or its group's) behind the launch:
+// the lnprob of the active slot's matrices, the events that give the slot and the shared workspaces back, and the
+// results and the launch's error words -- of `ctl`, the workspace that ran -- on their way to the host.
+// bracketed: k_finalize inside a profiling bracket (the handle's own launch).
+static int dag_tail(psoap_chunk* h, hipStream_t s, const DagCtl* ctl, bool bracketed)
+{
+    BatchSlot& sl = h->slot[h->act];
+    auto finalize = [&] { hipLaunchKernelGGL(k_finalize, dim3((sl.B + 63) / 64), dim3(64), 0, s, h->dAcc, h->dOut, sl.B, sl.dTooFast, h->P); };
+    if (!bracketed) finalize();
+    else if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, finalize)) return rc;
+    HIP_TRY(hipEventRecord(sl.evEval, s));
+    HIP_TRY(hipEventRecord(h->evLast, s));
+    h->last_recorded = true;
+    HIP_TRY(hipMemcpyAsync(h->hOut, h->dOut, sizeof(double) * sl.B, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(h->hDagErr, &ctl->error, 6 * sizeof(unsigned int), hipMemcpyDeviceToHost, s));
+    h->last_path = 1;
+    return 0;
 }
 
 // One persistent launch for the whole batched factorisation (dag_kernel.hpp).
@@ -1420,44 +1428,34 @@ static int eval_dag(psoap_chunk* h)
     if (int rc = dag_prepare(h)) return rc;
     HIP_TRY(hipStreamWaitEvent(s, sl.evUpload, 0));
     // no fill kernel: the DAG kernel evaluates the covariance tiles on the fly (dag_store_updated)
-    if (prof_begin(h, s, PSOAP_K_MISC, 0.0, 0.0)) return 1;
-    hipLaunchKernelGGL(k_init_rhs, dim3((h->Npad + 255) / 256, B), dim3(256), 0, s, h->dR, h->Npad, N,
-                       h->plan_first.empty() ? h->dFl : sl.dFlS, sl.mu, h->dAcc);
-    HIP_TRY(hipGetLastError());
-    // (flags, arrival counters and -- behind them -- the taken bitmap of the ready-only hand-out: one memset)
-    HIP_TRY(hipMemsetAsync(h->dag.ctl, 0, h->dag.ctl_bytes, s));
-    // PSOAP_DEBUG_POISON (tools/soak_batch_perm.py; bit 0: the matrices, bit 1: the mailboxes, bit 2: the partial-tile
-    // workspace, bit 3: the block records of the accumulators): NaN patterns in whatever the launch must write before it
-    // reads -- a task that reads ahead of its producer then returns NaN instead of the previous launch's (possibly
-    // identical) bits.  Everything poisoned here is written in full by the launch: upper-triangle tiles incl. their
-    // identity padding, the mailbox slots a follower reads, every slot a PART chain uses, one record per block row.
-    static const int poison = getenv("PSOAP_DEBUG_POISON") ? atoi(getenv("PSOAP_DEBUG_POISON")) : 0;
-    if (poison & 1) HIP_TRY(hipMemsetAsync(h->dK, 0xFF, sizeof(double) * h->mat_stride * (size_t)B, s));
-    if (poison & 2)
-        for (int b = 0; b < B; ++b)
-            HIP_TRY(hipMemsetAsync(h->dWt + (size_t)b * WT_STRIDE + (size_t)2 * NB * NB, 0xFF, sizeof(double) * MB_DOUBLES, s));
-    if ((poison & 4) && h->dag.n_slots) HIP_TRY(hipMemsetAsync(h->dag.ws, 0xFF, sizeof(double) * NB * NB * (size_t)h->dag.n_slots, s));
-    if (poison & 8) HIP_TRY(hipMemsetAsync(h->dAcc, 0xFF, sizeof(MatAcc) * ACC_ROWS * (size_t)B, s));
-    if (prof_end(h, s)) return 1;
+    if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&]() -> int {
+        hipLaunchKernelGGL(k_init_rhs, dim3((h->Npad + 255) / 256, B), dim3(256), 0, s, h->dR, h->Npad, N,
+                           h->plan_first.empty() ? h->dFl.p : sl.dFlS.p, sl.mu, h->dAcc);
+        HIP_TRY(hipGetLastError());
+        // (flags, arrival counters and -- behind them -- the taken bitmap of the ready-only hand-out: one memset)
+        HIP_TRY(hipMemsetAsync(h->dag.ctl, 0, h->dag.ctl_bytes, s));
+        // PSOAP_DEBUG_POISON (tools/soak_batch_perm.py; bit 0: the matrices, bit 1: the mailboxes, bit 2: the partial-tile
+        // workspace, bit 3: the block records of the accumulators): NaN patterns in whatever the launch must write before it
+        // reads -- a task that reads ahead of its producer then returns NaN instead of the previous launch's (possibly
+        // identical) bits.  Everything poisoned here is written in full by the launch: upper-triangle tiles incl. their
+        // identity padding, the mailbox slots a follower reads, every slot a PART chain uses, one record per block row.
+        static const int poison = getenv("PSOAP_DEBUG_POISON") ? atoi(getenv("PSOAP_DEBUG_POISON")) : 0;
+        if (poison & 1) HIP_TRY(hipMemsetAsync(h->dK, 0xFF, sizeof(double) * h->mat_stride * (size_t)B, s));
+        if (poison & 2)
+            for (int b = 0; b < B; ++b)
+                HIP_TRY(hipMemsetAsync(h->dWt + (size_t)b * WT_STRIDE + (size_t)2 * NB * NB, 0xFF, sizeof(double) * MB_DOUBLES, s));
+        if ((poison & 4) && h->dag.n_slots) HIP_TRY(hipMemsetAsync(h->dag.ws, 0xFF, sizeof(double) * NB * NB * (size_t)h->dag.n_slots, s));
+        if (poison & 8) HIP_TRY(hipMemsetAsync(h->dAcc, 0xFF, sizeof(MatAcc) * ACC_ROWS * (size_t)B, s));
+        return 0;
+        })) return rc;
     // executed MFMA flops: left-looking updates + strip solves, full 128^3 tiles
     double fl = 0.0;
     for (int q = 0; q < P; ++q) fl += 2.0 * NB * NB * ((double)q * NB * (P - q) + (double)NB * (P - q - 1));
     // (inside a skyline: the flops of the list that runs)
-    if (prof_begin(h, s, PSOAP_K_DAG, h->plan_first.empty() ? fl * B : h->plan_work.flops, 0.0)) return 1;
-    launch_lnlike(h, h->dag, h->plan_workers, C, sl.dMats, B, P, s, h->dTlog);
-    HIP_TRY(hipGetLastError());
-    if (prof_end(h, s)) return 1;
-    if (prof_begin(h, s, PSOAP_K_MISC, 0.0, 0.0)) return 1;
-    hipLaunchKernelGGL(k_finalize, dim3((B + 63) / 64), dim3(64), 0, s, h->dAcc, h->dOut, B, sl.dTooFast, P);
-    HIP_TRY(hipGetLastError());
-    if (prof_end(h, s)) return 1;
-    HIP_TRY(hipEventRecord(sl.evEval, s));
-    HIP_TRY(hipEventRecord(h->evLast, s));
-    h->last_recorded = true;
-    HIP_TRY(hipMemcpyAsync(h->hOut, h->dOut, sizeof(double) * B, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(h->hDagErr, h->dag.ctl.p + offsetof(DagCtl, error), 6 * sizeof(unsigned int),
-                           hipMemcpyDeviceToHost, s));
-    h->last_path = 1;
+    if (int rc = prof_launch(h, s, PSOAP_K_DAG, h->plan_first.empty() ? fl * B : h->plan_work.flops, 0.0,
+                             [&] { launch_lnlike(h, h->dag, h->plan_workers, C, sl.dMats, B, P, s, h->dTlog); }))
+        return rc;
+    if (int rc = dag_tail(h, s, h->dag.dag_ctl(), true)) return rc;
     g_share.dag_launches += 1;
     return 0;
 }
@@ -1493,7 +1491,7 @@ static int eval_staged(psoap_chunk* h)
     const int B = sl.B, C = sl.C, N = h->N, P = h->P;
     const int G = h->profiling ? 1 : (h->groups < B ? h->groups : B);
     for (int g = 1; g < G; ++g)
-        if (!h->streams[g]) HIP_TRY(hipStreamCreateWithFlags(&h->streams[g], hipStreamNonBlocking));
+        if (!h->streams[g]) HIP_TRY(h->streams[g].create());
     h->recs.clear();
     int gb0[MAX_GROUPS + 1];
     for (int g = 0; g <= G; ++g) gb0[g] = (int)((long long)B * g / G);
@@ -1507,17 +1505,13 @@ static int eval_staged(psoap_chunk* h)
         // the stream-group boundaries move with B, so the slot's own evEval says nothing about them)
         if (g != 0 && h->last_recorded) HIP_TRY(hipStreamWaitEvent(s, h->evLast, 0));
         const double fbytes = (double)nb * (4.0 * N * (N + 1.0) + 8.0 * (C + 1.0) * N);
-        if (prof_begin(h, s, PSOAP_K_FILL, 0.0, fbytes)) return 1;
-        if (C == 1) launch_fill<1>(h, sl, s, b0, nb, 1);
-        else if (C == 2) launch_fill<2>(h, sl, s, b0, nb, 1);
-        else launch_fill<3>(h, sl, s, b0, nb, 1);
-        HIP_TRY(hipGetLastError());
-        if (prof_end(h, s)) return 1;
-        if (prof_begin(h, s, PSOAP_K_MISC, 0.0, 0.0)) return 1;
-        hipLaunchKernelGGL(k_init_rhs, dim3((h->Npad + 255) / 256, nb), dim3(256), 0, s,
-                           h->dR + (size_t)b0 * h->Npad, h->Npad, N, h->dFl, sl.mu, h->dAcc + (size_t)b0 * ACC_ROWS);
-        HIP_TRY(hipGetLastError());
-        if (prof_end(h, s)) return 1;
+        if (int rc = prof_launch(h, s, PSOAP_K_FILL, 0.0, fbytes, [&] {
+                with_components(C, [&](auto nc) { launch_fill<nc()>(h, sl, s, b0, nb, 1); });
+            })) return rc;
+        if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
+                hipLaunchKernelGGL(k_init_rhs, dim3((h->Npad + 255) / 256, nb), dim3(256), 0, s,
+                                   h->dR + (size_t)b0 * h->Npad, h->Npad, N, h->dFl, sl.mu, h->dAcc + (size_t)b0 * ACC_ROWS);
+            })) return rc;
     }
     // panels, round-robin over the stream groups so their phases interleave on the device
     for (int p = 0; p < P; ++p) {
@@ -1527,38 +1521,32 @@ static int eval_staged(psoap_chunk* h)
             hipStream_t s = h->streams[g];
             const int b0 = gb0[g], nb = gb0[g + 1] - gb0[g];
             double* Kg = h->dK + (size_t)b0 * h->mat_stride;
-            if (p > 0) {
-                if (prof_begin(h, s, PSOAP_K_PANEL_UPDATE, 2.0 * NB * NB * (double)k0 * ntile * nb, 0.0)) return 1;
-                hipLaunchKernelGGL(k_panel_update, dim3(ntile, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, Kg,
-                                   h->mat_stride, h->ld, k0);
-                HIP_TRY(hipGetLastError());
-                if (prof_end(h, s)) return 1;
-            }
-            if (prof_begin(h, s, PSOAP_K_POTRF, 0.0, 0.0)) return 1;
-            hipLaunchKernelGGL(k_potrf_diag, dim3(nb), dim3(512), 0, s, Kg, h->mat_stride, h->ld, k0,
-                               h->dWt + (size_t)b0 * WT_STRIDE, h->dR + (size_t)b0 * h->Npad, h->Npad, h->dAcc + (size_t)b0 * ACC_ROWS,
-                               (size_t)WT_STRIDE);
-            HIP_TRY(hipGetLastError());
-            if (prof_end(h, s)) return 1;
-            if (ntile > 1) {
-                if (prof_begin(h, s, PSOAP_K_TRSM, 2.0 * NB * NB * (double)NB * (ntile - 1) * nb, 0.0)) return 1;
-                hipLaunchKernelGGL(k_trsm_strip, dim3(ntile - 1, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, Kg,
-                                   h->mat_stride, h->ld, k0, h->dWt + (size_t)b0 * WT_STRIDE,
-                                   h->dR + (size_t)b0 * h->Npad, h->Npad, (size_t)WT_STRIDE);
-                HIP_TRY(hipGetLastError());
-                if (prof_end(h, s)) return 1;
-            }
+            if (p > 0)
+                if (int rc = prof_launch(h, s, PSOAP_K_PANEL_UPDATE, 2.0 * NB * NB * (double)k0 * ntile * nb, 0.0, [&] {
+                        hipLaunchKernelGGL(k_panel_update, dim3(ntile, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, Kg,
+                                           h->mat_stride, h->ld, k0);
+                    })) return rc;
+            if (int rc = prof_launch(h, s, PSOAP_K_POTRF, 0.0, 0.0, [&] {
+                    hipLaunchKernelGGL(k_potrf_diag, dim3(nb), dim3(512), 0, s, Kg, h->mat_stride, h->ld, k0,
+                                       h->dWt + (size_t)b0 * WT_STRIDE, h->dR + (size_t)b0 * h->Npad, h->Npad,
+                                       h->dAcc + (size_t)b0 * ACC_ROWS, (size_t)WT_STRIDE);
+                })) return rc;
+            if (ntile > 1)
+                if (int rc = prof_launch(h, s, PSOAP_K_TRSM, 2.0 * NB * NB * (double)NB * (ntile - 1) * nb, 0.0, [&] {
+                        hipLaunchKernelGGL(k_trsm_strip, dim3(ntile - 1, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, Kg,
+                                           h->mat_stride, h->ld, k0, h->dWt + (size_t)b0 * WT_STRIDE,
+                                           h->dR + (size_t)b0 * h->Npad, h->Npad, (size_t)WT_STRIDE);
+                    })) return rc;
         }
     }
     // finalize per group; group 0's stream gathers the others and does the D2H
     for (int g = 0; g < G; ++g) {
         hipStream_t s = h->streams[g];
         const int b0 = gb0[g], nb = gb0[g + 1] - gb0[g];
-        if (prof_begin(h, s, PSOAP_K_MISC, 0.0, 0.0)) return 1;
-        hipLaunchKernelGGL(k_finalize, dim3((nb + 63) / 64), dim3(64), 0, s, h->dAcc + (size_t)b0 * ACC_ROWS, h->dOut + b0, nb,
-                           sl.dTooFast + b0, P);
-        HIP_TRY(hipGetLastError());
-        if (prof_end(h, s)) return 1;
+        if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
+                hipLaunchKernelGGL(k_finalize, dim3((nb + 63) / 64), dim3(64), 0, s, h->dAcc + (size_t)b0 * ACC_ROWS, h->dOut + b0, nb,
+                                   sl.dTooFast + b0, P);
+            })) return rc;
         if (g != 0) {
             HIP_TRY(hipEventRecord(h->evDone[g], s));
             HIP_TRY(hipStreamWaitEvent(h->streams[0], h->evDone[g], 0));
@@ -1600,8 +1588,8 @@ static int collect_timings(psoap_chunk* h)
 struct psoap_group {
     int device = 0;
     std::vector<psoap_chunk*> hs;
-    hipStream_t stream = nullptr;
-    hipEvent_t evDone = nullptr;
+    Stream stream;
+    Event evDone;
     DagWorkspace dag;
     Grow<DagMat> dMats;
     std::vector<int> key;      // B of every handle, then C: the plan is rebuilt when it changes
@@ -1628,8 +1616,8 @@ extern "C" int psoap_group_create(psoap_group** out, psoap_chunk* const* handles
     psoap_group* g = new psoap_group();
     g->device = handles[0]->device;
     g->hs.assign(handles, handles + n);
-    hipError_t e = hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&g->evDone, hipEventDisableTiming);
+    hipError_t e = g->stream.create();
+    if (e == hipSuccess) e = g->evDone.create();
     if (e != hipSuccess) {
         (void)psoap_group_destroy(g);
         g_err = std::string("psoap_group_create: ") + hipGetErrorString(e);
@@ -1653,8 +1641,6 @@ extern "C" int psoap_group_destroy(psoap_group* g)
         std::lock_guard<std::mutex> lk(g_groups_mu);
         g_live_groups.erase(g);
     }
-    if (g->stream) (void)hipStreamDestroy(g->stream);
-    if (g->evDone) (void)hipEventDestroy(g->evDone);
     delete g;
     return 0;
 }
@@ -1753,15 +1739,7 @@ static int group_eval_locked(psoap_group* g, bool promote)
     launch_lnlike(g->hs[0], g->dag, g->workers, C, g->dMats, total, Pmax_g, s, nullptr);
     HIP_TRY(hipGetLastError());
     for (psoap_chunk* h : g->hs) {
-        const BatchSlot& sl = h->slot[h->act];
-        hipLaunchKernelGGL(k_finalize, dim3((sl.B + 63) / 64), dim3(64), 0, s, h->dAcc, h->dOut, sl.B, sl.dTooFast, h->P);
-        HIP_TRY(hipEventRecord(sl.evEval, s));
-        HIP_TRY(hipEventRecord(h->evLast, s));
-        h->last_recorded = true;
-        HIP_TRY(hipMemcpyAsync(h->hOut, h->dOut, sizeof(double) * sl.B, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(h->hDagErr, g->dag.ctl.p + offsetof(DagCtl, error), 6 * sizeof(unsigned int),
-                               hipMemcpyDeviceToHost, s));
-        h->last_path = 1;
+        if (int rc = dag_tail(h, s, g->dag.dag_ctl(), false)) return rc;
         h->last_group = g;
     }
     g_share.dag_launches += 1;
@@ -1821,7 +1799,7 @@ static int stream_launch(psoap_chunk* h)
     // (every workgroup the device admits, at most two per compute unit: no task bound, never wide)
     dag_launch<false, true>(st.C, st.scheme >= 1, false, dag_two_per_cu(h->dag_grid, h->n_cus), s, st.dMats, st.dTasks,
                             st.queues, reinterpret_cast<MatFlags*>(st.dDag + sizeof(DagCtl)),
-                            reinterpret_cast<int*>(st.dDag + st.arrive_off), st.dWs, reinterpret_cast<DagCtl*>(st.dDag),
+                            reinterpret_cast<int*>(st.dDag + st.arrive_off), st.dWs, reinterpret_cast<DagCtl*>(st.dDag.p),
                             st.dTlog, DagAug{h->P, 0, 0, nullptr}, a, DagPool{});
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(st.evExit, s));
@@ -1846,18 +1824,6 @@ static int stream_ensure_running(psoap_chunk* h)
     return stream_launch(h);
 }
 
-static int stream_free(psoap_chunk* h)
-{
-    StreamState& st = h->stream;
-    (void)hipFree(st.dTasks); (void)hipFree(st.dLanes); (void)hipFree(st.dDev); (void)hipFree(st.dWs);
-    (void)hipFree(st.dDag); (void)hipFree(st.dMats); (void)hipFree(st.dTlog);
-    (void)hipHostFree(st.hHost); (void)hipHostFree(st.hLw); (void)hipHostFree(st.hGp);
-    if (st.evExit) (void)hipEventDestroy(st.evExit);
-    if (st.evStart) (void)hipEventDestroy(st.evStart);
-    st = StreamState();
-    return 0;
-}
-
 static int stream_open_impl(psoap_chunk* h, int c, int lanes, int scheme)
 {
     StreamState& st = h->stream;
@@ -1878,9 +1844,9 @@ static int stream_open_impl(psoap_chunk* h, int c, int lanes, int scheme)
     st.ctrs_per_lane = plan.n_ctrs + 4;
     st.slots_per_lane = plan.n_slots + 1;
     if (const char* e = getenv("PSOAP_STREAM_IDLE_MS")) st.idle_ms = atof(e) > 0.0 ? atof(e) : st.idle_ms;
-    HIP_TRY(hipMalloc(&st.dTasks, sizeof(DagTask) * plan.tasks.size()));
+    NEED(st.dTasks, plan.tasks.size());
     HIP_TRY(hipMemcpy(st.dTasks, plan.tasks.data(), sizeof(DagTask) * plan.tasks.size(), hipMemcpyHostToDevice));
-    HIP_TRY(hipMalloc(&st.dLanes, sizeof(StreamLane) * lanes));
+    NEED(st.dLanes, lanes);
     {
         // next >= n_tasks: nothing to hand out.  (Not 0xffffffff: a worker's failed fetch-add would wrap it to 0.)
         std::vector<StreamLane> init((size_t)lanes);
@@ -1888,43 +1854,30 @@ static int stream_open_impl(psoap_chunk* h, int c, int lanes, int scheme)
         for (StreamLane& ln : init) ln.next = 0x40000000u;
         HIP_TRY(hipMemcpy(st.dLanes, init.data(), sizeof(StreamLane) * lanes, hipMemcpyHostToDevice));
     }
-    HIP_TRY(hipMalloc(&st.dDev, sizeof(StreamDev)));
+    NEED(st.dDev, 1);
     {
         StreamDev init;
         memset(&init, 0, sizeof init);
         for (int x = 0; x < DAG_QUEUES; ++x) init.cur[x].lane = (unsigned int)(x % lanes);   // XCD x starts at its first lane
         HIP_TRY(hipMemcpy(st.dDev, &init, sizeof init, hipMemcpyHostToDevice));
     }
-    HIP_TRY(hipHostMalloc(&st.hHost, sizeof(StreamHost), hipHostMallocCoherent));
+    NEED(st.hHost, 1);
     memset(st.hHost, 0, sizeof(StreamHost));
     st.h_stride = (size_t)c * h->N > 16 ? (size_t)c * h->N : 16;      // (orbital parameters: up to 13 doubles)
-    HIP_TRY(hipHostMalloc(&st.hLw, sizeof(double) * (size_t)lanes * st.h_stride, hipHostMallocCoherent));
-    HIP_TRY(hipHostMalloc(&st.hGp, sizeof(double) * (size_t)lanes * 2 * c, hipHostMallocCoherent));
-    HIP_TRY(hipMalloc(&st.dWs, sizeof(double) * NB * NB * (size_t)st.slots_per_lane * lanes));
+    NEED(st.hLw, (size_t)lanes * st.h_stride);
+    NEED(st.hGp, (size_t)lanes * 2 * c);
+    NEED(st.dWs, (size_t)NB * NB * st.slots_per_lane * lanes);
     st.arrive_off = sizeof(DagCtl) + sizeof(MatFlags) * (size_t)lanes;
     const size_t dag_bytes = st.arrive_off + sizeof(int) * (size_t)st.ctrs_per_lane * lanes;
-    HIP_TRY(hipMalloc(&st.dDag, dag_bytes));
+    NEED(st.dDag, dag_bytes);
     HIP_TRY(hipMemset(st.dDag, 0, dag_bytes));
-    HIP_TRY(hipMalloc(&st.dMats, sizeof(DagMat) * lanes));
+    NEED(st.dMats, lanes);
     std::vector<DagMat> mats((size_t)lanes);
-    for (int b = 0; b < lanes; ++b) {
-        DagMat m{};
-        m.K = h->dK + (size_t)b * h->mat_stride;
-        m.R = h->dR + (size_t)b * h->Npad;
-        m.Wt = h->dWt + (size_t)b * WT_STRIDE;
-        m.lw = h->slot[0].dLwl + (size_t)b * c * h->N;       // the lane's device copy of its proposal (the dispatcher fills it)
-        m.gp = h->slot[0].dGp + (size_t)b * 2 * c;
-        m.sigma = h->dSigma;
-        m.acc = h->dAcc + (size_t)b * ACC_ROWS;
-        m.N = h->N;
-        m.Npad = h->Npad;
-        m.P = h->P;
-        m.ld = h->ld;
-        mats[b] = m;
-    }
+    // (slot 0's arrays: the lane's device copy of its proposal -- the dispatcher fills it)
+    for (int b = 0; b < lanes; ++b) mats[b] = chunk_mat(h, b, c, h->slot[0].dLwl, h->slot[0].dGp, h->dSigma);
     HIP_TRY(hipMemcpy(st.dMats, mats.data(), sizeof(DagMat) * lanes, hipMemcpyHostToDevice));
-    HIP_TRY(hipEventCreate(&st.evExit));
-    HIP_TRY(hipEventCreate(&st.evStart));
+    HIP_TRY(st.evExit.create(hipEventDefault));      // (timed)
+    HIP_TRY(st.evStart.create(hipEventDefault));
     st.lane_ticket.assign((size_t)lanes, -1);
     st.lane_seq.assign((size_t)lanes, 0ull);
     st.lane_tries.assign((size_t)lanes, 0);
@@ -1965,7 +1918,7 @@ extern "C" int psoap_stream_open(psoap_chunk* h, int c, int lanes, int scheme)
     h->slot[0].B = h->slot[1].B = 0;
     if (int rc = stream_open_impl(h, c, lanes, scheme)) {
         const std::string keep = g_err;
-        (void)stream_free(h);
+        h->stream = StreamState();      // (gives everything back)
         g_err = keep;
         return rc;
     }
@@ -2250,9 +2203,8 @@ extern "C" int psoap_stream_tasklog(psoap_chunk* h, int cap, unsigned long long*
     const size_t words = (size_t)cap * st.n_tasks * 8;
     if (!out) {
         if (st.launched) FAIL("psoap_stream_tasklog: allocate before the first submission");
-        if (st.dTlog) HIP_TRY(hipFree(st.dTlog));
-        st.dTlog = nullptr;
-        HIP_TRY(hipMalloc(&st.dTlog, sizeof(unsigned long long) * words));
+        st.dTlog.release();
+        NEED(st.dTlog, words);
         HIP_TRY(hipMemset(st.dTlog, 0, sizeof(unsigned long long) * words));
         st.tlog_cap = (unsigned int)cap;
         return 0;
@@ -2288,7 +2240,7 @@ static int stream_measure_launch(psoap_chunk* h)
     float ms = 0.f;
     HIP_TRY(hipEventElapsedTime(&ms, st.evStart, st.evExit));
     unsigned long long done = 0;
-    HIP_TRY(hipMemcpy(&done, reinterpret_cast<char*>(st.dDev) + offsetof(StreamDev, completed), sizeof done,
+    HIP_TRY(hipMemcpy(&done, reinterpret_cast<char*>(st.dDev.p) + offsetof(StreamDev, completed), sizeof done,
                       hipMemcpyDeviceToHost));
     st.last_launch_ms = ms;
     st.last_launch_matrices = (long long)(done - st.completed_before);
@@ -2350,7 +2302,7 @@ extern "C" int psoap_stream_close(psoap_chunk* h)
     __atomic_store_n(&st.hHost->close, 1u, __ATOMIC_RELEASE);
     if (pending && st.hHost->error == 0u) rc = stream_ensure_running(h);
     if (hipStreamSynchronize(h->streams[0]) != hipSuccess) rc = rc ? rc : 1;
-    (void)stream_free(h);
+    h->stream = StreamState();            // (frees what the stream held)
     handle_unlock(h, true);               // (the handle's stream is idle: nothing of this handle is in flight)
     return rc;
 }
@@ -2407,7 +2359,7 @@ extern "C" int psoap_batch_fetch(psoap_chunk* h, double* out)
     // upload pending (the pipelined loops) its copies are waited for first when the device is shared -- they are small, and
     // a collective or another process's launch must never find this process holding the lock (ranks that share a GPU
     // would wait for each other: one in the gather, one in flock)
-    if (h->pend >= 0 && share_procs(h->device) > 1) (void)hipStreamSynchronize(h->copy);
+    if (h->pend >= 0 && share_procs(h->device) > 1) (void)hipStreamSynchronize(h->copy());
     handle_unlock(h);
     if (rc_settle) return rc_settle;
     if (collect_timings(h)) return 1;
@@ -2436,7 +2388,7 @@ extern "C" int psoap_chunk_sync(psoap_chunk* h)
     hipError_t e = hipSuccess;
     for (int g = 0; g < MAX_GROUPS; ++g)
         if (h->streams[g] && e == hipSuccess) e = hipStreamSynchronize(h->streams[g]);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->copy);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->copy());
     handle_unlock(h);
     HIP_TRY(e);
     return 0;
@@ -2457,7 +2409,7 @@ extern "C" int psoap_lnlike_batch(psoap_chunk* h, int B, int c, const double* lw
     for (int b = 0; b < B; ++b) all_neg = all_neg && h->slot[h->pend].neg[b];
     if (all_neg) {  // covariance.py:317-318: -inf before any work
         for (int b = 0; b < B; ++b) out[b] = -INFINITY;
-        (void)hipStreamSynchronize(h->copy);      // (the upload's copies; nothing else was queued)
+        (void)hipStreamSynchronize(h->copy());      // (the upload's copies; nothing else was queued)
         handle_unlock(h);
         return 0;
     }
@@ -2523,7 +2475,7 @@ static int grad_run(psoap_chunk* h, int B, int c, const double* lwl, int model, 
     const size_t mstride = (size_t)Npad * ld;
     const int G = grad_group_size(B, Npad);
     const int ntiles = P * (P + 1) / 2, nslab = (Npad + 255) / 256;
-    if (!h->gws) h->gws = new GradWs();
+    if (!h->gws) h->gws.reset(new GradWs());
     GradWs& w = *h->gws;
     HIP_TRY(w.A.need((size_t)G * mstride));
     HIP_TRY(w.Wt.need((size_t)G * NB * NB));
@@ -2567,9 +2519,9 @@ static int grad_run(psoap_chunk* h, int B, int c, const double* lwl, int model, 
         }
         HIP_TRY(hipMemcpyAsync(w.Gp, gp + (size_t)b0 * 2 * c, sizeof(double) * (size_t)nb * 2 * c, hipMemcpyHostToDevice, s));
         if (prof_begin(h, s, PSOAP_K_FILL, 0.0, (double)nb * 12.0 * N * (N + 1.0))) return 1;
-        if (c == 1) launch_grad_fill_contract<1>(false, s, nb, ntiles, w.A, mstride, ld, N, Npad, P, w.Lwl, w.Gp, h->dSigma, nullptr, nullptr);
-        else if (c == 2) launch_grad_fill_contract<2>(false, s, nb, ntiles, w.A, mstride, ld, N, Npad, P, w.Lwl, w.Gp, h->dSigma, nullptr, nullptr);
-        else launch_grad_fill_contract<3>(false, s, nb, ntiles, w.A, mstride, ld, N, Npad, P, w.Lwl, w.Gp, h->dSigma, nullptr, nullptr);
+        with_components(c, [&](auto nc) {
+            launch_grad_fill_contract<nc()>(false, s, nb, ntiles, w.A, mstride, ld, N, Npad, P, w.Lwl, w.Gp, h->dSigma, nullptr, nullptr);
+        });
         hipLaunchKernelGGL(k_grad_init, dim3(ntiles, nb), dim3(256), 0, s, w.A.p, mstride, ld, Npad, P);
         HIP_TRY(hipGetLastError());
         if (prof_end(h, s)) return 1;
@@ -2609,9 +2561,9 @@ static int grad_run(psoap_chunk* h, int B, int c, const double* lwl, int model, 
         double cunits = 0.0;
         for (int tj = 0; tj < P; ++tj) cunits += (double)(tj + 1) * (P - tj);
         if (prof_begin(h, s, PSOAP_K_GRAD, tile_flops * cunits * nb, 0.0)) return 1;
-        if (c == 1) launch_grad_fill_contract<1>(true, s, nb, ntiles, w.A, mstride, ld, N, Npad, P, w.Lwl, w.Gp, nullptr, w.Alpha, w.Part);
-        else if (c == 2) launch_grad_fill_contract<2>(true, s, nb, ntiles, w.A, mstride, ld, N, Npad, P, w.Lwl, w.Gp, nullptr, w.Alpha, w.Part);
-        else launch_grad_fill_contract<3>(true, s, nb, ntiles, w.A, mstride, ld, N, Npad, P, w.Lwl, w.Gp, nullptr, w.Alpha, w.Part);
+        with_components(c, [&](auto nc) {
+            launch_grad_fill_contract<nc()>(true, s, nb, ntiles, w.A, mstride, ld, N, Npad, P, w.Lwl, w.Gp, nullptr, w.Alpha, w.Part);
+        });
         HIP_TRY(hipGetLastError());
         if (prof_end(h, s)) return 1;
         if (prof_begin(h, s, PSOAP_K_MISC, 0.0, 0.0)) return 1;
@@ -2714,8 +2666,7 @@ extern "C" int psoap_chunk_grad_release(psoap_chunk* h)
     DEVICE_SCOPE(h->device);
     if (set_dev(h)) return 1;
     HIP_TRY(hipStreamSynchronize(h->streams[0]));
-    delete h->gws;
-    h->gws = nullptr;
+    h->gws.reset();
     return 0;
 }
 
@@ -2738,12 +2689,9 @@ extern "C" int psoap_fill_sym(int device, int c, int N, const double* lwl, const
         HIP_TRY(hipMemcpy(dSig, sigma, sizeof(double) * N, hipMemcpyHostToDevice));
     }
     dim3 grid(P * P, 1);
-    if (c == 1)
-        hipLaunchKernelGGL(k_fill_sym<1>, grid, dim3(256), 0, 0, dK.p, (size_t)0, Npad, N, P, dLwl.p, dGp.p, dSig.p, 0);
-    else if (c == 2)
-        hipLaunchKernelGGL(k_fill_sym<2>, grid, dim3(256), 0, 0, dK.p, (size_t)0, Npad, N, P, dLwl.p, dGp.p, dSig.p, 0);
-    else
-        hipLaunchKernelGGL(k_fill_sym<3>, grid, dim3(256), 0, 0, dK.p, (size_t)0, Npad, N, P, dLwl.p, dGp.p, dSig.p, 0);
+    with_components(c, [&](auto nc) {
+        hipLaunchKernelGGL(k_fill_sym<nc()>, grid, dim3(256), 0, 0, dK.p, (size_t)0, Npad, N, P, dLwl.p, dGp.p, dSig.p, 0);
+    });
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpy2D(out, sizeof(double) * N, dK, sizeof(double) * Npad, sizeof(double) * N, N,
                         hipMemcpyDeviceToHost));
@@ -2945,7 +2893,7 @@ static int chunk_predict(psoap_chunk* h, int mode, int c, int M, const double* l
     DEVICE_SCOPE(h->device);
     if (int rc = enter_device(h->device)) return rc;
     if (!h->pws) {
-        h->pws = new PredictWs();
+        h->pws.reset(new PredictWs());
         h->pws->workers = dag_two_per_cu(h->dag_grid, h->n_cus);       // (as predict_ws_init)
         h->pws->n_cus = h->n_cus;
     }
@@ -2970,8 +2918,7 @@ extern "C" int psoap_chunk_predict_release(psoap_chunk* h)
     if (!h) FAIL("psoap_chunk_predict_release: null handle");
     DEVICE_SCOPE(h->device);
     if (set_dev(h)) return 1;
-    delete h->pws;
-    h->pws = nullptr;
+    h->pws.reset();
     return 0;
 }
 
