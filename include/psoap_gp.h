@@ -440,12 +440,21 @@ int psoap_dag_plan(int B, int P, int workers, void *out, long long max_tasks, lo
  *   skyline first_out (ceil(N / 128)) of a batch lwl (B, c, N), gp (B, 2c); either output may be NULL.
  * psoap_sky_order: host twin of the upload-side kernels with the choice -- the same outputs for the winning candidate, and
  *   its index in *cand_out; any output may be NULL.
+ * The list is the union's over the batch; inside it the kernel clips every matrix's updates to that matrix's own skyline
+ * (block rows above it are exact zeros of its factor: only products with zero are skipped, the results keep their bits).
+ * PSOAP_SKY_CLIP=0 at handle creation: every matrix runs the union's ranges.
+ * psoap_sky_clip: host twin of what the clip reads -- the winning candidate's per-matrix skylines first_b_out (B, ceil(N /
+ *   128)), row b that of matrix b (all zero for a matrix with an unusable hyper-parameter), and in *units_out the tile-GEMM
+ *   units they leave, summed over the batch; any output may be NULL.
  * psoap_chunk_sky_stats: out[0 .. n) of { tiles planned, tiles dense, tile-GEMM units planned, units dense, plan builds,
- *   plan-cache hits, skyline read (0 / 1) } for the handle's last evaluation; returns the number of fields (7). */
+ *   plan-cache hits, skyline read (0 / 1), units executed after the clip (== units planned where nothing is clipped) } for
+ *   the handle's last evaluation; returns the number of fields (8). */
 int psoap_dag_plan_sky(int B, int P, const int *first, int workers, void *out, long long max_tasks, long long *n_tasks,
                        long long *n_slots, long long *n_ctrs, unsigned int *queue_first /* 9 entries or NULL */);
 int psoap_sky_first(int c, int N, int B, const double *lwl, const double *gp, int *first_out, int *perm_out);
 int psoap_sky_order(int c, int N, int B, const double *lwl, const double *gp, int *first_out, int *perm_out, int *cand_out);
+int psoap_sky_clip(int c, int N, int B, const double *lwl, const double *gp, int *first_b_out, long long *units_out,
+                   int *cand_out);
 int psoap_chunk_sky_stats(psoap_chunk *h, long long *out, int n);
 /* The same for a heterogeneous batch (matrices of several chunks in one launch): matrix b has Ps[b]
  * block rows. */

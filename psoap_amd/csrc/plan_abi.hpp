@@ -55,9 +55,10 @@ extern "C" int psoap_dag_plan_sky(int B, int P, const int* first, int workers, v
 }
 
 // One candidate order on the host, by the routines the upload-side kernels run (sky_rules.hpp): its permutation and its
-// union skyline over the batch lwl (B, c, N), gp (B, 2c); returns the envelope's cost (sky_cost)
+// union skyline over the batch lwl (B, c, N), gp (B, 2c); returns the envelope's cost (sky_cost).  first_b, if given: the
+// per-matrix skylines (B, P) the union is the minimum of
 static long long sky_host_candidate(int c, int N, int B, const double* lwl, const double* gp, int cand, std::vector<int>& perm,
-                                    std::vector<int>& first)
+                                    std::vector<int>& first, std::vector<int>* first_b = nullptr)
 {
     const int P = round_up(N, NB) / NB;
     double w[3];
@@ -86,6 +87,7 @@ static long long sky_host_candidate(int c, int N, int B, const double* lwl, cons
         for (int j = 0; j < P; ++j) fb[j] = sky_first_raw(j, P, c, lo.data(), hi.data(), p2, ok);
         sky_first_finish(fb.data(), P);
         for (int j = 0; j < P; ++j) first[j] = (b == 0 || fb[j] < first[j]) ? fb[j] : first[j];
+        if (first_b) first_b->insert(first_b->end(), fb.begin(), fb.end());
     }
     return sky_cost(first.data(), P);
 }
@@ -136,6 +138,27 @@ extern "C" int psoap_sky_order(int c, int N, int B, const double* lwl, const dou
 {
     if (c < 1 || c > 3 || N < 1 || B < 1 || !lwl || !gp) FAIL("psoap_sky_order: bad arguments");
     sky_host_order(c, N, B, lwl, gp, sky_n_cand(c), first_out, perm_out, cand_out);
+    return 0;
+}
+
+// Pure host function, the twin of what the kernel's clip reads (DagMat::first): the winning candidate of psoap_sky_order and
+// its per-matrix skylines first_b_out (B, ceil(N / 128)) -- the union is their minimum over the batch -- with the tile-GEMM
+// units they leave, summed over the batch, in *units_out.  Any output may be null.  Beyond SKY_MAX_N: all zero, dense.
+extern "C" int psoap_sky_clip(int c, int N, int B, const double* lwl, const double* gp, int* first_b_out, long long* units_out,
+                              int* cand_out)
+{
+    if (c < 1 || c > 3 || N < 1 || B < 1 || !lwl || !gp) FAIL("psoap_sky_clip: bad arguments");
+    const int P = round_up(N, NB) / NB;
+    int cand = 0;
+    sky_host_order(c, N, B, lwl, gp, sky_n_cand(c), nullptr, nullptr, &cand);
+    std::vector<int> perm, first, first_b;
+    if (N <= SKY_MAX_N) sky_host_candidate(c, N, B, lwl, gp, cand, perm, first, &first_b);
+    else first_b.assign((size_t)B * P, 0);
+    long long units = 0;
+    for (int b = 0; b < B; ++b) units += sky_cost(first_b.data() + (size_t)b * P, P);
+    if (first_b_out) memcpy(first_b_out, first_b.data(), sizeof(int) * (size_t)B * P);
+    if (units_out) *units_out = units;
+    if (cand_out) *cand_out = cand;
     return 0;
 }
 

@@ -77,6 +77,8 @@ struct BatchSlot {
     Grow<int> dCand;           // the candidate the last upload chose: its permutation is the one of the sorted copies
     Grow<int> dFirstB;         // candidates x max_batch x P: first_b per candidate and matrix
     Grow<int, true> hFirst;    // P, pinned: the chosen candidate's union over the batch
+    Grow<int> dFirstW;         // max_batch x P: the chosen candidate's first_b rows -- what DagMat::first points at
+    Grow<long long, true> hClipUnits;   // 1, pinned: their cost summed over the batch, the units the clipped list executes
     Grow<int> dTooFast;        // max_batch: |v| >= c flags (orbit proposals)
     bool toofast_dirty = false;  // an orbit upload may have raised flags: clear before the slot is reused
     Grow<DagMat> dMats;        // per-matrix records of this slot (max_batch entries)
@@ -163,8 +165,10 @@ struct psoap_chunk {
     // skyline (PSOAP_SKYLINE=0, read at create, or N > SKY_MAX_N: off -- identity order, dense plan)
     bool sky = false;
     bool sky_order = true;            // PSOAP_SKY_ORDER=0, read at create: always candidate 0, the first component's order
+    bool sky_clip = true;             // PSOAP_SKY_CLIP=0, read at create: DagMat::first stays null, every matrix runs the union's ranges
     std::vector<int> plan_first;      // the skyline of the list in `dag` (empty: dense)
     DagPlanWork plan_work;            // what that list executes (a skyline list only)
+    long long clip_units = -1;        // units of that list the current evaluation executes under the clip (DagMat::first); -1: no clip
     struct SkyPlan {
         int B;
         std::vector<int> first;
@@ -174,7 +178,7 @@ struct psoap_chunk {
         Grow<DagTask> dTasks;                       // the list on the device
     };
     std::vector<SkyPlan> sky_cache;   // the last few skyline lists, newest first
-    long long sky_stats[7] = {};      // psoap_chunk_sky_stats
+    long long sky_stats[8] = {};      // psoap_chunk_sky_stats
     Grow<unsigned long long> dTlog;       // optional per-task timestamps (debug)
     long long tlog_tasks = 0;
     // pinned host staging (one set: reused once the previous upload's copies have completed)
@@ -335,6 +339,8 @@ static int chunk_alloc(psoap_chunk* h, const double* fl, const double* sigma)
         h->sky = N <= SKY_MAX_N && !(e && e[0] == '0');
         e = getenv("PSOAP_SKY_ORDER");
         h->sky_order = !(e && e[0] == '0');
+        e = getenv("PSOAP_SKY_CLIP");
+        h->sky_clip = !(e && e[0] == '0');
     }
     const size_t n_cand = h->sky_order ? SKY_MAX_CAND : 1;
     for (BatchSlot& sl : h->slot) {
@@ -348,6 +354,10 @@ static int chunk_alloc(psoap_chunk* h, const double* fl, const double* sigma)
             NEED(sl.dFirstB, n_cand * nb * h->P);
             NEED(sl.hFirst, h->P);
             memset(sl.hFirst, 0, sizeof(int) * h->P);
+            NEED(sl.dFirstW, nb * h->P);
+            HIP_TRY(hipMemset(sl.dFirstW, 0, sizeof(int) * nb * h->P));
+            NEED(sl.hClipUnits, 1);
+            sl.hClipUnits[0] = 0;
         }
         NEED(sl.dLwl, nb * 3 * N);
         NEED(sl.dGp, nb * 6);
@@ -498,15 +508,16 @@ extern "C" int psoap_chunk_dag_tasklog(psoap_chunk* h, unsigned long long* out, 
     return 0;
 }
 
-// (the pure-host entry points -- psoap_dag_plan*, psoap_sky_first / _order, psoap_stream_plan, psoap_dag_pick_workers: plan_abi.hpp)
+// (the pure-host entry points -- psoap_dag_plan*, psoap_sky_first / _order / _clip, psoap_stream_plan, psoap_dag_pick_workers: plan_abi.hpp)
 
 // The skyline of the handle's last evaluation: out[0 .. n) of { tiles planned, tiles dense, tile-GEMM units planned, units
-// dense, plan builds so far, plan-cache hits so far, 1 if the evaluation read the slot's skyline }.
+// dense, plan builds so far, plan-cache hits so far, 1 if the evaluation read the slot's skyline, units executed once
+// every matrix's updates are clipped to its own envelope (the units planned where nothing is clipped) }.
 extern "C" int psoap_chunk_sky_stats(psoap_chunk* h, long long* out, int n)
 {
     if (!h || !out || n < 0) FAIL("psoap_chunk_sky_stats: bad arguments");
-    for (int i = 0; i < n && i < 7; ++i) out[i] = h->sky_stats[i];
-    return 7;
+    for (int i = 0; i < n && i < 8; ++i) out[i] = h->sky_stats[i];
+    return 8;
 }
 
 // Debug: copy the current task list (16-byte DagTask records, ticket order) to the host.
@@ -608,7 +619,8 @@ static int upload_end(psoap_chunk* h, BatchSlot& sl)
         const int K = h->sky_order ? sky_n_cand(sl.C) : 1;
         hipLaunchKernelGGL(k_sky_perm, dim3((N + 255) / 256, K), dim3(256), 0, s, sl.dLwl, sl.C, N, sl.dPerm);
         hipLaunchKernelGGL(k_sky_first, dim3(sl.B, K), dim3(256), 0, s, sl.dLwl, sl.dPerm, sl.dGp, sl.C, N, h->P, sl.dFirstB);
-        hipLaunchKernelGGL(k_sky_choose, dim3(1), dim3(256), 0, s, sl.dFirstB, sl.B, h->P, K, sl.hFirst, sl.dCand);
+        hipLaunchKernelGGL(k_sky_choose, dim3(1), dim3(256), 0, s, sl.dFirstB, sl.B, h->P, K, sl.hFirst, sl.dCand,
+                           sl.dFirstW, sl.hClipUnits);
         hipLaunchKernelGGL(k_sky_gather, dim3((N + 255) / 256, rows + 2), dim3(256), 0, s, sl.dPerm, sl.dCand, N, rows, sl.dLwl,
                            sl.dLwlS, h->dFl, sl.dFlS, h->dSigma, sl.dSigmaS);
         HIP_TRY(hipGetLastError());
@@ -804,11 +816,14 @@ static DagMat chunk_mat(const psoap_chunk* h, int b, int C, const double* lw, co
 }
 
 // per-matrix records of a slot's batch (uniform: every matrix shares N, fl, sigma)
-// (sorted: for an evaluation inside the slot's skyline, the sorted copies; everything else reads the upload's order)
+// (sorted: for an evaluation inside the slot's skyline, the sorted copies and -- unless PSOAP_SKY_CLIP=0 -- the matrix's own
+// envelope in that order; everything else reads the upload's order and clips nothing)
 static void fill_mats(const psoap_chunk* h, const BatchSlot& sl, DagMat* out, bool sorted)
 {
-    for (int b = 0; b < sl.B; ++b)
+    for (int b = 0; b < sl.B; ++b) {
         out[b] = chunk_mat(h, b, sl.C, sorted ? sl.dLwlS : sl.dLwl, sl.dGp, sorted ? sl.dSigmaS : h->dSigma);
+        if (sorted && h->sky_clip) out[b].first = sl.dFirstW + (size_t)b * h->P;
+    }
 }
 
 // An evaluation consumes the pending upload, if there is one; otherwise it re-evaluates the active slot.
@@ -862,6 +877,8 @@ static int dag_prepare(psoap_chunk* h)
     }
     // (a proper skyline: the evaluation reads the slot's sorted copies; a dense one the upload's order, as ever)
     if (int rc = ensure_slot_mats(h, sl, !first.empty())) return rc;
+    // (the units this evaluation executes of its list once the kernel clips every matrix to its own envelope)
+    h->clip_units = !first.empty() && h->sky_clip ? sl.hClipUnits[0] : -1;
     long long units_dense = 0;
     for (int q = 0; q < P; ++q) units_dense += (long long)q * (P - q);
     h->sky_stats[1] = (long long)B * P * (P + 1) / 2;
@@ -871,6 +888,7 @@ static int dag_prepare(psoap_chunk* h)
         const bool dense = h->plan_first.empty();
         h->sky_stats[0] = dense ? h->sky_stats[1] : h->plan_work.tiles;
         h->sky_stats[2] = dense ? h->sky_stats[3] : h->plan_work.units;
+        h->sky_stats[7] = h->clip_units >= 0 ? h->clip_units : h->sky_stats[2];
     };
     if (h->plan_B == B && h->plan_first == first) {
         if (!first.empty()) h->sky_stats[5] += 1;      // (a skyline list, still loaded)
@@ -1003,8 +1021,11 @@ static int eval_dag(psoap_chunk* h)
     // executed MFMA flops: left-looking updates + strip solves, full 128^3 tiles
     double fl = 0.0;
     for (int q = 0; q < P; ++q) fl += 2.0 * NB * NB * ((double)q * NB * (P - q) + (double)NB * (P - q - 1));
-    // (inside a skyline: the flops of the list that runs)
-    if (int rc = prof_launch(h, s, PSOAP_K_DAG, h->plan_first.empty() ? fl * B : h->plan_work.flops, 0.0,
+    // (inside a skyline: the flops of the list that runs, less the panels the clip skips)
+    if (int rc = prof_launch(h, s, PSOAP_K_DAG,
+                             h->plan_first.empty() ? fl * B
+                                                     : h->plan_work.flops - 2.0 * NB * NB * NB * (double)(h->clip_units >= 0 ? h->plan_work.units - h->clip_units : 0),
+                             0.0,
                              [&] { launch_lnlike(h, h->dag, h->plan_workers, C, sl.dMats, B, P, s, h->dTlog); }))
         return rc;
     if (int rc = dag_tail(h, s, h->dag.dag_ctl(), true)) return rc;

@@ -17,7 +17,9 @@
 //   3. per candidate, form the union over the batch, first[j] = min_b first_b[j], and its cost in tile-GEMM units
 //      (sky_cost: what the planner's list executes per matrix); the smallest cost wins, ties to the lowest candidate, so
 //      the plan is never larger than candidate 0's; the winner's first[] goes to pinned host memory for the planner
-//      (dag_build_tasks);
+//      (dag_build_tasks), and the winner's first_b rows stay on the device for the kernel, which clips every matrix's
+//      updates to its own envelope inside that list (DagMat::first); what the clip leaves, sum_b sky_cost(first_b), goes
+//      to pinned host memory too;
 //   4. gather lwl, fl and sigma through the winner's permutation -- nothing is gathered for a candidate that loses.
 // The routines these kernels share with the host twins psoap_sky_first (candidate 0) and psoap_sky_order: sky_rules.hpp.
 #pragma once
@@ -117,13 +119,17 @@ __global__ __launch_bounds__(256) void k_sky_first(const double* __restrict__ lw
 }
 
 // per candidate the union over the batch and its cost; the cheapest candidate (ties: the lowest) to *cand_out, its union to
-// pinned host memory.  One block; first_b (K, B, P), K <= SKY_MAX_CAND, P <= SKY_MAX_P.
+// pinned host memory; its per-matrix rows to first_w (B, P) and their cost, summed over the batch, to *units_host (pinned).
+// One block; first_b (K, B, P), K <= SKY_MAX_CAND, P <= SKY_MAX_P.
 __global__ __launch_bounds__(256) void k_sky_choose(const int* __restrict__ first_b, int B, int P, int K,
-                                                    int* __restrict__ first_host, int* __restrict__ cand_out)
+                                                    int* __restrict__ first_host, int* __restrict__ cand_out,
+                                                    int* __restrict__ first_w, long long* __restrict__ units_host)
 {
     __shared__ int fu[SKY_MAX_CAND * SKY_MAX_P];
     __shared__ long long cost[SKY_MAX_CAND];
+    __shared__ unsigned long long units;
     __shared__ int win;
+    if (threadIdx.x == 0) units = 0ull;
     for (int idx = threadIdx.x; idx < K * P; idx += 256) {
         const int k = idx / P, j = idx % P;
         const int* f = first_b + (size_t)k * B * P + j;
@@ -142,6 +148,11 @@ __global__ __launch_bounds__(256) void k_sky_choose(const int* __restrict__ firs
     }
     __syncthreads();
     for (int j = threadIdx.x; j < P; j += 256) first_host[j] = fu[win * P + j];
+    const int* fw = first_b + (size_t)win * B * P;
+    for (int idx = threadIdx.x; idx < B * P; idx += 256) first_w[idx] = fw[idx];
+    for (int b = threadIdx.x; b < B; b += 256) atomicAdd(&units, (unsigned long long)sky_cost(fw + (size_t)b * P, P));
+    __syncthreads();
+    if (threadIdx.x == 0) units_host[0] = (long long)units;
 }
 
 }  // namespace psoap
