@@ -181,6 +181,36 @@ int psoap_orbit_velocity_jacobian(int device, int model, int B, const double *p_
                                   int n_dates, const double *dates, double *vel_out,
                                   double *jac_out);
 
+/* ---- Fisher information of the likelihood ----------------------------------------
+ * For one matrix (lwl (c, N), gp (2c)) and T tangents in (grid, hyper-parameter)
+ * space -- tan_lwl (T, c, N), or NULL for zeros, and tan_gp (T, 2c), a tangent's
+ * covariance derivative being, with d = lwl[c][n] - lwl[c][m] and e = exp(p_c d^2),
+ *   K_t[m][n] = sum_c e (2 a_c da_tc + a_c^2 c_kms^2 / l_c^3 d^2 dl_tc
+ *                        + a_c^2 2 p_c d (dx_tc[n] - dx_tc[m])) --
+ *   fisher    (T, T)  F_st = 1/2 tr(K^-1 K_s K^-1 K_t), both triangles, F == F^T bit
+ *                     for bit;
+ *   fisher_mu (1)     1^T K^-1 1, the information of mu_GP (its cross terms with the
+ *                     other parameters are zero in expectation); may be NULL.
+ * F does not depend on the data.  The factorisation of [K | I] runs as for the
+ * gradient, in the gradient's workspace for one matrix; K^-1 = W^T W is stored, and
+ * per tangent K_t, Z = K_t K^-1 and the upper tiles of G_t = 1/2 (K^-1 Z + Z^T K^-1)
+ * follow, G_t contracted in the accumulators with the derivative of K in every
+ * parameter (csrc/fisher_kernels.hpp; (1 + 4 T) N^3 flops).  No atomics, every sum in an order
+ * fixed by (N, c, T): the same arguments give the same bits, and a subsequence of
+ * the tangents gives the bits of the entries it shares.
+ * Conventions: a negative hyper-parameter or a matrix that is not positive definite
+ * gives NaN in every output and status 0; T < 1 or T > 32 and an open stream on the
+ * handle are refused (non-zero status, psoap_last_error).
+ * Workspace: 24 Npad^2 bytes (K^-1, K_t, Z) beyond the gradient's 16 Npad^2 for one
+ * matrix, whatever T is, allocated by the first call, kept with the handle and freed
+ * by psoap_chunk_fisher_release (the gradient's by psoap_chunk_grad_release) or
+ * psoap_chunk_destroy.  The handle's uploaded batches, their results and the
+ * likelihood workspaces are left as they are. */
+int psoap_chunk_fisher(psoap_chunk *h, int c, const double *lwl, const double *gp,
+                       int T, const double *tan_lwl, const double *tan_gp,
+                       double *fisher, double *fisher_mu);
+int psoap_chunk_fisher_release(psoap_chunk *h);
+
 /* Split-phase form of psoap_lnlike_batch: upload (H2D, async, on a copy stream of
  * its own), eval (kernels only, async), fetch (sync + D2H of B doubles).
  * A handle holds TWO proposal batches: an upload always goes to the one that is

@@ -145,6 +145,29 @@ class ChunkHandle:
         """Free the gradient workspace (16 Npad^2 bytes per matrix of a group); the next ``lnlike_grad`` allocates it again."""
         check(self._L.psoap_chunk_grad_release(self._h), "psoap_chunk_grad_release")
 
+    def fisher(self, lwls, gp, tan_gp, tan_lwl=None, want_mu: bool = False):
+        """Fisher information of the likelihood at ``lwls`` (c, N), ``gp`` (2c,) along T <= 32 tangents (include/psoap_gp.h:
+        psoap_chunk_fisher): ``tan_gp`` (T, 2c) and ``tan_lwl`` (T, c, N) (``None``: zeros) -> ``F (T, T)``,
+        ``F_st = 1/2 tr(K^-1 K_s K^-1 K_t)``, symmetric bit for bit; with ``want_mu`` ``(F, F_mu)``, ``F_mu = 1^T K^-1 1``.
+        A negative hyper-parameter or a matrix that is not positive definite gives NaN in every entry."""
+        lwls = as_f64(np.atleast_2d(lwls))
+        c = lwls.shape[0]
+        lwls = as_f64(lwls, (c, self.N))
+        gp = as_f64(gp, (2 * c,))
+        tan_gp = as_f64(np.atleast_2d(as_f64(tan_gp)))
+        T = tan_gp.shape[0]
+        tan_gp = as_f64(tan_gp, (T, 2 * c))
+        if tan_lwl is not None:
+            tan_lwl = as_f64(tan_lwl, (T, c, self.N))
+        F, mu = np.empty((T, T)), np.empty(1)
+        check(self._L.psoap_chunk_fisher(self._h, c, dptr(lwls), dptr(gp), T, None if tan_lwl is None else dptr(tan_lwl),
+                                         dptr(tan_gp), dptr(F), dptr(mu) if want_mu else None), "psoap_chunk_fisher")
+        return (F, float(mu[0])) if want_mu else F
+
+    def fisher_release(self):
+        """Free the Fisher workspace (24 Npad^2 bytes); the next ``fisher`` allocates it again."""
+        check(self._L.psoap_chunk_fisher_release(self._h), "psoap_chunk_fisher_release")
+
     def upload(self, lwls, gps, mu_GP: float = 1.0):
         lwls = as_f64(lwls)
         B, c, _ = lwls.shape

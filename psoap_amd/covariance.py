@@ -278,6 +278,28 @@ def lnlike_grad(lwls, fl, sigma, gp, mu_GP=1.0):
     return np.float64(lnp), g_gp, g_lwl, np.float64(g_mu)
 
 
+def fisher_information(lwls, fl, sigma, gp):
+    """The ``(2c, 2c)`` Fisher information of the hyper-parameters ``(amp_0, l_0, amp_1, ...)`` of one chunk,
+    ``F_st = 1/2 tr(K^-1 dK/dtheta_s K^-1 dK/dtheta_t)``, evaluated on the device (``ChunkHandle.fisher`` with unit
+    tangents): its inverse is the Laplace covariance of an ``optimize_GP`` fit.  It does not depend on ``fl``, which only
+    names the cached chunk, as for ``lnlike_grad``.  Degenerate input follows ``lnlike_grad``: a negative hyper-parameter
+    or a matrix that is not positive definite gives NaN in every entry."""
+    gp = [float(g) for g in gp]
+    lw = np.stack([as_f64(w) for w in np.atleast_2d(lwls)])
+    if len(gp) != 2 * lw.shape[0]:
+        raise ValueError(f"gp must hold {2 * lw.shape[0]} values for {lw.shape[0]} component(s)")
+    if any(g < 0.0 for g in gp):
+        return np.full((len(gp), len(gp)), np.nan)
+    if any(l == 0.0 for l in gp[1::2]):
+        raise ZeroDivisionError("float division")
+    if not _matrix_is_finite(lw, sigma, gp):
+        raise ValueError(_NONFINITE)
+    h = _chunk_for(fl, sigma)
+    if not hasattr(h, "fisher"):
+        raise _lib.PsoapError("fisher_information needs the device in this process (PSOAP_GPU_SERVER serves values only)")
+    return h.fisher(lw, gp, np.eye(len(gp)))
+
+
 def velocity_gradient(grad_lwl, epoch_index, n_epochs):
     """``dlnL/dv[c, e]`` from ``dlnL/dlwl[c, i]``: the rest-frame grids are ``lwl - v[c, epoch]/c_kms``
     (``data.replicate_wls``), so ``dlnL/dv[c, e] = -(1/c_kms) sum_{i in epoch e} dlnL/dlwl[c, i]``.

@@ -1,0 +1,381 @@
+// fisher_kernels.hpp -- Fisher information of the GP likelihood (not in the reference).
+//
+//   F_st = 1/2 tr(K^-1 K_s K^-1 K_t) = 1/2 sum_mn K_s[m,n] G_t[m,n],  G_t = K^-1 K_t K^-1
+// for tangents t = (dx_t (c, N), da_tc, dl_tc) in (grid, hyper-parameter) space, with d = x_c[n] - x_c[m], e_cmn = exp(p_c d^2):
+//   K_t[m,n] = sum_c e_cmn (2 a_c da_tc + a_c^2 c_kms^2 / l_c^3 d^2 dl_tc + a_c^2 2 p_c d (dx_tc[n] - dx_tc[m]))
+// F is positive semi-definite and does not depend on the data.  F_mu = 1^T K^-1 1 is the information of mu_GP.
+//
+// The staged factorisation of [K | I] runs as for the gradient (grad_kernels.hpp) and leaves W = U^-T.  Then
+//   k_fisher_kinv             K^-1 = W^T W, tile by tile with the K-loop bounds of k_grad_contract, stored with both triangles
+//                             (rows and columns >= N come out as the identity: K is the identity there)
+//   per tangent t:
+//   k_fisher_tangent_fill<C>  K_t, every tile, exp() as the fills evaluate it; rows and columns >= N exact zeros
+//   k_fisher_gemm             Z = K_t K^-1 (every tile, K = Npad)
+//   k_fisher_contract<C>      one workgroup per upper tile of G_t = 1/2 (K^-1 Z + Z^T K^-1), formed in the MFMA accumulators
+//                             and never stored
+//   k_grad_finish             (the gradient's, as it is) the tiles' sums in tile order
+//   k_fisher_dot              F_st = tan_s . g_t for every s >= t, mirrored: F == F^T bit for bit
+//
+// K_s is linear in its tangent, so <K_s, G_t> is taken one factor at a time: k_fisher_contract contracts G_t with the
+// derivative of K with respect to every hyper-parameter and every grid point -- the sums of k_grad_contract with Q = G_t:
+//   g_t[theta] = 1/2 sum_mn G_t[m,n] dK[m,n]/dtheta,   F_st = sum_theta tan_s[theta] g_t[theta]
+// 2c + c N numbers per tangent.  Forming K_s for every s >= t in the epilogue instead would ask for the 2 x 128 x c grid
+// tangents of every s in LDS (192 KiB at T = 32, c = 3: more than a compute unit has) and T / 2 times the epilogue's
+// arithmetic; the contraction with the derivatives costs what one gradient's does, whatever T is.  g_t depends on tangent t
+// alone and F_st on (s, t) alone: a subsequence of the tangents gives the same bits in the entries it shares.
+//
+// G_t is symmetric, K^-1 Z is so only up to rounding, and an upper tile stands for its mirror image too: contracted as it
+// comes, the antisymmetric part of the rounding error does not cancel (measured on the host in float64 at N = 300: errors of
+// 4e-13 .. 1.6e-12 sqrt(F_ss F_tt) in the amplitude entries against 4e-14 .. 9e-14 for the symmetrised product).  So the
+// contraction runs both K-loops, K^-1 Z and Z^T K^-1, into one accumulator tile: N^3 flops more per tangent, no storage.
+//
+// Workspace beyond [K | I]: THREE Npad^2 matrices (K^-1, K_t, Z) whatever T is -- 24 Npad^2 bytes, 869 MB at N = 6000 --
+// plus (T + 1) (c N + 2 c) doubles of tangents and their contractions and the gradient's per-tile sums.
+// Flops: the factorisation of [K | I] 2/3 N^3, K^-1 1/3 N^3, per tangent 2 N^3 (Z) + 2 N^3 (the upper tiles of G_t, two K-loops):
+//   F_fisher(N, T) = (1 + 4 T) N^3.
+// fp64 throughout, no atomics, every sum in an order fixed by (N, c, T).
+#pragma once
+#include "grad_kernels.hpp"
+
+namespace psoap {
+
+constexpr int FISHER_MAX_T = 32;
+
+// K^-1 = W^T W.  grid P (P + 1) / 2: the upper tile (ti, tj) and its mirror image
+__global__ __launch_bounds__(GEMM_THREADS, 2) void k_fisher_kinv(const double* __restrict__ A, int ld, int Npad, int P,
+                                                                double* __restrict__ Kinv)
+{
+    int ti, tj;
+    decode_upper(blockIdx.x, P, ti, tj);
+    const double* W = A + Npad + (size_t)NB * tj * ld;
+    Tile t;
+    t.zero();
+    tile_gemm_tn(t, W + NB * ti, (size_t)ld, W + NB * tj, (size_t)ld, Npad - NB * tj);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int wr = wave >> 1, wc = wave & 1;
+#pragma unroll
+    for (int m = 0; m < 4; ++m)
+#pragma unroll
+        for (int n = 0; n < 4; ++n)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = tile_row(wr, m, lane, r), col = tile_col(wc, n, lane);
+                if (ti != tj || row <= col) {      // a diagonal tile: its upper half, both ways
+                    const double v = t.acc[m][n][r];
+                    Kinv[(size_t)(NB * ti + row) * Npad + NB * tj + col] = v;
+                    Kinv[(size_t)(NB * tj + col) * Npad + NB * ti + row] = v;
+                }
+            }
+}
+
+// K_t, every tile (grid P P), in the layout of k_fill_sym: wave w owns the 32-column block w, a lane four rows x two columns
+// per step, the eight exponentials of a component through one batched, underflow-skipping evaluation.
+template <int C>
+__global__ __launch_bounds__(256) void k_fisher_tangent_fill(double* __restrict__ Kt, int Npad, int N, int P,
+                                                             const double* __restrict__ lwl, const double* __restrict__ gp,
+                                                             const double* __restrict__ tan_x,
+                                                             const double* __restrict__ tan_gp)
+{
+    __shared__ double xrow[C][NB];
+    __shared__ double drow[C][NB];
+    const int ti = blockIdx.x / P, tj = blockIdx.x % P;
+    const int tid = threadIdx.x;
+    const int i0 = ti * NB, j0 = tj * NB;
+    GpDev g;
+    load_gp(gp, C, g);
+    double ca[C], cl[C], cx[C];      // the coefficients of e, e d^2 and e d (dx[n] - dx[m])
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        const double a = gp[2 * c], l = gp[2 * c + 1];
+        ca[c] = 2.0 * a * tan_gp[2 * c];
+        cl[c] = g.a2[c] * (C_KMS * C_KMS) / (l * l * l) * tan_gp[2 * c + 1];
+        cx[c] = g.a2[c] * 2.0 * g.p2[c];
+    }
+    if (tid < NB) {
+        const int i = i0 + tid;
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            xrow[c][tid] = (i < N) ? lwl[(size_t)c * N + i] : 0.0;
+            drow[c][tid] = (i < N) ? tan_x[(size_t)c * N + i] : 0.0;
+        }
+    }
+    const int w = tid >> 6, rg = (tid >> 4) & 3, cp = tid & 15;
+    const int ja = j0 + 32 * w + 2 * cp, jb = ja + 1;
+    double xa[C], xb[C], da[C], db[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        xa[c] = (ja < N) ? lwl[(size_t)c * N + ja] : 0.0;
+        xb[c] = (jb < N) ? lwl[(size_t)c * N + jb] : 0.0;
+        da[c] = (ja < N) ? tan_x[(size_t)c * N + ja] : 0.0;
+        db[c] = (jb < N) ? tan_x[(size_t)c * N + jb] : 0.0;
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (int g4 = 0; g4 < NB / 16; ++g4) {
+        double va[4] = {0.0, 0.0, 0.0, 0.0}, vb[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            double d[8], a[8], e[8];
+            bool live = false;
+#pragma unroll
+            for (int s4 = 0; s4 < 4; ++s4) {
+#pragma clang fp contract(off)
+                const double xi = xrow[c][16 * g4 + rg + 4 * s4];
+                d[2 * s4] = xa[c] - xi;
+                d[2 * s4 + 1] = xb[c] - xi;
+                a[2 * s4] = g.p2[c] * d[2 * s4] * d[2 * s4];
+                a[2 * s4 + 1] = g.p2[c] * d[2 * s4 + 1] * d[2 * s4 + 1];
+                live = live || !(a[2 * s4] <= -746.0) || !(a[2 * s4 + 1] <= -746.0);
+            }
+            if (__builtin_amdgcn_ballot_w64(live) == 0ull) continue;      // exp() = +0 for the whole wave
+            exp_nonpos_batch<8>(a, e);
+#pragma unroll
+            for (int s4 = 0; s4 < 4; ++s4) {
+                const double di = drow[c][16 * g4 + rg + 4 * s4];
+                const double ua = d[2 * s4], ub = d[2 * s4 + 1];
+                va[s4] += e[2 * s4] * (ca[c] + cl[c] * (ua * ua) + cx[c] * (ua * (da[c] - di)));
+                vb[s4] += e[2 * s4 + 1] * (ca[c] + cl[c] * (ub * ub) + cx[c] * (ub * (db[c] - di)));
+            }
+        }
+#pragma unroll
+        for (int s4 = 0; s4 < 4; ++s4) {
+            const int i = i0 + 16 * g4 + rg + 4 * s4;
+            d2 v;
+            v.x = (i < N && ja < N) ? va[s4] : 0.0;
+            v.y = (i < N && jb < N) ? vb[s4] : 0.0;
+            *reinterpret_cast<d2*>(Kt + (size_t)i * Npad + ja) = v;
+        }
+    }
+}
+
+// Z = K_t K^-1: Z[m][n] = sum_k K_t[k][m] K^-1[k][n] (K_t is symmetric, so its block columns are the k-major operand).
+// grid P P
+__global__ __launch_bounds__(GEMM_THREADS, 2) void k_fisher_gemm(const double* __restrict__ Kt, const double* __restrict__ Kinv,
+                                                                int Npad, int P, double* __restrict__ Z)
+{
+    const int tm = blockIdx.x / P, tn = blockIdx.x % P;
+    Tile t;
+    t.zero();
+    tile_gemm_tn(t, Kt + NB * tm, (size_t)Npad, Kinv + NB * tn, (size_t)Npad, Npad);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int wr = wave >> 1, wc = wave & 1;
+#pragma unroll
+    for (int m = 0; m < 4; ++m)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            double* p0 = Z + (size_t)(NB * tm + tile_row(wr, m, lane, r)) * Npad + NB * tn + tile_col(wc, 0, lane);
+#pragma unroll
+            for (int n = 0; n < 4; ++n) p0[16 * n] = t.acc[m][n][r];
+        }
+}
+
+// One workgroup per upper tile (ti <= tj) of 2 G_t = K^-1 Z + Z^T K^-1, then the epilogue of k_grad_contract with q = G_t[i][j]: per
+// component e_c = exp(p_c d^2) once per element, and the sums
+//   hyper-parameters  sum w q e_c, sum w q e_c d^2   (w = 2 off the diagonal: the element stands for (i,j) and (j,i); 1 on it)
+//   rows of block ti  sum_j q e_c d;     rows of block tj  -sum_i q e_c d
+// in the tile's own GRAD_TILE_DOUBLES of `part` (the gradient's layout: k_grad_finish adds them up).  A diagonal tile takes
+// i <= j only; rows and columns >= N are masked (G_t is exactly zero there).
+template <int C>
+__global__ __launch_bounds__(GEMM_THREADS, 2) void k_fisher_contract(const double* __restrict__ Kinv, const double* __restrict__ Z,
+                                                                    int N, int Npad, int P, const double* __restrict__ lwl,
+                                                                    const double* __restrict__ gp, double* __restrict__ part)
+{
+    constexpr int XS = 0;                 // [2][3][NB]: abscissae of the tile's rows (side 0) and columns (side 1)
+    constexpr int RS = XS + 6 * NB;       // [2 wc][3][NB]: row sums of the two wave columns
+    constexpr int CS = RS + 6 * NB;       // [2 wr][3][NB]: column sums of the two wave rows
+    constexpr int HS = CS + 6 * NB;       // [4 waves][6]
+    static_assert((HS + 24) * sizeof(double) <= GEMM_LDS_BYTES, "the epilogue fits the operand buffers");
+    int ti, tj;
+    decode_upper(blockIdx.x, P, ti, tj);
+    Tile t;
+    t.zero();
+    tile_gemm_tn(t, Kinv + NB * ti, (size_t)Npad, Z + NB * tj, (size_t)Npad, Npad, ti == tj);
+    tile_gemm_tn(t, Z + NB * ti, (size_t)Npad, Kinv + NB * tj, (size_t)Npad, Npad, ti == tj);      // (+ its transpose's tile)
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int wr = wave >> 1, wc = wave & 1;
+    {
+        const int side = tid >> 7, idx = tid & 127;
+        const int g = NB * (side ? tj : ti) + idx;
+#pragma unroll
+        for (int c = 0; c < C; ++c) psoap_smem[XS + (side * 3 + c) * NB + idx] = (g < N) ? lwl[(size_t)c * N + g] : 0.0;
+    }
+    __syncthreads();
+    const bool diag_tile = ti == tj;
+#pragma unroll 1
+    for (int c = 0; c < C; ++c) {
+        double p2;
+        {
+#pragma clang fp contract(off)
+            const double l = gp[2 * c + 1];      // (as load_gp rounds it)
+            p2 = -0.5 * (C_KMS * C_KMS) / (l * l);
+        }
+        double xj[4], colacc[4];
+        bool jok[4];
+#pragma unroll
+        for (int n = 0; n < 4; ++n) {
+            const int col = tile_col(wc, n, lane);
+            xj[n] = psoap_smem[XS + (3 + c) * NB + col];
+            jok[n] = NB * tj + col < N;
+            colacc[n] = 0.0;
+        }
+        double sa = 0.0, sl = 0.0;
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            double xi[4], rowacc[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                xi[r] = psoap_smem[XS + c * NB + tile_row(wr, m, lane, r)];
+                rowacc[r] = 0.0;
+            }
+#pragma unroll
+            for (int n = 0; n < 4; ++n) {
+                const int col = tile_col(wc, n, lane);
+                double d[4], a[4], e[4];
+                bool live = false;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+#pragma clang fp contract(off)
+                    d[r] = xj[n] - xi[r];
+                    a[r] = p2 * d[r] * d[r];
+                    live = live || !(a[r] <= -746.0);
+                }
+                if (__builtin_amdgcn_ballot_w64(live) == 0ull) continue;      // exp() = +0 for the whole wave: nothing to add
+                exp_nonpos_batch<4>(a, e);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int row = tile_row(wr, m, lane, r);
+                    const bool ok = jok[n] && NB * ti + row < N && (!diag_tile || row <= col);
+                    const double qe = ok ? 0.5 * t.acc[m][n][r] * e[r] : 0.0;
+                    const double w = (diag_tile && row == col) ? 1.0 : 2.0;
+                    const double qed = qe * d[r];
+                    sa = fma(w, qe, sa);
+                    sl = fma(w * qed, d[r], sl);
+                    rowacc[r] += qed;
+                    colacc[n] -= qed;
+                }
+            }
+            // the row's 16 lanes (lane & 15 = column within the block), then the two wave columns in LDS
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+#pragma unroll
+                for (int off = 1; off <= 8; off <<= 1) rowacc[r] += __shfl_xor(rowacc[r], off, 64);
+                if ((lane & 15) == 0) psoap_smem[RS + (wc * 3 + c) * NB + tile_row(wr, m, lane, r)] = rowacc[r];
+            }
+        }
+#pragma unroll
+        for (int n = 0; n < 4; ++n) {
+            colacc[n] += __shfl_xor(colacc[n], 16, 64);
+            colacc[n] += __shfl_xor(colacc[n], 32, 64);
+            if (lane < 16) psoap_smem[CS + (wr * 3 + c) * NB + tile_col(wc, n, lane)] = colacc[n];
+        }
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+            sa += __shfl_xor(sa, off, 64);
+            sl += __shfl_xor(sl, off, 64);
+        }
+        if (lane == 0) {
+            psoap_smem[HS + wave * 6 + 2 * c] = sa;
+            psoap_smem[HS + wave * 6 + 2 * c + 1] = sl;
+        }
+    }
+    __syncthreads();
+    double* out = part + (size_t)blockIdx.x * GRAD_TILE_DOUBLES;
+    {
+        const int side = tid >> 7, idx = tid & 127;
+        const int src = side ? CS : RS;
+#pragma unroll
+        for (int c = 0; c < C; ++c)
+            out[(side ? GRAD_COLS_OFF : GRAD_ROWS_OFF) + c * NB + idx] =
+                psoap_smem[src + c * NB + idx] + psoap_smem[src + (3 + c) * NB + idx];
+    }
+    if (tid < 2 * C)
+        out[GRAD_HYP_OFF + tid] = ((psoap_smem[HS + tid] + psoap_smem[HS + 6 + tid]) + psoap_smem[HS + 12 + tid]) +
+                                  psoap_smem[HS + 18 + tid];
+}
+
+// F_mu = 1^T K^-1 1 = |W 1|^2 in two fixed-order stages.  y[k] = sum of row k of W over its columns q <= k, q < N (the rest is
+// exactly zero): thread j adds every 256th term, the 256 sums meet in a tree.  grid N, 256 threads
+__global__ __launch_bounds__(256) void k_fisher_w1(const double* __restrict__ A, int ld, int Npad, int N, double* __restrict__ y)
+{
+    __shared__ double red[256];
+    const int k = blockIdx.x, tid = threadIdx.x;
+    const double* Wk = A + (size_t)k * ld + Npad;
+    double s = 0.0;
+    for (int q = tid; q <= k && q < N; q += 256) s += Wk[q];
+    red[tid] = s;
+    __syncthreads();
+    for (int w = 128; w >= 1; w >>= 1) {
+        if (tid < w) red[tid] += red[tid + w];
+        __syncthreads();
+    }
+    if (tid == 0) y[k] = red[0];
+}
+
+// one workgroup of 256 threads: out = sum_k y[k]^2, the same way
+__global__ __launch_bounds__(256) void k_fisher_mu(const double* __restrict__ y, int N, double* __restrict__ out)
+{
+    __shared__ double red[256];
+    const int tid = threadIdx.x;
+    double s = 0.0;
+    for (int k = tid; k < N; k += 256) s = fma(y[k], y[k], s);
+    red[tid] = s;
+    __syncthreads();
+    for (int w = 128; w >= 1; w >>= 1) {
+        if (tid < w) red[tid] += red[tid + w];
+        __syncthreads();
+    }
+    if (tid == 0) *out = red[0];
+}
+
+// F[s][t] = F[t][s] = tan_s . g_t for s >= t.  grid (T, T), 256 threads: the c N grid terms strided and met in a tree, then
+// the 2c hyper-parameter terms one after the other.  g: what k_grad_finish made of tangent t's tiles (g_gp (T, 2c), g_x (T, c, N))
+__global__ __launch_bounds__(256) void k_fisher_dot(const double* __restrict__ tan_x, const double* __restrict__ tan_gp,
+                                                    const double* __restrict__ g_x, const double* __restrict__ g_gp, int C, int N,
+                                                    int T, double* __restrict__ F)
+{
+    __shared__ double red[256];
+    const int s = blockIdx.x, t = blockIdx.y, tid = threadIdx.x;
+    if (s < t) return;
+    const size_t CN = (size_t)C * N;
+    const double* ts = tan_x + (size_t)s * CN;
+    const double* gt = g_x + (size_t)t * CN;
+    double acc = 0.0;
+    for (size_t i = tid; i < CN; i += 256) acc = fma(ts[i], gt[i], acc);
+    red[tid] = acc;
+    __syncthreads();
+    for (int w = 128; w >= 1; w >>= 1) {
+        if (tid < w) red[tid] += red[tid + w];
+        __syncthreads();
+    }
+    if (tid == 0) {
+        double r = red[0];
+        for (int k = 0; k < 2 * C; ++k) r = fma(tan_gp[(size_t)s * 2 * C + k], g_gp[(size_t)t * 2 * C + k], r);
+        F[(size_t)s * T + t] = r;
+        F[(size_t)t * T + s] = r;
+    }
+}
+
+inline hipError_t fisher_configure_kernels()
+{
+    const int lds = (int)GEMM_LDS_BYTES;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_fisher_kinv), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_fisher_gemm), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_fisher_contract<1>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_fisher_contract<2>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_fisher_contract<3>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    return e;
+}
+
+// the Fisher workspace of a chunk handle (grow-only; psoap_chunk_fisher_release frees it)
+struct FisherWs {
+    Grow<double> Kinv, Kt, Z, TanX, TanGp, Part, GGp, GX, Y, Mu, F;
+    Grow<MatAcc> Info;
+};
+
+}  // namespace psoap

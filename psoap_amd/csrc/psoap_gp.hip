@@ -32,6 +32,7 @@
 #include "calibrate_kernels.hpp"
 #include "grad_kernels.hpp"
 #include "orbit_grad_kernels.hpp"
+#include "fisher_kernels.hpp"
 #include "abi_error.hpp"
 #include "plan_abi.hpp"
 #include "share.hpp"
@@ -92,7 +93,7 @@ struct BatchSlot {
     Event evEval;              // compute stream: last evaluation that read this slot complete
 };
 
-namespace psoap { struct PredictWs; struct GradWs; }
+namespace psoap { struct PredictWs; struct GradWs; struct FisherWs; }
 
 // Streamed evaluation (dag_kernel.hpp, "Streamed evaluation"): one resident launch of the persistent kernel, matrices
 // come and go through `lanes` workspaces of the handle.  Host side: lane allocation, the submission ring in pinned
@@ -210,6 +211,8 @@ struct psoap_chunk {
     std::unique_ptr<psoap::PredictWs> pws;
     // gradient workspace (allocated by the first psoap_chunk_lnlike_grad; psoap_chunk_grad_release)
     std::unique_ptr<psoap::GradWs> gws;
+    // Fisher workspace (allocated by the first psoap_chunk_fisher; psoap_chunk_fisher_release)
+    std::unique_ptr<psoap::FisherWs> fws;
     // streamed evaluation (psoap_stream_*)
     StreamState stream;
     bool dev_locked = false;     // this handle holds a reference on the device's inter-process lock (device_lock_acquire)
@@ -288,6 +291,7 @@ static int configure_kernels(int device)
     HIP_TRY((dag_set_lds<false, true>()));      // the stream's
     HIP_TRY(predict_configure_kernels());
     HIP_TRY(grad_configure_kernels());
+    HIP_TRY(fisher_configure_kernels());
     if (done.size() <= (size_t)device) done.resize((size_t)device + 1, 0);
     done[device] = 1;
     return 0;
@@ -2034,6 +2038,49 @@ static int grad_epoch_lists(psoap_chunk* h, GradWs& w, hipStream_t s)
     return 0;
 }
 
+// The staged factorisation of [K | I] for the nb matrices whose grids and hyper-parameters are in w.Lwl and w.Gp: afterwards
+// the appended block holds W = U^-T, w.R holds z = U^-T (fl - mu_GP) and w.Acc the block records.
+static int grad_factor(psoap_chunk* h, GradWs& w, hipStream_t s, int nb, int c, double mu_GP)
+{
+    const int N = h->N, Npad = h->Npad, P = h->P, ld = 2 * h->Npad;
+    const size_t mstride = (size_t)Npad * ld;
+    const int ntiles = P * (P + 1) / 2;
+    const double tile_flops = 2.0 * NB * NB * (double)NB;
+    if (prof_begin(h, s, PSOAP_K_FILL, 0.0, (double)nb * 12.0 * N * (N + 1.0))) return 1;
+    with_components(c, [&](auto nc) {
+        launch_grad_fill_contract<nc()>(false, s, nb, ntiles, w.A, mstride, ld, N, Npad, P, w.Lwl, w.Gp, h->dSigma, nullptr, nullptr);
+    });
+    hipLaunchKernelGGL(k_grad_init, dim3(ntiles, nb), dim3(256), 0, s, w.A.p, mstride, ld, Npad, P);
+    HIP_TRY(hipGetLastError());
+    if (prof_end(h, s)) return 1;
+    if (prof_begin(h, s, PSOAP_K_MISC, 0.0, 0.0)) return 1;
+    hipLaunchKernelGGL(k_init_rhs, dim3((Npad + 255) / 256, nb), dim3(256), 0, s, w.R.p, Npad, N, h->dFl, mu_GP, w.Acc.p);
+    HIP_TRY(hipGetLastError());
+    if (prof_end(h, s)) return 1;
+    // block row p: tile columns p .. P + p -- the rest of K's row and the appended tiles j <= p
+    for (int p = 0; p < P; ++p) {
+        const int k0 = p * NB;
+        if (p > 0) {
+            const double units = (double)p * (P - p) + 0.5 * p * (p + 1.0);
+            if (prof_begin(h, s, PSOAP_K_PANEL_UPDATE, tile_flops * units * nb, 0.0)) return 1;
+            hipLaunchKernelGGL(k_grad_panel_update, dim3(P + 1, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, w.A.p, mstride, ld, k0, P);
+            HIP_TRY(hipGetLastError());
+            if (prof_end(h, s)) return 1;
+        }
+        if (prof_begin(h, s, PSOAP_K_POTRF, 0.0, 0.0)) return 1;
+        hipLaunchKernelGGL(k_potrf_diag, dim3(nb), dim3(512), 0, s, w.A.p, mstride, ld, k0, w.Wt.p, w.R.p, Npad, w.Acc.p,
+                           (size_t)NB * NB);
+        HIP_TRY(hipGetLastError());
+        if (prof_end(h, s)) return 1;
+        if (prof_begin(h, s, PSOAP_K_TRSM, tile_flops * P * nb, 0.0)) return 1;
+        hipLaunchKernelGGL(k_trsm_strip, dim3(P, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, w.A.p, mstride, ld, k0,
+                           (const double*)w.Wt.p, w.R.p, Npad, (size_t)NB * NB);
+        HIP_TRY(hipGetLastError());
+        if (prof_end(h, s)) return 1;
+    }
+    return 0;
+}
+
 // The ln-wavelengths of a gradient call come from the host (lwl: psoap_chunk_lnlike_grad) or, with lwl == nullptr, from
 // the orbits p_orb of `model`: per group k_orbit_jacobian and k_doppler_shift make them from the handle's grid and dates, and
 // after k_grad_finish the fold and the chain (orbit_grad_kernels.hpp) turn GradX into grad_vel and grad_orb on the device.
@@ -2091,38 +2138,7 @@ static int grad_run(psoap_chunk* h, int B, int c, const double* lwl, int model, 
             HIP_TRY(hipGetLastError());
         }
         HIP_TRY(hipMemcpyAsync(w.Gp, gp + (size_t)b0 * 2 * c, sizeof(double) * (size_t)nb * 2 * c, hipMemcpyHostToDevice, s));
-        if (prof_begin(h, s, PSOAP_K_FILL, 0.0, (double)nb * 12.0 * N * (N + 1.0))) return 1;
-        with_components(c, [&](auto nc) {
-            launch_grad_fill_contract<nc()>(false, s, nb, ntiles, w.A, mstride, ld, N, Npad, P, w.Lwl, w.Gp, h->dSigma, nullptr, nullptr);
-        });
-        hipLaunchKernelGGL(k_grad_init, dim3(ntiles, nb), dim3(256), 0, s, w.A.p, mstride, ld, Npad, P);
-        HIP_TRY(hipGetLastError());
-        if (prof_end(h, s)) return 1;
-        if (prof_begin(h, s, PSOAP_K_MISC, 0.0, 0.0)) return 1;
-        hipLaunchKernelGGL(k_init_rhs, dim3((Npad + 255) / 256, nb), dim3(256), 0, s, w.R.p, Npad, N, h->dFl, mu_GP, w.Acc.p);
-        HIP_TRY(hipGetLastError());
-        if (prof_end(h, s)) return 1;
-        // block row p: tile columns p .. P + p -- the rest of K's row and the appended tiles j <= p
-        for (int p = 0; p < P; ++p) {
-            const int k0 = p * NB;
-            if (p > 0) {
-                const double units = (double)p * (P - p) + 0.5 * p * (p + 1.0);
-                if (prof_begin(h, s, PSOAP_K_PANEL_UPDATE, tile_flops * units * nb, 0.0)) return 1;
-                hipLaunchKernelGGL(k_grad_panel_update, dim3(P + 1, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, w.A.p, mstride, ld, k0, P);
-                HIP_TRY(hipGetLastError());
-                if (prof_end(h, s)) return 1;
-            }
-            if (prof_begin(h, s, PSOAP_K_POTRF, 0.0, 0.0)) return 1;
-            hipLaunchKernelGGL(k_potrf_diag, dim3(nb), dim3(512), 0, s, w.A.p, mstride, ld, k0, w.Wt.p, w.R.p, Npad, w.Acc.p,
-                               (size_t)NB * NB);
-            HIP_TRY(hipGetLastError());
-            if (prof_end(h, s)) return 1;
-            if (prof_begin(h, s, PSOAP_K_TRSM, tile_flops * P * nb, 0.0)) return 1;
-            hipLaunchKernelGGL(k_trsm_strip, dim3(P, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, w.A.p, mstride, ld, k0,
-                               (const double*)w.Wt.p, w.R.p, Npad, (size_t)NB * NB);
-            HIP_TRY(hipGetLastError());
-            if (prof_end(h, s)) return 1;
-        }
+        if (int rc = grad_factor(h, w, s, nb, c, mu_GP)) return rc;
         if (prof_begin(h, s, PSOAP_K_MISC, 0.0, 0.0)) return 1;
         hipLaunchKernelGGL(k_finalize, dim3((nb + 63) / 64), dim3(64), 0, s, (const MatAcc*)w.Acc.p, w.Out.p, nb, (const int*)nullptr, P);
         hipLaunchKernelGGL(k_grad_alpha_partial, dim3(P, nslab, nb), dim3(256), 0, s, (const double*)w.A.p, mstride, ld, Npad,
@@ -2240,6 +2256,121 @@ extern "C" int psoap_chunk_grad_release(psoap_chunk* h)
     if (set_dev(h)) return 1;
     HIP_TRY(hipStreamSynchronize(h->streams[0]));
     h->gws.reset();
+    return 0;
+}
+
+// ---- Fisher information of the likelihood (fisher_kernels.hpp) --------------------------------------
+// One matrix through the gradient's workspace and factorisation, then K^-1 and, tangent after tangent, K_t, Z = K_t K^-1
+// and the contraction of G_t = 1/2 (K^-1 Z + Z^T K^-1) -- on the handle's first stream behind whatever the handle has in flight; neither
+// the proposal slots nor the workspaces of the likelihood paths are touched.
+extern "C" int psoap_chunk_fisher(psoap_chunk* h, int c, const double* lwl, const double* gp, int T, const double* tan_lwl,
+                                  const double* tan_gp, double* fisher, double* fisher_mu)
+{
+    if (!h || !lwl || !gp || !tan_gp || !fisher) FAIL("psoap_chunk_fisher: bad arguments");
+    if (c < 1 || c > 3) FAIL("number of components must be 1, 2 or 3");
+    if (T < 1 || T > FISHER_MAX_T) FAIL("psoap_chunk_fisher: the number of tangents must be between 1 and 32");
+    if (h->stream.open) FAIL("psoap_chunk_fisher: the handle has an open stream (psoap_stream_close first)");
+    DEVICE_SCOPE(h->device);
+    if (int rc = enter_device(h->device)) return rc;
+    const int N = h->N, Npad = h->Npad, P = h->P, ld = 2 * h->Npad;
+    const size_t mstride = (size_t)Npad * ld, sq = (size_t)Npad * Npad, CN = (size_t)c * N;
+    const int ntiles = P * (P + 1) / 2;
+    if (!h->gws) h->gws.reset(new GradWs());
+    if (!h->fws) h->fws.reset(new FisherWs());
+    GradWs& w = *h->gws;
+    FisherWs& f = *h->fws;
+    HIP_TRY(w.A.need(mstride));
+    HIP_TRY(w.Wt.need((size_t)NB * NB));
+    HIP_TRY(w.R.need(Npad));
+    HIP_TRY(w.Acc.need(ACC_ROWS));
+    HIP_TRY(w.Lwl.need((size_t)3 * N));
+    HIP_TRY(w.Gp.need(6));
+    HIP_TRY(f.Kinv.need(sq));
+    HIP_TRY(f.Kt.need(sq));
+    HIP_TRY(f.Z.need(sq));
+    HIP_TRY(f.TanX.need((size_t)T * CN));
+    HIP_TRY(f.TanGp.need((size_t)T * 2 * c));
+    HIP_TRY(f.Part.need((size_t)ntiles * GRAD_TILE_DOUBLES));
+    HIP_TRY(f.GGp.need((size_t)T * 2 * c));
+    HIP_TRY(f.GX.need((size_t)T * CN));
+    HIP_TRY(f.Y.need(Npad));
+    HIP_TRY(f.Mu.need(2));
+    HIP_TRY(f.F.need((size_t)T * T));
+    HIP_TRY(f.Info.need(1));
+    hipStream_t s = h->streams[0];
+    h->recs.clear();
+    HIP_TRY(hipMemcpyAsync(w.Lwl, lwl, sizeof(double) * CN, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(w.Gp, gp, sizeof(double) * 2 * c, hipMemcpyHostToDevice, s));
+    if (tan_lwl) HIP_TRY(hipMemcpyAsync(f.TanX, tan_lwl, sizeof(double) * (size_t)T * CN, hipMemcpyHostToDevice, s));
+    else HIP_TRY(hipMemsetAsync(f.TanX, 0, sizeof(double) * (size_t)T * CN, s));
+    HIP_TRY(hipMemcpyAsync(f.TanGp, tan_gp, sizeof(double) * (size_t)T * 2 * c, hipMemcpyHostToDevice, s));
+    if (int rc = grad_factor(h, w, s, 1, c, 0.0)) return rc;      // (F does not depend on the data: any mu_GP)
+    const double tile_flops = 2.0 * NB * NB * (double)NB;
+    double kunits = 0.0;
+    for (int tj = 0; tj < P; ++tj) kunits += (double)(tj + 1) * (P - tj);
+    if (prof_begin(h, s, PSOAP_K_GRAD, tile_flops * kunits, 0.0)) return 1;
+    hipLaunchKernelGGL(k_fisher_kinv, dim3(ntiles), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)w.A.p, ld, Npad, P, f.Kinv.p);
+    HIP_TRY(hipGetLastError());
+    if (prof_end(h, s)) return 1;
+    if (prof_begin(h, s, PSOAP_K_MISC, 0.0, 0.0)) return 1;
+    hipLaunchKernelGGL(k_acc_total, dim3(1), dim3(1), 0, s, (const MatAcc*)w.Acc.p, P, f.Info.p);
+    hipLaunchKernelGGL(k_fisher_w1, dim3(N), dim3(256), 0, s, (const double*)w.A.p, ld, Npad, N, f.Y.p);
+    hipLaunchKernelGGL(k_fisher_mu, dim3(1), dim3(256), 0, s, (const double*)f.Y.p, N, f.Mu.p);
+    HIP_TRY(hipGetLastError());
+    if (prof_end(h, s)) return 1;
+    for (int t = 0; t < T; ++t) {
+        if (prof_begin(h, s, PSOAP_K_FILL, 0.0, 8.0 * (double)sq)) return 1;
+        with_components(c, [&](auto nc) {
+            hipLaunchKernelGGL(k_fisher_tangent_fill<nc()>, dim3(P * P), dim3(256), 0, s, f.Kt.p, Npad, N, P, (const double*)w.Lwl.p,
+                               (const double*)w.Gp.p, (const double*)(f.TanX.p + (size_t)t * CN),
+                               (const double*)(f.TanGp.p + (size_t)t * 2 * c));
+        });
+        HIP_TRY(hipGetLastError());
+        if (prof_end(h, s)) return 1;
+        if (prof_begin(h, s, PSOAP_K_GRAD, tile_flops * P * ((double)P * P + 2.0 * ntiles), 0.0)) return 1;
+        hipLaunchKernelGGL(k_fisher_gemm, dim3(P * P), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)f.Kt.p,
+                           (const double*)f.Kinv.p, Npad, P, f.Z.p);
+        with_components(c, [&](auto nc) {
+            hipLaunchKernelGGL(k_fisher_contract<nc()>, dim3(ntiles), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)f.Kinv.p,
+                               (const double*)f.Z.p, N, Npad, P, (const double*)w.Lwl.p, (const double*)w.Gp.p, f.Part.p);
+        });
+        HIP_TRY(hipGetLastError());
+        if (prof_end(h, s)) return 1;
+        // the gradient's finishing sums as they are: its alpha is W 1 here, and its sum over alpha goes nowhere (Mu[1])
+        if (prof_begin(h, s, PSOAP_K_MISC, 0.0, 0.0)) return 1;
+        hipLaunchKernelGGL(k_grad_finish, dim3(P + 1, 1), dim3(128), 0, s, (const double*)f.Part.p, (const double*)f.Y.p,
+                           (const double*)w.Gp.p, c, N, Npad, P, f.GGp.p + (size_t)t * 2 * c, f.GX.p + (size_t)t * CN, f.Mu.p + 1);
+        HIP_TRY(hipGetLastError());
+        if (prof_end(h, s)) return 1;
+    }
+    if (prof_begin(h, s, PSOAP_K_MISC, 0.0, 0.0)) return 1;
+    hipLaunchKernelGGL(k_fisher_dot, dim3(T, T), dim3(256), 0, s, (const double*)f.TanX.p, (const double*)f.TanGp.p,
+                       (const double*)f.GX.p, (const double*)f.GGp.p, c, N, T, f.F.p);
+    HIP_TRY(hipGetLastError());
+    if (prof_end(h, s)) return 1;
+    MatAcc info;
+    HIP_TRY(hipMemcpyAsync(fisher, f.F, sizeof(double) * (size_t)T * T, hipMemcpyDeviceToHost, s));
+    if (fisher_mu) HIP_TRY(hipMemcpyAsync(fisher_mu, f.Mu, sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&info, f.Info, sizeof info, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (collect_timings(h)) return 1;
+    // the conventions of the likelihood: a negative hyper-parameter or a matrix that is not positive definite -> no information
+    bool bad = info.info != 0.0;
+    for (int k = 0; k < 2 * c; ++k) bad = bad || gp[k] < 0.0;
+    if (bad) {
+        for (size_t k = 0; k < (size_t)T * T; ++k) fisher[k] = NAN;
+        if (fisher_mu) *fisher_mu = NAN;
+    }
+    return 0;
+}
+
+extern "C" int psoap_chunk_fisher_release(psoap_chunk* h)
+{
+    if (!h) FAIL("null handle");
+    DEVICE_SCOPE(h->device);
+    if (set_dev(h)) return 1;
+    HIP_TRY(hipStreamSynchronize(h->streams[0]));
+    h->fws.reset();
     return 0;
 }
 

@@ -29,6 +29,8 @@ class ChunkWorker:
         self.handle = ChunkHandle(fl, as_f64(sigma) * soften, max_batch=max_batch, device=device)
         dates = as_f64(dates)
         self.handle.set_grid(lwl, epoch_index, dates.shape[0])
+        # the observed-frame grid, the epoch of every pixel and the dates, for the grid tangents of ``fisher``
+        self.lwl, self.epoch_index, self.dates = as_f64(lwl), np.asarray(epoch_index, dtype=np.int64), dates
         check(self.handle._L.psoap_chunk_set_dates(self.handle._h, dptr(dates), dates.shape[0]), "psoap_chunk_set_dates")
 
     def close(self):
@@ -105,6 +107,83 @@ class ChunkWorker:
     def lnprob_grad(self, p, mu_GP: float = 1.0):
         lnp, grad = self.lnprob_grad_batch(np.atleast_2d(p), mu_GP)
         return float(lnp[0]), grad[0]
+
+    # -- Fisher information of lnprob(p) (include/psoap_gp.h: psoap_chunk_fisher) ------------------------------------
+    def fisher_orbits(self, p_orb, p_gp):
+        """The Fisher information of this chunk with the vectors already split: orbital parameters (n_orb,) and GP
+        parameters (2c,) -> ``(n_orb + 2c, n_orb + 2c)`` in registered order.  The tangent of orbital parameter i moves
+        the grid of component c by ``dx[n] = -J[c, epoch(n), i] / c_kms`` with ``J`` the device's velocity Jacobian
+        (``orbit.velocity_jacobian``, which also gives the velocities the grids are shifted by, as ``lnprob`` shifts
+        them); the tangents of the GP parameters are unit vectors.  The (T, c, N) tangents are assembled on the host,
+        everything of order N^3 runs on the device.  A faster-than-light orbit, a negative hyper-parameter or a matrix
+        that is not positive definite gives NaN in every entry."""
+        if os.environ.get("PSOAP_GPU_SERVER", "").strip().lower() not in ("", "0"):
+            raise _lib.PsoapError("fisher needs the device in this process (PSOAP_GPU_SERVER serves values only)")
+        from .data import c_kms
+        from .orbit import velocity_jacobian
+        c, n_orb = N_COMPONENTS[self.model], n_params_orb[self.model]
+        p_orb = as_f64(np.ravel(p_orb), (n_orb,))
+        p_gp = as_f64(np.ravel(p_gp), (2 * c,))
+        vel, jac = velocity_jacobian(self.model, p_orb[None], self.dates, device=self.handle.device)
+        T = n_orb + 2 * c
+        if np.any(np.abs(vel[0]) >= c_kms):
+            return np.full((T, T), np.nan)
+        ep = self.epoch_index
+        lwls = self.lwl[None, :] + (-vel[0][:, ep]) / c_kms          # (as the device shifts: fill_kernels.hpp)
+        tan_lwl = np.zeros((T, c, self.handle.N))
+        tan_lwl[:n_orb] = -np.moveaxis(jac[0], 2, 0)[:, :, ep] / c_kms
+        tan_gp = np.zeros((T, 2 * c))
+        tan_gp[n_orb:] = np.eye(2 * c)
+        return self.handle.fisher(lwls, p_gp, tan_gp, tan_lwl)
+
+    def fisher(self, p):
+        """One fitted parameter vector (n_fit,) -> ``(n_fit, n_fit)`` over the non-fixed parameters in registered order,
+        the ordering of ``lnprob_grad``; fixed parameters drop out."""
+        p_orb, p_gp = convert_vectors(np.atleast_2d(p), self.model, self.fix_params, **self.defaults)
+        full = self.fisher_orbits(p_orb[0], p_gp[0])
+        fit_ind = [i for i, name in enumerate(registered_params[self.model]) if name not in self.fix_params]
+        return np.ascontiguousarray(full[np.ix_(fit_ind, fit_ind)])
+
+
+def fisher_information(workers, p):
+    """The Fisher information of the SUM of the workers' ``lnprob`` at the fitted vector ``p``: the sum of
+    ``ChunkWorker.fisher`` over the chunks, ``(n_fit, n_fit)``."""
+    workers = list(workers) if isinstance(workers, (list, tuple)) else [workers]
+    total = None
+    for w in workers:
+        F = w.fisher(p)
+        total = F if total is None else total + F
+    return total
+
+
+def laplace_covariance(workers, p, prior_precision=None):
+    """The Laplace covariance at ``p``: the inverse, by Cholesky, of the summed Fisher information plus
+    ``prior_precision`` (``(n_fit, n_fit)``, or ``(n_fit,)`` for a diagonal one).  Raises ``np.linalg.LinAlgError`` when
+    that sum is not positive definite -- a direction the data do not constrain needs a prior."""
+    from scipy.linalg import cho_factor, cho_solve
+    F = fisher_information(workers, p)
+    if prior_precision is not None:
+        pp = as_f64(prior_precision)
+        F = F + (np.diag(pp) if pp.ndim == 1 else pp)
+    if not np.all(np.isfinite(F)):
+        raise np.linalg.LinAlgError("the Fisher information is not finite")
+    try:
+        factor = cho_factor(F, lower=True)
+    except np.linalg.LinAlgError:
+        raise np.linalg.LinAlgError("the summed Fisher information is not positive definite") from None
+    C = cho_solve(factor, np.eye(F.shape[0]))
+    return 0.5 * (C + C.T)
+
+
+def fisher_jumps(workers, p, fname=None, prior_precision=None):
+    """A proposal covariance before any chain exists: ``2.38**2 / d`` times the Laplace covariance at ``p`` (the scaling
+    of ``utils.estimate_covariance``).  With ``fname`` the matrix is also saved with ``np.save``: what the ``opt_jump``
+    key of config.yaml names (``sample_parallel.proposal_covariance``)."""
+    C = laplace_covariance(workers, p, prior_precision)
+    cov = 2.38 ** 2 / C.shape[0] * C
+    if fname is not None:
+        np.save(fname, cov)
+    return cov
 
 
 def optimize_orbit(workers, p0, bounds=None, mu_GP=1.0, ftol=1e-10, full_output=False):
