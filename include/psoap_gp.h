@@ -211,6 +211,56 @@ int psoap_chunk_fisher(psoap_chunk *h, int c, const double *lwl, const double *g
                        double *fisher, double *fisher_mu);
 int psoap_chunk_fisher_release(psoap_chunk *h);
 
+/* ---- leave-one-out cross-validation of the likelihood -----------------------------
+ * For one matrix (lwl (c, N), gp (2c), as for psoap_chunk_fisher), with r = fl - mu_GP,
+ * A = K^-1 and alpha = A r (K as psoap_lnlike builds it, noise on the diagonal: pix_var
+ * is the predictive variance of the observed flux, not of the latent spectrum):
+ *   lnp      (1)  the likelihood, with the bits of psoap_chunk_lnlike_grad;
+ *   loo_logp (1)  sum_i pix_logp[i], summed in pixel order;
+ *   pix_mean (N)  fl[i] - alpha[i] / A[i][i]: pixel i predicted from all the others;
+ *   pix_var  (N)  1 / A[i][i];
+ *   pix_logp (N)  1/2 log A[i][i] - alpha[i]^2 / (2 A[i][i]) - 1/2 log(2 pi);
+ * and per epoch e with the n_e pixels I_e, s_e = A[I_e,I_e]^-1 alpha[I_e]:
+ *   ep_resid (N)         s_e on the pixels of epoch e: fl[I_e] minus the prediction
+ *                        of the epoch from all other epochs;
+ *   ep_chi2  (n_epochs)  alpha[I_e] . s_e, chi-squared with n_e degrees of freedom
+ *                        under the model;
+ *   ep_logp  (n_epochs)  -1/2 ep_chi2 + 1/2 log det A[I_e,I_e] - n_e/2 log(2 pi);
+ *   ep_npix  (n_epochs)  n_e; an epoch without pixels gives 0.0, 0.0, 0.
+ * epoch == NULL: pixel outputs only; the ep_* pointers and n_epochs are ignored.
+ * epoch (N) given: values in [0, n_epochs), every epoch's pixels one contiguous run
+ * (the flattened, epoch-major order of Chunk.apply_mask; the runs in any order).
+ * Any output pointer may be NULL.
+ * The factorisation of [K | I] and alpha run as for the gradient, in the gradient's
+ * workspace for one matrix.  Then one workgroup per tile of the band of W^T W that
+ * meets an epoch's diagonal block scatters it into that epoch's packed block (square,
+ * side n_e rounded up to 128, the identity on the padding); the packed blocks go
+ * through the staged potrf / trsm / panel-update kernels as a batch, in groups of
+ * equal padded side; one kernel finishes (csrc/loo_kernels.hpp).  diag(A) is read off
+ * the packed blocks: pixel and epoch outputs rest on the same numbers, and the pixel
+ * outputs have the same bits with and without an epoch index.  No atomics, every sum
+ * in an order fixed by (N, c, epoch layout): the same arguments give the same bits.
+ * Conventions: a negative hyper-parameter or a matrix that is not positive definite
+ * gives lnp = -inf, NaN in every other floating output and status 0; a packed block
+ * that fails to factor (impossible for a positive definite K in exact arithmetic)
+ * gives NaN in that epoch's ep_resid, ep_chi2 and ep_logp only.  An epoch whose pixels
+ * are not contiguous, an epoch index outside [0, n_epochs), n_epochs < 1 with an epoch
+ * index and an open stream on the handle are refused (non-zero status,
+ * psoap_last_error).
+ * Workspace: the gradient's 16 Npad^2 bytes for one matrix (shared with it, freed by
+ * psoap_chunk_grad_release), plus the packed blocks (8 sum side_e^2 bytes), one
+ * 128 x 128 inverse per block row of every block and a few N-vectors, allocated by the
+ * first call, kept with the handle and freed by psoap_chunk_loo_release or
+ * psoap_chunk_destroy.  The handle's uploaded batches, their results and the
+ * likelihood workspaces are left as they are. */
+int psoap_chunk_loo(psoap_chunk *h, int c, const double *lwl, const double *gp, double mu_GP,
+                    const int32_t *epoch, int n_epochs,
+                    double *lnp, double *loo_logp,
+                    double *pix_mean, double *pix_var, double *pix_logp,
+                    double *ep_resid,
+                    double *ep_chi2, double *ep_logp, int32_t *ep_npix);
+int psoap_chunk_loo_release(psoap_chunk *h);
+
 /* Split-phase form of psoap_lnlike_batch: upload (H2D, async, on a copy stream of
  * its own), eval (kernels only, async), fetch (sync + D2H of B doubles).
  * A handle holds TWO proposal batches: an upload always goes to the one that is

@@ -15,6 +15,29 @@ from . import _lib
 from ._lib import K_NAMES, Timings, as_f64, check, dptr
 
 
+class LooResult:
+    """What ``ChunkHandle.loo`` returns: ``lnp``, ``loo_logp`` (the sum of ``pix_logp``); per pixel ``pix_mean``, ``pix_var``
+    (of the observed flux: noise included), ``pix_logp`` and the derived ``pix_z = (fl - pix_mean) / sqrt(pix_var)``; per epoch
+    ``ep_resid`` (N,), ``ep_chi2``, ``ep_logp``, ``ep_npix`` -- ``None`` when no epoch index was given."""
+    __slots__ = ("lnp", "loo_logp", "pix_mean", "pix_var", "pix_logp", "pix_z", "ep_resid", "ep_chi2", "ep_logp", "ep_npix")
+
+    def __init__(self, lnp, loo_logp, pix_mean, pix_var, pix_logp, fl, ep_resid=None, ep_chi2=None, ep_logp=None, ep_npix=None):
+        self.lnp, self.loo_logp = lnp, loo_logp
+        self.pix_mean, self.pix_var, self.pix_logp = pix_mean, pix_var, pix_logp
+        with np.errstate(invalid="ignore"):
+            self.pix_z = (np.asarray(fl, dtype=np.float64) - pix_mean) / np.sqrt(pix_var)      # = alpha_i / sqrt(A_ii)
+        self.ep_resid, self.ep_chi2, self.ep_logp, self.ep_npix = ep_resid, ep_chi2, ep_logp, ep_npix
+
+    @classmethod
+    def degenerate(cls, N, ep_npix=None):
+        """the ``-inf`` / NaN result of a call that never reaches the device (``ep_npix``: the epochs' pixel counts)"""
+        nan = lambda n: np.full(n, np.nan)      # noqa: E731
+        if ep_npix is None:
+            return cls(-np.inf, np.nan, nan(N), nan(N), nan(N), nan(N))
+        npix = np.asarray(ep_npix, dtype=np.int32)
+        return cls(-np.inf, np.nan, nan(N), nan(N), nan(N), nan(N), nan(N), nan(npix.size), nan(npix.size), npix)
+
+
 class ChunkHandle:
     def __init__(self, fl, sigma, max_batch: int = 1, device: int | None = None):
         self._L = _lib.load()
@@ -167,6 +190,39 @@ class ChunkHandle:
     def fisher_release(self):
         """Free the Fisher workspace (24 Npad^2 bytes); the next ``fisher`` allocates it again."""
         check(self._L.psoap_chunk_fisher_release(self._h), "psoap_chunk_fisher_release")
+
+    def loo(self, lwls, gp, mu_GP: float = 1.0, epoch_index=None, n_epochs: int | None = None) -> "LooResult":
+        """Leave-one-out cross-validation of the likelihood at ``lwls`` (c, N), ``gp`` (2c,) (include/psoap_gp.h:
+        psoap_chunk_loo): every pixel predicted from all the others and, with ``epoch_index`` (N,), every epoch from all the
+        other epochs.  Every epoch's pixels must be one contiguous run (the order of ``Chunk.apply_mask``); ``n_epochs``
+        defaults to ``max(epoch_index) + 1``.  A negative hyper-parameter or a matrix that is not positive definite gives
+        ``lnp = -inf`` and NaN in every other floating field."""
+        lwls = as_f64(np.atleast_2d(lwls))
+        c = lwls.shape[0]
+        lwls = as_f64(lwls, (c, self.N))
+        gp = as_f64(gp, (2 * c,))
+        N = self.N
+        lnp, logp = np.empty(1), np.empty(1)
+        mean, var, plogp = np.empty(N), np.empty(N), np.empty(N)
+        if epoch_index is None:
+            ep, ne, resid, chi2, elogp, npix = None, 0, None, None, None, None
+        else:
+            ep = np.ascontiguousarray(epoch_index, dtype=np.int32)
+            if ep.shape != (N,):
+                raise ValueError("epoch_index must have shape (N,)")
+            ne = int(ep.max()) + 1 if n_epochs is None else int(n_epochs)
+            resid, chi2, elogp, npix = np.empty(N), np.empty(max(ne, 0)), np.empty(max(ne, 0)), np.empty(max(ne, 0), dtype=np.int32)
+        i32 = ctypes.POINTER(ctypes.c_int32)
+        check(self._L.psoap_chunk_loo(self._h, c, dptr(lwls), dptr(gp), float(mu_GP),
+                                      None if ep is None else ep.ctypes.data_as(i32), ne, dptr(lnp), dptr(logp), dptr(mean),
+                                      dptr(var), dptr(plogp), None if ep is None else dptr(resid),
+                                      None if ep is None else dptr(chi2), None if ep is None else dptr(elogp),
+                                      None if ep is None else npix.ctypes.data_as(i32)), "psoap_chunk_loo")
+        return LooResult(float(lnp[0]), float(logp[0]), mean, var, plogp, self.fl, resid, chi2, elogp, npix)
+
+    def loo_release(self):
+        """Free the leave-one-out workspace (the packed epoch blocks); the next ``loo`` allocates it again."""
+        check(self._L.psoap_chunk_loo_release(self._h), "psoap_chunk_loo_release")
 
     def upload(self, lwls, gps, mu_GP: float = 1.0):
         lwls = as_f64(lwls)

@@ -300,6 +300,35 @@ def fisher_information(lwls, fl, sigma, gp):
     return h.fisher(lw, gp, np.eye(len(gp)))
 
 
+def loo(lwls, fl, sigma, gp, mu_GP=1.0, epoch_index=None):
+    """Leave-one-out cross-validation of one chunk at ``gp = (amp_0, l_0, ...)``, evaluated on the device through the cached
+    handle (``ChunkHandle.loo``): a ``chunk.LooResult`` with the prediction of every pixel from all the others and, with
+    ``epoch_index`` (N,), of every epoch from all the other epochs.  Degenerate input follows ``lnlike_grad``: a negative
+    hyper-parameter gives ``lnp = -inf`` and NaN before any work, ``l == 0`` raises ``ZeroDivisionError``, a non-finite matrix
+    raises ``ValueError``; a matrix that is not positive definite gives ``-inf`` and NaN."""
+    from .chunk import LooResult
+    gp = [float(g) for g in gp]
+    lw = np.stack([as_f64(w) for w in np.atleast_2d(lwls)])
+    if len(gp) != 2 * lw.shape[0]:
+        raise ValueError(f"gp must hold {2 * lw.shape[0]} values for {lw.shape[0]} component(s)")
+    ep = None if epoch_index is None else np.asarray(epoch_index, dtype=np.int64)
+    if ep is not None and (ep.shape != lw.shape[1:] or (ep.size and ep.min() < 0)):
+        raise ValueError("epoch_index must hold one non-negative epoch per pixel")
+    if any(g < 0.0 for g in gp):
+        return LooResult.degenerate(lw.shape[1], None if ep is None else np.bincount(ep))
+    if any(l == 0.0 for l in gp[1::2]):
+        raise ZeroDivisionError("float division")
+    if not _matrix_is_finite(lw, sigma, gp):
+        raise ValueError(_NONFINITE)
+    h = _chunk_for(fl, sigma)
+    if not hasattr(h, "loo"):
+        raise _lib.PsoapError("loo needs the device in this process (PSOAP_GPU_SERVER serves values only)")
+    res = h.loo(lw, gp, mu_GP, ep)
+    if not np.isneginf(res.lnp) and not (np.all(np.isfinite(np.asarray(fl, dtype=np.float64))) and np.isfinite(mu_GP)):
+        raise ValueError(_NONFINITE)
+    return res
+
+
 def velocity_gradient(grad_lwl, epoch_index, n_epochs):
     """``dlnL/dv[c, e]`` from ``dlnL/dlwl[c, i]``: the rest-frame grids are ``lwl - v[c, epoch]/c_kms``
     (``data.replicate_wls``), so ``dlnL/dv[c, e] = -(1/c_kms) sum_{i in epoch e} dlnL/dlwl[c, i]``.

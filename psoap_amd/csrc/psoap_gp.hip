@@ -33,6 +33,7 @@
 #include "grad_kernels.hpp"
 #include "orbit_grad_kernels.hpp"
 #include "fisher_kernels.hpp"
+#include "loo_kernels.hpp"
 #include "abi_error.hpp"
 #include "plan_abi.hpp"
 #include "share.hpp"
@@ -93,7 +94,7 @@ struct BatchSlot {
     Event evEval;              // compute stream: last evaluation that read this slot complete
 };
 
-namespace psoap { struct PredictWs; struct GradWs; struct FisherWs; }
+namespace psoap { struct PredictWs; struct GradWs; struct FisherWs; struct LooWs; }
 
 // Streamed evaluation (dag_kernel.hpp, "Streamed evaluation"): one resident launch of the persistent kernel, matrices
 // come and go through `lanes` workspaces of the handle.  Host side: lane allocation, the submission ring in pinned
@@ -213,6 +214,8 @@ struct psoap_chunk {
     std::unique_ptr<psoap::GradWs> gws;
     // Fisher workspace (allocated by the first psoap_chunk_fisher; psoap_chunk_fisher_release)
     std::unique_ptr<psoap::FisherWs> fws;
+    // leave-one-out workspace (allocated by the first psoap_chunk_loo; psoap_chunk_loo_release)
+    std::unique_ptr<psoap::LooWs> lws;
     // streamed evaluation (psoap_stream_*)
     StreamState stream;
     bool dev_locked = false;     // this handle holds a reference on the device's inter-process lock (device_lock_acquire)
@@ -292,6 +295,7 @@ static int configure_kernels(int device)
     HIP_TRY(predict_configure_kernels());
     HIP_TRY(grad_configure_kernels());
     HIP_TRY(fisher_configure_kernels());
+    HIP_TRY(loo_configure_kernels());
     if (done.size() <= (size_t)device) done.resize((size_t)device + 1, 0);
     done[device] = 1;
     return 0;
@@ -2371,6 +2375,158 @@ extern "C" int psoap_chunk_fisher_release(psoap_chunk* h)
     if (set_dev(h)) return 1;
     HIP_TRY(hipStreamSynchronize(h->streams[0]));
     h->fws.reset();
+    return 0;
+}
+
+// ---- leave-one-out cross-validation of the likelihood (loo_kernels.hpp) ------------------------------
+// One matrix through the gradient's workspace and factorisation, alpha as the gradient makes it, then the band of K^-1 into
+// the packed epoch blocks, their staged factorisation group after group of equal side, and the finishing kernel -- on the
+// handle's first stream behind whatever the handle has in flight; neither the proposal slots nor the workspaces of the
+// likelihood paths are touched.
+extern "C" int psoap_chunk_loo(psoap_chunk* h, int c, const double* lwl, const double* gp, double mu_GP, const int32_t* epoch,
+                               int n_epochs, double* lnp, double* loo_logp, double* pix_mean, double* pix_var, double* pix_logp,
+                               double* ep_resid, double* ep_chi2, double* ep_logp, int32_t* ep_npix)
+{
+    if (!h || !lwl || !gp) FAIL("psoap_chunk_loo: bad arguments");
+    if (c < 1 || c > 3) FAIL("number of components must be 1, 2 or 3");
+    if (epoch && n_epochs < 1) FAIL("psoap_chunk_loo: n_epochs must be at least 1");
+    if (h->stream.open) FAIL("psoap_chunk_loo: the handle has an open stream (psoap_stream_close first)");
+    const int N = h->N, Npad = h->Npad, P = h->P, ld = 2 * h->Npad;
+    LooLayout lay;
+    if (const char* why = loo_layout(epoch, N, n_epochs, lay)) FAIL(std::string("psoap_chunk_loo: ") + why);
+    const int ne = epoch ? n_epochs : 0, nblk = (int)lay.blocks.size(), ntile = (int)lay.tiles.size();
+    if (!epoch) ep_resid = ep_chi2 = ep_logp = nullptr, ep_npix = nullptr;
+    DEVICE_SCOPE(h->device);
+    if (int rc = enter_device(h->device)) return rc;
+    const size_t mstride = (size_t)Npad * ld, CN = (size_t)c * N;
+    const int nslab = (Npad + 255) / 256;
+    if (!h->gws) h->gws.reset(new GradWs());
+    if (!h->lws) h->lws.reset(new LooWs());
+    GradWs& w = *h->gws;
+    LooWs& l = *h->lws;
+    HIP_TRY(w.A.need(mstride));
+    HIP_TRY(w.Wt.need((size_t)NB * NB));
+    HIP_TRY(w.R.need(Npad));
+    HIP_TRY(w.Acc.need(ACC_ROWS));
+    HIP_TRY(w.Lwl.need((size_t)3 * N));
+    HIP_TRY(w.Gp.need(6));
+    HIP_TRY(w.Alpha.need(Npad));
+    HIP_TRY(w.APart.need((size_t)nslab * Npad));
+    HIP_TRY(w.Out.need(1));
+    HIP_TRY(l.Blk.need((size_t)lay.block_doubles));
+    HIP_TRY(l.Rhs.need((size_t)lay.rhs_doubles));
+    HIP_TRY(l.Sol.need((size_t)lay.rhs_doubles));
+    HIP_TRY(l.Wt.need((size_t)lay.wt_doubles));
+    HIP_TRY(l.Acc.need((size_t)nblk * ACC_ROWS));
+    HIP_TRY(l.Diag.need(N));
+    HIP_TRY(l.Pix.need((size_t)3 * N));
+    HIP_TRY(l.EpResid.need(N));
+    HIP_TRY(l.EpOut.need((size_t)2 * (ne + 1)));
+    HIP_TRY(l.EpNpix.need((size_t)ne + 1));
+    HIP_TRY(l.Logp.need(1));
+    HIP_TRY(l.Blocks.need(nblk));
+    HIP_TRY(l.Tiles.need(ntile));
+    HIP_TRY(l.PixBlock.need(N));
+    HIP_TRY(l.EpBlock.need(lay.epoch_block.size()));
+    hipStream_t s = h->streams[0];
+    h->recs.clear();
+    HIP_TRY(hipMemcpyAsync(w.Lwl, lwl, sizeof(double) * CN, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(w.Gp, gp, sizeof(double) * 2 * c, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(l.Blocks, lay.blocks.data(), sizeof(LooBlock) * (size_t)nblk, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(l.Tiles, lay.tiles.data(), sizeof(LooTile) * (size_t)ntile, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(l.PixBlock, lay.pixel_block.data(), sizeof(int) * (size_t)N, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(l.EpBlock, lay.epoch_block.data(), sizeof(int) * lay.epoch_block.size(), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(l.Blk, 0, sizeof(double) * (size_t)lay.block_doubles, s));
+    // the value and alpha exactly as psoap_chunk_lnlike_grad makes them for one matrix
+    if (int rc = grad_factor(h, w, s, 1, c, mu_GP)) return rc;
+    if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
+            hipLaunchKernelGGL(k_finalize, dim3(1), dim3(64), 0, s, (const MatAcc*)w.Acc.p, w.Out.p, 1, (const int*)nullptr, P);
+            hipLaunchKernelGGL(k_grad_alpha_partial, dim3(P, nslab, 1), dim3(256), 0, s, (const double*)w.A.p, mstride, ld, Npad,
+                               (const double*)w.R.p, w.APart.p, nslab);
+            hipLaunchKernelGGL(k_grad_alpha_finish, dim3((Npad + 255) / 256, 1), dim3(256), 0, s, (const double*)w.APart.p, nslab,
+                               Npad, w.Alpha.p);
+            hipLaunchKernelGGL(k_loo_pad, dim3(nblk), dim3(128), 0, s, (const LooBlock*)l.Blocks.p, l.Blk.p);
+        })) return rc;
+    const double tile_flops = 2.0 * NB * NB * (double)NB;
+    double bunits = 0.0;      // executed 128^3 products of the band: a diagonal tile issues three quarters of its MFMAs
+    for (const LooTile& t : lay.tiles) bunits += (t.ti == t.tj ? 0.75 : 1.0) * (P - t.tj);
+    if (int rc = prof_launch(h, s, PSOAP_K_GRAD, tile_flops * bunits, 0.0, [&] {
+            hipLaunchKernelGGL(k_loo_band, dim3(ntile), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)w.A.p, ld, N, Npad,
+                               (const LooTile*)l.Tiles.p, (const int*)l.PixBlock.p, (const LooBlock*)l.Blocks.p, l.Blk.p);
+        })) return rc;
+    if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
+            hipLaunchKernelGGL(k_loo_rhs, dim3(nblk), dim3(256), 0, s, (const LooBlock*)l.Blocks.p, (const double*)l.Blk.p,
+                               (const double*)w.Alpha.p, l.Rhs.p, l.Diag.p, l.Acc.p);
+        })) return rc;
+    // the packed blocks through the staged factorisation, one matrix of the batch per block, group after group of equal side
+    if (epoch)
+        for (const LooGroup& g : lay.groups) {
+            const LooBlock& b0 = lay.blocks[(size_t)g.first];
+            const int S = g.side, Pb = S / NB, nb = g.count;
+            const size_t bstride = (size_t)S * S, wstride = (size_t)Pb * NB * NB;
+            double* Kg = l.Blk.p + b0.offset;
+            double* Rg = l.Rhs.p + b0.rhs;
+            MatAcc* Ag = l.Acc.p + (size_t)g.first * ACC_ROWS;
+            for (int p = 0; p < Pb; ++p) {
+                const int k0 = p * NB, nt = Pb - p;
+                double* Wg = l.Wt.p + b0.wt + (size_t)p * NB * NB;
+                if (p > 0)
+                    if (int rc = prof_launch(h, s, PSOAP_K_PANEL_UPDATE, 2.0 * NB * NB * (double)k0 * nt * nb, 0.0, [&] {
+                            hipLaunchKernelGGL(k_panel_update, dim3(nt, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, Kg, bstride, S, k0);
+                        })) return rc;
+                if (int rc = prof_launch(h, s, PSOAP_K_POTRF, 0.0, 0.0, [&] {
+                        hipLaunchKernelGGL(k_potrf_diag, dim3(nb), dim3(512), 0, s, Kg, bstride, S, k0, Wg, Rg, S, Ag, wstride);
+                    })) return rc;
+                if (nt > 1)
+                    if (int rc = prof_launch(h, s, PSOAP_K_TRSM, tile_flops * (nt - 1) * nb, 0.0, [&] {
+                            hipLaunchKernelGGL(k_trsm_strip, dim3(nt - 1, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, Kg, bstride, S, k0,
+                                               (const double*)Wg, Rg, S, wstride);
+                        })) return rc;
+            }
+        }
+    if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
+            hipLaunchKernelGGL(k_loo_finish, dim3(ne + 1), dim3(256), 0, s, N, ne, (const int*)l.EpBlock.p, (const LooBlock*)l.Blocks.p,
+                               (const double*)l.Blk.p, (const double*)l.Wt.p, (const double*)l.Rhs.p, l.Sol.p, (const MatAcc*)l.Acc.p,
+                               (const double*)w.Alpha.p, (const double*)l.Diag.p, (const double*)h->dFl.p, l.Pix.p, l.Pix.p + N,
+                               l.Pix.p + 2 * (size_t)N, l.EpResid.p, l.EpOut.p, l.EpOut.p + (ne + 1), l.EpNpix.p, l.Logp.p);
+        })) return rc;
+    double value = 0.0;
+    HIP_TRY(hipMemcpyAsync(&value, w.Out, sizeof(double), hipMemcpyDeviceToHost, s));
+    if (loo_logp) HIP_TRY(hipMemcpyAsync(loo_logp, l.Logp, sizeof(double), hipMemcpyDeviceToHost, s));
+    if (pix_mean) HIP_TRY(hipMemcpyAsync(pix_mean, l.Pix, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost, s));
+    if (pix_var) HIP_TRY(hipMemcpyAsync(pix_var, l.Pix.p + N, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost, s));
+    if (pix_logp) HIP_TRY(hipMemcpyAsync(pix_logp, l.Pix.p + 2 * (size_t)N, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost, s));
+    if (ep_resid) HIP_TRY(hipMemcpyAsync(ep_resid, l.EpResid, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost, s));
+    if (ep_chi2) HIP_TRY(hipMemcpyAsync(ep_chi2, l.EpOut, sizeof(double) * (size_t)ne, hipMemcpyDeviceToHost, s));
+    if (ep_logp) HIP_TRY(hipMemcpyAsync(ep_logp, l.EpOut.p + (ne + 1), sizeof(double) * (size_t)ne, hipMemcpyDeviceToHost, s));
+    if (ep_npix) HIP_TRY(hipMemcpyAsync(ep_npix, l.EpNpix, sizeof(int32_t) * (size_t)ne, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));       // (the layout's vectors and the caller's pageable arrays)
+    if (collect_timings(h)) return 1;
+    // the conventions of the likelihood: a negative hyper-parameter or a matrix that is not positive definite -> -inf, and
+    // nothing else to say about it
+    bool neg = false;
+    for (int k = 0; k < 2 * c; ++k) neg = neg || gp[k] < 0.0;
+    if (neg) value = -INFINITY;
+    if (lnp) *lnp = value;
+    if (value == -INFINITY) {
+        if (loo_logp) *loo_logp = NAN;
+        for (double* v : {pix_mean, pix_var, pix_logp, ep_resid})
+            if (v)
+                for (int i = 0; i < N; ++i) v[i] = NAN;
+        for (double* v : {ep_chi2, ep_logp})
+            if (v)
+                for (int e = 0; e < ne; ++e) v[e] = NAN;
+    }
+    return 0;
+}
+
+extern "C" int psoap_chunk_loo_release(psoap_chunk* h)
+{
+    if (!h) FAIL("null handle");
+    DEVICE_SCOPE(h->device);
+    if (set_dev(h)) return 1;
+    HIP_TRY(hipStreamSynchronize(h->streams[0]));
+    h->lws.reset();
     return 0;
 }
 

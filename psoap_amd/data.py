@@ -173,6 +173,16 @@ def read_mask_table(fname):
     return rows
 
 
+def write_mask_table(fname, rows):
+    """Write ``masks.dat`` rows ``(wl0, wl1, t0, t1)`` the way the reference's scripts/psoap_generate_masks.py:101-103 does:
+    the header ``wl0 wl1 t0 t1``, wavelengths as ``%.1f`` and dates as ``%.2f``.  ``read_mask_table`` reads it back (the
+    numbers as rounded by those formats)."""
+    with open(fname, "w") as f:
+        f.write("wl0 wl1 t0 t1\n")
+        for wl0, wl1, t0, t1 in rows:
+            f.write("%.1f %.1f %.2f %.2f\n" % (wl0, wl1, t0, t1))
+
+
 def mask_from_regions(wl, date, regions):
     """Start from an all-good mask and reject every (wl, date) box, strict inequalities on both axes
     (psoap_process_masks.py:58-70)."""

@@ -144,6 +144,67 @@ class ChunkWorker:
         fit_ind = [i for i, name in enumerate(registered_params[self.model]) if name not in self.fix_params]
         return np.ascontiguousarray(full[np.ix_(fit_ind, fit_ind)])
 
+    # -- leave-one-out cross-validation at lnprob(p) (include/psoap_gp.h: psoap_chunk_loo) ----------------------------
+    def loo_orbits(self, p_orb, p_gp, mu_GP: float = 1.0):
+        """Leave-one-out cross-validation of this chunk with the vectors already split: orbital parameters (n_orb,) and GP
+        parameters (2c,) -> a ``chunk.LooResult`` with the epoch fields over the worker's own ``epoch_index``.  The
+        velocities come from the device (``orbit.velocities``) and the grids are shifted on the host exactly as
+        ``fisher_orbits`` shifts them.  A faster-than-light orbit gives ``lnp = -inf`` and NaN, as a negative
+        hyper-parameter or a matrix that is not positive definite does."""
+        if os.environ.get("PSOAP_GPU_SERVER", "").strip().lower() not in ("", "0"):
+            raise _lib.PsoapError("loo needs the device in this process (PSOAP_GPU_SERVER serves values only)")
+        from .chunk import LooResult
+        from .data import c_kms
+        from .orbit import velocities
+        c, n_orb = N_COMPONENTS[self.model], n_params_orb[self.model]
+        p_orb = as_f64(np.ravel(p_orb), (n_orb,))
+        p_gp = as_f64(np.ravel(p_gp), (2 * c,))
+        ep, ne = self.epoch_index, self.dates.shape[0]
+        vel = velocities(self.model, p_orb[None], self.dates, device=self.handle.device)[0]
+        if np.any(np.abs(vel) >= c_kms):
+            return LooResult.degenerate(self.handle.N, np.bincount(ep, minlength=ne))
+        lwls = self.lwl[None, :] + (-vel[:, ep]) / c_kms          # (as the device shifts: fill_kernels.hpp)
+        return self.handle.loo(lwls, p_gp, mu_GP, ep, ne)
+
+    def loo(self, p, mu_GP: float = 1.0):
+        """One fitted parameter vector (n_fit,) -> the ``chunk.LooResult`` of this chunk there"""
+        p_orb, p_gp = convert_vectors(np.atleast_2d(p), self.model, self.fix_params, **self.defaults)
+        return self.loo_orbits(p_orb[0], p_gp[0], mu_GP)
+
+
+def loo_outliers(workers, p, pix_sigma=5.0, epoch_p=1e-4, mu_GP=1.0):
+    """What disagrees with the fitted model at ``p``, per chunk: a list, in the order of ``workers``, of dicts with
+    ``pixels`` (indices with ``|pix_z| > pix_sigma``), ``epochs`` (ids whose ``ep_chi2`` has an upper-tail chi-squared
+    probability below ``epoch_p`` at ``ep_npix`` degrees of freedom, ``scipy.stats.chi2.sf``), the probabilities ``epoch_sf``
+    of every epoch and the ``LooResult`` itself (``loo``).  The two defaults are conventions, not measurements: 5 sigma per
+    pixel (one in 1.7 million under the model), and one in 10,000 per epoch (a hundred epochs of ten chunks then flag one
+    good epoch in ten runs)."""
+    from scipy.stats import chi2
+    workers = list(workers) if isinstance(workers, (list, tuple)) else [workers]
+    out = []
+    for w in workers:
+        r = w.loo(p, mu_GP)
+        with np.errstate(invalid="ignore"):
+            pixels = np.flatnonzero(np.abs(r.pix_z) > pix_sigma)
+            sf = np.where(r.ep_npix > 0, chi2.sf(r.ep_chi2, np.maximum(r.ep_npix, 1)), 1.0)
+            epochs = np.flatnonzero(sf < epoch_p)
+        out.append({"pixels": pixels, "epochs": epochs, "epoch_sf": sf, "loo": r})
+    return out
+
+
+def loo_mask_rows(chunks_meta, outliers, pad_days=0.1):
+    """``masks.dat`` rows ``(wl0, wl1, t0, t1)`` for the epochs ``loo_outliers`` flagged: ``chunks_meta`` holds, per chunk
+    and in the same order, ``(wl0, wl1, dates)`` -- the chunk's wavelength range as in ``chunks.dat`` and the date of every
+    epoch.  A flagged epoch becomes the chunk's whole range over ``date -+ pad_days``, the tenth of a day of
+    the reference's scripts/psoap_generate_masks.py:95-98 by default.  Flagged pixels make no row: a row removes a
+    whole epoch of a chunk.  Write them with ``data.write_mask_table``."""
+    rows = []
+    for (wl0, wl1, dates), found in zip(chunks_meta, outliers):
+        dates = np.asarray(dates, dtype=np.float64)
+        for e in found["epochs"]:
+            rows.append((float(wl0), float(wl1), float(dates[e] - pad_days), float(dates[e] + pad_days)))
+    return rows
+
 
 def fisher_information(workers, p):
     """The Fisher information of the SUM of the workers' ``lnprob`` at the fitted vector ``p``: the sum of
