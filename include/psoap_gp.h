@@ -261,6 +261,59 @@ int psoap_chunk_loo(psoap_chunk *h, int c, const double *lwl, const double *gp, 
                     double *ep_chi2, double *ep_logp, int32_t *ep_npix);
 int psoap_chunk_loo_release(psoap_chunk *h);
 
+/* ---- likelihood with a per-epoch continuum polynomial integrated out ----------------
+ * psoap_lnlike takes the continuum of every epoch as known: it subtracts the scalar
+ * mu_GP.  Here every epoch e carries a Chebyshev polynomial of degree `order` with a
+ * Gaussian prior, integrated out in closed form (Rasmussen & Williams 2.7).  With
+ * r = fl - mu_GP and K as psoap_lnlike builds it:
+ *   H[i][e (order+1) + k] = w[i] T_k(u_i) for the pixels i of epoch e, else 0, where u_i
+ *       is x[i] mapped so that the smallest and the largest abscissa of the epoch go
+ *       to -1 and +1 (numpy.polynomial.Chebyshev(domain=[a, b]); u = 0 for an epoch
+ *       with one pixel or equal abscissae); q = n_epochs (order+1) columns;
+ *   r = H beta + f + eps,  beta ~ N(0, Lambda),  Lambda = diag(prior_sd[k]^2), the same
+ *       for every epoch;
+ *   Ht = H Lambda^1/2,  W = U^-T Ht,  z = U^-T r  (K = U^T U),  M = I + W^T W,  bt = W^T z;
+ *   lnp  = -1/2 (z^T z - bt^T M^-1 bt + log det K + log det M): the likelihood of r under
+ *          K + H Lambda H^T, without N/2 log 2 pi as everywhere in this library;
+ *   parts (B, 4)     z^T z, log det K, the gain bt^T M^-1 bt, log det M;
+ *   beta (B, q)      E[beta] = Lambda^1/2 M^-1 bt;
+ *   beta_cov (B, q, q)  Cov[beta] = Lambda^1/2 M^-1 Lambda^1/2, symmetric bit for bit;
+ *   fl_cor (B, N)    fl - H E[beta].
+ * weight == NULL is w = 1 (an additive offset); w = fl is the first-order form of a
+ * multiplicative correction.  An epoch without pixels keeps its columns: mean 0,
+ * covariance Lambda, nothing added to lnp.  parts, beta, beta_cov and fl_cor may be NULL;
+ * the covariance and the solve for beta run only when asked for.
+ * psoap_chunk_set_baseline checks and keeps the baseline (H does not depend on the
+ * proposal: Ht is built once, by the next psoap_chunk_lnlike_marg, into a buffer of the
+ * handle).  psoap_chunk_lnlike_marg walks B proposals (lwl (B, c, N), gp (B, 2c)) in
+ * groups through the staged factorisation of [K | Ht] -- block row p updates and solves
+ * only the appended tile columns that can be non-zero there -- forms M tile by tile in
+ * the MFMA accumulators, factors it with the same staged kernels and finishes in one
+ * workgroup per matrix (csrc/marg_kernels.hpp, csrc/marg_plan.hpp).  No atomics, every
+ * sum in an order fixed by (N, c, epoch layout, order): the same arguments give the
+ * same bits, whatever the batch around a matrix and whichever outputs are asked for.
+ * Conventions: a negative hyper-parameter, a K that is not positive definite or an M
+ * that fails to factor (impossible in exact arithmetic: its eigenvalues are >= 1) gives
+ * lnp = -inf, NaN in every other output and status 0.  Refused (non-zero status,
+ * psoap_last_error): order < 0 or > 15; (order+1) n_epochs > 1024; a prior_sd that is
+ * not finite and positive; an epoch index outside [0, n_epochs); an epoch whose pixels
+ * are not one contiguous run (the runs may come in any order); a non-finite abscissa
+ * or weight; psoap_chunk_lnlike_marg before psoap_chunk_set_baseline, or after a
+ * psoap_chunk_set_data that followed a baseline WITH weights (they described the old
+ * data: set the baseline again); B < 1 or B > max_batch; an open stream on the handle.
+ * Workspace: the gradient's buffer (shared with it as leave-one-out shares it, freed by
+ * psoap_chunk_grad_release), 8 Npad (Npad + 128 Q) bytes per matrix of a group,
+ * Q = ceil(q / 128); plus Ht (8 Npad 128 Q bytes), per matrix of a group M (16 (128 Q)^2
+ * bytes; M^-1 and the covariance when asked for) and a few vectors, allocated by the
+ * first call and freed by psoap_chunk_marg_release or psoap_chunk_destroy.  After a
+ * release the baseline stays set: the next call builds Ht again.  The handle's
+ * uploaded batches, their results and the likelihood workspaces are left as they are. */
+int psoap_chunk_set_baseline(psoap_chunk *h, int order, const double *x, const int32_t *epoch, int n_epochs,
+                             const double *weight, const double *prior_sd);
+int psoap_chunk_lnlike_marg(psoap_chunk *h, int B, int c, const double *lwl, const double *gp, double mu_GP,
+                            double *lnp, double *parts, double *beta, double *beta_cov, double *fl_cor);
+int psoap_chunk_marg_release(psoap_chunk *h);
+
 /* Split-phase form of psoap_lnlike_batch: upload (H2D, async, on a copy stream of
  * its own), eval (kernels only, async), fetch (sync + D2H of B doubles).
  * A handle holds TWO proposal batches: an upload always goes to the one that is

@@ -38,6 +38,25 @@ class LooResult:
         return cls(-np.inf, np.nan, nan(N), nan(N), nan(N), nan(N), nan(N), nan(npix.size), nan(npix.size), npix)
 
 
+class MargResult:
+    """What ``ChunkHandle.lnlike_marg`` returns when more than the value is asked for: ``lnp``; ``parts`` = (z^T z,
+    log det K, the gain, log det M); ``beta`` (n_epochs, order + 1) and ``beta_cov`` (q, q), the posterior mean and covariance
+    of the continuum coefficients; ``fl_cor`` (N,), the flux minus the posterior-mean continuum term.  A field that was not
+    asked for is ``None``; a batched call gives every field a leading axis of B."""
+    __slots__ = ("lnp", "parts", "beta", "beta_cov", "fl_cor")
+
+    def __init__(self, lnp, parts, beta=None, beta_cov=None, fl_cor=None):
+        self.lnp, self.parts, self.beta, self.beta_cov, self.fl_cor = lnp, parts, beta, beta_cov, fl_cor
+
+    @property
+    def beta_sd(self):
+        """posterior standard deviations in the shape of ``beta`` (``None`` without ``beta_cov``)"""
+        if self.beta_cov is None:
+            return None
+        d = np.sqrt(np.diagonal(self.beta_cov, axis1=-2, axis2=-1))
+        return d if self.beta is None else d.reshape(np.shape(self.beta))
+
+
 class ChunkHandle:
     def __init__(self, fl, sigma, max_batch: int = 1, device: int | None = None):
         self._L = _lib.load()
@@ -223,6 +242,69 @@ class ChunkHandle:
     def loo_release(self):
         """Free the leave-one-out workspace (the packed epoch blocks); the next ``loo`` allocates it again."""
         check(self._L.psoap_chunk_loo_release(self._h), "psoap_chunk_loo_release")
+
+    def set_baseline(self, order: int, x, epoch_index, n_epochs: int, prior_sd, weight=None):
+        """A Chebyshev polynomial of degree ``order`` per epoch, with a Gaussian prior of standard deviations ``prior_sd``
+        (order + 1,), to be integrated out by ``lnlike_marg`` (include/psoap_gp.h: psoap_chunk_set_baseline).  ``x`` (N,): the
+        observed-frame ln-wavelengths; ``epoch_index`` (N,): every epoch's pixels one contiguous run; ``weight`` (N,): what
+        multiplies the polynomial at each pixel -- ``None`` for an additive offset, the flux for the first-order form of a
+        multiplicative correction.  A ``set_data`` after a baseline WITH weights makes ``lnlike_marg`` refuse until the
+        baseline is set again."""
+        x = as_f64(x, (self.N,))
+        ep = np.ascontiguousarray(epoch_index, dtype=np.int32)
+        if ep.shape != (self.N,):
+            raise ValueError("epoch_index must have shape (N,)")
+        sd = as_f64(np.atleast_1d(prior_sd))
+        if sd.shape != (int(order) + 1,):
+            raise ValueError("prior_sd must hold order + 1 values")
+        w = None if weight is None else as_f64(weight, (self.N,))
+        check(self._L.psoap_chunk_set_baseline(self._h, int(order), dptr(x), ep.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                               int(n_epochs), None if w is None else dptr(w), dptr(sd)),
+              "psoap_chunk_set_baseline")
+        self._baseline = (int(n_epochs), int(order))
+
+    def lnlike_marg(self, lwls, gps, mu_GP: float = 1.0, want_beta: bool = False, want_cov: bool = False,
+                    want_flux: bool = False):
+        """The likelihood with the baseline of ``set_baseline`` integrated out (include/psoap_gp.h:
+        psoap_chunk_lnlike_marg).  ``lwls`` (c, N) with ``gps`` (2c,) -> the value, or a ``MargResult`` when any of
+        ``want_beta`` / ``want_cov`` / ``want_flux`` is set; ``lwls`` (B, c, N) with ``gps`` (B, 2c), B <= max_batch -> the same
+        with a leading axis of B.  A negative hyper-parameter or a matrix that is not positive definite gives ``-inf`` and
+        NaN in every other field."""
+        if getattr(self, "_baseline", None) is None:
+            raise _lib.PsoapError("lnlike_marg: call set_baseline first")
+        ne, order = self._baseline
+        q = ne * (order + 1)
+        lwls = as_f64(lwls)
+        single = lwls.ndim <= 2
+        if single:
+            lwls = np.atleast_2d(lwls)[None]
+        if lwls.ndim != 3 or lwls.shape[2] != self.N:
+            raise ValueError("lwls must have shape (c, N) or (B, c, N)")
+        B, c, _ = lwls.shape
+        lwls = as_f64(lwls, (B, c, self.N))
+        gps = as_f64(np.atleast_2d(as_f64(gps)), (B, 2 * c))
+        more = want_beta or want_cov or want_flux
+        lnp = np.empty(B)
+        parts = np.empty((B, 4)) if more else None
+        beta = np.empty((B, q)) if want_beta else None
+        cov = np.empty((B, q, q)) if want_cov else None
+        flc = np.empty((B, self.N)) if want_flux else None
+        opt = lambda a: None if a is None else dptr(a)      # noqa: E731
+        check(self._L.psoap_chunk_lnlike_marg(self._h, B, c, dptr(lwls), dptr(gps), float(mu_GP), dptr(lnp), opt(parts),
+                                              opt(beta), opt(cov), opt(flc)), "psoap_chunk_lnlike_marg")
+        if not more:
+            return float(lnp[0]) if single else lnp
+        if beta is not None:
+            beta = beta.reshape(B, ne, order + 1)
+        if single:
+            return MargResult(float(lnp[0]), parts[0], None if beta is None else beta[0], None if cov is None else cov[0],
+                              None if flc is None else flc[0])
+        return MargResult(lnp, parts, beta, cov, flc)
+
+    def marg_release(self):
+        """Free the device side of the baseline and the workspace of ``lnlike_marg`` beyond the gradient's; the baseline
+        stays set and the next ``lnlike_marg`` allocates everything again."""
+        check(self._L.psoap_chunk_marg_release(self._h), "psoap_chunk_marg_release")
 
     def upload(self, lwls, gps, mu_GP: float = 1.0):
         lwls = as_f64(lwls)

@@ -329,6 +329,52 @@ def loo(lwls, fl, sigma, gp, mu_GP=1.0, epoch_index=None):
     return res
 
 
+def _marginal(lwls, fl, sigma, gp, x, epoch_index, order, prior_sd, weight, mu_GP, full):
+    """the shared front of ``lnlike_marginal`` and ``baseline_posterior``: the degenerate-input rules of ``lnlike_grad``, the
+    cached handle of the chunk.  A sampler keeps a ``ChunkHandle`` / ``ChunkWorker`` and sets the baseline once."""
+    gp = [float(g) for g in gp]
+    lw = np.stack([as_f64(w) for w in np.atleast_2d(lwls)])
+    if len(gp) != 2 * lw.shape[0]:
+        raise ValueError(f"gp must hold {2 * lw.shape[0]} values for {lw.shape[0]} component(s)")
+    ep = np.asarray(epoch_index, dtype=np.int64)
+    if ep.shape != lw.shape[1:] or (ep.size and ep.min() < 0):
+        raise ValueError("epoch_index must hold one non-negative epoch per pixel")
+    ne, N = int(ep.max()) + 1, lw.shape[1]
+    q = ne * (int(order) + 1)
+    nan = (np.full((ne, int(order) + 1), np.nan), np.full((q, q), np.nan), np.full(N, np.nan), -np.inf)
+    if any(g < 0.0 for g in gp):
+        return nan if full else -np.inf
+    if any(l == 0.0 for l in gp[1::2]):
+        raise ZeroDivisionError("float division")
+    if not _matrix_is_finite(lw, sigma, gp):
+        raise ValueError(_NONFINITE)
+    h = _chunk_for(fl, sigma)
+    if not hasattr(h, "lnlike_marg"):
+        raise _lib.PsoapError("lnlike_marginal needs the device in this process (PSOAP_GPU_SERVER serves values only)")
+    h.set_baseline(order, x, ep, ne, prior_sd, weight)      # (every call: the cached handle is shared by this module's callers)
+    res = h.lnlike_marg(lw, gp, mu_GP, want_beta=full, want_cov=full, want_flux=full)
+    lnp = res.lnp if full else res
+    if not np.isneginf(lnp) and not (np.all(np.isfinite(np.asarray(fl, dtype=np.float64))) and np.isfinite(mu_GP)):
+        raise ValueError(_NONFINITE)
+    return (res.beta, res.beta_cov, res.fl_cor, np.float64(lnp)) if full else np.float64(lnp)
+
+
+def lnlike_marginal(lwls, fl, sigma, gp, x, epoch_index, order, prior_sd, weight=None, mu_GP=1.0):
+    """The likelihood of one chunk with a Chebyshev polynomial of degree ``order`` per epoch integrated out under the
+    Gaussian prior ``prior_sd`` (order + 1,) -- ``lnlike_f`` / ``_f_g`` / ``_f_g_h`` by the rows of ``lwls``, under
+    ``K + H Lambda H^T`` (``ChunkHandle.lnlike_marg``).  ``x`` (N,): observed-frame ln-wavelengths; ``epoch_index`` (N,);
+    ``weight``: ``None`` (additive) or (N,), e.g. ``fl``.  ``-inf`` as ``lnlike``: a negative hyper-parameter, a matrix that is
+    not positive definite."""
+    return _marginal(lwls, fl, sigma, gp, x, epoch_index, order, prior_sd, weight, mu_GP, False)
+
+
+def baseline_posterior(lwls, fl, sigma, gp, x, epoch_index, order, prior_sd, weight=None, mu_GP=1.0):
+    """``(beta (n_epochs, order + 1), beta_cov (q, q), fl_cor (N,), lnp)`` at a fit: the posterior mean and covariance of every
+    epoch's continuum coefficients, jointly, and the flux with the posterior-mean term removed -- the one-shot counterpart
+    of ``cycle_calibration``, with error bars.  Arguments and ``-inf`` / NaN conventions as ``lnlike_marginal``."""
+    return _marginal(lwls, fl, sigma, gp, x, epoch_index, order, prior_sd, weight, mu_GP, True)
+
+
 def velocity_gradient(grad_lwl, epoch_index, n_epochs):
     """``dlnL/dv[c, e]`` from ``dlnL/dlwl[c, i]``: the rest-frame grids are ``lwl - v[c, epoch]/c_kms``
     (``data.replicate_wls``), so ``dlnL/dv[c, e] = -(1/c_kms) sum_{i in epoch e} dlnL/dlwl[c, i]``.

@@ -34,6 +34,7 @@
 #include "orbit_grad_kernels.hpp"
 #include "fisher_kernels.hpp"
 #include "loo_kernels.hpp"
+#include "marg_kernels.hpp"
 #include "abi_error.hpp"
 #include "plan_abi.hpp"
 #include "share.hpp"
@@ -94,7 +95,7 @@ struct BatchSlot {
     Event evEval;              // compute stream: last evaluation that read this slot complete
 };
 
-namespace psoap { struct PredictWs; struct GradWs; struct FisherWs; struct LooWs; }
+namespace psoap { struct PredictWs; struct GradWs; struct FisherWs; struct LooWs; struct MargWs; }
 
 // Streamed evaluation (dag_kernel.hpp, "Streamed evaluation"): one resident launch of the persistent kernel, matrices
 // come and go through `lanes` workspaces of the handle.  Host side: lane allocation, the submission ring in pinned
@@ -216,6 +217,10 @@ struct psoap_chunk {
     std::unique_ptr<psoap::FisherWs> fws;
     // leave-one-out workspace (allocated by the first psoap_chunk_loo; psoap_chunk_loo_release)
     std::unique_ptr<psoap::LooWs> lws;
+    // continuum-marginalised likelihood: the baseline as psoap_chunk_set_baseline took it (host), and its device side and
+    // workspace (allocated by the first psoap_chunk_lnlike_marg after it; psoap_chunk_marg_release)
+    psoap::MargSetup marg;
+    std::unique_ptr<psoap::MargWs> mws;
     // streamed evaluation (psoap_stream_*)
     StreamState stream;
     bool dev_locked = false;     // this handle holds a reference on the device's inter-process lock (device_lock_acquire)
@@ -296,6 +301,7 @@ static int configure_kernels(int device)
     HIP_TRY(grad_configure_kernels());
     HIP_TRY(fisher_configure_kernels());
     HIP_TRY(loo_configure_kernels());
+    HIP_TRY(marg_configure_kernels());
     if (done.size() <= (size_t)device) done.resize((size_t)device + 1, 0);
     done[device] = 1;
     return 0;
@@ -457,6 +463,8 @@ extern "C" int psoap_chunk_set_data(psoap_chunk* h, const double* fl, const doub
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(h->dFl, fl, sizeof(double) * h->N, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(h->dSigma, sigma, sizeof(double) * h->N, hipMemcpyHostToDevice));
+    // a baseline with weights described the old data (w = fl is the usual choice): psoap_chunk_set_baseline again
+    if (h->marg.valid && !h->marg.weight.empty()) h->marg.stale_weight = true;
     // the sorted copies of the slots that hold a batch
     for (BatchSlot& sl : h->slot)
         if (h->sky && sl.B > 0 && sl.sky_valid) {
@@ -2527,6 +2535,246 @@ extern "C" int psoap_chunk_loo_release(psoap_chunk* h)
     if (set_dev(h)) return 1;
     HIP_TRY(hipStreamSynchronize(h->streams[0]));
     h->lws.reset();
+    return 0;
+}
+
+// ---- likelihood with a per-epoch continuum polynomial integrated out (marg_kernels.hpp) ------------------
+extern "C" int psoap_chunk_set_baseline(psoap_chunk* h, int order, const double* x, const int32_t* epoch, int n_epochs,
+                                        const double* weight, const double* prior_sd)
+{
+    if (!h || !x || !epoch || !prior_sd) FAIL("psoap_chunk_set_baseline: bad arguments");
+    if (h->stream.open) FAIL("psoap_chunk_set_baseline: the handle has an open stream (psoap_stream_close first)");
+    MargPlan plan;
+    if (const char* why = marg_plan(x, epoch, h->N, n_epochs, order, prior_sd, plan)) FAIL(std::string("psoap_chunk_set_baseline: ") + why);
+    if (weight)
+        for (int i = 0; i < h->N; ++i)
+            if (!isfinite(weight[i])) FAIL("psoap_chunk_set_baseline: the weights must be finite");
+    MargSetup& m = h->marg;
+    m.plan = std::move(plan);
+    m.x.assign(x, x + h->N);
+    m.epoch.assign(epoch, epoch + h->N);
+    m.weight.clear();
+    if (weight) m.weight.assign(weight, weight + h->N);
+    m.sd.assign(prior_sd, prior_sd + order + 1);
+    m.valid = true;
+    m.stale_weight = false;
+    if (h->mws) h->mws->basis_ready = false;      // (Ht is built by the next psoap_chunk_lnlike_marg, on its stream)
+    return 0;
+}
+
+// Ht and the tables of the handle's baseline onto the device (once per psoap_chunk_set_baseline or _marg_release)
+static int marg_basis(psoap_chunk* h, MargWs& m, hipStream_t s)
+{
+    if (m.basis_ready) return 0;
+    const MargSetup& su = h->marg;
+    const MargPlan& pl = su.plan;
+    const int N = h->N, Npad = h->Npad, Q = pl.Q, ldh = NB * Q, ne = pl.n_epochs;
+    std::vector<int> tab((size_t)3 * Q), ep(su.epoch.begin(), su.epoch.end());
+    for (int t = 0; t < Q; ++t) {
+        tab[(size_t)marg_tab_first(Q) + t] = pl.first[pl.column[t]];
+        tab[(size_t)marg_tab_column(Q) + t] = pl.column[t];
+        tab[(size_t)marg_tab_slot(Q) + t] = pl.slot[t];
+    }
+    HIP_TRY(m.Ht.need((size_t)Npad * ldh));
+    HIP_TRY(m.X.need(N));
+    HIP_TRY(m.Weight.need(N));
+    HIP_TRY(m.Epoch.need(N));
+    HIP_TRY(m.EpOff.need(ne));
+    HIP_TRY(m.EpScl.need(ne));
+    HIP_TRY(m.Sd.need(pl.order + 1));
+    HIP_TRY(m.Tab.need(tab.size()));
+    HIP_TRY(m.Tiles.need(pl.tiles.size()));
+    HIP_TRY(hipMemsetAsync(m.Ht, 0, sizeof(double) * (size_t)Npad * ldh, s));
+    HIP_TRY(hipMemcpyAsync(m.X, su.x.data(), sizeof(double) * (size_t)N, hipMemcpyHostToDevice, s));
+    if (!su.weight.empty()) HIP_TRY(hipMemcpyAsync(m.Weight, su.weight.data(), sizeof(double) * (size_t)N, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(m.Epoch, ep.data(), sizeof(int) * (size_t)N, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(m.EpOff, pl.off.data(), sizeof(double) * (size_t)ne, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(m.EpScl, pl.scl.data(), sizeof(double) * (size_t)ne, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(m.Sd, su.sd.data(), sizeof(double) * (size_t)(pl.order + 1), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(m.Tab, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(m.Tiles, pl.tiles.data(), sizeof(MargTile) * pl.tiles.size(), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_marg_basis, dim3((N + 255) / 256), dim3(256), 0, s, m.Ht.p, ldh, N, pl.order, Q, (const double*)m.X.p,
+                       (const int*)m.Epoch.p, (const double*)m.EpOff.p, (const double*)m.EpScl.p,
+                       su.weight.empty() ? (const double*)nullptr : (const double*)m.Weight.p, (const double*)m.Sd.p,
+                       (const int*)m.Tab.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));       // (the vectors leave scope)
+    m.basis_ready = true;
+    return 0;
+}
+
+// Group after group of matrices through the gradient's workspace as [K | Ht] (ld = Npad + 128 Q), then the Gram matrices
+// through the staged kernels once more -- on the handle's first stream behind whatever the handle has in flight; neither
+// the proposal slots nor the workspaces of the likelihood paths are touched.
+extern "C" int psoap_chunk_lnlike_marg(psoap_chunk* h, int B, int c, const double* lwl, const double* gp, double mu_GP,
+                                       double* lnp, double* parts, double* beta, double* beta_cov, double* fl_cor)
+{
+    if (!h || !lwl || !gp || !lnp) FAIL("psoap_chunk_lnlike_marg: bad arguments");
+    if (c < 1 || c > 3) FAIL("number of components must be 1, 2 or 3");
+    if (B < 1 || B > h->max_batch) FAIL("psoap_chunk_lnlike_marg: batch size outside [1, max_batch]");
+    if (h->stream.open) FAIL("psoap_chunk_lnlike_marg: the handle has an open stream (psoap_stream_close first)");
+    if (!h->marg.valid) FAIL("psoap_chunk_lnlike_marg: call psoap_chunk_set_baseline first");
+    if (h->marg.stale_weight)
+        FAIL("psoap_chunk_lnlike_marg: psoap_chunk_set_data changed the data the baseline's weights were given for "
+             "(psoap_chunk_set_baseline again)");
+    DEVICE_SCOPE(h->device);
+    if (int rc = enter_device(h->device)) return rc;
+    const MargPlan& pl = h->marg.plan;
+    const int N = h->N, Npad = h->Npad, P = h->P, Q = pl.Q, q = pl.q, order = pl.order;
+    const int S = NB * Q, ld = Npad + S, ldm = 2 * S, ldh = S;
+    const size_t mstride = (size_t)Npad * ld, m_stride = (size_t)S * ldm, wstride = (size_t)Q * NB * NB;
+    const int G = marg_group_size(B, Npad, Q);
+    const int ntiles = P * (P + 1) / 2, nslab = (Npad + 255) / 256, ngram = Q * (Q + 1) / 2;
+    const bool want_cov = beta_cov != nullptr, want_sol = beta != nullptr || fl_cor != nullptr;
+    if (!h->gws) h->gws.reset(new GradWs());
+    if (!h->mws) h->mws.reset(new MargWs());
+    GradWs& w = *h->gws;
+    MargWs& m = *h->mws;
+    HIP_TRY(w.A.need((size_t)G * mstride));
+    HIP_TRY(w.Wt.need((size_t)G * NB * NB));
+    HIP_TRY(w.R.need((size_t)G * Npad));
+    HIP_TRY(w.Acc.need((size_t)G * ACC_ROWS));
+    HIP_TRY(w.Lwl.need((size_t)G * 3 * N));
+    HIP_TRY(w.Gp.need((size_t)G * 6));
+    HIP_TRY(m.M.need((size_t)G * m_stride));
+    HIP_TRY(m.WtM.need((size_t)G * wstride));
+    HIP_TRY(m.Rhs.need((size_t)G * S));
+    HIP_TRY(m.Gam.need((size_t)G * S));
+    HIP_TRY(m.RPart.need((size_t)G * nslab * S));
+    HIP_TRY(m.AccM.need((size_t)G * ACC_ROWS));
+    HIP_TRY(m.Out.need((size_t)G * 5));
+    HIP_TRY(m.Beta.need((size_t)G * q));
+    HIP_TRY(m.Flc.need((size_t)G * N));
+    if (want_cov) {
+        HIP_TRY(m.Minv.need((size_t)G * S * S));
+        HIP_TRY(m.Cov.need((size_t)G * q * q));
+    }
+    hipStream_t s = h->streams[0];
+    if (int rc = marg_basis(h, m, s)) return rc;
+    const int* tab = m.Tab.p;
+    h->recs.clear();
+    const double tile_flops = 2.0 * NB * NB * (double)NB;
+    std::vector<double> out((size_t)B * 5);
+    for (int b0 = 0; b0 < B; b0 += G) {
+        const int nb = (B - b0 < G) ? B - b0 : G;
+        HIP_TRY(hipMemcpyAsync(w.Lwl, lwl + (size_t)b0 * c * N, sizeof(double) * (size_t)nb * c * N, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(w.Gp, gp + (size_t)b0 * 2 * c, sizeof(double) * (size_t)nb * 2 * c, hipMemcpyHostToDevice, s));
+        if (int rc = prof_launch(h, s, PSOAP_K_FILL, 0.0, (double)nb * 12.0 * N * (N + 1.0), [&] {
+                with_components(c, [&](auto nc) {
+                    launch_grad_fill_contract<nc()>(false, s, nb, ntiles, w.A, mstride, ld, N, Npad, P, w.Lwl, w.Gp, h->dSigma, nullptr,
+                                                    nullptr);
+                });
+                hipLaunchKernelGGL(k_marg_load, dim3(Q * P, nb), dim3(256), 0, s, w.A.p, mstride, ld, Npad, P, (const double*)m.Ht.p,
+                                   ldh, tab);
+            })) return rc;
+        if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
+                hipLaunchKernelGGL(k_init_rhs, dim3((Npad + 255) / 256, nb), dim3(256), 0, s, w.R.p, Npad, N, h->dFl, mu_GP, w.Acc.p);
+            })) return rc;
+        // block row p: the rest of K's row and the appended slots whose first non-zero block row is <= p
+        for (int p = 0; p < P; ++p) {
+            const int k0 = p * NB, act = pl.active[(size_t)p];
+            if (p > 0)
+                if (int rc = prof_launch(h, s, PSOAP_K_PANEL_UPDATE, tile_flops * p * (P - p + act) * nb, 0.0, [&] {
+                        hipLaunchKernelGGL(k_marg_panel_update, dim3(P - p + act, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, w.A.p,
+                                           mstride, ld, k0, P, tab);
+                    })) return rc;
+            if (int rc = prof_launch(h, s, PSOAP_K_POTRF, 0.0, 0.0, [&] {
+                    hipLaunchKernelGGL(k_potrf_diag, dim3(nb), dim3(512), 0, s, w.A.p, mstride, ld, k0, w.Wt.p, w.R.p, Npad, w.Acc.p,
+                                       (size_t)NB * NB);
+                })) return rc;
+            const int nt = P - p - 1 + act;
+            if (nt > 0)
+                if (int rc = prof_launch(h, s, PSOAP_K_TRSM, tile_flops * nt * nb, 0.0, [&] {
+                        hipLaunchKernelGGL(k_trsm_strip, dim3(nt, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, w.A.p, mstride, ld, k0,
+                                           (const double*)w.Wt.p, w.R.p, Npad, (size_t)NB * NB);
+                    })) return rc;
+        }
+        if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
+                hipLaunchKernelGGL(k_marg_rhs_partial, dim3(Q, nslab, nb), dim3(256), 0, s, (const double*)w.A.p, mstride, ld, Npad, Q,
+                                   tab, (const double*)w.R.p, m.RPart.p, nslab);
+                hipLaunchKernelGGL(k_marg_rhs_finish, dim3((S + 255) / 256, nb), dim3(256), 0, s, (const double*)m.RPart.p, nslab, Npad,
+                                   Q, tab, m.Rhs.p);
+            })) return rc;
+        double gunits = 0.0;
+        for (const MargTile& t : pl.tiles) gunits += (t.ti == t.tj ? 0.75 : 1.0) * (Npad - t.k0) / NB;
+        if (int rc = prof_launch(h, s, PSOAP_K_GRAD, tile_flops * gunits * nb, 0.0, [&] {
+                hipLaunchKernelGGL(k_marg_gram, dim3(ngram, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)w.A.p, mstride, ld,
+                                   Npad, (const MargTile*)m.Tiles.p, m.M.p, m_stride, ldm);
+                if (want_cov) hipLaunchKernelGGL(k_grad_init, dim3(ngram, nb), dim3(256), 0, s, m.M.p, m_stride, ldm, S, Q);
+            })) return rc;
+        // M = U_M^T U_M with bt alongside; with the covariance asked for, [M | I] as the gradient factors [K | I]
+        for (int p = 0; p < Q; ++p) {
+            const int k0 = p * NB;
+            double* Wp = m.WtM.p + (size_t)p * NB * NB;
+            if (p > 0)
+                if (int rc = prof_launch(h, s, PSOAP_K_PANEL_UPDATE, tile_flops * p * (want_cov ? Q : Q - p) * nb, 0.0, [&] {
+                        if (want_cov)
+                            hipLaunchKernelGGL(k_grad_panel_update, dim3(Q + 1, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, m.M.p,
+                                               m_stride, ldm, k0, Q);
+                        else
+                            hipLaunchKernelGGL(k_panel_update, dim3(Q - p, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, m.M.p, m_stride,
+                                               ldm, k0);
+                    })) return rc;
+            if (int rc = prof_launch(h, s, PSOAP_K_POTRF, 0.0, 0.0, [&] {
+                    hipLaunchKernelGGL(k_potrf_diag, dim3(nb), dim3(512), 0, s, m.M.p, m_stride, ldm, k0, Wp, m.Rhs.p, S, m.AccM.p, wstride);
+                })) return rc;
+            const int nt = want_cov ? Q : Q - p - 1;
+            if (nt > 0)
+                if (int rc = prof_launch(h, s, PSOAP_K_TRSM, tile_flops * nt * nb, 0.0, [&] {
+                        hipLaunchKernelGGL(k_trsm_strip, dim3(nt, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, m.M.p, m_stride, ldm, k0,
+                                           (const double*)Wp, m.Rhs.p, S, wstride);
+                    })) return rc;
+        }
+        if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
+                hipLaunchKernelGGL(k_marg_finish, dim3(nb), dim3(256), 0, s, N, P, Q, q, order, (const MatAcc*)w.Acc.p,
+                                   (const MatAcc*)m.AccM.p, (const double*)m.M.p, m_stride, ldm, (const double*)m.WtM.p,
+                                   (const double*)m.Rhs.p, m.Gam.p, (const double*)m.Sd.p, (const int*)m.Epoch.p, tab,
+                                   (const double*)m.Ht.p, ldh, (const double*)h->dFl.p, m.Out.p, m.Beta.p, m.Flc.p, want_sol ? 1 : 0);
+            })) return rc;
+        if (want_cov)
+            if (int rc = prof_launch(h, s, PSOAP_K_GRAD, 0.0, 0.0, [&] {
+                    for (int b = 0; b < nb; ++b)
+                        hipLaunchKernelGGL(k_fisher_kinv, dim3(ngram), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s,
+                                           (const double*)(m.M.p + (size_t)b * m_stride), ldm, S, Q, m.Minv.p + (size_t)b * S * S);
+                    hipLaunchKernelGGL(k_marg_cov, dim3(q, nb), dim3(256), 0, s, (const double*)m.Minv.p, S, q, order,
+                                       (const double*)m.Sd.p, m.Cov.p);
+                })) return rc;
+        HIP_TRY(hipMemcpyAsync(out.data() + (size_t)b0 * 5, m.Out, sizeof(double) * (size_t)nb * 5, hipMemcpyDeviceToHost, s));
+        if (beta) HIP_TRY(hipMemcpyAsync(beta + (size_t)b0 * q, m.Beta, sizeof(double) * (size_t)nb * q, hipMemcpyDeviceToHost, s));
+        if (fl_cor) HIP_TRY(hipMemcpyAsync(fl_cor + (size_t)b0 * N, m.Flc, sizeof(double) * (size_t)nb * N, hipMemcpyDeviceToHost, s));
+        if (want_cov)
+            HIP_TRY(hipMemcpyAsync(beta_cov + (size_t)b0 * q * q, m.Cov, sizeof(double) * (size_t)nb * q * q, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));       // the next group reuses the workspace and the caller's arrays are pageable
+    }
+    if (collect_timings(h)) return 1;
+    // the conventions of the likelihood: a negative hyper-parameter, a K that is not positive definite or an M that fails to
+    // factor -> -inf, and nothing else to say about it
+    for (int b = 0; b < B; ++b) {
+        bool neg = false;
+        for (int k = 0; k < 2 * c; ++k) neg = neg || gp[(size_t)b * 2 * c + k] < 0.0;
+        lnp[b] = neg ? -INFINITY : out[(size_t)b * 5];
+        const bool bad = lnp[b] == -INFINITY;
+        if (parts)
+            for (int k = 0; k < 4; ++k) parts[(size_t)b * 4 + k] = bad ? NAN : out[(size_t)b * 5 + 1 + k];
+        if (!bad) continue;
+        if (beta)
+            for (int k = 0; k < q; ++k) beta[(size_t)b * q + k] = NAN;
+        if (beta_cov)
+            for (size_t k = 0; k < (size_t)q * q; ++k) beta_cov[(size_t)b * q * q + k] = NAN;
+        if (fl_cor)
+            for (int i = 0; i < N; ++i) fl_cor[(size_t)b * N + i] = NAN;
+    }
+    return 0;
+}
+
+// frees the device side of the baseline and the workspace; the baseline itself stays set (the next call builds Ht again)
+extern "C" int psoap_chunk_marg_release(psoap_chunk* h)
+{
+    if (!h) FAIL("null handle");
+    DEVICE_SCOPE(h->device);
+    if (set_dev(h)) return 1;
+    HIP_TRY(hipStreamSynchronize(h->streams[0]));
+    h->mws.reset();
     return 0;
 }
 

@@ -20,9 +20,15 @@ from .utils import MODEL_ID, N_COMPONENTS, convert_vectors, n_params_orb, regist
 
 class ChunkWorker:
     def __init__(self, model: str, lwl, fl, sigma, epoch_index, dates, fix_params=(), defaults=None,
-                 max_batch: int = 1, device: int | None = None, soften: float = 1.0):
+                 max_batch: int = 1, device: int | None = None, soften: float = 1.0, baseline: dict | None = None):
         """lwl/fl/sigma: the chunk's masked, flattened arrays (N,); epoch_index (N,): epoch of each pixel;
-        dates (n_epochs,): ``date1D``; ``soften`` scales sigma (sample_parallel.py:141)."""
+        dates (n_epochs,): ``date1D``; ``soften`` scales sigma (sample_parallel.py:141).
+
+        ``baseline = {"order": k, "sd": [s_0 .. s_k], "weight": "one" | "flux"}``: ``lnprob`` and ``lnprob_batch`` evaluate the
+        likelihood with a Chebyshev polynomial of degree k per epoch integrated out (``ChunkHandle.lnlike_marg``) -- an
+        additive offset ("one") or the polynomial times the flux ("flux").  The split-phase and streamed entries
+        (``upload_*``, ``stream_*``) evaluate the plain likelihood and refuse to run on such a worker.  ``None``: every
+        path as it was."""
         self.model = model
         self.fix_params = list(fix_params)
         self.defaults = dict(defaults or {})
@@ -32,13 +38,68 @@ class ChunkWorker:
         # the observed-frame grid, the epoch of every pixel and the dates, for the grid tangents of ``fisher``
         self.lwl, self.epoch_index, self.dates = as_f64(lwl), np.asarray(epoch_index, dtype=np.int64), dates
         check(self.handle._L.psoap_chunk_set_dates(self.handle._h, dptr(dates), dates.shape[0]), "psoap_chunk_set_dates")
+        self.baseline = None
+        if baseline is not None:
+            unknown = set(baseline) - {"order", "sd", "weight"}
+            if unknown or "order" not in baseline or "sd" not in baseline:
+                raise ValueError(f"baseline needs 'order' and 'sd' (and optionally 'weight'); got {sorted(baseline)}")
+            kind = baseline.get("weight", "one")
+            if kind not in ("one", "flux"):
+                raise ValueError("baseline['weight'] must be 'one' or 'flux'")
+            self.baseline = {"order": int(baseline["order"]), "sd": [float(v) for v in baseline["sd"]], "weight": kind}
+            self.handle.set_baseline(self.baseline["order"], self.lwl, self.epoch_index, dates.shape[0], self.baseline["sd"],
+                                     self.handle.fl if kind == "flux" else None)
 
     def close(self):
         self.handle.close()
 
+    def _no_baseline(self, what):
+        if self.baseline is not None:
+            raise _lib.PsoapError(f"{what} evaluates the plain likelihood; this worker has a baseline (use lnprob / lnprob_batch)")
+
+    # -- likelihood with the per-epoch continuum integrated out (include/psoap_gp.h: psoap_chunk_lnlike_marg) ---------
+    def shifted_grids(self, p_orb):
+        """(B, n_orb) -> ``(lwls (B, c, N), too_fast (B,))``: the velocities from the device (``orbit.velocities``), the
+        grids shifted on the host exactly as ``fisher_orbits`` and ``loo_orbits`` shift them"""
+        from .data import c_kms
+        from .orbit import velocities
+        p_orb = as_f64(np.atleast_2d(p_orb))
+        p_orb = as_f64(p_orb, (p_orb.shape[0], n_params_orb[self.model]))
+        vel = velocities(self.model, p_orb, self.dates, device=self.handle.device)
+        fast = np.any(np.abs(vel) >= c_kms, axis=(1, 2))
+        return self.lwl[None, None, :] + (-vel[:, :, self.epoch_index]) / c_kms, fast
+
+    def marg_orbits(self, p_orb, p_gp, mu_GP: float = 1.0, **want):
+        """The marginal likelihood with the vectors already split: (B, n_orb) and (B, 2c) -> (B,), or a ``chunk.MargResult``
+        with ``want_beta`` / ``want_cov`` / ``want_flux``; walked in pieces of ``max_batch``.  A faster-than-light orbit gives
+        ``-inf`` (and NaN), as a negative hyper-parameter or a matrix that is not positive definite does."""
+        if self.baseline is None:
+            raise _lib.PsoapError("this worker has no baseline (ChunkWorker(..., baseline=...))")
+        if os.environ.get("PSOAP_GPU_SERVER", "").strip().lower() not in ("", "0"):
+            raise _lib.PsoapError("the marginal likelihood needs the device in this process (PSOAP_GPU_SERVER serves values only)")
+        from .chunk import MargResult
+        lwls, fast = self.shifted_grids(p_orb)
+        B, c = lwls.shape[0], N_COMPONENTS[self.model]
+        p_gp = as_f64(np.atleast_2d(p_gp), (B, 2 * c))
+        lwls[fast] = lwls[~fast][0] if np.any(~fast) else self.lwl          # (a stand-in: overwritten below)
+        pieces = [self.handle.lnlike_marg(lwls[s:s + self.handle.max_batch], p_gp[s:s + self.handle.max_batch], mu_GP, **want)
+                  for s in range(0, B, self.handle.max_batch)]
+        if not isinstance(pieces[0], MargResult):
+            out = np.concatenate(pieces)
+            out[fast] = -np.inf
+            return out
+        cat = lambda k: None if getattr(pieces[0], k) is None else np.concatenate([getattr(r, k) for r in pieces])  # noqa: E731
+        res = MargResult(cat("lnp"), cat("parts"), cat("beta"), cat("beta_cov"), cat("fl_cor"))
+        res.lnp[fast] = -np.inf
+        for k in ("parts", "beta", "beta_cov", "fl_cor"):
+            if getattr(res, k) is not None:
+                getattr(res, k)[fast] = np.nan
+        return res
+
     def upload_proposals(self, ps, mu_GP: float = 1.0) -> None:
         """Ship fitted parameter vectors (B, n_fit); the orbit solve and the Doppler shift are queued on the
         chunk's stream.  Follow with ``handle.eval()`` (or a ``ChunkGroup.eval()``) and ``handle.fetch()``."""
+        self._no_baseline("upload_proposals")
         p_orb, p_gp = convert_vectors(np.atleast_2d(ps), self.model, self.fix_params, **self.defaults)
         self.upload_orbits(p_orb, p_gp, mu_GP)
 
@@ -47,6 +108,7 @@ class ChunkWorker:
         reads exactly 2c GP parameters per proposal, so a narrower array is refused here.  (ST2 registers two GP
         parameters, utils.py:7, for a likelihood of two components, covariance.py:379: its fitted vectors stop at
         ``upload_proposals`` as they stop with a TypeError in ``Worker.lnprob``; this entry takes all four.)"""
+        self._no_baseline("upload_orbits")
         p_orb = as_f64(np.atleast_2d(p_orb))
         B = p_orb.shape[0]
         p_orb = as_f64(p_orb, (B, n_params_orb[self.model]))
@@ -58,11 +120,13 @@ class ChunkWorker:
 
     # -- streamed form: ONE resident launch across sampler iterations (include/psoap_gp.h: psoap_stream_*) ----------
     def stream_open(self, lanes: int | None = None, scheme: int = -1):
+        self._no_baseline("the streamed path")
         self.handle.stream_open(N_COMPONENTS[self.model], lanes, scheme)
 
     def stream_submit(self, ps, mu_GP: float = 1.0) -> np.ndarray:
         """fitted parameter vectors (n, n_fit) -> tickets; Kepler solve, |v| >= c rule, Doppler shift and likelihood all
         inside the resident launch (``Worker.lnprob`` for n proposals, sample_parallel.py:168-198)"""
+        self._no_baseline("the streamed path")
         p_orb, p_gp = convert_vectors(np.atleast_2d(ps), self.model, self.fix_params, **self.defaults)
         return self.handle.stream_submit_orbits(MODEL_ID[self.model], p_orb, p_gp, mu_GP)
 
@@ -73,6 +137,9 @@ class ChunkWorker:
         self.handle.stream_close()
 
     def lnprob_batch(self, ps, mu_GP: float = 1.0) -> np.ndarray:
+        if self.baseline is not None:
+            p_orb, p_gp = convert_vectors(np.atleast_2d(ps), self.model, self.fix_params, **self.defaults)
+            return self.marg_orbits(p_orb, p_gp, mu_GP)
         self.upload_proposals(ps, mu_GP)
         self.handle.eval()
         return self.handle.fetch()
@@ -170,6 +237,40 @@ class ChunkWorker:
         """One fitted parameter vector (n_fit,) -> the ``chunk.LooResult`` of this chunk there"""
         p_orb, p_gp = convert_vectors(np.atleast_2d(p), self.model, self.fix_params, **self.defaults)
         return self.loo_orbits(p_orb[0], p_gp[0], mu_GP)
+
+
+def baseline_fit(workers, p, mu_GP=1.0):
+    """The continuum of every epoch at the fitted vector ``p``, per chunk: a list, in the order of ``workers`` (each made
+    with ``baseline=...``), of dicts with ``beta`` (n_epochs, order + 1), ``beta_cov`` (q, q), ``beta_sd`` (as ``beta``),
+    ``fl_cor`` (N,) and ``lnp`` -- all epochs of a chunk jointly, in one evaluation, with error bars: the counterpart of the
+    iterated, frozen ``cycle_calibration``."""
+    workers = list(workers) if isinstance(workers, (list, tuple)) else [workers]
+    out = []
+    for w in workers:
+        p_orb, p_gp = convert_vectors(np.atleast_2d(p), w.model, w.fix_params, **w.defaults)
+        r = w.marg_orbits(p_orb[:1], p_gp[:1], mu_GP, want_beta=True, want_cov=True, want_flux=True)
+        out.append({"beta": r.beta[0], "beta_cov": r.beta_cov[0], "beta_sd": r.beta_sd[0], "fl_cor": r.fl_cor[0],
+                    "lnp": float(r.lnp[0])})
+    return out
+
+
+def write_corrected_chunks(chunk_rows, chunks, fits, prefix="", fmt="npz"):
+    """Write the corrected fluxes of ``baseline_fit`` back into chunk files through ``data.Chunk.save`` (what
+    scripts/psoap_apply_calibration.py does with the frozen polynomials): ``chunk_rows`` holds ``(order, wl0, wl1)`` per chunk
+    as in ``chunks.dat``, ``chunks`` the UNMASKED 2-D ``data.Chunk`` objects in the same order (``Chunk.open``), ``fits`` the
+    list ``baseline_fit`` returned for workers built from their masked copies.  Masked pixels keep their flux.  -> the file
+    names."""
+    from .data import Chunk
+    names = []
+    for (order, wl0, wl1), ch, fit in zip(chunk_rows, chunks, fits):
+        if np.ndim(ch.wl) != 2:
+            raise ValueError("write_corrected_chunks needs the 2-D chunks (before apply_mask)")
+        if int(np.count_nonzero(ch.mask)) != np.shape(fit["fl_cor"])[0]:
+            raise ValueError("a fit does not have one corrected flux per unmasked pixel of its chunk")
+        fl = np.array(ch.fl, dtype=np.float64)
+        fl[ch.mask] = fit["fl_cor"]
+        names.append(Chunk(ch.wl, fl, ch.sigma, ch.date, ch.mask).save(order, wl0, wl1, prefix=prefix, fmt=fmt))
+    return names
 
 
 def loo_outliers(workers, p, pix_sigma=5.0, epoch_p=1e-4, mu_GP=1.0):

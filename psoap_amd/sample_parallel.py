@@ -65,6 +65,21 @@ def proposal_covariance(config, model, dim):
     return cov
 
 
+def baseline_block(config):
+    """config.yaml's optional ``baseline:`` block -> what ``ChunkWorker(baseline=...)`` takes, or ``None`` when it is absent:
+    ``order`` (Chebyshev degree per epoch), ``sd`` (order + 1 prior standard deviations), ``weight`` ("one" | "flux")."""
+    blk = config.get("baseline")
+    if blk is None:
+        return None
+    unknown = set(blk) - {"order", "sd", "weight"}
+    if unknown or "order" not in blk or "sd" not in blk:
+        raise ValueError(f"config baseline: needs 'order' and 'sd' (optionally 'weight'); got {sorted(blk)}")
+    sd = [float(v) for v in np.atleast_1d(blk["sd"])]
+    if len(sd) != int(blk["order"]) + 1:
+        raise ValueError("config baseline: 'sd' must hold order + 1 values")
+    return {"order": int(blk["order"]), "sd": sd, "weight": blk.get("weight", "one")}
+
+
 class Posterior:
     """``lnprob_batch(P)`` = prior + sum over chunks of the per-chunk GP log-likelihood (:371-390).
 
@@ -73,7 +88,7 @@ class Posterior:
     """
 
     def __init__(self, model, chunks, fix_params=(), parameters=None, soften=1.0, max_batch=1, world=1, rank=0,
-                 device_index=None, prior=None, make_worker=None):
+                 device_index=None, prior=None, make_worker=None, baseline=None):
         self.model = model
         self.fix_params = list(fix_params)
         self.parameters = dict(parameters or {})
@@ -90,12 +105,17 @@ class Posterior:
             def make_worker(ch):
                 return ChunkWorker(model, ch.lwl, ch.fl, ch.sigma, ch.epoch_index, ch.date1D,
                                    fix_params=self.fix_params, defaults=self.parameters, max_batch=self.max_batch,
-                                   device=device_index, soften=soften)
+                                   device=device_index, soften=soften, baseline=baseline)
+        elif baseline is not None:
+            raise ValueError("Posterior: a baseline needs the library's own workers (no make_worker)")
+        # a baseline (config.yaml's `baseline:` block): every chunk's likelihood with the per-epoch continuum integrated out --
+        # evaluated chunk by chunk, never through the group launch or a stream, which compute the plain likelihood
+        self.baseline = baseline
         self.workers = {k: make_worker(chunks[k]) for k in self.mine}
         self.device_lock = _NoLock()      # ensemble.SharedDeviceLock in dry runs with several ranks on one GPU
         # several chunks on this GPU: ONE launch of the persistent kernel over all of them per evaluation
         self.group = None
-        if len(self.mine) > 1 and all(hasattr(w, "upload_proposals") and hasattr(w, "handle") for w in self.workers.values()):
+        if baseline is None and len(self.mine) > 1 and all(hasattr(w, "upload_proposals") and hasattr(w, "handle") for w in self.workers.values()):
             from .chunk import ChunkGroup
             self.group = ChunkGroup([self.workers[k].handle for k in self.mine])
 
@@ -145,9 +165,12 @@ class Posterior:
     def can_stream(self) -> bool:
         """One chunk on this rank, and a worker that has the stream entry points: two resident launches cannot share a
         device (each takes every compute unit), so a rank with several chunks keeps the launch-per-step group path."""
-        return len(self.mine) == 1 and all(hasattr(w, "stream_submit") for w in self.workers.values())
+        return self.baseline is None and len(self.mine) == 1 and all(hasattr(w, "stream_submit") for w in self.workers.values())
 
     def stream_open(self, scheme: int = -1):
+        if self.baseline is not None:
+            raise RuntimeError("Posterior.stream_open: the streamed path evaluates the plain likelihood; this posterior has a "
+                               "baseline (run without --stream)")
         if not self.can_stream():
             raise RuntimeError("Posterior.stream_open: needs exactly one chunk on this rank (see can_stream)")
         self.workers[self.mine[0]].stream_open(self.max_batch, scheme)
@@ -237,7 +260,8 @@ def run(config, chunks, run_index=0, n_chains=1, seed=None, world=1, rank=0, dev
         raise FileExistsError("output directories exist (pass overwrite=True / --overwrite to replace them): "
                               + ", ".join(taken))
     post = Posterior(model, chunks, fix, pars, soften=config.get("soften", 1.0), max_batch=n_chains, world=world,
-                     rank=rank, device_index=device_index, prior=prior, make_worker=make_worker)
+                     rank=rank, device_index=device_index, prior=prior, make_worker=make_worker,
+                     baseline=baseline_block(config))
     if device_lock is not None:
         post.device_lock = device_lock
     try:
