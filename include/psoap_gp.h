@@ -314,6 +314,36 @@ int psoap_chunk_lnlike_marg(psoap_chunk *h, int B, int c, const double *lwl, con
                             double *lnp, double *parts, double *beta, double *beta_cov, double *fl_cor);
 int psoap_chunk_marg_release(psoap_chunk *h);
 
+/* ---- gradient of the continuum-marginalised likelihood ----------------------------------
+ * psoap_chunk_lnlike_marg_grad: the value psoap_chunk_lnlike_marg returns (lnp and parts
+ * bit for bit) and its analytic gradient, with the outputs of psoap_chunk_lnlike_grad:
+ *   grad_gp (B, 2c); grad_lwl (B, c, N), may be NULL; grad_mu (B), may be NULL; parts
+ *   (B, 4), may be NULL.
+ * H does not depend on the hyper-parameters, the rest-frame grids or mu_GP, so every
+ * derivative is that of psoap_chunk_lnlike_grad with K^-1 -> (K + Ht Ht^T)^-1 =
+ * Wi^T Wi - V V^T and alpha -> (K + Ht Ht^T)^-1 r: the staged factorisation runs on
+ * [K | I | Ht], the Gram matrix is factored with Xt = Wh^T Wi appended so that
+ * Vt = U_M^-T Xt falls out of it, and the fused contraction runs a second K loop of depth
+ * 128 Q over Vt (csrc/marg_grad_kernels.hpp, csrc/marg_grad_plan.hpp).  The derivative
+ * with respect to prior_sd is not provided.  No atomics, every sum in an order fixed by
+ * (N, c, baseline layout): a proposal's bits do not depend on the batch around it nor on
+ * which outputs are asked for; psoap_chunk_lnlike_grad keeps its bits.
+ * psoap_chunk_lnprob_marg_grad: psoap_chunk_lnprob_grad with that gradient in the middle
+ * (needs psoap_chunk_set_grid and psoap_chunk_set_dates); NOTE the order of its last two
+ * arguments: grad_mu (B, may be NULL), then grad_vel (B, c, n_epochs; may be NULL).
+ * Both take any B >= 1 (groups of at most 8 matrices and 1 GiB, as the gradient) and
+ * need psoap_chunk_set_baseline: without one, or after a psoap_chunk_set_data that
+ * followed a baseline with weights, they refuse with psoap_chunk_lnlike_marg's message.
+ * A negative hyper-parameter, a K or an M that does not factor, or a faster-than-light
+ * orbit gives lnp = -inf and NaN in every other output of that proposal, status 0.
+ * Workspace: the gradient's buffer with 8 Npad (2 Npad + 128 Q) bytes per matrix of a
+ * group (psoap_chunk_grad_release), and per matrix 8 * 128 Q (128 Q + Npad) bytes of
+ * [M | Xt] beside the baseline's device side (psoap_chunk_marg_release). */
+int psoap_chunk_lnlike_marg_grad(psoap_chunk *h, int B, int c, const double *lwl, const double *gp, double mu_GP,
+                                 double *lnp, double *parts, double *grad_gp, double *grad_lwl, double *grad_mu);
+int psoap_chunk_lnprob_marg_grad(psoap_chunk *h, int B, int model, const double *p_orb, const double *gp, double mu_GP,
+                                 double *lnp, double *grad_orb, double *grad_gp, double *grad_mu, double *grad_vel);
+
 /* Split-phase form of psoap_lnlike_batch: upload (H2D, async, on a copy stream of
  * its own), eval (kernels only, async), fetch (sync + D2H of B doubles).
  * A handle holds TWO proposal batches: an upload always goes to the one that is

@@ -65,6 +65,10 @@ SIGNATURES = {
     "psoap_chunk_lnlike_marg": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _dp, _dp, ctypes.c_double, _dp, _dp, _dp, _dp,
                                                _dp]),
     "psoap_chunk_marg_release": (ctypes.c_int, [_vp]),
+    "psoap_chunk_lnlike_marg_grad": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _dp, _dp, ctypes.c_double, _dp, _dp, _dp,
+                                                    _dp, _dp]),
+    "psoap_chunk_lnprob_marg_grad": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _dp, _dp, ctypes.c_double, _dp, _dp, _dp,
+                                                    _dp, _dp]),
     "psoap_batch_upload": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _dp, _dp, ctypes.c_double]),
     "psoap_batch_upload_velocities": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _dp, _dp, ctypes.c_double]),
     "psoap_chunk_set_dates": (ctypes.c_int, [_vp, _dp, ctypes.c_int]),

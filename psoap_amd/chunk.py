@@ -301,9 +301,53 @@ class ChunkHandle:
                               None if flc is None else flc[0])
         return MargResult(lnp, parts, beta, cov, flc)
 
+    def lnlike_marg_grad(self, lwls, gps, mu_GP: float = 1.0):
+        """Value and analytic gradient of the likelihood with the baseline of ``set_baseline`` integrated out
+        (include/psoap_gp.h: psoap_chunk_lnlike_marg_grad): ``(lnp, grad_gp, grad_lwl, grad_mu)`` with the shapes of
+        ``lnlike_grad`` -- ``lwls`` (c, N) with ``gps`` (2c,), or (B, c, N) with (B, 2c), any B.  ``lnp`` has the bits of
+        ``lnlike_marg``.  A negative hyper-parameter or a matrix that is not positive definite gives ``-inf`` and NaN
+        gradients."""
+        if getattr(self, "_baseline", None) is None:
+            raise _lib.PsoapError("lnlike_marg_grad: call set_baseline first")
+        lwls = as_f64(lwls)
+        single = lwls.ndim <= 2
+        if single:
+            lwls = np.atleast_2d(lwls)[None]
+        if lwls.ndim != 3 or lwls.shape[2] != self.N:
+            raise ValueError("lwls must have shape (c, N) or (B, c, N)")
+        B, c, _ = lwls.shape
+        lwls = as_f64(lwls, (B, c, self.N))
+        gps = as_f64(np.atleast_2d(as_f64(gps)), (B, 2 * c))
+        lnp, g_gp, g_lwl, g_mu = np.empty(B), np.empty((B, 2 * c)), np.empty((B, c, self.N)), np.empty(B)
+        check(self._L.psoap_chunk_lnlike_marg_grad(self._h, B, c, dptr(lwls), dptr(gps), float(mu_GP), dptr(lnp), None, dptr(g_gp),
+                                                   dptr(g_lwl), dptr(g_mu)), "psoap_chunk_lnlike_marg_grad")
+        if single:
+            return float(lnp[0]), g_gp[0], g_lwl[0], float(g_mu[0])
+        return lnp, g_gp, g_lwl, g_mu
+
+    def lnprob_marg_grad(self, model_id: int, p_orb, gps, mu_GP: float = 1.0, want_vel: bool = False):
+        """``lnprob_grad`` under the baseline of ``set_baseline`` (include/psoap_gp.h: psoap_chunk_lnprob_marg_grad; needs
+        ``set_grid`` and the dates): the same arguments, the same tuple."""
+        from .utils import MODEL_ID, N_COMPONENTS, n_params_orb
+        if getattr(self, "_baseline", None) is None:
+            raise _lib.PsoapError("lnprob_marg_grad: call set_baseline first")
+        name = {v: k for k, v in MODEL_ID.items()}.get(int(model_id))
+        if name is None:
+            raise ValueError(f"unknown orbit model {model_id}")
+        p_orb = as_f64(np.atleast_2d(p_orb))
+        B, c, n_orb = p_orb.shape[0], N_COMPONENTS[name], n_params_orb[name]
+        p_orb = as_f64(p_orb, (B, n_orb))
+        gps = as_f64(np.atleast_2d(as_f64(gps)), (B, 2 * c))
+        lnp, g_orb, g_gp, g_mu = np.empty(B), np.empty((B, n_orb)), np.empty((B, 2 * c)), np.empty(B)
+        g_vel = np.empty((B, c, self.n_epochs)) if want_vel else None
+        check(self._L.psoap_chunk_lnprob_marg_grad(self._h, B, int(model_id), dptr(p_orb), dptr(gps), float(mu_GP), dptr(lnp),
+                                                   dptr(g_orb), dptr(g_gp), dptr(g_mu), dptr(g_vel) if want_vel else None),
+              "psoap_chunk_lnprob_marg_grad")
+        return (lnp, g_orb, g_gp, g_mu, g_vel) if want_vel else (lnp, g_orb, g_gp, g_mu)
+
     def marg_release(self):
-        """Free the device side of the baseline and the workspace of ``lnlike_marg`` beyond the gradient's; the baseline
-        stays set and the next ``lnlike_marg`` allocates everything again."""
+        """Free the device side of the baseline and the workspace of ``lnlike_marg`` and ``lnlike_marg_grad`` beyond the
+        gradient's; the baseline stays set and the next call allocates everything again."""
         check(self._L.psoap_chunk_marg_release(self._h), "psoap_chunk_marg_release")
 
     def upload(self, lwls, gps, mu_GP: float = 1.0):

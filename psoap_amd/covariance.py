@@ -375,6 +375,34 @@ def baseline_posterior(lwls, fl, sigma, gp, x, epoch_index, order, prior_sd, wei
     return _marginal(lwls, fl, sigma, gp, x, epoch_index, order, prior_sd, weight, mu_GP, True)
 
 
+def lnlike_marginal_grad(lwls, fl, sigma, gp, x, epoch_index, order, prior_sd, weight=None, mu_GP=1.0):
+    """``(lnp, grad_gp (2c,), grad_lwl (c, N), grad_mu)``: the value of ``lnlike_marginal`` and its analytic derivatives with
+    respect to ``gp``, every rest-frame ln-wavelength and ``mu_GP`` (``ChunkHandle.lnlike_marg_grad``; the basis does not
+    depend on any of them, ``prior_sd`` has no derivative here).  Arguments as ``lnlike_marginal``; degenerate input as
+    ``lnlike_grad``: ``-inf`` with NaN gradients."""
+    gp = [float(g) for g in gp]
+    lw = np.stack([as_f64(w) for w in np.atleast_2d(lwls)])
+    if len(gp) != 2 * lw.shape[0]:
+        raise ValueError(f"gp must hold {2 * lw.shape[0]} values for {lw.shape[0]} component(s)")
+    ep = np.asarray(epoch_index, dtype=np.int64)
+    if ep.shape != lw.shape[1:] or (ep.size and ep.min() < 0):
+        raise ValueError("epoch_index must hold one non-negative epoch per pixel")
+    if any(g < 0.0 for g in gp):
+        return -np.inf, np.full(len(gp), np.nan), np.full(lw.shape, np.nan), np.nan
+    if any(l == 0.0 for l in gp[1::2]):
+        raise ZeroDivisionError("float division")
+    if not _matrix_is_finite(lw, sigma, gp):
+        raise ValueError(_NONFINITE)
+    h = _chunk_for(fl, sigma)
+    if not hasattr(h, "lnlike_marg_grad"):
+        raise _lib.PsoapError("lnlike_marginal_grad needs the device in this process (PSOAP_GPU_SERVER serves values only)")
+    h.set_baseline(order, x, ep, int(ep.max()) + 1, prior_sd, weight)      # (every call, as ``_marginal``)
+    lnp, g_gp, g_lwl, g_mu = h.lnlike_marg_grad(lw, gp, mu_GP)
+    if not np.isneginf(lnp) and not (np.all(np.isfinite(np.asarray(fl, dtype=np.float64))) and np.isfinite(mu_GP)):
+        raise ValueError(_NONFINITE)
+    return np.float64(lnp), g_gp, g_lwl, np.float64(g_mu)
+
+
 def velocity_gradient(grad_lwl, epoch_index, n_epochs):
     """``dlnL/dv[c, e]`` from ``dlnL/dlwl[c, i]``: the rest-frame grids are ``lwl - v[c, epoch]/c_kms``
     (``data.replicate_wls``), so ``dlnL/dv[c, e] = -(1/c_kms) sum_{i in epoch e} dlnL/dlwl[c, i]``.
@@ -396,17 +424,28 @@ def velocity_gradient(grad_lwl, epoch_index, n_epochs):
 GP_LOWER_BOUND = 1e-6       # optimize_GP keeps every amplitude and length scale at or above this
 
 
-def optimize_GP(lwls, fl, sigma, gp0, mu_GP=1.0, ftol=1e-10, full_output=False):
+def optimize_GP(lwls, fl, sigma, gp0, mu_GP=1.0, ftol=1e-10, full_output=False, baseline=None):
     """L-BFGS-B fit of the ``2c`` hyper-parameters ``(amp_0, l_0, ...)`` to one chunk from ``gp0``, with the analytic
     gradient (``lnlike_grad``, ``jac=True``) and every parameter bounded below at ``GP_LOWER_BOUND``.  Returns the fitted
     vector, or SciPy's whole result with ``full_output`` (``-result.fun`` is the likelihood reached, ``result.jac`` the
-    gradient of ``-lnL`` there).  ``optimize_GP_f`` is the reference's derivative-free fit."""
+    gradient of ``-lnL`` there).  ``optimize_GP_f`` is the reference's derivative-free fit.
+
+    ``baseline = dict(x=, epoch_index=, order=, prior_sd=, weight=)`` (``weight`` optional): the objective is the likelihood
+    with that per-epoch continuum integrated out (``lnlike_marginal_grad``), so no frozen calibration has to come first."""
     from scipy.optimize import minimize
     lw = np.stack([as_f64(w) for w in np.atleast_2d(lwls)])
     x0 = np.maximum(as_f64(gp0, (2 * lw.shape[0],)), GP_LOWER_BOUND)
+    if baseline is not None:
+        unknown = set(baseline) - {"x", "epoch_index", "order", "prior_sd", "weight"}
+        if unknown or not {"x", "epoch_index", "order", "prior_sd"} <= set(baseline):
+            raise ValueError(f"baseline needs 'x', 'epoch_index', 'order' and 'prior_sd' (and optionally 'weight'); got {sorted(baseline)}")
 
     def func(x):
-        lnp, g_gp, _g_lwl, _g_mu = lnlike_grad(lw, fl, sigma, x, mu_GP)
+        if baseline is None:
+            lnp, g_gp, _g_lwl, _g_mu = lnlike_grad(lw, fl, sigma, x, mu_GP)
+        else:
+            lnp, g_gp, _g_lwl, _g_mu = lnlike_marginal_grad(lw, fl, sigma, x, baseline["x"], baseline["epoch_index"],
+                                                            baseline["order"], baseline["prior_sd"], baseline.get("weight"), mu_GP)
         if not np.isfinite(lnp):
             return np.inf, np.zeros_like(x)
         return -lnp, -g_gp

@@ -109,13 +109,12 @@ __global__ void k_grad_alpha_finish(const double* __restrict__ partial, int nsla
 // A diagonal tile takes i <= j only; rows and columns >= N are masked.  The components are walked one after the other
 // (the accumulators leave few registers), the tile's sums meet in LDS -- the operand buffers of the product, free by then --
 // in a fixed order, and the workgroup stores them to its own GRAD_TILE_DOUBLES of `part`.
+// The epilogue: everything after the product, on the tile t = (K^-1)[ti][tj] in the accumulators (one function, two callers:
+// k_grad_contract below and k_marg_grad_contract of marg_grad_kernels.hpp, whose t is the tile of (K + Ht Ht^T)^-1).
 template <int C>
-__global__ __launch_bounds__(GEMM_THREADS, 2) void k_grad_contract(const double* __restrict__ Abase, size_t mat_stride,
-                                                                  int ld, int N, int Npad, int P,
-                                                                  const double* __restrict__ lwl,
-                                                                  const double* __restrict__ gp,
-                                                                  const double* __restrict__ alpha,
-                                                                  double* __restrict__ part)
+__device__ __forceinline__ void grad_contract_epilogue(const Tile& t, int b, int ti, int tj, int tile_index, int N, int Npad,
+                                                       int P, const double* __restrict__ lwl, const double* __restrict__ gp,
+                                                       const double* __restrict__ alpha, double* __restrict__ part)
 {
     constexpr int XS = 0;                 // [2][3][NB]: abscissae of the tile's rows (side 0) and columns (side 1)
     constexpr int AL = XS + 6 * NB;       // [2][NB]: alpha likewise
@@ -123,14 +122,6 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void k_grad_contract(const double*
     constexpr int CS = RS + 6 * NB;       // [2 wr][3][NB]: column sums of the two wave rows
     constexpr int HS = CS + 6 * NB;       // [4 waves][6]
     static_assert((HS + 24) * sizeof(double) <= GEMM_LDS_BYTES, "the epilogue fits the operand buffers");
-    const int b = blockIdx.y;
-    int ti, tj;
-    decode_upper(blockIdx.x, P, ti, tj);
-    const double* W = Abase + (size_t)b * mat_stride + Npad + (size_t)NB * tj * ld;
-    Tile t;
-    t.zero();
-    tile_gemm_tn(t, W + NB * ti, (size_t)ld, W + NB * tj, (size_t)ld, Npad - NB * tj, ti == tj);
-
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
     const int wr = wave >> 1, wc = wave & 1;
@@ -225,7 +216,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void k_grad_contract(const double*
         }
     }
     __syncthreads();
-    double* out = part + ((size_t)b * (P * (P + 1) / 2) + blockIdx.x) * GRAD_TILE_DOUBLES;
+    double* out = part + ((size_t)b * (P * (P + 1) / 2) + tile_index) * GRAD_TILE_DOUBLES;
     {
         const int side = tid >> 7, idx = tid & 127;
         const int src = side ? CS : RS;
@@ -237,6 +228,24 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void k_grad_contract(const double*
     if (tid < 2 * C)
         out[GRAD_HYP_OFF + tid] = ((psoap_smem[HS + tid] + psoap_smem[HS + 6 + tid]) + psoap_smem[HS + 12 + tid]) +
                                   psoap_smem[HS + 18 + tid];
+}
+
+template <int C>
+__global__ __launch_bounds__(GEMM_THREADS, 2) void k_grad_contract(const double* __restrict__ Abase, size_t mat_stride,
+                                                                  int ld, int N, int Npad, int P,
+                                                                  const double* __restrict__ lwl,
+                                                                  const double* __restrict__ gp,
+                                                                  const double* __restrict__ alpha,
+                                                                  double* __restrict__ part)
+{
+    const int b = blockIdx.y;
+    int ti, tj;
+    decode_upper(blockIdx.x, P, ti, tj);
+    const double* W = Abase + (size_t)b * mat_stride + Npad + (size_t)NB * tj * ld;
+    Tile t;
+    t.zero();
+    tile_gemm_tn(t, W + NB * ti, (size_t)ld, W + NB * tj, (size_t)ld, Npad - NB * tj, ti == tj);
+    grad_contract_epilogue<C>(t, b, ti, tj, (int)blockIdx.x, N, Npad, P, lwl, gp, alpha, part);
 }
 
 // The tiles' partial sums in tile order.  grid (P + 1, B), 128 threads.

@@ -35,6 +35,7 @@
 #include "fisher_kernels.hpp"
 #include "loo_kernels.hpp"
 #include "marg_kernels.hpp"
+#include "marg_grad_kernels.hpp"
 #include "abi_error.hpp"
 #include "plan_abi.hpp"
 #include "share.hpp"
@@ -221,6 +222,8 @@ struct psoap_chunk {
     // workspace (allocated by the first psoap_chunk_lnlike_marg after it; psoap_chunk_marg_release)
     psoap::MargSetup marg;
     std::unique_ptr<psoap::MargWs> mws;
+    // gradient of that likelihood: what it needs beyond the two workspaces above (psoap_chunk_marg_release)
+    std::unique_ptr<psoap::MargGradWs> mgws;
     // streamed evaluation (psoap_stream_*)
     StreamState stream;
     bool dev_locked = false;     // this handle holds a reference on the device's inter-process lock (device_lock_acquire)
@@ -302,6 +305,7 @@ static int configure_kernels(int device)
     HIP_TRY(fisher_configure_kernels());
     HIP_TRY(loo_configure_kernels());
     HIP_TRY(marg_configure_kernels());
+    HIP_TRY(marg_grad_configure_kernels());
     if (done.size() <= (size_t)device) done.resize((size_t)device + 1, 0);
     done[device] = 1;
     return 0;
@@ -2767,6 +2771,256 @@ extern "C" int psoap_chunk_lnlike_marg(psoap_chunk* h, int B, int c, const doubl
     return 0;
 }
 
+// ---- gradient of that likelihood (marg_grad_kernels.hpp) -------------------------------------------------
+template <int C>
+static void launch_marg_grad_contract(hipStream_t s, int nb, int ntiles, const double* A, size_t mstride, int ld, int N, int Npad,
+                                      int P, const double* dLwl, const double* dGp, const double* dAlpha, double* dPart,
+                                      const double* Mx, size_t m_stride, int ldm, int S)
+{
+    hipLaunchKernelGGL(k_marg_grad_contract<C>, dim3(ntiles, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, A, mstride, ld, N, Npad, P,
+                       dLwl, dGp, dAlpha, dPart, Mx, m_stride, ldm, S);
+}
+
+// Group after group of matrices through the gradient's workspace as [K | I | Ht] (marg_grad_plan.hpp), the Gram matrices
+// through the staged kernels as [M | Xt], then the gradient's own tail -- on the handle's first stream behind whatever the
+// handle has in flight.  The grids come from the host (lwl) or, with lwl == nullptr, from the orbits as in grad_run.
+static int marg_grad_run(psoap_chunk* h, const char* who, int B, int c, const double* lwl, int model, const double* p_orb,
+                         const double* gp, double mu_GP, double* lnp, double* parts, double* grad_gp, double* grad_lwl,
+                         double* grad_mu, double* grad_orb, double* grad_vel)
+{
+    if (const char* why = marg_grad_check(B, c, h->marg.valid, h->marg.stale_weight)) FAIL(std::string(who) + ": " + why);
+    const bool orbits = lwl == nullptr;
+    DEVICE_SCOPE(h->device);
+    if (int rc = enter_device(h->device)) return rc;
+    const MargPlan& pl = h->marg.plan;
+    MargGradPlan gpl;
+    marg_grad_plan(pl, gpl);
+    const int N = h->N, Npad = h->Npad, P = h->P, Q = pl.Q, q = pl.q, order = pl.order;
+    const int S = NB * Q, ld = gpl.ld, ldm = S + Npad, ldh = S;
+    const size_t mstride = marg_grad_matrix_doubles(Npad, Q), m_stride = (size_t)S * ldm, wstride = (size_t)Q * NB * NB;
+    const int G = marg_grad_group_size(B, Npad, Q);
+    const int ntiles = P * (P + 1) / 2, nslab = (Npad + 255) / 256, ngram = Q * (Q + 1) / 2;
+    if (!h->gws) h->gws.reset(new GradWs());
+    if (!h->mws) h->mws.reset(new MargWs());
+    if (!h->mgws) h->mgws.reset(new MargGradWs());
+    GradWs& w = *h->gws;
+    MargWs& m = *h->mws;
+    MargGradWs& mg = *h->mgws;
+    HIP_TRY(w.A.need((size_t)G * mstride));
+    HIP_TRY(w.Wt.need((size_t)G * NB * NB));
+    HIP_TRY(w.R.need((size_t)G * Npad));
+    HIP_TRY(w.Acc.need((size_t)G * ACC_ROWS));
+    HIP_TRY(w.Lwl.need((size_t)G * 3 * N));
+    HIP_TRY(w.Gp.need((size_t)G * 6));
+    HIP_TRY(w.Alpha.need((size_t)G * Npad));
+    HIP_TRY(w.APart.need((size_t)G * nslab * Npad));
+    HIP_TRY(w.Part.need((size_t)G * ntiles * GRAD_TILE_DOUBLES));
+    HIP_TRY(w.GradGp.need((size_t)G * 6));
+    HIP_TRY(w.GradX.need((size_t)G * 3 * N));
+    HIP_TRY(w.GradMu.need(G));
+    HIP_TRY(mg.Mx.need((size_t)G * m_stride));
+    HIP_TRY(mg.Zt.need((size_t)G * Npad));
+    HIP_TRY(m.WtM.need((size_t)G * wstride));
+    HIP_TRY(m.Rhs.need((size_t)G * S));
+    HIP_TRY(m.Gam.need((size_t)G * S));
+    HIP_TRY(m.RPart.need((size_t)G * nslab * S));
+    HIP_TRY(m.AccM.need((size_t)G * ACC_ROWS));
+    HIP_TRY(m.Out.need((size_t)G * 5));
+    HIP_TRY(m.Beta.need((size_t)G * q));
+    HIP_TRY(m.Flc.need((size_t)G * N));
+    hipStream_t s = h->streams[0];
+    if (int rc = marg_basis(h, m, s)) return rc;
+    const int* tab = m.Tab.p;
+    const int ne = h->n_epochs, np = orbits ? orbit_n_params(model) : 0;
+    std::vector<int> fast(orbits ? (size_t)B : 0, 0);
+    if (orbits) {
+        HIP_TRY(w.Porb.need((size_t)G * np));
+        HIP_TRY(w.Vel.need((size_t)G * c * ne));
+        HIP_TRY(w.Jac.need((size_t)G * c * ne * np));
+        HIP_TRY(w.Gv.need((size_t)G * c * ne));
+        HIP_TRY(w.GradOrb.need((size_t)G * np));
+        HIP_TRY(w.TooFast.need(G));
+        if (int rc = grad_epoch_lists(h, w, s)) return rc;
+    }
+    h->recs.clear();
+    const double tile_flops = 2.0 * NB * NB * (double)NB;
+    std::vector<double> out((size_t)B * 5);
+    double* Ah = w.A.p + Npad;          // what the kernels of marg_kernels.hpp take for [K | Ht]: Ht one block further right
+    for (int b0 = 0; b0 < B; b0 += G) {
+        const int nb = (B - b0 < G) ? B - b0 : G;
+        if (!orbits) {
+            HIP_TRY(hipMemcpyAsync(w.Lwl, lwl + (size_t)b0 * c * N, sizeof(double) * (size_t)nb * c * N, hipMemcpyHostToDevice, s));
+        } else {
+            HIP_TRY(hipMemcpyAsync(w.Porb, p_orb + (size_t)b0 * np, sizeof(double) * (size_t)nb * np, hipMemcpyHostToDevice, s));
+            HIP_TRY(hipMemsetAsync(w.TooFast, 0, sizeof(int) * (size_t)nb, s));
+            hipLaunchKernelGGL(k_orbit_jacobian, dim3((ne + 63) / 64, nb), dim3(64), 0, s, model, nb, ne, (const double*)w.Porb.p,
+                               (const double*)h->dDates, w.Vel.p, w.Jac.p, w.TooFast.p);
+            hipLaunchKernelGGL(k_doppler_shift, dim3((N + 255) / 256, nb * c), dim3(256), 0, s, w.Lwl.p, h->dGrid, h->dEpoch,
+                               (const double*)w.Vel.p, N, ne, nb * c);
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipMemcpyAsync(w.Gp, gp + (size_t)b0 * 2 * c, sizeof(double) * (size_t)nb * 2 * c, hipMemcpyHostToDevice, s));
+        if (int rc = prof_launch(h, s, PSOAP_K_FILL, 0.0, (double)nb * 12.0 * N * (N + 1.0), [&] {
+                with_components(c, [&](auto nc) {
+                    launch_grad_fill_contract<nc()>(false, s, nb, ntiles, w.A, mstride, ld, N, Npad, P, w.Lwl, w.Gp, h->dSigma, nullptr,
+                                                    nullptr);
+                });
+                hipLaunchKernelGGL(k_grad_init, dim3(ntiles, nb), dim3(256), 0, s, w.A.p, mstride, ld, Npad, P);
+                hipLaunchKernelGGL(k_marg_load, dim3(Q * P, nb), dim3(256), 0, s, Ah, mstride, ld, Npad, P, (const double*)m.Ht.p, ldh,
+                                   tab);
+            })) return rc;
+        if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
+                hipLaunchKernelGGL(k_init_rhs, dim3((Npad + 255) / 256, nb), dim3(256), 0, s, w.R.p, Npad, N, h->dFl, mu_GP, w.Acc.p);
+            })) return rc;
+        // block row p: the rest of K's row with I_0 .. I_p, and the slots of Ht whose first non-zero block row is <= p
+        for (int p = 0; p < P; ++p) {
+            const int k0 = p * NB;
+            const MargGradRow& row = gpl.rows[(size_t)p];
+            if (row.update_k + row.update_h > 0) {
+                const double units = (double)p * (P - p) + 0.5 * p * (p + 1.0) + (double)p * row.update_h;
+                if (int rc = prof_launch(h, s, PSOAP_K_PANEL_UPDATE, tile_flops * units * nb, 0.0, [&] {
+                        hipLaunchKernelGGL(k_marg_grad_panel_update, dim3(row.update_k + row.update_h, nb), dim3(GEMM_THREADS),
+                                           GEMM_LDS_BYTES, s, w.A.p, mstride, ld, k0, P, tab);
+                    })) return rc;
+            }
+            if (int rc = prof_launch(h, s, PSOAP_K_POTRF, 0.0, 0.0, [&] {
+                    hipLaunchKernelGGL(k_potrf_diag, dim3(nb), dim3(512), 0, s, w.A.p, mstride, ld, k0, w.Wt.p, w.R.p, Npad, w.Acc.p,
+                                       (size_t)NB * NB);
+                })) return rc;
+            if (int rc = prof_launch(h, s, PSOAP_K_TRSM, tile_flops * (row.strip_k + row.strip_h) * nb, 0.0, [&] {
+                    hipLaunchKernelGGL(k_trsm_strip, dim3(row.strip_k, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, w.A.p, mstride, ld, k0,
+                                       (const double*)w.Wt.p, w.R.p, Npad, (size_t)NB * NB);
+                    // the slots of Ht: the strip's first tile column moved onto tile column 2 P, and no right-hand side
+                    // (Npad = 0: every column counts as appended, r is only read)
+                    if (row.strip_h > 0)
+                        hipLaunchKernelGGL(k_trsm_strip, dim3(row.strip_h, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s,
+                                           w.A.p + (NB * gpl.tile_H - k0 - NB), mstride, ld, k0, (const double*)w.Wt.p, w.R.p, 0,
+                                           (size_t)NB * NB);
+                })) return rc;
+        }
+        if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
+                hipLaunchKernelGGL(k_marg_rhs_partial, dim3(Q, nslab, nb), dim3(256), 0, s, (const double*)Ah, mstride, ld, Npad, Q, tab,
+                                   (const double*)w.R.p, m.RPart.p, nslab);
+                hipLaunchKernelGGL(k_marg_rhs_finish, dim3((S + 255) / 256, nb), dim3(256), 0, s, (const double*)m.RPart.p, nslab, Npad,
+                                   Q, tab, m.Rhs.p);
+            })) return rc;
+        double gunits = 0.0;
+        for (const MargTile& t : pl.tiles) gunits += (t.ti == t.tj ? 0.75 : 1.0) * (Npad - t.k0) / NB;
+        for (int sl = 0; sl < Q; ++sl)
+            for (int tj = 0; tj < P; ++tj) gunits += P - std::min(P, std::max(pl.first[(size_t)pl.column[(size_t)sl]], tj));
+        if (int rc = prof_launch(h, s, PSOAP_K_GRAD, tile_flops * gunits * nb, 0.0, [&] {
+                hipLaunchKernelGGL(k_marg_gram, dim3(ngram, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)Ah, mstride, ld,
+                                   Npad, (const MargTile*)m.Tiles.p, mg.Mx.p, m_stride, ldm);
+                hipLaunchKernelGGL(k_marg_grad_cross, dim3(Q * P, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)w.A.p,
+                                   mstride, ld, Npad, P, Q, tab, mg.Mx.p, m_stride, ldm);
+            })) return rc;
+        // [M | Xt]: M = U_M^T U_M with bt alongside, and the appended block becomes Vt = U_M^-T Xt
+        for (int p = 0; p < Q; ++p) {
+            const int k0 = p * NB;
+            double* Wp = m.WtM.p + (size_t)p * NB * NB;
+            if (p > 0)
+                if (int rc = prof_launch(h, s, PSOAP_K_PANEL_UPDATE, tile_flops * p * (Q - p + P) * nb, 0.0, [&] {
+                        hipLaunchKernelGGL(k_panel_update, dim3(Q - p + P, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, mg.Mx.p, m_stride,
+                                           ldm, k0);
+                    })) return rc;
+            if (int rc = prof_launch(h, s, PSOAP_K_POTRF, 0.0, 0.0, [&] {
+                    hipLaunchKernelGGL(k_potrf_diag, dim3(nb), dim3(512), 0, s, mg.Mx.p, m_stride, ldm, k0, Wp, m.Rhs.p, S, m.AccM.p, wstride);
+                })) return rc;
+            if (int rc = prof_launch(h, s, PSOAP_K_TRSM, tile_flops * (Q - p - 1 + P) * nb, 0.0, [&] {
+                    hipLaunchKernelGGL(k_trsm_strip, dim3(Q - p - 1 + P, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, mg.Mx.p, m_stride, ldm,
+                                       k0, (const double*)Wp, m.Rhs.p, S, wstride);
+                })) return rc;
+        }
+        // lnL and g = U_M^-1 y; z - Wh g; alpha_m
+        if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
+                hipLaunchKernelGGL(k_marg_finish, dim3(nb), dim3(256), 0, s, N, P, Q, q, order, (const MatAcc*)w.Acc.p,
+                                   (const MatAcc*)m.AccM.p, (const double*)mg.Mx.p, m_stride, ldm, (const double*)m.WtM.p,
+                                   (const double*)m.Rhs.p, m.Gam.p, (const double*)m.Sd.p, (const int*)m.Epoch.p, tab,
+                                   (const double*)m.Ht.p, ldh, (const double*)h->dFl.p, m.Out.p, m.Beta.p, m.Flc.p, 1);
+                hipLaunchKernelGGL(k_marg_grad_resid, dim3(Npad / 4, nb), dim3(256), 0, s, (const double*)w.A.p, mstride, ld, Npad, Q,
+                                   tab, (const double*)w.R.p, (const double*)m.Gam.p, mg.Zt.p);
+                hipLaunchKernelGGL(k_grad_alpha_partial, dim3(P, nslab, nb), dim3(256), 0, s, (const double*)w.A.p, mstride, ld, Npad,
+                                   (const double*)mg.Zt.p, w.APart.p, nslab);
+                hipLaunchKernelGGL(k_grad_alpha_finish, dim3((Npad + 255) / 256, nb), dim3(256), 0, s, (const double*)w.APart.p, nslab,
+                                   Npad, w.Alpha.p);
+            })) return rc;
+        double cunits = 0.0;
+        for (int tj = 0; tj < P; ++tj) cunits += (double)(tj + 1) * (P - tj + Q);
+        if (int rc = prof_launch(h, s, PSOAP_K_GRAD, tile_flops * cunits * nb, 0.0, [&] {
+                with_components(c, [&](auto nc) {
+                    launch_marg_grad_contract<nc()>(s, nb, ntiles, w.A, mstride, ld, N, Npad, P, w.Lwl, w.Gp, w.Alpha, w.Part, mg.Mx,
+                                                    m_stride, ldm, S);
+                });
+            })) return rc;
+        if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
+                hipLaunchKernelGGL(k_grad_finish, dim3(P + 1, nb), dim3(128), 0, s, (const double*)w.Part.p, (const double*)w.Alpha.p,
+                                   (const double*)w.Gp.p, c, N, Npad, P, w.GradGp.p, w.GradX.p, w.GradMu.p);
+            })) return rc;
+        HIP_TRY(hipMemcpyAsync(out.data() + (size_t)b0 * 5, m.Out, sizeof(double) * (size_t)nb * 5, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(grad_gp + (size_t)b0 * 2 * c, w.GradGp, sizeof(double) * (size_t)nb * 2 * c, hipMemcpyDeviceToHost, s));
+        if (grad_lwl)
+            HIP_TRY(hipMemcpyAsync(grad_lwl + (size_t)b0 * c * N, w.GradX, sizeof(double) * (size_t)nb * c * N, hipMemcpyDeviceToHost, s));
+        if (grad_mu) HIP_TRY(hipMemcpyAsync(grad_mu + b0, w.GradMu, sizeof(double) * nb, hipMemcpyDeviceToHost, s));
+        if (orbits) {
+            const int CE = c * ne;
+            hipLaunchKernelGGL(k_epoch_fold, dim3((CE + 3) / 4, nb), dim3(256), 0, s, (const double*)w.GradX.p, (const int*)w.EpStart.p,
+                               (const int*)w.EpPix.p, c, N, ne, w.Gv.p);
+            hipLaunchKernelGGL(k_orbit_chain, dim3(nb), dim3(256), 0, s, (const double*)w.Gv.p, (const double*)w.Jac.p, CE, np,
+                               w.GradOrb.p);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(grad_orb + (size_t)b0 * np, w.GradOrb, sizeof(double) * (size_t)nb * np, hipMemcpyDeviceToHost, s));
+            if (grad_vel)
+                HIP_TRY(hipMemcpyAsync(grad_vel + (size_t)b0 * CE, w.Gv, sizeof(double) * (size_t)nb * CE, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemcpyAsync(fast.data() + b0, w.TooFast, sizeof(int) * (size_t)nb, hipMemcpyDeviceToHost, s));
+        }
+        HIP_TRY(hipStreamSynchronize(s));       // the next group reuses the workspace and the caller's arrays are pageable
+    }
+    if (collect_timings(h)) return 1;
+    // the conventions of psoap_chunk_lnlike_marg and psoap_chunk_lnlike_grad: a negative hyper-parameter, a K or an M that
+    // does not factor, a faster-than-light orbit -> -inf, and no gradient there
+    for (int b = 0; b < B; ++b) {
+        bool neg = false;
+        for (int k = 0; k < 2 * c; ++k) neg = neg || gp[(size_t)b * 2 * c + k] < 0.0;
+        if (orbits && fast[b]) neg = true;
+        lnp[b] = neg ? -INFINITY : out[(size_t)b * 5];
+        const bool bad = lnp[b] == -INFINITY;
+        if (parts)
+            for (int k = 0; k < 4; ++k) parts[(size_t)b * 4 + k] = bad ? NAN : out[(size_t)b * 5 + 1 + k];
+        if (!bad) continue;
+        for (int k = 0; k < 2 * c; ++k) grad_gp[(size_t)b * 2 * c + k] = NAN;
+        if (grad_lwl)
+            for (size_t k = 0; k < (size_t)c * N; ++k) grad_lwl[(size_t)b * c * N + k] = NAN;
+        if (grad_mu) grad_mu[b] = NAN;
+        if (orbits) {
+            for (int k = 0; k < np; ++k) grad_orb[(size_t)b * np + k] = NAN;
+            if (grad_vel)
+                for (size_t k = 0; k < (size_t)c * ne; ++k) grad_vel[(size_t)b * c * ne + k] = NAN;
+        }
+    }
+    return 0;
+}
+
+extern "C" int psoap_chunk_lnlike_marg_grad(psoap_chunk* h, int B, int c, const double* lwl, const double* gp, double mu_GP,
+                                            double* lnp, double* parts, double* grad_gp, double* grad_lwl, double* grad_mu)
+{
+    if (!h || !lwl || !gp || !lnp || !grad_gp) FAIL("psoap_chunk_lnlike_marg_grad: bad arguments");
+    if (h->stream.open) FAIL("psoap_chunk_lnlike_marg_grad: the handle has an open stream (psoap_stream_close first)");
+    return marg_grad_run(h, "psoap_chunk_lnlike_marg_grad", B, c, lwl, -1, nullptr, gp, mu_GP, lnp, parts, grad_gp, grad_lwl,
+                         grad_mu, nullptr, nullptr);
+}
+
+extern "C" int psoap_chunk_lnprob_marg_grad(psoap_chunk* h, int B, int model, const double* p_orb, const double* gp, double mu_GP,
+                                            double* lnp, double* grad_orb, double* grad_gp, double* grad_mu, double* grad_vel)
+{
+    if (!h || !p_orb || !gp || !lnp || !grad_orb || !grad_gp) FAIL("psoap_chunk_lnprob_marg_grad: bad arguments");
+    if (B < 1) FAIL("psoap_chunk_lnprob_marg_grad: B must be at least 1");
+    if (!h->dGrid || !h->dDates) FAIL("psoap_chunk_lnprob_marg_grad: call psoap_chunk_set_grid and psoap_chunk_set_dates first");
+    if (h->stream.open) FAIL("psoap_chunk_lnprob_marg_grad: the handle has an open stream (psoap_stream_close first)");
+    if (int rc = check_orbits(model, B, p_orb)) return rc;
+    return marg_grad_run(h, "psoap_chunk_lnprob_marg_grad", B, orbit_n_components(model), nullptr, model, p_orb, gp, mu_GP, lnp,
+                         nullptr, grad_gp, nullptr, grad_mu, grad_orb, grad_vel);
+}
+
 // frees the device side of the baseline and the workspace; the baseline itself stays set (the next call builds Ht again)
 extern "C" int psoap_chunk_marg_release(psoap_chunk* h)
 {
@@ -2775,6 +3029,7 @@ extern "C" int psoap_chunk_marg_release(psoap_chunk* h)
     if (set_dev(h)) return 1;
     HIP_TRY(hipStreamSynchronize(h->streams[0]));
     h->mws.reset();
+    h->mgws.reset();
     return 0;
 }
 

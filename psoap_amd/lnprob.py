@@ -26,7 +26,8 @@ class ChunkWorker:
 
         ``baseline = {"order": k, "sd": [s_0 .. s_k], "weight": "one" | "flux"}``: ``lnprob`` and ``lnprob_batch`` evaluate the
         likelihood with a Chebyshev polynomial of degree k per epoch integrated out (``ChunkHandle.lnlike_marg``) -- an
-        additive offset ("one") or the polynomial times the flux ("flux").  The split-phase and streamed entries
+        additive offset ("one") or the polynomial times the flux ("flux") -- and ``lnprob_grad*`` its gradient
+        (``ChunkHandle.lnprob_marg_grad``).  The split-phase and streamed entries
         (``upload_*``, ``stream_*``) evaluate the plain likelihood and refuse to run on such a worker.  ``None``: every
         path as it was."""
         self.model = model
@@ -152,13 +153,16 @@ class ChunkWorker:
         """The gradient with the vectors already split, as ``upload_orbits`` takes them: orbital parameters (B, n_orb) and
         GP parameters (B, 2c) -> ``(lnp (B,), grad_orb (B, n_orb), grad_gp (B, 2c), grad_mu (B,))`` (and ``grad_vel
         (B, c, n_epochs)`` with ``want_vel``).  Kepler solve, orbit Jacobian, Doppler shift, likelihood gradient and the
-        chain rule run on the device.  The only way in for ST2, for the reason ``upload_orbits`` documents."""
+        chain rule run on the device.  The only way in for ST2, for the reason ``upload_orbits`` documents.  On a worker
+        with a baseline the likelihood in the middle is the marginal one (``ChunkHandle.lnprob_marg_grad``)."""
         if os.environ.get("PSOAP_GPU_SERVER", "").strip().lower() not in ("", "0"):
             raise _lib.PsoapError("lnprob_grad needs the device in this process (PSOAP_GPU_SERVER serves values only)")
         p_orb = as_f64(np.atleast_2d(p_orb))
         B = p_orb.shape[0]
         p_orb = as_f64(p_orb, (B, n_params_orb[self.model]))
         p_gp = as_f64(np.atleast_2d(p_gp), (B, 2 * N_COMPONENTS[self.model]))
+        if getattr(self, "baseline", None) is not None:      # (the gradient of what ``lnprob`` returns on this worker)
+            return self.handle.lnprob_marg_grad(MODEL_ID[self.model], p_orb, p_gp, mu_GP, want_vel=want_vel)
         return self.handle.lnprob_grad(MODEL_ID[self.model], p_orb, p_gp, mu_GP, want_vel=want_vel)
 
     def lnprob_grad_batch(self, ps, mu_GP: float = 1.0):
@@ -353,7 +357,9 @@ def optimize_orbit(workers, p0, bounds=None, mu_GP=1.0, ftol=1e-10, full_output=
     (``ChunkWorker.lnprob_grad``, ``jac=True``): the objective is minus the SUM of the workers' ``lnprob``, the sum
     ``sample_parallel`` takes over its chunks.  No priors: the caller passes ``bounds`` (SciPy's form, one pair per fitted
     parameter).  Returns the fitted vector, or SciPy's whole result with ``full_output`` (``-result.fun`` is the summed
-    ``lnprob`` reached, ``result.jac`` the gradient of minus that sum there).  Modelled on ``covariance.optimize_GP``."""
+    ``lnprob`` reached, ``result.jac`` the gradient of minus that sum there).  Modelled on ``covariance.optimize_GP``.
+    Workers built with ``baseline=...`` are fitted under their marginal likelihood: ``baseline_fit`` at the result then gives
+    the continuum that belongs to the fit."""
     from scipy.optimize import minimize
     workers = list(workers) if isinstance(workers, (list, tuple)) else [workers]
     x0 = as_f64(np.atleast_1d(p0))
