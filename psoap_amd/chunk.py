@@ -139,12 +139,8 @@ class ChunkHandle:
               "psoap_lnlike_batch")
         return out
 
-    def lnlike_grad(self, lwls, gp, mu_GP: float = 1.0):
-        """Value and analytic gradient of the likelihood (include/psoap_gp.h: psoap_chunk_lnlike_grad).
-
-        ``lwls`` (c, N) with ``gp`` (2c,) -> ``(lnp, grad_gp (2c,), grad_lwl (c, N), grad_mu)``; ``lwls`` (B, c, N) with
-        ``gp`` (B, 2c) -> the same with a leading axis of B (any B: the proposals are walked in groups through a bounded
-        workspace).  A negative hyper-parameter or a matrix that is not positive definite gives ``-inf`` and NaN gradients."""
+    def _proposals(self, lwls, gp):
+        """``lwls`` (c, N) with ``gp`` (2c,), or (B, c, N) with (B, 2c) -> ``(single, B, c, lwls (B, c, N), gps (B, 2c))``"""
         lwls = as_f64(lwls)
         single = lwls.ndim <= 2
         if single:
@@ -152,14 +148,48 @@ class ChunkHandle:
         if lwls.ndim != 3 or lwls.shape[2] != self.N:
             raise ValueError("lwls must have shape (c, N) or (B, c, N)")
         B, c, _ = lwls.shape
-        lwls = as_f64(lwls, (B, c, self.N))
-        gps = as_f64(np.atleast_2d(as_f64(gp)), (B, 2 * c))
+        return single, B, c, as_f64(lwls, (B, c, self.N)), as_f64(np.atleast_2d(as_f64(gp)), (B, 2 * c))
+
+    def _orbit_proposals(self, model_id, p_orb, gps):
+        """-> ``(B, c, n_orb, p_orb (B, n_orb), gps (B, 2c))`` for the orbit model ``model_id``"""
+        from .utils import MODEL_ID, N_COMPONENTS, n_params_orb
+        name = {v: k for k, v in MODEL_ID.items()}.get(int(model_id))
+        if name is None:
+            raise ValueError(f"unknown orbit model {model_id}")
+        p_orb = as_f64(np.atleast_2d(p_orb))
+        B, c, n_orb = p_orb.shape[0], N_COMPONENTS[name], n_params_orb[name]
+        # (the library reads exactly n_orb doubles per proposal)
+        return B, c, n_orb, as_f64(p_orb, (B, n_orb)), as_f64(np.atleast_2d(as_f64(gps)), (B, 2 * c))
+
+    def _lnlike_grad(self, entry, lwls, gp, mu_GP, *after_lnp):
+        """the body of ``lnlike_grad`` and ``lnlike_marg_grad``: ``entry`` names the library's function, ``after_lnp`` is what
+        it takes between ``lnp`` and the three gradients"""
+        single, B, c, lwls, gps = self._proposals(lwls, gp)
         lnp, g_gp, g_lwl, g_mu = np.empty(B), np.empty((B, 2 * c)), np.empty((B, c, self.N)), np.empty(B)
-        check(self._L.psoap_chunk_lnlike_grad(self._h, B, c, dptr(lwls), dptr(gps), float(mu_GP), dptr(lnp), dptr(g_gp),
-                                              dptr(g_lwl), dptr(g_mu)), "psoap_chunk_lnlike_grad")
+        check(getattr(self._L, entry)(self._h, B, c, dptr(lwls), dptr(gps), float(mu_GP), dptr(lnp), *after_lnp, dptr(g_gp),
+                                      dptr(g_lwl), dptr(g_mu)), entry)
         if single:
             return float(lnp[0]), g_gp[0], g_lwl[0], float(g_mu[0])
         return lnp, g_gp, g_lwl, g_mu
+
+    def _lnprob_grad(self, entry, vel_last, model_id, p_orb, gps, mu_GP, want_vel):
+        """the body of ``lnprob_grad`` and ``lnprob_marg_grad``: ``entry`` names the library's function, which takes
+        ``grad_vel`` after ``grad_mu`` (``vel_last``) or before it"""
+        B, c, n_orb, p_orb, gps = self._orbit_proposals(model_id, p_orb, gps)
+        lnp, g_orb, g_gp, g_mu = np.empty(B), np.empty((B, n_orb)), np.empty((B, 2 * c)), np.empty(B)
+        g_vel = np.empty((B, c, self.n_epochs)) if want_vel else None
+        tail = (dptr(g_mu), dptr(g_vel) if want_vel else None)
+        check(getattr(self._L, entry)(self._h, B, int(model_id), dptr(p_orb), dptr(gps), float(mu_GP), dptr(lnp), dptr(g_orb),
+                                      dptr(g_gp), *(tail if vel_last else tail[::-1])), entry)
+        return (lnp, g_orb, g_gp, g_mu, g_vel) if want_vel else (lnp, g_orb, g_gp, g_mu)
+
+    def lnlike_grad(self, lwls, gp, mu_GP: float = 1.0):
+        """Value and analytic gradient of the likelihood (include/psoap_gp.h: psoap_chunk_lnlike_grad).
+
+        ``lwls`` (c, N) with ``gp`` (2c,) -> ``(lnp, grad_gp (2c,), grad_lwl (c, N), grad_mu)``; ``lwls`` (B, c, N) with
+        ``gp`` (B, 2c) -> the same with a leading axis of B (any B: the proposals are walked in groups through a bounded
+        workspace).  A negative hyper-parameter or a matrix that is not positive definite gives ``-inf`` and NaN gradients."""
+        return self._lnlike_grad("psoap_chunk_lnlike_grad", lwls, gp, mu_GP)
 
     def lnprob_grad(self, model_id: int, p_orb, gps, mu_GP: float = 1.0, want_vel: bool = False):
         """Value and gradient of ``lnprob`` through the Kepler solve and the Doppler shift (include/psoap_gp.h:
@@ -168,20 +198,7 @@ class ChunkHandle:
         ``p_orb`` (B, n_orb), ``gps`` (B, 2c) -> ``(lnp (B,), grad_orb (B, n_orb), grad_gp (B, 2c), grad_mu (B,))``, with
         ``grad_vel (B, c, n_epochs)`` appended when ``want_vel``.  A faster-than-light proposal, a negative hyper-parameter
         or a matrix that is not positive definite gives ``-inf`` and NaN gradients for that proposal."""
-        from .utils import MODEL_ID, N_COMPONENTS, n_params_orb
-        name = {v: k for k, v in MODEL_ID.items()}.get(int(model_id))
-        if name is None:
-            raise ValueError(f"unknown orbit model {model_id}")
-        p_orb = as_f64(np.atleast_2d(p_orb))
-        B, c, n_orb = p_orb.shape[0], N_COMPONENTS[name], n_params_orb[name]
-        p_orb = as_f64(p_orb, (B, n_orb))      # (the library reads exactly that many doubles per proposal)
-        gps = as_f64(np.atleast_2d(as_f64(gps)), (B, 2 * c))
-        lnp, g_orb, g_gp, g_mu = np.empty(B), np.empty((B, n_orb)), np.empty((B, 2 * c)), np.empty(B)
-        g_vel = np.empty((B, c, self.n_epochs)) if want_vel else None
-        check(self._L.psoap_chunk_lnprob_grad(self._h, B, int(model_id), dptr(p_orb), dptr(gps), float(mu_GP), dptr(lnp),
-                                              dptr(g_orb), dptr(g_gp), dptr(g_vel) if want_vel else None, dptr(g_mu)),
-              "psoap_chunk_lnprob_grad")
-        return (lnp, g_orb, g_gp, g_mu, g_vel) if want_vel else (lnp, g_orb, g_gp, g_mu)
+        return self._lnprob_grad("psoap_chunk_lnprob_grad", False, model_id, p_orb, gps, mu_GP, want_vel)
 
     def grad_release(self):
         """Free the gradient workspace (16 Npad^2 bytes per matrix of a group); the next ``lnlike_grad`` allocates it again."""
@@ -274,15 +291,7 @@ class ChunkHandle:
             raise _lib.PsoapError("lnlike_marg: call set_baseline first")
         ne, order = self._baseline
         q = ne * (order + 1)
-        lwls = as_f64(lwls)
-        single = lwls.ndim <= 2
-        if single:
-            lwls = np.atleast_2d(lwls)[None]
-        if lwls.ndim != 3 or lwls.shape[2] != self.N:
-            raise ValueError("lwls must have shape (c, N) or (B, c, N)")
-        B, c, _ = lwls.shape
-        lwls = as_f64(lwls, (B, c, self.N))
-        gps = as_f64(np.atleast_2d(as_f64(gps)), (B, 2 * c))
+        single, B, c, lwls, gps = self._proposals(lwls, gps)
         more = want_beta or want_cov or want_flux
         lnp = np.empty(B)
         parts = np.empty((B, 4)) if more else None
@@ -309,41 +318,14 @@ class ChunkHandle:
         gradients."""
         if getattr(self, "_baseline", None) is None:
             raise _lib.PsoapError("lnlike_marg_grad: call set_baseline first")
-        lwls = as_f64(lwls)
-        single = lwls.ndim <= 2
-        if single:
-            lwls = np.atleast_2d(lwls)[None]
-        if lwls.ndim != 3 or lwls.shape[2] != self.N:
-            raise ValueError("lwls must have shape (c, N) or (B, c, N)")
-        B, c, _ = lwls.shape
-        lwls = as_f64(lwls, (B, c, self.N))
-        gps = as_f64(np.atleast_2d(as_f64(gps)), (B, 2 * c))
-        lnp, g_gp, g_lwl, g_mu = np.empty(B), np.empty((B, 2 * c)), np.empty((B, c, self.N)), np.empty(B)
-        check(self._L.psoap_chunk_lnlike_marg_grad(self._h, B, c, dptr(lwls), dptr(gps), float(mu_GP), dptr(lnp), None, dptr(g_gp),
-                                                   dptr(g_lwl), dptr(g_mu)), "psoap_chunk_lnlike_marg_grad")
-        if single:
-            return float(lnp[0]), g_gp[0], g_lwl[0], float(g_mu[0])
-        return lnp, g_gp, g_lwl, g_mu
+        return self._lnlike_grad("psoap_chunk_lnlike_marg_grad", lwls, gps, mu_GP, None)      # (``parts``: not asked for)
 
     def lnprob_marg_grad(self, model_id: int, p_orb, gps, mu_GP: float = 1.0, want_vel: bool = False):
         """``lnprob_grad`` under the baseline of ``set_baseline`` (include/psoap_gp.h: psoap_chunk_lnprob_marg_grad; needs
         ``set_grid`` and the dates): the same arguments, the same tuple."""
-        from .utils import MODEL_ID, N_COMPONENTS, n_params_orb
         if getattr(self, "_baseline", None) is None:
             raise _lib.PsoapError("lnprob_marg_grad: call set_baseline first")
-        name = {v: k for k, v in MODEL_ID.items()}.get(int(model_id))
-        if name is None:
-            raise ValueError(f"unknown orbit model {model_id}")
-        p_orb = as_f64(np.atleast_2d(p_orb))
-        B, c, n_orb = p_orb.shape[0], N_COMPONENTS[name], n_params_orb[name]
-        p_orb = as_f64(p_orb, (B, n_orb))
-        gps = as_f64(np.atleast_2d(as_f64(gps)), (B, 2 * c))
-        lnp, g_orb, g_gp, g_mu = np.empty(B), np.empty((B, n_orb)), np.empty((B, 2 * c)), np.empty(B)
-        g_vel = np.empty((B, c, self.n_epochs)) if want_vel else None
-        check(self._L.psoap_chunk_lnprob_marg_grad(self._h, B, int(model_id), dptr(p_orb), dptr(gps), float(mu_GP), dptr(lnp),
-                                                   dptr(g_orb), dptr(g_gp), dptr(g_mu), dptr(g_vel) if want_vel else None),
-              "psoap_chunk_lnprob_marg_grad")
-        return (lnp, g_orb, g_gp, g_mu, g_vel) if want_vel else (lnp, g_orb, g_gp, g_mu)
+        return self._lnprob_grad("psoap_chunk_lnprob_marg_grad", True, model_id, p_orb, gps, mu_GP, want_vel)
 
     def marg_release(self):
         """Free the device side of the baseline and the workspace of ``lnlike_marg`` and ``lnlike_marg_grad`` beyond the

@@ -58,6 +58,7 @@ using namespace psoap;
 #define NEED(buf, count) HIP_TRY_AS((buf).pinned ? "hipHostMalloc(" #buf ")" : "hipMalloc(" #buf ")", (buf).need(count))
 
 static const int MAX_GROUPS = 8;
+static const double TILE_FLOPS = 2.0 * NB * NB * (double)NB;      // one NB^3 tile product: the unit the profiling records book
 
 // several processes on one device (share.hpp) ask the runtime one thing
 static std::string share_bus_id(int device)
@@ -766,45 +767,75 @@ extern "C" int psoap_orbit_velocities(int device, int model, int B, const double
 }
 
 // ---- profiling helpers ------------------------------------------------------------------
-static int prof_begin(psoap_chunk* h, hipStream_t s, int cls, double flops, double bytes)
-{
-    if (!h->profiling) return 0;
-    size_t need = h->recs.size() * 2 + 2;
-    while (h->evPool.size() < need) {
-        Event e;
-        HIP_TRY(e.create(hipEventDefault));      // (timed)
-        h->evPool.push_back(std::move(e));
-    }
-    psoap_chunk::Rec r;
-    r.cls = cls;
-    r.e0 = (int)h->recs.size() * 2;
-    r.e1 = r.e0 + 1;
-    r.flops = flops;
-    r.bytes = bytes;
-    h->recs.push_back(r);
-    HIP_TRY(hipEventRecord(h->evPool[r.e0], s));
-    return 0;
-}
-static int prof_end(psoap_chunk* h, hipStream_t s)
-{
-    if (!h->profiling) return 0;
-    HIP_TRY(hipEventRecord(h->evPool[h->recs.back().e1], s));
-    return 0;
-}
-
-// One bracketed step: what `launch` queues on s, booked under class cls.  A launch that returns nothing queues kernels
-// only and the launch error is asked for here; one that makes runtime calls of its own returns its status.
+// One bracketed step: what `launch` queues on s, booked under class cls (with profiling on: a record and a pair of timed
+// events around it).  A launch that returns nothing queues kernels only and the launch error is asked for here; one that
+// makes runtime calls of its own returns its status.
 template <class L>
 static int prof_launch(psoap_chunk* h, hipStream_t s, int cls, double flops, double bytes, L&& launch)
 {
-    if (prof_begin(h, s, cls, flops, bytes)) return 1;
+    if (h->profiling) {
+        size_t need = h->recs.size() * 2 + 2;
+        while (h->evPool.size() < need) {
+            Event e;
+            HIP_TRY(e.create(hipEventDefault));      // (timed)
+            h->evPool.push_back(std::move(e));
+        }
+        psoap_chunk::Rec r;
+        r.cls = cls;
+        r.e0 = (int)h->recs.size() * 2;
+        r.e1 = r.e0 + 1;
+        r.flops = flops;
+        r.bytes = bytes;
+        h->recs.push_back(r);
+        HIP_TRY(hipEventRecord(h->evPool[r.e0], s));
+    }
     if constexpr (std::is_void<decltype(launch())>::value) {
         launch();
         HIP_TRY(hipGetLastError());
     } else if (int rc = launch()) {
         return rc;
     }
-    return prof_end(h, s);
+    if (h->profiling) HIP_TRY(hipEventRecord(h->evPool[h->recs.back().e1], s));
+    return 0;
+}
+
+// One block row of the staged factorisation of nb matrices: what k_potrf_diag and k_trsm_strip take, and the extent of the strip.
+struct StagedRow {
+    double* A;             // the first matrix; `stride` doubles from one to the next, leading dimension ld
+    size_t stride;
+    int ld;
+    double* R;             // the right-hand sides, r_rows doubles each (columns from r_rows on count as appended)
+    int r_rows;
+    MatAcc* acc;
+    double* Wt;            // where THIS row's inverse diagonal tile goes, wt_stride doubles from one matrix to the next
+    size_t wt_stride;
+    int strip;             // tiles right of the diagonal tile
+    // a second strip under the same bracket with no right-hand side beside it (the slots of Ht in marg_grad_run): A2 is the
+    // matrix pointer moved so that the strip's first tile column, k0 + NB, falls on this strip's first tile
+    double* A2 = nullptr;
+    int strip2 = 0;
+};
+
+// The three brackets of block row k0 / NB, in this order: `update` (the caller's panel-update launch, booked with
+// update_flops under PANEL_UPDATE; nullptr: none), the diagonal tile under POTRF, the strip under TRSM where there is one.
+// Every staged sweep of this file goes through here: the only launch sites of k_potrf_diag and k_trsm_strip.
+template <class U>
+static int staged_row(psoap_chunk* h, hipStream_t s, const StagedRow& m, int nb, int k0, const U* update, double update_flops)
+{
+    if (update)
+        if (int rc = prof_launch(h, s, PSOAP_K_PANEL_UPDATE, update_flops, 0.0, *update)) return rc;
+    if (int rc = prof_launch(h, s, PSOAP_K_POTRF, 0.0, 0.0, [&] {
+            hipLaunchKernelGGL(k_potrf_diag, dim3(nb), dim3(512), 0, s, m.A, m.stride, m.ld, k0, m.Wt, m.R, m.r_rows, m.acc, m.wt_stride);
+        })) return rc;
+    if (m.strip + m.strip2 > 0)
+        if (int rc = prof_launch(h, s, PSOAP_K_TRSM, TILE_FLOPS * (m.strip + m.strip2) * nb, 0.0, [&] {
+                hipLaunchKernelGGL(k_trsm_strip, dim3(m.strip, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, m.A, m.stride, m.ld, k0,
+                                   (const double*)m.Wt, m.R, m.r_rows, m.wt_stride);
+                if (m.strip2 > 0)
+                    hipLaunchKernelGGL(k_trsm_strip, dim3(m.strip2, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, m.A2, m.stride, m.ld,
+                                       k0, (const double*)m.Wt, m.R, 0, m.wt_stride);
+            })) return rc;
+    return 0;
 }
 
 template <int C>
@@ -1113,23 +1144,12 @@ static int eval_staged(psoap_chunk* h)
         for (int g = 0; g < G; ++g) {
             hipStream_t s = h->streams[g];
             const int b0 = gb0[g], nb = gb0[g + 1] - gb0[g];
-            double* Kg = h->dK + (size_t)b0 * h->mat_stride;
-            if (p > 0)
-                if (int rc = prof_launch(h, s, PSOAP_K_PANEL_UPDATE, 2.0 * NB * NB * (double)k0 * ntile * nb, 0.0, [&] {
-                        hipLaunchKernelGGL(k_panel_update, dim3(ntile, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, Kg,
-                                           h->mat_stride, h->ld, k0);
-                    })) return rc;
-            if (int rc = prof_launch(h, s, PSOAP_K_POTRF, 0.0, 0.0, [&] {
-                    hipLaunchKernelGGL(k_potrf_diag, dim3(nb), dim3(512), 0, s, Kg, h->mat_stride, h->ld, k0,
-                                       h->dWt + (size_t)b0 * WT_STRIDE, h->dR + (size_t)b0 * h->Npad, h->Npad,
-                                       h->dAcc + (size_t)b0 * ACC_ROWS, (size_t)WT_STRIDE);
-                })) return rc;
-            if (ntile > 1)
-                if (int rc = prof_launch(h, s, PSOAP_K_TRSM, 2.0 * NB * NB * (double)NB * (ntile - 1) * nb, 0.0, [&] {
-                        hipLaunchKernelGGL(k_trsm_strip, dim3(ntile - 1, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, Kg,
-                                           h->mat_stride, h->ld, k0, h->dWt + (size_t)b0 * WT_STRIDE,
-                                           h->dR + (size_t)b0 * h->Npad, h->Npad, (size_t)WT_STRIDE);
-                    })) return rc;
+            const StagedRow row{h->dK + (size_t)b0 * h->mat_stride, h->mat_stride, h->ld, h->dR + (size_t)b0 * h->Npad, h->Npad,
+                                h->dAcc + (size_t)b0 * ACC_ROWS, h->dWt + (size_t)b0 * WT_STRIDE, (size_t)WT_STRIDE, ntile - 1};
+            auto update = [&] {
+                hipLaunchKernelGGL(k_panel_update, dim3(ntile, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, row.A, row.stride, row.ld, k0);
+            };
+            if (int rc = staged_row(h, s, row, nb, k0, p > 0 ? &update : nullptr, TILE_FLOPS * p * ntile * nb)) return rc;
         }
     }
     // finalize per group; group 0's stream gathers the others and does the D2H
@@ -2019,16 +2039,103 @@ extern "C" int psoap_lnlike(psoap_chunk* h, int c, const double* lwl, const doub
 // The staged factorisation of [K | I] per group of matrices, alpha = W^T z, the fused contraction, the finishing sums.
 // Everything lives in the handle's gradient workspace and runs on the handle's first stream behind whatever the handle
 // has in flight: neither the proposal slots nor the workspaces of the likelihood paths are touched.
-template <int C>
-static void launch_grad_fill_contract(bool contract, hipStream_t s, int nb, int ntiles, double* A, size_t mstride, int ld, int N,
-                                      int Npad, int P, const double* dLwl, const double* dGp, const double* dSigma,
-                                      const double* dAlpha, double* dPart)
+//
+// What the analysis paths below share, and what a new one is expected to reuse ("The host layer"): grad_ws_need sizes
+// the workspace, launch_grad_fill fills K, staged_row (above) is every block row of every factorisation, launch_alpha makes
+// alpha, orbit_front / orbit_back are the orbit entry, proposal_refused / poison_gradient the conventions, release_ws the
+// body of a *_release.
+
+// The gradient workspace for groups of G matrices of mstride doubles each: what the factorisation needs, always; alpha and
+// its partial sums (`alpha`); the contraction's partial tiles and the three gradients (`contract`); with np > 0 the orbit
+// entry's buffers for c components and np orbital parameters, and the epoch lists of the fold.
+static int grad_ws_need(psoap_chunk* h, GradWs& w, int G, size_t mstride, bool alpha, bool contract, int c = 0, int np = 0)
 {
-    if (!contract)
-        hipLaunchKernelGGL(k_fill_sym<C>, dim3(ntiles, nb), dim3(256), 0, s, A, mstride, ld, N, P, dLwl, dGp, dSigma, 1);
-    else
-        hipLaunchKernelGGL(k_grad_contract<C>, dim3(ntiles, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)A, mstride,
-                           ld, N, Npad, P, dLwl, dGp, dAlpha, dPart);
+    const int N = h->N, Npad = h->Npad, ne = h->n_epochs;
+    HIP_TRY(w.A.need((size_t)G * mstride));
+    HIP_TRY(w.Wt.need((size_t)G * NB * NB));
+    HIP_TRY(w.R.need((size_t)G * Npad));
+    HIP_TRY(w.Acc.need((size_t)G * ACC_ROWS));
+    HIP_TRY(w.Lwl.need((size_t)G * 3 * N));
+    HIP_TRY(w.Gp.need((size_t)G * 6));
+    if (alpha) {
+        HIP_TRY(w.Alpha.need((size_t)G * Npad));
+        HIP_TRY(w.APart.need((size_t)G * ((Npad + 255) / 256) * Npad));
+    }
+    if (contract) {
+        HIP_TRY(w.Part.need((size_t)G * (h->P * (h->P + 1) / 2) * GRAD_TILE_DOUBLES));
+        HIP_TRY(w.GradGp.need((size_t)G * 6));
+        HIP_TRY(w.GradX.need((size_t)G * 3 * N));
+        HIP_TRY(w.GradMu.need(G));
+    }
+    if (np > 0) {
+        HIP_TRY(w.Porb.need((size_t)G * np));
+        HIP_TRY(w.Vel.need((size_t)G * c * ne));
+        HIP_TRY(w.Jac.need((size_t)G * c * ne * np));
+        HIP_TRY(w.Gv.need((size_t)G * c * ne));
+        HIP_TRY(w.GradOrb.need((size_t)G * np));
+        HIP_TRY(w.TooFast.need(G));
+    }
+    return 0;
+}
+
+// K (upper tiles) of the nb matrices whose grids and hyper-parameters are in w.Lwl and w.Gp, into w.A as the caller lays it out
+static void launch_grad_fill(const psoap_chunk* h, GradWs& w, hipStream_t s, int nb, int c, size_t mstride, int ld)
+{
+    with_components(c, [&](auto nc) {
+        hipLaunchKernelGGL(k_fill_sym<nc()>, dim3(h->P * (h->P + 1) / 2, nb), dim3(256), 0, s, w.A.p, mstride, ld, h->N, h->P,
+                           (const double*)w.Lwl.p, (const double*)w.Gp.p, (const double*)h->dSigma.p, 1);
+    });
+}
+
+// w.Alpha = W^T z for nb factored matrices (z: w.R, or what the caller made of it).  Launches only: inside the caller's bracket.
+static void launch_alpha(GradWs& w, hipStream_t s, int nb, size_t mstride, int ld, int Npad, int P, const double* z)
+{
+    const int nslab = (Npad + 255) / 256;
+    hipLaunchKernelGGL(k_grad_alpha_partial, dim3(P, nslab, nb), dim3(256), 0, s, (const double*)w.A.p, mstride, ld, Npad, z,
+                       w.APart.p, nslab);
+    hipLaunchKernelGGL(k_grad_alpha_finish, dim3((Npad + 255) / 256, nb), dim3(256), 0, s, (const double*)w.APart.p, nslab, Npad,
+                       w.Alpha.p);
+}
+
+// the block-row record of [K | ...] in the gradient workspace, `strip` tiles right of the diagonal tile
+static StagedRow grad_row(GradWs& w, size_t mstride, int ld, int Npad, int strip)
+{
+    return StagedRow{w.A.p, mstride, ld, w.R.p, Npad, w.Acc.p, w.Wt.p, (size_t)NB * NB, strip};
+}
+
+// The conventions of the likelihood (covariance.py:317; sample_parallel.py:186-187): proposal b has a negative hyper-parameter
+// or, with `fast` given, an orbit with |v| >= c  ->  lnL = -inf whatever the device computed
+static bool proposal_refused(const double* gp, int c, int b, const int* fast = nullptr)
+{
+    bool neg = fast && fast[b];
+    for (int k = 0; k < 2 * c; ++k) neg = neg || gp[(size_t)b * 2 * c + k] < 0.0;
+    return neg;
+}
+
+// ... and no gradient there: NaN into proposal b of grad_gp and of every optional output that was asked for
+static void poison_gradient(int b, int c, int N, int ne, int np, double* grad_gp, double* grad_lwl, double* grad_mu,
+                            double* grad_orb, double* grad_vel)
+{
+    for (int k = 0; k < 2 * c; ++k) grad_gp[(size_t)b * 2 * c + k] = NAN;
+    if (grad_lwl)
+        for (size_t k = 0; k < (size_t)c * N; ++k) grad_lwl[(size_t)b * c * N + k] = NAN;
+    if (grad_mu) grad_mu[b] = NAN;
+    if (grad_orb)
+        for (int k = 0; k < np; ++k) grad_orb[(size_t)b * np + k] = NAN;
+    if (grad_vel)
+        for (size_t k = 0; k < (size_t)c * ne; ++k) grad_vel[(size_t)b * c * ne + k] = NAN;
+}
+
+// The body of a *_release: the handle's first stream drained (the workspace may still be read there), then `drop`
+template <class F>
+static int release_ws(psoap_chunk* h, F&& drop)
+{
+    if (!h) FAIL("null handle");
+    DEVICE_SCOPE(h->device);
+    if (set_dev(h)) return 1;
+    HIP_TRY(hipStreamSynchronize(h->streams[0]));
+    drop();
+    return 0;
 }
 
 // The pixels of every epoch for k_epoch_fold: a counting sort of the handle's epoch index (stable: ascending pixels within an
@@ -2060,46 +2167,58 @@ static int grad_factor(psoap_chunk* h, GradWs& w, hipStream_t s, int nb, int c, 
 {
     const int N = h->N, Npad = h->Npad, P = h->P, ld = 2 * h->Npad;
     const size_t mstride = (size_t)Npad * ld;
-    const int ntiles = P * (P + 1) / 2;
-    const double tile_flops = 2.0 * NB * NB * (double)NB;
-    if (prof_begin(h, s, PSOAP_K_FILL, 0.0, (double)nb * 12.0 * N * (N + 1.0))) return 1;
-    with_components(c, [&](auto nc) {
-        launch_grad_fill_contract<nc()>(false, s, nb, ntiles, w.A, mstride, ld, N, Npad, P, w.Lwl, w.Gp, h->dSigma, nullptr, nullptr);
-    });
-    hipLaunchKernelGGL(k_grad_init, dim3(ntiles, nb), dim3(256), 0, s, w.A.p, mstride, ld, Npad, P);
-    HIP_TRY(hipGetLastError());
-    if (prof_end(h, s)) return 1;
-    if (prof_begin(h, s, PSOAP_K_MISC, 0.0, 0.0)) return 1;
-    hipLaunchKernelGGL(k_init_rhs, dim3((Npad + 255) / 256, nb), dim3(256), 0, s, w.R.p, Npad, N, h->dFl, mu_GP, w.Acc.p);
-    HIP_TRY(hipGetLastError());
-    if (prof_end(h, s)) return 1;
+    if (int rc = prof_launch(h, s, PSOAP_K_FILL, 0.0, (double)nb * 12.0 * N * (N + 1.0), [&] {
+            launch_grad_fill(h, w, s, nb, c, mstride, ld);
+            hipLaunchKernelGGL(k_grad_init, dim3(P * (P + 1) / 2, nb), dim3(256), 0, s, w.A.p, mstride, ld, Npad, P);
+        })) return rc;
+    if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
+            hipLaunchKernelGGL(k_init_rhs, dim3((Npad + 255) / 256, nb), dim3(256), 0, s, w.R.p, Npad, N, h->dFl, mu_GP, w.Acc.p);
+        })) return rc;
     // block row p: tile columns p .. P + p -- the rest of K's row and the appended tiles j <= p
     for (int p = 0; p < P; ++p) {
         const int k0 = p * NB;
-        if (p > 0) {
-            const double units = (double)p * (P - p) + 0.5 * p * (p + 1.0);
-            if (prof_begin(h, s, PSOAP_K_PANEL_UPDATE, tile_flops * units * nb, 0.0)) return 1;
+        const double units = (double)p * (P - p) + 0.5 * p * (p + 1.0);
+        auto update = [&] {
             hipLaunchKernelGGL(k_grad_panel_update, dim3(P + 1, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, w.A.p, mstride, ld, k0, P);
-            HIP_TRY(hipGetLastError());
-            if (prof_end(h, s)) return 1;
-        }
-        if (prof_begin(h, s, PSOAP_K_POTRF, 0.0, 0.0)) return 1;
-        hipLaunchKernelGGL(k_potrf_diag, dim3(nb), dim3(512), 0, s, w.A.p, mstride, ld, k0, w.Wt.p, w.R.p, Npad, w.Acc.p,
-                           (size_t)NB * NB);
-        HIP_TRY(hipGetLastError());
-        if (prof_end(h, s)) return 1;
-        if (prof_begin(h, s, PSOAP_K_TRSM, tile_flops * P * nb, 0.0)) return 1;
-        hipLaunchKernelGGL(k_trsm_strip, dim3(P, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, w.A.p, mstride, ld, k0,
-                           (const double*)w.Wt.p, w.R.p, Npad, (size_t)NB * NB);
-        HIP_TRY(hipGetLastError());
-        if (prof_end(h, s)) return 1;
+        };
+        if (int rc = staged_row(h, s, grad_row(w, mstride, ld, Npad, P), nb, k0, p > 0 ? &update : nullptr, TILE_FLOPS * units * nb))
+            return rc;
     }
     return 0;
 }
 
+// The orbit entry of a gradient call, front: the group's nb orbits (np parameters each) go up, k_orbit_jacobian makes their
+// velocities, Jacobian and |v| >= c flags, k_doppler_shift the grids w.Lwl from the handle's grid and dates.
+static int orbit_front(psoap_chunk* h, GradWs& w, hipStream_t s, int nb, int c, int model, int np, const double* p_orb)
+{
+    const int N = h->N, ne = h->n_epochs;
+    HIP_TRY(hipMemcpyAsync(w.Porb, p_orb, sizeof(double) * (size_t)nb * np, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(w.TooFast, 0, sizeof(int) * (size_t)nb, s));
+    hipLaunchKernelGGL(k_orbit_jacobian, dim3((ne + 63) / 64, nb), dim3(64), 0, s, model, nb, ne, (const double*)w.Porb.p,
+                       (const double*)h->dDates, w.Vel.p, w.Jac.p, w.TooFast.p);
+    hipLaunchKernelGGL(k_doppler_shift, dim3((N + 255) / 256, nb * c), dim3(256), 0, s, w.Lwl.p, h->dGrid, h->dEpoch,
+                       (const double*)w.Vel.p, N, ne, nb * c);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ... and back: after k_grad_finish the fold and the chain (orbit_grad_kernels.hpp) turn w.GradX into dlnL/dv and dlnL/dp_orb
+// on the device; the group's grad_orb, grad_vel (optional) and flags come down.
+static int orbit_back(psoap_chunk* h, GradWs& w, hipStream_t s, int nb, int c, int np, double* grad_orb, double* grad_vel, int* fast)
+{
+    const int N = h->N, ne = h->n_epochs, CE = c * ne;
+    hipLaunchKernelGGL(k_epoch_fold, dim3((CE + 3) / 4, nb), dim3(256), 0, s, (const double*)w.GradX.p, (const int*)w.EpStart.p,
+                       (const int*)w.EpPix.p, c, N, ne, w.Gv.p);
+    hipLaunchKernelGGL(k_orbit_chain, dim3(nb), dim3(256), 0, s, (const double*)w.Gv.p, (const double*)w.Jac.p, CE, np, w.GradOrb.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(grad_orb, w.GradOrb, sizeof(double) * (size_t)nb * np, hipMemcpyDeviceToHost, s));
+    if (grad_vel) HIP_TRY(hipMemcpyAsync(grad_vel, w.Gv, sizeof(double) * (size_t)nb * CE, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(fast, w.TooFast, sizeof(int) * (size_t)nb, hipMemcpyDeviceToHost, s));
+    return 0;
+}
+
 // The ln-wavelengths of a gradient call come from the host (lwl: psoap_chunk_lnlike_grad) or, with lwl == nullptr, from
-// the orbits p_orb of `model`: per group k_orbit_jacobian and k_doppler_shift make them from the handle's grid and dates, and
-// after k_grad_finish the fold and the chain (orbit_grad_kernels.hpp) turn GradX into grad_vel and grad_orb on the device.
+// the orbits p_orb of `model` (orbit_front, orbit_back).
 static int grad_run(psoap_chunk* h, int B, int c, const double* lwl, int model, const double* p_orb,
                     const double* gp, double mu_GP, double* lnp, double* grad_gp, double* grad_lwl, double* grad_mu,
                     double* grad_orb, double* grad_vel)
@@ -2110,110 +2229,58 @@ static int grad_run(psoap_chunk* h, int B, int c, const double* lwl, int model, 
     const int N = h->N, Npad = h->Npad, P = h->P, ld = 2 * h->Npad;
     const size_t mstride = (size_t)Npad * ld;
     const int G = grad_group_size(B, Npad);
-    const int ntiles = P * (P + 1) / 2, nslab = (Npad + 255) / 256;
+    const int ne = h->n_epochs, np = orbits ? orbit_n_params(model) : 0;
     if (!h->gws) h->gws.reset(new GradWs());
     GradWs& w = *h->gws;
-    HIP_TRY(w.A.need((size_t)G * mstride));
-    HIP_TRY(w.Wt.need((size_t)G * NB * NB));
-    HIP_TRY(w.R.need((size_t)G * Npad));
-    HIP_TRY(w.Acc.need((size_t)G * ACC_ROWS));
-    HIP_TRY(w.Lwl.need((size_t)G * 3 * N));
-    HIP_TRY(w.Gp.need((size_t)G * 6));
-    HIP_TRY(w.Alpha.need((size_t)G * Npad));
-    HIP_TRY(w.APart.need((size_t)G * nslab * Npad));
-    HIP_TRY(w.Part.need((size_t)G * ntiles * GRAD_TILE_DOUBLES));
+    if (int rc = grad_ws_need(h, w, G, mstride, true, true, c, np)) return rc;
     HIP_TRY(w.Out.need(G));
-    HIP_TRY(w.GradGp.need((size_t)G * 6));
-    HIP_TRY(w.GradX.need((size_t)G * 3 * N));
-    HIP_TRY(w.GradMu.need(G));
     hipStream_t s = h->streams[0];
-    const int ne = h->n_epochs, np = orbits ? orbit_n_params(model) : 0;
     std::vector<int> fast(orbits ? (size_t)B : 0, 0);
-    if (orbits) {
-        HIP_TRY(w.Porb.need((size_t)G * np));
-        HIP_TRY(w.Vel.need((size_t)G * c * ne));
-        HIP_TRY(w.Jac.need((size_t)G * c * ne * np));
-        HIP_TRY(w.Gv.need((size_t)G * c * ne));
-        HIP_TRY(w.GradOrb.need((size_t)G * np));
-        HIP_TRY(w.TooFast.need(G));
+    if (orbits)
         if (int rc = grad_epoch_lists(h, w, s)) return rc;
-    }
     h->recs.clear();
-    const double tile_flops = 2.0 * NB * NB * (double)NB;
     for (int b0 = 0; b0 < B; b0 += G) {
         const int nb = (B - b0 < G) ? B - b0 : G;
-        if (!orbits) {
+        if (!orbits)
             HIP_TRY(hipMemcpyAsync(w.Lwl, lwl + (size_t)b0 * c * N, sizeof(double) * (size_t)nb * c * N, hipMemcpyHostToDevice, s));
-        } else {
-            HIP_TRY(hipMemcpyAsync(w.Porb, p_orb + (size_t)b0 * np, sizeof(double) * (size_t)nb * np, hipMemcpyHostToDevice, s));
-            HIP_TRY(hipMemsetAsync(w.TooFast, 0, sizeof(int) * (size_t)nb, s));
-            hipLaunchKernelGGL(k_orbit_jacobian, dim3((ne + 63) / 64, nb), dim3(64), 0, s, model, nb, ne, (const double*)w.Porb.p,
-                               (const double*)h->dDates, w.Vel.p, w.Jac.p, w.TooFast.p);
-            hipLaunchKernelGGL(k_doppler_shift, dim3((N + 255) / 256, nb * c), dim3(256), 0, s, w.Lwl.p, h->dGrid, h->dEpoch,
-                               (const double*)w.Vel.p, N, ne, nb * c);
-            HIP_TRY(hipGetLastError());
-        }
+        else if (int rc = orbit_front(h, w, s, nb, c, model, np, p_orb + (size_t)b0 * np))
+            return rc;
         HIP_TRY(hipMemcpyAsync(w.Gp, gp + (size_t)b0 * 2 * c, sizeof(double) * (size_t)nb * 2 * c, hipMemcpyHostToDevice, s));
         if (int rc = grad_factor(h, w, s, nb, c, mu_GP)) return rc;
-        if (prof_begin(h, s, PSOAP_K_MISC, 0.0, 0.0)) return 1;
-        hipLaunchKernelGGL(k_finalize, dim3((nb + 63) / 64), dim3(64), 0, s, (const MatAcc*)w.Acc.p, w.Out.p, nb, (const int*)nullptr, P);
-        hipLaunchKernelGGL(k_grad_alpha_partial, dim3(P, nslab, nb), dim3(256), 0, s, (const double*)w.A.p, mstride, ld, Npad,
-                           (const double*)w.R.p, w.APart.p, nslab);
-        hipLaunchKernelGGL(k_grad_alpha_finish, dim3((Npad + 255) / 256, nb), dim3(256), 0, s, (const double*)w.APart.p, nslab, Npad,
-                           w.Alpha.p);
-        HIP_TRY(hipGetLastError());
-        if (prof_end(h, s)) return 1;
+        if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
+                hipLaunchKernelGGL(k_finalize, dim3((nb + 63) / 64), dim3(64), 0, s, (const MatAcc*)w.Acc.p, w.Out.p, nb,
+                                   (const int*)nullptr, P);
+                launch_alpha(w, s, nb, mstride, ld, Npad, P, w.R.p);
+            })) return rc;
         double cunits = 0.0;
         for (int tj = 0; tj < P; ++tj) cunits += (double)(tj + 1) * (P - tj);
-        if (prof_begin(h, s, PSOAP_K_GRAD, tile_flops * cunits * nb, 0.0)) return 1;
-        with_components(c, [&](auto nc) {
-            launch_grad_fill_contract<nc()>(true, s, nb, ntiles, w.A, mstride, ld, N, Npad, P, w.Lwl, w.Gp, nullptr, w.Alpha, w.Part);
-        });
-        HIP_TRY(hipGetLastError());
-        if (prof_end(h, s)) return 1;
-        if (prof_begin(h, s, PSOAP_K_MISC, 0.0, 0.0)) return 1;
-        hipLaunchKernelGGL(k_grad_finish, dim3(P + 1, nb), dim3(128), 0, s, (const double*)w.Part.p, (const double*)w.Alpha.p,
-                           (const double*)w.Gp.p, c, N, Npad, P, w.GradGp.p, w.GradX.p, w.GradMu.p);
-        HIP_TRY(hipGetLastError());
-        if (prof_end(h, s)) return 1;
+        if (int rc = prof_launch(h, s, PSOAP_K_GRAD, TILE_FLOPS * cunits * nb, 0.0, [&] {
+                with_components(c, [&](auto nc) {
+                    hipLaunchKernelGGL(k_grad_contract<nc()>, dim3(P * (P + 1) / 2, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s,
+                                       (const double*)w.A.p, mstride, ld, N, Npad, P, (const double*)w.Lwl.p, (const double*)w.Gp.p,
+                                       (const double*)w.Alpha.p, w.Part.p);
+                });
+            })) return rc;
+        if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
+                hipLaunchKernelGGL(k_grad_finish, dim3(P + 1, nb), dim3(128), 0, s, (const double*)w.Part.p, (const double*)w.Alpha.p,
+                                   (const double*)w.Gp.p, c, N, Npad, P, w.GradGp.p, w.GradX.p, w.GradMu.p);
+            })) return rc;
         HIP_TRY(hipMemcpyAsync(lnp + b0, w.Out, sizeof(double) * nb, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipMemcpyAsync(grad_gp + (size_t)b0 * 2 * c, w.GradGp, sizeof(double) * (size_t)nb * 2 * c, hipMemcpyDeviceToHost, s));
         if (grad_lwl)
             HIP_TRY(hipMemcpyAsync(grad_lwl + (size_t)b0 * c * N, w.GradX, sizeof(double) * (size_t)nb * c * N, hipMemcpyDeviceToHost, s));
         if (grad_mu) HIP_TRY(hipMemcpyAsync(grad_mu + b0, w.GradMu, sizeof(double) * nb, hipMemcpyDeviceToHost, s));
-        if (orbits) {
-            const int CE = c * ne;
-            hipLaunchKernelGGL(k_epoch_fold, dim3((CE + 3) / 4, nb), dim3(256), 0, s, (const double*)w.GradX.p, (const int*)w.EpStart.p,
-                               (const int*)w.EpPix.p, c, N, ne, w.Gv.p);
-            hipLaunchKernelGGL(k_orbit_chain, dim3(nb), dim3(256), 0, s, (const double*)w.Gv.p, (const double*)w.Jac.p, CE, np,
-                               w.GradOrb.p);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(grad_orb + (size_t)b0 * np, w.GradOrb, sizeof(double) * (size_t)nb * np, hipMemcpyDeviceToHost, s));
-            if (grad_vel)
-                HIP_TRY(hipMemcpyAsync(grad_vel + (size_t)b0 * CE, w.Gv, sizeof(double) * (size_t)nb * CE, hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipMemcpyAsync(fast.data() + b0, w.TooFast, sizeof(int) * (size_t)nb, hipMemcpyDeviceToHost, s));
-        }
+        if (orbits)
+            if (int rc = orbit_back(h, w, s, nb, c, np, grad_orb + (size_t)b0 * np, grad_vel ? grad_vel + (size_t)b0 * c * ne : nullptr,
+                                    fast.data() + b0))
+                return rc;
         HIP_TRY(hipStreamSynchronize(s));       // the next group reuses the workspace and the caller's arrays are pageable
     }
     if (collect_timings(h)) return 1;
-    // the conventions of the likelihood: a negative hyper-parameter or a matrix that is not positive definite -> -inf,
-    // and no gradient there
+    // a refused proposal or a matrix that is not positive definite -> -inf, and no gradient there
     for (int b = 0; b < B; ++b) {
-        bool neg = false;
-        for (int k = 0; k < 2 * c; ++k) neg = neg || gp[(size_t)b * 2 * c + k] < 0.0;
-        if (orbits && fast[b]) neg = true;          // sample_parallel.py:186-187: |v| >= c  ->  -inf
-        if (neg) lnp[b] = -INFINITY;
-        if (lnp[b] == -INFINITY) {
-            for (int k = 0; k < 2 * c; ++k) grad_gp[(size_t)b * 2 * c + k] = NAN;
-            if (grad_lwl)
-                for (size_t k = 0; k < (size_t)c * N; ++k) grad_lwl[(size_t)b * c * N + k] = NAN;
-            if (grad_mu) grad_mu[b] = NAN;
-            if (orbits) {
-                for (int k = 0; k < np; ++k) grad_orb[(size_t)b * np + k] = NAN;
-                if (grad_vel)
-                    for (size_t k = 0; k < (size_t)c * ne; ++k) grad_vel[(size_t)b * c * ne + k] = NAN;
-            }
-        }
+        if (proposal_refused(gp, c, b, orbits ? fast.data() : nullptr)) lnp[b] = -INFINITY;
+        if (lnp[b] == -INFINITY) poison_gradient(b, c, N, ne, np, grad_gp, grad_lwl, grad_mu, grad_orb, grad_vel);
     }
     return 0;
 }
@@ -2267,12 +2334,7 @@ extern "C" int psoap_orbit_velocity_jacobian(int device, int model, int B, const
 
 extern "C" int psoap_chunk_grad_release(psoap_chunk* h)
 {
-    if (!h) FAIL("null handle");
-    DEVICE_SCOPE(h->device);
-    if (set_dev(h)) return 1;
-    HIP_TRY(hipStreamSynchronize(h->streams[0]));
-    h->gws.reset();
-    return 0;
+    return release_ws(h, [&] { h->gws.reset(); });
 }
 
 // ---- Fisher information of the likelihood (fisher_kernels.hpp) --------------------------------------
@@ -2295,12 +2357,7 @@ extern "C" int psoap_chunk_fisher(psoap_chunk* h, int c, const double* lwl, cons
     if (!h->fws) h->fws.reset(new FisherWs());
     GradWs& w = *h->gws;
     FisherWs& f = *h->fws;
-    HIP_TRY(w.A.need(mstride));
-    HIP_TRY(w.Wt.need((size_t)NB * NB));
-    HIP_TRY(w.R.need(Npad));
-    HIP_TRY(w.Acc.need(ACC_ROWS));
-    HIP_TRY(w.Lwl.need((size_t)3 * N));
-    HIP_TRY(w.Gp.need(6));
+    if (int rc = grad_ws_need(h, w, 1, mstride, false, false)) return rc;
     HIP_TRY(f.Kinv.need(sq));
     HIP_TRY(f.Kt.need(sq));
     HIP_TRY(f.Z.need(sq));
@@ -2321,49 +2378,45 @@ extern "C" int psoap_chunk_fisher(psoap_chunk* h, int c, const double* lwl, cons
     else HIP_TRY(hipMemsetAsync(f.TanX, 0, sizeof(double) * (size_t)T * CN, s));
     HIP_TRY(hipMemcpyAsync(f.TanGp, tan_gp, sizeof(double) * (size_t)T * 2 * c, hipMemcpyHostToDevice, s));
     if (int rc = grad_factor(h, w, s, 1, c, 0.0)) return rc;      // (F does not depend on the data: any mu_GP)
-    const double tile_flops = 2.0 * NB * NB * (double)NB;
     double kunits = 0.0;
     for (int tj = 0; tj < P; ++tj) kunits += (double)(tj + 1) * (P - tj);
-    if (prof_begin(h, s, PSOAP_K_GRAD, tile_flops * kunits, 0.0)) return 1;
-    hipLaunchKernelGGL(k_fisher_kinv, dim3(ntiles), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)w.A.p, ld, Npad, P, f.Kinv.p);
-    HIP_TRY(hipGetLastError());
-    if (prof_end(h, s)) return 1;
-    if (prof_begin(h, s, PSOAP_K_MISC, 0.0, 0.0)) return 1;
-    hipLaunchKernelGGL(k_acc_total, dim3(1), dim3(1), 0, s, (const MatAcc*)w.Acc.p, P, f.Info.p);
-    hipLaunchKernelGGL(k_fisher_w1, dim3(N), dim3(256), 0, s, (const double*)w.A.p, ld, Npad, N, f.Y.p);
-    hipLaunchKernelGGL(k_fisher_mu, dim3(1), dim3(256), 0, s, (const double*)f.Y.p, N, f.Mu.p);
-    HIP_TRY(hipGetLastError());
-    if (prof_end(h, s)) return 1;
+    if (int rc = prof_launch(h, s, PSOAP_K_GRAD, TILE_FLOPS * kunits, 0.0, [&] {
+            hipLaunchKernelGGL(k_fisher_kinv, dim3(ntiles), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)w.A.p, ld, Npad, P,
+                               f.Kinv.p);
+        })) return rc;
+    if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
+            hipLaunchKernelGGL(k_acc_total, dim3(1), dim3(1), 0, s, (const MatAcc*)w.Acc.p, P, f.Info.p);
+            hipLaunchKernelGGL(k_fisher_w1, dim3(N), dim3(256), 0, s, (const double*)w.A.p, ld, Npad, N, f.Y.p);
+            hipLaunchKernelGGL(k_fisher_mu, dim3(1), dim3(256), 0, s, (const double*)f.Y.p, N, f.Mu.p);
+        })) return rc;
     for (int t = 0; t < T; ++t) {
-        if (prof_begin(h, s, PSOAP_K_FILL, 0.0, 8.0 * (double)sq)) return 1;
-        with_components(c, [&](auto nc) {
-            hipLaunchKernelGGL(k_fisher_tangent_fill<nc()>, dim3(P * P), dim3(256), 0, s, f.Kt.p, Npad, N, P, (const double*)w.Lwl.p,
-                               (const double*)w.Gp.p, (const double*)(f.TanX.p + (size_t)t * CN),
-                               (const double*)(f.TanGp.p + (size_t)t * 2 * c));
-        });
-        HIP_TRY(hipGetLastError());
-        if (prof_end(h, s)) return 1;
-        if (prof_begin(h, s, PSOAP_K_GRAD, tile_flops * P * ((double)P * P + 2.0 * ntiles), 0.0)) return 1;
-        hipLaunchKernelGGL(k_fisher_gemm, dim3(P * P), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)f.Kt.p,
-                           (const double*)f.Kinv.p, Npad, P, f.Z.p);
-        with_components(c, [&](auto nc) {
-            hipLaunchKernelGGL(k_fisher_contract<nc()>, dim3(ntiles), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)f.Kinv.p,
-                               (const double*)f.Z.p, N, Npad, P, (const double*)w.Lwl.p, (const double*)w.Gp.p, f.Part.p);
-        });
-        HIP_TRY(hipGetLastError());
-        if (prof_end(h, s)) return 1;
+        if (int rc = prof_launch(h, s, PSOAP_K_FILL, 0.0, 8.0 * (double)sq, [&] {
+                with_components(c, [&](auto nc) {
+                    hipLaunchKernelGGL(k_fisher_tangent_fill<nc()>, dim3(P * P), dim3(256), 0, s, f.Kt.p, Npad, N, P,
+                                       (const double*)w.Lwl.p, (const double*)w.Gp.p, (const double*)(f.TanX.p + (size_t)t * CN),
+                                       (const double*)(f.TanGp.p + (size_t)t * 2 * c));
+                });
+            })) return rc;
+        if (int rc = prof_launch(h, s, PSOAP_K_GRAD, TILE_FLOPS * P * ((double)P * P + 2.0 * ntiles), 0.0, [&] {
+                hipLaunchKernelGGL(k_fisher_gemm, dim3(P * P), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)f.Kt.p,
+                                   (const double*)f.Kinv.p, Npad, P, f.Z.p);
+                with_components(c, [&](auto nc) {
+                    hipLaunchKernelGGL(k_fisher_contract<nc()>, dim3(ntiles), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s,
+                                       (const double*)f.Kinv.p, (const double*)f.Z.p, N, Npad, P, (const double*)w.Lwl.p,
+                                       (const double*)w.Gp.p, f.Part.p);
+                });
+            })) return rc;
         // the gradient's finishing sums as they are: its alpha is W 1 here, and its sum over alpha goes nowhere (Mu[1])
-        if (prof_begin(h, s, PSOAP_K_MISC, 0.0, 0.0)) return 1;
-        hipLaunchKernelGGL(k_grad_finish, dim3(P + 1, 1), dim3(128), 0, s, (const double*)f.Part.p, (const double*)f.Y.p,
-                           (const double*)w.Gp.p, c, N, Npad, P, f.GGp.p + (size_t)t * 2 * c, f.GX.p + (size_t)t * CN, f.Mu.p + 1);
-        HIP_TRY(hipGetLastError());
-        if (prof_end(h, s)) return 1;
+        if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
+                hipLaunchKernelGGL(k_grad_finish, dim3(P + 1, 1), dim3(128), 0, s, (const double*)f.Part.p, (const double*)f.Y.p,
+                                   (const double*)w.Gp.p, c, N, Npad, P, f.GGp.p + (size_t)t * 2 * c, f.GX.p + (size_t)t * CN,
+                                   f.Mu.p + 1);
+            })) return rc;
     }
-    if (prof_begin(h, s, PSOAP_K_MISC, 0.0, 0.0)) return 1;
-    hipLaunchKernelGGL(k_fisher_dot, dim3(T, T), dim3(256), 0, s, (const double*)f.TanX.p, (const double*)f.TanGp.p,
-                       (const double*)f.GX.p, (const double*)f.GGp.p, c, N, T, f.F.p);
-    HIP_TRY(hipGetLastError());
-    if (prof_end(h, s)) return 1;
+    if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
+            hipLaunchKernelGGL(k_fisher_dot, dim3(T, T), dim3(256), 0, s, (const double*)f.TanX.p, (const double*)f.TanGp.p,
+                               (const double*)f.GX.p, (const double*)f.GGp.p, c, N, T, f.F.p);
+        })) return rc;
     MatAcc info;
     HIP_TRY(hipMemcpyAsync(fisher, f.F, sizeof(double) * (size_t)T * T, hipMemcpyDeviceToHost, s));
     if (fisher_mu) HIP_TRY(hipMemcpyAsync(fisher_mu, f.Mu, sizeof(double), hipMemcpyDeviceToHost, s));
@@ -2371,9 +2424,7 @@ extern "C" int psoap_chunk_fisher(psoap_chunk* h, int c, const double* lwl, cons
     HIP_TRY(hipStreamSynchronize(s));
     if (collect_timings(h)) return 1;
     // the conventions of the likelihood: a negative hyper-parameter or a matrix that is not positive definite -> no information
-    bool bad = info.info != 0.0;
-    for (int k = 0; k < 2 * c; ++k) bad = bad || gp[k] < 0.0;
-    if (bad) {
+    if (info.info != 0.0 || proposal_refused(gp, c, 0)) {
         for (size_t k = 0; k < (size_t)T * T; ++k) fisher[k] = NAN;
         if (fisher_mu) *fisher_mu = NAN;
     }
@@ -2382,12 +2433,7 @@ extern "C" int psoap_chunk_fisher(psoap_chunk* h, int c, const double* lwl, cons
 
 extern "C" int psoap_chunk_fisher_release(psoap_chunk* h)
 {
-    if (!h) FAIL("null handle");
-    DEVICE_SCOPE(h->device);
-    if (set_dev(h)) return 1;
-    HIP_TRY(hipStreamSynchronize(h->streams[0]));
-    h->fws.reset();
-    return 0;
+    return release_ws(h, [&] { h->fws.reset(); });
 }
 
 // ---- leave-one-out cross-validation of the likelihood (loo_kernels.hpp) ------------------------------
@@ -2411,19 +2457,11 @@ extern "C" int psoap_chunk_loo(psoap_chunk* h, int c, const double* lwl, const d
     DEVICE_SCOPE(h->device);
     if (int rc = enter_device(h->device)) return rc;
     const size_t mstride = (size_t)Npad * ld, CN = (size_t)c * N;
-    const int nslab = (Npad + 255) / 256;
     if (!h->gws) h->gws.reset(new GradWs());
     if (!h->lws) h->lws.reset(new LooWs());
     GradWs& w = *h->gws;
     LooWs& l = *h->lws;
-    HIP_TRY(w.A.need(mstride));
-    HIP_TRY(w.Wt.need((size_t)NB * NB));
-    HIP_TRY(w.R.need(Npad));
-    HIP_TRY(w.Acc.need(ACC_ROWS));
-    HIP_TRY(w.Lwl.need((size_t)3 * N));
-    HIP_TRY(w.Gp.need(6));
-    HIP_TRY(w.Alpha.need(Npad));
-    HIP_TRY(w.APart.need((size_t)nslab * Npad));
+    if (int rc = grad_ws_need(h, w, 1, mstride, true, false)) return rc;
     HIP_TRY(w.Out.need(1));
     HIP_TRY(l.Blk.need((size_t)lay.block_doubles));
     HIP_TRY(l.Rhs.need((size_t)lay.rhs_doubles));
@@ -2453,16 +2491,12 @@ extern "C" int psoap_chunk_loo(psoap_chunk* h, int c, const double* lwl, const d
     if (int rc = grad_factor(h, w, s, 1, c, mu_GP)) return rc;
     if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
             hipLaunchKernelGGL(k_finalize, dim3(1), dim3(64), 0, s, (const MatAcc*)w.Acc.p, w.Out.p, 1, (const int*)nullptr, P);
-            hipLaunchKernelGGL(k_grad_alpha_partial, dim3(P, nslab, 1), dim3(256), 0, s, (const double*)w.A.p, mstride, ld, Npad,
-                               (const double*)w.R.p, w.APart.p, nslab);
-            hipLaunchKernelGGL(k_grad_alpha_finish, dim3((Npad + 255) / 256, 1), dim3(256), 0, s, (const double*)w.APart.p, nslab,
-                               Npad, w.Alpha.p);
+            launch_alpha(w, s, 1, mstride, ld, Npad, P, w.R.p);
             hipLaunchKernelGGL(k_loo_pad, dim3(nblk), dim3(128), 0, s, (const LooBlock*)l.Blocks.p, l.Blk.p);
         })) return rc;
-    const double tile_flops = 2.0 * NB * NB * (double)NB;
     double bunits = 0.0;      // executed 128^3 products of the band: a diagonal tile issues three quarters of its MFMAs
     for (const LooTile& t : lay.tiles) bunits += (t.ti == t.tj ? 0.75 : 1.0) * (P - t.tj);
-    if (int rc = prof_launch(h, s, PSOAP_K_GRAD, tile_flops * bunits, 0.0, [&] {
+    if (int rc = prof_launch(h, s, PSOAP_K_GRAD, TILE_FLOPS * bunits, 0.0, [&] {
             hipLaunchKernelGGL(k_loo_band, dim3(ntile), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)w.A.p, ld, N, Npad,
                                (const LooTile*)l.Tiles.p, (const int*)l.PixBlock.p, (const LooBlock*)l.Blocks.p, l.Blk.p);
         })) return rc;
@@ -2476,24 +2510,14 @@ extern "C" int psoap_chunk_loo(psoap_chunk* h, int c, const double* lwl, const d
             const LooBlock& b0 = lay.blocks[(size_t)g.first];
             const int S = g.side, Pb = S / NB, nb = g.count;
             const size_t bstride = (size_t)S * S, wstride = (size_t)Pb * NB * NB;
-            double* Kg = l.Blk.p + b0.offset;
-            double* Rg = l.Rhs.p + b0.rhs;
-            MatAcc* Ag = l.Acc.p + (size_t)g.first * ACC_ROWS;
             for (int p = 0; p < Pb; ++p) {
                 const int k0 = p * NB, nt = Pb - p;
-                double* Wg = l.Wt.p + b0.wt + (size_t)p * NB * NB;
-                if (p > 0)
-                    if (int rc = prof_launch(h, s, PSOAP_K_PANEL_UPDATE, 2.0 * NB * NB * (double)k0 * nt * nb, 0.0, [&] {
-                            hipLaunchKernelGGL(k_panel_update, dim3(nt, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, Kg, bstride, S, k0);
-                        })) return rc;
-                if (int rc = prof_launch(h, s, PSOAP_K_POTRF, 0.0, 0.0, [&] {
-                        hipLaunchKernelGGL(k_potrf_diag, dim3(nb), dim3(512), 0, s, Kg, bstride, S, k0, Wg, Rg, S, Ag, wstride);
-                    })) return rc;
-                if (nt > 1)
-                    if (int rc = prof_launch(h, s, PSOAP_K_TRSM, tile_flops * (nt - 1) * nb, 0.0, [&] {
-                            hipLaunchKernelGGL(k_trsm_strip, dim3(nt - 1, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, Kg, bstride, S, k0,
-                                               (const double*)Wg, Rg, S, wstride);
-                        })) return rc;
+                const StagedRow row{l.Blk.p + b0.offset, bstride, S, l.Rhs.p + b0.rhs, S, l.Acc.p + (size_t)g.first * ACC_ROWS,
+                                    l.Wt.p + b0.wt + (size_t)p * NB * NB, wstride, nt - 1};
+                auto update = [&] {
+                    hipLaunchKernelGGL(k_panel_update, dim3(nt, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, row.A, bstride, S, k0);
+                };
+                if (int rc = staged_row(h, s, row, nb, k0, p > 0 ? &update : nullptr, TILE_FLOPS * p * nt * nb)) return rc;
             }
         }
     if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
@@ -2516,9 +2540,7 @@ extern "C" int psoap_chunk_loo(psoap_chunk* h, int c, const double* lwl, const d
     if (collect_timings(h)) return 1;
     // the conventions of the likelihood: a negative hyper-parameter or a matrix that is not positive definite -> -inf, and
     // nothing else to say about it
-    bool neg = false;
-    for (int k = 0; k < 2 * c; ++k) neg = neg || gp[k] < 0.0;
-    if (neg) value = -INFINITY;
+    if (proposal_refused(gp, c, 0)) value = -INFINITY;
     if (lnp) *lnp = value;
     if (value == -INFINITY) {
         if (loo_logp) *loo_logp = NAN;
@@ -2534,12 +2556,7 @@ extern "C" int psoap_chunk_loo(psoap_chunk* h, int c, const double* lwl, const d
 
 extern "C" int psoap_chunk_loo_release(psoap_chunk* h)
 {
-    if (!h) FAIL("null handle");
-    DEVICE_SCOPE(h->device);
-    if (set_dev(h)) return 1;
-    HIP_TRY(hipStreamSynchronize(h->streams[0]));
-    h->lws.reset();
-    return 0;
+    return release_ws(h, [&] { h->lws.reset(); });
 }
 
 // ---- likelihood with a per-epoch continuum polynomial integrated out (marg_kernels.hpp) ------------------
@@ -2628,18 +2645,13 @@ extern "C" int psoap_chunk_lnlike_marg(psoap_chunk* h, int B, int c, const doubl
     const int S = NB * Q, ld = Npad + S, ldm = 2 * S, ldh = S;
     const size_t mstride = (size_t)Npad * ld, m_stride = (size_t)S * ldm, wstride = (size_t)Q * NB * NB;
     const int G = marg_group_size(B, Npad, Q);
-    const int ntiles = P * (P + 1) / 2, nslab = (Npad + 255) / 256, ngram = Q * (Q + 1) / 2;
+    const int nslab = (Npad + 255) / 256, ngram = Q * (Q + 1) / 2;
     const bool want_cov = beta_cov != nullptr, want_sol = beta != nullptr || fl_cor != nullptr;
     if (!h->gws) h->gws.reset(new GradWs());
     if (!h->mws) h->mws.reset(new MargWs());
     GradWs& w = *h->gws;
     MargWs& m = *h->mws;
-    HIP_TRY(w.A.need((size_t)G * mstride));
-    HIP_TRY(w.Wt.need((size_t)G * NB * NB));
-    HIP_TRY(w.R.need((size_t)G * Npad));
-    HIP_TRY(w.Acc.need((size_t)G * ACC_ROWS));
-    HIP_TRY(w.Lwl.need((size_t)G * 3 * N));
-    HIP_TRY(w.Gp.need((size_t)G * 6));
+    if (int rc = grad_ws_need(h, w, G, mstride, false, false)) return rc;
     HIP_TRY(m.M.need((size_t)G * m_stride));
     HIP_TRY(m.WtM.need((size_t)G * wstride));
     HIP_TRY(m.Rhs.need((size_t)G * S));
@@ -2657,17 +2669,13 @@ extern "C" int psoap_chunk_lnlike_marg(psoap_chunk* h, int B, int c, const doubl
     if (int rc = marg_basis(h, m, s)) return rc;
     const int* tab = m.Tab.p;
     h->recs.clear();
-    const double tile_flops = 2.0 * NB * NB * (double)NB;
     std::vector<double> out((size_t)B * 5);
     for (int b0 = 0; b0 < B; b0 += G) {
         const int nb = (B - b0 < G) ? B - b0 : G;
         HIP_TRY(hipMemcpyAsync(w.Lwl, lwl + (size_t)b0 * c * N, sizeof(double) * (size_t)nb * c * N, hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemcpyAsync(w.Gp, gp + (size_t)b0 * 2 * c, sizeof(double) * (size_t)nb * 2 * c, hipMemcpyHostToDevice, s));
         if (int rc = prof_launch(h, s, PSOAP_K_FILL, 0.0, (double)nb * 12.0 * N * (N + 1.0), [&] {
-                with_components(c, [&](auto nc) {
-                    launch_grad_fill_contract<nc()>(false, s, nb, ntiles, w.A, mstride, ld, N, Npad, P, w.Lwl, w.Gp, h->dSigma, nullptr,
-                                                    nullptr);
-                });
+                launch_grad_fill(h, w, s, nb, c, mstride, ld);
                 hipLaunchKernelGGL(k_marg_load, dim3(Q * P, nb), dim3(256), 0, s, w.A.p, mstride, ld, Npad, P, (const double*)m.Ht.p,
                                    ldh, tab);
             })) return rc;
@@ -2677,21 +2685,13 @@ extern "C" int psoap_chunk_lnlike_marg(psoap_chunk* h, int B, int c, const doubl
         // block row p: the rest of K's row and the appended slots whose first non-zero block row is <= p
         for (int p = 0; p < P; ++p) {
             const int k0 = p * NB, act = pl.active[(size_t)p];
-            if (p > 0)
-                if (int rc = prof_launch(h, s, PSOAP_K_PANEL_UPDATE, tile_flops * p * (P - p + act) * nb, 0.0, [&] {
-                        hipLaunchKernelGGL(k_marg_panel_update, dim3(P - p + act, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, w.A.p,
-                                           mstride, ld, k0, P, tab);
-                    })) return rc;
-            if (int rc = prof_launch(h, s, PSOAP_K_POTRF, 0.0, 0.0, [&] {
-                    hipLaunchKernelGGL(k_potrf_diag, dim3(nb), dim3(512), 0, s, w.A.p, mstride, ld, k0, w.Wt.p, w.R.p, Npad, w.Acc.p,
-                                       (size_t)NB * NB);
-                })) return rc;
-            const int nt = P - p - 1 + act;
-            if (nt > 0)
-                if (int rc = prof_launch(h, s, PSOAP_K_TRSM, tile_flops * nt * nb, 0.0, [&] {
-                        hipLaunchKernelGGL(k_trsm_strip, dim3(nt, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, w.A.p, mstride, ld, k0,
-                                           (const double*)w.Wt.p, w.R.p, Npad, (size_t)NB * NB);
-                    })) return rc;
+            auto update = [&] {
+                hipLaunchKernelGGL(k_marg_panel_update, dim3(P - p + act, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, w.A.p, mstride, ld,
+                                   k0, P, tab);
+            };
+            if (int rc = staged_row(h, s, grad_row(w, mstride, ld, Npad, P - p - 1 + act), nb, k0, p > 0 ? &update : nullptr,
+                                    TILE_FLOPS * p * (P - p + act) * nb))
+                return rc;
         }
         if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
                 hipLaunchKernelGGL(k_marg_rhs_partial, dim3(Q, nslab, nb), dim3(256), 0, s, (const double*)w.A.p, mstride, ld, Npad, Q,
@@ -2701,7 +2701,7 @@ extern "C" int psoap_chunk_lnlike_marg(psoap_chunk* h, int B, int c, const doubl
             })) return rc;
         double gunits = 0.0;
         for (const MargTile& t : pl.tiles) gunits += (t.ti == t.tj ? 0.75 : 1.0) * (Npad - t.k0) / NB;
-        if (int rc = prof_launch(h, s, PSOAP_K_GRAD, tile_flops * gunits * nb, 0.0, [&] {
+        if (int rc = prof_launch(h, s, PSOAP_K_GRAD, TILE_FLOPS * gunits * nb, 0.0, [&] {
                 hipLaunchKernelGGL(k_marg_gram, dim3(ngram, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)w.A.p, mstride, ld,
                                    Npad, (const MargTile*)m.Tiles.p, m.M.p, m_stride, ldm);
                 if (want_cov) hipLaunchKernelGGL(k_grad_init, dim3(ngram, nb), dim3(256), 0, s, m.M.p, m_stride, ldm, S, Q);
@@ -2709,25 +2709,17 @@ extern "C" int psoap_chunk_lnlike_marg(psoap_chunk* h, int B, int c, const doubl
         // M = U_M^T U_M with bt alongside; with the covariance asked for, [M | I] as the gradient factors [K | I]
         for (int p = 0; p < Q; ++p) {
             const int k0 = p * NB;
-            double* Wp = m.WtM.p + (size_t)p * NB * NB;
-            if (p > 0)
-                if (int rc = prof_launch(h, s, PSOAP_K_PANEL_UPDATE, tile_flops * p * (want_cov ? Q : Q - p) * nb, 0.0, [&] {
-                        if (want_cov)
-                            hipLaunchKernelGGL(k_grad_panel_update, dim3(Q + 1, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, m.M.p,
-                                               m_stride, ldm, k0, Q);
-                        else
-                            hipLaunchKernelGGL(k_panel_update, dim3(Q - p, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, m.M.p, m_stride,
-                                               ldm, k0);
-                    })) return rc;
-            if (int rc = prof_launch(h, s, PSOAP_K_POTRF, 0.0, 0.0, [&] {
-                    hipLaunchKernelGGL(k_potrf_diag, dim3(nb), dim3(512), 0, s, m.M.p, m_stride, ldm, k0, Wp, m.Rhs.p, S, m.AccM.p, wstride);
-                })) return rc;
-            const int nt = want_cov ? Q : Q - p - 1;
-            if (nt > 0)
-                if (int rc = prof_launch(h, s, PSOAP_K_TRSM, tile_flops * nt * nb, 0.0, [&] {
-                        hipLaunchKernelGGL(k_trsm_strip, dim3(nt, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, m.M.p, m_stride, ldm, k0,
-                                           (const double*)Wp, m.Rhs.p, S, wstride);
-                    })) return rc;
+            const StagedRow row{m.M.p, m_stride, ldm, m.Rhs.p, S, m.AccM.p, m.WtM.p + (size_t)p * NB * NB, wstride,
+                                want_cov ? Q : Q - p - 1};
+            auto update = [&] {
+                if (want_cov)
+                    hipLaunchKernelGGL(k_grad_panel_update, dim3(Q + 1, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, m.M.p, m_stride, ldm,
+                                       k0, Q);
+                else
+                    hipLaunchKernelGGL(k_panel_update, dim3(Q - p, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, m.M.p, m_stride, ldm, k0);
+            };
+            if (int rc = staged_row(h, s, row, nb, k0, p > 0 ? &update : nullptr, TILE_FLOPS * p * (want_cov ? Q : Q - p) * nb))
+                return rc;
         }
         if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
                 hipLaunchKernelGGL(k_marg_finish, dim3(nb), dim3(256), 0, s, N, P, Q, q, order, (const MatAcc*)w.Acc.p,
@@ -2754,9 +2746,7 @@ extern "C" int psoap_chunk_lnlike_marg(psoap_chunk* h, int B, int c, const doubl
     // the conventions of the likelihood: a negative hyper-parameter, a K that is not positive definite or an M that fails to
     // factor -> -inf, and nothing else to say about it
     for (int b = 0; b < B; ++b) {
-        bool neg = false;
-        for (int k = 0; k < 2 * c; ++k) neg = neg || gp[(size_t)b * 2 * c + k] < 0.0;
-        lnp[b] = neg ? -INFINITY : out[(size_t)b * 5];
+        lnp[b] = proposal_refused(gp, c, b) ? -INFINITY : out[(size_t)b * 5];
         const bool bad = lnp[b] == -INFINITY;
         if (parts)
             for (int k = 0; k < 4; ++k) parts[(size_t)b * 4 + k] = bad ? NAN : out[(size_t)b * 5 + 1 + k];
@@ -2772,15 +2762,6 @@ extern "C" int psoap_chunk_lnlike_marg(psoap_chunk* h, int B, int c, const doubl
 }
 
 // ---- gradient of that likelihood (marg_grad_kernels.hpp) -------------------------------------------------
-template <int C>
-static void launch_marg_grad_contract(hipStream_t s, int nb, int ntiles, const double* A, size_t mstride, int ld, int N, int Npad,
-                                      int P, const double* dLwl, const double* dGp, const double* dAlpha, double* dPart,
-                                      const double* Mx, size_t m_stride, int ldm, int S)
-{
-    hipLaunchKernelGGL(k_marg_grad_contract<C>, dim3(ntiles, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, A, mstride, ld, N, Npad, P,
-                       dLwl, dGp, dAlpha, dPart, Mx, m_stride, ldm, S);
-}
-
 // Group after group of matrices through the gradient's workspace as [K | I | Ht] (marg_grad_plan.hpp), the Gram matrices
 // through the staged kernels as [M | Xt], then the gradient's own tail -- on the handle's first stream behind whatever the
 // handle has in flight.  The grids come from the host (lwl) or, with lwl == nullptr, from the orbits as in grad_run.
@@ -2806,18 +2787,8 @@ static int marg_grad_run(psoap_chunk* h, const char* who, int B, int c, const do
     GradWs& w = *h->gws;
     MargWs& m = *h->mws;
     MargGradWs& mg = *h->mgws;
-    HIP_TRY(w.A.need((size_t)G * mstride));
-    HIP_TRY(w.Wt.need((size_t)G * NB * NB));
-    HIP_TRY(w.R.need((size_t)G * Npad));
-    HIP_TRY(w.Acc.need((size_t)G * ACC_ROWS));
-    HIP_TRY(w.Lwl.need((size_t)G * 3 * N));
-    HIP_TRY(w.Gp.need((size_t)G * 6));
-    HIP_TRY(w.Alpha.need((size_t)G * Npad));
-    HIP_TRY(w.APart.need((size_t)G * nslab * Npad));
-    HIP_TRY(w.Part.need((size_t)G * ntiles * GRAD_TILE_DOUBLES));
-    HIP_TRY(w.GradGp.need((size_t)G * 6));
-    HIP_TRY(w.GradX.need((size_t)G * 3 * N));
-    HIP_TRY(w.GradMu.need(G));
+    const int ne = h->n_epochs, np = orbits ? orbit_n_params(model) : 0;
+    if (int rc = grad_ws_need(h, w, G, mstride, true, true, c, np)) return rc;
     HIP_TRY(mg.Mx.need((size_t)G * m_stride));
     HIP_TRY(mg.Zt.need((size_t)G * Npad));
     HIP_TRY(m.WtM.need((size_t)G * wstride));
@@ -2831,40 +2802,21 @@ static int marg_grad_run(psoap_chunk* h, const char* who, int B, int c, const do
     hipStream_t s = h->streams[0];
     if (int rc = marg_basis(h, m, s)) return rc;
     const int* tab = m.Tab.p;
-    const int ne = h->n_epochs, np = orbits ? orbit_n_params(model) : 0;
     std::vector<int> fast(orbits ? (size_t)B : 0, 0);
-    if (orbits) {
-        HIP_TRY(w.Porb.need((size_t)G * np));
-        HIP_TRY(w.Vel.need((size_t)G * c * ne));
-        HIP_TRY(w.Jac.need((size_t)G * c * ne * np));
-        HIP_TRY(w.Gv.need((size_t)G * c * ne));
-        HIP_TRY(w.GradOrb.need((size_t)G * np));
-        HIP_TRY(w.TooFast.need(G));
+    if (orbits)
         if (int rc = grad_epoch_lists(h, w, s)) return rc;
-    }
     h->recs.clear();
-    const double tile_flops = 2.0 * NB * NB * (double)NB;
     std::vector<double> out((size_t)B * 5);
     double* Ah = w.A.p + Npad;          // what the kernels of marg_kernels.hpp take for [K | Ht]: Ht one block further right
     for (int b0 = 0; b0 < B; b0 += G) {
         const int nb = (B - b0 < G) ? B - b0 : G;
-        if (!orbits) {
+        if (!orbits)
             HIP_TRY(hipMemcpyAsync(w.Lwl, lwl + (size_t)b0 * c * N, sizeof(double) * (size_t)nb * c * N, hipMemcpyHostToDevice, s));
-        } else {
-            HIP_TRY(hipMemcpyAsync(w.Porb, p_orb + (size_t)b0 * np, sizeof(double) * (size_t)nb * np, hipMemcpyHostToDevice, s));
-            HIP_TRY(hipMemsetAsync(w.TooFast, 0, sizeof(int) * (size_t)nb, s));
-            hipLaunchKernelGGL(k_orbit_jacobian, dim3((ne + 63) / 64, nb), dim3(64), 0, s, model, nb, ne, (const double*)w.Porb.p,
-                               (const double*)h->dDates, w.Vel.p, w.Jac.p, w.TooFast.p);
-            hipLaunchKernelGGL(k_doppler_shift, dim3((N + 255) / 256, nb * c), dim3(256), 0, s, w.Lwl.p, h->dGrid, h->dEpoch,
-                               (const double*)w.Vel.p, N, ne, nb * c);
-            HIP_TRY(hipGetLastError());
-        }
+        else if (int rc = orbit_front(h, w, s, nb, c, model, np, p_orb + (size_t)b0 * np))
+            return rc;
         HIP_TRY(hipMemcpyAsync(w.Gp, gp + (size_t)b0 * 2 * c, sizeof(double) * (size_t)nb * 2 * c, hipMemcpyHostToDevice, s));
         if (int rc = prof_launch(h, s, PSOAP_K_FILL, 0.0, (double)nb * 12.0 * N * (N + 1.0), [&] {
-                with_components(c, [&](auto nc) {
-                    launch_grad_fill_contract<nc()>(false, s, nb, ntiles, w.A, mstride, ld, N, Npad, P, w.Lwl, w.Gp, h->dSigma, nullptr,
-                                                    nullptr);
-                });
+                launch_grad_fill(h, w, s, nb, c, mstride, ld);
                 hipLaunchKernelGGL(k_grad_init, dim3(ntiles, nb), dim3(256), 0, s, w.A.p, mstride, ld, Npad, P);
                 hipLaunchKernelGGL(k_marg_load, dim3(Q * P, nb), dim3(256), 0, s, Ah, mstride, ld, Npad, P, (const double*)m.Ht.p, ldh,
                                    tab);
@@ -2876,27 +2828,18 @@ static int marg_grad_run(psoap_chunk* h, const char* who, int B, int c, const do
         for (int p = 0; p < P; ++p) {
             const int k0 = p * NB;
             const MargGradRow& row = gpl.rows[(size_t)p];
-            if (row.update_k + row.update_h > 0) {
-                const double units = (double)p * (P - p) + 0.5 * p * (p + 1.0) + (double)p * row.update_h;
-                if (int rc = prof_launch(h, s, PSOAP_K_PANEL_UPDATE, tile_flops * units * nb, 0.0, [&] {
-                        hipLaunchKernelGGL(k_marg_grad_panel_update, dim3(row.update_k + row.update_h, nb), dim3(GEMM_THREADS),
-                                           GEMM_LDS_BYTES, s, w.A.p, mstride, ld, k0, P, tab);
-                    })) return rc;
-            }
-            if (int rc = prof_launch(h, s, PSOAP_K_POTRF, 0.0, 0.0, [&] {
-                    hipLaunchKernelGGL(k_potrf_diag, dim3(nb), dim3(512), 0, s, w.A.p, mstride, ld, k0, w.Wt.p, w.R.p, Npad, w.Acc.p,
-                                       (size_t)NB * NB);
-                })) return rc;
-            if (int rc = prof_launch(h, s, PSOAP_K_TRSM, tile_flops * (row.strip_k + row.strip_h) * nb, 0.0, [&] {
-                    hipLaunchKernelGGL(k_trsm_strip, dim3(row.strip_k, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, w.A.p, mstride, ld, k0,
-                                       (const double*)w.Wt.p, w.R.p, Npad, (size_t)NB * NB);
-                    // the slots of Ht: the strip's first tile column moved onto tile column 2 P, and no right-hand side
-                    // (Npad = 0: every column counts as appended, r is only read)
-                    if (row.strip_h > 0)
-                        hipLaunchKernelGGL(k_trsm_strip, dim3(row.strip_h, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s,
-                                           w.A.p + (NB * gpl.tile_H - k0 - NB), mstride, ld, k0, (const double*)w.Wt.p, w.R.p, 0,
-                                           (size_t)NB * NB);
-                })) return rc;
+            const double units = (double)p * (P - p) + 0.5 * p * (p + 1.0) + (double)p * row.update_h;
+            auto update = [&] {
+                hipLaunchKernelGGL(k_marg_grad_panel_update, dim3(row.update_k + row.update_h, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES,
+                                   s, w.A.p, mstride, ld, k0, P, tab);
+            };
+            // the slots of Ht are a second strip: its first tile column moved onto tile column 2 P, and no right-hand side
+            // (r_rows = 0: every column counts as appended, r is only read)
+            StagedRow sr = grad_row(w, mstride, ld, Npad, row.strip_k);
+            sr.A2 = w.A.p + (NB * gpl.tile_H - k0 - NB);
+            sr.strip2 = row.strip_h;
+            if (int rc = staged_row(h, s, sr, nb, k0, row.update_k + row.update_h > 0 ? &update : nullptr, TILE_FLOPS * units * nb))
+                return rc;
         }
         if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
                 hipLaunchKernelGGL(k_marg_rhs_partial, dim3(Q, nslab, nb), dim3(256), 0, s, (const double*)Ah, mstride, ld, Npad, Q, tab,
@@ -2908,7 +2851,7 @@ static int marg_grad_run(psoap_chunk* h, const char* who, int B, int c, const do
         for (const MargTile& t : pl.tiles) gunits += (t.ti == t.tj ? 0.75 : 1.0) * (Npad - t.k0) / NB;
         for (int sl = 0; sl < Q; ++sl)
             for (int tj = 0; tj < P; ++tj) gunits += P - std::min(P, std::max(pl.first[(size_t)pl.column[(size_t)sl]], tj));
-        if (int rc = prof_launch(h, s, PSOAP_K_GRAD, tile_flops * gunits * nb, 0.0, [&] {
+        if (int rc = prof_launch(h, s, PSOAP_K_GRAD, TILE_FLOPS * gunits * nb, 0.0, [&] {
                 hipLaunchKernelGGL(k_marg_gram, dim3(ngram, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)Ah, mstride, ld,
                                    Npad, (const MargTile*)m.Tiles.p, mg.Mx.p, m_stride, ldm);
                 hipLaunchKernelGGL(k_marg_grad_cross, dim3(Q * P, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)w.A.p,
@@ -2917,19 +2860,11 @@ static int marg_grad_run(psoap_chunk* h, const char* who, int B, int c, const do
         // [M | Xt]: M = U_M^T U_M with bt alongside, and the appended block becomes Vt = U_M^-T Xt
         for (int p = 0; p < Q; ++p) {
             const int k0 = p * NB;
-            double* Wp = m.WtM.p + (size_t)p * NB * NB;
-            if (p > 0)
-                if (int rc = prof_launch(h, s, PSOAP_K_PANEL_UPDATE, tile_flops * p * (Q - p + P) * nb, 0.0, [&] {
-                        hipLaunchKernelGGL(k_panel_update, dim3(Q - p + P, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, mg.Mx.p, m_stride,
-                                           ldm, k0);
-                    })) return rc;
-            if (int rc = prof_launch(h, s, PSOAP_K_POTRF, 0.0, 0.0, [&] {
-                    hipLaunchKernelGGL(k_potrf_diag, dim3(nb), dim3(512), 0, s, mg.Mx.p, m_stride, ldm, k0, Wp, m.Rhs.p, S, m.AccM.p, wstride);
-                })) return rc;
-            if (int rc = prof_launch(h, s, PSOAP_K_TRSM, tile_flops * (Q - p - 1 + P) * nb, 0.0, [&] {
-                    hipLaunchKernelGGL(k_trsm_strip, dim3(Q - p - 1 + P, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, mg.Mx.p, m_stride, ldm,
-                                       k0, (const double*)Wp, m.Rhs.p, S, wstride);
-                })) return rc;
+            const StagedRow mrow{mg.Mx.p, m_stride, ldm, m.Rhs.p, S, m.AccM.p, m.WtM.p + (size_t)p * NB * NB, wstride, Q - p - 1 + P};
+            auto update = [&] {
+                hipLaunchKernelGGL(k_panel_update, dim3(Q - p + P, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, mg.Mx.p, m_stride, ldm, k0);
+            };
+            if (int rc = staged_row(h, s, mrow, nb, k0, p > 0 ? &update : nullptr, TILE_FLOPS * p * (Q - p + P) * nb)) return rc;
         }
         // lnL and g = U_M^-1 y; z - Wh g; alpha_m
         if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
@@ -2939,17 +2874,15 @@ static int marg_grad_run(psoap_chunk* h, const char* who, int B, int c, const do
                                    (const double*)m.Ht.p, ldh, (const double*)h->dFl.p, m.Out.p, m.Beta.p, m.Flc.p, 1);
                 hipLaunchKernelGGL(k_marg_grad_resid, dim3(Npad / 4, nb), dim3(256), 0, s, (const double*)w.A.p, mstride, ld, Npad, Q,
                                    tab, (const double*)w.R.p, (const double*)m.Gam.p, mg.Zt.p);
-                hipLaunchKernelGGL(k_grad_alpha_partial, dim3(P, nslab, nb), dim3(256), 0, s, (const double*)w.A.p, mstride, ld, Npad,
-                                   (const double*)mg.Zt.p, w.APart.p, nslab);
-                hipLaunchKernelGGL(k_grad_alpha_finish, dim3((Npad + 255) / 256, nb), dim3(256), 0, s, (const double*)w.APart.p, nslab,
-                                   Npad, w.Alpha.p);
+                launch_alpha(w, s, nb, mstride, ld, Npad, P, mg.Zt.p);
             })) return rc;
         double cunits = 0.0;
         for (int tj = 0; tj < P; ++tj) cunits += (double)(tj + 1) * (P - tj + Q);
-        if (int rc = prof_launch(h, s, PSOAP_K_GRAD, tile_flops * cunits * nb, 0.0, [&] {
+        if (int rc = prof_launch(h, s, PSOAP_K_GRAD, TILE_FLOPS * cunits * nb, 0.0, [&] {
                 with_components(c, [&](auto nc) {
-                    launch_marg_grad_contract<nc()>(s, nb, ntiles, w.A, mstride, ld, N, Npad, P, w.Lwl, w.Gp, w.Alpha, w.Part, mg.Mx,
-                                                    m_stride, ldm, S);
+                    hipLaunchKernelGGL(k_marg_grad_contract<nc()>, dim3(ntiles, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s,
+                                       (const double*)w.A.p, mstride, ld, N, Npad, P, (const double*)w.Lwl.p, (const double*)w.Gp.p,
+                                       (const double*)w.Alpha.p, w.Part.p, (const double*)mg.Mx.p, m_stride, ldm, S);
                 });
             })) return rc;
         if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
@@ -2961,41 +2894,21 @@ static int marg_grad_run(psoap_chunk* h, const char* who, int B, int c, const do
         if (grad_lwl)
             HIP_TRY(hipMemcpyAsync(grad_lwl + (size_t)b0 * c * N, w.GradX, sizeof(double) * (size_t)nb * c * N, hipMemcpyDeviceToHost, s));
         if (grad_mu) HIP_TRY(hipMemcpyAsync(grad_mu + b0, w.GradMu, sizeof(double) * nb, hipMemcpyDeviceToHost, s));
-        if (orbits) {
-            const int CE = c * ne;
-            hipLaunchKernelGGL(k_epoch_fold, dim3((CE + 3) / 4, nb), dim3(256), 0, s, (const double*)w.GradX.p, (const int*)w.EpStart.p,
-                               (const int*)w.EpPix.p, c, N, ne, w.Gv.p);
-            hipLaunchKernelGGL(k_orbit_chain, dim3(nb), dim3(256), 0, s, (const double*)w.Gv.p, (const double*)w.Jac.p, CE, np,
-                               w.GradOrb.p);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(grad_orb + (size_t)b0 * np, w.GradOrb, sizeof(double) * (size_t)nb * np, hipMemcpyDeviceToHost, s));
-            if (grad_vel)
-                HIP_TRY(hipMemcpyAsync(grad_vel + (size_t)b0 * CE, w.Gv, sizeof(double) * (size_t)nb * CE, hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipMemcpyAsync(fast.data() + b0, w.TooFast, sizeof(int) * (size_t)nb, hipMemcpyDeviceToHost, s));
-        }
+        if (orbits)
+            if (int rc = orbit_back(h, w, s, nb, c, np, grad_orb + (size_t)b0 * np, grad_vel ? grad_vel + (size_t)b0 * c * ne : nullptr,
+                                    fast.data() + b0))
+                return rc;
         HIP_TRY(hipStreamSynchronize(s));       // the next group reuses the workspace and the caller's arrays are pageable
     }
     if (collect_timings(h)) return 1;
     // the conventions of psoap_chunk_lnlike_marg and psoap_chunk_lnlike_grad: a negative hyper-parameter, a K or an M that
     // does not factor, a faster-than-light orbit -> -inf, and no gradient there
     for (int b = 0; b < B; ++b) {
-        bool neg = false;
-        for (int k = 0; k < 2 * c; ++k) neg = neg || gp[(size_t)b * 2 * c + k] < 0.0;
-        if (orbits && fast[b]) neg = true;
-        lnp[b] = neg ? -INFINITY : out[(size_t)b * 5];
+        lnp[b] = proposal_refused(gp, c, b, orbits ? fast.data() : nullptr) ? -INFINITY : out[(size_t)b * 5];
         const bool bad = lnp[b] == -INFINITY;
         if (parts)
             for (int k = 0; k < 4; ++k) parts[(size_t)b * 4 + k] = bad ? NAN : out[(size_t)b * 5 + 1 + k];
-        if (!bad) continue;
-        for (int k = 0; k < 2 * c; ++k) grad_gp[(size_t)b * 2 * c + k] = NAN;
-        if (grad_lwl)
-            for (size_t k = 0; k < (size_t)c * N; ++k) grad_lwl[(size_t)b * c * N + k] = NAN;
-        if (grad_mu) grad_mu[b] = NAN;
-        if (orbits) {
-            for (int k = 0; k < np; ++k) grad_orb[(size_t)b * np + k] = NAN;
-            if (grad_vel)
-                for (size_t k = 0; k < (size_t)c * ne; ++k) grad_vel[(size_t)b * c * ne + k] = NAN;
-        }
+        if (bad) poison_gradient(b, c, N, ne, np, grad_gp, grad_lwl, grad_mu, grad_orb, grad_vel);
     }
     return 0;
 }
@@ -3024,13 +2937,10 @@ extern "C" int psoap_chunk_lnprob_marg_grad(psoap_chunk* h, int B, int model, co
 // frees the device side of the baseline and the workspace; the baseline itself stays set (the next call builds Ht again)
 extern "C" int psoap_chunk_marg_release(psoap_chunk* h)
 {
-    if (!h) FAIL("null handle");
-    DEVICE_SCOPE(h->device);
-    if (set_dev(h)) return 1;
-    HIP_TRY(hipStreamSynchronize(h->streams[0]));
-    h->mws.reset();
-    h->mgws.reset();
-    return 0;
+    return release_ws(h, [&] {
+        h->mws.reset();
+        h->mgws.reset();
+    });
 }
 
 // ---- fills (matrix_functions drop-ins) ------------------------------------------------------

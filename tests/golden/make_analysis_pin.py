@@ -1,0 +1,233 @@
+#!/usr/bin/env python3
+"""The exact pin of the analysis paths behind the C ABI (gradient, orbit gradient, Fisher information, leave-one-out, continuum
+marginalisation and its gradients, the staged likelihood): for every call of ``CALLS`` the int64 bit pattern of every output
+array and, from ``ChunkHandle.timings()``, the per-class ``launches``, ``flops`` and ``bytes`` -- host-computed integers held in
+doubles.  ``ms`` and ``total_ms`` are measurements and are not recorded.  tests/test_gpu_analysis_pin.py replays ``CALLS``
+through ``run`` and compares with ``==``.
+
+Needs the device: every call runs twice, with profiling on, on a fresh handle, and an output whose bits (or a bookkeeping
+field whose value) differ between the two runs is refused, not recorded.
+
+    python tests/golden/make_analysis_pin.py [--out PATH] [--commit ID]
+
+The fixture pins the library as it is when this runs: generate it BEFORE a change that has to keep the bits, never after.
+``--commit`` is stored in the file as ``generated_at``.  The shapes are those of the reference modules of tests/: the
+smallest at which each path differs (a second tile row, two groups of proposals, an empty epoch, a Gram matrix that crosses
+a block row).
+"""
+import contextlib
+import os
+import sys
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+TESTS = os.path.dirname(HERE)
+ROOT = os.path.dirname(TESTS)
+for _p in (ROOT, TESTS):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+
+import fisher_reference as fr  # noqa: E402
+import grad_reference as gr  # noqa: E402
+import marg_reference as mr  # noqa: E402
+import orbit_grad_reference as ogr  # noqa: E402
+from psoap_amd import synthetic as syn  # noqa: E402
+from psoap_amd._lib import K_NAMES  # noqa: E402
+from psoap_amd.utils import MODEL_ID  # noqa: E402
+
+PIN_PATH = os.path.join(HERE, "analysis_pin_v1.npz")
+BOOK_FIELDS = ("launches", "flops", "bytes")
+ORBIT_BASELINE = {"order": 1, "sd": list(mr.PLANT_SD), "weight": "one"}
+FAST_K = 4.0e6                  # km/s: thirteen times the speed of light (tests/test_gpu_marg_grad.py)
+
+
+# ---- set-ups -----------------------------------------------------------------------------------------------------------------
+@contextlib.contextmanager
+def _handle(ch, baseline=None, **kw):
+    """a fresh handle on the chunk's data, profiling on; ``baseline = (case, kind)`` sets that case's baseline"""
+    from psoap_amd.chunk import ChunkHandle
+    with ChunkHandle(ch.fl, ch.sigma, **kw) as h:
+        h.set_profiling(True)
+        if baseline is not None:
+            case, kind = baseline
+            h.set_baseline(ch.order, ch.x, ch.epoch_index, ch.n_epochs, mr.prior_sd(ch.order), mr.case_weight(case, kind))
+        yield h
+
+
+@contextlib.contextmanager
+def _orbit_worker(baseline):
+    """the SB2 chunk of the orbit-gradient tests at N = 129 (two tile rows), profiling on"""
+    from psoap_amd.lnprob import ChunkWorker
+    ch = ogr.CHAIN_CASES[0].chunk
+    w = ChunkWorker("SB2", ch.lwl, ch.fl, ch.sigma, ch.epoch_index, ch.dates, baseline=baseline)
+    try:
+        w.handle.set_profiling(True)
+        yield w.handle
+    finally:
+        w.close()
+
+
+def _batch(case, B, seed, negative=None):
+    """B proposals around a case of marg_reference: grids a few 1e-6 apart, seeded hyper-parameters (the case's own first);
+    ``negative``: the proposal whose second hyper-parameter changes sign"""
+    ch, c = mr.case_chunk(case), case[2]
+    gps = syn.make_walkers(c, B, seed=seed)
+    gps[0] = mr.case_gp(case)
+    if negative is not None:
+        gps[negative, 1] = -gps[negative, 1]
+    return np.stack([ch.lwls + 1e-6 * k for k in range(B)]), gps
+
+
+def _orbit_batch():
+    """three SB2 orbits, the one in the middle faster than light"""
+    P = syn.make_orbit_proposals("SB2", 3, seed=920)
+    P[1, 1] = FAST_K
+    return P, syn.make_walkers(2, 3, seed=921)
+
+
+def _named(names, values):
+    return dict(zip(names, values))
+
+
+GRAD_OUT = ("lnp", "grad_gp", "grad_lwl", "grad_mu")
+ORBIT_OUT = ("lnp", "grad_orb", "grad_gp", "grad_mu", "grad_vel")
+LOO_OUT = ("lnp", "loo_logp", "pix_mean", "pix_var", "pix_logp", "ep_resid", "ep_chi2", "ep_logp", "ep_npix")
+MARG_OUT = ("lnp", "parts", "beta", "beta_cov", "fl_cor")
+
+
+# ---- the calls: name -> a context manager that yields (handle, call); call() -> {output: array} ------------------------------
+@contextlib.contextmanager
+def _lnlike_grad(B):
+    case = mr.case_named("c")
+    ch = mr.case_chunk(case)
+    lw, gps = (ch.lwls, mr.case_gp(case)) if B == 1 else _batch(case, B, 9701, negative=4)
+    with _handle(ch) as h:
+        yield h, lambda: _named(GRAD_OUT, h.lnlike_grad(lw, gps, mr.MU_GP))
+
+
+@contextlib.contextmanager
+def _lnprob_grad(marg):
+    P, gps = _orbit_batch()
+    with _orbit_worker(ORBIT_BASELINE if marg else None) as h:
+        entry = h.lnprob_marg_grad if marg else h.lnprob_grad
+        yield h, lambda: _named(ORBIT_OUT, entry(MODEL_ID["SB2"], P, gps, gr.MU_GP, want_vel=True))
+
+
+@contextlib.contextmanager
+def _fisher(grid_tangents):
+    case = fr.CASES[2]                      # N = 129, c = 2
+    assert case[:2] == (129, 2)
+    ch, gp, c = fr.case_chunk(case), fr.case_gp(case), case[1]
+    tan_lwl, tan_gp = fr.case_tangents(case)
+    pick = [1, 2 * c] if grid_tangents else [0, 1]          # a hyper-parameter and a velocity tangent / two hyper-parameters
+    with _handle(ch) as h:
+        yield h, lambda: _named(("F", "F_mu"), h.fisher(ch.lwls, gp, tan_gp[pick], tan_lwl[pick] if grid_tangents else None,
+                                                        want_mu=True))
+
+
+@contextlib.contextmanager
+def _loo(name, epochs):
+    case = mr.case_named(name)
+    ch, gp = mr.case_chunk(case), mr.case_gp(case)
+    with _handle(ch) as h:
+        def call():
+            r = h.loo(ch.lwls, gp, mr.MU_GP, *((ch.epoch_index, ch.n_epochs) if epochs else ()))
+            return {k: getattr(r, k) for k in LOO_OUT if getattr(r, k) is not None}
+        yield h, call
+
+
+@contextlib.contextmanager
+def _lnlike_marg(name, kind, B, more):
+    case = mr.case_named(name)
+    ch = mr.case_chunk(case)
+    lw, gps = (ch.lwls, mr.case_gp(case)) if B == 1 else _batch(case, B, 9702)
+    with _handle(ch, baseline=(case, kind), max_batch=B) as h:
+        def call():
+            r = h.lnlike_marg(lw, gps, mr.MU_GP, want_beta=more, want_cov=more, want_flux=more)
+            return {k: getattr(r, k) for k in MARG_OUT} if more else {"lnp": r}
+        yield h, call
+
+
+@contextlib.contextmanager
+def _lnlike_marg_grad():
+    case = mr.case_named("f")
+    lw, gps = _batch(case, 10, 9801)
+    with _handle(mr.case_chunk(case), baseline=(case, "flux")) as h:
+        yield h, lambda: _named(GRAD_OUT, h.lnlike_marg_grad(lw, gps, mr.MU_GP))
+
+
+@contextlib.contextmanager
+def _staged_lnlike():
+    case = mr.case_named("c")
+    lw, gps = _batch(case, 3, 9703)
+    with _handle(mr.case_chunk(case), max_batch=3) as h:
+        h.set_mode("staged")
+        yield h, lambda: {"lnp": h.lnlike_batch(lw, gps, mr.MU_GP)}
+
+
+CALLS = {
+    "lnlike_grad-c-B1": lambda: _lnlike_grad(1),
+    "lnlike_grad-c-B10-negative": lambda: _lnlike_grad(10),               # two groups, 8 + 2
+    "lnprob_grad-SB2-N129-B3-fast": lambda: _lnprob_grad(False),
+    "fisher-N129-T2-no-grid-tangents": lambda: _fisher(False),
+    "fisher-N129-T2-grid-tangents": lambda: _fisher(True),
+    "loo-e-epochs": lambda: _loo("e", True),                              # an empty epoch, runs not in id order
+    "loo-c-pixels-only": lambda: _loo("c", False),
+    "lnlike_marg-c-B1": lambda: _lnlike_marg("c", "one", 1, False),
+    "lnlike_marg-c-B1-beta-cov-flux": lambda: _lnlike_marg("c", "one", 1, True),
+    "lnlike_marg-f-B3": lambda: _lnlike_marg("f", "flux", 3, False),       # Q = 2: M crosses a block row
+    "lnlike_marg-f-B3-beta-cov-flux": lambda: _lnlike_marg("f", "flux", 3, True),      # the [M | I] sweep
+    "lnlike_marg_grad-f-flux-B10": _lnlike_marg_grad,
+    "lnprob_marg_grad-SB2-N129-B3-fast": lambda: _lnprob_grad(True),
+    "staged-lnlike_batch-c-B3": _staged_lnlike,
+}
+
+
+# ---- running and comparing -------------------------------------------------------------------------------------------------
+def bits(a):
+    """the int64 bit pattern of a float64 array (or scalar); integer arrays as int64 values"""
+    a = np.atleast_1d(np.asarray(a))
+    if a.dtype.kind in "iu":
+        return a.astype(np.int64)
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.int64).copy()
+
+
+def book(timings):
+    """(3, classes): launches, flops and bytes per kernel class, in the order of ``K_NAMES``"""
+    return np.array([[float(timings[name][f]) for name in K_NAMES] for f in BOOK_FIELDS])
+
+
+def run(name, repeats=1):
+    """``repeats`` runs of the call on ONE fresh handle -> [({output: bits}, book), ...]"""
+    out = []
+    with CALLS[name]() as (h, call):
+        for _ in range(repeats):
+            got = call()
+            out.append(({k: bits(v) for k, v in got.items()}, book(h.timings())))
+    return out
+
+
+def main(argv):
+    path = argv[argv.index("--out") + 1] if "--out" in argv else PIN_PATH
+    commit = argv[argv.index("--commit") + 1] if "--commit" in argv else "unknown"
+    pin, refused = {"generated_at": np.array(commit)}, []
+    for name in CALLS:
+        (first, book1), (second, book2) = run(name, repeats=2)
+        for k in first:
+            if not np.array_equal(first[k], second[k]):
+                refused.append(f"{name}/{k}")
+            pin[f"{name}/{k}"] = first[k]
+        if not np.array_equal(book1, book2):
+            refused.append(f"{name}/book")
+        pin[f"{name}/book"] = book1
+        print(f"{name}: {', '.join(f'{k}{list(v.shape)}' for k, v in first.items())}; launches "
+              f"{dict(zip(K_NAMES, (int(v) for v in book1[0])))}")
+    if refused:
+        raise SystemExit("two runs on one handle differ, nothing written: " + ", ".join(refused))
+    np.savez_compressed(path, **pin)
+    print("wrote", path, os.path.getsize(path))
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:])
