@@ -344,6 +344,46 @@ int psoap_chunk_lnlike_marg_grad(psoap_chunk *h, int B, int c, const double *lwl
 int psoap_chunk_lnprob_marg_grad(psoap_chunk *h, int B, int model, const double *p_orb, const double *gp, double mu_GP,
                                  double *lnp, double *grad_orb, double *grad_gp, double *grad_mu, double *grad_vel);
 
+/* ---- Fisher information and leave-one-out under the marginalised continuum ---------------
+ * psoap_chunk_fisher_marg and psoap_chunk_loo_marg are psoap_chunk_fisher and
+ * psoap_chunk_loo with Kt = K + Ht Ht^T (the baseline of psoap_chunk_set_baseline) in the
+ * place of K: arguments, outputs, shapes and NULL rules are their plain twins'.
+ *   fisher    F_st = 1/2 tr(Kt^-1 K_s Kt^-1 K_t), both triangles, F == F^T bit for bit;
+ *   fisher_mu 1^T Kt^-1 1 = |Wi 1|^2 - |Vt 1|^2;
+ *   leave-one-out: A = Kt^-1 and alpha = Kt^-1 r in every formula of psoap_chunk_loo;
+ *             lnp is the marginal likelihood, with the bits of psoap_chunk_lnlike_marg.
+ * H does not depend on the hyper-parameters, the rest-frame grids or mu_GP, so a
+ * tangent's covariance derivative K_t is the plain one.  The staged factorisation of
+ * [K | I | Ht] and of [M | Xt] runs as psoap_chunk_lnlike_marg_grad runs it for one matrix
+ * and leaves Wi = U^-T, Vt = U_M^-T Wh^T Wi and alpha_m; Kt^-1 = Wi^T Wi - Vt^T Vt is formed
+ * tile by tile with a second K loop of depth 128 Q over Vt on the same accumulators, into
+ * the Fisher workspace's K^-1 slot or, for the band tiles, into the packed epoch blocks
+ * (csrc/marg_fisher_kernels.hpp); everything after that is the plain entry's launches.
+ * About 3 N^2 128 Q flops beyond the plain entries, nothing more per tangent.  No atomics,
+ * every sum in an order fixed by (N, c, baseline layout, T): the same arguments give the
+ * same bits, a subsequence of the tangents gives the bits of the entries it shares, and
+ * the plain entries keep their bits, also on a handle with a baseline.
+ * The epoch index of psoap_chunk_loo_marg is that of its own outputs (contiguous runs in
+ * any order, as for psoap_chunk_loo); it need not be the baseline's.
+ * Conventions: a negative hyper-parameter, a K that is not positive definite or an M that
+ * does not factor gives NaN in every output (lnp = -inf) and status 0.  Refused: what the
+ * plain twins refuse (T < 1 or T > 32, a bad epoch layout, an open stream), and a handle
+ * without a baseline or with a stale one, with psoap_chunk_lnlike_marg's messages.  The
+ * derivative with respect to prior_sd is not provided.
+ * Workspace: that of psoap_chunk_lnlike_marg_grad for one matrix (psoap_chunk_grad_release,
+ * psoap_chunk_marg_release) plus the three Npad^2 matrices of psoap_chunk_fisher
+ * (psoap_chunk_fisher_release) or the packed blocks of psoap_chunk_loo
+ * (psoap_chunk_loo_release): the workspaces of the plain twins, shared with them. */
+int psoap_chunk_fisher_marg(psoap_chunk *h, int c, const double *lwl, const double *gp,
+                            int T, const double *tan_lwl, const double *tan_gp,
+                            double *fisher, double *fisher_mu);
+int psoap_chunk_loo_marg(psoap_chunk *h, int c, const double *lwl, const double *gp, double mu_GP,
+                         const int32_t *epoch, int n_epochs,
+                         double *lnp, double *loo_logp,
+                         double *pix_mean, double *pix_var, double *pix_logp,
+                         double *ep_resid,
+                         double *ep_chi2, double *ep_logp, int32_t *ep_npix);
+
 /* Split-phase form of psoap_lnlike_batch: upload (H2D, async, on a copy stream of
  * its own), eval (kernels only, async), fetch (sync + D2H of B doubles).
  * A handle holds TWO proposal batches: an upload always goes to the one that is

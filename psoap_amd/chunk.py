@@ -208,7 +208,12 @@ class ChunkHandle:
         """Fisher information of the likelihood at ``lwls`` (c, N), ``gp`` (2c,) along T <= 32 tangents (include/psoap_gp.h:
         psoap_chunk_fisher): ``tan_gp`` (T, 2c) and ``tan_lwl`` (T, c, N) (``None``: zeros) -> ``F (T, T)``,
         ``F_st = 1/2 tr(K^-1 K_s K^-1 K_t)``, symmetric bit for bit; with ``want_mu`` ``(F, F_mu)``, ``F_mu = 1^T K^-1 1``.
-        A negative hyper-parameter or a matrix that is not positive definite gives NaN in every entry."""
+        A negative hyper-parameter or a matrix that is not positive definite gives NaN in every entry.  Always under the
+        plain ``K``, also on a handle with a baseline: ``fisher_marg`` is the form under ``K + H Lambda H^T``."""
+        return self._fisher("psoap_chunk_fisher", lwls, gp, tan_gp, tan_lwl, want_mu)
+
+    def _fisher(self, entry, lwls, gp, tan_gp, tan_lwl, want_mu):
+        """the body of ``fisher`` and ``fisher_marg``: ``entry`` names the library's function"""
         lwls = as_f64(np.atleast_2d(lwls))
         c = lwls.shape[0]
         lwls = as_f64(lwls, (c, self.N))
@@ -219,9 +224,19 @@ class ChunkHandle:
         if tan_lwl is not None:
             tan_lwl = as_f64(tan_lwl, (T, c, self.N))
         F, mu = np.empty((T, T)), np.empty(1)
-        check(self._L.psoap_chunk_fisher(self._h, c, dptr(lwls), dptr(gp), T, None if tan_lwl is None else dptr(tan_lwl),
-                                         dptr(tan_gp), dptr(F), dptr(mu) if want_mu else None), "psoap_chunk_fisher")
+        check(getattr(self._L, entry)(self._h, c, dptr(lwls), dptr(gp), T, None if tan_lwl is None else dptr(tan_lwl),
+                                      dptr(tan_gp), dptr(F), dptr(mu) if want_mu else None), entry)
         return (F, float(mu[0])) if want_mu else F
+
+    def fisher_marg(self, lwls, gp, tan_gp, tan_lwl=None, want_mu: bool = False):
+        """``fisher`` under the baseline of ``set_baseline`` (include/psoap_gp.h: psoap_chunk_fisher_marg): the same arguments,
+        ``F_st = 1/2 tr(Kt^-1 K_s Kt^-1 K_t)`` and ``F_mu = 1^T Kt^-1 1`` with ``Kt = K + H Lambda H^T`` -- the information of
+        the likelihood ``lnlike_marg`` returns (the basis does not depend on any parameter: ``K_t`` is the plain one).  A
+        negative hyper-parameter, a ``K`` that is not positive definite or an ``M`` that does not factor gives NaN in every
+        entry."""
+        if getattr(self, "_baseline", None) is None:
+            raise _lib.PsoapError("fisher_marg: call set_baseline first")
+        return self._fisher("psoap_chunk_fisher_marg", lwls, gp, tan_gp, tan_lwl, want_mu)
 
     def fisher_release(self):
         """Free the Fisher workspace (24 Npad^2 bytes); the next ``fisher`` allocates it again."""
@@ -232,7 +247,12 @@ class ChunkHandle:
         psoap_chunk_loo): every pixel predicted from all the others and, with ``epoch_index`` (N,), every epoch from all the
         other epochs.  Every epoch's pixels must be one contiguous run (the order of ``Chunk.apply_mask``); ``n_epochs``
         defaults to ``max(epoch_index) + 1``.  A negative hyper-parameter or a matrix that is not positive definite gives
-        ``lnp = -inf`` and NaN in every other floating field."""
+        ``lnp = -inf`` and NaN in every other floating field.  Always under the plain ``K``, also on a handle with a
+        baseline: ``loo_marg`` is the form under ``K + H Lambda H^T``."""
+        return self._loo("psoap_chunk_loo", lwls, gp, mu_GP, epoch_index, n_epochs)
+
+    def _loo(self, entry, lwls, gp, mu_GP, epoch_index, n_epochs):
+        """the body of ``loo`` and ``loo_marg``: ``entry`` names the library's function"""
         lwls = as_f64(np.atleast_2d(lwls))
         c = lwls.shape[0]
         lwls = as_f64(lwls, (c, self.N))
@@ -249,12 +269,22 @@ class ChunkHandle:
             ne = int(ep.max()) + 1 if n_epochs is None else int(n_epochs)
             resid, chi2, elogp, npix = np.empty(N), np.empty(max(ne, 0)), np.empty(max(ne, 0)), np.empty(max(ne, 0), dtype=np.int32)
         i32 = ctypes.POINTER(ctypes.c_int32)
-        check(self._L.psoap_chunk_loo(self._h, c, dptr(lwls), dptr(gp), float(mu_GP),
+        check(getattr(self._L, entry)(self._h, c, dptr(lwls), dptr(gp), float(mu_GP),
                                       None if ep is None else ep.ctypes.data_as(i32), ne, dptr(lnp), dptr(logp), dptr(mean),
                                       dptr(var), dptr(plogp), None if ep is None else dptr(resid),
                                       None if ep is None else dptr(chi2), None if ep is None else dptr(elogp),
-                                      None if ep is None else npix.ctypes.data_as(i32)), "psoap_chunk_loo")
+                                      None if ep is None else npix.ctypes.data_as(i32)), entry)
         return LooResult(float(lnp[0]), float(logp[0]), mean, var, plogp, self.fl, resid, chi2, elogp, npix)
+
+    def loo_marg(self, lwls, gp, mu_GP: float = 1.0, epoch_index=None, n_epochs: int | None = None) -> "LooResult":
+        """``loo`` under the baseline of ``set_baseline`` (include/psoap_gp.h: psoap_chunk_loo_marg): the same arguments and
+        the same ``LooResult`` with ``A = (K + H Lambda H^T)^-1`` -- every pixel and every epoch predicted from the others
+        with the continuum of each epoch integrated out, so an epoch whose only fault is a continuum offset within the
+        prior is not an outlier.  ``lnp`` has the bits of ``lnlike_marg``.  ``epoch_index`` is the index of the epoch
+        outputs; it need not be the baseline's."""
+        if getattr(self, "_baseline", None) is None:
+            raise _lib.PsoapError("loo_marg: call set_baseline first")
+        return self._loo("psoap_chunk_loo_marg", lwls, gp, mu_GP, epoch_index, n_epochs)
 
     def loo_release(self):
         """Free the leave-one-out workspace (the packed epoch blocks); the next ``loo`` allocates it again."""

@@ -403,6 +403,59 @@ def lnlike_marginal_grad(lwls, fl, sigma, gp, x, epoch_index, order, prior_sd, w
     return np.float64(lnp), g_gp, g_lwl, np.float64(g_mu)
 
 
+def _marginal_front(lwls, gp, epoch_index):
+    """the shared front of ``fisher_information_marginal`` and ``loo_marginal``: shapes and the degenerate-input rules of
+    ``lnlike_grad`` -> ``(gp, lw, ep, negative)``"""
+    gp = [float(g) for g in gp]
+    lw = np.stack([as_f64(w) for w in np.atleast_2d(lwls)])
+    if len(gp) != 2 * lw.shape[0]:
+        raise ValueError(f"gp must hold {2 * lw.shape[0]} values for {lw.shape[0]} component(s)")
+    ep = np.asarray(epoch_index, dtype=np.int64)
+    if ep.shape != lw.shape[1:] or (ep.size and ep.min() < 0):
+        raise ValueError("epoch_index must hold one non-negative epoch per pixel")
+    negative = any(g < 0.0 for g in gp)
+    if not negative and any(l == 0.0 for l in gp[1::2]):
+        raise ZeroDivisionError("float division")
+    return gp, lw, ep, negative
+
+
+def fisher_information_marginal(lwls, fl, sigma, gp, x, epoch_index, order, prior_sd, weight=None):
+    """``fisher_information`` under the baseline of ``lnlike_marginal``: the ``(2c, 2c)`` Fisher information of the
+    hyper-parameters with ``K + H Lambda H^T`` in the place of ``K`` (``ChunkHandle.fisher_marg`` with unit tangents) -- its
+    inverse is the Laplace covariance of an ``optimize_GP(..., baseline=...)`` fit.  Arguments as ``lnlike_marginal`` (``fl``
+    names the cached chunk and is the weight of a multiplicative baseline); degenerate input as ``fisher_information``."""
+    gp, lw, ep, negative = _marginal_front(lwls, gp, epoch_index)
+    if negative:
+        return np.full((len(gp), len(gp)), np.nan)
+    if not _matrix_is_finite(lw, sigma, gp):
+        raise ValueError(_NONFINITE)
+    h = _chunk_for(fl, sigma)
+    if not hasattr(h, "fisher_marg"):
+        raise _lib.PsoapError("fisher_information_marginal needs the device in this process (PSOAP_GPU_SERVER serves values only)")
+    h.set_baseline(order, x, ep, int(ep.max()) + 1, prior_sd, weight)      # (every call, as ``_marginal``)
+    return h.fisher_marg(lw, gp, np.eye(len(gp)))
+
+
+def loo_marginal(lwls, fl, sigma, gp, x, epoch_index, order, prior_sd, weight=None, mu_GP=1.0):
+    """``loo`` under the baseline of ``lnlike_marginal`` (``ChunkHandle.loo_marg``): a ``chunk.LooResult`` with every pixel and
+    every epoch of ``epoch_index`` predicted from the others under ``K + H Lambda H^T``, ``lnp`` the value of
+    ``lnlike_marginal``.  Arguments as ``lnlike_marginal``; degenerate input as ``loo``."""
+    from .chunk import LooResult
+    gp, lw, ep, negative = _marginal_front(lwls, gp, epoch_index)
+    if negative:
+        return LooResult.degenerate(lw.shape[1], np.bincount(ep))
+    if not _matrix_is_finite(lw, sigma, gp):
+        raise ValueError(_NONFINITE)
+    h = _chunk_for(fl, sigma)
+    if not hasattr(h, "loo_marg"):
+        raise _lib.PsoapError("loo_marginal needs the device in this process (PSOAP_GPU_SERVER serves values only)")
+    h.set_baseline(order, x, ep, int(ep.max()) + 1, prior_sd, weight)      # (every call, as ``_marginal``)
+    res = h.loo_marg(lw, gp, mu_GP, ep)
+    if not np.isneginf(res.lnp) and not (np.all(np.isfinite(np.asarray(fl, dtype=np.float64))) and np.isfinite(mu_GP)):
+        raise ValueError(_NONFINITE)
+    return res
+
+
 def velocity_gradient(grad_lwl, epoch_index, n_epochs):
     """``dlnL/dv[c, e]`` from ``dlnL/dlwl[c, i]``: the rest-frame grids are ``lwl - v[c, epoch]/c_kms``
     (``data.replicate_wls``), so ``dlnL/dv[c, e] = -(1/c_kms) sum_{i in epoch e} dlnL/dlwl[c, i]``.

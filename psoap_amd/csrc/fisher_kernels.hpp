@@ -41,6 +41,27 @@ namespace psoap {
 
 constexpr int FISHER_MAX_T = 32;
 
+// the upper tile (ti, tj) of a symmetric matrix out of the accumulators, and its mirror image (a diagonal tile: its upper
+// half, both ways)
+__device__ __forceinline__ void fisher_kinv_store(const Tile& t, int ti, int tj, int Npad, double* __restrict__ Kinv)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int wr = wave >> 1, wc = wave & 1;
+#pragma unroll
+    for (int m = 0; m < 4; ++m)
+#pragma unroll
+        for (int n = 0; n < 4; ++n)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = tile_row(wr, m, lane, r), col = tile_col(wc, n, lane);
+                if (ti != tj || row <= col) {
+                    const double v = t.acc[m][n][r];
+                    Kinv[(size_t)(NB * ti + row) * Npad + NB * tj + col] = v;
+                    Kinv[(size_t)(NB * tj + col) * Npad + NB * ti + row] = v;
+                }
+            }
+}
+
 // K^-1 = W^T W.  grid P (P + 1) / 2: the upper tile (ti, tj) and its mirror image
 __global__ __launch_bounds__(GEMM_THREADS, 2) void k_fisher_kinv(const double* __restrict__ A, int ld, int Npad, int P,
                                                                 double* __restrict__ Kinv)
@@ -51,21 +72,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void k_fisher_kinv(const double* _
     Tile t;
     t.zero();
     tile_gemm_tn(t, W + NB * ti, (size_t)ld, W + NB * tj, (size_t)ld, Npad - NB * tj);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int wr = wave >> 1, wc = wave & 1;
-#pragma unroll
-    for (int m = 0; m < 4; ++m)
-#pragma unroll
-        for (int n = 0; n < 4; ++n)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = tile_row(wr, m, lane, r), col = tile_col(wc, n, lane);
-                if (ti != tj || row <= col) {      // a diagonal tile: its upper half, both ways
-                    const double v = t.acc[m][n][r];
-                    Kinv[(size_t)(NB * ti + row) * Npad + NB * tj + col] = v;
-                    Kinv[(size_t)(NB * tj + col) * Npad + NB * ti + row] = v;
-                }
-            }
+    fisher_kinv_store(t, ti, tj, Npad, Kinv);
 }
 
 // K_t, every tile (grid P P), in the layout of k_fill_sym: wave w owns the 32-column block w, a lane four rows x two columns
@@ -375,6 +382,7 @@ inline hipError_t fisher_configure_kernels()
 // the Fisher workspace of a chunk handle (grow-only; psoap_chunk_fisher_release frees it)
 struct FisherWs {
     Grow<double> Kinv, Kt, Z, TanX, TanGp, Part, GGp, GX, Y, Mu, F;
+    Grow<double> V;      // Vt 1 of the marginal form (marg_fisher_kernels.hpp)
     Grow<MatAcc> Info;
 };
 

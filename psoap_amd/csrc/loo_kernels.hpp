@@ -35,21 +35,15 @@ namespace psoap {
 constexpr double LOO_HALF_LOG_2PI = 0.91893853320467274178;
 constexpr int LOO_CHUNK = 2048;      // doubles a sequential sum walks out of LDS at a time
 
-__global__ __launch_bounds__(GEMM_THREADS, 2) void k_loo_band(const double* __restrict__ A, int ld, int N, int Npad,
-                                                             const LooTile* __restrict__ tiles,
-                                                             const int* __restrict__ pixel_block,
-                                                             const LooBlock* __restrict__ blocks, double* __restrict__ Blk)
+// The epilogue of a band tile (ti <= tj) of a symmetric A held in the accumulators: every element whose row and column lie
+// in the same epoch, and its mirror image, into that epoch's packed block.  All 256 threads; LDS: the operand buffers.
+__device__ __forceinline__ void loo_band_scatter(const Tile& t, int ti, int tj, int N, const int* __restrict__ pixel_block,
+                                                 const LooBlock* __restrict__ blocks, double* __restrict__ Blk)
 {
     constexpr int OF = 0;                 // [NB] long long: per column of the tile, the first double of its packed block
     constexpr int IX = NB;                // then, as ints: [2][NB] the pixel's block (rows, columns), [2][NB] its position in it,
                                           // [NB] the side of the column's block
     static_assert((IX + 3 * NB) * sizeof(double) <= GEMM_LDS_BYTES, "the epilogue fits the operand buffers");
-    const int ti = tiles[blockIdx.x].ti, tj = tiles[blockIdx.x].tj;
-    const double* W = A + Npad + (size_t)NB * tj * ld;
-    Tile t;
-    t.zero();
-    tile_gemm_tn(t, W + NB * ti, (size_t)ld, W + NB * tj, (size_t)ld, Npad - NB * tj, ti == tj);
-
     // (the thread id passes through an opaque statement: nothing of the epilogue is computed, loaded and kept in registers
     // ahead of the K-loop)
     int tid = threadIdx.x;
@@ -92,6 +86,19 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void k_loo_band(const double* __re
                 }
             }
     }
+}
+
+__global__ __launch_bounds__(GEMM_THREADS, 2) void k_loo_band(const double* __restrict__ A, int ld, int N, int Npad,
+                                                             const LooTile* __restrict__ tiles,
+                                                             const int* __restrict__ pixel_block,
+                                                             const LooBlock* __restrict__ blocks, double* __restrict__ Blk)
+{
+    const int ti = tiles[blockIdx.x].ti, tj = tiles[blockIdx.x].tj;
+    const double* W = A + Npad + (size_t)NB * tj * ld;
+    Tile t;
+    t.zero();
+    tile_gemm_tn(t, W + NB * ti, (size_t)ld, W + NB * tj, (size_t)ld, Npad - NB * tj, ti == tj);
+    loo_band_scatter(t, ti, tj, N, pixel_block, blocks, Blk);
 }
 
 // ones on the padding diagonal of every packed block.  grid n_blocks, 128 threads

@@ -36,6 +36,7 @@
 #include "loo_kernels.hpp"
 #include "marg_kernels.hpp"
 #include "marg_grad_kernels.hpp"
+#include "marg_fisher_kernels.hpp"
 #include "abi_error.hpp"
 #include "plan_abi.hpp"
 #include "share.hpp"
@@ -307,6 +308,7 @@ static int configure_kernels(int device)
     HIP_TRY(loo_configure_kernels());
     HIP_TRY(marg_configure_kernels());
     HIP_TRY(marg_grad_configure_kernels());
+    HIP_TRY(marg_fisher_configure_kernels());
     if (done.size() <= (size_t)device) done.resize((size_t)device + 1, 0);
     done[device] = 1;
     return 0;
@@ -2337,27 +2339,48 @@ extern "C" int psoap_chunk_grad_release(psoap_chunk* h)
     return release_ws(h, [&] { h->gws.reset(); });
 }
 
+// What the marginal gradient, the marginal Fisher information and the marginal leave-one-out share: the dimensions of a call,
+// its workspace and its factorisation.
+struct MargGradDims {
+    MargGradPlan gpl;
+    int S, ld, ldm, ldh, G, nslab, ngram;
+    size_t mstride, m_stride, wstride;
+};
+
+static MargGradDims marg_grad_dims(const psoap_chunk* h, int B);
+static int marg_grad_ws_need(psoap_chunk* h, const MargGradDims& d, hipStream_t s, bool contract, int c = 0, int np = 0);
+static int marg_grad_factor(psoap_chunk* h, const MargGradDims& d, hipStream_t s, int nb, int c, double mu_GP);
+
 // ---- Fisher information of the likelihood (fisher_kernels.hpp) --------------------------------------
 // One matrix through the gradient's workspace and factorisation, then K^-1 and, tangent after tangent, K_t, Z = K_t K^-1
 // and the contraction of G_t = 1/2 (K^-1 Z + Z^T K^-1) -- on the handle's first stream behind whatever the handle has in flight; neither
 // the proposal slots nor the workspaces of the likelihood paths are touched.
-extern "C" int psoap_chunk_fisher(psoap_chunk* h, int c, const double* lwl, const double* gp, int T, const double* tan_lwl,
-                                  const double* tan_gp, double* fisher, double* fisher_mu)
+// `marg`: under Kt = K + Ht Ht^T (marg_fisher_kernels.hpp) -- the factorisation is the marginal gradient's for one matrix
+// and k_marg_fisher_kinv forms Kt^-1 where k_fisher_kinv forms K^-1; everything per tangent is the same launch.
+static int fisher_run(psoap_chunk* h, const char* who, bool marg, int c, const double* lwl, const double* gp, int T,
+                      const double* tan_lwl, const double* tan_gp, double* fisher, double* fisher_mu)
 {
-    if (!h || !lwl || !gp || !tan_gp || !fisher) FAIL("psoap_chunk_fisher: bad arguments");
+    if (!h || !lwl || !gp || !tan_gp || !fisher) FAIL(std::string(who) + ": bad arguments");
     if (c < 1 || c > 3) FAIL("number of components must be 1, 2 or 3");
-    if (T < 1 || T > FISHER_MAX_T) FAIL("psoap_chunk_fisher: the number of tangents must be between 1 and 32");
-    if (h->stream.open) FAIL("psoap_chunk_fisher: the handle has an open stream (psoap_stream_close first)");
+    if (T < 1 || T > FISHER_MAX_T) FAIL(std::string(who) + ": the number of tangents must be between 1 and 32");
+    if (h->stream.open) FAIL(std::string(who) + ": the handle has an open stream (psoap_stream_close first)");
+    if (marg)
+        if (const char* why = marg_grad_check(1, c, h->marg.valid, h->marg.stale_weight)) FAIL(std::string(who) + ": " + why);
     DEVICE_SCOPE(h->device);
     if (int rc = enter_device(h->device)) return rc;
-    const int N = h->N, Npad = h->Npad, P = h->P, ld = 2 * h->Npad;
+    hipStream_t s = h->streams[0];
+    const MargGradDims md = marg ? marg_grad_dims(h, 1) : MargGradDims();
+    const int N = h->N, Npad = h->Npad, P = h->P, ld = marg ? md.ld : 2 * h->Npad;
     const size_t mstride = (size_t)Npad * ld, sq = (size_t)Npad * Npad, CN = (size_t)c * N;
     const int ntiles = P * (P + 1) / 2;
     if (!h->gws) h->gws.reset(new GradWs());
     if (!h->fws) h->fws.reset(new FisherWs());
+    if (marg) {
+        if (int rc = marg_grad_ws_need(h, md, s, false)) return rc;
+    } else if (int rc = grad_ws_need(h, *h->gws, 1, mstride, false, false)) return rc;
     GradWs& w = *h->gws;
     FisherWs& f = *h->fws;
-    if (int rc = grad_ws_need(h, w, 1, mstride, false, false)) return rc;
+    if (marg) HIP_TRY(f.V.need(md.S));
     HIP_TRY(f.Kinv.need(sq));
     HIP_TRY(f.Kt.need(sq));
     HIP_TRY(f.Z.need(sq));
@@ -2370,24 +2393,34 @@ extern "C" int psoap_chunk_fisher(psoap_chunk* h, int c, const double* lwl, cons
     HIP_TRY(f.Mu.need(2));
     HIP_TRY(f.F.need((size_t)T * T));
     HIP_TRY(f.Info.need(1));
-    hipStream_t s = h->streams[0];
     h->recs.clear();
     HIP_TRY(hipMemcpyAsync(w.Lwl, lwl, sizeof(double) * CN, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(w.Gp, gp, sizeof(double) * 2 * c, hipMemcpyHostToDevice, s));
     if (tan_lwl) HIP_TRY(hipMemcpyAsync(f.TanX, tan_lwl, sizeof(double) * (size_t)T * CN, hipMemcpyHostToDevice, s));
     else HIP_TRY(hipMemsetAsync(f.TanX, 0, sizeof(double) * (size_t)T * CN, s));
     HIP_TRY(hipMemcpyAsync(f.TanGp, tan_gp, sizeof(double) * (size_t)T * 2 * c, hipMemcpyHostToDevice, s));
-    if (int rc = grad_factor(h, w, s, 1, c, 0.0)) return rc;      // (F does not depend on the data: any mu_GP)
+    // (F does not depend on the data: any mu_GP)
+    if (int rc = marg ? marg_grad_factor(h, md, s, 1, c, 0.0) : grad_factor(h, w, s, 1, c, 0.0)) return rc;
     double kunits = 0.0;
-    for (int tj = 0; tj < P; ++tj) kunits += (double)(tj + 1) * (P - tj);
+    for (int tj = 0; tj < P; ++tj) kunits += (double)(tj + 1) * (P - tj + (marg ? h->marg.plan.Q : 0));
     if (int rc = prof_launch(h, s, PSOAP_K_GRAD, TILE_FLOPS * kunits, 0.0, [&] {
-            hipLaunchKernelGGL(k_fisher_kinv, dim3(ntiles), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)w.A.p, ld, Npad, P,
-                               f.Kinv.p);
+            if (marg)
+                hipLaunchKernelGGL(k_marg_fisher_kinv, dim3(ntiles), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)w.A.p, ld,
+                                   Npad, P, (const double*)h->mgws->Mx.p, md.ldm, md.S, f.Kinv.p);
+            else
+                hipLaunchKernelGGL(k_fisher_kinv, dim3(ntiles), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)w.A.p, ld, Npad,
+                                   P, f.Kinv.p);
         })) return rc;
     if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
             hipLaunchKernelGGL(k_acc_total, dim3(1), dim3(1), 0, s, (const MatAcc*)w.Acc.p, P, f.Info.p);
             hipLaunchKernelGGL(k_fisher_w1, dim3(N), dim3(256), 0, s, (const double*)w.A.p, ld, Npad, N, f.Y.p);
-            hipLaunchKernelGGL(k_fisher_mu, dim3(1), dim3(256), 0, s, (const double*)f.Y.p, N, f.Mu.p);
+            if (marg) {
+                hipLaunchKernelGGL(k_marg_fisher_v1, dim3(md.S), dim3(256), 0, s, (const double*)h->mgws->Mx.p, md.ldm, md.S, N,
+                                   f.V.p);
+                hipLaunchKernelGGL(k_marg_fisher_mu, dim3(1), dim3(256), 0, s, (const double*)f.Y.p, N, (const double*)f.V.p, md.S,
+                                   f.Mu.p);
+            } else
+                hipLaunchKernelGGL(k_fisher_mu, dim3(1), dim3(256), 0, s, (const double*)f.Y.p, N, f.Mu.p);
         })) return rc;
     for (int t = 0; t < T; ++t) {
         if (int rc = prof_launch(h, s, PSOAP_K_FILL, 0.0, 8.0 * (double)sq, [&] {
@@ -2418,17 +2451,33 @@ extern "C" int psoap_chunk_fisher(psoap_chunk* h, int c, const double* lwl, cons
                                (const double*)f.GX.p, (const double*)f.GGp.p, c, N, T, f.F.p);
         })) return rc;
     MatAcc info;
+    double value = 0.0;      // (marg: -inf also when M does not factor)
+    if (marg) HIP_TRY(hipMemcpyAsync(&value, h->mws->Out, sizeof(double), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(fisher, f.F, sizeof(double) * (size_t)T * T, hipMemcpyDeviceToHost, s));
     if (fisher_mu) HIP_TRY(hipMemcpyAsync(fisher_mu, f.Mu, sizeof(double), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(&info, f.Info, sizeof info, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     if (collect_timings(h)) return 1;
     // the conventions of the likelihood: a negative hyper-parameter or a matrix that is not positive definite -> no information
-    if (info.info != 0.0 || proposal_refused(gp, c, 0)) {
+    if (info.info != 0.0 || value == -INFINITY || proposal_refused(gp, c, 0)) {
         for (size_t k = 0; k < (size_t)T * T; ++k) fisher[k] = NAN;
         if (fisher_mu) *fisher_mu = NAN;
     }
     return 0;
+}
+
+extern "C" int psoap_chunk_fisher(psoap_chunk* h, int c, const double* lwl, const double* gp, int T, const double* tan_lwl,
+                                  const double* tan_gp, double* fisher, double* fisher_mu)
+{
+    return fisher_run(h, "psoap_chunk_fisher", false, c, lwl, gp, T, tan_lwl, tan_gp, fisher, fisher_mu);
+}
+
+// under the baseline of psoap_chunk_set_baseline (marg_fisher_kernels.hpp); the workspaces are the plain entry's and the
+// marginal gradient's
+extern "C" int psoap_chunk_fisher_marg(psoap_chunk* h, int c, const double* lwl, const double* gp, int T, const double* tan_lwl,
+                                       const double* tan_gp, double* fisher, double* fisher_mu)
+{
+    return fisher_run(h, "psoap_chunk_fisher_marg", true, c, lwl, gp, T, tan_lwl, tan_gp, fisher, fisher_mu);
 }
 
 extern "C" int psoap_chunk_fisher_release(psoap_chunk* h)
@@ -2441,27 +2490,35 @@ extern "C" int psoap_chunk_fisher_release(psoap_chunk* h)
 // the packed epoch blocks, their staged factorisation group after group of equal side, and the finishing kernel -- on the
 // handle's first stream behind whatever the handle has in flight; neither the proposal slots nor the workspaces of the
 // likelihood paths are touched.
-extern "C" int psoap_chunk_loo(psoap_chunk* h, int c, const double* lwl, const double* gp, double mu_GP, const int32_t* epoch,
-                               int n_epochs, double* lnp, double* loo_logp, double* pix_mean, double* pix_var, double* pix_logp,
-                               double* ep_resid, double* ep_chi2, double* ep_logp, int32_t* ep_npix)
+// `marg`: under Kt = K + Ht Ht^T (marg_fisher_kernels.hpp) -- the factorisation, the value and alpha_m are the marginal
+// gradient's for one matrix and k_marg_loo_band scatters the band of Kt^-1 where k_loo_band scatters that of K^-1.
+static int loo_run(psoap_chunk* h, const char* who, bool marg, int c, const double* lwl, const double* gp, double mu_GP,
+                   const int32_t* epoch, int n_epochs, double* lnp, double* loo_logp, double* pix_mean, double* pix_var,
+                   double* pix_logp, double* ep_resid, double* ep_chi2, double* ep_logp, int32_t* ep_npix)
 {
-    if (!h || !lwl || !gp) FAIL("psoap_chunk_loo: bad arguments");
+    if (!h || !lwl || !gp) FAIL(std::string(who) + ": bad arguments");
     if (c < 1 || c > 3) FAIL("number of components must be 1, 2 or 3");
-    if (epoch && n_epochs < 1) FAIL("psoap_chunk_loo: n_epochs must be at least 1");
-    if (h->stream.open) FAIL("psoap_chunk_loo: the handle has an open stream (psoap_stream_close first)");
-    const int N = h->N, Npad = h->Npad, P = h->P, ld = 2 * h->Npad;
+    if (epoch && n_epochs < 1) FAIL(std::string(who) + ": n_epochs must be at least 1");
+    if (h->stream.open) FAIL(std::string(who) + ": the handle has an open stream (psoap_stream_close first)");
+    if (marg)
+        if (const char* why = marg_grad_check(1, c, h->marg.valid, h->marg.stale_weight)) FAIL(std::string(who) + ": " + why);
+    const MargGradDims md = marg ? marg_grad_dims(h, 1) : MargGradDims();
+    const int N = h->N, Npad = h->Npad, P = h->P, ld = marg ? md.ld : 2 * h->Npad;
     LooLayout lay;
-    if (const char* why = loo_layout(epoch, N, n_epochs, lay)) FAIL(std::string("psoap_chunk_loo: ") + why);
+    if (const char* why = loo_layout(epoch, N, n_epochs, lay)) FAIL(std::string(who) + ": " + why);
     const int ne = epoch ? n_epochs : 0, nblk = (int)lay.blocks.size(), ntile = (int)lay.tiles.size();
     if (!epoch) ep_resid = ep_chi2 = ep_logp = nullptr, ep_npix = nullptr;
     DEVICE_SCOPE(h->device);
     if (int rc = enter_device(h->device)) return rc;
     const size_t mstride = (size_t)Npad * ld, CN = (size_t)c * N;
+    hipStream_t s = h->streams[0];
     if (!h->gws) h->gws.reset(new GradWs());
     if (!h->lws) h->lws.reset(new LooWs());
+    if (marg) {
+        if (int rc = marg_grad_ws_need(h, md, s, false)) return rc;
+    } else if (int rc = grad_ws_need(h, *h->gws, 1, mstride, true, false)) return rc;
     GradWs& w = *h->gws;
     LooWs& l = *h->lws;
-    if (int rc = grad_ws_need(h, w, 1, mstride, true, false)) return rc;
     HIP_TRY(w.Out.need(1));
     HIP_TRY(l.Blk.need((size_t)lay.block_doubles));
     HIP_TRY(l.Rhs.need((size_t)lay.rhs_doubles));
@@ -2478,7 +2535,6 @@ extern "C" int psoap_chunk_loo(psoap_chunk* h, int c, const double* lwl, const d
     HIP_TRY(l.Tiles.need(ntile));
     HIP_TRY(l.PixBlock.need(N));
     HIP_TRY(l.EpBlock.need(lay.epoch_block.size()));
-    hipStream_t s = h->streams[0];
     h->recs.clear();
     HIP_TRY(hipMemcpyAsync(w.Lwl, lwl, sizeof(double) * CN, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(w.Gp, gp, sizeof(double) * 2 * c, hipMemcpyHostToDevice, s));
@@ -2487,18 +2543,25 @@ extern "C" int psoap_chunk_loo(psoap_chunk* h, int c, const double* lwl, const d
     HIP_TRY(hipMemcpyAsync(l.PixBlock, lay.pixel_block.data(), sizeof(int) * (size_t)N, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(l.EpBlock, lay.epoch_block.data(), sizeof(int) * lay.epoch_block.size(), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemsetAsync(l.Blk, 0, sizeof(double) * (size_t)lay.block_doubles, s));
-    // the value and alpha exactly as psoap_chunk_lnlike_grad makes them for one matrix
-    if (int rc = grad_factor(h, w, s, 1, c, mu_GP)) return rc;
+    // the value and alpha exactly as psoap_chunk_lnlike_grad (marg: psoap_chunk_lnlike_marg_grad) makes them for one matrix
+    if (int rc = marg ? marg_grad_factor(h, md, s, 1, c, mu_GP) : grad_factor(h, w, s, 1, c, mu_GP)) return rc;
     if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
-            hipLaunchKernelGGL(k_finalize, dim3(1), dim3(64), 0, s, (const MatAcc*)w.Acc.p, w.Out.p, 1, (const int*)nullptr, P);
-            launch_alpha(w, s, 1, mstride, ld, Npad, P, w.R.p);
+            if (!marg) {
+                hipLaunchKernelGGL(k_finalize, dim3(1), dim3(64), 0, s, (const MatAcc*)w.Acc.p, w.Out.p, 1, (const int*)nullptr, P);
+                launch_alpha(w, s, 1, mstride, ld, Npad, P, w.R.p);
+            }
             hipLaunchKernelGGL(k_loo_pad, dim3(nblk), dim3(128), 0, s, (const LooBlock*)l.Blocks.p, l.Blk.p);
         })) return rc;
     double bunits = 0.0;      // executed 128^3 products of the band: a diagonal tile issues three quarters of its MFMAs
-    for (const LooTile& t : lay.tiles) bunits += (t.ti == t.tj ? 0.75 : 1.0) * (P - t.tj);
+    for (const LooTile& t : lay.tiles) bunits += (t.ti == t.tj ? 0.75 : 1.0) * (P - t.tj + (marg ? h->marg.plan.Q : 0));
     if (int rc = prof_launch(h, s, PSOAP_K_GRAD, TILE_FLOPS * bunits, 0.0, [&] {
-            hipLaunchKernelGGL(k_loo_band, dim3(ntile), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)w.A.p, ld, N, Npad,
-                               (const LooTile*)l.Tiles.p, (const int*)l.PixBlock.p, (const LooBlock*)l.Blocks.p, l.Blk.p);
+            if (marg)
+                hipLaunchKernelGGL(k_marg_loo_band, dim3(ntile), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)w.A.p, ld, N,
+                                   Npad, (const double*)h->mgws->Mx.p, md.ldm, md.S, (const LooTile*)l.Tiles.p,
+                                   (const int*)l.PixBlock.p, (const LooBlock*)l.Blocks.p, l.Blk.p);
+            else
+                hipLaunchKernelGGL(k_loo_band, dim3(ntile), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)w.A.p, ld, N, Npad,
+                                   (const LooTile*)l.Tiles.p, (const int*)l.PixBlock.p, (const LooBlock*)l.Blocks.p, l.Blk.p);
         })) return rc;
     if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
             hipLaunchKernelGGL(k_loo_rhs, dim3(nblk), dim3(256), 0, s, (const LooBlock*)l.Blocks.p, (const double*)l.Blk.p,
@@ -2527,7 +2590,7 @@ extern "C" int psoap_chunk_loo(psoap_chunk* h, int c, const double* lwl, const d
                                l.Pix.p + 2 * (size_t)N, l.EpResid.p, l.EpOut.p, l.EpOut.p + (ne + 1), l.EpNpix.p, l.Logp.p);
         })) return rc;
     double value = 0.0;
-    HIP_TRY(hipMemcpyAsync(&value, w.Out, sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&value, marg ? h->mws->Out.p : w.Out.p, sizeof(double), hipMemcpyDeviceToHost, s));
     if (loo_logp) HIP_TRY(hipMemcpyAsync(loo_logp, l.Logp, sizeof(double), hipMemcpyDeviceToHost, s));
     if (pix_mean) HIP_TRY(hipMemcpyAsync(pix_mean, l.Pix, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost, s));
     if (pix_var) HIP_TRY(hipMemcpyAsync(pix_var, l.Pix.p + N, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost, s));
@@ -2552,6 +2615,24 @@ extern "C" int psoap_chunk_loo(psoap_chunk* h, int c, const double* lwl, const d
                 for (int e = 0; e < ne; ++e) v[e] = NAN;
     }
     return 0;
+}
+
+extern "C" int psoap_chunk_loo(psoap_chunk* h, int c, const double* lwl, const double* gp, double mu_GP, const int32_t* epoch,
+                               int n_epochs, double* lnp, double* loo_logp, double* pix_mean, double* pix_var, double* pix_logp,
+                               double* ep_resid, double* ep_chi2, double* ep_logp, int32_t* ep_npix)
+{
+    return loo_run(h, "psoap_chunk_loo", false, c, lwl, gp, mu_GP, epoch, n_epochs, lnp, loo_logp, pix_mean, pix_var, pix_logp,
+                   ep_resid, ep_chi2, ep_logp, ep_npix);
+}
+
+// under the baseline of psoap_chunk_set_baseline (marg_fisher_kernels.hpp); `epoch` is the index of the outputs and need not
+// be the baseline's
+extern "C" int psoap_chunk_loo_marg(psoap_chunk* h, int c, const double* lwl, const double* gp, double mu_GP, const int32_t* epoch,
+                                    int n_epochs, double* lnp, double* loo_logp, double* pix_mean, double* pix_var,
+                                    double* pix_logp, double* ep_resid, double* ep_chi2, double* ep_logp, int32_t* ep_npix)
+{
+    return loo_run(h, "psoap_chunk_loo_marg", true, c, lwl, gp, mu_GP, epoch, n_epochs, lnp, loo_logp, pix_mean, pix_var,
+                   pix_logp, ep_resid, ep_chi2, ep_logp, ep_npix);
 }
 
 extern "C" int psoap_chunk_loo_release(psoap_chunk* h)
@@ -2762,9 +2843,128 @@ extern "C" int psoap_chunk_lnlike_marg(psoap_chunk* h, int B, int c, const doubl
 }
 
 // ---- gradient of that likelihood (marg_grad_kernels.hpp) -------------------------------------------------
-// Group after group of matrices through the gradient's workspace as [K | I | Ht] (marg_grad_plan.hpp), the Gram matrices
-// through the staged kernels as [M | Xt], then the gradient's own tail -- on the handle's first stream behind whatever the
-// handle has in flight.  The grids come from the host (lwl) or, with lwl == nullptr, from the orbits as in grad_run.
+static MargGradDims marg_grad_dims(const psoap_chunk* h, int B)
+{
+    MargGradDims d;
+    const MargPlan& pl = h->marg.plan;
+    marg_grad_plan(pl, d.gpl);
+    d.S = NB * pl.Q;
+    d.ld = d.gpl.ld;
+    d.ldm = d.S + h->Npad;
+    d.ldh = d.S;
+    d.mstride = marg_grad_matrix_doubles(h->Npad, pl.Q);
+    d.m_stride = (size_t)d.S * d.ldm;
+    d.wstride = (size_t)pl.Q * NB * NB;
+    d.G = marg_grad_group_size(B, h->Npad, pl.Q);
+    d.nslab = (h->Npad + 255) / 256;
+    d.ngram = pl.Q * (pl.Q + 1) / 2;
+    return d;
+}
+
+// the handle's three workspaces sized for groups of d.G matrices (`contract`, c, np: as grad_ws_need), and Ht on the device
+static int marg_grad_ws_need(psoap_chunk* h, const MargGradDims& d, hipStream_t s, bool contract, int c, int np)
+{
+    const int N = h->N, Npad = h->Npad, G = d.G, S = d.S, q = h->marg.plan.q;
+    if (!h->gws) h->gws.reset(new GradWs());
+    if (!h->mws) h->mws.reset(new MargWs());
+    if (!h->mgws) h->mgws.reset(new MargGradWs());
+    MargWs& m = *h->mws;
+    MargGradWs& mg = *h->mgws;
+    if (int rc = grad_ws_need(h, *h->gws, G, d.mstride, true, contract, c, np)) return rc;
+    HIP_TRY(mg.Mx.need((size_t)G * d.m_stride));
+    HIP_TRY(mg.Zt.need((size_t)G * Npad));
+    HIP_TRY(m.WtM.need((size_t)G * d.wstride));
+    HIP_TRY(m.Rhs.need((size_t)G * S));
+    HIP_TRY(m.Gam.need((size_t)G * S));
+    HIP_TRY(m.RPart.need((size_t)G * d.nslab * S));
+    HIP_TRY(m.AccM.need((size_t)G * ACC_ROWS));
+    HIP_TRY(m.Out.need((size_t)G * 5));
+    HIP_TRY(m.Beta.need((size_t)G * q));
+    HIP_TRY(m.Flc.need((size_t)G * N));
+    return marg_basis(h, m, s);
+}
+
+// The staged factorisation of [K | I | Ht] (marg_grad_plan.hpp) and of [M | Xt] for the nb matrices whose grids and
+// hyper-parameters are in w.Lwl and w.Gp.  Afterwards the I block holds Wi = U^-T, the appended block of mg.Mx holds
+// Vt = U_M^-T Wh^T Wi, m.Out the value and its parts with the bits of psoap_chunk_lnlike_marg, mg.Zt = z - Wh g and
+// w.Alpha = alpha_m.
+static int marg_grad_factor(psoap_chunk* h, const MargGradDims& d, hipStream_t s, int nb, int c, double mu_GP)
+{
+    GradWs& w = *h->gws;
+    MargWs& m = *h->mws;
+    MargGradWs& mg = *h->mgws;
+    const MargPlan& pl = h->marg.plan;
+    const MargGradPlan& gpl = d.gpl;
+    const int N = h->N, Npad = h->Npad, P = h->P, Q = pl.Q, q = pl.q, order = pl.order;
+    const int S = d.S, ld = d.ld, ldm = d.ldm, ldh = d.ldh, nslab = d.nslab, ngram = d.ngram, ntiles = P * (P + 1) / 2;
+    const size_t mstride = d.mstride, m_stride = d.m_stride, wstride = d.wstride;
+    const int* tab = m.Tab.p;
+    double* Ah = w.A.p + Npad;          // what the kernels of marg_kernels.hpp take for [K | Ht]: Ht one block further right
+    if (int rc = prof_launch(h, s, PSOAP_K_FILL, 0.0, (double)nb * 12.0 * N * (N + 1.0), [&] {
+            launch_grad_fill(h, w, s, nb, c, mstride, ld);
+            hipLaunchKernelGGL(k_grad_init, dim3(ntiles, nb), dim3(256), 0, s, w.A.p, mstride, ld, Npad, P);
+            hipLaunchKernelGGL(k_marg_load, dim3(Q * P, nb), dim3(256), 0, s, Ah, mstride, ld, Npad, P, (const double*)m.Ht.p, ldh,
+                               tab);
+        })) return rc;
+    if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
+            hipLaunchKernelGGL(k_init_rhs, dim3((Npad + 255) / 256, nb), dim3(256), 0, s, w.R.p, Npad, N, h->dFl, mu_GP, w.Acc.p);
+        })) return rc;
+    // block row p: the rest of K's row with I_0 .. I_p, and the slots of Ht whose first non-zero block row is <= p
+    for (int p = 0; p < P; ++p) {
+        const int k0 = p * NB;
+        const MargGradRow& row = gpl.rows[(size_t)p];
+        const double units = (double)p * (P - p) + 0.5 * p * (p + 1.0) + (double)p * row.update_h;
+        auto update = [&] {
+            hipLaunchKernelGGL(k_marg_grad_panel_update, dim3(row.update_k + row.update_h, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES,
+                               s, w.A.p, mstride, ld, k0, P, tab);
+        };
+        // the slots of Ht are a second strip: its first tile column moved onto tile column 2 P, and no right-hand side
+        // (r_rows = 0: every column counts as appended, r is only read)
+        StagedRow sr = grad_row(w, mstride, ld, Npad, row.strip_k);
+        sr.A2 = w.A.p + (NB * gpl.tile_H - k0 - NB);
+        sr.strip2 = row.strip_h;
+        if (int rc = staged_row(h, s, sr, nb, k0, row.update_k + row.update_h > 0 ? &update : nullptr, TILE_FLOPS * units * nb))
+            return rc;
+    }
+    if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
+            hipLaunchKernelGGL(k_marg_rhs_partial, dim3(Q, nslab, nb), dim3(256), 0, s, (const double*)Ah, mstride, ld, Npad, Q, tab,
+                               (const double*)w.R.p, m.RPart.p, nslab);
+            hipLaunchKernelGGL(k_marg_rhs_finish, dim3((S + 255) / 256, nb), dim3(256), 0, s, (const double*)m.RPart.p, nslab, Npad,
+                               Q, tab, m.Rhs.p);
+        })) return rc;
+    double gunits = 0.0;
+    for (const MargTile& t : pl.tiles) gunits += (t.ti == t.tj ? 0.75 : 1.0) * (Npad - t.k0) / NB;
+    for (int sl = 0; sl < Q; ++sl)
+        for (int tj = 0; tj < P; ++tj) gunits += P - std::min(P, std::max(pl.first[(size_t)pl.column[(size_t)sl]], tj));
+    if (int rc = prof_launch(h, s, PSOAP_K_GRAD, TILE_FLOPS * gunits * nb, 0.0, [&] {
+            hipLaunchKernelGGL(k_marg_gram, dim3(ngram, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)Ah, mstride, ld,
+                               Npad, (const MargTile*)m.Tiles.p, mg.Mx.p, m_stride, ldm);
+            hipLaunchKernelGGL(k_marg_grad_cross, dim3(Q * P, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)w.A.p,
+                               mstride, ld, Npad, P, Q, tab, mg.Mx.p, m_stride, ldm);
+        })) return rc;
+    // [M | Xt]: M = U_M^T U_M with bt alongside, and the appended block becomes Vt = U_M^-T Xt
+    for (int p = 0; p < Q; ++p) {
+        const int k0 = p * NB;
+        const StagedRow mrow{mg.Mx.p, m_stride, ldm, m.Rhs.p, S, m.AccM.p, m.WtM.p + (size_t)p * NB * NB, wstride, Q - p - 1 + P};
+        auto update = [&] {
+            hipLaunchKernelGGL(k_panel_update, dim3(Q - p + P, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, mg.Mx.p, m_stride, ldm, k0);
+        };
+        if (int rc = staged_row(h, s, mrow, nb, k0, p > 0 ? &update : nullptr, TILE_FLOPS * p * (Q - p + P) * nb)) return rc;
+    }
+    // lnL and g = U_M^-1 y; z - Wh g; alpha_m
+    return prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
+        hipLaunchKernelGGL(k_marg_finish, dim3(nb), dim3(256), 0, s, N, P, Q, q, order, (const MatAcc*)w.Acc.p,
+                           (const MatAcc*)m.AccM.p, (const double*)mg.Mx.p, m_stride, ldm, (const double*)m.WtM.p,
+                           (const double*)m.Rhs.p, m.Gam.p, (const double*)m.Sd.p, (const int*)m.Epoch.p, tab,
+                           (const double*)m.Ht.p, ldh, (const double*)h->dFl.p, m.Out.p, m.Beta.p, m.Flc.p, 1);
+        hipLaunchKernelGGL(k_marg_grad_resid, dim3(Npad / 4, nb), dim3(256), 0, s, (const double*)w.A.p, mstride, ld, Npad, Q,
+                           tab, (const double*)w.R.p, (const double*)m.Gam.p, mg.Zt.p);
+        launch_alpha(w, s, nb, mstride, ld, Npad, P, mg.Zt.p);
+    });
+}
+
+// Group after group of matrices through marg_grad_factor, then the gradient's own tail -- on the handle's first stream behind
+// whatever the handle has in flight.  The grids come from the host (lwl) or, with lwl == nullptr, from the orbits as in grad_run.
 static int marg_grad_run(psoap_chunk* h, const char* who, int B, int c, const double* lwl, int model, const double* p_orb,
                          const double* gp, double mu_GP, double* lnp, double* parts, double* grad_gp, double* grad_lwl,
                          double* grad_mu, double* grad_orb, double* grad_vel)
@@ -2773,41 +2973,22 @@ static int marg_grad_run(psoap_chunk* h, const char* who, int B, int c, const do
     const bool orbits = lwl == nullptr;
     DEVICE_SCOPE(h->device);
     if (int rc = enter_device(h->device)) return rc;
-    const MargPlan& pl = h->marg.plan;
-    MargGradPlan gpl;
-    marg_grad_plan(pl, gpl);
-    const int N = h->N, Npad = h->Npad, P = h->P, Q = pl.Q, q = pl.q, order = pl.order;
-    const int S = NB * Q, ld = gpl.ld, ldm = S + Npad, ldh = S;
-    const size_t mstride = marg_grad_matrix_doubles(Npad, Q), m_stride = (size_t)S * ldm, wstride = (size_t)Q * NB * NB;
-    const int G = marg_grad_group_size(B, Npad, Q);
-    const int ntiles = P * (P + 1) / 2, nslab = (Npad + 255) / 256, ngram = Q * (Q + 1) / 2;
-    if (!h->gws) h->gws.reset(new GradWs());
-    if (!h->mws) h->mws.reset(new MargWs());
-    if (!h->mgws) h->mgws.reset(new MargGradWs());
+    const MargGradDims d = marg_grad_dims(h, B);
+    const int N = h->N, Npad = h->Npad, P = h->P, Q = h->marg.plan.Q;
+    const int S = d.S, ld = d.ld, ldm = d.ldm, G = d.G;
+    const size_t mstride = d.mstride, m_stride = d.m_stride;
+    const int ntiles = P * (P + 1) / 2;
+    const int ne = h->n_epochs, np = orbits ? orbit_n_params(model) : 0;
+    hipStream_t s = h->streams[0];
+    if (int rc = marg_grad_ws_need(h, d, s, true, c, np)) return rc;
     GradWs& w = *h->gws;
     MargWs& m = *h->mws;
     MargGradWs& mg = *h->mgws;
-    const int ne = h->n_epochs, np = orbits ? orbit_n_params(model) : 0;
-    if (int rc = grad_ws_need(h, w, G, mstride, true, true, c, np)) return rc;
-    HIP_TRY(mg.Mx.need((size_t)G * m_stride));
-    HIP_TRY(mg.Zt.need((size_t)G * Npad));
-    HIP_TRY(m.WtM.need((size_t)G * wstride));
-    HIP_TRY(m.Rhs.need((size_t)G * S));
-    HIP_TRY(m.Gam.need((size_t)G * S));
-    HIP_TRY(m.RPart.need((size_t)G * nslab * S));
-    HIP_TRY(m.AccM.need((size_t)G * ACC_ROWS));
-    HIP_TRY(m.Out.need((size_t)G * 5));
-    HIP_TRY(m.Beta.need((size_t)G * q));
-    HIP_TRY(m.Flc.need((size_t)G * N));
-    hipStream_t s = h->streams[0];
-    if (int rc = marg_basis(h, m, s)) return rc;
-    const int* tab = m.Tab.p;
     std::vector<int> fast(orbits ? (size_t)B : 0, 0);
     if (orbits)
         if (int rc = grad_epoch_lists(h, w, s)) return rc;
     h->recs.clear();
     std::vector<double> out((size_t)B * 5);
-    double* Ah = w.A.p + Npad;          // what the kernels of marg_kernels.hpp take for [K | Ht]: Ht one block further right
     for (int b0 = 0; b0 < B; b0 += G) {
         const int nb = (B - b0 < G) ? B - b0 : G;
         if (!orbits)
@@ -2815,67 +2996,7 @@ static int marg_grad_run(psoap_chunk* h, const char* who, int B, int c, const do
         else if (int rc = orbit_front(h, w, s, nb, c, model, np, p_orb + (size_t)b0 * np))
             return rc;
         HIP_TRY(hipMemcpyAsync(w.Gp, gp + (size_t)b0 * 2 * c, sizeof(double) * (size_t)nb * 2 * c, hipMemcpyHostToDevice, s));
-        if (int rc = prof_launch(h, s, PSOAP_K_FILL, 0.0, (double)nb * 12.0 * N * (N + 1.0), [&] {
-                launch_grad_fill(h, w, s, nb, c, mstride, ld);
-                hipLaunchKernelGGL(k_grad_init, dim3(ntiles, nb), dim3(256), 0, s, w.A.p, mstride, ld, Npad, P);
-                hipLaunchKernelGGL(k_marg_load, dim3(Q * P, nb), dim3(256), 0, s, Ah, mstride, ld, Npad, P, (const double*)m.Ht.p, ldh,
-                                   tab);
-            })) return rc;
-        if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
-                hipLaunchKernelGGL(k_init_rhs, dim3((Npad + 255) / 256, nb), dim3(256), 0, s, w.R.p, Npad, N, h->dFl, mu_GP, w.Acc.p);
-            })) return rc;
-        // block row p: the rest of K's row with I_0 .. I_p, and the slots of Ht whose first non-zero block row is <= p
-        for (int p = 0; p < P; ++p) {
-            const int k0 = p * NB;
-            const MargGradRow& row = gpl.rows[(size_t)p];
-            const double units = (double)p * (P - p) + 0.5 * p * (p + 1.0) + (double)p * row.update_h;
-            auto update = [&] {
-                hipLaunchKernelGGL(k_marg_grad_panel_update, dim3(row.update_k + row.update_h, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES,
-                                   s, w.A.p, mstride, ld, k0, P, tab);
-            };
-            // the slots of Ht are a second strip: its first tile column moved onto tile column 2 P, and no right-hand side
-            // (r_rows = 0: every column counts as appended, r is only read)
-            StagedRow sr = grad_row(w, mstride, ld, Npad, row.strip_k);
-            sr.A2 = w.A.p + (NB * gpl.tile_H - k0 - NB);
-            sr.strip2 = row.strip_h;
-            if (int rc = staged_row(h, s, sr, nb, k0, row.update_k + row.update_h > 0 ? &update : nullptr, TILE_FLOPS * units * nb))
-                return rc;
-        }
-        if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
-                hipLaunchKernelGGL(k_marg_rhs_partial, dim3(Q, nslab, nb), dim3(256), 0, s, (const double*)Ah, mstride, ld, Npad, Q, tab,
-                                   (const double*)w.R.p, m.RPart.p, nslab);
-                hipLaunchKernelGGL(k_marg_rhs_finish, dim3((S + 255) / 256, nb), dim3(256), 0, s, (const double*)m.RPart.p, nslab, Npad,
-                                   Q, tab, m.Rhs.p);
-            })) return rc;
-        double gunits = 0.0;
-        for (const MargTile& t : pl.tiles) gunits += (t.ti == t.tj ? 0.75 : 1.0) * (Npad - t.k0) / NB;
-        for (int sl = 0; sl < Q; ++sl)
-            for (int tj = 0; tj < P; ++tj) gunits += P - std::min(P, std::max(pl.first[(size_t)pl.column[(size_t)sl]], tj));
-        if (int rc = prof_launch(h, s, PSOAP_K_GRAD, TILE_FLOPS * gunits * nb, 0.0, [&] {
-                hipLaunchKernelGGL(k_marg_gram, dim3(ngram, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)Ah, mstride, ld,
-                                   Npad, (const MargTile*)m.Tiles.p, mg.Mx.p, m_stride, ldm);
-                hipLaunchKernelGGL(k_marg_grad_cross, dim3(Q * P, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)w.A.p,
-                                   mstride, ld, Npad, P, Q, tab, mg.Mx.p, m_stride, ldm);
-            })) return rc;
-        // [M | Xt]: M = U_M^T U_M with bt alongside, and the appended block becomes Vt = U_M^-T Xt
-        for (int p = 0; p < Q; ++p) {
-            const int k0 = p * NB;
-            const StagedRow mrow{mg.Mx.p, m_stride, ldm, m.Rhs.p, S, m.AccM.p, m.WtM.p + (size_t)p * NB * NB, wstride, Q - p - 1 + P};
-            auto update = [&] {
-                hipLaunchKernelGGL(k_panel_update, dim3(Q - p + P, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, mg.Mx.p, m_stride, ldm, k0);
-            };
-            if (int rc = staged_row(h, s, mrow, nb, k0, p > 0 ? &update : nullptr, TILE_FLOPS * p * (Q - p + P) * nb)) return rc;
-        }
-        // lnL and g = U_M^-1 y; z - Wh g; alpha_m
-        if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
-                hipLaunchKernelGGL(k_marg_finish, dim3(nb), dim3(256), 0, s, N, P, Q, q, order, (const MatAcc*)w.Acc.p,
-                                   (const MatAcc*)m.AccM.p, (const double*)mg.Mx.p, m_stride, ldm, (const double*)m.WtM.p,
-                                   (const double*)m.Rhs.p, m.Gam.p, (const double*)m.Sd.p, (const int*)m.Epoch.p, tab,
-                                   (const double*)m.Ht.p, ldh, (const double*)h->dFl.p, m.Out.p, m.Beta.p, m.Flc.p, 1);
-                hipLaunchKernelGGL(k_marg_grad_resid, dim3(Npad / 4, nb), dim3(256), 0, s, (const double*)w.A.p, mstride, ld, Npad, Q,
-                                   tab, (const double*)w.R.p, (const double*)m.Gam.p, mg.Zt.p);
-                launch_alpha(w, s, nb, mstride, ld, Npad, P, mg.Zt.p);
-            })) return rc;
+        if (int rc = marg_grad_factor(h, d, s, nb, c, mu_GP)) return rc;
         double cunits = 0.0;
         for (int tj = 0; tj < P; ++tj) cunits += (double)(tj + 1) * (P - tj + Q);
         if (int rc = prof_launch(h, s, PSOAP_K_GRAD, TILE_FLOPS * cunits * nb, 0.0, [&] {

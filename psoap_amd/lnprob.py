@@ -26,8 +26,9 @@ class ChunkWorker:
 
         ``baseline = {"order": k, "sd": [s_0 .. s_k], "weight": "one" | "flux"}``: ``lnprob`` and ``lnprob_batch`` evaluate the
         likelihood with a Chebyshev polynomial of degree k per epoch integrated out (``ChunkHandle.lnlike_marg``) -- an
-        additive offset ("one") or the polynomial times the flux ("flux") -- and ``lnprob_grad*`` its gradient
-        (``ChunkHandle.lnprob_marg_grad``).  The split-phase and streamed entries
+        additive offset ("one") or the polynomial times the flux ("flux") -- ``lnprob_grad*`` its gradient
+        (``ChunkHandle.lnprob_marg_grad``), ``fisher*`` its Fisher information (``ChunkHandle.fisher_marg``) and ``loo*`` its
+        leave-one-out cross-validation (``ChunkHandle.loo_marg``).  The split-phase and streamed entries
         (``upload_*``, ``stream_*``) evaluate the plain likelihood and refuse to run on such a worker.  ``None``: every
         path as it was."""
         self.model = model
@@ -187,7 +188,8 @@ class ChunkWorker:
         (``orbit.velocity_jacobian``, which also gives the velocities the grids are shifted by, as ``lnprob`` shifts
         them); the tangents of the GP parameters are unit vectors.  The (T, c, N) tangents are assembled on the host,
         everything of order N^3 runs on the device.  A faster-than-light orbit, a negative hyper-parameter or a matrix
-        that is not positive definite gives NaN in every entry."""
+        that is not positive definite gives NaN in every entry.  On a worker with a baseline the information is that of the
+        marginal likelihood (``ChunkHandle.fisher_marg``): of what ``lnprob`` returns on this worker."""
         if os.environ.get("PSOAP_GPU_SERVER", "").strip().lower() not in ("", "0"):
             raise _lib.PsoapError("fisher needs the device in this process (PSOAP_GPU_SERVER serves values only)")
         from .data import c_kms
@@ -205,6 +207,8 @@ class ChunkWorker:
         tan_lwl[:n_orb] = -np.moveaxis(jac[0], 2, 0)[:, :, ep] / c_kms
         tan_gp = np.zeros((T, 2 * c))
         tan_gp[n_orb:] = np.eye(2 * c)
+        if getattr(self, "baseline", None) is not None:      # (the information of what ``lnprob`` returns on this worker)
+            return self.handle.fisher_marg(lwls, p_gp, tan_gp, tan_lwl)
         return self.handle.fisher(lwls, p_gp, tan_gp, tan_lwl)
 
     def fisher(self, p):
@@ -221,7 +225,9 @@ class ChunkWorker:
         parameters (2c,) -> a ``chunk.LooResult`` with the epoch fields over the worker's own ``epoch_index``.  The
         velocities come from the device (``orbit.velocities``) and the grids are shifted on the host exactly as
         ``fisher_orbits`` shifts them.  A faster-than-light orbit gives ``lnp = -inf`` and NaN, as a negative
-        hyper-parameter or a matrix that is not positive definite does."""
+        hyper-parameter or a matrix that is not positive definite does.  On a worker with a baseline every prediction is made
+        under the marginal likelihood (``ChunkHandle.loo_marg``): an epoch whose only fault is a continuum offset within the
+        prior is not an outlier, and ``lnp`` is what ``lnprob`` returns on this worker."""
         if os.environ.get("PSOAP_GPU_SERVER", "").strip().lower() not in ("", "0"):
             raise _lib.PsoapError("loo needs the device in this process (PSOAP_GPU_SERVER serves values only)")
         from .chunk import LooResult
@@ -235,6 +241,8 @@ class ChunkWorker:
         if np.any(np.abs(vel) >= c_kms):
             return LooResult.degenerate(self.handle.N, np.bincount(ep, minlength=ne))
         lwls = self.lwl[None, :] + (-vel[:, ep]) / c_kms          # (as the device shifts: fill_kernels.hpp)
+        if getattr(self, "baseline", None) is not None:
+            return self.handle.loo_marg(lwls, p_gp, mu_GP, ep, ne)
         return self.handle.loo(lwls, p_gp, mu_GP, ep, ne)
 
     def loo(self, p, mu_GP: float = 1.0):
@@ -281,7 +289,8 @@ def loo_outliers(workers, p, pix_sigma=5.0, epoch_p=1e-4, mu_GP=1.0):
     """What disagrees with the fitted model at ``p``, per chunk: a list, in the order of ``workers``, of dicts with
     ``pixels`` (indices with ``|pix_z| > pix_sigma``), ``epochs`` (ids whose ``ep_chi2`` has an upper-tail chi-squared
     probability below ``epoch_p`` at ``ep_npix`` degrees of freedom, ``scipy.stats.chi2.sf``), the probabilities ``epoch_sf``
-    of every epoch and the ``LooResult`` itself (``loo``).  The two defaults are conventions, not measurements: 5 sigma per
+    of every epoch and the ``LooResult`` itself (``loo``).  Workers built with ``baseline=...`` predict under their marginal
+    likelihood: a continuum offset the baseline absorbs flags nothing.  The two defaults are conventions, not measurements: 5 sigma per
     pixel (one in 1.7 million under the model), and one in 10,000 per epoch (a hundred epochs of ten chunks then flag one
     good epoch in ten runs)."""
     from scipy.stats import chi2
@@ -313,7 +322,9 @@ def loo_mask_rows(chunks_meta, outliers, pad_days=0.1):
 
 def fisher_information(workers, p):
     """The Fisher information of the SUM of the workers' ``lnprob`` at the fitted vector ``p``: the sum of
-    ``ChunkWorker.fisher`` over the chunks, ``(n_fit, n_fit)``."""
+    ``ChunkWorker.fisher`` over the chunks, ``(n_fit, n_fit)``.  Workers built with ``baseline=...`` contribute the
+    information of their marginal likelihood, so ``laplace_covariance`` and ``fisher_jumps`` carry the uncertainty of the
+    continuum."""
     workers = list(workers) if isinstance(workers, (list, tuple)) else [workers]
     total = None
     for w in workers:
