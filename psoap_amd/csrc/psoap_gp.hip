@@ -812,7 +812,7 @@ struct StagedRow {
     double* Wt;            // where THIS row's inverse diagonal tile goes, wt_stride doubles from one matrix to the next
     size_t wt_stride;
     int strip;             // tiles right of the diagonal tile
-    // a second strip under the same bracket with no right-hand side beside it (the slots of Ht in marg_grad_run): A2 is the
+    // a second strip under the same bracket with no right-hand side beside it (the slots of Ht in marg_grad_factor): A2 is the
     // matrix pointer moved so that the strip's first tile column, k0 + NB, falls on this strip's first tile
     double* A2 = nullptr;
     int strip2 = 0;
@@ -2042,10 +2042,12 @@ extern "C" int psoap_lnlike(psoap_chunk* h, int c, const double* lwl, const doub
 // Everything lives in the handle's gradient workspace and runs on the handle's first stream behind whatever the handle
 // has in flight: neither the proposal slots nor the workspaces of the likelihood paths are touched.
 //
-// What the analysis paths below share, and what a new one is expected to reuse ("The host layer"): grad_ws_need sizes
-// the workspace, launch_grad_fill fills K, staged_row (above) is every block row of every factorisation, launch_alpha makes
-// alpha, orbit_front / orbit_back are the orbit entry, proposal_refused / poison_gradient the conventions, release_ws the
-// body of a *_release.
+// What the analysis paths below share, and what a new one is expected to reuse ("The host layer"): Factored says
+// where things are after a factorisation, plain or marginal, factored_ws_need sizes the workspaces for it and factor_group
+// runs it; launch_grad_fill fills K, staged_row (above) is every block row of every factorisation, launch_alpha makes
+// alpha, orbit_front / orbit_back are the orbit entry, proposal_refused / values_out / poison_gradient the conventions,
+// release_ws the body of a *_release.  The marginal pieces (marg_ws_need, launch_marg_rhs, gram_units, launch_marg_finish)
+// stand with psoap_chunk_lnlike_marg further down.
 
 // The gradient workspace for groups of G matrices of mstride doubles each: what the factorisation needs, always; alpha and
 // its partial sums (`alpha`); the contraction's partial tiles and the three gradients (`contract`); with np > 0 the orbit
@@ -2112,6 +2114,18 @@ static bool proposal_refused(const double* gp, int c, int b, const int* fast = n
     bool neg = fast && fast[b];
     for (int k = 0; k < 2 * c; ++k) neg = neg || gp[(size_t)b * 2 * c + k] < 0.0;
     return neg;
+}
+
+// The value record of proposal b (`stride` doubles per proposal: the value and, with stride 5, its four parts) into lnp[b] and,
+// where asked for, parts[4 b]: -inf for a refused proposal whatever the device computed, NaN parts beside a -inf.
+// -> the proposal has no value, and nothing else is to be said about it
+static bool values_out(const double* out, int stride, int b, bool refused, double* lnp, double* parts)
+{
+    lnp[b] = refused ? -INFINITY : out[(size_t)b * stride];
+    const bool bad = lnp[b] == -INFINITY;
+    if (parts)
+        for (int k = 0; k < 4; ++k) parts[(size_t)b * 4 + k] = bad ? NAN : out[(size_t)b * stride + 1 + k];
+    return bad;
 }
 
 // ... and no gradient there: NaN into proposal b of grad_gp and of every optional output that was asked for
@@ -2219,28 +2233,122 @@ static int orbit_back(psoap_chunk* h, GradWs& w, hipStream_t s, int nb, int c, i
     return 0;
 }
 
-// The ln-wavelengths of a gradient call come from the host (lwl: psoap_chunk_lnlike_grad) or, with lwl == nullptr, from
-// the orbits p_orb of `model` (orbit_front, orbit_back).
-static int grad_run(psoap_chunk* h, int B, int c, const double* lwl, int model, const double* p_orb,
-                    const double* gp, double mu_GP, double* lnp, double* grad_gp, double* grad_lwl, double* grad_mu,
-                    double* grad_orb, double* grad_vel)
+// Where things are once a group of matrices is factored (factor_group) -- [K | I], or under the handle's baseline
+// [K | I | Ht] and [M | Xt] (marg_grad_plan.hpp): what grad_run, fisher_run and loo_run read instead of asking which.
+struct Factored {
+    bool marg;
+    int G;                       // matrices per group
+    int ld;                      // doubles per row of a matrix in w.A, mstride from one matrix to the next
+    size_t mstride;
+    const Grow<double>* Out;     // the value record, out_stride doubles per matrix: w.Out, or m.Out with the four parts behind the value
+    int out_stride;
+    bool parts;
+    int Q;                       // slots of Ht, for the flop counts (plain: 0)
+    const Grow<double>* Vt;      // [M | Vt] as the marginal kernels take it (mg.Mx): m_stride doubles per matrix, ldm per row, M of
+    int ldm, S;                  // side S (plain: null and 0)
+    size_t m_stride;
+    MargGradPlan gpl;            // the block rows of [K | I | Ht]: marg_grad_factor's
+};
+
+static int marg_basis(psoap_chunk* h, MargWs& m, hipStream_t s);
+static int marg_ws_need(psoap_chunk* h, MargWs& m, int G, bool cov);
+static int marg_grad_factor(psoap_chunk* h, const Factored& fac, hipStream_t s, int nb, int c, double mu_GP);
+
+// ... of a call with B matrices; the workspaces it points into exist afterwards, empty until factored_ws_need
+static Factored factored(psoap_chunk* h, bool marg, int B)
 {
+    const int Npad = h->Npad;
+    if (!h->gws) h->gws.reset(new GradWs());
+    Factored fac{};
+    fac.marg = fac.parts = marg;
+    if (!marg) {
+        fac.G = grad_group_size(B, Npad);
+        fac.ld = 2 * Npad;
+        fac.mstride = (size_t)Npad * fac.ld;
+        fac.Out = &h->gws->Out;
+        fac.out_stride = 1;
+        return fac;
+    }
+    if (!h->mws) h->mws.reset(new MargWs());
+    if (!h->mgws) h->mgws.reset(new MargGradWs());
+    const MargPlan& pl = h->marg.plan;
+    marg_grad_plan(pl, fac.gpl);
+    fac.G = marg_grad_group_size(B, Npad, pl.Q);
+    fac.ld = fac.gpl.ld;
+    fac.mstride = marg_grad_matrix_doubles(Npad, pl.Q);
+    fac.Out = &h->mws->Out;
+    fac.out_stride = 5;
+    fac.Q = pl.Q;
+    fac.Vt = &h->mgws->Mx;
+    fac.S = NB * pl.Q;
+    fac.ldm = fac.S + Npad;
+    fac.m_stride = (size_t)fac.S * fac.ldm;
+    return fac;
+}
+
+// The handle's workspaces sized for groups of fac.G matrices: what the factorisation needs, always; alpha and the plain value
+// record (`values`: the marginal factorisation makes both whatever is asked); `contract`, c, np as grad_ws_need.  Under the
+// baseline Ht goes onto the device as well.
+static int factored_ws_need(psoap_chunk* h, const Factored& fac, hipStream_t s, bool values, bool contract, int c = 0, int np = 0)
+{
+    GradWs& w = *h->gws;
+    if (int rc = grad_ws_need(h, w, fac.G, fac.mstride, values || fac.marg, contract, c, np)) return rc;
+    if (!fac.marg) {
+        if (values) HIP_TRY(w.Out.need(fac.G));
+        return 0;
+    }
+    HIP_TRY(h->mgws->Mx.need((size_t)fac.G * fac.m_stride));
+    HIP_TRY(h->mgws->Zt.need((size_t)fac.G * h->Npad));
+    if (int rc = marg_ws_need(h, *h->mws, fac.G, false)) return rc;
+    return marg_basis(h, *h->mws, s);
+}
+
+// The factorisation of the nb matrices whose grids and hyper-parameters are in w.Lwl and w.Gp.  With `values`, w.Alpha and
+// the value record are ready afterwards: marg_grad_factor makes both anyway, the plain side in a bracket of their own, which
+// fisher_run does without.  `extra` (nullptr: none) is a launch of the caller's that shares that bracket on the plain side
+// and has one to itself under the baseline: the bookkeeping of loo_run.
+template <class X = void (*)()>
+static int factor_group(psoap_chunk* h, const Factored& fac, hipStream_t s, int nb, int c, double mu_GP, bool values,
+                        const X* extra = nullptr)
+{
+    GradWs& w = *h->gws;
+    if (int rc = fac.marg ? marg_grad_factor(h, fac, s, nb, c, mu_GP) : grad_factor(h, w, s, nb, c, mu_GP)) return rc;
+    const bool finish = values && !fac.marg;
+    if (!finish && !extra) return 0;
+    return prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
+        if (finish) {
+            hipLaunchKernelGGL(k_finalize, dim3((nb + 63) / 64), dim3(64), 0, s, (const MatAcc*)w.Acc.p, w.Out.p, nb,
+                               (const int*)nullptr, h->P);
+            launch_alpha(w, s, nb, fac.mstride, fac.ld, h->Npad, h->P, w.R.p);
+        }
+        if (extra) (*extra)();
+    });
+}
+
+// Group after group of matrices through factor_group, then the contraction and the finishing sums -- plain, or with `marg`
+// under the handle's baseline (marg_grad_kernels.hpp).  The ln-wavelengths come from the host (lwl: psoap_chunk_lnlike_grad)
+// or, with lwl == nullptr, from the orbits p_orb of `model` (orbit_front, orbit_back).
+static int grad_run(psoap_chunk* h, const char* who, bool marg, int B, int c, const double* lwl, int model, const double* p_orb,
+                    const double* gp, double mu_GP, double* lnp, double* parts, double* grad_gp, double* grad_lwl,
+                    double* grad_mu, double* grad_orb, double* grad_vel)
+{
+    if (marg)
+        if (const char* why = marg_grad_check(B, c, h->marg.valid, h->marg.stale_weight)) FAIL(std::string(who) + ": " + why);
     const bool orbits = lwl == nullptr;
     DEVICE_SCOPE(h->device);
     if (int rc = enter_device(h->device)) return rc;
-    const int N = h->N, Npad = h->Npad, P = h->P, ld = 2 * h->Npad;
-    const size_t mstride = (size_t)Npad * ld;
-    const int G = grad_group_size(B, Npad);
+    const Factored fac = factored(h, marg, B);
+    const int N = h->N, Npad = h->Npad, P = h->P, G = fac.G, ld = fac.ld, ntiles = P * (P + 1) / 2;
+    const size_t mstride = fac.mstride;
     const int ne = h->n_epochs, np = orbits ? orbit_n_params(model) : 0;
-    if (!h->gws) h->gws.reset(new GradWs());
-    GradWs& w = *h->gws;
-    if (int rc = grad_ws_need(h, w, G, mstride, true, true, c, np)) return rc;
-    HIP_TRY(w.Out.need(G));
     hipStream_t s = h->streams[0];
+    if (int rc = factored_ws_need(h, fac, s, true, true, c, np)) return rc;
+    GradWs& w = *h->gws;
     std::vector<int> fast(orbits ? (size_t)B : 0, 0);
     if (orbits)
         if (int rc = grad_epoch_lists(h, w, s)) return rc;
     h->recs.clear();
+    std::vector<double> out((size_t)B * fac.out_stride);
     for (int b0 = 0; b0 < B; b0 += G) {
         const int nb = (B - b0 < G) ? B - b0 : G;
         if (!orbits)
@@ -2248,26 +2356,27 @@ static int grad_run(psoap_chunk* h, int B, int c, const double* lwl, int model, 
         else if (int rc = orbit_front(h, w, s, nb, c, model, np, p_orb + (size_t)b0 * np))
             return rc;
         HIP_TRY(hipMemcpyAsync(w.Gp, gp + (size_t)b0 * 2 * c, sizeof(double) * (size_t)nb * 2 * c, hipMemcpyHostToDevice, s));
-        if (int rc = grad_factor(h, w, s, nb, c, mu_GP)) return rc;
-        if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
-                hipLaunchKernelGGL(k_finalize, dim3((nb + 63) / 64), dim3(64), 0, s, (const MatAcc*)w.Acc.p, w.Out.p, nb,
-                                   (const int*)nullptr, P);
-                launch_alpha(w, s, nb, mstride, ld, Npad, P, w.R.p);
-            })) return rc;
+        if (int rc = factor_group(h, fac, s, nb, c, mu_GP, true)) return rc;
         double cunits = 0.0;
-        for (int tj = 0; tj < P; ++tj) cunits += (double)(tj + 1) * (P - tj);
+        for (int tj = 0; tj < P; ++tj) cunits += (double)(tj + 1) * (P - tj + fac.Q);
         if (int rc = prof_launch(h, s, PSOAP_K_GRAD, TILE_FLOPS * cunits * nb, 0.0, [&] {
                 with_components(c, [&](auto nc) {
-                    hipLaunchKernelGGL(k_grad_contract<nc()>, dim3(P * (P + 1) / 2, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s,
-                                       (const double*)w.A.p, mstride, ld, N, Npad, P, (const double*)w.Lwl.p, (const double*)w.Gp.p,
-                                       (const double*)w.Alpha.p, w.Part.p);
+                    if (marg)
+                        hipLaunchKernelGGL(k_marg_grad_contract<nc()>, dim3(ntiles, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s,
+                                           (const double*)w.A.p, mstride, ld, N, Npad, P, (const double*)w.Lwl.p, (const double*)w.Gp.p,
+                                           (const double*)w.Alpha.p, w.Part.p, (const double*)fac.Vt->p, fac.m_stride, fac.ldm, fac.S);
+                    else
+                        hipLaunchKernelGGL(k_grad_contract<nc()>, dim3(ntiles, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s,
+                                           (const double*)w.A.p, mstride, ld, N, Npad, P, (const double*)w.Lwl.p, (const double*)w.Gp.p,
+                                           (const double*)w.Alpha.p, w.Part.p);
                 });
             })) return rc;
         if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
                 hipLaunchKernelGGL(k_grad_finish, dim3(P + 1, nb), dim3(128), 0, s, (const double*)w.Part.p, (const double*)w.Alpha.p,
                                    (const double*)w.Gp.p, c, N, Npad, P, w.GradGp.p, w.GradX.p, w.GradMu.p);
             })) return rc;
-        HIP_TRY(hipMemcpyAsync(lnp + b0, w.Out, sizeof(double) * nb, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(out.data() + (size_t)b0 * fac.out_stride, fac.Out->p, sizeof(double) * (size_t)nb * fac.out_stride,
+                               hipMemcpyDeviceToHost, s));
         HIP_TRY(hipMemcpyAsync(grad_gp + (size_t)b0 * 2 * c, w.GradGp, sizeof(double) * (size_t)nb * 2 * c, hipMemcpyDeviceToHost, s));
         if (grad_lwl)
             HIP_TRY(hipMemcpyAsync(grad_lwl + (size_t)b0 * c * N, w.GradX, sizeof(double) * (size_t)nb * c * N, hipMemcpyDeviceToHost, s));
@@ -2279,11 +2388,12 @@ static int grad_run(psoap_chunk* h, int B, int c, const double* lwl, int model, 
         HIP_TRY(hipStreamSynchronize(s));       // the next group reuses the workspace and the caller's arrays are pageable
     }
     if (collect_timings(h)) return 1;
-    // a refused proposal or a matrix that is not positive definite -> -inf, and no gradient there
-    for (int b = 0; b < B; ++b) {
-        if (proposal_refused(gp, c, b, orbits ? fast.data() : nullptr)) lnp[b] = -INFINITY;
-        if (lnp[b] == -INFINITY) poison_gradient(b, c, N, ne, np, grad_gp, grad_lwl, grad_mu, grad_orb, grad_vel);
-    }
+    // a negative hyper-parameter, a faster-than-light orbit, a K (or under the baseline an M) that does not factor -> -inf, and
+    // no gradient there
+    for (int b = 0; b < B; ++b)
+        if (values_out(out.data(), fac.out_stride, b, proposal_refused(gp, c, b, orbits ? fast.data() : nullptr), lnp,
+                       fac.parts ? parts : nullptr))
+            poison_gradient(b, c, N, ne, np, grad_gp, grad_lwl, grad_mu, grad_orb, grad_vel);
     return 0;
 }
 
@@ -2294,8 +2404,8 @@ extern "C" int psoap_chunk_lnlike_grad(psoap_chunk* h, int B, int c, const doubl
     if (B < 1) FAIL("psoap_chunk_lnlike_grad: B must be at least 1");
     if (c < 1 || c > 3) FAIL("number of components must be 1, 2 or 3");
     if (h->stream.open) FAIL("psoap_chunk_lnlike_grad: the handle has an open stream (psoap_stream_close first)");
-    return grad_run(h, B, c, lwl, -1, nullptr, gp, mu_GP, lnp, grad_gp, grad_lwl, grad_mu, nullptr,
-                    nullptr);
+    return grad_run(h, "psoap_chunk_lnlike_grad", false, B, c, lwl, -1, nullptr, gp, mu_GP, lnp, nullptr, grad_gp, grad_lwl,
+                    grad_mu, nullptr, nullptr);
 }
 
 extern "C" int psoap_chunk_lnprob_grad(psoap_chunk* h, int B, int model, const double* p_orb, const double* gp, double mu_GP,
@@ -2306,8 +2416,8 @@ extern "C" int psoap_chunk_lnprob_grad(psoap_chunk* h, int B, int model, const d
     if (!h->dGrid || !h->dDates) FAIL("psoap_chunk_lnprob_grad: call psoap_chunk_set_grid and psoap_chunk_set_dates first");
     if (h->stream.open) FAIL("psoap_chunk_lnprob_grad: the handle has an open stream (psoap_stream_close first)");
     if (int rc = check_orbits(model, B, p_orb)) return rc;
-    return grad_run(h, B, orbit_n_components(model), nullptr, model, p_orb, gp, mu_GP, lnp, grad_gp,
-                    nullptr, grad_mu, grad_orb, grad_vel);
+    return grad_run(h, "psoap_chunk_lnprob_grad", false, B, orbit_n_components(model), nullptr, model, p_orb, gp, mu_GP, lnp,
+                    nullptr, grad_gp, nullptr, grad_mu, grad_orb, grad_vel);
 }
 
 // stand-alone, beside psoap_orbit_velocities: vel_out (B, c, n_dates), jac_out (B, c, n_dates, n_orb)
@@ -2339,18 +2449,6 @@ extern "C" int psoap_chunk_grad_release(psoap_chunk* h)
     return release_ws(h, [&] { h->gws.reset(); });
 }
 
-// What the marginal gradient, the marginal Fisher information and the marginal leave-one-out share: the dimensions of a call,
-// its workspace and its factorisation.
-struct MargGradDims {
-    MargGradPlan gpl;
-    int S, ld, ldm, ldh, G, nslab, ngram;
-    size_t mstride, m_stride, wstride;
-};
-
-static MargGradDims marg_grad_dims(const psoap_chunk* h, int B);
-static int marg_grad_ws_need(psoap_chunk* h, const MargGradDims& d, hipStream_t s, bool contract, int c = 0, int np = 0);
-static int marg_grad_factor(psoap_chunk* h, const MargGradDims& d, hipStream_t s, int nb, int c, double mu_GP);
-
 // ---- Fisher information of the likelihood (fisher_kernels.hpp) --------------------------------------
 // One matrix through the gradient's workspace and factorisation, then K^-1 and, tangent after tangent, K_t, Z = K_t K^-1
 // and the contraction of G_t = 1/2 (K^-1 Z + Z^T K^-1) -- on the handle's first stream behind whatever the handle has in flight; neither
@@ -2369,18 +2467,15 @@ static int fisher_run(psoap_chunk* h, const char* who, bool marg, int c, const d
     DEVICE_SCOPE(h->device);
     if (int rc = enter_device(h->device)) return rc;
     hipStream_t s = h->streams[0];
-    const MargGradDims md = marg ? marg_grad_dims(h, 1) : MargGradDims();
-    const int N = h->N, Npad = h->Npad, P = h->P, ld = marg ? md.ld : 2 * h->Npad;
-    const size_t mstride = (size_t)Npad * ld, sq = (size_t)Npad * Npad, CN = (size_t)c * N;
+    const Factored fac = factored(h, marg, 1);
+    const int N = h->N, Npad = h->Npad, P = h->P, ld = fac.ld;
+    const size_t sq = (size_t)Npad * Npad, CN = (size_t)c * N;
     const int ntiles = P * (P + 1) / 2;
-    if (!h->gws) h->gws.reset(new GradWs());
     if (!h->fws) h->fws.reset(new FisherWs());
-    if (marg) {
-        if (int rc = marg_grad_ws_need(h, md, s, false)) return rc;
-    } else if (int rc = grad_ws_need(h, *h->gws, 1, mstride, false, false)) return rc;
+    if (int rc = factored_ws_need(h, fac, s, false, false)) return rc;
     GradWs& w = *h->gws;
     FisherWs& f = *h->fws;
-    if (marg) HIP_TRY(f.V.need(md.S));
+    if (marg) HIP_TRY(f.V.need(fac.S));
     HIP_TRY(f.Kinv.need(sq));
     HIP_TRY(f.Kt.need(sq));
     HIP_TRY(f.Z.need(sq));
@@ -2400,13 +2495,13 @@ static int fisher_run(psoap_chunk* h, const char* who, bool marg, int c, const d
     else HIP_TRY(hipMemsetAsync(f.TanX, 0, sizeof(double) * (size_t)T * CN, s));
     HIP_TRY(hipMemcpyAsync(f.TanGp, tan_gp, sizeof(double) * (size_t)T * 2 * c, hipMemcpyHostToDevice, s));
     // (F does not depend on the data: any mu_GP)
-    if (int rc = marg ? marg_grad_factor(h, md, s, 1, c, 0.0) : grad_factor(h, w, s, 1, c, 0.0)) return rc;
+    if (int rc = factor_group(h, fac, s, 1, c, 0.0, false)) return rc;
     double kunits = 0.0;
-    for (int tj = 0; tj < P; ++tj) kunits += (double)(tj + 1) * (P - tj + (marg ? h->marg.plan.Q : 0));
+    for (int tj = 0; tj < P; ++tj) kunits += (double)(tj + 1) * (P - tj + fac.Q);
     if (int rc = prof_launch(h, s, PSOAP_K_GRAD, TILE_FLOPS * kunits, 0.0, [&] {
             if (marg)
                 hipLaunchKernelGGL(k_marg_fisher_kinv, dim3(ntiles), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)w.A.p, ld,
-                                   Npad, P, (const double*)h->mgws->Mx.p, md.ldm, md.S, f.Kinv.p);
+                                   Npad, P, (const double*)fac.Vt->p, fac.ldm, fac.S, f.Kinv.p);
             else
                 hipLaunchKernelGGL(k_fisher_kinv, dim3(ntiles), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)w.A.p, ld, Npad,
                                    P, f.Kinv.p);
@@ -2415,9 +2510,9 @@ static int fisher_run(psoap_chunk* h, const char* who, bool marg, int c, const d
             hipLaunchKernelGGL(k_acc_total, dim3(1), dim3(1), 0, s, (const MatAcc*)w.Acc.p, P, f.Info.p);
             hipLaunchKernelGGL(k_fisher_w1, dim3(N), dim3(256), 0, s, (const double*)w.A.p, ld, Npad, N, f.Y.p);
             if (marg) {
-                hipLaunchKernelGGL(k_marg_fisher_v1, dim3(md.S), dim3(256), 0, s, (const double*)h->mgws->Mx.p, md.ldm, md.S, N,
+                hipLaunchKernelGGL(k_marg_fisher_v1, dim3(fac.S), dim3(256), 0, s, (const double*)fac.Vt->p, fac.ldm, fac.S, N,
                                    f.V.p);
-                hipLaunchKernelGGL(k_marg_fisher_mu, dim3(1), dim3(256), 0, s, (const double*)f.Y.p, N, (const double*)f.V.p, md.S,
+                hipLaunchKernelGGL(k_marg_fisher_mu, dim3(1), dim3(256), 0, s, (const double*)f.Y.p, N, (const double*)f.V.p, fac.S,
                                    f.Mu.p);
             } else
                 hipLaunchKernelGGL(k_fisher_mu, dim3(1), dim3(256), 0, s, (const double*)f.Y.p, N, f.Mu.p);
@@ -2452,7 +2547,7 @@ static int fisher_run(psoap_chunk* h, const char* who, bool marg, int c, const d
         })) return rc;
     MatAcc info;
     double value = 0.0;      // (marg: -inf also when M does not factor)
-    if (marg) HIP_TRY(hipMemcpyAsync(&value, h->mws->Out, sizeof(double), hipMemcpyDeviceToHost, s));
+    if (marg) HIP_TRY(hipMemcpyAsync(&value, fac.Out->p, sizeof(double), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(fisher, f.F, sizeof(double) * (size_t)T * T, hipMemcpyDeviceToHost, s));
     if (fisher_mu) HIP_TRY(hipMemcpyAsync(fisher_mu, f.Mu, sizeof(double), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(&info, f.Info, sizeof info, hipMemcpyDeviceToHost, s));
@@ -2502,24 +2597,21 @@ static int loo_run(psoap_chunk* h, const char* who, bool marg, int c, const doub
     if (h->stream.open) FAIL(std::string(who) + ": the handle has an open stream (psoap_stream_close first)");
     if (marg)
         if (const char* why = marg_grad_check(1, c, h->marg.valid, h->marg.stale_weight)) FAIL(std::string(who) + ": " + why);
-    const MargGradDims md = marg ? marg_grad_dims(h, 1) : MargGradDims();
-    const int N = h->N, Npad = h->Npad, P = h->P, ld = marg ? md.ld : 2 * h->Npad;
+    const int N = h->N, Npad = h->Npad, P = h->P;
     LooLayout lay;
     if (const char* why = loo_layout(epoch, N, n_epochs, lay)) FAIL(std::string(who) + ": " + why);
     const int ne = epoch ? n_epochs : 0, nblk = (int)lay.blocks.size(), ntile = (int)lay.tiles.size();
     if (!epoch) ep_resid = ep_chi2 = ep_logp = nullptr, ep_npix = nullptr;
     DEVICE_SCOPE(h->device);
     if (int rc = enter_device(h->device)) return rc;
-    const size_t mstride = (size_t)Npad * ld, CN = (size_t)c * N;
+    const Factored fac = factored(h, marg, 1);
+    const int ld = fac.ld;
+    const size_t CN = (size_t)c * N;
     hipStream_t s = h->streams[0];
-    if (!h->gws) h->gws.reset(new GradWs());
     if (!h->lws) h->lws.reset(new LooWs());
-    if (marg) {
-        if (int rc = marg_grad_ws_need(h, md, s, false)) return rc;
-    } else if (int rc = grad_ws_need(h, *h->gws, 1, mstride, true, false)) return rc;
+    if (int rc = factored_ws_need(h, fac, s, true, false)) return rc;
     GradWs& w = *h->gws;
     LooWs& l = *h->lws;
-    HIP_TRY(w.Out.need(1));
     HIP_TRY(l.Blk.need((size_t)lay.block_doubles));
     HIP_TRY(l.Rhs.need((size_t)lay.rhs_doubles));
     HIP_TRY(l.Sol.need((size_t)lay.rhs_doubles));
@@ -2544,20 +2636,14 @@ static int loo_run(psoap_chunk* h, const char* who, bool marg, int c, const doub
     HIP_TRY(hipMemcpyAsync(l.EpBlock, lay.epoch_block.data(), sizeof(int) * lay.epoch_block.size(), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemsetAsync(l.Blk, 0, sizeof(double) * (size_t)lay.block_doubles, s));
     // the value and alpha exactly as psoap_chunk_lnlike_grad (marg: psoap_chunk_lnlike_marg_grad) makes them for one matrix
-    if (int rc = marg ? marg_grad_factor(h, md, s, 1, c, mu_GP) : grad_factor(h, w, s, 1, c, mu_GP)) return rc;
-    if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
-            if (!marg) {
-                hipLaunchKernelGGL(k_finalize, dim3(1), dim3(64), 0, s, (const MatAcc*)w.Acc.p, w.Out.p, 1, (const int*)nullptr, P);
-                launch_alpha(w, s, 1, mstride, ld, Npad, P, w.R.p);
-            }
-            hipLaunchKernelGGL(k_loo_pad, dim3(nblk), dim3(128), 0, s, (const LooBlock*)l.Blocks.p, l.Blk.p);
-        })) return rc;
+    auto pad = [&] { hipLaunchKernelGGL(k_loo_pad, dim3(nblk), dim3(128), 0, s, (const LooBlock*)l.Blocks.p, l.Blk.p); };
+    if (int rc = factor_group(h, fac, s, 1, c, mu_GP, true, &pad)) return rc;
     double bunits = 0.0;      // executed 128^3 products of the band: a diagonal tile issues three quarters of its MFMAs
-    for (const LooTile& t : lay.tiles) bunits += (t.ti == t.tj ? 0.75 : 1.0) * (P - t.tj + (marg ? h->marg.plan.Q : 0));
+    for (const LooTile& t : lay.tiles) bunits += (t.ti == t.tj ? 0.75 : 1.0) * (P - t.tj + fac.Q);
     if (int rc = prof_launch(h, s, PSOAP_K_GRAD, TILE_FLOPS * bunits, 0.0, [&] {
             if (marg)
                 hipLaunchKernelGGL(k_marg_loo_band, dim3(ntile), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)w.A.p, ld, N,
-                                   Npad, (const double*)h->mgws->Mx.p, md.ldm, md.S, (const LooTile*)l.Tiles.p,
+                                   Npad, (const double*)fac.Vt->p, fac.ldm, fac.S, (const LooTile*)l.Tiles.p,
                                    (const int*)l.PixBlock.p, (const LooBlock*)l.Blocks.p, l.Blk.p);
             else
                 hipLaunchKernelGGL(k_loo_band, dim3(ntile), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)w.A.p, ld, N, Npad,
@@ -2590,7 +2676,7 @@ static int loo_run(psoap_chunk* h, const char* who, bool marg, int c, const doub
                                l.Pix.p + 2 * (size_t)N, l.EpResid.p, l.EpOut.p, l.EpOut.p + (ne + 1), l.EpNpix.p, l.Logp.p);
         })) return rc;
     double value = 0.0;
-    HIP_TRY(hipMemcpyAsync(&value, marg ? h->mws->Out.p : w.Out.p, sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&value, fac.Out->p, sizeof(double), hipMemcpyDeviceToHost, s));
     if (loo_logp) HIP_TRY(hipMemcpyAsync(loo_logp, l.Logp, sizeof(double), hipMemcpyDeviceToHost, s));
     if (pix_mean) HIP_TRY(hipMemcpyAsync(pix_mean, l.Pix, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost, s));
     if (pix_var) HIP_TRY(hipMemcpyAsync(pix_var, l.Pix.p + N, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost, s));
@@ -2705,6 +2791,61 @@ static int marg_basis(psoap_chunk* h, MargWs& m, hipStream_t s)
     return 0;
 }
 
+// What psoap_chunk_lnlike_marg and marg_grad_factor share.  Their K sweeps differ -- [K | Ht] with no identity to pay for,
+// [K | I | Ht] -- and so does where M lives (m.M, mg.Mx); the rest is here.
+
+// the marginal workspace beyond M for groups of G matrices; `cov`: the inverse of M and the covariance of beta as well
+static int marg_ws_need(psoap_chunk* h, MargWs& m, int G, bool cov)
+{
+    const MargPlan& pl = h->marg.plan;
+    const size_t S = (size_t)NB * pl.Q, q = pl.q, nslab = (h->Npad + 255) / 256;
+    HIP_TRY(m.WtM.need((size_t)G * pl.Q * NB * NB));
+    HIP_TRY(m.Rhs.need((size_t)G * S));
+    HIP_TRY(m.Gam.need((size_t)G * S));
+    HIP_TRY(m.RPart.need((size_t)G * nslab * S));
+    HIP_TRY(m.AccM.need((size_t)G * ACC_ROWS));
+    HIP_TRY(m.Out.need((size_t)G * 5));
+    HIP_TRY(m.Beta.need((size_t)G * q));
+    HIP_TRY(m.Flc.need((size_t)G * h->N));
+    if (cov) {
+        HIP_TRY(m.Minv.need((size_t)G * S * S));
+        HIP_TRY(m.Cov.need((size_t)G * q * q));
+    }
+    return 0;
+}
+
+// m.Rhs = Wh^T z for nb factored matrices, Ah what the kernels of marg_kernels.hpp take for [K | Ht].  Launches only: inside
+// the caller's bracket.
+static void launch_marg_rhs(const psoap_chunk* h, MargWs& m, hipStream_t s, int nb, const double* Ah, size_t mstride, int ld,
+                            const double* z)
+{
+    const int Npad = h->Npad, Q = h->marg.plan.Q, nslab = (Npad + 255) / 256;
+    hipLaunchKernelGGL(k_marg_rhs_partial, dim3(Q, nslab, nb), dim3(256), 0, s, Ah, mstride, ld, Npad, Q, (const int*)m.Tab.p, z,
+                       m.RPart.p, nslab);
+    hipLaunchKernelGGL(k_marg_rhs_finish, dim3((NB * Q + 255) / 256, nb), dim3(256), 0, s, (const double*)m.RPart.p, nslab, Npad, Q,
+                       (const int*)m.Tab.p, m.Rhs.p);
+}
+
+// executed 128^3 products of one Gram matrix M = I + Wh^T Wh: a diagonal tile issues three quarters of its MFMAs
+static double gram_units(const MargPlan& pl, int Npad)
+{
+    double units = 0.0;
+    for (const MargTile& t : pl.tiles) units += (t.ti == t.tj ? 0.75 : 1.0) * (Npad - t.k0) / NB;
+    return units;
+}
+
+// lnL, its parts and g = U_M^-1 y of nb matrices into m.Out and m.Gam from the factored M (m_stride doubles per matrix, ldm
+// per row); with want_sol beta and the corrected flux as well.  The only launch site of k_marg_finish; inside the caller's bracket.
+static void launch_marg_finish(const psoap_chunk* h, const GradWs& w, MargWs& m, hipStream_t s, int nb, const double* M,
+                               size_t m_stride, int ldm, bool want_sol)
+{
+    const MargPlan& pl = h->marg.plan;
+    hipLaunchKernelGGL(k_marg_finish, dim3(nb), dim3(256), 0, s, h->N, h->P, pl.Q, pl.q, pl.order, (const MatAcc*)w.Acc.p,
+                       (const MatAcc*)m.AccM.p, M, m_stride, ldm, (const double*)m.WtM.p, (const double*)m.Rhs.p, m.Gam.p,
+                       (const double*)m.Sd.p, (const int*)m.Epoch.p, (const int*)m.Tab.p, (const double*)m.Ht.p, NB * pl.Q,
+                       (const double*)h->dFl.p, m.Out.p, m.Beta.p, m.Flc.p, want_sol ? 1 : 0);
+}
+
 // Group after group of matrices through the gradient's workspace as [K | Ht] (ld = Npad + 128 Q), then the Gram matrices
 // through the staged kernels once more -- on the handle's first stream behind whatever the handle has in flight; neither
 // the proposal slots nor the workspaces of the likelihood paths are touched.
@@ -2725,8 +2866,7 @@ extern "C" int psoap_chunk_lnlike_marg(psoap_chunk* h, int B, int c, const doubl
     const int N = h->N, Npad = h->Npad, P = h->P, Q = pl.Q, q = pl.q, order = pl.order;
     const int S = NB * Q, ld = Npad + S, ldm = 2 * S, ldh = S;
     const size_t mstride = (size_t)Npad * ld, m_stride = (size_t)S * ldm, wstride = (size_t)Q * NB * NB;
-    const int G = marg_group_size(B, Npad, Q);
-    const int nslab = (Npad + 255) / 256, ngram = Q * (Q + 1) / 2;
+    const int G = marg_group_size(B, Npad, Q), ngram = Q * (Q + 1) / 2;
     const bool want_cov = beta_cov != nullptr, want_sol = beta != nullptr || fl_cor != nullptr;
     if (!h->gws) h->gws.reset(new GradWs());
     if (!h->mws) h->mws.reset(new MargWs());
@@ -2734,18 +2874,7 @@ extern "C" int psoap_chunk_lnlike_marg(psoap_chunk* h, int B, int c, const doubl
     MargWs& m = *h->mws;
     if (int rc = grad_ws_need(h, w, G, mstride, false, false)) return rc;
     HIP_TRY(m.M.need((size_t)G * m_stride));
-    HIP_TRY(m.WtM.need((size_t)G * wstride));
-    HIP_TRY(m.Rhs.need((size_t)G * S));
-    HIP_TRY(m.Gam.need((size_t)G * S));
-    HIP_TRY(m.RPart.need((size_t)G * nslab * S));
-    HIP_TRY(m.AccM.need((size_t)G * ACC_ROWS));
-    HIP_TRY(m.Out.need((size_t)G * 5));
-    HIP_TRY(m.Beta.need((size_t)G * q));
-    HIP_TRY(m.Flc.need((size_t)G * N));
-    if (want_cov) {
-        HIP_TRY(m.Minv.need((size_t)G * S * S));
-        HIP_TRY(m.Cov.need((size_t)G * q * q));
-    }
+    if (int rc = marg_ws_need(h, m, G, want_cov)) return rc;
     hipStream_t s = h->streams[0];
     if (int rc = marg_basis(h, m, s)) return rc;
     const int* tab = m.Tab.p;
@@ -2774,15 +2903,9 @@ extern "C" int psoap_chunk_lnlike_marg(psoap_chunk* h, int B, int c, const doubl
                                     TILE_FLOPS * p * (P - p + act) * nb))
                 return rc;
         }
-        if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
-                hipLaunchKernelGGL(k_marg_rhs_partial, dim3(Q, nslab, nb), dim3(256), 0, s, (const double*)w.A.p, mstride, ld, Npad, Q,
-                                   tab, (const double*)w.R.p, m.RPart.p, nslab);
-                hipLaunchKernelGGL(k_marg_rhs_finish, dim3((S + 255) / 256, nb), dim3(256), 0, s, (const double*)m.RPart.p, nslab, Npad,
-                                   Q, tab, m.Rhs.p);
-            })) return rc;
-        double gunits = 0.0;
-        for (const MargTile& t : pl.tiles) gunits += (t.ti == t.tj ? 0.75 : 1.0) * (Npad - t.k0) / NB;
-        if (int rc = prof_launch(h, s, PSOAP_K_GRAD, TILE_FLOPS * gunits * nb, 0.0, [&] {
+        if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] { launch_marg_rhs(h, m, s, nb, w.A.p, mstride, ld, w.R.p); }))
+            return rc;
+        if (int rc = prof_launch(h, s, PSOAP_K_GRAD, TILE_FLOPS * gram_units(pl, Npad) * nb, 0.0, [&] {
                 hipLaunchKernelGGL(k_marg_gram, dim3(ngram, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)w.A.p, mstride, ld,
                                    Npad, (const MargTile*)m.Tiles.p, m.M.p, m_stride, ldm);
                 if (want_cov) hipLaunchKernelGGL(k_grad_init, dim3(ngram, nb), dim3(256), 0, s, m.M.p, m_stride, ldm, S, Q);
@@ -2802,12 +2925,8 @@ extern "C" int psoap_chunk_lnlike_marg(psoap_chunk* h, int B, int c, const doubl
             if (int rc = staged_row(h, s, row, nb, k0, p > 0 ? &update : nullptr, TILE_FLOPS * p * (want_cov ? Q : Q - p) * nb))
                 return rc;
         }
-        if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
-                hipLaunchKernelGGL(k_marg_finish, dim3(nb), dim3(256), 0, s, N, P, Q, q, order, (const MatAcc*)w.Acc.p,
-                                   (const MatAcc*)m.AccM.p, (const double*)m.M.p, m_stride, ldm, (const double*)m.WtM.p,
-                                   (const double*)m.Rhs.p, m.Gam.p, (const double*)m.Sd.p, (const int*)m.Epoch.p, tab,
-                                   (const double*)m.Ht.p, ldh, (const double*)h->dFl.p, m.Out.p, m.Beta.p, m.Flc.p, want_sol ? 1 : 0);
-            })) return rc;
+        if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] { launch_marg_finish(h, w, m, s, nb, m.M.p, m_stride, ldm, want_sol); }))
+            return rc;
         if (want_cov)
             if (int rc = prof_launch(h, s, PSOAP_K_GRAD, 0.0, 0.0, [&] {
                     for (int b = 0; b < nb; ++b)
@@ -2827,11 +2946,7 @@ extern "C" int psoap_chunk_lnlike_marg(psoap_chunk* h, int B, int c, const doubl
     // the conventions of the likelihood: a negative hyper-parameter, a K that is not positive definite or an M that fails to
     // factor -> -inf, and nothing else to say about it
     for (int b = 0; b < B; ++b) {
-        lnp[b] = proposal_refused(gp, c, b) ? -INFINITY : out[(size_t)b * 5];
-        const bool bad = lnp[b] == -INFINITY;
-        if (parts)
-            for (int k = 0; k < 4; ++k) parts[(size_t)b * 4 + k] = bad ? NAN : out[(size_t)b * 5 + 1 + k];
-        if (!bad) continue;
+        if (!values_out(out.data(), 5, b, proposal_refused(gp, c, b), lnp, parts)) continue;
         if (beta)
             for (int k = 0; k < q; ++k) beta[(size_t)b * q + k] = NAN;
         if (beta_cov)
@@ -2843,61 +2958,20 @@ extern "C" int psoap_chunk_lnlike_marg(psoap_chunk* h, int B, int c, const doubl
 }
 
 // ---- gradient of that likelihood (marg_grad_kernels.hpp) -------------------------------------------------
-static MargGradDims marg_grad_dims(const psoap_chunk* h, int B)
-{
-    MargGradDims d;
-    const MargPlan& pl = h->marg.plan;
-    marg_grad_plan(pl, d.gpl);
-    d.S = NB * pl.Q;
-    d.ld = d.gpl.ld;
-    d.ldm = d.S + h->Npad;
-    d.ldh = d.S;
-    d.mstride = marg_grad_matrix_doubles(h->Npad, pl.Q);
-    d.m_stride = (size_t)d.S * d.ldm;
-    d.wstride = (size_t)pl.Q * NB * NB;
-    d.G = marg_grad_group_size(B, h->Npad, pl.Q);
-    d.nslab = (h->Npad + 255) / 256;
-    d.ngram = pl.Q * (pl.Q + 1) / 2;
-    return d;
-}
-
-// the handle's three workspaces sized for groups of d.G matrices (`contract`, c, np: as grad_ws_need), and Ht on the device
-static int marg_grad_ws_need(psoap_chunk* h, const MargGradDims& d, hipStream_t s, bool contract, int c, int np)
-{
-    const int N = h->N, Npad = h->Npad, G = d.G, S = d.S, q = h->marg.plan.q;
-    if (!h->gws) h->gws.reset(new GradWs());
-    if (!h->mws) h->mws.reset(new MargWs());
-    if (!h->mgws) h->mgws.reset(new MargGradWs());
-    MargWs& m = *h->mws;
-    MargGradWs& mg = *h->mgws;
-    if (int rc = grad_ws_need(h, *h->gws, G, d.mstride, true, contract, c, np)) return rc;
-    HIP_TRY(mg.Mx.need((size_t)G * d.m_stride));
-    HIP_TRY(mg.Zt.need((size_t)G * Npad));
-    HIP_TRY(m.WtM.need((size_t)G * d.wstride));
-    HIP_TRY(m.Rhs.need((size_t)G * S));
-    HIP_TRY(m.Gam.need((size_t)G * S));
-    HIP_TRY(m.RPart.need((size_t)G * d.nslab * S));
-    HIP_TRY(m.AccM.need((size_t)G * ACC_ROWS));
-    HIP_TRY(m.Out.need((size_t)G * 5));
-    HIP_TRY(m.Beta.need((size_t)G * q));
-    HIP_TRY(m.Flc.need((size_t)G * N));
-    return marg_basis(h, m, s);
-}
-
 // The staged factorisation of [K | I | Ht] (marg_grad_plan.hpp) and of [M | Xt] for the nb matrices whose grids and
 // hyper-parameters are in w.Lwl and w.Gp.  Afterwards the I block holds Wi = U^-T, the appended block of mg.Mx holds
 // Vt = U_M^-T Wh^T Wi, m.Out the value and its parts with the bits of psoap_chunk_lnlike_marg, mg.Zt = z - Wh g and
 // w.Alpha = alpha_m.
-static int marg_grad_factor(psoap_chunk* h, const MargGradDims& d, hipStream_t s, int nb, int c, double mu_GP)
+static int marg_grad_factor(psoap_chunk* h, const Factored& fac, hipStream_t s, int nb, int c, double mu_GP)
 {
     GradWs& w = *h->gws;
     MargWs& m = *h->mws;
     MargGradWs& mg = *h->mgws;
     const MargPlan& pl = h->marg.plan;
-    const MargGradPlan& gpl = d.gpl;
-    const int N = h->N, Npad = h->Npad, P = h->P, Q = pl.Q, q = pl.q, order = pl.order;
-    const int S = d.S, ld = d.ld, ldm = d.ldm, ldh = d.ldh, nslab = d.nslab, ngram = d.ngram, ntiles = P * (P + 1) / 2;
-    const size_t mstride = d.mstride, m_stride = d.m_stride, wstride = d.wstride;
+    const MargGradPlan& gpl = fac.gpl;
+    const int N = h->N, Npad = h->Npad, P = h->P, Q = pl.Q;
+    const int S = fac.S, ld = fac.ld, ldm = fac.ldm, ldh = S, ngram = Q * (Q + 1) / 2, ntiles = P * (P + 1) / 2;
+    const size_t mstride = fac.mstride, m_stride = fac.m_stride, wstride = (size_t)Q * NB * NB;
     const int* tab = m.Tab.p;
     double* Ah = w.A.p + Npad;          // what the kernels of marg_kernels.hpp take for [K | Ht]: Ht one block further right
     if (int rc = prof_launch(h, s, PSOAP_K_FILL, 0.0, (double)nb * 12.0 * N * (N + 1.0), [&] {
@@ -2926,14 +3000,8 @@ static int marg_grad_factor(psoap_chunk* h, const MargGradDims& d, hipStream_t s
         if (int rc = staged_row(h, s, sr, nb, k0, row.update_k + row.update_h > 0 ? &update : nullptr, TILE_FLOPS * units * nb))
             return rc;
     }
-    if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
-            hipLaunchKernelGGL(k_marg_rhs_partial, dim3(Q, nslab, nb), dim3(256), 0, s, (const double*)Ah, mstride, ld, Npad, Q, tab,
-                               (const double*)w.R.p, m.RPart.p, nslab);
-            hipLaunchKernelGGL(k_marg_rhs_finish, dim3((S + 255) / 256, nb), dim3(256), 0, s, (const double*)m.RPart.p, nslab, Npad,
-                               Q, tab, m.Rhs.p);
-        })) return rc;
-    double gunits = 0.0;
-    for (const MargTile& t : pl.tiles) gunits += (t.ti == t.tj ? 0.75 : 1.0) * (Npad - t.k0) / NB;
+    if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] { launch_marg_rhs(h, m, s, nb, Ah, mstride, ld, w.R.p); })) return rc;
+    double gunits = gram_units(pl, Npad);
     for (int sl = 0; sl < Q; ++sl)
         for (int tj = 0; tj < P; ++tj) gunits += P - std::min(P, std::max(pl.first[(size_t)pl.column[(size_t)sl]], tj));
     if (int rc = prof_launch(h, s, PSOAP_K_GRAD, TILE_FLOPS * gunits * nb, 0.0, [&] {
@@ -2953,85 +3021,11 @@ static int marg_grad_factor(psoap_chunk* h, const MargGradDims& d, hipStream_t s
     }
     // lnL and g = U_M^-1 y; z - Wh g; alpha_m
     return prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
-        hipLaunchKernelGGL(k_marg_finish, dim3(nb), dim3(256), 0, s, N, P, Q, q, order, (const MatAcc*)w.Acc.p,
-                           (const MatAcc*)m.AccM.p, (const double*)mg.Mx.p, m_stride, ldm, (const double*)m.WtM.p,
-                           (const double*)m.Rhs.p, m.Gam.p, (const double*)m.Sd.p, (const int*)m.Epoch.p, tab,
-                           (const double*)m.Ht.p, ldh, (const double*)h->dFl.p, m.Out.p, m.Beta.p, m.Flc.p, 1);
+        launch_marg_finish(h, w, m, s, nb, mg.Mx.p, m_stride, ldm, true);
         hipLaunchKernelGGL(k_marg_grad_resid, dim3(Npad / 4, nb), dim3(256), 0, s, (const double*)w.A.p, mstride, ld, Npad, Q,
                            tab, (const double*)w.R.p, (const double*)m.Gam.p, mg.Zt.p);
         launch_alpha(w, s, nb, mstride, ld, Npad, P, mg.Zt.p);
     });
-}
-
-// Group after group of matrices through marg_grad_factor, then the gradient's own tail -- on the handle's first stream behind
-// whatever the handle has in flight.  The grids come from the host (lwl) or, with lwl == nullptr, from the orbits as in grad_run.
-static int marg_grad_run(psoap_chunk* h, const char* who, int B, int c, const double* lwl, int model, const double* p_orb,
-                         const double* gp, double mu_GP, double* lnp, double* parts, double* grad_gp, double* grad_lwl,
-                         double* grad_mu, double* grad_orb, double* grad_vel)
-{
-    if (const char* why = marg_grad_check(B, c, h->marg.valid, h->marg.stale_weight)) FAIL(std::string(who) + ": " + why);
-    const bool orbits = lwl == nullptr;
-    DEVICE_SCOPE(h->device);
-    if (int rc = enter_device(h->device)) return rc;
-    const MargGradDims d = marg_grad_dims(h, B);
-    const int N = h->N, Npad = h->Npad, P = h->P, Q = h->marg.plan.Q;
-    const int S = d.S, ld = d.ld, ldm = d.ldm, G = d.G;
-    const size_t mstride = d.mstride, m_stride = d.m_stride;
-    const int ntiles = P * (P + 1) / 2;
-    const int ne = h->n_epochs, np = orbits ? orbit_n_params(model) : 0;
-    hipStream_t s = h->streams[0];
-    if (int rc = marg_grad_ws_need(h, d, s, true, c, np)) return rc;
-    GradWs& w = *h->gws;
-    MargWs& m = *h->mws;
-    MargGradWs& mg = *h->mgws;
-    std::vector<int> fast(orbits ? (size_t)B : 0, 0);
-    if (orbits)
-        if (int rc = grad_epoch_lists(h, w, s)) return rc;
-    h->recs.clear();
-    std::vector<double> out((size_t)B * 5);
-    for (int b0 = 0; b0 < B; b0 += G) {
-        const int nb = (B - b0 < G) ? B - b0 : G;
-        if (!orbits)
-            HIP_TRY(hipMemcpyAsync(w.Lwl, lwl + (size_t)b0 * c * N, sizeof(double) * (size_t)nb * c * N, hipMemcpyHostToDevice, s));
-        else if (int rc = orbit_front(h, w, s, nb, c, model, np, p_orb + (size_t)b0 * np))
-            return rc;
-        HIP_TRY(hipMemcpyAsync(w.Gp, gp + (size_t)b0 * 2 * c, sizeof(double) * (size_t)nb * 2 * c, hipMemcpyHostToDevice, s));
-        if (int rc = marg_grad_factor(h, d, s, nb, c, mu_GP)) return rc;
-        double cunits = 0.0;
-        for (int tj = 0; tj < P; ++tj) cunits += (double)(tj + 1) * (P - tj + Q);
-        if (int rc = prof_launch(h, s, PSOAP_K_GRAD, TILE_FLOPS * cunits * nb, 0.0, [&] {
-                with_components(c, [&](auto nc) {
-                    hipLaunchKernelGGL(k_marg_grad_contract<nc()>, dim3(ntiles, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s,
-                                       (const double*)w.A.p, mstride, ld, N, Npad, P, (const double*)w.Lwl.p, (const double*)w.Gp.p,
-                                       (const double*)w.Alpha.p, w.Part.p, (const double*)mg.Mx.p, m_stride, ldm, S);
-                });
-            })) return rc;
-        if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
-                hipLaunchKernelGGL(k_grad_finish, dim3(P + 1, nb), dim3(128), 0, s, (const double*)w.Part.p, (const double*)w.Alpha.p,
-                                   (const double*)w.Gp.p, c, N, Npad, P, w.GradGp.p, w.GradX.p, w.GradMu.p);
-            })) return rc;
-        HIP_TRY(hipMemcpyAsync(out.data() + (size_t)b0 * 5, m.Out, sizeof(double) * (size_t)nb * 5, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(grad_gp + (size_t)b0 * 2 * c, w.GradGp, sizeof(double) * (size_t)nb * 2 * c, hipMemcpyDeviceToHost, s));
-        if (grad_lwl)
-            HIP_TRY(hipMemcpyAsync(grad_lwl + (size_t)b0 * c * N, w.GradX, sizeof(double) * (size_t)nb * c * N, hipMemcpyDeviceToHost, s));
-        if (grad_mu) HIP_TRY(hipMemcpyAsync(grad_mu + b0, w.GradMu, sizeof(double) * nb, hipMemcpyDeviceToHost, s));
-        if (orbits)
-            if (int rc = orbit_back(h, w, s, nb, c, np, grad_orb + (size_t)b0 * np, grad_vel ? grad_vel + (size_t)b0 * c * ne : nullptr,
-                                    fast.data() + b0))
-                return rc;
-        HIP_TRY(hipStreamSynchronize(s));       // the next group reuses the workspace and the caller's arrays are pageable
-    }
-    if (collect_timings(h)) return 1;
-    // the conventions of psoap_chunk_lnlike_marg and psoap_chunk_lnlike_grad: a negative hyper-parameter, a K or an M that
-    // does not factor, a faster-than-light orbit -> -inf, and no gradient there
-    for (int b = 0; b < B; ++b) {
-        lnp[b] = proposal_refused(gp, c, b, orbits ? fast.data() : nullptr) ? -INFINITY : out[(size_t)b * 5];
-        const bool bad = lnp[b] == -INFINITY;
-        if (parts)
-            for (int k = 0; k < 4; ++k) parts[(size_t)b * 4 + k] = bad ? NAN : out[(size_t)b * 5 + 1 + k];
-        if (bad) poison_gradient(b, c, N, ne, np, grad_gp, grad_lwl, grad_mu, grad_orb, grad_vel);
-    }
-    return 0;
 }
 
 extern "C" int psoap_chunk_lnlike_marg_grad(psoap_chunk* h, int B, int c, const double* lwl, const double* gp, double mu_GP,
@@ -3039,8 +3033,8 @@ extern "C" int psoap_chunk_lnlike_marg_grad(psoap_chunk* h, int B, int c, const 
 {
     if (!h || !lwl || !gp || !lnp || !grad_gp) FAIL("psoap_chunk_lnlike_marg_grad: bad arguments");
     if (h->stream.open) FAIL("psoap_chunk_lnlike_marg_grad: the handle has an open stream (psoap_stream_close first)");
-    return marg_grad_run(h, "psoap_chunk_lnlike_marg_grad", B, c, lwl, -1, nullptr, gp, mu_GP, lnp, parts, grad_gp, grad_lwl,
-                         grad_mu, nullptr, nullptr);
+    return grad_run(h, "psoap_chunk_lnlike_marg_grad", true, B, c, lwl, -1, nullptr, gp, mu_GP, lnp, parts, grad_gp, grad_lwl,
+                    grad_mu, nullptr, nullptr);
 }
 
 extern "C" int psoap_chunk_lnprob_marg_grad(psoap_chunk* h, int B, int model, const double* p_orb, const double* gp, double mu_GP,
@@ -3051,8 +3045,8 @@ extern "C" int psoap_chunk_lnprob_marg_grad(psoap_chunk* h, int B, int model, co
     if (!h->dGrid || !h->dDates) FAIL("psoap_chunk_lnprob_marg_grad: call psoap_chunk_set_grid and psoap_chunk_set_dates first");
     if (h->stream.open) FAIL("psoap_chunk_lnprob_marg_grad: the handle has an open stream (psoap_stream_close first)");
     if (int rc = check_orbits(model, B, p_orb)) return rc;
-    return marg_grad_run(h, "psoap_chunk_lnprob_marg_grad", B, orbit_n_components(model), nullptr, model, p_orb, gp, mu_GP, lnp,
-                         nullptr, grad_gp, nullptr, grad_mu, grad_orb, grad_vel);
+    return grad_run(h, "psoap_chunk_lnprob_marg_grad", true, B, orbit_n_components(model), nullptr, model, p_orb, gp, mu_GP, lnp,
+                    nullptr, grad_gp, nullptr, grad_mu, grad_orb, grad_vel);
 }
 
 // frees the device side of the baseline and the workspace; the baseline itself stays set (the next call builds Ht again)

@@ -30,10 +30,11 @@ for _p in (ROOT, TESTS):
 
 import fisher_reference as fr  # noqa: E402
 import grad_reference as gr  # noqa: E402
+import marg_fisher_reference as mf  # noqa: E402
 import marg_reference as mr  # noqa: E402
 import orbit_grad_reference as ogr  # noqa: E402
 from psoap_amd import synthetic as syn  # noqa: E402
-from psoap_amd._lib import K_NAMES  # noqa: E402
+from psoap_amd._lib import K_NAMES, dptr  # noqa: E402
 from psoap_amd.utils import MODEL_ID  # noqa: E402
 
 PIN_PATH = os.path.join(HERE, "analysis_pin_v1.npz")
@@ -127,12 +128,27 @@ def _fisher(grid_tangents):
 
 
 @contextlib.contextmanager
-def _loo(name, epochs):
+def _fisher_marg(name, kind, grid_tangents, negative=False):
+    """as ``_fisher`` under the case's baseline; ``negative``: the second hyper-parameter changes sign"""
+    case = mr.case_named(name)
+    ch, gp, c = mr.case_chunk(case), mr.case_gp(case), case[2]
+    if negative:
+        gp[1] = -gp[1]
+    tan_lwl, tan_gp = mf.case_tangents(case)
+    pick = [1, 2 * c] if grid_tangents else [0, 1]
+    with _handle(ch, baseline=(case, kind)) as h:
+        yield h, lambda: _named(("F", "F_mu"), h.fisher_marg(ch.lwls, gp, tan_gp[pick], tan_lwl[pick] if grid_tangents else None,
+                                                             want_mu=True))
+
+
+@contextlib.contextmanager
+def _loo(name, epochs, kind=None):
+    """``kind``: under the case's baseline with that weight (``loo_marg``)"""
     case = mr.case_named(name)
     ch, gp = mr.case_chunk(case), mr.case_gp(case)
-    with _handle(ch) as h:
+    with _handle(ch, baseline=None if kind is None else (case, kind)) as h:
         def call():
-            r = h.loo(ch.lwls, gp, mr.MU_GP, *((ch.epoch_index, ch.n_epochs) if epochs else ()))
+            r = (h.loo if kind is None else h.loo_marg)(ch.lwls, gp, mr.MU_GP, *((ch.epoch_index, ch.n_epochs) if epochs else ()))
             return {k: getattr(r, k) for k in LOO_OUT if getattr(r, k) is not None}
         yield h, call
 
@@ -155,6 +171,19 @@ def _lnlike_marg_grad():
     lw, gps = _batch(case, 10, 9801)
     with _handle(mr.case_chunk(case), baseline=(case, "flux")) as h:
         yield h, lambda: _named(GRAD_OUT, h.lnlike_marg_grad(lw, gps, mr.MU_GP))
+
+
+@contextlib.contextmanager
+def _lnlike_marg_grad_parts():
+    """one group of three, the one in the middle refused; ``parts`` asked for, which ``ChunkHandle.lnlike_marg_grad`` does not"""
+    case = mr.case_named("c")
+    lw, gps = _batch(case, 3, 9802, negative=1)
+    with _handle(mr.case_chunk(case), baseline=(case, "one")) as h:
+        def call():
+            parts = np.empty((3, 4))
+            got = h._lnlike_grad("psoap_chunk_lnlike_marg_grad", lw, gps, mr.MU_GP, dptr(parts))
+            return dict(_named(GRAD_OUT, got), parts=parts)
+        yield h, call
 
 
 @contextlib.contextmanager
@@ -181,6 +210,12 @@ CALLS = {
     "lnlike_marg_grad-f-flux-B10": _lnlike_marg_grad,
     "lnprob_marg_grad-SB2-N129-B3-fast": lambda: _lnprob_grad(True),
     "staged-lnlike_batch-c-B3": _staged_lnlike,
+    "fisher_marg-c-one-T2-no-grid-tangents": lambda: _fisher_marg("c", "one", False),      # N = 129, Q = 1
+    "fisher_marg-f-flux-T2-grid-tangents": lambda: _fisher_marg("f", "flux", True),        # Q = 2: the second K loop spans two slots
+    "loo_marg-e-flux-epochs": lambda: _loo("e", True, "flux"),
+    "loo_marg-f-one-pixels-only": lambda: _loo("f", False, "one"),
+    "fisher_marg-c-one-negative": lambda: _fisher_marg("c", "one", False, negative=True),      # the NaN convention
+    "lnlike_marg_grad-c-one-B3-negative": _lnlike_marg_grad_parts,          # one group, a refusal: parts, the poisoned gradient
 }
 
 
