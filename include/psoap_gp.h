@@ -384,6 +384,42 @@ int psoap_chunk_loo_marg(psoap_chunk *h, int c, const double *lwl, const double 
                          double *ep_resid,
                          double *ep_chi2, double *ep_logp, int32_t *ep_npix);
 
+/* ---- component spectra under the marginalised continuum ------------------------------------------
+ * psoap_chunk_predict_marg and psoap_chunk_predict_marg_var are psoap_chunk_predict and psoap_chunk_predict_var with
+ * Kt = K + Ht Ht^T (the baseline of psoap_chunk_set_baseline) in the place of the data covariance K: arguments, output
+ * shapes and the NULL rule of Sigma_out are their plain twins'.  The continuum itself is not predicted (beta and fl_cor of
+ * psoap_chunk_lnlike_marg give it); it enters through the data covariance only, so the component spectra carry its
+ * uncertainty instead of a continuum frozen at its posterior mean.  With r = fl - offset, Cx (R x N), A and m0 exactly as
+ * the plain mode builds them (psoap_predict above):
+ *   mu = m0 + Cx Kt^-1 r,   Sigma = A - Cx Kt^-1 Cx^T;
+ *   Wc = U^-T Cx^T, Wh = U^-T Ht, z = U^-T r  (K = U^T U);  M = I + Wh^T Wh = U_M^T U_M,  G = Wh^T Wc (S x R, S = 128 Q),
+ *   bt = Wh^T z,  Y = U_M^-T G,  y = U_M^-T bt;
+ *   mu = m0 + Wc^T z - Y^T y,   Sigma = A - Wc^T Wc + Y^T Y,   var = prior - colnorm^2(Wc) + colnorm^2(Y):
+ * the plain Sigma plus a positive semi-definite term of rank <= q.  The staged factorisation runs on [K | Cx^T | Ht]
+ * (ld = Npad + Rpad + 128 Q; block row p updates and solves K's own columns, all of Cx^T and the slots of Ht that can be
+ * non-zero there), one launch forms [M | G] tile by tile in the MFMA accumulators, the same staged kernels factor it
+ * with bt as right-hand side, which leaves Y and y, and one workgroup per upper tile of Sigma runs two K loops (depth
+ * Npad over Wc, depth S over Y) on one accumulator set and mirrors the tile (csrc/marg_predict_kernels.hpp,
+ * csrc/marg_predict_plan.hpp).  No explicit inverse.  No atomics, every sum in an order fixed by (N, c, M, mode,
+ * baseline layout): the same arguments give the same bits, mu has the same bits whether Sigma, the variances or neither
+ * is asked for, Sigma == Sigma^T bit for bit, and psoap_chunk_predict keeps its bits on a handle with a baseline.
+ * Modes: 0 with c = 2 or 3, 1 with c = 2, 2 with c = 1.  Mode 1 with c = 3 (the transposed mean of predict_f_g_h_sum,
+ * covariance.py:294) is refused, as are an open stream and a handle without a baseline or with a stale one -- the
+ * baseline's with psoap_chunk_lnlike_marg's messages.
+ * status_out: 0 ok; 1 K is not positive definite or M does not factor -- every output is then NaN and the call itself returns 0.
+ * Workspace: 8 Npad (Npad + Rpad + 128 Q) bytes of [K | Cx^T | Ht] and, with Sigma, 8 Rpad^2 in the handle's predict
+ * workspace (grown, shared with psoap_chunk_predict; psoap_chunk_predict_release); 8 * 128 Q (128 Q + Rpad) bytes of
+ * [M | G] and a few vectors beside the baseline's device side (psoap_chunk_marg_release).  Rpad = R rounded up to 128.
+ * psoap_chunk_predict_timings reports the call: factor_ms = fill, both staged factorisations and the Gram launch,
+ * sigma_ms = mean + prior fill + Sigma (or the variances); flops = the plain F_pred + N S (S + R) + S^3 / 3 + S^2 R
+ * + S R^2 on padded sizes (S R^2, like N R^2, only when Sigma is formed; 2 S R for the variances). */
+int psoap_chunk_predict_marg(psoap_chunk *h, int mode, int c, int M, const double *lwl,
+                             const double *lwl_pred, const double *mu_c, const double *gp,
+                             double *mu_out, double *Sigma_out /* may be NULL */, int *status_out);
+int psoap_chunk_predict_marg_var(psoap_chunk *h, int mode, int c, int M, const double *lwl,
+                                 const double *lwl_pred, const double *mu_c, const double *gp,
+                                 double *mu_out, double *var_out, int *status_out);
+
 /* Split-phase form of psoap_lnlike_batch: upload (H2D, async, on a copy stream of
  * its own), eval (kernels only, async), fetch (sync + D2H of B doubles).
  * A handle holds TWO proposal batches: an upload always goes to the one that is

@@ -489,7 +489,13 @@ class ChunkHandle:
         """``predict_*`` on this chunk's resident ``fl`` / ``sigma`` (include/psoap_gp.h: psoap_chunk_predict;
         mode 0 components, 1 sum, 2 predict_f).  The workspace stays with the handle.
         ``want_sigma``: True -> (mu, Sigma); "diag" -> (mu, diag(Sigma)) without ever forming Sigma
-        (psoap_chunk_predict_var); False -> mu."""
+        (psoap_chunk_predict_var); False -> mu.  Always under the plain ``K``, also on a handle with a baseline:
+        ``predict_marg`` is the form under ``K + H Lambda H^T``."""
+        return self._predict("psoap_chunk_predict", mode, lwls, lwls_predict, mu_c, gp, want_sigma)
+
+    def _predict(self, entry, mode, lwls, lwls_predict, mu_c, gp, want_sigma):
+        """the body of ``predict`` and ``predict_marg``: ``entry`` names the library's function, ``entry + "_var"`` its
+        mean-and-variances form"""
         lwls = as_f64(np.atleast_2d(lwls))
         pred = as_f64(np.atleast_2d(lwls_predict))
         c = lwls.shape[0]
@@ -505,18 +511,29 @@ class ChunkHandle:
             if want_sigma != "diag":
                 raise ValueError('want_sigma must be True, False or "diag"')
             var = np.empty(R)
-            check(self._L.psoap_chunk_predict_var(self._h, int(mode), c, M, dptr(lwls), dptr(pred), dptr(mu_c), dptr(gp),
-                                                  dptr(mu), dptr(var), ctypes.byref(status)), "psoap_chunk_predict_var")
+            check(getattr(self._L, entry + "_var")(self._h, int(mode), c, M, dptr(lwls), dptr(pred), dptr(mu_c), dptr(gp),
+                                                   dptr(mu), dptr(var), ctypes.byref(status)), entry + "_var")
             if status.value != 0:
                 raise np.linalg.LinAlgError("data covariance matrix is not positive definite")
             return mu, var
         Sigma = np.empty((R, R)) if want_sigma else None
-        check(self._L.psoap_chunk_predict(self._h, int(mode), c, M, dptr(lwls), dptr(pred), dptr(mu_c), dptr(gp),
-                                          dptr(mu), None if Sigma is None else dptr(Sigma), ctypes.byref(status)),
-              "psoap_chunk_predict")
+        check(getattr(self._L, entry)(self._h, int(mode), c, M, dptr(lwls), dptr(pred), dptr(mu_c), dptr(gp),
+                                      dptr(mu), None if Sigma is None else dptr(Sigma), ctypes.byref(status)), entry)
         if status.value != 0:
             raise np.linalg.LinAlgError("data covariance matrix is not positive definite")
         return (mu, Sigma) if want_sigma else mu
+
+    def predict_marg(self, mode: int, lwls, lwls_predict, mu_c, gp, want_sigma=True):
+        """``predict`` under the baseline of ``set_baseline`` (include/psoap_gp.h: psoap_chunk_predict_marg): the same
+        arguments and return shapes, the conditional of the components under ``K + H Lambda H^T`` -- the continuum of
+        every epoch integrated out, its uncertainty in ``Sigma`` / the variances, instead of a continuum frozen at its
+        posterior mean.  Mode 0 with two or three components, mode 1 with two, mode 2 with one.  ``LinAlgError`` when ``K``
+        is not positive definite (or the Gram matrix does not factor); ``PsoapError`` without a baseline."""
+        return self._predict("psoap_chunk_predict_marg", mode, lwls, lwls_predict, mu_c, gp, want_sigma)
+
+    def predict_release(self):
+        """Free the predict workspace (``predict`` and ``predict_marg`` share it); the next call allocates it again."""
+        check(self._L.psoap_chunk_predict_release(self._h), "psoap_chunk_predict_release")
 
     def predict_timings(self) -> dict:
         t = _lib.PredictTimings()

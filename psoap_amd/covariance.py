@@ -456,6 +456,23 @@ def loo_marginal(lwls, fl, sigma, gp, x, epoch_index, order, prior_sd, weight=No
     return res
 
 
+def predict_marginal(lwls, fl, sigma, lwls_predict, mus, gp, x, epoch_index, order, prior_sd, weight=None, mode=0,
+                     want_sigma=True):
+    """The component spectra of one chunk under the baseline of ``lnlike_marginal`` (``ChunkHandle.predict_marg``):
+    ``predict_f`` / ``predict_f_g`` / ``predict_f_g_h`` (``mode`` 2 with one row of ``lwls``, else 0) or ``predict_f_g_sum``
+    (``mode`` 1) with ``K + H Lambda H^T`` as the data covariance, so ``Sigma`` carries the continuum's uncertainty.
+    ``lwls`` (c, N), ``lwls_predict`` (c, M), ``mus`` (c,) -- one value for modes 1 and 2 --, ``gp`` (2c,); the baseline
+    arguments as ``lnlike_marginal``.  ``want_sigma``: True -> ``(mu, Sigma)``, ``"diag"`` -> ``(mu, diag(Sigma))``, False ->
+    ``mu``.  ``LinAlgError`` where the plain predict raises it: a data covariance that is not positive definite."""
+    gp, lw, ep, _negative = _marginal_front(lwls, gp, epoch_index)
+    h = _chunk_for(fl, sigma)
+    if not hasattr(h, "predict_marg"):
+        raise _lib.PsoapError("predict_marginal needs the device in this process (PSOAP_GPU_SERVER serves values only)")
+    h.set_baseline(order, x, ep, int(ep.max()) + 1, prior_sd, weight)      # (every call, as ``_marginal``)
+    return h.predict_marg(int(mode), lw, np.stack([as_f64(w) for w in np.atleast_2d(lwls_predict)]), np.atleast_1d(mus), gp,
+                          want_sigma)
+
+
 def velocity_gradient(grad_lwl, epoch_index, n_epochs):
     """``dlnL/dv[c, e]`` from ``dlnL/dlwl[c, i]``: the rest-frame grids are ``lwl - v[c, epoch]/c_kms``
     (``data.replicate_wls``), so ``dlnL/dv[c, e] = -(1/c_kms) sum_{i in epoch e} dlnL/dlwl[c, i]``.

@@ -37,6 +37,7 @@
 #include "marg_kernels.hpp"
 #include "marg_grad_kernels.hpp"
 #include "marg_fisher_kernels.hpp"
+#include "marg_predict_kernels.hpp"
 #include "abi_error.hpp"
 #include "plan_abi.hpp"
 #include "share.hpp"
@@ -226,6 +227,8 @@ struct psoap_chunk {
     std::unique_ptr<psoap::MargWs> mws;
     // gradient of that likelihood: what it needs beyond the two workspaces above (psoap_chunk_marg_release)
     std::unique_ptr<psoap::MargGradWs> mgws;
+    // prediction under it: what it needs beyond the predict workspace and the two above (psoap_chunk_marg_release)
+    std::unique_ptr<psoap::MargPredictWs> mpws;
     // streamed evaluation (psoap_stream_*)
     StreamState stream;
     bool dev_locked = false;     // this handle holds a reference on the device's inter-process lock (device_lock_acquire)
@@ -309,6 +312,7 @@ static int configure_kernels(int device)
     HIP_TRY(marg_configure_kernels());
     HIP_TRY(marg_grad_configure_kernels());
     HIP_TRY(marg_fisher_configure_kernels());
+    HIP_TRY(marg_predict_configure_kernels());
     if (done.size() <= (size_t)device) done.resize((size_t)device + 1, 0);
     done[device] = 1;
     return 0;
@@ -3055,6 +3059,7 @@ extern "C" int psoap_chunk_marg_release(psoap_chunk* h)
     return release_ws(h, [&] {
         h->mws.reset();
         h->mgws.reset();
+        h->mpws.reset();
     });
 }
 
@@ -3308,6 +3313,241 @@ extern "C" int psoap_chunk_predict_release(psoap_chunk* h)
     if (set_dev(h)) return 1;
     h->pws.reset();
     return 0;
+}
+
+// ---- predict under the marginalised continuum (marg_predict_kernels.hpp) -----------------------------------
+// One matrix through the staged factorisation of [K | Cx^T | Ht] in the handle's predict workspace, the Gram launch, the
+// staged factorisation of [M | G] beside the baseline's device side, then mean, Sigma or the variances -- on the handle's
+// first stream behind whatever the handle has in flight, as the other analysis paths.  The plain predict path, its
+// persistent launch and its task lists are not touched: only its workspace is shared (grown, never shrunk).
+static int marg_predict_run(psoap_chunk* h, const char* who, int mode, int c, int M, const double* lwl, const double* lwl_pred,
+                            const double* mu_c, const double* gp, double* mu_out, double* Sigma_out, double* var_out,
+                            int* status_out)
+{
+    if (!h || !lwl || !lwl_pred || !mu_c || !gp || !mu_out) FAIL(std::string(who) + ": bad arguments");
+    if (h->stream.open) FAIL(std::string(who) + ": the handle has an open stream (psoap_stream_close first)");
+    if (const char* why = marg_predict_check(mode, c, M, h->marg.valid, h->marg.stale_weight)) FAIL(std::string(who) + ": " + why);
+    const auto t_begin = std::chrono::steady_clock::now();
+    SigmaPin pin;         // declared first, as in predict_run: its destructor drops the registration on every return path
+    DEVICE_SCOPE(h->device);
+    if (int rc = enter_device(h->device)) return rc;
+    if (!h->pws) {
+        h->pws.reset(new PredictWs());
+        h->pws->workers = dag_two_per_cu(h->dag_grid, h->n_cus);       // (as chunk_predict: the plain call finds what it expects)
+        h->pws->n_cus = h->n_cus;
+    }
+    if (!h->mws) h->mws.reset(new MargWs());
+    if (!h->mpws) h->mpws.reset(new MargPredictWs());
+    PredictWs& ws = *h->pws;
+    MargWs& m = *h->mws;
+    MargPredictWs& mp = *h->mpws;
+    const MargPlan& pl = h->marg.plan;
+    marg_predict_plan(pl, mode, c, M, mp.plan);
+    const MargPredictPlan& g = mp.plan;
+    const int N = h->N, Npad = h->Npad, P = h->P, Q = pl.Q, S = g.S, ld = g.ld, ldm = g.ldm;
+    const int Rq = g.R, Rt = g.Rt, Rq_pad = NB * Rt, St = g.St;
+    const int nslab = (Npad + 255) / 256, nslab_y = (S + 255) / 256, ntiles = (int)g.gram.size();
+    const double offset = (mode == 0 || mode == 1) ? 1.0 : mu_c[0];      // :140,:184,:248 vs :52 (mode 1 here is c == 2)
+    if (!ws.stream) {
+        HIP_TRY(ws.stream.create());
+        for (Event& e : ws.ev) HIP_TRY(e.create(hipEventDefault));
+    }
+    if (Sigma_out) pin.start(Sigma_out, sizeof(double) * (size_t)Rq * Rq, h->device);
+    hipStream_t s = h->streams[0];
+    HIP_TRY(ws.K.need((size_t)Npad * ld));
+    HIP_TRY(ws.W.need(WT_STRIDE));
+    HIP_TRY(ws.R.need(Npad));
+    HIP_TRY(ws.Acc.need(ACC_ROWS + 1));
+    HIP_TRY(ws.Lwl.need((size_t)c * N));
+    HIP_TRY(ws.Pred.need((size_t)c * M));
+    HIP_TRY(ws.Gp.need(6));
+    HIP_TRY(ws.Mu.need(Rq_pad));
+    HIP_TRY(ws.M0.need(Rq_pad));
+    HIP_TRY(ws.Part.need((size_t)nslab * Rq_pad));
+    HIP_TRY(ws.hSmall.need(4 * (size_t)Rq_pad + 8));
+    HIP_TRY(mp.Mx.need((size_t)S * ldm));
+    HIP_TRY(mp.PartY.need((size_t)nslab_y * Rq_pad));
+    HIP_TRY(mp.Tiles.need((size_t)ntiles));
+    HIP_TRY(mp.AccTot.need(2));
+    if (int rc = marg_ws_need(h, m, 1, false)) return rc;
+    if (int rc = marg_basis(h, m, s)) return rc;
+    double* h_m0 = ws.hSmall;               // pinned: (Rq_pad) each
+    double* h_mu = h_m0 + Rq_pad;
+    double* h_var = h_mu + Rq_pad;
+    double* h_prior = h_var + Rq_pad;
+    MatAcc* h_acc = reinterpret_cast<MatAcc*>(h_prior + Rq_pad);      // the totals of K's records, then of M's
+    double *dK = ws.K, *dW = ws.W, *dR = ws.R, *dLwl = ws.Lwl, *dPred = ws.Pred, *dGp = ws.Gp, *dMx = mp.Mx;
+    double* Ah = dK + Rq_pad;      // what the kernels of marg_kernels.hpp take for [K | Ht]: Ht lies Rpad further right
+    const double* Wc = dK + Npad;
+    const double* Y = dMx + S;
+    const int* tab = m.Tab.p;
+    GpHost gall;
+    for (int k = 0; k < 6; ++k) gall.v[k] = (k < 2 * c) ? gp[k] : 0.0;
+    h->recs.clear();
+    const auto t_ev0 = std::chrono::steady_clock::now();
+    HIP_TRY(hipEventRecord(ws.ev[0], s));
+    HIP_TRY(hipMemcpyAsync(dLwl, lwl, sizeof(double) * (size_t)c * N, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(dPred, lwl_pred, sizeof(double) * (size_t)c * M, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(dGp, gp, sizeof(double) * 2 * c, hipMemcpyHostToDevice, s));
+    for (int q = 0; q < Rq; ++q) h_m0[q] = (mode == 0) ? mu_c[q / M] : mu_c[0];
+    HIP_TRY(hipMemcpyAsync(ws.M0, h_m0, sizeof(double) * Rq, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(mp.Tiles, g.gram.data(), sizeof(MargPredictTile) * (size_t)ntiles, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(ws.ev[1], s));
+    // [K | Cx^T | Ht]: cleared (padding rows and columns are exact zeros), K's upper tiles, Cx^T as the staged branch of
+    // predict_run fills it, Ht from each slot's first block row on
+    if (int rc = prof_launch(h, s, PSOAP_K_FILL, 0.0, 12.0 * N * (N + 1.0), [&] {
+            hipLaunchKernelGGL(k_zero, dim3(2048), dim3(256), 0, s, dK, (size_t)Npad * ld);
+            with_components(c, [&](auto nc) {
+                hipLaunchKernelGGL(k_fill_sym<nc()>, dim3(P * (P + 1) / 2, 1), dim3(256), 0, s, dK, (size_t)0, ld, N, P,
+                                   (const double*)dLwl, (const double*)dGp, (const double*)h->dSigma.p, 1);
+            });
+            if (mode == 0) {
+                for (int k = 0; k < c; ++k) {
+                    GpHost g1;
+                    g1.v[0] = gp[2 * k];
+                    g1.v[1] = gp[2 * k + 1];
+                    launch_region_c(s, 1, dK, (size_t)ld, Npad + k * M, N, M, dLwl + (size_t)k * N, 0, dPred + (size_t)k * M, 0, g1, 0, 0.0);
+                }
+            } else {
+                launch_region_c(s, c, dK, (size_t)ld, Npad, N, M, dLwl, (size_t)N, dPred, (size_t)M, gall, 0, 0.0);
+            }
+            hipLaunchKernelGGL(k_marg_load, dim3(Q * P, 1), dim3(256), 0, s, Ah, (size_t)0, ld, Npad, P, (const double*)m.Ht.p, S, tab);
+        })) return rc;
+    if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
+            hipLaunchKernelGGL(k_init_rhs, dim3((Npad + 255) / 256, 1), dim3(256), 0, s, dR, Npad, N, h->dFl, offset, ws.Acc.p);
+        })) return rc;
+    // block row p: the rest of K's row, all of Cx^T and the slots of Ht whose first non-zero block row is <= p -- one
+    // contiguous range of tile columns (k_marg_panel_update with P + Rt in the place of P)
+    for (int p = 0; p < P; ++p) {
+        const int k0 = p * NB;
+        const MargPredictRow& row = g.rows[(size_t)p];
+        auto update = [&] {
+            hipLaunchKernelGGL(k_marg_panel_update, dim3(row.update, 1), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, dK, (size_t)0, ld, k0,
+                               P + Rt, tab);
+        };
+        const StagedRow sr{dK, 0, ld, dR, Npad, ws.Acc.p, dW, (size_t)NB * NB, row.strip};
+        if (int rc = staged_row(h, s, sr, 1, k0, row.update > 0 ? &update : nullptr, TILE_FLOPS * p * row.update)) return rc;
+    }
+    if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] { launch_marg_rhs(h, m, s, 1, Ah, 0, ld, dR); })) return rc;
+    if (int rc = prof_launch(h, s, PSOAP_K_GRAD, TILE_FLOPS * marg_predict_gram_units(g), 0.0, [&] {
+            hipLaunchKernelGGL(k_marg_predict_gram, dim3(ntiles), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)dK, ld, Npad,
+                               (const MargPredictTile*)mp.Tiles.p, dMx, ldm);
+        })) return rc;
+    // [M | G]: M = U_M^T U_M with bt alongside; the appended block becomes Y = U_M^-T G and the right-hand side y
+    for (int p = 0; p < Q; ++p) {
+        const int k0 = p * NB;
+        const MargPredictRow& row = g.mrows[(size_t)p];
+        const StagedRow mrow{dMx, 0, ldm, m.Rhs.p, S, m.AccM.p, m.WtM.p + (size_t)p * NB * NB, (size_t)Q * NB * NB, row.strip};
+        auto update = [&] {
+            hipLaunchKernelGGL(k_panel_update, dim3(row.update, 1), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, dMx, (size_t)0, ldm, k0);
+        };
+        if (int rc = staged_row(h, s, mrow, 1, k0, row.update > 0 ? &update : nullptr, TILE_FLOPS * p * row.update)) return rc;
+    }
+    HIP_TRY(hipEventRecord(ws.ev[2], s));
+    // mean: m0 + Wc^T z - Y^T y, the two sums each in two fixed-order stages; the totals of both factorisations' records
+    if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
+            hipLaunchKernelGGL(k_gemv_t_partial, dim3(Rt, nslab), dim3(256), 0, s, Wc, (size_t)ld, Npad, Rq, (const double*)dR, ws.Part.p);
+            hipLaunchKernelGGL(k_gemv_t_partial, dim3(Rt, nslab_y), dim3(256), 0, s, Y, (size_t)ldm, S, Rq, (const double*)m.Rhs.p,
+                               mp.PartY.p);
+            hipLaunchKernelGGL(k_marg_predict_mean, dim3((Rq + 255) / 256), dim3(256), 0, s, (const double*)ws.Part.p, nslab,
+                               (const double*)mp.PartY.p, nslab_y, Rq, (const double*)ws.M0.p, ws.Mu.p);
+            hipLaunchKernelGGL(k_acc_total, dim3(1), dim3(1), 0, s, (const MatAcc*)ws.Acc.p, P, mp.AccTot.p);
+            hipLaunchKernelGGL(k_acc_total, dim3(1), dim3(1), 0, s, (const MatAcc*)m.AccM.p, Q, mp.AccTot.p + 1);
+        })) return rc;
+    HIP_TRY(hipMemcpyAsync(h_mu, ws.Mu, sizeof(double) * Rq, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(h_acc, mp.AccTot, 2 * sizeof(MatAcc), hipMemcpyDeviceToHost, s));
+    bool sigma_direct = false;
+    if (Sigma_out) {
+        HIP_TRY(ws.S.need((size_t)Rq_pad * Rq_pad));
+        double* dS = ws.S;
+        // the prior covariance of the prediction in the upper tiles, as the separate product of predict_run has it; then
+        // every upper tile in one launch (predict_run: launching tile rows one after the other serialises them)
+        if (int rc = prof_launch(h, s, PSOAP_K_GRAD, TILE_FLOPS * g.sigma_tiles * (P + Q), 0.0, [&] {
+                if (mode == 0) {
+                    hipLaunchKernelGGL(k_zero, dim3(1024), dim3(256), 0, s, dS, (size_t)Rq_pad * Rq_pad);
+                    for (int k = 0; k < c; ++k) {
+                        GpHost g1;
+                        g1.v[0] = gp[2 * k];
+                        g1.v[1] = gp[2 * k + 1];
+                        launch_region_c(s, 1, dS + (size_t)k * M * Rq_pad, (size_t)Rq_pad, k * M, M, M, dPred + (size_t)k * M, 0,
+                                         dPred + (size_t)k * M, 0, g1, 1, 0.0);
+                    }
+                } else {
+                    const double nug = (mode == 1) ? 1e-8 : 0.0;      // predict_f_g_sum's nugget (:165)
+                    if (Rq_pad != Rq) hipLaunchKernelGGL(k_zero, dim3(1024), dim3(256), 0, s, dS, (size_t)Rq_pad * Rq_pad);
+                    launch_region_c(s, c, dS, (size_t)Rq_pad, 0, M, M, dPred, (size_t)M, dPred, (size_t)M, gall, 1, nug);
+                }
+                hipLaunchKernelGGL(k_marg_predict_sigma, dim3(g.sigma_tiles), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, Wc, (size_t)ld, Npad,
+                                   Y, (size_t)ldm, S, dS, (size_t)Rq_pad, St, 0);
+            })) return rc;
+        HIP_TRY(hipEventRecord(ws.ev[3], s));
+        const bool locked = pin.wait();
+        if (locked) {
+            pin.queued_on(s);
+            HIP_TRY(hipMemcpy2DAsync(Sigma_out, sizeof(double) * Rq, dS, sizeof(double) * Rq_pad, sizeof(double) * Rq, (size_t)Rq,
+                                     hipMemcpyDeviceToHost, s));
+        }
+        sigma_direct = locked;
+    }
+    if (var_out) {
+        HIP_TRY(ws.Var.need(Rq_pad));
+        HIP_TRY(ws.Prior.need(Rq_pad));
+        for (int q = 0; q < Rq; ++q) h_prior[q] = predict_prior_variance(mode, c, M, q, gp);
+        HIP_TRY(hipMemcpyAsync(ws.Prior, h_prior, sizeof(double) * Rq, hipMemcpyHostToDevice, s));
+        if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
+                hipLaunchKernelGGL(k_colnorm_partial, dim3(Rt, nslab), dim3(256), 0, s, Wc, (size_t)ld, Npad, Rq, ws.Part.p);
+                hipLaunchKernelGGL(k_colnorm_partial, dim3(Rt, nslab_y), dim3(256), 0, s, Y, (size_t)ldm, S, Rq, mp.PartY.p);
+                hipLaunchKernelGGL(k_marg_predict_var, dim3((Rq + 255) / 256), dim3(256), 0, s, (const double*)ws.Part.p, nslab,
+                                   (const double*)mp.PartY.p, nslab_y, Rq, (const double*)ws.Prior.p, ws.Var.p);
+            })) return rc;
+        HIP_TRY(hipMemcpyAsync(h_var, ws.Var, sizeof(double) * Rq, hipMemcpyDeviceToHost, s));
+    }
+    if (!Sigma_out) HIP_TRY(hipEventRecord(ws.ev[3], s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (Sigma_out && !sigma_direct)
+        HIP_TRY(hipMemcpy2D(Sigma_out, sizeof(double) * Rq, ws.S, sizeof(double) * Rq_pad, sizeof(double) * Rq, Rq,
+                            hipMemcpyDeviceToHost));
+    pin.release();
+    if (collect_timings(h)) return 1;
+    // K not positive definite or an M that does not factor: status 1 and NaN in every output (the plain predict's convention)
+    const bool bad = h_acc[0].info != 0.0 || h_acc[1].info != 0.0;
+    if (status_out) *status_out = bad ? 1 : 0;
+    for (int q = 0; q < Rq; ++q) mu_out[q] = bad ? NAN : h_mu[q];
+    if (var_out)
+        for (int q = 0; q < Rq; ++q) var_out[q] = bad ? NAN : h_var[q];
+    if (Sigma_out && bad)
+        for (size_t k = 0; k < (size_t)Rq * Rq; ++k) Sigma_out[k] = NAN;
+    const auto t_end = std::chrono::steady_clock::now();
+    {
+        float a = 0.f, b = 0.f, cms = 0.f;
+        (void)hipEventElapsedTime(&a, ws.ev[0], ws.ev[3]);
+        (void)hipEventElapsedTime(&b, ws.ev[1], ws.ev[2]);
+        (void)hipEventElapsedTime(&cms, ws.ev[2], ws.ev[3]);
+        PredictTimes& t = ws.times;
+        t.device_ms = a;
+        t.factor_ms = b;
+        t.sigma_ms = cms;
+        t.total_ms = std::chrono::duration<double, std::milli>(t_end - t_begin).count();
+        const double pre_ms = std::chrono::duration<double, std::milli>(t_ev0 - t_begin).count();
+        t.download_ms = t.total_ms - pre_ms - (double)a > 0.0 ? t.total_ms - pre_ms - (double)a : 0.0;
+        t.flops = marg_predict_flops(g, Sigma_out != nullptr, var_out != nullptr);
+    }
+    return 0;
+}
+
+extern "C" int psoap_chunk_predict_marg(psoap_chunk* h, int mode, int c, int M, const double* lwl, const double* lwl_pred,
+                                        const double* mu_c, const double* gp, double* mu_out, double* Sigma_out, int* status_out)
+{
+    return marg_predict_run(h, "psoap_chunk_predict_marg", mode, c, M, lwl, lwl_pred, mu_c, gp, mu_out, Sigma_out, nullptr,
+                            status_out);
+}
+
+extern "C" int psoap_chunk_predict_marg_var(psoap_chunk* h, int mode, int c, int M, const double* lwl, const double* lwl_pred,
+                                            const double* mu_c, const double* gp, double* mu_out, double* var_out, int* status_out)
+{
+    if (!var_out) FAIL("psoap_chunk_predict_marg_var: var_out is required");
+    return marg_predict_run(h, "psoap_chunk_predict_marg_var", mode, c, M, lwl, lwl_pred, mu_c, gp, mu_out, nullptr, var_out,
+                            status_out);
 }
 
 // ---- calibration ------------------------------------------------------------------------------

@@ -21,11 +21,17 @@ from .utils import N_COMPONENTS, n_params_orb, registered_params
 _NAMES = "fgh"
 
 
-def retrieve_components(model, chunk, parameters, n_pix_predict=None, get_Sigma=True):
+def retrieve_components(model, chunk, parameters, n_pix_predict=None, get_Sigma=True, baseline=None):
     """``chunk``: an UNMASKED ``psoap_amd.data.Chunk`` (2-D arrays); ``parameters``: the config's
     ``parameters`` dictionary (every registered parameter of ``model``).  Returns a dict with
     ``wl_predict``, ``lwl_predict``, ``mu`` (c * M,), ``Sigma`` (c * M, c * M) or None, and per
-    component ``mu_f`` / ``sigma_f`` (, ``_g``, ``_h``)."""
+    component ``mu_f`` / ``sigma_f`` (, ``_g``, ``_h``).
+
+    ``baseline``: the dictionary ``ChunkWorker(baseline=...)`` takes -- ``order``, ``sd`` (order + 1 prior standard
+    deviations) and optionally ``weight`` (``"flux"``: the polynomial multiplies the flux; ``"one"``: additive).  With it the
+    prediction conditions under the per-epoch continuum polynomial integrated out (``covariance.predict_marginal``), so
+    ``sigma_f`` / ``sigma_g`` / ``sigma_h`` carry the continuum's uncertainty, as the orbit and hyper-parameter error bars of
+    a fit under that baseline do."""
     if model not in ("SB2", "ST3", "SB1"):
         raise ValueError("retrieve_components supports SB1, SB2 and ST3 (the models the reference has scripts for)")
     c = N_COMPONENTS[model]
@@ -45,6 +51,8 @@ def retrieve_components(model, chunk, parameters, n_pix_predict=None, get_Sigma=
     M = int(n_pix_predict) if n_pix_predict is not None else 2 * int(chunk.n_pix)
     lwl_predict = np.linspace(np.min(lwls[0]), np.max(lwls[0]), num=M)
     pred = [lwl_predict] * c
+    if baseline is not None:
+        return _retrieve_marginal(c, lwls, fl, sigma, lwl, ep, lwl_predict, p_gp, get_Sigma, baseline)
     if isinstance(get_Sigma, str):
         # get_Sigma="diag": the per-component means and standard deviations only -- what the scripts plot and save as
         # f.npy / g.npy / h.npy -- without the (c M)^2 covariance matrix (psoap_predictor_run_var)
@@ -68,6 +76,33 @@ def retrieve_components(model, chunk, parameters, n_pix_predict=None, get_Sigma=
         mu, Sigma = covariance.predict_f_g_h(lwls[0], lwls[1], lwls[2], fl, sigma, *pred, 0.0, 0.0, 0.0, *p_gp)
     out = {"wl_predict": np.exp(lwl_predict), "lwl_predict": lwl_predict, "mu": mu, "Sigma": Sigma, "lwls": lwls}
     sd = np.sqrt(np.diag(Sigma)) if Sigma is not None else None
+    for k in range(c):
+        out["mu_" + _NAMES[k]] = mu[k * M:(k + 1) * M]
+        if sd is not None:
+            out["sigma_" + _NAMES[k]] = sd[k * M:(k + 1) * M]
+    return out
+
+
+def _retrieve_marginal(c, lwls, fl, sigma, lwl, ep, lwl_predict, p_gp, get_Sigma, baseline):
+    """the prediction of ``retrieve_components`` under ``baseline``: ``x`` is the observed-frame ln-wavelengths of the unmasked
+    pixels, the epoch index that of the mask"""
+    unknown = set(baseline) - {"order", "sd", "weight"}
+    if unknown or not {"order", "sd"} <= set(baseline):
+        raise ValueError(f"baseline needs 'order' and 'sd' (and optionally 'weight'); got {sorted(baseline)}")
+    kind = baseline.get("weight", "one")
+    if kind not in ("one", "flux"):
+        raise ValueError("baseline['weight'] must be 'one' or 'flux'")
+    weight = fl if kind == "flux" else None
+    if isinstance(get_Sigma, str) and get_Sigma != "diag":
+        raise ValueError('get_Sigma must be True, False or "diag"')
+    M = lwl_predict.shape[0]
+    want = get_Sigma if isinstance(get_Sigma, str) else bool(get_Sigma)
+    res = covariance.predict_marginal(lwls, fl, sigma, [lwl_predict] * c, [0.0] * c, p_gp, lwl, ep, int(baseline["order"]),
+                                      baseline["sd"], weight, mode=2 if c == 1 else 0, want_sigma=want)
+    mu, second = res if want else (res, None)
+    Sigma = second if want is True else None
+    out = {"wl_predict": np.exp(lwl_predict), "lwl_predict": lwl_predict, "mu": mu, "Sigma": Sigma, "lwls": lwls}
+    sd = None if second is None else np.sqrt(second if want == "diag" else np.diag(second))
     for k in range(c):
         out["mu_" + _NAMES[k]] = mu[k * M:(k + 1) * M]
         if sd is not None:
