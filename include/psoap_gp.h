@@ -685,15 +685,26 @@ int psoap_dag_plan(int B, int P, int workers, void *out, long long max_tasks, lo
  * psoap_sky_clip: host twin of what the clip reads -- the winning candidate's per-matrix skylines first_b_out (B, ceil(N /
  *   128)), row b that of matrix b (all zero for a matrix with an unusable hyper-parameter), and in *units_out the tile-GEMM
  *   units they leave, summed over the batch; any output may be NULL.
+ * The clip starts at a row, not a panel: the K-loop of an update streams 16 rows per stage, and behind every upload the
+ * device also computes, per matrix and column tile, the first 16-row group that is not provably zero (same test, the row
+ * interval taken over 16 rows; clamped to 8 max(j - 1, 0), non-decreasing, never above 8 times the tile-level row).  An
+ * update's panels before its last start at that row; its last panel runs whole, or not at all when the row lies beyond it.
+ * PSOAP_SKY_FINE=0 at handle creation: that kernel is not queued and every update starts at a whole panel.
+ * psoap_sky_clip16: host twin of it -- the winning candidate's rows by 16-row groups first16_b_out (B, ceil(N / 128)) and in
+ *   *stages_out the 16-row stages the updates of the union's list then run, summed over the batch and counted per tile (a
+ *   tile whose update the list splits into parts runs the last panel of each part whole); any output may be NULL.
  * psoap_chunk_sky_stats: out[0 .. n) of { tiles planned, tiles dense, tile-GEMM units planned, units dense, plan builds,
- *   plan-cache hits, skyline read (0 / 1), units executed after the clip (== units planned where nothing is clipped) } for
- *   the handle's last evaluation; returns the number of fields (8). */
+ *   plan-cache hits, skyline read (0 / 1), units executed after the clip (== units planned where nothing is clipped),
+ *   16-row stages of those units that run from each matrix's own first row group on (psoap_sky_clip16's figure; 8 per
+ *   unit where no stage is skipped) } for the handle's last evaluation; returns the number of fields (9). */
 int psoap_dag_plan_sky(int B, int P, const int *first, int workers, void *out, long long max_tasks, long long *n_tasks,
                        long long *n_slots, long long *n_ctrs, unsigned int *queue_first /* 9 entries or NULL */);
 int psoap_sky_first(int c, int N, int B, const double *lwl, const double *gp, int *first_out, int *perm_out);
 int psoap_sky_order(int c, int N, int B, const double *lwl, const double *gp, int *first_out, int *perm_out, int *cand_out);
 int psoap_sky_clip(int c, int N, int B, const double *lwl, const double *gp, int *first_b_out, long long *units_out,
                    int *cand_out);
+int psoap_sky_clip16(int c, int N, int B, const double *lwl, const double *gp, int *first16_b_out, long long *stages_out,
+                     int *cand_out);
 int psoap_chunk_sky_stats(psoap_chunk *h, long long *out, int n);
 /* The same for a heterogeneous batch (matrices of several chunks in one launch): matrix b has Ps[b]
  * block rows. */

@@ -146,6 +146,8 @@ SIGNATURES = {
     "psoap_sky_order": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, _dp, _ip, _ip, _ip]),
     "psoap_sky_clip": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, _dp, _ip, ctypes.POINTER(ctypes.c_longlong),
                                       _ip]),
+    "psoap_sky_clip16": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, _dp, _ip, ctypes.POINTER(ctypes.c_longlong),
+                                        _ip]),
     "psoap_chunk_sky_stats": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_longlong), ctypes.c_int]),
     "psoap_dag_plan_multi": (ctypes.c_int, [ctypes.c_int, _ip, ctypes.c_int, _vp, ctypes.c_longlong,
                                       ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_longlong),

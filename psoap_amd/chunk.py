@@ -551,9 +551,11 @@ class ChunkHandle:
     def sky_stats(self) -> dict:
         """The skyline of the last evaluation (include/psoap_gp.h: psoap_chunk_sky_stats): tiles and tile-GEMM units of the
         list that ran against the dense ones, plan builds and plan-cache hits so far, whether the slot's skyline was read, and
-        the units executed once every matrix's updates are clipped to its own envelope (PSOAP_SKY_CLIP=0: the planned ones)."""
+        the units executed once every matrix's updates are clipped to its own envelope (PSOAP_SKY_CLIP=0: the planned ones),
+        and the 16-row stages of those units that run once every update starts at its matrix's own first row group (8 per unit
+        under PSOAP_SKY_FINE=0)."""
         names = ("tiles_planned", "tiles_dense", "units_planned", "units_dense", "plan_builds", "cache_hits", "skyline_on",
-                 "units_clipped")
+                 "units_clipped", "stages_clipped")
         out = (ctypes.c_longlong * len(names))()
         n = self._L.psoap_chunk_sky_stats(self._h, out, len(names))
         if n != len(names):

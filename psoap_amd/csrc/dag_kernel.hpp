@@ -285,16 +285,18 @@ __device__ __forceinline__ void dag_task_done(MatFlags* f, int q, int ntasks_row
 // completed block rows.  A task then never waits for the stragglers of the row above, only for its own two operands --
 // with whole rows, every task of a row taken soon after the row above stalls until that row's last task is through: 7.5 %
 // of all worker time in a streamed run, where few matrices share a queue and the rows follow each other closely.)
-// (ka -- the clip of DagMat::first: block rows [pa, ka) of the two operands are exact zeros in THIS matrix, their products
-// are skipped.  Only the products: both waits stand whatever ka is -- the last panel's wait on the column's progress word
-// is also what puts this tile's turn at the right-hand side block j behind that of the tile above it.)
+// (ka16 -- the clip of DagMat::first, in 16-row groups (one stage of the K-loop each): rows [128 pa, 16 ka16) of the two
+// operands are exact zeros in THIS matrix, their products are skipped -- the panels before the last from that row on, the
+// last panel whole or, when the rows reach past it, not at all.  Only the products: both waits stand whatever ka16 is --
+// the last panel's wait on the column's progress word is also what puts this tile's turn at the right-hand side block j
+// behind that of the tile above it.)
 template <bool SW = false, class SM = SmemKernel, bool ROWMAP = false, bool TD = false>
 __device__ __forceinline__ void dag_update(Tile& t, double* Km, int ld, int k0, int j0, int pa, int pb, MatFlags* f,
                                            DagCtl* ctl, bool wait_next, unsigned long long* tl, int wave_s = -1, SM sm = SM(),
-                                           int* wa = nullptr, int* wb = nullptr, int ka = 0)
+                                           int* wa = nullptr, int* wb = nullptr, int ka16 = 0)
 {
     if (pb <= pa) return;
-    ka = ka > pa ? ka : pa;
+    const int r0 = pa * NB > ka16 * KB ? pa * NB : ka16 * KB;
     const bool diag = (k0 == j0);
     // (task log: the time spent in the two waits below is added up in bits 40.. of word 7 -- tools/stream_timeline.py)
     unsigned long long w0 = 0;
@@ -306,8 +308,7 @@ __device__ __forceinline__ void dag_update(Tile& t, double* Km, int ld, int k0, 
             const unsigned long long w1 = __builtin_amdgcn_s_memrealtime();
             tl[7] += (w1 - w0) << 40;
         }
-        const size_t r0 = (size_t)ka * NB;
-        tile_gemm_tn<SW, SM, ROWMAP>(t, Km + r0 * ld + k0, (size_t)ld, Km + r0 * ld + j0, (size_t)ld, (pb - 1 - ka) * NB, diag, 0x7fffffff, wave_s, sm);
+        tile_gemm_tn<SW, SM, ROWMAP>(t, Km + (size_t)r0 * ld + k0, (size_t)ld, Km + (size_t)r0 * ld + j0, (size_t)ld, (pb - 1) * NB - r0, diag, 0x7fffffff, wave_s, sm);
     }
     // the last panel: the whole block row above, or (diagonal tile of the latency scheme) only its tile
     // right of the diagonal -- U(pb-1, pb), all this tile reads of that row
@@ -321,7 +322,7 @@ __device__ __forceinline__ void dag_update(Tile& t, double* Km, int ld, int k0, 
     }
     const size_t r1 = (size_t)(pb - 1) * NB;
     // (K stays the constant it was: this call's loop is specialised on it)
-    if (ka < pb) tile_gemm_tn<SW, SM, ROWMAP>(t, Km + r1 * ld + k0, (size_t)ld, Km + r1 * ld + j0, (size_t)ld, NB, diag, 0x7fffffff, wave_s, sm);
+    if (r0 < pb * NB) tile_gemm_tn<SW, SM, ROWMAP>(t, Km + r1 * ld + k0, (size_t)ld, Km + r1 * ld + j0, (size_t)ld, NB, diag, 0x7fffffff, wave_s, sm);
 }
 
 // The last panel of a following strip solve's update, K = 128: its operands -- tiles (q-1, q) and (q-1, j) -- are being
@@ -403,8 +404,9 @@ struct DagMat {
     const double* sigma;  // (N)
     MatAcc* acc;
     int N, Npad, P, ld;
-    const int* first;     // (P) this matrix's own skyline inside the list's (sky_kernels.hpp: first_b of the chosen order):
-                          // block rows < first[j] of column tile j are exact zeros of its factor.  nullptr: no clip
+    const int* first;     // (P) this matrix's own skyline inside the list's, in 16-row groups (sky_kernels.hpp: k_sky_fine's
+                          // row of the chosen order; 8 first_b under PSOAP_SKY_FINE=0): rows < 16 first[j] of column tile j
+                          // are exact zeros of its factor.  nullptr: no clip
 };
 
 // INPLACE: the result replaces the accumulators instead of going to memory (the strip solve that follows works on the
@@ -1965,7 +1967,7 @@ __global__ __launch_bounds__(GEMM_THREADS, WPE) void k_chol_dag(const DagMat* __
         // records say -- dag_build_tasks; zero in a dense list)
         constexpr bool SKY = !LAT && !AUG && !STREAM;
         const unsigned int tctr = SKY ? (task.ctr & DAG_CTR_MASK) : task.ctr;
-        // (inside a skyline the list is the union's over the batch: this matrix's own first block row of column tile j --
+        // (inside a skyline the list is the union's over the batch: this matrix's own first 16-row group of column tile j --
         // j >= q, and first is non-decreasing, so it bounds both operands; one load per task, asked for here and read
         // where the update starts)
         int ka_v = 0;
@@ -2056,10 +2058,10 @@ __global__ __launch_bounds__(GEMM_THREADS, WPE) void k_chol_dag(const DagMat* __
         // the bit means "follow the factorisation" and the last panel needs the whole block row above, as always)
         // (scheme 0: tile-level dependencies; never in the LAT kernels, whose task lists carry their own protocols)
         // (said to be wave-uniform: the extents of the K-loop stay scalars)
-        const int ka = __builtin_amdgcn_readfirstlane(ka_v);
+        const int ka16 = __builtin_amdgcn_readfirstlane(ka_v);
         dag_update<true, SmemKernel, false, !LAT && DAG_TILE_DEPS>(
             t, Km, ld, k0, j0, task.pa, task.pb, f, ctl, ttype == DAG_DIAG && (task.type & DAG_WAITNEXT) != 0,
-            tlog_l ? tlog_l + ticket * 8 : nullptr, wave_s, SmemKernel(), &f->rvrow[q], &f->rvrow[j], ka);
+            tlog_l ? tlog_l + ticket * 8 : nullptr, wave_s, SmemKernel(), &f->rvrow[q], &f->rvrow[j], ka16);
         if (tlog_l && threadIdx.x == 0) tlog_l[ticket * 8 + 5] = __builtin_amdgcn_s_memrealtime();
         if (!preload && n_wait > 0) dag_wait_ge(&arrive_l[tctr], n_wait, ctl, 4u);
         if (tlog_l && threadIdx.x == 0) tlog_l[ticket * 8 + 6] = __builtin_amdgcn_s_memrealtime();

@@ -1,6 +1,6 @@
 // plan_abi.hpp -- the pure-host entry points of the C ABI (include/psoap_gp.h): the planner's task lists and the host
 // twins of the skyline kernels.  No HIP call and no HIP header: psoap_gp.hip includes it into the library, and a host
-// compiler builds the same text into a stand-alone, sanitized program (tests/host/plan_host_check.cpp).
+// compiler builds the same text into stand-alone, sanitized programs (tests/host/plan_host_check.cpp, sky_fine_host_check.cpp).
 #pragma once
 #include <string.h>
 
@@ -158,6 +158,50 @@ extern "C" int psoap_sky_clip(int c, int N, int B, const double* lwl, const doub
     for (int b = 0; b < B; ++b) units += sky_cost(first_b.data() + (size_t)b * P, P);
     if (first_b_out) memcpy(first_b_out, first_b.data(), sizeof(int) * (size_t)B * P);
     if (units_out) *units_out = units;
+    if (cand_out) *cand_out = cand;
+    return 0;
+}
+
+// Pure host function, the twin of k_sky_fine: the winning candidate of psoap_sky_order and, per matrix and column tile, the
+// first 16-row group that is not provably zero -- first16_b_out (B, ceil(N / 128)), what DagMat::first points at: clamped to
+// 8 max(j - 1, 0), non-decreasing, at or beyond 8 times psoap_sky_clip's row (checked here) -- with the 16-row stages the
+// updates of the union's list then run, summed over the batch, in *stages_out (sky_stages_col).  Any output may be null.
+// Beyond SKY_MAX_N: all zero, dense.
+extern "C" int psoap_sky_clip16(int c, int N, int B, const double* lwl, const double* gp, int* first16_b_out, long long* stages_out,
+                                int* cand_out)
+{
+    if (c < 1 || c > 3 || N < 1 || B < 1 || !lwl || !gp) FAIL("psoap_sky_clip16: bad arguments");
+    const int P = round_up(N, NB) / NB, G = round_up(N, SKY_G) / SKY_G;
+    int cand = 0;
+    sky_host_order(c, N, B, lwl, gp, sky_n_cand(c), nullptr, nullptr, &cand);
+    std::vector<int> perm, first((size_t)P, 0), first_b, first16((size_t)B * P, 0);
+    long long stages = 0;
+    if (N <= SKY_MAX_N) {
+        sky_host_candidate(c, N, B, lwl, gp, cand, perm, first, &first_b);
+        std::vector<double> x((size_t)c * N), lo((size_t)c * P), hi((size_t)c * P), lo16((size_t)c * G), hi16((size_t)c * G);
+        for (int b = 0; b < B; ++b) {
+            for (int k = 0; k < c; ++k) {
+                double* xk = x.data() + (size_t)k * N;
+                for (int r = 0; r < N; ++r) xk[r] = lwl[((size_t)b * c + k) * N + perm[r]];
+                for (int t = 0; t < P; ++t)
+                    sky_interval(xk, t * NB, (t + 1) * NB < N ? (t + 1) * NB : N, &lo[(size_t)k * P + t], &hi[(size_t)k * P + t]);
+                for (int g = 0; g < G; ++g)
+                    sky_interval(xk, g * SKY_G, (g + 1) * SKY_G < N ? (g + 1) * SKY_G : N, &lo16[(size_t)k * G + g],
+                                 &hi16[(size_t)k * G + g]);
+            }
+            double p2[3] = {0.0, 0.0, 0.0};
+            const bool ok = sky_gp(gp + (size_t)b * 2 * c, c, p2);
+            int* f16 = first16.data() + (size_t)b * P;
+            for (int j = 0; j < P; ++j) f16[j] = sky_first16_raw(j, G, P, c, lo16.data(), hi16.data(), lo.data(), hi.data(), p2, ok);
+            sky_first16_finish(f16, P);
+            for (int j = 0; j < P; ++j)
+                if (f16[j] < SKY_GPT * first_b[(size_t)b * P + j]) FAIL("psoap_sky_clip16: a column starts above its own first tile");
+        }
+    }
+    for (int b = 0; b < B; ++b)
+        for (int j = 0; j < P; ++j) stages += sky_stages_col(j, first[j], first16[(size_t)b * P + j]);
+    if (first16_b_out) memcpy(first16_b_out, first16.data(), sizeof(int) * (size_t)B * P);
+    if (stages_out) *stages_out = stages;
     if (cand_out) *cand_out = cand;
     return 0;
 }

@@ -84,8 +84,11 @@ struct BatchSlot {
     Grow<int> dCand;           // the candidate the last upload chose: its permutation is the one of the sorted copies
     Grow<int> dFirstB;         // candidates x max_batch x P: first_b per candidate and matrix
     Grow<int, true> hFirst;    // P, pinned: the chosen candidate's union over the batch
-    Grow<int> dFirstW;         // max_batch x P: the chosen candidate's first_b rows -- what DagMat::first points at
+    Grow<int> dFirstW;         // max_batch x P: the chosen candidate's first_b rows
     Grow<long long, true> hClipUnits;   // 1, pinned: their cost summed over the batch, the units the clipped list executes
+    Grow<int> dFirst16;        // max_batch x P: the same rows by 16-row groups (k_sky_fine; 8 x dFirstW under PSOAP_SKY_FINE=0)
+                               // -- what DagMat::first points at
+    Grow<long long, true> hStages16;    // max_batch, pinned: per matrix the 16-row stages its updates run from those rows on
     Grow<int> dTooFast;        // max_batch: |v| >= c flags (orbit proposals)
     bool toofast_dirty = false;  // an orbit upload may have raised flags: clear before the slot is reused
     Grow<DagMat> dMats;        // per-matrix records of this slot (max_batch entries)
@@ -175,7 +178,9 @@ struct psoap_chunk {
     bool sky_clip = true;             // PSOAP_SKY_CLIP=0, read at create: DagMat::first stays null, every matrix runs the union's ranges
     std::vector<int> plan_first;      // the skyline of the list in `dag` (empty: dense)
     DagPlanWork plan_work;            // what that list executes (a skyline list only)
+    bool sky_fine = true;             // PSOAP_SKY_FINE=0, read at create: k_sky_fine is not queued, the clip starts at whole panels
     long long clip_units = -1;        // units of that list the current evaluation executes under the clip (DagMat::first); -1: no clip
+    long long clip_stages = -1;       // 16-row stages of those units the updates run from each matrix's own first row group on
     struct SkyPlan {
         int B;
         std::vector<int> first;
@@ -185,7 +190,7 @@ struct psoap_chunk {
         Grow<DagTask> dTasks;                       // the list on the device
     };
     std::vector<SkyPlan> sky_cache;   // the last few skyline lists, newest first
-    long long sky_stats[8] = {};      // psoap_chunk_sky_stats
+    long long sky_stats[9] = {};      // psoap_chunk_sky_stats
     Grow<unsigned long long> dTlog;       // optional per-task timestamps (debug)
     long long tlog_tasks = 0;
     // pinned host staging (one set: reused once the previous upload's copies have completed)
@@ -366,6 +371,8 @@ static int chunk_alloc(psoap_chunk* h, const double* fl, const double* sigma)
         h->sky_order = !(e && e[0] == '0');
         e = getenv("PSOAP_SKY_CLIP");
         h->sky_clip = !(e && e[0] == '0');
+        e = getenv("PSOAP_SKY_FINE");
+        h->sky_fine = !(e && e[0] == '0');
     }
     const size_t n_cand = h->sky_order ? SKY_MAX_CAND : 1;
     for (BatchSlot& sl : h->slot) {
@@ -383,6 +390,10 @@ static int chunk_alloc(psoap_chunk* h, const double* fl, const double* sigma)
             HIP_TRY(hipMemset(sl.dFirstW, 0, sizeof(int) * nb * h->P));
             NEED(sl.hClipUnits, 1);
             sl.hClipUnits[0] = 0;
+            NEED(sl.dFirst16, nb * h->P);
+            HIP_TRY(hipMemset(sl.dFirst16, 0, sizeof(int) * nb * h->P));
+            NEED(sl.hStages16, nb);
+            memset(sl.hStages16, 0, sizeof(long long) * nb);
         }
         NEED(sl.dLwl, nb * 3 * N);
         NEED(sl.dGp, nb * 6);
@@ -539,12 +550,13 @@ extern "C" int psoap_chunk_dag_tasklog(psoap_chunk* h, unsigned long long* out, 
 
 // The skyline of the handle's last evaluation: out[0 .. n) of { tiles planned, tiles dense, tile-GEMM units planned, units
 // dense, plan builds so far, plan-cache hits so far, 1 if the evaluation read the slot's skyline, units executed once
-// every matrix's updates are clipped to its own envelope (the units planned where nothing is clipped) }.
+// every matrix's updates are clipped to its own envelope (the units planned where nothing is clipped), 16-row stages of
+// those units that run once every update starts at its matrix's own first row group (8 per unit where none is skipped) }.
 extern "C" int psoap_chunk_sky_stats(psoap_chunk* h, long long* out, int n)
 {
     if (!h || !out || n < 0) FAIL("psoap_chunk_sky_stats: bad arguments");
-    for (int i = 0; i < n && i < 8; ++i) out[i] = h->sky_stats[i];
-    return 8;
+    for (int i = 0; i < n && i < 9; ++i) out[i] = h->sky_stats[i];
+    return 9;
 }
 
 // Debug: copy the current task list (16-byte DagTask records, ticket order) to the host.
@@ -647,7 +659,11 @@ static int upload_end(psoap_chunk* h, BatchSlot& sl)
         hipLaunchKernelGGL(k_sky_perm, dim3((N + 255) / 256, K), dim3(256), 0, s, sl.dLwl, sl.C, N, sl.dPerm);
         hipLaunchKernelGGL(k_sky_first, dim3(sl.B, K), dim3(256), 0, s, sl.dLwl, sl.dPerm, sl.dGp, sl.C, N, h->P, sl.dFirstB);
         hipLaunchKernelGGL(k_sky_choose, dim3(1), dim3(256), 0, s, sl.dFirstB, sl.B, h->P, K, sl.hFirst, sl.dCand,
-                           sl.dFirstW, sl.hClipUnits);
+                           sl.dFirstW, sl.hClipUnits, sl.dFirst16);
+        // (PSOAP_SKY_FINE=0: not queued -- the rows stay k_sky_choose's whole panels)
+        if (h->sky_clip && h->sky_fine)
+            hipLaunchKernelGGL(k_sky_fine, dim3(sl.B), dim3(256), 0, s, sl.dLwl, sl.dPerm, sl.dCand, sl.dGp, sl.C, N, h->P,
+                               sl.dFirstW, sl.dFirst16, sl.hStages16);
         hipLaunchKernelGGL(k_sky_gather, dim3((N + 255) / 256, rows + 2), dim3(256), 0, s, sl.dPerm, sl.dCand, N, rows, sl.dLwl,
                            sl.dLwlS, h->dFl, sl.dFlS, h->dSigma, sl.dSigmaS);
         HIP_TRY(hipGetLastError());
@@ -879,7 +895,7 @@ static void fill_mats(const psoap_chunk* h, const BatchSlot& sl, DagMat* out, bo
 {
     for (int b = 0; b < sl.B; ++b) {
         out[b] = chunk_mat(h, b, sl.C, sorted ? sl.dLwlS : sl.dLwl, sl.dGp, sorted ? sl.dSigmaS : h->dSigma);
-        if (sorted && h->sky_clip) out[b].first = sl.dFirstW + (size_t)b * h->P;
+        if (sorted && h->sky_clip) out[b].first = sl.dFirst16 + (size_t)b * h->P;
     }
 }
 
@@ -936,6 +952,11 @@ static int dag_prepare(psoap_chunk* h)
     if (int rc = ensure_slot_mats(h, sl, !first.empty())) return rc;
     // (the units this evaluation executes of its list once the kernel clips every matrix to its own envelope)
     h->clip_units = !first.empty() && h->sky_clip ? sl.hClipUnits[0] : -1;
+    h->clip_stages = -1;
+    if (h->clip_units >= 0) {
+        h->clip_stages = h->sky_fine ? 0 : SKY_GPT * h->clip_units;
+        for (int b = 0; b < B && h->sky_fine; ++b) h->clip_stages += sl.hStages16[b];
+    }
     long long units_dense = 0;
     for (int q = 0; q < P; ++q) units_dense += (long long)q * (P - q);
     h->sky_stats[1] = (long long)B * P * (P + 1) / 2;
@@ -946,6 +967,7 @@ static int dag_prepare(psoap_chunk* h)
         h->sky_stats[0] = dense ? h->sky_stats[1] : h->plan_work.tiles;
         h->sky_stats[2] = dense ? h->sky_stats[3] : h->plan_work.units;
         h->sky_stats[7] = h->clip_units >= 0 ? h->clip_units : h->sky_stats[2];
+        h->sky_stats[8] = h->clip_stages >= 0 ? h->clip_stages : SKY_GPT * h->sky_stats[2];
     };
     if (h->plan_B == B && h->plan_first == first) {
         if (!first.empty()) h->sky_stats[5] += 1;      // (a skyline list, still loaded)
@@ -1078,10 +1100,10 @@ static int eval_dag(psoap_chunk* h)
     // executed MFMA flops: left-looking updates + strip solves, full 128^3 tiles
     double fl = 0.0;
     for (int q = 0; q < P; ++q) fl += 2.0 * NB * NB * ((double)q * NB * (P - q) + (double)NB * (P - q - 1));
-    // (inside a skyline: the flops of the list that runs, less the panels the clip skips)
+    // (inside a skyline: the flops of the list that runs, less the 16-row stages the clip skips)
     if (int rc = prof_launch(h, s, PSOAP_K_DAG,
                              h->plan_first.empty() ? fl * B
-                                                     : h->plan_work.flops - 2.0 * NB * NB * NB * (double)(h->clip_units >= 0 ? h->plan_work.units - h->clip_units : 0),
+                                                     : h->plan_work.flops - 2.0 * NB * NB * KB * (double)(h->clip_stages >= 0 ? SKY_GPT * h->plan_work.units - h->clip_stages : 0),
                              0.0,
                              [&] { launch_lnlike(h, h->dag, h->plan_workers, C, sl.dMats, B, P, s, h->dTlog); }))
         return rc;

@@ -20,8 +20,12 @@
 //      (dag_build_tasks), and the winner's first_b rows stay on the device for the kernel, which clips every matrix's
 //      updates to its own envelope inside that list (DagMat::first); what the clip leaves, sum_b sky_cost(first_b), goes
 //      to pinned host memory too;
+//   3a. for the winner only, per matrix and column tile the first 16-row group that is not provably zero by the same test
+//      (k_sky_fine; the row interval over 16 rows, the column interval over the tile): the row the updates of dag_update
+//      start at, one stage of the K-loop fine; not queued under PSOAP_SKY_FINE=0, where the rows stay 8 first_b;
 //   4. gather lwl, fl and sigma through the winner's permutation -- nothing is gathered for a candidate that loses.
-// The routines these kernels share with the host twins psoap_sky_first (candidate 0) and psoap_sky_order: sky_rules.hpp.
+// The routines these kernels share with the host twins psoap_sky_first (candidate 0), psoap_sky_order, psoap_sky_clip and
+// psoap_sky_clip16: sky_rules.hpp.
 #pragma once
 #include "common.hpp"
 #include "sky_rules.hpp"
@@ -120,10 +124,12 @@ __global__ __launch_bounds__(256) void k_sky_first(const double* __restrict__ lw
 
 // per candidate the union over the batch and its cost; the cheapest candidate (ties: the lowest) to *cand_out, its union to
 // pinned host memory; its per-matrix rows to first_w (B, P) and their cost, summed over the batch, to *units_host (pinned).
+// first16_w (B, P): the same rows in 16-row groups, 8 first_w -- what DagMat::first points at until k_sky_fine refines it.
 // One block; first_b (K, B, P), K <= SKY_MAX_CAND, P <= SKY_MAX_P.
 __global__ __launch_bounds__(256) void k_sky_choose(const int* __restrict__ first_b, int B, int P, int K,
                                                     int* __restrict__ first_host, int* __restrict__ cand_out,
-                                                    int* __restrict__ first_w, long long* __restrict__ units_host)
+                                                    int* __restrict__ first_w, long long* __restrict__ units_host,
+                                                    int* __restrict__ first16_w)
 {
     __shared__ int fu[SKY_MAX_CAND * SKY_MAX_P];
     __shared__ long long cost[SKY_MAX_CAND];
@@ -149,10 +155,87 @@ __global__ __launch_bounds__(256) void k_sky_choose(const int* __restrict__ firs
     __syncthreads();
     for (int j = threadIdx.x; j < P; j += 256) first_host[j] = fu[win * P + j];
     const int* fw = first_b + (size_t)win * B * P;
-    for (int idx = threadIdx.x; idx < B * P; idx += 256) first_w[idx] = fw[idx];
+    for (int idx = threadIdx.x; idx < B * P; idx += 256) {
+        first_w[idx] = fw[idx];
+        first16_w[idx] = SKY_GPT * fw[idx];
+    }
     for (int b = threadIdx.x; b < B; b += 256) atomicAdd(&units, (unsigned long long)sky_cost(fw + (size_t)b * P, P));
     __syncthreads();
     if (threadIdx.x == 0) units_host[0] = (long long)units;
+}
+
+// The chosen candidate's envelope of matrix blockIdx.x by 16-row groups (sky_rules.hpp: sky_first16_raw), behind
+// k_sky_choose: first16_w (B, P) row blockIdx.x, and to stages_host[blockIdx.x] (pinned) the 16-row stages the matrix's
+// updates then run inside the union's list (first_w (B, P): the chosen candidate's rows by tiles, their minimum is the
+// union).  Sixteen lanes per group interval, four groups per wavefront and step; G = ceil(N / 16) <= SKY_MAX_G.
+__global__ __launch_bounds__(256) void k_sky_fine(const double* __restrict__ lwl, const int* __restrict__ perm,
+                                                  const int* __restrict__ cand, const double* __restrict__ gp, int C, int N, int P,
+                                                  const int* __restrict__ first_w, int* __restrict__ first16_w,
+                                                  long long* __restrict__ stages_host)
+{
+    __shared__ double lo16[3 * SKY_MAX_G], hi16[3 * SKY_MAX_G];
+    __shared__ double lo[3 * SKY_MAX_P], hi[3 * SKY_MAX_P];
+    __shared__ int f16[SKY_MAX_P];
+    __shared__ unsigned long long stages;
+    const int b = blockIdx.x, B = gridDim.x, G = (N + SKY_G - 1) / SKY_G;
+    const double* x = lwl + (size_t)b * C * N;
+    const int* pm = perm + (size_t)cand[0] * N;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (threadIdx.x == 0) stages = 0ull;
+    for (int base = 4 * wave; base < C * G; base += 16) {
+        // (every lane takes the shuffles; one past the end, or past N in a ragged last group, carries the neutral values)
+        const int idx = base + (lane >> 4);
+        const int c = idx / G, g = idx % G, i = g * SKY_G + (lane & 15);
+        double a = __builtin_inf(), z = -__builtin_inf();
+        int nan = 0;
+        if (idx < C * G && i < N) {
+            const double v = x[(size_t)c * N + pm[i]];
+            nan = !(v == v) ? 1 : 0;
+            a = v < a ? v : a;
+            z = v > z ? v : z;
+        }
+        for (int off = 8; off > 0; off >>= 1) {
+            const double a2 = __shfl_xor(a, off), z2 = __shfl_xor(z, off);
+            nan |= __shfl_xor(nan, off);
+            a = a2 < a ? a2 : a;
+            z = z2 > z ? z2 : z;
+        }
+        if ((lane & 15) == 0 && idx < C * G) {
+            lo16[idx] = nan ? -__builtin_inf() : a;
+            hi16[idx] = nan ? __builtin_inf() : z;
+        }
+    }
+    __syncthreads();
+    // a tile's interval from its groups': minimum, maximum and the NaN flag (an infinite pair) do not depend on the grouping
+    for (int idx = threadIdx.x; idx < C * P; idx += 256) {
+        const int c = idx / P, t = idx % P;
+        const int g1 = (t + 1) * SKY_GPT < G ? (t + 1) * SKY_GPT : G;
+        double a = __builtin_inf(), z = -__builtin_inf();
+        for (int g = t * SKY_GPT; g < g1; ++g) {
+            a = lo16[c * G + g] < a ? lo16[c * G + g] : a;
+            z = hi16[c * G + g] > z ? hi16[c * G + g] : z;
+        }
+        lo[idx] = a;
+        hi[idx] = z;
+    }
+    __syncthreads();
+    double p2[3] = {0.0, 0.0, 0.0};
+    const bool ok = sky_gp(gp + (size_t)b * 2 * C, C, p2);
+    if ((int)threadIdx.x < P)
+        f16[threadIdx.x] = sky_first16_raw((int)threadIdx.x, G, P, C, lo16, hi16, lo, hi, p2, ok,
+                                           SKY_GPT * first_w[(size_t)b * P + threadIdx.x]);
+    __syncthreads();
+    if (threadIdx.x == 0) sky_first16_finish(f16, P);
+    __syncthreads();
+    if ((int)threadIdx.x < P) {
+        const int j = threadIdx.x;
+        int u = first_w[j];
+        for (int k = 1; k < B; ++k) u = first_w[(size_t)k * P + j] < u ? first_w[(size_t)k * P + j] : u;
+        first16_w[(size_t)b * P + j] = f16[j];
+        atomicAdd(&stages, (unsigned long long)sky_stages_col(j, u, f16[j]));
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) stages_host[b] = (long long)stages;
 }
 
 }  // namespace psoap

@@ -1,5 +1,5 @@
-// sky_rules.hpp -- the routines the skyline kernels (sky_kernels.hpp) share with their host twins psoap_sky_first and
-// psoap_sky_order (plan_abi.hpp): the envelope is integer work on comparisons both sides make alike, the keys are the same
+// sky_rules.hpp -- the routines the skyline kernels (sky_kernels.hpp) share with their host twins psoap_sky_first,
+// psoap_sky_order, psoap_sky_clip and psoap_sky_clip16 (plan_abi.hpp): the envelope is integer work on comparisons both sides make alike, the keys are the same
 // arithmetic.  No HIP header: PSOAP_HD (tile_consts.hpp) is __host__ __device__ under hipcc and empty for a host compiler.
 #pragma once
 #include "tile_consts.hpp"
@@ -130,6 +130,65 @@ PSOAP_HD inline void sky_first_finish(int* first, int P)
         first[j] = first[j] < cap ? first[j] : cap;
     }
     for (int j = P - 2; j >= 0; --j) first[j] = first[j] < first[j + 1] ? first[j] : first[j + 1];
+}
+
+// ---- the same envelope by 16-row groups (SKY_G = the k-rows of one stage of the tile engine, KB) --------------------
+// Row group g is rows [16 g, 16 g + 16); the columns stay whole tiles.  A group's interval lies inside its tile's, the gap
+// can only grow and every rounding is monotone: a group of a provably zero tile is provably zero, so the first group of
+// a column is at or beyond 8 times its first tile.
+constexpr int SKY_G = KB;
+constexpr int SKY_GPT = NB / SKY_G;          // groups per tile
+constexpr int SKY_MAX_G = SKY_MAX_N / SKY_G;
+
+// rows of group g against the columns of tile j are provably +0: sky_tile_zero with the row interval taken over the
+// group (lo16, hi16: [c * G + group]; lo, hi: [c * P + tile])
+PSOAP_HD inline bool sky_group_zero(int g, int j, int G, int P, int C, const double* lo16, const double* hi16, const double* lo,
+                                    const double* hi, const double* p2)
+{
+#pragma clang fp contract(off)
+    for (int c = 0; c < C; ++c) {
+        const double g1 = lo[c * P + j] - hi16[c * G + g], g2 = lo16[c * G + g] - hi[c * P + j];
+        const double d = g1 > g2 ? g1 : g2;
+        if (!(d > 0.0)) return false;
+        const double a = p2[c] * d * d;
+        if (!(a <= -746.0)) return false;
+    }
+    return true;
+}
+
+// the first group of column tile j that is not provably zero, looked for below the clamp 8 max(j - 1, 0) only (every
+// group there is a whole one: it lies above the last tile).  g0: groups known to be provably zero -- the kernel starts at
+// 8 times the column's first tile, the host twin at 0 and checks that it ends at or beyond that
+PSOAP_HD inline int sky_first16_raw(int j, int G, int P, int C, const double* lo16, const double* hi16, const double* lo,
+                                    const double* hi, const double* p2, bool ok, int g0 = 0)
+{
+    if (!ok) return 0;
+    const int cap = j > 0 ? SKY_GPT * (j - 1) : 0;
+    int g = g0 < cap ? g0 : cap;
+    while (g < cap && sky_group_zero(g, j, G, P, C, lo16, hi16, lo, hi, p2)) ++g;
+    return g;
+}
+
+// non-decreasing (running minimum from the right; the clamp is sky_first16_raw's)
+PSOAP_HD inline void sky_first16_finish(int* first16, int P)
+{
+    for (int j = P - 2; j >= 0; --j) first16[j] = first16[j] < first16[j + 1] ? first16[j] : first16[j + 1];
+}
+
+// 16-row stages column tile j of one matrix runs inside the list of the union `u` = first[j] when its updates start at
+// group s = first16[j] (dag_update): tile (q, j), u < q <= j, multiplies block rows [u, q) -- nothing if s lies at or
+// beyond row 128 q, else the last panel whole and the panels before it from max(8 u, s) on.  s = 8 first_b[j]: 8 times the
+// column's share of sky_cost(first_b).  (A tile whose update the list splits runs the last panel of every part whole.)
+PSOAP_HD inline long long sky_stages_col(int j, int u, int s)
+{
+    long long n = 0;
+    const int r0 = SKY_GPT * u > s ? SKY_GPT * u : s;
+    for (int q = u + 1; q <= j; ++q) {
+        if (s >= SKY_GPT * q) continue;
+        const int before = SKY_GPT * (q - 1) - r0;
+        n += SKY_GPT + (before > 0 ? before : 0);
+    }
+    return n;
 }
 
 }  // namespace psoap
