@@ -70,6 +70,8 @@ def main(argv=None):
     res = retrieve.retrieve_components("SB2", pdata.Chunk.open(order, wl0, wl1, prefix=args.workdir + "/"), pars)
     retrieve.save_components(res, os.path.join(args.workdir, "plots_" + pdata.chunk_fmt.format(order, wl0, wl1)))
     print("reconstructed f, g on", len(res["wl_predict"]), "pixels; acceptance", np.round(sampler.acceptance_fraction, 2))
+    drawn = retrieve.retrieve_components("SB2", pdata.Chunk.open(order, wl0, wl1, prefix=args.workdir + "/"), pars, n_draws=5, seed=1)
+    print("five posterior draws of f, g:", drawn["f_draws"].shape, drawn["g_draws"].shape)
     return sampler, res
 
 

@@ -493,6 +493,36 @@ int psoap_chunk_predict_var(psoap_chunk *h, int mode, int c, int M, const double
                             const double *lwl_pred, const double *mu_c, const double *gp,
                             double *mu_out, double *var_out, int *status_out);
 int psoap_chunk_predict_release(psoap_chunk *h);
+/* Posterior draws of the component spectra (csrc/draw_kernels.hpp, draw_plan.hpp, draw_rng.hpp): what the reference's
+ * scripts/psoap_retrieve_SB2_draw.py, psoap_retrieve_ST3_draw.py and psoap_predict_SB2.py / _ST3.py --draws make with
+ * np.random.multivariate_normal(mu, Sigma, size=n_draws), from the mean and Sigma the handle's predict workspace holds:
+ *     X[d, :] = mu + U^T z_d,   U^T U = Sigma + nugget I (U upper),   z_d ~ N(0, I_R),   d = 0 .. D-1
+ * with R the prediction rows of the handle's last successful psoap_chunk_predict or psoap_chunk_predict_marg call that
+ * formed Sigma (Sigma_out != NULL, status 0; any mode).  The draws are from N(mu, Sigma + nugget I), NOT N(mu, Sigma):
+ * nugget is an absolute variance (flux^2, >= 0) and is needed -- Sigma = A - W^T W on a prediction grid finer than the
+ * kernel's length scale is numerically rank deficient with small negative eigenvalues from rounding, which NumPy's SVD
+ * route hides and a Cholesky factorisation does not (the reference itself adds 1e-8 in predict_f_g_sum,
+ * covariance.py:165; the Python layers default to that).  Sigma and mu are only read: further calls with another seed,
+ * D or nugget need no new predict.
+ * z == NULL: the normals come from seed -- Philox4x32-10 with key (seed low word, seed high word) and counter
+ * (i >> 1, d, 0, 0) for element i of draw d, two 53-bit uniforms per block, Box-Muller (even element the cosine, odd the
+ * sine): element i of draw d depends on (seed, d, i) alone, not on D, the padding, the grid or the device.
+ * z != NULL: z (D, R) is used and seed ignored.  out (D, R).
+ * status_out: 0 ok, 1 Sigma + nugget I does not factor (out is NaN, the call returns 0).
+ * Returns 2 (psoap_last_error): no such predict call since the handle's creation, psoap_chunk_predict_release,
+ * psoap_chunk_set_data or psoap_chunk_set_baseline (the variance-only calls, Sigma_out == NULL and a predict call with
+ * status 1 clear the record too); D < 1 or D > 1048576; nugget < 0 or not finite; an open stream.
+ * Work: the copy, the staged factorisation of the copy (Rpad^3 / 3), the normals, and one fp64 MFMA launch for the
+ * triangular product, tile (td, tj) running block rows 0 .. tj of U with the diagonal tile masked to its upper half
+ * (D R^2 flops).  No atomics, every sum in an order fixed by (R, D).  Memory: 8 Rpad (Rpad + Dpad) + 8 Dpad Rpad bytes
+ * beside the predict workspace, grown as needed and freed by psoap_chunk_predict_release.  Launches are booked under
+ * PSOAP_K_FILL (copy), PANEL_UPDATE / POTRF / TRSM (factorisation), MISC (normals), GRAD (product). */
+int psoap_chunk_predict_draw(psoap_chunk *h, int D, unsigned long long seed, const double *z,
+                             double nugget, double *out, int *status_out);
+/* the generator alone: out[d * n + i] for d < D, i < n -- what the call above uses as z for the same seed */
+int psoap_draw_normals(int device, unsigned long long seed, int D, int n, double *out);
+/* host twin of the generator's integer core (pure host): the Philox4x32-10 block of key seed, counter (c0, c1, 0, 0) */
+int psoap_draw_philox(unsigned long long seed, unsigned int c0, unsigned int c1, unsigned int out[4]);
 /* Timings of the handle's last predict call, in ms: device_ms = first upload ->
  * mu and Sigma complete on the device (HIP events), factor_ms = the persistent
  * launch over [B | Cx^T], sigma_ms = mean + prior fill + Sigma = A - W^T W,

@@ -94,6 +94,9 @@ SIGNATURES = {
     "psoap_chunk_predict_marg_var": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp, _dp,
                                                     _dp, _ip]),
     "psoap_chunk_predict_release": (ctypes.c_int, [_vp]),
+    "psoap_chunk_predict_draw": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_ulonglong, _dp, ctypes.c_double, _dp, _ip]),
+    "psoap_draw_normals": (ctypes.c_int, [ctypes.c_int, ctypes.c_ulonglong, ctypes.c_int, ctypes.c_int, _dp]),
+    "psoap_draw_philox": (ctypes.c_int, [ctypes.c_ulonglong, ctypes.c_uint, ctypes.c_uint, ctypes.POINTER(ctypes.c_uint)]),
     "psoap_chunk_predict_timings": (ctypes.c_int, [_vp, ctypes.POINTER(PredictTimings)]),
     "psoap_predictor_create": (ctypes.c_int, [ctypes.POINTER(_vp), ctypes.c_int]),
     "psoap_predictor_run": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp,

@@ -72,6 +72,7 @@ class ChunkHandle:
                                          dptr(self.sigma), self.max_batch), "psoap_chunk_create")
         self._B = 0
         self.n_epochs = 0
+        self._sigma_rows = 0
 
     # -- lifetime -----------------------------------------------------------------
     def close(self):
@@ -507,6 +508,7 @@ class ChunkHandle:
         R = c * M if mode == 0 else M
         mu = np.empty(R)
         status = ctypes.c_int(0)
+        self._sigma_rows = 0           # (what predict_draw sizes its output by: the library keeps the record itself)
         if isinstance(want_sigma, str):
             if want_sigma != "diag":
                 raise ValueError('want_sigma must be True, False or "diag"')
@@ -521,6 +523,8 @@ class ChunkHandle:
                                       dptr(mu), None if Sigma is None else dptr(Sigma), ctypes.byref(status)), entry)
         if status.value != 0:
             raise np.linalg.LinAlgError("data covariance matrix is not positive definite")
+        if want_sigma:
+            self._sigma_rows = R
         return (mu, Sigma) if want_sigma else mu
 
     def predict_marg(self, mode: int, lwls, lwls_predict, mu_c, gp, want_sigma=True):
@@ -531,8 +535,43 @@ class ChunkHandle:
         is not positive definite (or the Gram matrix does not factor); ``PsoapError`` without a baseline."""
         return self._predict("psoap_chunk_predict_marg", mode, lwls, lwls_predict, mu_c, gp, want_sigma)
 
+    def predict_draw(self, n_draws: int, seed=None, z=None, nugget: float = 1e-8) -> np.ndarray:
+        """``n_draws`` spectra from the posterior of the last ``predict`` / ``predict_marg`` call of this handle that returned
+        ``Sigma`` (include/psoap_gp.h: psoap_chunk_predict_draw) -> ``(n_draws, R)``, ``R`` that call's rows:
+        ``mu + U^T z_d`` with ``U^T U = Sigma + nugget I``, i.e. draws from ``N(mu, Sigma + nugget I)`` -- not from
+        ``N(mu, Sigma)``: ``Sigma`` on a fine grid is numerically rank deficient and the Cholesky factor needs the nugget
+        (an absolute variance in flux^2).  ``seed``: the normals come from the device's counter-based generator (element
+        ``i`` of draw ``d`` depends on ``(seed, d, i)`` alone).  ``z`` ``(n_draws, R)``: these normals instead.  One of the
+        two.  ``mu`` and ``Sigma`` stay on the device: call again with another seed, number of draws or nugget without a
+        new predict.  ``LinAlgError`` when ``Sigma + nugget I`` does not factor; ``PsoapError`` without such a predict call."""
+        if (seed is None) == (z is None):
+            raise ValueError("predict_draw takes a seed or z (n_draws, R), one of the two")
+        D = int(n_draws)
+        if z is not None:
+            z = as_f64(np.atleast_2d(z))
+            if z.shape[0] != D:
+                raise ValueError(f"z must hold {D} rows, one per draw; got {z.shape}")
+            R = z.shape[1]
+        else:
+            R = self._sigma_rows
+            seed = int(seed)
+            if not 0 <= seed < 2 ** 64:
+                raise ValueError("seed must be an unsigned 64-bit integer")
+        if z is not None and self._sigma_rows and R != self._sigma_rows:
+            raise ValueError(f"z must have {self._sigma_rows} columns, the rows of the last predict call; got {R}")
+        out = np.empty((max(D, 0), max(R, 0)))
+        status = ctypes.c_int(0)
+        check(self._L.psoap_chunk_predict_draw(self._h, D, ctypes.c_ulonglong(0 if seed is None else seed),
+                                               None if z is None else dptr(z), float(nugget), dptr(out), ctypes.byref(status)),
+              "psoap_chunk_predict_draw")
+        if status.value != 0:
+            raise np.linalg.LinAlgError("Sigma + nugget I is not positive definite")
+        return out
+
     def predict_release(self):
-        """Free the predict workspace (``predict`` and ``predict_marg`` share it); the next call allocates it again."""
+        """Free the predict workspace (``predict``, ``predict_marg`` and ``predict_draw`` share it); the next call allocates
+        it again."""
+        self._sigma_rows = 0
         check(self._L.psoap_chunk_predict_release(self._h), "psoap_chunk_predict_release")
 
     def predict_timings(self) -> dict:

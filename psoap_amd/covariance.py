@@ -473,6 +473,35 @@ def predict_marginal(lwls, fl, sigma, lwls_predict, mus, gp, x, epoch_index, ord
                           want_sigma)
 
 
+def predict_draws(lwls, fl, sigma, lwls_predict, mus, gp, n_draws, seed, mode=0, nugget=1e-8, baseline=None,
+                  want_sigma=True):
+    """Not one function of the reference but the end of its reconstruction scripts (scripts/psoap_retrieve_SB2_draw.py,
+    psoap_retrieve_ST3_draw.py, psoap_predict_*.py --draws: ``np.random.multivariate_normal(mu, Sigma, size=n_draws)``):
+    the posterior of the component spectra and ``n_draws`` spectra drawn from it on the device, without an SVD of the
+    downloaded ``Sigma`` on the host -> ``(mu, Sigma or None, draws)``, ``draws`` ``(n_draws, R)``.  The draws are from
+    ``N(mu, Sigma + nugget I)`` (``ChunkHandle.predict_draw``: why the nugget is needed, what ``seed`` fixes).
+    ``lwls`` (c, N), ``lwls_predict`` (c, M), ``mus`` (c,) -- one value for modes 1 and 2 --, ``gp`` (2c,); ``mode`` as
+    ``ChunkHandle.predict``.  ``baseline``: a dictionary ``x``, ``epoch_index``, ``order``, ``prior_sd`` and optionally
+    ``weight`` -- the arguments of ``predict_marginal``, whose posterior is then the one drawn from.  ``want_sigma=False``
+    forms ``Sigma`` on the device all the same (the draws need it) and spares the download's copy to the caller."""
+    lw = np.stack([as_f64(w) for w in np.atleast_2d(lwls)])
+    pred = np.stack([as_f64(w) for w in np.atleast_2d(lwls_predict)])
+    fl, sigma = as_f64(fl), as_f64(sigma)      # (once: the cache below is keyed on the buffers, and predict_marginal asks it again)
+    h = _chunk_for(fl, sigma)
+    if not hasattr(h, "predict_draw"):
+        raise _lib.PsoapError("predict_draws needs the device in this process (PSOAP_GPU_SERVER serves values only)")
+    if baseline is None:
+        mu, Sigma = h.predict(int(mode), lw, pred, np.atleast_1d(mus), as_f64(gp), True)
+    else:
+        unknown = set(baseline) - {"x", "epoch_index", "order", "prior_sd", "weight"}
+        if unknown or not {"x", "epoch_index", "order", "prior_sd"} <= set(baseline):
+            raise ValueError(f"baseline needs 'x', 'epoch_index', 'order' and 'prior_sd' (and optionally 'weight'); got {sorted(baseline)}")
+        mu, Sigma = predict_marginal(lw, fl, sigma, pred, mus, gp, baseline["x"], baseline["epoch_index"], baseline["order"],
+                                     baseline["prior_sd"], baseline.get("weight"), mode=mode, want_sigma=True)
+    draws = h.predict_draw(n_draws, seed=seed, nugget=nugget)
+    return mu, (Sigma if want_sigma else None), draws
+
+
 def velocity_gradient(grad_lwl, epoch_index, n_epochs):
     """``dlnL/dv[c, e]`` from ``dlnL/dlwl[c, i]``: the rest-frame grids are ``lwl - v[c, epoch]/c_kms``
     (``data.replicate_wls``), so ``dlnL/dv[c, e] = -(1/c_kms) sum_{i in epoch e} dlnL/dlwl[c, i]``.

@@ -9,6 +9,7 @@
 
 #include "abi_error.hpp"
 #include "dag_plan.hpp"
+#include "draw_rng.hpp"
 #include "sky_rules.hpp"
 
 using namespace psoap;
@@ -274,5 +275,15 @@ extern "C" int psoap_dag_pick_workers(int B, const int* Ps, int Mt, int compute_
 {
     if (B < 1 || !Ps || Mt < 0 || compute_units < 1 || max_workers < 1 || !workers) FAIL("psoap_dag_pick_workers: bad arguments");
     *workers = dag_batch_workers(std::vector<int>(Ps, Ps + B), Mt, compute_units, max_workers);
+    return 0;
+}
+
+// Pure host function: the counter block (pair index c0, draw index c1) of the generator behind psoap_chunk_predict_draw and
+// psoap_draw_normals (draw_rng.hpp: Philox4x32-10, key = the two words of seed, counter (c0, c1, 0, 0)).
+extern "C" int psoap_draw_philox(unsigned long long seed, unsigned int c0, unsigned int c1, unsigned int out[4])
+{
+    if (!out) FAIL("psoap_draw_philox: bad arguments");
+    const PhiloxBlock b = draw_block(seed, c0, c1);
+    for (int k = 0; k < 4; ++k) out[k] = b.w[k];
     return 0;
 }

@@ -38,6 +38,7 @@
 #include "marg_grad_kernels.hpp"
 #include "marg_fisher_kernels.hpp"
 #include "marg_predict_kernels.hpp"
+#include "draw_kernels.hpp"
 #include "abi_error.hpp"
 #include "plan_abi.hpp"
 #include "share.hpp"
@@ -220,6 +221,14 @@ struct psoap_chunk {
     psoap_timings last = {};
     // predict workspace (grow-only; psoap_chunk_predict)
     std::unique_ptr<psoap::PredictWs> pws;
+    // posterior draws (psoap_chunk_predict_draw): whether pws holds the mean and Sigma of a predict call that succeeded, of
+    // how many rows and in which mode -- cleared by the calls that form no Sigma, by psoap_chunk_predict_release and by a
+    // change of the data or the baseline; and what a draw needs beyond pws (freed with it)
+    struct SigmaRecord {
+        bool valid = false;
+        int R = 0, mode = 0;
+    } sigma;
+    std::unique_ptr<psoap::DrawWs> dws;
     // gradient workspace (allocated by the first psoap_chunk_lnlike_grad; psoap_chunk_grad_release)
     std::unique_ptr<psoap::GradWs> gws;
     // Fisher workspace (allocated by the first psoap_chunk_fisher; psoap_chunk_fisher_release)
@@ -318,6 +327,7 @@ static int configure_kernels(int device)
     HIP_TRY(marg_grad_configure_kernels());
     HIP_TRY(marg_fisher_configure_kernels());
     HIP_TRY(marg_predict_configure_kernels());
+    HIP_TRY(draw_configure_kernels());
     if (done.size() <= (size_t)device) done.resize((size_t)device + 1, 0);
     done[device] = 1;
     return 0;
@@ -487,6 +497,7 @@ extern "C" int psoap_chunk_set_data(psoap_chunk* h, const double* fl, const doub
     HIP_TRY(hipMemcpy(h->dSigma, sigma, sizeof(double) * h->N, hipMemcpyHostToDevice));
     // a baseline with weights described the old data (w = fl is the usual choice): psoap_chunk_set_baseline again
     if (h->marg.valid && !h->marg.weight.empty()) h->marg.stale_weight = true;
+    h->sigma.valid = false;      // (the posterior in the predict workspace was the old data's)
     // the sorted copies of the slots that hold a batch
     for (BatchSlot& sl : h->slot)
         if (h->sky && sl.B > 0 && sl.sky_valid) {
@@ -2772,6 +2783,7 @@ extern "C" int psoap_chunk_set_baseline(psoap_chunk* h, int order, const double*
     m.sd.assign(prior_sd, prior_sd + order + 1);
     m.valid = true;
     m.stale_weight = false;
+    h->sigma.valid = false;
     if (h->mws) h->mws->basis_ready = false;      // (Ht is built by the next psoap_chunk_lnlike_marg, on its stream)
     return 0;
 }
@@ -3313,8 +3325,10 @@ static int chunk_predict(psoap_chunk* h, int mode, int c, int M, const double* l
         h->pws->n_cus = h->n_cus;
     }
     int status = 0;
+    h->sigma.valid = false;
     const int rc = predict_settled(*h->pws, h->device, mode, c, h->N, M, lwl, nullptr, nullptr, h->dFl, h->dSigma, lwl_pred,
                                    mu_c, gp, mu_out, Sigma_out, &status, var_out);
+    if (rc == 0 && status == 0 && Sigma_out) h->sigma = psoap_chunk::SigmaRecord{true, mode == 0 ? c * M : M, mode};
     if (status_out) *status_out = status;
     return rc;
 }
@@ -3334,6 +3348,8 @@ extern "C" int psoap_chunk_predict_release(psoap_chunk* h)
     DEVICE_SCOPE(h->device);
     if (set_dev(h)) return 1;
     h->pws.reset();
+    h->dws.reset();
+    h->sigma.valid = false;
     return 0;
 }
 
@@ -3351,6 +3367,7 @@ static int marg_predict_run(psoap_chunk* h, const char* who, int mode, int c, in
     if (const char* why = marg_predict_check(mode, c, M, h->marg.valid, h->marg.stale_weight)) FAIL(std::string(who) + ": " + why);
     const auto t_begin = std::chrono::steady_clock::now();
     SigmaPin pin;         // declared first, as in predict_run: its destructor drops the registration on every return path
+    h->sigma.valid = false;
     DEVICE_SCOPE(h->device);
     if (int rc = enter_device(h->device)) return rc;
     if (!h->pws) {
@@ -3539,6 +3556,7 @@ static int marg_predict_run(psoap_chunk* h, const char* who, int mode, int c, in
         for (int q = 0; q < Rq; ++q) var_out[q] = bad ? NAN : h_var[q];
     if (Sigma_out && bad)
         for (size_t k = 0; k < (size_t)Rq * Rq; ++k) Sigma_out[k] = NAN;
+    if (Sigma_out && !bad) h->sigma = psoap_chunk::SigmaRecord{true, Rq, mode};
     const auto t_end = std::chrono::steady_clock::now();
     {
         float a = 0.f, b = 0.f, cms = 0.f;
@@ -3570,6 +3588,96 @@ extern "C" int psoap_chunk_predict_marg_var(psoap_chunk* h, int mode, int c, int
     if (!var_out) FAIL("psoap_chunk_predict_marg_var: var_out is required");
     return marg_predict_run(h, "psoap_chunk_predict_marg_var", mode, c, M, lwl, lwl_pred, mu_c, gp, mu_out, nullptr, var_out,
                             status_out);
+}
+
+// ---- posterior draws (draw_kernels.hpp) ----------------------------------------------------------------------
+// D draws from N(mu, Sigma + nugget I) of the mean and Sigma the handle's predict workspace holds: the copy with the nugget,
+// the staged factorisation of the copy (no right-hand side: the staged kernels carry a zero vector along), the normals and
+// the triangular product -- on the handle's first stream, as the other analysis paths.  Sigma and mu are only read: a second
+// call with another seed or D needs no new predict.
+extern "C" int psoap_chunk_predict_draw(psoap_chunk* h, int D, unsigned long long seed, const double* z, double nugget,
+                                        double* out, int* status_out)
+{
+    if (!h || !out) FAIL("psoap_chunk_predict_draw: bad arguments");
+    if (h->stream.open) FAIL("psoap_chunk_predict_draw: the handle has an open stream (psoap_stream_close first)");
+    if (const char* why = draw_check(h->sigma.valid && h->pws, D, nugget)) FAIL(std::string("psoap_chunk_predict_draw: ") + why);
+    DEVICE_SCOPE(h->device);
+    if (int rc = enter_device(h->device)) return rc;
+    if (!h->dws) h->dws.reset(new DrawWs());
+    PredictWs& ws = *h->pws;
+    DrawWs& w = *h->dws;
+    draw_plan(h->sigma.R, D, w.plan);
+    const DrawPlan& g = w.plan;
+    const int R = g.R, Rpad = g.Rpad, Dpad = g.Dpad, Rt = g.Rt, ld = g.ld;
+    HIP_TRY(w.F.need((size_t)g.factor_doubles));
+    HIP_TRY(w.X.need((size_t)g.out_doubles));
+    HIP_TRY(w.Rhs.need(Rpad));
+    HIP_TRY(w.Wt.need((size_t)NB * NB));
+    HIP_TRY(w.Acc.need(ACC_ROWS + 1));
+    HIP_TRY(w.hAcc.need(1));
+    if (z) HIP_TRY(w.Zin.need((size_t)D * R));
+    hipStream_t s = h->streams[0];
+    double* dF = w.F;
+    double* dZ = dF + Rpad;
+    h->recs.clear();
+    if (z) HIP_TRY(hipMemcpyAsync(w.Zin, z, sizeof(double) * (size_t)D * R, hipMemcpyHostToDevice, s));
+    if (int rc = prof_launch(h, s, PSOAP_K_FILL, 0.0, 16.0 * Rpad * (double)Rpad, [&]() -> int {
+            HIP_TRY(hipMemsetAsync(w.Rhs, 0, sizeof(double) * Rpad, s));
+            HIP_TRY(hipMemsetAsync(w.Acc, 0, sizeof(MatAcc) * (ACC_ROWS + 1), s));
+            hipLaunchKernelGGL(k_draw_copy, dim3((Rpad + 255) / 256, Rpad), dim3(256), 0, s, (const double*)ws.S.p, (size_t)Rpad, R, Rpad,
+                               nugget, dF, (size_t)ld);
+            HIP_TRY(hipGetLastError());
+            return 0;
+        })) return rc;
+    for (int p = 0; p < Rt; ++p) {
+        const int k0 = p * NB;
+        const DrawRow& row = g.rows[(size_t)p];
+        auto update = [&] {
+            hipLaunchKernelGGL(k_panel_update, dim3(row.update, 1), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, dF, (size_t)0, ld, k0);
+        };
+        const StagedRow sr{dF, 0, ld, w.Rhs.p, Rpad, w.Acc.p, w.Wt.p, (size_t)NB * NB, row.strip};
+        if (int rc = staged_row(h, s, sr, 1, k0, row.update > 0 ? &update : nullptr, TILE_FLOPS * p * row.update)) return rc;
+    }
+    if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
+            if (z)
+                hipLaunchKernelGGL(k_draw_load_z, dim3((Dpad + 255) / 256, Rpad), dim3(256), 0, s, (const double*)w.Zin.p, R, Rpad, D,
+                                   Dpad, dZ, (size_t)ld);
+            else
+                hipLaunchKernelGGL(k_draw_normals<true>, dim3((unsigned)(((size_t)(Rpad / 2) * Dpad + 255) / 256)), dim3(256), 0, s, dZ,
+                                   (size_t)ld, (size_t)1, R, Rpad, D, Dpad, seed);
+            hipLaunchKernelGGL(k_acc_total, dim3(1), dim3(1), 0, s, (const MatAcc*)w.Acc.p, Rt, w.Acc.p + ACC_ROWS);
+        })) return rc;
+    if (int rc = prof_launch(h, s, PSOAP_K_GRAD, TILE_FLOPS * draw_trmm_units(g), 0.0, [&] {
+            hipLaunchKernelGGL(k_draw_trmm, dim3(Rt * g.Dt), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)dF, (size_t)ld, Rpad,
+                               Rt, g.Dt, (const double*)ws.Mu.p, R, w.X.p, (size_t)Rpad);
+        })) return rc;
+    HIP_TRY(hipMemcpyAsync(w.hAcc, w.Acc.p + ACC_ROWS, sizeof(MatAcc), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    // Sigma + nugget I does not factor: status 1 and NaN in the output (the plain predict's convention)
+    const bool bad = w.hAcc.p[0].info != 0.0;
+    if (bad)
+        for (size_t k = 0; k < (size_t)D * R; ++k) out[k] = NAN;
+    else
+        HIP_TRY(hipMemcpy2D(out, sizeof(double) * R, w.X, sizeof(double) * Rpad, sizeof(double) * R, (size_t)D, hipMemcpyDeviceToHost));
+    if (collect_timings(h)) return 1;
+    if (status_out) *status_out = bad ? 1 : 0;
+    return 0;
+}
+
+// the generator alone: out[d * n + i], d < D, i < n -- what psoap_chunk_predict_draw uses as z for the same seed
+extern "C" int psoap_draw_normals(int device, unsigned long long seed, int D, int n, double* out)
+{
+    if (D < 1 || n < 1 || !out || (long long)D * n > (1ll << 31)) FAIL("psoap_draw_normals: bad arguments");
+    DEVICE_SCOPE(device);
+    if (int rc = enter_device(device)) return rc;
+    Grow<double> dZ;
+    HIP_TRY(dZ.need((size_t)D * n));
+    const size_t threads = (size_t)((n + 1) / 2) * D;
+    hipLaunchKernelGGL(k_draw_normals<false>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, 0, dZ.p, (size_t)1, (size_t)n, n, n,
+                       D, D, seed);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(out, dZ, sizeof(double) * (size_t)D * n, hipMemcpyDeviceToHost));
+    return 0;
 }
 
 // ---- calibration ------------------------------------------------------------------------------
