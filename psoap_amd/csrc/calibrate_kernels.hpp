@@ -23,6 +23,10 @@
 
 #include "predict_kernels.hpp"
 
+// The staged sweep of [B | appended columns] that both passes run: predict_host.hpp's, through staged_row like every other
+// sweep of the library (defined in psoap_gp.hip behind it, with that file's error channel).
+static int staged_augmented(hipStream_t st, double* dK, int ld, int P, int Mt, double* dW, double* dR, int Npad, psoap::MatAcc* dAcc);
+
 namespace psoap {
 
 // rows / columns N..Npad-1 of a padded symmetric matrix: unit diagonal (the rest is already zero)
@@ -186,7 +190,7 @@ inline int calibrate_run(const CalibInputs& in, double* fl_cor, double* X, int* 
 
         // ---- pass 1
         hipLaunchKernelGGL(k_init_rhs, dim3((Npad + 255) / 256, 1), dim3(256), 0, 0, dR, Npad, N, dFlFix, in.mu, dAcc);
-        factor_augmented((hipStream_t)0, dK1, ld1, P1, Mpad / NB, dW, dR, Npad, dAcc);
+        if (int rc = staged_augmented((hipStream_t)0, dK1, (int)ld1, P1, Mpad / NB, dW, dR, Npad, dAcc)) return rc;
         hipLaunchKernelGGL(k_acc_total, dim3(1), dim3(1), 0, 0, dAcc, P1, dAcc + ACC_ROWS);
         CAL_TRY(hipGetLastError());
         CAL_TRY(hipMemcpy(&hacc, dAcc + ACC_ROWS, sizeof(MatAcc), hipMemcpyDeviceToHost));
@@ -202,7 +206,7 @@ inline int calibrate_run(const CalibInputs& in, double* fl_cor, double* X, int* 
 
         // ---- pass 2
         hipLaunchKernelGGL(k_init_rhs, dim3((Mpad + 255) / 256, 1), dim3(256), 0, 0, dR, Mpad, M, dMu, 0.0, dAcc);
-        factor_augmented((hipStream_t)0, dK2, ld2, P2, 1, dW, dR, Mpad, dAcc);
+        if (int rc = staged_augmented((hipStream_t)0, dK2, (int)ld2, P2, 1, dW, dR, Mpad, dAcc)) return rc;
         hipLaunchKernelGGL(k_acc_total, dim3(1), dim3(1), 0, 0, dAcc, P2, dAcc + ACC_ROWS);
         CAL_TRY(hipGetLastError());
         CAL_TRY(hipMemcpy(&hacc, dAcc + ACC_ROWS, sizeof(MatAcc), hipMemcpyDeviceToHost));

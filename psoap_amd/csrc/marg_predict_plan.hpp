@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "marg_plan.hpp"
+#include "predict_plan.hpp"
 
 namespace psoap {
 
@@ -40,7 +41,8 @@ struct MargPredictRow {
 struct MargPredictPlan {
     int N = 0, P = 0, Q = 0;
     int mode = 0, c = 0, M = 0;
-    int R = 0, Rt = 0;                    // prediction columns, their tile columns
+    PredictShape shape;                   // the plain call's numbers for this mode, c and M (its ld is not this layout's)
+    int R = 0, Rt = 0;                    // prediction columns, their tile columns: the shape's
     int ld = 0;                           // doubles per row of [K | Cx^T | Ht]
     int tile_C = 0, tile_H = 0;           // first tile column of Cx^T and of Ht
     std::vector<int> tile, first;         // per appended column (C_0 .. C_{Rt-1}, H_0 .. H_{Q-1} in the column order of H)
@@ -66,7 +68,8 @@ inline const char* marg_predict_check(int mode, int c, int M, bool have_baseline
     return nullptr;
 }
 
-inline void marg_predict_plan(const MargPlan& pl, int mode, int c, int M, MargPredictPlan& out)
+// mu0: the first prior mean (what predict_f takes off fl)
+inline void marg_predict_plan(const MargPlan& pl, int mode, int c, int M, MargPredictPlan& out, double mu0 = 1.0)
 {
     out = MargPredictPlan();
     const int P = pl.P, Q = pl.Q;
@@ -76,8 +79,9 @@ inline void marg_predict_plan(const MargPlan& pl, int mode, int c, int M, MargPr
     out.mode = mode;
     out.c = c;
     out.M = M;
-    out.R = mode == 0 ? c * M : M;
-    const int Rt = round_up(out.R, NB) / NB;
+    (void)predict_shape(mode, c, pl.N, M, mu0, out.shape);      // (never the transposed mean: marg_predict_check)
+    out.R = out.shape.Rq;
+    const int Rt = out.shape.Rq_pad / NB;
     out.Rt = Rt;
     out.ld = NB * (P + Rt + Q);
     out.tile_C = P;
@@ -129,8 +133,7 @@ inline double marg_predict_gram_units(const MargPredictPlan& g)
 inline double marg_predict_flops(const MargPredictPlan& g, bool sigma, bool var)
 {
     const double n = (double)NB * g.P, r = (double)NB * g.Rt, s = g.S;
-    const double plain = n * n * n / 3.0 + n * n * r + (sigma ? n * r * r : (var ? 2.0 * n * r : 0.0)) + 2.0 * n * r;
-    return plain + n * s * (s + r) + s * s * s / 3.0 + s * s * r + (sigma ? s * r * r : (var ? 2.0 * s * r : 0.0));
+    return predict_flops(n, r, sigma, var) + n * s * (s + r) + s * s * s / 3.0 + s * s * r + (sigma ? s * r * r : (var ? 2.0 * s * r : 0.0));
 }
 
 }  // namespace psoap

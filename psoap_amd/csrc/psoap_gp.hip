@@ -802,11 +802,12 @@ extern "C" int psoap_orbit_velocities(int device, int model, int B, const double
 // ---- profiling helpers ------------------------------------------------------------------
 // One bracketed step: what `launch` queues on s, booked under class cls (with profiling on: a record and a pair of timed
 // events around it).  A launch that returns nothing queues kernels only and the launch error is asked for here; one that
-// makes runtime calls of its own returns its status.
+// makes runtime calls of its own returns its status.  h == nullptr: the step is queued and nothing is booked.
 template <class L>
 static int prof_launch(psoap_chunk* h, hipStream_t s, int cls, double flops, double bytes, L&& launch)
 {
-    if (h->profiling) {
+    const bool book = h && h->profiling;      // (no handle: nothing to book into -- the plain predict's staged sweep)
+    if (book) {
         size_t need = h->recs.size() * 2 + 2;
         while (h->evPool.size() < need) {
             Event e;
@@ -828,7 +829,7 @@ static int prof_launch(psoap_chunk* h, hipStream_t s, int cls, double flops, dou
     } else if (int rc = launch()) {
         return rc;
     }
-    if (h->profiling) HIP_TRY(hipEventRecord(h->evPool[h->recs.back().e1], s));
+    if (book) HIP_TRY(hipEventRecord(h->evPool[h->recs.back().e1], s));
     return 0;
 }
 
@@ -870,6 +871,8 @@ static int staged_row(psoap_chunk* h, hipStream_t s, const StagedRow& m, int nb,
             })) return rc;
     return 0;
 }
+
+#include "predict_host.hpp"
 
 template <int C>
 static void launch_fill(psoap_chunk* h, const BatchSlot& sl, hipStream_t s, int b0, int nb, int upper_only)
@@ -3147,15 +3150,6 @@ extern "C" int psoap_fill_cross(int device, int M, int N, const double* lwl_row,
 }
 
 // ---- predict ---------------------------------------------------------------------------------
-static int predict_check(int mode, int c, int N, int M, const void* lwl, const void* lwl_pred, const void* mu_c,
-                         const void* gp, const void* mu_out)
-{
-    if (mode < 0 || mode > 2 || c < 1 || c > 3 || N <= 0 || M <= 0 || !lwl || !lwl_pred || !mu_c || !gp || !mu_out)
-        FAIL("psoap_predict: bad arguments");
-    if (mode == 2 && c != 1) FAIL("psoap_predict: mode 2 (predict_f) needs c == 1");
-    return 0;
-}
-
 // predict_run until its persistent launch came through undisturbed (return code 3: a workgroup moved, see dag_where), then
 // -- or at once where share_wants_staged says so -- by the staged loop of the transposed-mean variant
 static int predict_settled(PredictWs& ws, int device, int mode, int c, int N, int M, const double* lwl, const double* fl,
@@ -3167,8 +3161,7 @@ static int predict_settled(PredictWs& ws, int device, int mode, int c, int N, in
     if (staged) g_share.staged_policy += 1;
     for (int attempt = 0;; ++attempt) {
         if (!staged) g_share.dag_launches += 1;
-        int rc = predict_run(ws, mode, c, N, M, lwl, fl, sigma, dFl, dSig, lwl_pred, mu_c, gp, mu_out, Sigma_out, status, g_err,
-                             var_out, staged);
+        int rc = predict_run(ws, mode, c, N, M, lwl, fl, sigma, dFl, dSig, lwl_pred, mu_c, gp, mu_out, Sigma_out, status, var_out, staged);
         if (rc == 0 && !staged && share_inject_taint()) rc = 3;
         if (rc != 3) return rc;
         g_share.tainted += 1;
@@ -3195,7 +3188,7 @@ extern "C" int psoap_predict(int device, int mode, int c, int N, int M, const do
                              double* mu_out, double* Sigma_out, int* status_out)
 {
     if (!fl || !sigma) FAIL("psoap_predict: bad arguments");
-    if (int rc = predict_check(mode, c, N, M, lwl, lwl_pred, mu_c, gp, mu_out)) return rc;
+    if (const char* why = predict_check(mode, c, N, M, lwl && lwl_pred && mu_c && gp && mu_out)) FAIL(why);
     DEVICE_SCOPE(device);
     if (int rc = enter_device(device)) return rc;
     PredictWs ws;
@@ -3217,12 +3210,7 @@ struct psoap_predictor {
 
 static void copy_times(const PredictTimes& pt, psoap_predict_timings* t)
 {
-    t->device_ms = pt.device_ms;
-    t->factor_ms = pt.factor_ms;
-    t->sigma_ms = pt.sigma_ms;
-    t->download_ms = pt.download_ms;
-    t->total_ms = pt.total_ms;
-    t->flops = pt.flops;
+    *t = psoap_predict_timings{pt.device_ms, pt.factor_ms, pt.sigma_ms, pt.download_ms, pt.total_ms, pt.flops};
 }
 
 extern "C" int psoap_predictor_create(psoap_predictor** out, int device)
@@ -3256,7 +3244,7 @@ extern "C" int psoap_predictor_run(psoap_predictor* p, int mode, int c, int N, i
                                    const double* gp, double* mu_out, double* Sigma_out, int* status_out)
 {
     if (!p || !fl || !sigma) FAIL("psoap_predictor_run: bad arguments");
-    if (int rc = predict_check(mode, c, N, M, lwl, lwl_pred, mu_c, gp, mu_out)) return rc;
+    if (const char* why = predict_check(mode, c, N, M, lwl && lwl_pred && mu_c && gp && mu_out)) FAIL(why);
     DEVICE_SCOPE(p->device);
     if (int rc = enter_device(p->device)) return rc;
     int status = 0;
@@ -3272,7 +3260,7 @@ extern "C" int psoap_predictor_run_var(psoap_predictor* p, int mode, int c, int 
                                        const double* gp, double* mu_out, double* var_out, int* status_out)
 {
     if (!p || !fl || !sigma || !var_out) FAIL("psoap_predictor_run_var: bad arguments");
-    if (int rc = predict_check(mode, c, N, M, lwl, lwl_pred, mu_c, gp, mu_out)) return rc;
+    if (const char* why = predict_check(mode, c, N, M, lwl && lwl_pred && mu_c && gp && mu_out)) FAIL(why);
     DEVICE_SCOPE(p->device);
     if (int rc = enter_device(p->device)) return rc;
     int status = 0;
@@ -3293,7 +3281,20 @@ extern "C" int psoap_predictor_timings(psoap_predictor* p, psoap_predict_timings
 // grow-only workspace owned by the handle, so a second call of the same shape allocates nothing.
 static int chunk_predict(psoap_chunk* h, int mode, int c, int M, const double* lwl, const double* lwl_pred,
                          const double* mu_c, const double* gp, double* mu_out, double* Sigma_out, double* var_out,
-                         int* status_out);
+                         int* status_out)
+{
+    if (!h) FAIL("psoap_chunk_predict: null handle");
+    if (const char* why = predict_check(mode, c, h->N, M, lwl && lwl_pred && mu_c && gp && mu_out)) FAIL(why);
+    DEVICE_SCOPE(h->device);
+    if (int rc = enter_device(h->device)) return rc;
+    int status = 0;
+    h->sigma.valid = false;
+    const int rc = predict_settled(predict_ws_of(h), h->device, mode, c, h->N, M, lwl, nullptr, nullptr, h->dFl, h->dSigma, lwl_pred,
+                                   mu_c, gp, mu_out, Sigma_out, &status, var_out);
+    if (rc == 0 && status == 0 && Sigma_out) h->sigma = psoap_chunk::SigmaRecord{true, mode == 0 ? c * M : M, mode};
+    if (status_out) *status_out = status;
+    return rc;
+}
 
 extern "C" int psoap_chunk_predict(psoap_chunk* h, int mode, int c, int M, const double* lwl, const double* lwl_pred,
                                    const double* mu_c, const double* gp, double* mu_out, double* Sigma_out,
@@ -3309,28 +3310,6 @@ extern "C" int psoap_chunk_predict_var(psoap_chunk* h, int mode, int c, int M, c
 {
     if (!var_out) FAIL("psoap_chunk_predict_var: var_out is required");
     return chunk_predict(h, mode, c, M, lwl, lwl_pred, mu_c, gp, mu_out, nullptr, var_out, status_out);
-}
-
-static int chunk_predict(psoap_chunk* h, int mode, int c, int M, const double* lwl, const double* lwl_pred,
-                         const double* mu_c, const double* gp, double* mu_out, double* Sigma_out, double* var_out,
-                         int* status_out)
-{
-    if (!h) FAIL("psoap_chunk_predict: null handle");
-    if (int rc = predict_check(mode, c, h->N, M, lwl, lwl_pred, mu_c, gp, mu_out)) return rc;
-    DEVICE_SCOPE(h->device);
-    if (int rc = enter_device(h->device)) return rc;
-    if (!h->pws) {
-        h->pws.reset(new PredictWs());
-        h->pws->workers = dag_two_per_cu(h->dag_grid, h->n_cus);       // (as predict_ws_init)
-        h->pws->n_cus = h->n_cus;
-    }
-    int status = 0;
-    h->sigma.valid = false;
-    const int rc = predict_settled(*h->pws, h->device, mode, c, h->N, M, lwl, nullptr, nullptr, h->dFl, h->dSigma, lwl_pred,
-                                   mu_c, gp, mu_out, Sigma_out, &status, var_out);
-    if (rc == 0 && status == 0 && Sigma_out) h->sigma = psoap_chunk::SigmaRecord{true, mode == 0 ? c * M : M, mode};
-    if (status_out) *status_out = status;
-    return rc;
 }
 
 extern "C" int psoap_chunk_predict_timings(psoap_chunk* h, psoap_predict_timings* t)
@@ -3358,6 +3337,50 @@ extern "C" int psoap_chunk_predict_release(psoap_chunk* h)
 // staged factorisation of [M | G] beside the baseline's device side, then mean, Sigma or the variances -- on the handle's
 // first stream behind whatever the handle has in flight, as the other analysis paths.  The plain predict path, its
 // persistent launch and its task lists are not touched: only its workspace is shared (grown, never shrunk).
+// the two staged factorisations of a call and the Gram launch between them: [K | Cx^T | Ht] in the predict workspace (block
+// row p: the rest of K's row, all of Cx^T and the slots of Ht whose first non-zero block row is <= p -- one contiguous range
+// of tile columns, k_marg_panel_update with P + Rt in the place of P), then [M | G]: M = U_M^T U_M with bt alongside; the
+// appended block becomes Y = U_M^-T G and the right-hand side y
+static int marg_predict_factor(psoap_chunk* h, PredictWs& ws, MargWs& m, MargPredictWs& mp, hipStream_t s, const double* gp)
+{
+    const MargPredictPlan& g = mp.plan;
+    const int N = h->N, Npad = h->Npad, P = h->P, Q = g.Q, S = g.S, ld = g.ld, ldm = g.ldm, Rt = g.Rt, ntiles = (int)g.gram.size();
+    double *dK = ws.K, *dR = ws.R, *dMx = mp.Mx;
+    double* Ah = dK + NB * Rt;      // what the kernels of marg_kernels.hpp take for [K | Ht]: Ht lies Rpad further right
+    const int* tab = m.Tab.p;
+    // Ht from each slot's first block row on
+    if (int rc = prof_launch(h, s, PSOAP_K_FILL, 0.0, 12.0 * N * (N + 1.0), [&] {
+            predict_fill(ws, g.shape, s, (size_t)ld, gp, h->dSigma.p);
+            hipLaunchKernelGGL(k_marg_load, dim3(Q * P, 1), dim3(256), 0, s, Ah, (size_t)0, ld, Npad, P, (const double*)m.Ht.p, S, tab);
+        })) return rc;
+    if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
+            hipLaunchKernelGGL(k_init_rhs, dim3((Npad + 255) / 256, 1), dim3(256), 0, s, dR, Npad, N, h->dFl, g.shape.offset, ws.Acc.p);
+        })) return rc;
+    for (int p = 0; p < P; ++p) {
+        const int k0 = p * NB;
+        const MargPredictRow& row = g.rows[(size_t)p];
+        auto update = [&] {
+            hipLaunchKernelGGL(k_marg_panel_update, dim3(row.update, 1), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, dK, (size_t)0, ld, k0,
+                               P + Rt, tab);
+        };
+        const StagedRow sr{dK, 0, ld, dR, Npad, ws.Acc.p, ws.W.p, (size_t)NB * NB, row.strip};
+        if (int rc = staged_row(h, s, sr, 1, k0, row.update > 0 ? &update : nullptr, TILE_FLOPS * p * row.update)) return rc;
+    }
+    if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] { launch_marg_rhs(h, m, s, 1, Ah, 0, ld, dR); })) return rc;
+    if (int rc = prof_launch(h, s, PSOAP_K_GRAD, TILE_FLOPS * marg_predict_gram_units(g), 0.0, [&] {
+            hipLaunchKernelGGL(k_marg_predict_gram, dim3(ntiles), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)dK, ld, Npad,
+                               (const MargPredictTile*)mp.Tiles.p, dMx, ldm);
+        })) return rc;
+    for (int p = 0; p < Q; ++p) {
+        const int k0 = p * NB;
+        const MargPredictRow& row = g.mrows[(size_t)p];
+        const StagedRow mrow{dMx, 0, ldm, m.Rhs.p, S, m.AccM.p, m.WtM.p + (size_t)p * NB * NB, (size_t)Q * NB * NB, row.strip};
+        const auto update = plain_update(s, dMx, ldm, k0, row.update);
+        if (int rc = staged_row(h, s, mrow, 1, k0, row.update > 0 ? &update : nullptr, TILE_FLOPS * p * row.update)) return rc;
+    }
+    return 0;
+}
+
 static int marg_predict_run(psoap_chunk* h, const char* who, int mode, int c, int M, const double* lwl, const double* lwl_pred,
                             const double* mu_c, const double* gp, double* mu_out, double* Sigma_out, double* var_out,
                             int* status_out)
@@ -3370,122 +3393,42 @@ static int marg_predict_run(psoap_chunk* h, const char* who, int mode, int c, in
     h->sigma.valid = false;
     DEVICE_SCOPE(h->device);
     if (int rc = enter_device(h->device)) return rc;
-    if (!h->pws) {
-        h->pws.reset(new PredictWs());
-        h->pws->workers = dag_two_per_cu(h->dag_grid, h->n_cus);       // (as chunk_predict: the plain call finds what it expects)
-        h->pws->n_cus = h->n_cus;
-    }
+    PredictWs& ws = predict_ws_of(h);      // (the plain call finds what it expects)
     if (!h->mws) h->mws.reset(new MargWs());
     if (!h->mpws) h->mpws.reset(new MargPredictWs());
-    PredictWs& ws = *h->pws;
     MargWs& m = *h->mws;
     MargPredictWs& mp = *h->mpws;
-    const MargPlan& pl = h->marg.plan;
-    marg_predict_plan(pl, mode, c, M, mp.plan);
+    marg_predict_plan(h->marg.plan, mode, c, M, mp.plan, mu_c[0]);
     const MargPredictPlan& g = mp.plan;
-    const int N = h->N, Npad = h->Npad, P = h->P, Q = pl.Q, S = g.S, ld = g.ld, ldm = g.ldm;
-    const int Rq = g.R, Rt = g.Rt, Rq_pad = NB * Rt, St = g.St;
-    const int nslab = (Npad + 255) / 256, nslab_y = (S + 255) / 256, ntiles = (int)g.gram.size();
-    const double offset = (mode == 0 || mode == 1) ? 1.0 : mu_c[0];      // :140,:184,:248 vs :52 (mode 1 here is c == 2)
-    if (!ws.stream) {
-        HIP_TRY(ws.stream.create());
-        for (Event& e : ws.ev) HIP_TRY(e.create(hipEventDefault));
-    }
+    const PredictShape& sh = g.shape;
+    const int Npad = h->Npad, P = h->P, Q = g.Q, S = g.S, ld = g.ld, ldm = g.ldm;
+    const int Rq = g.R, Rt = g.Rt, Rq_pad = sh.Rq_pad, nslab = sh.nslab, nslab_y = (S + 255) / 256, ntiles = (int)g.gram.size();
+    const PredictStaging hs = predict_staging(Rq_pad, 2 * sizeof(MatAcc), 0);
+    if (int rc = predict_stream(ws)) return rc;
     if (Sigma_out) pin.start(Sigma_out, sizeof(double) * (size_t)Rq * Rq, h->device);
     hipStream_t s = h->streams[0];
-    HIP_TRY(ws.K.need((size_t)Npad * ld));
-    HIP_TRY(ws.W.need(WT_STRIDE));
-    HIP_TRY(ws.R.need(Npad));
-    HIP_TRY(ws.Acc.need(ACC_ROWS + 1));
-    HIP_TRY(ws.Lwl.need((size_t)c * N));
-    HIP_TRY(ws.Pred.need((size_t)c * M));
-    HIP_TRY(ws.Gp.need(6));
-    HIP_TRY(ws.Mu.need(Rq_pad));
-    HIP_TRY(ws.M0.need(Rq_pad));
-    HIP_TRY(ws.Part.need((size_t)nslab * Rq_pad));
-    HIP_TRY(ws.hSmall.need(4 * (size_t)Rq_pad + 8));
+    if (int rc = predict_need(ws, sh, (size_t)ld, hs.total)) return rc;
     HIP_TRY(mp.Mx.need((size_t)S * ldm));
     HIP_TRY(mp.PartY.need((size_t)nslab_y * Rq_pad));
     HIP_TRY(mp.Tiles.need((size_t)ntiles));
     HIP_TRY(mp.AccTot.need(2));
     if (int rc = marg_ws_need(h, m, 1, false)) return rc;
     if (int rc = marg_basis(h, m, s)) return rc;
-    double* h_m0 = ws.hSmall;               // pinned: (Rq_pad) each
-    double* h_mu = h_m0 + Rq_pad;
-    double* h_var = h_mu + Rq_pad;
-    double* h_prior = h_var + Rq_pad;
-    MatAcc* h_acc = reinterpret_cast<MatAcc*>(h_prior + Rq_pad);      // the totals of K's records, then of M's
-    double *dK = ws.K, *dW = ws.W, *dR = ws.R, *dLwl = ws.Lwl, *dPred = ws.Pred, *dGp = ws.Gp, *dMx = mp.Mx;
-    double* Ah = dK + Rq_pad;      // what the kernels of marg_kernels.hpp take for [K | Ht]: Ht lies Rpad further right
-    const double* Wc = dK + Npad;
-    const double* Y = dMx + S;
-    const int* tab = m.Tab.p;
-    GpHost gall;
-    for (int k = 0; k < 6; ++k) gall.v[k] = (k < 2 * c) ? gp[k] : 0.0;
+    double *h_mu = ws.hSmall.p + hs.mu, *h_var = ws.hSmall.p + hs.var;
+    MatAcc* h_acc = reinterpret_cast<MatAcc*>(ws.hSmall.p + hs.acc);      // the totals of K's records, then of M's
+    const double* Wc = ws.K.p + Npad;
+    const double* Y = mp.Mx.p + S;
     h->recs.clear();
     const auto t_ev0 = std::chrono::steady_clock::now();
     HIP_TRY(hipEventRecord(ws.ev[0], s));
-    HIP_TRY(hipMemcpyAsync(dLwl, lwl, sizeof(double) * (size_t)c * N, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(dPred, lwl_pred, sizeof(double) * (size_t)c * M, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(dGp, gp, sizeof(double) * 2 * c, hipMemcpyHostToDevice, s));
-    for (int q = 0; q < Rq; ++q) h_m0[q] = (mode == 0) ? mu_c[q / M] : mu_c[0];
-    HIP_TRY(hipMemcpyAsync(ws.M0, h_m0, sizeof(double) * Rq, hipMemcpyHostToDevice, s));
+    if (int rc = predict_upload(ws, sh, s, lwl, lwl_pred, gp, mu_c, nullptr, nullptr, ws.hSmall.p + hs.m0)) return rc;
     HIP_TRY(hipMemcpyAsync(mp.Tiles, g.gram.data(), sizeof(MargPredictTile) * (size_t)ntiles, hipMemcpyHostToDevice, s));
     HIP_TRY(hipEventRecord(ws.ev[1], s));
-    // [K | Cx^T | Ht]: cleared (padding rows and columns are exact zeros), K's upper tiles, Cx^T as the staged branch of
-    // predict_run fills it, Ht from each slot's first block row on
-    if (int rc = prof_launch(h, s, PSOAP_K_FILL, 0.0, 12.0 * N * (N + 1.0), [&] {
-            hipLaunchKernelGGL(k_zero, dim3(2048), dim3(256), 0, s, dK, (size_t)Npad * ld);
-            with_components(c, [&](auto nc) {
-                hipLaunchKernelGGL(k_fill_sym<nc()>, dim3(P * (P + 1) / 2, 1), dim3(256), 0, s, dK, (size_t)0, ld, N, P,
-                                   (const double*)dLwl, (const double*)dGp, (const double*)h->dSigma.p, 1);
-            });
-            if (mode == 0) {
-                for (int k = 0; k < c; ++k) {
-                    GpHost g1;
-                    g1.v[0] = gp[2 * k];
-                    g1.v[1] = gp[2 * k + 1];
-                    launch_region_c(s, 1, dK, (size_t)ld, Npad + k * M, N, M, dLwl + (size_t)k * N, 0, dPred + (size_t)k * M, 0, g1, 0, 0.0);
-                }
-            } else {
-                launch_region_c(s, c, dK, (size_t)ld, Npad, N, M, dLwl, (size_t)N, dPred, (size_t)M, gall, 0, 0.0);
-            }
-            hipLaunchKernelGGL(k_marg_load, dim3(Q * P, 1), dim3(256), 0, s, Ah, (size_t)0, ld, Npad, P, (const double*)m.Ht.p, S, tab);
-        })) return rc;
-    if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
-            hipLaunchKernelGGL(k_init_rhs, dim3((Npad + 255) / 256, 1), dim3(256), 0, s, dR, Npad, N, h->dFl, offset, ws.Acc.p);
-        })) return rc;
-    // block row p: the rest of K's row, all of Cx^T and the slots of Ht whose first non-zero block row is <= p -- one
-    // contiguous range of tile columns (k_marg_panel_update with P + Rt in the place of P)
-    for (int p = 0; p < P; ++p) {
-        const int k0 = p * NB;
-        const MargPredictRow& row = g.rows[(size_t)p];
-        auto update = [&] {
-            hipLaunchKernelGGL(k_marg_panel_update, dim3(row.update, 1), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, dK, (size_t)0, ld, k0,
-                               P + Rt, tab);
-        };
-        const StagedRow sr{dK, 0, ld, dR, Npad, ws.Acc.p, dW, (size_t)NB * NB, row.strip};
-        if (int rc = staged_row(h, s, sr, 1, k0, row.update > 0 ? &update : nullptr, TILE_FLOPS * p * row.update)) return rc;
-    }
-    if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] { launch_marg_rhs(h, m, s, 1, Ah, 0, ld, dR); })) return rc;
-    if (int rc = prof_launch(h, s, PSOAP_K_GRAD, TILE_FLOPS * marg_predict_gram_units(g), 0.0, [&] {
-            hipLaunchKernelGGL(k_marg_predict_gram, dim3(ntiles), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)dK, ld, Npad,
-                               (const MargPredictTile*)mp.Tiles.p, dMx, ldm);
-        })) return rc;
-    // [M | G]: M = U_M^T U_M with bt alongside; the appended block becomes Y = U_M^-T G and the right-hand side y
-    for (int p = 0; p < Q; ++p) {
-        const int k0 = p * NB;
-        const MargPredictRow& row = g.mrows[(size_t)p];
-        const StagedRow mrow{dMx, 0, ldm, m.Rhs.p, S, m.AccM.p, m.WtM.p + (size_t)p * NB * NB, (size_t)Q * NB * NB, row.strip};
-        auto update = [&] {
-            hipLaunchKernelGGL(k_panel_update, dim3(row.update, 1), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, dMx, (size_t)0, ldm, k0);
-        };
-        if (int rc = staged_row(h, s, mrow, 1, k0, row.update > 0 ? &update : nullptr, TILE_FLOPS * p * row.update)) return rc;
-    }
+    if (int rc = marg_predict_factor(h, ws, m, mp, s, gp)) return rc;
     HIP_TRY(hipEventRecord(ws.ev[2], s));
     // mean: m0 + Wc^T z - Y^T y, the two sums each in two fixed-order stages; the totals of both factorisations' records
     if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
-            hipLaunchKernelGGL(k_gemv_t_partial, dim3(Rt, nslab), dim3(256), 0, s, Wc, (size_t)ld, Npad, Rq, (const double*)dR, ws.Part.p);
+            hipLaunchKernelGGL(k_gemv_t_partial, dim3(Rt, nslab), dim3(256), 0, s, Wc, (size_t)ld, Npad, Rq, (const double*)ws.R.p, ws.Part.p);
             hipLaunchKernelGGL(k_gemv_t_partial, dim3(Rt, nslab_y), dim3(256), 0, s, Y, (size_t)ldm, S, Rq, (const double*)m.Rhs.p,
                                mp.PartY.p);
             hipLaunchKernelGGL(k_marg_predict_mean, dim3((Rq + 255) / 256), dim3(256), 0, s, (const double*)ws.Part.p, nslab,
@@ -3498,41 +3441,18 @@ static int marg_predict_run(psoap_chunk* h, const char* who, int mode, int c, in
     bool sigma_direct = false;
     if (Sigma_out) {
         HIP_TRY(ws.S.need((size_t)Rq_pad * Rq_pad));
-        double* dS = ws.S;
-        // the prior covariance of the prediction in the upper tiles, as the separate product of predict_run has it; then
-        // every upper tile in one launch (predict_run: launching tile rows one after the other serialises them)
+        // the prior covariance of the prediction in the upper tiles (mode 1 here is predict_f_g_sum: its nugget, :165), then
+        // every upper tile in one launch (launching tile rows one after the other serialises them)
         if (int rc = prof_launch(h, s, PSOAP_K_GRAD, TILE_FLOPS * g.sigma_tiles * (P + Q), 0.0, [&] {
-                if (mode == 0) {
-                    hipLaunchKernelGGL(k_zero, dim3(1024), dim3(256), 0, s, dS, (size_t)Rq_pad * Rq_pad);
-                    for (int k = 0; k < c; ++k) {
-                        GpHost g1;
-                        g1.v[0] = gp[2 * k];
-                        g1.v[1] = gp[2 * k + 1];
-                        launch_region_c(s, 1, dS + (size_t)k * M * Rq_pad, (size_t)Rq_pad, k * M, M, M, dPred + (size_t)k * M, 0,
-                                         dPred + (size_t)k * M, 0, g1, 1, 0.0);
-                    }
-                } else {
-                    const double nug = (mode == 1) ? 1e-8 : 0.0;      // predict_f_g_sum's nugget (:165)
-                    if (Rq_pad != Rq) hipLaunchKernelGGL(k_zero, dim3(1024), dim3(256), 0, s, dS, (size_t)Rq_pad * Rq_pad);
-                    launch_region_c(s, c, dS, (size_t)Rq_pad, 0, M, M, dPred, (size_t)M, dPred, (size_t)M, gall, 1, nug);
-                }
+                predict_fill_prior(ws, sh, s, gp, (mode == 1) ? 1e-8 : 0.0);
                 hipLaunchKernelGGL(k_marg_predict_sigma, dim3(g.sigma_tiles), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, Wc, (size_t)ld, Npad,
-                                   Y, (size_t)ldm, S, dS, (size_t)Rq_pad, St, 0);
+                                   Y, (size_t)ldm, S, ws.S.p, (size_t)Rq_pad, g.St, 0);
             })) return rc;
         HIP_TRY(hipEventRecord(ws.ev[3], s));
-        const bool locked = pin.wait();
-        if (locked) {
-            pin.queued_on(s);
-            HIP_TRY(hipMemcpy2DAsync(Sigma_out, sizeof(double) * Rq, dS, sizeof(double) * Rq_pad, sizeof(double) * Rq, (size_t)Rq,
-                                     hipMemcpyDeviceToHost, s));
-        }
-        sigma_direct = locked;
+        if (int rc = predict_sigma_direct(pin, ws, sh, s, Sigma_out, &sigma_direct)) return rc;
     }
     if (var_out) {
-        HIP_TRY(ws.Var.need(Rq_pad));
-        HIP_TRY(ws.Prior.need(Rq_pad));
-        for (int q = 0; q < Rq; ++q) h_prior[q] = predict_prior_variance(mode, c, M, q, gp);
-        HIP_TRY(hipMemcpyAsync(ws.Prior, h_prior, sizeof(double) * Rq, hipMemcpyHostToDevice, s));
+        if (int rc = predict_upload_prior(ws, sh, s, gp, ws.hSmall.p + hs.prior)) return rc;
         if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
                 hipLaunchKernelGGL(k_colnorm_partial, dim3(Rt, nslab), dim3(256), 0, s, Wc, (size_t)ld, Npad, Rq, ws.Part.p);
                 hipLaunchKernelGGL(k_colnorm_partial, dim3(Rt, nslab_y), dim3(256), 0, s, Y, (size_t)ldm, S, Rq, mp.PartY.p);
@@ -3544,8 +3464,7 @@ static int marg_predict_run(psoap_chunk* h, const char* who, int mode, int c, in
     if (!Sigma_out) HIP_TRY(hipEventRecord(ws.ev[3], s));
     HIP_TRY(hipStreamSynchronize(s));
     if (Sigma_out && !sigma_direct)
-        HIP_TRY(hipMemcpy2D(Sigma_out, sizeof(double) * Rq, ws.S, sizeof(double) * Rq_pad, sizeof(double) * Rq, Rq,
-                            hipMemcpyDeviceToHost));
+        if (int rc = predict_sigma_staged(ws, sh, Sigma_out)) return rc;
     pin.release();
     if (collect_timings(h)) return 1;
     // K not positive definite or an M that does not factor: status 1 and NaN in every output (the plain predict's convention)
@@ -3557,21 +3476,7 @@ static int marg_predict_run(psoap_chunk* h, const char* who, int mode, int c, in
     if (Sigma_out && bad)
         for (size_t k = 0; k < (size_t)Rq * Rq; ++k) Sigma_out[k] = NAN;
     if (Sigma_out && !bad) h->sigma = psoap_chunk::SigmaRecord{true, Rq, mode};
-    const auto t_end = std::chrono::steady_clock::now();
-    {
-        float a = 0.f, b = 0.f, cms = 0.f;
-        (void)hipEventElapsedTime(&a, ws.ev[0], ws.ev[3]);
-        (void)hipEventElapsedTime(&b, ws.ev[1], ws.ev[2]);
-        (void)hipEventElapsedTime(&cms, ws.ev[2], ws.ev[3]);
-        PredictTimes& t = ws.times;
-        t.device_ms = a;
-        t.factor_ms = b;
-        t.sigma_ms = cms;
-        t.total_ms = std::chrono::duration<double, std::milli>(t_end - t_begin).count();
-        const double pre_ms = std::chrono::duration<double, std::milli>(t_ev0 - t_begin).count();
-        t.download_ms = t.total_ms - pre_ms - (double)a > 0.0 ? t.total_ms - pre_ms - (double)a : 0.0;
-        t.flops = marg_predict_flops(g, Sigma_out != nullptr, var_out != nullptr);
-    }
+    predict_times(ws, t_begin, t_ev0, marg_predict_flops(g, Sigma_out != nullptr, var_out != nullptr));
     return 0;
 }
 
@@ -3632,9 +3537,7 @@ extern "C" int psoap_chunk_predict_draw(psoap_chunk* h, int D, unsigned long lon
     for (int p = 0; p < Rt; ++p) {
         const int k0 = p * NB;
         const DrawRow& row = g.rows[(size_t)p];
-        auto update = [&] {
-            hipLaunchKernelGGL(k_panel_update, dim3(row.update, 1), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, dF, (size_t)0, ld, k0);
-        };
+        const auto update = plain_update(s, dF, ld, k0, row.update);
         const StagedRow sr{dF, 0, ld, w.Rhs.p, Rpad, w.Acc.p, w.Wt.p, (size_t)NB * NB, row.strip};
         if (int rc = staged_row(h, s, sr, 1, k0, row.update > 0 ? &update : nullptr, TILE_FLOPS * p * row.update)) return rc;
     }

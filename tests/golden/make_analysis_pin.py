@@ -1,14 +1,18 @@
 #!/usr/bin/env python3
 """The exact pin of the analysis paths behind the C ABI (gradient, orbit gradient, Fisher information, leave-one-out, continuum
-marginalisation and its gradients, the staged likelihood): for every call of ``CALLS`` the int64 bit pattern of every output
+marginalisation and its gradients, the staged likelihood, the predict family): for every call of ``CALLS`` the int64 bit pattern of every output
 array and, from ``ChunkHandle.timings()``, the per-class ``launches``, ``flops`` and ``bytes`` -- host-computed integers held in
-doubles.  ``ms`` and ``total_ms`` are measurements and are not recorded.  tests/test_gpu_analysis_pin.py replays ``CALLS``
+doubles.  ``ms`` and ``total_ms`` are measurements and are not recorded.  A predict call also records ``predict_timings()["flops"]`` (host-computed; no ``*_ms``
+field).  tests/test_gpu_analysis_pin.py replays ``CALLS``
 through ``run`` and compares with ``==``.
 
 Needs the device: every call runs twice, with profiling on, on a fresh handle, and an output whose bits (or a bookkeeping
 field whose value) differ between the two runs is refused, not recorded.
 
-    python tests/golden/make_analysis_pin.py [--out PATH] [--commit ID]
+    python tests/golden/make_analysis_pin.py [--out DIRECTORY] [--commit ID]
+
+The calls are spread over the files of ``PIN_FILES`` by the prefix of their names, so that no fixture outgrows what the
+repository takes for one file; ``load_pin`` reads them back as one.
 
 The fixture pins the library as it is when this runs: generate it BEFORE a change that has to keep the bits, never after.
 ``--commit`` is stored in the file as ``generated_at``.  The shapes are those of the reference modules of tests/: the
@@ -31,13 +35,16 @@ for _p in (ROOT, TESTS):
 import fisher_reference as fr  # noqa: E402
 import grad_reference as gr  # noqa: E402
 import marg_fisher_reference as mf  # noqa: E402
+import marg_predict_reference as mp  # noqa: E402
 import marg_reference as mr  # noqa: E402
 import orbit_grad_reference as ogr  # noqa: E402
 from psoap_amd import synthetic as syn  # noqa: E402
+from psoap_amd import _lib  # noqa: E402
 from psoap_amd._lib import K_NAMES, dptr  # noqa: E402
 from psoap_amd.utils import MODEL_ID  # noqa: E402
 
-PIN_PATH = os.path.join(HERE, "analysis_pin_v1.npz")
+# prefix of a call's name -> its file, the first that matches (the plain predict calls and the draws share one)
+PIN_FILES = (("predict_marg", "predict_marg_pin_v1.npz"), ("predict", "predict_pin_v1.npz"), ("", "analysis_pin_v1.npz"))
 BOOK_FIELDS = ("launches", "flops", "bytes")
 ORBIT_BASELINE = {"order": 1, "sd": list(mr.PLANT_SD), "weight": "one"}
 FAST_K = 4.0e6                  # km/s: thirteen times the speed of light (tests/test_gpu_marg_grad.py)
@@ -195,6 +202,106 @@ def _staged_lnlike():
         yield h, lambda: {"lnp": h.lnlike_batch(lw, gps, mr.MU_GP)}
 
 
+# ---- the predict family ------------------------------------------------------------------------------------------------------
+FORMS = {"full": True, "diag": "diag", "mean": False}       # want_sigma of ChunkHandle.predict / predict_marg
+PRED_OUT = {"full": ("mu", "Sigma"), "diag": ("mu", "var"), "mean": ("mu",)}
+STAGED_ENV = {"PSOAP_SHARE_PROCS": "9", "PSOAP_QUIET": "1"}       # nine processes: more than PSOAP_SHARE_DAG_MAX's 8
+
+
+@contextlib.contextmanager
+def _environ(**kw):
+    """the variables set for the duration of a call (the library reads them per call), the old values back afterwards"""
+    old = {k: os.environ.get(k) for k in kw}
+    os.environ.update(kw)
+    try:
+        yield
+    finally:
+        for k, v in old.items():
+            if v is None:
+                del os.environ[k]
+            else:
+                os.environ[k] = v
+
+
+def _pcase(name, mode):
+    """the case of marg_predict_reference.PCASES on chunk ``name`` in ``mode`` -> (case, chunk, (mode, lwls, pred, mus, gp))"""
+    pc, = [p for p in mp.PCASES if p[:2] == (name, mode)]
+    case = mr.case_named(name)
+    ch = mr.case_chunk(case)
+    return case, ch, (mode, ch.lwls, mp.pcase_pred(pc), mp.pcase_mus(pc), mr.case_gp(case))
+
+
+def _predicted(h, entry, args, form):
+    """one predict call in ``form`` -> its arrays and the host-computed flop count of ``predict_timings()``"""
+    got = entry(*args, want_sigma=FORMS[form])
+    out = _named(PRED_OUT[form], got if isinstance(got, tuple) else (got,))
+    out["predict_flops"] = h.predict_timings()["flops"]
+    return out
+
+
+@contextlib.contextmanager
+def _predict(name, mode, form, env=None, staged=False):
+    """plain ``predict`` of a case; ``env``: variables around the call; ``staged``: the call has to take the staged branch,
+    which the library's own count of such calls says -- the pin cannot silently record the persistent one"""
+    _, ch, args = _pcase(name, mode)
+    with _handle(ch) as h:
+        def call():
+            before = _lib.share_stats()["staged_policy"]
+            with _environ(**(env or {})):
+                out = _predicted(h, h.predict, args, form)
+            assert not staged or _lib.share_stats()["staged_policy"] > before, "the call did not take the staged branch"
+            return out
+        yield h, call
+
+
+@contextlib.contextmanager
+def _predict_transposed():
+    """predict_f_g_h_sum (mode 1, c = 3, M == N = 129): the transposed mean on a prediction grid of its own, always staged"""
+    ch = syn.make_chunk(3, 3, 43, seed=9901)
+    assert ch.N == 129
+    pred = np.stack([np.linspace(w.min(), w.max(), ch.N) for w in ch.lwls])
+    with _handle(ch) as h:
+        yield h, lambda: _predicted(h, h.predict, (1, ch.lwls, pred, [1.07], syn.GP_BASE[3]), "full")
+
+
+@contextlib.contextmanager
+def _predict_marg(name, mode, kind, form):
+    case, ch, args = _pcase(name, mode)
+    with _handle(ch, baseline=(case, kind)) as h:
+        yield h, lambda: _predicted(h, h.predict_marg, args, form)
+
+
+@contextlib.contextmanager
+def _predict_draw(name, kind, D, seed=None, z_seed=None):
+    """``D`` draws after ``predict`` (``kind`` None) or ``predict_marg`` of a case; ``z_seed``: the normals handed in"""
+    case, ch, args = _pcase(name, 0)
+    R = args[2].size                    # mode 0: c M rows
+    z = None if z_seed is None else np.random.default_rng(z_seed).standard_normal((D, R))
+    with _handle(ch, baseline=None if kind is None else (case, kind)) as h:
+        (h.predict if kind is None else h.predict_marg)(*args)
+        yield h, lambda: {"draws": h.predict_draw(D, seed=seed, z=z)}
+
+
+def _predict_calls():
+    calls = {}
+    for form in FORMS:
+        calls[f"predict-c-mode0-M65-{form}"] = lambda form=form: _predict("c", 0, form)       # two block rows, two prediction tile columns
+        calls[f"predict-a-mode1-M130-{form}"] = lambda form=form: _predict("a", 1, form)      # the 1e-8 nugget
+        calls[f"predict-b-mode2-M128-{form}"] = lambda form=form: _predict("b", 2, form)
+        calls[f"predict_marg-c-one-mode0-M65-{form}"] = lambda form=form: _predict_marg("c", 0, "one", form)
+        calls[f"predict_marg-f-flux-mode0-M100-{form}"] = lambda form=form: _predict_marg("f", 0, "flux", form)   # Q = 2
+        calls[f"predict_marg-a-one-mode1-M130-{form}"] = lambda form=form: _predict_marg("a", 1, "one", form)
+        calls[f"predict_marg-b-one-mode2-M128-{form}"] = lambda form=form: _predict_marg("b", 2, "one", form)
+    calls["predict-c-mode0-M65-full-unfused"] = lambda: _predict("c", 0, "full", env={"PSOAP_PREDICT_FUSED": "0"})
+    calls["predict-mode1-c3-N129-transposed-mean"] = _predict_transposed
+    calls["predict-c-mode0-M65-full-staged"] = lambda: _predict("c", 0, "full", env=STAGED_ENV, staged=True)
+    calls["predict-b-mode2-M128-full-staged"] = lambda: _predict("b", 2, "full", env=STAGED_ENV, staged=True)
+    calls["predict_draw-c-plain-seed-D3"] = lambda: _predict_draw("c", None, 3, seed=20261)        # R = 130: two tile rows
+    calls["predict_draw-c-plain-z-D2"] = lambda: _predict_draw("c", None, 2, z_seed=20262)
+    calls["predict_draw-f-flux-seed-D3"] = lambda: _predict_draw("f", "flux", 3, seed=20263)
+    return calls
+
+
 CALLS = {
     "lnlike_grad-c-B1": lambda: _lnlike_grad(1),
     "lnlike_grad-c-B10-negative": lambda: _lnlike_grad(10),               # two groups, 8 + 2
@@ -216,6 +323,7 @@ CALLS = {
     "loo_marg-f-one-pixels-only": lambda: _loo("f", False, "one"),
     "fisher_marg-c-one-negative": lambda: _fisher_marg("c", "one", False, negative=True),      # the NaN convention
     "lnlike_marg_grad-c-one-B3-negative": _lnlike_marg_grad_parts,          # one group, a refusal: parts, the poisoned gradient
+    **_predict_calls(),
 }
 
 
@@ -243,8 +351,30 @@ def run(name, repeats=1):
     return out
 
 
+def pin_file(name):
+    return next(f for prefix, f in PIN_FILES if name.startswith(prefix))
+
+
+def load_pin(directory=HERE):
+    """every fixture file as one dict: "<call>/<output>" -> array, and "generated_at", which all of them share"""
+    pin = {}
+    for _, fname in PIN_FILES:
+        with np.load(os.path.join(directory, fname)) as f:
+            assert pin.get("generated_at", f["generated_at"]) == f["generated_at"], "the fixture files are of different commits"
+            pin.update({k: f[k] for k in f.files})
+    return pin
+
+
+def write_pin(pin, directory):
+    for _, fname in PIN_FILES:
+        path = os.path.join(directory, fname)
+        np.savez_compressed(path, generated_at=pin["generated_at"],
+                            **{k: v for k, v in pin.items() if "/" in k and pin_file(k.rsplit("/", 1)[0]) == fname})
+        print("wrote", path, os.path.getsize(path))
+
+
 def main(argv):
-    path = argv[argv.index("--out") + 1] if "--out" in argv else PIN_PATH
+    directory = argv[argv.index("--out") + 1] if "--out" in argv else HERE
     commit = argv[argv.index("--commit") + 1] if "--commit" in argv else "unknown"
     pin, refused = {"generated_at": np.array(commit)}, []
     for name in CALLS:
@@ -260,8 +390,7 @@ def main(argv):
               f"{dict(zip(K_NAMES, (int(v) for v in book1[0])))}")
     if refused:
         raise SystemExit("two runs on one handle differ, nothing written: " + ", ".join(refused))
-    np.savez_compressed(path, **pin)
-    print("wrote", path, os.path.getsize(path))
+    write_pin(pin, directory)
 
 
 if __name__ == "__main__":

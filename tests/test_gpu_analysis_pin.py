@@ -1,5 +1,5 @@
-"""The analysis paths behind the C ABI against their exact pin (tests/golden/analysis_pin_v1.npz, written by
-tests/golden/make_analysis_pin.py on an MI355X): every output bit for bit, and the per-class ``launches``, ``flops`` and
+"""The analysis paths behind the C ABI against their exact pin (tests/golden/analysis_pin_v1.npz, predict_pin_v1.npz and
+predict_marg_pin_v1.npz, written by tests/golden/make_analysis_pin.py on an MI355X): every output bit for bit, and the per-class ``launches``, ``flops`` and
 ``bytes`` of ``ChunkHandle.timings()`` -- host-computed integers held in doubles -- with ``==``.  ``ms`` and ``total_ms`` are
 measurements and are not compared.
 
@@ -25,8 +25,7 @@ pytestmark = pytest.mark.gpu
 
 @functools.lru_cache(maxsize=None)
 def _fixture():
-    with np.load(pin.PIN_PATH) as f:
-        return {k: f[k] for k in f.files}
+    return pin.load_pin()
 
 
 def test_the_fixture_holds_exactly_the_calls():

@@ -350,7 +350,7 @@ def test_predict_sum_transposed_mean_and_predict_f(oracle, cov):
     np.testing.assert_allclose(Sig, Sig_o, rtol=0, atol=1e-9)
     with pytest.raises(AssertionError, match="Input wavelengths must be the same length."):
         cov.predict_f_g(ch.lwls[0], ch.lwls[1][:-1], ch.fl, ch.sigma, pg, pg, 0.0, 0.2, 5.0, 0.0, 0.1, 7.0)
-    # away from mu = 1 the two offsets differ (predict_kernels.hpp: 1.0 for the joint conditional and the sum of two, the
+    # away from mu = 1 the two offsets differ (predict_plan.hpp: 1.0 for the joint conditional and the sum of two, the
     # prior mean for predict_f and the sum of three): predict_f against oracle.predict_f, and both against the values the
     # reference itself returned (golden_predict_f_v1.npz)
     for mu_gp in (0.9, 1.15):
