@@ -160,10 +160,6 @@ SIGNATURES = {
                                           ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_longlong),
                                           ctypes.POINTER(ctypes.c_uint32)]),
     "psoap_dag_pick_workers": (ctypes.c_int, [ctypes.c_int, _ip, ctypes.c_int, ctypes.c_int, ctypes.c_int, _ip]),
-    "psoap_dag_plan_pool": (ctypes.c_int, [ctypes.c_int, _ip, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp,
-                                           ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_uint32),
-                                           ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32),
-                                           ctypes.POINTER(ctypes.c_uint32), _ip, ctypes.POINTER(ctypes.c_longlong)]),
 }
 
 # include/psoap_bench.h (libpsoap_bench.so): measurement kernels, loaded by bench.py / tools / one GPU test only

@@ -52,8 +52,8 @@ __device__ __forceinline__ void acc_store(MatAcc* acc, int q, double logdet_half
 // on the understanding that a read-modify-write executes at the memory side -- and hipcc turned every one of them into a
 // load: LLVM folds an atomic read-modify-write whose operand is the operation's identity (add 0, or 0) and whose ordering
 // is relaxed into an ATOMIC LOAD (`flat_load_dword ... sc1`, 2868 of them in the round-5 binary), which the XCD's L2 may
-// serve.  With -DPSOAP_RMW_POLL the zero passes through an opaque statement, the fold cannot happen and the poll is the
-// returning atomic add the design asked for (round 6: the A/B that decides which of the two the streams need).
+// serve.  In rmw_read the zero passes through an opaque statement, the fold cannot happen and the read is the returning
+// atomic add (round 6's A/B: the polls do not need it -- `sc1` loads are coherent -- and are 1.2 % slower with it).
 template <class T>
 __device__ __forceinline__ T rmw_read(T* p)      // always the returning atomic add (executed at the memory side, past every L2)
 {
@@ -64,11 +64,7 @@ __device__ __forceinline__ T rmw_read(T* p)      // always the returning atomic 
 template <class T>
 __device__ __forceinline__ T poll_word(T* p)
 {
-#ifdef PSOAP_RMW_POLL
-    return rmw_read(p);
-#else
     return __hip_atomic_fetch_add(p, (T)0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
 }
 
 // row-major upper-triangle tile index t in [0, P(P+1)/2)  ->  (ti, tj), tj >= ti

@@ -84,7 +84,7 @@ struct alignas(64) DagCtl {
     } queue[DAG_QUEUES];
 };
 
-// (DagQueues, DagPool, DagTask and the other records the host planner writes: dag_task.hpp)
+// (DagQueues, DagTask and the other records the host planner writes: dag_task.hpp)
 
 constexpr long long DAG_MAX_SPINS = 2000000;  // x (s_sleep + atomic round trip) ~ seconds
 
@@ -94,26 +94,22 @@ constexpr long long DAG_MAX_SPINS = 2000000;  // x (s_sleep + atomic round trip)
 // LOAD could be served stale from the polling XCD's L2 "indefinitely"; hipcc compiled every such add to exactly that load
 // (`flat_load_dword ... sc1`) all along, and the litmus tests of round 6 (tools/litmus.py, profiles/r6_litmus.txt) show sc1 loads
 // coherent between XCDs -- line planted in the reader's L2 or not, idle or under L2 pressure, 0 stale in 20,000 rounds per
-// combination.  -DPSOAP_RMW_POLL makes the polls the returning atomics they were meant to be (1 % slower; not needed).
+// combination.  (Polls as the returning atomics they were meant to be: 1 % slower and not needed)
 __device__ __forceinline__ int dag_peek(int* flag) { return poll_word(flag); }
 
 // A tile element other workgroups will read (the two store routines every tile goes through: dag_store_updated, dag_trsm)
 // is WRITTEN THROUGH (sc0 sc1) instead of left dirty in the writing XCD's L2 for the release fence to write back: what the
 // consumer reads is in memory when the storing wave's vmcnt reaches zero, wherever the workgroup is when its release
-// fence runs (round 5; measured performance-neutral in round 4: 848.1 against 847.3 evals/s).  -DPSOAP_NO_WT_STORES: plain.
+// fence runs (round 5; measured performance-neutral in round 4: 848.1 against 847.3 evals/s).
 // WT = false: a plain store -- the tiles of a matrix that ONE workgroup factors by itself (solo_kernel.hpp: nobody else reads
 // them inside the launch, and what stays in the L2 is what that workgroup reads next).
 template <bool WT = true>
 __device__ __forceinline__ void dag_st(double* p, double v)
 {
-#ifdef PSOAP_NO_WT_STORES
-    *p = v;
-#else
     if constexpr (WT)
         __hip_atomic_store((__attribute__((address_space(1))) double*)(uintptr_t)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     else
         *p = v;
-#endif
 }
 
 // Where this workgroup runs: XCC_ID[3:0] and HW_ID[15:8] (compute unit, shader array, shader engine).  A workgroup normally
@@ -135,10 +131,6 @@ __device__ __forceinline__ unsigned int dag_where()
 // (lane_taint: the word of the task's lane in a stream, nullptr otherwise)
 __device__ __forceinline__ void dag_moved_check(unsigned int w0, DagCtl* ctl, unsigned int* lane_taint)
 {
-#ifdef PSOAP_NO_MOVE_CHECK            // (A/B builds only: what the check costs)
-    (void)w0; (void)ctl; (void)lane_taint;
-    return;
-#endif
     const unsigned int w1 = dag_where();
     if (w1 != w0) {
         __hip_atomic_fetch_add(&ctl->pad[3], 1u, PSOAP_RLX_AGENT);
@@ -200,8 +192,8 @@ __device__ __forceinline__ void dag_wait_ge2(int* fa, int* fb, int target, DagCt
 // publications.  A protocol whose every dependency is an explicit hand-off returns the same bits whatever a task's timing;
 // one that leans on "that task is always through by then" does not: round 6 found two such places in the following scheme
 // (the accumulator chain, the in-order progress words) through the rare wrong values they produced, and this is the
-// instrument that shows there is no third (tools/soak_stream.py under the chaos build; -DPSOAP_NO_INORDER brings the
-// second one back, to show that the instrument sees it).
+// instrument that shows there is no third (tools/soak_stream.py under the chaos build; with dag_spin_ge compiled out it
+// showed the second one again: the instrument sees it).
 __device__ __forceinline__ void dag_chaos(unsigned int key, unsigned int place)
 {
 #ifdef PSOAP_CHAOS
@@ -225,10 +217,6 @@ __device__ __forceinline__ void dag_chaos(unsigned int key, unsigned int place)
 // that hole, this closes the rest).  The predecessor holds a smaller ticket: it runs or is through.
 __device__ __forceinline__ void dag_spin_ge(int* flag, int target, DagCtl* ctl, unsigned int code)
 {
-#ifdef PSOAP_NO_INORDER            // (A/B of the chaos build only: rounds 3-5's publication, ordered by time alone)
-    (void)flag; (void)target; (void)ctl; (void)code;
-    return;
-#endif
     long long spins = 0;
     while (dag_peek(flag) < target) {
         __builtin_amdgcn_s_sleep(8);
@@ -411,13 +399,8 @@ struct DagMat {
 
 // INPLACE: the result replaces the accumulators instead of going to memory (the strip solve that follows works on the
 // tile in registers: dag_pss)
-#ifdef PSOAP_FAST_STREAM
-#define DAG_FAST_STORE(stream) true
-#else
-#define DAG_FAST_STORE(stream) (!(stream))
-#endif
 // FAST: a task that adds no covariance (every PART but a chain's first, and the final of a chain) stores its tile through a
-// loop of its own (see there).
+// loop of its own (see there; a wash in the stream kernels, which do without it).
 template <int C, bool AUG, bool INPLACE = false, bool ROWMAP = false, bool FAST = false, bool WT = true>
 __device__ __forceinline__ void dag_store_updated(Tile& t, double* __restrict__ dest, size_t ldd, int k0, int j0,
                                                   const double* __restrict__ lw, const GpDev& g, double dsum,
@@ -582,9 +565,6 @@ __device__ __forceinline__ void dag_store_updated(Tile& t, double* __restrict__ 
     // the diagonal of the matrix: sigma_i^2 + sum of amp^2 (the prior variance for a row of the Schur complement), 1 in
     // the identity padding -- the 16 loads first, then the stores
     if (k0 == j0 && wr == wc) {
-#ifdef PSOAP_DIAG_PASS_WAIT
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // the loop's stores are in memory before the pass stores
-#endif
         double dg[4][4];
 #pragma unroll
         for (int m = 0; m < 4; ++m)
@@ -661,7 +641,6 @@ __device__ __forceinline__ void dag_sub_partials(Tile& t, const double* __restri
     const int wr = wave >> 1, wc = wave & 1;
     for (int sidx = 0; sidx < n_prev; ++sidx) {
         const double* __restrict__ ps = prev + (size_t)sidx * NB * NB;
-#ifndef PSOAP_NO_BATCH_FOLD
         if constexpr (BATCH && !ROWMAP) {
 #pragma unroll
             for (int m = 0; m < 4; ++m) {
@@ -674,7 +653,6 @@ __device__ __forceinline__ void dag_sub_partials(Tile& t, const double* __restri
             }
             continue;
         }
-#endif
 #pragma unroll
         for (int m = 0; m < 4; ++m)
 #pragma unroll
@@ -1646,169 +1624,6 @@ __device__ __forceinline__ void stream_dispatch(const StreamArgs& st, const DagM
     }
 }
 
-// Ready-only hand-out (DagPool): wave 0 finds this workgroup's next task -- the head final of a queue when it may be handed
-// out, else the first READY part in a window of that queue's pool, its own queue first, then the others from `steal0` on.
-// *s_ticket: the task's index in tasks[], or 0xffffffff when every queue is through (or the launch has failed).
-// Everything read here changes under the reader: the flag words are read with atomics (executed at the memory side, like
-// every poll of this kernel), claims are atomic compare-exchange / or.  Per scan of a queue: the ticket word, the pool's
-// first-untaken cursor, two words of the taken bitmap (a window of 64 parts), rows_done once per matrix in the window and
-// one wave instruction of arrival-counter reads.
-constexpr unsigned int DAG_NO_TASK = 0xffffffffu;
-#ifndef PSOAP_POOL_WINDOWS
-#define PSOAP_POOL_WINDOWS 4
-#endif
-constexpr unsigned int DAG_POOL_WINDOWS = PSOAP_POOL_WINDOWS;
-__device__ __forceinline__ void pool_take(const DagTask* __restrict__ tasks, const DagQueues& queues, const DagPool& pool,
-                                          DagCtl* ctl, MatFlags* flags, int home, int steal0,
-                                          unsigned int* s_ticket, unsigned int* s_pending)
-{
-    // *s_pending (in / out, LDS): the position in order[] of a final this workgroup has drawn a ticket for but may not
-    // run yet -- its chain's last part has not been taken.  Finals are drawn with ONE fetch-add each, like the tickets of
-    // the in-order list (a compare-exchange per final serialised the workgroups: one winner per round trip, 30-60 us per
-    // block row); whoever overshoots the finals that may be handed out keeps its ticket and takes ready parts meanwhile.
-    if (threadIdx.x < 64) {
-        const int l = hw_lane();
-        unsigned int got = DAG_NO_TASK;
-        unsigned int pending = (unsigned int)__builtin_amdgcn_readfirstlane((int)*s_pending);
-        long long spins = 0;
-        auto taken_bit = [&](unsigned int d) -> unsigned int {
-            unsigned int w = 0u;
-            if (l == 0) w = poll_word(&pool.taken[d >> 5]);
-            return ((unsigned int)__builtin_amdgcn_readfirstlane((int)w) >> (d & 31u)) & 1u;
-        };
-        for (;;) {
-            bool left = pending != DAG_NO_TASK;     // something is still to be handed out somewhere
-            if (pending != DAG_NO_TASK) {
-                const unsigned int d = pool.dep[pending];
-                if (d == DAG_POOL_NONE || taken_bit(d)) {
-                    got = pool.order[pending];
-                    pending = DAG_NO_TASK;
-                    break;
-                }
-            }
-            for (int probe = 0; probe <= DAG_QUEUES && got == DAG_NO_TASK; ++probe) {
-                const int g = probe == 0 ? home : (steal0 + probe - 1) % DAG_QUEUES;
-                if (probe > 0 && g == home) continue;
-                const unsigned int lo = queues.first[g], n_all = queues.first[g + 1] - lo, n_main = pool.n_main[g];
-                if (n_all == 0u) continue;
-                // 1. the head final: handed out in list order, and only once the last part of its chain has been taken
-                unsigned int m = 0u;
-                if (l == 0) m = poll_word(&ctl->queue[g].next);
-                m = (unsigned int)__builtin_amdgcn_readfirstlane((int)m);
-                if (m < n_main) {
-                    left = true;
-                    const unsigned int d = pool.dep[lo + m];
-                    if (pending == DAG_NO_TASK && (d == DAG_POOL_NONE || taken_bit(d))) {
-                        unsigned int tk = 0u;
-                        if (l == 0) tk = __hip_atomic_fetch_add(&ctl->queue[g].next, 1u, PSOAP_RLX_AGENT);
-                        tk = (unsigned int)__builtin_amdgcn_readfirstlane((int)tk);
-                        if (tk < n_main) {
-                            const unsigned int d2 = pool.dep[lo + tk];
-                            if (d2 == DAG_POOL_NONE || taken_bit(d2)) {
-                                got = pool.order[lo + tk];
-                                break;
-                            }
-                            pending = lo + tk;      // drawn ahead of what may run: held, parts meanwhile
-                        }
-                    }
-                }
-                // 2. the pool: the 64 parts of the two bitmap words around the first untaken one
-                const unsigned int p0 = lo + n_main, p1 = lo + n_all;       // the pool's positions in order[]
-                if (p0 == p1) continue;
-                unsigned int cur = 0u;
-                if (l == 0) cur = poll_word(&ctl->queue[g].fill[0]);
-                cur = p0 + (unsigned int)__builtin_amdgcn_readfirstlane((int)cur);
-                if (cur >= p1) continue;
-                left = true;
-                // (a second window when the first holds nothing ready: the parts at the cursor may all wait for a predecessor
-                // that is running, while the next rows' are ready)
-#pragma unroll 1
-                for (unsigned int win = 0u; win < DAG_POOL_WINDOWS && got == DAG_NO_TASK; ++win) {
-                const unsigned int base = (cur & ~31u) + 64u * win;
-                if (base >= p1) break;
-                unsigned int word = 0xffffffffu;
-                if (l < 2 && base + 32u * (unsigned int)l < p1)
-                    word = poll_word(&pool.taken[(base >> 5) + (unsigned int)l]);
-                const unsigned int w0 = (unsigned int)__builtin_amdgcn_readlane((int)word, 0);
-                const unsigned int w1 = (unsigned int)__builtin_amdgcn_readlane((int)word, 1);
-                const unsigned int pos = base + (unsigned int)l;
-                const bool mine = pos >= cur && pos < p1 && !(((l < 32 ? w0 : w1) >> (l & 31)) & 1u);     // untaken, in range
-                // the cursor moves up to the first untaken part (monotone; a stale view only makes it lag)
-                if (win == 0u) {
-                    const unsigned long long un = __ballot(mine);
-                    const unsigned int first_un = un ? base + (unsigned int)__builtin_ctzll(un) : (base + 64u < p1 ? base + 64u : p1);
-                    if (l == 0 && first_un > cur) __hip_atomic_fetch_max(&ctl->queue[g].fill[0], first_un - p0, PSOAP_RLX_AGENT);
-                }
-                // ready: the block rows its panels read are complete and its predecessor's running sum is there
-                DagTask t{};
-                if (mine) t = tasks[pool.order[pos]];
-                bool ready = false;
-                {
-                    unsigned long long todo = __ballot(mine);
-                    while (todo) {                  // rows_done once per matrix of the window
-                        const int src = __builtin_ctzll(todo);
-                        const int b0 = __builtin_amdgcn_readlane((int)t.b, src);
-                        int rd = 0;
-                        if (l == 0) rd = dag_peek(&flags[b0].rows_done);
-                        rd = __builtin_amdgcn_readfirstlane(rd);
-                        const bool same = mine && (int)t.b == b0;
-                        if (same) ready = rd >= (int)t.pb;
-                        todo &= ~__ballot(same);
-                    }
-                }
-                if (ready && (t.type & DAG_CHAIN) && t.S > 0) {
-                    // the predecessor has been taken (it runs, or is through): the part may start, it waits for the
-                    // predecessor's tile only when its own update is done
-                    const unsigned int pp = pool.dep[pos];
-                    ready = (poll_word(&pool.taken[pp >> 5]) >> (pp & 31u)) & 1u;
-                }
-                unsigned long long rdy = __ballot(ready);
-                while (rdy) {
-                    // (the workgroups scan the same window at the same time: each starts at another ready part)
-                    const int n_rdy = __builtin_popcountll(rdy);
-                    int skip = (int)(blockIdx.x % (unsigned int)n_rdy);
-                    unsigned long long r2 = rdy;
-                    while (skip-- > 0) r2 &= r2 - 1ull;
-                    const int pick = __builtin_ctzll(r2);
-                    unsigned int old = 0xffffffffu;
-                    if (l == pick) old = __hip_atomic_fetch_or(&pool.taken[pos >> 5], 1u << (pos & 31u), PSOAP_RLX_AGENT);
-                    old = (unsigned int)__builtin_amdgcn_readlane((int)old, pick);
-                    const unsigned int ppos = base + (unsigned int)pick;
-                    if (!((old >> (ppos & 31u)) & 1u)) {
-                        got = pool.order[ppos];
-                        break;
-                    }
-                    rdy &= ~(1ull << pick);
-                }
-                }
-            }
-            if (got != DAG_NO_TASK || !left) break;
-            unsigned int err = 0u;
-            if (l == 0) err = poll_word(&ctl->error);
-            if (__builtin_amdgcn_readfirstlane((int)err) != 0) break;
-            __builtin_amdgcn_s_sleep(64);
-            if (++spins > DAG_MAX_SPINS) {          // (nothing became ready for seconds: a failed launch, reported)
-                if (l == 0 && __hip_atomic_fetch_or(&ctl->error, 1u, PSOAP_RLX_AGENT) == 0u)
-                    __hip_atomic_store(&ctl->pad[0], 10u, PSOAP_RLX_AGENT);
-                break;
-            }
-        }
-        if (l == 0) {
-            *s_ticket = got;
-            *s_pending = pending;
-        }
-    }
-    __syncthreads();
-}
-
-// Waves per SIMD of the throughput-scheme kernels (k_chol_dag<C, false, false, *>).  -DPSOAP_WPE3 (round 5, experiment): three
-// workgroups per compute unit, 168 registers per lane -- see DESIGN.md / LABNOTES.md for what it measured.
-#ifdef PSOAP_WPE3
-constexpr int DAG_WPE_TP = 3;
-#else
-constexpr int DAG_WPE_TP = 2;
-#endif
-
 // LAT: the instantiation launched for task lists of the latency scheme; only it contains the fused diagonal
 // fast path (dag_diag_fast).  With that path compiled into the one kernel, hipcc keeps a spilled value in the
 // MFMA loops of every task (a scratch load per 64-MFMA stage: 32-walker batch 39.5 -> 43.7 ms); the
@@ -1824,12 +1639,11 @@ __global__ __launch_bounds__(GEMM_THREADS, WPE) void k_chol_dag(const DagMat* __
                                                              const DagTask* __restrict__ tasks, DagQueues queues,
                                                              MatFlags* flags, int* arrive, double* wspace,
                                                              DagCtl* ctl, unsigned long long* tlog, DagAug aug,
-                                                             StreamArgs st, DagPool pool)
+                                                             StreamArgs st)
 {
     __shared__ double vec1[NB];   // z_k (OFF)
     __shared__ double vec2[NB];   // column sums (OFF)
     __shared__ unsigned int s_ticket;
-    __shared__ unsigned int s_pending;      // ready-only hand-out: a final drawn ahead of its turn (pool_take)
     __shared__ int s_lane;
     if constexpr (STREAM) {
         if (blockIdx.x == 0) {
@@ -1871,17 +1685,7 @@ __global__ __launch_bounds__(GEMM_THREADS, WPE) void k_chol_dag(const DagMat* __
     // skips it).  The tile above the diagonal is all DIAG(q+1) waits for, so it starts the moment it can, never holds a
     // workgroup waiting (257 us per diagonal task before, 1.9 % of all worker time of a streamed run) and potrf(q+1) is
     // out long before the strip solves of row q+1 ask for it.
-    constexpr bool CONT = !LAT && DAG_TILE_DEPS;
-    // ready-only hand-out of the PART tasks (DagPool): an experiment of round 5, compiled in with -DPSOAP_POOL only -- it is
-    // SLOWER than the list order (see the comment at DagPool)
-#ifdef PSOAP_POOL
-    constexpr bool POOL = LAT && !STREAM;
-#else
-    constexpr bool POOL = false;
-#endif
-    (void)pool;
-    if (threadIdx.x == 0) s_pending = DAG_NO_TASK;
-    __syncthreads();
+    constexpr bool CONT = !LAT;
     bool cont = false;
     unsigned int ticket = 0;
     int b = 0;
@@ -1901,12 +1705,6 @@ __global__ __launch_bounds__(GEMM_THREADS, WPE) void k_chol_dag(const DagMat* __
             // scalar cache (uniform loads -- the hyper-parameters -- go through it; the vector caches were invalidated by
             // the acquire in stream_take)
             asm volatile("s_dcache_inv\n\ts_waitcnt lgkmcnt(0)" ::: "memory");
-        } else if constexpr (POOL) {
-            // the latency schemes' plain launches: finals in list order, parts ready-only (pool_take)
-            pool_take(tasks, queues, pool, ctl, flags, home, steal0, &s_ticket, &s_pending);
-            ticket = (unsigned int)__builtin_amdgcn_readfirstlane((int)s_ticket);
-            __syncthreads();  // s_ticket is rewritten by the next pool_take
-            if (ticket == DAG_NO_TASK) return;
         } else {
             if (dry == (1u << DAG_QUEUES) - 1u) return;
             const int g = (probe == 0) ? home : (steal0 + probe - 1) % DAG_QUEUES;
@@ -2059,7 +1857,7 @@ __global__ __launch_bounds__(GEMM_THREADS, WPE) void k_chol_dag(const DagMat* __
         // (scheme 0: tile-level dependencies; never in the LAT kernels, whose task lists carry their own protocols)
         // (said to be wave-uniform: the extents of the K-loop stay scalars)
         const int ka16 = __builtin_amdgcn_readfirstlane(ka_v);
-        dag_update<true, SmemKernel, false, !LAT && DAG_TILE_DEPS>(
+        dag_update<true, SmemKernel, false, !LAT>(
             t, Km, ld, k0, j0, task.pa, task.pb, f, ctl, ttype == DAG_DIAG && (task.type & DAG_WAITNEXT) != 0,
             tlog_l ? tlog_l + ticket * 8 : nullptr, wave_s, SmemKernel(), &f->rvrow[q], &f->rvrow[j], ka16);
         if (tlog_l && threadIdx.x == 0) tlog_l[ticket * 8 + 5] = __builtin_amdgcn_s_memrealtime();
@@ -2088,7 +1886,7 @@ __global__ __launch_bounds__(GEMM_THREADS, WPE) void k_chol_dag(const DagMat* __
             // right after the block row above completes; its PARTs ran ahead)
             const bool carries_k = chain ? (is_part ? task.S == 0 : task.S <= 1) : !is_part;
             if (tlog_l && is_part && threadIdx.x == 0) tlog_l[ticket * 8 + 1] = __builtin_amdgcn_s_memrealtime();   // folded
-            dag_store_updated<C, AUG, false, false, DAG_FAST_STORE(STREAM)>(t, dest, ldd, k0, j0, mat.lw, g, dsum, mat.sigma, N, carries_k ? 1.0 : 0.0, Npad, aug,
+            dag_store_updated<C, AUG, false, false, !STREAM>(t, dest, ldd, k0, j0, mat.lw, g, dsum, mat.sigma, N, carries_k ? 1.0 : 0.0, Npad, aug,
                                       mirror, !(AUG && ttype == DAG_SCHUR));
         }
         if (tlog_l && !is_part && threadIdx.x == 0) tlog_l[ticket * 8 + 4] = __builtin_amdgcn_s_memrealtime();     // a final's stores issued

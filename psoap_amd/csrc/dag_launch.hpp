@@ -13,18 +13,14 @@
 namespace psoap {
 
 // ---- one task list on the device ------------------------------------------------------------------
-// The plan's tasks (and, for the ready-only hand-out, order[] and dep[]), the split-K partial tiles, and the control region:
-// DagCtl, MatFlags[n_mats], the arrival counters, and behind them the `taken` bitmap (one bit per task) -- all of it zeroed
-// by one memset of ctl_bytes before every launch.  Grow-only; load() only while no launch reads it.
+// The plan's tasks, the split-K partial tiles, and the control region: DagCtl, MatFlags[n_mats] and the arrival counters --
+// all of it zeroed by one memset of ctl_bytes before every launch.  Grow-only; load() only while no launch reads it.
 struct DagWorkspace {
     Grow<DagTask> tasks;
-    Grow<unsigned int> order, dep;
     Grow<double> ws;
     Grow<unsigned char> ctl;
-    size_t arrive_off = 0, taken_off = 0, ctl_bytes = 0;
+    size_t arrive_off = 0, ctl_bytes = 0;
     DagQueues queues{};
-    unsigned int n_main[DAG_QUEUES] = {};
-    bool pool = false;
     int scheme = 0;
     unsigned int n_tasks = 0, n_slots = 0;
 
@@ -36,9 +32,7 @@ struct DagWorkspace {
         // (the throughput kernels read bits 24.. of a final's ctr as its block row's shortfall: dag_build_tasks)
         if (plan.n_ctrs > DAG_CTR_MASK) return hipErrorInvalidValue;
         arrive_off = sizeof(DagCtl) + sizeof(MatFlags) * n_mats;
-        taken_off = arrive_off + sizeof(int) * ((size_t)plan.n_ctrs + 4);
-        ctl_bytes = taken_off + sizeof(unsigned int) * ((nt + 31) / 32 + 1);
-        pool = !plan.order.empty();
+        ctl_bytes = arrive_off + sizeof(int) * ((size_t)plan.n_ctrs + 4);
         hipError_t e = hipSuccess;
         const size_t ws_count = (size_t)NB * NB * ((size_t)plan.n_slots + 1);
         if (resident && (ctl_bytes > ctl.cap || nt > tasks.cap || ws_count > ws.cap || !ctl.p || !tasks.p || !ws.p))
@@ -49,15 +43,6 @@ struct DagWorkspace {
         if (e == hipSuccess)
             e = resident ? hipMemcpyAsync(tasks, resident, sizeof(DagTask) * nt, hipMemcpyDeviceToDevice, s)
                          : hipMemcpy(tasks, plan.tasks.data(), sizeof(DagTask) * nt, hipMemcpyHostToDevice);
-        if (pool) {
-            if (e == hipSuccess) e = order.need(plan.order.size());
-            if (e == hipSuccess) e = dep.need(plan.dep.size());
-            if (e == hipSuccess)
-                e = hipMemcpy(order, plan.order.data(), sizeof(unsigned int) * plan.order.size(), hipMemcpyHostToDevice);
-            if (e == hipSuccess)
-                e = hipMemcpy(dep, plan.dep.data(), sizeof(unsigned int) * plan.dep.size(), hipMemcpyHostToDevice);
-            memcpy(n_main, plan.n_main, sizeof n_main);
-        }
         queues = plan.queues;
         scheme = plan.scheme;
         n_tasks = (unsigned int)nt;
@@ -67,17 +52,6 @@ struct DagWorkspace {
     DagCtl* dag_ctl() const { return reinterpret_cast<DagCtl*>(ctl.p); }
     MatFlags* flags() const { return reinterpret_cast<MatFlags*>(ctl.p + sizeof(DagCtl)); }
     int* arrive() const { return reinterpret_cast<int*>(ctl.p + arrive_off); }
-    DagPool dag_pool() const
-    {
-        DagPool p{};
-        if (pool) {
-            p.order = order;
-            p.dep = dep;
-            p.taken = reinterpret_cast<unsigned int*>(ctl.p + taken_off);
-            memcpy(p.n_main, n_main, sizeof p.n_main);
-        }
-        return p;
-    }
 };
 
 // Grid and form of a launch of a task list: at most one workgroup per task, `workers` of them, the LAT kernels at most two
@@ -102,16 +76,14 @@ inline DagShape dag_shape(const DagWorkspace& w, int workers, int n_cus)
 // Every k_chol_dag the library launches comes from this list: dag_launch dispatches over it and dag_set_lds gives each
 // member its LDS attribute, so no form is launched without one.  C in 1..3 x {throughput, LAT, LAT wide}, for the
 // likelihood (AUG = false) and predict (AUG = true); the stream (STREAM = true) has no wide form.
-// Waves per SIMD, the one rule: wide 1; LAT 2; throughput DAG_WPE_TP for the likelihood, 2 for predict and the stream (the
-// stream kernels are compiled for two workgroups per compute unit also in a -DPSOAP_WPE3 build: with three, hipcc's code
-// for them shows the exec-restore defect of psoap_amd/asmcheck.py and the build refuses it).
+// Waves per SIMD, the one rule: wide 1, every other form 2.
 enum DagForm { DAG_TP, DAG_LAT, DAG_WIDE };
 
 template <int C_, bool AUG, bool STREAM, int FORM>
 struct DagKernel {
     static constexpr int C = C_;
     static constexpr bool LAT = FORM != DAG_TP;
-    static constexpr int WPE = FORM == DAG_WIDE ? 1 : (LAT || AUG || STREAM) ? 2 : DAG_WPE_TP;
+    static constexpr int WPE = FORM == DAG_WIDE ? 1 : 2;
     // the member's place in the list (include/psoap_gp.h: psoap_dag_form_launches)
     static constexpr int INDEX = STREAM ? 18 + 2 * (C - 1) + (LAT ? 1 : 0) : 9 * (AUG ? 1 : 0) + 3 * (C - 1) + FORM;
     static const void* fn() { return reinterpret_cast<const void*>(k_chol_dag<C, AUG, LAT, STREAM, WPE>); }
@@ -162,12 +134,12 @@ inline std::atomic<long long>* dag_form_launches()
 template <bool AUG, bool STREAM>
 inline void dag_launch(int C, bool lat, bool wide, int grid, hipStream_t s, const DagMat* mats, const DagTask* tasks,
                        DagQueues queues, MatFlags* flags, int* arrive, double* wspace, DagCtl* ctl,
-                       unsigned long long* tlog, DagAug aug, StreamArgs st, DagPool pool)
+                       unsigned long long* tlog, DagAug aug, StreamArgs st)
 {
     dag_visit<AUG, STREAM>(C, wide ? DAG_WIDE : lat ? DAG_LAT : DAG_TP, [&](auto k) {
         using K = decltype(k);
         hipLaunchKernelGGL((k_chol_dag<K::C, AUG, K::LAT, STREAM, K::WPE>), dim3(grid), dim3(GEMM_THREADS), GEMM_LDS_BYTES,
-                           s, mats, tasks, queues, flags, arrive, wspace, ctl, tlog, aug, st, pool);
+                           s, mats, tasks, queues, flags, arrive, wspace, ctl, tlog, aug, st);
         dag_form_launches()[K::INDEX] += 1;
     });
 }

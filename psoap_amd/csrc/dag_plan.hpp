@@ -1,5 +1,5 @@
-// dag_plan.hpp -- the host scheduler of the persistent Cholesky kernel (k_chol_dag, dag_kernel.hpp): the task lists, their
-// hand-out orders, the scheme and worker rules, and the plan rule of a likelihood launch.  Plain C++17 over std::vector: no
+// dag_plan.hpp -- the host scheduler of the persistent Cholesky kernel (k_chol_dag, dag_kernel.hpp): the task lists,
+// the scheme and worker rules, and the plan rule of a likelihood launch.  Plain C++17 over std::vector: no
 // HIP type, so it is compiled, run and sanitized by a host compiler alone (tests/host/plan_host_check.cpp).
 #pragma once
 #include <stdlib.h>
@@ -23,9 +23,6 @@ namespace psoap {
 // ---------------------------------------------------------------------------------------------
 struct DagPlan {
     std::vector<DagTask> tasks;
-    // ready-only hand-out (DagPool): filled for the latency schemes by dag_build_tasks
-    std::vector<unsigned int> order, dep;
-    unsigned int n_main[DAG_QUEUES] = {};
     DagQueues queues{};
     unsigned int n_slots = 0;
     unsigned int n_ctrs = 0;
@@ -228,7 +225,7 @@ inline void dag_build_queue(DagPlan& plan, const std::vector<int>& mats, const s
     // scheme 0 (round 4): the final of DIAG(q+1) sits right BEHIND the final of tile (q, q+1) and is run by the workgroup
     // that ran that one (DAG_FUSED on the OFF final: "continue with the next record"; DAG_NOSOLVE on the DIAG final:
     // "owned", skipped by whoever draws its ticket) -- see k_chol_dag
-    const bool cont0 = (scheme == 0) && DAG_TILE_DEPS;
+    const bool cont0 = (scheme == 0);
     std::vector<DagTask> owned_final(Ps.size());          // per matrix: the DIAG(q+1) final to emit behind tile (q, q+1)
     std::vector<char> has_owned(Ps.size(), 0);
     auto fj = [first](int j) { return first ? first[j] : 0; };
@@ -407,36 +404,6 @@ inline void dag_build_queue(DagPlan& plan, const std::vector<int>& mats, const s
         for (int b : mats) dag_emit_schur(plan, b, Ps[b], Ms);
 }
 
-
-// The two hand-out orders of a latency-scheme list (DagPool): per queue the finals in list order, then the PARTs in list
-// order; for a final with a chain the position of the chain's last part.
-inline void dag_build_pool(DagPlan& plan)
-{
-    const size_t n = plan.tasks.size();
-    plan.order.assign(n, 0u);
-    plan.dep.assign(n, DAG_POOL_NONE);
-    for (int g = 0; g < DAG_QUEUES; ++g) {
-        const unsigned int lo = plan.queues.first[g], hi = plan.queues.first[g + 1];
-        unsigned int pos = lo;
-        for (unsigned int t = lo; t < hi; ++t)
-            if ((plan.tasks[t].type & DAG_TYPE_MASK) != DAG_PART) plan.order[pos++] = t;
-        plan.n_main[g] = pos - lo;
-        std::vector<unsigned int> last_part(plan.n_ctrs + 1, DAG_POOL_NONE);      // per arrival counter: its last part's position
-        for (unsigned int t = lo; t < hi; ++t)
-            if ((plan.tasks[t].type & DAG_TYPE_MASK) == DAG_PART) {
-                // a chained part adds its predecessor's running sum at the END of its own update: it may start while the
-                // predecessor still runs -- but only once the predecessor has been TAKEN (dep[] of a pool entry)
-                if ((plan.tasks[t].type & DAG_CHAIN) && plan.tasks[t].S > 0) plan.dep[pos] = last_part[plan.tasks[t].ctr];
-                last_part[plan.tasks[t].ctr] = pos;        // (a chain's parts are in list order: the last one wins)
-                plan.order[pos++] = t;
-            }
-        for (unsigned int m = lo; m < lo + plan.n_main[g]; ++m) {
-            const DagTask& f = plan.tasks[plan.order[m]];
-            if (f.S > 1) plan.dep[m] = last_part[f.ctr];   // S - 1 parts
-        }
-    }
-}
-
 // scheme: 0 throughput, 1 latency (dag_emit), -1 automatic: latency while the row-to-row dependency chain,
 // not the MFMA work, bounds the run time -- i.e. while a queue has too few block rows in flight to hide the
 // wait for the row above.  Measured on MI355X (tools/scheme_table.py; N = 2000 .. 8192, B = 1 .. 32, round 2,
@@ -605,9 +572,6 @@ inline DagPlan dag_build_tasks(const std::vector<int>& Ps, int workers, int sche
             if ((t.type & DAG_TYPE_MASK) != DAG_PART)
                 t.ctr |= (unsigned int)(Ps[t.b] - t.q - dag_sky_row_tiles(first, Ps[t.b], t.q)) << 24;
     plan.queues.follow_first = (unsigned int)dag_follow_first_row();
-#ifdef PSOAP_POOL
-    if (scheme >= 1) dag_build_pool(plan);
-#endif
     return plan;
 }
 
@@ -665,7 +629,7 @@ inline DagPlan dag_build_lane_plan(int P, int lanes, int workers, int scheme, bo
     const int share15 = workers / STREAM_NOMINAL_LANES > 0 ? workers / STREAM_NOMINAL_LANES : 1;
     DagPlan plan = scheme == 0 ? dag_build_tasks(std::vector<int>(1, P), share15, 0, 0, 0, dag_nominal_share(workers))
                                : dag_build_tasks(std::vector<int>(1, P), share15, scheme);
-    const bool rows = plan.scheme == 0 && DAG_TILE_DEPS;
+    const bool rows = plan.scheme == 0;
     // (schemes 1, 2: the list is in order of readiness already and its tasks are short -- the lanes ticket by ticket in turn
     // measured 8 % faster at N = 2000, the same at N = 4096)
     if (plan.scheme != 0) bursts = false;

@@ -244,31 +244,6 @@ extern "C" int psoap_dag_plan_multi(int B, const int* Ps, int workers, void* out
     return 0;
 }
 
-// Pure host function: the task list of a batch (Ps[b] block rows each; Mt appended column tiles and an Ms x Ms Schur block
-// for a single matrix: predict) together with the two hand-out orders of the ready-only scheme (DagPool, dag_task.hpp):
-// order[] (per queue the finals' task indices, then the parts'), dep[] (per final: the position in order[] of the last
-// part of its chain, 0xffffffff without one), n_main[8].  Empty orders (*has_pool = 0) for the throughput scheme.
-extern "C" int psoap_dag_plan_pool(int B, const int* Ps, int workers, int Mt, int Ms, int scheme, void* tasks_out,
-                                   long long max_tasks, long long* n_tasks, unsigned int* order_out, unsigned int* dep_out,
-                                   unsigned int* n_main_out, unsigned int* queue_first, int* has_pool, long long* n_ctrs)
-{
-    if (B < 1 || !Ps || workers < 1 || !n_tasks || Mt < 0 || Ms < 0 || Ms > Mt || (Mt > 0 && B != 1))
-        FAIL("psoap_dag_plan_pool: bad arguments");
-    for (int b = 0; b < B; ++b)
-        if (Ps[b] < 1 || Ps[b] + Mt > 255) FAIL("psoap_dag_plan_pool: 1 <= P (+ Mt) <= 255");
-    DagPlan plan = dag_build_tasks(std::vector<int>(Ps, Ps + B), workers, scheme, Mt, Ms);
-    if (plan.scheme >= 1 && plan.order.empty()) dag_build_pool(plan);      // (the shipped build does not use the orders)
-    plan_export(plan, tasks_out, max_tasks, n_tasks, nullptr, n_ctrs, queue_first);
-    if (has_pool) *has_pool = plan.order.empty() ? 0 : 1;
-    if (n_main_out) memcpy(n_main_out, plan.n_main, sizeof plan.n_main);
-    if (!plan.order.empty()) {      // (each by its own size -- today both equal the task count)
-        const long long n_order = (long long)plan.order.size(), n_dep = (long long)plan.dep.size();
-        if (order_out) memcpy(order_out, plan.order.data(), sizeof(unsigned int) * (max_tasks < n_order ? max_tasks : n_order));
-        if (dep_out) memcpy(dep_out, plan.dep.data(), sizeof(unsigned int) * (max_tasks < n_dep ? max_tasks : n_dep));
-    }
-    return 0;
-}
-
 // Pure host function: how many persistent workgroups a batch of B matrices (Ps[b] block rows each, Mt appended
 // column tiles) gets on a device with `compute_units` CUs that admits `max_workers` of them (dag_pick_workers).
 extern "C" int psoap_dag_pick_workers(int B, const int* Ps, int Mt, int compute_units, int max_workers, int* workers)

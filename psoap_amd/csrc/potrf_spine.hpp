@@ -130,12 +130,8 @@ __device__ __forceinline__ void pub_block(const SpinePub& pub, int b, int J, int
 // The count is exact by construction: every operation between the vouched-for stores and the wait is a relaxed ATOMIC
 // store (pub_block; pb::emit_w<.., COUNTED>), four per block, which the compiler can neither merge nor drop -- a wait
 // for `younger` outstanding operations would otherwise let vouched-for stores stay in flight if fewer had been emitted.
-// -DPSOAP_PUB_WAIT_ALL: wait for everything (the knob to rule the counting out when a result is in doubt).
 __device__ __forceinline__ void pub_flag(const SpinePub& pub, int wave, int n_steps, int lane, int younger = 0)
 {
-#ifdef PSOAP_PUB_WAIT_ALL
-    younger = 0;
-#endif
     switch (younger) {
         case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
         case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;

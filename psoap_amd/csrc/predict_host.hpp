@@ -325,7 +325,7 @@ static int predict_factor_dag(PredictWs& ws, const PredictShape& g, const Predic
     // (the workers are clamped to two per compute unit already: predict_ws_init)
     const DagShape sh = dag_shape(dag, workers, ws.n_cus);
     dag_launch<true, false>(c, sh.lat, sh.wide, sh.grid, st, ws.Mat, dag.tasks, dag.queues, dag.flags(), dag.arrive(),
-                            dag.ws, dag.dag_ctl(), tlog_, aug, StreamArgs{}, dag.dag_pool());
+                            dag.ws, dag.dag_ctl(), tlog_, aug, StreamArgs{});
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -350,7 +350,6 @@ static int dag_workers(int device, int* out, int* cus = nullptr)
                                                          GEMM_LDS_BYTES));
     if (blocks_per_cu < 1) blocks_per_cu = 1;
     if (blocks_per_cu > 2) blocks_per_cu = 2;
-    if (DAG_WPE_TP > 2) blocks_per_cu = DAG_WPE_TP;      // (-DPSOAP_WPE3: the throughput kernels are compiled for three)
     *out = blocks_per_cu * prop.multiProcessorCount;
     if (cus) *cus = prop.multiProcessorCount;
     return 0;
@@ -414,10 +413,9 @@ static int chunk_alloc(psoap_chunk* h, const double* fl, const double* sigma)
         HIP_TRY(sl.evEval.create());
     }
     // the control region of the persistent kernel, sized for max_batch here (out of memory surfaces at create, not in the
-    // first evaluation): DagCtl, the matrices' flags, the arrival counters, and behind them the `taken` bitmap of the
-    // ready-only hand-out -- one bit per task, at most 9 parts per tile + the early diagonal parts
+    // first evaluation): DagCtl, the matrices' flags and the arrival counters, at most one per tile
     const size_t tiles = nb * (size_t)h->P * (h->P + 1) / 2;
-    HIP_TRY(h->dag.ctl.need(sizeof(DagCtl) + sizeof(MatFlags) * nb + sizeof(int) * (tiles + 16 + (9 * tiles + 1024) / 32 + 8)));
+    HIP_TRY(h->dag.ctl.need(sizeof(DagCtl) + sizeof(MatFlags) * nb + sizeof(int) * (tiles + 16)));
     NEED(h->hDagErr, 16);
     h->hDagErr[0] = 0;
     if (int rc = dag_workers(h->device, &h->dag_grid, &h->n_cus)) return rc;
@@ -1059,7 +1057,7 @@ static void launch_lnlike(const psoap_chunk* h, const DagWorkspace& w, int worke
     const DagShape sh = dag_shape(w, workers, h->n_cus);
     // (DagAug: read by the AUG kernels only)
     dag_launch<false, false>(C, sh.lat, sh.wide, sh.grid, s, mats, w.tasks, w.queues, w.flags(), w.arrive(), w.ws, w.dag_ctl(),
-                             tlog, DagAug{}, StreamArgs{}, w.dag_pool());
+                             tlog, DagAug{}, StreamArgs{});
 }
 
 // The tail of a persistent launch for one handle, queued on s (the handle's stream, or its group's) behind the launch:
@@ -1095,7 +1093,7 @@ static int eval_dag(psoap_chunk* h)
         hipLaunchKernelGGL(k_init_rhs, dim3((h->Npad + 255) / 256, B), dim3(256), 0, s, h->dR, h->Npad, N,
                            h->plan_first.empty() ? h->dFl.p : sl.dFlS.p, sl.mu, h->dAcc);
         HIP_TRY(hipGetLastError());
-        // (flags, arrival counters and -- behind them -- the taken bitmap of the ready-only hand-out: one memset)
+        // (flags and arrival counters: one memset)
         HIP_TRY(hipMemsetAsync(h->dag.ctl, 0, h->dag.ctl_bytes, s));
         // PSOAP_DEBUG_POISON (tools/soak_batch_perm.py; bit 0: the matrices, bit 1: the mailboxes, bit 2: the partial-tile
         // workspace, bit 3: the block records of the accumulators): NaN patterns in whatever the launch must write before it
@@ -1448,14 +1446,14 @@ static int stream_launch(psoap_chunk* h)
         // ticks (10 ns) between two block rows of one lane; PSOAP_STREAM_GATE_US overrides (0: lanes strictly in turn)
         const char* e = getenv("PSOAP_STREAM_GATE_US");
         const double us = e ? atof(e) : 250.0;
-        a.gate = (st.scheme == 0 && DAG_TILE_DEPS && us > 0.0) ? (unsigned int)(us * 100.0) : 0u;
+        a.gate = (st.scheme == 0 && us > 0.0) ? (unsigned int)(us * 100.0) : 0u;
     }
     a.tlog_cap = st.tlog_cap;
     // (every workgroup the device admits, at most two per compute unit: no task bound, never wide)
     dag_launch<false, true>(st.C, st.scheme >= 1, false, dag_two_per_cu(h->dag_grid, h->n_cus), s, st.dMats, st.dTasks,
                             st.queues, reinterpret_cast<MatFlags*>(st.dDag + sizeof(DagCtl)),
                             reinterpret_cast<int*>(st.dDag + st.arrive_off), st.dWs, reinterpret_cast<DagCtl*>(st.dDag.p),
-                            st.dTlog, DagAug{h->P, 0, 0, nullptr}, a, DagPool{});
+                            st.dTlog, DagAug{h->P, 0, 0, nullptr}, a);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(st.evExit, s));
     st.launched = true;

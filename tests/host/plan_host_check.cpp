@@ -126,27 +126,6 @@ static void case_stream_plan(int P, int lanes, int workers, int scheme)
     print_list(c, nullptr, tasks);
 }
 
-// the list with its two hand-out orders; order[] and dep[] get n_tasks entries, the size the entry point documents
-static void case_plan_pool(const std::vector<int>& Ps, int workers, int Mt, int Ms, int scheme)
-{
-    const int B = (int)Ps.size();
-    long long n_tasks = 0, n_ctrs = 0;
-    check(psoap_dag_plan_pool(B, Ps.data(), workers, Mt, Ms, scheme, nullptr, 0, &n_tasks, nullptr, nullptr, nullptr, nullptr,
-                              nullptr, nullptr),
-          "psoap_dag_plan_pool");
-    Exact<DagTask> tasks((size_t)n_tasks);
-    Exact<unsigned int> order((size_t)n_tasks), dep((size_t)n_tasks);
-    unsigned int n_main[8] = {}, qf[9];
-    int has_pool = -9;
-    check(psoap_dag_plan_pool(B, Ps.data(), workers, Mt, Ms, scheme, tasks.p.get(), n_tasks, &n_tasks, order.p.get(), dep.p.get(),
-                              n_main, qf, &has_pool, &n_ctrs),
-          "psoap_dag_plan_pool");
-    printf("plan_pool Ps=%s workers=%d Mt=%d Ms=%d scheme=%d : n_tasks=%lld n_ctrs=%lld has_pool=%d queue_first=%016llx "
-           "n_main=%016llx tasks=%016llx order=%016llx dep=%016llx\n",
-           join(Ps).c_str(), workers, Mt, Ms, scheme, n_tasks, n_ctrs, has_pool, fnv1a(qf, sizeof qf), fnv1a(n_main, sizeof n_main),
-           tasks.hash(), order.hash(), dep.hash());
-}
-
 static void case_pick_workers(int B, int P, int Mt, int compute_units, int max_workers)
 {
     const std::vector<int> Ps((size_t)B, P);
@@ -226,10 +205,7 @@ int main()
     for (int B : Bs)
         for (int P : Pgrid) {
             if (!kept(B, P)) continue;
-            for (int w : Ws) {
-                case_plan(B, P, w);
-                for (int s : schemes) case_plan_pool(std::vector<int>((size_t)B, P), w, 0, 0, s);
-            }
+            for (int w : Ws) case_plan(B, P, w);
             for (int Mt : {0, 8}) {
                 case_pick_workers(B, P, Mt, 256, 512);
                 case_pick_workers(B, P, Mt, 256, 256);
@@ -237,10 +213,7 @@ int main()
             }
         }
     for (const std::vector<int>& Ps : {std::vector<int>{1, 5, 16}, std::vector<int>{47, 2}, std::vector<int>{3, 3, 16, 1, 9, 2, 2, 5, 16, 7}})
-        for (int w : Ws) {
-            case_plan_multi(Ps, w);
-            for (int s : {1, 2}) case_plan_pool(Ps, w, 0, 0, s);
-        }
+        for (int w : Ws) case_plan_multi(Ps, w);
     for (int P : {3, 16, 47})
         for (int width : {0, 1, 2, P / 2})
             for (int B : {1, 9})
@@ -252,7 +225,6 @@ int main()
                 case_plan_aug(P, Mt, Ms, 512, -1);
                 case_plan_aug(P, Mt, Ms, 7, 0);
                 case_plan_aug(P, Mt, Ms, 256, 1);
-                case_plan_pool(std::vector<int>(1, P), 512, Mt, Ms, 2);
             }
     for (int P : {1, 16, 64})
         for (int lanes : {1, 32, 64})

@@ -177,3 +177,32 @@ def test_variant_matrix_predictions_match_the_gpu_outcomes():
         faulted = d["check_rc"] != 0 or d["repro_rc"] != 0
         assert predicted_fault == faulted, d["name"]
     assert sum(bool(d["detector_hits"]) for d in rows) >= 7
+
+
+COMPILE_TIME_SWITCHES = {"PSOAP_FOLLOW", "PSOAP_NO_FOLLOW", "PSOAP_DIAG_INLINE", "PSOAP_CHAOS", "__HIPCC__", "__x86_64__"}
+
+
+def test_the_kernel_sources_test_no_macro_outside_the_listed_switches():
+    """Every #if / #ifdef / #ifndef / #elif under psoap_amd/csrc tests only the build's flag ladder, the chaos build and
+    the two compiler guards.  An experiment behind a new macro adds its name to the set above in the change that adds the
+    #ifdef -- and takes it out again with the verdict (DESIGN.md 8 keeps those)."""
+    import re
+    csrc = os.path.join(ROOT, "psoap_amd", "csrc")
+    lines = []
+    for name in sorted(os.listdir(csrc)):
+        if not name.endswith((".hpp", ".hip", ".h", ".cpp")):
+            continue
+        with open(os.path.join(csrc, name)) as fh:
+            for k, ln in enumerate(fh, 1):
+                if re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b", ln):
+                    lines.append((name, k, ln.strip()))
+    assert lines, "no conditional at all: the walk found no source"
+    tested = {}
+    for name, k, ln in lines:
+        expr = re.sub(r"//.*|/\*.*?\*/", "", re.sub(r"^\s*#\s*\w+", "", ln))
+        for ident in re.findall(r"[A-Za-z_]\w*", expr):
+            if ident != "defined":
+                tested.setdefault(ident, (name, k, ln))
+    assert set(tested) <= COMPILE_TIME_SWITCHES, {m: w for m, w in tested.items() if m not in COMPILE_TIME_SWITCHES}
+    named = {m for _, _, ln in lines for m in re.findall(r"PSOAP_\w+", ln)}
+    assert named <= COMPILE_TIME_SWITCHES, named - COMPILE_TIME_SWITCHES

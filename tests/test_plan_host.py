@@ -119,17 +119,6 @@ def library_line(L, name, p):
             lambda out, mx, n, ns, nc, qf: L.psoap_stream_plan(p["P"], p["lanes"], p["workers"], p["scheme"], out, mx, n, ns, nc,
                                                                ctypes.byref(so) if out is not None else None))
         return f"scheme_out={so.value} " + _fmt_list(n, ns, nc, None, tasks)
-    if name == "plan_pool":
-        Ps, head = _ints(p["Ps"]), (len(p["Ps"]),)
-        tail = (p["workers"], p["Mt"], p["Ms"], p["scheme"])
-        n, nc, has = ctypes.c_longlong(), ctypes.c_longlong(), ctypes.c_int(-9)
-        assert L.psoap_dag_plan_pool(*head, Ps, *tail, None, 0, ctypes.byref(n), None, None, None, None, None, None) == 0
-        tasks, order, dep = (DagTask * n.value)(), (ctypes.c_uint32 * n.value)(), (ctypes.c_uint32 * n.value)()
-        n_main, qf = (ctypes.c_uint32 * 8)(), (ctypes.c_uint32 * 9)()
-        assert L.psoap_dag_plan_pool(*head, Ps, *tail, tasks, n.value, ctypes.byref(n), order, dep, n_main, qf, ctypes.byref(has),
-                                     ctypes.byref(nc)) == 0
-        return (f"n_tasks={n.value} n_ctrs={nc.value} has_pool={has.value} queue_first={fnv1a(qf)} n_main={fnv1a(n_main)} "
-                f"tasks={fnv1a(tasks)} order={fnv1a(order)} dep={fnv1a(dep)}")
     if name == "pick_workers":
         w = ctypes.c_int(-9)
         assert L.psoap_dag_pick_workers(p["B"], _ints([p["P"]] * p["B"]), p["Mt"], p["compute_units"], p["max_workers"],
@@ -173,8 +162,7 @@ def test_planner_runs_clean_under_sanitizers_and_matches_the_library(tmp_path):
     assert run.stderr == ""
     lines = run.stdout.splitlines()
     names = {ln.split()[0] for ln in lines}
-    assert names == {"plan", "plan_sky", "plan_multi", "plan_aug", "stream_plan", "plan_pool", "pick_workers", "sky_first",
-                     "sky_order"}
+    assert names == {"plan", "plan_sky", "plan_multi", "plan_aug", "stream_plan", "pick_workers", "sky_first", "sky_order"}
     again = library_lines(_lib.load(), lines)
     wrong = [(a, b) for a, b in zip(lines, again) if a != b]
     assert not wrong, f"{len(wrong)} of {len(lines)} lines differ, the first: program {wrong[0][0]!r}, library {wrong[0][1]!r}"

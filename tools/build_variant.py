@@ -1,5 +1,5 @@
 """Build libpsoap_gp.so with extra hipcc flags into ab_libs/<name>.so (A/B runs: PSOAP_GP_LIB=$PWD/ab_libs/<name>.so), with the
-same assembly gate as the product build.      python tools/build_variant.py sc1 -DPSOAP_SC1_LOADS"""
+same assembly gate as the product build.      python tools/build_variant.py chaos -DPSOAP_CHAOS"""
 import os
 import shutil
 import sys
