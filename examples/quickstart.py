@@ -2,7 +2,7 @@
 them, sample with B Metropolis-Hastings chains on the GPU, check convergence, reconstruct the component
 spectra.  (Needs an MI355X and the built library: python -m psoap_amd.build.)
 
-    python examples/quickstart.py [workdir] [--chunks 3] [--chains 8] [--samples 60]
+    python examples/quickstart.py [workdir] [--chunks 3] [--chains 8] [--samples 60] [--posterior 32]
 """
 import argparse
 import os
@@ -53,6 +53,8 @@ def main(argv=None):
     ap.add_argument("--chunks", type=int, default=3)
     ap.add_argument("--chains", type=int, default=8)
     ap.add_argument("--samples", type=int, default=60)
+    ap.add_argument("--posterior", type=int, default=0, metavar="S",
+                    help="also reconstruct marginalised over S chain samples (retrieve.retrieve_posterior)")
     args = ap.parse_args(argv)
     os.makedirs(args.workdir, exist_ok=True)
     config = write_dataset(args.workdir, args.chunks)
@@ -72,6 +74,12 @@ def main(argv=None):
     print("reconstructed f, g on", len(res["wl_predict"]), "pixels; acceptance", np.round(sampler.acceptance_fraction, 2))
     drawn = retrieve.retrieve_components("SB2", pdata.Chunk.open(order, wl0, wl1, prefix=args.workdir + "/"), pars, n_draws=5, seed=1)
     print("five posterior draws of f, g:", drawn["f_draws"].shape, drawn["g_draws"].shape)
+    if args.posterior > 0:
+        post = retrieve.retrieve_posterior("SB2", pdata.Chunk.open(order, wl0, wl1, prefix=args.workdir + "/"), pars,
+                                           np.concatenate(chains), config["fix_params"], n_samples=args.posterior)
+        retrieve.save_components(post, os.path.join(args.workdir, "plots_posterior_" + pdata.chunk_fmt.format(order, wl0, wl1)))
+        print("marginalised over", post["n_folded"], "chain samples: median sigma_g", np.median(post["sigma_g"]), "of which between samples",
+              np.median(post["sigma_between_g"]), "(at the point estimate:", np.median(res["sigma_g"]), ")")
     return sampler, res
 
 

@@ -523,6 +523,44 @@ int psoap_chunk_predict_draw(psoap_chunk *h, int D, unsigned long long seed, con
 int psoap_draw_normals(int device, unsigned long long seed, int D, int n, double *out);
 /* host twin of the generator's integer core (pure host): the Philox4x32-10 block of key seed, counter (c0, c1, 0, 0) */
 int psoap_draw_philox(unsigned long long seed, unsigned int c0, unsigned int c1, unsigned int out[4]);
+/* Component spectra marginalised over the chain: mixture moments on the device (csrc/mix_kernels.hpp, mix_plan.hpp).
+ * Over samples s = 1 .. S of the orbit and the hyper-parameters with weights w_s, W = sum_s w_s, and the conditional
+ * (mu_s, Sigma_s) of each sample as psoap_chunk_predict (marg = 0) or psoap_chunk_predict_marg (marg = 1) computes it:
+ *     mu_mix    = sum_s w_s mu_s / W
+ *     Sigma_mix = sum_s w_s Sigma_s / W  +  sum_s w_s (mu_s - mu_mix)(mu_s - mu_mix)^T / W      (within + between)
+ * Every sample is folded on the device; one mu and one Sigma travel to the host at the end.
+ * psoap_chunk_mix_begin fixes what the samples share -- marg, mode, c, M and lwl_pred (c, M) as the twins take them (marg = 1
+ * needs a current baseline), the prior means mu_c (c values in mode 0, else one), S_max (1 .. 4096) and whether full Sigma
+ * (want_sigma = 1) or the variances only (0) are accumulated -- and zeroes the accumulators.  Memory, beside the predict
+ * workspace and untouched by psoap_chunk_predict_release: 2 x 8 Rpad^2 (Sbar, Sigma_mix; 8 Rpad in the variance-only mode)
+ * + 2 x 8 Spad Rpad (the stacked means and their centred copy), Rpad = R rounded up to 128, Spad = S_max rounded up to 16.
+ * psoap_chunk_mix_add runs exactly the predict call of the twins (their _var forms with want_sigma = 0) for (lwl (c, N),
+ * gp (2c)) with the outputs staying on the device -- no Sigma download -- and folds the result with `weight` (finite, > 0):
+ * Sbar += weight Sigma_s without FMA contraction (weight 1 adds exactly), mu_s into row s of the stacked means.  With
+ * want_sigma = 1 the handle's draw record is left as by a predict call with Sigma_out: psoap_chunk_predict_draw then draws
+ * from that sample's posterior.  status_out: 0 folded; 1 not positive definite -- the sample is NOT folded, the accumulators
+ * are untouched, the call returns 0.
+ * psoap_chunk_mix_finish only reads the accumulators: it may be called repeatedly and between adds.  mu_out (R), Sigma_out
+ * (R, R; symmetric bit for bit; must be NULL in the variance-only mode, may be NULL otherwise), var_within_out and
+ * var_between_out (R): diag of the two terms, diag(Sigma_mix) = var_within + var_between.  n_folded_out, W_out: optional.
+ * W and the weighted means are summed in ascending order of the adds, one lane per column; the between term is one fp64
+ * MFMA launch over all upper tiles (K loop over the samples in that order); no atomics: the result is fixed by
+ * (R, the samples, the order of the adds).
+ * Each returns 2 (psoap_last_error): an open stream; weight not finite or <= 0; more than S_max folded samples; S_max < 1 or
+ * > 4096; add or finish without begin, or after psoap_chunk_set_data, psoap_chunk_set_baseline or psoap_chunk_mix_release
+ * ended the mixture; finish with nothing folded; Sigma_out in the variance-only mode.
+ * Launches are booked under PSOAP_K_FILL (fold), GRAD (the rank-S product), MISC (the rest). */
+int psoap_chunk_mix_begin(psoap_chunk *h, int marg, int mode, int c, int M, const double *lwl_pred,
+                          const double *mu_c, int S_max, int want_sigma);
+int psoap_chunk_mix_add(psoap_chunk *h, const double *lwl, const double *gp, double weight, int *status_out);
+int psoap_chunk_mix_finish(psoap_chunk *h, double *mu_out, double *Sigma_out, double *var_within_out,
+                           double *var_between_out, int *n_folded_out, double *W_out);
+int psoap_chunk_mix_release(psoap_chunk *h);
+/* host twin of the mixture's plan (pure host): Rpad, Spad, the upper tiles of the rank-S product in launch order
+ * (tiles_out: min(max_tiles, n_tiles) pairs (ti, tj)) and the bytes of all its device buffers; any output may be NULL.
+ * Returns 2: R < 1 or > 32768, S_max < 1 or > 4096, want_sigma not 0 or 1. */
+int psoap_mix_plan(int R, int S_max, int want_sigma, int *Rpad, int *Spad, int *n_tiles, int *tiles_out,
+                   int max_tiles, long long *bytes);
 /* Timings of the handle's last predict call, in ms: device_ms = first upload ->
  * mu and Sigma complete on the device (HIP events), factor_ms = the persistent
  * launch over [B | Cx^T], sigma_ms = mean + prior fill + Sigma = A - W^T W,

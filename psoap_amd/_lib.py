@@ -97,6 +97,13 @@ SIGNATURES = {
     "psoap_chunk_predict_draw": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_ulonglong, _dp, ctypes.c_double, _dp, _ip]),
     "psoap_draw_normals": (ctypes.c_int, [ctypes.c_int, ctypes.c_ulonglong, ctypes.c_int, ctypes.c_int, _dp]),
     "psoap_draw_philox": (ctypes.c_int, [ctypes.c_ulonglong, ctypes.c_uint, ctypes.c_uint, ctypes.POINTER(ctypes.c_uint)]),
+    "psoap_chunk_mix_begin": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, _dp, ctypes.c_int,
+                                             ctypes.c_int]),
+    "psoap_chunk_mix_add": (ctypes.c_int, [_vp, _dp, _dp, ctypes.c_double, _ip]),
+    "psoap_chunk_mix_finish": (ctypes.c_int, [_vp, _dp, _dp, _dp, _dp, _ip, _dp]),
+    "psoap_chunk_mix_release": (ctypes.c_int, [_vp]),
+    "psoap_mix_plan": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _ip, _ip, _ip, _ip, ctypes.c_int,
+                                      ctypes.POINTER(ctypes.c_longlong)]),
     "psoap_chunk_predict_timings": (ctypes.c_int, [_vp, ctypes.POINTER(PredictTimings)]),
     "psoap_predictor_create": (ctypes.c_int, [ctypes.POINTER(_vp), ctypes.c_int]),
     "psoap_predictor_run": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp,

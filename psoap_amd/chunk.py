@@ -568,6 +568,54 @@ class ChunkHandle:
             raise np.linalg.LinAlgError("Sigma + nugget I is not positive definite")
         return out
 
+    # -- mixture moments over chain samples (include/psoap_gp.h: psoap_chunk_mix_*) -------------------------------
+    def mix_begin(self, mode: int, lwls_predict, mu_c, s_max: int, want_sigma: bool = True, marg: bool = False):
+        """Start a mixture of up to ``s_max`` parameter samples on this handle: all of them are predicted on ``lwls_predict``
+        (c, M) with prior means ``mu_c``, as ``predict`` (``marg``: as ``predict_marg``, under the current baseline) takes
+        them.  ``want_sigma=False`` accumulates the variances only.  The accumulators start at zero."""
+        pred = as_f64(np.atleast_2d(lwls_predict))
+        c, M = pred.shape
+        mu_c = as_f64(np.atleast_1d(mu_c))
+        if mu_c.shape[0] < (c if mode == 0 else 1):
+            raise ValueError("mu_c must hold one prior mean per component in mode 0, else one")
+        check(self._L.psoap_chunk_mix_begin(self._h, int(bool(marg)), int(mode), c, M, dptr(pred), dptr(mu_c), int(s_max),
+                                            int(bool(want_sigma))), "psoap_chunk_mix_begin")
+        self._mix = (c, c * M if mode == 0 else M, bool(want_sigma))
+
+    def mix_add(self, lwls, gp, weight: float = 1.0) -> bool:
+        """Predict one sample -- rest-frame grids ``lwls`` (c, N), hyper-parameters ``gp`` (2c,) -- and fold its mean and
+        ``Sigma`` (or variances) into the mixture with ``weight``; nothing of size R^2 leaves the device.  -> True, or False
+        when the sample's data covariance is not positive definite: it is then not folded and the mixture is as before.
+        After a folded sample of a full-``Sigma`` mixture ``predict_draw`` draws from that sample's posterior."""
+        c, R, full = getattr(self, "_mix", None) or (np.atleast_2d(lwls).shape[0], 0, False)
+        lwls = as_f64(np.atleast_2d(lwls), (c, self.N))
+        gp = as_f64(gp, (2 * c,))
+        status = ctypes.c_int(0)
+        self._sigma_rows = 0
+        check(self._L.psoap_chunk_mix_add(self._h, dptr(lwls), dptr(gp), float(weight), ctypes.byref(status)), "psoap_chunk_mix_add")
+        if status.value == 0 and full:
+            self._sigma_rows = R
+        return status.value == 0
+
+    def mix_finish(self, want_sigma=None) -> dict:
+        """The moments of what has been folded so far (it only reads the accumulators: call it again, or go on adding):
+        ``mu`` (R,), ``Sigma`` (R, R) or None, ``var_within`` and ``var_between`` (R,) with ``diag(Sigma) = var_within +
+        var_between``, ``n_folded`` and the sum of the weights ``W``.  ``want_sigma=False`` on a full-``Sigma`` mixture spares
+        the download."""
+        c, R, full = getattr(self, "_mix", None) or (0, 1, False)
+        want = full if want_sigma is None else bool(want_sigma)
+        mu, vw, vb = np.empty(R), np.empty(R), np.empty(R)
+        Sigma = np.empty((R, R)) if want else None
+        n, W = ctypes.c_int(0), ctypes.c_double(0.0)
+        check(self._L.psoap_chunk_mix_finish(self._h, dptr(mu), None if Sigma is None else dptr(Sigma), dptr(vw), dptr(vb),
+                                             ctypes.byref(n), ctypes.byref(W)), "psoap_chunk_mix_finish")
+        return {"mu": mu, "Sigma": Sigma, "var_within": vw, "var_between": vb, "n_folded": n.value, "W": W.value}
+
+    def mix_release(self):
+        """End the mixture and free its buffers (the predict workspace stays)."""
+        self._mix = None
+        check(self._L.psoap_chunk_mix_release(self._h), "psoap_chunk_mix_release")
+
     def predict_release(self):
         """Free the predict workspace (``predict``, ``predict_marg`` and ``predict_draw`` share it); the next call allocates
         it again."""

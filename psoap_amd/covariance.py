@@ -502,6 +502,64 @@ def predict_draws(lwls, fl, sigma, lwls_predict, mus, gp, n_draws, seed, mode=0,
     return mu, (Sigma if want_sigma else None), draws
 
 
+def _baseline_args(baseline):
+    unknown = set(baseline) - {"x", "epoch_index", "order", "prior_sd", "weight"}
+    if unknown or not {"x", "epoch_index", "order", "prior_sd"} <= set(baseline):
+        raise ValueError(f"baseline needs 'x', 'epoch_index', 'order' and 'prior_sd' (and optionally 'weight'); got {sorted(baseline)}")
+    ep = np.asarray(baseline["epoch_index"], dtype=np.int64)
+    return baseline["order"], baseline["x"], ep, int(ep.max()) + 1, baseline["prior_sd"], baseline.get("weight")
+
+
+def predict_mixture(lwls_list, fl, sigma, lwls_predict, mus, gps, weights=None, mode=0, baseline=None, want_sigma=True,
+                    draws_per_sample=0, seed=None, nugget=1e-8):
+    """Not a function of the reference: the component spectra of one chunk marginalised over ``S`` samples of the orbit and
+    the hyper-parameters (a thinned chain), by the law of total covariance with weights ``w_s``, ``W = sum w_s``:
+
+        mu    = sum_s w_s mu_s / W
+        Sigma = sum_s w_s Sigma_s / W  +  sum_s w_s (mu_s - mu)(mu_s - mu)^T / W          (within + between)
+
+    ``(mu_s, Sigma_s)`` is what ``ChunkHandle.predict`` (``predict_marg`` with ``baseline``, the dictionary of
+    ``predict_draws``) returns for sample ``s``; every sample is folded on the device through the chunk's cached handle
+    (``ChunkHandle.mix_*``) and one ``mu`` and one ``Sigma`` are downloaded at the end.  ``lwls_list`` (S, c, N): the
+    rest-frame grids of every sample; ``gps`` (S, 2c); ``lwls_predict`` (c, M) and ``mus``: ONE prediction grid and the
+    prior means for all samples; ``weights`` (S,), default all one.  ``want_sigma=False`` accumulates variances only.
+    Returns a dict: ``mu``, ``Sigma`` (or None), ``var_within``, ``var_between`` (``diag(Sigma)`` is their sum),
+    ``n_folded``, ``skipped`` -- the indices of the samples whose data covariance was not positive definite; they are left
+    out -- and, with ``draws_per_sample > 0`` (needs ``want_sigma`` and ``seed``), ``draws`` of shape
+    ``(n_folded * draws_per_sample, R)``: draws from the mixture itself -- a parameter sample, then spectra from
+    ``N(mu_s, Sigma_s + nugget I)`` with the generator's seed ``seed + s`` (``ChunkHandle.predict_draw``)."""
+    lw = np.stack([np.stack([as_f64(w) for w in np.atleast_2d(l)]) for l in lwls_list])
+    S, c = lw.shape[0], lw.shape[1]
+    gps = as_f64(np.atleast_2d(gps), (S, 2 * c))
+    w = np.ones(S) if weights is None else as_f64(weights, (S,))
+    pred = np.stack([as_f64(p) for p in np.atleast_2d(lwls_predict)])
+    n_draw = int(draws_per_sample)
+    if n_draw > 0 and (seed is None or not want_sigma):
+        raise ValueError("draws_per_sample > 0 needs a seed and want_sigma=True")
+    fl, sigma = as_f64(fl), as_f64(sigma)
+    h = _chunk_for(fl, sigma)
+    if not hasattr(h, "mix_begin"):
+        raise _lib.PsoapError("predict_mixture needs the device in this process (PSOAP_GPU_SERVER serves values only)")
+    if baseline is not None:
+        h.set_baseline(*_baseline_args(baseline))
+    h.mix_begin(int(mode), pred, np.atleast_1d(mus), S, want_sigma=bool(want_sigma), marg=baseline is not None)
+    skipped, draws = [], []
+    try:
+        for s in range(S):
+            if not h.mix_add(lw[s], gps[s], w[s]):
+                skipped.append(s)
+            elif n_draw > 0:
+                draws.append(h.predict_draw(n_draw, seed=int(seed) + s, nugget=nugget))
+        out = h.mix_finish()
+    finally:
+        h.mix_release()
+    del out["W"]
+    out["skipped"] = skipped
+    if n_draw > 0:
+        out["draws"] = np.concatenate(draws, axis=0)
+    return out
+
+
 def velocity_gradient(grad_lwl, epoch_index, n_epochs):
     """``dlnL/dv[c, e]`` from ``dlnL/dlwl[c, i]``: the rest-frame grids are ``lwl - v[c, epoch]/c_kms``
     (``data.replicate_wls``), so ``dlnL/dv[c, e] = -(1/c_kms) sum_{i in epoch e} dlnL/dlwl[c, i]``.

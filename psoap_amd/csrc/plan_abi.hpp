@@ -10,6 +10,7 @@
 #include "abi_error.hpp"
 #include "dag_plan.hpp"
 #include "draw_rng.hpp"
+#include "mix_plan.hpp"
 #include "sky_rules.hpp"
 
 using namespace psoap;
@@ -260,5 +261,23 @@ extern "C" int psoap_draw_philox(unsigned long long seed, unsigned int c0, unsig
     if (!out) FAIL("psoap_draw_philox: bad arguments");
     const PhiloxBlock b = draw_block(seed, c0, c1);
     for (int k = 0; k < 4; ++k) out[k] = b.w[k];
+    return 0;
+}
+
+// Pure host function: the plan of a mixture of R prediction rows and up to S_max samples (mix_plan.hpp) -- the padded sizes,
+// the upper tiles of the rank-S product in launch order (tiles_out: min(max_tiles, n_tiles) pairs (ti, tj); may be null) and
+// the bytes of all its device buffers.  Any output may be null.
+extern "C" int psoap_mix_plan(int R, int S_max, int want_sigma, int* Rpad, int* Spad, int* n_tiles, int* tiles_out, int max_tiles,
+                              long long* bytes)
+{
+    if (const char* why = mix_check_plan(R, S_max, want_sigma)) FAIL(std::string("psoap_mix_plan: ") + why);
+    MixPlan g;
+    mix_plan(R, S_max, want_sigma, g);
+    if (Rpad) *Rpad = g.Rpad;
+    if (Spad) *Spad = g.Spad;
+    if (n_tiles) *n_tiles = (int)g.tiles.size();
+    if (tiles_out)
+        for (int t = 0; t < (int)g.tiles.size() && t < max_tiles; ++t) tiles_out[2 * t] = g.tiles[(size_t)t].ti, tiles_out[2 * t + 1] = g.tiles[(size_t)t].tj;
+    if (bytes) *bytes = g.bytes;
     return 0;
 }

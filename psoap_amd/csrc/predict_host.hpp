@@ -380,19 +380,23 @@ static int predict_dag_verdict(PredictWs& ws, const PredictShape& g)
 // dFl_res / dSig_res: the data and noise vectors already resident on the device (a chunk handle's), or nullptr -> fl /
 // sigma are uploaded into the workspace.  var_out (optional): diag(Sigma) alone -- R doubles instead of R^2, and no N R^2
 // product.  force_staged: several processes share the device and the persistent launch is not to be used, or was disturbed
-// (predict_settled).  A matrix that is not positive definite: *status = 1 and the values as they came out.
+// (predict_settled).  keep_sigma: Sigma is formed in the workspace as with Sigma_out, by the same launches, and stays there --
+// no download (the mixture moments fold it on the device).  A matrix that is not positive definite: *status = 1 and the values
+// as they came out.
 static int predict_run(PredictWs& ws, int mode, int c, int N, int M, const double* lwl, const double* fl, const double* sigma,
                        const double* dFl_res, const double* dSig_res, const double* lwl_pred, const double* mu_c, const double* gp,
-                       double* mu_out, double* Sigma_out, int* status, double* var_out = nullptr, bool force_staged = false)
+                       double* mu_out, double* Sigma_out, int* status, double* var_out = nullptr, bool force_staged = false,
+                       bool keep_sigma = false)
 {
     const auto t_begin = std::chrono::steady_clock::now();
     SigmaPin pin;         // declared first: its destructor joins the helper thread and drops the registration on every return path
     PredictShape g;
     if (const char* why = predict_shape(mode, c, N, M, mu_c[0], g)) FAIL(why);
     const bool use_dag = !force_staged && g.dag_ok;
+    const bool want_S = Sigma_out || keep_sigma;
     // PSOAP_PREDICT_FUSED=0: Sigma by the separate product (k_syrk_sub_sym) also behind the persistent launch
     const char* env_fused = getenv("PSOAP_PREDICT_FUSED");
-    const bool fused_sigma = use_dag && Sigma_out && !(env_fused && atoi(env_fused) == 0);
+    const bool fused_sigma = use_dag && want_S && !(env_fused && atoi(env_fused) == 0);
     const int Npad = g.Npad, Rq = g.Rq, Rq_pad = g.Rq_pad, nslab = g.nslab;
     const PredictStaging hs = predict_staging(Rq_pad, sizeof(MatAcc), c);
     if (int rc = predict_stream(ws)) return rc;
@@ -426,7 +430,7 @@ static int predict_run(PredictWs& ws, int mode, int c, int N, int M, const doubl
     HIP_TRY(hipMemcpyAsync(h_acc, dAcc + ACC_ROWS, sizeof(MatAcc), hipMemcpyDeviceToHost, st));
 
     bool sigma_direct = false;
-    if (Sigma_out) {
+    if (want_S) {
         const int St = Rq_pad / NB;
         HIP_TRY(ws.S.need((size_t)Rq_pad * Rq_pad));
         if (!fused_sigma) {
@@ -439,7 +443,8 @@ static int predict_run(PredictWs& ws, int mode, int c, int N, int M, const doubl
             HIP_TRY(hipGetLastError());
         }
         HIP_TRY(hipEventRecord(ws.ev[3], st));           // the device work of the call ends here
-        if (int rc = predict_sigma_direct(pin, ws, g, st, Sigma_out, &sigma_direct)) return rc;
+        if (Sigma_out)
+            if (int rc = predict_sigma_direct(pin, ws, g, st, Sigma_out, &sigma_direct)) return rc;
     }
     if (var_out) {
         if (int rc = predict_upload_prior(ws, g, st, gp, ws.hSmall.p + hs.prior)) return rc;
@@ -448,7 +453,7 @@ static int predict_run(PredictWs& ws, int mode, int c, int N, int M, const doubl
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(h_var, ws.Var, sizeof(double) * Rq, hipMemcpyDeviceToHost, st));
     }
-    if (!Sigma_out) HIP_TRY(hipEventRecord(ws.ev[3], st));
+    if (!want_S) HIP_TRY(hipEventRecord(ws.ev[3], st));
     HIP_TRY(hipStreamSynchronize(st));
     if (use_dag)
         if (int rc = predict_dag_verdict(ws, g)) return rc;      // (pin's destructor drops the registration)
@@ -458,6 +463,6 @@ static int predict_run(PredictWs& ws, int mode, int c, int N, int M, const doubl
     *status = (h_acc->info != 0.0) ? 1 : 0;
     memcpy(mu_out, h_mu, sizeof(double) * Rq);
     if (var_out) memcpy(var_out, h_var, sizeof(double) * Rq);
-    predict_times(ws, t_begin, t_ev0, predict_flops(Npad, Rq_pad, Sigma_out != nullptr, var_out != nullptr));
+    predict_times(ws, t_begin, t_ev0, predict_flops(Npad, Rq_pad, want_S, var_out != nullptr));
     return 0;
 }

@@ -39,6 +39,7 @@
 #include "marg_fisher_kernels.hpp"
 #include "marg_predict_kernels.hpp"
 #include "draw_kernels.hpp"
+#include "mix_kernels.hpp"
 #include "abi_error.hpp"
 #include "plan_abi.hpp"
 #include "share.hpp"
@@ -229,6 +230,9 @@ struct psoap_chunk {
         int R = 0, mode = 0;
     } sigma;
     std::unique_ptr<psoap::DrawWs> dws;
+    // mixture moments over chain samples (psoap_chunk_mix_*): the accumulators and what psoap_chunk_mix_begin fixed -- buffers
+    // of their own, untouched by psoap_chunk_predict_release; ended by a change of the data or the baseline
+    std::unique_ptr<psoap::MixWs> xws;
     // gradient workspace (allocated by the first psoap_chunk_lnlike_grad; psoap_chunk_grad_release)
     std::unique_ptr<psoap::GradWs> gws;
     // Fisher workspace (allocated by the first psoap_chunk_fisher; psoap_chunk_fisher_release)
@@ -328,6 +332,7 @@ static int configure_kernels(int device)
     HIP_TRY(marg_fisher_configure_kernels());
     HIP_TRY(marg_predict_configure_kernels());
     HIP_TRY(draw_configure_kernels());
+    HIP_TRY(mix_configure_kernels());
     if (done.size() <= (size_t)device) done.resize((size_t)device + 1, 0);
     done[device] = 1;
     return 0;
@@ -496,6 +501,7 @@ extern "C" int psoap_chunk_set_data(psoap_chunk* h, const double* fl, const doub
     // a baseline with weights described the old data (w = fl is the usual choice): psoap_chunk_set_baseline again
     if (h->marg.valid && !h->marg.weight.empty()) h->marg.stale_weight = true;
     h->sigma.valid = false;      // (the posterior in the predict workspace was the old data's)
+    if (h->xws) h->xws->active = false;      // (and so were the samples a mixture has folded)
     // the sorted copies of the slots that hold a batch
     for (BatchSlot& sl : h->slot)
         if (h->sky && sl.B > 0 && sl.sky_valid) {
@@ -2785,6 +2791,7 @@ extern "C" int psoap_chunk_set_baseline(psoap_chunk* h, int order, const double*
     m.valid = true;
     m.stale_weight = false;
     h->sigma.valid = false;
+    if (h->xws) h->xws->active = false;
     if (h->mws) h->mws->basis_ready = false;      // (Ht is built by the next psoap_chunk_lnlike_marg, on its stream)
     return 0;
 }
@@ -3153,13 +3160,14 @@ extern "C" int psoap_fill_cross(int device, int M, int N, const double* lwl_row,
 static int predict_settled(PredictWs& ws, int device, int mode, int c, int N, int M, const double* lwl, const double* fl,
                            const double* sigma, const double* dFl, const double* dSig, const double* lwl_pred,
                            const double* mu_c, const double* gp, double* mu_out, double* Sigma_out, int* status,
-                           double* var_out)
+                           double* var_out, bool keep_sigma = false)
 {
     bool staged = share_wants_staged(device);
     if (staged) g_share.staged_policy += 1;
     for (int attempt = 0;; ++attempt) {
         if (!staged) g_share.dag_launches += 1;
-        int rc = predict_run(ws, mode, c, N, M, lwl, fl, sigma, dFl, dSig, lwl_pred, mu_c, gp, mu_out, Sigma_out, status, var_out, staged);
+        int rc = predict_run(ws, mode, c, N, M, lwl, fl, sigma, dFl, dSig, lwl_pred, mu_c, gp, mu_out, Sigma_out, status, var_out, staged,
+                             keep_sigma);
         if (rc == 0 && !staged && share_inject_taint()) rc = 3;
         if (rc != 3) return rc;
         g_share.tainted += 1;
@@ -3381,12 +3389,13 @@ static int marg_predict_factor(psoap_chunk* h, PredictWs& ws, MargWs& m, MargPre
 
 static int marg_predict_run(psoap_chunk* h, const char* who, int mode, int c, int M, const double* lwl, const double* lwl_pred,
                             const double* mu_c, const double* gp, double* mu_out, double* Sigma_out, double* var_out,
-                            int* status_out)
+                            int* status_out, bool keep_sigma = false)
 {
     if (!h || !lwl || !lwl_pred || !mu_c || !gp || !mu_out) FAIL(std::string(who) + ": bad arguments");
     if (h->stream.open) FAIL(std::string(who) + ": the handle has an open stream (psoap_stream_close first)");
     if (const char* why = marg_predict_check(mode, c, M, h->marg.valid, h->marg.stale_weight)) FAIL(std::string(who) + ": " + why);
     const auto t_begin = std::chrono::steady_clock::now();
+    const bool want_S = Sigma_out || keep_sigma;      // (keep_sigma: as predict_run's)
     SigmaPin pin;         // declared first, as in predict_run: its destructor drops the registration on every return path
     h->sigma.valid = false;
     DEVICE_SCOPE(h->device);
@@ -3437,7 +3446,7 @@ static int marg_predict_run(psoap_chunk* h, const char* who, int mode, int c, in
     HIP_TRY(hipMemcpyAsync(h_mu, ws.Mu, sizeof(double) * Rq, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(h_acc, mp.AccTot, 2 * sizeof(MatAcc), hipMemcpyDeviceToHost, s));
     bool sigma_direct = false;
-    if (Sigma_out) {
+    if (want_S) {
         HIP_TRY(ws.S.need((size_t)Rq_pad * Rq_pad));
         // the prior covariance of the prediction in the upper tiles (mode 1 here is predict_f_g_sum: its nugget, :165), then
         // every upper tile in one launch (launching tile rows one after the other serialises them)
@@ -3447,7 +3456,8 @@ static int marg_predict_run(psoap_chunk* h, const char* who, int mode, int c, in
                                    Y, (size_t)ldm, S, ws.S.p, (size_t)Rq_pad, g.St, 0);
             })) return rc;
         HIP_TRY(hipEventRecord(ws.ev[3], s));
-        if (int rc = predict_sigma_direct(pin, ws, sh, s, Sigma_out, &sigma_direct)) return rc;
+        if (Sigma_out)
+            if (int rc = predict_sigma_direct(pin, ws, sh, s, Sigma_out, &sigma_direct)) return rc;
     }
     if (var_out) {
         if (int rc = predict_upload_prior(ws, sh, s, gp, ws.hSmall.p + hs.prior)) return rc;
@@ -3459,7 +3469,7 @@ static int marg_predict_run(psoap_chunk* h, const char* who, int mode, int c, in
             })) return rc;
         HIP_TRY(hipMemcpyAsync(h_var, ws.Var, sizeof(double) * Rq, hipMemcpyDeviceToHost, s));
     }
-    if (!Sigma_out) HIP_TRY(hipEventRecord(ws.ev[3], s));
+    if (!want_S) HIP_TRY(hipEventRecord(ws.ev[3], s));
     HIP_TRY(hipStreamSynchronize(s));
     if (Sigma_out && !sigma_direct)
         if (int rc = predict_sigma_staged(ws, sh, Sigma_out)) return rc;
@@ -3473,8 +3483,8 @@ static int marg_predict_run(psoap_chunk* h, const char* who, int mode, int c, in
         for (int q = 0; q < Rq; ++q) var_out[q] = bad ? NAN : h_var[q];
     if (Sigma_out && bad)
         for (size_t k = 0; k < (size_t)Rq * Rq; ++k) Sigma_out[k] = NAN;
-    if (Sigma_out && !bad) h->sigma = psoap_chunk::SigmaRecord{true, Rq, mode};
-    predict_times(ws, t_begin, t_ev0, marg_predict_flops(g, Sigma_out != nullptr, var_out != nullptr));
+    if (want_S && !bad) h->sigma = psoap_chunk::SigmaRecord{true, Rq, mode};
+    predict_times(ws, t_begin, t_ev0, marg_predict_flops(g, want_S, var_out != nullptr));
     return 0;
 }
 
@@ -3578,6 +3588,155 @@ extern "C" int psoap_draw_normals(int device, unsigned long long seed, int D, in
                        D, D, seed);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpy(out, dZ, sizeof(double) * (size_t)D * n, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ---- mixture moments over chain samples (mix_kernels.hpp) ------------------------------------------------------
+// begin fixes what the samples share and zeroes the accumulators; add runs the predict call of the twins for one sample with
+// mu and Sigma (or the variances) staying in the predict workspace and folds them; finish forms the moments and downloads
+// one mu and one Sigma.  The folds and the finish run on the handle's first stream; every call returns with the device idle.
+static int mix_refuse_stream(const psoap_chunk* h, const char* who)
+{
+    if (h->stream.open) FAIL(std::string(who) + ": the handle has an open stream (psoap_stream_close first)");
+    return 0;
+}
+
+extern "C" int psoap_chunk_mix_begin(psoap_chunk* h, int marg, int mode, int c, int M, const double* lwl_pred, const double* mu_c,
+                                     int S_max, int want_sigma)
+{
+    if (!h) FAIL("psoap_chunk_mix_begin: bad arguments");
+    if (int rc = mix_refuse_stream(h, "psoap_chunk_mix_begin")) return rc;
+    if (const char* why = mix_check_begin(marg, mode, c, M, S_max, want_sigma, lwl_pred && mu_c))
+        FAIL(std::string("psoap_chunk_mix_begin: ") + why);
+    if (marg) {
+        if (const char* why = marg_predict_check(mode, c, M, h->marg.valid, h->marg.stale_weight))
+            FAIL(std::string("psoap_chunk_mix_begin: ") + why);
+    }
+    PredictShape sh;
+    if (const char* why = predict_shape(mode, c, h->N, M, mu_c[0], sh)) FAIL(std::string("psoap_chunk_mix_begin: ") + why);
+    DEVICE_SCOPE(h->device);
+    if (int rc = enter_device(h->device)) return rc;
+    if (!h->xws) h->xws.reset(new MixWs());
+    MixWs& x = *h->xws;
+    x.active = false;
+    mix_plan(mix_rows(mode, c, M), S_max, want_sigma, x.plan);
+    const MixPlan& g = x.plan;
+    HIP_TRY(x.Sbar.need((size_t)g.sbar_doubles));
+    if (want_sigma) HIP_TRY(x.Out.need((size_t)g.out_doubles));
+    HIP_TRY(x.Mu.need((size_t)g.mu_doubles));
+    HIP_TRY(x.D.need((size_t)g.mu_doubles));
+    HIP_TRY(x.Small.need((size_t)g.small_doubles));
+    HIP_TRY(x.hSmall.need(3 * (size_t)g.Rpad + 1));
+    hipStream_t s = h->streams[0];
+    HIP_TRY(hipMemsetAsync(x.Sbar, 0, sizeof(double) * (size_t)g.sbar_doubles, s));
+    HIP_TRY(hipMemsetAsync(x.Small, 0, sizeof(double) * (size_t)g.small_doubles, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    x.marg = marg, x.mode = mode, x.c = c, x.M = M, x.n_folded = 0;
+    x.lwl_pred.assign(lwl_pred, lwl_pred + (size_t)c * M);
+    x.mu_c.assign(mu_c, mu_c + (mode == 0 ? c : 1));
+    x.mu_host.assign((size_t)g.R, 0.0);
+    x.var_host.assign((size_t)g.R, 0.0);
+    x.active = true;
+    return 0;
+}
+
+extern "C" int psoap_chunk_mix_add(psoap_chunk* h, const double* lwl, const double* gp, double weight, int* status_out)
+{
+    if (!h) FAIL("psoap_chunk_mix_add: bad arguments");
+    if (int rc = mix_refuse_stream(h, "psoap_chunk_mix_add")) return rc;
+    if (const char* why = mix_check_add(h->xws && h->xws->active, h->xws ? h->xws->n_folded : 0, h->xws ? h->xws->plan.S_max : 0,
+                                        weight, lwl && gp))
+        FAIL(std::string("psoap_chunk_mix_add: ") + why);
+    MixWs& x = *h->xws;
+    const MixPlan& g = x.plan;
+    const bool full = g.want_sigma != 0;
+    DEVICE_SCOPE(h->device);
+    if (int rc = enter_device(h->device)) return rc;
+    int status = 0;
+    // the predict call of the twins: Sigma formed and kept on the device (full), or the variances (their download is R doubles)
+    if (x.marg) {
+        if (int rc = marg_predict_run(h, "psoap_chunk_mix_add", x.mode, x.c, x.M, lwl, x.lwl_pred.data(), x.mu_c.data(), gp,
+                                      x.mu_host.data(), nullptr, full ? nullptr : x.var_host.data(), &status, full)) return rc;
+    } else {
+        h->sigma.valid = false;
+        if (int rc = predict_settled(predict_ws_of(h), h->device, x.mode, x.c, h->N, x.M, lwl, nullptr, nullptr, h->dFl, h->dSigma,
+                                     x.lwl_pred.data(), x.mu_c.data(), gp, x.mu_host.data(), nullptr, &status,
+                                     full ? nullptr : x.var_host.data(), full)) return rc;
+        if (status == 0 && full) h->sigma = psoap_chunk::SigmaRecord{true, g.R, x.mode};
+        h->recs.clear();      // (the plain call books nothing)
+    }
+    if (status_out) *status_out = status;
+    if (status != 0) return 0;      // not positive definite: nothing is folded
+    PredictWs& ws = *h->pws;
+    hipStream_t s = h->streams[0];
+    const int R = g.R, Rpad = g.Rpad, slot = x.n_folded;
+    if (int rc = prof_launch(h, s, PSOAP_K_FILL, 0.0, full ? 24.0 * R * (double)R : 24.0 * R, [&] {
+            if (full)
+                hipLaunchKernelGGL(k_mix_fold, dim3((Rpad + 511) / 512, R), dim3(256), 0, s, (const double*)ws.S.p, (size_t)Rpad,
+                                   (const double*)ws.Mu.p, R, Rpad, weight, slot, x.Sbar.p, x.Mu.p, x.wv());
+            else
+                hipLaunchKernelGGL(k_mix_fold_var, dim3((Rpad + 255) / 256), dim3(256), 0, s, (const double*)ws.Var.p,
+                                   (const double*)ws.Mu.p, R, Rpad, weight, slot, x.Sbar.p, x.Mu.p, x.wv());
+        })) return rc;
+    HIP_TRY(hipStreamSynchronize(s));
+    x.n_folded = slot + 1;
+    return collect_timings(h);
+}
+
+extern "C" int psoap_chunk_mix_finish(psoap_chunk* h, double* mu_out, double* Sigma_out, double* var_within_out,
+                                      double* var_between_out, int* n_folded_out, double* W_out)
+{
+    if (!h) FAIL("psoap_chunk_mix_finish: bad arguments");
+    if (int rc = mix_refuse_stream(h, "psoap_chunk_mix_finish")) return rc;
+    if (const char* why = mix_check_finish(h->xws && h->xws->active, h->xws ? h->xws->n_folded : 0,
+                                           h->xws ? h->xws->plan.want_sigma : 0, Sigma_out != nullptr,
+                                           mu_out && var_within_out && var_between_out))
+        FAIL(std::string("psoap_chunk_mix_finish: ") + why);
+    MixWs& x = *h->xws;
+    const MixPlan& g = x.plan;
+    DEVICE_SCOPE(h->device);
+    if (int rc = enter_device(h->device)) return rc;
+    hipStream_t s = h->streams[0];
+    const int R = g.R, Rpad = g.Rpad, n = x.n_folded, depth = mix_depth(n), ntiles = (int)g.tiles.size();
+    h->recs.clear();
+    if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
+            hipLaunchKernelGGL(k_mix_mean, dim3((Rpad + 255) / 256), dim3(256), 0, s, (const double*)x.Mu.p, (const double*)x.wv(), n, Rpad,
+                               x.mu_mix(), x.W());
+            hipLaunchKernelGGL(k_mix_center, dim3((Rpad + 255) / 256, depth), dim3(256), 0, s, (const double*)x.Mu.p,
+                               (const double*)x.wv(), (const double*)x.W(), (const double*)x.mu_mix(), n, Rpad, x.D.p);
+        })) return rc;
+    if (g.want_sigma) {
+        // every upper tile in one launch (launching tile rows one after the other serialises them)
+        if (int rc = prof_launch(h, s, PSOAP_K_GRAD, TILE_FLOPS * ntiles * (double)depth / NB, 0.0, [&] {
+                hipLaunchKernelGGL(k_mix_syrk, dim3(ntiles), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)x.D.p, (size_t)Rpad,
+                                   depth, (const double*)x.Sbar.p, (const double*)x.W(), x.Out.p, g.Rt, x.var_within(), x.var_between());
+            })) return rc;
+    } else {
+        if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
+                hipLaunchKernelGGL(k_mix_var, dim3((Rpad + 255) / 256), dim3(256), 0, s, (const double*)x.D.p, n, Rpad,
+                                   (const double*)x.Sbar.p, (const double*)x.W(), x.var_within(), x.var_between());
+            })) return rc;
+    }
+    // mu_mix | var_within | var_between | W lie together
+    HIP_TRY(hipMemcpyAsync(x.hSmall, x.mu_mix(), sizeof(double) * (3 * (size_t)Rpad + 1), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (Sigma_out)
+        HIP_TRY(hipMemcpy2D(Sigma_out, sizeof(double) * R, x.Out, sizeof(double) * Rpad, sizeof(double) * R, (size_t)R, hipMemcpyDeviceToHost));
+    memcpy(mu_out, x.hSmall.p, sizeof(double) * R);
+    memcpy(var_within_out, x.hSmall.p + Rpad, sizeof(double) * R);
+    memcpy(var_between_out, x.hSmall.p + 2 * (size_t)Rpad, sizeof(double) * R);
+    if (n_folded_out) *n_folded_out = n;
+    if (W_out) *W_out = x.hSmall.p[3 * (size_t)Rpad];
+    return collect_timings(h);
+}
+
+// drop the handle's mixture and its buffers (also freed by psoap_chunk_destroy)
+extern "C" int psoap_chunk_mix_release(psoap_chunk* h)
+{
+    if (!h) FAIL("psoap_chunk_mix_release: null handle");
+    DEVICE_SCOPE(h->device);
+    if (set_dev(h)) return 1;
+    h->xws.reset();
     return 0;
 }
 

@@ -155,6 +155,79 @@ def _retrieve_draws(c, lwls, fl, sigma, lwl, ep, lwl_predict, p_gp, get_Sigma, b
     return out
 
 
+def retrieve_posterior(model, chunk, parameters, flatchain, fix_params, n_samples=64, thin_seed=0, n_pix_predict=None,
+                       get_Sigma=True, baseline=None, draws_per_sample=0, seed=None):
+    """``retrieve_components`` marginalised over the chain instead of taken at one parameter vector: the component spectra
+    under the posterior of the orbit and the hyper-parameters, by the law of total covariance over chain samples
+    (``covariance.predict_mixture``: every sample is predicted and folded on the device).
+
+    ``flatchain`` ``(n, n_free)``: rows in the layout ``utils.convert_vector`` takes, the parameters named in ``fix_params``
+    held at their values in ``parameters``.  ``n_samples`` rows are picked without replacement by
+    ``numpy.random.default_rng(thin_seed)`` (all rows when there are fewer) and weigh the same.  The orbits of all of them
+    are evaluated in one batched device call.
+
+    Every sample is predicted on ONE grid: ``retrieve_components``' own, taken at ``parameters`` -- ``linspace(min, max)``
+    of the primary's rest-frame range at the point estimate.  A per-sample grid would make the means incomparable: the
+    between-sample term is the scatter of ``mu_s`` at fixed rest wavelengths.
+
+    Returns the dict ``retrieve_components`` returns (``save_components`` works on it unchanged; ``lwls`` are the grids at
+    ``parameters``), where ``sigma_f`` (, ``_g``, ``_h``) now carry the orbit's and the hyper-parameters' uncertainty, and
+    beside it ``sigma_within_f`` / ``sigma_between_f`` (, ``_g``, ``_h``) -- the square roots of the two terms' diagonals,
+    ``sigma_f**2 = sigma_within_f**2 + sigma_between_f**2`` --, ``n_folded`` and ``skipped`` (positions among the picked
+    rows whose data covariance was not positive definite), and ``rows``, the picked chain rows.  ``get_Sigma`` other than
+    True accumulates variances only and ``Sigma`` is None.  With one sample equal to ``parameters`` the result is
+    ``retrieve_components``'.  ``baseline``: as ``retrieve_components``.  ``draws_per_sample > 0`` (needs ``seed`` and
+    ``get_Sigma=True``): ``f_draws`` (, ``g_``, ``h_``), ``(n_folded * draws_per_sample, M)`` each -- draws from the
+    mixture, sample ``s`` with the generator's seed ``seed + s``."""
+    from .utils import convert_vectors
+    if model not in ("SB2", "ST3", "SB1"):
+        raise ValueError("retrieve_posterior supports SB1, SB2 and ST3 (the models the reference has scripts for)")
+    if isinstance(get_Sigma, str) and get_Sigma != "diag":
+        raise ValueError('get_Sigma must be True, False or "diag"')
+    c = N_COMPONENTS[model]
+    reg = registered_params[model]
+    chain = np.atleast_2d(np.asarray(flatchain, dtype=np.float64))
+    n = chain.shape[0]
+    rows = np.arange(n) if n <= int(n_samples) else np.sort(np.random.default_rng(thin_seed).choice(n, size=int(n_samples), replace=False))
+    p_orb, p_gp = convert_vectors(chain[rows], model, fix_params, **{k: parameters[k] for k in fix_params})
+    mask = np.asarray(chunk.mask, dtype=bool)
+    if np.ndim(chunk.wl) != 2:
+        raise ValueError("retrieve_posterior needs the 2-D chunk: call it before apply_mask()")
+    lwl2d = np.log(np.asarray(chunk.wl, dtype=np.float64))
+    # the point estimate rides along as the last orbit of the batch: its primary fixes the grid
+    p0 = np.array([[parameters[k] for k in reg[:n_params_orb[model]]]], dtype=np.float64)
+    vel = orbit.velocities(model, np.concatenate([p_orb, p0]), np.asarray(chunk.date1D))      # (S + 1, c, n_epochs)
+    ep = epoch_index_of(mask)
+    lwl = lwl2d[mask]
+    lwls_all = lwl[None, None, :] + (-vel[:, :, ep]) / c_kms
+    lwls0 = lwls_all[-1]
+    fl = np.asarray(chunk.fl, dtype=np.float64)[mask]
+    sigma = np.asarray(chunk.sigma, dtype=np.float64)[mask]
+    M = int(n_pix_predict) if n_pix_predict is not None else 2 * int(chunk.n_pix)
+    lwl_predict = np.linspace(np.min(lwls0[0]), np.max(lwls0[0]), num=M)
+    marg = None
+    if baseline is not None:
+        marg = {"x": lwl, "epoch_index": ep, "order": int(baseline["order"]), "prior_sd": baseline["sd"],
+                "weight": _baseline_weight(baseline, fl)}
+    full = get_Sigma is True
+    res = covariance.predict_mixture(lwls_all[:-1], fl, sigma, [lwl_predict] * c, [0.0] * c, p_gp, mode=2 if c == 1 else 0,
+                                     baseline=marg, want_sigma=full, draws_per_sample=draws_per_sample, seed=seed)
+    mu, Sigma = res["mu"], res["Sigma"]
+    out = {"wl_predict": np.exp(lwl_predict), "lwl_predict": lwl_predict, "mu": mu, "Sigma": Sigma, "lwls": lwls0,
+           "n_folded": res["n_folded"], "skipped": res["skipped"], "rows": rows}
+    sd = np.sqrt(np.diag(Sigma)) if full else np.sqrt(res["var_within"] + res["var_between"])
+    sd_w, sd_b = np.sqrt(res["var_within"]), np.sqrt(res["var_between"])
+    for k in range(c):
+        sl = slice(k * M, (k + 1) * M)
+        out["mu_" + _NAMES[k]] = mu[sl]
+        out["sigma_" + _NAMES[k]] = sd[sl]
+        out["sigma_within_" + _NAMES[k]] = sd_w[sl]
+        out["sigma_between_" + _NAMES[k]] = sd_b[sl]
+        if "draws" in res:
+            out[_NAMES[k] + "_draws"] = np.ascontiguousarray(res["draws"][:, sl])
+    return out
+
+
 def save_components(result, outdir):
     """Write ``f.npy``, ``g.npy`` (, ``h.npy``), ``mu.npy``, ``Sigma.npy`` into ``outdir`` (the scripts'
     ``plots_chunk_*`` directory), and ``f_draws.npy``, ``g_draws.npy`` (, ``h_draws.npy``) where the result has draws."""
