@@ -211,6 +211,56 @@ int psoap_chunk_fisher(psoap_chunk *h, int c, const double *lwl, const double *g
                        double *fisher, double *fisher_mu);
 int psoap_chunk_fisher_release(psoap_chunk *h);
 
+/* ---- Fisher information of the per-epoch radial velocities -------------------------
+ * For one matrix (lwl (c, N), gp (2c), as for psoap_chunk_fisher) and the epoch of
+ * every pixel (epoch (N), values in [0, n_epochs), any pixel order, an epoch may have no
+ * pixel): the information of the c n_epochs velocities v[k][e] behind the grids
+ * lwl[k][n] = lwl0[n] - v[k][epoch[n]] / c_kms, AT FIXED hyper-parameters,
+ *   fisher (c E, c E)  F[(k, e), (j, f)] = 1/2 tr(K^-1 K_(k,e) K^-1 K_(j,f)), row
+ *                      k * n_epochs + e (grad_vel's order), both triangles, F == F^T
+ *                      bit for bit --
+ * what psoap_chunk_fisher gives for the c E tangents dx = -1 / c_kms on component k,
+ * epoch e, without its limit of 32 and at c + c (c + 1) / 2 dense products whatever
+ * n_epochs is: a velocity tangent touches only the rows and columns of one epoch
+ * (csrc/vel_fisher_kernels.hpp; (2 c + c (c + 1)) N^3 flops beyond the factorisation
+ * of [K | I] and K^-1).  F has c null directions, the constant shift of each component
+ * (the kernel is stationary): velocities are determined up to one offset per
+ * component.  An epoch without pixels gives an exactly-zero row and column.  The cross
+ * terms with the hyper-parameters stay with psoap_chunk_fisher.
+ * No atomics, every sum in an order fixed by (N, c, epoch): the same arguments give the
+ * same bits.
+ * Conventions: a negative hyper-parameter or a matrix that is not positive definite
+ * gives NaN in every entry and status 0; n_epochs < 1 or > 2048, an epoch index out of
+ * range and an open stream on the handle are refused (non-zero status,
+ * psoap_last_error).
+ * Workspace: K^-1 in the Fisher workspace (8 Npad^2 bytes, psoap_chunk_fisher_release)
+ * and, of its own, 16 c Npad^2 bytes (Dv_k, Z_k) + 4 c (c + 1) S^2 + 8 (c E)^2 bytes
+ * (S: the slots of psoap_vel_fisher_plan), allocated by the first call, kept with the
+ * handle and freed by psoap_chunk_fisher_vel_release or psoap_chunk_destroy.  S is
+ * about Npad / 128 + n_epochs for an epoch-major chunk; for pixels in no epoch order it
+ * is at most min(Npad, Npad / 128 * n_epochs), the bin sums then reach 4 c (c + 1) Npad^2
+ * bytes and the binning epilogue up to 128 x 128 passes per tile (estimated at tenths of
+ * a second to a second per call at N = 6000 .. 8192; csrc/vel_fisher_kernels.hpp): sort
+ * the pixels by epoch.  n_epochs is capped at 2048 because fisher grows as (c E)^2
+ * (302 MB at c = 3 there).  The
+ * handle's uploaded batches, their results and the likelihood workspaces are left as
+ * they are.  Launches are booked under PSOAP_K_FILL (Dv_k), GRAD (K^-1 and the
+ * products), MISC (the rest) and the factorisation's own classes. */
+int psoap_chunk_fisher_vel(psoap_chunk *h, int c, const double *lwl, const double *gp,
+                           int n_epochs, const int32_t *epoch, double *fisher);
+int psoap_chunk_fisher_vel_release(psoap_chunk *h);
+/* host twin of that call's plan (pure host): a slot is one of the distinct epochs of a
+ * 128-row tile row, in ascending epoch id, numbered through the tile rows.  n_slots;
+ * slot_of_out (N) the slot of every pixel; slot_first_out (ceil(N / 128) + 1);
+ * slot_epoch_out (min(max_slots, n_slots)) the epoch of a slot; the tiles of a cross
+ * product (all) and of a symmetrised one (upper); the bytes of every device buffer
+ * beyond [K | I].  Any output may be NULL.  Returns 2 where psoap_chunk_fisher_vel
+ * refuses c, n_epochs or epoch, and for N < 1. */
+int psoap_vel_fisher_plan(int c, int N, int n_epochs, const int32_t *epoch, int *n_slots,
+                          int *slot_of_out, int *slot_first_out, int *slot_epoch_out,
+                          int max_slots, int *n_tiles_all, int *n_tiles_upper,
+                          long long *bytes);
+
 /* ---- leave-one-out cross-validation of the likelihood -----------------------------
  * For one matrix (lwl (c, N), gp (2c), as for psoap_chunk_fisher), with r = fl - mu_GP,
  * A = K^-1 and alpha = A r (K as psoap_lnlike builds it, noise on the diagonal: pix_var

@@ -243,6 +243,33 @@ class ChunkHandle:
         """Free the Fisher workspace (24 Npad^2 bytes); the next ``fisher`` allocates it again."""
         check(self._L.psoap_chunk_fisher_release(self._h), "psoap_chunk_fisher_release")
 
+    def fisher_vel(self, lwls, gp, epoch_index, n_epochs: int | None = None) -> np.ndarray:
+        """Fisher information of the per-epoch radial velocities at ``lwls`` (c, N), ``gp`` (2c,) (include/psoap_gp.h:
+        psoap_chunk_fisher_vel): ``epoch_index`` (N,) with values in ``[0, n_epochs)``, any pixel order (``n_epochs``
+        defaults to ``max(epoch_index) + 1``) -> ``F (c E, c E)``, row ``k * E + e`` as ``grad_vel``, symmetric bit for bit:
+        what ``fisher`` gives for the ``c E`` tangents ``dx = -1/c_kms`` on component k, epoch e, for any number of epochs.
+        The information of the velocities AT FIXED hyper-parameters; it has ``c`` null directions, the constant shift of
+        each component; an epoch without pixels gives an exactly-zero row and column.  A negative hyper-parameter or a
+        matrix that is not positive definite gives NaN in every entry.  Always under the plain ``K``, also on a handle with
+        a baseline."""
+        lwls = as_f64(np.atleast_2d(lwls))
+        c = lwls.shape[0]
+        lwls = as_f64(lwls, (c, self.N))
+        gp = as_f64(gp, (2 * c,))
+        ep = np.ascontiguousarray(epoch_index, dtype=np.int32)
+        if ep.shape != (self.N,):
+            raise ValueError("epoch_index must have shape (N,)")
+        ne = int(ep.max()) + 1 if n_epochs is None else int(n_epochs)
+        F = np.empty((c * max(ne, 0),) * 2)
+        check(self._L.psoap_chunk_fisher_vel(self._h, c, dptr(lwls), dptr(gp), ne, ep.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                             dptr(F)), "psoap_chunk_fisher_vel")
+        return F
+
+    def fisher_vel_release(self):
+        """Free the workspace of ``fisher_vel`` beyond the Fisher workspace's K^-1 (16 c Npad^2 bytes and the bin sums); the
+        next ``fisher_vel`` allocates it again."""
+        check(self._L.psoap_chunk_fisher_vel_release(self._h), "psoap_chunk_fisher_vel_release")
+
     def loo(self, lwls, gp, mu_GP: float = 1.0, epoch_index=None, n_epochs: int | None = None) -> "LooResult":
         """Leave-one-out cross-validation of the likelihood at ``lwls`` (c, N), ``gp`` (2c,) (include/psoap_gp.h:
         psoap_chunk_loo): every pixel predicted from all the others and, with ``epoch_index`` (N,), every epoch from all the

@@ -578,6 +578,34 @@ def velocity_gradient(grad_lwl, epoch_index, n_epochs):
     return (-out / c_kms).reshape(g.shape[:-1] + (int(n_epochs),))
 
 
+def velocity_information(lwls, fl, sigma, gp, epoch_index):
+    """The ``(c E, c E)`` Fisher information of the per-epoch radial velocities ``v[c, e]`` of one chunk, row ``c * E + e``
+    (the order of ``velocity_gradient``, ``E = max(epoch_index) + 1``), evaluated on the device through the cached handle
+    (``ChunkHandle.fisher_vel``): the second-order half of ``velocity_gradient``, free of any orbit model.  It is the
+    information AT FIXED hyper-parameters and has ``c`` null directions, the constant shift of each component: velocities
+    are determined up to one offset per component.  It does not depend on ``fl``, which only names the cached chunk.
+    Degenerate input follows ``fisher_information``: a negative hyper-parameter or a matrix that is not positive definite
+    gives NaN in every entry."""
+    gp = [float(g) for g in gp]
+    lw = np.stack([as_f64(w) for w in np.atleast_2d(lwls)])
+    if len(gp) != 2 * lw.shape[0]:
+        raise ValueError(f"gp must hold {2 * lw.shape[0]} values for {lw.shape[0]} component(s)")
+    ep = np.asarray(epoch_index, dtype=np.int64)
+    if ep.shape != lw.shape[1:] or ep.size == 0 or ep.min() < 0:
+        raise ValueError("epoch_index must hold one non-negative epoch per pixel")
+    T = lw.shape[0] * (int(ep.max()) + 1)
+    if any(g < 0.0 for g in gp):
+        return np.full((T, T), np.nan)
+    if any(l == 0.0 for l in gp[1::2]):
+        raise ZeroDivisionError("float division")
+    if not _matrix_is_finite(lw, sigma, gp):
+        raise ValueError(_NONFINITE)
+    h = _chunk_for(fl, sigma)
+    if not hasattr(h, "fisher_vel"):
+        raise _lib.PsoapError("velocity_information needs the device in this process (PSOAP_GPU_SERVER serves values only)")
+    return h.fisher_vel(lw, gp, ep)
+
+
 GP_LOWER_BOUND = 1e-6       # optimize_GP keeps every amplitude and length scale at or above this
 
 

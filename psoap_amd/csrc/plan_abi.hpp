@@ -12,6 +12,7 @@
 #include "draw_rng.hpp"
 #include "mix_plan.hpp"
 #include "sky_rules.hpp"
+#include "vel_fisher_plan.hpp"
 
 using namespace psoap;
 
@@ -278,6 +279,28 @@ extern "C" int psoap_mix_plan(int R, int S_max, int want_sigma, int* Rpad, int* 
     if (n_tiles) *n_tiles = (int)g.tiles.size();
     if (tiles_out)
         for (int t = 0; t < (int)g.tiles.size() && t < max_tiles; ++t) tiles_out[2 * t] = g.tiles[(size_t)t].ti, tiles_out[2 * t + 1] = g.tiles[(size_t)t].tj;
+    if (bytes) *bytes = g.bytes;
+    return 0;
+}
+
+// Pure host function: the plan of psoap_chunk_fisher_vel for a chunk of N pixels with the epoch index `epoch` (N values in
+// [0, n_epochs)) and c components (vel_fisher_plan.hpp) -- the number of slots (the distinct epochs of every 128-row tile
+// row), slot_of_out (N): the slot of every pixel, slot_first_out (ceil(N / 128) + 1), slot_epoch_out (min(max_slots, n_slots)),
+// the numbers of tiles of the two product launches and the bytes of every device buffer beyond [K | I].  Any output may be null.
+extern "C" int psoap_vel_fisher_plan(int c, int N, int n_epochs, const int32_t* epoch, int* n_slots, int* slot_of_out,
+                                     int* slot_first_out, int* slot_epoch_out, int max_slots, int* n_tiles_all, int* n_tiles_upper,
+                                     long long* bytes)
+{
+    if (const char* why = vel_fisher_check(c, N, n_epochs, epoch)) FAIL(std::string("psoap_vel_fisher_plan: ") + why);
+    VelFisherPlan g;
+    vel_fisher_plan(c, N, n_epochs, epoch, g);
+    if (n_slots) *n_slots = g.S;
+    if (slot_of_out) memcpy(slot_of_out, g.slot_of.data(), sizeof(int) * (size_t)N);
+    if (slot_first_out) memcpy(slot_first_out, g.slot_first.data(), sizeof(int) * ((size_t)g.P + 1));
+    if (slot_epoch_out)
+        for (int a = 0; a < g.S && a < max_slots; ++a) slot_epoch_out[a] = g.slot_epoch[(size_t)a];
+    if (n_tiles_all) *n_tiles_all = (int)g.tiles_all.size();
+    if (n_tiles_upper) *n_tiles_upper = (int)g.tiles_upper.size();
     if (bytes) *bytes = g.bytes;
     return 0;
 }

@@ -33,6 +33,7 @@
 #include "grad_kernels.hpp"
 #include "orbit_grad_kernels.hpp"
 #include "fisher_kernels.hpp"
+#include "vel_fisher_kernels.hpp"
 #include "loo_kernels.hpp"
 #include "marg_kernels.hpp"
 #include "marg_grad_kernels.hpp"
@@ -104,7 +105,7 @@ struct BatchSlot {
     Event evEval;              // compute stream: last evaluation that read this slot complete
 };
 
-namespace psoap { struct PredictWs; struct GradWs; struct FisherWs; struct LooWs; struct MargWs; }
+namespace psoap { struct PredictWs; struct GradWs; struct FisherWs; struct VelFisherWs; struct LooWs; struct MargWs; }
 
 // Streamed evaluation (dag_kernel.hpp, "Streamed evaluation"): one resident launch of the persistent kernel, matrices
 // come and go through `lanes` workspaces of the handle.  Host side: lane allocation, the submission ring in pinned
@@ -237,6 +238,8 @@ struct psoap_chunk {
     std::unique_ptr<psoap::GradWs> gws;
     // Fisher workspace (allocated by the first psoap_chunk_fisher; psoap_chunk_fisher_release)
     std::unique_ptr<psoap::FisherWs> fws;
+    // epoch-velocity Fisher workspace beyond fws's K^-1 (allocated by the first psoap_chunk_fisher_vel; psoap_chunk_fisher_vel_release)
+    std::unique_ptr<psoap::VelFisherWs> vws;
     // leave-one-out workspace (allocated by the first psoap_chunk_loo; psoap_chunk_loo_release)
     std::unique_ptr<psoap::LooWs> lws;
     // continuum-marginalised likelihood: the baseline as psoap_chunk_set_baseline took it (host), and its device side and
@@ -326,6 +329,7 @@ static int configure_kernels(int device)
     HIP_TRY(predict_configure_kernels());
     HIP_TRY(grad_configure_kernels());
     HIP_TRY(fisher_configure_kernels());
+    HIP_TRY(vel_fisher_configure_kernels());
     HIP_TRY(loo_configure_kernels());
     HIP_TRY(marg_configure_kernels());
     HIP_TRY(marg_grad_configure_kernels());
@@ -2622,6 +2626,102 @@ extern "C" int psoap_chunk_fisher_marg(psoap_chunk* h, int c, const double* lwl,
 extern "C" int psoap_chunk_fisher_release(psoap_chunk* h)
 {
     return release_ws(h, [&] { h->fws.reset(); });
+}
+
+// ---- Fisher information of the per-epoch velocities (vel_fisher_kernels.hpp) ------------------------
+// One matrix through the gradient's workspace and factorisation and the Fisher workspace's K^-1, as fisher_run; then Dv_k and
+// Z_k = K^-1 Dv_k for every component, the c (c + 1) / 2 products X_kj with their binning epilogue, and the finishing sums --
+// on the handle's first stream behind whatever the handle has in flight; neither the proposal slots nor the workspaces of
+// the likelihood paths are touched.
+extern "C" int psoap_chunk_fisher_vel(psoap_chunk* h, int c, const double* lwl, const double* gp, int n_epochs,
+                                      const int32_t* epoch, double* fisher)
+{
+    if (!h || !lwl || !gp || !epoch || !fisher) FAIL("psoap_chunk_fisher_vel: bad arguments");
+    if (const char* why = vel_fisher_check(c, h->N, n_epochs, epoch)) FAIL(std::string("psoap_chunk_fisher_vel: ") + why);
+    if (h->stream.open) FAIL("psoap_chunk_fisher_vel: the handle has an open stream (psoap_stream_close first)");
+    DEVICE_SCOPE(h->device);
+    if (int rc = enter_device(h->device)) return rc;
+    hipStream_t s = h->streams[0];
+    const Factored fac = factored(h, false, 1);
+    const int N = h->N, Npad = h->Npad, P = h->P, ld = fac.ld;
+    const size_t sq = (size_t)Npad * Npad, CN = (size_t)c * N, T = (size_t)c * n_epochs;
+    const int ntiles = P * (P + 1) / 2;
+    VelFisherPlan pl;
+    vel_fisher_plan(c, N, n_epochs, epoch, pl);
+    std::vector<int> packed;
+    vel_plan_pack(pl, packed);
+    const VelPlanOffsets off = vel_plan_offsets(Npad, P, pl.S, n_epochs);
+    if (!h->fws) h->fws.reset(new FisherWs());
+    if (!h->vws) h->vws.reset(new VelFisherWs());
+    if (int rc = factored_ws_need(h, fac, s, false, false)) return rc;
+    GradWs& w = *h->gws;
+    FisherWs& f = *h->fws;
+    VelFisherWs& v = *h->vws;
+    HIP_TRY(f.Kinv.need(sq));
+    HIP_TRY(f.Info.need(1));
+    HIP_TRY(v.Dv.need((size_t)c * sq));
+    HIP_TRY(v.Z.need((size_t)c * sq));
+    HIP_TRY(v.Part.need((size_t)pl.part_doubles));
+    HIP_TRY(v.F.need(T * T));
+    HIP_TRY(v.Plan.need(packed.size()));
+    HIP_TRY(v.Epoch.need((size_t)N));
+    h->recs.clear();
+    HIP_TRY(hipMemcpyAsync(w.Lwl, lwl, sizeof(double) * CN, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(w.Gp, gp, sizeof(double) * 2 * c, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(v.Plan, packed.data(), sizeof(int) * packed.size(), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(v.Epoch, epoch, sizeof(int32_t) * (size_t)N, hipMemcpyHostToDevice, s));
+    // (F does not depend on the data: any mu_GP)
+    if (int rc = factor_group(h, fac, s, 1, c, 0.0, false)) return rc;
+    double kunits = 0.0;
+    for (int tj = 0; tj < P; ++tj) kunits += (double)(tj + 1) * (P - tj);
+    if (int rc = prof_launch(h, s, PSOAP_K_GRAD, TILE_FLOPS * kunits, 0.0, [&] {
+            hipLaunchKernelGGL(k_fisher_kinv, dim3(ntiles), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)w.A.p, ld, Npad, P,
+                               f.Kinv.p);
+        })) return rc;
+    if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
+            hipLaunchKernelGGL(k_acc_total, dim3(1), dim3(1), 0, s, (const MatAcc*)w.Acc.p, P, f.Info.p);
+        })) return rc;
+    const int* plan = v.Plan.p;
+    if (int rc = prof_launch(h, s, PSOAP_K_FILL, 0.0, 8.0 * (double)sq * c, [&] {
+            hipLaunchKernelGGL(k_vel_dv_fill, dim3(P * P, c), dim3(256), 0, s, v.Dv.p, sq, Npad, N, P, (const double*)w.Lwl.p,
+                               (const double*)w.Gp.p, (const int*)v.Epoch.p);
+        })) return rc;
+    if (int rc = prof_launch(h, s, PSOAP_K_GRAD, TILE_FLOPS * pl.tile_units, 0.0, [&] {
+            hipLaunchKernelGGL(k_vel_z, dim3(P * P, c), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)f.Kinv.p,
+                               (const double*)v.Dv.p, sq, Npad, plan + off.tiles_all, v.Z.p);
+            for (int k = 0; k < c; ++k)
+                for (int j = 0; j <= k; ++j) {
+                    const double *Zk = v.Z.p + (size_t)k * sq, *Zj = v.Z.p + (size_t)j * sq;
+                    const double *Dk = v.Dv.p + (size_t)k * sq, *Dj = v.Dv.p + (size_t)j * sq;
+                    double* part = v.Part.p + (size_t)(k * (k + 1) / 2 + j) * pl.S * pl.S;
+                    if (k == j)
+                        hipLaunchKernelGGL(k_vel_contract<true>, dim3(ntiles), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s,
+                                           (const double*)f.Kinv.p, Zk, Zj, Dk, Dj, Npad, pl.S, plan + off.tiles_upper,
+                                           plan + off.slot_of, plan + off.slot_first, part);
+                    else
+                        hipLaunchKernelGGL(k_vel_contract<false>, dim3(P * P), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s,
+                                           (const double*)f.Kinv.p, Zk, Zj, Dk, Dj, Npad, pl.S, plan + off.tiles_all,
+                                           plan + off.slot_of, plan + off.slot_first, part);
+                }
+        })) return rc;
+    if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
+            hipLaunchKernelGGL(k_vel_finish, dim3((unsigned)((T * T + 63) / 64)), dim3(64), 0, s, (const double*)v.Part.p, pl.S, c,
+                               n_epochs, plan + off.epoch_ptr, plan + off.epoch_slots, plan + off.slot_block, v.F.p);
+        })) return rc;
+    MatAcc info;
+    HIP_TRY(hipMemcpyAsync(fisher, v.F, sizeof(double) * T * T, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&info, f.Info, sizeof info, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (collect_timings(h)) return 1;
+    // the conventions of the likelihood: a negative hyper-parameter or a matrix that is not positive definite -> no information
+    if (info.info != 0.0 || proposal_refused(gp, c, 0))
+        for (size_t k = 0; k < T * T; ++k) fisher[k] = NAN;
+    return 0;
+}
+
+extern "C" int psoap_chunk_fisher_vel_release(psoap_chunk* h)
+{
+    return release_ws(h, [&] { h->vws.reset(); });
 }
 
 // ---- leave-one-out cross-validation of the likelihood (loo_kernels.hpp) ------------------------------

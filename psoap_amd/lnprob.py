@@ -250,6 +250,41 @@ class ChunkWorker:
         p_orb, p_gp = convert_vectors(np.atleast_2d(p), self.model, self.fix_params, **self.defaults)
         return self.loo_orbits(p_orb[0], p_gp[0], mu_GP)
 
+    # -- per-epoch velocities free of any orbit (include/psoap_gp.h: psoap_chunk_fisher_vel) ---------------------------
+    def _grids_at(self, vel, what):
+        """a free velocity table (c, E) -> ``(lwls (c, N), too_fast)``, the grids shifted as ``shifted_grids`` shifts them"""
+        self._no_baseline(what)
+        if os.environ.get("PSOAP_GPU_SERVER", "").strip().lower() not in ("", "0"):
+            raise _lib.PsoapError(f"{what} needs the device in this process (PSOAP_GPU_SERVER serves values only)")
+        from .data import c_kms
+        vel = as_f64(vel, (N_COMPONENTS[self.model], self.dates.shape[0]))
+        fast = bool(np.any(np.abs(vel) >= c_kms))
+        return self.lwl[None, :] + (-vel[:, self.epoch_index]) / c_kms, fast
+
+    def fisher_vel_at(self, vel, p_gp):
+        """The ``(c E, c E)`` information of the per-epoch velocities of this chunk at the free velocity table ``vel``
+        (c, E) and GP parameters ``p_gp`` (2c,), row ``c * E + e`` (``ChunkHandle.fisher_vel``): AT FIXED hyper-parameters,
+        with one null direction per component.  Any ``|v| >= c_kms``, a negative hyper-parameter or a matrix that is not
+        positive definite gives NaN in every entry.  A worker with a baseline is refused: the variant under the
+        marginalised continuum, with ``(K + H Lambda H^T)^-1`` in place of ``K^-1``, is not built yet."""
+        lwls, fast = self._grids_at(vel, "fisher_vel_at")
+        c, E = N_COMPONENTS[self.model], self.dates.shape[0]
+        if fast:
+            return np.full((c * E, c * E), np.nan)
+        return self.handle.fisher_vel(lwls, as_f64(np.ravel(p_gp), (2 * c,)), self.epoch_index, E)
+
+    def lnlike_grad_vel(self, vel, p_gp, mu_GP: float = 1.0):
+        """``(lnp, grad_vel (c, E))`` of this chunk at the free velocity table ``vel`` (c, E): ``ChunkHandle.lnlike_grad``
+        folded by ``covariance.velocity_gradient``.  Any ``|v| >= c_kms``, a negative hyper-parameter or a matrix that is
+        not positive definite gives ``-inf`` and NaN.  A worker with a baseline is refused, as for ``fisher_vel_at``."""
+        from .covariance import velocity_gradient
+        lwls, fast = self._grids_at(vel, "lnlike_grad_vel")
+        c, E = N_COMPONENTS[self.model], self.dates.shape[0]
+        if fast:
+            return -np.inf, np.full((c, E), np.nan)
+        lnp, _g_gp, g_lwl, _g_mu = self.handle.lnlike_grad(lwls, as_f64(np.ravel(p_gp), (2 * c,)), mu_GP)
+        return float(lnp), velocity_gradient(g_lwl, self.epoch_index, E)
+
 
 def baseline_fit(workers, p, mu_GP=1.0):
     """The continuum of every epoch at the fitted vector ``p``, per chunk: a list, in the order of ``workers`` (each made
@@ -387,3 +422,140 @@ def optimize_orbit(workers, p0, bounds=None, mu_GP=1.0, ftol=1e-10, full_output=
 
     res = minimize(func, x0, jac=True, method="L-BFGS-B", bounds=bounds, options={"ftol": ftol})
     return res if full_output else res["x"]
+
+
+# ---- per-epoch radial velocities with error bars, free of any orbit model --------------------------------------------------
+def velocity_pinv(F, c, n_epochs, seen):
+    """``F^+`` on the complement of the ``c`` per-component constant vectors and of the epochs nobody sees (``seen`` (E,)
+    bool): with ``Q`` an orthonormal basis of that complement (per component the Helmert contrasts of the seen epochs),
+    ``Q (Q^T F Q)^-1 Q^T``.  Rows and columns of unseen epochs are zero."""
+    n = c * n_epochs
+    idx = np.flatnonzero(np.asarray(seen, dtype=bool))
+    cols = []
+    for k in range(c):
+        for j in range(1, idx.size):
+            v = np.zeros(n)
+            v[k * n_epochs + idx[:j]] = 1.0
+            v[k * n_epochs + idx[j]] = -float(j)
+            cols.append(v / np.sqrt(j * (j + 1.0)))
+    if not cols:
+        return np.zeros((n, n))
+    Q = np.array(cols).T
+    M = Q.T @ as_f64(F) @ Q
+    return Q @ np.linalg.solve(0.5 * (M + M.T), Q.T)
+
+
+def velocity_scoring(value, grad_info, vel0, seen, max_iter=20, tol=1e-10):
+    """Fisher scoring on a velocity table from ``vel0`` (c, E): ``value(vel) -> lnp`` and ``grad_info(vel) -> (g (c, E),
+    F (c E, c E))`` are the summed likelihood, its gradient and its information.  Per iteration ``delta = F^+ g``
+    (``velocity_pinv``), the step halved until the value does not decrease; stops when the Newton decrement
+    ``g^T F^+ g <= tol``.  -> dict with ``vel``, ``cov`` (F^+ at ``vel``), ``n_iter``, ``decrement``, ``lnp_start``, ``lnp``,
+    ``converged``.  The loop of ``epoch_velocities``; the tests run it on a float64 CPU twin as well."""
+    vel = as_f64(vel0).copy()
+    c, E = vel.shape
+    lnp = lnp0 = float(value(vel))
+    it = 0
+    while True:
+        g, F = grad_info(vel)
+        if not (np.isfinite(lnp) and np.all(np.isfinite(g)) and np.all(np.isfinite(F))):
+            raise np.linalg.LinAlgError("the likelihood, its gradient or its information is not finite at the velocity table")
+        cov = velocity_pinv(F, c, E, seen)
+        gv = as_f64(g).reshape(-1)
+        delta = cov @ gv
+        dec = float(gv @ delta)
+        if dec <= tol or it >= max_iter:
+            return {"vel": vel, "cov": cov, "n_iter": it, "decrement": dec, "lnp_start": lnp0, "lnp": lnp, "converged": dec <= tol}
+        step, moved = 1.0, False
+        for _ in range(60):
+            trial = vel + step * delta.reshape(c, E)
+            v = float(value(trial))
+            if v >= lnp:
+                vel, lnp, moved = trial, v, True
+                break
+            step *= 0.5
+        it += 1
+        if not moved:
+            return {"vel": vel, "cov": cov, "n_iter": it, "decrement": dec, "lnp_start": lnp0, "lnp": lnp, "converged": False}
+
+
+class EpochVelocities:
+    """What ``epoch_velocities`` returns: ``dates`` (E,), ``vel`` (c, E), ``cov`` (c E, c E) ``= F^+``, ``sigma`` (c, E) (NaN
+    for an epoch no chunk sees), ``n_iter``, ``decrement``, ``lnp_start``, ``lnp``, ``converged``.  The errors are those of
+    RELATIVE velocities at FIXED hyper-parameters: the constant shift of each component is a null direction of the
+    likelihood and is never moved -- each component's mean over the seen epochs stays the orbit's."""
+
+    def __init__(self, dates, fit, seen):
+        self.dates = as_f64(dates)
+        self.vel, self.cov = fit["vel"], fit["cov"]
+        c, E = self.vel.shape
+        self.seen = np.asarray(seen, dtype=bool)
+        self.sigma = np.where(self.seen[None, :], np.sqrt(np.maximum(np.diag(self.cov), 0.0)).reshape(c, E), np.nan)
+        self.n_iter, self.decrement, self.converged = fit["n_iter"], fit["decrement"], fit["converged"]
+        self.lnp_start, self.lnp = fit["lnp_start"], fit["lnp"]
+
+    def write_table(self, fname):
+        """``date, v_0, sigma_0, v_1, sigma_1, ...`` per epoch, one row each, with ``np.savetxt``"""
+        cols = [self.dates]
+        for k in range(self.vel.shape[0]):
+            cols += [self.vel[k], self.sigma[k]]
+        head = "date " + " ".join(f"v_{k} sigma_{k}" for k in range(self.vel.shape[0]))
+        np.savetxt(fname, np.column_stack(cols), header=head)
+        return fname
+
+
+def epoch_velocities(workers, p, max_iter=20, tol=1e-10, mu_GP=1.0, vel0=None):
+    """The radial velocity of every component at every epoch with its error bar, free of any orbit model: Fisher scoring
+    on the velocity table of the SUM of the workers' likelihoods, from the orbit's velocities at the fitted vector ``p``
+    with the GP parameters of ``p`` held fixed.  The workers must share ``dates``.  Per iteration the summed
+    ``g = sum_k grad_vel_k`` (``ChunkWorker.lnlike_grad_vel``) and ``F = sum_k F_k`` (``ChunkWorker.fisher_vel_at``), the
+    step ``F^+ g`` with the pseudo-inverse taken on the complement of the ``c`` per-component constant vectors and of the
+    epochs no chunk sees (a chunk in which an epoch is fully masked contributes zeros for it), halved until the summed
+    likelihood (``ChunkHandle.upload_velocities``) does not decrease; it stops when the Newton decrement
+    ``g^T F^+ g <= tol`` -- dimensionless, half of it the expected gain in ``lnp``: every velocity is then within
+    ``sqrt(tol)`` of its error bar from the stationary point.  -> ``EpochVelocities``.
+
+    The errors are those of RELATIVE velocities AT FIXED hyper-parameters: each component's constant shift is a null
+    direction (the kernel is stationary) and its plain mean over the seen epochs stays the orbit's (the plain mean, not a
+    weighted one, on purpose: the null vector of ``F`` is the constant vector, and a step in its complement keeps that mean); the cross information with
+    ``(amp, l)`` stays with ``fisher_information``.  Workers with a baseline are refused: the variant under the marginalised
+    continuum is not built yet.  ``vel0`` (c, E): a table to start from instead of the orbit's (an earlier fit; its
+    per-component means are then the ones that stay).  Fisher scoring converges linearly -- the information is the expected
+    curvature, not the data's own -- so ``converged`` can be False after ``max_iter``; the result then still never lowered
+    ``lnp``, and ``decrement`` says how far it is."""
+    from .orbit import velocities
+    workers = list(workers) if isinstance(workers, (list, tuple)) else [workers]
+    w0 = workers[0]
+    if os.environ.get("PSOAP_GPU_SERVER", "").strip().lower() not in ("", "0"):
+        raise _lib.PsoapError("epoch_velocities needs the device in this process (PSOAP_GPU_SERVER serves values only)")
+    for w in workers:
+        w._no_baseline("epoch_velocities")
+        if w.model != w0.model or w.dates.shape != w0.dates.shape or not np.array_equal(w.dates, w0.dates):
+            raise ValueError("epoch_velocities: the workers must share the model and the dates")
+    c, E = N_COMPONENTS[w0.model], w0.dates.shape[0]
+    p_orb, p_gp = convert_vectors(np.atleast_2d(p), w0.model, w0.fix_params, **w0.defaults)
+    gp = as_f64(p_gp[0], (2 * c,))
+    if vel0 is None:
+        vel0 = velocities(w0.model, as_f64(p_orb[:1]), w0.dates, device=w0.handle.device)[0]
+    vel0 = as_f64(vel0, (c, E))
+    seen = np.zeros(E, dtype=bool)
+    for w in workers:
+        seen |= np.bincount(w.epoch_index, minlength=E) > 0
+
+    def value(vel):
+        from .data import c_kms
+        if np.any(np.abs(vel) >= c_kms):
+            return -np.inf
+        for w in workers:
+            w.handle.upload_velocities(vel[None], gp[None], mu_GP)
+        for w in workers:
+            w.handle.eval()
+        return float(sum(float(w.handle.fetch()[0]) for w in workers))
+
+    def grad_info(vel):
+        g, F = np.zeros((c, E)), np.zeros((c * E, c * E))
+        for w in workers:
+            g += w.lnlike_grad_vel(vel, gp, mu_GP)[1]
+            F += w.fisher_vel_at(vel, gp)
+        return g, F
+
+    return EpochVelocities(w0.dates, velocity_scoring(value, grad_info, vel0, seen, max_iter, tol), seen)
