@@ -249,7 +249,38 @@ int psoap_chunk_fisher_release(psoap_chunk *h);
 int psoap_chunk_fisher_vel(psoap_chunk *h, int c, const double *lwl, const double *gp,
                            int n_epochs, const int32_t *epoch, double *fisher);
 int psoap_chunk_fisher_vel_release(psoap_chunk *h);
-/* host twin of that call's plan (pure host): a slot is one of the distinct epochs of a
+
+/* ---- observed information of the per-epoch radial velocities ------------------------
+ * Value, gradient, expected and OBSERVED information of the velocities of
+ * psoap_chunk_fisher_vel (same lwl, gp, epoch, n_epochs, same order of rows) at the
+ * handle's flux, from one factorisation:
+ *   lnp                the likelihood, as psoap_lnlike returns it (marg: psoap_chunk_lnlike_marg)
+ *   grad (c E)         dlnL/dv[k][e]
+ *   fisher (c E, c E)  F; with marg = 0 the bits of psoap_chunk_fisher_vel
+ *   observed (c E, c E)  J = -d2 lnL / dv dv = -F + U^T G U + T at the data, E[J] = F;
+ *                      both triangles, J == J^T bit for bit
+ * (csrc/vel_newton_kernels.hpp: one pass over the pixel pairs, c N^2 exponentials, and
+ * 2 N^2 Tpad + N Tpad^2 flops of dense products, Tpad = c E rounded up to 128, beyond the
+ * work of psoap_chunk_fisher_vel).  J has the c null directions of F; it need not be
+ * positive semi-definite away from the optimum.  An epoch without pixels gives
+ * exactly-zero rows, columns and gradient entries.
+ * marg != 0: everything under the baseline of psoap_chunk_set_baseline, K + H Lambda H^T
+ * in place of K and alpha_m in place of alpha (H does not depend on the velocities);
+ * refused without a baseline.
+ * No atomics, every sum in an order fixed by (N, c, epoch): the same arguments give the
+ * same bits.
+ * Conventions: a negative hyper-parameter or a matrix that is not positive definite
+ * gives lnp = -inf, NaN in grad, fisher and observed and status 0; the refusals are
+ * those of psoap_chunk_fisher_vel.
+ * Workspace: that of psoap_chunk_fisher_vel (and under marg of the marginal gradient
+ * for one matrix) and, of its own, 8 (c S Npad + 2 c S^2 + 2 Npad Tpad + Tpad^2 +
+ * (c E)^2 + c E) bytes, freed by psoap_chunk_fisher_vel_release as well.  Launches are
+ * booked under PSOAP_K_FILL (the pair pass), GRAD (the products) and MISC. */
+int psoap_chunk_info_vel(psoap_chunk *h, int marg, int c, const double *lwl,
+                         const double *gp, double mu_GP, int n_epochs, const int32_t *epoch,
+                         double *lnp, double *grad, double *fisher, double *observed);
+/* host twin of the plan of psoap_chunk_fisher_vel, which psoap_chunk_info_vel shares
+ * (pure host): a slot is one of the distinct epochs of a
  * 128-row tile row, in ascending epoch id, numbered through the tile rows.  n_slots;
  * slot_of_out (N) the slot of every pixel; slot_first_out (ceil(N / 128) + 1);
  * slot_epoch_out (min(max_slots, n_slots)) the epoch of a slot; the tiles of a cross

@@ -60,6 +60,8 @@ SIGNATURES = {
     "psoap_chunk_fisher_release": (ctypes.c_int, [_vp]),
     "psoap_chunk_fisher_vel": (ctypes.c_int, [_vp, ctypes.c_int, _dp, _dp, ctypes.c_int, _i32p, _dp]),
     "psoap_chunk_fisher_vel_release": (ctypes.c_int, [_vp]),
+    "psoap_chunk_info_vel": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _dp, _dp, ctypes.c_double, ctypes.c_int, _i32p, _dp, _dp,
+                                           _dp, _dp]),
     "psoap_vel_fisher_plan": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _i32p, _ip, _ip, _ip, _ip, ctypes.c_int,
                                              _ip, _ip, ctypes.POINTER(ctypes.c_longlong)]),
     "psoap_chunk_loo": (ctypes.c_int, [_vp, ctypes.c_int, _dp, _dp, ctypes.c_double, _i32p, ctypes.c_int, _dp, _dp, _dp, _dp, _dp,

@@ -266,9 +266,34 @@ class ChunkHandle:
         return F
 
     def fisher_vel_release(self):
-        """Free the workspace of ``fisher_vel`` beyond the Fisher workspace's K^-1 (16 c Npad^2 bytes and the bin sums); the
-        next ``fisher_vel`` allocates it again."""
+        """Free the workspace of ``fisher_vel`` beyond the Fisher workspace's K^-1 (16 c Npad^2 bytes and the bin sums) and
+        that of ``info_vel``; the next call allocates it again."""
         check(self._L.psoap_chunk_fisher_vel_release(self._h), "psoap_chunk_fisher_vel_release")
+
+    def info_vel(self, lwls, gp, epoch_index, n_epochs: int | None = None, mu_GP: float = 1.0, marg: bool = False):
+        """Value, gradient, expected and OBSERVED information of the per-epoch radial velocities from one factorisation
+        (include/psoap_gp.h: psoap_chunk_info_vel), arguments as ``fisher_vel`` -> ``(lnp, grad (c, E), F (c E, c E),
+        J (c E, c E))``: ``lnp`` as ``lnlike``, ``grad = dlnL/dv`` (``covariance.velocity_gradient`` of ``lnlike_grad``),
+        ``F`` the bits of ``fisher_vel`` and ``J = -d2 lnL / dv dv`` at the handle's flux, ``E[J] = F``, symmetric bit for
+        bit, with the ``c`` null directions of ``F``.  ``marg``: everything under the baseline of ``set_baseline`` (``lnp``
+        as ``lnlike_marg``).  A negative hyper-parameter or a matrix that is not positive definite gives ``-inf`` and NaN in
+        every entry of the three arrays."""
+        lwls = as_f64(np.atleast_2d(lwls))
+        c = lwls.shape[0]
+        lwls = as_f64(lwls, (c, self.N))
+        gp = as_f64(gp, (2 * c,))
+        ep = np.ascontiguousarray(epoch_index, dtype=np.int32)
+        if ep.shape != (self.N,):
+            raise ValueError("epoch_index must have shape (N,)")
+        if marg and getattr(self, "_baseline", None) is None:
+            raise _lib.PsoapError("info_vel: call set_baseline first")
+        ne = int(ep.max()) + 1 if n_epochs is None else int(n_epochs)
+        T = c * max(ne, 0)
+        lnp, g, F, J = np.empty(1), np.empty(T), np.empty((T, T)), np.empty((T, T))
+        check(self._L.psoap_chunk_info_vel(self._h, int(bool(marg)), c, dptr(lwls), dptr(gp), float(mu_GP), ne,
+                                           ep.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), dptr(lnp), dptr(g), dptr(F), dptr(J)),
+              "psoap_chunk_info_vel")
+        return float(lnp[0]), g.reshape(c, max(ne, 0)), F, J
 
     def loo(self, lwls, gp, mu_GP: float = 1.0, epoch_index=None, n_epochs: int | None = None) -> "LooResult":
         """Leave-one-out cross-validation of the likelihood at ``lwls`` (c, N), ``gp`` (2c,) (include/psoap_gp.h:

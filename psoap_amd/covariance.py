@@ -606,6 +606,35 @@ def velocity_information(lwls, fl, sigma, gp, epoch_index):
     return h.fisher_vel(lw, gp, ep)
 
 
+def velocity_information_observed(lwls, fl, sigma, gp, epoch_index, mu_GP=1.0, baseline=None):
+    """``(lnp, grad (c, E), F, J)`` of one chunk from one factorisation on the device (``ChunkHandle.info_vel``): the value,
+    ``velocity_gradient``, ``velocity_information`` and the OBSERVED information ``J = -d2 lnL / dv dv`` at the flux ``fl``,
+    of which ``F`` is the expectation -- the curvature a Newton step and an error bar at the data want.  Rows as
+    ``velocity_information``; ``J`` has the same ``c`` null directions and is symmetric bit for bit.  ``baseline`` (the dict
+    of ``lnlike_marg``): everything under the marginalised continuum.  A negative hyper-parameter or a matrix that is not
+    positive definite gives ``-inf`` and NaN in every entry."""
+    gp = [float(g) for g in gp]
+    lw = np.stack([as_f64(w) for w in np.atleast_2d(lwls)])
+    if len(gp) != 2 * lw.shape[0]:
+        raise ValueError(f"gp must hold {2 * lw.shape[0]} values for {lw.shape[0]} component(s)")
+    ep = np.asarray(epoch_index, dtype=np.int64)
+    if ep.shape != lw.shape[1:] or ep.size == 0 or ep.min() < 0:
+        raise ValueError("epoch_index must hold one non-negative epoch per pixel")
+    c, E = lw.shape[0], int(ep.max()) + 1
+    if any(g < 0.0 for g in gp):
+        return -np.inf, np.full((c, E), np.nan), np.full((c * E, c * E), np.nan), np.full((c * E, c * E), np.nan)
+    if any(l == 0.0 for l in gp[1::2]):
+        raise ZeroDivisionError("float division")
+    if not _matrix_is_finite(lw, sigma, gp):
+        raise ValueError(_NONFINITE)
+    h = _chunk_for(fl, sigma)
+    if not hasattr(h, "info_vel"):
+        raise _lib.PsoapError("velocity_information_observed needs the device in this process (PSOAP_GPU_SERVER serves values only)")
+    if baseline is not None:
+        h.set_baseline(*_baseline_args(baseline))
+    return h.info_vel(lw, gp, ep, E, mu_GP, marg=baseline is not None)
+
+
 GP_LOWER_BOUND = 1e-6       # optimize_GP keeps every amplitude and length scale at or above this
 
 

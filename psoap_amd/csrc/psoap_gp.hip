@@ -34,6 +34,7 @@
 #include "orbit_grad_kernels.hpp"
 #include "fisher_kernels.hpp"
 #include "vel_fisher_kernels.hpp"
+#include "vel_newton_kernels.hpp"
 #include "loo_kernels.hpp"
 #include "marg_kernels.hpp"
 #include "marg_grad_kernels.hpp"
@@ -105,7 +106,7 @@ struct BatchSlot {
     Event evEval;              // compute stream: last evaluation that read this slot complete
 };
 
-namespace psoap { struct PredictWs; struct GradWs; struct FisherWs; struct VelFisherWs; struct LooWs; struct MargWs; }
+namespace psoap { struct PredictWs; struct GradWs; struct FisherWs; struct VelFisherWs; struct VelNewtonWs; struct LooWs; struct MargWs; }
 
 // Streamed evaluation (dag_kernel.hpp, "Streamed evaluation"): one resident launch of the persistent kernel, matrices
 // come and go through `lanes` workspaces of the handle.  Host side: lane allocation, the submission ring in pinned
@@ -240,6 +241,8 @@ struct psoap_chunk {
     std::unique_ptr<psoap::FisherWs> fws;
     // epoch-velocity Fisher workspace beyond fws's K^-1 (allocated by the first psoap_chunk_fisher_vel; psoap_chunk_fisher_vel_release)
     std::unique_ptr<psoap::VelFisherWs> vws;
+    // ... and of psoap_chunk_info_vel beyond that (vel_newton_kernels.hpp; freed by psoap_chunk_fisher_vel_release as well)
+    std::unique_ptr<psoap::VelNewtonWs> nws;
     // leave-one-out workspace (allocated by the first psoap_chunk_loo; psoap_chunk_loo_release)
     std::unique_ptr<psoap::LooWs> lws;
     // continuum-marginalised likelihood: the baseline as psoap_chunk_set_baseline took it (host), and its device side and
@@ -330,6 +333,7 @@ static int configure_kernels(int device)
     HIP_TRY(grad_configure_kernels());
     HIP_TRY(fisher_configure_kernels());
     HIP_TRY(vel_fisher_configure_kernels());
+    HIP_TRY(vel_newton_configure_kernels());
     HIP_TRY(loo_configure_kernels());
     HIP_TRY(marg_configure_kernels());
     HIP_TRY(marg_grad_configure_kernels());
@@ -2629,31 +2633,23 @@ extern "C" int psoap_chunk_fisher_release(psoap_chunk* h)
 }
 
 // ---- Fisher information of the per-epoch velocities (vel_fisher_kernels.hpp) ------------------------
-// One matrix through the gradient's workspace and factorisation and the Fisher workspace's K^-1, as fisher_run; then Dv_k and
-// Z_k = K^-1 Dv_k for every component, the c (c + 1) / 2 products X_kj with their binning epilogue, and the finishing sums --
-// on the handle's first stream behind whatever the handle has in flight; neither the proposal slots nor the workspaces of
-// the likelihood paths are touched.
-extern "C" int psoap_chunk_fisher_vel(psoap_chunk* h, int c, const double* lwl, const double* gp, int n_epochs,
-                                      const int32_t* epoch, double* fisher)
+// The launches of psoap_chunk_fisher_vel up to k_vel_finish, for it and for psoap_chunk_info_vel (inside the caller's device
+// scope, after its checks): afterwards F is in h->vws->F, K^-1 in the Fisher workspace, the plan in h->vws->Plan and the
+// epoch of every pixel in h->vws->Epoch.  `marg`: under the handle's baseline, Kt^-1 by k_marg_fisher_kinv as fisher_run forms
+// it.  `values`: the value record and alpha (alpha_m) of the data at mu_GP as well (factor_group).
+static int vel_fisher_launches(psoap_chunk* h, hipStream_t s, const Factored& fac, bool values, int c, const double* lwl,
+                               const double* gp, double mu_GP, int n_epochs, const int32_t* epoch, VelFisherPlan& pl,
+                               std::vector<int>& packed /* the caller keeps it until its stream is drained */)
 {
-    if (!h || !lwl || !gp || !epoch || !fisher) FAIL("psoap_chunk_fisher_vel: bad arguments");
-    if (const char* why = vel_fisher_check(c, h->N, n_epochs, epoch)) FAIL(std::string("psoap_chunk_fisher_vel: ") + why);
-    if (h->stream.open) FAIL("psoap_chunk_fisher_vel: the handle has an open stream (psoap_stream_close first)");
-    DEVICE_SCOPE(h->device);
-    if (int rc = enter_device(h->device)) return rc;
-    hipStream_t s = h->streams[0];
-    const Factored fac = factored(h, false, 1);
     const int N = h->N, Npad = h->Npad, P = h->P, ld = fac.ld;
     const size_t sq = (size_t)Npad * Npad, CN = (size_t)c * N, T = (size_t)c * n_epochs;
     const int ntiles = P * (P + 1) / 2;
-    VelFisherPlan pl;
     vel_fisher_plan(c, N, n_epochs, epoch, pl);
-    std::vector<int> packed;
     vel_plan_pack(pl, packed);
     const VelPlanOffsets off = vel_plan_offsets(Npad, P, pl.S, n_epochs);
     if (!h->fws) h->fws.reset(new FisherWs());
     if (!h->vws) h->vws.reset(new VelFisherWs());
-    if (int rc = factored_ws_need(h, fac, s, false, false)) return rc;
+    if (int rc = factored_ws_need(h, fac, s, values, false)) return rc;
     GradWs& w = *h->gws;
     FisherWs& f = *h->fws;
     VelFisherWs& v = *h->vws;
@@ -2671,12 +2667,16 @@ extern "C" int psoap_chunk_fisher_vel(psoap_chunk* h, int c, const double* lwl, 
     HIP_TRY(hipMemcpyAsync(v.Plan, packed.data(), sizeof(int) * packed.size(), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(v.Epoch, epoch, sizeof(int32_t) * (size_t)N, hipMemcpyHostToDevice, s));
     // (F does not depend on the data: any mu_GP)
-    if (int rc = factor_group(h, fac, s, 1, c, 0.0, false)) return rc;
+    if (int rc = factor_group(h, fac, s, 1, c, mu_GP, values)) return rc;
     double kunits = 0.0;
-    for (int tj = 0; tj < P; ++tj) kunits += (double)(tj + 1) * (P - tj);
+    for (int tj = 0; tj < P; ++tj) kunits += (double)(tj + 1) * (P - tj + fac.Q);
     if (int rc = prof_launch(h, s, PSOAP_K_GRAD, TILE_FLOPS * kunits, 0.0, [&] {
-            hipLaunchKernelGGL(k_fisher_kinv, dim3(ntiles), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)w.A.p, ld, Npad, P,
-                               f.Kinv.p);
+            if (fac.marg)
+                hipLaunchKernelGGL(k_marg_fisher_kinv, dim3(ntiles), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)w.A.p, ld,
+                                   Npad, P, (const double*)fac.Vt->p, fac.ldm, fac.S, f.Kinv.p);
+            else
+                hipLaunchKernelGGL(k_fisher_kinv, dim3(ntiles), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)w.A.p, ld, Npad,
+                                   P, f.Kinv.p);
         })) return rc;
     if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
             hipLaunchKernelGGL(k_acc_total, dim3(1), dim3(1), 0, s, (const MatAcc*)w.Acc.p, P, f.Info.p);
@@ -2704,13 +2704,33 @@ extern "C" int psoap_chunk_fisher_vel(psoap_chunk* h, int c, const double* lwl, 
                                            plan + off.slot_of, plan + off.slot_first, part);
                 }
         })) return rc;
-    if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
-            hipLaunchKernelGGL(k_vel_finish, dim3((unsigned)((T * T + 63) / 64)), dim3(64), 0, s, (const double*)v.Part.p, pl.S, c,
-                               n_epochs, plan + off.epoch_ptr, plan + off.epoch_slots, plan + off.slot_block, v.F.p);
-        })) return rc;
+    return prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
+        hipLaunchKernelGGL(k_vel_finish, dim3((unsigned)((T * T + 63) / 64)), dim3(64), 0, s, (const double*)v.Part.p, pl.S, c,
+                           n_epochs, plan + off.epoch_ptr, plan + off.epoch_slots, plan + off.slot_block, v.F.p);
+    });
+}
+
+// One matrix through the gradient's workspace and factorisation and the Fisher workspace's K^-1, as fisher_run; then Dv_k and
+// Z_k = K^-1 Dv_k for every component, the c (c + 1) / 2 products X_kj with their binning epilogue, and the finishing sums --
+// on the handle's first stream behind whatever the handle has in flight; neither the proposal slots nor the workspaces of
+// the likelihood paths are touched.
+extern "C" int psoap_chunk_fisher_vel(psoap_chunk* h, int c, const double* lwl, const double* gp, int n_epochs,
+                                      const int32_t* epoch, double* fisher)
+{
+    if (!h || !lwl || !gp || !epoch || !fisher) FAIL("psoap_chunk_fisher_vel: bad arguments");
+    if (const char* why = vel_fisher_check(c, h->N, n_epochs, epoch)) FAIL(std::string("psoap_chunk_fisher_vel: ") + why);
+    if (h->stream.open) FAIL("psoap_chunk_fisher_vel: the handle has an open stream (psoap_stream_close first)");
+    DEVICE_SCOPE(h->device);
+    if (int rc = enter_device(h->device)) return rc;
+    hipStream_t s = h->streams[0];
+    const Factored fac = factored(h, false, 1);
+    const size_t T = (size_t)c * n_epochs;
+    VelFisherPlan pl;
+    std::vector<int> packed;
+    if (int rc = vel_fisher_launches(h, s, fac, false, c, lwl, gp, 0.0, n_epochs, epoch, pl, packed)) return rc;
     MatAcc info;
-    HIP_TRY(hipMemcpyAsync(fisher, v.F, sizeof(double) * T * T, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(&info, f.Info, sizeof info, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(fisher, h->vws->F, sizeof(double) * T * T, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&info, h->fws->Info, sizeof info, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     if (collect_timings(h)) return 1;
     // the conventions of the likelihood: a negative hyper-parameter or a matrix that is not positive definite -> no information
@@ -2719,9 +2739,86 @@ extern "C" int psoap_chunk_fisher_vel(psoap_chunk* h, int c, const double* lwl, 
     return 0;
 }
 
+// ---- observed information of the per-epoch velocities (vel_newton_kernels.hpp) -----------------------
+// Value, gradient, F and J from ONE factorisation: the launches of psoap_chunk_fisher_vel with the value record and alpha
+// (under the baseline: the marginal ones), then the pair pass over K^-1, U, V = K^-1 U, U^T V and the finishing kernel.
+extern "C" int psoap_chunk_info_vel(psoap_chunk* h, int marg, int c, const double* lwl, const double* gp, double mu_GP,
+                                    int n_epochs, const int32_t* epoch, double* lnp, double* grad, double* fisher,
+                                    double* observed)
+{
+    if (!h || !lwl || !gp || !epoch || !lnp || !grad || !fisher || !observed) FAIL("psoap_chunk_info_vel: bad arguments");
+    if (const char* why = vel_fisher_check(c, h->N, n_epochs, epoch)) FAIL(std::string("psoap_chunk_info_vel: ") + why);
+    if (h->stream.open) FAIL("psoap_chunk_info_vel: the handle has an open stream (psoap_stream_close first)");
+    if (marg)
+        if (const char* why = marg_grad_check(1, c, h->marg.valid, h->marg.stale_weight))
+            FAIL(std::string("psoap_chunk_info_vel: ") + why);
+    DEVICE_SCOPE(h->device);
+    if (int rc = enter_device(h->device)) return rc;
+    hipStream_t s = h->streams[0];
+    const Factored fac = factored(h, marg != 0, 1);
+    const int N = h->N, Npad = h->Npad, P = h->P;
+    const size_t T = (size_t)c * n_epochs;
+    const int Tpad = round_up((int)T, NB), Tp = Tpad / NB;
+    VelFisherPlan pl;
+    std::vector<int> packed;
+    if (int rc = vel_fisher_launches(h, s, fac, true, c, lwl, gp, mu_GP, n_epochs, epoch, pl, packed)) return rc;
+    const VelPlanOffsets off = vel_plan_offsets(Npad, P, pl.S, n_epochs);
+    const size_t S = (size_t)pl.S;
+    if (!h->nws) h->nws.reset(new VelNewtonWs());
+    GradWs& w = *h->gws;
+    FisherWs& f = *h->fws;
+    VelFisherWs& v = *h->vws;
+    VelNewtonWs& nw = *h->nws;
+    HIP_TRY(nw.Y.need((size_t)c * S * Npad));
+    HIP_TRY(nw.A.need((size_t)c * S * S));
+    HIP_TRY(nw.B.need((size_t)c * S * S));
+    HIP_TRY(nw.U.need((size_t)Npad * Tpad));
+    HIP_TRY(nw.V.need((size_t)Npad * Tpad));
+    HIP_TRY(nw.M.need((size_t)Tpad * Tpad));
+    HIP_TRY(nw.J.need(T * T));
+    HIP_TRY(nw.Grad.need(T));
+    const int* plan = v.Plan.p;
+    if (int rc = prof_launch(h, s, PSOAP_K_FILL, 0.0, 8.0 * (double)Npad * Npad * c, [&] {
+            hipLaunchKernelGGL(k_vel_pair, dim3(P * P, c), dim3(VEL_PAIR_THREADS), 0, s, (const double*)f.Kinv.p,
+                               (const double*)w.Alpha.p, Npad, N, P, pl.S, (const double*)w.Lwl.p, (const double*)w.Gp.p,
+                               (const int*)v.Epoch.p, plan + off.slot_of, plan + off.slot_first, nw.Y.p, nw.A.p, nw.B.p);
+        })) return rc;
+    if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
+            hipLaunchKernelGGL(k_vel_u, dim3((Npad + 255) / 256, Tpad), dim3(256), 0, s, (const double*)nw.Y.p, Npad, N, pl.S, c,
+                               n_epochs, Tpad, (const int*)v.Epoch.p, plan + off.epoch_ptr, plan + off.epoch_slots, nw.U.p);
+        })) return rc;
+    if (int rc = prof_launch(h, s, PSOAP_K_GRAD, TILE_FLOPS * ((double)P * P * Tp + 0.5 * P * Tp * (Tp + 1.0)), 0.0, [&] {
+            hipLaunchKernelGGL(k_vel_v, dim3(P, Tp), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)f.Kinv.p,
+                               (const double*)nw.U.p, Npad, Tpad, nw.V.p);
+            hipLaunchKernelGGL(k_vel_gram, dim3(Tp, Tp), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)nw.U.p,
+                               (const double*)nw.V.p, Npad, Tpad, nw.M.p);
+        })) return rc;
+    if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
+            hipLaunchKernelGGL(k_vel_newton_finish, dim3((unsigned)((T * T + 63) / 64)), dim3(64), 0, s, (const double*)nw.A.p,
+                               (const double*)nw.B.p, (const double*)nw.M.p, (const double*)v.F.p, pl.S, c, n_epochs, Tpad,
+                               plan + off.epoch_ptr, plan + off.epoch_slots, nw.J.p, nw.Grad.p);
+        })) return rc;
+    MatAcc info;
+    std::vector<double> out((size_t)fac.out_stride);
+    HIP_TRY(hipMemcpyAsync(out.data(), fac.Out->p, sizeof(double) * (size_t)fac.out_stride, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(fisher, v.F, sizeof(double) * T * T, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(observed, nw.J, sizeof(double) * T * T, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(grad, nw.Grad, sizeof(double) * T, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&info, f.Info, sizeof info, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (collect_timings(h)) return 1;
+    // the conventions of the likelihood: a negative hyper-parameter or a matrix that is not positive definite -> -inf, and
+    // neither gradient nor information there
+    if (values_out(out.data(), fac.out_stride, 0, proposal_refused(gp, c, 0) || info.info != 0.0, lnp, nullptr)) {
+        for (size_t k = 0; k < T * T; ++k) fisher[k] = observed[k] = NAN;
+        for (size_t k = 0; k < T; ++k) grad[k] = NAN;
+    }
+    return 0;
+}
+
 extern "C" int psoap_chunk_fisher_vel_release(psoap_chunk* h)
 {
-    return release_ws(h, [&] { h->vws.reset(); });
+    return release_ws(h, [&] { h->vws.reset(), h->nws.reset(); });
 }
 
 // ---- leave-one-out cross-validation of the likelihood (loo_kernels.hpp) ------------------------------

@@ -251,9 +251,10 @@ class ChunkWorker:
         return self.loo_orbits(p_orb[0], p_gp[0], mu_GP)
 
     # -- per-epoch velocities free of any orbit (include/psoap_gp.h: psoap_chunk_fisher_vel) ---------------------------
-    def _grids_at(self, vel, what):
+    def _grids_at(self, vel, what, baseline_ok=False):
         """a free velocity table (c, E) -> ``(lwls (c, N), too_fast)``, the grids shifted as ``shifted_grids`` shifts them"""
-        self._no_baseline(what)
+        if not baseline_ok:
+            self._no_baseline(what)
         if os.environ.get("PSOAP_GPU_SERVER", "").strip().lower() not in ("", "0"):
             raise _lib.PsoapError(f"{what} needs the device in this process (PSOAP_GPU_SERVER serves values only)")
         from .data import c_kms
@@ -265,8 +266,8 @@ class ChunkWorker:
         """The ``(c E, c E)`` information of the per-epoch velocities of this chunk at the free velocity table ``vel``
         (c, E) and GP parameters ``p_gp`` (2c,), row ``c * E + e`` (``ChunkHandle.fisher_vel``): AT FIXED hyper-parameters,
         with one null direction per component.  Any ``|v| >= c_kms``, a negative hyper-parameter or a matrix that is not
-        positive definite gives NaN in every entry.  A worker with a baseline is refused: the variant under the
-        marginalised continuum, with ``(K + H Lambda H^T)^-1`` in place of ``K^-1``, is not built yet."""
+        positive definite gives NaN in every entry.  A worker with a baseline is refused here: ``info_vel_at`` is the path
+        that accepts one, with ``(K + H Lambda H^T)^-1`` in place of ``K^-1``."""
         lwls, fast = self._grids_at(vel, "fisher_vel_at")
         c, E = N_COMPONENTS[self.model], self.dates.shape[0]
         if fast:
@@ -276,7 +277,8 @@ class ChunkWorker:
     def lnlike_grad_vel(self, vel, p_gp, mu_GP: float = 1.0):
         """``(lnp, grad_vel (c, E))`` of this chunk at the free velocity table ``vel`` (c, E): ``ChunkHandle.lnlike_grad``
         folded by ``covariance.velocity_gradient``.  Any ``|v| >= c_kms``, a negative hyper-parameter or a matrix that is
-        not positive definite gives ``-inf`` and NaN.  A worker with a baseline is refused, as for ``fisher_vel_at``."""
+        not positive definite gives ``-inf`` and NaN.  A worker with a baseline is refused, as for ``fisher_vel_at``;
+        ``info_vel_at`` accepts one."""
         from .covariance import velocity_gradient
         lwls, fast = self._grids_at(vel, "lnlike_grad_vel")
         c, E = N_COMPONENTS[self.model], self.dates.shape[0]
@@ -284,6 +286,19 @@ class ChunkWorker:
             return -np.inf, np.full((c, E), np.nan)
         lnp, _g_gp, g_lwl, _g_mu = self.handle.lnlike_grad(lwls, as_f64(np.ravel(p_gp), (2 * c,)), mu_GP)
         return float(lnp), velocity_gradient(g_lwl, self.epoch_index, E)
+
+    def info_vel_at(self, vel, p_gp, mu_GP: float = 1.0):
+        """``(lnp, grad_vel (c, E), F (c E, c E), J (c E, c E))`` of this chunk at the free velocity table ``vel`` (c, E) from
+        one factorisation (``ChunkHandle.info_vel``): value, gradient, expected and observed information, ``E[J] = F``.  On
+        a worker with a baseline everything is taken under the marginal likelihood, the one ``lnprob`` returns on this
+        worker -- this is the path that accepts a baseline.  Any ``|v| >= c_kms``, a negative hyper-parameter or a matrix
+        that is not positive definite gives ``-inf`` and NaN."""
+        lwls, fast = self._grids_at(vel, "info_vel_at", baseline_ok=True)
+        c, E = N_COMPONENTS[self.model], self.dates.shape[0]
+        if fast:
+            return -np.inf, np.full((c, E), np.nan), np.full((c * E, c * E), np.nan), np.full((c * E, c * E), np.nan)
+        return self.handle.info_vel(lwls, as_f64(np.ravel(p_gp), (2 * c,)), self.epoch_index, E, mu_GP,
+                                    marg=self.baseline is not None)
 
 
 def baseline_fit(workers, p, mu_GP=1.0):
@@ -425,22 +440,28 @@ def optimize_orbit(workers, p0, bounds=None, mu_GP=1.0, ftol=1e-10, full_output=
 
 
 # ---- per-epoch radial velocities with error bars, free of any orbit model --------------------------------------------------
+def _velocity_contrasts(c, n_epochs, idx):
+    """``Q^T`` (c (len(idx) - 1), c E) of ``velocity_pinv``: per component the Helmert contrasts of the seen epochs ``idx``"""
+    n = c * n_epochs
+    rows = []
+    for k in range(c):
+        for j in range(1, idx.size):
+            v = np.zeros(n)
+            v[k * n_epochs + idx[:j]] = 1.0
+            v[k * n_epochs + idx[j]] = -float(j)
+            rows.append(v / np.sqrt(j * (j + 1.0)))
+    return np.array(rows)
+
+
 def velocity_pinv(F, c, n_epochs, seen):
     """``F^+`` on the complement of the ``c`` per-component constant vectors and of the epochs nobody sees (``seen`` (E,)
     bool): with ``Q`` an orthonormal basis of that complement (per component the Helmert contrasts of the seen epochs),
     ``Q (Q^T F Q)^-1 Q^T``.  Rows and columns of unseen epochs are zero."""
     n = c * n_epochs
     idx = np.flatnonzero(np.asarray(seen, dtype=bool))
-    cols = []
-    for k in range(c):
-        for j in range(1, idx.size):
-            v = np.zeros(n)
-            v[k * n_epochs + idx[:j]] = 1.0
-            v[k * n_epochs + idx[j]] = -float(j)
-            cols.append(v / np.sqrt(j * (j + 1.0)))
-    if not cols:
+    if idx.size < 2:
         return np.zeros((n, n))
-    Q = np.array(cols).T
+    Q = _velocity_contrasts(c, n_epochs, idx).T
     M = Q.T @ as_f64(F) @ Q
     return Q @ np.linalg.solve(0.5 * (M + M.T), Q.T)
 
@@ -478,8 +499,61 @@ def velocity_scoring(value, grad_info, vel0, seen, max_iter=20, tol=1e-10):
             return {"vel": vel, "cov": cov, "n_iter": it, "decrement": dec, "lnp_start": lnp0, "lnp": lnp, "converged": False}
 
 
+def velocity_newton(value, info, vel0, seen, max_iter=20, tol=1e-10):
+    """Newton's method on a velocity table from ``vel0`` (c, E): ``info(vel) -> (lnp, g (c, E), F, J)`` is one call for the
+    summed likelihood, its gradient, its expected and its observed information; ``value(vel) -> lnp`` serves the line
+    search.  Per iteration the step is ``J^+ g`` when ``Q^T J Q`` (the ``Q`` of ``velocity_pinv``) has a Cholesky factor --
+    the data's own curvature: quadratic convergence near the optimum -- and ``F^+ g`` otherwise (``n_fallback`` counts
+    those); the step is halved until ``value`` does not decrease (one more ``value`` call at the start gives the line search
+    its first level), so ``lnp`` is never lowered.  Stops when the decrement
+    ``g^T cov g <= tol``.  -> the dict of ``velocity_scoring`` plus ``cov_kind`` (``"observed"``: ``cov = J^+`` at ``vel``,
+    or ``"expected"``) and ``n_fallback``."""
+    vel = as_f64(vel0).copy()
+    c, E = vel.shape
+    idx = np.flatnonzero(np.asarray(seen, dtype=bool))
+    it, n_fallback, lnp0 = 0, 0, None
+    ref = float(value(vel))      # the line search compares values of ONE evaluation path: info's lnp may differ from it by rounding
+    while True:
+        lnp, g, F, J = info(vel)
+        lnp = float(lnp)
+        if lnp0 is None:
+            lnp0 = lnp
+        if not (np.isfinite(lnp) and np.all(np.isfinite(g)) and np.all(np.isfinite(F)) and np.all(np.isfinite(J))):
+            raise np.linalg.LinAlgError("the likelihood, its gradient or its information is not finite at the velocity table")
+        kind = "observed"
+        if idx.size >= 2:
+            Qt = _velocity_contrasts(c, E, idx)
+            M = Qt @ as_f64(J) @ Qt.T
+            try:
+                np.linalg.cholesky(0.5 * (M + M.T))
+            except np.linalg.LinAlgError:
+                kind = "expected"
+        cov = velocity_pinv(J if kind == "observed" else F, c, E, seen)
+        gv = as_f64(g).reshape(-1)
+        delta = cov @ gv
+        dec = float(gv @ delta)
+        out = {"vel": vel, "cov": cov, "n_iter": it, "decrement": dec, "lnp_start": lnp0, "lnp": lnp, "converged": dec <= tol,
+               "cov_kind": kind, "n_fallback": n_fallback}
+        if dec <= tol or it >= max_iter:
+            return out
+        n_fallback += kind == "expected"
+        step, moved = 1.0, False
+        for _ in range(60):
+            trial = vel + step * delta.reshape(c, E)
+            v = float(value(trial))
+            if v >= ref:
+                vel, ref, moved = trial, v, True
+                break
+            step *= 0.5
+        it += 1
+        if not moved:
+            out.update(n_iter=it, converged=False, n_fallback=n_fallback)
+            return out
+
+
 class EpochVelocities:
-    """What ``epoch_velocities`` returns: ``dates`` (E,), ``vel`` (c, E), ``cov`` (c E, c E) ``= F^+``, ``sigma`` (c, E) (NaN
+    """What ``epoch_velocities`` returns: ``dates`` (E,), ``vel`` (c, E), ``cov`` (c E, c E) ``= F^+`` (``cov_kind``
+    ``"expected"``; with ``method="newton"`` ``J^+``, ``"observed"``, unless the last iteration fell back), ``sigma`` (c, E) (NaN
     for an epoch no chunk sees), ``n_iter``, ``decrement``, ``lnp_start``, ``lnp``, ``converged``.  The errors are those of
     RELATIVE velocities at FIXED hyper-parameters: the constant shift of each component is a null direction of the
     likelihood and is never moved -- each component's mean over the seen epochs stays the orbit's."""
@@ -492,6 +566,7 @@ class EpochVelocities:
         self.sigma = np.where(self.seen[None, :], np.sqrt(np.maximum(np.diag(self.cov), 0.0)).reshape(c, E), np.nan)
         self.n_iter, self.decrement, self.converged = fit["n_iter"], fit["decrement"], fit["converged"]
         self.lnp_start, self.lnp = fit["lnp_start"], fit["lnp"]
+        self.cov_kind, self.n_fallback = fit.get("cov_kind", "expected"), fit.get("n_fallback", 0)
 
     def write_table(self, fname):
         """``date, v_0, sigma_0, v_1, sigma_1, ...`` per epoch, one row each, with ``np.savetxt``"""
@@ -503,7 +578,7 @@ class EpochVelocities:
         return fname
 
 
-def epoch_velocities(workers, p, max_iter=20, tol=1e-10, mu_GP=1.0, vel0=None):
+def epoch_velocities(workers, p, max_iter=20, tol=1e-10, mu_GP=1.0, vel0=None, method="scoring"):
     """The radial velocity of every component at every epoch with its error bar, free of any orbit model: Fisher scoring
     on the velocity table of the SUM of the workers' likelihoods, from the orbit's velocities at the fitted vector ``p``
     with the GP parameters of ``p`` held fixed.  The workers must share ``dates``.  Per iteration the summed
@@ -517,18 +592,27 @@ def epoch_velocities(workers, p, max_iter=20, tol=1e-10, mu_GP=1.0, vel0=None):
     The errors are those of RELATIVE velocities AT FIXED hyper-parameters: each component's constant shift is a null
     direction (the kernel is stationary) and its plain mean over the seen epochs stays the orbit's (the plain mean, not a
     weighted one, on purpose: the null vector of ``F`` is the constant vector, and a step in its complement keeps that mean); the cross information with
-    ``(amp, l)`` stays with ``fisher_information``.  Workers with a baseline are refused: the variant under the marginalised
-    continuum is not built yet.  ``vel0`` (c, E): a table to start from instead of the orbit's (an earlier fit; its
+    ``(amp, l)`` stays with ``fisher_information``.  Workers with a baseline are refused by the default method;
+    ``method="newton"`` is the path that accepts them.  ``vel0`` (c, E): a table to start from instead of the orbit's (an earlier fit; its
     per-component means are then the ones that stay).  Fisher scoring converges linearly -- the information is the expected
     curvature, not the data's own -- so ``converged`` can be False after ``max_iter``; the result then still never lowered
-    ``lnp``, and ``decrement`` says how far it is."""
+    ``lnp``, and ``decrement`` says how far it is.
+
+    ``method="newton"``: Newton's method on the OBSERVED information (``velocity_newton``), one ``ChunkWorker.info_vel_at``
+    per worker and iteration -- value, gradient, ``F`` and ``J`` from one factorisation -- with quadratic convergence near
+    the optimum, ``cov = J^+`` there (``cov_kind``), and a fall-back to the scoring step wherever ``J`` is not positive
+    definite on the complement.  Workers with a baseline are fitted under their marginal likelihood: a per-epoch continuum
+    offset within the prior does not bias the velocities."""
     from .orbit import velocities
+    if method not in ("scoring", "newton"):
+        raise ValueError("epoch_velocities: method must be 'scoring' or 'newton'")
     workers = list(workers) if isinstance(workers, (list, tuple)) else [workers]
     w0 = workers[0]
     if os.environ.get("PSOAP_GPU_SERVER", "").strip().lower() not in ("", "0"):
         raise _lib.PsoapError("epoch_velocities needs the device in this process (PSOAP_GPU_SERVER serves values only)")
     for w in workers:
-        w._no_baseline("epoch_velocities")
+        if method == "scoring":
+            w._no_baseline("epoch_velocities")
         if w.model != w0.model or w.dates.shape != w0.dates.shape or not np.array_equal(w.dates, w0.dates):
             raise ValueError("epoch_velocities: the workers must share the model and the dates")
     c, E = N_COMPONENTS[w0.model], w0.dates.shape[0]
@@ -540,6 +624,29 @@ def epoch_velocities(workers, p, max_iter=20, tol=1e-10, mu_GP=1.0, vel0=None):
     seen = np.zeros(E, dtype=bool)
     for w in workers:
         seen |= np.bincount(w.epoch_index, minlength=E) > 0
+
+    if method == "newton":
+        def info(vel):
+            lnp, g, F, J = 0.0, np.zeros((c, E)), np.zeros((c * E, c * E)), np.zeros((c * E, c * E))
+            for w in workers:
+                lnp_w, g_w, F_w, J_w = w.info_vel_at(vel, gp, mu_GP)
+                lnp, g, F, J = lnp + lnp_w, g + g_w, F + F_w, J + J_w
+            return lnp, g, F, J
+
+        def value_newton(vel):
+            from .data import c_kms
+            if np.any(np.abs(vel) >= c_kms):
+                return -np.inf
+            total = 0.0
+            for w in workers:
+                lwls = w._grids_at(vel, "epoch_velocities", baseline_ok=True)[0]
+                if w.baseline is not None:
+                    total += float(w.handle.lnlike_marg(lwls, gp, mu_GP))
+                else:
+                    total += float(w.handle.lnlike_batch(lwls[None], gp[None], mu_GP)[0])
+            return total
+
+        return EpochVelocities(w0.dates, velocity_newton(value_newton, info, vel0, seen, max_iter, tol), seen)
 
     def value(vel):
         from .data import c_kms

@@ -91,7 +91,8 @@ def run_shape(name: str, repeats: int) -> dict:
     return out
 
 
-def run_fit() -> dict:
+def run_fit(method: str = "scoring") -> dict:
+    """the 8-chunk cfg4 fit; ``method`` goes to lnprob.epoch_velocities (tools/vel_newton_bench.py runs both)"""
     import oracle
     from psoap_amd import lnprob, synthetic as syn
     from psoap_amd.utils import registered_params
@@ -116,7 +117,7 @@ def run_fit() -> dict:
     p = np.array([full[n] for n in registered_params["SB2"]])
     try:
         t0 = time.perf_counter()
-        res = lnprob.epoch_velocities(workers, p, vel0=first.velocities + d)
+        res = lnprob.epoch_velocities(workers, p, vel0=first.velocities + d, method=method)
         wall = time.perf_counter() - t0
     finally:
         for w in workers:
