@@ -143,6 +143,53 @@ int psoap_chunk_lnlike_grad(psoap_chunk *h, int B, int c, const double *lwl,
                             double *grad_gp, double *grad_lwl, double *grad_mu);
 int psoap_chunk_grad_release(psoap_chunk *h);
 
+/* ---- time-variable component spectra: a temporal factor in the GP kernel -------------
+ * Model: each component's squared exponential in ln-wavelength times one in observation
+ * time, with a time scale tau_c (days) per component:
+ *   K_ij = sum_c a_c^2 exp(p_c d_cij^2 + q_c dt_ij^2) + sigma_i^2 delta_ij
+ *   d_cij = x_c[j] - x_c[i],  p_c = -1/2 c_kms^2 / l_c^2
+ *   dt_ij = t[j] - t[i],      q_c = -1/2 / tau_c^2
+ * tau_c = +inf is the static model of psoap_chunk_lnlike_grad; a finite tau_c lets that
+ * component's spectrum drift from epoch to epoch.
+ *
+ * psoap_chunk_set_times: t (N), the observation time of every pixel in days, copied to
+ * the device and kept with the handle as fl and sigma are.  Any order: a pixel-permuted
+ * chunk is legal.  Pass times from which a constant (their minimum) has been taken, so
+ * that the differences are formed from small numbers.  Refused on an open stream.
+ *
+ * psoap_chunk_lnlike_tv_grad: lwl (B, c, N), gp (B, 2c) and the outputs lnp, grad_gp,
+ * grad_lwl (may be NULL), grad_mu (may be NULL) as for psoap_chunk_lnlike_grad; tau (B, c)
+ * and grad_tau (B, c) = d lnp / d tau_c.  With Q = alpha alpha^T - K^-1 and
+ * e_cij = exp(p_c d_cij^2 + q_c dt_ij^2) the formulas of psoap_chunk_lnlike_grad hold
+ * with that e, and
+ *   d lnp / d tau_c = 1/2 a_c^2 / tau_c^3 sum_ij Q_ij e_cij dt_ij^2
+ * One exp per element and component: the argument is evaluated as a = p * d * d, then
+ * a = a + q * dt * dt, without contraction, and the underflow shortcut works on the sum
+ * (csrc/timevar_kernels.hpp).  The factorisation, alpha and the product are those of
+ * psoap_chunk_lnlike_grad; no atomics, the same arguments give the same bits alone or in
+ * any batch.
+ * Bit-identity at tau = inf: q = -0, the added term is -0 and a keeps its bits, so with
+ * every tau_c = +inf lnp, grad_gp, grad_lwl and grad_mu have the bits
+ * psoap_chunk_lnlike_grad returns on the same handle, and grad_tau is exactly 0.
+ * grad_gp == NULL asks for the value only: grad_tau, grad_lwl and grad_mu must then be
+ * NULL too, the contraction is skipped, and lnp has the bits of a call that asks for the
+ * gradient.  With grad_gp, grad_tau is required.
+ * Conventions: tau_c <= 0 or NaN, a negative hyper-parameter or a matrix that is not
+ * positive definite gives lnp = -inf and NaN in every gradient entry of that proposal;
+ * the other proposals keep their bits; tau_c = +inf is valid.  The status is non-zero
+ * for runtime and argument errors only: a call before psoap_chunk_set_times, on a handle
+ * with an open stream, or on a handle with a baseline (psoap_chunk_set_baseline: the
+ * combination with the marginalised continuum is not built) is refused with a message.
+ * Workspace: that of psoap_chunk_lnlike_grad, walked in the same groups (at most 8
+ * matrices and 1 GiB), plus 3 doubles per matrix of a group for tau and for grad_tau and
+ * one double more per tile record; psoap_chunk_grad_release frees all of it, the times
+ * stay with the handle. */
+int psoap_chunk_set_times(psoap_chunk *h, const double *t);
+int psoap_chunk_lnlike_tv_grad(psoap_chunk *h, int B, int c, const double *lwl,
+                               const double *gp, const double *tau, double mu_GP,
+                               double *lnp, double *grad_gp, double *grad_tau,
+                               double *grad_lwl, double *grad_mu);
+
 /* ---- gradient of lnprob(p): through the Kepler solve and the Doppler shift ----------
  * B proposals as for psoap_batch_upload_orbits (needs set_grid + set_dates); B is NOT
  * bound by max_batch.
@@ -538,7 +585,17 @@ int psoap_chunk_sync(psoap_chunk *h);
  * sigma != NULL fuses V11[diag] += sigma**2 (covariance.py:322). */
 int psoap_fill_sym(int device, int c, int N, const double *lwl, const double *gp,
                    const double *sigma, double *out);
-/* fill_V12_f (psoap/matrix_functions.pyx:61-96): out (M,N),
+/* psoap_fill_sym under the time-variable kernel (psoap_chunk_lnlike_tv_grad above):
+ * t (N) the pixels' times, tau (c) the time scales,
+ *   out[i,j] = sum_c amp_c^2 exp(p_c (lwl_c[j]-lwl_c[i])^2 + q_c (t[j]-t[i])^2),
+ * the argument formed as p * d * d, then + q * dt * dt, without contraction; diagonal,
+ * sigma and everything else as psoap_fill_sym.  With every tau_c = +inf the matrix is
+ * bit-identical to psoap_fill_sym's.  Stand-alone (no handle): it exists so that the
+ * matrix of the time-variable likelihood can be checked element by element. */
+int psoap_fill_sym_tv(int device, int c, int N, const double *lwl, const double *t,
+                      const double *gp, const double *tau, const double *sigma,
+                      double *out);
+/* fill_V12_f(psoap/matrix_functions.pyx:61-96): out (M,N),
  * out[i,j] = amp^2 exp(p (lwl_col[j]-lwl_row[i])^2), M = len(lwl_row). */
 int psoap_fill_cross(int device, int M, int N, const double *lwl_row,
                      const double *lwl_col, double amp, double l, double *out);

@@ -205,6 +205,42 @@ class ChunkHandle:
         """Free the gradient workspace (16 Npad^2 bytes per matrix of a group); the next ``lnlike_grad`` allocates it again."""
         check(self._L.psoap_chunk_grad_release(self._h), "psoap_chunk_grad_release")
 
+    # -- time-variable component spectra (include/psoap_gp.h: psoap_chunk_lnlike_tv_grad) ---------------------------
+    def set_times(self, t):
+        """The observation time of every pixel in days, ``(N,)``, any order; kept on the device with the handle.  Pass
+        times minus a constant (their minimum): the device subtracts them from each other."""
+        t = as_f64(t, (self.N,))
+        check(self._L.psoap_chunk_set_times(self._h, dptr(t)), "psoap_chunk_set_times")
+
+    def _tv(self, lwls, gp, tau, mu_GP, want_grad):
+        single, B, c, lwls, gps = self._proposals(lwls, gp)
+        taus = as_f64(np.atleast_2d(as_f64(tau)), (B, c))
+        lnp = np.empty(B)
+        if not want_grad:
+            check(self._L.psoap_chunk_lnlike_tv_grad(self._h, B, c, dptr(lwls), dptr(gps), dptr(taus), float(mu_GP), dptr(lnp),
+                                                     None, None, None, None), "psoap_chunk_lnlike_tv_grad")
+            return float(lnp[0]) if single else lnp
+        g_gp, g_tau, g_lwl, g_mu = np.empty((B, 2 * c)), np.empty((B, c)), np.empty((B, c, self.N)), np.empty(B)
+        check(self._L.psoap_chunk_lnlike_tv_grad(self._h, B, c, dptr(lwls), dptr(gps), dptr(taus), float(mu_GP), dptr(lnp),
+                                                 dptr(g_gp), dptr(g_tau), dptr(g_lwl), dptr(g_mu)), "psoap_chunk_lnlike_tv_grad")
+        if single:
+            return float(lnp[0]), g_gp[0], g_tau[0], g_lwl[0], float(g_mu[0])
+        return lnp, g_gp, g_tau, g_lwl, g_mu
+
+    def lnlike_tv(self, lwls, gp, tau, mu_GP: float = 1.0):
+        """The likelihood under the time-variable kernel, ``K_ij = sum_c a_c^2 exp(p_c d^2 - dt^2 / (2 tau_c^2)) + sigma^2``
+        (needs ``set_times``): ``lwls`` (c, N) with ``gp`` (2c,) and ``tau`` (c,) -> ``lnp``; (B, c, N) with (B, 2c) and
+        (B, c) -> ``(B,)``.  ``tau = inf`` is the static model; ``tau <= 0`` or NaN gives ``-inf``.  The bits of ``lnp`` are
+        those of ``lnlike_tv_grad``."""
+        return self._tv(lwls, gp, tau, mu_GP, False)
+
+    def lnlike_tv_grad(self, lwls, gp, tau, mu_GP: float = 1.0):
+        """``lnlike_tv`` and its analytic gradient: ``(lnp, grad_gp, grad_tau, grad_lwl, grad_mu)``, shapes as
+        ``lnlike_grad`` with ``grad_tau`` (c,) or (B, c).  With every ``tau = inf`` the other four outputs have the bits of
+        ``lnlike_grad`` and ``grad_tau`` is exactly 0.  ``tau <= 0`` or NaN, a negative hyper-parameter or a matrix that is
+        not positive definite gives ``-inf`` and NaN gradients for that proposal."""
+        return self._tv(lwls, gp, tau, mu_GP, True)
+
     def fisher(self, lwls, gp, tan_gp, tan_lwl=None, want_mu: bool = False):
         """Fisher information of the likelihood at ``lwls`` (c, N), ``gp`` (2c,) along T <= 32 tangents (include/psoap_gp.h:
         psoap_chunk_fisher): ``tan_gp`` (T, 2c) and ``tan_lwl`` (T, c, N) (``None``: zeros) -> ``F (T, T)``,

@@ -669,6 +669,109 @@ def optimize_GP(lwls, fl, sigma, gp0, mu_GP=1.0, ftol=1e-10, full_output=False, 
     return res if full_output else res["x"]
 
 
+# ---- time-variable component spectra (not in the reference) ------------------------------------
+def _timevar(lwls, fl, sigma, gp, tau, times, mu_GP, want_grad):
+    """the front of ``lnlike_timevar`` and ``lnlike_timevar_grad``: the degenerate input of ``lnlike_grad``, ``tau <= 0`` or NaN
+    like a negative hyper-parameter, the cached handle with ``times - min(times)`` on it"""
+    gp = [float(g) for g in gp]
+    lw = np.stack([as_f64(w) for w in np.atleast_2d(lwls)])
+    c, N = lw.shape
+    if len(gp) != 2 * c:
+        raise ValueError(f"gp must hold {2 * c} values for {c} component(s)")
+    tau = as_f64(np.atleast_1d(as_f64(tau)), (c,))
+    t = as_f64(times, (N,))
+    if not np.all(np.isfinite(t)):
+        raise ValueError(_NONFINITE)
+    if any(g < 0.0 for g in gp) or not np.all(tau > 0.0):
+        if not want_grad:
+            return -np.inf
+        return -np.inf, np.full(len(gp), np.nan), np.full(c, np.nan), np.full(lw.shape, np.nan), np.nan
+    if any(l == 0.0 for l in gp[1::2]):
+        raise ZeroDivisionError("float division")
+    if not _matrix_is_finite(lw, sigma, gp):
+        raise ValueError(_NONFINITE)
+    h = _chunk_for(fl, sigma)
+    if not hasattr(h, "lnlike_tv_grad"):
+        raise _lib.PsoapError("lnlike_timevar needs the device in this process (PSOAP_GPU_SERVER serves the static likelihood only)")
+    t = t - t.min()
+    if getattr(h, "_tv_times", None) is None or not np.array_equal(h._tv_times, t):
+        h.set_times(t)
+        h._tv_times = t
+    res = h.lnlike_tv_grad(lw, gp, tau, mu_GP) if want_grad else (h.lnlike_tv(lw, gp, tau, mu_GP),)
+    if not np.isneginf(res[0]) and not (np.all(np.isfinite(np.asarray(fl, dtype=np.float64))) and np.isfinite(mu_GP)):
+        raise ValueError(_NONFINITE)
+    if not want_grad:
+        return np.float64(res[0])
+    return np.float64(res[0]), res[1], res[2], res[3], np.float64(res[4])
+
+
+def lnlike_timevar(lwls, fl, sigma, gp, tau, times, mu_GP=1.0):
+    """The likelihood under time-variable component spectra: each component's kernel in ln-wavelength times a squared
+    exponential in observation time, ``K_ij = sum_c a_c^2 exp(p_c d_cij^2 - (t_j - t_i)^2 / (2 tau_c^2)) + sigma_i^2 delta_ij``.
+    ``tau`` (c,) in the unit of ``times`` (days); ``tau_c = inf`` keeps component c static, and with every ``tau = inf`` this is
+    ``lnlike_f`` / ``_f_g`` / ``_f_g_h``.  ``times`` (N,): the observation time of every pixel -- ``dates[epoch_index]`` -- in
+    any order; their minimum is subtracted before they go to the device.  ``tau <= 0`` or NaN gives ``-inf``; other
+    degenerate input follows ``lnlike_grad``."""
+    return _timevar(lwls, fl, sigma, gp, tau, times, mu_GP, False)
+
+
+def lnlike_timevar_grad(lwls, fl, sigma, gp, tau, times, mu_GP=1.0):
+    """``(lnp, grad_gp (2c,), grad_tau (c,), grad_lwl (c, N), grad_mu)``: ``lnlike_timevar`` and its analytic derivatives on the
+    device (``ChunkHandle.lnlike_tv_grad``).  ``grad_tau`` is exactly 0 where ``tau = inf``."""
+    return _timevar(lwls, fl, sigma, gp, tau, times, mu_GP, True)
+
+
+def optimize_GP_timevar(lwls, fl, sigma, gp0, tau0, times, free_tau=None, mu_GP=1.0, ftol=1e-10, full_output=False):
+    """L-BFGS-B fit of the hyper-parameters and time scales of ``lnlike_timevar`` from ``(gp0, tau0)``, on the device gradient,
+    in ``log amp``, ``log l`` and ``log tau``.  ``free_tau`` (c,) of booleans (default: every finite ``tau0``): a component left
+    out keeps its ``tau0``, and ``inf`` is allowed there -- a free one must start finite.  Amplitudes and length scales stay at
+    or above ``GP_LOWER_BOUND``.  Returns ``(gp, tau)``; with ``full_output`` ``(gp, tau, lnp, lnp_static, result)``:
+    the likelihood reached, the likelihood at the same ``gp`` with every ``tau = inf``, and SciPy's result.
+    ``lnp - lnp_static`` is the variability statistic: what the time-variable kernel gains over the static one."""
+    lw = np.stack([as_f64(w) for w in np.atleast_2d(lwls)])
+    c = lw.shape[0]
+
+    def value_grad(gp, tau):
+        lnp, g_gp, g_tau, _g_lwl, _g_mu = lnlike_timevar_grad(lw, fl, sigma, gp, tau, times, mu_GP)
+        return lnp, g_gp, g_tau
+
+    gp, tau, res = _fit_timevar(value_grad, c, gp0, tau0, free_tau, ftol)
+    if not full_output:
+        return gp, tau
+    lnp_static = lnlike_timevar(lw, fl, sigma, gp, np.full(c, np.inf), times, mu_GP)
+    return gp, tau, -float(res["fun"]), float(lnp_static), res
+
+
+def _fit_timevar(value_grad, c, gp0, tau0, free_tau, ftol):
+    """The driver of ``optimize_GP_timevar``: L-BFGS-B over ``x = (log gp, log tau[free])`` on ``value_grad(gp, tau) -> (lnp,
+    grad_gp, grad_tau)`` -> ``(gp, tau, SciPy's result)``.  (Apart from ``value_grad`` nothing here knows the device: the
+    tests run the same driver on the float64 CPU evaluation.)"""
+    from scipy.optimize import minimize
+    g0 = np.maximum(as_f64(gp0, (2 * c,)), GP_LOWER_BOUND)
+    t0 = as_f64(np.atleast_1d(as_f64(tau0)), (c,)).copy()
+    free = np.isfinite(t0) if free_tau is None else np.asarray(free_tau, dtype=bool).reshape(c)
+    if not np.all(t0 > 0.0) or not np.all(np.isfinite(t0[free])):
+        raise ValueError("tau0 must be positive, and finite where free_tau is set")
+
+    def unpack(x):
+        tau = t0.copy()
+        tau[free] = np.exp(x[2 * c:])
+        return np.exp(x[:2 * c]), tau
+
+    def func(x):
+        gp, tau = unpack(x)
+        lnp, g_gp, g_tau = value_grad(gp, tau)
+        if not np.isfinite(lnp):
+            return np.inf, np.zeros_like(x)
+        return -lnp, -np.concatenate([g_gp * gp, g_tau[free] * tau[free]])       # d/dlog theta = theta d/dtheta
+
+    x0 = np.concatenate([np.log(g0), np.log(t0[free])])
+    bounds = [(np.log(GP_LOWER_BOUND), None)] * (2 * c) + [(None, None)] * int(free.sum())
+    res = minimize(func, x0, jac=True, method="L-BFGS-B", bounds=bounds, options={"ftol": ftol})
+    gp, tau = unpack(res["x"])
+    return gp, tau, res
+
+
 # ---- calibration (SURVEY.md 8(f) f-4) ---------------------------------------------------------------
 _CAL_FAIL = {1: "reference-epoch covariance B", 2: "conditional covariance C'", 3: "Chebyshev normal equations"}
 

@@ -336,6 +336,8 @@ struct GradWs {
     Grow<double> Porb, Vel, Jac, Gv, GradOrb;
     Grow<int> TooFast, EpStart, EpPix;
     bool epochs_valid = false;
+    // psoap_chunk_lnlike_tv_grad (timevar_kernels.hpp): the group's time scales and dlnL/dtau
+    Grow<double> Tau, GradTau;
 };
 
 }  // namespace psoap

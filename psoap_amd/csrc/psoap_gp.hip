@@ -32,6 +32,7 @@
 #include "calibrate_kernels.hpp"
 #include "grad_kernels.hpp"
 #include "orbit_grad_kernels.hpp"
+#include "timevar_kernels.hpp"
 #include "fisher_kernels.hpp"
 #include "vel_fisher_kernels.hpp"
 #include "vel_newton_kernels.hpp"
@@ -160,6 +161,7 @@ struct psoap_chunk {
     Grow<double> dFl, dSigma, dGrid;
     Grow<int32_t> dEpoch;
     int n_epochs = 0;
+    Grow<double> dTimes;     // N observation times of the pixels in days (psoap_chunk_set_times; null until then)
     // workspaces
     Grow<double> dK;         // max_batch x Npad x ld
     Grow<double> dWt;        // max_batch x 2 x 128 x 128 (the persistent kernel alternates two per matrix)
@@ -331,6 +333,7 @@ static int configure_kernels(int device)
     HIP_TRY((dag_set_lds<false, true>()));      // the stream's
     HIP_TRY(predict_configure_kernels());
     HIP_TRY(grad_configure_kernels());
+    HIP_TRY(tv_configure_kernels());
     HIP_TRY(fisher_configure_kernels());
     HIP_TRY(vel_fisher_configure_kernels());
     HIP_TRY(vel_newton_configure_kernels());
@@ -2135,9 +2138,16 @@ static int grad_ws_need(psoap_chunk* h, GradWs& w, int G, size_t mstride, bool a
 }
 
 // K (upper tiles) of the nb matrices whose grids and hyper-parameters are in w.Lwl and w.Gp, into w.A as the caller lays it out
-static void launch_grad_fill(const psoap_chunk* h, GradWs& w, hipStream_t s, int nb, int c, size_t mstride, int ld)
+// (`tv`: under the time-variable kernel -- k_fill_sym_tv with the handle's times and w.Tau)
+static void launch_grad_fill(const psoap_chunk* h, GradWs& w, hipStream_t s, int nb, int c, size_t mstride, int ld, bool tv = false)
 {
     with_components(c, [&](auto nc) {
+        if (tv) {
+            hipLaunchKernelGGL(k_fill_sym_tv<nc()>, dim3(h->P * (h->P + 1) / 2, nb), dim3(256), 0, s, w.A.p, mstride, ld, h->N, h->P,
+                               (const double*)w.Lwl.p, (const double*)h->dTimes.p, (const double*)w.Gp.p, (const double*)w.Tau.p,
+                               (const double*)h->dSigma.p, 1);
+            return;
+        }
         hipLaunchKernelGGL(k_fill_sym<nc()>, dim3(h->P * (h->P + 1) / 2, nb), dim3(256), 0, s, w.A.p, mstride, ld, h->N, h->P,
                            (const double*)w.Lwl.p, (const double*)w.Gp.p, (const double*)h->dSigma.p, 1);
     });
@@ -2231,12 +2241,12 @@ static int grad_epoch_lists(psoap_chunk* h, GradWs& w, hipStream_t s)
 
 // The staged factorisation of [K | I] for the nb matrices whose grids and hyper-parameters are in w.Lwl and w.Gp: afterwards
 // the appended block holds W = U^-T, w.R holds z = U^-T (fl - mu_GP) and w.Acc the block records.
-static int grad_factor(psoap_chunk* h, GradWs& w, hipStream_t s, int nb, int c, double mu_GP)
+static int grad_factor(psoap_chunk* h, GradWs& w, hipStream_t s, int nb, int c, double mu_GP, bool tv = false)
 {
     const int N = h->N, Npad = h->Npad, P = h->P, ld = 2 * h->Npad;
     const size_t mstride = (size_t)Npad * ld;
     if (int rc = prof_launch(h, s, PSOAP_K_FILL, 0.0, (double)nb * 12.0 * N * (N + 1.0), [&] {
-            launch_grad_fill(h, w, s, nb, c, mstride, ld);
+            launch_grad_fill(h, w, s, nb, c, mstride, ld, tv);
             hipLaunchKernelGGL(k_grad_init, dim3(P * (P + 1) / 2, nb), dim3(256), 0, s, w.A.p, mstride, ld, Npad, P);
         })) return rc;
     if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
@@ -2289,6 +2299,7 @@ static int orbit_back(psoap_chunk* h, GradWs& w, hipStream_t s, int nb, int c, i
 // [K | I | Ht] and [M | Xt] (marg_grad_plan.hpp): what grad_run, fisher_run and loo_run read instead of asking which.
 struct Factored {
     bool marg;
+    bool tv;                     // K under the time-variable kernel (timevar_kernels.hpp; plain only): the fill reads w.Tau
     int G;                       // matrices per group
     int ld;                      // doubles per row of a matrix in w.A, mstride from one matrix to the next
     size_t mstride;
@@ -2307,12 +2318,13 @@ static int marg_ws_need(psoap_chunk* h, MargWs& m, int G, bool cov);
 static int marg_grad_factor(psoap_chunk* h, const Factored& fac, hipStream_t s, int nb, int c, double mu_GP);
 
 // ... of a call with B matrices; the workspaces it points into exist afterwards, empty until factored_ws_need
-static Factored factored(psoap_chunk* h, bool marg, int B)
+static Factored factored(psoap_chunk* h, bool marg, int B, bool tv = false)
 {
     const int Npad = h->Npad;
     if (!h->gws) h->gws.reset(new GradWs());
     Factored fac{};
     fac.marg = fac.parts = marg;
+    fac.tv = tv;
     if (!marg) {
         fac.G = grad_group_size(B, Npad);
         fac.ld = 2 * Npad;
@@ -2364,7 +2376,7 @@ static int factor_group(psoap_chunk* h, const Factored& fac, hipStream_t s, int 
                         const X* extra = nullptr)
 {
     GradWs& w = *h->gws;
-    if (int rc = fac.marg ? marg_grad_factor(h, fac, s, nb, c, mu_GP) : grad_factor(h, w, s, nb, c, mu_GP)) return rc;
+    if (int rc = fac.marg ? marg_grad_factor(h, fac, s, nb, c, mu_GP) : grad_factor(h, w, s, nb, c, mu_GP, fac.tv)) return rc;
     const bool finish = values && !fac.marg;
     if (!finish && !extra) return 0;
     return prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
@@ -2499,6 +2511,105 @@ extern "C" int psoap_orbit_velocity_jacobian(int device, int model, int B, const
 extern "C" int psoap_chunk_grad_release(psoap_chunk* h)
 {
     return release_ws(h, [&] { h->gws.reset(); });
+}
+
+// ---- time-variable component spectra (timevar_kernels.hpp) ------------------------------------------
+// The value and the gradient under K_ij = sum_c a_c^2 exp(p_c d^2 + q_c dt^2) + sigma_i^2 delta_ij: grad_run's sibling on the
+// same workspace, grouping, factor_group and conventions -- the fill, the contraction and the finishing sums are the
+// time-variable kernels, nothing else differs.  The pixels' times stay with the handle as the flux and sigma do.
+extern "C" int psoap_chunk_set_times(psoap_chunk* h, const double* t)
+{
+    if (!h || !t) FAIL("psoap_chunk_set_times: bad arguments");
+    if (h->stream.open) FAIL("psoap_chunk_set_times: the handle has an open stream (psoap_stream_close first)");
+    DEVICE_SCOPE(h->device);
+    if (set_dev(h)) return 1;
+    HIP_TRY(hipStreamSynchronize(h->streams[0]));       // (a time-variable call in flight reads the old times)
+    NEED(h->dTimes, h->N);
+    HIP_TRY(hipMemcpy(h->dTimes, t, sizeof(double) * h->N, hipMemcpyHostToDevice));
+    return 0;
+}
+
+// a time scale that is no time scale: tau <= 0 or NaN (+inf is the static model)
+static bool tau_refused(const double* tau, int c, int b)
+{
+    bool bad = false;
+    for (int k = 0; k < c; ++k) bad = bad || !(tau[(size_t)b * c + k] > 0.0);
+    return bad;
+}
+
+extern "C" int psoap_chunk_lnlike_tv_grad(psoap_chunk* h, int B, int c, const double* lwl, const double* gp, const double* tau,
+                                          double mu_GP, double* lnp, double* grad_gp, double* grad_tau, double* grad_lwl,
+                                          double* grad_mu)
+{
+    if (!h || !lwl || !gp || !tau || !lnp) FAIL("psoap_chunk_lnlike_tv_grad: bad arguments");
+    if (!grad_gp && (grad_tau || grad_lwl || grad_mu))
+        FAIL("psoap_chunk_lnlike_tv_grad: grad_gp == NULL asks for the value only: grad_tau, grad_lwl and grad_mu must be NULL too");
+    if (grad_gp && !grad_tau) FAIL("psoap_chunk_lnlike_tv_grad: grad_tau goes with grad_gp");
+    if (B < 1) FAIL("psoap_chunk_lnlike_tv_grad: B must be at least 1");
+    if (c < 1 || c > 3) FAIL("number of components must be 1, 2 or 3");
+    if (!h->dTimes) FAIL("psoap_chunk_lnlike_tv_grad: call psoap_chunk_set_times first");
+    if (h->stream.open)
+        FAIL("psoap_chunk_lnlike_tv_grad: the handle has an open stream (psoap_stream_close first; psoap_chunk_set_times refuses one too)");
+    if (h->marg.valid)
+        FAIL("psoap_chunk_lnlike_tv_grad: the handle has a baseline (psoap_chunk_set_baseline): the time-variable kernel under the "
+             "marginalised continuum is not built yet");
+    const bool contract = grad_gp != nullptr;
+    DEVICE_SCOPE(h->device);
+    if (int rc = enter_device(h->device)) return rc;
+    const Factored fac = factored(h, false, B, true);
+    const int N = h->N, Npad = h->Npad, P = h->P, G = fac.G, ld = fac.ld, ntiles = P * (P + 1) / 2;
+    const size_t mstride = fac.mstride;
+    hipStream_t s = h->streams[0];
+    if (int rc = factored_ws_need(h, fac, s, true, contract, c, 0)) return rc;
+    GradWs& w = *h->gws;
+    HIP_TRY(w.Tau.need((size_t)G * 3));
+    if (contract) {
+        HIP_TRY(w.Part.need((size_t)G * ntiles * TV_TILE_DOUBLES));       // (a record is a double longer than the static one)
+        HIP_TRY(w.GradTau.need((size_t)G * 3));
+    }
+    h->recs.clear();
+    std::vector<double> out((size_t)B);
+    for (int b0 = 0; b0 < B; b0 += G) {
+        const int nb = (B - b0 < G) ? B - b0 : G;
+        HIP_TRY(hipMemcpyAsync(w.Lwl, lwl + (size_t)b0 * c * N, sizeof(double) * (size_t)nb * c * N, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(w.Gp, gp + (size_t)b0 * 2 * c, sizeof(double) * (size_t)nb * 2 * c, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(w.Tau, tau + (size_t)b0 * c, sizeof(double) * (size_t)nb * c, hipMemcpyHostToDevice, s));
+        if (int rc = factor_group(h, fac, s, nb, c, mu_GP, true)) return rc;
+        if (contract) {
+            double cunits = 0.0;
+            for (int tj = 0; tj < P; ++tj) cunits += (double)(tj + 1) * (P - tj);
+            if (int rc = prof_launch(h, s, PSOAP_K_GRAD, TILE_FLOPS * cunits * nb, 0.0, [&] {
+                    with_components(c, [&](auto nc) {
+                        hipLaunchKernelGGL(k_tv_grad_contract<nc()>, dim3(ntiles, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s,
+                                           (const double*)w.A.p, mstride, ld, N, Npad, P, (const double*)w.Lwl.p,
+                                           (const double*)h->dTimes.p, (const double*)w.Gp.p, (const double*)w.Tau.p,
+                                           (const double*)w.Alpha.p, w.Part.p);
+                    });
+                })) return rc;
+            if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
+                    hipLaunchKernelGGL(k_tv_grad_finish, dim3(P + 1, nb), dim3(128), 0, s, (const double*)w.Part.p,
+                                       (const double*)w.Alpha.p, (const double*)w.Gp.p, (const double*)w.Tau.p, c, N, Npad, P,
+                                       w.GradGp.p, w.GradTau.p, w.GradX.p, w.GradMu.p);
+                })) return rc;
+        }
+        HIP_TRY(hipMemcpyAsync(out.data() + b0, fac.Out->p, sizeof(double) * (size_t)nb, hipMemcpyDeviceToHost, s));
+        if (contract) {
+            HIP_TRY(hipMemcpyAsync(grad_gp + (size_t)b0 * 2 * c, w.GradGp, sizeof(double) * (size_t)nb * 2 * c, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemcpyAsync(grad_tau + (size_t)b0 * c, w.GradTau, sizeof(double) * (size_t)nb * c, hipMemcpyDeviceToHost, s));
+            if (grad_lwl)
+                HIP_TRY(hipMemcpyAsync(grad_lwl + (size_t)b0 * c * N, w.GradX, sizeof(double) * (size_t)nb * c * N, hipMemcpyDeviceToHost, s));
+            if (grad_mu) HIP_TRY(hipMemcpyAsync(grad_mu + b0, w.GradMu, sizeof(double) * nb, hipMemcpyDeviceToHost, s));
+        }
+        HIP_TRY(hipStreamSynchronize(s));       // the next group reuses the workspace and the caller's arrays are pageable
+    }
+    if (collect_timings(h)) return 1;
+    // a negative hyper-parameter, a tau that is no time scale, a K that does not factor -> -inf, and no gradient there
+    for (int b = 0; b < B; ++b)
+        if (values_out(out.data(), 1, b, proposal_refused(gp, c, b) || tau_refused(tau, c, b), lnp, nullptr) && contract) {
+            poison_gradient(b, c, N, 0, 0, grad_gp, grad_lwl, grad_mu, nullptr, nullptr);
+            for (int k = 0; k < c; ++k) grad_tau[(size_t)b * c + k] = NAN;
+        }
+    return 0;
 }
 
 // ---- Fisher information of the likelihood (fisher_kernels.hpp) --------------------------------------
@@ -3323,6 +3434,39 @@ extern "C" int psoap_fill_sym(int device, int c, int N, const double* lwl, const
     dim3 grid(P * P, 1);
     with_components(c, [&](auto nc) {
         hipLaunchKernelGGL(k_fill_sym<nc()>, grid, dim3(256), 0, 0, dK.p, (size_t)0, Npad, N, P, dLwl.p, dGp.p, dSig.p, 0);
+    });
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy2D(out, sizeof(double) * N, dK, sizeof(double) * Npad, sizeof(double) * N, N,
+                        hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// psoap_fill_sym under the time-variable kernel (timevar_kernels.hpp): t (N), tau (c)
+extern "C" int psoap_fill_sym_tv(int device, int c, int N, const double* lwl, const double* t, const double* gp,
+                                 const double* tau, const double* sigma, double* out)
+{
+    if (c < 1 || c > 3 || N <= 0 || !lwl || !t || !gp || !tau || !out) FAIL("psoap_fill_sym_tv: bad arguments");
+    DEVICE_SCOPE(device);
+    HIP_TRY(hipSetDevice(device));
+    const int Npad = round_up(N, NB), P = Npad / NB;
+    Grow<double> dK, dLwl, dT, dGp, dTau, dSig;
+    HIP_TRY(dK.need((size_t)Npad * Npad));
+    HIP_TRY(dLwl.need((size_t)c * N));
+    HIP_TRY(dT.need(N));
+    HIP_TRY(dGp.need(6));
+    HIP_TRY(dTau.need(3));
+    HIP_TRY(hipMemcpy(dLwl, lwl, sizeof(double) * (size_t)c * N, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dT, t, sizeof(double) * N, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dGp, gp, sizeof(double) * 2 * c, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dTau, tau, sizeof(double) * c, hipMemcpyHostToDevice));
+    if (sigma) {
+        HIP_TRY(dSig.need(N));
+        HIP_TRY(hipMemcpy(dSig, sigma, sizeof(double) * N, hipMemcpyHostToDevice));
+    }
+    dim3 grid(P * P, 1);
+    with_components(c, [&](auto nc) {
+        hipLaunchKernelGGL(k_fill_sym_tv<nc()>, grid, dim3(256), 0, 0, dK.p, (size_t)0, Npad, N, P, (const double*)dLwl.p,
+                           (const double*)dT.p, (const double*)dGp.p, (const double*)dTau.p, (const double*)dSig.p, 0);
     });
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpy2D(out, sizeof(double) * N, dK, sizeof(double) * Npad, sizeof(double) * N, N,

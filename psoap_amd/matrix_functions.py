@@ -52,6 +52,29 @@ def fill_V11_f_g_h(mat, lwl_f, lwl_g, lwl_h, amp_f, l_f, amp_g, l_g, amp_h, l_h)
               [amp_f, l_f, amp_g, l_g, amp_h, l_h])
 
 
+def fill_V11_timevar(mat, lwls, times, gp, tau, sigma=None, device=None):
+    """The symmetric fill under the time-variable kernel (not in the reference; include/psoap_gp.h: psoap_fill_sym_tv), in
+    place like its siblings: ``mat[i, j] = sum_c amp_c^2 exp(p_c (lwls[c, j] - lwls[c, i])^2 - (times[j] - times[i])^2 /
+    (2 tau_c^2))`` for ``lwls`` (c, N), ``times`` (N,), ``gp = (amp_0, l_0, ...)`` and ``tau`` (c,).  With every
+    ``tau = inf`` the matrix is bit-identical to ``fill_V11_f`` / ``_f_g`` / ``_f_g_h``."""
+    lwls = as_f64(np.atleast_2d(as_f64(lwls)))
+    c, n_vec = lwls.shape
+    N = len(mat)
+    if n_vec < N:
+        raise ValueError("wavelength vector shorter than the matrix")
+    lwls = as_f64(lwls[:, :N])
+    times = as_f64(as_f64(times)[:N], (N,))
+    gp = as_f64(gp, (2 * c,))
+    tau = as_f64(np.atleast_1d(as_f64(tau)), (c,))
+    out = _target(mat, (N, N))
+    sig = None if sigma is None else as_f64(sigma, (N,))
+    dev = _lib.default_device() if device is None else device
+    check(_lib.load().psoap_fill_sym_tv(dev, c, N, dptr(lwls), dptr(times), dptr(gp), dptr(tau),
+                                        None if sig is None else dptr(sig), dptr(out)), "psoap_fill_sym_tv")
+    if out is not mat:
+        mat[...] = out
+
+
 def fill_V12_f(mat, lwl_f, lwl_predict, amp_f, l_f):
     lwl_f = as_f64(lwl_f)
     lwl_predict = as_f64(lwl_predict)
