@@ -165,7 +165,7 @@ int psoap_chunk_grad_release(psoap_chunk *h);
  *   d lnp / d tau_c = 1/2 a_c^2 / tau_c^3 sum_ij Q_ij e_cij dt_ij^2
  * One exp per element and component: the argument is evaluated as a = p * d * d, then
  * a = a + q * dt * dt, without contraction, and the underflow shortcut works on the sum
- * (csrc/timevar_kernels.hpp).  The factorisation, alpha and the product are those of
+ * (csrc/fill_kernels.hpp, TV).  The factorisation, alpha and the product are those of
  * psoap_chunk_lnlike_grad; no atomics, the same arguments give the same bits alone or in
  * any batch.
  * Bit-identity at tau = inf: q = -0, the added term is -0 and a keeps its bits, so with

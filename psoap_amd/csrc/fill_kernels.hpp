@@ -11,6 +11,16 @@
 // (a wave writes four 256-byte row segments per instruction).  Arithmetic mirrors the reference exactly
 // (no FMA contraction in p*r*r and in the component sum), so the only
 // difference from libm is the device exp().
+//
+// Time-variable component spectra (`TV`; not in the reference, whose paper names it as the next step): a temporal factor,
+//   K_ij = sum_c a_c^2 exp(p_c d_cij^2 + q_c dt_ij^2) + sigma_i^2 delta_ij
+//   d_cij = x_c[j] - x_c[i],  p_c = -1/2 c_kms^2 / l_c^2;     dt_ij = t[j] - t[i],  q_c = -1/2 / tau_c^2
+// t[i] is the observation time of pixel i (days), tau_c the time scale over which component c's spectrum drifts;
+// tau_c = +inf is the static model.  One exp: the temporal term joins the argument the kernels already form --
+// a = p2 * d * d, then a = a + q2 * dt * dt, both without contraction, in that order -- so the cost is a multiply-add per
+// element and the wave-uniform underflow shortcut works on the combined argument.  Bit-identity at tau = inf:
+// q2 = -0.5 / (tau * tau) = -0, the added term (-0 * dt) * dt is -0 for every finite dt, and a + (-0) has the bits of a
+// (a = -0 included): k_fill_sym_tv then writes the matrix of k_fill_sym.
 #pragma once
 #include "common.hpp"
 
@@ -34,6 +44,13 @@ __device__ inline void load_gp(const double* __restrict__ gp, int C, GpDev& g)
             g.p2[c] = 0.0;
         }
     }
+}
+
+// q_c = -1/2 / tau_c^2 as every time-variable kernel rounds it (tau = inf: -0)
+__device__ __forceinline__ double tv_q2(double tau)
+{
+#pragma clang fp contract(off)
+    return -0.5 / (tau * tau);
 }
 
 template <int C>
@@ -237,6 +254,121 @@ __global__ __launch_bounds__(256) void k_fill_sym(double* __restrict__ Kbase, si
                 v.y = (jb == i) ? 1.0 : 0.0;
             }
             // (non-temporal stores measured slower here: 5.4 vs 5.75 TB/s at c = 1, no difference at c = 2, 3)
+            *reinterpret_cast<d2*>(Km + (size_t)i * ld + ja) = v;
+        }
+    }
+}
+
+// k_fill_sym (fill_kernels.hpp) with the temporal term: t (N) the pixels' times, tau (B, C).  Everything else -- the
+// layout, one exp_nonpos_batch<8> per component and step, the underflow shortcut, the diagonal rule, the identity
+// padding, upper_only -- is k_fill_sym's.
+template <int C>
+__global__ __launch_bounds__(256) void k_fill_sym_tv(double* __restrict__ Kbase, size_t mat_stride, int ld, int N, int P,
+                                                     const double* __restrict__ lwl, const double* __restrict__ t,
+                                                     const double* __restrict__ gp, const double* __restrict__ tau,
+                                                     const double* __restrict__ sigma, int upper_only)
+{
+    __shared__ double xrow[C][NB];
+    __shared__ double trow[NB];
+    __shared__ double srow[NB];
+    const int b = blockIdx.y;
+    int ti, tj;
+    if (upper_only) {
+        decode_upper(blockIdx.x, P, ti, tj);
+    } else {
+        ti = blockIdx.x / P;
+        tj = blockIdx.x % P;
+    }
+    const int tid = threadIdx.x;
+    const int i0 = ti * NB, j0 = tj * NB;
+    const double* lw = lwl + (size_t)b * C * N;
+    GpDev g;
+    load_gp(gp + (size_t)b * 2 * C, C, g);
+    double q2[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) q2[c] = tv_q2(tau[(size_t)b * C + c]);
+    double dsum = g.a2[0];
+    {
+#pragma clang fp contract(off)
+        for (int c = 1; c < C; ++c) dsum = dsum + g.a2[c];
+    }
+
+    if (tid < NB) {
+        int i = i0 + tid;
+#pragma unroll
+        for (int c = 0; c < C; ++c) xrow[c][tid] = (i < N) ? lw[(size_t)c * N + i] : 0.0;
+        trow[tid] = (i < N) ? t[i] : 0.0;
+        double s = (sigma != nullptr && i < N) ? sigma[i] : 0.0;
+        srow[tid] = s * s;
+    }
+    // (the patch shape of k_fill_sym: wave w owns the 32-column block w, a step covers 16 rows x 32 columns)
+    const int w = tid >> 6, rg = (tid >> 4) & 3, cp = tid & 15;
+    const int ja = j0 + 32 * w + 2 * cp, jb = ja + 1;
+    double xa[C], xb[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        xa[c] = (ja < N) ? lw[(size_t)c * N + ja] : 0.0;
+        xb[c] = (jb < N) ? lw[(size_t)c * N + jb] : 0.0;
+    }
+    const double ta = (ja < N) ? t[ja] : 0.0, tb = (jb < N) ? t[jb] : 0.0;
+    __syncthreads();
+
+    double* Km = Kbase + (size_t)b * mat_stride;
+#pragma unroll 1
+    for (int g4 = 0; g4 < NB / 16; ++g4) {
+        double va[4], vb[4];
+        double dta[4], dtb[4];
+#pragma unroll
+        for (int s4 = 0; s4 < 4; ++s4) {
+            const double tr = trow[16 * g4 + rg + 4 * s4];
+            dta[s4] = ta - tr;
+            dtb[s4] = tb - tr;
+        }
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+#pragma clang fp contract(off)
+            double a[8], e[8];
+            bool live = false;
+#pragma unroll
+            for (int s4 = 0; s4 < 4; ++s4) {
+                const double xi = xrow[c][16 * g4 + rg + 4 * s4];
+                const double da = xa[c] - xi, db = xb[c] - xi;
+                a[2 * s4] = g.p2[c] * da * da;
+                a[2 * s4] = a[2 * s4] + q2[c] * dta[s4] * dta[s4];
+                a[2 * s4 + 1] = g.p2[c] * db * db;
+                a[2 * s4 + 1] = a[2 * s4 + 1] + q2[c] * dtb[s4] * dtb[s4];
+                live = live || !(a[2 * s4] <= -746.0) || !(a[2 * s4 + 1] <= -746.0);
+            }
+            if (__builtin_amdgcn_ballot_w64(live) != 0ull) {
+                exp_nonpos_batch<8>(a, e);
+#pragma unroll
+                for (int k = 0; k < 8; ++k) e[k] = g.a2[c] * e[k];
+            } else {
+#pragma unroll
+                for (int k = 0; k < 8; ++k) e[k] = 0.0;
+            }
+#pragma unroll
+            for (int s4 = 0; s4 < 4; ++s4) {
+                va[s4] = (c == 0) ? e[2 * s4] : va[s4] + e[2 * s4];
+                vb[s4] = (c == 0) ? e[2 * s4 + 1] : vb[s4] + e[2 * s4 + 1];
+            }
+        }
+#pragma unroll
+        for (int s4 = 0; s4 < 4; ++s4) {
+            const int r = 16 * g4 + rg + 4 * s4;
+            const int i = i0 + r;
+            d2 v;
+            if (i < N) {
+                double x = (ja < N) ? va[s4] : 0.0;
+                double y = (jb < N) ? vb[s4] : 0.0;
+                if (ja == i) x = dsum + srow[r];
+                if (jb == i) y = dsum + srow[r];
+                v.x = x;
+                v.y = y;
+            } else {
+                v.x = (ja == i) ? 1.0 : 0.0;
+                v.y = (jb == i) ? 1.0 : 0.0;
+            }
             *reinterpret_cast<d2*>(Km + (size_t)i * ld + ja) = v;
         }
     }

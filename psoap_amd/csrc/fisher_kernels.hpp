@@ -180,7 +180,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void k_fisher_gemm(const double* _
 // component e_c = exp(p_c d^2) once per element, and the sums
 //   hyper-parameters  sum w q e_c, sum w q e_c d^2   (w = 2 off the diagonal: the element stands for (i,j) and (j,i); 1 on it)
 //   rows of block ti  sum_j q e_c d;     rows of block tj  -sum_i q e_c d
-// in the tile's own GRAD_TILE_DOUBLES of `part` (the gradient's layout: k_grad_finish adds them up).  A diagonal tile takes
+// in the tile's own GradTile<false>::DOUBLES of `part` (the gradient's layout: k_grad_finish adds them up).  A diagonal tile takes
 // i <= j only; rows and columns >= N are masked (G_t is exactly zero there).
 template <int C>
 __global__ __launch_bounds__(GEMM_THREADS, 2) void k_fisher_contract(const double* __restrict__ Kinv, const double* __restrict__ Z,
@@ -288,18 +288,18 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void k_fisher_contract(const doubl
         }
     }
     __syncthreads();
-    double* out = part + (size_t)blockIdx.x * GRAD_TILE_DOUBLES;
+    double* out = part + (size_t)blockIdx.x * GradTile<false>::DOUBLES;
     {
         const int side = tid >> 7, idx = tid & 127;
         const int src = side ? CS : RS;
 #pragma unroll
         for (int c = 0; c < C; ++c)
-            out[(side ? GRAD_COLS_OFF : GRAD_ROWS_OFF) + c * NB + idx] =
+            out[(side ? GradTile<false>::COLS_OFF : GradTile<false>::ROWS_OFF) + c * NB + idx] =
                 psoap_smem[src + c * NB + idx] + psoap_smem[src + (3 + c) * NB + idx];
     }
     if (tid < 2 * C)
-        out[GRAD_HYP_OFF + tid] = ((psoap_smem[HS + tid] + psoap_smem[HS + 6 + tid]) + psoap_smem[HS + 12 + tid]) +
-                                  psoap_smem[HS + 18 + tid];
+        out[GradTile<false>::HYP_OFF + tid] = ((psoap_smem[HS + tid] + psoap_smem[HS + 6 + tid]) + psoap_smem[HS + 12 + tid]) +
+                                              psoap_smem[HS + 18 + tid];
 }
 
 // F_mu = 1^T K^-1 1 = |W 1|^2 in two fixed-order stages.  y[k] = sum of row k of W over its columns q <= k, q < N (the rest is

@@ -18,14 +18,35 @@
 // K^-1 is never stored: k_grad_contract forms one 128 x 128 tile of W^T W in the MFMA accumulators and contracts it with
 // the covariance derivatives in its epilogue.  Every sum runs in a fixed order and no kernel uses an atomic: two calls
 // with the same arguments return the same bits, whatever the batch around a matrix.
+//
+// Under the time-variable kernel of fill_kernels.hpp (`TV`), e_cij = exp(p_c d_cij^2 + q_c dt_ij^2): the gradient keeps its
+// formulas and gains
+//   dlnL/dtau_c = 1/2 a_c^2 / tau_c^3 sum_ij Q_ij e_cij dt_ij^2            (exactly 0 at tau_c = inf)
+// The factorisation, alpha and the product W_ti^T W_tj are the same; the epilogue of the contraction forms the argument as the
+// fill does (so at tau = inf the value and the static gradient have the static bits) and carries one more sum per
+// component, and the finishing sums add it up.
 #pragma once
 #include "chol_kernels.hpp"
 #include "fill_kernels.hpp"
 
 namespace psoap {
 
-// doubles per tile in the partial-sum workspace: row sums [3][128], column sums [3][128], 2 x 3 hyper-parameter sums (+ 2)
-constexpr int GRAD_ROWS_OFF = 0, GRAD_COLS_OFF = 3 * NB, GRAD_HYP_OFF = 6 * NB, GRAD_TILE_DOUBLES = 6 * NB + 8;
+// One tile of the contraction, static or time-variable: its record in the partial-sum workspace -- row sums [3][128], column
+// sums [3][128], then HYP sums per component (sa, sl and under TV st; the static record has two spare doubles) -- and the map
+// of the epilogue's LDS.  GradTile<false> is also the record of fisher_kernels.hpp.
+template <bool TV>
+struct GradTile {
+    static constexpr int HYP = TV ? 3 : 2;
+    static constexpr int ROWS_OFF = 0, COLS_OFF = 3 * NB, HYP_OFF = 6 * NB, DOUBLES = 6 * NB + (TV ? 9 : 8);
+    static constexpr int XS = 0;                            // [2][3][NB]: abscissae of the tile's rows (side 0) and columns (side 1)
+    static constexpr int AL = XS + 6 * NB;                  // [2][NB]: alpha likewise
+    static constexpr int TS = AL + 2 * NB;                  // [2][NB]: times likewise (TV only)
+    static constexpr int RS = TS + (TV ? 2 * NB : 0);       // [2 wc][3][NB]: row sums of the two wave columns
+    static constexpr int CS = RS + 6 * NB;                  // [2 wr][3][NB]: column sums of the two wave rows
+    static constexpr int HS = CS + 6 * NB;                  // [4 waves][WS]
+    static constexpr int WS = 3 * HYP;
+    static_assert((HS + 4 * WS) * sizeof(double) <= GEMM_LDS_BYTES, "the epilogue fits the operand buffers");
+};
 
 __host__ __device__ inline int upper_index(int ti, int tj, int P) { return ti * P - ti * (ti - 1) / 2 + (tj - ti); }
 
@@ -108,20 +129,21 @@ __global__ void k_grad_alpha_finish(const double* __restrict__ partial, int nsla
 //   rows of block ti  sum_j q e_c d;     rows of block tj  -sum_i q e_c d   (the mirrored element has -d)
 // A diagonal tile takes i <= j only; rows and columns >= N are masked.  The components are walked one after the other
 // (the accumulators leave few registers), the tile's sums meet in LDS -- the operand buffers of the product, free by then --
-// in a fixed order, and the workgroup stores them to its own GRAD_TILE_DOUBLES of `part`.
-// The epilogue: everything after the product, on the tile t = (K^-1)[ti][tj] in the accumulators (one function, two callers:
-// k_grad_contract below and k_marg_grad_contract of marg_grad_kernels.hpp, whose t is the tile of (K + Ht Ht^T)^-1).
-template <int C>
+// in a fixed order, and the workgroup stores them to its own GradTile<TV>::DOUBLES of `part`.
+// The epilogue: everything after the product, on the tile t = (K^-1)[ti][tj] in the accumulators (one function, three
+// callers: the two kernels below and k_marg_grad_contract of marg_grad_kernels.hpp, whose t is the tile of (K + Ht Ht^T)^-1).
+// TV: e_c = exp(p_c d^2 + q_c dt^2) from `times` (N) and tau (B, C), the tile's row and column times beside its abscissae in
+// LDS, and one more sum per component, st = sum w q e_c dt^2; sa, sl and the row and column sums keep their formulas and
+// their order.
+template <int C, bool TV = false>
 __device__ __forceinline__ void grad_contract_epilogue(const Tile& t, int b, int ti, int tj, int tile_index, int N, int Npad,
                                                        int P, const double* __restrict__ lwl, const double* __restrict__ gp,
-                                                       const double* __restrict__ alpha, double* __restrict__ part)
+                                                       const double* __restrict__ alpha, double* __restrict__ part,
+                                                       const double* __restrict__ times = nullptr,
+                                                       const double* __restrict__ tau = nullptr)
 {
-    constexpr int XS = 0;                 // [2][3][NB]: abscissae of the tile's rows (side 0) and columns (side 1)
-    constexpr int AL = XS + 6 * NB;       // [2][NB]: alpha likewise
-    constexpr int RS = AL + 2 * NB;       // [2 wc][3][NB]: row sums of the two wave columns
-    constexpr int CS = RS + 6 * NB;       // [2 wr][3][NB]: column sums of the two wave rows
-    constexpr int HS = CS + 6 * NB;       // [4 waves][6]
-    static_assert((HS + 24) * sizeof(double) <= GEMM_LDS_BYTES, "the epilogue fits the operand buffers");
+    using L = GradTile<TV>;
+    constexpr int XS = L::XS, AL = L::AL, RS = L::RS, CS = L::CS, HS = L::HS, WS = L::WS;
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
     const int wr = wave >> 1, wc = wave & 1;
@@ -132,6 +154,7 @@ __device__ __forceinline__ void grad_contract_epilogue(const Tile& t, int b, int
 #pragma unroll
         for (int c = 0; c < C; ++c) psoap_smem[XS + (side * 3 + c) * NB + idx] = (g < N) ? lw[(size_t)c * N + g] : 0.0;
         psoap_smem[AL + side * NB + idx] = alpha[(size_t)b * Npad + g];
+        if constexpr (TV) psoap_smem[L::TS + side * NB + idx] = (g < N) ? times[g] : 0.0;
     }
     __syncthreads();
     const bool diag_tile = ti == tj;
@@ -143,6 +166,8 @@ __device__ __forceinline__ void grad_contract_epilogue(const Tile& t, int b, int
             const double l = gp[(size_t)b * 2 * C + 2 * c + 1];      // (as load_gp rounds it)
             p2 = -0.5 * (C_KMS * C_KMS) / (l * l);
         }
+        [[maybe_unused]] double q2;
+        if constexpr (TV) q2 = tv_q2(tau[(size_t)b * C + c]);
         double xj[4], aj[4], colacc[4];
         bool jok[4];
 #pragma unroll
@@ -154,6 +179,7 @@ __device__ __forceinline__ void grad_contract_epilogue(const Tile& t, int b, int
             colacc[n] = 0.0;
         }
         double sa = 0.0, sl = 0.0;
+        [[maybe_unused]] double st = 0.0;
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
             double xi[4], ai[4], rowacc[4];
@@ -167,13 +193,20 @@ __device__ __forceinline__ void grad_contract_epilogue(const Tile& t, int b, int
 #pragma unroll
             for (int n = 0; n < 4; ++n) {
                 const int col = tile_col(wc, n, lane);
+                // (the times are read where they are used: two more values per row and column kept across the tile would
+                // not fit beside the accumulators)
+                [[maybe_unused]] double tcol;
+                if constexpr (TV) tcol = psoap_smem[L::TS + NB + col];
                 double d[4], a[4], e[4];
                 bool live = false;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
 #pragma clang fp contract(off)
                     d[r] = xj[n] - xi[r];
+                    [[maybe_unused]] double dt;
+                    if constexpr (TV) dt = tcol - psoap_smem[L::TS + tile_row(wr, m, lane, r)];
                     a[r] = p2 * d[r] * d[r];
+                    if constexpr (TV) a[r] = a[r] + q2 * dt * dt;
                     live = live || !(a[r] <= -746.0);
                 }
                 if (__builtin_amdgcn_ballot_w64(live) == 0ull) continue;      // exp() = +0 for the whole wave: nothing to add
@@ -185,8 +218,17 @@ __device__ __forceinline__ void grad_contract_epilogue(const Tile& t, int b, int
                     const double qe = ok ? (ai[r] * aj[n] - t.acc[m][n][r]) * e[r] : 0.0;
                     const double w = (diag_tile && row == col) ? 1.0 : 2.0;
                     const double qed = qe * d[r];
+                    [[maybe_unused]] double dt;
+                    if constexpr (TV) {
+                        // dt again from LDS, through an index the optimiser cannot match with the one above: four time
+                        // differences kept across the exp are registers the kernel does not have
+                        int trow = L::TS + row;
+                        asm volatile("" : "+v"(trow));
+                        dt = tcol - psoap_smem[trow];
+                    }
                     sa = fma(w, qe, sa);
                     sl = fma(w * qed, d[r], sl);
+                    if constexpr (TV) st = fma(w * qe * dt, dt, st);
                     rowacc[r] += qed;
                     colacc[n] -= qed;
                 }
@@ -209,25 +251,44 @@ __device__ __forceinline__ void grad_contract_epilogue(const Tile& t, int b, int
         for (int off = 32; off >= 1; off >>= 1) {
             sa += __shfl_xor(sa, off, 64);
             sl += __shfl_xor(sl, off, 64);
+            if constexpr (TV) st += __shfl_xor(st, off, 64);
         }
         if (lane == 0) {
-            psoap_smem[HS + wave * 6 + 2 * c] = sa;
-            psoap_smem[HS + wave * 6 + 2 * c + 1] = sl;
+            psoap_smem[HS + wave * WS + L::HYP * c] = sa;
+            psoap_smem[HS + wave * WS + L::HYP * c + 1] = sl;
+            if constexpr (TV) psoap_smem[HS + wave * WS + L::HYP * c + 2] = st;
         }
     }
     __syncthreads();
-    double* out = part + ((size_t)b * (P * (P + 1) / 2) + tile_index) * GRAD_TILE_DOUBLES;
+    double* out = part + ((size_t)b * (P * (P + 1) / 2) + tile_index) * L::DOUBLES;
     {
         const int side = tid >> 7, idx = tid & 127;
         const int src = side ? CS : RS;
 #pragma unroll
         for (int c = 0; c < C; ++c)
-            out[(side ? GRAD_COLS_OFF : GRAD_ROWS_OFF) + c * NB + idx] =
+            out[(side ? L::COLS_OFF : L::ROWS_OFF) + c * NB + idx] =
                 psoap_smem[src + c * NB + idx] + psoap_smem[src + (3 + c) * NB + idx];
     }
-    if (tid < 2 * C)
-        out[GRAD_HYP_OFF + tid] = ((psoap_smem[HS + tid] + psoap_smem[HS + 6 + tid]) + psoap_smem[HS + 12 + tid]) +
-                                  psoap_smem[HS + 18 + tid];
+    if (tid < L::HYP * C)
+        out[L::HYP_OFF + tid] = ((psoap_smem[HS + tid] + psoap_smem[HS + WS + tid]) + psoap_smem[HS + 2 * WS + tid]) +
+                                psoap_smem[HS + 3 * WS + tid];
+}
+
+// The product and the epilogue: what k_grad_contract and k_tv_grad_contract are.  grid (P (P + 1) / 2, B)
+template <int C, bool TV>
+__device__ __forceinline__ void grad_contract_tile(const double* __restrict__ Abase, size_t mat_stride, int ld, int N, int Npad,
+                                                   int P, const double* __restrict__ lwl, const double* __restrict__ gp,
+                                                   const double* __restrict__ alpha, double* __restrict__ part,
+                                                   const double* __restrict__ times, const double* __restrict__ tau)
+{
+    const int b = blockIdx.y;
+    int ti, tj;
+    decode_upper(blockIdx.x, P, ti, tj);
+    const double* W = Abase + (size_t)b * mat_stride + Npad + (size_t)NB * tj * ld;
+    Tile t;
+    t.zero();
+    tile_gemm_tn(t, W + NB * ti, (size_t)ld, W + NB * tj, (size_t)ld, Npad - NB * tj, ti == tj);
+    grad_contract_epilogue<C, TV>(t, b, ti, tj, (int)blockIdx.x, N, Npad, P, lwl, gp, alpha, part, times, tau);
 }
 
 template <int C>
@@ -238,45 +299,55 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void k_grad_contract(const double*
                                                                   const double* __restrict__ alpha,
                                                                   double* __restrict__ part)
 {
-    const int b = blockIdx.y;
-    int ti, tj;
-    decode_upper(blockIdx.x, P, ti, tj);
-    const double* W = Abase + (size_t)b * mat_stride + Npad + (size_t)NB * tj * ld;
-    Tile t;
-    t.zero();
-    tile_gemm_tn(t, W + NB * ti, (size_t)ld, W + NB * tj, (size_t)ld, Npad - NB * tj, ti == tj);
-    grad_contract_epilogue<C>(t, b, ti, tj, (int)blockIdx.x, N, Npad, P, lwl, gp, alpha, part);
+    grad_contract_tile<C, false>(Abase, mat_stride, ld, N, Npad, P, lwl, gp, alpha, part, nullptr, nullptr);
+}
+
+template <int C>
+__global__ __launch_bounds__(GEMM_THREADS, 2) void k_tv_grad_contract(const double* __restrict__ Abase, size_t mat_stride,
+                                                                     int ld, int N, int Npad, int P,
+                                                                     const double* __restrict__ lwl,
+                                                                     const double* __restrict__ times,
+                                                                     const double* __restrict__ gp,
+                                                                     const double* __restrict__ tau,
+                                                                     const double* __restrict__ alpha,
+                                                                     double* __restrict__ part)
+{
+    grad_contract_tile<C, true>(Abase, mat_stride, ld, N, Npad, P, lwl, gp, alpha, part, times, tau);
 }
 
 // The tiles' partial sums in tile order.  grid (P + 1, B), 128 threads.
 //   blocks x < P:  grad_x[b][c][128 x + i]: the column sums of tiles (ti, x), ti <= x, then the row sums of tiles (x, tj), tj >= x
-//   block  x == P: grad_gp[b][2C] and grad_mu[b] = sum_i alpha_i: thread k adds every 128th term, the 128 sums meet in a tree
-__global__ __launch_bounds__(128) void k_grad_finish(const double* __restrict__ part, const double* __restrict__ alpha,
-                                                     const double* __restrict__ gp, int C, int N, int Npad, int P,
-                                                     double* __restrict__ grad_gp, double* __restrict__ grad_x,
-                                                     double* __restrict__ grad_mu)
+//   block  x == P: the HYP C hyper-parameter sums and sum_i alpha_i: thread k adds every 128th term, the 128 sums meet in a tree
+//                  grad_gp[b][2C], under TV grad_tau[b][c] = 1/2 a_c^2 / tau_c^3 st_c, grad_mu[b]
+template <bool TV>
+__device__ __forceinline__ void grad_finish_sums(const double* __restrict__ part, const double* __restrict__ alpha,
+                                                 const double* __restrict__ gp, int C, int N, int Npad, int P,
+                                                 double* __restrict__ grad_gp, double* __restrict__ grad_x,
+                                                 double* __restrict__ grad_mu, const double* __restrict__ tau,
+                                                 double* __restrict__ grad_tau)
 {
+    using L = GradTile<TV>;
     __shared__ double red[128];
     const int b = blockIdx.y, x = blockIdx.x, tid = threadIdx.x;
     const int ntiles = P * (P + 1) / 2;
-    const double* pb = part + (size_t)b * ntiles * GRAD_TILE_DOUBLES;
+    const double* pb = part + (size_t)b * ntiles * L::DOUBLES;
     const double* gpb = gp + (size_t)b * 2 * C;
     if (x < P) {
         const int i = NB * x + tid;
         for (int c = 0; c < C; ++c) {
             double s = 0.0;
-            for (int ti = 0; ti <= x; ++ti) s += pb[(size_t)upper_index(ti, x, P) * GRAD_TILE_DOUBLES + GRAD_COLS_OFF + c * NB + tid];
-            for (int tj = x; tj < P; ++tj) s += pb[(size_t)upper_index(x, tj, P) * GRAD_TILE_DOUBLES + GRAD_ROWS_OFF + c * NB + tid];
+            for (int ti = 0; ti <= x; ++ti) s += pb[(size_t)upper_index(ti, x, P) * L::DOUBLES + L::COLS_OFF + c * NB + tid];
+            for (int tj = x; tj < P; ++tj) s += pb[(size_t)upper_index(x, tj, P) * L::DOUBLES + L::ROWS_OFF + c * NB + tid];
             const double a = gpb[2 * c], l = gpb[2 * c + 1];
             const double p2 = -0.5 * (C_KMS * C_KMS) / (l * l);
             if (i < N) grad_x[((size_t)b * C + c) * N + i] = -2.0 * p2 * (a * a) * s;
         }
         return;
     }
-    for (int k = 0; k <= 2 * C; ++k) {
+    for (int k = 0; k <= L::HYP * C; ++k) {
         double s = 0.0;
-        if (k < 2 * C) {
-            for (int t = tid; t < ntiles; t += 128) s += pb[(size_t)t * GRAD_TILE_DOUBLES + GRAD_HYP_OFF + k];
+        if (k < L::HYP * C) {
+            for (int t = tid; t < ntiles; t += 128) s += pb[(size_t)t * L::DOUBLES + L::HYP_OFF + k];
         } else {
             for (int i = tid; i < N; i += 128) s += alpha[(size_t)b * Npad + i];
         }
@@ -288,28 +359,52 @@ __global__ __launch_bounds__(128) void k_grad_finish(const double* __restrict__ 
             __syncthreads();
         }
         if (tid == 0) {
-            if (k == 2 * C) {
+            if (k == L::HYP * C) {
                 grad_mu[b] = red[0];
             } else {
-                const double a = gpb[k & ~1], l = gpb[k | 1];
-                grad_gp[(size_t)b * 2 * C + k] = (k & 1) ? 0.5 * (a * a) * (C_KMS * C_KMS) / (l * l * l) * red[0] : a * red[0];
+                const int c = k / L::HYP, what = k % L::HYP;
+                const double a = gpb[2 * c], l = gpb[2 * c + 1];
+                if (what == 0) {
+                    grad_gp[(size_t)b * 2 * C + 2 * c] = a * red[0];
+                } else if (what == 1) {
+                    grad_gp[(size_t)b * 2 * C + 2 * c + 1] = 0.5 * (a * a) * (C_KMS * C_KMS) / (l * l * l) * red[0];
+                } else if constexpr (TV) {
+                    const double tc = tau[(size_t)b * C + c];
+                    grad_tau[(size_t)b * C + c] = 0.5 * (a * a) / (tc * tc * tc) * red[0];
+                }
             }
         }
     }
 }
 
+__global__ __launch_bounds__(128) void k_grad_finish(const double* __restrict__ part, const double* __restrict__ alpha,
+                                                     const double* __restrict__ gp, int C, int N, int Npad, int P,
+                                                     double* __restrict__ grad_gp, double* __restrict__ grad_x,
+                                                     double* __restrict__ grad_mu)
+{
+    grad_finish_sums<false>(part, alpha, gp, C, N, Npad, P, grad_gp, grad_x, grad_mu, nullptr, nullptr);
+}
+
+__global__ __launch_bounds__(128) void k_tv_grad_finish(const double* __restrict__ part, const double* __restrict__ alpha,
+                                                        const double* __restrict__ gp, const double* __restrict__ tau, int C,
+                                                        int N, int Npad, int P, double* __restrict__ grad_gp,
+                                                        double* __restrict__ grad_tau, double* __restrict__ grad_x,
+                                                        double* __restrict__ grad_mu)
+{
+    grad_finish_sums<true>(part, alpha, gp, C, N, Npad, P, grad_gp, grad_x, grad_mu, tau, grad_tau);
+}
+
+// the LDS attribute of every kernel here that takes the operand buffers
 inline hipError_t grad_configure_kernels()
 {
-    const int lds = (int)GEMM_LDS_BYTES;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_grad_panel_update),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_grad_contract<1>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_grad_contract<2>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_grad_contract<3>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    return e;
+    const void* const kernels[] = {
+        reinterpret_cast<const void*>(k_grad_panel_update),
+        reinterpret_cast<const void*>(k_grad_contract<1>),    reinterpret_cast<const void*>(k_grad_contract<2>),
+        reinterpret_cast<const void*>(k_grad_contract<3>),    reinterpret_cast<const void*>(k_tv_grad_contract<1>),
+        reinterpret_cast<const void*>(k_tv_grad_contract<2>), reinterpret_cast<const void*>(k_tv_grad_contract<3>)};
+    for (const void* k : kernels)
+        if (hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GEMM_LDS_BYTES)) return e;
+    return hipSuccess;
 }
 
 // Matrices per group of a gradient call: a call with more proposals walks them group after group through ONE workspace,
@@ -336,7 +431,7 @@ struct GradWs {
     Grow<double> Porb, Vel, Jac, Gv, GradOrb;
     Grow<int> TooFast, EpStart, EpPix;
     bool epochs_valid = false;
-    // psoap_chunk_lnlike_tv_grad (timevar_kernels.hpp): the group's time scales and dlnL/dtau
+    // psoap_chunk_lnlike_tv_grad (the TV kernels above): the group's time scales and dlnL/dtau
     Grow<double> Tau, GradTau;
 };
 

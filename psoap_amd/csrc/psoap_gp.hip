@@ -32,7 +32,6 @@
 #include "calibrate_kernels.hpp"
 #include "grad_kernels.hpp"
 #include "orbit_grad_kernels.hpp"
-#include "timevar_kernels.hpp"
 #include "fisher_kernels.hpp"
 #include "vel_fisher_kernels.hpp"
 #include "vel_newton_kernels.hpp"
@@ -333,7 +332,6 @@ static int configure_kernels(int device)
     HIP_TRY((dag_set_lds<false, true>()));      // the stream's
     HIP_TRY(predict_configure_kernels());
     HIP_TRY(grad_configure_kernels());
-    HIP_TRY(tv_configure_kernels());
     HIP_TRY(fisher_configure_kernels());
     HIP_TRY(vel_fisher_configure_kernels());
     HIP_TRY(vel_newton_configure_kernels());
@@ -2100,14 +2098,17 @@ extern "C" int psoap_lnlike(psoap_chunk* h, int c, const double* lwl, const doub
 // What the analysis paths below share, and what a new one is expected to reuse ("The host layer"): Factored says
 // where things are after a factorisation, plain or marginal, factored_ws_need sizes the workspaces for it and factor_group
 // runs it; launch_grad_fill fills K, staged_row (above) is every block row of every factorisation, launch_alpha makes
-// alpha, orbit_front / orbit_back are the orbit entry, proposal_refused / values_out / poison_gradient the conventions,
-// release_ws the body of a *_release.  The marginal pieces (marg_ws_need, launch_marg_rhs, gram_units, launch_marg_finish)
-// stand with psoap_chunk_lnlike_marg further down.
+// alpha, orbit_front / orbit_back are the orbit entry, proposal_refused / tau_refused / values_out / poison_gradient the
+// conventions, release_ws the body of a *_release.  The time-variable kernel is a flag on the same path, not a path: Factored::tv
+// (grad_run's tau != nullptr) picks the TV fill, contraction and finishing sums and sizes the longer tile record.  The marginal
+// pieces (marg_ws_need, launch_marg_rhs, gram_units, launch_marg_finish) stand with psoap_chunk_lnlike_marg further down.
 
 // The gradient workspace for groups of G matrices of mstride doubles each: what the factorisation needs, always; alpha and
 // its partial sums (`alpha`); the contraction's partial tiles and the three gradients (`contract`); with np > 0 the orbit
-// entry's buffers for c components and np orbital parameters, and the epoch lists of the fold.
-static int grad_ws_need(psoap_chunk* h, GradWs& w, int G, size_t mstride, bool alpha, bool contract, int c = 0, int np = 0)
+// entry's buffers for c components and np orbital parameters, and the epoch lists of the fold.  `tv`: the time scales, the
+// longer tile record of the time-variable contraction and, with `contract`, dlnL/dtau.
+static int grad_ws_need(psoap_chunk* h, GradWs& w, int G, size_t mstride, bool alpha, bool contract, int c = 0, int np = 0,
+                        bool tv = false)
 {
     const int N = h->N, Npad = h->Npad, ne = h->n_epochs;
     HIP_TRY(w.A.need((size_t)G * mstride));
@@ -2120,11 +2121,13 @@ static int grad_ws_need(psoap_chunk* h, GradWs& w, int G, size_t mstride, bool a
         HIP_TRY(w.Alpha.need((size_t)G * Npad));
         HIP_TRY(w.APart.need((size_t)G * ((Npad + 255) / 256) * Npad));
     }
+    if (tv) HIP_TRY(w.Tau.need((size_t)G * 3));
     if (contract) {
-        HIP_TRY(w.Part.need((size_t)G * (h->P * (h->P + 1) / 2) * GRAD_TILE_DOUBLES));
+        HIP_TRY(w.Part.need((size_t)G * (h->P * (h->P + 1) / 2) * (tv ? GradTile<true>::DOUBLES : GradTile<false>::DOUBLES)));
         HIP_TRY(w.GradGp.need((size_t)G * 6));
         HIP_TRY(w.GradX.need((size_t)G * 3 * N));
         HIP_TRY(w.GradMu.need(G));
+        if (tv) HIP_TRY(w.GradTau.need((size_t)G * 3));
     }
     if (np > 0) {
         HIP_TRY(w.Porb.need((size_t)G * np));
@@ -2178,6 +2181,14 @@ static bool proposal_refused(const double* gp, int c, int b, const int* fast = n
     return neg;
 }
 
+// a time scale that is no time scale: tau <= 0 or NaN (+inf is the static model)
+static bool tau_refused(const double* tau, int c, int b)
+{
+    bool bad = false;
+    for (int k = 0; k < c; ++k) bad = bad || !(tau[(size_t)b * c + k] > 0.0);
+    return bad;
+}
+
 // The value record of proposal b (`stride` doubles per proposal: the value and, with stride 5, its four parts) into lnp[b] and,
 // where asked for, parts[4 b]: -inf for a refused proposal whatever the device computed, NaN parts beside a -inf.
 // -> the proposal has no value, and nothing else is to be said about it
@@ -2191,10 +2202,12 @@ static bool values_out(const double* out, int stride, int b, bool refused, doubl
 }
 
 // ... and no gradient there: NaN into proposal b of grad_gp and of every optional output that was asked for
-static void poison_gradient(int b, int c, int N, int ne, int np, double* grad_gp, double* grad_lwl, double* grad_mu,
-                            double* grad_orb, double* grad_vel)
+static void poison_gradient(int b, int c, int N, int ne, int np, double* grad_gp, double* grad_tau, double* grad_lwl,
+                            double* grad_mu, double* grad_orb, double* grad_vel)
 {
     for (int k = 0; k < 2 * c; ++k) grad_gp[(size_t)b * 2 * c + k] = NAN;
+    if (grad_tau)
+        for (int k = 0; k < c; ++k) grad_tau[(size_t)b * c + k] = NAN;
     if (grad_lwl)
         for (size_t k = 0; k < (size_t)c * N; ++k) grad_lwl[(size_t)b * c * N + k] = NAN;
     if (grad_mu) grad_mu[b] = NAN;
@@ -2299,7 +2312,7 @@ static int orbit_back(psoap_chunk* h, GradWs& w, hipStream_t s, int nb, int c, i
 // [K | I | Ht] and [M | Xt] (marg_grad_plan.hpp): what grad_run, fisher_run and loo_run read instead of asking which.
 struct Factored {
     bool marg;
-    bool tv;                     // K under the time-variable kernel (timevar_kernels.hpp; plain only): the fill reads w.Tau
+    bool tv;                     // K under the time-variable kernel (fill_kernels.hpp; plain only): the fill reads w.Tau
     int G;                       // matrices per group
     int ld;                      // doubles per row of a matrix in w.A, mstride from one matrix to the next
     size_t mstride;
@@ -2356,7 +2369,7 @@ static Factored factored(psoap_chunk* h, bool marg, int B, bool tv = false)
 static int factored_ws_need(psoap_chunk* h, const Factored& fac, hipStream_t s, bool values, bool contract, int c = 0, int np = 0)
 {
     GradWs& w = *h->gws;
-    if (int rc = grad_ws_need(h, w, fac.G, fac.mstride, values || fac.marg, contract, c, np)) return rc;
+    if (int rc = grad_ws_need(h, w, fac.G, fac.mstride, values || fac.marg, contract, c, np, fac.tv)) return rc;
     if (!fac.marg) {
         if (values) HIP_TRY(w.Out.need(fac.G));
         return 0;
@@ -2391,22 +2404,24 @@ static int factor_group(psoap_chunk* h, const Factored& fac, hipStream_t s, int 
 
 // Group after group of matrices through factor_group, then the contraction and the finishing sums -- plain, or with `marg`
 // under the handle's baseline (marg_grad_kernels.hpp).  The ln-wavelengths come from the host (lwl: psoap_chunk_lnlike_grad)
-// or, with lwl == nullptr, from the orbits p_orb of `model` (orbit_front, orbit_back).
+// or, with lwl == nullptr, from the orbits p_orb of `model` (orbit_front, orbit_back).  With `tau` (B, c; plain only) K is the
+// time-variable kernel over the handle's times: the TV fill, contraction and finishing sums, and grad_tau beside grad_gp.
+// `contract` false is the value only: no contraction, no finishing sums, no gradient touched.
 static int grad_run(psoap_chunk* h, const char* who, bool marg, int B, int c, const double* lwl, int model, const double* p_orb,
-                    const double* gp, double mu_GP, double* lnp, double* parts, double* grad_gp, double* grad_lwl,
-                    double* grad_mu, double* grad_orb, double* grad_vel)
+                    const double* gp, const double* tau, double mu_GP, double* lnp, double* parts, double* grad_gp,
+                    double* grad_tau, double* grad_lwl, double* grad_mu, double* grad_orb, double* grad_vel, bool contract)
 {
     if (marg)
         if (const char* why = marg_grad_check(B, c, h->marg.valid, h->marg.stale_weight)) FAIL(std::string(who) + ": " + why);
-    const bool orbits = lwl == nullptr;
+    const bool orbits = lwl == nullptr, tv = tau != nullptr;
     DEVICE_SCOPE(h->device);
     if (int rc = enter_device(h->device)) return rc;
-    const Factored fac = factored(h, marg, B);
+    const Factored fac = factored(h, marg, B, tv);
     const int N = h->N, Npad = h->Npad, P = h->P, G = fac.G, ld = fac.ld, ntiles = P * (P + 1) / 2;
     const size_t mstride = fac.mstride;
     const int ne = h->n_epochs, np = orbits ? orbit_n_params(model) : 0;
     hipStream_t s = h->streams[0];
-    if (int rc = factored_ws_need(h, fac, s, true, true, c, np)) return rc;
+    if (int rc = factored_ws_need(h, fac, s, true, contract, c, np)) return rc;
     GradWs& w = *h->gws;
     std::vector<int> fast(orbits ? (size_t)B : 0, 0);
     if (orbits)
@@ -2420,44 +2435,64 @@ static int grad_run(psoap_chunk* h, const char* who, bool marg, int B, int c, co
         else if (int rc = orbit_front(h, w, s, nb, c, model, np, p_orb + (size_t)b0 * np))
             return rc;
         HIP_TRY(hipMemcpyAsync(w.Gp, gp + (size_t)b0 * 2 * c, sizeof(double) * (size_t)nb * 2 * c, hipMemcpyHostToDevice, s));
+        if (tv) HIP_TRY(hipMemcpyAsync(w.Tau, tau + (size_t)b0 * c, sizeof(double) * (size_t)nb * c, hipMemcpyHostToDevice, s));
         if (int rc = factor_group(h, fac, s, nb, c, mu_GP, true)) return rc;
-        double cunits = 0.0;
-        for (int tj = 0; tj < P; ++tj) cunits += (double)(tj + 1) * (P - tj + fac.Q);
-        if (int rc = prof_launch(h, s, PSOAP_K_GRAD, TILE_FLOPS * cunits * nb, 0.0, [&] {
-                with_components(c, [&](auto nc) {
-                    if (marg)
-                        hipLaunchKernelGGL(k_marg_grad_contract<nc()>, dim3(ntiles, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s,
-                                           (const double*)w.A.p, mstride, ld, N, Npad, P, (const double*)w.Lwl.p, (const double*)w.Gp.p,
-                                           (const double*)w.Alpha.p, w.Part.p, (const double*)fac.Vt->p, fac.m_stride, fac.ldm, fac.S);
+        if (contract) {
+            double cunits = 0.0;
+            for (int tj = 0; tj < P; ++tj) cunits += (double)(tj + 1) * (P - tj + fac.Q);
+            if (int rc = prof_launch(h, s, PSOAP_K_GRAD, TILE_FLOPS * cunits * nb, 0.0, [&] {
+                    with_components(c, [&](auto nc) {
+                        if (marg)
+                            hipLaunchKernelGGL(k_marg_grad_contract<nc()>, dim3(ntiles, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s,
+                                               (const double*)w.A.p, mstride, ld, N, Npad, P, (const double*)w.Lwl.p,
+                                               (const double*)w.Gp.p, (const double*)w.Alpha.p, w.Part.p, (const double*)fac.Vt->p,
+                                               fac.m_stride, fac.ldm, fac.S);
+                        else if (tv)
+                            hipLaunchKernelGGL(k_tv_grad_contract<nc()>, dim3(ntiles, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s,
+                                               (const double*)w.A.p, mstride, ld, N, Npad, P, (const double*)w.Lwl.p,
+                                               (const double*)h->dTimes.p, (const double*)w.Gp.p, (const double*)w.Tau.p,
+                                               (const double*)w.Alpha.p, w.Part.p);
+                        else
+                            hipLaunchKernelGGL(k_grad_contract<nc()>, dim3(ntiles, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s,
+                                               (const double*)w.A.p, mstride, ld, N, Npad, P, (const double*)w.Lwl.p,
+                                               (const double*)w.Gp.p, (const double*)w.Alpha.p, w.Part.p);
+                    });
+                })) return rc;
+            if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
+                    if (tv)
+                        hipLaunchKernelGGL(k_tv_grad_finish, dim3(P + 1, nb), dim3(128), 0, s, (const double*)w.Part.p,
+                                           (const double*)w.Alpha.p, (const double*)w.Gp.p, (const double*)w.Tau.p, c, N, Npad, P,
+                                           w.GradGp.p, w.GradTau.p, w.GradX.p, w.GradMu.p);
                     else
-                        hipLaunchKernelGGL(k_grad_contract<nc()>, dim3(ntiles, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s,
-                                           (const double*)w.A.p, mstride, ld, N, Npad, P, (const double*)w.Lwl.p, (const double*)w.Gp.p,
-                                           (const double*)w.Alpha.p, w.Part.p);
-                });
-            })) return rc;
-        if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
-                hipLaunchKernelGGL(k_grad_finish, dim3(P + 1, nb), dim3(128), 0, s, (const double*)w.Part.p, (const double*)w.Alpha.p,
-                                   (const double*)w.Gp.p, c, N, Npad, P, w.GradGp.p, w.GradX.p, w.GradMu.p);
-            })) return rc;
+                        hipLaunchKernelGGL(k_grad_finish, dim3(P + 1, nb), dim3(128), 0, s, (const double*)w.Part.p,
+                                           (const double*)w.Alpha.p, (const double*)w.Gp.p, c, N, Npad, P, w.GradGp.p, w.GradX.p,
+                                           w.GradMu.p);
+                })) return rc;
+        }
         HIP_TRY(hipMemcpyAsync(out.data() + (size_t)b0 * fac.out_stride, fac.Out->p, sizeof(double) * (size_t)nb * fac.out_stride,
                                hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(grad_gp + (size_t)b0 * 2 * c, w.GradGp, sizeof(double) * (size_t)nb * 2 * c, hipMemcpyDeviceToHost, s));
-        if (grad_lwl)
-            HIP_TRY(hipMemcpyAsync(grad_lwl + (size_t)b0 * c * N, w.GradX, sizeof(double) * (size_t)nb * c * N, hipMemcpyDeviceToHost, s));
-        if (grad_mu) HIP_TRY(hipMemcpyAsync(grad_mu + b0, w.GradMu, sizeof(double) * nb, hipMemcpyDeviceToHost, s));
-        if (orbits)
-            if (int rc = orbit_back(h, w, s, nb, c, np, grad_orb + (size_t)b0 * np, grad_vel ? grad_vel + (size_t)b0 * c * ne : nullptr,
-                                    fast.data() + b0))
-                return rc;
+        if (contract) {
+            HIP_TRY(hipMemcpyAsync(grad_gp + (size_t)b0 * 2 * c, w.GradGp, sizeof(double) * (size_t)nb * 2 * c, hipMemcpyDeviceToHost, s));
+            if (tv) HIP_TRY(hipMemcpyAsync(grad_tau + (size_t)b0 * c, w.GradTau, sizeof(double) * (size_t)nb * c, hipMemcpyDeviceToHost, s));
+            if (grad_lwl)
+                HIP_TRY(hipMemcpyAsync(grad_lwl + (size_t)b0 * c * N, w.GradX, sizeof(double) * (size_t)nb * c * N, hipMemcpyDeviceToHost, s));
+            if (grad_mu) HIP_TRY(hipMemcpyAsync(grad_mu + b0, w.GradMu, sizeof(double) * nb, hipMemcpyDeviceToHost, s));
+            if (orbits)
+                if (int rc = orbit_back(h, w, s, nb, c, np, grad_orb + (size_t)b0 * np,
+                                        grad_vel ? grad_vel + (size_t)b0 * c * ne : nullptr, fast.data() + b0))
+                    return rc;
+        }
         HIP_TRY(hipStreamSynchronize(s));       // the next group reuses the workspace and the caller's arrays are pageable
     }
     if (collect_timings(h)) return 1;
-    // a negative hyper-parameter, a faster-than-light orbit, a K (or under the baseline an M) that does not factor -> -inf, and
-    // no gradient there
+    // a negative hyper-parameter, a faster-than-light orbit, a tau that is no time scale, a K (or under the baseline an M) that
+    // does not factor -> -inf, and no gradient there
     for (int b = 0; b < B; ++b)
-        if (values_out(out.data(), fac.out_stride, b, proposal_refused(gp, c, b, orbits ? fast.data() : nullptr), lnp,
-                       fac.parts ? parts : nullptr))
-            poison_gradient(b, c, N, ne, np, grad_gp, grad_lwl, grad_mu, grad_orb, grad_vel);
+        if (values_out(out.data(), fac.out_stride, b,
+                       proposal_refused(gp, c, b, orbits ? fast.data() : nullptr) || (tv && tau_refused(tau, c, b)), lnp,
+                       fac.parts ? parts : nullptr) &&
+            contract)
+            poison_gradient(b, c, N, ne, np, grad_gp, grad_tau, grad_lwl, grad_mu, grad_orb, grad_vel);
     return 0;
 }
 
@@ -2468,8 +2503,8 @@ extern "C" int psoap_chunk_lnlike_grad(psoap_chunk* h, int B, int c, const doubl
     if (B < 1) FAIL("psoap_chunk_lnlike_grad: B must be at least 1");
     if (c < 1 || c > 3) FAIL("number of components must be 1, 2 or 3");
     if (h->stream.open) FAIL("psoap_chunk_lnlike_grad: the handle has an open stream (psoap_stream_close first)");
-    return grad_run(h, "psoap_chunk_lnlike_grad", false, B, c, lwl, -1, nullptr, gp, mu_GP, lnp, nullptr, grad_gp, grad_lwl,
-                    grad_mu, nullptr, nullptr);
+    return grad_run(h, "psoap_chunk_lnlike_grad", false, B, c, lwl, -1, nullptr, gp, nullptr, mu_GP, lnp, nullptr, grad_gp, nullptr,
+                    grad_lwl, grad_mu, nullptr, nullptr, true);
 }
 
 extern "C" int psoap_chunk_lnprob_grad(psoap_chunk* h, int B, int model, const double* p_orb, const double* gp, double mu_GP,
@@ -2480,8 +2515,8 @@ extern "C" int psoap_chunk_lnprob_grad(psoap_chunk* h, int B, int model, const d
     if (!h->dGrid || !h->dDates) FAIL("psoap_chunk_lnprob_grad: call psoap_chunk_set_grid and psoap_chunk_set_dates first");
     if (h->stream.open) FAIL("psoap_chunk_lnprob_grad: the handle has an open stream (psoap_stream_close first)");
     if (int rc = check_orbits(model, B, p_orb)) return rc;
-    return grad_run(h, "psoap_chunk_lnprob_grad", false, B, orbit_n_components(model), nullptr, model, p_orb, gp, mu_GP, lnp,
-                    nullptr, grad_gp, nullptr, grad_mu, grad_orb, grad_vel);
+    return grad_run(h, "psoap_chunk_lnprob_grad", false, B, orbit_n_components(model), nullptr, model, p_orb, gp, nullptr, mu_GP,
+                    lnp, nullptr, grad_gp, nullptr, nullptr, grad_mu, grad_orb, grad_vel, true);
 }
 
 // stand-alone, beside psoap_orbit_velocities: vel_out (B, c, n_dates), jac_out (B, c, n_dates, n_orb)
@@ -2513,10 +2548,9 @@ extern "C" int psoap_chunk_grad_release(psoap_chunk* h)
     return release_ws(h, [&] { h->gws.reset(); });
 }
 
-// ---- time-variable component spectra (timevar_kernels.hpp) ------------------------------------------
-// The value and the gradient under K_ij = sum_c a_c^2 exp(p_c d^2 + q_c dt^2) + sigma_i^2 delta_ij: grad_run's sibling on the
-// same workspace, grouping, factor_group and conventions -- the fill, the contraction and the finishing sums are the
-// time-variable kernels, nothing else differs.  The pixels' times stay with the handle as the flux and sigma do.
+// ---- time-variable component spectra (the TV kernels of fill_kernels.hpp, grad_kernels.hpp) ---------
+// The value and the gradient under K_ij = sum_c a_c^2 exp(p_c d^2 + q_c dt^2) + sigma_i^2 delta_ij: grad_run with `tau`.
+// The pixels' times stay with the handle as the flux and sigma do.
 extern "C" int psoap_chunk_set_times(psoap_chunk* h, const double* t)
 {
     if (!h || !t) FAIL("psoap_chunk_set_times: bad arguments");
@@ -2527,14 +2561,6 @@ extern "C" int psoap_chunk_set_times(psoap_chunk* h, const double* t)
     NEED(h->dTimes, h->N);
     HIP_TRY(hipMemcpy(h->dTimes, t, sizeof(double) * h->N, hipMemcpyHostToDevice));
     return 0;
-}
-
-// a time scale that is no time scale: tau <= 0 or NaN (+inf is the static model)
-static bool tau_refused(const double* tau, int c, int b)
-{
-    bool bad = false;
-    for (int k = 0; k < c; ++k) bad = bad || !(tau[(size_t)b * c + k] > 0.0);
-    return bad;
 }
 
 extern "C" int psoap_chunk_lnlike_tv_grad(psoap_chunk* h, int B, int c, const double* lwl, const double* gp, const double* tau,
@@ -2553,63 +2579,8 @@ extern "C" int psoap_chunk_lnlike_tv_grad(psoap_chunk* h, int B, int c, const do
     if (h->marg.valid)
         FAIL("psoap_chunk_lnlike_tv_grad: the handle has a baseline (psoap_chunk_set_baseline): the time-variable kernel under the "
              "marginalised continuum is not built yet");
-    const bool contract = grad_gp != nullptr;
-    DEVICE_SCOPE(h->device);
-    if (int rc = enter_device(h->device)) return rc;
-    const Factored fac = factored(h, false, B, true);
-    const int N = h->N, Npad = h->Npad, P = h->P, G = fac.G, ld = fac.ld, ntiles = P * (P + 1) / 2;
-    const size_t mstride = fac.mstride;
-    hipStream_t s = h->streams[0];
-    if (int rc = factored_ws_need(h, fac, s, true, contract, c, 0)) return rc;
-    GradWs& w = *h->gws;
-    HIP_TRY(w.Tau.need((size_t)G * 3));
-    if (contract) {
-        HIP_TRY(w.Part.need((size_t)G * ntiles * TV_TILE_DOUBLES));       // (a record is a double longer than the static one)
-        HIP_TRY(w.GradTau.need((size_t)G * 3));
-    }
-    h->recs.clear();
-    std::vector<double> out((size_t)B);
-    for (int b0 = 0; b0 < B; b0 += G) {
-        const int nb = (B - b0 < G) ? B - b0 : G;
-        HIP_TRY(hipMemcpyAsync(w.Lwl, lwl + (size_t)b0 * c * N, sizeof(double) * (size_t)nb * c * N, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(w.Gp, gp + (size_t)b0 * 2 * c, sizeof(double) * (size_t)nb * 2 * c, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(w.Tau, tau + (size_t)b0 * c, sizeof(double) * (size_t)nb * c, hipMemcpyHostToDevice, s));
-        if (int rc = factor_group(h, fac, s, nb, c, mu_GP, true)) return rc;
-        if (contract) {
-            double cunits = 0.0;
-            for (int tj = 0; tj < P; ++tj) cunits += (double)(tj + 1) * (P - tj);
-            if (int rc = prof_launch(h, s, PSOAP_K_GRAD, TILE_FLOPS * cunits * nb, 0.0, [&] {
-                    with_components(c, [&](auto nc) {
-                        hipLaunchKernelGGL(k_tv_grad_contract<nc()>, dim3(ntiles, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s,
-                                           (const double*)w.A.p, mstride, ld, N, Npad, P, (const double*)w.Lwl.p,
-                                           (const double*)h->dTimes.p, (const double*)w.Gp.p, (const double*)w.Tau.p,
-                                           (const double*)w.Alpha.p, w.Part.p);
-                    });
-                })) return rc;
-            if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
-                    hipLaunchKernelGGL(k_tv_grad_finish, dim3(P + 1, nb), dim3(128), 0, s, (const double*)w.Part.p,
-                                       (const double*)w.Alpha.p, (const double*)w.Gp.p, (const double*)w.Tau.p, c, N, Npad, P,
-                                       w.GradGp.p, w.GradTau.p, w.GradX.p, w.GradMu.p);
-                })) return rc;
-        }
-        HIP_TRY(hipMemcpyAsync(out.data() + b0, fac.Out->p, sizeof(double) * (size_t)nb, hipMemcpyDeviceToHost, s));
-        if (contract) {
-            HIP_TRY(hipMemcpyAsync(grad_gp + (size_t)b0 * 2 * c, w.GradGp, sizeof(double) * (size_t)nb * 2 * c, hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipMemcpyAsync(grad_tau + (size_t)b0 * c, w.GradTau, sizeof(double) * (size_t)nb * c, hipMemcpyDeviceToHost, s));
-            if (grad_lwl)
-                HIP_TRY(hipMemcpyAsync(grad_lwl + (size_t)b0 * c * N, w.GradX, sizeof(double) * (size_t)nb * c * N, hipMemcpyDeviceToHost, s));
-            if (grad_mu) HIP_TRY(hipMemcpyAsync(grad_mu + b0, w.GradMu, sizeof(double) * nb, hipMemcpyDeviceToHost, s));
-        }
-        HIP_TRY(hipStreamSynchronize(s));       // the next group reuses the workspace and the caller's arrays are pageable
-    }
-    if (collect_timings(h)) return 1;
-    // a negative hyper-parameter, a tau that is no time scale, a K that does not factor -> -inf, and no gradient there
-    for (int b = 0; b < B; ++b)
-        if (values_out(out.data(), 1, b, proposal_refused(gp, c, b) || tau_refused(tau, c, b), lnp, nullptr) && contract) {
-            poison_gradient(b, c, N, 0, 0, grad_gp, grad_lwl, grad_mu, nullptr, nullptr);
-            for (int k = 0; k < c; ++k) grad_tau[(size_t)b * c + k] = NAN;
-        }
-    return 0;
+    return grad_run(h, "psoap_chunk_lnlike_tv_grad", false, B, c, lwl, -1, nullptr, gp, tau, mu_GP, lnp, nullptr, grad_gp, grad_tau,
+                    grad_lwl, grad_mu, nullptr, nullptr, grad_gp != nullptr);
 }
 
 // ---- Fisher information of the likelihood (fisher_kernels.hpp) --------------------------------------
@@ -2644,7 +2615,7 @@ static int fisher_run(psoap_chunk* h, const char* who, bool marg, int c, const d
     HIP_TRY(f.Z.need(sq));
     HIP_TRY(f.TanX.need((size_t)T * CN));
     HIP_TRY(f.TanGp.need((size_t)T * 2 * c));
-    HIP_TRY(f.Part.need((size_t)ntiles * GRAD_TILE_DOUBLES));
+    HIP_TRY(f.Part.need((size_t)ntiles * GradTile<false>::DOUBLES));
     HIP_TRY(f.GGp.need((size_t)T * 2 * c));
     HIP_TRY(f.GX.need((size_t)T * CN));
     HIP_TRY(f.Y.need(Npad));
@@ -3387,8 +3358,8 @@ extern "C" int psoap_chunk_lnlike_marg_grad(psoap_chunk* h, int B, int c, const 
 {
     if (!h || !lwl || !gp || !lnp || !grad_gp) FAIL("psoap_chunk_lnlike_marg_grad: bad arguments");
     if (h->stream.open) FAIL("psoap_chunk_lnlike_marg_grad: the handle has an open stream (psoap_stream_close first)");
-    return grad_run(h, "psoap_chunk_lnlike_marg_grad", true, B, c, lwl, -1, nullptr, gp, mu_GP, lnp, parts, grad_gp, grad_lwl,
-                    grad_mu, nullptr, nullptr);
+    return grad_run(h, "psoap_chunk_lnlike_marg_grad", true, B, c, lwl, -1, nullptr, gp, nullptr, mu_GP, lnp, parts, grad_gp, nullptr,
+                    grad_lwl, grad_mu, nullptr, nullptr, true);
 }
 
 extern "C" int psoap_chunk_lnprob_marg_grad(psoap_chunk* h, int B, int model, const double* p_orb, const double* gp, double mu_GP,
@@ -3399,8 +3370,8 @@ extern "C" int psoap_chunk_lnprob_marg_grad(psoap_chunk* h, int B, int model, co
     if (!h->dGrid || !h->dDates) FAIL("psoap_chunk_lnprob_marg_grad: call psoap_chunk_set_grid and psoap_chunk_set_dates first");
     if (h->stream.open) FAIL("psoap_chunk_lnprob_marg_grad: the handle has an open stream (psoap_stream_close first)");
     if (int rc = check_orbits(model, B, p_orb)) return rc;
-    return grad_run(h, "psoap_chunk_lnprob_marg_grad", true, B, orbit_n_components(model), nullptr, model, p_orb, gp, mu_GP, lnp,
-                    nullptr, grad_gp, nullptr, grad_mu, grad_orb, grad_vel);
+    return grad_run(h, "psoap_chunk_lnprob_marg_grad", true, B, orbit_n_components(model), nullptr, model, p_orb, gp, nullptr, mu_GP,
+                    lnp, nullptr, grad_gp, nullptr, nullptr, grad_mu, grad_orb, grad_vel, true);
 }
 
 // frees the device side of the baseline and the workspace; the baseline itself stays set (the next call builds Ht again)
@@ -3414,26 +3385,36 @@ extern "C" int psoap_chunk_marg_release(psoap_chunk* h)
 }
 
 // ---- fills (matrix_functions drop-ins) ------------------------------------------------------
-extern "C" int psoap_fill_sym(int device, int c, int N, const double* lwl, const double* gp, const double* sigma,
-                              double* out)
+// K (full) of one matrix on `device`, static or -- with t (N) and tau (c) -- under the time-variable kernel
+static int fill_sym_run(int device, int c, int N, const double* lwl, const double* t, const double* gp, const double* tau,
+                        const double* sigma, double* out)
 {
-    if (c < 1 || c > 3 || N <= 0 || !lwl || !gp || !out) FAIL("psoap_fill_sym: bad arguments");
     DEVICE_SCOPE(device);
     HIP_TRY(hipSetDevice(device));
     const int Npad = round_up(N, NB), P = Npad / NB;
-    Grow<double> dK, dLwl, dGp, dSig;
+    Grow<double> dK, dLwl, dT, dGp, dTau, dSig;
     HIP_TRY(dK.need((size_t)Npad * Npad));
     HIP_TRY(dLwl.need((size_t)c * N));
     HIP_TRY(dGp.need(6));
     HIP_TRY(hipMemcpy(dLwl, lwl, sizeof(double) * (size_t)c * N, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(dGp, gp, sizeof(double) * 2 * c, hipMemcpyHostToDevice));
+    if (t) {
+        HIP_TRY(dT.need(N));
+        HIP_TRY(dTau.need(3));
+        HIP_TRY(hipMemcpy(dT, t, sizeof(double) * N, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(dTau, tau, sizeof(double) * c, hipMemcpyHostToDevice));
+    }
     if (sigma) {
         HIP_TRY(dSig.need(N));
         HIP_TRY(hipMemcpy(dSig, sigma, sizeof(double) * N, hipMemcpyHostToDevice));
     }
     dim3 grid(P * P, 1);
     with_components(c, [&](auto nc) {
-        hipLaunchKernelGGL(k_fill_sym<nc()>, grid, dim3(256), 0, 0, dK.p, (size_t)0, Npad, N, P, dLwl.p, dGp.p, dSig.p, 0);
+        if (t)
+            hipLaunchKernelGGL(k_fill_sym_tv<nc()>, grid, dim3(256), 0, 0, dK.p, (size_t)0, Npad, N, P, (const double*)dLwl.p,
+                               (const double*)dT.p, (const double*)dGp.p, (const double*)dTau.p, (const double*)dSig.p, 0);
+        else
+            hipLaunchKernelGGL(k_fill_sym<nc()>, grid, dim3(256), 0, 0, dK.p, (size_t)0, Npad, N, P, dLwl.p, dGp.p, dSig.p, 0);
     });
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpy2D(out, sizeof(double) * N, dK, sizeof(double) * Npad, sizeof(double) * N, N,
@@ -3441,37 +3422,19 @@ extern "C" int psoap_fill_sym(int device, int c, int N, const double* lwl, const
     return 0;
 }
 
-// psoap_fill_sym under the time-variable kernel (timevar_kernels.hpp): t (N), tau (c)
+extern "C" int psoap_fill_sym(int device, int c, int N, const double* lwl, const double* gp, const double* sigma,
+                              double* out)
+{
+    if (c < 1 || c > 3 || N <= 0 || !lwl || !gp || !out) FAIL("psoap_fill_sym: bad arguments");
+    return fill_sym_run(device, c, N, lwl, nullptr, gp, nullptr, sigma, out);
+}
+
+// psoap_fill_sym under the time-variable kernel: t (N), tau (c)
 extern "C" int psoap_fill_sym_tv(int device, int c, int N, const double* lwl, const double* t, const double* gp,
                                  const double* tau, const double* sigma, double* out)
 {
     if (c < 1 || c > 3 || N <= 0 || !lwl || !t || !gp || !tau || !out) FAIL("psoap_fill_sym_tv: bad arguments");
-    DEVICE_SCOPE(device);
-    HIP_TRY(hipSetDevice(device));
-    const int Npad = round_up(N, NB), P = Npad / NB;
-    Grow<double> dK, dLwl, dT, dGp, dTau, dSig;
-    HIP_TRY(dK.need((size_t)Npad * Npad));
-    HIP_TRY(dLwl.need((size_t)c * N));
-    HIP_TRY(dT.need(N));
-    HIP_TRY(dGp.need(6));
-    HIP_TRY(dTau.need(3));
-    HIP_TRY(hipMemcpy(dLwl, lwl, sizeof(double) * (size_t)c * N, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dT, t, sizeof(double) * N, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dGp, gp, sizeof(double) * 2 * c, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dTau, tau, sizeof(double) * c, hipMemcpyHostToDevice));
-    if (sigma) {
-        HIP_TRY(dSig.need(N));
-        HIP_TRY(hipMemcpy(dSig, sigma, sizeof(double) * N, hipMemcpyHostToDevice));
-    }
-    dim3 grid(P * P, 1);
-    with_components(c, [&](auto nc) {
-        hipLaunchKernelGGL(k_fill_sym_tv<nc()>, grid, dim3(256), 0, 0, dK.p, (size_t)0, Npad, N, P, (const double*)dLwl.p,
-                           (const double*)dT.p, (const double*)dGp.p, (const double*)dTau.p, (const double*)dSig.p, 0);
-    });
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy2D(out, sizeof(double) * N, dK, sizeof(double) * Npad, sizeof(double) * N, N,
-                        hipMemcpyDeviceToHost));
-    return 0;
+    return fill_sym_run(device, c, N, lwl, t, gp, tau, sigma, out);
 }
 
 extern "C" int psoap_fill_cross(int device, int M, int N, const double* lwl_row, const double* lwl_col, double amp,

@@ -1,5 +1,5 @@
 """GPU tests of the time-variable kernel (psoap_chunk_set_times, psoap_chunk_lnlike_tv_grad, psoap_fill_sym_tv;
-psoap_amd/csrc/timevar_kernels.hpp).
+k_fill_sym_tv in psoap_amd/csrc/fill_kernels.hpp and the TV branches of grad_kernels.hpp).
 
 The cases are those of tests/timevar_reference.py: the seven shapes of grad_reference.CASES (N = 100 .. 520 at the edges of
 the 128-row tiles, c = 1, 2, 3, masked chunks with unequal epochs, mu_GP = 0.9), times = dates[epoch] of the chunk's own

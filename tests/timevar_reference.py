@@ -122,7 +122,7 @@ def tv_ext(lwls, times, fl, sigma, gp, tau, mu_GP=1.0) -> TvGrad:
 
 
 def matrix_f64(lwls, times, gp, tau, sigma=None, want_args=False):
-    """K in float64 as the device's fill forms it (timevar_kernels.hpp): per component the argument ``p * d * d`` then
+    """K in float64 as the device's fill forms it (k_fill_sym_tv): per component the argument ``p * d * d`` then
     ``+ q * dt * dt`` with every operation rounded on its own, ``a^2 exp()``, the components added in order; the diagonal is
     ``sum a^2 (+ sigma^2)``.  ``want_args``: also the (c, N, N) arguments, for the places where exp() must be exactly +0."""
     lwls = np.ascontiguousarray(np.atleast_2d(lwls), dtype=np.float64)

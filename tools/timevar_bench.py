@@ -5,7 +5,7 @@ psoap_chunk_lnlike_grad, the static call it extends, on the same handle in the s
 
 Shapes and timing as tools/vel_newton_bench.py: SB2, N = 6000, 20 epochs; ST3, N = 8192, 16 epochs; one warm-up call, then
 ``--repeats`` calls with the handle's profiling on; the time of a call is psoap_chunk_get_timings' total_ms, the classes the
-summed event times per kernel class of the last call.  tau = (0.25 x span, inf[, 2 x span]) of the chunk's dates; a third
+summed event times per kernel class of every call (and of the last one by itself).  tau = (0.25 x span, inf[, 2 x span]) of the chunk's dates; a third
 measurement runs the new call at tau = inf throughout, where its outputs must have the bits of the static call.
 One JSON line per shape on stdout.
 """
@@ -46,18 +46,19 @@ def run_shape(name: str, repeats: int) -> dict:
                            ("lnlike_tv_value_only", lambda: (h.lnlike_tv(ch.lwls, gp, tau, 1.0),)),
                            ("lnlike_grad", lambda: h.lnlike_grad(ch.lwls, gp, 1.0))):
             first = call()                                   # warm-up: code objects, the workspace
-            ms, classes = [], {}
+            ms, classes = [], []
             for _ in range(repeats):
                 again = call()
                 t = h.timings()
                 ms.append(t["total_ms"])
-                classes = {k: round(v["ms"], 3) for k, v in t.items() if isinstance(v, dict) and v["launches"]}
+                classes.append({k: round(v["ms"], 3) for k, v in t.items() if isinstance(v, dict) and v["launches"]})
             assert all(np.array_equal(a, b) for a, b in zip(first, again)) and np.isfinite(first[0])
             res[what], last[what] = (float(np.median(ms)), [round(v, 3) for v in ms], classes), again
         for what, (med, all_ms, classes) in res.items():
             out[what + "_device_ms"] = all_ms
             out[what + "_device_ms_median"] = med
-            out[what + "_classes_ms_last_call"] = classes
+            out[what + "_classes_ms_last_call"] = classes[-1]
+            out[what + "_classes_ms"] = {k: [cl.get(k) for cl in classes] for k in classes[-1]}      # every call's, per class
         out["ratio_tv_grad_over_lnlike_grad"] = res["lnlike_tv_grad"][0] / res["lnlike_grad"][0]
         out["ratio_tv_grad_tau_inf_over_lnlike_grad"] = res["lnlike_tv_grad_tau_inf"][0] / res["lnlike_grad"][0]
         a, b = last["lnlike_tv_grad_tau_inf"], last["lnlike_grad"]
