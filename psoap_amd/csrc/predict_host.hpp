@@ -1,7 +1,7 @@
 // predict_host.hpp -- the host side of the predict family: the workspace, the Sigma download, the steps that the plain
 // call (predict_run), the one under the marginalised continuum (marg_predict_run) and the draws share, and predict_run
 // itself.  Part of psoap_gp.hip, included behind staged_row: it uses that file's error macros, prof_launch and staged_row.
-// The arithmetic of a call is predict_plan.hpp's, the kernels are predict_kernels.hpp's.
+// The arithmetic of a call is predict_plan.hpp's, the kernels are predict_kernels.hpp's.  (factor_host.hpp comes behind it.)
 //
 // Every step queues on the stream it is given and books nothing: marg_predict_run calls them inside its prof_launch
 // brackets, predict_run has no handle to book into.

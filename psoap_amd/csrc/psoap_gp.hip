@@ -846,6 +846,27 @@ static int prof_launch(psoap_chunk* h, hipStream_t s, int cls, double flops, dou
     return 0;
 }
 
+static int collect_timings(psoap_chunk* h)
+{
+    psoap_timings t;
+    memset(&t, 0, sizeof t);
+    if (h->profiling && !h->recs.empty()) {
+        for (auto& r : h->recs) {
+            float ms = 0.f;
+            HIP_TRY(hipEventElapsedTime(&ms, h->evPool[r.e0], h->evPool[r.e1]));
+            t.ms[r.cls] += ms;
+            t.launches[r.cls] += 1;
+            t.flops[r.cls] += r.flops;
+            t.bytes[r.cls] += r.bytes;
+        }
+        float tot = 0.f;
+        HIP_TRY(hipEventElapsedTime(&tot, h->evPool[h->recs.front().e0], h->evPool[h->recs.back().e1]));
+        t.total_ms = tot;
+    }
+    h->last = t;
+    return 0;
+}
+
 // One block row of the staged factorisation of nb matrices: what k_potrf_diag and k_trsm_strip take, and the extent of the strip.
 struct StagedRow {
     double* A;             // the first matrix; `stride` doubles from one to the next, leading dimension ld
@@ -886,6 +907,8 @@ static int staged_row(psoap_chunk* h, hipStream_t s, const StagedRow& m, int nb,
 }
 
 #include "predict_host.hpp"
+#include "factor_host.hpp"
+#include "analysis_host.hpp"
 
 template <int C>
 static void launch_fill(psoap_chunk* h, const BatchSlot& sl, hipStream_t s, int b0, int nb, int upper_only)
@@ -1224,27 +1247,6 @@ static int eval_staged(psoap_chunk* h)
     HIP_TRY(hipEventRecord(h->evLast, h->streams[0]));
     h->last_recorded = true;
     HIP_TRY(hipMemcpyAsync(h->hOut, h->dOut, sizeof(double) * B, hipMemcpyDeviceToHost, h->streams[0]));
-    return 0;
-}
-
-static int collect_timings(psoap_chunk* h)
-{
-    psoap_timings t;
-    memset(&t, 0, sizeof t);
-    if (h->profiling && !h->recs.empty()) {
-        for (auto& r : h->recs) {
-            float ms = 0.f;
-            HIP_TRY(hipEventElapsedTime(&ms, h->evPool[r.e0], h->evPool[r.e1]));
-            t.ms[r.cls] += ms;
-            t.launches[r.cls] += 1;
-            t.flops[r.cls] += r.flops;
-            t.bytes[r.cls] += r.bytes;
-        }
-        float tot = 0.f;
-        HIP_TRY(hipEventElapsedTime(&tot, h->evPool[h->recs.front().e0], h->evPool[h->recs.back().e1]));
-        t.total_ms = tot;
-    }
-    h->last = t;
     return 0;
 }
 
@@ -2090,421 +2092,18 @@ extern "C" int psoap_lnlike(psoap_chunk* h, int c, const double* lwl, const doub
     return psoap_lnlike_batch(h, 1, c, lwl, gp, mu_GP, out);
 }
 
-// ---- gradient of the likelihood (grad_kernels.hpp) ------------------------------------------------
-// The staged factorisation of [K | I] per group of matrices, alpha = W^T z, the fused contraction, the finishing sums.
-// Everything lives in the handle's gradient workspace and runs on the handle's first stream behind whatever the handle
-// has in flight: neither the proposal slots nor the workspaces of the likelihood paths are touched.
-//
-// What the analysis paths below share, and what a new one is expected to reuse ("The host layer"): Factored says
-// where things are after a factorisation, plain or marginal, factored_ws_need sizes the workspaces for it and factor_group
-// runs it; launch_grad_fill fills K, staged_row (above) is every block row of every factorisation, launch_alpha makes
-// alpha, orbit_front / orbit_back are the orbit entry, proposal_refused / tau_refused / values_out / poison_gradient the
-// conventions, release_ws the body of a *_release.  The time-variable kernel is a flag on the same path, not a path: Factored::tv
-// (grad_run's tau != nullptr) picks the TV fill, contraction and finishing sums and sizes the longer tile record.  The marginal
-// pieces (marg_ws_need, launch_marg_rhs, gram_units, launch_marg_finish) stand with psoap_chunk_lnlike_marg further down.
-
-// The gradient workspace for groups of G matrices of mstride doubles each: what the factorisation needs, always; alpha and
-// its partial sums (`alpha`); the contraction's partial tiles and the three gradients (`contract`); with np > 0 the orbit
-// entry's buffers for c components and np orbital parameters, and the epoch lists of the fold.  `tv`: the time scales, the
-// longer tile record of the time-variable contraction and, with `contract`, dlnL/dtau.
-static int grad_ws_need(psoap_chunk* h, GradWs& w, int G, size_t mstride, bool alpha, bool contract, int c = 0, int np = 0,
-                        bool tv = false)
-{
-    const int N = h->N, Npad = h->Npad, ne = h->n_epochs;
-    HIP_TRY(w.A.need((size_t)G * mstride));
-    HIP_TRY(w.Wt.need((size_t)G * NB * NB));
-    HIP_TRY(w.R.need((size_t)G * Npad));
-    HIP_TRY(w.Acc.need((size_t)G * ACC_ROWS));
-    HIP_TRY(w.Lwl.need((size_t)G * 3 * N));
-    HIP_TRY(w.Gp.need((size_t)G * 6));
-    if (alpha) {
-        HIP_TRY(w.Alpha.need((size_t)G * Npad));
-        HIP_TRY(w.APart.need((size_t)G * ((Npad + 255) / 256) * Npad));
-    }
-    if (tv) HIP_TRY(w.Tau.need((size_t)G * 3));
-    if (contract) {
-        HIP_TRY(w.Part.need((size_t)G * (h->P * (h->P + 1) / 2) * (tv ? GradTile<true>::DOUBLES : GradTile<false>::DOUBLES)));
-        HIP_TRY(w.GradGp.need((size_t)G * 6));
-        HIP_TRY(w.GradX.need((size_t)G * 3 * N));
-        HIP_TRY(w.GradMu.need(G));
-        if (tv) HIP_TRY(w.GradTau.need((size_t)G * 3));
-    }
-    if (np > 0) {
-        HIP_TRY(w.Porb.need((size_t)G * np));
-        HIP_TRY(w.Vel.need((size_t)G * c * ne));
-        HIP_TRY(w.Jac.need((size_t)G * c * ne * np));
-        HIP_TRY(w.Gv.need((size_t)G * c * ne));
-        HIP_TRY(w.GradOrb.need((size_t)G * np));
-        HIP_TRY(w.TooFast.need(G));
-    }
-    return 0;
-}
-
-// K (upper tiles) of the nb matrices whose grids and hyper-parameters are in w.Lwl and w.Gp, into w.A as the caller lays it out
-// (`tv`: under the time-variable kernel -- k_fill_sym_tv with the handle's times and w.Tau)
-static void launch_grad_fill(const psoap_chunk* h, GradWs& w, hipStream_t s, int nb, int c, size_t mstride, int ld, bool tv = false)
-{
-    with_components(c, [&](auto nc) {
-        if (tv) {
-            hipLaunchKernelGGL(k_fill_sym_tv<nc()>, dim3(h->P * (h->P + 1) / 2, nb), dim3(256), 0, s, w.A.p, mstride, ld, h->N, h->P,
-                               (const double*)w.Lwl.p, (const double*)h->dTimes.p, (const double*)w.Gp.p, (const double*)w.Tau.p,
-                               (const double*)h->dSigma.p, 1);
-            return;
-        }
-        hipLaunchKernelGGL(k_fill_sym<nc()>, dim3(h->P * (h->P + 1) / 2, nb), dim3(256), 0, s, w.A.p, mstride, ld, h->N, h->P,
-                           (const double*)w.Lwl.p, (const double*)w.Gp.p, (const double*)h->dSigma.p, 1);
-    });
-}
-
-// w.Alpha = W^T z for nb factored matrices (z: w.R, or what the caller made of it).  Launches only: inside the caller's bracket.
-static void launch_alpha(GradWs& w, hipStream_t s, int nb, size_t mstride, int ld, int Npad, int P, const double* z)
-{
-    const int nslab = (Npad + 255) / 256;
-    hipLaunchKernelGGL(k_grad_alpha_partial, dim3(P, nslab, nb), dim3(256), 0, s, (const double*)w.A.p, mstride, ld, Npad, z,
-                       w.APart.p, nslab);
-    hipLaunchKernelGGL(k_grad_alpha_finish, dim3((Npad + 255) / 256, nb), dim3(256), 0, s, (const double*)w.APart.p, nslab, Npad,
-                       w.Alpha.p);
-}
-
-// the block-row record of [K | ...] in the gradient workspace, `strip` tiles right of the diagonal tile
-static StagedRow grad_row(GradWs& w, size_t mstride, int ld, int Npad, int strip)
-{
-    return StagedRow{w.A.p, mstride, ld, w.R.p, Npad, w.Acc.p, w.Wt.p, (size_t)NB * NB, strip};
-}
-
-// The conventions of the likelihood (covariance.py:317; sample_parallel.py:186-187): proposal b has a negative hyper-parameter
-// or, with `fast` given, an orbit with |v| >= c  ->  lnL = -inf whatever the device computed
-static bool proposal_refused(const double* gp, int c, int b, const int* fast = nullptr)
-{
-    bool neg = fast && fast[b];
-    for (int k = 0; k < 2 * c; ++k) neg = neg || gp[(size_t)b * 2 * c + k] < 0.0;
-    return neg;
-}
-
-// a time scale that is no time scale: tau <= 0 or NaN (+inf is the static model)
-static bool tau_refused(const double* tau, int c, int b)
-{
-    bool bad = false;
-    for (int k = 0; k < c; ++k) bad = bad || !(tau[(size_t)b * c + k] > 0.0);
-    return bad;
-}
-
-// The value record of proposal b (`stride` doubles per proposal: the value and, with stride 5, its four parts) into lnp[b] and,
-// where asked for, parts[4 b]: -inf for a refused proposal whatever the device computed, NaN parts beside a -inf.
-// -> the proposal has no value, and nothing else is to be said about it
-static bool values_out(const double* out, int stride, int b, bool refused, double* lnp, double* parts)
-{
-    lnp[b] = refused ? -INFINITY : out[(size_t)b * stride];
-    const bool bad = lnp[b] == -INFINITY;
-    if (parts)
-        for (int k = 0; k < 4; ++k) parts[(size_t)b * 4 + k] = bad ? NAN : out[(size_t)b * stride + 1 + k];
-    return bad;
-}
-
-// ... and no gradient there: NaN into proposal b of grad_gp and of every optional output that was asked for
-static void poison_gradient(int b, int c, int N, int ne, int np, double* grad_gp, double* grad_tau, double* grad_lwl,
-                            double* grad_mu, double* grad_orb, double* grad_vel)
-{
-    for (int k = 0; k < 2 * c; ++k) grad_gp[(size_t)b * 2 * c + k] = NAN;
-    if (grad_tau)
-        for (int k = 0; k < c; ++k) grad_tau[(size_t)b * c + k] = NAN;
-    if (grad_lwl)
-        for (size_t k = 0; k < (size_t)c * N; ++k) grad_lwl[(size_t)b * c * N + k] = NAN;
-    if (grad_mu) grad_mu[b] = NAN;
-    if (grad_orb)
-        for (int k = 0; k < np; ++k) grad_orb[(size_t)b * np + k] = NAN;
-    if (grad_vel)
-        for (size_t k = 0; k < (size_t)c * ne; ++k) grad_vel[(size_t)b * c * ne + k] = NAN;
-}
-
-// The body of a *_release: the handle's first stream drained (the workspace may still be read there), then `drop`
-template <class F>
-static int release_ws(psoap_chunk* h, F&& drop)
-{
-    if (!h) FAIL("null handle");
-    DEVICE_SCOPE(h->device);
-    if (set_dev(h)) return 1;
-    HIP_TRY(hipStreamSynchronize(h->streams[0]));
-    drop();
-    return 0;
-}
-
-// The pixels of every epoch for k_epoch_fold: a counting sort of the handle's epoch index (stable: ascending pixels within an
-// epoch), made once per psoap_chunk_set_grid.
-static int grad_epoch_lists(psoap_chunk* h, GradWs& w, hipStream_t s)
-{
-    if (w.epochs_valid) return 0;
-    const int N = h->N, ne = h->n_epochs;
-    std::vector<int32_t> ep((size_t)N);
-    HIP_TRY(hipMemcpyAsync(ep.data(), h->dEpoch, sizeof(int32_t) * (size_t)N, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    std::vector<int> start((size_t)ne + 1, 0), pix((size_t)N);
-    for (int i = 0; i < N; ++i) start[(size_t)ep[i] + 1]++;
-    for (int e = 0; e < ne; ++e) start[(size_t)e + 1] += start[e];
-    std::vector<int> at(start.begin(), start.end() - 1);
-    for (int i = 0; i < N; ++i) pix[(size_t)at[ep[i]]++] = i;
-    HIP_TRY(w.EpStart.need((size_t)ne + 1));
-    HIP_TRY(w.EpPix.need((size_t)N));
-    HIP_TRY(hipMemcpyAsync(w.EpStart, start.data(), sizeof(int) * ((size_t)ne + 1), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(w.EpPix, pix.data(), sizeof(int) * (size_t)N, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipStreamSynchronize(s));       // (the vectors leave scope)
-    w.epochs_valid = true;
-    return 0;
-}
-
-// The staged factorisation of [K | I] for the nb matrices whose grids and hyper-parameters are in w.Lwl and w.Gp: afterwards
-// the appended block holds W = U^-T, w.R holds z = U^-T (fl - mu_GP) and w.Acc the block records.
-static int grad_factor(psoap_chunk* h, GradWs& w, hipStream_t s, int nb, int c, double mu_GP, bool tv = false)
-{
-    const int N = h->N, Npad = h->Npad, P = h->P, ld = 2 * h->Npad;
-    const size_t mstride = (size_t)Npad * ld;
-    if (int rc = prof_launch(h, s, PSOAP_K_FILL, 0.0, (double)nb * 12.0 * N * (N + 1.0), [&] {
-            launch_grad_fill(h, w, s, nb, c, mstride, ld, tv);
-            hipLaunchKernelGGL(k_grad_init, dim3(P * (P + 1) / 2, nb), dim3(256), 0, s, w.A.p, mstride, ld, Npad, P);
-        })) return rc;
-    if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
-            hipLaunchKernelGGL(k_init_rhs, dim3((Npad + 255) / 256, nb), dim3(256), 0, s, w.R.p, Npad, N, h->dFl, mu_GP, w.Acc.p);
-        })) return rc;
-    // block row p: tile columns p .. P + p -- the rest of K's row and the appended tiles j <= p
-    for (int p = 0; p < P; ++p) {
-        const int k0 = p * NB;
-        const double units = (double)p * (P - p) + 0.5 * p * (p + 1.0);
-        auto update = [&] {
-            hipLaunchKernelGGL(k_grad_panel_update, dim3(P + 1, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, w.A.p, mstride, ld, k0, P);
-        };
-        if (int rc = staged_row(h, s, grad_row(w, mstride, ld, Npad, P), nb, k0, p > 0 ? &update : nullptr, TILE_FLOPS * units * nb))
-            return rc;
-    }
-    return 0;
-}
-
-// The orbit entry of a gradient call, front: the group's nb orbits (np parameters each) go up, k_orbit_jacobian makes their
-// velocities, Jacobian and |v| >= c flags, k_doppler_shift the grids w.Lwl from the handle's grid and dates.
-static int orbit_front(psoap_chunk* h, GradWs& w, hipStream_t s, int nb, int c, int model, int np, const double* p_orb)
-{
-    const int N = h->N, ne = h->n_epochs;
-    HIP_TRY(hipMemcpyAsync(w.Porb, p_orb, sizeof(double) * (size_t)nb * np, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemsetAsync(w.TooFast, 0, sizeof(int) * (size_t)nb, s));
-    hipLaunchKernelGGL(k_orbit_jacobian, dim3((ne + 63) / 64, nb), dim3(64), 0, s, model, nb, ne, (const double*)w.Porb.p,
-                       (const double*)h->dDates, w.Vel.p, w.Jac.p, w.TooFast.p);
-    hipLaunchKernelGGL(k_doppler_shift, dim3((N + 255) / 256, nb * c), dim3(256), 0, s, w.Lwl.p, h->dGrid, h->dEpoch,
-                       (const double*)w.Vel.p, N, ne, nb * c);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-// ... and back: after k_grad_finish the fold and the chain (orbit_grad_kernels.hpp) turn w.GradX into dlnL/dv and dlnL/dp_orb
-// on the device; the group's grad_orb, grad_vel (optional) and flags come down.
-static int orbit_back(psoap_chunk* h, GradWs& w, hipStream_t s, int nb, int c, int np, double* grad_orb, double* grad_vel, int* fast)
-{
-    const int N = h->N, ne = h->n_epochs, CE = c * ne;
-    hipLaunchKernelGGL(k_epoch_fold, dim3((CE + 3) / 4, nb), dim3(256), 0, s, (const double*)w.GradX.p, (const int*)w.EpStart.p,
-                       (const int*)w.EpPix.p, c, N, ne, w.Gv.p);
-    hipLaunchKernelGGL(k_orbit_chain, dim3(nb), dim3(256), 0, s, (const double*)w.Gv.p, (const double*)w.Jac.p, CE, np, w.GradOrb.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(grad_orb, w.GradOrb, sizeof(double) * (size_t)nb * np, hipMemcpyDeviceToHost, s));
-    if (grad_vel) HIP_TRY(hipMemcpyAsync(grad_vel, w.Gv, sizeof(double) * (size_t)nb * CE, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(fast, w.TooFast, sizeof(int) * (size_t)nb, hipMemcpyDeviceToHost, s));
-    return 0;
-}
-
-// Where things are once a group of matrices is factored (factor_group) -- [K | I], or under the handle's baseline
-// [K | I | Ht] and [M | Xt] (marg_grad_plan.hpp): what grad_run, fisher_run and loo_run read instead of asking which.
-struct Factored {
-    bool marg;
-    bool tv;                     // K under the time-variable kernel (fill_kernels.hpp; plain only): the fill reads w.Tau
-    int G;                       // matrices per group
-    int ld;                      // doubles per row of a matrix in w.A, mstride from one matrix to the next
-    size_t mstride;
-    const Grow<double>* Out;     // the value record, out_stride doubles per matrix: w.Out, or m.Out with the four parts behind the value
-    int out_stride;
-    bool parts;
-    int Q;                       // slots of Ht, for the flop counts (plain: 0)
-    const Grow<double>* Vt;      // [M | Vt] as the marginal kernels take it (mg.Mx): m_stride doubles per matrix, ldm per row, M of
-    int ldm, S;                  // side S (plain: null and 0)
-    size_t m_stride;
-    MargGradPlan gpl;            // the block rows of [K | I | Ht]: marg_grad_factor's
-};
-
-static int marg_basis(psoap_chunk* h, MargWs& m, hipStream_t s);
-static int marg_ws_need(psoap_chunk* h, MargWs& m, int G, bool cov);
-static int marg_grad_factor(psoap_chunk* h, const Factored& fac, hipStream_t s, int nb, int c, double mu_GP);
-
-// ... of a call with B matrices; the workspaces it points into exist afterwards, empty until factored_ws_need
-static Factored factored(psoap_chunk* h, bool marg, int B, bool tv = false)
-{
-    const int Npad = h->Npad;
-    if (!h->gws) h->gws.reset(new GradWs());
-    Factored fac{};
-    fac.marg = fac.parts = marg;
-    fac.tv = tv;
-    if (!marg) {
-        fac.G = grad_group_size(B, Npad);
-        fac.ld = 2 * Npad;
-        fac.mstride = (size_t)Npad * fac.ld;
-        fac.Out = &h->gws->Out;
-        fac.out_stride = 1;
-        return fac;
-    }
-    if (!h->mws) h->mws.reset(new MargWs());
-    if (!h->mgws) h->mgws.reset(new MargGradWs());
-    const MargPlan& pl = h->marg.plan;
-    marg_grad_plan(pl, fac.gpl);
-    fac.G = marg_grad_group_size(B, Npad, pl.Q);
-    fac.ld = fac.gpl.ld;
-    fac.mstride = marg_grad_matrix_doubles(Npad, pl.Q);
-    fac.Out = &h->mws->Out;
-    fac.out_stride = 5;
-    fac.Q = pl.Q;
-    fac.Vt = &h->mgws->Mx;
-    fac.S = NB * pl.Q;
-    fac.ldm = fac.S + Npad;
-    fac.m_stride = (size_t)fac.S * fac.ldm;
-    return fac;
-}
-
-// The handle's workspaces sized for groups of fac.G matrices: what the factorisation needs, always; alpha and the plain value
-// record (`values`: the marginal factorisation makes both whatever is asked); `contract`, c, np as grad_ws_need.  Under the
-// baseline Ht goes onto the device as well.
-static int factored_ws_need(psoap_chunk* h, const Factored& fac, hipStream_t s, bool values, bool contract, int c = 0, int np = 0)
-{
-    GradWs& w = *h->gws;
-    if (int rc = grad_ws_need(h, w, fac.G, fac.mstride, values || fac.marg, contract, c, np, fac.tv)) return rc;
-    if (!fac.marg) {
-        if (values) HIP_TRY(w.Out.need(fac.G));
-        return 0;
-    }
-    HIP_TRY(h->mgws->Mx.need((size_t)fac.G * fac.m_stride));
-    HIP_TRY(h->mgws->Zt.need((size_t)fac.G * h->Npad));
-    if (int rc = marg_ws_need(h, *h->mws, fac.G, false)) return rc;
-    return marg_basis(h, *h->mws, s);
-}
-
-// The factorisation of the nb matrices whose grids and hyper-parameters are in w.Lwl and w.Gp.  With `values`, w.Alpha and
-// the value record are ready afterwards: marg_grad_factor makes both anyway, the plain side in a bracket of their own, which
-// fisher_run does without.  `extra` (nullptr: none) is a launch of the caller's that shares that bracket on the plain side
-// and has one to itself under the baseline: the bookkeeping of loo_run.
-template <class X = void (*)()>
-static int factor_group(psoap_chunk* h, const Factored& fac, hipStream_t s, int nb, int c, double mu_GP, bool values,
-                        const X* extra = nullptr)
-{
-    GradWs& w = *h->gws;
-    if (int rc = fac.marg ? marg_grad_factor(h, fac, s, nb, c, mu_GP) : grad_factor(h, w, s, nb, c, mu_GP, fac.tv)) return rc;
-    const bool finish = values && !fac.marg;
-    if (!finish && !extra) return 0;
-    return prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
-        if (finish) {
-            hipLaunchKernelGGL(k_finalize, dim3((nb + 63) / 64), dim3(64), 0, s, (const MatAcc*)w.Acc.p, w.Out.p, nb,
-                               (const int*)nullptr, h->P);
-            launch_alpha(w, s, nb, fac.mstride, fac.ld, h->Npad, h->P, w.R.p);
-        }
-        if (extra) (*extra)();
-    });
-}
-
-// Group after group of matrices through factor_group, then the contraction and the finishing sums -- plain, or with `marg`
-// under the handle's baseline (marg_grad_kernels.hpp).  The ln-wavelengths come from the host (lwl: psoap_chunk_lnlike_grad)
-// or, with lwl == nullptr, from the orbits p_orb of `model` (orbit_front, orbit_back).  With `tau` (B, c; plain only) K is the
-// time-variable kernel over the handle's times: the TV fill, contraction and finishing sums, and grad_tau beside grad_gp.
-// `contract` false is the value only: no contraction, no finishing sums, no gradient touched.
-static int grad_run(psoap_chunk* h, const char* who, bool marg, int B, int c, const double* lwl, int model, const double* p_orb,
-                    const double* gp, const double* tau, double mu_GP, double* lnp, double* parts, double* grad_gp,
-                    double* grad_tau, double* grad_lwl, double* grad_mu, double* grad_orb, double* grad_vel, bool contract)
-{
-    if (marg)
-        if (const char* why = marg_grad_check(B, c, h->marg.valid, h->marg.stale_weight)) FAIL(std::string(who) + ": " + why);
-    const bool orbits = lwl == nullptr, tv = tau != nullptr;
-    DEVICE_SCOPE(h->device);
-    if (int rc = enter_device(h->device)) return rc;
-    const Factored fac = factored(h, marg, B, tv);
-    const int N = h->N, Npad = h->Npad, P = h->P, G = fac.G, ld = fac.ld, ntiles = P * (P + 1) / 2;
-    const size_t mstride = fac.mstride;
-    const int ne = h->n_epochs, np = orbits ? orbit_n_params(model) : 0;
-    hipStream_t s = h->streams[0];
-    if (int rc = factored_ws_need(h, fac, s, true, contract, c, np)) return rc;
-    GradWs& w = *h->gws;
-    std::vector<int> fast(orbits ? (size_t)B : 0, 0);
-    if (orbits)
-        if (int rc = grad_epoch_lists(h, w, s)) return rc;
-    h->recs.clear();
-    std::vector<double> out((size_t)B * fac.out_stride);
-    for (int b0 = 0; b0 < B; b0 += G) {
-        const int nb = (B - b0 < G) ? B - b0 : G;
-        if (!orbits)
-            HIP_TRY(hipMemcpyAsync(w.Lwl, lwl + (size_t)b0 * c * N, sizeof(double) * (size_t)nb * c * N, hipMemcpyHostToDevice, s));
-        else if (int rc = orbit_front(h, w, s, nb, c, model, np, p_orb + (size_t)b0 * np))
-            return rc;
-        HIP_TRY(hipMemcpyAsync(w.Gp, gp + (size_t)b0 * 2 * c, sizeof(double) * (size_t)nb * 2 * c, hipMemcpyHostToDevice, s));
-        if (tv) HIP_TRY(hipMemcpyAsync(w.Tau, tau + (size_t)b0 * c, sizeof(double) * (size_t)nb * c, hipMemcpyHostToDevice, s));
-        if (int rc = factor_group(h, fac, s, nb, c, mu_GP, true)) return rc;
-        if (contract) {
-            double cunits = 0.0;
-            for (int tj = 0; tj < P; ++tj) cunits += (double)(tj + 1) * (P - tj + fac.Q);
-            if (int rc = prof_launch(h, s, PSOAP_K_GRAD, TILE_FLOPS * cunits * nb, 0.0, [&] {
-                    with_components(c, [&](auto nc) {
-                        if (marg)
-                            hipLaunchKernelGGL(k_marg_grad_contract<nc()>, dim3(ntiles, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s,
-                                               (const double*)w.A.p, mstride, ld, N, Npad, P, (const double*)w.Lwl.p,
-                                               (const double*)w.Gp.p, (const double*)w.Alpha.p, w.Part.p, (const double*)fac.Vt->p,
-                                               fac.m_stride, fac.ldm, fac.S);
-                        else if (tv)
-                            hipLaunchKernelGGL(k_tv_grad_contract<nc()>, dim3(ntiles, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s,
-                                               (const double*)w.A.p, mstride, ld, N, Npad, P, (const double*)w.Lwl.p,
-                                               (const double*)h->dTimes.p, (const double*)w.Gp.p, (const double*)w.Tau.p,
-                                               (const double*)w.Alpha.p, w.Part.p);
-                        else
-                            hipLaunchKernelGGL(k_grad_contract<nc()>, dim3(ntiles, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s,
-                                               (const double*)w.A.p, mstride, ld, N, Npad, P, (const double*)w.Lwl.p,
-                                               (const double*)w.Gp.p, (const double*)w.Alpha.p, w.Part.p);
-                    });
-                })) return rc;
-            if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
-                    if (tv)
-                        hipLaunchKernelGGL(k_tv_grad_finish, dim3(P + 1, nb), dim3(128), 0, s, (const double*)w.Part.p,
-                                           (const double*)w.Alpha.p, (const double*)w.Gp.p, (const double*)w.Tau.p, c, N, Npad, P,
-                                           w.GradGp.p, w.GradTau.p, w.GradX.p, w.GradMu.p);
-                    else
-                        hipLaunchKernelGGL(k_grad_finish, dim3(P + 1, nb), dim3(128), 0, s, (const double*)w.Part.p,
-                                           (const double*)w.Alpha.p, (const double*)w.Gp.p, c, N, Npad, P, w.GradGp.p, w.GradX.p,
-                                           w.GradMu.p);
-                })) return rc;
-        }
-        HIP_TRY(hipMemcpyAsync(out.data() + (size_t)b0 * fac.out_stride, fac.Out->p, sizeof(double) * (size_t)nb * fac.out_stride,
-                               hipMemcpyDeviceToHost, s));
-        if (contract) {
-            HIP_TRY(hipMemcpyAsync(grad_gp + (size_t)b0 * 2 * c, w.GradGp, sizeof(double) * (size_t)nb * 2 * c, hipMemcpyDeviceToHost, s));
-            if (tv) HIP_TRY(hipMemcpyAsync(grad_tau + (size_t)b0 * c, w.GradTau, sizeof(double) * (size_t)nb * c, hipMemcpyDeviceToHost, s));
-            if (grad_lwl)
-                HIP_TRY(hipMemcpyAsync(grad_lwl + (size_t)b0 * c * N, w.GradX, sizeof(double) * (size_t)nb * c * N, hipMemcpyDeviceToHost, s));
-            if (grad_mu) HIP_TRY(hipMemcpyAsync(grad_mu + b0, w.GradMu, sizeof(double) * nb, hipMemcpyDeviceToHost, s));
-            if (orbits)
-                if (int rc = orbit_back(h, w, s, nb, c, np, grad_orb + (size_t)b0 * np,
-                                        grad_vel ? grad_vel + (size_t)b0 * c * ne : nullptr, fast.data() + b0))
-                    return rc;
-        }
-        HIP_TRY(hipStreamSynchronize(s));       // the next group reuses the workspace and the caller's arrays are pageable
-    }
-    if (collect_timings(h)) return 1;
-    // a negative hyper-parameter, a faster-than-light orbit, a tau that is no time scale, a K (or under the baseline an M) that
-    // does not factor -> -inf, and no gradient there
-    for (int b = 0; b < B; ++b)
-        if (values_out(out.data(), fac.out_stride, b,
-                       proposal_refused(gp, c, b, orbits ? fast.data() : nullptr) || (tv && tau_refused(tau, c, b)), lnp,
-                       fac.parts ? parts : nullptr) &&
-            contract)
-            poison_gradient(b, c, N, ne, np, grad_gp, grad_tau, grad_lwl, grad_mu, grad_orb, grad_vel);
-    return 0;
-}
-
+// ---- the analysis paths, from here to the fills: an entry is its argument checks and one call of a run of analysis_host.hpp
+// (fisher_run and loo_run make their checks themselves, under the entry's name); a *_release is release_ws (factor_host.hpp)
+// ---- gradient of the likelihood (grad_kernels.hpp): grad_run ----------------------------------------
 extern "C" int psoap_chunk_lnlike_grad(psoap_chunk* h, int B, int c, const double* lwl, const double* gp, double mu_GP,
                                        double* lnp, double* grad_gp, double* grad_lwl, double* grad_mu)
 {
     if (!h || !lwl || !gp || !lnp || !grad_gp) FAIL("psoap_chunk_lnlike_grad: bad arguments");
     if (B < 1) FAIL("psoap_chunk_lnlike_grad: B must be at least 1");
     if (c < 1 || c > 3) FAIL("number of components must be 1, 2 or 3");
-    if (h->stream.open) FAIL("psoap_chunk_lnlike_grad: the handle has an open stream (psoap_stream_close first)");
-    return grad_run(h, "psoap_chunk_lnlike_grad", false, B, c, lwl, -1, nullptr, gp, nullptr, mu_GP, lnp, nullptr, grad_gp, nullptr,
-                    grad_lwl, grad_mu, nullptr, nullptr, true);
+    if (int rc = analysis_refused(h, "psoap_chunk_lnlike_grad", false, B, c)) return rc;
+    return grad_run(h, false, B, c, lwl, -1, nullptr, gp, nullptr, mu_GP, lnp, nullptr, grad_gp, nullptr, grad_lwl, grad_mu, nullptr,
+                    nullptr, true);
 }
 
 extern "C" int psoap_chunk_lnprob_grad(psoap_chunk* h, int B, int model, const double* p_orb, const double* gp, double mu_GP,
@@ -2513,10 +2112,10 @@ extern "C" int psoap_chunk_lnprob_grad(psoap_chunk* h, int B, int model, const d
     if (!h || !p_orb || !gp || !lnp || !grad_orb || !grad_gp) FAIL("psoap_chunk_lnprob_grad: bad arguments");
     if (B < 1) FAIL("psoap_chunk_lnprob_grad: B must be at least 1");
     if (!h->dGrid || !h->dDates) FAIL("psoap_chunk_lnprob_grad: call psoap_chunk_set_grid and psoap_chunk_set_dates first");
-    if (h->stream.open) FAIL("psoap_chunk_lnprob_grad: the handle has an open stream (psoap_stream_close first)");
+    if (int rc = analysis_refused(h, "psoap_chunk_lnprob_grad", false, B, 0)) return rc;
     if (int rc = check_orbits(model, B, p_orb)) return rc;
-    return grad_run(h, "psoap_chunk_lnprob_grad", false, B, orbit_n_components(model), nullptr, model, p_orb, gp, nullptr, mu_GP,
-                    lnp, nullptr, grad_gp, nullptr, nullptr, grad_mu, grad_orb, grad_vel, true);
+    return grad_run(h, false, B, orbit_n_components(model), nullptr, model, p_orb, gp, nullptr, mu_GP, lnp, nullptr, grad_gp,
+                    nullptr, nullptr, grad_mu, grad_orb, grad_vel, true);
 }
 
 // stand-alone, beside psoap_orbit_velocities: vel_out (B, c, n_dates), jac_out (B, c, n_dates, n_orb)
@@ -2579,122 +2178,11 @@ extern "C" int psoap_chunk_lnlike_tv_grad(psoap_chunk* h, int B, int c, const do
     if (h->marg.valid)
         FAIL("psoap_chunk_lnlike_tv_grad: the handle has a baseline (psoap_chunk_set_baseline): the time-variable kernel under the "
              "marginalised continuum is not built yet");
-    return grad_run(h, "psoap_chunk_lnlike_tv_grad", false, B, c, lwl, -1, nullptr, gp, tau, mu_GP, lnp, nullptr, grad_gp, grad_tau,
-                    grad_lwl, grad_mu, nullptr, nullptr, grad_gp != nullptr);
+    return grad_run(h, false, B, c, lwl, -1, nullptr, gp, tau, mu_GP, lnp, nullptr, grad_gp, grad_tau, grad_lwl, grad_mu, nullptr,
+                    nullptr, grad_gp != nullptr);
 }
 
-// ---- Fisher information of the likelihood (fisher_kernels.hpp) --------------------------------------
-// One matrix through the gradient's workspace and factorisation, then K^-1 and, tangent after tangent, K_t, Z = K_t K^-1
-// and the contraction of G_t = 1/2 (K^-1 Z + Z^T K^-1) -- on the handle's first stream behind whatever the handle has in flight; neither
-// the proposal slots nor the workspaces of the likelihood paths are touched.
-// `marg`: under Kt = K + Ht Ht^T (marg_fisher_kernels.hpp) -- the factorisation is the marginal gradient's for one matrix
-// and k_marg_fisher_kinv forms Kt^-1 where k_fisher_kinv forms K^-1; everything per tangent is the same launch.
-static int fisher_run(psoap_chunk* h, const char* who, bool marg, int c, const double* lwl, const double* gp, int T,
-                      const double* tan_lwl, const double* tan_gp, double* fisher, double* fisher_mu)
-{
-    if (!h || !lwl || !gp || !tan_gp || !fisher) FAIL(std::string(who) + ": bad arguments");
-    if (c < 1 || c > 3) FAIL("number of components must be 1, 2 or 3");
-    if (T < 1 || T > FISHER_MAX_T) FAIL(std::string(who) + ": the number of tangents must be between 1 and 32");
-    if (h->stream.open) FAIL(std::string(who) + ": the handle has an open stream (psoap_stream_close first)");
-    if (marg)
-        if (const char* why = marg_grad_check(1, c, h->marg.valid, h->marg.stale_weight)) FAIL(std::string(who) + ": " + why);
-    DEVICE_SCOPE(h->device);
-    if (int rc = enter_device(h->device)) return rc;
-    hipStream_t s = h->streams[0];
-    const Factored fac = factored(h, marg, 1);
-    const int N = h->N, Npad = h->Npad, P = h->P, ld = fac.ld;
-    const size_t sq = (size_t)Npad * Npad, CN = (size_t)c * N;
-    const int ntiles = P * (P + 1) / 2;
-    if (!h->fws) h->fws.reset(new FisherWs());
-    if (int rc = factored_ws_need(h, fac, s, false, false)) return rc;
-    GradWs& w = *h->gws;
-    FisherWs& f = *h->fws;
-    if (marg) HIP_TRY(f.V.need(fac.S));
-    HIP_TRY(f.Kinv.need(sq));
-    HIP_TRY(f.Kt.need(sq));
-    HIP_TRY(f.Z.need(sq));
-    HIP_TRY(f.TanX.need((size_t)T * CN));
-    HIP_TRY(f.TanGp.need((size_t)T * 2 * c));
-    HIP_TRY(f.Part.need((size_t)ntiles * GradTile<false>::DOUBLES));
-    HIP_TRY(f.GGp.need((size_t)T * 2 * c));
-    HIP_TRY(f.GX.need((size_t)T * CN));
-    HIP_TRY(f.Y.need(Npad));
-    HIP_TRY(f.Mu.need(2));
-    HIP_TRY(f.F.need((size_t)T * T));
-    HIP_TRY(f.Info.need(1));
-    h->recs.clear();
-    HIP_TRY(hipMemcpyAsync(w.Lwl, lwl, sizeof(double) * CN, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(w.Gp, gp, sizeof(double) * 2 * c, hipMemcpyHostToDevice, s));
-    if (tan_lwl) HIP_TRY(hipMemcpyAsync(f.TanX, tan_lwl, sizeof(double) * (size_t)T * CN, hipMemcpyHostToDevice, s));
-    else HIP_TRY(hipMemsetAsync(f.TanX, 0, sizeof(double) * (size_t)T * CN, s));
-    HIP_TRY(hipMemcpyAsync(f.TanGp, tan_gp, sizeof(double) * (size_t)T * 2 * c, hipMemcpyHostToDevice, s));
-    // (F does not depend on the data: any mu_GP)
-    if (int rc = factor_group(h, fac, s, 1, c, 0.0, false)) return rc;
-    double kunits = 0.0;
-    for (int tj = 0; tj < P; ++tj) kunits += (double)(tj + 1) * (P - tj + fac.Q);
-    if (int rc = prof_launch(h, s, PSOAP_K_GRAD, TILE_FLOPS * kunits, 0.0, [&] {
-            if (marg)
-                hipLaunchKernelGGL(k_marg_fisher_kinv, dim3(ntiles), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)w.A.p, ld,
-                                   Npad, P, (const double*)fac.Vt->p, fac.ldm, fac.S, f.Kinv.p);
-            else
-                hipLaunchKernelGGL(k_fisher_kinv, dim3(ntiles), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)w.A.p, ld, Npad,
-                                   P, f.Kinv.p);
-        })) return rc;
-    if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
-            hipLaunchKernelGGL(k_acc_total, dim3(1), dim3(1), 0, s, (const MatAcc*)w.Acc.p, P, f.Info.p);
-            hipLaunchKernelGGL(k_fisher_w1, dim3(N), dim3(256), 0, s, (const double*)w.A.p, ld, Npad, N, f.Y.p);
-            if (marg) {
-                hipLaunchKernelGGL(k_marg_fisher_v1, dim3(fac.S), dim3(256), 0, s, (const double*)fac.Vt->p, fac.ldm, fac.S, N,
-                                   f.V.p);
-                hipLaunchKernelGGL(k_marg_fisher_mu, dim3(1), dim3(256), 0, s, (const double*)f.Y.p, N, (const double*)f.V.p, fac.S,
-                                   f.Mu.p);
-            } else
-                hipLaunchKernelGGL(k_fisher_mu, dim3(1), dim3(256), 0, s, (const double*)f.Y.p, N, f.Mu.p);
-        })) return rc;
-    for (int t = 0; t < T; ++t) {
-        if (int rc = prof_launch(h, s, PSOAP_K_FILL, 0.0, 8.0 * (double)sq, [&] {
-                with_components(c, [&](auto nc) {
-                    hipLaunchKernelGGL(k_fisher_tangent_fill<nc()>, dim3(P * P), dim3(256), 0, s, f.Kt.p, Npad, N, P,
-                                       (const double*)w.Lwl.p, (const double*)w.Gp.p, (const double*)(f.TanX.p + (size_t)t * CN),
-                                       (const double*)(f.TanGp.p + (size_t)t * 2 * c));
-                });
-            })) return rc;
-        if (int rc = prof_launch(h, s, PSOAP_K_GRAD, TILE_FLOPS * P * ((double)P * P + 2.0 * ntiles), 0.0, [&] {
-                hipLaunchKernelGGL(k_fisher_gemm, dim3(P * P), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)f.Kt.p,
-                                   (const double*)f.Kinv.p, Npad, P, f.Z.p);
-                with_components(c, [&](auto nc) {
-                    hipLaunchKernelGGL(k_fisher_contract<nc()>, dim3(ntiles), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s,
-                                       (const double*)f.Kinv.p, (const double*)f.Z.p, N, Npad, P, (const double*)w.Lwl.p,
-                                       (const double*)w.Gp.p, f.Part.p);
-                });
-            })) return rc;
-        // the gradient's finishing sums as they are: its alpha is W 1 here, and its sum over alpha goes nowhere (Mu[1])
-        if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
-                hipLaunchKernelGGL(k_grad_finish, dim3(P + 1, 1), dim3(128), 0, s, (const double*)f.Part.p, (const double*)f.Y.p,
-                                   (const double*)w.Gp.p, c, N, Npad, P, f.GGp.p + (size_t)t * 2 * c, f.GX.p + (size_t)t * CN,
-                                   f.Mu.p + 1);
-            })) return rc;
-    }
-    if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
-            hipLaunchKernelGGL(k_fisher_dot, dim3(T, T), dim3(256), 0, s, (const double*)f.TanX.p, (const double*)f.TanGp.p,
-                               (const double*)f.GX.p, (const double*)f.GGp.p, c, N, T, f.F.p);
-        })) return rc;
-    MatAcc info;
-    double value = 0.0;      // (marg: -inf also when M does not factor)
-    if (marg) HIP_TRY(hipMemcpyAsync(&value, fac.Out->p, sizeof(double), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(fisher, f.F, sizeof(double) * (size_t)T * T, hipMemcpyDeviceToHost, s));
-    if (fisher_mu) HIP_TRY(hipMemcpyAsync(fisher_mu, f.Mu, sizeof(double), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(&info, f.Info, sizeof info, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (collect_timings(h)) return 1;
-    // the conventions of the likelihood: a negative hyper-parameter or a matrix that is not positive definite -> no information
-    if (info.info != 0.0 || value == -INFINITY || proposal_refused(gp, c, 0)) {
-        for (size_t k = 0; k < (size_t)T * T; ++k) fisher[k] = NAN;
-        if (fisher_mu) *fisher_mu = NAN;
-    }
-    return 0;
-}
-
+// ---- Fisher information of the likelihood (fisher_kernels.hpp): fisher_run ---------------------------
 extern "C" int psoap_chunk_fisher(psoap_chunk* h, int c, const double* lwl, const double* gp, int T, const double* tan_lwl,
                                   const double* tan_gp, double* fisher, double* fisher_mu)
 {
@@ -2714,188 +2202,25 @@ extern "C" int psoap_chunk_fisher_release(psoap_chunk* h)
     return release_ws(h, [&] { h->fws.reset(); });
 }
 
-// ---- Fisher information of the per-epoch velocities (vel_fisher_kernels.hpp) ------------------------
-// The launches of psoap_chunk_fisher_vel up to k_vel_finish, for it and for psoap_chunk_info_vel (inside the caller's device
-// scope, after its checks): afterwards F is in h->vws->F, K^-1 in the Fisher workspace, the plan in h->vws->Plan and the
-// epoch of every pixel in h->vws->Epoch.  `marg`: under the handle's baseline, Kt^-1 by k_marg_fisher_kinv as fisher_run forms
-// it.  `values`: the value record and alpha (alpha_m) of the data at mu_GP as well (factor_group).
-static int vel_fisher_launches(psoap_chunk* h, hipStream_t s, const Factored& fac, bool values, int c, const double* lwl,
-                               const double* gp, double mu_GP, int n_epochs, const int32_t* epoch, VelFisherPlan& pl,
-                               std::vector<int>& packed /* the caller keeps it until its stream is drained */)
-{
-    const int N = h->N, Npad = h->Npad, P = h->P, ld = fac.ld;
-    const size_t sq = (size_t)Npad * Npad, CN = (size_t)c * N, T = (size_t)c * n_epochs;
-    const int ntiles = P * (P + 1) / 2;
-    vel_fisher_plan(c, N, n_epochs, epoch, pl);
-    vel_plan_pack(pl, packed);
-    const VelPlanOffsets off = vel_plan_offsets(Npad, P, pl.S, n_epochs);
-    if (!h->fws) h->fws.reset(new FisherWs());
-    if (!h->vws) h->vws.reset(new VelFisherWs());
-    if (int rc = factored_ws_need(h, fac, s, values, false)) return rc;
-    GradWs& w = *h->gws;
-    FisherWs& f = *h->fws;
-    VelFisherWs& v = *h->vws;
-    HIP_TRY(f.Kinv.need(sq));
-    HIP_TRY(f.Info.need(1));
-    HIP_TRY(v.Dv.need((size_t)c * sq));
-    HIP_TRY(v.Z.need((size_t)c * sq));
-    HIP_TRY(v.Part.need((size_t)pl.part_doubles));
-    HIP_TRY(v.F.need(T * T));
-    HIP_TRY(v.Plan.need(packed.size()));
-    HIP_TRY(v.Epoch.need((size_t)N));
-    h->recs.clear();
-    HIP_TRY(hipMemcpyAsync(w.Lwl, lwl, sizeof(double) * CN, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(w.Gp, gp, sizeof(double) * 2 * c, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(v.Plan, packed.data(), sizeof(int) * packed.size(), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(v.Epoch, epoch, sizeof(int32_t) * (size_t)N, hipMemcpyHostToDevice, s));
-    // (F does not depend on the data: any mu_GP)
-    if (int rc = factor_group(h, fac, s, 1, c, mu_GP, values)) return rc;
-    double kunits = 0.0;
-    for (int tj = 0; tj < P; ++tj) kunits += (double)(tj + 1) * (P - tj + fac.Q);
-    if (int rc = prof_launch(h, s, PSOAP_K_GRAD, TILE_FLOPS * kunits, 0.0, [&] {
-            if (fac.marg)
-                hipLaunchKernelGGL(k_marg_fisher_kinv, dim3(ntiles), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)w.A.p, ld,
-                                   Npad, P, (const double*)fac.Vt->p, fac.ldm, fac.S, f.Kinv.p);
-            else
-                hipLaunchKernelGGL(k_fisher_kinv, dim3(ntiles), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)w.A.p, ld, Npad,
-                                   P, f.Kinv.p);
-        })) return rc;
-    if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
-            hipLaunchKernelGGL(k_acc_total, dim3(1), dim3(1), 0, s, (const MatAcc*)w.Acc.p, P, f.Info.p);
-        })) return rc;
-    const int* plan = v.Plan.p;
-    if (int rc = prof_launch(h, s, PSOAP_K_FILL, 0.0, 8.0 * (double)sq * c, [&] {
-            hipLaunchKernelGGL(k_vel_dv_fill, dim3(P * P, c), dim3(256), 0, s, v.Dv.p, sq, Npad, N, P, (const double*)w.Lwl.p,
-                               (const double*)w.Gp.p, (const int*)v.Epoch.p);
-        })) return rc;
-    if (int rc = prof_launch(h, s, PSOAP_K_GRAD, TILE_FLOPS * pl.tile_units, 0.0, [&] {
-            hipLaunchKernelGGL(k_vel_z, dim3(P * P, c), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)f.Kinv.p,
-                               (const double*)v.Dv.p, sq, Npad, plan + off.tiles_all, v.Z.p);
-            for (int k = 0; k < c; ++k)
-                for (int j = 0; j <= k; ++j) {
-                    const double *Zk = v.Z.p + (size_t)k * sq, *Zj = v.Z.p + (size_t)j * sq;
-                    const double *Dk = v.Dv.p + (size_t)k * sq, *Dj = v.Dv.p + (size_t)j * sq;
-                    double* part = v.Part.p + (size_t)(k * (k + 1) / 2 + j) * pl.S * pl.S;
-                    if (k == j)
-                        hipLaunchKernelGGL(k_vel_contract<true>, dim3(ntiles), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s,
-                                           (const double*)f.Kinv.p, Zk, Zj, Dk, Dj, Npad, pl.S, plan + off.tiles_upper,
-                                           plan + off.slot_of, plan + off.slot_first, part);
-                    else
-                        hipLaunchKernelGGL(k_vel_contract<false>, dim3(P * P), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s,
-                                           (const double*)f.Kinv.p, Zk, Zj, Dk, Dj, Npad, pl.S, plan + off.tiles_all,
-                                           plan + off.slot_of, plan + off.slot_first, part);
-                }
-        })) return rc;
-    return prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
-        hipLaunchKernelGGL(k_vel_finish, dim3((unsigned)((T * T + 63) / 64)), dim3(64), 0, s, (const double*)v.Part.p, pl.S, c,
-                           n_epochs, plan + off.epoch_ptr, plan + off.epoch_slots, plan + off.slot_block, v.F.p);
-    });
-}
-
-// One matrix through the gradient's workspace and factorisation and the Fisher workspace's K^-1, as fisher_run; then Dv_k and
-// Z_k = K^-1 Dv_k for every component, the c (c + 1) / 2 products X_kj with their binning epilogue, and the finishing sums --
-// on the handle's first stream behind whatever the handle has in flight; neither the proposal slots nor the workspaces of
-// the likelihood paths are touched.
+// ---- Fisher information of the per-epoch velocities (vel_fisher_kernels.hpp): fisher_vel_run ----------
 extern "C" int psoap_chunk_fisher_vel(psoap_chunk* h, int c, const double* lwl, const double* gp, int n_epochs,
                                       const int32_t* epoch, double* fisher)
 {
     if (!h || !lwl || !gp || !epoch || !fisher) FAIL("psoap_chunk_fisher_vel: bad arguments");
     if (const char* why = vel_fisher_check(c, h->N, n_epochs, epoch)) FAIL(std::string("psoap_chunk_fisher_vel: ") + why);
-    if (h->stream.open) FAIL("psoap_chunk_fisher_vel: the handle has an open stream (psoap_stream_close first)");
-    DEVICE_SCOPE(h->device);
-    if (int rc = enter_device(h->device)) return rc;
-    hipStream_t s = h->streams[0];
-    const Factored fac = factored(h, false, 1);
-    const size_t T = (size_t)c * n_epochs;
-    VelFisherPlan pl;
-    std::vector<int> packed;
-    if (int rc = vel_fisher_launches(h, s, fac, false, c, lwl, gp, 0.0, n_epochs, epoch, pl, packed)) return rc;
-    MatAcc info;
-    HIP_TRY(hipMemcpyAsync(fisher, h->vws->F, sizeof(double) * T * T, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(&info, h->fws->Info, sizeof info, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (collect_timings(h)) return 1;
-    // the conventions of the likelihood: a negative hyper-parameter or a matrix that is not positive definite -> no information
-    if (info.info != 0.0 || proposal_refused(gp, c, 0))
-        for (size_t k = 0; k < T * T; ++k) fisher[k] = NAN;
-    return 0;
+    if (int rc = analysis_refused(h, "psoap_chunk_fisher_vel", false, 1, c)) return rc;
+    return fisher_vel_run(h, c, lwl, gp, n_epochs, epoch, fisher);
 }
 
-// ---- observed information of the per-epoch velocities (vel_newton_kernels.hpp) -----------------------
-// Value, gradient, F and J from ONE factorisation: the launches of psoap_chunk_fisher_vel with the value record and alpha
-// (under the baseline: the marginal ones), then the pair pass over K^-1, U, V = K^-1 U, U^T V and the finishing kernel.
+// ---- observed information of the per-epoch velocities (vel_newton_kernels.hpp): info_vel_run ----------
 extern "C" int psoap_chunk_info_vel(psoap_chunk* h, int marg, int c, const double* lwl, const double* gp, double mu_GP,
                                     int n_epochs, const int32_t* epoch, double* lnp, double* grad, double* fisher,
                                     double* observed)
 {
     if (!h || !lwl || !gp || !epoch || !lnp || !grad || !fisher || !observed) FAIL("psoap_chunk_info_vel: bad arguments");
     if (const char* why = vel_fisher_check(c, h->N, n_epochs, epoch)) FAIL(std::string("psoap_chunk_info_vel: ") + why);
-    if (h->stream.open) FAIL("psoap_chunk_info_vel: the handle has an open stream (psoap_stream_close first)");
-    if (marg)
-        if (const char* why = marg_grad_check(1, c, h->marg.valid, h->marg.stale_weight))
-            FAIL(std::string("psoap_chunk_info_vel: ") + why);
-    DEVICE_SCOPE(h->device);
-    if (int rc = enter_device(h->device)) return rc;
-    hipStream_t s = h->streams[0];
-    const Factored fac = factored(h, marg != 0, 1);
-    const int N = h->N, Npad = h->Npad, P = h->P;
-    const size_t T = (size_t)c * n_epochs;
-    const int Tpad = round_up((int)T, NB), Tp = Tpad / NB;
-    VelFisherPlan pl;
-    std::vector<int> packed;
-    if (int rc = vel_fisher_launches(h, s, fac, true, c, lwl, gp, mu_GP, n_epochs, epoch, pl, packed)) return rc;
-    const VelPlanOffsets off = vel_plan_offsets(Npad, P, pl.S, n_epochs);
-    const size_t S = (size_t)pl.S;
-    if (!h->nws) h->nws.reset(new VelNewtonWs());
-    GradWs& w = *h->gws;
-    FisherWs& f = *h->fws;
-    VelFisherWs& v = *h->vws;
-    VelNewtonWs& nw = *h->nws;
-    HIP_TRY(nw.Y.need((size_t)c * S * Npad));
-    HIP_TRY(nw.A.need((size_t)c * S * S));
-    HIP_TRY(nw.B.need((size_t)c * S * S));
-    HIP_TRY(nw.U.need((size_t)Npad * Tpad));
-    HIP_TRY(nw.V.need((size_t)Npad * Tpad));
-    HIP_TRY(nw.M.need((size_t)Tpad * Tpad));
-    HIP_TRY(nw.J.need(T * T));
-    HIP_TRY(nw.Grad.need(T));
-    const int* plan = v.Plan.p;
-    if (int rc = prof_launch(h, s, PSOAP_K_FILL, 0.0, 8.0 * (double)Npad * Npad * c, [&] {
-            hipLaunchKernelGGL(k_vel_pair, dim3(P * P, c), dim3(VEL_PAIR_THREADS), 0, s, (const double*)f.Kinv.p,
-                               (const double*)w.Alpha.p, Npad, N, P, pl.S, (const double*)w.Lwl.p, (const double*)w.Gp.p,
-                               (const int*)v.Epoch.p, plan + off.slot_of, plan + off.slot_first, nw.Y.p, nw.A.p, nw.B.p);
-        })) return rc;
-    if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
-            hipLaunchKernelGGL(k_vel_u, dim3((Npad + 255) / 256, Tpad), dim3(256), 0, s, (const double*)nw.Y.p, Npad, N, pl.S, c,
-                               n_epochs, Tpad, (const int*)v.Epoch.p, plan + off.epoch_ptr, plan + off.epoch_slots, nw.U.p);
-        })) return rc;
-    if (int rc = prof_launch(h, s, PSOAP_K_GRAD, TILE_FLOPS * ((double)P * P * Tp + 0.5 * P * Tp * (Tp + 1.0)), 0.0, [&] {
-            hipLaunchKernelGGL(k_vel_v, dim3(P, Tp), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)f.Kinv.p,
-                               (const double*)nw.U.p, Npad, Tpad, nw.V.p);
-            hipLaunchKernelGGL(k_vel_gram, dim3(Tp, Tp), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)nw.U.p,
-                               (const double*)nw.V.p, Npad, Tpad, nw.M.p);
-        })) return rc;
-    if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
-            hipLaunchKernelGGL(k_vel_newton_finish, dim3((unsigned)((T * T + 63) / 64)), dim3(64), 0, s, (const double*)nw.A.p,
-                               (const double*)nw.B.p, (const double*)nw.M.p, (const double*)v.F.p, pl.S, c, n_epochs, Tpad,
-                               plan + off.epoch_ptr, plan + off.epoch_slots, nw.J.p, nw.Grad.p);
-        })) return rc;
-    MatAcc info;
-    std::vector<double> out((size_t)fac.out_stride);
-    HIP_TRY(hipMemcpyAsync(out.data(), fac.Out->p, sizeof(double) * (size_t)fac.out_stride, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(fisher, v.F, sizeof(double) * T * T, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(observed, nw.J, sizeof(double) * T * T, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(grad, nw.Grad, sizeof(double) * T, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(&info, f.Info, sizeof info, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (collect_timings(h)) return 1;
-    // the conventions of the likelihood: a negative hyper-parameter or a matrix that is not positive definite -> -inf, and
-    // neither gradient nor information there
-    if (values_out(out.data(), fac.out_stride, 0, proposal_refused(gp, c, 0) || info.info != 0.0, lnp, nullptr)) {
-        for (size_t k = 0; k < T * T; ++k) fisher[k] = observed[k] = NAN;
-        for (size_t k = 0; k < T; ++k) grad[k] = NAN;
-    }
-    return 0;
+    if (int rc = analysis_refused(h, "psoap_chunk_info_vel", marg != 0, 1, c)) return rc;
+    return info_vel_run(h, marg != 0, c, lwl, gp, mu_GP, n_epochs, epoch, lnp, grad, fisher, observed);
 }
 
 extern "C" int psoap_chunk_fisher_vel_release(psoap_chunk* h)
@@ -2903,129 +2228,7 @@ extern "C" int psoap_chunk_fisher_vel_release(psoap_chunk* h)
     return release_ws(h, [&] { h->vws.reset(), h->nws.reset(); });
 }
 
-// ---- leave-one-out cross-validation of the likelihood (loo_kernels.hpp) ------------------------------
-// One matrix through the gradient's workspace and factorisation, alpha as the gradient makes it, then the band of K^-1 into
-// the packed epoch blocks, their staged factorisation group after group of equal side, and the finishing kernel -- on the
-// handle's first stream behind whatever the handle has in flight; neither the proposal slots nor the workspaces of the
-// likelihood paths are touched.
-// `marg`: under Kt = K + Ht Ht^T (marg_fisher_kernels.hpp) -- the factorisation, the value and alpha_m are the marginal
-// gradient's for one matrix and k_marg_loo_band scatters the band of Kt^-1 where k_loo_band scatters that of K^-1.
-static int loo_run(psoap_chunk* h, const char* who, bool marg, int c, const double* lwl, const double* gp, double mu_GP,
-                   const int32_t* epoch, int n_epochs, double* lnp, double* loo_logp, double* pix_mean, double* pix_var,
-                   double* pix_logp, double* ep_resid, double* ep_chi2, double* ep_logp, int32_t* ep_npix)
-{
-    if (!h || !lwl || !gp) FAIL(std::string(who) + ": bad arguments");
-    if (c < 1 || c > 3) FAIL("number of components must be 1, 2 or 3");
-    if (epoch && n_epochs < 1) FAIL(std::string(who) + ": n_epochs must be at least 1");
-    if (h->stream.open) FAIL(std::string(who) + ": the handle has an open stream (psoap_stream_close first)");
-    if (marg)
-        if (const char* why = marg_grad_check(1, c, h->marg.valid, h->marg.stale_weight)) FAIL(std::string(who) + ": " + why);
-    const int N = h->N, Npad = h->Npad, P = h->P;
-    LooLayout lay;
-    if (const char* why = loo_layout(epoch, N, n_epochs, lay)) FAIL(std::string(who) + ": " + why);
-    const int ne = epoch ? n_epochs : 0, nblk = (int)lay.blocks.size(), ntile = (int)lay.tiles.size();
-    if (!epoch) ep_resid = ep_chi2 = ep_logp = nullptr, ep_npix = nullptr;
-    DEVICE_SCOPE(h->device);
-    if (int rc = enter_device(h->device)) return rc;
-    const Factored fac = factored(h, marg, 1);
-    const int ld = fac.ld;
-    const size_t CN = (size_t)c * N;
-    hipStream_t s = h->streams[0];
-    if (!h->lws) h->lws.reset(new LooWs());
-    if (int rc = factored_ws_need(h, fac, s, true, false)) return rc;
-    GradWs& w = *h->gws;
-    LooWs& l = *h->lws;
-    HIP_TRY(l.Blk.need((size_t)lay.block_doubles));
-    HIP_TRY(l.Rhs.need((size_t)lay.rhs_doubles));
-    HIP_TRY(l.Sol.need((size_t)lay.rhs_doubles));
-    HIP_TRY(l.Wt.need((size_t)lay.wt_doubles));
-    HIP_TRY(l.Acc.need((size_t)nblk * ACC_ROWS));
-    HIP_TRY(l.Diag.need(N));
-    HIP_TRY(l.Pix.need((size_t)3 * N));
-    HIP_TRY(l.EpResid.need(N));
-    HIP_TRY(l.EpOut.need((size_t)2 * (ne + 1)));
-    HIP_TRY(l.EpNpix.need((size_t)ne + 1));
-    HIP_TRY(l.Logp.need(1));
-    HIP_TRY(l.Blocks.need(nblk));
-    HIP_TRY(l.Tiles.need(ntile));
-    HIP_TRY(l.PixBlock.need(N));
-    HIP_TRY(l.EpBlock.need(lay.epoch_block.size()));
-    h->recs.clear();
-    HIP_TRY(hipMemcpyAsync(w.Lwl, lwl, sizeof(double) * CN, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(w.Gp, gp, sizeof(double) * 2 * c, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(l.Blocks, lay.blocks.data(), sizeof(LooBlock) * (size_t)nblk, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(l.Tiles, lay.tiles.data(), sizeof(LooTile) * (size_t)ntile, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(l.PixBlock, lay.pixel_block.data(), sizeof(int) * (size_t)N, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(l.EpBlock, lay.epoch_block.data(), sizeof(int) * lay.epoch_block.size(), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemsetAsync(l.Blk, 0, sizeof(double) * (size_t)lay.block_doubles, s));
-    // the value and alpha exactly as psoap_chunk_lnlike_grad (marg: psoap_chunk_lnlike_marg_grad) makes them for one matrix
-    auto pad = [&] { hipLaunchKernelGGL(k_loo_pad, dim3(nblk), dim3(128), 0, s, (const LooBlock*)l.Blocks.p, l.Blk.p); };
-    if (int rc = factor_group(h, fac, s, 1, c, mu_GP, true, &pad)) return rc;
-    double bunits = 0.0;      // executed 128^3 products of the band: a diagonal tile issues three quarters of its MFMAs
-    for (const LooTile& t : lay.tiles) bunits += (t.ti == t.tj ? 0.75 : 1.0) * (P - t.tj + fac.Q);
-    if (int rc = prof_launch(h, s, PSOAP_K_GRAD, TILE_FLOPS * bunits, 0.0, [&] {
-            if (marg)
-                hipLaunchKernelGGL(k_marg_loo_band, dim3(ntile), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)w.A.p, ld, N,
-                                   Npad, (const double*)fac.Vt->p, fac.ldm, fac.S, (const LooTile*)l.Tiles.p,
-                                   (const int*)l.PixBlock.p, (const LooBlock*)l.Blocks.p, l.Blk.p);
-            else
-                hipLaunchKernelGGL(k_loo_band, dim3(ntile), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)w.A.p, ld, N, Npad,
-                                   (const LooTile*)l.Tiles.p, (const int*)l.PixBlock.p, (const LooBlock*)l.Blocks.p, l.Blk.p);
-        })) return rc;
-    if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
-            hipLaunchKernelGGL(k_loo_rhs, dim3(nblk), dim3(256), 0, s, (const LooBlock*)l.Blocks.p, (const double*)l.Blk.p,
-                               (const double*)w.Alpha.p, l.Rhs.p, l.Diag.p, l.Acc.p);
-        })) return rc;
-    // the packed blocks through the staged factorisation, one matrix of the batch per block, group after group of equal side
-    if (epoch)
-        for (const LooGroup& g : lay.groups) {
-            const LooBlock& b0 = lay.blocks[(size_t)g.first];
-            const int S = g.side, Pb = S / NB, nb = g.count;
-            const size_t bstride = (size_t)S * S, wstride = (size_t)Pb * NB * NB;
-            for (int p = 0; p < Pb; ++p) {
-                const int k0 = p * NB, nt = Pb - p;
-                const StagedRow row{l.Blk.p + b0.offset, bstride, S, l.Rhs.p + b0.rhs, S, l.Acc.p + (size_t)g.first * ACC_ROWS,
-                                    l.Wt.p + b0.wt + (size_t)p * NB * NB, wstride, nt - 1};
-                auto update = [&] {
-                    hipLaunchKernelGGL(k_panel_update, dim3(nt, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, row.A, bstride, S, k0);
-                };
-                if (int rc = staged_row(h, s, row, nb, k0, p > 0 ? &update : nullptr, TILE_FLOPS * p * nt * nb)) return rc;
-            }
-        }
-    if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
-            hipLaunchKernelGGL(k_loo_finish, dim3(ne + 1), dim3(256), 0, s, N, ne, (const int*)l.EpBlock.p, (const LooBlock*)l.Blocks.p,
-                               (const double*)l.Blk.p, (const double*)l.Wt.p, (const double*)l.Rhs.p, l.Sol.p, (const MatAcc*)l.Acc.p,
-                               (const double*)w.Alpha.p, (const double*)l.Diag.p, (const double*)h->dFl.p, l.Pix.p, l.Pix.p + N,
-                               l.Pix.p + 2 * (size_t)N, l.EpResid.p, l.EpOut.p, l.EpOut.p + (ne + 1), l.EpNpix.p, l.Logp.p);
-        })) return rc;
-    double value = 0.0;
-    HIP_TRY(hipMemcpyAsync(&value, fac.Out->p, sizeof(double), hipMemcpyDeviceToHost, s));
-    if (loo_logp) HIP_TRY(hipMemcpyAsync(loo_logp, l.Logp, sizeof(double), hipMemcpyDeviceToHost, s));
-    if (pix_mean) HIP_TRY(hipMemcpyAsync(pix_mean, l.Pix, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost, s));
-    if (pix_var) HIP_TRY(hipMemcpyAsync(pix_var, l.Pix.p + N, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost, s));
-    if (pix_logp) HIP_TRY(hipMemcpyAsync(pix_logp, l.Pix.p + 2 * (size_t)N, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost, s));
-    if (ep_resid) HIP_TRY(hipMemcpyAsync(ep_resid, l.EpResid, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost, s));
-    if (ep_chi2) HIP_TRY(hipMemcpyAsync(ep_chi2, l.EpOut, sizeof(double) * (size_t)ne, hipMemcpyDeviceToHost, s));
-    if (ep_logp) HIP_TRY(hipMemcpyAsync(ep_logp, l.EpOut.p + (ne + 1), sizeof(double) * (size_t)ne, hipMemcpyDeviceToHost, s));
-    if (ep_npix) HIP_TRY(hipMemcpyAsync(ep_npix, l.EpNpix, sizeof(int32_t) * (size_t)ne, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));       // (the layout's vectors and the caller's pageable arrays)
-    if (collect_timings(h)) return 1;
-    // the conventions of the likelihood: a negative hyper-parameter or a matrix that is not positive definite -> -inf, and
-    // nothing else to say about it
-    if (proposal_refused(gp, c, 0)) value = -INFINITY;
-    if (lnp) *lnp = value;
-    if (value == -INFINITY) {
-        if (loo_logp) *loo_logp = NAN;
-        for (double* v : {pix_mean, pix_var, pix_logp, ep_resid})
-            if (v)
-                for (int i = 0; i < N; ++i) v[i] = NAN;
-        for (double* v : {ep_chi2, ep_logp})
-            if (v)
-                for (int e = 0; e < ne; ++e) v[e] = NAN;
-    }
-    return 0;
-}
-
+// ---- leave-one-out cross-validation of the likelihood (loo_kernels.hpp): loo_run ----------------------
 extern "C" int psoap_chunk_loo(psoap_chunk* h, int c, const double* lwl, const double* gp, double mu_GP, const int32_t* epoch,
                                int n_epochs, double* lnp, double* loo_logp, double* pix_mean, double* pix_var, double* pix_logp,
                                double* ep_resid, double* ep_chi2, double* ep_logp, int32_t* ep_npix)
@@ -3075,105 +2278,6 @@ extern "C" int psoap_chunk_set_baseline(psoap_chunk* h, int order, const double*
     return 0;
 }
 
-// Ht and the tables of the handle's baseline onto the device (once per psoap_chunk_set_baseline or _marg_release)
-static int marg_basis(psoap_chunk* h, MargWs& m, hipStream_t s)
-{
-    if (m.basis_ready) return 0;
-    const MargSetup& su = h->marg;
-    const MargPlan& pl = su.plan;
-    const int N = h->N, Npad = h->Npad, Q = pl.Q, ldh = NB * Q, ne = pl.n_epochs;
-    std::vector<int> tab((size_t)3 * Q), ep(su.epoch.begin(), su.epoch.end());
-    for (int t = 0; t < Q; ++t) {
-        tab[(size_t)marg_tab_first(Q) + t] = pl.first[pl.column[t]];
-        tab[(size_t)marg_tab_column(Q) + t] = pl.column[t];
-        tab[(size_t)marg_tab_slot(Q) + t] = pl.slot[t];
-    }
-    HIP_TRY(m.Ht.need((size_t)Npad * ldh));
-    HIP_TRY(m.X.need(N));
-    HIP_TRY(m.Weight.need(N));
-    HIP_TRY(m.Epoch.need(N));
-    HIP_TRY(m.EpOff.need(ne));
-    HIP_TRY(m.EpScl.need(ne));
-    HIP_TRY(m.Sd.need(pl.order + 1));
-    HIP_TRY(m.Tab.need(tab.size()));
-    HIP_TRY(m.Tiles.need(pl.tiles.size()));
-    HIP_TRY(hipMemsetAsync(m.Ht, 0, sizeof(double) * (size_t)Npad * ldh, s));
-    HIP_TRY(hipMemcpyAsync(m.X, su.x.data(), sizeof(double) * (size_t)N, hipMemcpyHostToDevice, s));
-    if (!su.weight.empty()) HIP_TRY(hipMemcpyAsync(m.Weight, su.weight.data(), sizeof(double) * (size_t)N, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(m.Epoch, ep.data(), sizeof(int) * (size_t)N, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(m.EpOff, pl.off.data(), sizeof(double) * (size_t)ne, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(m.EpScl, pl.scl.data(), sizeof(double) * (size_t)ne, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(m.Sd, su.sd.data(), sizeof(double) * (size_t)(pl.order + 1), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(m.Tab, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(m.Tiles, pl.tiles.data(), sizeof(MargTile) * pl.tiles.size(), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_marg_basis, dim3((N + 255) / 256), dim3(256), 0, s, m.Ht.p, ldh, N, pl.order, Q, (const double*)m.X.p,
-                       (const int*)m.Epoch.p, (const double*)m.EpOff.p, (const double*)m.EpScl.p,
-                       su.weight.empty() ? (const double*)nullptr : (const double*)m.Weight.p, (const double*)m.Sd.p,
-                       (const int*)m.Tab.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(s));       // (the vectors leave scope)
-    m.basis_ready = true;
-    return 0;
-}
-
-// What psoap_chunk_lnlike_marg and marg_grad_factor share.  Their K sweeps differ -- [K | Ht] with no identity to pay for,
-// [K | I | Ht] -- and so does where M lives (m.M, mg.Mx); the rest is here.
-
-// the marginal workspace beyond M for groups of G matrices; `cov`: the inverse of M and the covariance of beta as well
-static int marg_ws_need(psoap_chunk* h, MargWs& m, int G, bool cov)
-{
-    const MargPlan& pl = h->marg.plan;
-    const size_t S = (size_t)NB * pl.Q, q = pl.q, nslab = (h->Npad + 255) / 256;
-    HIP_TRY(m.WtM.need((size_t)G * pl.Q * NB * NB));
-    HIP_TRY(m.Rhs.need((size_t)G * S));
-    HIP_TRY(m.Gam.need((size_t)G * S));
-    HIP_TRY(m.RPart.need((size_t)G * nslab * S));
-    HIP_TRY(m.AccM.need((size_t)G * ACC_ROWS));
-    HIP_TRY(m.Out.need((size_t)G * 5));
-    HIP_TRY(m.Beta.need((size_t)G * q));
-    HIP_TRY(m.Flc.need((size_t)G * h->N));
-    if (cov) {
-        HIP_TRY(m.Minv.need((size_t)G * S * S));
-        HIP_TRY(m.Cov.need((size_t)G * q * q));
-    }
-    return 0;
-}
-
-// m.Rhs = Wh^T z for nb factored matrices, Ah what the kernels of marg_kernels.hpp take for [K | Ht].  Launches only: inside
-// the caller's bracket.
-static void launch_marg_rhs(const psoap_chunk* h, MargWs& m, hipStream_t s, int nb, const double* Ah, size_t mstride, int ld,
-                            const double* z)
-{
-    const int Npad = h->Npad, Q = h->marg.plan.Q, nslab = (Npad + 255) / 256;
-    hipLaunchKernelGGL(k_marg_rhs_partial, dim3(Q, nslab, nb), dim3(256), 0, s, Ah, mstride, ld, Npad, Q, (const int*)m.Tab.p, z,
-                       m.RPart.p, nslab);
-    hipLaunchKernelGGL(k_marg_rhs_finish, dim3((NB * Q + 255) / 256, nb), dim3(256), 0, s, (const double*)m.RPart.p, nslab, Npad, Q,
-                       (const int*)m.Tab.p, m.Rhs.p);
-}
-
-// executed 128^3 products of one Gram matrix M = I + Wh^T Wh: a diagonal tile issues three quarters of its MFMAs
-static double gram_units(const MargPlan& pl, int Npad)
-{
-    double units = 0.0;
-    for (const MargTile& t : pl.tiles) units += (t.ti == t.tj ? 0.75 : 1.0) * (Npad - t.k0) / NB;
-    return units;
-}
-
-// lnL, its parts and g = U_M^-1 y of nb matrices into m.Out and m.Gam from the factored M (m_stride doubles per matrix, ldm
-// per row); with want_sol beta and the corrected flux as well.  The only launch site of k_marg_finish; inside the caller's bracket.
-static void launch_marg_finish(const psoap_chunk* h, const GradWs& w, MargWs& m, hipStream_t s, int nb, const double* M,
-                               size_t m_stride, int ldm, bool want_sol)
-{
-    const MargPlan& pl = h->marg.plan;
-    hipLaunchKernelGGL(k_marg_finish, dim3(nb), dim3(256), 0, s, h->N, h->P, pl.Q, pl.q, pl.order, (const MatAcc*)w.Acc.p,
-                       (const MatAcc*)m.AccM.p, M, m_stride, ldm, (const double*)m.WtM.p, (const double*)m.Rhs.p, m.Gam.p,
-                       (const double*)m.Sd.p, (const int*)m.Epoch.p, (const int*)m.Tab.p, (const double*)m.Ht.p, NB * pl.Q,
-                       (const double*)h->dFl.p, m.Out.p, m.Beta.p, m.Flc.p, want_sol ? 1 : 0);
-}
-
-// Group after group of matrices through the gradient's workspace as [K | Ht] (ld = Npad + 128 Q), then the Gram matrices
-// through the staged kernels once more -- on the handle's first stream behind whatever the handle has in flight; neither
-// the proposal slots nor the workspaces of the likelihood paths are touched.
 extern "C" int psoap_chunk_lnlike_marg(psoap_chunk* h, int B, int c, const double* lwl, const double* gp, double mu_GP,
                                        double* lnp, double* parts, double* beta, double* beta_cov, double* fl_cor)
 {
@@ -3185,181 +2289,17 @@ extern "C" int psoap_chunk_lnlike_marg(psoap_chunk* h, int B, int c, const doubl
     if (h->marg.stale_weight)
         FAIL("psoap_chunk_lnlike_marg: psoap_chunk_set_data changed the data the baseline's weights were given for "
              "(psoap_chunk_set_baseline again)");
-    DEVICE_SCOPE(h->device);
-    if (int rc = enter_device(h->device)) return rc;
-    const MargPlan& pl = h->marg.plan;
-    const int N = h->N, Npad = h->Npad, P = h->P, Q = pl.Q, q = pl.q, order = pl.order;
-    const int S = NB * Q, ld = Npad + S, ldm = 2 * S, ldh = S;
-    const size_t mstride = (size_t)Npad * ld, m_stride = (size_t)S * ldm, wstride = (size_t)Q * NB * NB;
-    const int G = marg_group_size(B, Npad, Q), ngram = Q * (Q + 1) / 2;
-    const bool want_cov = beta_cov != nullptr, want_sol = beta != nullptr || fl_cor != nullptr;
-    if (!h->gws) h->gws.reset(new GradWs());
-    if (!h->mws) h->mws.reset(new MargWs());
-    GradWs& w = *h->gws;
-    MargWs& m = *h->mws;
-    if (int rc = grad_ws_need(h, w, G, mstride, false, false)) return rc;
-    HIP_TRY(m.M.need((size_t)G * m_stride));
-    if (int rc = marg_ws_need(h, m, G, want_cov)) return rc;
-    hipStream_t s = h->streams[0];
-    if (int rc = marg_basis(h, m, s)) return rc;
-    const int* tab = m.Tab.p;
-    h->recs.clear();
-    std::vector<double> out((size_t)B * 5);
-    for (int b0 = 0; b0 < B; b0 += G) {
-        const int nb = (B - b0 < G) ? B - b0 : G;
-        HIP_TRY(hipMemcpyAsync(w.Lwl, lwl + (size_t)b0 * c * N, sizeof(double) * (size_t)nb * c * N, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(w.Gp, gp + (size_t)b0 * 2 * c, sizeof(double) * (size_t)nb * 2 * c, hipMemcpyHostToDevice, s));
-        if (int rc = prof_launch(h, s, PSOAP_K_FILL, 0.0, (double)nb * 12.0 * N * (N + 1.0), [&] {
-                launch_grad_fill(h, w, s, nb, c, mstride, ld);
-                hipLaunchKernelGGL(k_marg_load, dim3(Q * P, nb), dim3(256), 0, s, w.A.p, mstride, ld, Npad, P, (const double*)m.Ht.p,
-                                   ldh, tab);
-            })) return rc;
-        if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
-                hipLaunchKernelGGL(k_init_rhs, dim3((Npad + 255) / 256, nb), dim3(256), 0, s, w.R.p, Npad, N, h->dFl, mu_GP, w.Acc.p);
-            })) return rc;
-        // block row p: the rest of K's row and the appended slots whose first non-zero block row is <= p
-        for (int p = 0; p < P; ++p) {
-            const int k0 = p * NB, act = pl.active[(size_t)p];
-            auto update = [&] {
-                hipLaunchKernelGGL(k_marg_panel_update, dim3(P - p + act, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, w.A.p, mstride, ld,
-                                   k0, P, tab);
-            };
-            if (int rc = staged_row(h, s, grad_row(w, mstride, ld, Npad, P - p - 1 + act), nb, k0, p > 0 ? &update : nullptr,
-                                    TILE_FLOPS * p * (P - p + act) * nb))
-                return rc;
-        }
-        if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] { launch_marg_rhs(h, m, s, nb, w.A.p, mstride, ld, w.R.p); }))
-            return rc;
-        if (int rc = prof_launch(h, s, PSOAP_K_GRAD, TILE_FLOPS * gram_units(pl, Npad) * nb, 0.0, [&] {
-                hipLaunchKernelGGL(k_marg_gram, dim3(ngram, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)w.A.p, mstride, ld,
-                                   Npad, (const MargTile*)m.Tiles.p, m.M.p, m_stride, ldm);
-                if (want_cov) hipLaunchKernelGGL(k_grad_init, dim3(ngram, nb), dim3(256), 0, s, m.M.p, m_stride, ldm, S, Q);
-            })) return rc;
-        // M = U_M^T U_M with bt alongside; with the covariance asked for, [M | I] as the gradient factors [K | I]
-        for (int p = 0; p < Q; ++p) {
-            const int k0 = p * NB;
-            const StagedRow row{m.M.p, m_stride, ldm, m.Rhs.p, S, m.AccM.p, m.WtM.p + (size_t)p * NB * NB, wstride,
-                                want_cov ? Q : Q - p - 1};
-            auto update = [&] {
-                if (want_cov)
-                    hipLaunchKernelGGL(k_grad_panel_update, dim3(Q + 1, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, m.M.p, m_stride, ldm,
-                                       k0, Q);
-                else
-                    hipLaunchKernelGGL(k_panel_update, dim3(Q - p, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, m.M.p, m_stride, ldm, k0);
-            };
-            if (int rc = staged_row(h, s, row, nb, k0, p > 0 ? &update : nullptr, TILE_FLOPS * p * (want_cov ? Q : Q - p) * nb))
-                return rc;
-        }
-        if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] { launch_marg_finish(h, w, m, s, nb, m.M.p, m_stride, ldm, want_sol); }))
-            return rc;
-        if (want_cov)
-            if (int rc = prof_launch(h, s, PSOAP_K_GRAD, 0.0, 0.0, [&] {
-                    for (int b = 0; b < nb; ++b)
-                        hipLaunchKernelGGL(k_fisher_kinv, dim3(ngram), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s,
-                                           (const double*)(m.M.p + (size_t)b * m_stride), ldm, S, Q, m.Minv.p + (size_t)b * S * S);
-                    hipLaunchKernelGGL(k_marg_cov, dim3(q, nb), dim3(256), 0, s, (const double*)m.Minv.p, S, q, order,
-                                       (const double*)m.Sd.p, m.Cov.p);
-                })) return rc;
-        HIP_TRY(hipMemcpyAsync(out.data() + (size_t)b0 * 5, m.Out, sizeof(double) * (size_t)nb * 5, hipMemcpyDeviceToHost, s));
-        if (beta) HIP_TRY(hipMemcpyAsync(beta + (size_t)b0 * q, m.Beta, sizeof(double) * (size_t)nb * q, hipMemcpyDeviceToHost, s));
-        if (fl_cor) HIP_TRY(hipMemcpyAsync(fl_cor + (size_t)b0 * N, m.Flc, sizeof(double) * (size_t)nb * N, hipMemcpyDeviceToHost, s));
-        if (want_cov)
-            HIP_TRY(hipMemcpyAsync(beta_cov + (size_t)b0 * q * q, m.Cov, sizeof(double) * (size_t)nb * q * q, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));       // the next group reuses the workspace and the caller's arrays are pageable
-    }
-    if (collect_timings(h)) return 1;
-    // the conventions of the likelihood: a negative hyper-parameter, a K that is not positive definite or an M that fails to
-    // factor -> -inf, and nothing else to say about it
-    for (int b = 0; b < B; ++b) {
-        if (!values_out(out.data(), 5, b, proposal_refused(gp, c, b), lnp, parts)) continue;
-        if (beta)
-            for (int k = 0; k < q; ++k) beta[(size_t)b * q + k] = NAN;
-        if (beta_cov)
-            for (size_t k = 0; k < (size_t)q * q; ++k) beta_cov[(size_t)b * q * q + k] = NAN;
-        if (fl_cor)
-            for (int i = 0; i < N; ++i) fl_cor[(size_t)b * N + i] = NAN;
-    }
-    return 0;
+    return marg_run(h, B, c, lwl, gp, mu_GP, lnp, parts, beta, beta_cov, fl_cor);
 }
 
-// ---- gradient of that likelihood (marg_grad_kernels.hpp) -------------------------------------------------
-// The staged factorisation of [K | I | Ht] (marg_grad_plan.hpp) and of [M | Xt] for the nb matrices whose grids and
-// hyper-parameters are in w.Lwl and w.Gp.  Afterwards the I block holds Wi = U^-T, the appended block of mg.Mx holds
-// Vt = U_M^-T Wh^T Wi, m.Out the value and its parts with the bits of psoap_chunk_lnlike_marg, mg.Zt = z - Wh g and
-// w.Alpha = alpha_m.
-static int marg_grad_factor(psoap_chunk* h, const Factored& fac, hipStream_t s, int nb, int c, double mu_GP)
-{
-    GradWs& w = *h->gws;
-    MargWs& m = *h->mws;
-    MargGradWs& mg = *h->mgws;
-    const MargPlan& pl = h->marg.plan;
-    const MargGradPlan& gpl = fac.gpl;
-    const int N = h->N, Npad = h->Npad, P = h->P, Q = pl.Q;
-    const int S = fac.S, ld = fac.ld, ldm = fac.ldm, ldh = S, ngram = Q * (Q + 1) / 2, ntiles = P * (P + 1) / 2;
-    const size_t mstride = fac.mstride, m_stride = fac.m_stride, wstride = (size_t)Q * NB * NB;
-    const int* tab = m.Tab.p;
-    double* Ah = w.A.p + Npad;          // what the kernels of marg_kernels.hpp take for [K | Ht]: Ht one block further right
-    if (int rc = prof_launch(h, s, PSOAP_K_FILL, 0.0, (double)nb * 12.0 * N * (N + 1.0), [&] {
-            launch_grad_fill(h, w, s, nb, c, mstride, ld);
-            hipLaunchKernelGGL(k_grad_init, dim3(ntiles, nb), dim3(256), 0, s, w.A.p, mstride, ld, Npad, P);
-            hipLaunchKernelGGL(k_marg_load, dim3(Q * P, nb), dim3(256), 0, s, Ah, mstride, ld, Npad, P, (const double*)m.Ht.p, ldh,
-                               tab);
-        })) return rc;
-    if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
-            hipLaunchKernelGGL(k_init_rhs, dim3((Npad + 255) / 256, nb), dim3(256), 0, s, w.R.p, Npad, N, h->dFl, mu_GP, w.Acc.p);
-        })) return rc;
-    // block row p: the rest of K's row with I_0 .. I_p, and the slots of Ht whose first non-zero block row is <= p
-    for (int p = 0; p < P; ++p) {
-        const int k0 = p * NB;
-        const MargGradRow& row = gpl.rows[(size_t)p];
-        const double units = (double)p * (P - p) + 0.5 * p * (p + 1.0) + (double)p * row.update_h;
-        auto update = [&] {
-            hipLaunchKernelGGL(k_marg_grad_panel_update, dim3(row.update_k + row.update_h, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES,
-                               s, w.A.p, mstride, ld, k0, P, tab);
-        };
-        // the slots of Ht are a second strip: its first tile column moved onto tile column 2 P, and no right-hand side
-        // (r_rows = 0: every column counts as appended, r is only read)
-        StagedRow sr = grad_row(w, mstride, ld, Npad, row.strip_k);
-        sr.A2 = w.A.p + (NB * gpl.tile_H - k0 - NB);
-        sr.strip2 = row.strip_h;
-        if (int rc = staged_row(h, s, sr, nb, k0, row.update_k + row.update_h > 0 ? &update : nullptr, TILE_FLOPS * units * nb))
-            return rc;
-    }
-    if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] { launch_marg_rhs(h, m, s, nb, Ah, mstride, ld, w.R.p); })) return rc;
-    double gunits = gram_units(pl, Npad);
-    for (int sl = 0; sl < Q; ++sl)
-        for (int tj = 0; tj < P; ++tj) gunits += P - std::min(P, std::max(pl.first[(size_t)pl.column[(size_t)sl]], tj));
-    if (int rc = prof_launch(h, s, PSOAP_K_GRAD, TILE_FLOPS * gunits * nb, 0.0, [&] {
-            hipLaunchKernelGGL(k_marg_gram, dim3(ngram, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)Ah, mstride, ld,
-                               Npad, (const MargTile*)m.Tiles.p, mg.Mx.p, m_stride, ldm);
-            hipLaunchKernelGGL(k_marg_grad_cross, dim3(Q * P, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)w.A.p,
-                               mstride, ld, Npad, P, Q, tab, mg.Mx.p, m_stride, ldm);
-        })) return rc;
-    // [M | Xt]: M = U_M^T U_M with bt alongside, and the appended block becomes Vt = U_M^-T Xt
-    for (int p = 0; p < Q; ++p) {
-        const int k0 = p * NB;
-        const StagedRow mrow{mg.Mx.p, m_stride, ldm, m.Rhs.p, S, m.AccM.p, m.WtM.p + (size_t)p * NB * NB, wstride, Q - p - 1 + P};
-        auto update = [&] {
-            hipLaunchKernelGGL(k_panel_update, dim3(Q - p + P, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, mg.Mx.p, m_stride, ldm, k0);
-        };
-        if (int rc = staged_row(h, s, mrow, nb, k0, p > 0 ? &update : nullptr, TILE_FLOPS * p * (Q - p + P) * nb)) return rc;
-    }
-    // lnL and g = U_M^-1 y; z - Wh g; alpha_m
-    return prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
-        launch_marg_finish(h, w, m, s, nb, mg.Mx.p, m_stride, ldm, true);
-        hipLaunchKernelGGL(k_marg_grad_resid, dim3(Npad / 4, nb), dim3(256), 0, s, (const double*)w.A.p, mstride, ld, Npad, Q,
-                           tab, (const double*)w.R.p, (const double*)m.Gam.p, mg.Zt.p);
-        launch_alpha(w, s, nb, mstride, ld, Npad, P, mg.Zt.p);
-    });
-}
-
+// ---- gradient of that likelihood (marg_grad_kernels.hpp): grad_run with `marg` ---------------------------
 extern "C" int psoap_chunk_lnlike_marg_grad(psoap_chunk* h, int B, int c, const double* lwl, const double* gp, double mu_GP,
                                             double* lnp, double* parts, double* grad_gp, double* grad_lwl, double* grad_mu)
 {
     if (!h || !lwl || !gp || !lnp || !grad_gp) FAIL("psoap_chunk_lnlike_marg_grad: bad arguments");
-    if (h->stream.open) FAIL("psoap_chunk_lnlike_marg_grad: the handle has an open stream (psoap_stream_close first)");
-    return grad_run(h, "psoap_chunk_lnlike_marg_grad", true, B, c, lwl, -1, nullptr, gp, nullptr, mu_GP, lnp, parts, grad_gp, nullptr,
-                    grad_lwl, grad_mu, nullptr, nullptr, true);
+    if (int rc = analysis_refused(h, "psoap_chunk_lnlike_marg_grad", true, B, c)) return rc;
+    return grad_run(h, true, B, c, lwl, -1, nullptr, gp, nullptr, mu_GP, lnp, parts, grad_gp, nullptr, grad_lwl, grad_mu, nullptr,
+                    nullptr, true);
 }
 
 extern "C" int psoap_chunk_lnprob_marg_grad(psoap_chunk* h, int B, int model, const double* p_orb, const double* gp, double mu_GP,
@@ -3368,10 +2308,12 @@ extern "C" int psoap_chunk_lnprob_marg_grad(psoap_chunk* h, int B, int model, co
     if (!h || !p_orb || !gp || !lnp || !grad_orb || !grad_gp) FAIL("psoap_chunk_lnprob_marg_grad: bad arguments");
     if (B < 1) FAIL("psoap_chunk_lnprob_marg_grad: B must be at least 1");
     if (!h->dGrid || !h->dDates) FAIL("psoap_chunk_lnprob_marg_grad: call psoap_chunk_set_grid and psoap_chunk_set_dates first");
-    if (h->stream.open) FAIL("psoap_chunk_lnprob_marg_grad: the handle has an open stream (psoap_stream_close first)");
+    // (an open stream is refused before the orbits are looked at, the baseline after them: c comes from a checked model)
+    if (int rc = analysis_refused(h, "psoap_chunk_lnprob_marg_grad", false, B, 0)) return rc;
     if (int rc = check_orbits(model, B, p_orb)) return rc;
-    return grad_run(h, "psoap_chunk_lnprob_marg_grad", true, B, orbit_n_components(model), nullptr, model, p_orb, gp, nullptr, mu_GP,
-                    lnp, nullptr, grad_gp, nullptr, nullptr, grad_mu, grad_orb, grad_vel, true);
+    if (int rc = analysis_refused(h, "psoap_chunk_lnprob_marg_grad", true, B, orbit_n_components(model))) return rc;
+    return grad_run(h, true, B, orbit_n_components(model), nullptr, model, p_orb, gp, nullptr, mu_GP, lnp, nullptr, grad_gp,
+                    nullptr, nullptr, grad_mu, grad_orb, grad_vel, true);
 }
 
 // frees the device side of the baseline and the workspace; the baseline itself stays set (the next call builds Ht again)
