@@ -877,7 +877,9 @@ int psoap_dag_plan(int B, int P, int workers, void *out, long long max_tasks, lo
  * created: input order and dense lists, as before.
  * psoap_dag_plan_sky: the throughput list inside the skyline first[0 .. P) (tile (q, j) exists iff q >= first[j]; first
  *   non-decreasing, first[j] <= max(j - 1, 0)); the ctr field of a final carries in bits 24.. how many tiles its block row
- *   is short of P - q.  first all zero: the list of psoap_dag_plan, byte for byte.
+ *   is short of P - q.  first all zero: the list of psoap_dag_plan, byte for byte.  Inside a skyline the tiles of a block
+ *   row are emitted column by column over a queue's matrices and a diagonal tile's pre-accumulation is cut by its clipped
+ *   length (dag_plan.hpp); PSOAP_SKY_SPLIT=0 -- at handle creation, or when this function is called -- keeps the dense order and split rules.
  * The row order is chosen behind every upload from the slot's contents: among convex blends of the first walker's component
  * grids (1, 9, 15 candidates for 1, 2, 3 components; candidate 0 is the first component alone) the one whose union skyline
  * costs the fewest tile-GEMM units, ties to the lowest candidate.  PSOAP_SKY_ORDER=0 at handle creation: always candidate 0.

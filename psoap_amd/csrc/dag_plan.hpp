@@ -19,7 +19,7 @@ namespace psoap {
 // (every wait targets a smaller ticket of the same queue):
 //   for each block row q:  DIAG finals of row q (the queue's matrices)
 //                          PARTs that pre-accumulate the diagonal tile of row q+1 over rows < q
-//                          PARTs + OFF finals of row q (b-major, then j)
+//                          PARTs + OFF finals of row q (b-major, then j; inside a skyline j-major, then b: below)
 // ---------------------------------------------------------------------------------------------
 struct DagPlan {
     std::vector<DagTask> tasks;
@@ -199,6 +199,32 @@ inline bool dag_fixed_plan()
 }
 inline int dag_nominal_share(int workers_total) { const int s = workers_total / STREAM_NOMINAL_LANES / 2; return s > 0 ? s : 1; }
 
+// ---- skyline-aware list rules (scheme 0 inside a skyline; profiles/sky_sched.md, profiles/sky_split_ab.md) ----------------
+// The split and order rules above were measured on dense lists, where a block row offers P - q tiles of q panels each.
+// Inside a skyline a row is a band of tiles whose updates run over q - first[j] panels, and the rules look at that work:
+//   order    the tiles of a block row column by column over the queue's matrices (j-major), not matrix after matrix: tile
+//            (q, q+1), whose strip solve continues into the diagonal task of block q+1, comes up first for EVERY matrix
+//            of the queue and not behind all tiles of the matrices in front of it; within a matrix the order stays j
+//            ascending, which inside a skyline is longest update first (first is non-decreasing);
+//   history  the pre-accumulation of diagonal tile q+1 is cut by its clipped span q - first[q+1] into parts of at
+//            least DAG_SKY_PRE_LEN panels (at most 8 parts), not by "a quarter of the workers".
+// The off-diagonal tiles keep the dense split rule (dag_split_factor on the row's tile count): cutting them by the row's
+// work in panels instead was tried and stayed inside the run-to-run spread (profiles/sky_split_ab.md).
+// The list stays a function of (B, P, scheme, first).  PSOAP_SKY_SPLIT=0 (read at handle creation, and by
+// psoap_dag_plan_sky when it is called): the dense rules inside the skyline, the list as it was.
+inline bool dag_sky_split_env()
+{
+    const char* e = getenv("PSOAP_SKY_SPLIT");
+    return !(e && e[0] == '0');
+}
+constexpr int DAG_SKY_PRE_LEN = 6;
+// PARTs of a pre-accumulation over `span` panels: pieces of at least DAG_SKY_PRE_LEN, at most 8
+inline int dag_sky_pre_parts(int span)
+{
+    const int n = span / DAG_SKY_PRE_LEN;
+    return n < 1 ? 1 : (n > 8 ? 8 : n);
+}
+
 // tiles of block row q inside the skyline `first` of a matrix of P block rows (the diagonal tile included)
 inline int dag_sky_row_tiles(const int* first, int P, int q)
 {
@@ -210,7 +236,8 @@ inline int dag_sky_row_tiles(const int* first, int P, int q)
 // q >= first[j], first non-decreasing with first[j] <= max(j - 1, 0); the update of an existing tile runs over the block rows
 // [first[j], q) and is cut into equal ranges of that.  All zero: the dense list, byte for byte.
 inline void dag_build_queue(DagPlan& plan, const std::vector<int>& mats, const std::vector<int>& Ps, int workers,
-                            int Bq_nominal, int scheme, int Mt = 0, int Ms = 0, int fixed_share = 0, const int* first = nullptr)
+                            int Bq_nominal, int scheme, int Mt = 0, int Ms = 0, int fixed_share = 0, const int* first = nullptr,
+                            bool sky_split = false)
 {
     // Ps[b]: block rows of matrix b.  A heterogeneous batch (matrices of several chunks) walks the block
     // rows of all its matrices together; a matrix simply drops out once its rows are used up.
@@ -229,6 +256,8 @@ inline void dag_build_queue(DagPlan& plan, const std::vector<int>& mats, const s
     std::vector<DagTask> owned_final(Ps.size());          // per matrix: the DIAG(q+1) final to emit behind tile (q, q+1)
     std::vector<char> has_owned(Ps.size(), 0);
     auto fj = [first](int j) { return first ? first[j] : 0; };
+    // (the skyline-aware rules, above)
+    const bool sky = first && sky_split;
     for (int q = 0; q < P; ++q) {
         // tiles of this block row in the queue; uniform batches use the nominal matrix count so that the
         // split factors do not depend on the slot a matrix sits in
@@ -315,7 +344,9 @@ inline void dag_build_queue(DagPlan& plan, const std::vector<int>& mats, const s
         // of row q-1 is finished) is one panel long; the long ones cover [0, q-1) and run a row earlier.
         if (q + 1 < P && q >= 1) {
             const int f_pre = fj(q + 1), span_pre = q - f_pre;      // (skyline: the diagonal tile's history starts at first[q+1])
-            const int S_pre = fixed_share > 0
+            const int S_pre = sky
+                                  ? dag_sky_pre_parts(span_pre)
+                              : fixed_share > 0
                                   ? dag_split_factor(1, q, fixed_share / 4 > 0 ? fixed_share / 4 : 1, scheme)
                                   : dag_split_factor(Bq, span_pre, workers / 4 > 0 ? workers / 4 : 1, scheme);
             for (int b : mats) {
@@ -381,24 +412,33 @@ inline void dag_build_queue(DagPlan& plan, const std::vector<int>& mats, const s
             }
         }
         // 3. off-diagonal tiles of this row
-        for (int b : mats)
-            for (int j = q + 1; j < Ps[b] + Mt && q < Ps[b]; ++j) {
-                if (fj(j) > q) break;      // outside the skyline (first is non-decreasing: so is the rest of the row)
-                const bool owner = cont0 && j == q + 1 && q + 1 < Ps[b];     // its workgroup goes on with DIAG(q+1)
-                dag_emit(plan, DAG_OFF, b, q, j, fj(j), q, s_off(b, q - fj(j)), scheme,
-                         following ? (unsigned char)(DAG_WAITNEXT | (xlink(q) ? DAG_FUSED : 0) |
-                                                     ((j == q + 1 && q + 1 < Ps[b]) ? DAG_NOSOLVE : 0))
-                                   : (unsigned char)(((j == q + 1 && fused(b)) ? DAG_NOSOLVE : 0) | (owner ? DAG_FUSED : 0)),
-                         following ? dag_final_panels() : 1);
-                if (owner) {
-                    if (q == 0) {
-                        dag_emit(plan, DAG_DIAG, b, 1, 1, 0, 1, 1, scheme, DAG_NOSOLVE);   // DIAG(1): one final over [0, 1)
-                    } else {
-                        plan.tasks.push_back(owned_final[b]);
-                        has_owned[b] = 0;
-                    }
+        auto emit_off = [&](int b, int j) {
+            const bool owner = cont0 && j == q + 1 && q + 1 < Ps[b];     // its workgroup goes on with DIAG(q+1)
+            dag_emit(plan, DAG_OFF, b, q, j, fj(j), q, s_off(b, q - fj(j)), scheme,
+                     following ? (unsigned char)(DAG_WAITNEXT | (xlink(q) ? DAG_FUSED : 0) |
+                                                 ((j == q + 1 && q + 1 < Ps[b]) ? DAG_NOSOLVE : 0))
+                               : (unsigned char)(((j == q + 1 && fused(b)) ? DAG_NOSOLVE : 0) | (owner ? DAG_FUSED : 0)),
+                     following ? dag_final_panels() : 1);
+            if (owner) {
+                if (q == 0) {
+                    dag_emit(plan, DAG_DIAG, b, 1, 1, 0, 1, 1, scheme, DAG_NOSOLVE);   // DIAG(1): one final over [0, 1)
+                } else {
+                    plan.tasks.push_back(owned_final[b]);
+                    has_owned[b] = 0;
                 }
             }
+        };
+        if (sky) {
+            // (a skyline batch is uniform: every matrix has P block rows)
+            for (int j = q + 1; j < P && first[j] <= q; ++j)
+                for (int b : mats) emit_off(b, j);
+        } else {
+            for (int b : mats)
+                for (int j = q + 1; j < Ps[b] + Mt && q < Ps[b]; ++j) {
+                    if (fj(j) > q) break;      // outside the skyline (first is non-decreasing: so is the rest of the row)
+                    emit_off(b, j);
+                }
+        }
     }
     if (Ms > 0)
         for (int b : mats) dag_emit_schur(plan, b, Ps[b], Ms);
@@ -476,7 +516,7 @@ inline int dag_auto_scheme(const std::vector<int>& Ps)
 // DagTask::ctr carries in bits 24.. how many tiles its block row is SHORT of the dense P - q (the kernel counts a row's
 // finished tasks against it); zero everywhere in a dense list.
 inline DagPlan dag_build_tasks(const std::vector<int>& Ps, int workers, int scheme = -1, int Mt = 0, int Ms = 0,
-                               int fixed_share = 0, const int* first = nullptr)
+                               int fixed_share = 0, const int* first = nullptr, bool sky_split = false)
 {
     DagPlan plan;
     const int B = (int)Ps.size();
@@ -495,7 +535,7 @@ inline DagPlan dag_build_tasks(const std::vector<int>& Ps, int workers, int sche
         std::vector<int> mats;
         if (g < nq)
             for (int b = g; b < B; b += nq) mats.push_back(b);
-        dag_build_queue(plan, mats, Ps, per_queue, (B + nq - 1) / nq, scheme, Mt, Ms, fixed_share, first);
+        dag_build_queue(plan, mats, Ps, per_queue, (B + nq - 1) / nq, scheme, Mt, Ms, fixed_share, first, sky_split);
         if (scheme >= 1) {
             // Latency scheme: hand the tasks out in order of READINESS instead of block row by block row.
             // A task over panels [pa, pb) can run once block row pb-1 is finished ("stage" pb); within a
@@ -691,11 +731,12 @@ inline int dag_lnlike_scheme(const std::vector<int>& Ps)
 }
 
 // The throughput list of a uniform batch inside the skyline first[0 .. P) (sky_kernels.hpp; dag_build_queue)
-inline DagPlan dag_lnlike_plan_sky(int B, int P, const int* first, int n_cus, int dag_grid, int* workers)
+// (sky_split: the skyline-aware rules -- the handle's PSOAP_SKY_SPLIT, read at its creation)
+inline DagPlan dag_lnlike_plan_sky(int B, int P, const int* first, int n_cus, int dag_grid, int* workers, bool sky_split)
 {
     const std::vector<int> Ps((size_t)B, P);
     *workers = dag_batch_workers(Ps, 0, n_cus, dag_grid);
-    return dag_build_tasks(Ps, *workers, 0, 0, 0, 0, first);
+    return dag_build_tasks(Ps, *workers, 0, 0, 0, 0, first, sky_split);
 }
 
 // what a list executes: tiles (finals), tile-GEMM units (128-row panels of the updates), MFMA flops (updates + strip solves)

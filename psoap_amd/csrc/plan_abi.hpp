@@ -52,7 +52,8 @@ extern "C" int psoap_dag_plan_sky(int B, int P, const int* first, int workers, v
             FAIL("psoap_dag_plan_sky: first must be non-decreasing with 0 <= first[j] <= max(j - 1, 0)");
         any = any || first[j] > 0;
     }
-    DagPlan plan = any ? dag_build_tasks(std::vector<int>((size_t)B, P), workers, 0, 0, 0, 0, first) : dag_build_tasks(B, P, workers);
+    DagPlan plan = any ? dag_build_tasks(std::vector<int>((size_t)B, P), workers, 0, 0, 0, 0, first, dag_sky_split_env())
+                       : dag_build_tasks(B, P, workers);
     plan_export(plan, out, max_tasks, n_tasks, n_slots, n_ctrs, queue_first);
     return 0;
 }

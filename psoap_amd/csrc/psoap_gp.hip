@@ -184,6 +184,7 @@ struct psoap_chunk {
     std::vector<int> plan_first;      // the skyline of the list in `dag` (empty: dense)
     DagPlanWork plan_work;            // what that list executes (a skyline list only)
     bool sky_fine = true;             // PSOAP_SKY_FINE=0, read at create: k_sky_fine is not queued, the clip starts at whole panels
+    bool sky_split = true;            // PSOAP_SKY_SPLIT=0, read at create: the dense split and order rules inside the skyline (dag_plan.hpp)
     long long clip_units = -1;        // units of that list the current evaluation executes under the clip (DagMat::first); -1: no clip
     long long clip_stages = -1;       // 16-row stages of those units the updates run from each matrix's own first row group on
     struct SkyPlan {
@@ -396,6 +397,7 @@ static int chunk_alloc(psoap_chunk* h, const double* fl, const double* sigma)
         h->sky_clip = !(e && e[0] == '0');
         e = getenv("PSOAP_SKY_FINE");
         h->sky_fine = !(e && e[0] == '0');
+        h->sky_split = dag_sky_split_env();
     }
     const size_t n_cand = h->sky_order ? SKY_MAX_CAND : 1;
     for (BatchSlot& sl : h->slot) {
@@ -1037,7 +1039,7 @@ static int dag_prepare(psoap_chunk* h)
             psoap_chunk::SkyPlan e;
             e.B = B;
             e.first = first;
-            e.plan = dag_lnlike_plan_sky(B, P, first.data(), h->n_cus, h->dag_grid, &e.workers);
+            e.plan = dag_lnlike_plan_sky(B, P, first.data(), h->n_cus, h->dag_grid, &e.workers, h->sky_split);
             e.work = dag_plan_work(e.plan);
             HIP_TRY(e.dTasks.need(e.plan.tasks.size()));
             HIP_TRY(hipMemcpy(e.dTasks, e.plan.tasks.data(), sizeof(DagTask) * e.plan.tasks.size(), hipMemcpyHostToDevice));
