@@ -548,6 +548,37 @@ int psoap_chunk_predict_marg_var(psoap_chunk *h, int mode, int c, int M, const d
                                  const double *lwl_pred, const double *mu_c, const double *gp,
                                  double *mu_out, double *var_out, int *status_out);
 
+/* ---- component spectra under the time-variable kernel: the spectrum at a date ----------------------
+ * psoap_chunk_predict_tv and psoap_chunk_predict_tv_var are psoap_chunk_predict and psoap_chunk_predict_var under the
+ * kernel of psoap_chunk_lnlike_tv_grad, K_ij = sum_c a_c^2 exp(p_c d_cij^2 + q_c dt_ij^2) + sigma_i^2 delta_ij with
+ * q_c = -1/2 / tau_c^2 over the times of psoap_chunk_set_times.  A prediction point is a pair: ln-wavelength
+ * lwl_pred[k][m] and date t_pred[m] -- t_pred (M) is shared by the components, in days, with the constant removed that
+ * was removed from the handle's times.  With tau (c):
+ *   cross-covariance of component k with pixel i:  a_k^2 exp(p_k (lwl_pred[k][m] - lwl[k][i])^2 + q_k (t_pred[m] - t[i])^2)
+ *   prior covariance of points m and n:            a_k^2 exp(p_k d^2 + q_k (t_pred[n] - t_pred[m])^2)
+ * (the diagonal: a_k^2, with the nugget where the static mode has one); modes, offsets, m0, the block layout and the
+ * NULL rule of Sigma_out are psoap_predict's.  Several dates in one call are several runs of t_pred (with lwl_pred
+ * repeated): Sigma then holds the covariance between the dates as well.
+ * Mode 0 with c = 2 or 3, mode 1 with c = 2, mode 2 with c = 1; refused with a message: mode 1 with c = 3, a call before
+ * psoap_chunk_set_times, an open stream, a handle with a baseline (that combination is not built), a tau_c that is <= 0 or
+ * NaN (+inf is valid: that component is static) and a t_pred that is not finite.
+ * status_out: 0 ok; 1 K is not positive definite -- every output is then NaN and the call itself returns 0.
+ * The factorisation is always the staged sweep (the persistent launch evaluates the static covariance): with every
+ * tau_c = +inf the outputs have the bits of psoap_chunk_predict / _var on that route (PSOAP_SHARE_POLICY=staged).  A
+ * component with finite tau_c whose every q_c (t_pred[m] - t[i])^2 is <= -746 gets its prior back exactly: m0, its block
+ * of A, variances a_c^2.  No atomics: every sum runs in an order fixed by (N, c, M, mode).
+ * With Sigma_out the handle keeps mean and Sigma for psoap_chunk_predict_draw, as after psoap_chunk_predict.
+ * Workspace: the handle's predict workspace (psoap_chunk_predict_release); psoap_chunk_predict_timings and, with
+ * profiling on, psoap_chunk_get_timings report the call (flops: those of the plain call). */
+int psoap_chunk_predict_tv(psoap_chunk *h, int mode, int c, int M, const double *lwl,
+                           const double *lwl_pred, const double *t_pred, const double *mu_c,
+                           const double *gp, const double *tau,
+                           double *mu_out, double *Sigma_out /* may be NULL */, int *status_out);
+int psoap_chunk_predict_tv_var(psoap_chunk *h, int mode, int c, int M, const double *lwl,
+                               const double *lwl_pred, const double *t_pred, const double *mu_c,
+                               const double *gp, const double *tau,
+                               double *mu_out, double *var_out, int *status_out);
+
 /* Split-phase form of psoap_lnlike_batch: upload (H2D, async, on a copy stream of
  * its own), eval (kernels only, async), fetch (sync + D2H of B doubles).
  * A handle holds TWO proposal batches: an upload always goes to the one that is

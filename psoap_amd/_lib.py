@@ -103,6 +103,10 @@ SIGNATURES = {
                                                 _ip]),
     "psoap_chunk_predict_marg_var": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp, _dp,
                                                     _dp, _ip]),
+    "psoap_chunk_predict_tv": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
+                                              _dp, _ip]),
+    "psoap_chunk_predict_tv_var": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp, _dp, _dp,
+                                                  _dp, _dp, _ip]),
     "psoap_chunk_predict_release": (ctypes.c_int, [_vp]),
     "psoap_chunk_predict_draw": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_ulonglong, _dp, ctypes.c_double, _dp, _ip]),
     "psoap_draw_normals": (ctypes.c_int, [ctypes.c_int, ctypes.c_ulonglong, ctypes.c_int, ctypes.c_int, _dp]),

@@ -623,6 +623,46 @@ class ChunkHandle:
         is not positive definite (or the Gram matrix does not factor); ``PsoapError`` without a baseline."""
         return self._predict("psoap_chunk_predict_marg", mode, lwls, lwls_predict, mu_c, gp, want_sigma)
 
+    def predict_tv(self, mode: int, lwls, lwls_predict, t_predict, mu_c, gp, tau, want_sigma=True):
+        """``predict`` under the time-variable kernel of ``lnlike_tv`` (include/psoap_gp.h: psoap_chunk_predict_tv; needs
+        ``set_times``): the component spectra at chosen dates.  A prediction point is ``(lwls_predict[k][m], t_predict[m])``:
+        ``t_predict`` (M,) in days is shared by the components and has the constant removed that ``set_times``' times have;
+        several dates are several runs of it (with the grid repeated), and ``Sigma`` then holds the covariance between the
+        dates.  ``tau`` (c,); ``inf`` keeps a component static, and with every ``tau = inf`` the result has the bits of
+        ``predict`` on the staged route.  Return forms as ``predict``; ``predict_draw`` works after a call that returned
+        ``Sigma``.  Mode 0 with two or three components, mode 1 with two, mode 2 with one.  ``LinAlgError`` when ``K`` is not
+        positive definite; ``PsoapError`` without times, with a baseline or an open stream, for a ``tau`` that is no time
+        scale or a ``t_predict`` that is not finite."""
+        lwls = as_f64(np.atleast_2d(lwls))
+        pred = as_f64(np.atleast_2d(lwls_predict))
+        c = lwls.shape[0]
+        lwls = as_f64(lwls, (c, self.N))
+        M = pred.shape[1]
+        pred = as_f64(pred, (c, M))
+        t_pred = as_f64(np.atleast_1d(as_f64(t_predict)), (M,))
+        mu_c = as_f64(mu_c)
+        gp = as_f64(gp, (2 * c,))
+        tau = as_f64(np.atleast_1d(as_f64(tau)), (c,))
+        R = c * M if mode == 0 else M
+        mu = np.empty(R)
+        status = ctypes.c_int(0)
+        self._sigma_rows = 0
+        if isinstance(want_sigma, str):
+            if want_sigma != "diag":
+                raise ValueError('want_sigma must be True, False or "diag"')
+            second = np.empty(R)
+            entry = "psoap_chunk_predict_tv_var"
+        else:
+            second = np.empty((R, R)) if want_sigma else None
+            entry = "psoap_chunk_predict_tv"
+        check(getattr(self._L, entry)(self._h, int(mode), c, M, dptr(lwls), dptr(pred), dptr(t_pred), dptr(mu_c), dptr(gp), dptr(tau),
+                                      dptr(mu), None if second is None else dptr(second), ctypes.byref(status)), entry)
+        if status.value != 0:
+            raise np.linalg.LinAlgError("data covariance matrix is not positive definite")
+        if second is not None and second.ndim == 2:
+            self._sigma_rows = R
+        return mu if second is None else (mu, second)
+
     def predict_draw(self, n_draws: int, seed=None, z=None, nugget: float = 1e-8) -> np.ndarray:
         """``n_draws`` spectra from the posterior of the last ``predict`` / ``predict_marg`` call of this handle that returned
         ``Sigma`` (include/psoap_gp.h: psoap_chunk_predict_draw) -> ``(n_draws, R)``, ``R`` that call's rows:

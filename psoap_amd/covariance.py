@@ -474,7 +474,7 @@ def predict_marginal(lwls, fl, sigma, lwls_predict, mus, gp, x, epoch_index, ord
 
 
 def predict_draws(lwls, fl, sigma, lwls_predict, mus, gp, n_draws, seed, mode=0, nugget=1e-8, baseline=None,
-                  want_sigma=True):
+                  want_sigma=True, timevar=None):
     """Not one function of the reference but the end of its reconstruction scripts (scripts/psoap_retrieve_SB2_draw.py,
     psoap_retrieve_ST3_draw.py, psoap_predict_*.py --draws: ``np.random.multivariate_normal(mu, Sigma, size=n_draws)``):
     the posterior of the component spectra and ``n_draws`` spectra drawn from it on the device, without an SVD of the
@@ -483,14 +483,23 @@ def predict_draws(lwls, fl, sigma, lwls_predict, mus, gp, n_draws, seed, mode=0,
     ``lwls`` (c, N), ``lwls_predict`` (c, M), ``mus`` (c,) -- one value for modes 1 and 2 --, ``gp`` (2c,); ``mode`` as
     ``ChunkHandle.predict``.  ``baseline``: a dictionary ``x``, ``epoch_index``, ``order``, ``prior_sd`` and optionally
     ``weight`` -- the arguments of ``predict_marginal``, whose posterior is then the one drawn from.  ``want_sigma=False``
-    forms ``Sigma`` on the device all the same (the draws need it) and spares the download's copy to the caller."""
+    forms ``Sigma`` on the device all the same (the draws need it) and spares the download's copy to the caller.
+    ``timevar``: a dictionary ``times``, ``tau``, ``t_predict`` -- the arguments of ``predict_timevar``, whose posterior is
+    then the one drawn from: spectra at the dates ``t_predict`` (not together with ``baseline``)."""
     lw = np.stack([as_f64(w) for w in np.atleast_2d(lwls)])
     pred = np.stack([as_f64(w) for w in np.atleast_2d(lwls_predict)])
     fl, sigma = as_f64(fl), as_f64(sigma)      # (once: the cache below is keyed on the buffers, and predict_marginal asks it again)
     h = _chunk_for(fl, sigma)
     if not hasattr(h, "predict_draw"):
         raise _lib.PsoapError("predict_draws needs the device in this process (PSOAP_GPU_SERVER serves values only)")
-    if baseline is None:
+    if timevar is not None:
+        if baseline is not None:
+            raise ValueError("predict_draws takes a baseline or timevar, not both (the combination is not built)")
+        if set(timevar) != {"times", "tau", "t_predict"}:
+            raise ValueError(f"timevar needs 'times', 'tau' and 't_predict'; got {sorted(timevar)}")
+        mu, Sigma = predict_timevar(lw, fl, sigma, pred, timevar["t_predict"], mus, gp, timevar["tau"], timevar["times"], mode=mode,
+                                    want_sigma=True)
+    elif baseline is None:
         mu, Sigma = h.predict(int(mode), lw, pred, np.atleast_1d(mus), as_f64(gp), True)
     else:
         unknown = set(baseline) - {"x", "epoch_index", "order", "prior_sd", "weight"}
@@ -719,6 +728,39 @@ def lnlike_timevar_grad(lwls, fl, sigma, gp, tau, times, mu_GP=1.0):
     """``(lnp, grad_gp (2c,), grad_tau (c,), grad_lwl (c, N), grad_mu)``: ``lnlike_timevar`` and its analytic derivatives on the
     device (``ChunkHandle.lnlike_tv_grad``).  ``grad_tau`` is exactly 0 where ``tau = inf``."""
     return _timevar(lwls, fl, sigma, gp, tau, times, mu_GP, True)
+
+
+def _timevar_handle(fl, sigma, times, N, who):
+    """the cached handle of ``(fl, sigma)`` with ``times - min(times)`` on it, as ``lnlike_timevar`` leaves it -> (h, min(times))"""
+    t = as_f64(times, (N,))
+    if not np.all(np.isfinite(t)):
+        raise ValueError(_NONFINITE)
+    h = _chunk_for(fl, sigma)
+    if not hasattr(h, "predict_tv"):
+        raise _lib.PsoapError(f"{who} needs the device in this process (PSOAP_GPU_SERVER serves the static likelihood only)")
+    t0 = t.min()
+    t = t - t0
+    if getattr(h, "_tv_times", None) is None or not np.array_equal(h._tv_times, t):
+        h.set_times(t)
+        h._tv_times = t
+    return h, t0
+
+
+def predict_timevar(lwls, fl, sigma, lwls_predict, t_predict, mus, gp, tau, times, mode=0, want_sigma=True):
+    """The component spectra of one chunk at chosen dates under the time-variable kernel of ``lnlike_timevar``
+    (``ChunkHandle.predict_tv``): ``predict_f`` / ``predict_f_g`` / ``predict_f_g_h`` (``mode`` 2 with one row of ``lwls``, else
+    0) or ``predict_f_g_sum`` (``mode`` 1) with the temporal factor in the data covariance, the cross-covariance and the prior.
+    ``lwls`` (c, N), ``times`` (N,) the pixels' observation times; ``lwls_predict`` (c, M) with ``t_predict`` (M,), the date of
+    every prediction point in the unit and from the origin of ``times`` (the minimum of ``times`` is taken off both before they
+    go to the device) -- several dates are several runs, the grid repeated, and ``Sigma`` then holds the covariance between the
+    dates; ``mus`` (c,) -- one value for modes 1 and 2 --, ``gp`` (2c,), ``tau`` (c,) with ``inf`` for a static component.
+    ``want_sigma``: True -> ``(mu, Sigma)``, ``"diag"`` -> ``(mu, diag(Sigma))``, False -> ``mu``.  ``LinAlgError`` where the
+    plain predict raises it; a ``tau <= 0`` or NaN and a ``t_predict`` that is not finite are refused (``PsoapError``)."""
+    lw = np.stack([as_f64(w) for w in np.atleast_2d(lwls)])
+    pred = np.stack([as_f64(w) for w in np.atleast_2d(lwls_predict)])
+    h, t0 = _timevar_handle(fl, sigma, times, lw.shape[1], "predict_timevar")
+    t_pred = as_f64(np.atleast_1d(as_f64(t_predict)), (pred.shape[1],)) - t0
+    return h.predict_tv(int(mode), lw, pred, t_pred, np.atleast_1d(mus), as_f64(gp), tau, want_sigma)
 
 
 def optimize_GP_timevar(lwls, fl, sigma, gp0, tau0, times, free_tau=None, mu_GP=1.0, ftol=1e-10, full_output=False):

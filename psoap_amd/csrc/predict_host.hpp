@@ -35,6 +35,7 @@ struct PredictWs {
     Stream stream;
     Event ev[5];                  // (timed)
     Grow<double> Var, Prior, Rowx, Diag;
+    Grow<double> Tpred, Tau;      // the prediction dates (M) and the components' time scales (predict_tv_run)
     PredictTimes times;
 };
 
@@ -193,6 +194,54 @@ static void predict_fill_prior(PredictWs& ws, const PredictShape& g, hipStream_t
     } else {
         if (Rq_pad != g.Rq) hipLaunchKernelGGL(k_zero, dim3(1024), dim3(256), 0, s, dS, (size_t)Rq_pad * Rq_pad);
         launch_region_c(s, c, dS, (size_t)Rq_pad, 0, M, M, dPred, (size_t)M, dPred, (size_t)M, gp_host(gp, 0, c), 1, nugget);
+    }
+}
+
+// predict_fill under the time-variable kernel, launch for launch: K by k_fill_sym_tv over the handle's times dT with ws.Tau,
+// the blocks of Cx^T by k_fill_region_tv -- rows at the pixels' times, columns at the prediction dates ws.Tpred (M, shared by
+// the components)
+static void predict_fill_tv(PredictWs& ws, const PredictShape& g, hipStream_t s, size_t ld, const double* gp, const double* tau,
+                            const double* dT, const double* dSig)
+{
+    const int c = g.c, N = g.N, M = g.M;
+    double *dK = ws.K, *dLwl = ws.Lwl, *dPred = ws.Pred;
+    const double* dTp = ws.Tpred;
+    TauHost th;
+    hipLaunchKernelGGL(k_zero, dim3(2048), dim3(256), 0, s, dK, (size_t)g.Npad * ld);
+    with_components(c, [&](auto nc) {
+        hipLaunchKernelGGL(k_fill_sym_tv<nc()>, dim3(g.P * (g.P + 1) / 2, 1), dim3(256), 0, s, dK, (size_t)0, (int)ld, N, g.P,
+                           (const double*)dLwl, dT, (const double*)ws.Gp.p, (const double*)ws.Tau.p, dSig, 1);
+    });
+    if (g.mode == 0) {
+        for (int k = 0; k < c; ++k) {
+            predict_tv_taus(tau, k, 1, th.v);
+            launch_region_tv_c(s, 1, dK, ld, g.Npad + k * M, N, M, dLwl + (size_t)k * N, 0, dPred + (size_t)k * M, 0, dT, dTp,
+                               gp_host(gp, k, 1), th, 0, 0.0);
+        }
+    } else {
+        predict_tv_taus(tau, 0, c, th.v);
+        launch_region_tv_c(s, c, dK, ld, g.Npad, N, M, dLwl, (size_t)N, dPred, (size_t)M, dT, dTp, gp_host(gp, 0, c), th, 0, 0.0);
+    }
+}
+
+// predict_fill_prior under the time-variable kernel: rows and columns both at the prediction dates
+static void predict_fill_prior_tv(PredictWs& ws, const PredictShape& g, hipStream_t s, const double* gp, const double* tau, double nugget)
+{
+    const int c = g.c, M = g.M, Rq_pad = g.Rq_pad;
+    double *dS = ws.S, *dPred = ws.Pred;
+    const double* dTp = ws.Tpred;
+    TauHost th;
+    if (g.mode == 0) {
+        hipLaunchKernelGGL(k_zero, dim3(1024), dim3(256), 0, s, dS, (size_t)Rq_pad * Rq_pad);
+        for (int k = 0; k < c; ++k) {
+            predict_tv_taus(tau, k, 1, th.v);
+            launch_region_tv_c(s, 1, dS + (size_t)k * M * Rq_pad, (size_t)Rq_pad, k * M, M, M, dPred + (size_t)k * M, 0,
+                               dPred + (size_t)k * M, 0, dTp, dTp, gp_host(gp, k, 1), th, 1, 0.0);
+        }
+    } else {
+        if (Rq_pad != g.Rq) hipLaunchKernelGGL(k_zero, dim3(1024), dim3(256), 0, s, dS, (size_t)Rq_pad * Rq_pad);
+        predict_tv_taus(tau, 0, c, th.v);
+        launch_region_tv_c(s, c, dS, (size_t)Rq_pad, 0, M, M, dPred, (size_t)M, dPred, (size_t)M, dTp, dTp, gp_host(gp, 0, c), th, 1, nugget);
     }
 }
 
@@ -464,5 +513,106 @@ static int predict_run(PredictWs& ws, int mode, int c, int N, int M, const doubl
     memcpy(mu_out, h_mu, sizeof(double) * Rq);
     if (var_out) memcpy(var_out, h_var, sizeof(double) * Rq);
     predict_times(ws, t_begin, t_ev0, predict_flops(Npad, Rq_pad, want_S, var_out != nullptr));
+    return 0;
+}
+
+// ---- the call under the time-variable kernel ---------------------------------------------------------------------------------
+// psoap_chunk_predict_tv / _var: the staged route of predict_run with the time-variable fills, on the handle's first stream
+// and booked like the other analysis paths (marg_predict_run's shape without its Gram half).  The launches behind the fill
+// are predict_factor_staged's and predict_run's, kernel for kernel and grid for grid: with every tau = +inf the outputs have
+// the bits of the plain call on the staged route.  The persistent launch evaluates the static covariance in its epilogue and
+// is not used.  (The caller has run predict_tv_check.)
+static int predict_tv_run(psoap_chunk* h, int mode, int c, int M, const double* lwl, const double* lwl_pred, const double* t_pred,
+                          const double* mu_c, const double* gp, const double* tau, double* mu_out, double* Sigma_out, double* var_out,
+                          int* status_out)
+{
+    const auto t_begin = std::chrono::steady_clock::now();
+    SigmaPin pin;         // declared first, as in predict_run: its destructor drops the registration on every return path
+    h->sigma.valid = false;
+    DEVICE_SCOPE(h->device);
+    if (int rc = enter_device(h->device)) return rc;
+    PredictWs& ws = predict_ws_of(h);
+    PredictShape g;
+    if (const char* why = predict_shape(mode, c, h->N, M, mu_c[0], g)) FAIL(why);
+    const int N = h->N, Npad = g.Npad, P = g.P, Mt = g.Mt, Rq = g.Rq, Rq_pad = g.Rq_pad, nslab = g.nslab, ld = (int)g.ld;
+    const PredictStaging hs = predict_staging(Rq_pad, sizeof(MatAcc), 0);
+    if (int rc = predict_stream(ws)) return rc;
+    if (Sigma_out) pin.start(Sigma_out, sizeof(double) * (size_t)Rq * Rq, h->device);
+    hipStream_t s = h->streams[0];
+    if (int rc = predict_need(ws, g, g.ld, hs.total)) return rc;
+    HIP_TRY(ws.Tpred.need(M));
+    HIP_TRY(ws.Tau.need(3));
+    double *h_mu = ws.hSmall.p + hs.mu, *h_var = ws.hSmall.p + hs.var;
+    MatAcc* h_acc = reinterpret_cast<MatAcc*>(ws.hSmall.p + hs.acc);
+    double* dK = ws.K;
+    const double* W = dK + Npad;
+    h->recs.clear();
+    const auto t_ev0 = std::chrono::steady_clock::now();
+    HIP_TRY(hipEventRecord(ws.ev[0], s));
+    if (int rc = predict_upload(ws, g, s, lwl, lwl_pred, gp, mu_c, nullptr, nullptr, ws.hSmall.p + hs.m0)) return rc;
+    HIP_TRY(hipMemcpyAsync(ws.Tpred, t_pred, sizeof(double) * M, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(ws.Tau, tau, sizeof(double) * c, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(ws.ev[1], s));
+    if (int rc = prof_launch(h, s, PSOAP_K_FILL, 0.0, 8.0 * Npad * (double)g.ld,
+                             [&] { predict_fill_tv(ws, g, s, g.ld, gp, tau, h->dTimes.p, h->dSigma.p); })) return rc;
+    if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
+            hipLaunchKernelGGL(k_init_rhs, dim3((Npad + 255) / 256, 1), dim3(256), 0, s, ws.R.p, Npad, N, h->dFl.p, g.offset, ws.Acc.p);
+        })) return rc;
+    for (int p = 0; p < P; ++p) {      // (staged_augmented's rows, booked)
+        const int k0 = p * NB, ntile = P - p + Mt;
+        const auto update = plain_update(s, dK, ld, k0, ntile);
+        const StagedRow row{dK, 0, ld, ws.R.p, Npad, ws.Acc.p, ws.W.p, (size_t)NB * NB, ntile - 1};
+        if (int rc = staged_row(h, s, row, 1, k0, p > 0 ? &update : nullptr, TILE_FLOPS * p * ntile)) return rc;
+    }
+    HIP_TRY(hipEventRecord(ws.ev[2], s));
+    // mean: m0 + W^T z; the records' total
+    if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
+            hipLaunchKernelGGL(k_gemv_t_partial, dim3((Rq + 127) / 128, nslab), dim3(256), 0, s, W, g.ld, Npad, Rq, (const double*)ws.R.p,
+                               ws.Part.p);
+            hipLaunchKernelGGL(k_gemv_finish, dim3((Rq + 255) / 256), dim3(256), 0, s, (const double*)ws.Part.p, nslab, Rq,
+                               (const double*)ws.M0.p, ws.Mu.p);
+            hipLaunchKernelGGL(k_acc_total, dim3(1), dim3(1), 0, s, (const MatAcc*)ws.Acc.p, P, ws.Acc.p + ACC_ROWS);
+        })) return rc;
+    HIP_TRY(hipMemcpyAsync(h_mu, ws.Mu, sizeof(double) * Rq, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(h_acc, ws.Acc.p + ACC_ROWS, sizeof(MatAcc), hipMemcpyDeviceToHost, s));
+    bool sigma_direct = false;
+    if (Sigma_out) {
+        const int St = Rq_pad / NB;
+        HIP_TRY(ws.S.need((size_t)Rq_pad * Rq_pad));
+        // Sigma = A - W^T W over the prior at the prediction dates: every upper tile in one launch, as predict_run
+        if (int rc = prof_launch(h, s, PSOAP_K_GRAD, TILE_FLOPS * (St * (St + 1) / 2) * P, 0.0, [&] {
+                predict_fill_prior_tv(ws, g, s, gp, tau, (mode == 1) ? 1e-8 : 0.0);
+                hipLaunchKernelGGL(k_syrk_sub_sym, dim3(St * (St + 1) / 2), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, W, g.ld, Npad, ws.S.p,
+                                   (size_t)Rq_pad, St, 0);
+            })) return rc;
+        HIP_TRY(hipEventRecord(ws.ev[3], s));
+        if (int rc = predict_sigma_direct(pin, ws, g, s, Sigma_out, &sigma_direct)) return rc;
+    }
+    if (var_out) {
+        // (the prior variances are the static ones: dt = 0 on the diagonal)
+        if (int rc = predict_upload_prior(ws, g, s, gp, ws.hSmall.p + hs.prior)) return rc;
+        if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
+                hipLaunchKernelGGL(k_colnorm_partial, dim3((Rq + 127) / 128, nslab), dim3(256), 0, s, W, g.ld, Npad, Rq, ws.Part.p);
+                hipLaunchKernelGGL(k_var_finish, dim3((Rq + 255) / 256), dim3(256), 0, s, (const double*)ws.Part.p, nslab, Rq,
+                                   (const double*)ws.Prior.p, ws.Var.p);
+            })) return rc;
+        HIP_TRY(hipMemcpyAsync(h_var, ws.Var, sizeof(double) * Rq, hipMemcpyDeviceToHost, s));
+    }
+    if (!Sigma_out) HIP_TRY(hipEventRecord(ws.ev[3], s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (Sigma_out && !sigma_direct)
+        if (int rc = predict_sigma_staged(ws, g, Sigma_out)) return rc;
+    pin.release();
+    if (collect_timings(h)) return 1;
+    // K not positive definite: status 1 and NaN in every output (the marginal call's convention)
+    const bool bad = h_acc->info != 0.0;
+    if (status_out) *status_out = bad ? 1 : 0;
+    for (int q = 0; q < Rq; ++q) mu_out[q] = bad ? NAN : h_mu[q];
+    if (var_out)
+        for (int q = 0; q < Rq; ++q) var_out[q] = bad ? NAN : h_var[q];
+    if (Sigma_out && bad)
+        for (size_t k = 0; k < (size_t)Rq * Rq; ++k) Sigma_out[k] = NAN;
+    if (Sigma_out && !bad) h->sigma = psoap_chunk::SigmaRecord{true, Rq, mode};
+    predict_times(ws, t_begin, t_ev0, predict_tv_flops(Npad, Rq_pad, Sigma_out != nullptr, var_out != nullptr));
     return 0;
 }

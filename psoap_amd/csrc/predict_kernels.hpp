@@ -74,6 +74,78 @@ __global__ __launch_bounds__(256) void k_fill_region(double* __restrict__ out, s
     }
 }
 
+// the time scales of the components a region launch evaluates, as GpHost carries their hyper-parameters
+struct TauHost {
+    double v[3];
+};
+
+// k_fill_region under the time-variable kernel (fill_kernels.hpp, `TV`): trow (nrows) and tcol (ncols) are the times of
+// the rows and the columns in days -- ONE vector each, shared by the components --, tauh the components' time scales:
+//   out[i][col0 + j] = sum_{c<C} a_c^2 exp(p_c (xcol_c[j] - xrow_c[i])^2 + q_c (tcol[j] - trow[i])^2),   q_c = tv_q2(tau_c)
+// The argument is formed as every time-variable kernel forms it -- a = p * d * d, then a = a + q * dt * dt, no contraction,
+// one exp -- so with tau_c = +inf (q = -0) the bits are k_fill_region's.  The sym_diag / nugget branch is k_fill_region's
+// (dt = 0 there).  The tiling and the element-wise stores are k_fill_region's too: a body shared with the static fill
+// changed that fill's instructions and the predict family is pinned bit for bit, so the two kernels stand
+// side by side as k_fill_sym_tv and k_fill_sym do -- a change to the region's shape is made in BOTH.
+template <int C>
+__global__ __launch_bounds__(256) void k_fill_region_tv(double* __restrict__ out, size_t ld, int col0, int nrows, int ncols,
+                                                        const double* __restrict__ xrow, size_t xrow_stride,
+                                                        const double* __restrict__ xcol, size_t xcol_stride,
+                                                        const double* __restrict__ trow, const double* __restrict__ tcol,
+                                                        GpHost gph, TauHost tauh, int sym_diag, double nugget)
+{
+    __shared__ double xr[C][NB];
+    __shared__ double tr[NB];
+    const int tid = threadIdx.x;
+    const int i0 = blockIdx.y * NB, j0 = blockIdx.x * NB;
+    GpDev g;
+    load_gp(gph.v, C, g);
+    double q2[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) q2[c] = tv_q2(tauh.v[c]);
+    double dsum = g.a2[0];
+    {
+#pragma clang fp contract(off)
+        for (int c = 1; c < C; ++c) dsum = dsum + g.a2[c];
+    }
+    if (tid < NB) {
+#pragma unroll
+        for (int c = 0; c < C; ++c) xr[c][tid] = (i0 + tid < nrows) ? xrow[c * xrow_stride + i0 + tid] : 0.0;
+        tr[tid] = (i0 + tid < nrows) ? trow[i0 + tid] : 0.0;
+    }
+    const int col = tid & 127, half = tid >> 7;
+    const int j = j0 + col;
+    double xj[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) xj[c] = (j < ncols) ? xcol[c * xcol_stride + j] : 0.0;
+    const double tj = (j < ncols) ? tcol[j] : 0.0;
+    __syncthreads();
+    if (j >= ncols) return;
+    for (int it = 0; it < NB / 2; ++it) {
+        const int r = half + 2 * it;
+        const int i = i0 + r;
+        if (i >= nrows) break;
+        const double dt = tj - tr[r];
+        double v = 0.0;
+        {
+#pragma clang fp contract(off)
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                const double d = xj[c] - xr[c][r];
+                double a = g.p2[c] * d * d;
+                a = a + q2[c] * dt * dt;
+                const double t = g.a2[c] * exp(a);
+                v = (c == 0) ? t : v + t;
+            }
+        }
+        if (sym_diag && i == j) {
+#pragma clang fp contract(off)
+            v = dsum + nugget;
+        }
+        out[(size_t)i * ld + col0 + j] = v;
+    }
+}
+
 // S tile (ti, tj) -= sum_k W[k][128 ti + .] W[k][128 tj + .]   (all tiles; calibration's pass 1 / 2)
 __global__ __launch_bounds__(GEMM_THREADS, 2) void k_syrk_sub(const double* __restrict__ W, size_t ldw, int K,
                                                              double* __restrict__ S, size_t lds)
@@ -220,6 +292,18 @@ static void launch_region_c(hipStream_t st, int C, double* out, size_t ld, int c
                             double nug)
 {
     with_components(C, [&](auto nc) { launch_region<nc()>(st, out, ld, col0, nrows, ncols, xrow, xrs, xcol, xcs, g, sym, nug); });
+}
+
+// launch_region_c for k_fill_region_tv: the same grid
+static void launch_region_tv_c(hipStream_t st, int C, double* out, size_t ld, int col0, int nrows, int ncols, const double* xrow,
+                               size_t xrs, const double* xcol, size_t xcs, const double* trow, const double* tcol, const GpHost& g,
+                               const TauHost& tau, int sym, double nug)
+{
+    dim3 grid((ncols + NB - 1) / NB, (nrows + NB - 1) / NB);
+    with_components(C, [&](auto nc) {
+        hipLaunchKernelGGL(k_fill_region_tv<nc()>, grid, dim3(256), 0, st, out, ld, col0, nrows, ncols, xrow, xrs, xcol, xcs, trow,
+                           tcol, g, tau, sym, nug);
+    });
 }
 
 }  // namespace psoap

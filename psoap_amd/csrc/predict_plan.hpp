@@ -128,4 +128,39 @@ inline double predict_flops(double n, double r, bool sigma, bool var)
     return n * n * n / 3.0 + n * n * r + (sigma ? n * r * r : (var ? 2.0 * n * r : 0.0)) + 2.0 * n * r;
 }
 
+// ---- predict under the time-variable kernel (psoap_chunk_predict_tv; predict_tv_run) ------------------------------------------
+// -> nullptr, or why the call is refused, without a device: the modes built (the transposed mean of the sum of three is not,
+// as under the baseline), the handle's state -- times set, no open stream, no baseline --, tau (c; +inf is the static model)
+// and t_pred (M).  The caller puts the entry's name in front.
+inline const char* predict_tv_check(int mode, int c, int M, bool arrays, bool have_times, bool open_stream, bool have_baseline,
+                                    const double* tau, const double* t_pred)
+{
+    if (mode < 0 || mode > 2 || c < 1 || c > 3 || M < 1 || !arrays || !tau || !t_pred) return "bad arguments";
+    if (mode == 2 && c != 1) return "mode 2 (predict_f) needs c == 1";
+    if (mode == 1 && c == 3)
+        return "mode 1 with three components is not provided (the transposed mean of predict_f_g_h_sum, covariance.py:294)";
+    if (mode == 1 && c != 2) return "mode 1 (the sum) needs c == 2";
+    if (mode == 0 && c < 2) return "mode 0 (the components) needs c == 2 or 3";
+    if (!have_times) return "call psoap_chunk_set_times first";
+    if (open_stream) return "the handle has an open stream (psoap_stream_close first)";
+    if (have_baseline)
+        return "the handle has a baseline (psoap_chunk_set_baseline): the time-variable kernel under the marginalised continuum "
+               "is not built yet";
+    for (int k = 0; k < c; ++k)
+        if (!(tau[k] > 0.0)) return "every tau must be a time scale: positive, +inf for a static component";
+    for (int m = 0; m < M; ++m)
+        if (!(t_pred[m] - t_pred[m] == 0.0)) return "t_pred must be finite";
+    return nullptr;
+}
+
+// the temporal factor adds one multiply-add per filled element and nothing to the sweep: the count is the plain call's
+inline double predict_tv_flops(double n, double r, bool sigma, bool var) { return predict_flops(n, r, sigma, var); }
+
+// the time scales of components k0 .. k0 + n - 1 for a region launch (TauHost::v), the rest +inf -- static, like the zero
+// amplitudes gp_host leaves there
+inline void predict_tv_taus(const double* tau, int k0, int n, double out[3])
+{
+    for (int k = 0; k < 3; ++k) out[k] = (k < n) ? tau[k0 + k] : __builtin_inf();
+}
+
 }  // namespace psoap

@@ -2751,6 +2751,35 @@ extern "C" int psoap_chunk_predict_marg_var(psoap_chunk* h, int mode, int c, int
                             status_out);
 }
 
+// ---- predict under the time-variable kernel (k_fill_region_tv, predict_kernels.hpp): predict_tv_run -------------------
+static int chunk_predict_tv(psoap_chunk* h, const char* who, int mode, int c, int M, const double* lwl, const double* lwl_pred,
+                            const double* t_pred, const double* mu_c, const double* gp, const double* tau, double* mu_out,
+                            double* Sigma_out, double* var_out, int* status_out)
+{
+    if (!h) FAIL(std::string(who) + ": bad arguments");
+    if (const char* why = predict_tv_check(mode, c, M, lwl && lwl_pred && mu_c && gp && mu_out, h->dTimes.p != nullptr, h->stream.open,
+                                           h->marg.valid, tau, t_pred))
+        FAIL(std::string(who) + ": " + why);
+    return predict_tv_run(h, mode, c, M, lwl, lwl_pred, t_pred, mu_c, gp, tau, mu_out, Sigma_out, var_out, status_out);
+}
+
+extern "C" int psoap_chunk_predict_tv(psoap_chunk* h, int mode, int c, int M, const double* lwl, const double* lwl_pred,
+                                      const double* t_pred, const double* mu_c, const double* gp, const double* tau,
+                                      double* mu_out, double* Sigma_out, int* status_out)
+{
+    return chunk_predict_tv(h, "psoap_chunk_predict_tv", mode, c, M, lwl, lwl_pred, t_pred, mu_c, gp, tau, mu_out, Sigma_out, nullptr,
+                            status_out);
+}
+
+extern "C" int psoap_chunk_predict_tv_var(psoap_chunk* h, int mode, int c, int M, const double* lwl, const double* lwl_pred,
+                                          const double* t_pred, const double* mu_c, const double* gp, const double* tau,
+                                          double* mu_out, double* var_out, int* status_out)
+{
+    if (!var_out) FAIL("psoap_chunk_predict_tv_var: var_out is required");
+    return chunk_predict_tv(h, "psoap_chunk_predict_tv_var", mode, c, M, lwl, lwl_pred, t_pred, mu_c, gp, tau, mu_out, nullptr, var_out,
+                            status_out);
+}
+
 // ---- posterior draws (draw_kernels.hpp) ----------------------------------------------------------------------
 // D draws from N(mu, Sigma + nugget I) of the mean and Sigma the handle's predict workspace holds: the copy with the nugget,
 // the staged factorisation of the copy (no right-hand side: the staged kernels carry a zero vector along), the normals and

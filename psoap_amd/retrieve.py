@@ -155,6 +155,71 @@ def _retrieve_draws(c, lwls, fl, sigma, lwl, ep, lwl_predict, p_gp, get_Sigma, b
     return out
 
 
+def retrieve_components_at(model, chunk, parameters, tau, dates, n_pix_predict=None, get_Sigma="diag", n_draws=0, seed=None,
+                           nugget=1e-8):
+    """``retrieve_components`` under time-variable component spectra (``covariance.predict_timevar``): the spectrum of every
+    component at each of ``dates`` (in the unit and from the origin of ``chunk.date1D``), for time scales ``tau`` (c,) -- ``inf``
+    keeps a component static -- as ``optimize_GP_timevar`` finds them.  ONE device call over ``len(dates)`` runs of
+    ``retrieve_components``' prediction grid, the date of run ``d`` being ``dates[d] - min(chunk.date1D)``.
+
+    Returns ``wl_predict``, ``lwl_predict`` (M,), ``dates``, ``lwls``, ``mu`` (c * n_dates * M,) -- component by component, date
+    by date -- and ``Sigma`` (``get_Sigma=True``: the full matrix, the covariances between dates in it; else None), and per
+    component ``mu_f`` / ``sigma_f`` (, ``_g``, ``_h``) of shape ``(n_dates, M)`` (``sigma_*`` unless ``get_Sigma`` is False).
+    ``n_draws > 0`` (needs ``seed``): ``f_draws`` (, ``g_``, ``h_``) of shape ``(n_draws, n_dates, M)`` from ``N(mu, Sigma +
+    nugget I)``: every draw is one history of the spectrum over the dates."""
+    if model not in ("SB2", "ST3", "SB1"):
+        raise ValueError("retrieve_components_at supports SB1, SB2 and ST3 (the models the reference has scripts for)")
+    if isinstance(get_Sigma, str) and get_Sigma != "diag":
+        raise ValueError('get_Sigma must be True, False or "diag"')
+    if int(n_draws) > 0 and seed is None:
+        raise ValueError("retrieve_components_at(n_draws > 0) needs a seed")
+    c = N_COMPONENTS[model]
+    reg = registered_params[model]
+    p_orb = [parameters[n] for n in reg[:n_params_orb[model]]]
+    p_gp = [parameters[n] for n in reg[n_params_orb[model]:]]
+    mask = np.asarray(chunk.mask, dtype=bool)
+    if np.ndim(chunk.wl) != 2:
+        raise ValueError("retrieve_components_at needs the 2-D chunk: call it before apply_mask()")
+    lwl2d = np.log(np.asarray(chunk.wl, dtype=np.float64))
+    date1D = np.asarray(chunk.date1D, dtype=np.float64)
+    vel = np.atleast_2d(orbit.models[model](*p_orb, date1D).get_velocities())   # (c, n_epochs)
+    ep = epoch_index_of(mask)
+    lwls = lwl2d[mask][None, :] + (-vel[:, ep]) / c_kms
+    fl = np.asarray(chunk.fl, dtype=np.float64)[mask]
+    sigma = np.asarray(chunk.sigma, dtype=np.float64)[mask]
+    M = int(n_pix_predict) if n_pix_predict is not None else 2 * int(chunk.n_pix)
+    lwl_predict = np.linspace(np.min(lwls[0]), np.max(lwls[0]), num=M)
+    dates = np.atleast_1d(np.asarray(dates, dtype=np.float64))
+    D = dates.shape[0]
+    t0 = date1D.min()
+    times = date1D[ep] - t0
+    t_predict = np.repeat(dates - t0, M)
+    pred = [np.tile(lwl_predict, D)] * c
+    mode = 2 if c == 1 else 0
+    draws = None
+    if int(n_draws) > 0:
+        mu, second, draws = covariance.predict_draws(lwls, fl, sigma, pred, [0.0] * c, p_gp, int(n_draws), seed, mode=mode, nugget=nugget,
+                                                     timevar={"times": times, "tau": tau, "t_predict": t_predict})
+        want = True
+    else:
+        want = get_Sigma if isinstance(get_Sigma, str) else bool(get_Sigma)
+        res = covariance.predict_timevar(lwls, fl, sigma, pred, t_predict, [0.0] * c, p_gp, tau, times, mode=mode, want_sigma=want)
+        mu, second = res if want else (res, None)
+    out = {"wl_predict": np.exp(lwl_predict), "lwl_predict": lwl_predict, "dates": dates, "mu": mu,
+           "Sigma": second if (want is True and get_Sigma is True) else None, "lwls": lwls}
+    sd = None
+    if second is not None and get_Sigma:
+        sd = np.sqrt(second if want == "diag" else np.diag(second))
+    for k in range(c):
+        sl = slice(k * D * M, (k + 1) * D * M)
+        out["mu_" + _NAMES[k]] = mu[sl].reshape(D, M)
+        if sd is not None:
+            out["sigma_" + _NAMES[k]] = sd[sl].reshape(D, M)
+        if draws is not None:
+            out[_NAMES[k] + "_draws"] = np.ascontiguousarray(draws[:, sl]).reshape(int(n_draws), D, M)
+    return out
+
+
 def retrieve_posterior(model, chunk, parameters, flatchain, fix_params, n_samples=64, thin_seed=0, n_pix_predict=None,
                        get_Sigma=True, baseline=None, draws_per_sample=0, seed=None):
     """``retrieve_components`` marginalised over the chain instead of taken at one parameter vector: the component spectra
