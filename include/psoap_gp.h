@@ -512,6 +512,54 @@ int psoap_chunk_loo_marg(psoap_chunk *h, int c, const double *lwl, const double 
                          double *ep_resid,
                          double *ep_chi2, double *ep_logp, int32_t *ep_npix);
 
+/* ---- Fisher information and leave-one-out under the time-variable kernel -----------------
+ * psoap_chunk_fisher_tv and psoap_chunk_loo_tv are psoap_chunk_fisher and psoap_chunk_loo
+ * with the time-variable kernel of psoap_chunk_lnlike_tv_grad over the handle's times
+ * (psoap_chunk_set_times) in the place of K: tau (c) as there, the other arguments,
+ * outputs, shapes and NULL rules are their plain twins'.
+ * A tangent is t = (dx_t (c, N), da_tc, dl_tc, dtau_tc): tan_lwl (T, c, N; NULL: zeros),
+ * tan_gp (T, 2c), tan_tau (T, c; NULL: zeros), 1 <= T <= 32.  With d = x_c[n] - x_c[m],
+ * dt = t[n] - t[m] and e = exp(p_c d^2 + q_c dt^2), formed as psoap_chunk_lnlike_tv_grad
+ * forms it (a = p * d * d, then a = a + q * dt * dt, without contraction, one exp),
+ *   K_t[m,n] = sum_c e (2 a_c da_tc + a_c^2 c_kms^2 / l_c^3 d^2 dl_tc
+ *                       + a_c^2 2 p_c d (dx_tc[n] - dx_tc[m]) + a_c^2 / tau_c^3 dt^2 dtau_tc)
+ *   fisher    F_st = 1/2 tr(K^-1 K_s K^-1 K_t), both triangles, F == F^T bit for bit;
+ *   fisher_mu 1^T K^-1 1 (may be NULL);
+ *   leave-one-out: A = K^-1 and alpha = K^-1 r of that K in every formula of
+ *             psoap_chunk_loo; lnp has the bits of psoap_chunk_lnlike_tv_grad.
+ * The launches are the plain entries' with [K | I] factored under the time-variable fill;
+ * the Fisher information takes a tangent fill, a contraction, finishing sums and a dot of
+ * its own (csrc/tv_fisher_kernels.hpp), the leave-one-out nothing: behind the factorisation
+ * it reads K through W and alpha alone.  One multiply-add more per element in one fill and
+ * one epilogue per tangent; the flops are psoap_chunk_fisher's, (1 + 4 T) N^3.  No
+ * atomics, every sum in an order fixed by (N, c, T): the same arguments give the same
+ * bits, a subsequence of the tangents gives the bits of the entries it shares.
+ * Bit-identity at tau = inf: with every tau_c = +inf, F has the bits of psoap_chunk_fisher
+ * in every entry -- whatever tan_tau holds: its coefficient a^2 / tau^3 dtau is 0, added
+ * last -- and an entry whose tangent has nothing but dtau is exactly 0; fisher_mu and
+ * every field of the leave-one-out have the bits of the plain entries.
+ * Conventions: tau_c <= 0 or NaN, a negative hyper-parameter or a matrix that is not
+ * positive definite gives NaN in every entry of fisher and in fisher_mu, and for the
+ * leave-one-out lnp = -inf and NaN in every other floating output; status 0.  Refused
+ * with a message: what the plain twins refuse, a call before psoap_chunk_set_times, on a
+ * handle with an open stream, or on a handle with a baseline (the combination with the
+ * marginalised continuum is not built).
+ * Workspace: that of the plain twins, shared with them, plus 3 doubles for tau,
+ * 2 T c doubles of time-scale tangents and contractions and one double more per tile
+ * record; psoap_chunk_fisher_release, psoap_chunk_loo_release and
+ * psoap_chunk_grad_release free all of it, the times stay with the handle. */
+int psoap_chunk_fisher_tv(psoap_chunk *h, int c, const double *lwl, const double *gp,
+                          const double *tau, int T, const double *tan_lwl,
+                          const double *tan_gp, const double *tan_tau,
+                          double *fisher, double *fisher_mu);
+int psoap_chunk_loo_tv(psoap_chunk *h, int c, const double *lwl, const double *gp,
+                       const double *tau, double mu_GP,
+                       const int32_t *epoch, int n_epochs,
+                       double *lnp, double *loo_logp,
+                       double *pix_mean, double *pix_var, double *pix_logp,
+                       double *ep_resid,
+                       double *ep_chi2, double *ep_logp, int32_t *ep_npix);
+
 /* ---- component spectra under the marginalised continuum ------------------------------------------
  * psoap_chunk_predict_marg and psoap_chunk_predict_marg_var are psoap_chunk_predict and psoap_chunk_predict_var with
  * Kt = K + Ht Ht^T (the baseline of psoap_chunk_set_baseline) in the place of the data covariance K: arguments, output

@@ -249,8 +249,9 @@ class ChunkHandle:
         plain ``K``, also on a handle with a baseline: ``fisher_marg`` is the form under ``K + H Lambda H^T``."""
         return self._fisher("psoap_chunk_fisher", lwls, gp, tan_gp, tan_lwl, want_mu)
 
-    def _fisher(self, entry, lwls, gp, tan_gp, tan_lwl, want_mu):
-        """the body of ``fisher`` and ``fisher_marg``: ``entry`` names the library's function"""
+    def _fisher(self, entry, lwls, gp, tan_gp, tan_lwl, want_mu, tau=None, tan_tau=None):
+        """the body of ``fisher``, ``fisher_marg`` and ``fisher_tv``: ``entry`` names the library's function, which with ``tau``
+        takes it after ``gp`` and ``tan_tau`` after ``tan_gp``"""
         lwls = as_f64(np.atleast_2d(lwls))
         c = lwls.shape[0]
         lwls = as_f64(lwls, (c, self.N))
@@ -260,10 +261,25 @@ class ChunkHandle:
         tan_gp = as_f64(tan_gp, (T, 2 * c))
         if tan_lwl is not None:
             tan_lwl = as_f64(tan_lwl, (T, c, self.N))
+        after_gp, after_tan_gp = (), ()
+        if tau is not None:
+            tau = as_f64(np.atleast_1d(as_f64(tau)), (c,))
+            if tan_tau is not None:
+                tan_tau = as_f64(np.atleast_2d(as_f64(tan_tau)), (T, c))
+            after_gp, after_tan_gp = (dptr(tau),), (None if tan_tau is None else dptr(tan_tau),)
         F, mu = np.empty((T, T)), np.empty(1)
-        check(getattr(self._L, entry)(self._h, c, dptr(lwls), dptr(gp), T, None if tan_lwl is None else dptr(tan_lwl),
-                                      dptr(tan_gp), dptr(F), dptr(mu) if want_mu else None), entry)
+        check(getattr(self._L, entry)(self._h, c, dptr(lwls), dptr(gp), *after_gp, T, None if tan_lwl is None else dptr(tan_lwl),
+                                      dptr(tan_gp), *after_tan_gp, dptr(F), dptr(mu) if want_mu else None), entry)
         return (F, float(mu[0])) if want_mu else F
+
+    def fisher_tv(self, lwls, gp, tau, tan_gp, tan_tau=None, tan_lwl=None, want_mu: bool = False):
+        """``fisher`` under the time-variable kernel of ``lnlike_tv`` (include/psoap_gp.h: psoap_chunk_fisher_tv; needs
+        ``set_times``): ``tau`` (c,), and a tangent has a time-scale part, ``tan_tau`` (T, c) (``None``: zeros), beside
+        ``tan_gp`` (T, 2c) and ``tan_lwl`` (T, c, N).  ``F (T, T)`` symmetric bit for bit; with every ``tau = inf`` it has
+        the bits of ``fisher`` whatever ``tan_tau`` holds, and a tangent with nothing but a time-scale part gives an
+        exactly-zero row and column.  ``tau <= 0`` or NaN, a negative hyper-parameter or a matrix that is not positive
+        definite gives NaN in every entry; a handle with a baseline is refused."""
+        return self._fisher("psoap_chunk_fisher_tv", lwls, gp, tan_gp, tan_lwl, want_mu, tau, tan_tau)
 
     def fisher_marg(self, lwls, gp, tan_gp, tan_lwl=None, want_mu: bool = False):
         """``fisher`` under the baseline of ``set_baseline`` (include/psoap_gp.h: psoap_chunk_fisher_marg): the same arguments,
@@ -340,12 +356,14 @@ class ChunkHandle:
         baseline: ``loo_marg`` is the form under ``K + H Lambda H^T``."""
         return self._loo("psoap_chunk_loo", lwls, gp, mu_GP, epoch_index, n_epochs)
 
-    def _loo(self, entry, lwls, gp, mu_GP, epoch_index, n_epochs):
-        """the body of ``loo`` and ``loo_marg``: ``entry`` names the library's function"""
+    def _loo(self, entry, lwls, gp, mu_GP, epoch_index, n_epochs, tau=None):
+        """the body of ``loo``, ``loo_marg`` and ``loo_tv``: ``entry`` names the library's function, which with ``tau`` takes it
+        after ``gp``"""
         lwls = as_f64(np.atleast_2d(lwls))
         c = lwls.shape[0]
         lwls = as_f64(lwls, (c, self.N))
         gp = as_f64(gp, (2 * c,))
+        after_gp = () if tau is None else (dptr(as_f64(np.atleast_1d(as_f64(tau)), (c,))),)
         N = self.N
         lnp, logp = np.empty(1), np.empty(1)
         mean, var, plogp = np.empty(N), np.empty(N), np.empty(N)
@@ -358,7 +376,7 @@ class ChunkHandle:
             ne = int(ep.max()) + 1 if n_epochs is None else int(n_epochs)
             resid, chi2, elogp, npix = np.empty(N), np.empty(max(ne, 0)), np.empty(max(ne, 0)), np.empty(max(ne, 0), dtype=np.int32)
         i32 = ctypes.POINTER(ctypes.c_int32)
-        check(getattr(self._L, entry)(self._h, c, dptr(lwls), dptr(gp), float(mu_GP),
+        check(getattr(self._L, entry)(self._h, c, dptr(lwls), dptr(gp), *after_gp, float(mu_GP),
                                       None if ep is None else ep.ctypes.data_as(i32), ne, dptr(lnp), dptr(logp), dptr(mean),
                                       dptr(var), dptr(plogp), None if ep is None else dptr(resid),
                                       None if ep is None else dptr(chi2), None if ep is None else dptr(elogp),
@@ -374,6 +392,15 @@ class ChunkHandle:
         if getattr(self, "_baseline", None) is None:
             raise _lib.PsoapError("loo_marg: call set_baseline first")
         return self._loo("psoap_chunk_loo_marg", lwls, gp, mu_GP, epoch_index, n_epochs)
+
+    def loo_tv(self, lwls, gp, tau, mu_GP: float = 1.0, epoch_index=None, n_epochs: int | None = None) -> "LooResult":
+        """``loo`` under the time-variable kernel of ``lnlike_tv`` (include/psoap_gp.h: psoap_chunk_loo_tv; needs
+        ``set_times``): the same arguments with ``tau`` (c,) and the same ``LooResult`` with ``A = K^-1`` of that kernel --
+        every pixel and every epoch predicted from the others by the model ``optimize_GP_timevar`` fits, so an epoch whose
+        lines drifted as the fitted time scale allows is not an outlier.  ``lnp`` has the bits of ``lnlike_tv``; with every
+        ``tau = inf`` every field has the bits of ``loo``.  ``tau <= 0`` or NaN gives ``lnp = -inf`` and NaN like a negative
+        hyper-parameter; a handle with a baseline is refused."""
+        return self._loo("psoap_chunk_loo_tv", lwls, gp, mu_GP, epoch_index, n_epochs, tau)
 
     def loo_release(self):
         """Free the leave-one-out workspace (the packed epoch blocks); the next ``loo`` allocates it again."""

@@ -814,6 +814,106 @@ def _fit_timevar(value_grad, c, gp0, tau0, free_tau, ftol):
     return gp, tau, res
 
 
+def _timevar_front(lwls, gp, tau):
+    """``(lw (c, N), gp, tau (c,), degenerate)`` of a time-variable analysis call: the checks of ``_timevar`` up to the device
+    -- ``degenerate``: a negative hyper-parameter or a ``tau <= 0`` or NaN, to be answered before any work"""
+    gp = [float(g) for g in gp]
+    lw = np.stack([as_f64(w) for w in np.atleast_2d(lwls)])
+    c = lw.shape[0]
+    if len(gp) != 2 * c:
+        raise ValueError(f"gp must hold {2 * c} values for {c} component(s)")
+    tau = as_f64(np.atleast_1d(as_f64(tau)), (c,))
+    return lw, gp, tau, any(g < 0.0 for g in gp) or not np.all(tau > 0.0)
+
+
+def fisher_information_timevar(lwls, fl, sigma, gp, tau, times):
+    """The ``(3c, 3c)`` Fisher information of ``(amp_0, l_0, ..., tau_0, ..., tau_{c-1})`` under the time-variable kernel of
+    ``lnlike_timevar``, evaluated on the device (``ChunkHandle.fisher_tv`` with unit tangents, the cached handle with
+    ``times - min(times)`` on it): what ``fisher_information`` is for the static kernel, with the time scales and their
+    correlations with the amplitudes and length scales.  The row and column of a component with ``tau = inf`` are exactly
+    zero.  Degenerate input follows ``lnlike_timevar``: a negative hyper-parameter, a ``tau <= 0`` or NaN or a matrix that is
+    not positive definite gives NaN in every entry."""
+    lw, gp, tau, degenerate = _timevar_front(lwls, gp, tau)
+    c, N = lw.shape
+    t = as_f64(times, (N,))
+    if not np.all(np.isfinite(t)):
+        raise ValueError(_NONFINITE)
+    if degenerate:
+        return np.full((3 * c, 3 * c), np.nan)
+    if any(l == 0.0 for l in gp[1::2]):
+        raise ZeroDivisionError("float division")
+    if not _matrix_is_finite(lw, sigma, gp):
+        raise ValueError(_NONFINITE)
+    h, _t0 = _timevar_handle(fl, sigma, t, N, "fisher_information_timevar")
+    eye = np.eye(3 * c)
+    return h.fisher_tv(lw, gp, tau, eye[:, :2 * c], eye[:, 2 * c:])
+
+
+def _laplace_from_fisher(F, gp, tau, free):
+    """The algebra of ``timevar_laplace`` on a given ``F (3c, 3c)`` -> ``(cov_log, sd_gp, sd_tau)``.  (Nothing here knows the
+    device: the tests run it on the float64 CPU evaluation.)"""
+    gp, tau = as_f64(gp), as_f64(np.atleast_1d(as_f64(tau)))
+    c = tau.shape[0]
+    free = np.asarray(free, dtype=bool).reshape(c)
+    F = as_f64(F, (3 * c, 3 * c))
+    if not np.all(np.isfinite(tau[free])):
+        raise ValueError("a free tau must be finite")
+    idx = np.concatenate([np.arange(2 * c), 2 * c + np.flatnonzero(free)])
+    theta = np.concatenate([gp, tau])[idx]
+    F_log = theta[:, None] * F[np.ix_(idx, idx)] * theta[None, :]       # d/dlog theta = theta d/dtheta
+    try:
+        if not np.all(np.isfinite(F_log)):
+            raise np.linalg.LinAlgError
+        L = np.linalg.cholesky(F_log)
+    except np.linalg.LinAlgError:
+        raise np.linalg.LinAlgError("timevar_laplace: the Fisher information of the free log parameters is singular") from None
+    Linv = np.linalg.inv(L)
+    cov_log = Linv.T @ Linv
+    sd = theta * np.sqrt(np.diag(cov_log))                               # back to the parameters' own units
+    sd_tau = np.full(c, np.nan)
+    sd_tau[free] = sd[2 * c:]
+    return cov_log, sd[:2 * c], sd_tau
+
+
+def timevar_laplace(lwls, fl, sigma, gp, tau, times, free_tau=None):
+    """The Laplace covariance of an ``optimize_GP_timevar`` fit at ``(gp, tau)``, in the parameters ``_fit_timevar`` fits in,
+    ``(log gp, log tau[free])``: ``F_log = diag(theta) F diag(theta)`` of ``fisher_information_timevar`` restricted to the free
+    parameters, inverted.  ``free_tau`` (c,) of booleans defaults as in ``optimize_GP_timevar``: every finite ``tau``.
+    Returns ``(cov_log, sd_gp (2c,), sd_tau (c,))``: the covariance, and the standard deviations in the parameters' own units
+    (``theta`` times that of ``log theta``), ``nan`` for a ``tau`` that is not free.  ``LinAlgError`` where ``F_log`` is
+    singular -- also for the NaN of degenerate input."""
+    tau = as_f64(np.atleast_1d(as_f64(tau)))
+    free = np.isfinite(tau) if free_tau is None else np.asarray(free_tau, dtype=bool).reshape(tau.shape)
+    return _laplace_from_fisher(fisher_information_timevar(lwls, fl, sigma, gp, tau, times), gp, tau, free)
+
+
+def loo_timevar(lwls, fl, sigma, gp, tau, times, mu_GP=1.0, epoch_index=None):
+    """``loo`` under the time-variable kernel of ``lnlike_timevar`` (``ChunkHandle.loo_tv`` through the cached handle with
+    ``times - min(times)`` on it): the ``chunk.LooResult`` of the model ``optimize_GP_timevar`` fits, for the outlier search
+    that matches it.  Degenerate input follows ``loo`` and ``lnlike_timevar``: a negative hyper-parameter or a ``tau <= 0`` or
+    NaN gives ``lnp = -inf`` and NaN before any work."""
+    from .chunk import LooResult
+    lw, gp, tau, degenerate = _timevar_front(lwls, gp, tau)
+    N = lw.shape[1]
+    t = as_f64(times, (N,))
+    if not np.all(np.isfinite(t)):
+        raise ValueError(_NONFINITE)
+    ep = None if epoch_index is None else np.asarray(epoch_index, dtype=np.int64)
+    if ep is not None and (ep.shape != lw.shape[1:] or (ep.size and ep.min() < 0)):
+        raise ValueError("epoch_index must hold one non-negative epoch per pixel")
+    if degenerate:
+        return LooResult.degenerate(N, None if ep is None else np.bincount(ep))
+    if any(l == 0.0 for l in gp[1::2]):
+        raise ZeroDivisionError("float division")
+    if not _matrix_is_finite(lw, sigma, gp):
+        raise ValueError(_NONFINITE)
+    h, _t0 = _timevar_handle(fl, sigma, t, N, "loo_timevar")
+    res = h.loo_tv(lw, gp, tau, mu_GP, ep)
+    if not np.isneginf(res.lnp) and not (np.all(np.isfinite(np.asarray(fl, dtype=np.float64))) and np.isfinite(mu_GP)):
+        raise ValueError(_NONFINITE)
+    return res
+
+
 # ---- calibration (SURVEY.md 8(f) f-4) ---------------------------------------------------------------
 _CAL_FAIL = {1: "reference-epoch covariance B", 2: "conditional covariance C'", 3: "Chebyshev normal equations"}
 

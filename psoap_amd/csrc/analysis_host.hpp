@@ -118,9 +118,14 @@ static int inverse_bracket(psoap_chunk* h, hipStream_t s, const Factored& fac, F
 // The Fisher information of the likelihood (fisher_kernels.hpp).  One matrix through the gradient's workspace and
 // factorisation, then K^-1 and, tangent after tangent, K_t, Z = K_t K^-1 and the contraction of G_t = 1/2 (K^-1 Z + Z^T K^-1).
 // `marg`: under Kt = K + Ht Ht^T (marg_fisher_kernels.hpp) -- the marginal gradient's factorisation, Kt^-1, the same tangents.
-static int fisher_run(psoap_chunk* h, const char* who, bool marg, int c, const double* lwl, const double* gp, int T,
-                      const double* tan_lwl, const double* tan_gp, double* fisher, double* fisher_mu)
+// With `tau` (c; plain only, as grad_run's) K is the time-variable kernel over the handle's times and a tangent has a
+// time-scale part, tan_tau (T, c; nullptr: zeros): the TV fill, tangent fill, contraction, finishing sums and dot
+// (tv_fisher_kernels.hpp).  The caller has made the checks of fisher_tv_check.
+static int fisher_run(psoap_chunk* h, const char* who, bool marg, int c, const double* lwl, const double* gp, const double* tau,
+                      int T, const double* tan_lwl, const double* tan_gp, const double* tan_tau, double* fisher,
+                      double* fisher_mu)
 {
+    const bool tv = tau != nullptr;
     if (!h || !lwl || !gp || !tan_gp || !fisher) FAIL(std::string(who) + ": bad arguments");
     if (c < 1 || c > 3) FAIL("number of components must be 1, 2 or 3");
     if (T < 1 || T > FISHER_MAX_T) FAIL(std::string(who) + ": the number of tangents must be between 1 and 32");
@@ -128,7 +133,7 @@ static int fisher_run(psoap_chunk* h, const char* who, bool marg, int c, const d
     DEVICE_SCOPE(h->device);
     if (int rc = enter_device(h->device)) return rc;
     hipStream_t s = h->streams[0];
-    const Factored fac = factored(h, marg, 1);
+    const Factored fac = factored(h, marg, 1, tv);
     const int N = h->N, Npad = h->Npad, P = h->P, ld = fac.ld, ntiles = P * (P + 1) / 2;
     const size_t sq = (size_t)Npad * Npad, CN = (size_t)c * N;
     if (!h->fws) h->fws.reset(new FisherWs());
@@ -141,8 +146,12 @@ static int fisher_run(psoap_chunk* h, const char* who, bool marg, int c, const d
     HIP_TRY(f.Z.need(sq));
     HIP_TRY(f.TanX.need((size_t)T * CN));
     HIP_TRY(f.TanGp.need((size_t)T * 2 * c));
-    HIP_TRY(f.Part.need((size_t)ntiles * GradTile<false>::DOUBLES));
+    HIP_TRY(f.Part.need((size_t)ntiles * (tv ? GradTile<true>::DOUBLES : GradTile<false>::DOUBLES)));
     HIP_TRY(f.GGp.need((size_t)T * 2 * c));
+    if (tv) {
+        HIP_TRY(f.TanTau.need((size_t)T * c));
+        HIP_TRY(f.GTau.need((size_t)T * c));
+    }
     HIP_TRY(f.GX.need((size_t)T * CN));
     HIP_TRY(f.Y.need(Npad));
     HIP_TRY(f.Mu.need(2));
@@ -152,6 +161,11 @@ static int fisher_run(psoap_chunk* h, const char* who, bool marg, int c, const d
     if (tan_lwl) HIP_TRY(hipMemcpyAsync(f.TanX, tan_lwl, sizeof(double) * (size_t)T * CN, hipMemcpyHostToDevice, s));
     else HIP_TRY(hipMemsetAsync(f.TanX, 0, sizeof(double) * (size_t)T * CN, s));
     HIP_TRY(hipMemcpyAsync(f.TanGp, tan_gp, sizeof(double) * (size_t)T * 2 * c, hipMemcpyHostToDevice, s));
+    if (tv) {
+        HIP_TRY(hipMemcpyAsync(w.Tau, tau, sizeof(double) * c, hipMemcpyHostToDevice, s));
+        if (tan_tau) HIP_TRY(hipMemcpyAsync(f.TanTau, tan_tau, sizeof(double) * (size_t)T * c, hipMemcpyHostToDevice, s));
+        else HIP_TRY(hipMemsetAsync(f.TanTau, 0, sizeof(double) * (size_t)T * c, s));
+    }
     // (F does not depend on the data: any mu_GP)
     if (int rc = factor_group(h, fac, s, 1, c, 0.0, false)) return rc;
     if (int rc = inverse_bracket(h, s, fac, f)) return rc;
@@ -169,30 +183,53 @@ static int fisher_run(psoap_chunk* h, const char* who, bool marg, int c, const d
     for (int t = 0; t < T; ++t) {
         if (int rc = prof_launch(h, s, PSOAP_K_FILL, 0.0, 8.0 * (double)sq, [&] {
                 with_components(c, [&](auto nc) {
-                    hipLaunchKernelGGL(k_fisher_tangent_fill<nc()>, dim3(P * P), dim3(256), 0, s, f.Kt.p, Npad, N, P,
-                                       (const double*)w.Lwl.p, (const double*)w.Gp.p, (const double*)(f.TanX.p + (size_t)t * CN),
-                                       (const double*)(f.TanGp.p + (size_t)t * 2 * c));
+                    if (tv)
+                        hipLaunchKernelGGL(k_tv_fisher_tangent_fill<nc()>, dim3(P * P), dim3(256), 0, s, f.Kt.p, Npad, N, P,
+                                           (const double*)w.Lwl.p, (const double*)h->dTimes.p, (const double*)w.Gp.p,
+                                           (const double*)w.Tau.p, (const double*)(f.TanX.p + (size_t)t * CN),
+                                           (const double*)(f.TanGp.p + (size_t)t * 2 * c),
+                                           (const double*)(f.TanTau.p + (size_t)t * c));
+                    else
+                        hipLaunchKernelGGL(k_fisher_tangent_fill<nc()>, dim3(P * P), dim3(256), 0, s, f.Kt.p, Npad, N, P,
+                                           (const double*)w.Lwl.p, (const double*)w.Gp.p,
+                                           (const double*)(f.TanX.p + (size_t)t * CN),
+                                           (const double*)(f.TanGp.p + (size_t)t * 2 * c));
                 });
             })) return rc;
         if (int rc = prof_launch(h, s, PSOAP_K_GRAD, TILE_FLOPS * P * ((double)P * P + 2.0 * ntiles), 0.0, [&] {
                 hipLaunchKernelGGL(k_fisher_gemm, dim3(P * P), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)f.Kt.p,
                                    (const double*)f.Kinv.p, Npad, P, f.Z.p);
                 with_components(c, [&](auto nc) {
-                    hipLaunchKernelGGL(k_fisher_contract<nc()>, dim3(ntiles), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s,
-                                       (const double*)f.Kinv.p, (const double*)f.Z.p, N, Npad, P, (const double*)w.Lwl.p,
-                                       (const double*)w.Gp.p, f.Part.p);
+                    if (tv)
+                        hipLaunchKernelGGL(k_tv_fisher_contract<nc()>, dim3(ntiles), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s,
+                                           (const double*)f.Kinv.p, (const double*)f.Z.p, N, Npad, P, (const double*)w.Lwl.p,
+                                           (const double*)h->dTimes.p, (const double*)w.Gp.p, (const double*)w.Tau.p, f.Part.p);
+                    else
+                        hipLaunchKernelGGL(k_fisher_contract<nc()>, dim3(ntiles), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s,
+                                           (const double*)f.Kinv.p, (const double*)f.Z.p, N, Npad, P, (const double*)w.Lwl.p,
+                                           (const double*)w.Gp.p, f.Part.p);
                 });
             })) return rc;
         // the gradient's finishing sums as they are: its alpha is W 1 here, and its sum over alpha goes nowhere (Mu[1])
         if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
-                hipLaunchKernelGGL(k_grad_finish, dim3(P + 1, 1), dim3(128), 0, s, (const double*)f.Part.p, (const double*)f.Y.p,
-                                   (const double*)w.Gp.p, c, N, Npad, P, f.GGp.p + (size_t)t * 2 * c, f.GX.p + (size_t)t * CN,
-                                   f.Mu.p + 1);
+                if (tv)
+                    hipLaunchKernelGGL(k_tv_grad_finish, dim3(P + 1, 1), dim3(128), 0, s, (const double*)f.Part.p,
+                                       (const double*)f.Y.p, (const double*)w.Gp.p, (const double*)w.Tau.p, c, N, Npad, P,
+                                       f.GGp.p + (size_t)t * 2 * c, f.GTau.p + (size_t)t * c, f.GX.p + (size_t)t * CN, f.Mu.p + 1);
+                else
+                    hipLaunchKernelGGL(k_grad_finish, dim3(P + 1, 1), dim3(128), 0, s, (const double*)f.Part.p,
+                                       (const double*)f.Y.p, (const double*)w.Gp.p, c, N, Npad, P, f.GGp.p + (size_t)t * 2 * c,
+                                       f.GX.p + (size_t)t * CN, f.Mu.p + 1);
             })) return rc;
     }
     if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
-            hipLaunchKernelGGL(k_fisher_dot, dim3(T, T), dim3(256), 0, s, (const double*)f.TanX.p, (const double*)f.TanGp.p,
-                               (const double*)f.GX.p, (const double*)f.GGp.p, c, N, T, f.F.p);
+            if (tv)
+                hipLaunchKernelGGL(k_tv_fisher_dot, dim3(T, T), dim3(256), 0, s, (const double*)f.TanX.p, (const double*)f.TanGp.p,
+                                   (const double*)f.TanTau.p, (const double*)f.GX.p, (const double*)f.GGp.p,
+                                   (const double*)f.GTau.p, c, N, T, f.F.p);
+            else
+                hipLaunchKernelGGL(k_fisher_dot, dim3(T, T), dim3(256), 0, s, (const double*)f.TanX.p, (const double*)f.TanGp.p,
+                                   (const double*)f.GX.p, (const double*)f.GGp.p, c, N, T, f.F.p);
         })) return rc;
     MatAcc info;
     double value = 0.0;      // (marg: -inf also when M does not factor)
@@ -202,8 +239,9 @@ static int fisher_run(psoap_chunk* h, const char* who, bool marg, int c, const d
     HIP_TRY(hipMemcpyAsync(&info, f.Info, sizeof info, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     if (collect_timings(h)) return 1;
-    // the conventions of the likelihood: a negative hyper-parameter or a matrix that is not positive definite -> no information
-    if (info.info != 0.0 || value == -INFINITY || proposal_refused(gp, c, 0)) {
+    // the conventions of the likelihood: a negative hyper-parameter, a tau that is no time scale or a matrix that is not
+    // positive definite -> no information
+    if (info.info != 0.0 || value == -INFINITY || proposal_refused(gp, c, 0) || (tv && tau_refused(tau, c, 0))) {
         fill_nan(fisher, 0, (size_t)T * T);
         fill_nan(fisher_mu, 0, 1);
     }
@@ -367,8 +405,10 @@ static int info_vel_run(psoap_chunk* h, bool marg, int c, const double* lwl, con
 // as the gradient makes it, the band of K^-1 into the packed epoch blocks, their staged factorisation, the finishing kernel.
 // `marg`: under Kt = K + Ht Ht^T (marg_fisher_kernels.hpp) -- the factorisation, the value and alpha_m are the marginal
 // gradient's for one matrix and k_marg_loo_band scatters the band of Kt^-1 where k_loo_band scatters that of K^-1.
-static int loo_run(psoap_chunk* h, const char* who, bool marg, int c, const double* lwl, const double* gp, double mu_GP,
-                   const int32_t* epoch, int n_epochs, double* lnp, double* loo_logp, double* pix_mean, double* pix_var,
+// With `tau` (c; plain only, as grad_run's) K is the time-variable kernel over the handle's times: the factorisation alone
+// knows -- everything behind it reads K through W and alpha.
+static int loo_run(psoap_chunk* h, const char* who, bool marg, int c, const double* lwl, const double* gp, const double* tau,
+                   double mu_GP, const int32_t* epoch, int n_epochs, double* lnp, double* loo_logp, double* pix_mean, double* pix_var,
                    double* pix_logp, double* ep_resid, double* ep_chi2, double* ep_logp, int32_t* ep_npix)
 {
     if (!h || !lwl || !gp) FAIL(std::string(who) + ": bad arguments");
@@ -382,7 +422,8 @@ static int loo_run(psoap_chunk* h, const char* who, bool marg, int c, const doub
     if (!epoch) ep_resid = ep_chi2 = ep_logp = nullptr, ep_npix = nullptr;
     DEVICE_SCOPE(h->device);
     if (int rc = enter_device(h->device)) return rc;
-    const Factored fac = factored(h, marg, 1);
+    const bool tv = tau != nullptr;
+    const Factored fac = factored(h, marg, 1, tv);
     hipStream_t s = h->streams[0];
     if (!h->lws) h->lws.reset(new LooWs());
     if (int rc = factored_ws_need(h, fac, s, true, false)) return rc;
@@ -404,6 +445,7 @@ static int loo_run(psoap_chunk* h, const char* who, bool marg, int c, const doub
     HIP_TRY(l.PixBlock.need(N));
     HIP_TRY(l.EpBlock.need(lay.epoch_block.size()));
     if (int rc = single_front(h, s, c, lwl, gp)) return rc;
+    if (tv) HIP_TRY(hipMemcpyAsync(w.Tau, tau, sizeof(double) * c, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(l.Blocks, lay.blocks.data(), sizeof(LooBlock) * (size_t)nblk, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(l.Tiles, lay.tiles.data(), sizeof(LooTile) * (size_t)ntile, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(l.PixBlock, lay.pixel_block.data(), sizeof(int) * (size_t)N, hipMemcpyHostToDevice, s));
@@ -461,8 +503,9 @@ static int loo_run(psoap_chunk* h, const char* who, bool marg, int c, const doub
     if (ep_npix) HIP_TRY(hipMemcpyAsync(ep_npix, l.EpNpix, sizeof(int32_t) * (size_t)ne, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));       // (the layout's vectors and the caller's pageable arrays)
     if (collect_timings(h)) return 1;
-    // the conventions: a negative hyper-parameter or a matrix that is not positive definite -> -inf, and nothing else to say
-    if (proposal_refused(gp, c, 0)) value = -INFINITY;
+    // the conventions: a negative hyper-parameter, a tau that is no time scale or a matrix that is not positive definite ->
+    // -inf, and nothing else to say
+    if (proposal_refused(gp, c, 0) || (tv && tau_refused(tau, c, 0))) value = -INFINITY;
     if (lnp) *lnp = value;
     if (value == -INFINITY) {
         fill_nan(loo_logp, 0, 1);

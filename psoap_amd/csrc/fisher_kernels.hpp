@@ -383,6 +383,7 @@ inline hipError_t fisher_configure_kernels()
 struct FisherWs {
     Grow<double> Kinv, Kt, Z, TanX, TanGp, Part, GGp, GX, Y, Mu, F;
     Grow<double> V;      // Vt 1 of the marginal form (marg_fisher_kernels.hpp)
+    Grow<double> TanTau, GTau;      // the time-scale tangents (T, c) and their contractions (tv_fisher_kernels.hpp)
     Grow<MatAcc> Info;
 };
 

@@ -153,6 +153,31 @@ inline const char* predict_tv_check(int mode, int c, int M, bool arrays, bool ha
     return nullptr;
 }
 
+// ---- the analysis paths under the time-variable kernel (psoap_chunk_fisher_tv, psoap_chunk_loo_tv) -----------------------------
+// -> nullptr, or why the call is refused, without a device: the handle's state in the order and the words of predict_tv_check
+// -- times set, no open stream, no baseline.  A tau that is no time scale is not a refusal here: like a negative
+// hyper-parameter it gives NaN (the leave-one-out: -inf), after the call.  The caller puts the entry's name in front.
+inline const char* tv_analysis_check(int c, bool arrays, bool have_times, bool open_stream, bool have_baseline)
+{
+    if (!arrays) return "bad arguments";
+    if (c < 1 || c > 3) return "number of components must be 1, 2 or 3";
+    if (!have_times) return "call psoap_chunk_set_times first";
+    if (open_stream) return "the handle has an open stream (psoap_stream_close first)";
+    if (have_baseline)
+        return "the handle has a baseline (psoap_chunk_set_baseline): the time-variable kernel under the marginalised continuum "
+               "is not built yet";
+    return nullptr;
+}
+
+// ... and of psoap_chunk_fisher_tv: the number of tangents as well (max_T: FISHER_MAX_T of fisher_kernels.hpp)
+inline const char* fisher_tv_check(int c, int T, int max_T, bool arrays, bool have_times, bool open_stream, bool have_baseline)
+{
+    if (!arrays) return "bad arguments";
+    if (c < 1 || c > 3) return "number of components must be 1, 2 or 3";
+    if (T < 1 || T > max_T) return "the number of tangents must be between 1 and 32";
+    return tv_analysis_check(c, arrays, have_times, open_stream, have_baseline);
+}
+
 // the temporal factor adds one multiply-add per filled element and nothing to the sweep: the count is the plain call's
 inline double predict_tv_flops(double n, double r, bool sigma, bool var) { return predict_flops(n, r, sigma, var); }
 

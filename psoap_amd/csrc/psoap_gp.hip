@@ -33,6 +33,7 @@
 #include "grad_kernels.hpp"
 #include "orbit_grad_kernels.hpp"
 #include "fisher_kernels.hpp"
+#include "tv_fisher_kernels.hpp"
 #include "vel_fisher_kernels.hpp"
 #include "vel_newton_kernels.hpp"
 #include "loo_kernels.hpp"
@@ -334,6 +335,7 @@ static int configure_kernels(int device)
     HIP_TRY(predict_configure_kernels());
     HIP_TRY(grad_configure_kernels());
     HIP_TRY(fisher_configure_kernels());
+    HIP_TRY(tv_fisher_configure_kernels());
     HIP_TRY(vel_fisher_configure_kernels());
     HIP_TRY(vel_newton_configure_kernels());
     HIP_TRY(loo_configure_kernels());
@@ -2188,7 +2190,7 @@ extern "C" int psoap_chunk_lnlike_tv_grad(psoap_chunk* h, int B, int c, const do
 extern "C" int psoap_chunk_fisher(psoap_chunk* h, int c, const double* lwl, const double* gp, int T, const double* tan_lwl,
                                   const double* tan_gp, double* fisher, double* fisher_mu)
 {
-    return fisher_run(h, "psoap_chunk_fisher", false, c, lwl, gp, T, tan_lwl, tan_gp, fisher, fisher_mu);
+    return fisher_run(h, "psoap_chunk_fisher", false, c, lwl, gp, nullptr, T, tan_lwl, tan_gp, nullptr, fisher, fisher_mu);
 }
 
 // under the baseline of psoap_chunk_set_baseline (marg_fisher_kernels.hpp); the workspaces are the plain entry's and the
@@ -2196,7 +2198,19 @@ extern "C" int psoap_chunk_fisher(psoap_chunk* h, int c, const double* lwl, cons
 extern "C" int psoap_chunk_fisher_marg(psoap_chunk* h, int c, const double* lwl, const double* gp, int T, const double* tan_lwl,
                                        const double* tan_gp, double* fisher, double* fisher_mu)
 {
-    return fisher_run(h, "psoap_chunk_fisher_marg", true, c, lwl, gp, T, tan_lwl, tan_gp, fisher, fisher_mu);
+    return fisher_run(h, "psoap_chunk_fisher_marg", true, c, lwl, gp, nullptr, T, tan_lwl, tan_gp, nullptr, fisher, fisher_mu);
+}
+
+// under the time-variable kernel over the handle's times (tv_fisher_kernels.hpp); the workspaces are the plain entry's
+extern "C" int psoap_chunk_fisher_tv(psoap_chunk* h, int c, const double* lwl, const double* gp, const double* tau, int T,
+                                     const double* tan_lwl, const double* tan_gp, const double* tan_tau, double* fisher,
+                                     double* fisher_mu)
+{
+    if (!h) FAIL("psoap_chunk_fisher_tv: bad arguments");
+    if (const char* why = fisher_tv_check(c, T, FISHER_MAX_T, lwl && gp && tau && tan_gp && fisher, h->dTimes.p != nullptr,
+                                          h->stream.open, h->marg.valid))
+        FAIL(std::string("psoap_chunk_fisher_tv: ") + why);
+    return fisher_run(h, "psoap_chunk_fisher_tv", false, c, lwl, gp, tau, T, tan_lwl, tan_gp, tan_tau, fisher, fisher_mu);
 }
 
 extern "C" int psoap_chunk_fisher_release(psoap_chunk* h)
@@ -2235,7 +2249,7 @@ extern "C" int psoap_chunk_loo(psoap_chunk* h, int c, const double* lwl, const d
                                int n_epochs, double* lnp, double* loo_logp, double* pix_mean, double* pix_var, double* pix_logp,
                                double* ep_resid, double* ep_chi2, double* ep_logp, int32_t* ep_npix)
 {
-    return loo_run(h, "psoap_chunk_loo", false, c, lwl, gp, mu_GP, epoch, n_epochs, lnp, loo_logp, pix_mean, pix_var, pix_logp,
+    return loo_run(h, "psoap_chunk_loo", false, c, lwl, gp, nullptr, mu_GP, epoch, n_epochs, lnp, loo_logp, pix_mean, pix_var, pix_logp,
                    ep_resid, ep_chi2, ep_logp, ep_npix);
 }
 
@@ -2245,7 +2259,20 @@ extern "C" int psoap_chunk_loo_marg(psoap_chunk* h, int c, const double* lwl, co
                                     int n_epochs, double* lnp, double* loo_logp, double* pix_mean, double* pix_var,
                                     double* pix_logp, double* ep_resid, double* ep_chi2, double* ep_logp, int32_t* ep_npix)
 {
-    return loo_run(h, "psoap_chunk_loo_marg", true, c, lwl, gp, mu_GP, epoch, n_epochs, lnp, loo_logp, pix_mean, pix_var,
+    return loo_run(h, "psoap_chunk_loo_marg", true, c, lwl, gp, nullptr, mu_GP, epoch, n_epochs, lnp, loo_logp, pix_mean, pix_var,
+                   pix_logp, ep_resid, ep_chi2, ep_logp, ep_npix);
+}
+
+// under the time-variable kernel over the handle's times: lnp has the bits of psoap_chunk_lnlike_tv_grad
+extern "C" int psoap_chunk_loo_tv(psoap_chunk* h, int c, const double* lwl, const double* gp, const double* tau, double mu_GP,
+                                  const int32_t* epoch, int n_epochs, double* lnp, double* loo_logp, double* pix_mean,
+                                  double* pix_var, double* pix_logp, double* ep_resid, double* ep_chi2, double* ep_logp,
+                                  int32_t* ep_npix)
+{
+    if (!h) FAIL("psoap_chunk_loo_tv: bad arguments");
+    if (const char* why = tv_analysis_check(c, lwl && gp && tau, h->dTimes.p != nullptr, h->stream.open, h->marg.valid))
+        FAIL(std::string("psoap_chunk_loo_tv: ") + why);
+    return loo_run(h, "psoap_chunk_loo_tv", false, c, lwl, gp, tau, mu_GP, epoch, n_epochs, lnp, loo_logp, pix_mean, pix_var,
                    pix_logp, ep_resid, ep_chi2, ep_logp, ep_npix);
 }
 

@@ -208,3 +208,19 @@ def make_walker_velocities(chunk: SyntheticChunk, n_walkers: int, seed: int,
 def walker_lwls(chunk: SyntheticChunk, walker_velocities: np.ndarray) -> np.ndarray:
     """(n_walkers, c, N) rest-frame grids for each walker's velocity table."""
     return np.stack([replicate_wls(chunk.lwl, v, chunk.mask) for v in walker_velocities])
+
+
+def draw_timevar_flux(lwls, times, sigma, gp, tau, mu_GP: float, seed: int) -> np.ndarray:
+    """(N,) flux ``mu_GP + L z``: one seeded draw from the model of ``covariance.lnlike_timevar``, ``K = L L^T`` with
+    ``K_ij = sum_c a_c^2 exp(p_c d_cij^2 - dt_ij^2 / (2 tau_c^2)) + sigma_i^2 delta_ij`` -- a chunk whose spectra really drift
+    with the time scales ``tau`` (c,), for the checks of the time-variable analysis paths."""
+    lwls = np.atleast_2d(np.asarray(lwls, dtype=np.float64))
+    t = np.asarray(times, dtype=np.float64)
+    DT = t[None, :] - t[:, None]
+    K = np.zeros((t.shape[0],) * 2)
+    for k in range(lwls.shape[0]):
+        D = lwls[k][None, :] - lwls[k][:, None]
+        K += gp[2 * k] ** 2 * np.exp(-0.5 * (C_KMS / gp[2 * k + 1]) ** 2 * D * D - 0.5 * DT * DT / tau[k] ** 2)
+    K[np.diag_indices_from(K)] += np.asarray(sigma, dtype=np.float64) ** 2
+    z = np.random.default_rng(seed).standard_normal(t.shape[0])
+    return mu_GP + np.linalg.cholesky(K) @ z
