@@ -528,8 +528,9 @@ int psoap_chunk_loo_marg(psoap_chunk *h, int c, const double *lwl, const double 
  *   leave-one-out: A = K^-1 and alpha = K^-1 r of that K in every formula of
  *             psoap_chunk_loo; lnp has the bits of psoap_chunk_lnlike_tv_grad.
  * The launches are the plain entries' with [K | I] factored under the time-variable fill;
- * the Fisher information takes a tangent fill, a contraction, finishing sums and a dot of
- * its own (csrc/tv_fisher_kernels.hpp), the leave-one-out nothing: behind the factorisation
+ * the Fisher information takes the time-variable forms of its tangent fill, contraction and
+ * finishing sums and a dot with time-scale terms (csrc/fisher_kernels.hpp), the
+ * leave-one-out nothing: behind the factorisation
  * it reads K through W and alpha alone.  One multiply-add more per element in one fill and
  * one epilogue per tangent; the flops are psoap_chunk_fisher's, (1 + 4 T) N^3.  No
  * atomics, every sum in an order fixed by (N, c, T): the same arguments give the same

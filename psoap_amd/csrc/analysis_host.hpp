@@ -119,8 +119,8 @@ static int inverse_bracket(psoap_chunk* h, hipStream_t s, const Factored& fac, F
 // factorisation, then K^-1 and, tangent after tangent, K_t, Z = K_t K^-1 and the contraction of G_t = 1/2 (K^-1 Z + Z^T K^-1).
 // `marg`: under Kt = K + Ht Ht^T (marg_fisher_kernels.hpp) -- the marginal gradient's factorisation, Kt^-1, the same tangents.
 // With `tau` (c; plain only, as grad_run's) K is the time-variable kernel over the handle's times and a tangent has a
-// time-scale part, tan_tau (T, c; nullptr: zeros): the TV fill, tangent fill, contraction, finishing sums and dot
-// (tv_fisher_kernels.hpp).  The caller has made the checks of fisher_tv_check.
+// time-scale part, tan_tau (T, c; nullptr: zeros): the TV fill, tangent fill, contraction and finishing sums, and the dot
+// with its time-scale terms.  The caller has made the checks of fisher_tv_check.
 static int fisher_run(psoap_chunk* h, const char* who, bool marg, int c, const double* lwl, const double* gp, const double* tau,
                       int T, const double* tan_lwl, const double* tan_gp, const double* tan_tau, double* fisher,
                       double* fisher_mu)
@@ -180,41 +180,32 @@ static int fisher_run(psoap_chunk* h, const char* who, bool marg, int c, const d
             } else
                 hipLaunchKernelGGL(k_fisher_mu, dim3(1), dim3(256), 0, s, (const double*)f.Y.p, N, f.Mu.p);
         })) return rc;
+    // (static: the handle's times, w.Tau, f.TanTau and f.GTau may be null pointers; the static kernels do not read them)
+    const double *times = h->dTimes.p, *dtau = w.Tau.p;
     for (int t = 0; t < T; ++t) {
+        const double* tan_tau_t = tv ? f.TanTau.p + (size_t)t * c : nullptr;
         if (int rc = prof_launch(h, s, PSOAP_K_FILL, 0.0, 8.0 * (double)sq, [&] {
                 with_components(c, [&](auto nc) {
-                    if (tv)
-                        hipLaunchKernelGGL(k_tv_fisher_tangent_fill<nc()>, dim3(P * P), dim3(256), 0, s, f.Kt.p, Npad, N, P,
-                                           (const double*)w.Lwl.p, (const double*)h->dTimes.p, (const double*)w.Gp.p,
-                                           (const double*)w.Tau.p, (const double*)(f.TanX.p + (size_t)t * CN),
-                                           (const double*)(f.TanGp.p + (size_t)t * 2 * c),
-                                           (const double*)(f.TanTau.p + (size_t)t * c));
-                    else
-                        hipLaunchKernelGGL(k_fisher_tangent_fill<nc()>, dim3(P * P), dim3(256), 0, s, f.Kt.p, Npad, N, P,
-                                           (const double*)w.Lwl.p, (const double*)w.Gp.p,
-                                           (const double*)(f.TanX.p + (size_t)t * CN),
-                                           (const double*)(f.TanGp.p + (size_t)t * 2 * c));
+                    hipLaunchKernelGGL(tv ? k_tv_fisher_tangent_fill<nc()> : k_fisher_tangent_fill<nc()>, dim3(P * P), dim3(256),
+                                       0, s, f.Kt.p, Npad, N, P, (const double*)w.Lwl.p, times, (const double*)w.Gp.p, dtau,
+                                       (const double*)(f.TanX.p + (size_t)t * CN),
+                                       (const double*)(f.TanGp.p + (size_t)t * 2 * c), tan_tau_t);
                 });
             })) return rc;
         if (int rc = prof_launch(h, s, PSOAP_K_GRAD, TILE_FLOPS * P * ((double)P * P + 2.0 * ntiles), 0.0, [&] {
                 hipLaunchKernelGGL(k_fisher_gemm, dim3(P * P), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)f.Kt.p,
                                    (const double*)f.Kinv.p, Npad, P, f.Z.p);
                 with_components(c, [&](auto nc) {
-                    if (tv)
-                        hipLaunchKernelGGL(k_tv_fisher_contract<nc()>, dim3(ntiles), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s,
-                                           (const double*)f.Kinv.p, (const double*)f.Z.p, N, Npad, P, (const double*)w.Lwl.p,
-                                           (const double*)h->dTimes.p, (const double*)w.Gp.p, (const double*)w.Tau.p, f.Part.p);
-                    else
-                        hipLaunchKernelGGL(k_fisher_contract<nc()>, dim3(ntiles), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s,
-                                           (const double*)f.Kinv.p, (const double*)f.Z.p, N, Npad, P, (const double*)w.Lwl.p,
-                                           (const double*)w.Gp.p, f.Part.p);
+                    hipLaunchKernelGGL(tv ? k_tv_fisher_contract<nc()> : k_fisher_contract<nc()>, dim3(ntiles),
+                                       dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)f.Kinv.p, (const double*)f.Z.p, N,
+                                       Npad, P, (const double*)w.Lwl.p, times, (const double*)w.Gp.p, dtau, f.Part.p);
                 });
             })) return rc;
         // the gradient's finishing sums as they are: its alpha is W 1 here, and its sum over alpha goes nowhere (Mu[1])
         if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
                 if (tv)
                     hipLaunchKernelGGL(k_tv_grad_finish, dim3(P + 1, 1), dim3(128), 0, s, (const double*)f.Part.p,
-                                       (const double*)f.Y.p, (const double*)w.Gp.p, (const double*)w.Tau.p, c, N, Npad, P,
+                                       (const double*)f.Y.p, (const double*)w.Gp.p, dtau, c, N, Npad, P,
                                        f.GGp.p + (size_t)t * 2 * c, f.GTau.p + (size_t)t * c, f.GX.p + (size_t)t * CN, f.Mu.p + 1);
                 else
                     hipLaunchKernelGGL(k_grad_finish, dim3(P + 1, 1), dim3(128), 0, s, (const double*)f.Part.p,
@@ -222,14 +213,11 @@ static int fisher_run(psoap_chunk* h, const char* who, bool marg, int c, const d
                                        f.GX.p + (size_t)t * CN, f.Mu.p + 1);
             })) return rc;
     }
+    // (static: no time-scale terms in the dot)
     if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
-            if (tv)
-                hipLaunchKernelGGL(k_tv_fisher_dot, dim3(T, T), dim3(256), 0, s, (const double*)f.TanX.p, (const double*)f.TanGp.p,
-                                   (const double*)f.TanTau.p, (const double*)f.GX.p, (const double*)f.GGp.p,
-                                   (const double*)f.GTau.p, c, N, T, f.F.p);
-            else
-                hipLaunchKernelGGL(k_fisher_dot, dim3(T, T), dim3(256), 0, s, (const double*)f.TanX.p, (const double*)f.TanGp.p,
-                                   (const double*)f.GX.p, (const double*)f.GGp.p, c, N, T, f.F.p);
+            hipLaunchKernelGGL(k_fisher_dot, dim3(T, T), dim3(256), 0, s, (const double*)f.TanX.p, (const double*)f.TanGp.p,
+                               (const double*)(tv ? f.TanTau.p : nullptr), (const double*)f.GX.p, (const double*)f.GGp.p,
+                               (const double*)(tv ? f.GTau.p : nullptr), c, N, T, f.F.p);
         })) return rc;
     MatAcc info;
     double value = 0.0;      // (marg: -inf also when M does not factor)

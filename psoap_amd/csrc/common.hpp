@@ -81,6 +81,21 @@ __device__ inline void decode_upper(int t, int P, int& ti, int& tj)
     tj = r + (t - (r * P - r * (r - 1) / 2));
 }
 
+// The sum of one value per thread of a 256-thread workgroup through red[256] in LDS: store, barrier, then eight halvings with a
+// barrier behind each -- a fixed order of additions.  Every thread returns the sum; a caller that uses `red` again puts a
+// barrier in between.
+__device__ __forceinline__ double block_sum_256(double* red, double v)
+{
+    const int tid = threadIdx.x;
+    red[tid] = v;
+    __syncthreads();
+    for (int w = 128; w >= 1; w >>= 1) {
+        if (tid < w) red[tid] += red[tid + w];
+        __syncthreads();
+    }
+    return red[0];
+}
+
 // ---- host ----------------------------------------------------------------------------------
 // The owners.  A field that holds a device resource is one of these: it is released where the field goes out of scope, on
 // every return path, and no destroy function names it.  All are move-only and convert to the raw handle.

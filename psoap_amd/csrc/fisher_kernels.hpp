@@ -15,6 +15,7 @@
 //                             and never stored
 //   k_grad_finish             (the gradient's, as it is) the tiles' sums in tile order
 //   k_fisher_dot              F_st = tan_s . g_t for every s >= t, mirrored: F == F^T bit for bit
+// The contraction's epilogue is the gradient's, grad_contract_epilogue with ContractQ::Fisher.
 //
 // K_s is linear in its tangent, so <K_s, G_t> is taken one factor at a time: k_fisher_contract contracts G_t with the
 // derivative of K with respect to every hyper-parameter and every grid point -- the sums of k_grad_contract with Q = G_t:
@@ -34,6 +35,28 @@
 // Flops: the factorisation of [K | I] 2/3 N^3, K^-1 1/3 N^3, per tangent 2 N^3 (Z) + 2 N^3 (the upper tiles of G_t, two K-loops):
 //   F_fisher(N, T) = (1 + 4 T) N^3.
 // fp64 throughout, no atomics, every sum in an order fixed by (N, c, T).
+//
+// Under the time-variable kernel of fill_kernels.hpp (psoap_chunk_fisher_tv)
+//   K_ij = sum_c a_c^2 e_cij + sigma_i^2 delta_ij,   e_cij = exp(p_c d_cij^2 + q_c dt_ij^2),   q_c = -1/2 / tau_c^2
+// a tangent is t = (dx_t (c, N), da_tc, dl_tc, dtau_tc), and with dt = t[n] - t[m]
+//   K_t[m,n] = sum_c e_cmn (2 a_c da_tc + a_c^2 c_kms^2 / l_c^3 d^2 dl_tc + a_c^2 2 p_c d (dx_tc[n] - dx_tc[m])
+//                           + a_c^2 / tau_c^3 dt^2 dtau_tc)
+// The launch sequence is the one above on [K | I] factored under the time-variable fill (Factored::tv), with the TV = true
+// wrappers of the same two bodies and the time-variable finishing sums:
+//   k_tv_fisher_tangent_fill<C>  the row times in LDS beside xrow / drow, two column times per lane, the fourth coefficient
+//   k_tv_fisher_contract<C>      the tile's row and column times in LDS, the combined argument, one more hyper sum per
+//                                component, sum w q e dt^2, in a GradTile<true> record
+//   k_tv_grad_finish             (the time-variable gradient's, as it is) leaves g_t[tau_c] beside g_t[gp] and g_t[x]
+//   k_fisher_dot                 with tan_tau and g_tau: c N + 3 c numbers
+// The argument of every exp() is formed as k_fill_sym_tv forms it: a = p2 * d * d, then a = a + q2 * dt * dt, without
+// contraction, one exp, the wave-uniform <= -746 shortcut on the combined argument.
+//
+// tau_c = +inf is the static model, bit for bit.  q2 = -0, so q2 * dt * dt = -0 whatever the sign of dt and a + (-0) = a;
+// ct = a^2 / inf * dtau = 0 whatever dtau is, and its term is ADDED LAST to the static sum of the fill, s + ct * dt^2 = s
+// (fused or not: the product is an exact zero); the contraction's new sum st goes nowhere near sa, sl or the row and column
+// sums; k_tv_grad_finish gives g_t[tau_c] = (1/2 a^2 / inf) * st = 0; and the dot adds the tau terms AFTER the static ones,
+// r + 0 = r.  So with every tau = inf the entries of F have the bits of psoap_chunk_fisher whatever tan_tau holds, and a
+// tangent with nothing but dtau gives K_t = 0 and an exactly-zero row and column.
 #pragma once
 #include "grad_kernels.hpp"
 
@@ -76,27 +99,36 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void k_fisher_kinv(const double* _
 }
 
 // K_t, every tile (grid P P), in the layout of k_fill_sym: wave w owns the 32-column block w, a lane four rows x two columns
-// per step, the eight exponentials of a component through one batched, underflow-skipping evaluation.
-template <int C>
-__global__ __launch_bounds__(256) void k_fisher_tangent_fill(double* __restrict__ Kt, int Npad, int N, int P,
-                                                             const double* __restrict__ lwl, const double* __restrict__ gp,
-                                                             const double* __restrict__ tan_x,
-                                                             const double* __restrict__ tan_gp)
+// per step, the eight exponentials of a component through one batched, underflow-skipping evaluation.  TV: the row times in
+// LDS beside xrow / drow, two column times per lane, the fourth coefficient ct[c] = a_c^2 / tau_c^3 dtau_tc.
+template <int C, bool TV>
+__device__ __forceinline__ void fisher_tangent_fill_tile(double* __restrict__ Kt, int Npad, int N, int P,
+                                                         const double* __restrict__ lwl, const double* __restrict__ times,
+                                                         const double* __restrict__ gp, const double* __restrict__ tau,
+                                                         const double* __restrict__ tan_x, const double* __restrict__ tan_gp,
+                                                         const double* __restrict__ tan_tau)
 {
     __shared__ double xrow[C][NB];
     __shared__ double drow[C][NB];
+    __shared__ double trow[TV ? NB : 1];      // (static: never referenced, and not allocated)
     const int ti = blockIdx.x / P, tj = blockIdx.x % P;
     const int tid = threadIdx.x;
     const int i0 = ti * NB, j0 = tj * NB;
     GpDev g;
     load_gp(gp, C, g);
     double ca[C], cl[C], cx[C];      // the coefficients of e, e d^2 and e d (dx[n] - dx[m])
+    [[maybe_unused]] double q2[C], ct[C];      // TV: q_c and the coefficient of e dt^2
 #pragma unroll
     for (int c = 0; c < C; ++c) {
         const double a = gp[2 * c], l = gp[2 * c + 1];
         ca[c] = 2.0 * a * tan_gp[2 * c];
         cl[c] = g.a2[c] * (C_KMS * C_KMS) / (l * l * l) * tan_gp[2 * c + 1];
         cx[c] = g.a2[c] * 2.0 * g.p2[c];
+        if constexpr (TV) {
+            const double tc = tau[c];
+            q2[c] = tv_q2(tc);
+            ct[c] = g.a2[c] / (tc * tc * tc) * tan_tau[c];
+        }
     }
     if (tid < NB) {
         const int i = i0 + tid;
@@ -105,6 +137,7 @@ __global__ __launch_bounds__(256) void k_fisher_tangent_fill(double* __restrict_
             xrow[c][tid] = (i < N) ? lwl[(size_t)c * N + i] : 0.0;
             drow[c][tid] = (i < N) ? tan_x[(size_t)c * N + i] : 0.0;
         }
+        if constexpr (TV) trow[tid] = (i < N) ? times[i] : 0.0;
     }
     const int w = tid >> 6, rg = (tid >> 4) & 3, cp = tid & 15;
     const int ja = j0 + 32 * w + 2 * cp, jb = ja + 1;
@@ -116,10 +149,24 @@ __global__ __launch_bounds__(256) void k_fisher_tangent_fill(double* __restrict_
         da[c] = (ja < N) ? tan_x[(size_t)c * N + ja] : 0.0;
         db[c] = (jb < N) ? tan_x[(size_t)c * N + jb] : 0.0;
     }
+    [[maybe_unused]] double ta, tb;
+    if constexpr (TV) {
+        ta = (ja < N) ? times[ja] : 0.0;
+        tb = (jb < N) ? times[jb] : 0.0;
+    }
     __syncthreads();
 #pragma unroll 1
     for (int g4 = 0; g4 < NB / 16; ++g4) {
         double va[4] = {0.0, 0.0, 0.0, 0.0}, vb[4] = {0.0, 0.0, 0.0, 0.0};
+        [[maybe_unused]] double dta[4], dtb[4];
+        if constexpr (TV) {
+#pragma unroll
+            for (int s4 = 0; s4 < 4; ++s4) {
+                const double tr = trow[16 * g4 + rg + 4 * s4];
+                dta[s4] = ta - tr;
+                dtb[s4] = tb - tr;
+            }
+        }
 #pragma unroll
         for (int c = 0; c < C; ++c) {
             double d[8], a[8], e[8];
@@ -131,7 +178,9 @@ __global__ __launch_bounds__(256) void k_fisher_tangent_fill(double* __restrict_
                 d[2 * s4] = xa[c] - xi;
                 d[2 * s4 + 1] = xb[c] - xi;
                 a[2 * s4] = g.p2[c] * d[2 * s4] * d[2 * s4];
+                if constexpr (TV) a[2 * s4] = a[2 * s4] + q2[c] * dta[s4] * dta[s4];
                 a[2 * s4 + 1] = g.p2[c] * d[2 * s4 + 1] * d[2 * s4 + 1];
+                if constexpr (TV) a[2 * s4 + 1] = a[2 * s4 + 1] + q2[c] * dtb[s4] * dtb[s4];
                 live = live || !(a[2 * s4] <= -746.0) || !(a[2 * s4 + 1] <= -746.0);
             }
             if (__builtin_amdgcn_ballot_w64(live) == 0ull) continue;      // exp() = +0 for the whole wave
@@ -140,8 +189,18 @@ __global__ __launch_bounds__(256) void k_fisher_tangent_fill(double* __restrict_
             for (int s4 = 0; s4 < 4; ++s4) {
                 const double di = drow[c][16 * g4 + rg + 4 * s4];
                 const double ua = d[2 * s4], ub = d[2 * s4 + 1];
-                va[s4] += e[2 * s4] * (ca[c] + cl[c] * (ua * ua) + cx[c] * (ua * (da[c] - di)));
-                vb[s4] += e[2 * s4 + 1] * (ca[c] + cl[c] * (ub * ub) + cx[c] * (ub * (db[c] - di)));
+                double sa = ca[c] + cl[c] * (ua * ua) + cx[c] * (ua * (da[c] - di));
+                double sb = ca[c] + cl[c] * (ub * ub) + cx[c] * (ub * (db[c] - di));
+                if constexpr (TV) {
+                    // the static sum first, the temporal term last: at tau = inf it adds an exact zero.  (The opaque statement
+                    // ends the static expression where the static kernel ends it: what is fused into multiply-adds inside
+                    // it does not depend on the term that follows.)
+                    asm volatile("" : "+v"(sa), "+v"(sb));
+                    sa = sa + ct[c] * (dta[s4] * dta[s4]);
+                    sb = sb + ct[c] * (dtb[s4] * dtb[s4]);
+                }
+                va[s4] += e[2 * s4] * sa;
+                vb[s4] += e[2 * s4 + 1] * sb;
             }
         }
 #pragma unroll
@@ -153,6 +212,29 @@ __global__ __launch_bounds__(256) void k_fisher_tangent_fill(double* __restrict_
             *reinterpret_cast<d2*>(Kt + (size_t)i * Npad + ja) = v;
         }
     }
+}
+
+// (one argument list for both, so that fisher_run launches either the same way: the static kernel reads none of times, tau
+// and tan_tau)
+template <int C>
+__global__ __launch_bounds__(256) void k_fisher_tangent_fill(double* __restrict__ Kt, int Npad, int N, int P,
+                                                             const double* __restrict__ lwl, const double* __restrict__ times,
+                                                             const double* __restrict__ gp, const double* __restrict__ tau,
+                                                             const double* __restrict__ tan_x, const double* __restrict__ tan_gp,
+                                                             const double* __restrict__ tan_tau)
+{
+    fisher_tangent_fill_tile<C, false>(Kt, Npad, N, P, lwl, times, gp, tau, tan_x, tan_gp, tan_tau);
+}
+
+template <int C>
+__global__ __launch_bounds__(256) void k_tv_fisher_tangent_fill(double* __restrict__ Kt, int Npad, int N, int P,
+                                                                const double* __restrict__ lwl, const double* __restrict__ times,
+                                                                const double* __restrict__ gp, const double* __restrict__ tau,
+                                                                const double* __restrict__ tan_x,
+                                                                const double* __restrict__ tan_gp,
+                                                                const double* __restrict__ tan_tau)
+{
+    fisher_tangent_fill_tile<C, true>(Kt, Npad, N, P, lwl, times, gp, tau, tan_x, tan_gp, tan_tau);
 }
 
 // Z = K_t K^-1: Z[m][n] = sum_k K_t[k][m] K^-1[k][n] (K_t is symmetric, so its block columns are the k-major operand).
@@ -176,134 +258,52 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void k_fisher_gemm(const double* _
         }
 }
 
-// One workgroup per upper tile (ti <= tj) of 2 G_t = K^-1 Z + Z^T K^-1, then the epilogue of k_grad_contract with q = G_t[i][j]: per
-// component e_c = exp(p_c d^2) once per element, and the sums
-//   hyper-parameters  sum w q e_c, sum w q e_c d^2   (w = 2 off the diagonal: the element stands for (i,j) and (j,i); 1 on it)
+// One workgroup per upper tile (ti <= tj) of 2 G_t = K^-1 Z + Z^T K^-1, then the epilogue of the gradient's contraction
+// (grad_contract_epilogue, ContractQ::Fisher) with q = G_t[i][j]: per component e_c = exp(p_c d^2), under TV
+// exp(p_c d^2 + q_c dt^2), once per element, and the sums
+//   hyper-parameters  sum w q e_c, sum w q e_c d^2, under TV sum w q e_c dt^2   (w = 2 off the diagonal: the element stands for
+//                     (i,j) and (j,i); 1 on it)
 //   rows of block ti  sum_j q e_c d;     rows of block tj  -sum_i q e_c d
-// in the tile's own GradTile<false>::DOUBLES of `part` (the gradient's layout: k_grad_finish adds them up).  A diagonal tile takes
-// i <= j only; rows and columns >= N are masked (G_t is exactly zero there).
-template <int C>
-__global__ __launch_bounds__(GEMM_THREADS, 2) void k_fisher_contract(const double* __restrict__ Kinv, const double* __restrict__ Z,
-                                                                    int N, int Npad, int P, const double* __restrict__ lwl,
-                                                                    const double* __restrict__ gp, double* __restrict__ part)
+// in the tile's own GradTile<TV>::DOUBLES of `part` (the gradient's layout: k_grad_finish / k_tv_grad_finish add them up).  A
+// diagonal tile takes i <= j only; rows and columns >= N are masked (G_t is exactly zero there).  grid P (P + 1) / 2
+template <int C, bool TV>
+__device__ __forceinline__ void fisher_contract_tile(const double* __restrict__ Kinv, const double* __restrict__ Z, int N, int Npad,
+                                                     int P, const double* __restrict__ lwl, const double* __restrict__ times,
+                                                     const double* __restrict__ gp, const double* __restrict__ tau,
+                                                     double* __restrict__ part)
 {
-    constexpr int XS = 0;                 // [2][3][NB]: abscissae of the tile's rows (side 0) and columns (side 1)
-    constexpr int RS = XS + 6 * NB;       // [2 wc][3][NB]: row sums of the two wave columns
-    constexpr int CS = RS + 6 * NB;       // [2 wr][3][NB]: column sums of the two wave rows
-    constexpr int HS = CS + 6 * NB;       // [4 waves][6]
-    static_assert((HS + 24) * sizeof(double) <= GEMM_LDS_BYTES, "the epilogue fits the operand buffers");
     int ti, tj;
     decode_upper(blockIdx.x, P, ti, tj);
     Tile t;
     t.zero();
     tile_gemm_tn(t, Kinv + NB * ti, (size_t)Npad, Z + NB * tj, (size_t)Npad, Npad, ti == tj);
     tile_gemm_tn(t, Z + NB * ti, (size_t)Npad, Kinv + NB * tj, (size_t)Npad, Npad, ti == tj);      // (+ its transpose's tile)
+    grad_contract_epilogue<C, TV, ContractQ::Fisher>(t, 0, ti, tj, (int)blockIdx.x, N, Npad, P, lwl, gp, nullptr, part, times, tau);
+}
 
-    const int tid = threadIdx.x;
-    const int lane = tid & 63, wave = tid >> 6;
-    const int wr = wave >> 1, wc = wave & 1;
-    {
-        const int side = tid >> 7, idx = tid & 127;
-        const int g = NB * (side ? tj : ti) + idx;
-#pragma unroll
-        for (int c = 0; c < C; ++c) psoap_smem[XS + (side * 3 + c) * NB + idx] = (g < N) ? lwl[(size_t)c * N + g] : 0.0;
-    }
-    __syncthreads();
-    const bool diag_tile = ti == tj;
-#pragma unroll 1
-    for (int c = 0; c < C; ++c) {
-        double p2;
-        {
-#pragma clang fp contract(off)
-            const double l = gp[2 * c + 1];      // (as load_gp rounds it)
-            p2 = -0.5 * (C_KMS * C_KMS) / (l * l);
-        }
-        double xj[4], colacc[4];
-        bool jok[4];
-#pragma unroll
-        for (int n = 0; n < 4; ++n) {
-            const int col = tile_col(wc, n, lane);
-            xj[n] = psoap_smem[XS + (3 + c) * NB + col];
-            jok[n] = NB * tj + col < N;
-            colacc[n] = 0.0;
-        }
-        double sa = 0.0, sl = 0.0;
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            double xi[4], rowacc[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                xi[r] = psoap_smem[XS + c * NB + tile_row(wr, m, lane, r)];
-                rowacc[r] = 0.0;
-            }
-#pragma unroll
-            for (int n = 0; n < 4; ++n) {
-                const int col = tile_col(wc, n, lane);
-                double d[4], a[4], e[4];
-                bool live = false;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-#pragma clang fp contract(off)
-                    d[r] = xj[n] - xi[r];
-                    a[r] = p2 * d[r] * d[r];
-                    live = live || !(a[r] <= -746.0);
-                }
-                if (__builtin_amdgcn_ballot_w64(live) == 0ull) continue;      // exp() = +0 for the whole wave: nothing to add
-                exp_nonpos_batch<4>(a, e);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int row = tile_row(wr, m, lane, r);
-                    const bool ok = jok[n] && NB * ti + row < N && (!diag_tile || row <= col);
-                    const double qe = ok ? 0.5 * t.acc[m][n][r] * e[r] : 0.0;
-                    const double w = (diag_tile && row == col) ? 1.0 : 2.0;
-                    const double qed = qe * d[r];
-                    sa = fma(w, qe, sa);
-                    sl = fma(w * qed, d[r], sl);
-                    rowacc[r] += qed;
-                    colacc[n] -= qed;
-                }
-            }
-            // the row's 16 lanes (lane & 15 = column within the block), then the two wave columns in LDS
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-#pragma unroll
-                for (int off = 1; off <= 8; off <<= 1) rowacc[r] += __shfl_xor(rowacc[r], off, 64);
-                if ((lane & 15) == 0) psoap_smem[RS + (wc * 3 + c) * NB + tile_row(wr, m, lane, r)] = rowacc[r];
-            }
-        }
-#pragma unroll
-        for (int n = 0; n < 4; ++n) {
-            colacc[n] += __shfl_xor(colacc[n], 16, 64);
-            colacc[n] += __shfl_xor(colacc[n], 32, 64);
-            if (lane < 16) psoap_smem[CS + (wr * 3 + c) * NB + tile_col(wc, n, lane)] = colacc[n];
-        }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            sa += __shfl_xor(sa, off, 64);
-            sl += __shfl_xor(sl, off, 64);
-        }
-        if (lane == 0) {
-            psoap_smem[HS + wave * 6 + 2 * c] = sa;
-            psoap_smem[HS + wave * 6 + 2 * c + 1] = sl;
-        }
-    }
-    __syncthreads();
-    double* out = part + (size_t)blockIdx.x * GradTile<false>::DOUBLES;
-    {
-        const int side = tid >> 7, idx = tid & 127;
-        const int src = side ? CS : RS;
-#pragma unroll
-        for (int c = 0; c < C; ++c)
-            out[(side ? GradTile<false>::COLS_OFF : GradTile<false>::ROWS_OFF) + c * NB + idx] =
-                psoap_smem[src + c * NB + idx] + psoap_smem[src + (3 + c) * NB + idx];
-    }
-    if (tid < 2 * C)
-        out[GradTile<false>::HYP_OFF + tid] = ((psoap_smem[HS + tid] + psoap_smem[HS + 6 + tid]) + psoap_smem[HS + 12 + tid]) +
-                                              psoap_smem[HS + 18 + tid];
+// (one argument list for both, as the tangent fills)
+template <int C>
+__global__ __launch_bounds__(GEMM_THREADS, 2) void k_fisher_contract(const double* __restrict__ Kinv, const double* __restrict__ Z,
+                                                                    int N, int Npad, int P, const double* __restrict__ lwl,
+                                                                    const double* __restrict__ times,
+                                                                    const double* __restrict__ gp,
+                                                                    const double* __restrict__ tau, double* __restrict__ part)
+{
+    fisher_contract_tile<C, false>(Kinv, Z, N, Npad, P, lwl, times, gp, tau, part);
+}
+
+template <int C>
+__global__ __launch_bounds__(GEMM_THREADS, 2) void k_tv_fisher_contract(const double* __restrict__ Kinv, const double* __restrict__ Z,
+                                                                       int N, int Npad, int P, const double* __restrict__ lwl,
+                                                                       const double* __restrict__ times,
+                                                                       const double* __restrict__ gp,
+                                                                       const double* __restrict__ tau, double* __restrict__ part)
+{
+    fisher_contract_tile<C, true>(Kinv, Z, N, Npad, P, lwl, times, gp, tau, part);
 }
 
 // F_mu = 1^T K^-1 1 = |W 1|^2 in two fixed-order stages.  y[k] = sum of row k of W over its columns q <= k, q < N (the rest is
-// exactly zero): thread j adds every 256th term, the 256 sums meet in a tree.  grid N, 256 threads
+// exactly zero): thread j adds every 256th term, the 256 sums meet in a tree (block_sum_256).  grid N, 256 threads
 __global__ __launch_bounds__(256) void k_fisher_w1(const double* __restrict__ A, int ld, int Npad, int N, double* __restrict__ y)
 {
     __shared__ double red[256];
@@ -311,13 +311,8 @@ __global__ __launch_bounds__(256) void k_fisher_w1(const double* __restrict__ A,
     const double* Wk = A + (size_t)k * ld + Npad;
     double s = 0.0;
     for (int q = tid; q <= k && q < N; q += 256) s += Wk[q];
-    red[tid] = s;
-    __syncthreads();
-    for (int w = 128; w >= 1; w >>= 1) {
-        if (tid < w) red[tid] += red[tid + w];
-        __syncthreads();
-    }
-    if (tid == 0) y[k] = red[0];
+    const double sum = block_sum_256(red, s);
+    if (tid == 0) y[k] = sum;
 }
 
 // one workgroup of 256 threads: out = sum_k y[k]^2, the same way
@@ -327,20 +322,17 @@ __global__ __launch_bounds__(256) void k_fisher_mu(const double* __restrict__ y,
     const int tid = threadIdx.x;
     double s = 0.0;
     for (int k = tid; k < N; k += 256) s = fma(y[k], y[k], s);
-    red[tid] = s;
-    __syncthreads();
-    for (int w = 128; w >= 1; w >>= 1) {
-        if (tid < w) red[tid] += red[tid + w];
-        __syncthreads();
-    }
-    if (tid == 0) *out = red[0];
+    const double sum = block_sum_256(red, s);
+    if (tid == 0) *out = sum;
 }
 
 // F[s][t] = F[t][s] = tan_s . g_t for s >= t.  grid (T, T), 256 threads: the c N grid terms strided and met in a tree, then
-// the 2c hyper-parameter terms one after the other.  g: what k_grad_finish made of tangent t's tiles (g_gp (T, 2c), g_x (T, c, N))
+// the 2c hyper-parameter terms one after the other, then (tan_tau, g_tau not nullptr) the c time-scale terms likewise.  g: what
+// k_grad_finish / k_tv_grad_finish made of tangent t's tiles (g_gp (T, 2c), g_tau (T, c), g_x (T, c, N))
 __global__ __launch_bounds__(256) void k_fisher_dot(const double* __restrict__ tan_x, const double* __restrict__ tan_gp,
-                                                    const double* __restrict__ g_x, const double* __restrict__ g_gp, int C, int N,
-                                                    int T, double* __restrict__ F)
+                                                    const double* __restrict__ tan_tau, const double* __restrict__ g_x,
+                                                    const double* __restrict__ g_gp, const double* __restrict__ g_tau, int C,
+                                                    int N, int T, double* __restrict__ F)
 {
     __shared__ double red[256];
     const int s = blockIdx.x, t = blockIdx.y, tid = threadIdx.x;
@@ -350,40 +342,34 @@ __global__ __launch_bounds__(256) void k_fisher_dot(const double* __restrict__ t
     const double* gt = g_x + (size_t)t * CN;
     double acc = 0.0;
     for (size_t i = tid; i < CN; i += 256) acc = fma(ts[i], gt[i], acc);
-    red[tid] = acc;
-    __syncthreads();
-    for (int w = 128; w >= 1; w >>= 1) {
-        if (tid < w) red[tid] += red[tid + w];
-        __syncthreads();
-    }
+    double r = block_sum_256(red, acc);
     if (tid == 0) {
-        double r = red[0];
         for (int k = 0; k < 2 * C; ++k) r = fma(tan_gp[(size_t)s * 2 * C + k], g_gp[(size_t)t * 2 * C + k], r);
+        if (tan_tau)
+            for (int k = 0; k < C; ++k) r = fma(tan_tau[(size_t)s * C + k], g_tau[(size_t)t * C + k], r);
         F[(size_t)s * T + t] = r;
         F[(size_t)t * T + s] = r;
     }
 }
 
+// the LDS attribute of every kernel here that takes the operand buffers
 inline hipError_t fisher_configure_kernels()
 {
-    const int lds = (int)GEMM_LDS_BYTES;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_fisher_kinv), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_fisher_gemm), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_fisher_contract<1>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_fisher_contract<2>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_fisher_contract<3>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    return e;
+    const void* const kernels[] = {
+        reinterpret_cast<const void*>(k_fisher_kinv),           reinterpret_cast<const void*>(k_fisher_gemm),
+        reinterpret_cast<const void*>(k_fisher_contract<1>),    reinterpret_cast<const void*>(k_fisher_contract<2>),
+        reinterpret_cast<const void*>(k_fisher_contract<3>),    reinterpret_cast<const void*>(k_tv_fisher_contract<1>),
+        reinterpret_cast<const void*>(k_tv_fisher_contract<2>), reinterpret_cast<const void*>(k_tv_fisher_contract<3>)};
+    for (const void* k : kernels)
+        if (hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GEMM_LDS_BYTES)) return e;
+    return hipSuccess;
 }
 
 // the Fisher workspace of a chunk handle (grow-only; psoap_chunk_fisher_release frees it)
 struct FisherWs {
     Grow<double> Kinv, Kt, Z, TanX, TanGp, Part, GGp, GX, Y, Mu, F;
     Grow<double> V;      // Vt 1 of the marginal form (marg_fisher_kernels.hpp)
-    Grow<double> TanTau, GTau;      // the time-scale tangents (T, c) and their contractions (tv_fisher_kernels.hpp)
+    Grow<double> TanTau, GTau;      // the time-scale tangents (T, c) and their contractions (fisher_tv)
     Grow<MatAcc> Info;
 };
 

@@ -33,13 +33,13 @@ namespace psoap {
 
 // One tile of the contraction, static or time-variable: its record in the partial-sum workspace -- row sums [3][128], column
 // sums [3][128], then HYP sums per component (sa, sl and under TV st; the static record has two spare doubles) -- and the map
-// of the epilogue's LDS.  GradTile<false> is also the record of fisher_kernels.hpp.
+// of the epilogue's LDS.  Both are also those of the contractions of fisher_kernels.hpp.
 template <bool TV>
 struct GradTile {
     static constexpr int HYP = TV ? 3 : 2;
     static constexpr int ROWS_OFF = 0, COLS_OFF = 3 * NB, HYP_OFF = 6 * NB, DOUBLES = 6 * NB + (TV ? 9 : 8);
     static constexpr int XS = 0;                            // [2][3][NB]: abscissae of the tile's rows (side 0) and columns (side 1)
-    static constexpr int AL = XS + 6 * NB;                  // [2][NB]: alpha likewise
+    static constexpr int AL = XS + 6 * NB;                  // [2][NB]: alpha likewise (ContractQ::Gradient only)
     static constexpr int TS = AL + 2 * NB;                  // [2][NB]: times likewise (TV only)
     static constexpr int RS = TS + (TV ? 2 * NB : 0);       // [2 wc][3][NB]: row sums of the two wave columns
     static constexpr int CS = RS + 6 * NB;                  // [2 wr][3][NB]: column sums of the two wave rows
@@ -47,6 +47,11 @@ struct GradTile {
     static constexpr int WS = 3 * HYP;
     static_assert((HS + 4 * WS) * sizeof(double) <= GEMM_LDS_BYTES, "the epilogue fits the operand buffers");
 };
+
+// How a lane of the epilogue forms q from its element t of the accumulator tile:
+//   Gradient  q = alpha_i alpha_j - t   t = (K^-1)_ij: the gradient's Q
+//   Fisher    q = 1/2 t                 t = (2 G_t)_ij: the symmetrised product of fisher_kernels.hpp; no alpha is read
+enum class ContractQ { Gradient, Fisher };
 
 __host__ __device__ inline int upper_index(int ti, int tj, int P) { return ti * P - ti * (ti - 1) / 2 + (tj - ti); }
 
@@ -130,12 +135,16 @@ __global__ void k_grad_alpha_finish(const double* __restrict__ partial, int nsla
 // A diagonal tile takes i <= j only; rows and columns >= N are masked.  The components are walked one after the other
 // (the accumulators leave few registers), the tile's sums meet in LDS -- the operand buffers of the product, free by then --
 // in a fixed order, and the workgroup stores them to its own GradTile<TV>::DOUBLES of `part`.
-// The epilogue: everything after the product, on the tile t = (K^-1)[ti][tj] in the accumulators (one function, three
-// callers: the two kernels below and k_marg_grad_contract of marg_grad_kernels.hpp, whose t is the tile of (K + Ht Ht^T)^-1).
+// The epilogue: everything after the product, on the tile t = (K^-1)[ti][tj] in the accumulators (one function: the two
+// kernels below, k_marg_grad_contract of marg_grad_kernels.hpp, whose t is the tile of (K + Ht Ht^T)^-1, and with
+// Q = ContractQ::Fisher the two contractions of fisher_kernels.hpp, whose t is the tile of 2 G_t and whose alpha is nullptr).
 // TV: e_c = exp(p_c d^2 + q_c dt^2) from `times` (N) and tau (B, C), the tile's row and column times beside its abscissae in
 // LDS, and one more sum per component, st = sum w q e_c dt^2; sa, sl and the row and column sums keep their formulas and
 // their order.
-template <int C, bool TV = false>
+// Fisher: behind two K-loops the kernel has fewer registers, so the thread id passes through an opaque statement in every turn
+// of the component loop: the rows, columns, masks and weights derived from it are formed again per component and not kept
+// across the loop -- 64 predicates and weights held live beside the accumulators spill (profiles/timevar_fisher.md).
+template <int C, bool TV = false, ContractQ Q = ContractQ::Gradient>
 __device__ __forceinline__ void grad_contract_epilogue(const Tile& t, int b, int ti, int tj, int tile_index, int N, int Npad,
                                                        int P, const double* __restrict__ lwl, const double* __restrict__ gp,
                                                        const double* __restrict__ alpha, double* __restrict__ part,
@@ -144,22 +153,31 @@ __device__ __forceinline__ void grad_contract_epilogue(const Tile& t, int b, int
 {
     using L = GradTile<TV>;
     constexpr int XS = L::XS, AL = L::AL, RS = L::RS, CS = L::CS, HS = L::HS, WS = L::WS;
+    constexpr bool FISHER = Q == ContractQ::Fisher;
     const int tid = threadIdx.x;
-    const int lane = tid & 63, wave = tid >> 6;
-    const int wr = wave >> 1, wc = wave & 1;
+    int lane = tid & 63, wave = tid >> 6;
+    int wr = wave >> 1, wc = wave & 1;
     const double* lw = lwl + (size_t)b * C * N;
     {
         const int side = tid >> 7, idx = tid & 127;
         const int g = NB * (side ? tj : ti) + idx;
 #pragma unroll
         for (int c = 0; c < C; ++c) psoap_smem[XS + (side * 3 + c) * NB + idx] = (g < N) ? lw[(size_t)c * N + g] : 0.0;
-        psoap_smem[AL + side * NB + idx] = alpha[(size_t)b * Npad + g];
+        if constexpr (!FISHER) psoap_smem[AL + side * NB + idx] = alpha[(size_t)b * Npad + g];
         if constexpr (TV) psoap_smem[L::TS + side * NB + idx] = (g < N) ? times[g] : 0.0;
     }
     __syncthreads();
     const bool diag_tile = ti == tj;
 #pragma unroll 1
     for (int c = 0; c < C; ++c) {
+        if constexpr (FISHER) {      // (the gradient keeps what it formed ahead of the loop, and its instructions)
+            int tl = tid;
+            asm volatile("" : "+v"(tl));
+            lane = tl & 63;
+            wave = tl >> 6;
+            wr = wave >> 1;
+            wc = wave & 1;
+        }
         double p2;
         {
 #pragma clang fp contract(off)
@@ -168,13 +186,14 @@ __device__ __forceinline__ void grad_contract_epilogue(const Tile& t, int b, int
         }
         [[maybe_unused]] double q2;
         if constexpr (TV) q2 = tv_q2(tau[(size_t)b * C + c]);
-        double xj[4], aj[4], colacc[4];
+        double xj[4], colacc[4];
+        [[maybe_unused]] double aj[4];
         bool jok[4];
 #pragma unroll
         for (int n = 0; n < 4; ++n) {
             const int col = tile_col(wc, n, lane);
             xj[n] = psoap_smem[XS + (3 + c) * NB + col];
-            aj[n] = psoap_smem[AL + NB + col];
+            if constexpr (!FISHER) aj[n] = psoap_smem[AL + NB + col];
             jok[n] = NB * tj + col < N;
             colacc[n] = 0.0;
         }
@@ -182,12 +201,13 @@ __device__ __forceinline__ void grad_contract_epilogue(const Tile& t, int b, int
         [[maybe_unused]] double st = 0.0;
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
-            double xi[4], ai[4], rowacc[4];
+            double xi[4], rowacc[4];
+            [[maybe_unused]] double ai[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int row = tile_row(wr, m, lane, r);
                 xi[r] = psoap_smem[XS + c * NB + row];
-                ai[r] = psoap_smem[AL + row];
+                if constexpr (!FISHER) ai[r] = psoap_smem[AL + row];
                 rowacc[r] = 0.0;
             }
 #pragma unroll
@@ -215,7 +235,9 @@ __device__ __forceinline__ void grad_contract_epilogue(const Tile& t, int b, int
                 for (int r = 0; r < 4; ++r) {
                     const int row = tile_row(wr, m, lane, r);
                     const bool ok = jok[n] && NB * ti + row < N && (!diag_tile || row <= col);
-                    const double qe = ok ? (ai[r] * aj[n] - t.acc[m][n][r]) * e[r] : 0.0;
+                    double qe;
+                    if constexpr (FISHER) qe = ok ? 0.5 * t.acc[m][n][r] * e[r] : 0.0;
+                    else qe = ok ? (ai[r] * aj[n] - t.acc[m][n][r]) * e[r] : 0.0;
                     const double w = (diag_tile && row == col) ? 1.0 : 2.0;
                     const double qed = qe * d[r];
                     [[maybe_unused]] double dt;

@@ -93,13 +93,8 @@ __global__ __launch_bounds__(256) void k_marg_fisher_v1(const double* __restrict
     const double* Vk = Mx + (size_t)k * ldm + S;
     double s = 0.0;
     for (int q = tid; q < N; q += 256) s += Vk[q];
-    red[tid] = s;
-    __syncthreads();
-    for (int w = 128; w >= 1; w >>= 1) {
-        if (tid < w) red[tid] += red[tid + w];
-        __syncthreads();
-    }
-    if (tid == 0) v[k] = red[0];
+    const double sum = block_sum_256(red, s);
+    if (tid == 0) v[k] = sum;
 }
 
 // one workgroup of 256 threads: out = sum_k y[k]^2 - sum_k v[k]^2, each sum as k_fisher_mu makes it
@@ -115,13 +110,7 @@ __global__ __launch_bounds__(256) void k_marg_fisher_mu(const double* __restrict
         const int n = pass ? S : N;
         double s = 0.0;
         for (int k = tid; k < n; k += 256) s = fma(x[k], x[k], s);
-        red[tid] = s;
-        __syncthreads();
-        for (int w = 128; w >= 1; w >>= 1) {
-            if (tid < w) red[tid] += red[tid + w];
-            __syncthreads();
-        }
-        total[pass] = red[0];
+        total[pass] = block_sum_256(red, s);
         __syncthreads();
     }
     if (tid == 0) *out = total[0] - total[1];

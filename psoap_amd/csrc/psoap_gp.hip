@@ -33,7 +33,6 @@
 #include "grad_kernels.hpp"
 #include "orbit_grad_kernels.hpp"
 #include "fisher_kernels.hpp"
-#include "tv_fisher_kernels.hpp"
 #include "vel_fisher_kernels.hpp"
 #include "vel_newton_kernels.hpp"
 #include "loo_kernels.hpp"
@@ -335,7 +334,6 @@ static int configure_kernels(int device)
     HIP_TRY(predict_configure_kernels());
     HIP_TRY(grad_configure_kernels());
     HIP_TRY(fisher_configure_kernels());
-    HIP_TRY(tv_fisher_configure_kernels());
     HIP_TRY(vel_fisher_configure_kernels());
     HIP_TRY(vel_newton_configure_kernels());
     HIP_TRY(loo_configure_kernels());
@@ -2201,7 +2199,7 @@ extern "C" int psoap_chunk_fisher_marg(psoap_chunk* h, int c, const double* lwl,
     return fisher_run(h, "psoap_chunk_fisher_marg", true, c, lwl, gp, nullptr, T, tan_lwl, tan_gp, nullptr, fisher, fisher_mu);
 }
 
-// under the time-variable kernel over the handle's times (tv_fisher_kernels.hpp); the workspaces are the plain entry's
+// under the time-variable kernel over the handle's times (fisher_kernels.hpp); the workspaces are the plain entry's
 extern "C" int psoap_chunk_fisher_tv(psoap_chunk* h, int c, const double* lwl, const double* gp, const double* tau, int T,
                                      const double* tan_lwl, const double* tan_gp, const double* tan_tau, double* fisher,
                                      double* fisher_mu)

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """The exact pin of the analysis paths behind the C ABI (gradient, orbit gradient, Fisher information, leave-one-out, continuum
-marginalisation and its gradients, the staged likelihood, the predict family): for every call of ``CALLS`` the int64 bit pattern of every output
+marginalisation and its gradients, the time-variable kernel's gradient and Fisher information, the staged likelihood, the
+predict family): for every call of ``CALLS`` the int64 bit pattern of every output
 array and, from ``ChunkHandle.timings()``, the per-class ``launches``, ``flops`` and ``bytes`` -- host-computed integers held in
 doubles.  ``ms`` and ``total_ms`` are measurements and are not recorded.  A predict call also records ``predict_timings()["flops"]`` (host-computed; no ``*_ms``
 field).  tests/test_gpu_analysis_pin.py replays ``CALLS``
@@ -38,6 +39,7 @@ import marg_fisher_reference as mf  # noqa: E402
 import marg_predict_reference as mp  # noqa: E402
 import marg_reference as mr  # noqa: E402
 import orbit_grad_reference as ogr  # noqa: E402
+import timevar_fisher_reference as tf  # noqa: E402
 from psoap_amd import synthetic as syn  # noqa: E402
 from psoap_amd import _lib  # noqa: E402
 from psoap_amd._lib import K_NAMES, dptr  # noqa: E402
@@ -99,6 +101,7 @@ def _named(names, values):
 
 
 GRAD_OUT = ("lnp", "grad_gp", "grad_lwl", "grad_mu")
+TV_GRAD_OUT = ("lnp", "grad_gp", "grad_tau", "grad_lwl", "grad_mu")
 ORBIT_OUT = ("lnp", "grad_orb", "grad_gp", "grad_mu", "grad_vel")
 LOO_OUT = ("lnp", "loo_logp", "pix_mean", "pix_var", "pix_logp", "ep_resid", "ep_chi2", "ep_logp", "ep_npix")
 MARG_OUT = ("lnp", "parts", "beta", "beta_cov", "fl_cor")
@@ -132,6 +135,35 @@ def _fisher(grid_tangents):
     with _handle(ch) as h:
         yield h, lambda: _named(("F", "F_mu"), h.fisher(ch.lwls, gp, tan_gp[pick], tan_lwl[pick] if grid_tangents else None,
                                                         want_mu=True))
+
+
+@contextlib.contextmanager
+def _fisher_tv():
+    """N = 129, c = 2 (an off-diagonal tile, a diagonal tile with masked rows, 127 padded rows), tau = (2 span, inf): an
+    amplitude, a length-scale, a time-scale (of the finite tau) and a grid tangent"""
+    case = next(k for k in tf.CASES if tf.case_id(k) == "N129-c2")
+    d = tf.case_data(case)
+    assert np.isfinite(d.tau[0]) and np.isinf(d.tau[1])
+    tan_lwl, tan_gp, tan_tau = tf.case_tangents(case)
+    pick = [0, 1, 4, 6]
+    assert all(np.any(a[pick]) for a in (tan_lwl, tan_gp[:, 0::2], tan_gp[:, 1::2], tan_tau))
+    with _handle(d) as h:
+        h.set_times(d.times)
+        yield h, lambda: _named(("F", "F_mu"), h.fisher_tv(d.lwls, d.gp, d.tau, tan_gp[pick], tan_tau[pick], tan_lwl[pick],
+                                                           want_mu=True))
+
+
+@contextlib.contextmanager
+def _lnlike_tv_grad():
+    """the batch of ``_lnlike_grad`` cut to one group of three, the epochs 30 days apart, one tau finite and one infinite in
+    every proposal"""
+    case = mr.case_named("c")
+    ch = mr.case_chunk(case)
+    lw, gps = _batch(case, 3, 9703)
+    tau = np.array([[40.0, np.inf], [np.inf, 25.0], [70.0, np.inf]])
+    with _handle(ch) as h:
+        h.set_times(30.0 * ch.epoch_index)
+        yield h, lambda: _named(TV_GRAD_OUT, h.lnlike_tv_grad(lw, gps, tau, mr.MU_GP))
 
 
 @contextlib.contextmanager
@@ -323,6 +355,8 @@ CALLS = {
     "loo_marg-f-one-pixels-only": lambda: _loo("f", False, "one"),
     "fisher_marg-c-one-negative": lambda: _fisher_marg("c", "one", False, negative=True),      # the NaN convention
     "lnlike_marg_grad-c-one-B3-negative": _lnlike_marg_grad_parts,          # one group, a refusal: parts, the poisoned gradient
+    "fisher_tv-N129-T4-finite-tau": _fisher_tv,
+    "lnlike_tv_grad-c-B3-finite-tau": _lnlike_tv_grad,
     **_predict_calls(),
 }
 

@@ -1,5 +1,5 @@
 """GPU tests of the Fisher information and the leave-one-out under the time-variable kernel (psoap_chunk_fisher_tv,
-psoap_chunk_loo_tv; psoap_amd/csrc/tv_fisher_kernels.hpp).
+psoap_chunk_loo_tv; psoap_amd/csrc/fisher_kernels.hpp).
 
 Shapes at the edges of the 128-row tiles (tests/timevar_fisher_reference.py: CASES, each with its own tau, one with the pixels
 in no time order); per case T = 3c + 3 tangents: the 2c unit tangents of gp, the c of tau, two velocity tangents and one random

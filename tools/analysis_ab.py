@@ -80,6 +80,7 @@ def calls(ch, N):
     tau = np.array([[40.0, 90.0], [np.inf, 25.0], [60.0, 60.0]])
     rng = np.random.default_rng(7300 + N)
     tan_gp, tan_lwl = rng.standard_normal((2, 2 * C)), 1e-5 * rng.standard_normal((2, C, N))
+    tan_tau = np.array([[7.0, -3.0], [0.0, 11.0]])      # fisher_tv and loo_tv run at tau[0]: both finite
     ep = ch["epoch"]
     GRAD, ORB = ("lnp", "grad_gp", "grad_lwl", "grad_mu"), ("lnp", "grad_orb", "grad_gp", "grad_mu", "grad_vel")
     LOO = ("lnp", "loo_logp", "pix_mean", "pix_var", "pix_logp", "ep_resid", "ep_chi2", "ep_logp", "ep_npix")
@@ -93,12 +94,15 @@ def calls(ch, N):
         "lnlike_tv_grad": ({"times": True}, "lnlike_tv_grad",
                            lambda h: tup(("lnp", "grad_gp", "grad_tau", "grad_lwl", "grad_mu"), h.lnlike_tv_grad(lw, gps, tau, MU))),
         "fisher": ({}, "fisher", lambda h: tup(("F", "F_mu"), h.fisher(ch["lwls"], gp, tan_gp, tan_lwl, want_mu=True))),
+        "fisher_tv": ({"times": True}, "fisher_tv",
+                      lambda h: tup(("F", "F_mu"), h.fisher_tv(ch["lwls"], gp, tau[0], tan_gp, tan_tau, tan_lwl, want_mu=True))),
         "fisher_marg": ({"baseline": True}, "fisher_marg",
                         lambda h: tup(("F", "F_mu"), h.fisher_marg(ch["lwls"], gp, tan_gp, tan_lwl, want_mu=True))),
         "fisher_vel": ({}, "fisher_vel", lambda h: tup(("F",), h.fisher_vel(ch["lwls"], gp, ep, EPOCHS))),
         "info_vel": ({}, "info_vel", lambda h: tup(INFO, h.info_vel(ch["lwls"], gp, ep, EPOCHS, MU))),
         "info_vel-marg": ({"baseline": True}, "info_vel", lambda h: tup(INFO, h.info_vel(ch["lwls"], gp, ep, EPOCHS, MU, marg=True))),
         "loo": ({}, "loo", lambda h: fields(h.loo(ch["lwls"], gp, MU, ep, EPOCHS), LOO)),
+        "loo_tv": ({"times": True}, "loo_tv", lambda h: fields(h.loo_tv(ch["lwls"], gp, tau[0], MU, ep, EPOCHS), LOO)),
         "loo_marg": ({"baseline": True}, "loo_marg", lambda h: fields(h.loo_marg(ch["lwls"], gp, MU, ep, EPOCHS), LOO)),
         "lnlike_marg": ({"baseline": True, "max_batch": B}, "lnlike_marg", lambda h: tup(("lnp",), h.lnlike_marg(lw, gps, MU))),
         "lnlike_marg-want_cov": ({"baseline": True, "max_batch": B}, "lnlike_marg",
