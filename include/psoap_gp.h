@@ -561,6 +561,69 @@ int psoap_chunk_loo_tv(psoap_chunk *h, int c, const double *lwl, const double *g
                        double *ep_resid,
                        double *ep_chi2, double *ep_logp, int32_t *ep_npix);
 
+/* ---- the time-variable kernel under the marginalised continuum ------------------------------
+ * Kt = K_tv + Ht Ht^T: K_tv the time-variable kernel of psoap_chunk_lnlike_tv_grad over the
+ * handle's times (psoap_chunk_set_times), Ht from the handle's baseline
+ * (psoap_chunk_set_baseline).  Three entries, each its marginal twin with tau:
+ *   psoap_chunk_lnlike_marg_tv       psoap_chunk_lnlike_marg with tau (B, c): lnp, parts, beta,
+ *                                    beta_cov, fl_cor with its shapes and NULL rules,
+ *                                    B <= max_batch;
+ *   psoap_chunk_lnlike_marg_tv_grad  psoap_chunk_lnlike_marg_grad with tau (B, c) and grad_tau
+ *                                    (B, c), any B >= 1; lnp and parts have the bits of the
+ *                                    value entry above; grad_gp == NULL asks for the value
+ *                                    only, with the NULL rules of psoap_chunk_lnlike_tv_grad
+ *                                    (grad_tau, grad_lwl and grad_mu NULL too; with grad_gp,
+ *                                    grad_tau is required), and the same bits;
+ *   psoap_chunk_fisher_marg_tv       psoap_chunk_fisher_tv under Kt: tau (c), tangents
+ *                                    (tan_lwl, tan_gp, tan_tau), 1 <= T <= 32.
+ * H does not depend on tau, so every derivative is the time-variable one with
+ * K^-1 -> Kt^-1 = Wi^T Wi - Vt^T Vt and alpha -> alpha_m = Kt^-1 r; in particular, with
+ * Q_m = alpha_m alpha_m^T - Kt^-1,
+ *   d lnp / d tau_c = 1/2 a_c^2 / tau_c^3 sum_ij Q_m,ij e_cij dt_ij^2.
+ * The launches are the marginal entries' with K filled by the time-variable fill; the
+ * gradient's contraction is k_marg_tv_grad_contract (csrc/marg_grad_kernels.hpp: the two K
+ * loops of the marginal contraction, the epilogue of the time-variable one) and its
+ * finishing sums the time-variable ones; the Fisher information forms Kt^-1 as
+ * psoap_chunk_fisher_marg does and then runs the tangent fill, product, contraction,
+ * finishing sums and dot of psoap_chunk_fisher_tv.  One multiply-add more per element in
+ * the fill and the epilogues; the flops are the marginal entries'.  No atomics, every sum
+ * in an order fixed by (N, c, baseline layout, T): a proposal's bits do not depend on the
+ * batch around it, on the grouping or on which optional outputs are asked for; a
+ * subsequence of the tangents gives the bits of the entries it shares.
+ * Bit-identity at tau = inf: with every tau_c = +inf, lnp, parts, beta, beta_cov, fl_cor,
+ * grad_gp, grad_lwl, grad_mu, every entry of fisher and fisher_mu have the bits of
+ * psoap_chunk_lnlike_marg, psoap_chunk_lnlike_marg_grad and psoap_chunk_fisher_marg on the
+ * same handle; grad_tau is exactly 0, and so is a Fisher entry whose tangent has nothing
+ * but dtau.
+ * Conventions: tau_c <= 0 or NaN, a negative hyper-parameter, or a K or an M that does not
+ * factor gives lnp = -inf and NaN in every other output of that proposal (NaN in every
+ * entry of fisher and in fisher_mu), status 0; the other proposals keep their bits.
+ * Refused with a message, in this order: missing arrays; the NULL rules above; c outside
+ * 1 .. 3; B < 1 (the value entry: B outside [1, max_batch]) or T outside 1 .. 32; a call
+ * before psoap_chunk_set_times; an open stream; a handle without a baseline or with a
+ * stale one (psoap_chunk_lnlike_marg's messages).  The plain, _tv and _marg entries keep
+ * their bits, and the _tv entries and psoap_chunk_predict_tv go on refusing a handle with
+ * a baseline: the combination is reached through these three entries only.  Not built
+ * under it: leave-one-out, predict, draws and the mixture; the derivative with respect to
+ * prior_sd is not provided.
+ * Workspace: that of psoap_chunk_lnlike_marg / _marg_grad / _fisher_marg in the same groups
+ * (at most 8 matrices and 1 GiB), plus 3 doubles per matrix of a group for tau and for
+ * grad_tau, one double more per tile record and 2 T c doubles of time-scale tangents and
+ * contractions; psoap_chunk_grad_release, psoap_chunk_marg_release and
+ * psoap_chunk_fisher_release free all of it, the times and the baseline stay with the
+ * handle. */
+int psoap_chunk_lnlike_marg_tv(psoap_chunk *h, int B, int c, const double *lwl, const double *gp,
+                               const double *tau, double mu_GP,
+                               double *lnp, double *parts, double *beta, double *beta_cov, double *fl_cor);
+int psoap_chunk_lnlike_marg_tv_grad(psoap_chunk *h, int B, int c, const double *lwl, const double *gp,
+                                    const double *tau, double mu_GP,
+                                    double *lnp, double *parts, double *grad_gp, double *grad_tau,
+                                    double *grad_lwl, double *grad_mu);
+int psoap_chunk_fisher_marg_tv(psoap_chunk *h, int c, const double *lwl, const double *gp,
+                               const double *tau, int T, const double *tan_lwl,
+                               const double *tan_gp, const double *tan_tau,
+                               double *fisher, double *fisher_mu);
+
 /* ---- component spectra under the marginalised continuum ------------------------------------------
  * psoap_chunk_predict_marg and psoap_chunk_predict_marg_var are psoap_chunk_predict and psoap_chunk_predict_var with
  * Kt = K + Ht Ht^T (the baseline of psoap_chunk_set_baseline) in the place of the data covariance K: arguments, output

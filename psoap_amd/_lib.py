@@ -82,6 +82,11 @@ SIGNATURES = {
     "psoap_chunk_loo_marg": (ctypes.c_int, [_vp, ctypes.c_int, _dp, _dp, ctypes.c_double, _i32p, ctypes.c_int, _dp, _dp, _dp, _dp,
                                             _dp, _dp, _dp, _dp, _i32p]),
     "psoap_chunk_fisher_tv": (ctypes.c_int, [_vp, ctypes.c_int, _dp, _dp, _dp, ctypes.c_int, _dp, _dp, _dp, _dp, _dp]),
+    "psoap_chunk_lnlike_marg_tv": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, ctypes.c_double, _dp, _dp, _dp,
+                                                  _dp, _dp]),
+    "psoap_chunk_lnlike_marg_tv_grad": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, ctypes.c_double, _dp, _dp,
+                                                       _dp, _dp, _dp, _dp]),
+    "psoap_chunk_fisher_marg_tv": (ctypes.c_int, [_vp, ctypes.c_int, _dp, _dp, _dp, ctypes.c_int, _dp, _dp, _dp, _dp, _dp]),
     "psoap_chunk_loo_tv": (ctypes.c_int, [_vp, ctypes.c_int, _dp, _dp, _dp, ctypes.c_double, _i32p, ctypes.c_int, _dp, _dp, _dp,
                                           _dp, _dp, _dp, _dp, _dp, _i32p]),
     "psoap_batch_upload":(ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _dp, _dp, ctypes.c_double]),

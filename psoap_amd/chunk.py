@@ -250,7 +250,7 @@ class ChunkHandle:
         return self._fisher("psoap_chunk_fisher", lwls, gp, tan_gp, tan_lwl, want_mu)
 
     def _fisher(self, entry, lwls, gp, tan_gp, tan_lwl, want_mu, tau=None, tan_tau=None):
-        """the body of ``fisher``, ``fisher_marg`` and ``fisher_tv``: ``entry`` names the library's function, which with ``tau``
+        """the body of ``fisher``, ``fisher_marg``, ``fisher_tv`` and ``fisher_marg_tv``: ``entry`` names the library's function, which with ``tau``
         takes it after ``gp`` and ``tan_tau`` after ``tan_gp``"""
         lwls = as_f64(np.atleast_2d(lwls))
         c = lwls.shape[0]
@@ -433,11 +433,18 @@ class ChunkHandle:
         ``want_beta`` / ``want_cov`` / ``want_flux`` is set; ``lwls`` (B, c, N) with ``gps`` (B, 2c), B <= max_batch -> the same
         with a leading axis of B.  A negative hyper-parameter or a matrix that is not positive definite gives ``-inf`` and
         NaN in every other field."""
+        return self._lnlike_marg("psoap_chunk_lnlike_marg", "lnlike_marg", lwls, gps, mu_GP, want_beta, want_cov, want_flux)
+
+    def _lnlike_marg(self, entry, who, lwls, gps, mu_GP, want_beta, want_cov, want_flux, tau=None):
+        """the body of ``lnlike_marg`` and ``lnlike_marg_tv``: ``entry`` names the library's function, which with ``tau`` takes
+        it after ``gp``"""
         if getattr(self, "_baseline", None) is None:
-            raise _lib.PsoapError("lnlike_marg: call set_baseline first")
+            raise _lib.PsoapError(f"{who}: call set_baseline first")
         ne, order = self._baseline
         q = ne * (order + 1)
         single, B, c, lwls, gps = self._proposals(lwls, gps)
+        taus = None if tau is None else as_f64(np.atleast_2d(as_f64(tau)), (B, c))      # (kept alive over the call)
+        after_gp = () if taus is None else (dptr(taus),)
         more = want_beta or want_cov or want_flux
         lnp = np.empty(B)
         parts = np.empty((B, 4)) if more else None
@@ -445,8 +452,8 @@ class ChunkHandle:
         cov = np.empty((B, q, q)) if want_cov else None
         flc = np.empty((B, self.N)) if want_flux else None
         opt = lambda a: None if a is None else dptr(a)      # noqa: E731
-        check(self._L.psoap_chunk_lnlike_marg(self._h, B, c, dptr(lwls), dptr(gps), float(mu_GP), dptr(lnp), opt(parts),
-                                              opt(beta), opt(cov), opt(flc)), "psoap_chunk_lnlike_marg")
+        check(getattr(self._L, entry)(self._h, B, c, dptr(lwls), dptr(gps), *after_gp, float(mu_GP), dptr(lnp), opt(parts),
+                                      opt(beta), opt(cov), opt(flc)), entry)
         if not more:
             return float(lnp[0]) if single else lnp
         if beta is not None:
@@ -472,6 +479,43 @@ class ChunkHandle:
         if getattr(self, "_baseline", None) is None:
             raise _lib.PsoapError("lnprob_marg_grad: call set_baseline first")
         return self._lnprob_grad("psoap_chunk_lnprob_marg_grad", True, model_id, p_orb, gps, mu_GP, want_vel)
+
+    # -- the time-variable kernel under the baseline (include/psoap_gp.h: psoap_chunk_lnlike_marg_tv) ----------------
+    def lnlike_marg_tv(self, lwls, gps, tau, mu_GP: float = 1.0, want_beta: bool = False, want_cov: bool = False,
+                       want_flux: bool = False):
+        """``lnlike_marg`` under the time-variable kernel of ``lnlike_tv`` (include/psoap_gp.h: psoap_chunk_lnlike_marg_tv;
+        needs ``set_baseline`` and ``set_times``): ``tau`` (c,) or (B, c) beside ``gps``, the other arguments and the return
+        value as ``lnlike_marg``.  With every ``tau = inf`` every field has the bits of ``lnlike_marg``; ``tau <= 0`` or NaN
+        gives ``-inf`` and NaN like a negative hyper-parameter."""
+        return self._lnlike_marg("psoap_chunk_lnlike_marg_tv", "lnlike_marg_tv", lwls, gps, mu_GP, want_beta, want_cov, want_flux,
+                                 tau)
+
+    def lnlike_marg_tv_grad(self, lwls, gps, tau, mu_GP: float = 1.0):
+        """Value and analytic gradient of ``lnlike_marg_tv`` (include/psoap_gp.h: psoap_chunk_lnlike_marg_tv_grad):
+        ``(lnp, grad_gp, grad_tau, grad_lwl, grad_mu)`` with the shapes of ``lnlike_tv_grad``, any B.  ``lnp`` has the bits
+        of ``lnlike_marg_tv``; with every ``tau = inf`` the other four outputs have the bits of ``lnlike_marg_grad`` and
+        ``grad_tau`` is exactly 0.  ``tau <= 0`` or NaN, a negative hyper-parameter or a matrix that does not factor gives
+        ``-inf`` and NaN gradients for that proposal."""
+        if getattr(self, "_baseline", None) is None:
+            raise _lib.PsoapError("lnlike_marg_tv_grad: call set_baseline first")
+        single, B, c, lwls, gps = self._proposals(lwls, gps)
+        taus = as_f64(np.atleast_2d(as_f64(tau)), (B, c))
+        lnp, g_gp, g_tau, g_lwl, g_mu = np.empty(B), np.empty((B, 2 * c)), np.empty((B, c)), np.empty((B, c, self.N)), np.empty(B)
+        check(self._L.psoap_chunk_lnlike_marg_tv_grad(self._h, B, c, dptr(lwls), dptr(gps), dptr(taus), float(mu_GP), dptr(lnp),
+                                                      None, dptr(g_gp), dptr(g_tau), dptr(g_lwl), dptr(g_mu)),
+              "psoap_chunk_lnlike_marg_tv_grad")      # (``parts``: not asked for)
+        if single:
+            return float(lnp[0]), g_gp[0], g_tau[0], g_lwl[0], float(g_mu[0])
+        return lnp, g_gp, g_tau, g_lwl, g_mu
+
+    def fisher_marg_tv(self, lwls, gp, tau, tan_gp, tan_tau=None, tan_lwl=None, want_mu: bool = False):
+        """``fisher_tv`` under the baseline of ``set_baseline`` (include/psoap_gp.h: psoap_chunk_fisher_marg_tv): the same
+        arguments, ``F_st = 1/2 tr(Kt^-1 K_s Kt^-1 K_t)`` with ``Kt = K_tv + H Lambda H^T`` -- the information of the
+        likelihood ``lnlike_marg_tv`` returns.  With every ``tau = inf`` it has the bits of ``fisher_marg``, and a tangent
+        with nothing but a time-scale part gives an exactly-zero row and column."""
+        if getattr(self, "_baseline", None) is None:
+            raise _lib.PsoapError("fisher_marg_tv: call set_baseline first")
+        return self._fisher("psoap_chunk_fisher_marg_tv", lwls, gp, tan_gp, tan_lwl, want_mu, tau, tan_tau)
 
     def marg_release(self):
         """Free the device side of the baseline and the workspace of ``lnlike_marg`` and ``lnlike_marg_grad`` beyond the

@@ -55,6 +55,19 @@ def _chunk_for(fl, sigma):
     return h
 
 
+def _chunk_without_baseline(fl, sigma):
+    """``_chunk_for`` for the time-variable calls that take no baseline: the library's time-variable entries refuse a handle that
+    has one, and a baseline cannot be taken off a handle, so a cached handle on which an earlier call of this module set one
+    is closed and made again (its workspaces go with it; the next call with a baseline sets it again)."""
+    h = _chunk_for(fl, sigma)
+    if getattr(h, "_baseline", None) is None:
+        return h
+    for key in [k for k, v in _handles.items() if v is h]:
+        del _handles[key]
+    h.close()
+    return _chunk_for(fl, sigma)
+
+
 def release_handles():
     """Free every cached device chunk and the predict workspaces."""
     while _handles:
@@ -679,9 +692,11 @@ def optimize_GP(lwls, fl, sigma, gp0, mu_GP=1.0, ftol=1e-10, full_output=False, 
 
 
 # ---- time-variable component spectra (not in the reference) ------------------------------------
-def _timevar(lwls, fl, sigma, gp, tau, times, mu_GP, want_grad):
+def _timevar(lwls, fl, sigma, gp, tau, times, mu_GP, want_grad, baseline=None):
     """the front of ``lnlike_timevar`` and ``lnlike_timevar_grad``: the degenerate input of ``lnlike_grad``, ``tau <= 0`` or NaN
-    like a negative hyper-parameter, the cached handle with ``times - min(times)`` on it"""
+    like a negative hyper-parameter, the cached handle with ``times - min(times)`` on it; with ``baseline`` that baseline on
+    the handle as well and the entries under it (``ChunkHandle.lnlike_marg_tv`` / ``lnlike_marg_tv_grad``)"""
+    base = None if baseline is None else _baseline_args(baseline)
     gp = [float(g) for g in gp]
     lw = np.stack([as_f64(w) for w in np.atleast_2d(lwls)])
     c, N = lw.shape
@@ -699,14 +714,18 @@ def _timevar(lwls, fl, sigma, gp, tau, times, mu_GP, want_grad):
         raise ZeroDivisionError("float division")
     if not _matrix_is_finite(lw, sigma, gp):
         raise ValueError(_NONFINITE)
-    h = _chunk_for(fl, sigma)
+    h = _chunk_for(fl, sigma) if base is not None else _chunk_without_baseline(fl, sigma)
     if not hasattr(h, "lnlike_tv_grad"):
         raise _lib.PsoapError("lnlike_timevar needs the device in this process (PSOAP_GPU_SERVER serves the static likelihood only)")
     t = t - t.min()
     if getattr(h, "_tv_times", None) is None or not np.array_equal(h._tv_times, t):
         h.set_times(t)
         h._tv_times = t
-    res = h.lnlike_tv_grad(lw, gp, tau, mu_GP) if want_grad else (h.lnlike_tv(lw, gp, tau, mu_GP),)
+    if base is None:
+        res = h.lnlike_tv_grad(lw, gp, tau, mu_GP) if want_grad else (h.lnlike_tv(lw, gp, tau, mu_GP),)
+    else:
+        h.set_baseline(*base)      # (every call, as ``_marginal``: the cached handle is shared by this module's callers)
+        res = h.lnlike_marg_tv_grad(lw, gp, tau, mu_GP) if want_grad else (h.lnlike_marg_tv(lw, gp, tau, mu_GP),)
     if not np.isneginf(res[0]) and not (np.all(np.isfinite(np.asarray(fl, dtype=np.float64))) and np.isfinite(mu_GP)):
         raise ValueError(_NONFINITE)
     if not want_grad:
@@ -724,18 +743,31 @@ def lnlike_timevar(lwls, fl, sigma, gp, tau, times, mu_GP=1.0):
     return _timevar(lwls, fl, sigma, gp, tau, times, mu_GP, False)
 
 
-def lnlike_timevar_grad(lwls, fl, sigma, gp, tau, times, mu_GP=1.0):
+def lnlike_timevar_marginal(lwls, fl, sigma, gp, tau, times, baseline, mu_GP=1.0):
+    """``lnlike_timevar`` with a per-epoch continuum integrated out under the same kernel, ``K_tv + H Lambda H^T``
+    (``ChunkHandle.lnlike_marg_tv``).  ``baseline``: the dict of ``optimize_GP`` -- ``x``, ``epoch_index``, ``order``,
+    ``prior_sd`` and optionally ``weight``.  With every ``tau = inf`` this is ``lnlike_marginal``.  (A function of its own:
+    the parameter list of ``lnlike_timevar`` is fixed.)  Calls with and without a baseline on the same ``(fl, sigma)`` may
+    alternate -- the variability statistic with the baseline on and off: the cached handle is made again where a call without
+    one finds a baseline on it."""
+    _baseline_args(baseline)
+    return _timevar(lwls, fl, sigma, gp, tau, times, mu_GP, False, baseline)
+
+
+def lnlike_timevar_grad(lwls, fl, sigma, gp, tau, times, mu_GP=1.0, baseline=None):
     """``(lnp, grad_gp (2c,), grad_tau (c,), grad_lwl (c, N), grad_mu)``: ``lnlike_timevar`` and its analytic derivatives on the
-    device (``ChunkHandle.lnlike_tv_grad``).  ``grad_tau`` is exactly 0 where ``tau = inf``."""
-    return _timevar(lwls, fl, sigma, gp, tau, times, mu_GP, True)
+    device (``ChunkHandle.lnlike_tv_grad``; with ``baseline``, as ``lnlike_timevar_marginal`` takes it, ``lnlike_marg_tv_grad``).
+    ``grad_tau`` is exactly 0 where ``tau = inf``."""
+    return _timevar(lwls, fl, sigma, gp, tau, times, mu_GP, True, baseline)
 
 
-def _timevar_handle(fl, sigma, times, N, who):
-    """the cached handle of ``(fl, sigma)`` with ``times - min(times)`` on it, as ``lnlike_timevar`` leaves it -> (h, min(times))"""
+def _timevar_handle(fl, sigma, times, N, who, baseline=False):
+    """the cached handle of ``(fl, sigma)`` with ``times - min(times)`` on it, as ``lnlike_timevar`` leaves it -> (h, min(times));
+    unless the caller is about to set a ``baseline``, a handle without one (``_chunk_without_baseline``)"""
     t = as_f64(times, (N,))
     if not np.all(np.isfinite(t)):
         raise ValueError(_NONFINITE)
-    h = _chunk_for(fl, sigma)
+    h = _chunk_for(fl, sigma) if baseline else _chunk_without_baseline(fl, sigma)
     if not hasattr(h, "predict_tv"):
         raise _lib.PsoapError(f"{who} needs the device in this process (PSOAP_GPU_SERVER serves the static likelihood only)")
     t0 = t.min()
@@ -770,17 +802,33 @@ def optimize_GP_timevar(lwls, fl, sigma, gp0, tau0, times, free_tau=None, mu_GP=
     or above ``GP_LOWER_BOUND``.  Returns ``(gp, tau)``; with ``full_output`` ``(gp, tau, lnp, lnp_static, result)``:
     the likelihood reached, the likelihood at the same ``gp`` with every ``tau = inf``, and SciPy's result.
     ``lnp - lnp_static`` is the variability statistic: what the time-variable kernel gains over the static one."""
+    return _optimize_timevar(lwls, fl, sigma, gp0, tau0, times, free_tau, mu_GP, ftol, full_output, None)
+
+
+def optimize_GP_timevar_marginal(lwls, fl, sigma, gp0, tau0, times, baseline, free_tau=None, mu_GP=1.0, ftol=1e-10,
+                                 full_output=False):
+    """``optimize_GP_timevar`` under a baseline (the dict of ``optimize_GP``): the objective is the likelihood with that
+    per-epoch continuum integrated out (``lnlike_timevar_grad(..., baseline=...)``), and ``lnp_static`` the marginal
+    likelihood at ``tau = inf`` -- the statistic compares like with like, and a continuum error from epoch to epoch is no
+    longer there for a finite ``tau`` to absorb.  (A function of its own: the parameter list of ``optimize_GP_timevar`` is
+    fixed.)  ``timevar_laplace(..., baseline=...)`` gives the error bars of the fit."""
+    _baseline_args(baseline)
+    return _optimize_timevar(lwls, fl, sigma, gp0, tau0, times, free_tau, mu_GP, ftol, full_output, baseline)
+
+
+def _optimize_timevar(lwls, fl, sigma, gp0, tau0, times, free_tau, mu_GP, ftol, full_output, baseline):
+    """the body of ``optimize_GP_timevar`` (``baseline`` None) and ``optimize_GP_timevar_marginal``"""
     lw = np.stack([as_f64(w) for w in np.atleast_2d(lwls)])
     c = lw.shape[0]
 
     def value_grad(gp, tau):
-        lnp, g_gp, g_tau, _g_lwl, _g_mu = lnlike_timevar_grad(lw, fl, sigma, gp, tau, times, mu_GP)
+        lnp, g_gp, g_tau, _g_lwl, _g_mu = lnlike_timevar_grad(lw, fl, sigma, gp, tau, times, mu_GP, baseline)
         return lnp, g_gp, g_tau
 
     gp, tau, res = _fit_timevar(value_grad, c, gp0, tau0, free_tau, ftol)
     if not full_output:
         return gp, tau
-    lnp_static = lnlike_timevar(lw, fl, sigma, gp, np.full(c, np.inf), times, mu_GP)
+    lnp_static = _timevar(lw, fl, sigma, gp, np.full(c, np.inf), times, mu_GP, False, baseline)
     return gp, tau, -float(res["fun"]), float(lnp_static), res
 
 
@@ -826,13 +874,16 @@ def _timevar_front(lwls, gp, tau):
     return lw, gp, tau, any(g < 0.0 for g in gp) or not np.all(tau > 0.0)
 
 
-def fisher_information_timevar(lwls, fl, sigma, gp, tau, times):
+def fisher_information_timevar(lwls, fl, sigma, gp, tau, times, baseline=None):
     """The ``(3c, 3c)`` Fisher information of ``(amp_0, l_0, ..., tau_0, ..., tau_{c-1})`` under the time-variable kernel of
     ``lnlike_timevar``, evaluated on the device (``ChunkHandle.fisher_tv`` with unit tangents, the cached handle with
     ``times - min(times)`` on it): what ``fisher_information`` is for the static kernel, with the time scales and their
     correlations with the amplitudes and length scales.  The row and column of a component with ``tau = inf`` are exactly
     zero.  Degenerate input follows ``lnlike_timevar``: a negative hyper-parameter, a ``tau <= 0`` or NaN or a matrix that is
-    not positive definite gives NaN in every entry."""
+    not positive definite gives NaN in every entry.  ``baseline`` (the dict of ``optimize_GP``): the information of
+    ``lnlike_timevar_marginal``, under ``K_tv + H Lambda H^T`` (``ChunkHandle.fisher_marg_tv``) -- an error bar on
+    ``tau`` from it carries the continuum's uncertainty."""
+    base = None if baseline is None else _baseline_args(baseline)
     lw, gp, tau, degenerate = _timevar_front(lwls, gp, tau)
     c, N = lw.shape
     t = as_f64(times, (N,))
@@ -844,9 +895,12 @@ def fisher_information_timevar(lwls, fl, sigma, gp, tau, times):
         raise ZeroDivisionError("float division")
     if not _matrix_is_finite(lw, sigma, gp):
         raise ValueError(_NONFINITE)
-    h, _t0 = _timevar_handle(fl, sigma, t, N, "fisher_information_timevar")
+    h, _t0 = _timevar_handle(fl, sigma, t, N, "fisher_information_timevar", base is not None)
     eye = np.eye(3 * c)
-    return h.fisher_tv(lw, gp, tau, eye[:, :2 * c], eye[:, 2 * c:])
+    if base is None:
+        return h.fisher_tv(lw, gp, tau, eye[:, :2 * c], eye[:, 2 * c:])
+    h.set_baseline(*base)      # (every call, as ``_marginal``)
+    return h.fisher_marg_tv(lw, gp, tau, eye[:, :2 * c], eye[:, 2 * c:])
 
 
 def _laplace_from_fisher(F, gp, tau, free):
@@ -875,16 +929,17 @@ def _laplace_from_fisher(F, gp, tau, free):
     return cov_log, sd[:2 * c], sd_tau
 
 
-def timevar_laplace(lwls, fl, sigma, gp, tau, times, free_tau=None):
+def timevar_laplace(lwls, fl, sigma, gp, tau, times, free_tau=None, baseline=None):
     """The Laplace covariance of an ``optimize_GP_timevar`` fit at ``(gp, tau)``, in the parameters ``_fit_timevar`` fits in,
     ``(log gp, log tau[free])``: ``F_log = diag(theta) F diag(theta)`` of ``fisher_information_timevar`` restricted to the free
     parameters, inverted.  ``free_tau`` (c,) of booleans defaults as in ``optimize_GP_timevar``: every finite ``tau``.
     Returns ``(cov_log, sd_gp (2c,), sd_tau (c,))``: the covariance, and the standard deviations in the parameters' own units
     (``theta`` times that of ``log theta``), ``nan`` for a ``tau`` that is not free.  ``LinAlgError`` where ``F_log`` is
-    singular -- also for the NaN of degenerate input."""
+    singular -- also for the NaN of degenerate input.  ``baseline``: as ``fisher_information_timevar`` takes it, for a fit
+    made with ``optimize_GP_timevar_marginal``."""
     tau = as_f64(np.atleast_1d(as_f64(tau)))
     free = np.isfinite(tau) if free_tau is None else np.asarray(free_tau, dtype=bool).reshape(tau.shape)
-    return _laplace_from_fisher(fisher_information_timevar(lwls, fl, sigma, gp, tau, times), gp, tau, free)
+    return _laplace_from_fisher(fisher_information_timevar(lwls, fl, sigma, gp, tau, times, baseline), gp, tau, free)
 
 
 def loo_timevar(lwls, fl, sigma, gp, tau, times, mu_GP=1.0, epoch_index=None):

@@ -5,9 +5,10 @@
 
 // The gradient of the likelihood (grad_kernels.hpp).  Group after group of matrices through factor_group, then the contraction
 // and the finishing sums -- plain, or with `marg` under the handle's baseline (marg_grad_kernels.hpp).  The ln-wavelengths come
-// from the host (lwl) or, with lwl == nullptr, from the orbits p_orb of `model` (orbit_front, orbit_back).  With `tau` (B, c;
-// plain only) K is the time-variable kernel over the handle's times: the TV fill, contraction and finishing sums, and grad_tau
-// beside grad_gp.  `contract` false is the value only: no contraction, no finishing sums, no gradient touched.
+// from the host (lwl) or, with lwl == nullptr, from the orbits p_orb of `model` (orbit_front, orbit_back).  With `tau` (B, c)
+// K is the time-variable kernel over the handle's times: the TV fill, contraction and finishing sums, and grad_tau beside
+// grad_gp -- plain, or with `marg` on Kt = K_tv + Ht Ht^T (k_marg_tv_grad_contract).  `contract` false is the value only: no
+// contraction, no finishing sums, no gradient touched.
 static int grad_run(psoap_chunk* h, bool marg, int B, int c, const double* lwl, int model, const double* p_orb,
                     const double* gp, const double* tau, double mu_GP, double* lnp, double* parts, double* grad_gp,
                     double* grad_tau, double* grad_lwl, double* grad_mu, double* grad_orb, double* grad_vel, bool contract)
@@ -37,7 +38,13 @@ static int grad_run(psoap_chunk* h, bool marg, int B, int c, const double* lwl, 
         if (contract) {
             if (int rc = prof_launch(h, s, PSOAP_K_GRAD, TILE_FLOPS * tile_units(P, fac.Q) * nb, 0.0, [&] {
                     with_components(c, [&](auto nc) {
-                        if (marg)
+                        if (marg && tv)
+                            hipLaunchKernelGGL(k_marg_tv_grad_contract<nc()>, dim3(ntiles, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES,
+                                               s, (const double*)w.A.p, mstride, ld, N, Npad, P, (const double*)w.Lwl.p,
+                                               (const double*)h->dTimes.p, (const double*)w.Gp.p, (const double*)w.Tau.p,
+                                               (const double*)w.Alpha.p, w.Part.p, (const double*)fac.Vt->p, fac.m_stride, fac.ldm,
+                                               fac.S);
+                        else if (marg)
                             hipLaunchKernelGGL(k_marg_grad_contract<nc()>, dim3(ntiles, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s,
                                                (const double*)w.A.p, mstride, ld, N, Npad, P, (const double*)w.Lwl.p,
                                                (const double*)w.Gp.p, (const double*)w.Alpha.p, w.Part.p, (const double*)fac.Vt->p,
@@ -118,9 +125,9 @@ static int inverse_bracket(psoap_chunk* h, hipStream_t s, const Factored& fac, F
 // The Fisher information of the likelihood (fisher_kernels.hpp).  One matrix through the gradient's workspace and
 // factorisation, then K^-1 and, tangent after tangent, K_t, Z = K_t K^-1 and the contraction of G_t = 1/2 (K^-1 Z + Z^T K^-1).
 // `marg`: under Kt = K + Ht Ht^T (marg_fisher_kernels.hpp) -- the marginal gradient's factorisation, Kt^-1, the same tangents.
-// With `tau` (c; plain only, as grad_run's) K is the time-variable kernel over the handle's times and a tangent has a
+// With `tau` (c, as grad_run's; also with `marg`) K is the time-variable kernel over the handle's times and a tangent has a
 // time-scale part, tan_tau (T, c; nullptr: zeros): the TV fill, tangent fill, contraction and finishing sums, and the dot
-// with its time-scale terms.  The caller has made the checks of fisher_tv_check.
+// with its time-scale terms.  The caller has made the checks of fisher_tv_check (with `marg`: of marg_tv_check).
 static int fisher_run(psoap_chunk* h, const char* who, bool marg, int c, const double* lwl, const double* gp, const double* tau,
                       int T, const double* tan_lwl, const double* tan_gp, const double* tan_tau, double* fisher,
                       double* fisher_mu)
@@ -506,9 +513,11 @@ static int loo_run(psoap_chunk* h, const char* who, bool marg, int c, const doub
 // The likelihood with a per-epoch continuum polynomial integrated out (marg_kernels.hpp).  Group after group of matrices
 // through the gradient's workspace as [K | Ht] (ld = Npad + 128 Q), then the Gram matrices through the staged kernels once
 // more.  This K sweep stays apart from marg_grad_factor's [K | I | Ht]: the value alone has no appended identity to pay for.
-static int marg_run(psoap_chunk* h, int B, int c, const double* lwl, const double* gp, double mu_GP, double* lnp, double* parts,
-                    double* beta, double* beta_cov, double* fl_cor)
+// With `tau` (B, c) K is the time-variable kernel over the handle's times: the fill alone knows.
+static int marg_run(psoap_chunk* h, int B, int c, const double* lwl, const double* gp, const double* tau, double mu_GP, double* lnp,
+                    double* parts, double* beta, double* beta_cov, double* fl_cor)
 {
+    const bool tv = tau != nullptr;
     DEVICE_SCOPE(h->device);
     if (int rc = enter_device(h->device)) return rc;
     const MargPlan& pl = h->marg.plan;
@@ -521,7 +530,7 @@ static int marg_run(psoap_chunk* h, int B, int c, const double* lwl, const doubl
     if (!h->mws) h->mws.reset(new MargWs());
     GradWs& w = *h->gws;
     MargWs& m = *h->mws;
-    if (int rc = grad_ws_need(h, w, G, mstride, false, false)) return rc;
+    if (int rc = grad_ws_need(h, w, G, mstride, false, false, 0, 0, tv)) return rc;
     HIP_TRY(m.M.need((size_t)G * m_stride));
     if (int rc = marg_ws_need(h, m, G, want_cov)) return rc;
     hipStream_t s = h->streams[0];
@@ -533,8 +542,9 @@ static int marg_run(psoap_chunk* h, int B, int c, const double* lwl, const doubl
         const int nb = (B - b0 < G) ? B - b0 : G;
         HIP_TRY(hipMemcpyAsync(w.Lwl, lwl + (size_t)b0 * c * N, sizeof(double) * (size_t)nb * c * N, hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemcpyAsync(w.Gp, gp + (size_t)b0 * 2 * c, sizeof(double) * (size_t)nb * 2 * c, hipMemcpyHostToDevice, s));
+        if (tv) HIP_TRY(hipMemcpyAsync(w.Tau, tau + (size_t)b0 * c, sizeof(double) * (size_t)nb * c, hipMemcpyHostToDevice, s));
         if (int rc = prof_launch(h, s, PSOAP_K_FILL, 0.0, (double)nb * 12.0 * N * (N + 1.0), [&] {
-                launch_grad_fill(h, w, s, nb, c, mstride, ld);
+                launch_grad_fill(h, w, s, nb, c, mstride, ld, tv);
                 hipLaunchKernelGGL(k_marg_load, dim3(Q * P, nb), dim3(256), 0, s, w.A.p, mstride, ld, Npad, P, (const double*)m.Ht.p,
                                    ldh, tab);
             })) return rc;
@@ -591,9 +601,10 @@ static int marg_run(psoap_chunk* h, int B, int c, const double* lwl, const doubl
         HIP_TRY(hipStreamSynchronize(s));       // the next group reuses the workspace and the caller's arrays are pageable
     }
     if (collect_timings(h)) return 1;
-    // the conventions: a negative hyper-parameter, a K that is not positive definite or an M that fails to factor -> -inf only
+    // the conventions: a negative hyper-parameter, a tau that is no time scale, a K that is not positive definite or an M that
+    // fails to factor -> -inf only
     for (int b = 0; b < B; ++b) {
-        if (!values_out(out.data(), 5, b, proposal_refused(gp, c, b), lnp, parts)) continue;
+        if (!values_out(out.data(), 5, b, proposal_refused(gp, c, b) || (tv && tau_refused(tau, c, b)), lnp, parts)) continue;
         fill_nan(beta, b, q);
         fill_nan(beta_cov, b, (size_t)q * q);
         fill_nan(fl_cor, b, N);

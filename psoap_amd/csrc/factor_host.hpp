@@ -331,7 +331,7 @@ static void launch_marg_finish(const psoap_chunk* h, const GradWs& w, MargWs& m,
 // [K | I | Ht] and [M | Xt] (marg_grad_plan.hpp): what grad_run, fisher_run and loo_run read instead of asking which.
 struct Factored {
     bool marg;
-    bool tv;                     // K under the time-variable kernel (fill_kernels.hpp; plain only): the fill reads w.Tau
+    bool tv;                     // K under the time-variable kernel (fill_kernels.hpp), plain or marginal: the fill reads w.Tau
     int G;                       // matrices per group
     int ld;                      // doubles per row of a matrix in w.A, mstride from one matrix to the next
     size_t mstride;
@@ -348,6 +348,7 @@ struct Factored {
 // The staged factorisation of [K | I | Ht] (marg_grad_kernels.hpp, marg_grad_plan.hpp) and of [M | Xt] for the nb matrices
 // whose grids and hyper-parameters are in w.Lwl and w.Gp.  Afterwards the I block holds Wi = U^-T, the appended block of mg.Mx
 // holds Vt = U_M^-T Wh^T Wi, m.Out the value and its parts with the bits of marg_run, mg.Zt = z - Wh g and w.Alpha = alpha_m.
+// Under fac.tv K is the time-variable kernel (the fill reads the handle's times and w.Tau); nothing behind the fill knows.
 static int marg_grad_factor(psoap_chunk* h, const Factored& fac, hipStream_t s, int nb, int c, double mu_GP)
 {
     GradWs& w = *h->gws;
@@ -361,7 +362,7 @@ static int marg_grad_factor(psoap_chunk* h, const Factored& fac, hipStream_t s, 
     const int* tab = m.Tab.p;
     double* Ah = w.A.p + Npad;          // what the kernels of marg_kernels.hpp take for [K | Ht]: Ht one block further right
     if (int rc = prof_launch(h, s, PSOAP_K_FILL, 0.0, (double)nb * 12.0 * N * (N + 1.0), [&] {
-            launch_grad_fill(h, w, s, nb, c, mstride, ld);
+            launch_grad_fill(h, w, s, nb, c, mstride, ld, fac.tv);
             hipLaunchKernelGGL(k_grad_init, dim3(ntiles, nb), dim3(256), 0, s, w.A.p, mstride, ld, Npad, P);
             hipLaunchKernelGGL(k_marg_load, dim3(Q * P, nb), dim3(256), 0, s, Ah, mstride, ld, Npad, P, (const double*)m.Ht.p, ldh,
                                tab);

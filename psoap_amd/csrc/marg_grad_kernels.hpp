@@ -25,6 +25,9 @@
 //   k_grad_alpha_partial / _finish   alpha_m, unchanged
 //   k_marg_grad_contract<C>      k_grad_contract<C> with a second K loop of depth q' that takes Vt_ti^T Vt_tj off the same
 //                                accumulators; the epilogue is grad_contract_epilogue
+//   k_marg_tv_grad_contract<C>   the same two K loops under the time-variable kernel of fill_kernels.hpp: the epilogue is
+//                                grad_contract_epilogue<C, true> with the handle's times and tau, the record GradTile<true>
+//                                (k_tv_grad_finish adds up dlnL/dtau); H does not depend on tau, so Q -> Q_m is all there is
 //   k_grad_finish                unchanged
 // fp64 throughout, no atomics, every sum in an order fixed by (N, c, baseline layout).
 //
@@ -120,6 +123,7 @@ __global__ __launch_bounds__(256) void k_marg_grad_resid(const double* __restric
 // k_grad_contract<C> on Kt: after G = Wi_ti^T Wi_tj a second K loop of depth 128 Q takes Vt_ti^T Vt_tj off the same
 // accumulators (the MFMA only adds: the tile changes sign around the loop, which is exact), and the epilogue sees the tile
 // of Kt^-1.  Vt: the appended block of [M | Xt] after its factorisation.  grid (P (P + 1) / 2, B)
+// (k_marg_tv_grad_contract<C> below repeats these lines up to the epilogue call: a change here is a change there.)
 template <int C>
 __global__ __launch_bounds__(GEMM_THREADS, 2) void k_marg_grad_contract(const double* __restrict__ Abase, size_t mat_stride,
                                                                        int ld, int N, int Npad, int P,
@@ -150,6 +154,43 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void k_marg_grad_contract(const do
     grad_contract_epilogue<C>(t, b, ti, tj, (int)blockIdx.x, N, Npad, P, lwl, gp, alpha, part);
 }
 
+// k_marg_grad_contract<C> on Kt = K_tv + Ht Ht^T (psoap_chunk_lnlike_marg_tv_grad): the same two K loops -- the products do not
+// know how K was filled -- then grad_contract_epilogue<C, true> with the handle's times and tau (B, C): the argument formed as
+// the TV fill forms it, the sum for dlnL/dtau, the GradTile<true> record k_tv_grad_finish reads.  A kernel of its own beside
+// the static one, not one body for both: behind a shared inlined body k_marg_grad_contract<C> came out with other
+// instructions than it has alone (profiles/marg_timevar.md; k_fill_sym did the same, profiles/timevar_fold.md).
+template <int C>
+__global__ __launch_bounds__(GEMM_THREADS, 2) void k_marg_tv_grad_contract(const double* __restrict__ Abase, size_t mat_stride,
+                                                                          int ld, int N, int Npad, int P,
+                                                                          const double* __restrict__ lwl,
+                                                                          const double* __restrict__ times,
+                                                                          const double* __restrict__ gp,
+                                                                          const double* __restrict__ tau,
+                                                                          const double* __restrict__ alpha,
+                                                                          double* __restrict__ part,
+                                                                          const double* __restrict__ Mbase, size_t m_stride,
+                                                                          int ldm, int S)
+{
+    const int b = blockIdx.y;
+    int ti, tj;
+    decode_upper(blockIdx.x, P, ti, tj);
+    const double* W = Abase + (size_t)b * mat_stride + Npad + (size_t)NB * tj * ld;
+    Tile t;
+    t.zero();
+    tile_gemm_tn(t, W + NB * ti, (size_t)ld, W + NB * tj, (size_t)ld, Npad - NB * tj, ti == tj);
+#pragma unroll
+    for (int m = 0; m < 4; ++m)
+#pragma unroll
+        for (int n = 0; n < 4; ++n) t.acc[m][n] = -t.acc[m][n];
+    const double* Vt = Mbase + (size_t)b * m_stride + S;
+    tile_gemm_tn(t, Vt + NB * ti, (size_t)ldm, Vt + NB * tj, (size_t)ldm, S, ti == tj);
+#pragma unroll
+    for (int m = 0; m < 4; ++m)
+#pragma unroll
+        for (int n = 0; n < 4; ++n) t.acc[m][n] = -t.acc[m][n];
+    grad_contract_epilogue<C, true>(t, b, ti, tj, (int)blockIdx.x, N, Npad, P, lwl, gp, alpha, part, times, tau);
+}
+
 inline hipError_t marg_grad_configure_kernels()
 {
     const int lds = (int)GEMM_LDS_BYTES;
@@ -163,6 +204,12 @@ inline hipError_t marg_grad_configure_kernels()
         e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_marg_grad_contract<2>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e == hipSuccess)
         e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_marg_grad_contract<3>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_marg_tv_grad_contract<1>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_marg_tv_grad_contract<2>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_marg_tv_grad_contract<3>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     return e;
 }
 

@@ -71,6 +71,38 @@ inline const char* marg_grad_check(int B, int c, bool have_baseline, bool stale_
     return nullptr;
 }
 
+// ---- the time-variable kernel under the baseline (psoap_chunk_lnlike_marg_tv, _marg_tv_grad, psoap_chunk_fisher_marg_tv) ----
+// What the three entries are called with, as far as a refusal can depend on it: no pointer is read.
+enum class MargTvEntry { Value, Grad, Fisher };
+struct MargTvCall {
+    bool arrays;                          // the required arrays are there (Grad: grad_gp is not one of them)
+    bool grad_gp, grad_tau, grad_rest;    // Grad: grad_gp, grad_tau, and grad_lwl or grad_mu, are there
+    int B, c, T;                          // Value, Grad: B;  Fisher: T
+    int max_batch, max_T;                 // Value: B <= max_batch;  Fisher: T <= max_T (FISHER_MAX_T of fisher_kernels.hpp)
+    bool have_times, open_stream, have_baseline, stale_weight;
+};
+
+// -> nullptr, or why a call is refused, in this order: the arrays; (Grad) the NULL rules of psoap_chunk_lnlike_tv_grad; c;
+// B or T; the handle's state as the time-variable entries ask for it -- times set, no open stream -- and then as the marginal
+// entries do, with the messages of psoap_chunk_lnlike_marg: a baseline, and not a stale one.  A tau that is no time scale is
+// not a refusal: like a negative hyper-parameter it gives -inf / NaN, after the call.  The caller puts the entry's name in front.
+inline const char* marg_tv_check(MargTvEntry entry, const MargTvCall& a)
+{
+    if (!a.arrays) return "bad arguments";
+    if (entry == MargTvEntry::Grad) {
+        if (!a.grad_gp && (a.grad_tau || a.grad_rest))
+            return "grad_gp == NULL asks for the value only: grad_tau, grad_lwl and grad_mu must be NULL too";
+        if (a.grad_gp && !a.grad_tau) return "grad_tau goes with grad_gp";
+    }
+    if (a.c < 1 || a.c > 3) return "number of components must be 1, 2 or 3";
+    if (entry == MargTvEntry::Value && (a.B < 1 || a.B > a.max_batch)) return "batch size outside [1, max_batch]";
+    if (entry == MargTvEntry::Grad && a.B < 1) return "B must be at least 1";
+    if (entry == MargTvEntry::Fisher && (a.T < 1 || a.T > a.max_T)) return "the number of tangents must be between 1 and 32";
+    if (!a.have_times) return "call psoap_chunk_set_times first";
+    if (a.open_stream) return "the handle has an open stream (psoap_stream_close first)";
+    return marg_grad_check(1, a.c, a.have_baseline, a.stale_weight);
+}
+
 inline void marg_grad_plan(const MargPlan& pl, MargGradPlan& out)
 {
     out = MargGradPlan();

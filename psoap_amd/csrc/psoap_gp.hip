@@ -2316,7 +2316,7 @@ extern "C" int psoap_chunk_lnlike_marg(psoap_chunk* h, int B, int c, const doubl
     if (h->marg.stale_weight)
         FAIL("psoap_chunk_lnlike_marg: psoap_chunk_set_data changed the data the baseline's weights were given for "
              "(psoap_chunk_set_baseline again)");
-    return marg_run(h, B, c, lwl, gp, mu_GP, lnp, parts, beta, beta_cov, fl_cor);
+    return marg_run(h, B, c, lwl, gp, nullptr, mu_GP, lnp, parts, beta, beta_cov, fl_cor);
 }
 
 // ---- gradient of that likelihood (marg_grad_kernels.hpp): grad_run with `marg` ---------------------------
@@ -2341,6 +2341,46 @@ extern "C" int psoap_chunk_lnprob_marg_grad(psoap_chunk* h, int B, int model, co
     if (int rc = analysis_refused(h, "psoap_chunk_lnprob_marg_grad", true, B, orbit_n_components(model))) return rc;
     return grad_run(h, true, B, orbit_n_components(model), nullptr, model, p_orb, gp, nullptr, mu_GP, lnp, nullptr, grad_gp,
                     nullptr, nullptr, grad_mu, grad_orb, grad_vel, true);
+}
+
+// ---- the time-variable kernel under the baseline: Kt = K_tv + Ht Ht^T (marg_grad_kernels.hpp: k_marg_tv_grad_contract) ------
+// The runs are those of the marginal entries with `tau`; the checks are marg_tv_check's (marg_grad_plan.hpp).  The handle's state
+// as that function is to see it:
+static MargTvCall marg_tv_call(const psoap_chunk* h, bool arrays, int B, int c, int T)
+{
+    return MargTvCall{arrays, false, false, false, B, c, T, h->max_batch, FISHER_MAX_T, h->dTimes.p != nullptr, h->stream.open,
+                      h->marg.valid, h->marg.stale_weight};
+}
+
+extern "C" int psoap_chunk_lnlike_marg_tv(psoap_chunk* h, int B, int c, const double* lwl, const double* gp, const double* tau,
+                                          double mu_GP, double* lnp, double* parts, double* beta, double* beta_cov, double* fl_cor)
+{
+    if (!h) FAIL("psoap_chunk_lnlike_marg_tv: bad arguments");
+    if (const char* why = marg_tv_check(MargTvEntry::Value, marg_tv_call(h, lwl && gp && tau && lnp, B, c, 0)))
+        FAIL(std::string("psoap_chunk_lnlike_marg_tv: ") + why);
+    return marg_run(h, B, c, lwl, gp, tau, mu_GP, lnp, parts, beta, beta_cov, fl_cor);
+}
+
+extern "C" int psoap_chunk_lnlike_marg_tv_grad(psoap_chunk* h, int B, int c, const double* lwl, const double* gp, const double* tau,
+                                               double mu_GP, double* lnp, double* parts, double* grad_gp, double* grad_tau,
+                                               double* grad_lwl, double* grad_mu)
+{
+    if (!h) FAIL("psoap_chunk_lnlike_marg_tv_grad: bad arguments");
+    MargTvCall call = marg_tv_call(h, lwl && gp && tau && lnp, B, c, 0);
+    call.grad_gp = grad_gp != nullptr, call.grad_tau = grad_tau != nullptr, call.grad_rest = grad_lwl || grad_mu;
+    if (const char* why = marg_tv_check(MargTvEntry::Grad, call)) FAIL(std::string("psoap_chunk_lnlike_marg_tv_grad: ") + why);
+    return grad_run(h, true, B, c, lwl, -1, nullptr, gp, tau, mu_GP, lnp, parts, grad_gp, grad_tau, grad_lwl, grad_mu, nullptr,
+                    nullptr, grad_gp != nullptr);
+}
+
+extern "C" int psoap_chunk_fisher_marg_tv(psoap_chunk* h, int c, const double* lwl, const double* gp, const double* tau, int T,
+                                          const double* tan_lwl, const double* tan_gp, const double* tan_tau, double* fisher,
+                                          double* fisher_mu)
+{
+    if (!h) FAIL("psoap_chunk_fisher_marg_tv: bad arguments");
+    if (const char* why = marg_tv_check(MargTvEntry::Fisher, marg_tv_call(h, lwl && gp && tau && tan_gp && fisher, 1, c, T)))
+        FAIL(std::string("psoap_chunk_fisher_marg_tv: ") + why);
+    return fisher_run(h, "psoap_chunk_fisher_marg_tv", true, c, lwl, gp, tau, T, tan_lwl, tan_gp, tan_tau, fisher, fisher_mu);
 }
 
 // frees the device side of the baseline and the workspace; the baseline itself stays set (the next call builds Ht again)
