@@ -624,6 +624,24 @@ int psoap_chunk_fisher_marg_tv(psoap_chunk *h, int c, const double *lwl, const d
                                const double *tan_gp, const double *tan_tau,
                                double *fisher, double *fisher_mu);
 
+/* ---- lnprob(p) under the time-variable kernel ---------------------------------------------------
+ * psoap_chunk_lnprob_grad and psoap_chunk_lnprob_marg_grad with tau (B, c) after gp and
+ * grad_tau (B, c) after grad_gp: the same orbit front end (Kepler solve, Jacobian, Doppler shift
+ * on the device), the gradient run of psoap_chunk_lnlike_tv_grad / _marg_tv_grad, the epoch fold
+ * and the Jacobian contraction.  Needs psoap_chunk_set_grid, _set_dates and _set_times; the
+ * _marg_ entry a baseline, which the plain entry refuses.  NULL rules as
+ * psoap_chunk_lnlike_tv_grad: grad_gp == NULL asks for the value only (every other gradient
+ * NULL too); grad_orb and grad_tau go with grad_gp; grad_vel and grad_mu are optional.
+ * A faster-than-light orbit, a negative hyper-parameter, a tau that is no time scale or a
+ * matrix that does not factor gives -inf and NaN gradients for that proposal.  With every
+ * tau = +inf the outputs have the bits of the entries without tau and grad_tau is exactly 0. */
+int psoap_chunk_lnprob_tv_grad(psoap_chunk *h, int B, int model, const double *p_orb, const double *gp,
+                               const double *tau, double mu_GP, double *lnp, double *grad_orb,
+                               double *grad_gp, double *grad_tau, double *grad_vel, double *grad_mu);
+int psoap_chunk_lnprob_marg_tv_grad(psoap_chunk *h, int B, int model, const double *p_orb, const double *gp,
+                                    const double *tau, double mu_GP, double *lnp, double *grad_orb,
+                                    double *grad_gp, double *grad_tau, double *grad_mu, double *grad_vel);
+
 /* ---- component spectra under the marginalised continuum ------------------------------------------
  * psoap_chunk_predict_marg and psoap_chunk_predict_marg_var are psoap_chunk_predict and psoap_chunk_predict_var with
  * Kt = K + Ht Ht^T (the baseline of psoap_chunk_set_baseline) in the place of the data covariance K: arguments, output
@@ -717,6 +735,21 @@ int psoap_batch_upload_orbits(psoap_chunk *h, int B, int model, const double *p_
  * (psoap/orbit.py:95-115,148-170,301-320,394-417,463-487): vel_out (B, c, n_dates) km/s. */
 int psoap_orbit_velocities(int device, int model, int B, const double *p_orb, int n_dates, const double *dates,
                            double *vel_out);
+/* Time scales for the PENDING upload (whichever of the three uploads made it): tau (B, c) in days, the
+ * tau_c of psoap_chunk_lnlike_tv_grad, over the times of psoap_chunk_set_times.  B and c must be the
+ * upload's.  The copy is queued on the upload's stream behind it (no host round trip: the upload stays
+ * asynchronous); the next upload to that slot clears the time scales.  psoap_batch_eval on a slot that
+ * carries them always takes the staged path, whatever psoap_chunk_set_mode says -- the persistent kernel
+ * has no temporal factor -- with the time-variable fill; it is not counted as a staged_policy event.
+ * tau_c <= 0 or NaN gives -inf for that proposal alone, flagged on the device with the fill (the others
+ * keep their bits); tau_c = +inf is the static model, and with every tau = +inf the results have the bits
+ * of the same upload evaluated without this call under psoap_chunk_set_mode(h, 0).  A proposal's bits
+ * depend neither on B nor on its position in the batch nor on the number of stream groups.
+ * Refused: no pending upload, another B or c, no times, an open stream, a handle with a baseline (the
+ * value under a baseline goes through psoap_chunk_lnlike_marg_tv).  psoap_group_eval and
+ * psoap_stream_open refuse a handle while the slot its next evaluation would read -- the pending one
+ * if there is one, else the active one -- carries time scales. */
+int psoap_batch_set_tau(psoap_chunk *h, int B, int c, const double *tau);
 int psoap_batch_eval(psoap_chunk *h);
 int psoap_batch_fetch(psoap_chunk *h, double *out);
 int psoap_chunk_sync(psoap_chunk *h);

@@ -89,6 +89,11 @@ SIGNATURES = {
     "psoap_chunk_fisher_marg_tv": (ctypes.c_int, [_vp, ctypes.c_int, _dp, _dp, _dp, ctypes.c_int, _dp, _dp, _dp, _dp, _dp]),
     "psoap_chunk_loo_tv": (ctypes.c_int, [_vp, ctypes.c_int, _dp, _dp, _dp, ctypes.c_double, _i32p, ctypes.c_int, _dp, _dp, _dp,
                                           _dp, _dp, _dp, _dp, _dp, _i32p]),
+    "psoap_chunk_lnprob_tv_grad": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, ctypes.c_double, _dp, _dp, _dp,
+                                                  _dp, _dp, _dp]),
+    "psoap_chunk_lnprob_marg_tv_grad": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, ctypes.c_double, _dp, _dp,
+                                                       _dp, _dp, _dp, _dp]),
+    "psoap_batch_set_tau": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _dp]),
     "psoap_batch_upload":(ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _dp, _dp, ctypes.c_double]),
     "psoap_batch_upload_velocities": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _dp, _dp, ctypes.c_double]),
     "psoap_chunk_set_dates": (ctypes.c_int, [_vp, _dp, ctypes.c_int]),

@@ -173,16 +173,22 @@ class ChunkHandle:
             return float(lnp[0]), g_gp[0], g_lwl[0], float(g_mu[0])
         return lnp, g_gp, g_lwl, g_mu
 
-    def _lnprob_grad(self, entry, vel_last, model_id, p_orb, gps, mu_GP, want_vel):
-        """the body of ``lnprob_grad`` and ``lnprob_marg_grad``: ``entry`` names the library's function, which takes
-        ``grad_vel`` after ``grad_mu`` (``vel_last``) or before it"""
+    def _lnprob_grad(self, entry, vel_last, model_id, p_orb, gps, mu_GP, want_vel, tau=None):
+        """the body of ``lnprob_grad``, ``lnprob_marg_grad`` and their ``_tv`` forms: ``entry`` names the library's function,
+        which takes ``grad_vel`` after ``grad_mu`` (``vel_last``) or before it and, with ``tau``, the time scales after ``gps``
+        and ``grad_tau`` after ``grad_gp`` (returned there as well)"""
         B, c, n_orb, p_orb, gps = self._orbit_proposals(model_id, p_orb, gps)
         lnp, g_orb, g_gp, g_mu = np.empty(B), np.empty((B, n_orb)), np.empty((B, 2 * c)), np.empty(B)
         g_vel = np.empty((B, c, self.n_epochs)) if want_vel else None
+        after_gp, after_grad_gp = (), ()
+        if tau is not None:
+            taus, g_tau = as_f64(np.atleast_2d(as_f64(tau)), (B, c)), np.empty((B, c))
+            after_gp, after_grad_gp = (dptr(taus),), (dptr(g_tau),)
         tail = (dptr(g_mu), dptr(g_vel) if want_vel else None)
-        check(getattr(self._L, entry)(self._h, B, int(model_id), dptr(p_orb), dptr(gps), float(mu_GP), dptr(lnp), dptr(g_orb),
-                                      dptr(g_gp), *(tail if vel_last else tail[::-1])), entry)
-        return (lnp, g_orb, g_gp, g_mu, g_vel) if want_vel else (lnp, g_orb, g_gp, g_mu)
+        check(getattr(self._L, entry)(self._h, B, int(model_id), dptr(p_orb), dptr(gps), *after_gp, float(mu_GP), dptr(lnp),
+                                      dptr(g_orb), dptr(g_gp), *after_grad_gp, *(tail if vel_last else tail[::-1])), entry)
+        out = (lnp, g_orb, g_gp) + (() if tau is None else (g_tau,)) + (g_mu,)
+        return out + (g_vel,) if want_vel else out
 
     def lnlike_grad(self, lwls, gp, mu_GP: float = 1.0):
         """Value and analytic gradient of the likelihood (include/psoap_gp.h: psoap_chunk_lnlike_grad).
@@ -539,6 +545,35 @@ class ChunkHandle:
         check(self._L.psoap_batch_upload_velocities(self._h, B, c, dptr(vel), dptr(gps), float(mu_GP)),
               "psoap_batch_upload_velocities")
         self._B = B
+
+    def set_tau(self, tau):
+        """Time scales ``tau`` (B, c) in days for the upload that is pending (``upload``, ``upload_velocities`` or a
+        ``ChunkWorker.upload_*``; include/psoap_gp.h: psoap_batch_set_tau; needs ``set_times``): ``eval`` then evaluates the
+        time-variable kernel of ``lnlike_tv`` on the staged path, whatever ``set_mode`` says.  ``inf`` is the static model
+        (the bits of the same upload under ``set_mode("staged")``); ``tau <= 0`` or NaN gives ``-inf`` for that proposal
+        alone.  The next upload clears the time scales.  Refused without a pending upload, for another shape, without
+        times, with an open stream or on a handle with a baseline."""
+        tau = as_f64(np.atleast_2d(as_f64(tau)))
+        if tau.ndim != 2:
+            raise ValueError("tau must have shape (B, c)")
+        B, c = tau.shape
+        check(self._L.psoap_batch_set_tau(self._h, B, c, dptr(tau)), "psoap_batch_set_tau")
+
+    def lnprob_tv_grad(self, model_id: int, p_orb, gps, tau, mu_GP: float = 1.0, want_vel: bool = False):
+        """``lnprob_grad`` under the time-variable kernel of ``lnlike_tv`` (include/psoap_gp.h: psoap_chunk_lnprob_tv_grad;
+        needs ``set_grid``, the dates and ``set_times``): ``tau`` (B, c) beside ``gps`` ->
+        ``(lnp (B,), grad_orb (B, n_orb), grad_gp (B, 2c), grad_tau (B, c), grad_mu (B,))``, with ``grad_vel`` appended when
+        ``want_vel``.  With every ``tau = inf`` ``grad_tau`` is exactly 0.  A faster-than-light proposal, a negative
+        hyper-parameter, ``tau <= 0`` or NaN, or a matrix that is not positive definite gives ``-inf`` and NaN gradients
+        for that proposal."""
+        return self._lnprob_grad("psoap_chunk_lnprob_tv_grad", False, model_id, p_orb, gps, mu_GP, want_vel, tau)
+
+    def lnprob_marg_tv_grad(self, model_id: int, p_orb, gps, tau, mu_GP: float = 1.0, want_vel: bool = False):
+        """``lnprob_tv_grad`` under the baseline of ``set_baseline`` (include/psoap_gp.h: psoap_chunk_lnprob_marg_tv_grad):
+        the same arguments, the same tuple."""
+        if getattr(self, "_baseline", None) is None:
+            raise _lib.PsoapError("lnprob_marg_tv_grad: call set_baseline first")
+        return self._lnprob_grad("psoap_chunk_lnprob_marg_tv_grad", True, model_id, p_orb, gps, mu_GP, want_vel, tau)
 
     def eval(self):
         check(self._L.psoap_batch_eval(self._h), "psoap_batch_eval")

@@ -83,6 +83,8 @@ static int grad_run(psoap_chunk* h, bool marg, int B, int c, const double* lwl, 
                 if (int rc = orbit_back(h, w, s, nb, c, np, grad_orb + (size_t)b0 * np,
                                         grad_vel ? grad_vel + (size_t)b0 * c * ne : nullptr, fast.data() + b0))
                     return rc;
+        } else if (orbits) {      // (the value only: the faster-than-light flags still decide it)
+            HIP_TRY(hipMemcpyAsync(fast.data() + b0, w.TooFast, sizeof(int) * (size_t)nb, hipMemcpyDeviceToHost, s));
         }
         HIP_TRY(hipStreamSynchronize(s));       // the next group reuses the workspace and the caller's arrays are pageable
     }

@@ -374,6 +374,18 @@ __global__ __launch_bounds__(256) void k_fill_sym_tv(double* __restrict__ Kbase,
     }
 }
 
+// The proposals of a batch whose tau (nb, C) holds a value that is no time scale -- zero, negative or NaN; +inf is one -- get
+// their flag raised (the word k_finalize reads: -inf for that proposal alone).  Flags are only ever raised here.
+__global__ void k_tau_flags(const double* __restrict__ tau, int C, int nb, int* __restrict__ flags)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < nb) {
+        bool bad = false;
+        for (int c = 0; c < C; ++c) bad = bad || !(tau[(size_t)b * C + c] > 0.0);
+        if (bad) flags[b] = 1;
+    }
+}
+
 // Rectangular cross fill (pyx:61-96): out (M x ld), out[i,j] = a2 * exp(p2 * (xcol[j]-xrow[i])^2).
 // grid.x = tiles over columns, grid.y = tiles over rows.
 __global__ __launch_bounds__(256) void k_fill_cross(double* __restrict__ out, int ld, int M, int Ncol,

@@ -103,6 +103,46 @@ inline const char* marg_tv_check(MargTvEntry entry, const MargTvCall& a)
     return marg_grad_check(1, a.c, a.have_baseline, a.stale_weight);
 }
 
+// ---- time scales on the batch route (psoap_batch_set_tau) -------------------------------------------------------------------
+// -> nullptr, or why the call is refused, in this order: the array; c; B; the handle's state in the words of the time-variable
+// entries -- times set, no open stream -- and no baseline: the value under one goes through psoap_chunk_lnlike_marg_tv; then a
+// pending upload (psoap_batch_upload, _upload_velocities or _upload_orbits) and its B and c.  A tau that is
+// no time scale is not a refusal: the evaluation gives -inf for that proposal.  The caller puts the entry's name in front.
+inline const char* batch_tau_check(bool array, int B, int c, bool pending, int pend_B, int pend_c, bool have_times,
+                                   bool open_stream, bool have_baseline)
+{
+    if (!array) return "bad arguments";
+    if (c < 1 || c > 3) return "number of components must be 1, 2 or 3";
+    if (B < 1) return "B must be at least 1";
+    if (!have_times) return "call psoap_chunk_set_times first";
+    if (open_stream) return "the handle has an open stream (psoap_stream_close first)";
+    if (have_baseline)
+        return "the handle has a baseline (psoap_chunk_set_baseline): the value under a baseline goes through "
+               "psoap_chunk_lnlike_marg_tv";
+    if (!pending) return "no upload is pending (psoap_batch_upload, psoap_batch_upload_velocities or psoap_batch_upload_orbits first)";
+    if (B != pend_B || c != pend_c) return "B and c must be those of the pending upload";
+    return nullptr;
+}
+
+// ---- lnprob(p) under the time-variable kernel (psoap_chunk_lnprob_tv_grad, psoap_chunk_lnprob_marg_tv_grad) -----------------
+// -> nullptr, or why the call is refused before the orbits are looked at: the arrays; the NULL rules of
+// psoap_chunk_lnlike_tv_grad (grad_gp == NULL: the value only, and then grad_orb, grad_tau, grad_vel and grad_mu are NULL too;
+// grad_orb and grad_tau go with grad_gp); B; the grid and the dates; times set, no open stream.  `who` is not needed: the caller
+// puts the entry's name in front.  The baseline is asked for (marg) or refused (plain) after the orbits, by the caller.
+inline const char* lnprob_tv_check(bool arrays, bool grad_gp, bool grad_orb, bool grad_tau, bool grad_rest, int B, bool have_grid,
+                                   bool have_times, bool open_stream)
+{
+    if (!arrays) return "bad arguments";
+    if (!grad_gp && (grad_orb || grad_tau || grad_rest))
+        return "grad_gp == NULL asks for the value only: grad_orb, grad_tau, grad_vel and grad_mu must be NULL too";
+    if (grad_gp && !(grad_orb && grad_tau)) return "grad_orb and grad_tau go with grad_gp";
+    if (B < 1) return "B must be at least 1";
+    if (!have_grid) return "call psoap_chunk_set_grid and psoap_chunk_set_dates first";
+    if (!have_times) return "call psoap_chunk_set_times first";
+    if (open_stream) return "the handle has an open stream (psoap_stream_close first)";
+    return nullptr;
+}
+
 inline void marg_grad_plan(const MargPlan& pl, MargGradPlan& out)
 {
     out = MargGradPlan();

@@ -102,6 +102,10 @@ struct BatchSlot {
     int B = 0, C = 0;
     double mu = 1.0;
     std::vector<char> neg;     // per-proposal: a hyper-parameter was negative -> -inf
+    // time scales of the time-variable kernel (psoap_batch_set_tau): attached to ONE upload, gone with the next to this slot
+    Grow<double> dTau;         // max_batch x 3
+    Grow<double, true> hTau;   // its pinned staging, the slot's own
+    bool has_tau = false;
     Event evUpload;            // copy stream: H2D (+ Doppler shift) of this slot complete
     Event evEval;              // compute stream: last evaluation that read this slot complete
 };
@@ -640,6 +644,7 @@ static int upload_begin(psoap_chunk* h, int B, int c, const double* gp, double m
     sl.B = B;
     sl.C = c;
     sl.mu = mu_GP;
+    sl.has_tau = false;
     sl.neg.assign(B, 0);
     for (int b = 0; b < B; ++b)
         for (int k = 0; k < 2 * c; ++k)
@@ -792,6 +797,31 @@ extern "C" int psoap_batch_upload_orbits(psoap_chunk* h, int B, int model, const
     return upload_end(h, *sl);
 }
 
+// Time scales tau (B, c) for the pending upload: its evaluation fills K with the time-variable kernel over the handle's times
+// (eval_staged).  The copy is queued on the upload's stream behind it; the events that say "the upload is complete" and "the
+// staging is free" move behind the copy.  No host round trip: a tau that is no time scale is flagged on the device, with the fill.
+extern "C" int psoap_batch_set_tau(psoap_chunk* h, int B, int c, const double* tau)
+{
+    if (!h) FAIL("psoap_batch_set_tau: bad arguments");
+    const bool pending = h->pend >= 0 && h->slot[h->pend].B >= 1;
+    if (const char* why = batch_tau_check(tau != nullptr, B, c, pending, pending ? h->slot[h->pend].B : 0,
+                                          pending ? h->slot[h->pend].C : 0, h->dTimes.p != nullptr, h->stream.open, h->marg.valid))
+        FAIL(std::string("psoap_batch_set_tau: ") + why);
+    DEVICE_SCOPE(h->device);
+    if (set_dev(h)) return 1;
+    BatchSlot& sl = h->slot[h->pend];
+    // (a second call for the same upload: the first one's copy may still read the staging)
+    if (sl.has_tau) HIP_TRY(hipEventSynchronize(h->evStaging));
+    NEED(sl.dTau, (size_t)h->max_batch * 3);
+    NEED(sl.hTau, (size_t)h->max_batch * 3);
+    memcpy(sl.hTau, tau, sizeof(double) * (size_t)B * c);
+    HIP_TRY(hipMemcpyAsync(sl.dTau, sl.hTau, sizeof(double) * (size_t)B * c, hipMemcpyHostToDevice, h->copy()));
+    HIP_TRY(hipEventRecord(h->evStaging, h->copy()));
+    HIP_TRY(hipEventRecord(sl.evUpload, h->copy()));
+    sl.has_tau = true;
+    return 0;
+}
+
 // stand-alone batched orbit evaluation: vel_out (B, c, n_dates)
 extern "C" int psoap_orbit_velocities(int device, int model, int B, const double* p_orb, int n_dates,
                                       const double* dates, double* vel_out)
@@ -919,6 +949,20 @@ static void launch_fill(psoap_chunk* h, const BatchSlot& sl, hipStream_t s, int 
     hipLaunchKernelGGL(k_fill_sym<C>, dim3(tiles, nb), dim3(256), 0, s, h->dK + (size_t)b0 * h->mat_stride,
                        h->mat_stride, h->ld, h->N, h->P, sl.dLwl + (size_t)b0 * C * h->N,
                        sl.dGp + (size_t)b0 * 2 * C, h->dSigma, upper_only);
+}
+
+// ... of a slot that carries time scales: the time-variable fill over the handle's times, and beside it the flags of the
+// proposals whose tau is no time scale, in the word the faster-than-light rule uses (k_finalize: -inf)
+template <int C>
+static void launch_fill_tv(psoap_chunk* h, const BatchSlot& sl, hipStream_t s, int b0, int nb, int upper_only)
+{
+    const int tiles = upper_only ? h->P * (h->P + 1) / 2 : h->P * h->P;
+    hipLaunchKernelGGL(k_fill_sym_tv<C>, dim3(tiles, nb), dim3(256), 0, s, h->dK + (size_t)b0 * h->mat_stride,
+                       h->mat_stride, h->ld, h->N, h->P, (const double*)(sl.dLwl + (size_t)b0 * C * h->N),
+                       (const double*)h->dTimes.p, (const double*)(sl.dGp + (size_t)b0 * 2 * C),
+                       (const double*)(sl.dTau + (size_t)b0 * C), (const double*)h->dSigma.p, upper_only);
+    hipLaunchKernelGGL(k_tau_flags, dim3((nb + 63) / 64), dim3(64), 0, s, (const double*)(sl.dTau + (size_t)b0 * C), C, nb,
+                       sl.dTooFast + b0);
 }
 
 // The record of the handle's matrix b: its share of the workspaces, and what it reads -- proposal b of the arrays lw and gp
@@ -1177,7 +1221,10 @@ extern "C" int psoap_batch_eval(psoap_chunk* h)
     // the persistent kernel indexes block rows with 8 bits (beyond N = 32640: the staged path), and it is not used where
     // it cannot be made safe among several processes (share_wants_staged)
     int rc;
-    if (h->mode == 1 && h->P <= 255 && !share_wants_staged(h->device)) {
+    if (h->slot[h->act].has_tau) {
+        // the persistent kernel has no temporal factor: always the staged path, whatever the mode -- not a policy event
+        rc = eval_staged(h);
+    } else if (h->mode == 1 && h->P <= 255 && !share_wants_staged(h->device)) {
         rc = eval_dag(h);
     } else {
         if (h->mode == 1 && h->P <= 255) g_share.staged_policy += 1;
@@ -1197,6 +1244,7 @@ static int eval_staged(psoap_chunk* h)
     for (int g = 1; g < G; ++g)
         if (!h->streams[g]) HIP_TRY(h->streams[g].create());
     h->recs.clear();
+    if (sl.has_tau) sl.toofast_dirty = true;      // (k_tau_flags may raise flags: cleared before the slot is reused)
     int gb0[MAX_GROUPS + 1];
     for (int g = 0; g <= G; ++g) gb0[g] = (int)((long long)B * g / G);
 
@@ -1210,7 +1258,10 @@ static int eval_staged(psoap_chunk* h)
         if (g != 0 && h->last_recorded) HIP_TRY(hipStreamWaitEvent(s, h->evLast, 0));
         const double fbytes = (double)nb * (4.0 * N * (N + 1.0) + 8.0 * (C + 1.0) * N);
         if (int rc = prof_launch(h, s, PSOAP_K_FILL, 0.0, fbytes, [&] {
-                with_components(C, [&](auto nc) { launch_fill<nc()>(h, sl, s, b0, nb, 1); });
+                with_components(C, [&](auto nc) {
+                    if (sl.has_tau) launch_fill_tv<nc()>(h, sl, s, b0, nb, 1);
+                    else launch_fill<nc()>(h, sl, s, b0, nb, 1);
+                });
             })) return rc;
         if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
                 hipLaunchKernelGGL(k_init_rhs, dim3((h->Npad + 255) / 256, nb), dim3(256), 0, s,
@@ -1271,6 +1322,13 @@ struct psoap_group {
 };
 
 extern "C" int psoap_group_destroy(psoap_group* g);
+// the slot the handle's next evaluation reads -- the pending one if there is one, else the active one -- carries time scales
+// (psoap_batch_set_tau)
+static bool slot_has_tau(const psoap_chunk* h)
+{
+    const int k = h->pend >= 0 ? h->pend : h->act;
+    return k >= 0 && h->slot[k].B >= 1 && h->slot[k].has_tau;
+}
 static std::mutex g_groups_mu;
 static std::set<psoap_group*> g_live_groups;      // groups that exist: a handle's last_group is only followed while it is in here
 
@@ -1324,6 +1382,10 @@ static int group_eval_locked(psoap_group* g, bool promote);
 extern "C" int psoap_group_eval(psoap_group* g)
 {
     if (!g) FAIL("psoap_group_eval: null group");
+    for (psoap_chunk* h : g->hs)
+        if (slot_has_tau(h))
+            FAIL("psoap_group_eval: a member's upload carries time scales (psoap_batch_set_tau): the group launch has no temporal "
+                 "factor (psoap_batch_eval on that handle)");
     HIP_TRY(hipSetDevice(g->device));
     for (psoap_chunk* h : g->hs)                      // each member's fetch releases its own reference
         if (int rc = handle_lock(h)) {
@@ -1570,6 +1632,9 @@ extern "C" int psoap_stream_open(psoap_chunk* h, int c, int lanes, int scheme)
     if (scheme < -1 || scheme > 2) FAIL("psoap_stream_open: scheme must be -1 (automatic), 0, 1 or 2");
     if (h->P > 255) FAIL("psoap_stream_open: N too large for the persistent kernel (N <= 32640)");
     if (h->stream.open) FAIL("psoap_stream_open: the handle already has an open stream");
+    if (slot_has_tau(h))
+        FAIL("psoap_stream_open: the handle's last upload carries time scales (psoap_batch_set_tau): the resident launch has no "
+             "temporal factor (upload without them first)");
     // (Late round 5 refused the following scheme (2) here: through a resident launch it returned a wrong value once in 20,000
     // ... 150,000 matrices.  Round 6 found the cause -- an unordered read-modify-write chain on the per-matrix accumulator
     // record and two progress words published out of order, both in the second level of following, neither specific to
@@ -2381,6 +2446,47 @@ extern "C" int psoap_chunk_fisher_marg_tv(psoap_chunk* h, int c, const double* l
     if (const char* why = marg_tv_check(MargTvEntry::Fisher, marg_tv_call(h, lwl && gp && tau && tan_gp && fisher, 1, c, T)))
         FAIL(std::string("psoap_chunk_fisher_marg_tv: ") + why);
     return fisher_run(h, "psoap_chunk_fisher_marg_tv", true, c, lwl, gp, tau, T, tan_lwl, tan_gp, tan_tau, fisher, fisher_mu);
+}
+
+// ---- lnprob(p) under the time-variable kernel: the orbit front end of psoap_chunk_lnprob_grad and grad_run with `tau`, plain
+// or -- `marg` -- under the handle's baseline.  The checks before the orbits are lnprob_tv_check's (marg_grad_plan.hpp).
+static int lnprob_tv_run(psoap_chunk* h, const char* who, bool marg, int B, int model, const double* p_orb, const double* gp,
+                         const double* tau, double mu_GP, double* lnp, double* grad_orb, double* grad_gp, double* grad_tau,
+                         double* grad_vel, double* grad_mu)
+{
+    if (!h) FAIL(std::string(who) + ": bad arguments");
+    if (const char* why = lnprob_tv_check(p_orb && gp && tau && lnp, grad_gp != nullptr, grad_orb != nullptr, grad_tau != nullptr,
+                                          grad_vel || grad_mu, B, h->dGrid.p && h->dDates.p, h->dTimes.p != nullptr, h->stream.open))
+        FAIL(std::string(who) + ": " + why);
+    if (int rc = check_orbits(model, B, p_orb)) return rc;
+    const int c = orbit_n_components(model);
+    if (int rc = analysis_refused(h, who, marg, B, c)) return rc;
+    if (!marg && h->marg.valid)
+        FAIL(std::string(who) + ": the handle has a baseline (psoap_chunk_set_baseline): psoap_chunk_lnprob_marg_tv_grad is the entry "
+                                "under it");
+    if (int rc = grad_run(h, marg, B, c, nullptr, model, p_orb, gp, tau, mu_GP, lnp, nullptr, grad_gp, grad_tau, nullptr, grad_mu,
+                          grad_orb, grad_vel, grad_gp != nullptr))
+        return rc;
+    // a static component's derivative is +0: the finishing sums give 0 * st with the sign of st (-0 + 0 = +0; nothing else moves)
+    if (grad_tau)
+        for (size_t k = 0; k < (size_t)B * c; ++k) grad_tau[k] = grad_tau[k] + 0.0;
+    return 0;
+}
+
+extern "C" int psoap_chunk_lnprob_tv_grad(psoap_chunk* h, int B, int model, const double* p_orb, const double* gp, const double* tau,
+                                          double mu_GP, double* lnp, double* grad_orb, double* grad_gp, double* grad_tau,
+                                          double* grad_vel, double* grad_mu)
+{
+    return lnprob_tv_run(h, "psoap_chunk_lnprob_tv_grad", false, B, model, p_orb, gp, tau, mu_GP, lnp, grad_orb, grad_gp, grad_tau,
+                         grad_vel, grad_mu);
+}
+
+extern "C" int psoap_chunk_lnprob_marg_tv_grad(psoap_chunk* h, int B, int model, const double* p_orb, const double* gp,
+                                               const double* tau, double mu_GP, double* lnp, double* grad_orb, double* grad_gp,
+                                               double* grad_tau, double* grad_mu, double* grad_vel)
+{
+    return lnprob_tv_run(h, "psoap_chunk_lnprob_marg_tv_grad", true, B, model, p_orb, gp, tau, mu_GP, lnp, grad_orb, grad_gp,
+                         grad_tau, grad_vel, grad_mu);
 }
 
 // frees the device side of the baseline and the workspace; the baseline itself stays set (the next call builds Ht again)

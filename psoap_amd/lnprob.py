@@ -15,12 +15,15 @@ import numpy as np
 from . import _lib
 from ._lib import as_f64, check, dptr
 from .chunk import ChunkHandle
-from .utils import MODEL_ID, N_COMPONENTS, convert_vectors, n_params_orb, registered_params
+from .utils import MODEL_ID, N_COMPONENTS, convert_vectors, convert_vectors_timevar, n_params_orb, registered_params, timevar_spec
 
 
 class ChunkWorker:
+    timevar = None      # (``{"fit", "tau"}`` on a worker made with ``timevar=...``)
+
     def __init__(self, model: str, lwl, fl, sigma, epoch_index, dates, fix_params=(), defaults=None,
-                 max_batch: int = 1, device: int | None = None, soften: float = 1.0, baseline: dict | None = None):
+                 max_batch: int = 1, device: int | None = None, soften: float = 1.0, baseline: dict | None = None,
+                 timevar: dict | None = None):
         """lwl/fl/sigma: the chunk's masked, flattened arrays (N,); epoch_index (N,): epoch of each pixel;
         dates (n_epochs,): ``date1D``; ``soften`` scales sigma (sample_parallel.py:141).
 
@@ -30,7 +33,17 @@ class ChunkWorker:
         (``ChunkHandle.lnprob_marg_grad``), ``fisher*`` its Fisher information (``ChunkHandle.fisher_marg``) and ``loo*`` its
         leave-one-out cross-validation (``ChunkHandle.loo_marg``).  The split-phase and streamed entries
         (``upload_*``, ``stream_*``) evaluate the plain likelihood and refuse to run on such a worker.  ``None``: every
-        path as it was."""
+        path as it was.
+
+        ``timevar = {"fit": [bool per component], "tau": [default per component, inf allowed], "times": None | (N,)}``: the
+        time-variable kernel of ``ChunkHandle.lnlike_tv`` over the pixels' ``times`` in days (``None``:
+        ``dates[epoch_index]`` minus its minimum).  A fitted vector is then the model's registered vector followed by one
+        ``tau_c`` in days for every component with ``fit`` true, in component order (``utils.convert_vectors_timevar``); the
+        other components stay at their default.  ``lnprob`` / ``lnprob_batch`` and the split-phase ``upload_*`` carry the
+        time scales to the device (``ChunkHandle.set_tau``; with a baseline ``ChunkHandle.lnlike_marg_tv``),
+        ``lnprob_grad*`` return the ``tau`` entries in vector order, ``fisher*`` / ``loo*`` dispatch to ``fisher_tv`` /
+        ``loo_tv`` (``fisher_marg_tv`` under a baseline; ``loo`` under a baseline is refused: not built).  The streamed
+        entries and ``PSOAP_GPU_SERVER`` are refused.  ``None``: every path as it was."""
         self.model = model
         self.fix_params = list(fix_params)
         self.defaults = dict(defaults or {})
@@ -51,6 +64,53 @@ class ChunkWorker:
             self.baseline = {"order": int(baseline["order"]), "sd": [float(v) for v in baseline["sd"]], "weight": kind}
             self.handle.set_baseline(self.baseline["order"], self.lwl, self.epoch_index, dates.shape[0], self.baseline["sd"],
                                      self.handle.fl if kind == "flux" else None)
+        self.timevar = None
+        if timevar is not None:
+            if os.environ.get("PSOAP_GPU_SERVER", "").strip().lower() not in ("", "0"):
+                raise _lib.PsoapError("a timevar worker needs the device in this process (PSOAP_GPU_SERVER serves the static "
+                                      "likelihood only)")
+            fit, tau, times = timevar_spec(model, timevar)
+            if times is None:
+                times = dates[self.epoch_index]
+                times = times - times.min()
+            self.times = as_f64(times, (self.handle.N,))
+            self.timevar = {"fit": fit, "tau": tau}
+            self.handle.set_times(self.times)
+            # an upload that will carry time scales is evaluated on the staged path whatever the mode: in staged mode the
+            # upload does not queue the skyline's sort and envelope kernels, whose results only the persistent kernel reads
+            self.handle.set_mode("staged")
+
+    # -- time scales in the fitted vector (utils.convert_vectors_timevar) ------------------------------------------------
+    def split_vectors(self, ps):
+        """fitted vectors (B, n_fit) -> ``(p_orb, p_gp, taus)``; ``taus`` (B, c) on a ``timevar`` worker, else ``None``"""
+        if self.timevar is None:
+            return (*convert_vectors(np.atleast_2d(ps), self.model, self.fix_params, **self.defaults), None)
+        return convert_vectors_timevar(np.atleast_2d(ps), self.model, self.fix_params, self.timevar["fit"], self.timevar["tau"],
+                                       **self.defaults)
+
+    def _taus(self, tau, B):
+        """``tau`` (c,) or (B, c), ``None``: the defaults -> (B, c); ``None`` on a worker without ``timevar``"""
+        if self.timevar is None:
+            if tau is not None:
+                raise _lib.PsoapError("this worker has no time scales (ChunkWorker(..., timevar=...))")
+            return None
+        c = N_COMPONENTS[self.model]
+        tau = self.timevar["tau"] if tau is None else as_f64(tau)
+        return as_f64(np.broadcast_to(np.atleast_2d(tau), (B, c)))
+
+    def _no_timevar(self, what):
+        if self.timevar is not None:
+            raise _lib.PsoapError(f"{what} has no temporal factor; this worker has time scales (use lnprob / lnprob_batch or "
+                                  "the upload_* entries)")
+
+    def _fit_index(self):
+        """columns of a full ``[orbit, GP, tau]`` array that a fitted vector holds, in vector order"""
+        reg = registered_params[self.model]
+        ind = [i for i, name in enumerate(reg) if name not in self.fix_params]
+        if self.timevar is not None:
+            first = n_params_orb[self.model] + 2 * N_COMPONENTS[self.model]
+            ind += [first + int(k) for k in np.flatnonzero(self.timevar["fit"])]
+        return ind
 
     def close(self):
         self.handle.close()
@@ -71,10 +131,12 @@ class ChunkWorker:
         fast = np.any(np.abs(vel) >= c_kms, axis=(1, 2))
         return self.lwl[None, None, :] + (-vel[:, :, self.epoch_index]) / c_kms, fast
 
-    def marg_orbits(self, p_orb, p_gp, mu_GP: float = 1.0, **want):
+    def marg_orbits(self, p_orb, p_gp, mu_GP: float = 1.0, tau=None, **want):
         """The marginal likelihood with the vectors already split: (B, n_orb) and (B, 2c) -> (B,), or a ``chunk.MargResult``
         with ``want_beta`` / ``want_cov`` / ``want_flux``; walked in pieces of ``max_batch``.  A faster-than-light orbit gives
-        ``-inf`` (and NaN), as a negative hyper-parameter or a matrix that is not positive definite does."""
+        ``-inf`` (and NaN), as a negative hyper-parameter or a matrix that is not positive definite does.  On a ``timevar``
+        worker the kernel is the time-variable one (``ChunkHandle.lnlike_marg_tv``) at ``tau`` (B, c) or (c,) (``None``: the
+        defaults)."""
         if self.baseline is None:
             raise _lib.PsoapError("this worker has no baseline (ChunkWorker(..., baseline=...))")
         if os.environ.get("PSOAP_GPU_SERVER", "").strip().lower() not in ("", "0"):
@@ -84,8 +146,12 @@ class ChunkWorker:
         B, c = lwls.shape[0], N_COMPONENTS[self.model]
         p_gp = as_f64(np.atleast_2d(p_gp), (B, 2 * c))
         lwls[fast] = lwls[~fast][0] if np.any(~fast) else self.lwl          # (a stand-in: overwritten below)
-        pieces = [self.handle.lnlike_marg(lwls[s:s + self.handle.max_batch], p_gp[s:s + self.handle.max_batch], mu_GP, **want)
-                  for s in range(0, B, self.handle.max_batch)]
+        taus, mb = self._taus(tau, B), self.handle.max_batch
+        if taus is None:
+            pieces = [self.handle.lnlike_marg(lwls[s:s + mb], p_gp[s:s + mb], mu_GP, **want) for s in range(0, B, mb)]
+        else:
+            pieces = [self.handle.lnlike_marg_tv(lwls[s:s + mb], p_gp[s:s + mb], taus[s:s + mb], mu_GP, **want)
+                      for s in range(0, B, mb)]
         if not isinstance(pieces[0], MargResult):
             out = np.concatenate(pieces)
             out[fast] = -np.inf
@@ -102,33 +168,40 @@ class ChunkWorker:
         """Ship fitted parameter vectors (B, n_fit); the orbit solve and the Doppler shift are queued on the
         chunk's stream.  Follow with ``handle.eval()`` (or a ``ChunkGroup.eval()``) and ``handle.fetch()``."""
         self._no_baseline("upload_proposals")
-        p_orb, p_gp = convert_vectors(np.atleast_2d(ps), self.model, self.fix_params, **self.defaults)
-        self.upload_orbits(p_orb, p_gp, mu_GP)
+        p_orb, p_gp, taus = self.split_vectors(ps)
+        self.upload_orbits(p_orb, p_gp, mu_GP, taus)
 
-    def upload_orbits(self, p_orb, p_gp, mu_GP: float = 1.0) -> None:
+    def upload_orbits(self, p_orb, p_gp, mu_GP: float = 1.0, tau=None) -> None:
         """The same with the vectors already split: orbital parameters (B, n_orb) and GP parameters (B, 2c).  The library
         reads exactly 2c GP parameters per proposal, so a narrower array is refused here.  (ST2 registers two GP
         parameters, utils.py:7, for a likelihood of two components, covariance.py:379: its fitted vectors stop at
-        ``upload_proposals`` as they stop with a TypeError in ``Worker.lnprob``; this entry takes all four.)"""
+        ``upload_proposals`` as they stop with a TypeError in ``Worker.lnprob``; this entry takes all four.)  On a ``timevar``
+        worker the upload carries ``tau`` (B, c) or (c,) (``None``: the defaults) and ``handle.eval()`` takes the staged path
+        with the time-variable fill (``ChunkHandle.set_tau``); such a handle cannot join a ``ChunkGroup.eval()``."""
         self._no_baseline("upload_orbits")
         p_orb = as_f64(np.atleast_2d(p_orb))
         B = p_orb.shape[0]
         p_orb = as_f64(p_orb, (B, n_params_orb[self.model]))
         p_gp = as_f64(np.atleast_2d(p_gp), (B, 2 * N_COMPONENTS[self.model]))
+        taus = self._taus(tau, B)          # (before anything is queued: a refusal leaves no upload pending)
         h = self.handle
         check(h._L.psoap_batch_upload_orbits(h._h, B, MODEL_ID[self.model], dptr(p_orb), dptr(p_gp), float(mu_GP)),
               "psoap_batch_upload_orbits")
         h._B = B
+        if taus is not None:
+            h.set_tau(taus)
 
     # -- streamed form: ONE resident launch across sampler iterations (include/psoap_gp.h: psoap_stream_*) ----------
     def stream_open(self, lanes: int | None = None, scheme: int = -1):
         self._no_baseline("the streamed path")
+        self._no_timevar("the streamed path")
         self.handle.stream_open(N_COMPONENTS[self.model], lanes, scheme)
 
     def stream_submit(self, ps, mu_GP: float = 1.0) -> np.ndarray:
         """fitted parameter vectors (n, n_fit) -> tickets; Kepler solve, |v| >= c rule, Doppler shift and likelihood all
         inside the resident launch (``Worker.lnprob`` for n proposals, sample_parallel.py:168-198)"""
         self._no_baseline("the streamed path")
+        self._no_timevar("the streamed path")
         p_orb, p_gp = convert_vectors(np.atleast_2d(ps), self.model, self.fix_params, **self.defaults)
         return self.handle.stream_submit_orbits(MODEL_ID[self.model], p_orb, p_gp, mu_GP)
 
@@ -140,8 +213,8 @@ class ChunkWorker:
 
     def lnprob_batch(self, ps, mu_GP: float = 1.0) -> np.ndarray:
         if self.baseline is not None:
-            p_orb, p_gp = convert_vectors(np.atleast_2d(ps), self.model, self.fix_params, **self.defaults)
-            return self.marg_orbits(p_orb, p_gp, mu_GP)
+            p_orb, p_gp, taus = self.split_vectors(ps)
+            return self.marg_orbits(p_orb, p_gp, mu_GP, taus)
         self.upload_proposals(ps, mu_GP)
         self.handle.eval()
         return self.handle.fetch()
@@ -150,18 +223,24 @@ class ChunkWorker:
         return float(self.lnprob_batch(np.atleast_2d(p), mu_GP)[0])
 
     # -- gradient of lnprob(p) (include/psoap_gp.h: psoap_chunk_lnprob_grad) ----------------------------------------
-    def lnprob_grad_orbits(self, p_orb, p_gp, mu_GP: float = 1.0, want_vel: bool = False):
+    def lnprob_grad_orbits(self, p_orb, p_gp, mu_GP: float = 1.0, want_vel: bool = False, tau=None):
         """The gradient with the vectors already split, as ``upload_orbits`` takes them: orbital parameters (B, n_orb) and
         GP parameters (B, 2c) -> ``(lnp (B,), grad_orb (B, n_orb), grad_gp (B, 2c), grad_mu (B,))`` (and ``grad_vel
         (B, c, n_epochs)`` with ``want_vel``).  Kepler solve, orbit Jacobian, Doppler shift, likelihood gradient and the
         chain rule run on the device.  The only way in for ST2, for the reason ``upload_orbits`` documents.  On a worker
-        with a baseline the likelihood in the middle is the marginal one (``ChunkHandle.lnprob_marg_grad``)."""
+        with a baseline the likelihood in the middle is the marginal one (``ChunkHandle.lnprob_marg_grad``).  On a ``timevar``
+        worker the kernel is the time-variable one at ``tau`` (B, c) or (c,) (``None``: the defaults) and ``grad_tau (B, c)``
+        follows ``grad_gp`` in the tuple (``ChunkHandle.lnprob_tv_grad`` / ``lnprob_marg_tv_grad``)."""
         if os.environ.get("PSOAP_GPU_SERVER", "").strip().lower() not in ("", "0"):
             raise _lib.PsoapError("lnprob_grad needs the device in this process (PSOAP_GPU_SERVER serves values only)")
         p_orb = as_f64(np.atleast_2d(p_orb))
         B = p_orb.shape[0]
         p_orb = as_f64(p_orb, (B, n_params_orb[self.model]))
         p_gp = as_f64(np.atleast_2d(p_gp), (B, 2 * N_COMPONENTS[self.model]))
+        taus = self._taus(tau, B)
+        if taus is not None:
+            entry = self.handle.lnprob_marg_tv_grad if self.baseline is not None else self.handle.lnprob_tv_grad
+            return entry(MODEL_ID[self.model], p_orb, p_gp, taus, mu_GP, want_vel=want_vel)
         if getattr(self, "baseline", None) is not None:      # (the gradient of what ``lnprob`` returns on this worker)
             return self.handle.lnprob_marg_grad(MODEL_ID[self.model], p_orb, p_gp, mu_GP, want_vel=want_vel)
         return self.handle.lnprob_grad(MODEL_ID[self.model], p_orb, p_gp, mu_GP, want_vel=want_vel)
@@ -169,19 +248,22 @@ class ChunkWorker:
     def lnprob_grad_batch(self, ps, mu_GP: float = 1.0):
         """Fitted parameter vectors (B, n_fit) -> ``(lnp (B,), grad (B, n_fit))``: the derivative with respect to every
         non-fixed parameter, in registered order; fixed parameters drop out.  A proposal whose ``lnp`` is ``-inf`` has a
-        NaN gradient."""
-        p_orb, p_gp = convert_vectors(np.atleast_2d(ps), self.model, self.fix_params, **self.defaults)
-        lnp, g_orb, g_gp, _g_mu = self.lnprob_grad_orbits(p_orb, p_gp, mu_GP)
-        full = np.concatenate([g_orb, g_gp], axis=1)
-        fit_ind = [i for i, name in enumerate(registered_params[self.model]) if name not in self.fix_params]
-        return lnp, np.ascontiguousarray(full[:, fit_ind])
+        NaN gradient.  On a ``timevar`` worker the fitted time scales' derivatives follow, in vector order."""
+        p_orb, p_gp, taus = self.split_vectors(ps)
+        if taus is None:
+            lnp, g_orb, g_gp, _g_mu = self.lnprob_grad_orbits(p_orb, p_gp, mu_GP)
+            full = np.concatenate([g_orb, g_gp], axis=1)
+        else:
+            lnp, g_orb, g_gp, g_tau, _g_mu = self.lnprob_grad_orbits(p_orb, p_gp, mu_GP, tau=taus)
+            full = np.concatenate([g_orb, g_gp, g_tau], axis=1)
+        return lnp, np.ascontiguousarray(full[:, self._fit_index()])
 
     def lnprob_grad(self, p, mu_GP: float = 1.0):
         lnp, grad = self.lnprob_grad_batch(np.atleast_2d(p), mu_GP)
         return float(lnp[0]), grad[0]
 
     # -- Fisher information of lnprob(p) (include/psoap_gp.h: psoap_chunk_fisher) ------------------------------------
-    def fisher_orbits(self, p_orb, p_gp):
+    def fisher_orbits(self, p_orb, p_gp, tau=None):
         """The Fisher information of this chunk with the vectors already split: orbital parameters (n_orb,) and GP
         parameters (2c,) -> ``(n_orb + 2c, n_orb + 2c)`` in registered order.  The tangent of orbital parameter i moves
         the grid of component c by ``dx[n] = -J[c, epoch(n), i] / c_kms`` with ``J`` the device's velocity Jacobian
@@ -189,7 +271,10 @@ class ChunkWorker:
         them); the tangents of the GP parameters are unit vectors.  The (T, c, N) tangents are assembled on the host,
         everything of order N^3 runs on the device.  A faster-than-light orbit, a negative hyper-parameter or a matrix
         that is not positive definite gives NaN in every entry.  On a worker with a baseline the information is that of the
-        marginal likelihood (``ChunkHandle.fisher_marg``): of what ``lnprob`` returns on this worker."""
+        marginal likelihood (``ChunkHandle.fisher_marg``): of what ``lnprob`` returns on this worker.  On a ``timevar`` worker
+        the kernel is the time-variable one at ``tau`` (c,) (``None``: the defaults) and the matrix has one more row and
+        column per component, the unit ``dtau`` tangents, after the GP parameters: ``(n_orb + 3c, n_orb + 3c)``
+        (``ChunkHandle.fisher_tv``, under a baseline ``fisher_marg_tv``)."""
         if os.environ.get("PSOAP_GPU_SERVER", "").strip().lower() not in ("", "0"):
             raise _lib.PsoapError("fisher needs the device in this process (PSOAP_GPU_SERVER serves values only)")
         from .data import c_kms
@@ -198,7 +283,8 @@ class ChunkWorker:
         p_orb = as_f64(np.ravel(p_orb), (n_orb,))
         p_gp = as_f64(np.ravel(p_gp), (2 * c,))
         vel, jac = velocity_jacobian(self.model, p_orb[None], self.dates, device=self.handle.device)
-        T = n_orb + 2 * c
+        taus = self._taus(tau, 1)
+        T = n_orb + 2 * c + (0 if taus is None else c)
         if np.any(np.abs(vel[0]) >= c_kms):
             return np.full((T, T), np.nan)
         ep = self.epoch_index
@@ -206,7 +292,12 @@ class ChunkWorker:
         tan_lwl = np.zeros((T, c, self.handle.N))
         tan_lwl[:n_orb] = -np.moveaxis(jac[0], 2, 0)[:, :, ep] / c_kms
         tan_gp = np.zeros((T, 2 * c))
-        tan_gp[n_orb:] = np.eye(2 * c)
+        tan_gp[n_orb:n_orb + 2 * c] = np.eye(2 * c)
+        if taus is not None:
+            tan_tau = np.zeros((T, c))
+            tan_tau[n_orb + 2 * c:] = np.eye(c)
+            entry = self.handle.fisher_marg_tv if self.baseline is not None else self.handle.fisher_tv
+            return entry(lwls, p_gp, taus[0], tan_gp, tan_tau, tan_lwl)
         if getattr(self, "baseline", None) is not None:      # (the information of what ``lnprob`` returns on this worker)
             return self.handle.fisher_marg(lwls, p_gp, tan_gp, tan_lwl)
         return self.handle.fisher(lwls, p_gp, tan_gp, tan_lwl)
@@ -214,20 +305,24 @@ class ChunkWorker:
     def fisher(self, p):
         """One fitted parameter vector (n_fit,) -> ``(n_fit, n_fit)`` over the non-fixed parameters in registered order,
         the ordering of ``lnprob_grad``; fixed parameters drop out."""
-        p_orb, p_gp = convert_vectors(np.atleast_2d(p), self.model, self.fix_params, **self.defaults)
-        full = self.fisher_orbits(p_orb[0], p_gp[0])
-        fit_ind = [i for i, name in enumerate(registered_params[self.model]) if name not in self.fix_params]
+        p_orb, p_gp, taus = self.split_vectors(p)
+        full = self.fisher_orbits(p_orb[0], p_gp[0], None if taus is None else taus[0])
+        fit_ind = self._fit_index()
         return np.ascontiguousarray(full[np.ix_(fit_ind, fit_ind)])
 
     # -- leave-one-out cross-validation at lnprob(p) (include/psoap_gp.h: psoap_chunk_loo) ----------------------------
-    def loo_orbits(self, p_orb, p_gp, mu_GP: float = 1.0):
+    def loo_orbits(self, p_orb, p_gp, mu_GP: float = 1.0, tau=None):
         """Leave-one-out cross-validation of this chunk with the vectors already split: orbital parameters (n_orb,) and GP
         parameters (2c,) -> a ``chunk.LooResult`` with the epoch fields over the worker's own ``epoch_index``.  The
         velocities come from the device (``orbit.velocities``) and the grids are shifted on the host exactly as
         ``fisher_orbits`` shifts them.  A faster-than-light orbit gives ``lnp = -inf`` and NaN, as a negative
         hyper-parameter or a matrix that is not positive definite does.  On a worker with a baseline every prediction is made
         under the marginal likelihood (``ChunkHandle.loo_marg``): an epoch whose only fault is a continuum offset within the
-        prior is not an outlier, and ``lnp`` is what ``lnprob`` returns on this worker."""
+        prior is not an outlier, and ``lnp`` is what ``lnprob`` returns on this worker.  On a ``timevar`` worker every
+        prediction is made under the time-variable kernel at ``tau`` (c,) (``None``: the defaults; ``ChunkHandle.loo_tv``);
+        with a baseline as well it is refused: that combination is not built."""
+        if self.timevar is not None and self.baseline is not None:
+            raise _lib.PsoapError("loo: leave-one-out under a baseline and time scales together is not built")
         if os.environ.get("PSOAP_GPU_SERVER", "").strip().lower() not in ("", "0"):
             raise _lib.PsoapError("loo needs the device in this process (PSOAP_GPU_SERVER serves values only)")
         from .chunk import LooResult
@@ -241,20 +336,24 @@ class ChunkWorker:
         if np.any(np.abs(vel) >= c_kms):
             return LooResult.degenerate(self.handle.N, np.bincount(ep, minlength=ne))
         lwls = self.lwl[None, :] + (-vel[:, ep]) / c_kms          # (as the device shifts: fill_kernels.hpp)
+        taus = self._taus(tau, 1)
+        if taus is not None:
+            return self.handle.loo_tv(lwls, p_gp, taus[0], mu_GP, ep, ne)
         if getattr(self, "baseline", None) is not None:
             return self.handle.loo_marg(lwls, p_gp, mu_GP, ep, ne)
         return self.handle.loo(lwls, p_gp, mu_GP, ep, ne)
 
     def loo(self, p, mu_GP: float = 1.0):
         """One fitted parameter vector (n_fit,) -> the ``chunk.LooResult`` of this chunk there"""
-        p_orb, p_gp = convert_vectors(np.atleast_2d(p), self.model, self.fix_params, **self.defaults)
-        return self.loo_orbits(p_orb[0], p_gp[0], mu_GP)
+        p_orb, p_gp, taus = self.split_vectors(p)
+        return self.loo_orbits(p_orb[0], p_gp[0], mu_GP, None if taus is None else taus[0])
 
     # -- per-epoch velocities free of any orbit (include/psoap_gp.h: psoap_chunk_fisher_vel) ---------------------------
     def _grids_at(self, vel, what, baseline_ok=False):
         """a free velocity table (c, E) -> ``(lwls (c, N), too_fast)``, the grids shifted as ``shifted_grids`` shifts them"""
         if not baseline_ok:
             self._no_baseline(what)
+        self._no_timevar(what)
         if os.environ.get("PSOAP_GPU_SERVER", "").strip().lower() not in ("", "0"):
             raise _lib.PsoapError(f"{what} needs the device in this process (PSOAP_GPU_SERVER serves values only)")
         from .data import c_kms

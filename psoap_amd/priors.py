@@ -60,6 +60,25 @@ def make_prior(model, fix_params=(), **defaults):
     return prior
 
 
+def make_prior_timevar(model, fix_params=(), fit=(), **defaults):
+    """``make_prior`` for fitted vectors that end in time scales (``utils.convert_vectors_timevar``): the model part goes
+    through the model's box, and every fitted ``tau_c`` must be a time scale, ``tau_c > 0`` (``inf`` allowed), otherwise
+    ``-inf`` -- decided here, with no device call."""
+    n_tau = int(np.count_nonzero(np.asarray(fit, dtype=bool)))
+    model_prior = make_prior(model, fix_params, **defaults)
+    if n_tau == 0:
+        return model_prior
+
+    def prior(P):
+        P = np.atleast_2d(np.asarray(P, dtype=np.float64))
+        if P.shape[1] <= n_tau:
+            raise ValueError(f"expected the model's fitted parameters followed by {n_tau} time scale(s)")
+        bad = ~np.all(P[:, -n_tau:] > 0.0, axis=1)
+        return np.where(bad, -np.inf, model_prior(P[:, :-n_tau]))
+
+    return prior
+
+
 def load_user_prior(directory="."):
     """A ``prior(p)`` from ``prior.py`` in ``directory`` if present (sample_parallel.py:362-366), else None.
     The user function is scalar; it is wrapped to take a batch."""

@@ -54,15 +54,40 @@ def load_chunks(config, prefix=""):
     return chunks
 
 
-def proposal_covariance(config, model, dim):
-    """``opt_jump`` covariance if the file loads, else the diagonal of squared hand-specified jumps (:425-431)."""
+def proposal_covariance(config, model, dim, timevar=None):
+    """``opt_jump`` covariance if the file loads, else the diagonal of squared hand-specified jumps (:425-431); with a
+    ``timevar`` block (``timevar_block``) the jumps of the fitted time scales follow the model's."""
     try:
         cov = np.load(config["opt_jump"])
         print("using optimal jumps")
     except Exception:
         print("using hand-specified jumps")
-        cov = utils.convert_dict(model, config["fix_params"], **config["jumps"]) ** 2 * np.eye(dim)
+        jumps = utils.convert_dict(model, config["fix_params"], **config["jumps"])
+        if timevar is not None:
+            jumps = np.concatenate([jumps, timevar["jumps"][timevar["fit"]]])
+        cov = jumps ** 2 * np.eye(dim)
     return cov
+
+
+def timevar_block(config):
+    """config.yaml's optional ``timevar:`` block, or ``None`` when it is absent: ``fit`` (one bool per component), ``tau`` (one
+    time scale in days per component: the starting value of a fitted one, the fixed value of the others; ``.inf`` keeps a
+    component static) and ``jumps`` (one per component; read for the fitted ones when no ``opt_jump`` loads).  Every chunk
+    shares the same time scales.  -> ``{"fit", "tau", "jumps"}`` as arrays; ``fit`` and ``tau`` are what
+    ``ChunkWorker(timevar=...)`` takes."""
+    blk = config.get("timevar")
+    if blk is None:
+        return None
+    unknown = set(blk) - {"fit", "tau", "jumps"}
+    if unknown or "fit" not in blk or "tau" not in blk:
+        raise ValueError(f"config timevar: needs 'fit' and 'tau' (optionally 'jumps'); got {sorted(blk)}")
+    fit, tau, _ = utils.timevar_spec(config["model"], {"fit": list(blk["fit"]), "tau": list(blk["tau"])})
+    jumps = np.asarray(blk.get("jumps", np.zeros(fit.shape[0])), dtype=np.float64)
+    if jumps.shape != fit.shape:
+        raise ValueError("config timevar: 'jumps' must hold one value per component")
+    if np.any(fit & ~np.isfinite(tau)):
+        raise ValueError("config timevar: a fitted time scale needs a finite starting value")
+    return {"fit": fit, "tau": tau, "jumps": jumps}
 
 
 def baseline_block(config):
@@ -88,7 +113,7 @@ class Posterior:
     """
 
     def __init__(self, model, chunks, fix_params=(), parameters=None, soften=1.0, max_batch=1, world=1, rank=0,
-                 device_index=None, prior=None, make_worker=None, baseline=None):
+                 device_index=None, prior=None, make_worker=None, baseline=None, timevar=None):
         self.model = model
         self.fix_params = list(fix_params)
         self.parameters = dict(parameters or {})
@@ -98,8 +123,25 @@ class Posterior:
         self.mine = owned_chunks(self.n_chunks, self.world, self.rank)
         if self.world > 1 and not self.mine:
             raise ValueError("every rank must own at least one chunk (n_chunks >= world)")
-        self.prior = prior if prior is not None else ppriors.make_prior(model, self.fix_params, **self.parameters)
-        if make_worker is None:
+        # time scales (config.yaml's `timevar:` block): fitted vectors end in one tau_c per fitted component; every chunk's
+        # likelihood under the time-variable kernel, chunk by chunk -- never through the group launch or a stream
+        self.timevar = None if timevar is None else {"fit": timevar["fit"], "tau": timevar["tau"]}
+        if prior is not None:
+            self.prior = prior
+        elif self.timevar is not None:
+            self.prior = ppriors.make_prior_timevar(model, self.fix_params, self.timevar["fit"], **self.parameters)
+        else:
+            self.prior = ppriors.make_prior(model, self.fix_params, **self.parameters)
+        if make_worker is None and self.timevar is not None:
+            from .lnprob import ChunkWorker
+
+            def make_worker(ch):
+                return ChunkWorker(model, ch.lwl, ch.fl, ch.sigma, ch.epoch_index, ch.date1D,
+                                   fix_params=self.fix_params, defaults=self.parameters, max_batch=self.max_batch,
+                                   device=device_index, soften=soften, baseline=baseline, timevar=self.timevar)
+        elif self.timevar is not None:
+            raise ValueError("Posterior: time scales need the library's own workers (no make_worker)")
+        elif make_worker is None:
             from .lnprob import ChunkWorker
 
             def make_worker(ch):
@@ -115,7 +157,7 @@ class Posterior:
         self.device_lock = _NoLock()      # ensemble.SharedDeviceLock in dry runs with several ranks on one GPU
         # several chunks on this GPU: ONE launch of the persistent kernel over all of them per evaluation
         self.group = None
-        if baseline is None and len(self.mine) > 1 and all(hasattr(w, "upload_proposals") and hasattr(w, "handle") for w in self.workers.values()):
+        if baseline is None and self.timevar is None and len(self.mine) > 1 and all(hasattr(w, "upload_proposals") and hasattr(w, "handle") for w in self.workers.values()):
             from .chunk import ChunkGroup
             self.group = ChunkGroup([self.workers[k].handle for k in self.mine])
 
@@ -165,12 +207,15 @@ class Posterior:
     def can_stream(self) -> bool:
         """One chunk on this rank, and a worker that has the stream entry points: two resident launches cannot share a
         device (each takes every compute unit), so a rank with several chunks keeps the launch-per-step group path."""
-        return self.baseline is None and len(self.mine) == 1 and all(hasattr(w, "stream_submit") for w in self.workers.values())
+        return self.baseline is None and self.timevar is None and len(self.mine) == 1 and all(hasattr(w, "stream_submit") for w in self.workers.values())
 
     def stream_open(self, scheme: int = -1):
         if self.baseline is not None:
             raise RuntimeError("Posterior.stream_open: the streamed path evaluates the plain likelihood; this posterior has a "
                                "baseline (run without --stream)")
+        if self.timevar is not None:
+            raise RuntimeError("Posterior.stream_open: the streamed path has no temporal factor; this posterior has time scales "
+                               "(run without --stream)")
         if not self.can_stream():
             raise RuntimeError("Posterior.stream_open: needs exactly one chunk on this rank (see can_stream)")
         self.workers[self.mine[0]].stream_open(self.max_batch, scheme)
@@ -243,6 +288,10 @@ def run(config, chunks, run_index=0, n_chains=1, seed=None, world=1, rank=0, dev
     fix = config["fix_params"]
     dim = len(utils.registered_params[model]) - len(fix)
     p0 = utils.convert_dict(model, fix, **pars)
+    tv = timevar_block(config)
+    if tv is not None:
+        p0 = utils.join_vectors_timevar(p0, tv["tau"], tv["fit"])[0]
+        dim = p0.shape[0]
     if world > 1 and seed is None:
         raise ValueError("multi-rank sampling needs an explicit seed so that all ranks draw the same proposals")
     routdirs = [os.path.join(config["outdir"], "run{:0>2}".format(run_index + b)) + "/" for b in range(n_chains)]
@@ -261,7 +310,7 @@ def run(config, chunks, run_index=0, n_chains=1, seed=None, world=1, rank=0, dev
                               + ", ".join(taken))
     post = Posterior(model, chunks, fix, pars, soften=config.get("soften", 1.0), max_batch=n_chains, world=world,
                      rank=rank, device_index=device_index, prior=prior, make_worker=make_worker,
-                     baseline=baseline_block(config))
+                     baseline=baseline_block(config), timevar=tv)
     if device_lock is not None:
         post.device_lock = device_lock
     try:
@@ -272,7 +321,7 @@ def run(config, chunks, run_index=0, n_chains=1, seed=None, world=1, rank=0, dev
             raise RuntimeError("Starting position for Markov Chain evaluates to -np.inf")     # :405-419
         if verbose and rank == 0:
             print("Starting position good. lnp: {}".format(lnp0))
-        cov = proposal_covariance(config, model, dim)
+        cov = proposal_covariance(config, model, dim, tv)
         seeds = [None if seed is None else seed + b for b in range(n_chains)]
         sampler = MultiChainMHSampler(cov, dim, post.lnprob_batch, n_chains, seeds)
         n_iter = int(config["samples"] if iterations is None else iterations)

@@ -48,6 +48,53 @@ def convert_vectors(ps, model, fix_params, **kwargs):
     return np.ascontiguousarray(full[:, :k]), np.ascontiguousarray(full[:, k:])
 
 
+def timevar_spec(model, timevar):
+    """The ``timevar`` block of ``ChunkWorker`` / config.yaml checked and normalised: ``{"fit": [bool per component],
+    "tau": [default per component in days, inf allowed], "times": None | (N,)}`` -> ``(fit (c,) bool, tau (c,) float64, times)``.
+    ``fit`` defaults to all false, ``tau`` to all ``inf``."""
+    c = N_COMPONENTS[model]
+    unknown = set(timevar) - {"fit", "tau", "times"}
+    if unknown:
+        raise ValueError(f"timevar takes 'fit', 'tau' and 'times'; got {sorted(timevar)}")
+    fit = np.asarray(timevar.get("fit", [False] * c))
+    if fit.shape != (c,) or fit.dtype != np.bool_:
+        raise ValueError(f"timevar['fit'] must hold one bool per component ({c} for model {model})")
+    tau = np.asarray(timevar.get("tau", [np.inf] * c), dtype=np.float64)
+    if tau.shape != (c,):
+        raise ValueError(f"timevar['tau'] must hold one default per component ({c} for model {model})")
+    if not np.all(tau > 0.0):
+        raise ValueError("timevar['tau']: every default must be a time scale, positive (inf: a static component)")
+    return fit, tau, timevar.get("times")
+
+
+def convert_vectors_timevar(ps, model, fix_params, fit, tau, **kwargs):
+    """``convert_vectors`` for fitted vectors that carry time scales: ps (B, n_fit + n_tau) is the model's fitted vector
+    followed by one ``tau_c`` in days for every component with ``fit[c]`` true, in component order; the other components
+    stay at their default ``tau[c]``.  -> ``(p_orb (B, n_orb), p_gp (B, n_gp), taus (B, c))``; the first two are exactly
+    ``convert_vectors``' output for the model part.  Nothing is judged here: a ``tau_c <= 0`` is the priors' and the
+    likelihood's business."""
+    fit = np.asarray(fit, dtype=bool)
+    tau = np.asarray(tau, dtype=np.float64)
+    n_tau = int(np.count_nonzero(fit))
+    ps = np.asarray(ps, dtype=np.float64)
+    n_model = len([name for name in registered_params[model] if name not in fix_params])
+    if ps.ndim != 2 or ps.shape[1] != n_model + n_tau:
+        raise ValueError(f"expected (B, {n_model} + {n_tau}) fitted parameters for model {model} with {n_tau} fitted time scale(s)")
+    p_orb, p_gp = convert_vectors(ps[:, :n_model], model, fix_params, **kwargs)
+    taus = np.tile(tau, (ps.shape[0], 1))
+    taus[:, fit] = ps[:, n_model:]
+    return p_orb, p_gp, np.ascontiguousarray(taus)
+
+
+def join_vectors_timevar(ps_model, taus, fit):
+    """The inverse of the split: the model's fitted vectors (B, n_fit) and time scales (B, c) or (c,) -> (B, n_fit + n_tau),
+    the fitted components' ``tau_c`` appended in component order."""
+    ps_model = np.atleast_2d(np.asarray(ps_model, dtype=np.float64))
+    fit = np.asarray(fit, dtype=bool)
+    taus = np.broadcast_to(np.asarray(taus, dtype=np.float64), (ps_model.shape[0], fit.shape[0]))
+    return np.ascontiguousarray(np.concatenate([ps_model, taus[:, fit]], axis=1))
+
+
 def convert_dict(model, fix_params, **kwargs):
     """Fitted-parameter vector from a ``{name: value}`` dictionary such as config.yaml's ``parameters`` or
     ``jumps`` (utils.py:71-84): the registered parameters that are not fixed, in registered order."""
