@@ -190,6 +190,50 @@ int psoap_chunk_lnlike_tv_grad(psoap_chunk *h, int B, int c, const double *lwl,
                                double *lnp, double *grad_gp, double *grad_tau,
                                double *grad_lwl, double *grad_mu);
 
+/* ---- quasi-periodic temporal factor: value and gradient ------------------------------
+ * (not in the reference.)  The time-variable kernel forgets; the line-profile variability
+ * of a spotted, rotating star repeats with the rotation period and decays over the spot
+ * lifetime.  The decaying factor is multiplied by a periodic one:
+ *   K_ij = sum_c a_c^2 exp(p_c d_cij^2 + q_c dt_ij^2 - Gamma_c sin^2(pi dt_ij / P_c))
+ *          + sigma_i^2 delta_ij
+ * over the times of psoap_chunk_set_times; Gamma_c >= 0 is dimensionless, P_c > 0 in days.
+ * Gamma_c = 0 is the time-variable model of psoap_chunk_lnlike_tv_grad, and with
+ * tau_c = +inf as well the static one; tau_c = +inf with Gamma_c > 0 is purely periodic.
+ *
+ * psoap_chunk_lnlike_qp_grad: lwl, gp, tau, lnp, grad_gp, grad_tau, grad_lwl (may be NULL),
+ * grad_mu (may be NULL) as for psoap_chunk_lnlike_tv_grad; gamma, period (B, c) and
+ * grad_gamma, grad_period (B, c).  With e_cij the exponential above the formulas of
+ * psoap_chunk_lnlike_tv_grad hold with that e, and
+ *   d lnp / d Gamma_c = -1/2 a_c^2 sum_ij Q_ij e_cij sin^2(pi dt_ij / P_c)
+ *   d lnp / d P_c     =  1/2 a_c^2 Gamma_c pi / P_c^2 sum_ij Q_ij e_cij dt_ij sin(2 pi dt_ij / P_c)
+ * Still one exp per element and component: the argument is a = p * d * d, a = a + q * dt * dt,
+ * u = dt * rP with rP = 1 / P rounded once, sincospi(u, &s, &co), a = a + ng * s * s with
+ * ng = -Gamma, without contraction (csrc/fill_kernels.hpp, QP); the contraction rebuilds it
+ * the same way and takes sin(2 pi dt / P) = 2 s co from sincospi of the same rounded u.  No atomics: the same
+ * arguments give the same bits alone or in any batch.
+ * Bit-identity.  At Gamma_c = 0 the added term is -0 for every finite s: whatever P, lnp,
+ * grad_gp, grad_tau, grad_lwl and grad_mu have the bits psoap_chunk_lnlike_tv_grad returns
+ * on the same handle, grad_period is exactly 0, and grad_gamma is the score of a test for
+ * periodicity.  At dt = 0, s = +0 exactly: pixels of one epoch see the static kernel.
+ * grad_gp == NULL asks for the value only: every other gradient must then be NULL, and lnp
+ * has the bits of a call that asks for the gradient.  With grad_gp, grad_tau, grad_gamma
+ * and grad_period are required.
+ * Conventions: Gamma_c < 0, NaN or inf, P_c <= 0, NaN, inf or with 1 / P_c not finite, tau_c <= 0 or NaN, a negative
+ * hyper-parameter or a matrix that is not positive definite gives lnp = -inf and NaN in
+ * every gradient entry of that proposal; the other proposals keep their bits.  A call
+ * before psoap_chunk_set_times, on a handle with an open stream or on a handle with a
+ * baseline is refused with a message.  Not built under this kernel: the batch / lnprob(p)
+ * route, Fisher, leave-one-out, predict, draws, the mixture, the marginalised continuum and
+ * the persistent kernel.
+ * Workspace: that of psoap_chunk_lnlike_tv_grad plus 3 doubles per matrix of a group for
+ * each of gamma, period and their gradients and two doubles more per component in a tile
+ * record; psoap_chunk_grad_release frees all of it. */
+int psoap_chunk_lnlike_qp_grad(psoap_chunk *h, int B, int c, const double *lwl,
+                               const double *gp, const double *tau, const double *gamma,
+                               const double *period, double mu_GP, double *lnp,
+                               double *grad_gp, double *grad_tau, double *grad_gamma,
+                               double *grad_period, double *grad_lwl, double *grad_mu);
+
 /* ---- gradient of lnprob(p): through the Kepler solve and the Doppler shift ----------
  * B proposals as for psoap_batch_upload_orbits (needs set_grid + set_dates); B is NOT
  * bound by max_batch.
@@ -771,6 +815,14 @@ int psoap_fill_sym(int device, int c, int N, const double *lwl, const double *gp
 int psoap_fill_sym_tv(int device, int c, int N, const double *lwl, const double *t,
                       const double *gp, const double *tau, const double *sigma,
                       double *out);
+/* psoap_fill_sym under the quasi-periodic kernel (psoap_chunk_lnlike_qp_grad above):
+ * gamma, period (c) beside tau,
+ *   out[i,j] = sum_c amp_c^2 exp(p_c d^2 + q_c dt^2 - gamma_c sin^2(pi dt / period_c)),
+ * the argument formed as that entry describes; everything else as psoap_fill_sym_tv.
+ * With every gamma_c = 0 the matrix is bit-identical to psoap_fill_sym_tv's. */
+int psoap_fill_sym_qp(int device, int c, int N, const double *lwl, const double *t,
+                      const double *gp, const double *tau, const double *gamma,
+                      const double *period, const double *sigma, double *out);
 /* fill_V12_f(psoap/matrix_functions.pyx:61-96): out (M,N),
  * out[i,j] = amp^2 exp(p (lwl_col[j]-lwl_row[i])^2), M = len(lwl_row). */
 int psoap_fill_cross(int device, int M, int N, const double *lwl_row,

@@ -55,6 +55,8 @@ SIGNATURES = {
     "psoap_chunk_set_times": (ctypes.c_int, [_vp, _dp]),
     "psoap_chunk_lnlike_tv_grad": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, ctypes.c_double, _dp, _dp, _dp,
                                                   _dp, _dp]),
+    "psoap_chunk_lnlike_qp_grad": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp, _dp, ctypes.c_double, _dp,
+                                                  _dp, _dp, _dp, _dp, _dp, _dp]),
     "psoap_chunk_lnprob_grad": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _dp, _dp, ctypes.c_double, _dp, _dp, _dp, _dp,
                                                _dp]),
     "psoap_orbit_velocity_jacobian": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, ctypes.c_int, _dp, _dp,
@@ -104,6 +106,7 @@ SIGNATURES = {
     "psoap_chunk_sync": (ctypes.c_int, [_vp]),
     "psoap_fill_sym": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp]),
     "psoap_fill_sym_tv": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "psoap_fill_sym_qp": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "psoap_fill_cross": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, _dp, ctypes.c_double,
                                         ctypes.c_double, _dp]),
     "psoap_predict": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, _dp,

@@ -247,6 +247,36 @@ class ChunkHandle:
         not positive definite gives ``-inf`` and NaN gradients for that proposal."""
         return self._tv(lwls, gp, tau, mu_GP, True)
 
+    # -- quasi-periodic temporal factor (include/psoap_gp.h: psoap_chunk_lnlike_qp_grad) -------------------------------
+    def _qp(self, lwls, gp, tau, gamma, period, mu_GP, want_grad):
+        single, B, c, lwls, gps = self._proposals(lwls, gp)
+        taus, gams, pers = (as_f64(np.atleast_2d(as_f64(v)), (B, c)) for v in (tau, gamma, period))
+        lnp = np.empty(B)
+        entry = "psoap_chunk_lnlike_qp_grad"
+        head = (self._h, B, c, dptr(lwls), dptr(gps), dptr(taus), dptr(gams), dptr(pers), float(mu_GP), dptr(lnp))
+        if not want_grad:
+            check(getattr(self._L, entry)(*head, None, None, None, None, None, None), entry)
+            return float(lnp[0]) if single else lnp
+        g_gp, g_lwl, g_mu = np.empty((B, 2 * c)), np.empty((B, c, self.N)), np.empty(B)
+        g_tau, g_gam, g_per = np.empty((B, c)), np.empty((B, c)), np.empty((B, c))
+        check(getattr(self._L, entry)(*head, dptr(g_gp), dptr(g_tau), dptr(g_gam), dptr(g_per), dptr(g_lwl), dptr(g_mu)), entry)
+        if single:
+            return float(lnp[0]), g_gp[0], g_tau[0], g_gam[0], g_per[0], g_lwl[0], float(g_mu[0])
+        return lnp, g_gp, g_tau, g_gam, g_per, g_lwl, g_mu
+
+    def lnlike_qp(self, lwls, gp, tau, gamma, period, mu_GP: float = 1.0):
+        """The likelihood under the quasi-periodic kernel, ``K_ij = sum_c a_c^2 exp(p_c d^2 - dt^2 / (2 tau_c^2) - gamma_c
+        sin^2(pi dt / period_c)) + sigma^2`` (needs ``set_times``): the shapes of ``lnlike_tv`` with ``gamma`` and ``period``
+        shaped as ``tau``.  ``gamma = 0`` is ``lnlike_tv`` bit for bit whatever ``period``; ``gamma < 0``, NaN or inf,
+        ``period <= 0``, NaN or inf and ``tau <= 0`` or NaN give ``-inf``.  The bits of ``lnp`` are those of ``lnlike_qp_grad``."""
+        return self._qp(lwls, gp, tau, gamma, period, mu_GP, False)
+
+    def lnlike_qp_grad(self, lwls, gp, tau, gamma, period, mu_GP: float = 1.0):
+        """``lnlike_qp`` and its analytic gradient: ``(lnp, grad_gp, grad_tau, grad_gamma, grad_period, grad_lwl, grad_mu)``.
+        At ``gamma = 0`` the outputs ``lnlike_tv_grad`` has carry its bits, ``grad_period`` is exactly 0 and ``grad_gamma`` is
+        the score of a test for periodicity.  A value that is no proposal gives ``-inf`` and NaN gradients there only."""
+        return self._qp(lwls, gp, tau, gamma, period, mu_GP, True)
+
     def fisher(self, lwls, gp, tan_gp, tan_lwl=None, want_mu: bool = False):
         """Fisher information of the likelihood at ``lwls`` (c, N), ``gp`` (2c,) along T <= 32 tangents (include/psoap_gp.h:
         psoap_chunk_fisher): ``tan_gp`` (T, 2c) and ``tan_lwl`` (T, c, N) (``None``: zeros) -> ``F (T, T)``,

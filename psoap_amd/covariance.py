@@ -862,6 +862,213 @@ def _fit_timevar(value_grad, c, gp0, tau0, free_tau, ftol):
     return gp, tau, res
 
 
+# ---- quasi-periodic temporal factor (not in the reference) -------------------------------------
+def _quasiperiodic(lwls, fl, sigma, gp, tau, gamma, period, times, mu_GP, want_grad):
+    """the front of ``lnlike_quasiperiodic`` and ``lnlike_quasiperiodic_grad``: ``_timevar``'s checks with ``gamma < 0``, NaN or
+    inf and ``period <= 0``, NaN or inf beside ``tau <= 0`` or NaN, then the cached handle with ``times - min(times)`` on it"""
+    gp = [float(g) for g in gp]
+    lw = np.stack([as_f64(w) for w in np.atleast_2d(lwls)])
+    c, N = lw.shape
+    if len(gp) != 2 * c:
+        raise ValueError(f"gp must hold {2 * c} values for {c} component(s)")
+    tau, gamma, period = (as_f64(np.atleast_1d(as_f64(v)), (c,)) for v in (tau, gamma, period))
+    t = as_f64(times, (N,))
+    if not np.all(np.isfinite(t)):
+        raise ValueError(_NONFINITE)
+    if any(g < 0.0 for g in gp) or not _quasiperiodic_valid(tau, gamma, period):
+        if not want_grad:
+            return -np.inf
+        nan_c = np.full(c, np.nan)
+        return -np.inf, np.full(len(gp), np.nan), nan_c, nan_c.copy(), nan_c.copy(), np.full(lw.shape, np.nan), np.nan
+    _quasiperiodic_input(lw, sigma, gp)
+    h = _quasiperiodic_handle(fl, sigma, t, "lnlike_quasiperiodic")
+    res = h.lnlike_qp_grad(lw, gp, tau, gamma, period, mu_GP) if want_grad else (h.lnlike_qp(lw, gp, tau, gamma, period, mu_GP),)
+    if not np.isneginf(res[0]) and not (np.all(np.isfinite(np.asarray(fl, dtype=np.float64))) and np.isfinite(mu_GP)):
+        raise ValueError(_NONFINITE)
+    if not want_grad:
+        return np.float64(res[0])
+    return (np.float64(res[0]),) + tuple(res[1:6]) + (np.float64(res[6]),)
+
+
+def _quasiperiodic_valid(tau, gamma, period):
+    """every tau is a time scale, every gamma finite and not negative, every period positive and finite with a finite
+    reciprocal (qp_refused of psoap_amd/csrc/qp_plan.hpp); any shape"""
+    tau, gamma, period = (np.asarray(v, dtype=np.float64) for v in (tau, gamma, period))
+    with np.errstate(all="ignore"):
+        return bool(np.all(tau > 0.0) and np.all((gamma >= 0.0) & np.isfinite(gamma)) and
+                    np.all((period > 0.0) & np.isfinite(period) & np.isfinite(1.0 / period)))
+
+
+def _quasiperiodic_input(lw, sigma, gp):
+    """the input that ``lnlike_grad`` refuses with an exception, refused the same way: a zero length scale, a matrix that is
+    not finite"""
+    if any(l == 0.0 for l in gp[1::2]):
+        raise ZeroDivisionError("float division")
+    if not _matrix_is_finite(lw, sigma, gp):
+        raise ValueError(_NONFINITE)
+
+
+def _quasiperiodic_handle(fl, sigma, t, who):
+    """the cached handle of ``(fl, sigma)`` without a baseline and with ``t - min(t)`` on it (``_timevar``'s bookkeeping)"""
+    h = _chunk_without_baseline(fl, sigma)
+    if not hasattr(h, "lnlike_qp_grad"):
+        raise _lib.PsoapError(f"{who} needs the device in this process (PSOAP_GPU_SERVER serves the static likelihood only)")
+    t = t - t.min()
+    if getattr(h, "_tv_times", None) is None or not np.array_equal(h._tv_times, t):
+        h.set_times(t)
+        h._tv_times = t
+    return h
+
+
+def lnlike_quasiperiodic(lwls, fl, sigma, gp, tau, gamma, period, times, mu_GP=1.0):
+    """The likelihood under quasi-periodic component spectra: ``lnlike_timevar``'s kernel times a periodic factor,
+    ``K_ij = sum_c a_c^2 exp(p_c d_cij^2 - dt_ij^2 / (2 tau_c^2) - gamma_c sin^2(pi dt_ij / period_c)) + sigma_i^2 delta_ij``.
+    ``gamma`` (c,) is dimensionless, ``period`` (c,) in the unit of ``times``.  ``gamma_c = 0`` is ``lnlike_timevar`` bit for
+    bit whatever the period; ``tau_c = inf`` with ``gamma_c > 0`` is a purely periodic component.  ``gamma < 0``, NaN or inf,
+    ``period <= 0``, NaN or inf and ``tau <= 0`` or NaN give ``-inf``; other degenerate input follows ``lnlike_timevar``."""
+    return _quasiperiodic(lwls, fl, sigma, gp, tau, gamma, period, times, mu_GP, False)
+
+
+def lnlike_quasiperiodic_grad(lwls, fl, sigma, gp, tau, gamma, period, times, mu_GP=1.0):
+    """``(lnp, grad_gp (2c,), grad_tau (c,), grad_gamma (c,), grad_period (c,), grad_lwl (c, N), grad_mu)``:
+    ``lnlike_quasiperiodic`` and its analytic derivatives on the device (``ChunkHandle.lnlike_qp_grad``).  ``grad_period`` is
+    exactly 0 where ``gamma = 0``; ``grad_gamma`` there is the score of a test for periodicity at that period."""
+    return _quasiperiodic(lwls, fl, sigma, gp, tau, gamma, period, times, mu_GP, True)
+
+
+def default_period_bounds(times):
+    """``(twice the smallest positive separation of two epochs, the span)`` of ``times``: shorter periods are not sampled,
+    longer ones are not covered once"""
+    t = np.unique(as_f64(times))
+    if t.shape[0] < 2:
+        raise ValueError("period bounds need at least two different times")
+    return 2.0 * float(np.diff(t).min()), float(t[-1] - t[0])
+
+
+def optimize_GP_quasiperiodic(lwls, fl, sigma, gp0, tau0, gamma0, period0, times, free=None, period_bounds=None, mu_GP=1.0,
+                              ftol=1e-10, full_output=False):
+    """L-BFGS-B fit of ``lnlike_quasiperiodic`` from ``(gp0, tau0, gamma0, period0)`` on the device gradient, in the logarithm
+    of every parameter (``_fit_timevar``'s pattern).  ``free``: a dictionary of (c,) booleans under ``"tau"``, ``"gamma"`` and
+    ``"period"``; the defaults are every finite ``tau0`` and, for both others, every ``gamma0 > 0``.  A free ``gamma`` must
+    start positive.  ``period_bounds`` ``(lo, hi)`` hold every free period; ``None``: ``default_period_bounds(times)``.
+    Returns ``(gp, tau, gamma, period)``; with ``full_output`` ``(gp, tau, gamma, period, lnp, lnp_gamma0, lnp_timevar,
+    result)``: the likelihood reached, the likelihood at ``gamma = 0`` on the same ``(gp, tau)``, and the likelihood of the
+    time-variable model re-fitted from there (``_fit_timevar`` at ``gamma = 0``).  ``lnp - lnp_timevar`` is the periodicity
+    statistic: what the periodic factor gains over the best time-variable fit."""
+    lw = np.stack([as_f64(w) for w in np.atleast_2d(lwls)])
+    c = lw.shape[0]
+    if period_bounds is None:
+        period_bounds = default_period_bounds(times)
+
+    def value_grad(gp, tau, gamma, period):
+        return lnlike_quasiperiodic_grad(lw, fl, sigma, gp, tau, gamma, period, times, mu_GP)[:5]
+
+    gp, tau, gamma, period, res = _fit_quasiperiodic(value_grad, c, gp0, tau0, gamma0, period0, free, period_bounds, ftol)
+    if not full_output:
+        return gp, tau, gamma, period
+    free_tau = None if free is None or "tau" not in free else free["tau"]
+    lnp_gamma0, lnp_tv = _quasiperiodic_null(value_grad, c, gp, tau, free_tau, ftol)
+    return gp, tau, gamma, period, -float(res["fun"]), lnp_gamma0, lnp_tv, res
+
+
+def _fit_quasiperiodic(value_grad, c, gp0, tau0, gamma0, period0, free, period_bounds, ftol):
+    """The driver of ``optimize_GP_quasiperiodic``: L-BFGS-B over ``x = (log gp, log tau[free], log gamma[free], log
+    period[free])`` on ``value_grad(gp, tau, gamma, period) -> (lnp, grad_gp, grad_tau, grad_gamma, grad_period)`` ->
+    ``(gp, tau, gamma, period, SciPy's result)``.  (Nothing here knows the device: the tests run it on the float64 twin.)"""
+    from scipy.optimize import minimize
+    g0 = np.maximum(as_f64(gp0, (2 * c,)), GP_LOWER_BOUND)
+    t0, m0, p0 = (as_f64(np.atleast_1d(as_f64(v)), (c,)).copy() for v in (tau0, gamma0, period0))
+    free = {} if free is None else dict(free)
+    if set(free) - {"tau", "gamma", "period"}:
+        raise ValueError(f"free takes 'tau', 'gamma' and 'period'; got {sorted(free)}")
+    f_t = np.asarray(free.get("tau", np.isfinite(t0)), dtype=bool).reshape(c)
+    f_m = np.asarray(free.get("gamma", m0 > 0.0), dtype=bool).reshape(c)
+    f_p = np.asarray(free.get("period", m0 > 0.0), dtype=bool).reshape(c)
+    if not np.all(t0 > 0.0) or not np.all(np.isfinite(t0[f_t])):
+        raise ValueError("tau0 must be positive, and finite where free['tau'] is set")
+    if not np.all((m0 >= 0.0) & np.isfinite(m0)) or not np.all(m0[f_m] > 0.0):
+        raise ValueError("gamma0 must be finite and not negative, and positive where free['gamma'] is set")
+    if not np.all((p0 > 0.0) & np.isfinite(p0)):
+        raise ValueError("period0 must be positive and finite")
+    lo, hi = float(period_bounds[0]), float(period_bounds[1])
+    if not (0.0 < lo < hi) or not np.all((p0[f_p] >= lo) & (p0[f_p] <= hi)):
+        raise ValueError("period_bounds must be 0 < lo < hi and hold every free period0")
+    n_t, n_m = int(f_t.sum()), int(f_m.sum())
+
+    def unpack(x):
+        tau, gamma, period = t0.copy(), m0.copy(), p0.copy()
+        tau[f_t] = np.exp(x[2 * c:2 * c + n_t])
+        gamma[f_m] = np.exp(x[2 * c + n_t:2 * c + n_t + n_m])
+        period[f_p] = np.exp(x[2 * c + n_t + n_m:])
+        return np.exp(x[:2 * c]), tau, gamma, period
+
+    def func(x):
+        gp, tau, gamma, period = unpack(x)
+        lnp, g_gp, g_tau, g_gamma, g_period = value_grad(gp, tau, gamma, period)
+        if not np.isfinite(lnp):
+            return np.inf, np.zeros_like(x)
+        return -lnp, -np.concatenate([g_gp * gp, g_tau[f_t] * tau[f_t], g_gamma[f_m] * gamma[f_m], g_period[f_p] * period[f_p]])
+
+    x0 = np.concatenate([np.log(g0), np.log(t0[f_t]), np.log(m0[f_m]), np.log(p0[f_p])])
+    bounds = [(np.log(GP_LOWER_BOUND), None)] * (2 * c) + [(None, None)] * (n_t + n_m) + [(np.log(lo), np.log(hi))] * int(f_p.sum())
+    res = minimize(func, x0, jac=True, method="L-BFGS-B", bounds=bounds, options={"ftol": ftol})
+    gp, tau, gamma, period = unpack(res["x"])
+    return gp, tau, gamma, period, res
+
+
+def _quasiperiodic_null(value_grad, c, gp, tau, free_tau, ftol):
+    """The two ``gamma = 0`` values of ``optimize_GP_quasiperiodic`` on ``value_grad`` (the driver's): ``lnp`` at ``(gp, tau)``
+    as they are, and the maximum ``_fit_timevar`` reaches from there -> ``(lnp_gamma0, lnp_timevar)``"""
+    zero, one = np.zeros(c), np.ones(c)
+
+    def null(gp_, tau_):
+        return value_grad(gp_, tau_, zero, one)[:3]
+
+    lnp_gamma0 = float(null(np.asarray(gp, dtype=np.float64), np.asarray(tau, dtype=np.float64))[0])
+    _gp, _tau, res = _fit_timevar(null, c, gp, tau, free_tau, ftol)
+    return lnp_gamma0, -float(res["fun"])
+
+
+def period_scan(lwls, fl, sigma, gp, tau, gamma, times, periods, component=0, mu_GP=1.0):
+    """The likelihood periodogram of one component: ``lnp(P)`` of ``lnlike_quasiperiodic`` over the trial ``periods`` (n,) of
+    ``component`` in ONE value-only batched call (``B = n``), every other parameter held; and the score ``d lnp / d gamma`` of
+    that component at ``gamma = 0`` for every trial period, from one gradient call -- where the time-variable model is all
+    there is the score is what a periodic factor of that period would gain to first order.  ``periods`` (n,) are the trial
+    periods of ``component``; another component with ``gamma > 0`` needs a period of its own, and then ``periods`` must be
+    (n, c), every component's (``ValueError`` otherwise: no ``gamma`` is changed behind the caller's back).  The score call
+    takes every ``gamma = 0``.  Degenerate input follows ``lnlike_quasiperiodic``: a negative hyper-parameter, a ``tau`` or
+    ``gamma`` that is none gives ``-inf`` and NaN throughout, a trial period that is none ``-inf`` and NaN in its place, a zero
+    length scale or non-finite input the exception.  -> ``(lnp (n,), score (n,))``"""
+    lw = np.stack([as_f64(w) for w in np.atleast_2d(lwls)])
+    c, N = lw.shape
+    k = int(component)
+    if not 0 <= k < c:
+        raise ValueError(f"component must be in [0, {c})")
+    gp, tau, gamma = as_f64(gp, (2 * c,)), as_f64(np.atleast_1d(as_f64(tau)), (c,)), as_f64(np.atleast_1d(as_f64(gamma)), (c,))
+    per = as_f64(periods)
+    if per.ndim == 1:
+        if np.any(np.delete(gamma, k) != 0.0):
+            raise ValueError("another component has gamma != 0 and needs a period of its own: give periods as (n, c)")
+        trial = per
+        per = np.ones((per.shape[0], c))      # (the period of a component at gamma = 0 does not enter: any)
+        per[:, k] = trial
+    n = per.shape[0]
+    per = as_f64(per, (n, c))
+    t = as_f64(times, (N,))
+    if not np.all(np.isfinite(t)):
+        raise ValueError(_NONFINITE)
+    if np.any(gp < 0.0) or not _quasiperiodic_valid(tau, gamma, 1.0):
+        return np.full(n, -np.inf), np.full(n, np.nan)
+    _quasiperiodic_input(lw, sigma, [float(g) for g in gp])
+    if not (np.all(np.isfinite(np.asarray(fl, dtype=np.float64))) and np.isfinite(mu_GP)):
+        raise ValueError(_NONFINITE)
+    h = _quasiperiodic_handle(fl, sigma, t, "period_scan")
+    lws, gps, taus = np.broadcast_to(lw, (n, c, N)), np.broadcast_to(gp, (n, 2 * c)), np.broadcast_to(tau, (n, c))
+    lnp = h.lnlike_qp(lws, gps, taus, np.broadcast_to(gamma, (n, c)), per, mu_GP)
+    score = h.lnlike_qp_grad(lws, gps, taus, np.zeros((n, c)), per, mu_GP)[3][:, k]
+    return np.asarray(lnp), np.asarray(score)
+
+
 def _timevar_front(lwls, gp, tau):
     """``(lw (c, N), gp, tau (c,), degenerate)`` of a time-variable analysis call: the checks of ``_timevar`` up to the device
     -- ``degenerate``: a negative hyper-parameter or a ``tau <= 0`` or NaN, to be answered before any work"""

@@ -8,15 +8,23 @@
 // from the host (lwl) or, with lwl == nullptr, from the orbits p_orb of `model` (orbit_front, orbit_back).  With `tau` (B, c)
 // K is the time-variable kernel over the handle's times: the TV fill, contraction and finishing sums, and grad_tau beside
 // grad_gp -- plain, or with `marg` on Kt = K_tv + Ht Ht^T (k_marg_tv_grad_contract).  `contract` false is the value only: no
-// contraction, no finishing sums, no gradient touched.
+// contraction, no finishing sums, no gradient touched.  With `qp` (plain, host grids, with `tau`) K is the quasi-periodic
+// kernel: Gamma and P (B, c) go up beside tau, the QP fill, contraction and finishing sums run, and grad_gamma and grad_period
+// come down beside grad_tau.
+struct QpArgs {
+    const double *gamma, *period;
+    double *grad_gamma, *grad_period;
+};
+
 static int grad_run(psoap_chunk* h, bool marg, int B, int c, const double* lwl, int model, const double* p_orb,
                     const double* gp, const double* tau, double mu_GP, double* lnp, double* parts, double* grad_gp,
-                    double* grad_tau, double* grad_lwl, double* grad_mu, double* grad_orb, double* grad_vel, bool contract)
+                    double* grad_tau, double* grad_lwl, double* grad_mu, double* grad_orb, double* grad_vel, bool contract,
+                    const QpArgs* qp = nullptr)
 {
     const bool orbits = lwl == nullptr, tv = tau != nullptr;
     DEVICE_SCOPE(h->device);
     if (int rc = enter_device(h->device)) return rc;
-    const Factored fac = factored(h, marg, B, tv);
+    const Factored fac = factored(h, marg, B, tv, qp != nullptr);
     const int N = h->N, Npad = h->Npad, P = h->P, G = fac.G, ld = fac.ld, ntiles = P * (P + 1) / 2;
     const size_t mstride = fac.mstride;
     const int ne = h->n_epochs, np = orbits ? orbit_n_params(model) : 0;
@@ -34,11 +42,21 @@ static int grad_run(psoap_chunk* h, bool marg, int B, int c, const double* lwl, 
         else if (int rc = orbit_front(h, w, s, nb, c, model, np, p_orb + (size_t)b0 * np)) return rc;
         HIP_TRY(hipMemcpyAsync(w.Gp, gp + (size_t)b0 * 2 * c, sizeof(double) * (size_t)nb * 2 * c, hipMemcpyHostToDevice, s));
         if (tv) HIP_TRY(hipMemcpyAsync(w.Tau, tau + (size_t)b0 * c, sizeof(double) * (size_t)nb * c, hipMemcpyHostToDevice, s));
+        if (qp) {
+            HIP_TRY(hipMemcpyAsync(w.Gamma, qp->gamma + (size_t)b0 * c, sizeof(double) * (size_t)nb * c, hipMemcpyHostToDevice, s));
+            HIP_TRY(hipMemcpyAsync(w.Period, qp->period + (size_t)b0 * c, sizeof(double) * (size_t)nb * c, hipMemcpyHostToDevice, s));
+        }
         if (int rc = factor_group(h, fac, s, nb, c, mu_GP, true)) return rc;
         if (contract) {
             if (int rc = prof_launch(h, s, PSOAP_K_GRAD, TILE_FLOPS * tile_units(P, fac.Q) * nb, 0.0, [&] {
                     with_components(c, [&](auto nc) {
-                        if (marg && tv)
+                        if (qp)
+                            hipLaunchKernelGGL(k_qp_grad_contract<nc()>, dim3(ntiles, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s,
+                                               (const double*)w.A.p, mstride, ld, N, Npad, P, (const double*)w.Lwl.p,
+                                               (const double*)h->dTimes.p, (const double*)w.Gp.p, (const double*)w.Tau.p,
+                                               (const double*)w.Gamma.p, (const double*)w.Period.p, (const double*)w.Alpha.p,
+                                               w.Part.p);
+                        else if (marg && tv)
                             hipLaunchKernelGGL(k_marg_tv_grad_contract<nc()>, dim3(ntiles, nb), dim3(GEMM_THREADS), GEMM_LDS_BYTES,
                                                s, (const double*)w.A.p, mstride, ld, N, Npad, P, (const double*)w.Lwl.p,
                                                (const double*)h->dTimes.p, (const double*)w.Gp.p, (const double*)w.Tau.p,
@@ -61,7 +79,12 @@ static int grad_run(psoap_chunk* h, bool marg, int B, int c, const double* lwl, 
                     });
                 })) return rc;
             if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
-                    if (tv)
+                    if (qp)
+                        hipLaunchKernelGGL(k_qp_grad_finish, dim3(P + 1, nb), dim3(128), 0, s, (const double*)w.Part.p,
+                                           (const double*)w.Alpha.p, (const double*)w.Gp.p, (const double*)w.Tau.p,
+                                           (const double*)w.Gamma.p, (const double*)w.Period.p, c, N, Npad, P, w.GradGp.p,
+                                           w.GradTau.p, w.GradGamma.p, w.GradPeriod.p, w.GradX.p, w.GradMu.p);
+                    else if (tv)
                         hipLaunchKernelGGL(k_tv_grad_finish, dim3(P + 1, nb), dim3(128), 0, s, (const double*)w.Part.p,
                                            (const double*)w.Alpha.p, (const double*)w.Gp.p, (const double*)w.Tau.p, c, N, Npad, P,
                                            w.GradGp.p, w.GradTau.p, w.GradX.p, w.GradMu.p);
@@ -76,6 +99,10 @@ static int grad_run(psoap_chunk* h, bool marg, int B, int c, const double* lwl, 
         if (contract) {
             HIP_TRY(hipMemcpyAsync(grad_gp + (size_t)b0 * 2 * c, w.GradGp, sizeof(double) * (size_t)nb * 2 * c, hipMemcpyDeviceToHost, s));
             if (tv) HIP_TRY(hipMemcpyAsync(grad_tau + (size_t)b0 * c, w.GradTau, sizeof(double) * (size_t)nb * c, hipMemcpyDeviceToHost, s));
+            if (qp) {
+                HIP_TRY(hipMemcpyAsync(qp->grad_gamma + (size_t)b0 * c, w.GradGamma, sizeof(double) * (size_t)nb * c, hipMemcpyDeviceToHost, s));
+                HIP_TRY(hipMemcpyAsync(qp->grad_period + (size_t)b0 * c, w.GradPeriod, sizeof(double) * (size_t)nb * c, hipMemcpyDeviceToHost, s));
+            }
             if (grad_lwl)
                 HIP_TRY(hipMemcpyAsync(grad_lwl + (size_t)b0 * c * N, w.GradX, sizeof(double) * (size_t)nb * c * N, hipMemcpyDeviceToHost, s));
             if (grad_mu) HIP_TRY(hipMemcpyAsync(grad_mu + b0, w.GradMu, sizeof(double) * nb, hipMemcpyDeviceToHost, s));
@@ -89,14 +116,20 @@ static int grad_run(psoap_chunk* h, bool marg, int B, int c, const double* lwl, 
         HIP_TRY(hipStreamSynchronize(s));       // the next group reuses the workspace and the caller's arrays are pageable
     }
     if (collect_timings(h)) return 1;
-    // a negative hyper-parameter, a faster-than-light orbit, a tau that is no time scale, a K (or under the baseline an M) that
-    // does not factor -> -inf, and no gradient there
+    // a negative hyper-parameter, a faster-than-light orbit, a tau that is no time scale, a Gamma or P that is none (qp_refused),
+    // a K (or under the baseline an M) that does not factor -> -inf, and no gradient there
     for (int b = 0; b < B; ++b)
         if (values_out(out.data(), fac.out_stride, b,
-                       proposal_refused(gp, c, b, orbits ? fast.data() : nullptr) || (tv && tau_refused(tau, c, b)), lnp,
-                       fac.parts ? parts : nullptr) &&
-            contract)
+                       proposal_refused(gp, c, b, orbits ? fast.data() : nullptr) || (tv && tau_refused(tau, c, b)) ||
+                           (qp && qp_refused(qp->gamma, qp->period, c, b)),
+                       lnp, fac.parts ? parts : nullptr) &&
+            contract) {
             poison_gradient(b, c, N, ne, np, grad_gp, grad_tau, grad_lwl, grad_mu, grad_orb, grad_vel);
+            if (qp) {
+                fill_nan(qp->grad_gamma, b, c);
+                fill_nan(qp->grad_period, b, c);
+            }
+        }
     return 0;
 }
 

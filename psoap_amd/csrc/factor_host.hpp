@@ -21,9 +21,10 @@ static double tile_units(int P, int Q)
 // The gradient workspace for groups of G matrices of mstride doubles each: what the factorisation needs, always; alpha and
 // its partial sums (`alpha`); the contraction's partial tiles and the three gradients (`contract`); with np > 0 the orbit
 // entry's buffers for c components and np orbital parameters, and the epoch lists of the fold.  `tv`: the time scales, the
-// longer tile record of the time-variable contraction and, with `contract`, dlnL/dtau.
+// longer tile record of the time-variable contraction and, with `contract`, dlnL/dtau.  `qp` (with `tv`): Gamma and P, the
+// still longer record of the quasi-periodic contraction (QpTile) and dlnL/dGamma, dlnL/dP.
 static int grad_ws_need(psoap_chunk* h, GradWs& w, int G, size_t mstride, bool alpha, bool contract, int c = 0, int np = 0,
-                        bool tv = false)
+                        bool tv = false, bool qp = false)
 {
     const int N = h->N, Npad = h->Npad, ne = h->n_epochs;
     HIP_TRY(w.A.need((size_t)G * mstride));
@@ -37,12 +38,21 @@ static int grad_ws_need(psoap_chunk* h, GradWs& w, int G, size_t mstride, bool a
         HIP_TRY(w.APart.need((size_t)G * ((Npad + 255) / 256) * Npad));
     }
     if (tv) HIP_TRY(w.Tau.need((size_t)G * 3));
+    if (qp) {
+        HIP_TRY(w.Gamma.need((size_t)G * 3));
+        HIP_TRY(w.Period.need((size_t)G * 3));
+    }
     if (contract) {
-        HIP_TRY(w.Part.need((size_t)G * (h->P * (h->P + 1) / 2) * (tv ? GradTile<true>::DOUBLES : GradTile<false>::DOUBLES)));
+        HIP_TRY(w.Part.need((size_t)G * (h->P * (h->P + 1) / 2) *
+                            (qp ? QpTile::DOUBLES : tv ? GradTile<true>::DOUBLES : GradTile<false>::DOUBLES)));
         HIP_TRY(w.GradGp.need((size_t)G * 6));
         HIP_TRY(w.GradX.need((size_t)G * 3 * N));
         HIP_TRY(w.GradMu.need(G));
         if (tv) HIP_TRY(w.GradTau.need((size_t)G * 3));
+        if (qp) {
+            HIP_TRY(w.GradGamma.need((size_t)G * 3));
+            HIP_TRY(w.GradPeriod.need((size_t)G * 3));
+        }
     }
     if (np > 0) {
         HIP_TRY(w.Porb.need((size_t)G * np));
@@ -56,10 +66,18 @@ static int grad_ws_need(psoap_chunk* h, GradWs& w, int G, size_t mstride, bool a
 }
 
 // K (upper tiles) of the nb matrices whose grids and hyper-parameters are in w.Lwl and w.Gp, into w.A as the caller lays it out
-// (`tv`: under the time-variable kernel -- k_fill_sym_tv with the handle's times and w.Tau)
-static void launch_grad_fill(const psoap_chunk* h, GradWs& w, hipStream_t s, int nb, int c, size_t mstride, int ld, bool tv = false)
+// (`tv`: under the time-variable kernel -- k_fill_sym_tv with the handle's times and w.Tau; `qp` with it: under the
+// quasi-periodic one -- k_fill_sym_qp with w.Gamma and w.Period as well)
+static void launch_grad_fill(const psoap_chunk* h, GradWs& w, hipStream_t s, int nb, int c, size_t mstride, int ld, bool tv = false,
+                             bool qp = false)
 {
     with_components(c, [&](auto nc) {
+        if (qp) {
+            hipLaunchKernelGGL(k_fill_sym_qp<nc()>, dim3(h->P * (h->P + 1) / 2, nb), dim3(256), 0, s, w.A.p, mstride, ld, h->N, h->P,
+                               (const double*)w.Lwl.p, (const double*)h->dTimes.p, (const double*)w.Gp.p, (const double*)w.Tau.p,
+                               (const double*)w.Gamma.p, (const double*)w.Period.p, (const double*)h->dSigma.p, 1);
+            return;
+        }
         if (tv) {
             hipLaunchKernelGGL(k_fill_sym_tv<nc()>, dim3(h->P * (h->P + 1) / 2, nb), dim3(256), 0, s, w.A.p, mstride, ld, h->N, h->P,
                                (const double*)w.Lwl.p, (const double*)h->dTimes.p, (const double*)w.Gp.p, (const double*)w.Tau.p,
@@ -177,12 +195,12 @@ static int grad_epoch_lists(psoap_chunk* h, GradWs& w, hipStream_t s)
 
 // The staged factorisation of [K | I] for the nb matrices whose grids and hyper-parameters are in w.Lwl and w.Gp: afterwards
 // the appended block holds W = U^-T, w.R holds z = U^-T (fl - mu_GP) and w.Acc the block records.
-static int grad_factor(psoap_chunk* h, GradWs& w, hipStream_t s, int nb, int c, double mu_GP, bool tv = false)
+static int grad_factor(psoap_chunk* h, GradWs& w, hipStream_t s, int nb, int c, double mu_GP, bool tv = false, bool qp = false)
 {
     const int N = h->N, Npad = h->Npad, P = h->P, ld = 2 * h->Npad;
     const size_t mstride = (size_t)Npad * ld;
     if (int rc = prof_launch(h, s, PSOAP_K_FILL, 0.0, (double)nb * 12.0 * N * (N + 1.0), [&] {
-            launch_grad_fill(h, w, s, nb, c, mstride, ld, tv);
+            launch_grad_fill(h, w, s, nb, c, mstride, ld, tv, qp);
             hipLaunchKernelGGL(k_grad_init, dim3(P * (P + 1) / 2, nb), dim3(256), 0, s, w.A.p, mstride, ld, Npad, P);
         })) return rc;
     if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
@@ -332,6 +350,7 @@ static void launch_marg_finish(const psoap_chunk* h, const GradWs& w, MargWs& m,
 struct Factored {
     bool marg;
     bool tv;                     // K under the time-variable kernel (fill_kernels.hpp), plain or marginal: the fill reads w.Tau
+    bool qp;                     // ... under the quasi-periodic one (plain only, and tv is set with it): w.Gamma and w.Period too
     int G;                       // matrices per group
     int ld;                      // doubles per row of a matrix in w.A, mstride from one matrix to the next
     size_t mstride;
@@ -416,13 +435,14 @@ static int marg_grad_factor(psoap_chunk* h, const Factored& fac, hipStream_t s, 
 }
 
 // `Factored` of a call with B matrices; the workspaces it points into exist afterwards, empty until factored_ws_need
-static Factored factored(psoap_chunk* h, bool marg, int B, bool tv = false)
+static Factored factored(psoap_chunk* h, bool marg, int B, bool tv = false, bool qp = false)
 {
     const int Npad = h->Npad;
     if (!h->gws) h->gws.reset(new GradWs());
     Factored fac{};
     fac.marg = fac.parts = marg;
-    fac.tv = tv;
+    fac.tv = tv || qp;
+    fac.qp = qp;
     if (!marg) {
         fac.G = grad_group_size(B, Npad);
         fac.ld = 2 * Npad;
@@ -454,7 +474,7 @@ static Factored factored(psoap_chunk* h, bool marg, int B, bool tv = false)
 static int factored_ws_need(psoap_chunk* h, const Factored& fac, hipStream_t s, bool values, bool contract, int c = 0, int np = 0)
 {
     GradWs& w = *h->gws;
-    if (int rc = grad_ws_need(h, w, fac.G, fac.mstride, values || fac.marg, contract, c, np, fac.tv)) return rc;
+    if (int rc = grad_ws_need(h, w, fac.G, fac.mstride, values || fac.marg, contract, c, np, fac.tv, fac.qp)) return rc;
     if (!fac.marg) {
         if (values) HIP_TRY(w.Out.need(fac.G));
         return 0;
@@ -474,7 +494,7 @@ static int factor_group(psoap_chunk* h, const Factored& fac, hipStream_t s, int 
                         const X* extra = nullptr)
 {
     GradWs& w = *h->gws;
-    if (int rc = fac.marg ? marg_grad_factor(h, fac, s, nb, c, mu_GP) : grad_factor(h, w, s, nb, c, mu_GP, fac.tv)) return rc;
+    if (int rc = fac.marg ? marg_grad_factor(h, fac, s, nb, c, mu_GP) : grad_factor(h, w, s, nb, c, mu_GP, fac.tv, fac.qp)) return rc;
     const bool finish = values && !fac.marg;
     if (!finish && !extra) return 0;
     return prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {

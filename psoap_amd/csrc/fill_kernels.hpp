@@ -374,6 +374,153 @@ __global__ __launch_bounds__(256) void k_fill_sym_tv(double* __restrict__ Kbase,
     }
 }
 
+// Quasi-periodic temporal factor (`QP`): the decaying factor of the time-variable kernel times a periodic one,
+//   K_ij = sum_c a_c^2 exp(p_c d_cij^2 + q_c dt_ij^2 - Gamma_c sin^2(pi dt_ij / P_c)) + sigma_i^2 delta_ij
+// Gamma_c >= 0 (dimensionless), P_c > 0 (days).  Still one exp: the periodic term is the third term of the same argument,
+//   a = p2 * d * d;  a = a + q2 * dt * dt;  u = dt * rP;  sincospi(u, &s, &co);  a = a + ng * s * s
+// every operation rounded on its own, rP = 1 / P and ng = -Gamma rounded once per component and matrix by the pair below.
+// Bit-identity: at Gamma = 0, ng = -0, (-0 * s) * s is -0 for every finite s and a + (-0) has the bits of a -- the matrix of
+// k_fill_sym_tv, whatever P; at dt = 0, sincospi(0) gives s = +0 exactly -- within an epoch the blocks of the static fill.
+__device__ __forceinline__ double qp_rp(double period)
+{
+#pragma clang fp contract(off)
+    return 1.0 / period;
+}
+
+__device__ __forceinline__ double qp_ng(double gamma) { return -gamma; }
+
+// k_fill_sym_tv with the periodic term: gam (B, C), per (B, C).  The layout, the row times in LDS, the two column times per
+// lane, one exp_nonpos_batch<8> per component and step, the diagonal rule, the identity padding and upper_only are
+// k_fill_sym_tv's.  The underflow shortcut works on the full three-term argument; since the periodic term is <= 0 it may be
+// taken one step early, on the two-term argument, before any sincospi is evaluated -- exp() is +0 either way.
+template <int C>
+__global__ __launch_bounds__(256) void k_fill_sym_qp(double* __restrict__ Kbase, size_t mat_stride, int ld, int N, int P,
+                                                     const double* __restrict__ lwl, const double* __restrict__ t,
+                                                     const double* __restrict__ gp, const double* __restrict__ tau,
+                                                     const double* __restrict__ gam, const double* __restrict__ per,
+                                                     const double* __restrict__ sigma, int upper_only)
+{
+    __shared__ double xrow[C][NB];
+    __shared__ double trow[NB];
+    __shared__ double srow[NB];
+    const int b = blockIdx.y;
+    int ti, tj;
+    if (upper_only) {
+        decode_upper(blockIdx.x, P, ti, tj);
+    } else {
+        ti = blockIdx.x / P;
+        tj = blockIdx.x % P;
+    }
+    const int tid = threadIdx.x;
+    const int i0 = ti * NB, j0 = tj * NB;
+    const double* lw = lwl + (size_t)b * C * N;
+    GpDev g;
+    load_gp(gp + (size_t)b * 2 * C, C, g);
+    double q2[C], rP[C], ng[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        q2[c] = tv_q2(tau[(size_t)b * C + c]);
+        rP[c] = qp_rp(per[(size_t)b * C + c]);
+        ng[c] = qp_ng(gam[(size_t)b * C + c]);
+    }
+    double dsum = g.a2[0];
+    {
+#pragma clang fp contract(off)
+        for (int c = 1; c < C; ++c) dsum = dsum + g.a2[c];
+    }
+
+    if (tid < NB) {
+        int i = i0 + tid;
+#pragma unroll
+        for (int c = 0; c < C; ++c) xrow[c][tid] = (i < N) ? lw[(size_t)c * N + i] : 0.0;
+        trow[tid] = (i < N) ? t[i] : 0.0;
+        double s = (sigma != nullptr && i < N) ? sigma[i] : 0.0;
+        srow[tid] = s * s;
+    }
+    // (the patch shape of k_fill_sym: wave w owns the 32-column block w, a step covers 16 rows x 32 columns)
+    const int w = tid >> 6, rg = (tid >> 4) & 3, cp = tid & 15;
+    const int ja = j0 + 32 * w + 2 * cp, jb = ja + 1;
+    double xa[C], xb[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        xa[c] = (ja < N) ? lw[(size_t)c * N + ja] : 0.0;
+        xb[c] = (jb < N) ? lw[(size_t)c * N + jb] : 0.0;
+    }
+    const double ta = (ja < N) ? t[ja] : 0.0, tb = (jb < N) ? t[jb] : 0.0;
+    __syncthreads();
+
+    double* Km = Kbase + (size_t)b * mat_stride;
+#pragma unroll 1
+    for (int g4 = 0; g4 < NB / 16; ++g4) {
+        double va[4], vb[4];
+        double dt[8];
+#pragma unroll
+        for (int s4 = 0; s4 < 4; ++s4) {
+            const double tr = trow[16 * g4 + rg + 4 * s4];
+            dt[2 * s4] = ta - tr;
+            dt[2 * s4 + 1] = tb - tr;
+        }
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+#pragma clang fp contract(off)
+            double a[8], e[8];
+            bool live = false;
+#pragma unroll
+            for (int s4 = 0; s4 < 4; ++s4) {
+                const double xi = xrow[c][16 * g4 + rg + 4 * s4];
+                const double da = xa[c] - xi, db = xb[c] - xi;
+                a[2 * s4] = g.p2[c] * da * da;
+                a[2 * s4] = a[2 * s4] + q2[c] * dt[2 * s4] * dt[2 * s4];
+                a[2 * s4 + 1] = g.p2[c] * db * db;
+                a[2 * s4 + 1] = a[2 * s4 + 1] + q2[c] * dt[2 * s4 + 1] * dt[2 * s4 + 1];
+                live = live || !(a[2 * s4] <= -746.0) || !(a[2 * s4 + 1] <= -746.0);
+            }
+            if (__builtin_amdgcn_ballot_w64(live) != 0ull) {
+                live = false;
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    const double u = dt[k] * rP[c];
+                    double s, co;
+                    sincospi(u, &s, &co);
+                    a[k] = a[k] + ng[c] * s * s;
+                    live = live || !(a[k] <= -746.0);
+                }
+            }
+            if (__builtin_amdgcn_ballot_w64(live) != 0ull) {
+                exp_nonpos_batch<8>(a, e);
+#pragma unroll
+                for (int k = 0; k < 8; ++k) e[k] = g.a2[c] * e[k];
+            } else {
+#pragma unroll
+                for (int k = 0; k < 8; ++k) e[k] = 0.0;
+            }
+#pragma unroll
+            for (int s4 = 0; s4 < 4; ++s4) {
+                va[s4] = (c == 0) ? e[2 * s4] : va[s4] + e[2 * s4];
+                vb[s4] = (c == 0) ? e[2 * s4 + 1] : vb[s4] + e[2 * s4 + 1];
+            }
+        }
+#pragma unroll
+        for (int s4 = 0; s4 < 4; ++s4) {
+            const int r = 16 * g4 + rg + 4 * s4;
+            const int i = i0 + r;
+            d2 v;
+            if (i < N) {
+                double x = (ja < N) ? va[s4] : 0.0;
+                double y = (jb < N) ? vb[s4] : 0.0;
+                if (ja == i) x = dsum + srow[r];
+                if (jb == i) y = dsum + srow[r];
+                v.x = x;
+                v.y = y;
+            } else {
+                v.x = (ja == i) ? 1.0 : 0.0;
+                v.y = (jb == i) ? 1.0 : 0.0;
+            }
+            *reinterpret_cast<d2*>(Km + (size_t)i * ld + ja) = v;
+        }
+    }
+}
+
 // The proposals of a batch whose tau (nb, C) holds a value that is no time scale -- zero, negative or NaN; +inf is one -- get
 // their flag raised (the word k_finalize reads: -inf for that proposal alone).  Flags are only ever raised here.
 __global__ void k_tau_flags(const double* __restrict__ tau, int C, int nb, int* __restrict__ flags)

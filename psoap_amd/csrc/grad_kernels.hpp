@@ -416,6 +416,287 @@ __global__ __launch_bounds__(128) void k_tv_grad_finish(const double* __restrict
     grad_finish_sums<true>(part, alpha, gp, C, N, Npad, P, grad_gp, grad_x, grad_mu, tau, grad_tau);
 }
 
+// ---- the quasi-periodic kernel of fill_kernels.hpp (`QP`) ---------------------------------------------------------------------
+//   e_cij = exp(p_c d_cij^2 + q_c dt_ij^2 - Gamma_c sin^2(pi dt_ij / P_c))
+// The gradient keeps the time-variable formulas with this e and gains
+//   dlnL/dGamma_c = -1/2 a_c^2 sum_ij Q_ij e_cij sin^2(pi dt_ij / P_c)
+//   dlnL/dP_c     =  1/2 a_c^2 Gamma_c pi / P_c^2 sum_ij Q_ij e_cij dt_ij sin(2 pi dt_ij / P_c)      (exactly 0 at Gamma_c = 0)
+// The tile record and the epilogue's LDS map are decided here: GradTile<true> with five sums per component -- sa, sl, st and
+//   sg = sum w q e s^2,   sp = sum w q e dt (2 s co)        (s, co = sincospi(dt * rP), the pair the argument is built from)
+// -- so a record is two doubles per component longer than the time-variable one.
+struct QpTile {
+    static constexpr int HYP = 5;
+    static constexpr int ROWS_OFF = 0, COLS_OFF = 3 * NB, HYP_OFF = 6 * NB, DOUBLES = 6 * NB + 3 * HYP;
+    static constexpr int XS = 0;                 // [2][3][NB]: abscissae of the tile's rows (side 0) and columns (side 1)
+    static constexpr int AL = XS + 6 * NB;       // [2][NB]: alpha likewise
+    static constexpr int TS = AL + 2 * NB;       // [2][NB]: times likewise
+    static constexpr int RS = TS + 2 * NB;       // [2 wc][3][NB]: row sums of the two wave columns
+    static constexpr int CS = RS + 6 * NB;       // [2 wr][3][NB]: column sums of the two wave rows
+    static constexpr int HS = CS + 6 * NB;       // [4 waves][WS]
+    static constexpr int WS = 3 * HYP;
+    static_assert((HS + 4 * WS) * sizeof(double) <= GEMM_LDS_BYTES, "the epilogue fits the operand buffers");
+};
+
+// grad_contract_epilogue<C, true> (the gradient's q) with the periodic term in the argument and the two sums more.  A function
+// of its own beside it: the shared one keeps its instructions.  sa, sl, st and the row and column sums are formed by the same
+// operations in the same order, so at Gamma = 0 -- where the argument has the time-variable bits -- they have the
+// time-variable bits.  The underflow shortcut is taken on the two-term argument first (the periodic term is <= 0), ahead of
+// the sincospi, and then on the full one.
+// Registers.  Beside the accumulators the kernel has none to spare, and whatever the epilogue holds too long the allocator
+// takes out of the K loop's operand registers, as scratch traffic in every turn.  So nothing is kept that can be formed
+// again: s and co are evaluated a second time behind the exp, by the same sincospi on the same rounded u = dt * rP (the bits
+// that rebuilt the argument), where keeping s^2 and 2 s co of four elements across the exp cost 16 registers; d is the same
+// subtraction again; and the column's abscissa, alpha and time come from LDS where they are used, not once per tile.  With
+// that no instance has a scratch instruction in or ahead of its K loop (profiles/quasiperiodic.md has the forms that had).
+template <int C>
+__device__ __forceinline__ void qp_contract_epilogue(const Tile& t, int b, int ti, int tj, int tile_index, int N, int Npad,
+                                                     int P, const double* __restrict__ lwl, const double* __restrict__ gp,
+                                                     const double* __restrict__ alpha, double* __restrict__ part,
+                                                     const double* __restrict__ times, const double* __restrict__ tau,
+                                                     const double* __restrict__ gam, const double* __restrict__ per)
+{
+    using L = QpTile;
+    constexpr int XS = L::XS, AL = L::AL, TS = L::TS, RS = L::RS, CS = L::CS, HS = L::HS, WS = L::WS;
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int wr = wave >> 1, wc = wave & 1;
+    const double* lw = lwl + (size_t)b * C * N;
+    {
+        const int side = tid >> 7, idx = tid & 127;
+        const int g = NB * (side ? tj : ti) + idx;
+#pragma unroll
+        for (int c = 0; c < C; ++c) psoap_smem[XS + (side * 3 + c) * NB + idx] = (g < N) ? lw[(size_t)c * N + g] : 0.0;
+        psoap_smem[AL + side * NB + idx] = alpha[(size_t)b * Npad + g];
+        psoap_smem[TS + side * NB + idx] = (g < N) ? times[g] : 0.0;
+    }
+    __syncthreads();
+    const bool diag_tile = ti == tj;
+#pragma unroll 1
+    for (int c = 0; c < C; ++c) {
+        double p2;
+        {
+#pragma clang fp contract(off)
+            const double l = gp[(size_t)b * 2 * C + 2 * c + 1];      // (as load_gp rounds it)
+            p2 = -0.5 * (C_KMS * C_KMS) / (l * l);
+        }
+        const double q2 = tv_q2(tau[(size_t)b * C + c]);
+        const double rP = qp_rp(per[(size_t)b * C + c]);
+        const double ng = qp_ng(gam[(size_t)b * C + c]);
+        double colacc[4];
+        bool jok[4];
+#pragma unroll
+        for (int n = 0; n < 4; ++n) {
+            jok[n] = NB * tj + tile_col(wc, n, lane) < N;
+            colacc[n] = 0.0;
+        }
+        double sa = 0.0, sl = 0.0, st = 0.0, sg = 0.0, sp = 0.0;
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            double xi[4], rowacc[4], ai[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = tile_row(wr, m, lane, r);
+                xi[r] = psoap_smem[XS + c * NB + row];
+                ai[r] = psoap_smem[AL + row];
+                rowacc[r] = 0.0;
+            }
+#pragma unroll
+            for (int n = 0; n < 4; ++n) {
+                const int col = tile_col(wc, n, lane);
+                // (the column's abscissa, alpha and time are read where they are used, through an index the optimiser cannot
+                // follow: kept across the tile they are 24 registers the kernel does not have beside the sincospi)
+                int cidx = col;
+                asm volatile("" : "+v"(cidx));
+                const double xjn = psoap_smem[XS + (3 + c) * NB + cidx], ajn = psoap_smem[AL + NB + cidx];
+                const double tcol = psoap_smem[TS + NB + cidx];
+                double a[4], e[4];
+                bool live = false;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+#pragma clang fp contract(off)
+                    const double d = xjn - xi[r];
+                    const double dt = tcol - psoap_smem[TS + tile_row(wr, m, lane, r)];
+                    a[r] = p2 * d * d;
+                    a[r] = a[r] + q2 * dt * dt;
+                    live = live || !(a[r] <= -746.0);
+                }
+                if (__builtin_amdgcn_ballot_w64(live) == 0ull) continue;      // exp() = +0 for the whole wave: nothing to add
+                live = false;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+#pragma clang fp contract(off)
+                    const double dt = tcol - psoap_smem[TS + tile_row(wr, m, lane, r)];
+                    const double u = dt * rP;
+                    double s, co;
+                    sincospi(u, &s, &co);
+                    a[r] = a[r] + ng * s * s;
+                    live = live || !(a[r] <= -746.0);
+                }
+                if (__builtin_amdgcn_ballot_w64(live) == 0ull) continue;
+                exp_nonpos_batch<4>(a, e);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int row = tile_row(wr, m, lane, r);
+                    const bool ok = jok[n] && NB * ti + row < N && (!diag_tile || row <= col);
+                    const double qe = ok ? (ai[r] * ajn - t.acc[m][n][r]) * e[r] : 0.0;
+                    const double w = (diag_tile && row == col) ? 1.0 : 2.0;
+                    const double d = xjn - xi[r];
+                    const double qed = qe * d;
+                    // (dt again from LDS through an opaque index, as the time-variable epilogue does and for its reason)
+                    int trow = TS + row;
+                    asm volatile("" : "+v"(trow));
+                    const double dt = tcol - psoap_smem[trow];
+                    double s, co;
+                    {
+#pragma clang fp contract(off)
+                        sincospi(dt * rP, &s, &co);
+                    }
+                    sa = fma(w, qe, sa);
+                    sl = fma(w * qed, d, sl);
+                    st = fma(w * qe * dt, dt, st);
+                    sg = fma(w * qe, s * s, sg);
+                    sp = fma(w * qe * dt, 2.0 * s * co, sp);
+                    rowacc[r] += qed;
+                    colacc[n] -= qed;
+                }
+            }
+            // the row's 16 lanes (lane & 15 = column within the block), then the two wave columns in LDS
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+#pragma unroll
+                for (int off = 1; off <= 8; off <<= 1) rowacc[r] += __shfl_xor(rowacc[r], off, 64);
+                if ((lane & 15) == 0) psoap_smem[RS + (wc * 3 + c) * NB + tile_row(wr, m, lane, r)] = rowacc[r];
+            }
+        }
+#pragma unroll
+        for (int n = 0; n < 4; ++n) {
+            colacc[n] += __shfl_xor(colacc[n], 16, 64);
+            colacc[n] += __shfl_xor(colacc[n], 32, 64);
+            if (lane < 16) psoap_smem[CS + (wr * 3 + c) * NB + tile_col(wc, n, lane)] = colacc[n];
+        }
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+            sa += __shfl_xor(sa, off, 64);
+            sl += __shfl_xor(sl, off, 64);
+            st += __shfl_xor(st, off, 64);
+            sg += __shfl_xor(sg, off, 64);
+            sp += __shfl_xor(sp, off, 64);
+        }
+        if (lane == 0) {
+            double* hs = psoap_smem + HS + wave * WS + L::HYP * c;
+            hs[0] = sa;
+            hs[1] = sl;
+            hs[2] = st;
+            hs[3] = sg;
+            hs[4] = sp;
+        }
+    }
+    __syncthreads();
+    double* out = part + ((size_t)b * (P * (P + 1) / 2) + tile_index) * L::DOUBLES;
+    {
+        const int side = tid >> 7, idx = tid & 127;
+        const int src = side ? CS : RS;
+#pragma unroll
+        for (int c = 0; c < C; ++c)
+            out[(side ? L::COLS_OFF : L::ROWS_OFF) + c * NB + idx] =
+                psoap_smem[src + c * NB + idx] + psoap_smem[src + (3 + c) * NB + idx];
+    }
+    if (tid < L::HYP * C)
+        out[L::HYP_OFF + tid] = ((psoap_smem[HS + tid] + psoap_smem[HS + WS + tid]) + psoap_smem[HS + 2 * WS + tid]) +
+                                psoap_smem[HS + 3 * WS + tid];
+}
+
+// The K loop of k_tv_grad_contract<C> and the epilogue above.  grid (P (P + 1) / 2, B)
+template <int C>
+__global__ __launch_bounds__(GEMM_THREADS, 2) void k_qp_grad_contract(const double* __restrict__ Abase, size_t mat_stride,
+                                                                     int ld, int N, int Npad, int P,
+                                                                     const double* __restrict__ lwl,
+                                                                     const double* __restrict__ times,
+                                                                     const double* __restrict__ gp,
+                                                                     const double* __restrict__ tau,
+                                                                     const double* __restrict__ gam,
+                                                                     const double* __restrict__ per,
+                                                                     const double* __restrict__ alpha,
+                                                                     double* __restrict__ part)
+{
+    const int b = blockIdx.y;
+    int ti, tj;
+    decode_upper(blockIdx.x, P, ti, tj);
+    const double* W = Abase + (size_t)b * mat_stride + Npad + (size_t)NB * tj * ld;
+    Tile t;
+    t.zero();
+    tile_gemm_tn(t, W + NB * ti, (size_t)ld, W + NB * tj, (size_t)ld, Npad - NB * tj, ti == tj);
+    qp_contract_epilogue<C>(t, b, ti, tj, (int)blockIdx.x, N, Npad, P, lwl, gp, alpha, part, times, tau, gam, per);
+}
+
+// grad_finish_sums over QpTile records: the wavelength gradient, grad_gp, grad_tau and grad_mu by the operations and in the
+// order of k_tv_grad_finish (thread k adds every 128th tile, the 128 sums meet in a tree), and
+//   grad_gamma[b][c] = -1/2 a_c^2 sg_c,   grad_period[b][c] = 1/2 a_c^2 Gamma_c pi / P_c^2 sp_c  (+ 0.0: no -0 at Gamma = 0)
+// grid (P + 1, B), 128 threads
+__global__ __launch_bounds__(128) void k_qp_grad_finish(const double* __restrict__ part, const double* __restrict__ alpha,
+                                                        const double* __restrict__ gp, const double* __restrict__ tau,
+                                                        const double* __restrict__ gam, const double* __restrict__ per, int C,
+                                                        int N, int Npad, int P, double* __restrict__ grad_gp,
+                                                        double* __restrict__ grad_tau, double* __restrict__ grad_gamma,
+                                                        double* __restrict__ grad_period, double* __restrict__ grad_x,
+                                                        double* __restrict__ grad_mu)
+{
+    using L = QpTile;
+    __shared__ double red[128];
+    const int b = blockIdx.y, x = blockIdx.x, tid = threadIdx.x;
+    const int ntiles = P * (P + 1) / 2;
+    const double* pb = part + (size_t)b * ntiles * L::DOUBLES;
+    const double* gpb = gp + (size_t)b * 2 * C;
+    if (x < P) {
+        const int i = NB * x + tid;
+        for (int c = 0; c < C; ++c) {
+            double s = 0.0;
+            for (int ti = 0; ti <= x; ++ti) s += pb[(size_t)upper_index(ti, x, P) * L::DOUBLES + L::COLS_OFF + c * NB + tid];
+            for (int tj = x; tj < P; ++tj) s += pb[(size_t)upper_index(x, tj, P) * L::DOUBLES + L::ROWS_OFF + c * NB + tid];
+            const double a = gpb[2 * c], l = gpb[2 * c + 1];
+            const double p2 = -0.5 * (C_KMS * C_KMS) / (l * l);
+            if (i < N) grad_x[((size_t)b * C + c) * N + i] = -2.0 * p2 * (a * a) * s;
+        }
+        return;
+    }
+    for (int k = 0; k <= L::HYP * C; ++k) {
+        double s = 0.0;
+        if (k < L::HYP * C) {
+            for (int t = tid; t < ntiles; t += 128) s += pb[(size_t)t * L::DOUBLES + L::HYP_OFF + k];
+        } else {
+            for (int i = tid; i < N; i += 128) s += alpha[(size_t)b * Npad + i];
+        }
+        __syncthreads();
+        red[tid] = s;
+        __syncthreads();
+        for (int w = 64; w >= 1; w >>= 1) {
+            if (tid < w) red[tid] += red[tid + w];
+            __syncthreads();
+        }
+        if (tid == 0) {
+            if (k == L::HYP * C) {
+                grad_mu[b] = red[0];
+            } else {
+                const int c = k / L::HYP, what = k % L::HYP;
+                const double a = gpb[2 * c], l = gpb[2 * c + 1];
+                if (what == 0) {
+                    grad_gp[(size_t)b * 2 * C + 2 * c] = a * red[0];
+                } else if (what == 1) {
+                    grad_gp[(size_t)b * 2 * C + 2 * c + 1] = 0.5 * (a * a) * (C_KMS * C_KMS) / (l * l * l) * red[0];
+                } else if (what == 2) {
+                    const double tc = tau[(size_t)b * C + c];
+                    grad_tau[(size_t)b * C + c] = 0.5 * (a * a) / (tc * tc * tc) * red[0];
+                } else if (what == 3) {
+                    grad_gamma[(size_t)b * C + c] = -0.5 * (a * a) * red[0];
+                } else {
+                    const double G = gam[(size_t)b * C + c], Pc = per[(size_t)b * C + c];
+                    grad_period[(size_t)b * C + c] = 0.5 * (a * a) * G * 3.14159265358979323846 / (Pc * Pc) * red[0] + 0.0;
+                }
+            }
+        }
+    }
+}
+
 // the LDS attribute of every kernel here that takes the operand buffers
 inline hipError_t grad_configure_kernels()
 {
@@ -423,7 +704,9 @@ inline hipError_t grad_configure_kernels()
         reinterpret_cast<const void*>(k_grad_panel_update),
         reinterpret_cast<const void*>(k_grad_contract<1>),    reinterpret_cast<const void*>(k_grad_contract<2>),
         reinterpret_cast<const void*>(k_grad_contract<3>),    reinterpret_cast<const void*>(k_tv_grad_contract<1>),
-        reinterpret_cast<const void*>(k_tv_grad_contract<2>), reinterpret_cast<const void*>(k_tv_grad_contract<3>)};
+        reinterpret_cast<const void*>(k_tv_grad_contract<2>), reinterpret_cast<const void*>(k_tv_grad_contract<3>),
+        reinterpret_cast<const void*>(k_qp_grad_contract<1>), reinterpret_cast<const void*>(k_qp_grad_contract<2>),
+        reinterpret_cast<const void*>(k_qp_grad_contract<3>)};
     for (const void* k : kernels)
         if (hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GEMM_LDS_BYTES)) return e;
     return hipSuccess;
@@ -455,6 +738,8 @@ struct GradWs {
     bool epochs_valid = false;
     // psoap_chunk_lnlike_tv_grad (the TV kernels above): the group's time scales and dlnL/dtau
     Grow<double> Tau, GradTau;
+    // psoap_chunk_lnlike_qp_grad (the QP kernels above): the group's Gamma and P, dlnL/dGamma and dlnL/dP
+    Grow<double> Gamma, Period, GradGamma, GradPeriod;
 };
 
 }  // namespace psoap

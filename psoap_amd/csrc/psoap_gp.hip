@@ -44,6 +44,7 @@
 #include "mix_kernels.hpp"
 #include "abi_error.hpp"
 #include "plan_abi.hpp"
+#include "qp_plan.hpp"
 #include "share.hpp"
 
 using namespace psoap;
@@ -2249,6 +2250,24 @@ extern "C" int psoap_chunk_lnlike_tv_grad(psoap_chunk* h, int B, int c, const do
                     nullptr, grad_gp != nullptr);
 }
 
+// ---- quasi-periodic temporal factor (the QP kernels of fill_kernels.hpp, grad_kernels.hpp) ----------
+// The value and the gradient under K_ij = sum_c a_c^2 exp(p_c d^2 + q_c dt^2 - Gamma_c sin^2(pi dt / P_c)) + sigma_i^2 delta_ij:
+// the checks of qp_check (qp_plan.hpp) and grad_run with `tau` and `qp`.
+extern "C" int psoap_chunk_lnlike_qp_grad(psoap_chunk* h, int B, int c, const double* lwl, const double* gp, const double* tau,
+                                          const double* gamma, const double* period, double mu_GP, double* lnp, double* grad_gp,
+                                          double* grad_tau, double* grad_gamma, double* grad_period, double* grad_lwl,
+                                          double* grad_mu)
+{
+    const bool arrays = h && lwl && gp && tau && gamma && period && lnp;
+    const QpCall call{arrays,  grad_gp != nullptr, grad_tau != nullptr, grad_gamma != nullptr, grad_period != nullptr,
+                      grad_lwl || grad_mu, B, c, arrays && h->dTimes.p != nullptr, arrays && h->stream.open,
+                      arrays && h->marg.valid};
+    if (const char* why = qp_check(call)) FAIL(std::string("psoap_chunk_lnlike_qp_grad: ") + why);
+    const QpArgs qp{gamma, period, grad_gamma, grad_period};
+    return grad_run(h, false, B, c, lwl, -1, nullptr, gp, tau, mu_GP, lnp, nullptr, grad_gp, grad_tau, grad_lwl, grad_mu, nullptr,
+                    nullptr, grad_gp != nullptr, &qp);
+}
+
 // ---- Fisher information of the likelihood (fisher_kernels.hpp): fisher_run ---------------------------
 extern "C" int psoap_chunk_fisher(psoap_chunk* h, int c, const double* lwl, const double* gp, int T, const double* tan_lwl,
                                   const double* tan_gp, double* fisher, double* fisher_mu)
@@ -2500,14 +2519,15 @@ extern "C" int psoap_chunk_marg_release(psoap_chunk* h)
 }
 
 // ---- fills (matrix_functions drop-ins) ------------------------------------------------------
-// K (full) of one matrix on `device`, static or -- with t (N) and tau (c) -- under the time-variable kernel
+// K (full) of one matrix on `device`, static or -- with t (N) and tau (c) -- under the time-variable kernel or -- with gamma
+// and period (c) as well -- under the quasi-periodic one
 static int fill_sym_run(int device, int c, int N, const double* lwl, const double* t, const double* gp, const double* tau,
-                        const double* sigma, double* out)
+                        const double* sigma, double* out, const double* gamma = nullptr, const double* period = nullptr)
 {
     DEVICE_SCOPE(device);
     HIP_TRY(hipSetDevice(device));
     const int Npad = round_up(N, NB), P = Npad / NB;
-    Grow<double> dK, dLwl, dT, dGp, dTau, dSig;
+    Grow<double> dK, dLwl, dT, dGp, dTau, dSig, dGam, dPer;
     HIP_TRY(dK.need((size_t)Npad * Npad));
     HIP_TRY(dLwl.need((size_t)c * N));
     HIP_TRY(dGp.need(6));
@@ -2519,13 +2539,23 @@ static int fill_sym_run(int device, int c, int N, const double* lwl, const doubl
         HIP_TRY(hipMemcpy(dT, t, sizeof(double) * N, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(dTau, tau, sizeof(double) * c, hipMemcpyHostToDevice));
     }
+    if (gamma) {
+        HIP_TRY(dGam.need(3));
+        HIP_TRY(dPer.need(3));
+        HIP_TRY(hipMemcpy(dGam, gamma, sizeof(double) * c, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(dPer, period, sizeof(double) * c, hipMemcpyHostToDevice));
+    }
     if (sigma) {
         HIP_TRY(dSig.need(N));
         HIP_TRY(hipMemcpy(dSig, sigma, sizeof(double) * N, hipMemcpyHostToDevice));
     }
     dim3 grid(P * P, 1);
     with_components(c, [&](auto nc) {
-        if (t)
+        if (gamma)
+            hipLaunchKernelGGL(k_fill_sym_qp<nc()>, grid, dim3(256), 0, 0, dK.p, (size_t)0, Npad, N, P, (const double*)dLwl.p,
+                               (const double*)dT.p, (const double*)dGp.p, (const double*)dTau.p, (const double*)dGam.p,
+                               (const double*)dPer.p, (const double*)dSig.p, 0);
+        else if (t)
             hipLaunchKernelGGL(k_fill_sym_tv<nc()>, grid, dim3(256), 0, 0, dK.p, (size_t)0, Npad, N, P, (const double*)dLwl.p,
                                (const double*)dT.p, (const double*)dGp.p, (const double*)dTau.p, (const double*)dSig.p, 0);
         else
@@ -2550,6 +2580,14 @@ extern "C" int psoap_fill_sym_tv(int device, int c, int N, const double* lwl, co
 {
     if (c < 1 || c > 3 || N <= 0 || !lwl || !t || !gp || !tau || !out) FAIL("psoap_fill_sym_tv: bad arguments");
     return fill_sym_run(device, c, N, lwl, t, gp, tau, sigma, out);
+}
+
+// psoap_fill_sym under the quasi-periodic kernel: t (N), tau, gamma, period (c)
+extern "C" int psoap_fill_sym_qp(int device, int c, int N, const double* lwl, const double* t, const double* gp,
+                                 const double* tau, const double* gamma, const double* period, const double* sigma, double* out)
+{
+    if (c < 1 || c > 3 || N <= 0 || !lwl || !t || !gp || !tau || !gamma || !period || !out) FAIL("psoap_fill_sym_qp: bad arguments");
+    return fill_sym_run(device, c, N, lwl, t, gp, tau, sigma, out, gamma, period);
 }
 
 extern "C" int psoap_fill_cross(int device, int M, int N, const double* lwl_row, const double* lwl_col, double amp,

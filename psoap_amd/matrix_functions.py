@@ -75,6 +75,29 @@ def fill_V11_timevar(mat, lwls, times, gp, tau, sigma=None, device=None):
         mat[...] = out
 
 
+def fill_V11_quasiperiodic(mat, lwls, times, gp, tau, gamma, period, sigma=None, device=None):
+    """The symmetric fill under the quasi-periodic kernel (not in the reference; include/psoap_gp.h: psoap_fill_sym_qp), in
+    place like its siblings: ``fill_V11_timevar``'s element times ``exp(-gamma_c sin^2(pi (times[j] - times[i]) / period_c))``
+    per component, inside the one exponential; ``gamma``, ``period`` (c,).  With every ``gamma = 0`` the matrix is
+    bit-identical to ``fill_V11_timevar``'s."""
+    lwls = as_f64(np.atleast_2d(as_f64(lwls)))
+    c, n_vec = lwls.shape
+    N = len(mat)
+    if n_vec < N:
+        raise ValueError("wavelength vector shorter than the matrix")
+    lwls = as_f64(lwls[:, :N])
+    times = as_f64(as_f64(times)[:N], (N,))
+    gp = as_f64(gp, (2 * c,))
+    tau, gamma, period = (as_f64(np.atleast_1d(as_f64(v)), (c,)) for v in (tau, gamma, period))
+    out = _target(mat, (N, N))
+    sig = None if sigma is None else as_f64(sigma, (N,))
+    dev = _lib.default_device() if device is None else device
+    check(_lib.load().psoap_fill_sym_qp(dev, c, N, dptr(lwls), dptr(times), dptr(gp), dptr(tau), dptr(gamma), dptr(period),
+                                        None if sig is None else dptr(sig), dptr(out)), "psoap_fill_sym_qp")
+    if out is not mat:
+        mat[...] = out
+
+
 def fill_V12_f(mat, lwl_f, lwl_predict, amp_f, l_f):
     lwl_f = as_f64(lwl_f)
     lwl_predict = as_f64(lwl_predict)

@@ -224,3 +224,20 @@ def draw_timevar_flux(lwls, times, sigma, gp, tau, mu_GP: float, seed: int) -> n
     K[np.diag_indices_from(K)] += np.asarray(sigma, dtype=np.float64) ** 2
     z = np.random.default_rng(seed).standard_normal(t.shape[0])
     return mu_GP + np.linalg.cholesky(K) @ z
+
+
+def draw_quasiperiodic_flux(lwls, times, sigma, gp, tau, gamma, period, mu_GP: float, seed: int) -> np.ndarray:
+    """(N,) flux ``mu_GP + L z``: ``draw_timevar_flux`` under the model of ``covariance.lnlike_quasiperiodic``, whose elements
+    carry ``exp(-gamma_c sin^2(pi dt_ij / period_c))`` as well -- a chunk whose component spectra repeat with the periods
+    ``period`` (c,) and decay over ``tau`` (c,), for the checks of the quasi-periodic fit and the period scan."""
+    lwls = np.atleast_2d(np.asarray(lwls, dtype=np.float64))
+    t = np.asarray(times, dtype=np.float64)
+    DT = t[None, :] - t[:, None]
+    K = np.zeros((t.shape[0],) * 2)
+    for k in range(lwls.shape[0]):
+        D = lwls[k][None, :] - lwls[k][:, None]
+        K += gp[2 * k] ** 2 * np.exp(-0.5 * (C_KMS / gp[2 * k + 1]) ** 2 * D * D - 0.5 * DT * DT / tau[k] ** 2 -
+                                     gamma[k] * np.sin(np.pi * DT / period[k]) ** 2)
+    K[np.diag_indices_from(K)] += np.asarray(sigma, dtype=np.float64) ** 2
+    z = np.random.default_rng(seed).standard_normal(t.shape[0])
+    return mu_GP + np.linalg.cholesky(K) @ z
