@@ -605,6 +605,45 @@ int psoap_chunk_loo_tv(psoap_chunk *h, int c, const double *lwl, const double *g
                        double *ep_resid,
                        double *ep_chi2, double *ep_logp, int32_t *ep_npix);
 
+/* ---- Fisher information and leave-one-out under the quasi-periodic kernel ------------------
+ * psoap_chunk_fisher_qp and psoap_chunk_loo_qp are psoap_chunk_fisher_tv and
+ * psoap_chunk_loo_tv with the quasi-periodic kernel of psoap_chunk_lnlike_qp_grad in the
+ * place of K: gamma (c) and period (c) behind tau as there, the other arguments, outputs,
+ * shapes and NULL rules are the time-variable twins'.
+ * A tangent is t = (dx_t (c, N), da_tc, dl_tc, dtau_tc, dGamma_tc, dP_tc): tan_gamma and
+ * tan_period (T, c; NULL: zeros) behind tan_tau.  With s, co = sincospi(dt / P_c) and
+ * e = exp(p_c d^2 + q_c dt^2 - Gamma_c s^2), formed as psoap_chunk_lnlike_qp_grad forms it,
+ *   K_t[m,n] = sum_c e (the time-variable terms - a_c^2 s^2 dGamma_tc
+ *                       + a_c^2 Gamma_c pi / P_c^2 dt (2 s co) dP_tc)
+ * and F_st, fisher_mu and the leave-one-out are the time-variable twins' formulas on that K.
+ * New device code per tangent: k_qp_fisher_tangent_fill, k_qp_fisher_contract (the two K
+ * loops of the time-variable contraction, the quasi-periodic epilogue), then
+ * k_qp_grad_finish as it is and k_qp_fisher_dot; the leave-one-out has none.  No atomics,
+ * every sum in an order fixed by (N, c, T): F == F^T bit for bit, a subsequence of the
+ * tangents gives the bits of the entries it shares.
+ * Bit-identity at Gamma = 0: with every Gamma_c = 0 and tan_gamma = 0, fisher and
+ * fisher_mu have the bits of psoap_chunk_fisher_tv whatever period and tan_period hold, and
+ * every field of the leave-one-out has the bits of psoap_chunk_loo_tv (lnp those of
+ * psoap_chunk_lnlike_qp_grad).  A tangent with nothing but dP_c of a component with
+ * Gamma_c = 0 has an exactly-zero row and column.
+ * Conventions: those of the time-variable twins, and a Gamma_c < 0, NaN or inf or a
+ * P_c <= 0, NaN or inf likewise.  Refused with a message: what the twins refuse.
+ * Workspace: that of the twins, shared with them, plus 6 doubles for Gamma and P, 4 T c
+ * doubles of tangents and contractions and two doubles more per component in a tile record;
+ * the same releases free all of it. */
+int psoap_chunk_fisher_qp(psoap_chunk *h, int c, const double *lwl, const double *gp,
+                          const double *tau, const double *gamma, const double *period,
+                          int T, const double *tan_lwl, const double *tan_gp,
+                          const double *tan_tau, const double *tan_gamma,
+                          const double *tan_period, double *fisher, double *fisher_mu);
+int psoap_chunk_loo_qp(psoap_chunk *h, int c, const double *lwl, const double *gp,
+                       const double *tau, const double *gamma, const double *period,
+                       double mu_GP, const int32_t *epoch, int n_epochs,
+                       double *lnp, double *loo_logp,
+                       double *pix_mean, double *pix_var, double *pix_logp,
+                       double *ep_resid,
+                       double *ep_chi2, double *ep_logp, int32_t *ep_npix);
+
 /* ---- the time-variable kernel under the marginalised continuum ------------------------------
  * Kt = K_tv + Ht Ht^T: K_tv the time-variable kernel of psoap_chunk_lnlike_tv_grad over the
  * handle's times (psoap_chunk_set_times), Ht from the handle's baseline

@@ -91,6 +91,10 @@ SIGNATURES = {
     "psoap_chunk_fisher_marg_tv": (ctypes.c_int, [_vp, ctypes.c_int, _dp, _dp, _dp, ctypes.c_int, _dp, _dp, _dp, _dp, _dp]),
     "psoap_chunk_loo_tv": (ctypes.c_int, [_vp, ctypes.c_int, _dp, _dp, _dp, ctypes.c_double, _i32p, ctypes.c_int, _dp, _dp, _dp,
                                           _dp, _dp, _dp, _dp, _dp, _i32p]),
+    "psoap_chunk_fisher_qp": (ctypes.c_int, [_vp, ctypes.c_int, _dp, _dp, _dp, _dp, _dp, ctypes.c_int, _dp, _dp, _dp, _dp, _dp, _dp,
+                                             _dp]),
+    "psoap_chunk_loo_qp": (ctypes.c_int, [_vp, ctypes.c_int, _dp, _dp, _dp, _dp, _dp, ctypes.c_double, _i32p, ctypes.c_int, _dp, _dp,
+                                          _dp, _dp, _dp, _dp, _dp, _dp, _i32p]),
     "psoap_chunk_lnprob_tv_grad": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, ctypes.c_double, _dp, _dp, _dp,
                                                   _dp, _dp, _dp]),
     "psoap_chunk_lnprob_marg_tv_grad": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, ctypes.c_double, _dp, _dp,

@@ -217,6 +217,32 @@ def scan_hot_loops(text: str):
     return out
 
 
+def scan_mfma_scratch(text: str, name_part: str):
+    """-> {mangled function: (MFMAs, scratch instructions ahead of the first MFMA, between the first and the last, behind the
+    last)} for every function whose mangled name contains ``name_part``.  A kernel whose K loops come first and whose epilogue
+    follows them has its loops between the first and the last MFMA: a scratch instruction there or ahead of it is a spill
+    paid in every turn of a loop, one behind the last MFMA is paid once per tile."""
+    out = {}
+    lines = text.split("\n")
+    i = 0
+    while i < len(lines):
+        m = re.match(r"^(_Z\w+):", lines[i])
+        if not m or name_part not in m.group(1):
+            i += 1
+            continue
+        j = i
+        while j < len(lines) and not lines[j].strip().startswith(".Lfunc_end"):
+            j += 1
+        code = [ln.split(";")[0].strip() for ln in lines[i:j]]
+        mfma = [n for n, s in enumerate(code) if s.startswith("v_mfma")]
+        scratch = [n for n, s in enumerate(code) if s.startswith(("scratch_load", "scratch_store"))]
+        first, last = (mfma[0], mfma[-1]) if mfma else (len(code), len(code))
+        out[m.group(1)] = (len(mfma), sum(n < first for n in scratch), sum(first <= n <= last for n in scratch),
+                           sum(n > last for n in scratch))
+        i = j
+    return out
+
+
 def kernel_resources(text: str):
     """-> {kernel: {"vgpr_spill_count": n, "private_segment_fixed_size": n, ...}} from the code-object metadata"""
     out = {}

@@ -285,9 +285,10 @@ class ChunkHandle:
         plain ``K``, also on a handle with a baseline: ``fisher_marg`` is the form under ``K + H Lambda H^T``."""
         return self._fisher("psoap_chunk_fisher", lwls, gp, tan_gp, tan_lwl, want_mu)
 
-    def _fisher(self, entry, lwls, gp, tan_gp, tan_lwl, want_mu, tau=None, tan_tau=None):
-        """the body of ``fisher``, ``fisher_marg``, ``fisher_tv`` and ``fisher_marg_tv``: ``entry`` names the library's function, which with ``tau``
-        takes it after ``gp`` and ``tan_tau`` after ``tan_gp``"""
+    def _fisher(self, entry, lwls, gp, tan_gp, tan_lwl, want_mu, tau=None, tan_tau=None, qp=None):
+        """the body of ``fisher``, ``fisher_marg``, ``fisher_tv``, ``fisher_marg_tv`` and ``fisher_qp``: ``entry`` names the library's function, which with ``tau``
+        takes it after ``gp`` and ``tan_tau`` after ``tan_gp``, and with ``qp = (gamma, period, tan_gamma, tan_period)`` the first
+        two behind ``tau`` and the other two behind ``tan_tau``"""
         lwls = as_f64(np.atleast_2d(lwls))
         c = lwls.shape[0]
         lwls = as_f64(lwls, (c, self.N))
@@ -303,6 +304,11 @@ class ChunkHandle:
             if tan_tau is not None:
                 tan_tau = as_f64(np.atleast_2d(as_f64(tan_tau)), (T, c))
             after_gp, after_tan_gp = (dptr(tau),), (None if tan_tau is None else dptr(tan_tau),)
+        if qp is not None:
+            hyper = [as_f64(np.atleast_1d(as_f64(v)), (c,)) for v in qp[:2]]
+            tans = [None if v is None else as_f64(np.atleast_2d(as_f64(v)), (T, c)) for v in qp[2:]]
+            after_gp += tuple(dptr(v) for v in hyper)
+            after_tan_gp += tuple(None if v is None else dptr(v) for v in tans)
         F, mu = np.empty((T, T)), np.empty(1)
         check(getattr(self._L, entry)(self._h, c, dptr(lwls), dptr(gp), *after_gp, T, None if tan_lwl is None else dptr(tan_lwl),
                                       dptr(tan_gp), *after_tan_gp, dptr(F), dptr(mu) if want_mu else None), entry)
@@ -316,6 +322,18 @@ class ChunkHandle:
         exactly-zero row and column.  ``tau <= 0`` or NaN, a negative hyper-parameter or a matrix that is not positive
         definite gives NaN in every entry; a handle with a baseline is refused."""
         return self._fisher("psoap_chunk_fisher_tv", lwls, gp, tan_gp, tan_lwl, want_mu, tau, tan_tau)
+
+    def fisher_qp(self, lwls, gp, tau, gamma, period, tan_gp, tan_tau=None, tan_gamma=None, tan_period=None, tan_lwl=None,
+                  want_mu: bool = False):
+        """``fisher_tv`` under the quasi-periodic kernel of ``lnlike_qp`` (include/psoap_gp.h: psoap_chunk_fisher_qp; needs
+        ``set_times``): ``gamma`` and ``period`` (c,) behind ``tau``, and a tangent has a ``Gamma`` and a period part,
+        ``tan_gamma`` and ``tan_period`` (T, c) (``None``: zeros), behind ``tan_tau``.  ``F (T, T)`` symmetric bit for bit; with
+        every ``gamma = 0`` and ``tan_gamma`` zero it has the bits of ``fisher_tv`` whatever ``period`` and ``tan_period`` hold,
+        and a tangent with nothing but the period of a component with ``gamma = 0`` gives an exactly-zero row and column.  A
+        ``tau``, ``gamma`` or ``period`` that is no proposal (``lnlike_qp``), a negative hyper-parameter or a matrix that is not
+        positive definite gives NaN in every entry; a handle with a baseline is refused."""
+        return self._fisher("psoap_chunk_fisher_qp", lwls, gp, tan_gp, tan_lwl, want_mu, tau, tan_tau,
+                            (gamma, period, tan_gamma, tan_period))
 
     def fisher_marg(self, lwls, gp, tan_gp, tan_lwl=None, want_mu: bool = False):
         """``fisher`` under the baseline of ``set_baseline`` (include/psoap_gp.h: psoap_chunk_fisher_marg): the same arguments,
@@ -392,14 +410,15 @@ class ChunkHandle:
         baseline: ``loo_marg`` is the form under ``K + H Lambda H^T``."""
         return self._loo("psoap_chunk_loo", lwls, gp, mu_GP, epoch_index, n_epochs)
 
-    def _loo(self, entry, lwls, gp, mu_GP, epoch_index, n_epochs, tau=None):
-        """the body of ``loo``, ``loo_marg`` and ``loo_tv``: ``entry`` names the library's function, which with ``tau`` takes it
-        after ``gp``"""
+    def _loo(self, entry, lwls, gp, mu_GP, epoch_index, n_epochs, tau=None, qp=None):
+        """the body of ``loo``, ``loo_marg``, ``loo_tv`` and ``loo_qp``: ``entry`` names the library's function, which with ``tau``
+        takes it after ``gp`` and with ``qp = (gamma, period)`` those two behind ``tau``"""
         lwls = as_f64(np.atleast_2d(lwls))
         c = lwls.shape[0]
         lwls = as_f64(lwls, (c, self.N))
         gp = as_f64(gp, (2 * c,))
-        after_gp = () if tau is None else (dptr(as_f64(np.atleast_1d(as_f64(tau)), (c,))),)
+        hyper = [as_f64(np.atleast_1d(as_f64(v)), (c,)) for v in (() if tau is None else (tau,)) + (() if qp is None else tuple(qp))]
+        after_gp = tuple(dptr(v) for v in hyper)
         N = self.N
         lnp, logp = np.empty(1), np.empty(1)
         mean, var, plogp = np.empty(N), np.empty(N), np.empty(N)
@@ -437,6 +456,14 @@ class ChunkHandle:
         ``tau = inf`` every field has the bits of ``loo``.  ``tau <= 0`` or NaN gives ``lnp = -inf`` and NaN like a negative
         hyper-parameter; a handle with a baseline is refused."""
         return self._loo("psoap_chunk_loo_tv", lwls, gp, mu_GP, epoch_index, n_epochs, tau)
+
+    def loo_qp(self, lwls, gp, tau, gamma, period, mu_GP: float = 1.0, epoch_index=None, n_epochs: int | None = None) -> "LooResult":
+        """``loo_tv`` under the quasi-periodic kernel of ``lnlike_qp`` (include/psoap_gp.h: psoap_chunk_loo_qp; needs
+        ``set_times``): ``gamma`` and ``period`` (c,) behind ``tau``, the same ``LooResult`` with ``A = K^-1`` of that kernel --
+        the outlier search under the model ``optimize_GP_quasiperiodic`` fits.  ``lnp`` has the bits of ``lnlike_qp``; with every
+        ``gamma = 0`` every field has the bits of ``loo_tv``.  A value that is no proposal gives ``lnp = -inf`` and NaN like a
+        negative hyper-parameter; a handle with a baseline is refused."""
+        return self._loo("psoap_chunk_loo_qp", lwls, gp, mu_GP, epoch_index, n_epochs, tau, (gamma, period))
 
     def loo_release(self):
         """Free the leave-one-out workspace (the packed epoch blocks); the next ``loo`` allocates it again."""

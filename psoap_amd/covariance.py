@@ -1176,6 +1176,181 @@ def loo_timevar(lwls, fl, sigma, gp, tau, times, mu_GP=1.0, epoch_index=None):
     return res
 
 
+# ---- Fisher information and leave-one-out under the quasi-periodic kernel -------------------------
+def _quasiperiodic_front(lwls, gp, tau, gamma, period, times):
+    """``(lw (c, N), gp, tau, gamma, period, t, degenerate)`` of a quasi-periodic analysis call: the front checks of
+    ``_quasiperiodic`` up to the device -- ``degenerate``: a negative hyper-parameter or a ``tau``, ``gamma`` or ``period``
+    that is none, to be answered before any work"""
+    gp = [float(g) for g in gp]
+    lw = np.stack([as_f64(w) for w in np.atleast_2d(lwls)])
+    c, N = lw.shape
+    if len(gp) != 2 * c:
+        raise ValueError(f"gp must hold {2 * c} values for {c} component(s)")
+    tau, gamma, period = (as_f64(np.atleast_1d(as_f64(v)), (c,)) for v in (tau, gamma, period))
+    t = as_f64(times, (N,))
+    if not np.all(np.isfinite(t)):
+        raise ValueError(_NONFINITE)
+    return lw, gp, tau, gamma, period, t, any(g < 0.0 for g in gp) or not _quasiperiodic_valid(tau, gamma, period)
+
+
+def fisher_information_quasiperiodic(lwls, fl, sigma, gp, tau, gamma, period, times):
+    """The ``(5c, 5c)`` Fisher information of ``(amp_0, l_0, ..., tau_*, Gamma_*, P_*)`` under the quasi-periodic kernel of
+    ``lnlike_quasiperiodic``, evaluated on the device (``ChunkHandle.fisher_qp`` with unit tangents, the cached handle with
+    ``times - min(times)`` on it): what ``fisher_information_timevar`` is for the time-variable kernel, with ``Gamma``, the
+    periods and their correlations with everything else.  The row and column of the period of a component with
+    ``gamma = 0`` are exactly zero, as are those of a ``tau = inf``.  Degenerate input follows ``lnlike_quasiperiodic``: a
+    negative hyper-parameter, a ``tau``, ``gamma`` or ``period`` that is none or a matrix that is not positive definite gives
+    NaN in every entry."""
+    lw, gp, tau, gamma, period, t, degenerate = _quasiperiodic_front(lwls, gp, tau, gamma, period, times)
+    c = lw.shape[0]
+    if degenerate:
+        return np.full((5 * c, 5 * c), np.nan)
+    _quasiperiodic_input(lw, sigma, gp)
+    h = _quasiperiodic_handle(fl, sigma, t, "fisher_information_quasiperiodic")
+    eye = np.eye(5 * c)
+    return h.fisher_qp(lw, gp, tau, gamma, period, eye[:, :2 * c], eye[:, 2 * c:3 * c], eye[:, 3 * c:4 * c], eye[:, 4 * c:])
+
+
+def _qp_free(tau, gamma, free):
+    """the free masks ``(tau, gamma, period)`` of ``_fit_quasiperiodic``: its dictionary and its defaults -- every finite
+    ``tau`` and, for both others, every ``gamma > 0``"""
+    c = tau.shape[0]
+    free = {} if free is None else dict(free)
+    if set(free) - {"tau", "gamma", "period"}:
+        raise ValueError(f"free takes 'tau', 'gamma' and 'period'; got {sorted(free)}")
+    return (np.asarray(free.get("tau", np.isfinite(tau)), dtype=bool).reshape(c),
+            np.asarray(free.get("gamma", gamma > 0.0), dtype=bool).reshape(c),
+            np.asarray(free.get("period", gamma > 0.0), dtype=bool).reshape(c))
+
+
+def _laplace_from_fisher_blocks(F, theta, free, who):
+    """``_laplace_from_fisher`` for any number of parameter blocks: ``F (n, n)`` over the parameters ``theta (n,)`` in their
+    own units, ``free (n,)`` of booleans -> ``(cov_log, sd (n,))``: the inverse of ``F_log = diag(theta) F diag(theta)``
+    restricted to the free parameters, and the standard deviations in the parameters' own units, ``nan`` where not free.
+    ``LinAlgError`` where the restricted ``F_log`` is singular or not finite.  (Nothing here knows the device.)"""
+    theta = as_f64(theta)
+    n = theta.shape[0]
+    F = as_f64(F, (n, n))
+    idx = np.flatnonzero(np.asarray(free, dtype=bool).reshape(n))
+    th = theta[idx]
+    if not np.all(np.isfinite(th)):
+        raise ValueError("a free parameter must be finite")
+    F_log = th[:, None] * F[np.ix_(idx, idx)] * th[None, :]       # d/dlog theta = theta d/dtheta
+    try:
+        if not np.all(np.isfinite(F_log)):
+            raise np.linalg.LinAlgError
+        L = np.linalg.cholesky(F_log)
+    except np.linalg.LinAlgError:
+        raise np.linalg.LinAlgError(f"{who}: the Fisher information of the free log parameters is singular") from None
+    Linv = np.linalg.inv(L)
+    cov_log = Linv.T @ Linv
+    sd = np.full(n, np.nan)
+    sd[idx] = th * np.sqrt(np.diag(cov_log))
+    return cov_log, sd
+
+
+def _qp_laplace_from_fisher(F, gp, tau, gamma, period, free):
+    """The algebra of ``quasiperiodic_laplace`` on a given ``F (5c, 5c)`` -> ``(cov_log, sd_gp, sd_tau, sd_gamma, sd_period)``
+    (the tests run it on the float64 CPU evaluation)"""
+    gp = as_f64(gp)
+    tau, gamma, period = (as_f64(np.atleast_1d(as_f64(v))) for v in (tau, gamma, period))
+    c = tau.shape[0]
+    f_t, f_m, f_p = _qp_free(tau, gamma, free)
+    mask = np.concatenate([np.ones(2 * c, dtype=bool), f_t, f_m, f_p])
+    cov_log, sd = _laplace_from_fisher_blocks(F, np.concatenate([gp, tau, gamma, period]), mask, "quasiperiodic_laplace")
+    return cov_log, sd[:2 * c], sd[2 * c:3 * c], sd[3 * c:4 * c], sd[4 * c:]
+
+
+def quasiperiodic_laplace(lwls, fl, sigma, gp, tau, gamma, period, times, free=None):
+    """The Laplace covariance of an ``optimize_GP_quasiperiodic`` fit at ``(gp, tau, gamma, period)``, in the parameters
+    ``_fit_quasiperiodic`` fits in, ``(log gp, log tau[free], log gamma[free], log period[free])``: ``F_log = diag(theta) F
+    diag(theta)`` of ``fisher_information_quasiperiodic`` restricted to the free parameters, inverted.  ``free`` is that
+    function's dictionary with its defaults.  Returns ``(cov_log, sd_gp (2c,), sd_tau (c,), sd_gamma (c,), sd_period (c,))``:
+    the covariance, and the standard deviations in the parameters' own units, ``nan`` where a parameter is not free.
+    ``LinAlgError`` where ``F_log`` is singular -- a free period of a component with ``gamma = 0``, or the NaN of degenerate
+    input."""
+    return _qp_laplace_from_fisher(fisher_information_quasiperiodic(lwls, fl, sigma, gp, tau, gamma, period, times), gp, tau,
+                                   gamma, period, free)
+
+
+def loo_quasiperiodic(lwls, fl, sigma, gp, tau, gamma, period, times, mu_GP=1.0, epoch_index=None):
+    """``loo_timevar`` under the quasi-periodic kernel of ``lnlike_quasiperiodic`` (``ChunkHandle.loo_qp``): the
+    ``chunk.LooResult`` of the model ``optimize_GP_quasiperiodic`` fits.  Degenerate input follows ``loo_timevar`` and
+    ``lnlike_quasiperiodic``: ``lnp = -inf`` and NaN before any work."""
+    from .chunk import LooResult
+    lw, gp, tau, gamma, period, t, degenerate = _quasiperiodic_front(lwls, gp, tau, gamma, period, times)
+    N = lw.shape[1]
+    ep = None if epoch_index is None else np.asarray(epoch_index, dtype=np.int64)
+    if ep is not None and (ep.shape != lw.shape[1:] or (ep.size and ep.min() < 0)):
+        raise ValueError("epoch_index must hold one non-negative epoch per pixel")
+    if degenerate:
+        return LooResult.degenerate(N, None if ep is None else np.bincount(ep))
+    _quasiperiodic_input(lw, sigma, gp)
+    h = _quasiperiodic_handle(fl, sigma, t, "loo_quasiperiodic")
+    res = h.loo_qp(lw, gp, tau, gamma, period, mu_GP, ep)
+    if not np.isneginf(res.lnp) and not (np.all(np.isfinite(np.asarray(fl, dtype=np.float64))) and np.isfinite(mu_GP)):
+        raise ValueError(_NONFINITE)
+    return res
+
+
+def _periodicity_tangents(c, free_tau, k):
+    """The ``2c + n_free + 1`` tangents of ``periodicity_score``: unit directions of ``gp``, of every free ``tau`` and, last,
+    of ``Gamma`` of component ``k`` -> ``(tan_gp, tan_tau, tan_gamma)``"""
+    f = np.flatnonzero(free_tau)
+    T = 2 * c + f.shape[0] + 1
+    tan_gp, tan_tau, tan_gamma = np.zeros((T, 2 * c)), np.zeros((T, c)), np.zeros((T, c))
+    tan_gp[:2 * c] = np.eye(2 * c)
+    tan_tau[2 * c + np.arange(f.shape[0]), f] = 1.0
+    tan_gamma[T - 1, k] = 1.0
+    return tan_gp, tan_tau, tan_gamma
+
+
+def _periodicity_from_fisher(S, F):
+    """The algebra of ``periodicity_score``: the score ``S`` of ``Gamma`` and the information ``F`` over (the nuisance
+    parameters, ``Gamma``), ``Gamma`` last -> ``(z, S, I)`` with the efficient information ``I = F_GG - F_Gt F_tt^-1 F_tG`` and
+    ``z = S / sqrt(I)``.  ``LinAlgError`` where ``F_tt`` is singular.  (Nothing here knows the device.)"""
+    F = as_f64(F)
+    n = F.shape[0] - 1
+    if not np.all(np.isfinite(F)):
+        raise np.linalg.LinAlgError("periodicity_score: the Fisher information is not finite")
+    # (scaled to a unit diagonal: the parameters' units differ by many decades)
+    d = 1.0 / np.sqrt(np.diag(F)[:n])
+    L = np.linalg.cholesky(d[:, None] * F[:n, :n] * d[None, :])
+    v = np.linalg.solve(L, d * F[:n, n])
+    I = float(F[n, n] - v @ v)
+    return float(S) / np.sqrt(I), float(S), I
+
+
+def periodicity_score(lwls, fl, sigma, gp, tau, times, period, component=0, free_tau=None, mu_GP=1.0):
+    """The score test for a periodic factor of ``component`` at the trial ``period``, evaluated at ``Gamma = 0`` on the
+    time-variable fit ``(gp, tau)``: ``S = d lnp / d Gamma`` of that component (one ``lnlike_qp_grad`` call) and the Fisher
+    information over ``(gp, tau[free], Gamma_component)`` (one ``fisher_qp`` call with ``2c + n_free + 1`` tangents), from
+    which the efficient information ``I = F_GG - F_Gt F_tt^-1 F_tG`` discounts what a re-fit of ``(gp, tau)`` would absorb.
+    -> ``(z, S, I)``, ``z = S / sqrt(I)``: asymptotically standard normal where ``(gp, tau)`` is the time-variable fit, and the
+    test is one-sided (``Gamma >= 0``): a large positive ``z`` speaks for the period.  ``free_tau`` (c,) defaults to every
+    finite ``tau``.  The period is no nuisance direction: at ``Gamma = 0`` its row of ``F`` is exactly zero.  Degenerate
+    input follows ``lnlike_quasiperiodic`` and gives ``(nan, nan, nan)``."""
+    c = np.atleast_2d(lwls).shape[0]
+    k = int(component)
+    if not 0 <= k < c:
+        raise ValueError(f"component must be in [0, {c})")
+    per = np.ones(c)      # (the period of a component at Gamma = 0 does not enter: any)
+    per[k] = float(period)
+    zero = np.zeros(c)
+    lw, gp, tau, gamma, per, t, degenerate = _quasiperiodic_front(lwls, gp, tau, zero, per, times)
+    free = np.isfinite(tau) if free_tau is None else np.asarray(free_tau, dtype=bool).reshape(c)
+    if degenerate:
+        return np.nan, np.nan, np.nan
+    _quasiperiodic_input(lw, sigma, gp)
+    if not (np.all(np.isfinite(np.asarray(fl, dtype=np.float64))) and np.isfinite(mu_GP)):
+        raise ValueError(_NONFINITE)
+    h = _quasiperiodic_handle(fl, sigma, t, "periodicity_score")
+    S = h.lnlike_qp_grad(lw, gp, tau, gamma, per, mu_GP)[3][k]
+    tan_gp, tan_tau, tan_gamma = _periodicity_tangents(c, free, k)
+    F = h.fisher_qp(lw, gp, tau, gamma, per, tan_gp, tan_tau, tan_gamma)
+    return _periodicity_from_fisher(S, F)
+
+
 # ---- calibration (SURVEY.md 8(f) f-4) ---------------------------------------------------------------
 _CAL_FAIL = {1: "reference-epoch covariance B", 2: "conditional covariance C'", 3: "Chebyshev normal equations"}
 

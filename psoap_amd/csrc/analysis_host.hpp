@@ -16,6 +16,12 @@ struct QpArgs {
     double *grad_gamma, *grad_period;
 };
 
+// ... and of fisher_run: Gamma and P (c), and the tangents' parts in them (T, c; nullptr: zeros)
+struct QpFisherArgs {
+    const double *gamma, *period;
+    const double *tan_gamma, *tan_period;
+};
+
 static int grad_run(psoap_chunk* h, bool marg, int B, int c, const double* lwl, int model, const double* p_orb,
                     const double* gp, const double* tau, double mu_GP, double* lnp, double* parts, double* grad_gp,
                     double* grad_tau, double* grad_lwl, double* grad_mu, double* grad_orb, double* grad_vel, bool contract,
@@ -163,9 +169,12 @@ static int inverse_bracket(psoap_chunk* h, hipStream_t s, const Factored& fac, F
 // With `tau` (c, as grad_run's; also with `marg`) K is the time-variable kernel over the handle's times and a tangent has a
 // time-scale part, tan_tau (T, c; nullptr: zeros): the TV fill, tangent fill, contraction and finishing sums, and the dot
 // with its time-scale terms.  The caller has made the checks of fisher_tv_check (with `marg`: of marg_tv_check).
+// With `qp` (plain, with `tau`; the checks of fisher_qp_check) K is the quasi-periodic kernel: Gamma and P go up beside tau, a
+// tangent has a Gamma and a period part as well, and the QP fill, tangent fill, contraction, finishing sums and dot run in the
+// places of the time-variable ones.  With `qp` null the launches are those of the call without it.
 static int fisher_run(psoap_chunk* h, const char* who, bool marg, int c, const double* lwl, const double* gp, const double* tau,
                       int T, const double* tan_lwl, const double* tan_gp, const double* tan_tau, double* fisher,
-                      double* fisher_mu)
+                      double* fisher_mu, const QpFisherArgs* qp = nullptr)
 {
     const bool tv = tau != nullptr;
     if (!h || !lwl || !gp || !tan_gp || !fisher) FAIL(std::string(who) + ": bad arguments");
@@ -175,7 +184,7 @@ static int fisher_run(psoap_chunk* h, const char* who, bool marg, int c, const d
     DEVICE_SCOPE(h->device);
     if (int rc = enter_device(h->device)) return rc;
     hipStream_t s = h->streams[0];
-    const Factored fac = factored(h, marg, 1, tv);
+    const Factored fac = factored(h, marg, 1, tv, qp != nullptr);
     const int N = h->N, Npad = h->Npad, P = h->P, ld = fac.ld, ntiles = P * (P + 1) / 2;
     const size_t sq = (size_t)Npad * Npad, CN = (size_t)c * N;
     if (!h->fws) h->fws.reset(new FisherWs());
@@ -188,12 +197,16 @@ static int fisher_run(psoap_chunk* h, const char* who, bool marg, int c, const d
     HIP_TRY(f.Z.need(sq));
     HIP_TRY(f.TanX.need((size_t)T * CN));
     HIP_TRY(f.TanGp.need((size_t)T * 2 * c));
-    HIP_TRY(f.Part.need((size_t)ntiles * (tv ? GradTile<true>::DOUBLES : GradTile<false>::DOUBLES)));
+    HIP_TRY(f.Part.need(qp ? fisher_qp_sizes(c, N, P, T, QpTile::DOUBLES).part
+                           : (size_t)ntiles * (tv ? GradTile<true>::DOUBLES : GradTile<false>::DOUBLES)));
     HIP_TRY(f.GGp.need((size_t)T * 2 * c));
     if (tv) {
         HIP_TRY(f.TanTau.need((size_t)T * c));
         HIP_TRY(f.GTau.need((size_t)T * c));
     }
+    if (qp)
+        for (Grow<double>* g : {&f.TanGamma, &f.TanPeriod, &f.GGamma, &f.GPeriod})
+            HIP_TRY(g->need(fisher_qp_sizes(c, N, P, T, QpTile::DOUBLES).temporal));
     HIP_TRY(f.GX.need((size_t)T * CN));
     HIP_TRY(f.Y.need(Npad));
     HIP_TRY(f.Mu.need(2));
@@ -207,6 +220,15 @@ static int fisher_run(psoap_chunk* h, const char* who, bool marg, int c, const d
         HIP_TRY(hipMemcpyAsync(w.Tau, tau, sizeof(double) * c, hipMemcpyHostToDevice, s));
         if (tan_tau) HIP_TRY(hipMemcpyAsync(f.TanTau, tan_tau, sizeof(double) * (size_t)T * c, hipMemcpyHostToDevice, s));
         else HIP_TRY(hipMemsetAsync(f.TanTau, 0, sizeof(double) * (size_t)T * c, s));
+    }
+    if (qp) {
+        HIP_TRY(hipMemcpyAsync(w.Gamma, qp->gamma, sizeof(double) * c, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(w.Period, qp->period, sizeof(double) * c, hipMemcpyHostToDevice, s));
+        const std::pair<Grow<double>*, const double*> parts[] = {{&f.TanGamma, qp->tan_gamma}, {&f.TanPeriod, qp->tan_period}};
+        for (const auto& [dst, src] : parts) {
+            if (src) HIP_TRY(hipMemcpyAsync(dst->p, src, sizeof(double) * (size_t)T * c, hipMemcpyHostToDevice, s));
+            else HIP_TRY(hipMemsetAsync(dst->p, 0, sizeof(double) * (size_t)T * c, s));
+        }
     }
     // (F does not depend on the data: any mu_GP)
     if (int rc = factor_group(h, fac, s, 1, c, 0.0, false)) return rc;
@@ -228,6 +250,15 @@ static int fisher_run(psoap_chunk* h, const char* who, bool marg, int c, const d
         const double* tan_tau_t = tv ? f.TanTau.p + (size_t)t * c : nullptr;
         if (int rc = prof_launch(h, s, PSOAP_K_FILL, 0.0, 8.0 * (double)sq, [&] {
                 with_components(c, [&](auto nc) {
+                    if (qp) {
+                        hipLaunchKernelGGL(k_qp_fisher_tangent_fill<nc()>, dim3(P * P), dim3(256), 0, s, f.Kt.p, Npad, N, P,
+                                           (const double*)w.Lwl.p, times, (const double*)w.Gp.p, dtau, (const double*)w.Gamma.p,
+                                           (const double*)w.Period.p, (const double*)(f.TanX.p + (size_t)t * CN),
+                                           (const double*)(f.TanGp.p + (size_t)t * 2 * c), tan_tau_t,
+                                           (const double*)(f.TanGamma.p + (size_t)t * c),
+                                           (const double*)(f.TanPeriod.p + (size_t)t * c));
+                        return;
+                    }
                     hipLaunchKernelGGL(tv ? k_tv_fisher_tangent_fill<nc()> : k_fisher_tangent_fill<nc()>, dim3(P * P), dim3(256),
                                        0, s, f.Kt.p, Npad, N, P, (const double*)w.Lwl.p, times, (const double*)w.Gp.p, dtau,
                                        (const double*)(f.TanX.p + (size_t)t * CN),
@@ -238,6 +269,13 @@ static int fisher_run(psoap_chunk* h, const char* who, bool marg, int c, const d
                 hipLaunchKernelGGL(k_fisher_gemm, dim3(P * P), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)f.Kt.p,
                                    (const double*)f.Kinv.p, Npad, P, f.Z.p);
                 with_components(c, [&](auto nc) {
+                    if (qp) {
+                        hipLaunchKernelGGL(k_qp_fisher_contract<nc()>, dim3(ntiles), dim3(GEMM_THREADS), GEMM_LDS_BYTES, s,
+                                           (const double*)f.Kinv.p, (const double*)f.Z.p, N, Npad, P, (const double*)w.Lwl.p, times,
+                                           (const double*)w.Gp.p, dtau, (const double*)w.Gamma.p, (const double*)w.Period.p,
+                                           f.Part.p);
+                        return;
+                    }
                     hipLaunchKernelGGL(tv ? k_tv_fisher_contract<nc()> : k_fisher_contract<nc()>, dim3(ntiles),
                                        dim3(GEMM_THREADS), GEMM_LDS_BYTES, s, (const double*)f.Kinv.p, (const double*)f.Z.p, N,
                                        Npad, P, (const double*)w.Lwl.p, times, (const double*)w.Gp.p, dtau, f.Part.p);
@@ -245,7 +283,13 @@ static int fisher_run(psoap_chunk* h, const char* who, bool marg, int c, const d
             })) return rc;
         // the gradient's finishing sums as they are: its alpha is W 1 here, and its sum over alpha goes nowhere (Mu[1])
         if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
-                if (tv)
+                if (qp)
+                    hipLaunchKernelGGL(k_qp_grad_finish, dim3(P + 1, 1), dim3(128), 0, s, (const double*)f.Part.p,
+                                       (const double*)f.Y.p, (const double*)w.Gp.p, dtau, (const double*)w.Gamma.p,
+                                       (const double*)w.Period.p, c, N, Npad, P, f.GGp.p + (size_t)t * 2 * c,
+                                       f.GTau.p + (size_t)t * c, f.GGamma.p + (size_t)t * c, f.GPeriod.p + (size_t)t * c,
+                                       f.GX.p + (size_t)t * CN, f.Mu.p + 1);
+                else if (tv)
                     hipLaunchKernelGGL(k_tv_grad_finish, dim3(P + 1, 1), dim3(128), 0, s, (const double*)f.Part.p,
                                        (const double*)f.Y.p, (const double*)w.Gp.p, dtau, c, N, Npad, P,
                                        f.GGp.p + (size_t)t * 2 * c, f.GTau.p + (size_t)t * c, f.GX.p + (size_t)t * CN, f.Mu.p + 1);
@@ -257,6 +301,13 @@ static int fisher_run(psoap_chunk* h, const char* who, bool marg, int c, const d
     }
     // (static: no time-scale terms in the dot)
     if (int rc = prof_launch(h, s, PSOAP_K_MISC, 0.0, 0.0, [&] {
+            if (qp) {
+                hipLaunchKernelGGL(k_qp_fisher_dot, dim3(T, T), dim3(256), 0, s, (const double*)f.TanX.p, (const double*)f.TanGp.p,
+                                   (const double*)f.TanTau.p, (const double*)f.TanGamma.p, (const double*)f.TanPeriod.p,
+                                   (const double*)f.GX.p, (const double*)f.GGp.p, (const double*)f.GTau.p,
+                                   (const double*)f.GGamma.p, (const double*)f.GPeriod.p, c, N, T, f.F.p);
+                return;
+            }
             hipLaunchKernelGGL(k_fisher_dot, dim3(T, T), dim3(256), 0, s, (const double*)f.TanX.p, (const double*)f.TanGp.p,
                                (const double*)(tv ? f.TanTau.p : nullptr), (const double*)f.GX.p, (const double*)f.GGp.p,
                                (const double*)(tv ? f.GTau.p : nullptr), c, N, T, f.F.p);
@@ -269,9 +320,10 @@ static int fisher_run(psoap_chunk* h, const char* who, bool marg, int c, const d
     HIP_TRY(hipMemcpyAsync(&info, f.Info, sizeof info, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     if (collect_timings(h)) return 1;
-    // the conventions of the likelihood: a negative hyper-parameter, a tau that is no time scale or a matrix that is not
-    // positive definite -> no information
-    if (info.info != 0.0 || value == -INFINITY || proposal_refused(gp, c, 0) || (tv && tau_refused(tau, c, 0))) {
+    // the conventions of the likelihood: a negative hyper-parameter, a tau that is no time scale, a Gamma or P that is none
+    // (qp_refused) or a matrix that is not positive definite -> no information
+    if (info.info != 0.0 || value == -INFINITY || proposal_refused(gp, c, 0) || (tv && tau_refused(tau, c, 0)) ||
+        (qp && qp_refused(qp->gamma, qp->period, c, 0))) {
         fill_nan(fisher, 0, (size_t)T * T);
         fill_nan(fisher_mu, 0, 1);
     }
@@ -436,10 +488,12 @@ static int info_vel_run(psoap_chunk* h, bool marg, int c, const double* lwl, con
 // `marg`: under Kt = K + Ht Ht^T (marg_fisher_kernels.hpp) -- the factorisation, the value and alpha_m are the marginal
 // gradient's for one matrix and k_marg_loo_band scatters the band of Kt^-1 where k_loo_band scatters that of K^-1.
 // With `tau` (c; plain only, as grad_run's) K is the time-variable kernel over the handle's times: the factorisation alone
-// knows -- everything behind it reads K through W and alpha.
+// knows -- everything behind it reads K through W and alpha.  With `qp` (its gamma and period, c; plain, with `tau`) it is the
+// quasi-periodic kernel, and again the factorisation alone knows; with `qp` null the launches are those of the call without it.
 static int loo_run(psoap_chunk* h, const char* who, bool marg, int c, const double* lwl, const double* gp, const double* tau,
                    double mu_GP, const int32_t* epoch, int n_epochs, double* lnp, double* loo_logp, double* pix_mean, double* pix_var,
-                   double* pix_logp, double* ep_resid, double* ep_chi2, double* ep_logp, int32_t* ep_npix)
+                   double* pix_logp, double* ep_resid, double* ep_chi2, double* ep_logp, int32_t* ep_npix,
+                   const QpArgs* qp = nullptr)
 {
     if (!h || !lwl || !gp) FAIL(std::string(who) + ": bad arguments");
     if (c < 1 || c > 3) FAIL("number of components must be 1, 2 or 3");
@@ -453,7 +507,7 @@ static int loo_run(psoap_chunk* h, const char* who, bool marg, int c, const doub
     DEVICE_SCOPE(h->device);
     if (int rc = enter_device(h->device)) return rc;
     const bool tv = tau != nullptr;
-    const Factored fac = factored(h, marg, 1, tv);
+    const Factored fac = factored(h, marg, 1, tv, qp != nullptr);
     hipStream_t s = h->streams[0];
     if (!h->lws) h->lws.reset(new LooWs());
     if (int rc = factored_ws_need(h, fac, s, true, false)) return rc;
@@ -476,6 +530,10 @@ static int loo_run(psoap_chunk* h, const char* who, bool marg, int c, const doub
     HIP_TRY(l.EpBlock.need(lay.epoch_block.size()));
     if (int rc = single_front(h, s, c, lwl, gp)) return rc;
     if (tv) HIP_TRY(hipMemcpyAsync(w.Tau, tau, sizeof(double) * c, hipMemcpyHostToDevice, s));
+    if (qp) {
+        HIP_TRY(hipMemcpyAsync(w.Gamma, qp->gamma, sizeof(double) * c, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(w.Period, qp->period, sizeof(double) * c, hipMemcpyHostToDevice, s));
+    }
     HIP_TRY(hipMemcpyAsync(l.Blocks, lay.blocks.data(), sizeof(LooBlock) * (size_t)nblk, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(l.Tiles, lay.tiles.data(), sizeof(LooTile) * (size_t)ntile, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(l.PixBlock, lay.pixel_block.data(), sizeof(int) * (size_t)N, hipMemcpyHostToDevice, s));
@@ -533,9 +591,10 @@ static int loo_run(psoap_chunk* h, const char* who, bool marg, int c, const doub
     if (ep_npix) HIP_TRY(hipMemcpyAsync(ep_npix, l.EpNpix, sizeof(int32_t) * (size_t)ne, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));       // (the layout's vectors and the caller's pageable arrays)
     if (collect_timings(h)) return 1;
-    // the conventions: a negative hyper-parameter, a tau that is no time scale or a matrix that is not positive definite ->
-    // -inf, and nothing else to say
-    if (proposal_refused(gp, c, 0) || (tv && tau_refused(tau, c, 0))) value = -INFINITY;
+    // the conventions: a negative hyper-parameter, a tau that is no time scale, a Gamma or P that is none (qp_refused) or a
+    // matrix that is not positive definite -> -inf, and nothing else to say
+    if (proposal_refused(gp, c, 0) || (tv && tau_refused(tau, c, 0)) || (qp && qp_refused(qp->gamma, qp->period, c, 0)))
+        value = -INFINITY;
     if (lnp) *lnp = value;
     if (value == -INFINITY) {
         fill_nan(loo_logp, 0, 1);

@@ -57,6 +57,21 @@
 // sums; k_tv_grad_finish gives g_t[tau_c] = (1/2 a^2 / inf) * st = 0; and the dot adds the tau terms AFTER the static ones,
 // r + 0 = r.  So with every tau = inf the entries of F have the bits of psoap_chunk_fisher whatever tan_tau holds, and a
 // tangent with nothing but dtau gives K_t = 0 and an exactly-zero row and column.
+//
+// Under the quasi-periodic kernel (psoap_chunk_fisher_qp), e_cij = exp(p_c d^2 + q_c dt^2 - Gamma_c s^2) with
+// s, co = sincospi(dt / P_c), a tangent is t = (dx_t, da_tc, dl_tc, dtau_tc, dGamma_tc, dP_tc) and K_t gains
+//   e_cmn (-a_c^2 s^2 dGamma_tc + a_c^2 Gamma_c pi / P_c^2 dt (2 s co) dP_tc)
+// The launch sequence is the time-variable one on [K | I] factored under the quasi-periodic fill (Factored::qp):
+//   k_qp_fisher_tangent_fill<C>  the time-variable tangent fill with the periodic term in the argument and two coefficients more
+//   k_qp_fisher_contract<C>      the two K loops, then qp_contract_epilogue<C, ContractQ::Fisher> (grad_kernels.hpp): a QpTile
+//                                record with the five hyper sums per component
+//   k_qp_grad_finish             (the quasi-periodic gradient's, as it is) leaves g_t[Gamma_c] and g_t[P_c] beside the rest
+//   k_qp_fisher_dot              k_fisher_dot's sums in its order, then the c Gamma terms, then the c period terms
+// Gamma_c = 0 for every c with dGamma = 0 is the time-variable call, bit for bit, whatever P and dP are: ng = -0 leaves the
+// argument as it is, cg = -a^2 0 and cq = a^2 0 pi / P^2 dP are zeros added behind the time-variable sum, the contraction's sa,
+// sl, st and row and column sums are formed by the time-variable operations on the same e, k_qp_grad_finish gives
+// g_t[P_c] = 0, and the dot's last 2c steps add exact zeros.  A tangent with nothing but dP_c of a component with Gamma_c = 0
+// gives K_t = 0 and an exactly-zero row and column.
 #pragma once
 #include "grad_kernels.hpp"
 
@@ -101,13 +116,22 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void k_fisher_kinv(const double* _
 // K_t, every tile (grid P P), in the layout of k_fill_sym: wave w owns the 32-column block w, a lane four rows x two columns
 // per step, the eight exponentials of a component through one batched, underflow-skipping evaluation.  TV: the row times in
 // LDS beside xrow / drow, two column times per lane, the fourth coefficient ct[c] = a_c^2 / tau_c^3 dtau_tc.
-template <int C, bool TV>
+// QP (with TV): the periodic term in the argument as k_fill_sym_qp forms it -- u = dt * rP, sincospi, a = a + ng * s * s, the
+// underflow shortcut on the two-term argument first and then on the full one -- and two more coefficients,
+// cg[c] = -a_c^2 dGamma_tc of e s^2 and cq[c] = a_c^2 Gamma_c pi / P_c^2 dP_tc of e dt (2 s co).  s^2 and 2 s co of the eight
+// elements are kept across the exp: this kernel holds no accumulator tile.
+template <int C, bool TV, bool QP = false>
 __device__ __forceinline__ void fisher_tangent_fill_tile(double* __restrict__ Kt, int Npad, int N, int P,
                                                          const double* __restrict__ lwl, const double* __restrict__ times,
                                                          const double* __restrict__ gp, const double* __restrict__ tau,
                                                          const double* __restrict__ tan_x, const double* __restrict__ tan_gp,
-                                                         const double* __restrict__ tan_tau)
+                                                         const double* __restrict__ tan_tau,
+                                                         const double* __restrict__ gam = nullptr,
+                                                         const double* __restrict__ per = nullptr,
+                                                         const double* __restrict__ tan_gamma = nullptr,
+                                                         const double* __restrict__ tan_period = nullptr)
 {
+    static_assert(TV || !QP, "the periodic factor stands on the temporal one");
     __shared__ double xrow[C][NB];
     __shared__ double drow[C][NB];
     __shared__ double trow[TV ? NB : 1];      // (static: never referenced, and not allocated)
@@ -118,6 +142,7 @@ __device__ __forceinline__ void fisher_tangent_fill_tile(double* __restrict__ Kt
     load_gp(gp, C, g);
     double ca[C], cl[C], cx[C];      // the coefficients of e, e d^2 and e d (dx[n] - dx[m])
     [[maybe_unused]] double q2[C], ct[C];      // TV: q_c and the coefficient of e dt^2
+    [[maybe_unused]] double rP[C], ng[C], cg[C], cq[C];      // QP: 1 / P_c, -Gamma_c and the coefficients of e s^2, e dt (2 s co)
 #pragma unroll
     for (int c = 0; c < C; ++c) {
         const double a = gp[2 * c], l = gp[2 * c + 1];
@@ -128,6 +153,13 @@ __device__ __forceinline__ void fisher_tangent_fill_tile(double* __restrict__ Kt
             const double tc = tau[c];
             q2[c] = tv_q2(tc);
             ct[c] = g.a2[c] / (tc * tc * tc) * tan_tau[c];
+        }
+        if constexpr (QP) {
+            const double G = gam[c], Pc = per[c];
+            rP[c] = qp_rp(Pc);
+            ng[c] = qp_ng(G);
+            cg[c] = -g.a2[c] * tan_gamma[c];
+            cq[c] = g.a2[c] * G * 3.14159265358979323846 / (Pc * Pc) * tan_period[c];
         }
     }
     if (tid < NB) {
@@ -184,6 +216,22 @@ __device__ __forceinline__ void fisher_tangent_fill_tile(double* __restrict__ Kt
                 live = live || !(a[2 * s4] <= -746.0) || !(a[2 * s4 + 1] <= -746.0);
             }
             if (__builtin_amdgcn_ballot_w64(live) == 0ull) continue;      // exp() = +0 for the whole wave
+            [[maybe_unused]] double s2[8], sc[8];      // QP: s^2 and 2 s co of the element
+            if constexpr (QP) {
+                live = false;
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+#pragma clang fp contract(off)
+                    const double u = ((k & 1) ? dtb[k >> 1] : dta[k >> 1]) * rP[c];
+                    double s, co;
+                    sincospi(u, &s, &co);
+                    a[k] = a[k] + ng[c] * s * s;
+                    live = live || !(a[k] <= -746.0);
+                    s2[k] = s * s;
+                    sc[k] = 2.0 * s * co;
+                }
+                if (__builtin_amdgcn_ballot_w64(live) == 0ull) continue;
+            }
             exp_nonpos_batch<8>(a, e);
 #pragma unroll
             for (int s4 = 0; s4 < 4; ++s4) {
@@ -198,6 +246,15 @@ __device__ __forceinline__ void fisher_tangent_fill_tile(double* __restrict__ Kt
                     asm volatile("" : "+v"(sa), "+v"(sb));
                     sa = sa + ct[c] * (dta[s4] * dta[s4]);
                     sb = sb + ct[c] * (dtb[s4] * dtb[s4]);
+                }
+                if constexpr (QP) {
+                    // the time-variable sum first, the periodic terms last, behind an opaque statement of their own: with
+                    // Gamma_c = 0 and dGamma_tc = 0 both add exact zeros, whatever P_c and dP_tc are
+                    asm volatile("" : "+v"(sa), "+v"(sb));
+                    sa = sa + cg[c] * s2[2 * s4];
+                    sb = sb + cg[c] * s2[2 * s4 + 1];
+                    sa = sa + cq[c] * (dta[s4] * sc[2 * s4]);
+                    sb = sb + cq[c] * (dtb[s4] * sc[2 * s4 + 1]);
                 }
                 va[s4] += e[2 * s4] * sa;
                 vb[s4] += e[2 * s4 + 1] * sb;
@@ -235,6 +292,22 @@ __global__ __launch_bounds__(256) void k_tv_fisher_tangent_fill(double* __restri
                                                                 const double* __restrict__ tan_tau)
 {
     fisher_tangent_fill_tile<C, true>(Kt, Npad, N, P, lwl, times, gp, tau, tan_x, tan_gp, tan_tau);
+}
+
+// ... under the quasi-periodic kernel (psoap_chunk_fisher_qp): gam, per (c) and the tangent's dGamma, dP (c) behind tan_tau
+template <int C>
+__global__ __launch_bounds__(256) void k_qp_fisher_tangent_fill(double* __restrict__ Kt, int Npad, int N, int P,
+                                                                const double* __restrict__ lwl, const double* __restrict__ times,
+                                                                const double* __restrict__ gp, const double* __restrict__ tau,
+                                                                const double* __restrict__ gam, const double* __restrict__ per,
+                                                                const double* __restrict__ tan_x,
+                                                                const double* __restrict__ tan_gp,
+                                                                const double* __restrict__ tan_tau,
+                                                                const double* __restrict__ tan_gamma,
+                                                                const double* __restrict__ tan_period)
+{
+    fisher_tangent_fill_tile<C, true, true>(Kt, Npad, N, P, lwl, times, gp, tau, tan_x, tan_gp, tan_tau, gam, per, tan_gamma,
+                                            tan_period);
 }
 
 // Z = K_t K^-1: Z[m][n] = sum_k K_t[k][m] K^-1[k][n] (K_t is symmetric, so its block columns are the k-major operand).
@@ -302,6 +375,28 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void k_tv_fisher_contract(const do
     fisher_contract_tile<C, true>(Kinv, Z, N, Npad, P, lwl, times, gp, tau, part);
 }
 
+// The two K loops of fisher_contract_tile, then the quasi-periodic epilogue (qp_contract_epilogue of grad_kernels.hpp with
+// ContractQ::Fisher): e_c with the periodic term, the five hyper sums per component, a QpTile record per tile for
+// k_qp_grad_finish.  grid P (P + 1) / 2
+template <int C>
+__global__ __launch_bounds__(GEMM_THREADS, 2) void k_qp_fisher_contract(const double* __restrict__ Kinv, const double* __restrict__ Z,
+                                                                       int N, int Npad, int P, const double* __restrict__ lwl,
+                                                                       const double* __restrict__ times,
+                                                                       const double* __restrict__ gp,
+                                                                       const double* __restrict__ tau,
+                                                                       const double* __restrict__ gam,
+                                                                       const double* __restrict__ per, double* __restrict__ part)
+{
+    int ti, tj;
+    decode_upper(blockIdx.x, P, ti, tj);
+    Tile t;
+    t.zero();
+    tile_gemm_tn(t, Kinv + NB * ti, (size_t)Npad, Z + NB * tj, (size_t)Npad, Npad, ti == tj);
+    tile_gemm_tn(t, Z + NB * ti, (size_t)Npad, Kinv + NB * tj, (size_t)Npad, Npad, ti == tj);      // (+ its transpose's tile)
+    qp_contract_epilogue<C, ContractQ::Fisher>(t, 0, ti, tj, (int)blockIdx.x, N, Npad, P, lwl, gp, nullptr, part, times, tau, gam,
+                                               per);
+}
+
 // F_mu = 1^T K^-1 1 = |W 1|^2 in two fixed-order stages.  y[k] = sum of row k of W over its columns q <= k, q < N (the rest is
 // exactly zero): thread j adds every 256th term, the 256 sums meet in a tree (block_sum_256).  grid N, 256 threads
 __global__ __launch_bounds__(256) void k_fisher_w1(const double* __restrict__ A, int ld, int Npad, int N, double* __restrict__ y)
@@ -352,6 +447,35 @@ __global__ __launch_bounds__(256) void k_fisher_dot(const double* __restrict__ t
     }
 }
 
+// k_fisher_dot under the quasi-periodic kernel: the same sums in the same order -- the c N grid terms, the 2c hyper-parameter
+// terms, the c time-scale terms -- then the c Gamma terms, then the c period terms.  With tan_gamma = 0 and g_period = 0 (every
+// Gamma_c = 0) the last 2c steps leave r as it is.  grid (T, T), 256 threads
+__global__ __launch_bounds__(256) void k_qp_fisher_dot(const double* __restrict__ tan_x, const double* __restrict__ tan_gp,
+                                                       const double* __restrict__ tan_tau, const double* __restrict__ tan_gamma,
+                                                       const double* __restrict__ tan_period, const double* __restrict__ g_x,
+                                                       const double* __restrict__ g_gp, const double* __restrict__ g_tau,
+                                                       const double* __restrict__ g_gamma, const double* __restrict__ g_period,
+                                                       int C, int N, int T, double* __restrict__ F)
+{
+    __shared__ double red[256];
+    const int s = blockIdx.x, t = blockIdx.y, tid = threadIdx.x;
+    if (s < t) return;
+    const size_t CN = (size_t)C * N;
+    const double* ts = tan_x + (size_t)s * CN;
+    const double* gt = g_x + (size_t)t * CN;
+    double acc = 0.0;
+    for (size_t i = tid; i < CN; i += 256) acc = fma(ts[i], gt[i], acc);
+    double r = block_sum_256(red, acc);
+    if (tid == 0) {
+        for (int k = 0; k < 2 * C; ++k) r = fma(tan_gp[(size_t)s * 2 * C + k], g_gp[(size_t)t * 2 * C + k], r);
+        for (int k = 0; k < C; ++k) r = fma(tan_tau[(size_t)s * C + k], g_tau[(size_t)t * C + k], r);
+        for (int k = 0; k < C; ++k) r = fma(tan_gamma[(size_t)s * C + k], g_gamma[(size_t)t * C + k], r);
+        for (int k = 0; k < C; ++k) r = fma(tan_period[(size_t)s * C + k], g_period[(size_t)t * C + k], r);
+        F[(size_t)s * T + t] = r;
+        F[(size_t)t * T + s] = r;
+    }
+}
+
 // the LDS attribute of every kernel here that takes the operand buffers
 inline hipError_t fisher_configure_kernels()
 {
@@ -359,7 +483,9 @@ inline hipError_t fisher_configure_kernels()
         reinterpret_cast<const void*>(k_fisher_kinv),           reinterpret_cast<const void*>(k_fisher_gemm),
         reinterpret_cast<const void*>(k_fisher_contract<1>),    reinterpret_cast<const void*>(k_fisher_contract<2>),
         reinterpret_cast<const void*>(k_fisher_contract<3>),    reinterpret_cast<const void*>(k_tv_fisher_contract<1>),
-        reinterpret_cast<const void*>(k_tv_fisher_contract<2>), reinterpret_cast<const void*>(k_tv_fisher_contract<3>)};
+        reinterpret_cast<const void*>(k_tv_fisher_contract<2>), reinterpret_cast<const void*>(k_tv_fisher_contract<3>),
+        reinterpret_cast<const void*>(k_qp_fisher_contract<1>), reinterpret_cast<const void*>(k_qp_fisher_contract<2>),
+        reinterpret_cast<const void*>(k_qp_fisher_contract<3>)};
     for (const void* k : kernels)
         if (hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GEMM_LDS_BYTES)) return e;
     return hipSuccess;
@@ -370,6 +496,7 @@ struct FisherWs {
     Grow<double> Kinv, Kt, Z, TanX, TanGp, Part, GGp, GX, Y, Mu, F;
     Grow<double> V;      // Vt 1 of the marginal form (marg_fisher_kernels.hpp)
     Grow<double> TanTau, GTau;      // the time-scale tangents (T, c) and their contractions (fisher_tv)
+    Grow<double> TanGamma, TanPeriod, GGamma, GPeriod;      // those of Gamma and P likewise (fisher_qp)
     Grow<MatAcc> Info;
 };
 

@@ -448,7 +448,10 @@ struct QpTile {
 // that rebuilt the argument), where keeping s^2 and 2 s co of four elements across the exp cost 16 registers; d is the same
 // subtraction again; and the column's abscissa, alpha and time come from LDS where they are used, not once per tile.  With
 // that no instance has a scratch instruction in or ahead of its K loop (profiles/quasiperiodic.md has the forms that had).
-template <int C>
+// Q = ContractQ::Fisher (k_qp_fisher_contract of fisher_kernels.hpp): t is the tile of 2 G_t, q = 1/2 t, alpha is nullptr and no
+// alpha row is staged or read; behind two K loops the thread id passes through an opaque statement in every turn of the
+// component loop, as in grad_contract_epilogue and for its reason.  The gradient's instance keeps its instructions.
+template <int C, ContractQ Q = ContractQ::Gradient>
 __device__ __forceinline__ void qp_contract_epilogue(const Tile& t, int b, int ti, int tj, int tile_index, int N, int Npad,
                                                      int P, const double* __restrict__ lwl, const double* __restrict__ gp,
                                                      const double* __restrict__ alpha, double* __restrict__ part,
@@ -457,22 +460,31 @@ __device__ __forceinline__ void qp_contract_epilogue(const Tile& t, int b, int t
 {
     using L = QpTile;
     constexpr int XS = L::XS, AL = L::AL, TS = L::TS, RS = L::RS, CS = L::CS, HS = L::HS, WS = L::WS;
+    constexpr bool FISHER = Q == ContractQ::Fisher;
     const int tid = threadIdx.x;
-    const int lane = tid & 63, wave = tid >> 6;
-    const int wr = wave >> 1, wc = wave & 1;
+    int lane = tid & 63, wave = tid >> 6;
+    int wr = wave >> 1, wc = wave & 1;
     const double* lw = lwl + (size_t)b * C * N;
     {
         const int side = tid >> 7, idx = tid & 127;
         const int g = NB * (side ? tj : ti) + idx;
 #pragma unroll
         for (int c = 0; c < C; ++c) psoap_smem[XS + (side * 3 + c) * NB + idx] = (g < N) ? lw[(size_t)c * N + g] : 0.0;
-        psoap_smem[AL + side * NB + idx] = alpha[(size_t)b * Npad + g];
+        if constexpr (!FISHER) psoap_smem[AL + side * NB + idx] = alpha[(size_t)b * Npad + g];
         psoap_smem[TS + side * NB + idx] = (g < N) ? times[g] : 0.0;
     }
     __syncthreads();
     const bool diag_tile = ti == tj;
 #pragma unroll 1
     for (int c = 0; c < C; ++c) {
+        if constexpr (FISHER) {
+            int tl = tid;
+            asm volatile("" : "+v"(tl));
+            lane = tl & 63;
+            wave = tl >> 6;
+            wr = wave >> 1;
+            wc = wave & 1;
+        }
         double p2;
         {
 #pragma clang fp contract(off)
@@ -492,12 +504,13 @@ __device__ __forceinline__ void qp_contract_epilogue(const Tile& t, int b, int t
         double sa = 0.0, sl = 0.0, st = 0.0, sg = 0.0, sp = 0.0;
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
-            double xi[4], rowacc[4], ai[4];
+            double xi[4], rowacc[4];
+            [[maybe_unused]] double ai[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int row = tile_row(wr, m, lane, r);
                 xi[r] = psoap_smem[XS + c * NB + row];
-                ai[r] = psoap_smem[AL + row];
+                if constexpr (!FISHER) ai[r] = psoap_smem[AL + row];
                 rowacc[r] = 0.0;
             }
 #pragma unroll
@@ -507,7 +520,9 @@ __device__ __forceinline__ void qp_contract_epilogue(const Tile& t, int b, int t
                 // follow: kept across the tile they are 24 registers the kernel does not have beside the sincospi)
                 int cidx = col;
                 asm volatile("" : "+v"(cidx));
-                const double xjn = psoap_smem[XS + (3 + c) * NB + cidx], ajn = psoap_smem[AL + NB + cidx];
+                const double xjn = psoap_smem[XS + (3 + c) * NB + cidx];
+                [[maybe_unused]] double ajn;
+                if constexpr (!FISHER) ajn = psoap_smem[AL + NB + cidx];
                 const double tcol = psoap_smem[TS + NB + cidx];
                 double a[4], e[4];
                 bool live = false;
@@ -538,7 +553,9 @@ __device__ __forceinline__ void qp_contract_epilogue(const Tile& t, int b, int t
                 for (int r = 0; r < 4; ++r) {
                     const int row = tile_row(wr, m, lane, r);
                     const bool ok = jok[n] && NB * ti + row < N && (!diag_tile || row <= col);
-                    const double qe = ok ? (ai[r] * ajn - t.acc[m][n][r]) * e[r] : 0.0;
+                    double qe;
+                    if constexpr (FISHER) qe = ok ? 0.5 * t.acc[m][n][r] * e[r] : 0.0;
+                    else qe = ok ? (ai[r] * ajn - t.acc[m][n][r]) * e[r] : 0.0;
                     const double w = (diag_tile && row == col) ? 1.0 : 2.0;
                     const double d = xjn - xi[r];
                     const double qed = qe * d;

@@ -2295,6 +2295,22 @@ extern "C" int psoap_chunk_fisher_tv(psoap_chunk* h, int c, const double* lwl, c
     return fisher_run(h, "psoap_chunk_fisher_tv", false, c, lwl, gp, tau, T, tan_lwl, tan_gp, tan_tau, fisher, fisher_mu);
 }
 
+// under the quasi-periodic kernel (k_qp_fisher_tangent_fill, k_qp_fisher_contract, k_qp_fisher_dot); the workspaces are the plain
+// entry's and, for Gamma and P, the gradient's
+static_assert(QpTile::DOUBLES == 6 * 128 + 3 * 5, "the record length tests/host/qp_fisher_host_check.cpp sizes with");
+extern "C" int psoap_chunk_fisher_qp(psoap_chunk* h, int c, const double* lwl, const double* gp, const double* tau,
+                                     const double* gamma, const double* period, int T, const double* tan_lwl,
+                                     const double* tan_gp, const double* tan_tau, const double* tan_gamma,
+                                     const double* tan_period, double* fisher, double* fisher_mu)
+{
+    if (!h) FAIL("psoap_chunk_fisher_qp: bad arguments");
+    if (const char* why = fisher_qp_check(c, T, FISHER_MAX_T, lwl && gp && tau && gamma && period && tan_gp && fisher,
+                                          h->dTimes.p != nullptr, h->stream.open, h->marg.valid))
+        FAIL(std::string("psoap_chunk_fisher_qp: ") + why);
+    const QpFisherArgs qp{gamma, period, tan_gamma, tan_period};
+    return fisher_run(h, "psoap_chunk_fisher_qp", false, c, lwl, gp, tau, T, tan_lwl, tan_gp, tan_tau, fisher, fisher_mu, &qp);
+}
+
 extern "C" int psoap_chunk_fisher_release(psoap_chunk* h)
 {
     return release_ws(h, [&] { h->fws.reset(); });
@@ -2356,6 +2372,21 @@ extern "C" int psoap_chunk_loo_tv(psoap_chunk* h, int c, const double* lwl, cons
         FAIL(std::string("psoap_chunk_loo_tv: ") + why);
     return loo_run(h, "psoap_chunk_loo_tv", false, c, lwl, gp, tau, mu_GP, epoch, n_epochs, lnp, loo_logp, pix_mean, pix_var,
                    pix_logp, ep_resid, ep_chi2, ep_logp, ep_npix);
+}
+
+// under the quasi-periodic kernel: lnp has the bits of psoap_chunk_lnlike_qp_grad
+extern "C" int psoap_chunk_loo_qp(psoap_chunk* h, int c, const double* lwl, const double* gp, const double* tau,
+                                  const double* gamma, const double* period, double mu_GP, const int32_t* epoch, int n_epochs,
+                                  double* lnp, double* loo_logp, double* pix_mean, double* pix_var, double* pix_logp,
+                                  double* ep_resid, double* ep_chi2, double* ep_logp, int32_t* ep_npix)
+{
+    if (!h) FAIL("psoap_chunk_loo_qp: bad arguments");
+    if (const char* why = loo_qp_check(c, lwl && gp && tau && gamma && period, h->dTimes.p != nullptr, h->stream.open,
+                                       h->marg.valid))
+        FAIL(std::string("psoap_chunk_loo_qp: ") + why);
+    const QpArgs qp{gamma, period, nullptr, nullptr};
+    return loo_run(h, "psoap_chunk_loo_qp", false, c, lwl, gp, tau, mu_GP, epoch, n_epochs, lnp, loo_logp, pix_mean, pix_var,
+                   pix_logp, ep_resid, ep_chi2, ep_logp, ep_npix, &qp);
 }
 
 extern "C" int psoap_chunk_loo_release(psoap_chunk* h)

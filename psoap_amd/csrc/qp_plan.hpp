@@ -1,7 +1,8 @@
-// qp_plan.hpp -- the pure-host part of the quasi-periodic kernel's entry (psoap_chunk_lnlike_qp_grad; the QP kernels of
-// fill_kernels.hpp and grad_kernels.hpp): the refusals of a call and the values of Gamma and P that are no proposal.  No HIP
-// call and no HIP header: psoap_gp.hip includes it into the library, and a host compiler builds the same text into a
-// stand-alone, sanitized program (tests/host/qp_host_check.cpp).
+// qp_plan.hpp -- the pure-host part of the quasi-periodic kernel's entries (psoap_chunk_lnlike_qp_grad, psoap_chunk_fisher_qp,
+// psoap_chunk_loo_qp; the QP kernels of fill_kernels.hpp, grad_kernels.hpp and fisher_kernels.hpp): the refusals of a call, the
+// values of Gamma and P that are no proposal, the sizes of the Fisher workspace's additions.  No HIP call and no HIP header:
+// psoap_gp.hip includes it into the library, and a host compiler builds the same text into stand-alone, sanitized programs
+// (tests/host/qp_host_check.cpp, tests/host/qp_fisher_host_check.cpp).
 #pragma once
 #include <math.h>
 #include <stddef.h>
@@ -36,6 +37,43 @@ inline const char* qp_check(const QpCall& a)
         return "the handle has a baseline (psoap_chunk_set_baseline): the quasi-periodic kernel under the marginalised continuum is "
                "not built";
     return nullptr;
+}
+
+// ---- the analysis paths under the quasi-periodic kernel (psoap_chunk_fisher_qp, psoap_chunk_loo_qp) ----------------------------
+// -> nullptr, or why the call is refused, with the arguments, the order and the words of tv_analysis_check and fisher_tv_check
+// (predict_plan.hpp): the arrays (gamma and period among them); c; T within 1 .. max_T (FISHER_MAX_T of fisher_kernels.hpp);
+// times set; no open stream; no baseline.  A tau, Gamma or P that is no proposal is not a refusal: NaN (the leave-one-out:
+// -inf) after the call.  The caller puts the entry's name in front.
+inline const char* loo_qp_check(int c, bool arrays, bool have_times, bool open_stream, bool have_baseline)
+{
+    if (!arrays) return "bad arguments";
+    if (c < 1 || c > 3) return "number of components must be 1, 2 or 3";
+    if (!have_times) return "call psoap_chunk_set_times first";
+    if (open_stream) return "the handle has an open stream (psoap_stream_close first)";
+    if (have_baseline)
+        return "the handle has a baseline (psoap_chunk_set_baseline): the quasi-periodic kernel under the marginalised continuum is "
+               "not built";
+    return nullptr;
+}
+
+inline const char* fisher_qp_check(int c, int T, int max_T, bool arrays, bool have_times, bool open_stream, bool have_baseline)
+{
+    if (!arrays) return "bad arguments";
+    if (c < 1 || c > 3) return "number of components must be 1, 2 or 3";
+    if (T < 1 || T > max_T) return "the number of tangents must be between 1 and 32";
+    return loo_qp_check(c, arrays, have_times, open_stream, have_baseline);
+}
+
+// What psoap_chunk_fisher_qp asks of the Fisher workspace beyond the three Npad^2 matrices, in doubles: the tangents and their
+// contractions ((T, c N) grid parts, (T, 2c) hyper-parameter parts, (T, c) parts of tau, Gamma and P, each twice) and the
+// tiles' records of `tile_doubles` (QpTile::DOUBLES of grad_kernels.hpp) for the P (P + 1) / 2 upper tiles of ONE tangent.
+struct FisherQpSizes {
+    size_t grid, hyper, temporal, part;
+};
+
+inline FisherQpSizes fisher_qp_sizes(int c, int N, int P, int T, int tile_doubles)
+{
+    return FisherQpSizes{(size_t)T * c * N, (size_t)T * 2 * c, (size_t)T * c, (size_t)P * (P + 1) / 2 * tile_doubles};
 }
 
 // Proposal b of gamma, period (B, c) holds a value that is none: Gamma < 0, NaN or inf; P <= 0, NaN or inf, or so small that
